@@ -10,7 +10,7 @@ column-major serpentine path (89 consecutive pairs, 8 turns), SURF (hessian 100,
 BF-L2 2-NN + ratio 0.75 + mode vote (>= 3), incremental ROI (roiRatio 0.2) with direction rotation
 (direction 1, directIncre 1) -- exactly Main.py's settings.  One "step" = registering all 89 pairs.
 
-`value`: tiles already resident in HBM when the timed region starts.  `value_host_resident_tiles`: the same K steps with
+`value`: tiles already resident in HBM when the timed region starts.  `value_host_resident_tiles` (--full): the same K steps with
 the tiles in (pinned) host memory at the start of every step -- uploaded inside the timed region on the engine's copy
 stream, overlapped with the registration of earlier pairs (SURVEY 8d's reading: "tiles decoded and resident in host memory").
 
@@ -20,7 +20,7 @@ tables closes the step ("strong" scaling: total work is fixed).  Prints ONE JSON
 Path memory (round 4): the registrar remembers the accepted directions of the path it registered last and plans the speculative batches of
 the next path of the same length from them (GridRegistrar.path_memory; a prior like a branch predictor's: every attempt is still evaluated,
 results never depend on it).  The warm-up step teaches it the grid's scan pattern, the K timed steps run on it: 3 batches per step instead
-of 13, one primed chain per rank at N > 1.  `value_cold_path` (N = 1) is the same K steps by a registrar without memory -- the
+of 13, one primed chain per rank at N > 1.  `value_cold_path` (N = 1, --full) is the same K steps by a registrar without memory -- the
 configuration of rounds 1-3; --no-path-memory makes it the headline.
 
 The prior of the timed steps is learned on ANOTHER instance of the scan pattern (--prior other, the default since round 5: same geometry,
@@ -38,6 +38,10 @@ by worker processes; --also-fuse prints the mosaic-assembly line of the same res
 the step's all-gather through torch.distributed "nccl" (RCCL) at world size 1.
 --workload dendritic25 (N = 1): the 25 committed pairs of the reference's dendriticCrystal set (tests/golden/real_path_strips.*), a second
 SURF line on real texture.  --from-files (N = 1): the same grid as JPEG files through Stitcher's ingest pipeline, decode inclusive.
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the line; --full adds what the headline does not need (the
+host-resident-tiles and cold-path legs, CPU baselines, rooflines that take runs of their own, the side legs of the other lines: --help).  --dump-outputs DIR writes what the last timed step computed (DIR/*.npy): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -178,6 +182,37 @@ def hbm_roofline(kernel, bytes_per_launch, ms_per_launch, launches, note=None, *
     return d
 
 
+def host_workers():
+    """Host CPUs this process may use: its affinity set, capped by OMP_NUM_THREADS where the host sets it (a share of a shared machine)."""
+    n = len(os.sched_getaffinity(0))
+    cap = int(os.environ.get("OMP_NUM_THREADS") or 0)
+    return max(1, min(n, cap) if cap > 0 else n)
+
+
+def start_synthesis(grid, need, workers):
+    """Tiles `need` of `grid` from a pool of `workers` spawned processes running the grid's own worker code (SyntheticGrid.tiles with
+    processes > 1) -> (pool, iterator).  Unlike that generator, the pool starts working at once: bench.py starts it before torch and
+    the device come up, so that the texture synthesis (the blob layer is interpreter-bound: threads do not scale it) overlaps their
+    start-up.  Tiles are pure functions of (seed, k): the bytes do not depend on the workers."""
+    import multiprocessing as mp
+    from imagestitch_amd import synthetic
+    init = (grid.rows, grid.cols, grid.th, grid.tw, grid.seed, grid.blobs, grid.origins)
+    pool = mp.get_context("spawn").Pool(max(1, min(workers, len(need))), initializer=synthetic._worker_init, initargs=(init,))
+    return pool, pool.imap(synthetic._worker_tile, need, chunksize=1)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64 (the step's outputs are small integer tables: exact)."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        if total > 64 << 20:
+            raise SystemExit("--dump-outputs: outputs over 64 MB, dump a seeded sample instead")
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def optimal_dft_size(n):
     m = max(int(n), 1)
     while True:
@@ -250,22 +285,24 @@ def bench_fuse(args, eng, grid, tiles, handles, torch, close=True):
         assemble(False)
     torch.cuda.synchronize(); eng.sync()
     dt = (time.perf_counter() - t0) / args.steps
-    eng.profile_enable(True); eng.profile_read(reset=True)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        assemble(False)
-    torch.cuda.synchronize(); eng.sync()
-    dt_prof = (time.perf_counter() - t0) / args.steps
-    prof = eng.profile_read(reset=True)
-    eng.profile_enable(False)
-    out = assemble(True)
-    dl = dl_s[0]
-    dt_host = None
-    if not big:
-        t2 = time.perf_counter()
-        out_host = assemble(True, resident=False)
-        dt_host = time.perf_counter() - t2 - dl_s[0]
-        assert np.array_equal(out, out_host)
+    # --full only: the K steps with stage events (stages, roofline), the canvas download and the host-tiles pass checked against it
+    prof, dt_prof, out, dl, dt_host = {}, None, None, None, None
+    if args.full:
+        eng.profile_enable(True); eng.profile_read(reset=True)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            assemble(False)
+        torch.cuda.synchronize(); eng.sync()
+        dt_prof = (time.perf_counter() - t0) / args.steps
+        prof = eng.profile_read(reset=True)
+        eng.profile_enable(False)
+        out = assemble(True)
+        dl = dl_s[0]
+        if not big:
+            t2 = time.perf_counter()
+            out_host = assemble(True, resident=False)
+            dt_host = time.perf_counter() - t2 - dl_s[0]
+            assert np.array_equal(out, out_host)
     mpx = rows * cols / 1e6
     # algorithmic bytes: per fused tile read canvas ROI + read tile ROI + write ROI (3 r c) plus the paste of the
     # tile's pixels outside the ROI (read + write); the validity plane adds r c / 8 -- not counted
@@ -294,16 +331,16 @@ def bench_fuse(args, eng, grid, tiles, handles, torch, close=True):
             roof["traffic_over_algorithmic"] = round(tot / fuse_bytes, 3)
     print(json.dumps({
         "metric": "fuse Mpx/sec (mosaic pixels, fadeInAndFadeOut)", "value": round(mpx / dt, 2), "unit": "Mpx/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "ms_per_step_with_stage_events": round(dt_prof * 1e3, 3),
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "ms_per_step_with_stage_events": round(dt_prof * 1e3, 3) if dt_prof is not None else None,
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "u8", "data": "synthetic",
         "config": {"workload": "synthetic %dx%d grid of %dx%d u8 tiles assembled from the ground-truth offsets, fadeInAndFadeOut, mosaic %dx%d"
                                % (args.rows, args.cols, args.tile, args.tile, rows, cols), "tiles": n, "tiles_resident_in_hbm": True,
-                   "canvas_download_ms": round(dl * 1e3, 1), "canvas_download_is": "the first %d rows" % min(rows, grid.th) if big else "the whole mosaic",
+                   "canvas_download_ms": round(dl * 1e3, 1) if dl is not None else None, "canvas_download_is": "the first %d rows" % min(rows, grid.th) if big else "the whole mosaic",
                    "ms_per_step_with_host_tiles": round(dt_host * 1e3, 1) if dt_host is not None else None},
-        "roofline": roof, "cpu_baseline": (cpu_baseline_fuse(args, grid, tiles, offsetList, rois, offs, rows, cols) if args.cpu_sample > 0 else None),
+        "roofline": roof, "cpu_baseline": (cpu_baseline_fuse(args, grid, tiles, offsetList, rois, offs, rows, cols) if args.full and args.cpu_sample > 0 else None),
         "stages": {k: dict(ms=round(v[0], 3), launches=v[1]) for k, v in prof.items()},
-        "tile_Mpx_per_s": round(n * grid.th * grid.tw / 1e6 / dt, 2), "mosaic_nonzero_fraction": round(float((out > 0).mean()), 4),
+        "tile_Mpx_per_s": round(n * grid.th * grid.tw / 1e6 / dt, 2), "mosaic_nonzero_fraction": round(float((out > 0).mean()), 4) if out is not None else None,
         "mosaic_Mpx_per_s_of_the_fuse_kernels": round(mpx / (f_ms / args.steps * 1e-3), 2) if f_n else None,
         "note": "value = mosaic pixels / wall clock of one assembly INCLUDING the canvas allocation + clear and its release (at configs[4]'s 13.9 GB canvas "
                 "that is most of the step: the fuse kernels themselves take stages.fuse)"}))
@@ -418,8 +455,10 @@ def bench_line_scan(args, eng, torch):
 
         def batched():
             return s._fullImageTable(hs)
-        want = loop(); got = batched()
-        assert all(w[0] for w in want) and [[r[1], r[2]] for r in got] == [w[1] for w in want]
+        got = batched()
+        if args.full:                                       # the pair-by-pair loop is --full only (check + timing)
+            want = loop()
+            assert all(w[0] for w in want) and [[r[1], r[2]] for r in got] == [w[1] for w in want]
         worst = max(max(abs(r[1] - t_[0]), abs(r[2] - t_[1])) for r, t_ in zip(got, truth))
         t_w = time.perf_counter()
         while time.perf_counter() - t_w < MIN_WARM_S:
@@ -431,11 +470,13 @@ def bench_line_scan(args, eng, torch):
         torch.cuda.synchronize(); eng.sync()
         dt = (time.perf_counter() - t0) / args.steps
         prof = eng.profile_read(reset=True); eng.profile_enable(False)
-        loop(); eng.sync(); t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loop()
-        eng.sync()
-        dt_loop = (time.perf_counter() - t0) / args.steps
+        dt_loop = None
+        if args.full:
+            loop(); eng.sync(); t0 = time.perf_counter()
+            for _ in range(args.steps):
+                loop()
+            eng.sync()
+            dt_loop = (time.perf_counter() - t0) / args.steps
     finally:
         isa.Stitcher.direction, isa.Stitcher.directIncre, isa.Stitcher.featureMethod, isa.Stitcher.offsetEvaluate, isa.Stitcher.isEnhance = old
     stages = {k: dict(ms=round(v[0], 3), launches=v[1], ms_per_launch=round(v[0] / max(v[1], 1), 4)) for k, v in prof.items()}
@@ -446,8 +487,9 @@ def bench_line_scan(args, eng, torch):
                                       "SURF(100,4,3,64-d), every tile described once, BF-L2 knn2 ratio 0.75 + mode vote; batched: 16 tiles per launch sequence, 23 matches in one batch",
                           "pairs": P, "parallelism": "pairs1"},
                "max_abs_offset_error_px": int(worst),
-               "pair_by_pair_loop_pairs_per_s": round(P / dt_loop, 3), "pair_by_pair_loop_ms_per_step": round(dt_loop * 1e3, 3),
-               "batched_over_loop": round(dt_loop / dt, 2), "roofline": None, "cpu_baseline": None, "stages": stages})
+               "pair_by_pair_loop_pairs_per_s": round(P / dt_loop, 3) if dt_loop else None,
+               "pair_by_pair_loop_ms_per_step": round(dt_loop * 1e3, 3) if dt_loop else None,
+               "batched_over_loop": round(dt_loop / dt, 2) if dt_loop else None, "roofline": None, "cpu_baseline": None, "stages": stages})
     eng.close()
 
 
@@ -508,49 +550,51 @@ def bench_from_files(args, eng, grid, torch):
             # decode only, same pool size, the decoder the pipeline used: the library's own (libjpeg-turbo into a buffer kept per thread) when
             # every tile of the last step went through vfsms_tile_fill_jpeg, else Pillow (with the block allocator the Stitcher's pool sets)
             native = ist.get("native", 0) == ist.get("tiles", -1)
-            if native:
-                import ctypes, threading
-                tl = threading.local()
+            dt_dec = dt_one = dt_reg = None
+            if args.full:                                   # the decode-only and registration-only legs
+                if native:
+                    import ctypes, threading
+                    tl = threading.local()
 
-                def decode_only(f):
-                    if not hasattr(tl, "buf"):
-                        tl.buf = np.empty(grid.th * grid.tw * 3, np.uint8)
-                    data = open(f, "rb").read()
-                    h_, w_, c_ = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-                    rc = eng.lib.vfsms_jpeg_decode(data, len(data), int(color), tl.buf.ctypes.data_as(ctypes.c_void_p), tl.buf.nbytes,
-                                                   ctypes.byref(h_), ctypes.byref(w_), ctypes.byref(c_))
-                    assert rc == 0 and (h_.value, w_.value) == (grid.th, grid.tw), rc
-            else:
-                def decode_only(f):
-                    ST._decode_once(f, color)
-            with ST._PillowBlocks(color and not native), ThreadPoolExecutor(max_workers=nthreads) as ex:
-                list(ex.map(decode_only, files[:nthreads]))
+                    def decode_only(f):
+                        if not hasattr(tl, "buf"):
+                            tl.buf = np.empty(grid.th * grid.tw * 3, np.uint8)
+                        data = open(f, "rb").read()
+                        h_, w_, c_ = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+                        rc = eng.lib.vfsms_jpeg_decode(data, len(data), int(color), tl.buf.ctypes.data_as(ctypes.c_void_p), tl.buf.nbytes,
+                                                       ctypes.byref(h_), ctypes.byref(w_), ctypes.byref(c_))
+                        assert rc == 0 and (h_.value, w_.value) == (grid.th, grid.tw), rc
+                else:
+                    def decode_only(f):
+                        ST._decode_once(f, color)
+                with ST._PillowBlocks(color and not native), ThreadPoolExecutor(max_workers=nthreads) as ex:
+                    list(ex.map(decode_only, files[:nthreads]))
+                    t0 = time.perf_counter()
+                    list(ex.map(decode_only, files))
+                    dt_dec = time.perf_counter() - t0
                 t0 = time.perf_counter()
-                list(ex.map(decode_only, files))
-                dt_dec = time.perf_counter() - t0
-            t0 = time.perf_counter()
-            decode_only(files[0])
-            dt_one = time.perf_counter() - t0
-            # registration only (tiles resident)
-            from imagestitch_amd.grid import GridRegistrar
-            hs = [eng.tile_upload(ST._imread(f, False)) for f in files]
-            reg = GridRegistrar(eng, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=args.offset_evaluate, directIncre=1,
-                                surfParams=eng.surf_params(), window=48)
-            shapes = [(grid.th, grid.tw)] * grid.n_tiles
-            reg.register(hs, shapes, 1)
-            reg.register(hs, shapes, 1)                       # (the second one runs on the learned scan pattern: arena and clocks settled)
-            eng.sync(); t0 = time.perf_counter()
-            for _ in range(args.steps):
+                decode_only(files[0])
+                dt_one = time.perf_counter() - t0
+                # registration only (tiles resident)
+                from imagestitch_amd.grid import GridRegistrar
+                hs = [eng.tile_upload(ST._imread(f, False)) for f in files]
+                reg = GridRegistrar(eng, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=args.offset_evaluate, directIncre=1,
+                                    surfParams=eng.surf_params(), window=48)
+                shapes = [(grid.th, grid.tw)] * grid.n_tiles
                 reg.register(hs, shapes, 1)
-            eng.sync()
-            dt_reg = (time.perf_counter() - t0) / args.steps
-            for h in hs:
-                eng.tile_free(h)
+                reg.register(hs, shapes, 1)                       # (the second one runs on the learned scan pattern: arena and clocks settled)
+                eng.sync(); t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    reg.register(hs, shapes, 1)
+                eng.sync()
+                dt_reg = (time.perf_counter() - t0) / args.steps
+                for h in hs:
+                    eng.tile_free(h)
         finally:
             (isa.Stitcher.direction, isa.Stitcher.directIncre, isa.Stitcher.roiRatio, isa.Stitcher.featureMethod, isa.Stitcher.offsetEvaluate,
              isa.Stitcher.isColorMode, isa.Stitcher.fuseMethod) = old
     P = grid.n_pairs
-    slower = max(dt_dec, dt_reg)
+    slower = max(dt_dec, dt_reg) if args.full else None
     _jsonline({"metric": "image-pairs/sec, decode inclusive (2048x2048 %s JPEG files, SURF+BF)" % ("colour" if color else "grayscale"), "value": round(P / dt, 3), "unit": "image-pairs/s",
                "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "strong",
                "vs_baseline": None, "dtype": "f32", "data": "synthetic (JPEG quality 90 on local disk, %.0f MB for %d tiles)" % (mb, grid.n_tiles),
@@ -562,10 +606,12 @@ def bench_from_files(args, eng, grid, torch):
                           "decoder": ("libjpeg-turbo inside libvfsms (vfsms_tile_fill_jpeg: pinned staging, no interpreter lock)" if native
                                       else "Pillow (VFSMS_NATIVE_JPEG=0 or no libjpeg.so.8) + %s" % ("vfsms_tile_fill_pair" if color else "vfsms_tile_fill"))},
                "max_abs_offset_error_px": int(worst),
-               "decode_only_ms_per_step": round(dt_dec * 1e3, 2), "decode_only_tiles_per_s": round(grid.n_tiles / dt_dec, 1),
-               "decode_one_tile_one_thread_ms": round(dt_one * 1e3, 2),
-               "registration_only_ms_per_step": round(dt_reg * 1e3, 2), "registration_only_pairs_per_s": round(P / dt_reg, 1),
-               "end_to_end_over_slower_stage": round(dt / slower, 3),
+               "decode_only_ms_per_step": round(dt_dec * 1e3, 2) if args.full else None,
+               "decode_only_tiles_per_s": round(grid.n_tiles / dt_dec, 1) if args.full else None,
+               "decode_one_tile_one_thread_ms": round(dt_one * 1e3, 2) if args.full else None,
+               "registration_only_ms_per_step": round(dt_reg * 1e3, 2) if args.full else None,
+               "registration_only_pairs_per_s": round(P / dt_reg, 1) if args.full else None,
+               "end_to_end_over_slower_stage": round(dt / slower, 3) if args.full else None,
                "ingest_thread_ms_per_tile": (dict(decode=round(ist["decode_s"] / max(ist["tiles"], 1) * 1e3, 2), hand_over=round(ist["fill_s"] / max(ist["tiles"], 1) * 1e3, 2))
                                              if ist.get("tiles") else None),
                "startup_bubble_note": "a path cannot start before its first tiles are decoded: end-to-end >= one tile's decode latency + the registration time",
@@ -783,11 +829,41 @@ def main():
                     "pairs/s = pairs / (slowest rank + gather + assembly).  A projection from one GPU, not a measurement of N.")
     ap.add_argument("--all-tiles-on-every-rank", action="store_true", help="N > 1: keep the whole grid resident on every rank (rounds 1-5); default: a rank "
                     "synthesises, uploads and holds only the tiles of its chunk + one halo tile and re-fetches when the learned work split moves")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need -- grid registration: the "
+                    "host-resident-tiles and cold-path legs, the CPU baseline, the descriptor roofline (a describe run of its own); fuse: the "
+                    "steps with stage events (stages, roofline), the canvas download, the host-tiles pass, the CPU baseline; surf_full: the "
+                    "pair-by-pair loop; --from-files: the decode-only and registration-only legs.  A plain run sets up, warms up, times the "
+                    "steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                    "(float64): pair_table (the int32[P, 6] result table: status, dx, dy, direction, i, votes) and final_direction; "
+                    "the grid registration path (--method surf | orb | phase) only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    grid_path = args.workload == "grid" and not args.from_files and args.method in ("surf", "orb", "phase", "fuse")
+    if args.dump_outputs and not (grid_path and args.method != "fuse"):
+        ap.error("--dump-outputs: the grid registration path (--method surf | orb | phase) only")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    grid = g2 = synth = synth2 = None
+    if grid_path:
+        from imagestitch_amd.grid import GridRegistrar
+        from imagestitch_amd.synthetic import SyntheticGrid
+        grid = SyntheticGrid(args.rows, args.cols, args.tile, overlap=args.overlap)
+        P = grid.n_pairs
+        bounds = GridRegistrar.chunk_bounds(P, world)
+        lo, hi = bounds[rank]
+        shard_local = world > 1 and not args.all_tiles_on_every_rank
+        need = list(range(grid.n_tiles)) if (world > 1 and not shard_local) else (list(range(lo, hi + 1)) if hi > lo else [])
+        prior_other = args.prior == "other" and not args.no_path_memory and args.method in ("surf", "orb", "phase") and bool(need)
+        if prior_other:
+            g2 = SyntheticGrid(args.rows, args.cols, args.tile, overlap=args.overlap, seed=grid.seed + 1)
+        if grid.n_tiles <= 128 and need:
+            w = max(1, host_workers() // world)             # (both grids are needed before the warm-up: the workers are shared)
+            synth = start_synthesis(grid, need, w if g2 is None else max(1, w // 2))
+            synth2 = start_synthesis(g2, need, max(1, w - w // 2)) if g2 is not None else None
     import torch
     dist = None
     # VFSMS_DIST_BACKEND=gloo: rehearsal of the N > 1 code path on a box with fewer GPUs than ranks (ranks share devices, the
@@ -819,7 +895,6 @@ def main():
             assert torch.cuda.device_count() >= world, "%d visible GPUs for %d ranks" % (torch.cuda.device_count(), world)
 
     import imagestitch_amd as isa
-    from imagestitch_amd.grid import GridRegistrar
     from imagestitch_amd.distributed import make_all_gather, single_process_all_gather
     from imagestitch_amd.synthetic import SyntheticGrid
 
@@ -828,29 +903,25 @@ def main():
         return bench_dendritic25(args, eng, torch)
     if args.method == "surf_full":
         return bench_line_scan(args, eng, torch)
-    grid = SyntheticGrid(args.rows, args.cols, args.tile, overlap=args.overlap)
     if args.from_files:
-        return bench_from_files(args, eng, grid, torch)
-    P = grid.n_pairs
+        return bench_from_files(args, eng, SyntheticGrid(args.rows, args.cols, args.tile, overlap=args.overlap), torch)
     truth = np.array(grid.true_offsets(), np.int64)
     # Path memory (GridRegistrar.path_memory): the accepted directions of the previous registration of this scan pattern -- the warm-up
     # step -- are the speculation prior of the timed steps (batches planned over the whole predicted path from the first pair on; with
     # N > 1 one primed chain per rank instead of four blind ones, chunks cut by the predicted attempts).  Nothing comes from the ground
     # truth, every attempt is still evaluated, results never depend on it; --no-path-memory measures every step cold.
-    bounds = GridRegistrar.chunk_bounds(P, world)
-    lo, hi = bounds[rank]
-    # a rank holds only the tiles of its chunk + one halo tile.  The chunk of the first (cold) step is cut by pair count; the
-    # learned pattern moves the boundaries afterwards (chunks by predicted attempts), so the set is re-checked before every step
-    # (ensure_tiles below) and the missing tiles are synthesised + uploaded then -- inside the timed region if it happens there.
-    shard_local = world > 1 and not args.all_tiles_on_every_rank
-    need = list(range(grid.n_tiles)) if (world > 1 and not shard_local) else (list(range(lo, hi + 1)) if hi > lo else [])
+    # a rank holds only the tiles of its chunk + one halo tile (`need`, cut above).  The chunk of the first (cold) step is cut by
+    # pair count; the learned pattern moves the boundaries afterwards (chunks by predicted attempts), so the set is re-checked before every
+    # step (ensure_tiles below) and the missing tiles are synthesised + uploaded then -- inside the timed region if it happens there.
     # tiles live in pinned host memory (what a decoder feeding this engine would write into): uploads from it are asynchronous DMA
     tiles = {}
-    # (grids beyond 128 tiles -- configs[4]: 1024 tiles of 4096^2, two core-hours of texture synthesis -- are generated by worker processes)
+    # (grids beyond 128 tiles -- configs[4]: 1024 tiles of 4096^2, two core-hours of texture synthesis -- are generated by worker processes;
+    #  smaller ones come from the pool start_synthesis started before torch)
     t_start = time.perf_counter()
     gen_procs = 0 if grid.n_tiles <= 128 else max(2, min(96, (os.cpu_count() or 4) // (2 * world)))
     t_gen = time.perf_counter()
-    for k, t in zip(need, grid.tiles(need, threads=min(8, os.cpu_count() or 1), processes=gen_procs)):
+    synth_it = synth[1] if synth else grid.tiles(need, threads=min(8, os.cpu_count() or 1), processes=gen_procs)
+    for k, t in zip(need, synth_it):
         buf = eng.pinned_empty(t.shape)
         buf[...] = t
         tiles[k] = buf
@@ -868,6 +939,8 @@ def main():
         handles[k] = eng.tile_upload(tiles[k])               # tiles resident in HBM before the timed region
     eng.sync()
     t_up = time.perf_counter() - t_up
+    if synth:
+        synth[0].close()
     if args.method == "fuse":
         return bench_fuse(args, eng, grid, tiles, handles, torch)
     reg = GridRegistrar(eng, method=args.method, roiRatio=0.2, searchRatio=0.75, offsetEvaluate=args.offset_evaluate, directIncre=1,
@@ -916,11 +989,12 @@ def main():
     # warm-up steps of the timed grid teach it.)
     prior_note = "the warm-up steps of the timed grid itself (--prior same)"
     refetch_prior = dict(refetch)
-    if args.prior == "other" and not args.no_path_memory and args.method in ("surf", "orb", "phase") and need:
-        g2 = SyntheticGrid(args.rows, args.cols, args.tile, overlap=args.overlap, seed=grid.seed + 1)
+    if prior_other:
         hs2 = [None] * grid.n_tiles
-        for k, t in zip(need, g2.tiles(need, threads=min(8, os.cpu_count() or 1), processes=gen_procs)):
+        for k, t in zip(need, synth2[1] if synth2 else g2.tiles(need, threads=min(8, os.cpu_count() or 1), processes=gen_procs)):
             hs2[k] = eng.tile_upload(t)
+        if synth2:
+            synth2[0].close()
         res2, _d2 = step(hs2)                    # (cold: the chunks are those `need` was cut for)
         if args.method == "surf":
             t2 = np.array(g2.true_offsets(), np.int64)
@@ -995,7 +1069,7 @@ def main():
     refetch_at_t0 = dict(refetch)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     progress("%d timed steps: %.1f ms per step" % (args.steps, elapsed / args.steps * 1e3))
@@ -1003,8 +1077,12 @@ def main():
     eng.profile_enable(False)
     st = dict(reg.stats)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(pair_table=last[0], final_direction=[last[1]]))
+    # Everything below up to the result line, besides the per-rank figures and the stage times of the timed steps, is --full only:
+    # the headline needs none of it.
     elapsed_host = None
-    if not args.no_host_leg:
+    if args.full and not args.no_host_leg:
         res_h, _d = step_from_host()                              # warm the tile pool
         assert np.array_equal(res_h, res)
         fence()
@@ -1014,7 +1092,7 @@ def main():
         fence()
         elapsed_host = time.perf_counter() - t0
     elapsed_cold = None
-    if world == 1 and not args.no_path_memory and not args.no_cold_leg:
+    if args.full and world == 1 and not args.no_path_memory and not args.no_cold_leg:
         reg_c = GridRegistrar(eng, method=args.method, roiRatio=0.2, searchRatio=0.75, offsetEvaluate=args.offset_evaluate, directIncre=1,
                               surfParams=reg.params, window=args.window)
         reg_c.remember = False
@@ -1063,7 +1141,7 @@ def main():
             return (a[0], a[1])                       # the profiled launch groups themselves (a capacity retry is a group of its own)
         return (a[0] + b[0], groups if (a[1] + b[1]) else 0)
     de_ms, de_n = stage("describe")
-    if de_n and args.method == "surf":
+    if de_n and args.method == "surf" and args.full:
         # dominant kernels: k_describe + k_describe_small (descriptor windows).  Until the row-pair image they were bound by the
         # texture-address path (TA busy 73 % of the launch: two gathers per sample); with one gather per sample the VALU is the
         # busiest unit (PMC: SQ_INSTS_VALU x 4 cycles = ~94 % of the SIMD cycles of k_describe, TA ~60 %); HBM traffic is a few per
@@ -1213,9 +1291,9 @@ def main():
 
     # ---- CPU baseline: the oracle (a port, cv2 is not installable) on a bounded sample, rank 0 at N = 1 only ------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.method == "surf":
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.method == "surf":
         cpu = cpu_baseline_surf(args, grid, tiles, isa)
-    elif rank == 0 and world == 1 and args.cpu_sample > 0 and args.method in ("orb", "phase"):
+    elif args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.method in ("orb", "phase"):
         cpu = cpu_baseline_pairs(args, grid, tiles, isa, args.method)
 
     if rank == 0:

@@ -936,21 +936,14 @@ def test_fast_header_reader_equals_pillow(tmp_path):
 
 
 def test_decode_once_on_the_reference_demo_tiles():
-    """The same identity on the reference's own micrographs, where they are present (this container; the GPU box has no /root/reference and
-    no `-m gpu` test reads it): one file per demo dataset -- 4:2:0 colour JPEGs from the microscope cameras and the grayscale zircon scans --
-    decoded ONCE to planes gives the grayscale decode (Y) and the colour decode (jdcolor arithmetic) byte for byte."""
+    """The same identity on stored JPEGs of the kinds the reference's demo datasets hold (tests/golden/decode_once: 4:2:0 colour files like
+    the microscope cameras', a 4:2:2 one, and a grayscale file like the zircon scans; odd sizes included): every file decoded ONCE to planes
+    gives the grayscale decode (Y) and the colour decode (jdcolor arithmetic) byte for byte."""
     import ctypes
     import glob
     from imagestitch_amd import stitcher as ST
-    root = "/root/reference/demoImages"
-    if not os.path.isdir(root):
-        pytest.skip("the reference checkout is not present here")
     seen = 0
-    for d in sorted(glob.glob(os.path.join(root, "*", "1"))):
-        files = sorted(f for f in glob.glob(os.path.join(d, "*")) if f.lower().endswith((".jpg", ".jpeg")))
-        if not files:
-            continue
-        p = files[len(files) // 2]
+    for p in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "decode_once", "*.jpg"))):
         owner, shape, parts = ST._decode_once(p, True)
         assert parts[0] == "src" and shape == ST._imshape(p)
         spx = {0: 1, 1: 3, 2: 4}[parts[3]]
@@ -1039,3 +1032,34 @@ def test_bench_says_when_its_pmc_evidence_is_of_another_build(tmp_path, monkeypa
     assert bench.pmc_build()["pmc_stale"] is True                       # the newest summary is of other sources
     (prof / "r99_pmc_summary.txt").write_text("k_describe launches=1 INSTS_VALU=1e9\n")
     assert bench.pmc_build()["pmc_stale"] is True                       # no stamp at all (summaries of rounds 1-4)
+
+
+def test_bench_dump_outputs_and_synthesis_pool(tmp_path):
+    """bench.py --dump-outputs writes every array as <name>.npy in float64 (the result table exactly); the pool that synthesises a
+    grid before torch comes up hands out the same bytes as SyntheticGrid.tiles, for the timed grid and its seed + 1 instance; --steps 0 and --dump-outputs off the grid registration path are refused before any work."""
+    import importlib
+    import subprocess
+    import sys
+    from imagestitch_amd.synthetic import SyntheticGrid
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    table = np.array([[1, 1846, 4, 1, 1, 844], [0, -7, 0, 3, 2, 0]], np.int32)
+    bench.dump_outputs(str(tmp_path / "d"), dict(pair_table=table, final_direction=[3]))
+    got = np.load(str(tmp_path / "d" / "pair_table.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, table)
+    assert np.load(str(tmp_path / "d" / "final_direction.npy")).tolist() == [3.0]
+
+    need = [1, 2, 3]
+    for g in (SyntheticGrid(2, 2, 96, overlap=0.25), SyntheticGrid(2, 2, 96, overlap=0.25, seed=SyntheticGrid(1, 1, 8).seed + 1)):
+        pool, it = bench.start_synthesis(g, need, 2)
+        try:
+            got = [t for _k, t in zip(need, it)]
+        finally:
+            pool.close()
+            pool.join()
+        assert len(got) == len(need) and all(np.array_equal(a, b) for a, b in zip(got, g.tiles(need, threads=1)))
+    for argv in (["--steps", "0"], ["--method", "fuse", "--dump-outputs", str(tmp_path / "f")]):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and "error" in out.stderr, (argv, out.stderr)

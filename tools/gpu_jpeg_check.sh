@@ -5,7 +5,7 @@ O=gpurun_out/jpeg
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 tail -3 $O/pytest.log
 run() { # name, env value, extra args
-  VFSMS_NATIVE_JPEG=$2 timeout 150 python bench.py --from-files ${@:3} > $O/$1.json 2> $O/$1.err || tail -c 300 $O/$1.err
+  VFSMS_NATIVE_JPEG=$2 timeout 150 python bench.py --full --from-files ${@:3} > $O/$1.json 2> $O/$1.err || tail -c 300 $O/$1.err
   python - $O/$1.json $1 <<'PY'
 import json, sys
 try:
@@ -22,7 +22,7 @@ run gray_pillow16 0
 run color_native32 1 --color --decode-threads 32
 run gray_native32 1 --decode-threads 32
 timeout 200 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/jpeg/bench_default.json').read().strip().splitlines()[-1])

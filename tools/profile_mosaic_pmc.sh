@@ -3,7 +3,7 @@
 # <out dir>/pmc_summary.txt (called by tools/profile_round.sh; the summary's build stamp must be this build's)
 OUT=$1
 # ---- the mosaic walk's kernels: HBM traffic per launch, and how many launches one mosaic is ----
-FZCMD="python bench.py --method fuse --steps 2 --warmup 1 --cpu-sample 0"
+FZCMD="python bench.py --full --method fuse --steps 2 --warmup 1 --cpu-sample 0"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fz_fetch -o pmc --output-format csv -- $FZCMD > $OUT/pmc_fz_fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_fz_write -o pmc --output-format csv -- $FZCMD > $OUT/pmc_fz_write.log 2>&1
 python - <<PY

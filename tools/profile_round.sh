@@ -12,17 +12,17 @@ mkdir -p $OUT
 #  per-kernel averages are those of the timed region -- the unprimed default run mixes in the 13 small launches of the first, cold step;
 #  --no-cold-leg for the same reason.  The JSON written under the profiler says so: path_memory_primed_for_profiling.)
 export VFSMS_BENCH_PRIME=1
-CMD="python bench.py --cpu-sample 0 --no-cold-leg"
+CMD="python bench.py --full --cpu-sample 0 --no-cold-leg"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $CMD > $OUT/trace_bench.json 2> $OUT/trace.err
 python tools/rocpd_summary.py $(ls $OUT/trace/*results.db | head -1) $OUT/kernel_stats.csv
 for m in orb phase fuse; do
-  VFSMS_BENCH_PRIME=0 timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace_$m -o trace -- python bench.py --method $m --cpu-sample 0 --no-cold-leg > $OUT/trace_bench_$m.json 2> $OUT/trace_$m.err
+  VFSMS_BENCH_PRIME=0 timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace_$m -o trace -- python bench.py --full --method $m --cpu-sample 0 --no-cold-leg > $OUT/trace_bench_$m.json 2> $OUT/trace_$m.err
   python tools/rocpd_summary.py $(ls $OUT/trace_$m/*results.db | head -1) $OUT/kernel_stats_$m.csv
 done
 rm -rf $OUT/trace $OUT/trace_orb $OUT/trace_phase $OUT/trace_fuse
 [ "$PMC" = "pmc" ] || exit 0
 export VFSMS_BENCH_MIN_WARM=0
-PCMD="python bench.py --steps 1 --warmup 0 --cpu-sample 0 --no-host-leg --no-cold-leg"
+PCMD="python bench.py --full --steps 1 --warmup 0 --cpu-sample 0 --no-host-leg --no-cold-leg"
 timeout 500 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/pmc_sq -o pmc --output-format csv -- $PCMD > $OUT/pmc_sq_bench.json 2> $OUT/pmc_sq.err
 timeout 500 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc --output-format csv -- $PCMD > $OUT/pmc_fetch_bench.json 2> $OUT/pmc_fetch.err
 timeout 500 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o pmc --output-format csv -- $PCMD > $OUT/pmc_write_bench.json 2> $OUT/pmc_write.err
