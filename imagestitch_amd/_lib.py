@@ -140,6 +140,9 @@ _SIGNATURES = {
     "vfsms_canvas_fuse_tile_m": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_fuse_trig_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfsms_fuse_multiband_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p]),
+    "vfsms_canvas_set_multiband_levels": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "vfsms_features_surf_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_features_match_offset_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "vfsms_canvas_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
@@ -480,6 +483,19 @@ class Engine:
         self._check(self.lib.vfsms_fuse_trig_i64(self.ctx, _ptr(A), _ptr(B), r, c, ch, int(dx), int(dy), _ptr(out), _ptr(info)))
         return (out, info) if return_info else out
 
+    def fuse_multiband_i64(self, A, B, dx, dy, levels=4, return_info=False):
+        """multiBandBlending on int64 regions (-1 = empty) -> uint8: seam where the fade's weights tie, Laplacian pyramid of `levels`
+        levels (vfsms_fuse_multiband_i64; the arithmetic is the library's own, tests/multiband_ref.py)."""
+        A = np.ascontiguousarray(A, np.int64); B = np.ascontiguousarray(B, np.int64)
+        if A.shape != B.shape:
+            raise ValueError("fuse: shapes differ")
+        r, c = A.shape[:2]
+        ch = 1 if A.ndim == 2 else A.shape[2]
+        out = np.empty(A.shape, np.uint8)
+        info = np.zeros(4, np.int32)
+        self._check(self.lib.vfsms_fuse_multiband_i64(self.ctx, _ptr(A), _ptr(B), r, c, ch, int(dx), int(dy), int(levels), _ptr(out), _ptr(info)))
+        return (out, info) if return_info else out
+
     def fuse_ramps_i64(self, A, dx, dy, force_corner=False):
         """-> ((wA_r, wB_r, wA_c, wB_c), info): the separable float32 ramps of the fade blend / getWeightsMatrix."""
         A = np.ascontiguousarray(A, np.int64)
@@ -642,7 +658,7 @@ class Engine:
         self._check(self.lib.vfsms_canvas_paste(self.ctx, C.c_int64(handle), _ptr(tile), tile.shape[0], tile.shape[1], int(y0), int(x0)))
 
     def canvas_fuse_tile(self, handle, tile, y0, x0, roi, dx, dy, method=0):
-        """method 0: fadeInAndFadeOut, 1: trigonometric"""
+        """method 0: fadeInAndFadeOut, 1: trigonometric, 2: multiBandBlending (levels: canvas_set_multiband_levels)"""
         tile = np.ascontiguousarray(tile, np.uint8)
         info = np.zeros(4, np.int32)
         ry0, rx0, ry1, rx1 = [int(v) for v in roi]
@@ -668,7 +684,8 @@ class Engine:
         self._check(self.lib.vfsms_canvas_paste_tile(self.ctx, C.c_int64(handle), C.c_int64(tile_handle), int(y0), int(x0)))
 
     def canvas_fuse_tile_resident(self, handle, tile_handle, y0, x0, roi, dx, dy, want_info=False, method=0):
-        """want_info=False: the call only enqueues work; geometry errors surface in canvas_download.  method 0: fadeInAndFadeOut, 1: trigonometric"""
+        """want_info=False: the call only enqueues work; geometry errors surface in canvas_download.  method 0: fadeInAndFadeOut, 1: trigonometric,
+        2: multiBandBlending"""
         info = np.zeros(4, np.int32) if want_info else None
         ry0, rx0, ry1, rx1 = [int(v) for v in roi]
         self._check(self.lib.vfsms_canvas_fuse_tile_resident_m(self.ctx, C.c_int64(handle), C.c_int64(tile_handle), int(y0), int(x0),
@@ -677,12 +694,17 @@ class Engine:
 
     def canvas_assemble_resident(self, handle, tile_handles, geom):
         """The mosaic walk over resident tiles as one call.  geom: int32 [n][9] = y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode
-        (mode -1 paste, 0 fadeInAndFadeOut, 1 trigonometric, 2 / 3 / 4 average / maximum / minimum); enqueue only, geometry errors surface in canvas_download."""
+        (mode -1 paste, 0 fadeInAndFadeOut, 1 trigonometric, 2 / 3 / 4 average / maximum / minimum, 6 multiBandBlending); enqueue only, geometry
+        errors surface in canvas_download."""
         th = np.ascontiguousarray(tile_handles, np.int64)
         g = np.ascontiguousarray(geom, np.int32).reshape(-1, 9)
         if len(th) != len(g):
             raise ValueError("canvas_assemble_resident: one geometry row per tile")
         self._check(self.lib.vfsms_canvas_assemble_resident(self.ctx, C.c_int64(handle), len(th), _ptr(th), _ptr(g)))
+
+    def canvas_set_multiband_levels(self, handle, levels):
+        """pyramid levels (1..8) of the canvas's multiBandBlending fuses (default 4)"""
+        self._check(self.lib.vfsms_canvas_set_multiband_levels(self.ctx, C.c_int64(handle), int(levels)))
 
     def canvas_download(self, handle, rows, cols, ch):
         out = np.empty((rows, cols, ch) if ch > 1 else (rows, cols), np.uint8)

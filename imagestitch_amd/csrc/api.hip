@@ -7,7 +7,7 @@
 #include <algorithm>
 
 int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy,
-                    uint8_t *d_out, int32_t *info, int method = 0);
+                    uint8_t *d_out, int32_t *info, int method = 0, int levels = 4);
 
 // ---- errors -------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -251,6 +251,7 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     for (auto &kv : ctx->feats) if (!kv.second.block) { if (kv.second.kps_xy) hipFree(kv.second.kps_xy); if (kv.second.desc) hipFree(kv.second.desc); }
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
+    if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->d_layers) hipFree(ctx->d_layers);
     if (ctx->d_tables) hipFree(ctx->d_tables);
@@ -1534,6 +1535,26 @@ extern "C" int vfsms_fuse_trig_i64(vfsms_ctx *ctx, const int64_t *A, const int64
     return VFSMS_OK;
 }
 
+// multiBandBlending on the reference's own array representation: the seam from the fade's geometry (degenerate corner geometries
+// fail as the fade's do), then the Laplacian-pyramid blend of multiband_kernels.hip with `levels` levels
+extern "C" int vfsms_fuse_multiband_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
+                                        int dx, int dy, int levels, uint8_t *out, int32_t *info)
+{
+    CTX_ENTER(ctx);
+    if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_multiband_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (levels < 1 || levels > VFSMS_MB_MAX_LEVELS) { vfsms_set_error("fuse_multiband_i64: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    const size_t nel = (size_t)r * c * ch;
+    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 4 * ((size_t)r + c) + 65536));
+    long long *dA, *dB;
+    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
+    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
+    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
+    TRY(fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, 2, levels));
+    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 int fuse_i64_ramps(vfsms_ctx *ctx, const long long *dA, int r, int c, int ch, int dx, int dy, int force_corner,
                    float *h_ramps, int32_t *info);
 
@@ -1556,7 +1577,7 @@ extern "C" int vfsms_canvas_create(vfsms_ctx *ctx, int rows, int cols, int ch, i
     if (!handle || rows <= 0 || cols <= 0 || ch < 1 || ch > 4) { vfsms_set_error("canvas_create: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec cv; cv.rows = rows; cv.cols = cols; cv.ch = ch;
     if (ctx->has_spare_canvas && ctx->spare_canvas.rows == rows && ctx->spare_canvas.cols == cols && ctx->spare_canvas.ch == ch) {
-        cv = ctx->spare_canvas; cv.placed.clear();          // same size as the canvas freed last: its buffers, re-initialised below in stream order
+        cv = ctx->spare_canvas; cv.placed.clear(); cv.mb_levels = 4;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
         ctx->has_spare_canvas = false;
     } else {
         HIP_TRY(hipMalloc((void **)&cv.pix, (size_t)rows * cols * ch));
@@ -1613,7 +1634,7 @@ extern "C" int vfsms_canvas_fuse_tile_m(vfsms_ctx *ctx, int64_t canvas, const ui
                                         int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 1) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut) or 1 (trigonometric)"); return VFSMS_ERR_BAD_ARG; }
+    if (method < 0 || method > 2) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric) or 2 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec *cv;
     TRY(canvas_tile_args(ctx, canvas, tile, h, w, y0, x0, &cv));
     if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + h || rx1 > x0 + w)) {
@@ -1678,7 +1699,7 @@ extern "C" int vfsms_canvas_fuse_tile_resident_m(vfsms_ctx *ctx, int64_t canvas,
                                                  int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 1) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut) or 1 (trigonometric)"); return VFSMS_ERR_BAD_ARG; }
+    if (method < 0 || method > 2) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric) or 2 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec *cv; TileRec *tr;
     TRY(canvas_resident_args(ctx, canvas, tile, y0, x0, &cv, &tr));
     const int h = tr->h, w = tr->w;
@@ -1712,7 +1733,7 @@ extern "C" int vfsms_canvas_fuse_tile_resident(vfsms_ctx *ctx, int64_t canvas, i
 }
 // The whole mosaic walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over resident tiles as ONE call: per tile nine ints
 // [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode] with mode -1 = paste (the first tile, notFuse), 0 = fadeInAndFadeOut, 1 = trigonometric,
-// 2 / 3 / 4 = average / maximum / minimum.
+// 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending (5 is not a mode).
 // Enqueue only (one library call per mosaic instead of one per tile; the device chain stays two launches per tile); geometry errors are latched
 // in the canvas and reported by the download, as with vfsms_canvas_fuse_tile_resident(info = NULL).
 extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, int n, const int64_t *tiles, const int32_t *geom)
@@ -1721,7 +1742,7 @@ extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, in
     if (n < 0 || (n > 0 && (!tiles || !geom))) { vfsms_set_error("canvas_assemble_resident: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     for (int i = 0; i < n; i++) {                       // everything is checked before anything is enqueued
         const int32_t *g = geom + 9 * (size_t)i;
-        if (g[8] < -1 || g[8] > 4) { vfsms_set_error("canvas_assemble_resident: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum)"); return VFSMS_ERR_BAD_ARG; }
+        if (g[8] < -1 || g[8] > 6 || g[8] == 5) { vfsms_set_error("canvas_assemble_resident: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum), 6 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
         CanvasRec *cv; TileRec *tr;
         TRY(canvas_resident_args(ctx, canvas, tiles[i], g[0], g[1], &cv, &tr));
         if (g[8] >= 0 && g[4] > g[2] && g[5] > g[3] && (g[2] < g[0] || g[3] < g[1] || g[4] > g[0] + tr->h || g[5] > g[1] + tr->w)) {
@@ -1731,9 +1752,20 @@ extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, in
     for (int i = 0; i < n; i++) {
         const int32_t *g = geom + 9 * (size_t)i;
         if (g[8] < 0) TRY(vfsms_canvas_paste_tile(ctx, canvas, tiles[i], g[0], g[1]));
+        else if (g[8] == 6) TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], 2, nullptr));
         else if (g[8] >= 2) TRY(vfsms_canvas_blend_tile_resident(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[8] - 2));
         else TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], nullptr));
     }
+    return VFSMS_OK;
+}
+// the level count of the canvas's multiBandBlending fuses (method 2 / geom mode 6); a new canvas starts at 4
+extern "C" int vfsms_canvas_set_multiband_levels(vfsms_ctx *ctx, int64_t canvas, int levels)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->canvases.find(canvas);
+    if (it == ctx->canvases.end()) { vfsms_set_error("canvas_set_multiband_levels: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    if (levels < 1 || levels > VFSMS_MB_MAX_LEVELS) { vfsms_set_error("canvas_set_multiband_levels: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    it->second.mb_levels = levels;
     return VFSMS_OK;
 }
 extern "C" int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out)

@@ -169,7 +169,7 @@ struct MatchDev {
 struct TileRec { uint8_t *ptr; int h, w, stride; bool owned; hipEvent_t ready; bool pending; int ch = 1; size_t bytes = 0; int fill = 0; };
 struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device staging of one decoded source image (vfsms_tile_fill_pair)
 struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
-struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; };   // d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; };   // d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct ProfRec { int id; hipEvent_t a, b; };
@@ -200,6 +200,7 @@ struct vfsms_ctx {
     size_t tile_pool_bytes = 0;
     std::vector<hipEvent_t> event_pool;
     std::unordered_map<int64_t, CanvasRec> canvases;
+    void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
     CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a batch (vfsms_features_surf_batch), freed with its last set
@@ -272,12 +273,18 @@ int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int
 int launch_enhance(vfsms_ctx *ctx, const EnhJob *d_jobs, const EnhJob *h_jobs, int n, int mode, double clip_limit, int tiles);
 // fuse_kernels.hip
 int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
-                       int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info, int method = 0);   // method 0 fadeInAndFadeOut, 1 trigonometric
+                       int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info, int method = 0);   // method 0 fadeInAndFadeOut, 1 trigonometric, 2 multiBandBlending
 int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
                         int ry0, int rx0, int ry1, int rx1, int mode);
 int canvas_paste_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0);
 size_t canvas_scratch_bytes(int rows, int cols);
 int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv);
+// multiband_kernels.hip (SeamGeom: fuse_geom.h)
+#define VFSMS_MB_MAX_LEVELS 8
+struct SeamGeom;
+int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
+                    const SeamGeom &G, int levels);
+int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, const SeamGeom &G, int levels, uint8_t *d_out);
 
 #ifdef __HIPCC__
 // Speed only (placement is not a contract): workgroups are observed to land on XCD (linear block id % 8), each XCD with a private

@@ -11,6 +11,7 @@
 // quirks) runs on the host.
 #include "common.h"
 #include "detmath.h"
+#include "fuse_geom.h"
 #include <vector>
 #include <algorithm>
 #include <string.h>
@@ -80,30 +81,6 @@ __device__ __forceinline__ uint8_t trig_px(const TrigGeom &G, bool corner, int i
     res = res > 255 ? 255 : res;
     return (uint8_t)res;
 }
-// the strip ramps of fuseByFadeInAndFadeOut in closed form, with the reference's float32 expression ((1. * f) * 1.0) / n:
-//   col <= row: weightMatA_2[col - i - 1] = weightMatB_2[i] = f(i) / col, f(i) = i (dy >= 0) or col - i;  else  weightMatA_1[i] =
-//   weightMatB_1[row - i - 1] = g(i) / row, g(i) = i (dx <= 0) or row - i  (what fuse_weights_body's strip branch stores into the arrays)
-// kind 3: getWeightsMatrix's corner ramps (ImageFusion.py:43-190 as fuse_weights_body stores them) from (index, rowIndex, colIndex):
-//   rows, index 2 / 1: weightMatB_1[i] = i / ri for 0 <= i <= rowIndex (ri = rowIndex, 0 patched to 1: then only [1] = 1 is written);
-//         index 3 / 0: weightMatB_1[i] = (row - i - 1) / (row - ri - 1) for i >= max(rowIndex, 0);   columns alike with colIndex, index 2 / 3 | 0 / 1
-//   quotients in float64, stored as float32; everything else stays 1
-struct AnalyticRamps {
-    int kind, r, c, dx, dy;
-    int index, rowIndex, colIndex;
-    __device__ __forceinline__ float corner_b(int i, int n, int at, bool counting_up) const
-    {
-        const int ai = at == 0 ? 1 : at;
-        if (counting_up) return (at >= 1 && i <= at) ? (float)((double)i * 1 / ai) : 1.f;
-        return i >= max(at, 0) ? (float)((double)(n - i - 1) * 1 / (n - ai - 1)) : 1.f;
-    }
-    __device__ __forceinline__ float cb_row(int i) const { return corner_b(i, r, rowIndex, index == 2 || index == 1); }
-    __device__ __forceinline__ float cb_col(int j) const { return corner_b(j, c, colIndex, index == 2 || index == 3); }
-    __device__ __forceinline__ float ratio(int n, int d) const { return ((1.f * (float)n) * 1.0f) / (float)d; }
-    __device__ __forceinline__ float a_col(int j) const { return kind == 1 ? ratio(dy >= 0 ? c - 1 - j : j + 1, c) : 1.f; }
-    __device__ __forceinline__ float b_col(int j) const { return kind == 1 ? ratio(dy >= 0 ? j : c - j, c) : 1.f; }
-    __device__ __forceinline__ float a_row(int i) const { return kind == 2 ? ratio(dx <= 0 ? i : r - i, r) : 1.f; }
-    __device__ __forceinline__ float b_row(int i) const { return kind == 2 ? ratio(dx <= 0 ? r - 1 - i : i + 1, r) : 1.f; }
-};
 // (bx, by): the block of the tile this workgroup blends -- blockIdx for the per-tile launch, a drawn index inside k_mosaic_walk
 __device__ __forceinline__ void fuse_apply_block(uint8_t *pix, uint8_t *mask, int ccols, int ch,
                                                  const uint8_t *tile, int th, int tw, int y0, int x0,
@@ -744,8 +721,9 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int
         const long long valid = canvas_valid_area(cv, ry0, rx0, ry1, rx1) * cv->ch;
         const double nel = (double)r * c * cv->ch;
         if ((double)valid / nel > 0.65) {
-            hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
-                               (const int *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, c <= r ? 1 : 2);
+            if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{c <= r ? 1 : 2, r, c, dx, dy}, cv->mb_levels));
+            else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
+                                    (const int *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, c <= r ? 1 : 2);
             HIP_TRY(hipGetLastError());
             canvas_mark(cv, y0, x0, h, w);
             if (info) { info[0] = 0; info[1] = -1; info[2] = 0; info[3] = 0; }      // what the ramp kernel reports for a strip: mode 0, no corner index
@@ -803,11 +781,13 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int
             P.rowIndex[index] = rowIndex; P.colIndex[index] = colIndex; P.err[index] = err;
         }
         hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err, wx_n);
-        hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
+        if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{3, r, c, dx, dy, S.out}, cv->mb_levels));
+        else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
                            (const int *)S.out, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, 3);
     } else {
         hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, dx, dy, cv->d_err, wx_n);
-        hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
+        if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{0, r, c, dx, dy, S.out, S.wAr, S.wAc, S.wBr, S.wBc}, cv->mb_levels));
+        else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
                            d_tile, h, w, y0, x0, ry0, rx0, r, c, (const int *)S.out, (const float *)S.wAr, (const float *)S.wAc, (const float *)S.wBr, (const float *)S.wBc, TG, 0);
     }
     HIP_TRY(hipGetLastError());
@@ -836,9 +816,9 @@ int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv)
     return VFSMS_OK;
 }
 
-// A, B: device int64 [r][c][ch]; out: device u8
+// A, B: device int64 [r][c][ch]; out: device u8.  method 0 fade, 1 trigonometric, 2 multi-band with `levels` (its seam from the fade's ramps)
 int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy,
-                    uint8_t *d_out, int32_t *info, int method)
+                    uint8_t *d_out, int32_t *info, int method, int levels)
 {
     FuseScratch S;
     TRY(fuse_scratch(ctx, r, c, &S));
@@ -847,8 +827,9 @@ int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, in
     hipLaunchKernelGGL(k_i64_stats_rows, dim3(r), dim3(256), 0, ctx->stream, V, r, c, S.st, S.rowFirst, S.rowLast);
     hipLaunchKernelGGL(k_i64_stats_cols, dim3((c + 255) / 256), dim3(256), 0, ctx->stream, V, r, c, S.colFirst, S.colLast);
     TRY(launch_weights(ctx, S, r, c, ch, dx, dy));
-    hipLaunchKernelGGL(k_i64_apply, dim3((c + 255) / 256, r), dim3(256), 0, ctx->stream, V, r, c, S.out,
-                       S.wAr, S.wAc, S.wBr, S.wBc, d_out, TrigGeom{method == 1, r, c, dx, dy});
+    if (method == 2) TRY(mb_blend_i64(ctx, dA, dB, r, c, ch, SeamGeom{0, r, c, dx, dy, S.out, S.wAr, S.wAc, S.wBr, S.wBc}, levels, d_out));
+    else hipLaunchKernelGGL(k_i64_apply, dim3((c + 255) / 256, r), dim3(256), 0, ctx->stream, V, r, c, S.out,
+                            S.wAr, S.wAc, S.wBr, S.wBc, d_out, TrigGeom{method == 1, r, c, dx, dy});
     HIP_TRY(hipGetLastError());
     return finish_weights(ctx, S, r, c, info);
 }

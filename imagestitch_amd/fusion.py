@@ -3,7 +3,8 @@
 Stitcher.getStitchByOffset hands to fuseImage (Stitcher.py:434-436,475-483).
 
 On the hot path (north_star): fuseByFadeInAndFadeOut + getWeightsMatrix -> HIP (csrc/fuse_kernels.hip); fuseByTrigonometric
-shares their kernels (scope row f-4).  fuseByAverage / Maximum / Minimum are numpy one-liners as array operators (inside
+shares their kernels (scope row f-4); fuseByMultiBandBlending takes its seam from the same geometry and blends with the pyramid
+kernels of csrc/multiband_kernels.hip.  fuseByAverage / Maximum / Minimum are numpy one-liners as array operators (inside
 Stitcher.getStitchByOffset they run on the device canvas: vfsms_canvas_blend_tile).
 """
 import numpy as np
@@ -65,8 +66,20 @@ class ImageFusion(Utility.Method):
         imageA[hole] = imageB[hole]
         return out
 
-    def fuseByMultiBandBlending(self, images):
-        raise NotImplementedError("multi-band blending (ImageFusion.py:296-367) is outside the VFSMS hot path")
+    # ---- multi-band (Laplacian pyramid) blending -------------------------------------------------------------------------------
+    def fuseByMultiBandBlending(self, images, dx=0, dy=0):
+        """Laplacian-pyramid blend of the overlap with self.multiBandLevels levels, gray or colour, on the device
+        (vfsms_fuse_multiband_i64).  The seam is hard where the fade's weights tie (wA >= wB -> A, from A's -1 pattern, so dx / dy
+        pick the strip orientation as in fuseByFadeInAndFadeOut; geometries the fade refuses are refused the same way); the
+        pyramids are float32 with 5-tap pyrDown / pyrUp and the result is rounded half to even.  The arithmetic is this project's
+        own specification (tests/multiband_ref.py), NOT a restatement of cv2.pyrDown / pyrUp or of the reference's
+        ImageFusion.py:296-367 (gray only there): neither can be compared byte for byte here.
+        Like the fade, empty pixels of imageA are filled from imageB IN PLACE."""
+        (imageA, imageB) = images
+        out = self.engine.fuse_multiband_i64(imageA, imageB, dx, dy, levels=int(self.multiBandLevels))
+        hole = imageA < 0
+        imageA[hole] = imageB[hole]
+        return out
 
     def fuseByOptimalSeamLine(self, images, direction="horizontal"):
         raise NotImplementedError("optimal seam line (ImageFusion.py:377-492, interactive cv2.imshow) is outside the VFSMS hot path")

@@ -82,6 +82,9 @@ class Method():
     clipLimit = 20
     tileSize = 5
 
+    # ---- fusion (fuseMethod "multiBandBlending": pyramid levels, ImageFusion.fuseByMultiBandBlending / the device canvas) ----
+    multiBandLevels = 4
+
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None
 
