@@ -974,7 +974,7 @@ def test_config2_full_orb_grid_equals_the_oracle_chain(engine, oracle):
     reference's search does with three equal random votes -- is counted and bounded, the pairs that DO land on the truth are exact."""
     from concurrent.futures import ThreadPoolExecutor
     from imagestitch_amd.grid import GridRegistrar
-    from test_oracle_golden import _chain_search, oracle_orb_attempt
+    from test_oracle_golden import _chain_search, oracle_orb_attempt, pool_size
     g = SyntheticGrid(10, 9, 2048, overlap=0.10)
     tiles = g.tiles(threads=8)
     P = len(tiles) - 1
@@ -995,7 +995,7 @@ def test_config2_full_orb_grid_equals_the_oracle_chain(engine, oracle):
         return attempt
     # every pair's first ring, evaluated ahead in parallel (the C oracle releases the interpreter lock); the walk below decides alone
     jobs = [(k, d, 1) for k in range(P) for d in (1, 2, 3, 4)]
-    with ThreadPoolExecutor(max_workers=min(64, os.cpu_count() or 8)) as ex:
+    with ThreadPoolExecutor(max_workers=pool_size()) as ex:
         for key, r in zip(jobs, ex.map(lambda kd: oracle_orb_attempt(oracle, tiles[kd[0]], tiles[kd[0] + 1])(kd[1], kd[2]), jobs)):
             memo[key] = r
     direction, exp = 1, []
@@ -1014,6 +1014,105 @@ def test_config2_full_orb_grid_equals_the_oracle_chain(engine, oracle):
     off_truth = [k for k, r in enumerate(exp) if not (r[0] and [r[1], r[2]] == [int(truth[k][0]), int(truth[k][1])])]
     print("configs[2]: %d of %d pairs accepted off truth (reference behaviour at 3 votes): %s" % (len(off_truth), P, off_truth))
     assert len(off_truth) <= 30, off_truth
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_headline_surf_grid_equals_the_oracle_chain(engine, oracle):
+    """The workload bench.py times, row for row: the synthetic 10 x 9 grid of 2048^2 tiles (89 pairs, 10 % overlap, default seed), SURF +
+    BF-L2 2-NN + ratio 0.75 + mode vote at offsetEvaluate = 3, registered by the native registrar with bench.py's window of 48.
+      1. The whole table -- status, offset, direction, i, votes of every pair -- equals the ORACLE's chain (Stitcher.py:316-361 walked
+         pair after pair with the direction threaded), and every pair lands within 1 px of the synthetic truth.
+      2. Every attempt the oracle walk evaluated, the failed candidates included, goes through ONE attempt_surf_batch: its raw row
+         (status, offset, votes, keypoint counts of both strips, match count) equals the oracle's.
+      3. The path memory and the speculation window never change results: a hint of the true directions, two wrong hints, window 24
+         and a registrar that has learned the grid all give the same table.
+    The oracle's attempts are evaluated ahead on host threads at the keys the engine's table implies; the walk decides from oracle results
+    alone and computes any key it misses on demand."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from imagestitch_amd.grid import GridRegistrar
+    from test_oracle_golden import _chain_search, oracle_surf_attempt, pool_size
+    t0 = time.perf_counter()
+    g = SyntheticGrid(10, 9, 2048, overlap=0.10)
+    tiles = g.tiles(threads=pool_size())
+    P = len(tiles) - 1
+    assert P == 89
+    shapes = [t.shape for t in tiles]
+    hs = [engine.tile_upload(t) for t in tiles]
+
+    def registrar(window=48):
+        return GridRegistrar(engine, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=3, directIncre=1,
+                             surfParams=engine.surf_params(), window=window)
+    try:
+        reg = registrar()
+        table, d_out = reg.register(hs, shapes, 1)
+        got = [[int(v) for v in row[:6]] for row in table]
+
+        # -- 1. the oracle chain --
+        # (one OpenMP thread per oracle call: the attempts themselves run on the pool, on-demand ones included)
+        raw = [oracle_surf_attempt(oracle, tiles[k], tiles[k + 1], nthreads=1) for k in range(P)]
+        implied, d_in = [], 1
+        for k, r in enumerate(got):
+            for ring in reg.rings(d_in):
+                for (d, i) in ring:
+                    implied.append((k, d, i))
+                    if r[0] and (d, i) == (r[3], r[4]):
+                        break
+                else:
+                    continue
+                break
+            d_in = r[3] if r[0] else d_in
+        walked = []
+        with ThreadPoolExecutor(max_workers=pool_size()) as ex:
+            list(ex.map(lambda kdi: raw[kdi[0]](kdi[1], kdi[2]), implied))
+
+            def attempt_of(k):
+                def attempt(d, i):
+                    if (d, i) not in raw[k].rows:
+                        ex.submit(raw[k], d, i).result()
+                    walked.append((k, d, i))
+                    r = raw[k].rows[(d, i)]
+                    return bool(r[0]) and r[4] > 0 and r[5] > 0, [r[1], r[2]], r[3]
+                return attempt
+            direction, exp = 1, []
+            for k in range(P):
+                st, off, d, i, log = _chain_search(attempt_of(k), shapes[k], shapes[k + 1], direction)
+                exp.append([int(st), off[0], off[1], d if st else direction, i, log[-1][5] if st else 0])
+                if st:
+                    direction = d
+        truth = g.true_offsets()
+        for k, b in enumerate(exp):
+            assert b[0] == 1 and abs(b[1] - truth[k][0]) <= 1 and abs(b[2] - truth[k][1]) <= 1, (k, b, truth[k])
+        for k, (a, b) in enumerate(zip(got, exp)):
+            assert a == b, (k, a, b, truth[k])
+        assert int(d_out) == direction
+        print("headline surf grid: the oracle walk evaluated %d attempts (%d prefetched)" % (len(walked), len(implied)))
+
+        # -- 2. every attempt of the walk in one batch, counts included --
+        jobs = []
+        for (k, d, i) in walked:
+            ra = isa.roi_rect(shapes[k], d, "first", i * 0.2); rb = isa.roi_rect(shapes[k + 1], d, "second", i * 0.2)
+            jobs.append((hs[k], hs[k + 1], ra[0], ra[1], rb[0], rb[1], ra[2], ra[3]))
+        rows = engine.attempt_surf_batch(jobs, engine.surf_params(), 0.75, 3)
+        for (k, d, i), row in zip(walked, rows):
+            assert row[:7].tolist() == raw[k].rows[(d, i)], (k, d, i, row, raw[k].rows[(d, i)])
+
+        # -- 3. prior and window never change the table --
+        true_dirs = [int(v) for v in g.true_directions()]
+        assert reg.path_memory is not None
+        variants = [("learned path memory", reg, None),
+                    ("hint = true directions", registrar(), true_dirs),
+                    ("hint = all 1", registrar(), [1] * P),
+                    ("hint = true directions shifted by one", registrar(), true_dirs[1:] + true_dirs[:1]),
+                    ("window 24", registrar(24), None)]
+        for name, r, hint in variants:
+            t2, d2 = r.register(hs, shapes, 1, hint=hint)
+            assert np.array_equal(t2, table) and int(d2) == int(d_out), name
+    finally:
+        for h in hs:
+            engine.tile_free(h)
+    print("headline surf grid: %.1f s" % (time.perf_counter() - t0))
 
 
 @pytest.mark.gpu

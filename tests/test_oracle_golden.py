@@ -312,6 +312,30 @@ def oracle_orb_attempt(oracle, A, B, roiRatio=0.2, offsetEvaluate=3):
     return attempt
 
 
+def oracle_surf_attempt(oracle, A, B, roiRatio=0.2, ratio=0.75, offsetEvaluate=3, nthreads=0):
+    """attempt(direction, i) with the oracle's SURF + BF-L2 2-NN + ratio test + mode vote (ImageUtility.py:258-262, 288-296, 139-178)
+    -> (status, [dx, dy], votes), status gated on keypoints on both sides as the registrar gates it.  attempt.rows[(direction, i)] keeps
+    the attempt's raw row as the engine's batch reports it: [status, dx, dy, votes, nA, nB, nMatches].  nthreads: the oracle's OpenMP
+    threads per call (1 when the attempts themselves run on a thread pool)."""
+    from imagestitch_amd.utility import roi_rect
+
+    def attempt(d, i):
+        ra = roi_rect(A.shape, d, "first", i * roiRatio); rb = roi_rect(B.shape, d, "second", i * roiRatio)
+        a = np.ascontiguousarray(A[ra[0]:ra[0] + ra[2], ra[1]:ra[1] + ra[3]]); b = np.ascontiguousarray(B[rb[0]:rb[0] + rb[2], rb[1]:rb[1] + rb[3]])
+        ka, da = oracle.surf_detect_describe(a, nthreads=nthreads); kb, db = oracle.surf_detect_describe(b, nthreads=nthreads)
+        pairs = oracle.bf_l2_ratio_matches(da, db, ratio, nthreads=nthreads)
+        st, off, votes = oracle.mode_offset(np.stack([ka["x"], ka["y"]], 1), np.stack([kb["x"], kb["y"]], 1), pairs, offsetEvaluate)
+        attempt.rows[(d, i)] = [int(st), int(off[0]), int(off[1]), int(votes), len(ka), len(kb), len(pairs)]
+        return bool(st) and len(ka) > 0 and len(kb) > 0, off, votes
+    attempt.rows = {}
+    return attempt
+
+
+def pool_size():
+    """Threads for a CPU pool in the tests: the CPUs this process may use, at most 16 (os.cpu_count() reports the whole host)."""
+    return min(16, len(os.sched_getaffinity(0)))
+
+
 def test_phase_oracle_against_independent_numpy_restatement(oracle, golden_dir):
     """The phase-correlation leg has no reference-held vector (cv2 is not installable).  What can be ruled out is a transcription
     slip shared by nobody: tests/phase_numpy.py restates cv2.phaseCorrelate a second time (numpy rfft2 / irfft2, no code in common
@@ -541,3 +565,126 @@ def test_rbrief_table_second_transcription():
     from oracle import oracle as O
     O.build()
     assert O.orb_pattern().reshape(-1).tolist() == vals
+
+
+def _det_sincos_sweep_chunk(oracle, lo, hi):
+    """Angles with float32 bit patterns [lo, hi) in degrees, as both users form them: x = (double)(float)(deg * (float)(pi / 180)).
+    -> (x of every candidate, [sin, cos] of det_sincos there, numpy's [sin, cos] there, how many angles were screened).  A candidate is an
+    angle where the float32 rounding of det_sincos differs from that of numpy's float64 sin / cos, or where numpy's value lies within 16
+    double ulps of a float32 rounding midpoint (within that distance numpy's own error could put it on the wrong side)."""
+    x = (np.arange(lo, hi, dtype=np.uint32).view(np.float32) * np.float32(np.pi / 180)).astype(np.float64)
+    det = np.empty((len(x), 2), np.float64)
+    oracle.lib().orc_det_sincos(oracle._p(x), len(x), oracle._p(det))
+    cand = np.zeros(len(x), bool)
+    for j, f in ((0, np.sin), (1, np.cos)):
+        ref = f(x)
+        cand |= det[:, j].astype(np.float32) != ref.astype(np.float32)
+        # a double's rounding to float32 (normal range) is decided by its low 29 significand bits; the midpoint is 1 << 28
+        low = ref.view(np.int64) & ((1 << 29) - 1)
+        cand |= np.abs(low - (1 << 28)) <= 16
+        tiny = np.nonzero(np.abs(ref) < 2.0 ** -126)[0]          # float32 subnormal range: midpoints from the float32 neighbours
+        if len(tiny):
+            r = ref[tiny]; r32 = r.astype(np.float32)
+            nb = np.nextafter(r32, np.where(r > r32, np.float32(np.inf), np.float32(-np.inf)))
+            cand[tiny] |= np.abs(r - (r32.astype(np.float64) + nb.astype(np.float64)) * 0.5) <= 16 * np.spacing(np.abs(r))
+    idx = np.nonzero(cand)[0]
+    return x[idx], det[idx], np.stack([np.sin(x[idx]), np.cos(x[idx])], 1), len(x)
+
+
+def _f32_correctly_rounded(v):
+    """float32 nearest to the mpf v (200 bits): its float32 neighbours' midpoints are exact doubles, so v is compared with them, never
+    rounded to double first.  A tie cannot occur for sin / cos of a nonzero double; it is refused rather than resolved."""
+    import mpmath
+    f = np.float32(float(v))
+    for _ in range(2):
+        lo = (float(f) + float(np.nextafter(f, np.float32(-np.inf)))) * 0.5
+        hi = (float(f) + float(np.nextafter(f, np.float32(np.inf)))) * 0.5
+        assert v != mpmath.mpf(lo) and v != mpmath.mpf(hi), v
+        if v < mpmath.mpf(lo):
+            f = np.nextafter(f, np.float32(-np.inf))
+        elif v > mpmath.mpf(hi):
+            f = np.nextafter(f, np.float32(np.inf))
+        else:
+            return f
+    raise AssertionError(("no float32 neighbour found", v))
+
+
+def test_det_sincos_equals_correctly_rounded_sin_cos_on_every_path_angle(oracle):
+    """det_sincos (oracle/vfsms_oracle.h; the device copy is imagestitch_amd/csrc/detmath.h) rotates the SURF descriptor window and the ORB
+    rBRIEF pattern.  Every descriptor test compares engine with oracle, and both carry the same algorithm, so a slip made in both would pass
+    them all.  This holds the oracle's copy against the mathematical sin / cos on EVERY angle those paths can feed it: each float32 `deg`
+    in [0, 360] (bit patterns 0 .. 0x43B40000, 1,135,869,953 angles) turned into x = (double)(float)(deg * (float)(pi / 180)).  Two targets:
+      SURF, std::sin(float) / std::cos(float): (float)det_sin(x) is the correctly rounded float32 of sin(x), likewise cos;
+      ORB, (float)cos(double) / (float)sin(double): (float)det_cos(x) is the float32 rounding of the correctly rounded double of cos(x).
+    numpy's float64 sin / cos screen the angles; the candidates (a float32 disagreement, or numpy within 16 double ulps of a float32
+    rounding midpoint) are settled with mpmath at 200 bits.  detmath.h's claim is that none of them is an exception, and none may be."""
+    import mpmath
+    from concurrent.futures import ThreadPoolExecutor
+    from mpmath.libmp import to_float
+    END, CHUNK = 0x43B40000 + 1, 1 << 22
+    assert np.float32(np.uint32(0x43B40000).view(np.float32)) == np.float32(360)
+    with ThreadPoolExecutor(max_workers=pool_size()) as ex:
+        parts = list(ex.map(lambda lo: _det_sincos_sweep_chunk(oracle, lo, min(lo + CHUNK, END)), range(0, END, CHUNK)))
+    assert sum(p[3] for p in parts) == END == 1135869953
+    xs = np.concatenate([p[0] for p in parts]); det = np.concatenate([p[1] for p in parts]); npv = np.concatenate([p[2] for p in parts])
+    # the sweep finds a few dozen; tens of thousands mean the algorithm has changed, and settling them all would only take longer
+    assert len(xs) <= 20000, ("det_sincos disagrees with numpy's float64 sin / cos on too many angles", len(xs))
+    # the screen's premise -- numpy within 16 double ulps of the true value -- on the candidates and on samples of all angles (uniform in
+    # bit pattern, which favours small angles, and uniform in degrees)
+    rng = np.random.default_rng(0)
+    deg = np.concatenate([rng.integers(0, END, 1024, dtype=np.uint32).view(np.float32), rng.uniform(0, 360, 1024).astype(np.float32)])
+    sample = (deg * np.float32(np.pi / 180)).astype(np.float64)
+    exceptions = []
+    with mpmath.workprec(200):
+        def exact(x):
+            return mpmath.sin(mpmath.mpf(float(x))), mpmath.cos(mpmath.mpf(float(x)))
+
+        def premise(x, v, ref):
+            assert abs(v - mpmath.mpf(float(ref))) < 16 * np.spacing(abs(ref)), (float(x), float(ref))
+        for x, d, ref in zip(xs, det, npv):
+            for j, v in enumerate(exact(x)):
+                premise(x, v, ref[j])
+                got = np.float32(d[j])
+                surf = _f32_correctly_rounded(v)                      # std::sin(float): one rounding, straight to float32
+                orb = np.float32(to_float(v._mpf_, rnd="n"))           # (float)cos(double): nearest double, then float32
+                if got != surf or got != orb:
+                    exceptions.append((float(x), "sin" if j == 0 else "cos", float(got), float(surf), float(orb)))
+        for x in sample:
+            for v, ref in zip(exact(x), (np.sin(x), np.cos(x))):
+                premise(x, v, ref)
+    print("det_sincos: %d candidates settled with mpmath, %d exceptions" % (len(xs), len(exceptions)))
+    assert exceptions == []
+
+
+def test_det_sincos_device_and_oracle_copies_agree():
+    """The sweep above checks the oracle's det_sincos; the device's copy (imagestitch_amd/csrc/detmath.h) is held to it only on the angles
+    the descriptor tests happen to produce.  Both copies must carry the same 15 double constants, the same reduction and polynomial
+    expressions, and the same quadrant table."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ["INV_PIO2", "PIO2_HI", "PIO2_LO"] + ["S%d" % k for k in range(1, 7)] + ["C%d" % k for k in range(1, 7)]
+
+    def body(path):
+        txt = open(os.path.join(root, path)).read()
+        start = txt.index("void det_sincos(")
+        return txt[start:txt.index("\n}", start)]
+
+    def parse(b):
+        consts = {}
+        for name in names:
+            m = re.findall(r"\b%s\s*=\s*([-+0-9.eE]+)\s*[,;]" % name, b)
+            assert len(m) == 1, (name, m)
+            consts[name] = m[0]
+        cases = re.findall(r"(case \d|default):\s*s\s*=\s*(-?\w+);\s*c\s*=\s*(-?\w+);\s*break;", b)
+        exprs = [re.sub(r"\s+", "", m) for m in re.findall(r"const double (?:ps|sr|pc|cr|r|z) = ([^;]+);", b)]
+        return consts, cases, exprs
+    dev, orc = parse(body("imagestitch_amd/csrc/detmath.h")), parse(body("oracle/vfsms_oracle.h"))
+    assert dev[0] == orc[0]
+    assert [float(dev[0][n]) for n in names] == [float(orc[0][n]) for n in names]
+    assert dev[1] == orc[1] == [("case 0", "sr", "cr"), ("case 1", "cr", "-sr"), ("case 2", "-sr", "-cr"), ("default", "-cr", "sr")]
+    assert dev[2] == orc[2] and len(dev[2]) == 6
+    # 2 / pi, and pi / 2 split as documented: PIO2_HI has at most 33 significant bits (a multiple of 2^-32 in [1, 2)), so that k * PIO2_HI
+    # and x - k * PIO2_HI are exact for the float-valued |x| <= 2^10 of these paths
+    hi, lo = float(dev[0]["PIO2_HI"]), float(dev[0]["PIO2_LO"])
+    assert float(dev[0]["INV_PIO2"]) == 2 / np.pi
+    assert 1 <= hi < 2 and hi * 2.0 ** 32 == int(hi * 2.0 ** 32) and hi + lo == np.pi / 2
