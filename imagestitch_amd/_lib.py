@@ -32,6 +32,11 @@ class OrbParams(C.Structure):
                 ("fast_threshold", C.c_int32)]
 
 
+class SiftParams(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("n_octave_layers", C.c_int32), ("contrast_threshold", C.c_double),
+                ("edge_threshold", C.c_double), ("sigma", C.c_double)]
+
+
 class AttemptKey(C.Structure):
     _fields_ = [("pair", C.c_int32), ("direction", C.c_int32), ("i", C.c_int32)]
 
@@ -91,6 +96,10 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_orb_detect_describe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OrbParams),
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vfsms_sift_detect_describe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SiftParams),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vfsms_sift_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SiftParams),
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_attempt_orb_batch": (C.c_int, [C.c_void_p, C.POINTER(RoiPair), C.c_int, C.POINTER(OrbParams), C.c_int, C.c_int, C.c_void_p]),
     "vfsms_bf_l2_knn2_ratio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                          C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -396,6 +405,54 @@ class Engine:
         if full:
             return kxy[:n].copy(), desc[:n].copy(), kfull[:n].copy()
         return kxy[:n].copy(), desc[:n].copy()
+
+    @staticmethod
+    def sift_params(n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6, n_features=0):
+        """cv2.xfeatures2d.SIFT_create() defaults; n_features > 0 (retainBest) is refused by the library"""
+        return SiftParams(int(n_features), int(n_octave_layers), float(contrast_threshold), float(edge_threshold), float(sigma))
+
+    def sift_detect_describe(self, img, params=None, cap=None, full=False):
+        """-> (kps float32[N, 2], desc float32[N, 128]) [+ KP_DTYPE keypoints if full], keypoints in detection order"""
+        img = _u8_2d(img)
+        h, w = img.shape
+        params = params or self.sift_params()
+        cap = cap or (h * w // 16 + 4096)
+        kxy = np.empty((cap, 2), np.float32)
+        desc = np.empty((cap, 128), np.float32)
+        kfull = np.empty(cap, KP_DTYPE) if full else None
+        n = C.c_int()
+        self._check(self.lib.vfsms_sift_detect_describe(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params),
+                                                        _ptr(kxy), _ptr(desc), _ptr(kfull), cap, C.byref(n)))
+        n = n.value
+        if full:
+            return kxy[:n].copy(), desc[:n].copy(), kfull[:n].copy()
+        return kxy[:n].copy(), desc[:n].copy()
+
+    def sift_pyramid(self, img, params=None):
+        """-> (gauss, dog): per octave a list of float32 levels (n_octave_layers + 3 Gaussian, n_octave_layers + 2 DoG)"""
+        img = _u8_2d(img)
+        h, w = img.shape
+        params = params or self.sift_params()
+        shapes = np.zeros((32, 2), np.int32)
+        nref = C.c_int()
+        self._check(self.lib.vfsms_sift_pyramid(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params), None, None, 0,
+                                                _ptr(shapes), 32, C.byref(nref)))
+        no = nref.value
+        L = params.n_octave_layers
+        gn = sum((L + 3) * int(r) * int(c) for r, c in shapes[:no])
+        dn = sum((L + 2) * int(r) * int(c) for r, c in shapes[:no])
+        g = np.empty(max(gn, 1), np.float32)
+        d = np.empty(max(dn, 1), np.float32)
+        self._check(self.lib.vfsms_sift_pyramid(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params), _ptr(g), _ptr(d), g.size,
+                                                _ptr(shapes), 32, C.byref(nref)))
+        gauss, dog, go, do = [], [], 0, 0
+        for r, c in shapes[:no]:
+            r, c = int(r), int(c)
+            gauss.append([g[go + i * r * c:go + (i + 1) * r * c].reshape(r, c).copy() for i in range(L + 3)])
+            dog.append([d[do + i * r * c:do + (i + 1) * r * c].reshape(r, c).copy() for i in range(L + 2)])
+            go += (L + 3) * r * c
+            do += (L + 2) * r * c
+        return gauss, dog
 
     def attempt_orb_batch(self, jobs, params=None, max_dist=-1, offset_evaluate=3):
         n = len(jobs)

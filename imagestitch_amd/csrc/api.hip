@@ -252,6 +252,8 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
+    if (ctx->sift_scratch) hipFree(ctx->sift_scratch);
+    if (ctx->sift_kp) hipFree(ctx->sift_kp);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->d_layers) hipFree(ctx->d_layers);
     if (ctx->d_tables) hipFree(ctx->d_tables);
@@ -1847,6 +1849,32 @@ extern "C" int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     return VFSMS_OK;
+}
+
+// ---- SIFT (sift_kernels.hip) -----------------------------------------------------------------------------------------------------
+extern "C" int vfsms_sift_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride, const vfsms_sift_params *params,
+                                          float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out)
+{
+    CTX_ENTER(ctx);
+    if (!img || !params || !n_out || h <= 0 || w <= 0 || stride < w || cap < 0) { vfsms_set_error("sift: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    *n_out = 0;
+    TRY(sift_check_params(params));
+    TRY(ctx_arena_reserve(ctx, (size_t)h * w + 65536));
+    uint8_t *d_img;
+    TRY(upload_image(ctx, img, h, w, stride, &d_img));
+    return sift_detect_describe_device(ctx, d_img, h, w, params, kps_xy, desc, kps_full, cap, n_out);
+}
+
+extern "C" int vfsms_sift_pyramid(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride, const vfsms_sift_params *params,
+                                  float *gauss, float *dog, size_t cap_floats, int32_t *shapes, int shapes_cap, int *n_octaves)
+{
+    CTX_ENTER(ctx);
+    if (!img || !params || !shapes || !n_octaves || h <= 0 || w <= 0 || stride < w) { vfsms_set_error("sift_pyramid: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(sift_check_params(params));
+    TRY(ctx_arena_reserve(ctx, (size_t)h * w + 65536));
+    uint8_t *d_img;
+    TRY(upload_image(ctx, img, h, w, stride, &d_img));
+    return sift_pyramid_device(ctx, d_img, h, w, params, gauss, dog, cap_floats, shapes, shapes_cap, n_octaves);
 }
 
 extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,

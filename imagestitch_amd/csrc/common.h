@@ -200,7 +200,9 @@ struct vfsms_ctx {
     size_t tile_pool_bytes = 0;
     std::vector<hipEvent_t> event_pool;
     std::unordered_map<int64_t, CanvasRec> canvases;
-    void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
+    void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;
+    void *sift_scratch = nullptr; size_t sift_scratch_bytes = 0;   // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
+    void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
     CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a batch (vfsms_features_surf_batch), freed with its last set
@@ -285,6 +287,15 @@ struct SeamGeom;
 int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
                     const SeamGeom &G, int levels);
 int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, const SeamGeom &G, int levels, uint8_t *d_out);
+
+// sift_kernels.hip
+#define VFSMS_SIFT_MAX_LAYERS 8
+#define VFSMS_SIFT_MAX_OCT 16
+int sift_check_params(const vfsms_sift_params *p);
+int sift_detect_describe_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
+                                float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out);
+int sift_pyramid_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
+                        float *gauss, float *dog, size_t cap_floats, int32_t *shapes, int shapes_cap, int *n_oct);
 
 #ifdef __HIPCC__
 // Speed only (placement is not a contract): workgroups are observed to land on XCD (linear block id % 8), each XCD with a private

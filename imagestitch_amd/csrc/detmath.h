@@ -43,3 +43,28 @@ __device__ __forceinline__ void det_sincos(double x, double *s_out, double *c_ou
     }
     *s_out = s; *c_out = c;
 }
+
+// det_exp -- exp in double with the same kind of fixed operation order, for the SIFT path (sift_kernels.hip; the numpy
+// specification tests/sift_ref.py carries a float64 copy).  Every expf / powf of upstream SIFT (the Gaussian window weights of the
+// orientation histogram and of the descriptor, the 2^((layer + xi) / nOctaveLayers) of the keypoint size) goes through it:
+//   k = rint(x * INVLN2);  hi = x - k * LN2_HI;  lo = k * LN2_LO;  r = hi - lo      (Cody-Waite; LN2_HI has 32 significant bits)
+//   c = r - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5)))),  t = r * r            (fdlibm __ieee754_exp, Horner form)
+//   y = 1 - ((lo - (r * c) / (2 - c)) - hi);  result = y * 2^k (ldexp, exact)
+// For the float-valued arguments of this path (|x| <= 88) the float rounding of the result equals the correctly rounded expf(x);
+// tests/test_sift_host.py checks every float32 x the path can form.
+__device__ __forceinline__ double det_exp(double x)
+{
+    const double INVLN2 = 1.44269504088896338700e+00;
+    const double LN2_HI = 6.93147180369123816490e-01;      // first 32 bits of ln 2
+    const double LN2_LO = 1.90821492927058770002e-10;      // ln 2 - LN2_HI
+    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
+                 P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+    const double kd = rint(x * INVLN2);
+    const double hi = x - kd * LN2_HI;
+    const double lo = kd * LN2_LO;
+    const double r = hi - lo;
+    const double t = r * r;
+    const double c = r - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+    return ldexp(y, (int)kd);
+}

@@ -72,6 +72,12 @@ class Method():
     orbBlurForDescriptor = False
     orbMaxDistance = 30
 
+    # ---- SIFT parameters: cv2.xfeatures2d.SIFT_create() defaults (ImageUtility.py:256,268; the reference passes none) ----
+    siftNOctaveLayers = 3
+    siftContrastThreshold = 0.04
+    siftEdgeThreshold = 10
+    siftSigma = 1.6
+
     # ---- registration (ImageUtility.py:42-44) ----
     offsetCaculate = "mode"     # "mode" or "ransac"
     offsetEvaluate = 3
@@ -151,8 +157,16 @@ class Method():
         return self.engine.orb_params(self.orbNfeatures, self.orbScaleFactor, self.orbNlevels, self.orbEdgeThreshold,
                                       self.orbFirstLevel, self.orbWTA_K, 0, self.orbPatchSize, self.orbFastThreshold)
 
+    def _siftParams(self):
+        """cv2.xfeatures2d.SIFT_create() -- ImageUtility.py:256,268 (both backends of the reference create SIFT without arguments)"""
+        return self.engine.sift_params(self.siftNOctaveLayers, self.siftContrastThreshold, self.siftEdgeThreshold, self.siftSigma)
+
     def detectAndDescribe(self, image, featureMethod):
-        """ImageUtility.py:248-276 -> (kps float32[N,2] of (x, y), features float32[N,D] or None)."""
+        """ImageUtility.py:248-276 -> (kps float32[N,2] of (x, y), features float32[N,D] or None).
+
+        "sift" runs csrc/sift_kernels.hip: OpenCV 3.3.1's SIFT_Impl arithmetic with SIFT_create() defaults, in the evaluation order that
+        tests/sift_ref.py specifies (the device output equals that numpy restatement bit for bit).  No byte parity with cv2 is claimed:
+        OpenCV's own float blur depends on whether its IPP / SIMD paths are compiled in."""
         if featureMethod == "surf":
             kps, feats = self.engine.surf_detect_describe(np.asarray(image), self._surfParams())
             if len(kps) == 0:
@@ -163,7 +177,12 @@ class Method():
             if len(kps) == 0:
                 return (np.float32([]), None)
             return (kps, feats)
-        raise NotImplementedError("featureMethod %r is outside the VFSMS hot path (sift is CPU-only in the reference too)" % (featureMethod,))
+        if featureMethod == "sift":
+            kps, feats = self.engine.sift_detect_describe(np.asarray(image), self._siftParams())
+            if len(kps) == 0:
+                return (np.float32([]), None)
+            return (kps, feats)
+        raise NotImplementedError("featureMethod %r is outside the VFSMS hot path" % (featureMethod,))
 
     def matchDescriptors(self, featuresA, featuresB):
         """ImageUtility.py:278-309 -> [(trainIdx, queryIdx)] in query order."""

@@ -63,6 +63,14 @@ typedef struct {
     int32_t n_levels, edge_threshold, first_level, wta_k, score_type, patch_size, fast_threshold;
 } vfsms_orb_params;
 
+/* SIFT parameters: cv2.xfeatures2d.SIFT_create() defaults (ImageUtility.py:256,268) are {0, 3, 0.04, 10, 1.6}.
+ * Supported: n_features 0 (retainBest is not), n_octave_layers 1..8.                                                               */
+typedef struct {
+    int32_t n_features;
+    int32_t n_octave_layers;
+    double contrast_threshold, edge_threshold, sigma;
+} vfsms_sift_params;
+
 /* One ROI attempt of the incremental search (Stitcher.py:319-351): ROI rectangles inside two
  * device-resident tiles, as Method.getROIRegionForIncreMethod (ImageUtility.py:66-101) slices them. */
 typedef struct {
@@ -185,6 +193,17 @@ int vfsms_surf_detect(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stri
 int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride,
                               const vfsms_orb_params *params,
                               float *kps_xy, uint8_t *desc, vfsms_keypoint *kps_full, int cap, int *n_out);
+
+/* cv2 SIFT detectAndCompute (ImageUtility.py:256,262) as specified by tests/sift_ref.py (OpenCV 3.3.1's SIFT_Impl arithmetic in a fixed
+ * evaluation order; no byte parity with cv2 is claimed).  kps_xy: float32[cap][2]; desc: float32[cap][128] of u8 values; kps_full
+ * optional (class_id -1).  Keypoints in detection order (octave, layer, row, column, peak bin), duplicates removed (first kept).       */
+int vfsms_sift_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride, const vfsms_sift_params *params,
+                               float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out);
+/* the Gaussian and DoG pyramids of the same call, for staged parity checks.  shapes: int32[shapes_cap][2] = (rows, cols) of each octave;
+ * gauss: octave after octave, n_octave_layers + 3 levels of rows x cols floats each; dog likewise with n_octave_layers + 2 levels.
+ * gauss == dog == NULL: only *n_octaves and shapes are filled.  cap_floats bounds gauss (dog needs fewer).                           */
+int vfsms_sift_pyramid(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride, const vfsms_sift_params *params,
+                       float *gauss, float *dog, size_t cap_floats, int32_t *shapes, int shapes_cap, int *n_octaves);
 
 /* replaces myGpuFeatures.matchDescriptors(featureType 1|2, param=ratio) (appendix/myGpuFeatures.cpp:160-173)
  * and BFMatcher("BruteForce").knnMatch(k=2) + ratio filter (ImageUtility.py:288-296).
