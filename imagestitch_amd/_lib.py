@@ -416,10 +416,10 @@ class Engine:
         img = _u8_2d(img)
         h, w = img.shape
         params = params or self.sift_params()
-        cap = cap or (h * w // 16 + 4096)
-        kxy = np.empty((cap, 2), np.float32)
-        desc = np.empty((cap, 128), np.float32)
-        kfull = np.empty(cap, KP_DTYPE) if full else None
+        cap = (h * w // 16 + 4096) if cap is None else int(cap)
+        kxy = np.empty((max(cap, 1), 2), np.float32)
+        desc = np.empty((max(cap, 1), 128), np.float32)
+        kfull = np.empty(max(cap, 1), KP_DTYPE) if full else None
         n = C.c_int()
         self._check(self.lib.vfsms_sift_detect_describe(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params),
                                                         _ptr(kxy), _ptr(desc), _ptr(kfull), cap, C.byref(n)))

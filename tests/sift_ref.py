@@ -372,8 +372,8 @@ def orientation_hist(img, px, py, radius, sigma):
     return hist
 
 
-def peaks(hist):
-    """-> angles of the histogram's peaks in bin order"""
+def peaks(hist, stats=None):
+    """-> angles of the histogram's peaks in bin order; stats (a dict), if given, counts in "angle_reset" the angles set to 0"""
     n = ORI_HIST_BINS
     omax = hist.max()
     mag_thr = F(omax * F(0.8))
@@ -388,12 +388,16 @@ def peaks(hist):
             a = F(360) - F(F(10) * b)
             if abs(F(a - F(360))) < FLT_EPSILON:
                 a = F(0)
+                if stats is not None:
+                    stats["angle_reset"] = stats.get("angle_reset", 0) + 1
             out.append(F(a))
     return out
 
 
-def detect(gauss, dog, p):
-    """findScaleSpaceExtrema + removeDuplicated + the firstOctave = -1 adjustment -> KP_DTYPE array in detection order"""
+def detect(gauss, dog, p, stats=None):
+    """findScaleSpaceExtrema + removeDuplicated + the firstOctave = -1 adjustment -> KP_DTYPE array in detection order.
+    stats (a dict), if given, receives what the output does not show: "rows_before" / "rows_after" removeDuplicated, "orientations" (the
+    number of peaks of each candidate, in candidate order) and "angle_reset" (angles within FLT_EPSILON of 360 set to 0)."""
     L = p.n_octave_layers
     rows = []
     for o in range(len(gauss)):
@@ -404,7 +408,10 @@ def detect(gauss, dog, p):
             scl = F(F(k["size"][q] * F(0.5)) / F(1 << o))
             img = gauss[o][int(k["l"][q])]
             hist = orientation_hist(img, int(k["c"][q]), int(k["r"][q]), int(cv_round(F(4.5) * scl)), F(F(1.5) * scl))
-            for a in peaks(hist):
+            pk = peaks(hist, stats)
+            if stats is not None:
+                stats.setdefault("orientations", []).append(len(pk))
+            for a in pk:
                 rows.append((k["x"][q], k["y"][q], k["size"][q], a, k["response"][q], int(k["octave"][q])))
     seen = set()
     kept = []
@@ -414,6 +421,10 @@ def detect(gauss, dog, p):
             continue
         seen.add(key)
         kept.append(t)
+    if stats is not None:
+        stats["rows_before"], stats["rows_after"] = len(rows), len(kept)
+        stats.setdefault("orientations", [])
+        stats.setdefault("angle_reset", 0)
     kps = np.zeros(len(kept), KP_DTYPE)
     for q, (x, y, size, a, resp, octv) in enumerate(kept):
         kps[q] = (F(x * F(0.5)), F(y * F(0.5)), F(size * F(0.5)), a, resp, (octv & ~255) | ((octv - 1) & 255), -1)
