@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <map>
+#include <tuple>
 
 int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy,
                     uint8_t *d_out, int32_t *info, int method = 0, int levels = 4);
@@ -991,6 +993,46 @@ static int resolve_job(vfsms_ctx *ctx, const vfsms_roi_pair &j, const uint8_t **
     return VFSMS_OK;
 }
 
+// ---- strip table of a fused batch -----------------------------------------------------------------------------------------------
+// The 2n ROI slots of a batch (job ord[s]'s A strip, its B strip) name fewer distinct strips: at a turn of the serpentine path the
+// failed direction-1 attempt's B strip is the next pair's direction-3 A strip, and both are in the batch (28 of the bench grid's 242
+// strips).  Detecting and describing a strip depends on its pixels alone, so each distinct strip is carved and run once and the match
+// blocks of every job that uses it read it.  The key is the strip's first pixel (after the tile's stride), its stride and its shape, not
+// the tile handle: vfsms_tile_wrap can give one buffer two handles.  Scope: one call; nothing is kept across calls.
+// A strip's part is that of the first slot that uses it (slots < n0: part 0), so part 1's jobs may read part-0 strips -- described
+// before part 0's search, in stream order -- and never the other way round.  Slots run in (shape) order and a strip has its job's shape,
+// so the order of first use is already the (part, shape) order the shape-run launchers need.
+// VFSMS_STRIP_DEDUP=0 carves every slot a strip of its own (2s, 2s + 1: the layout before the table) for A/B runs.
+struct StripTable {
+    struct Strip { const uint8_t *p; int stride, h, w; };
+    std::vector<Strip> strips;               // distinct strips in launch order
+    std::vector<int> a, b;                   // per slot: its A / B strip
+    int u0 = 0;                              // strips of part 0 (the first u0)
+};
+static int build_strip_table(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, const int *ord, int n, int n0, StripTable *T)
+{
+    static const bool dedup = !(getenv("VFSMS_STRIP_DEDUP") && atoi(getenv("VFSMS_STRIP_DEDUP")) == 0);
+    std::map<std::tuple<const uint8_t *, int, int, int>, int> seen;
+    T->strips.clear(); T->a.assign(n, 0); T->b.assign(n, 0); T->u0 = 0;
+    auto strip_of = [&](const uint8_t *p, int stride, int h, int w) {
+        if (dedup) {
+            auto it = seen.emplace(std::make_tuple(p, stride, h, w), (int)T->strips.size());
+            if (!it.second) return it.first->second;
+        }
+        T->strips.push_back(StripTable::Strip{p, stride, h, w});
+        return (int)T->strips.size() - 1;
+    };
+    for (int s = 0; s < n; s++) {
+        const vfsms_roi_pair &j = jobs[ord[s]];
+        const uint8_t *pa, *pb; int sa, sb;
+        TRY(resolve_job(ctx, j, &pa, &sa, &pb, &sb));
+        T->a[s] = strip_of(pa, sa, j.h, j.w);
+        T->b[s] = strip_of(pb, sb, j.h, j.w);
+        if (s == n0 - 1) T->u0 = (int)T->strips.size();
+    }
+    return VFSMS_OK;
+}
+
 extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out)
 {
     CTX_ENTER(ctx);
@@ -1066,7 +1108,7 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     if (n == 0) return VFSMS_OK;
     TRY(ctx_prepare_surf(ctx, params));
     const int dim = params->extended ? 128 : 64;
-    size_t need = 0; int maxcap = 0;
+    int maxcap = 0;
     std::vector<int> caps(n);
     for (int k = 0; k < n; k++) {
         caps[k] = kp_capacity(ctx, jobs[k].h, jobs[k].w);
@@ -1077,54 +1119,6 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     const bool filtered = dim == 64 && !bf_force_exact();
     const int cns = pick_filter_nsplit(maxcap * 2 / 3, n, maxcap * 2 / 3);   // the registrar sizes the capacity at 1.5x the largest ROI seen
     const int ns = filtered ? 1 : pick_nsplit(maxcap / 3, maxcap / 3, n, dim);   // typical occupancy of the capacity
-    for (int k = 0; k < n; k++)
-        need += 2 * surf_roi_bytes(jobs[k].h, jobs[k].w, caps[k], ctx->n_layers, params->n_octaves, dim) + match_bytes(caps[k], ns) +
-                (filtered ? match_filter_bytes(caps[k], caps[k], cns) : 0);
-    need += (sizeof(RoiDev) * 2 + sizeof(MatchDev)) * n + 64 * 3 * n + 65536;
-    if (enh_mode) for (int k = 0; k < n; k++) need += 2 * enhance_scratch_bytes(jobs[k].h, jobs[k].w, enh_mode, tile_grid) + 2 * sizeof(EnhJob) + 512;
-    TRY(ctx_arena_reserve(ctx, need));
-    ctx->pinned_off = 0;
-    std::vector<RoiDev> R(2 * n);
-    std::vector<EnhJob> E(enh_mode ? 2 * n : 0);
-    std::vector<MatchDev> M(n);
-    // counters of all ROIs and results of all jobs live in two contiguous blocks: one memset, two D2H copies per batch
-    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * 2 * n);
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-    // ROIs of one shape next to each other (the column strips, then the strips of the turn candidates): the kernels whose grid follows the
-    // image size are launched per shape run (surf_kernels.hip: shape_runs).  Slot s of the batch holds job ord[s]; results go to the job's row.
-    std::vector<int> ord(n);
-    for (int k = 0; k < n; k++) ord[k] = k;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
-        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
-    for (int s_ = 0; s_ < n; s_++) {
-        const int k = ord[s_];
-        const uint8_t *pa, *pb; int sa, sb;
-        TRY(resolve_job(ctx, jobs[k], &pa, &sa, &pb, &sb));
-        if (enh_mode) {            // Stitcher.py:327-334: the ROI strips are equalised / CLAHE'd before detectAndDescribe
-            TRY(enhance_carve(ctx, &E[2 * s_], pa, sa, jobs[k].h, jobs[k].w, enh_mode, tile_grid));
-            TRY(enhance_carve(ctx, &E[2 * s_ + 1], pb, sb, jobs[k].h, jobs[k].w, enh_mode, tile_grid));
-            pa = E[2 * s_].dst; sa = jobs[k].w; pb = E[2 * s_ + 1].dst; sb = jobs[k].w;
-        }
-        TRY(surf_roi_carve(ctx, &R[2 * s_], pa, sa, jobs[k].h, jobs[k].w, caps[k], params));
-        TRY(surf_roi_carve(ctx, &R[2 * s_ + 1], pb, sb, jobs[k].h, jobs[k].w, caps[k], params));
-        R[2 * s_].counters = cblock + 16 * (2 * s_); R[2 * s_ + 1].counters = cblock + 16 * (2 * s_ + 1);
-        memset(&M[s_], 0, sizeof(MatchDev));
-        TRY(match_carve(ctx, &M[s_], caps[k], dim, ns));
-        if (filtered) TRY(match_filter_carve(ctx, &M[s_], caps[k], caps[k], cns));
-        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-        M[s_].q = R[2 * s_].desc; M[s_].t = R[2 * s_ + 1].desc;
-        M[s_].nq_ptr = R[2 * s_].counters + 1; M[s_].nt_ptr = R[2 * s_ + 1].counters + 1;
-        M[s_].kq = R[2 * s_].kps_xy; M[s_].kt = R[2 * s_ + 1].kps_xy;
-    }
-    RoiDev *dR; MatchDev *dM;
-    TRY(upload_pinned(ctx, R.data(), sizeof(RoiDev) * 2 * n, (void **)&dR));
-    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-    if (enh_mode) {
-        EnhJob *dE;
-        TRY(upload_pinned(ctx, E.data(), sizeof(EnhJob) * 2 * n, (void **)&dE));
-        TRY(launch_enhance(ctx, dE, E.data(), 2 * n, enh_mode, clip_limit, tile_grid));
-    }
-    HIP_TRY(hipMemsetAsync(cblock, 0, sizeof(int) * 16 * 2 * n, ctx->stream));
     // Two pipes at once -- built, measured, OFF by default.  The 2-NN search lives on the matrix cores (k_bf_mfma16_d64: MFMA pipe 55-65 %
     // busy, VALU idle), detection on the VALU and the texture-address path.  With VFSMS_OVERLAP=1 a large batch is cut in two parts of
     // slots: part 0 (VFSMS_OVERLAP_PCT, default 70 %) is detected and described, then its search + ratio + vote run on the second stream
@@ -1138,9 +1132,66 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     static const bool overlap_on = getenv("VFSMS_OVERLAP") && atoi(getenv("VFSMS_OVERLAP")) != 0;
     static const int overlap_pct = getenv("VFSMS_OVERLAP_PCT") ? atoi(getenv("VFSMS_OVERLAP_PCT")) : 70;
     const int n0 = (overlap_on && filtered && n >= 12) ? std::min(n - 2, std::max(2, n * overlap_pct / 100)) : n;
+    // ROIs of one shape next to each other (the column strips, then the strips of the turn candidates): the kernels whose grid follows the
+    // image size are launched per shape run (surf_kernels.hip: shape_runs).  Slot s of the batch holds job ord[s]; results go to the job's row.
+    std::vector<int> ord(n);
+    for (int k = 0; k < n; k++) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
+        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    StripTable T;
+    TRY(build_strip_table(ctx, jobs, ord.data(), n, n0, &T));
+    const int u = (int)T.strips.size(), u0 = T.u0;
+    std::vector<int> scap(u);
+    size_t need = 0;
+    for (int i = 0; i < u; i++) {
+        const StripTable::Strip &S = T.strips[i];
+        scap[i] = kp_capacity(ctx, S.h, S.w);
+        need += surf_roi_bytes(S.h, S.w, scap[i], ctx->n_layers, params->n_octaves, dim);
+        if (enh_mode) need += enhance_scratch_bytes(S.h, S.w, enh_mode, tile_grid) + sizeof(EnhJob) + 256;
+    }
+    for (int k = 0; k < n; k++) need += match_bytes(caps[k], ns) + (filtered ? match_filter_bytes(caps[k], caps[k], cns) : 0);
+    need += sizeof(RoiDev) * u + sizeof(MatchDev) * n + 64 * (u + n) + 65536;
+    TRY(ctx_arena_reserve(ctx, need));
+    ctx->pinned_off = 0;
+    std::vector<RoiDev> R(u);
+    std::vector<EnhJob> E(enh_mode ? u : 0);
+    std::vector<MatchDev> M(n);
+    // counters of all strips and results of all jobs live in two contiguous blocks: one memset, two D2H copies per batch
+    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * u);
+    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
+    for (int i = 0; i < u; i++) {
+        const StripTable::Strip &S = T.strips[i];
+        const uint8_t *p = S.p; int stride = S.stride;
+        if (enh_mode) {            // Stitcher.py:327-334: the ROI strips are equalised / CLAHE'd before detectAndDescribe
+            TRY(enhance_carve(ctx, &E[i], p, stride, S.h, S.w, enh_mode, tile_grid));
+            p = E[i].dst; stride = S.w;
+        }
+        TRY(surf_roi_carve(ctx, &R[i], p, stride, S.h, S.w, scap[i], params));
+        R[i].counters = cblock + 16 * i;
+    }
+    for (int s_ = 0; s_ < n; s_++) {
+        const int k = ord[s_];
+        const RoiDev &A = R[T.a[s_]], &B = R[T.b[s_]];
+        memset(&M[s_], 0, sizeof(MatchDev));
+        TRY(match_carve(ctx, &M[s_], caps[k], dim, ns));
+        if (filtered) TRY(match_filter_carve(ctx, &M[s_], caps[k], caps[k], cns));
+        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
+        M[s_].q = A.desc; M[s_].t = B.desc;
+        M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
+        M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
+    }
+    RoiDev *dR; MatchDev *dM;
+    TRY(upload_pinned(ctx, R.data(), sizeof(RoiDev) * u, (void **)&dR));
+    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
+    if (enh_mode) {
+        EnhJob *dE;
+        TRY(upload_pinned(ctx, E.data(), sizeof(EnhJob) * u, (void **)&dE));
+        TRY(launch_enhance(ctx, dE, E.data(), u, enh_mode, clip_limit, tile_grid));
+    }
+    HIP_TRY(hipMemsetAsync(cblock, 0, sizeof(int) * 16 * u, ctx->stream));
     if (n0 < n) TRY(ctx_second_stream(ctx));
-    TRY(launch_surf_detect(ctx, dR, R.data(), 2 * n0, params));
-    TRY(launch_surf_describe(ctx, dR, R.data(), 2 * n0, params));
+    TRY(launch_surf_detect(ctx, dR, R.data(), u0, params));
+    TRY(launch_surf_describe(ctx, dR, R.data(), u0, params));
     SecondStreamJoin join_guard(ctx);
     if (n0 < n) {
         HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -1152,8 +1203,8 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
             TRY(launch_ratio_mode(ctx, dM, n0, maxcap, ratio, offset_evaluate));
             HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
         }
-        TRY(launch_surf_detect(ctx, dR + 2 * n0, R.data() + 2 * n0, 2 * (n - n0), params));
-        TRY(launch_surf_describe(ctx, dR + 2 * n0, R.data() + 2 * n0, 2 * (n - n0), params));
+        TRY(launch_surf_detect(ctx, dR + u0, R.data() + u0, u - u0, params));
+        TRY(launch_surf_describe(ctx, dR + u0, R.data() + u0, u - u0, params));
         TRY(launch_bf_l2_filtered(ctx, dM + n0, n - n0, maxcap, maxcap, cns));
         TRY(launch_ratio_mode(ctx, dM + n0, n - n0, maxcap, ratio, offset_evaluate));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
@@ -1163,13 +1214,14 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         else { TRY(launch_bf_l2(ctx, dM, n, maxcap, ns, dim)); }
         TRY(launch_ratio_mode(ctx, dM, n, maxcap, ratio, offset_evaluate));
     }
-    std::vector<int> counters((size_t)16 * 2 * n);
-    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 16 * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<int> counters((size_t)16 * u);
+    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 16 * u, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2 * n; k++)
-        if (counters[(size_t)16 * k + 2] || counters[(size_t)16 * k] > R[k].cap) {
-            vfsms_set_error("attempt_surf: ROI %d exceeded %d keypoint candidates (vfsms_ctx_set_keypoint_capacity)", k, R[k].cap);
+    for (int i = 0; i < u; i++)
+        if (counters[(size_t)16 * i + 2] || counters[(size_t)16 * i] > R[i].cap) {
+            vfsms_set_error("attempt_surf: strip %d of %d (%d x %d) exceeded %d keypoint candidates (vfsms_ctx_set_keypoint_capacity)",
+                            i, u, R[i].h, R[i].w, R[i].cap);
             return VFSMS_ERR_CAPACITY;
         }
     return VFSMS_OK;
@@ -1889,48 +1941,52 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
     // a wave owns 64 queries and walks its share of the trains: split the trains so that a batch fills the chip a few times over
     const long long hwaves = (long long)((c + 63) / 64) * n;
     const int hns = (int)std::max<long long>(1, std::min<long long>(8, (8192 + hwaves - 1) / hwaves));
-    size_t need = 0;
-    for (int k = 0; k < n; k++) need += 2 * orb_roi_bytes(params, jobs[k].h, jobs[k].w, c1, c2, c) + match_bytes(c, hns);
-    need += (sizeof(OrbDev) * 2 + sizeof(MatchDev)) * n + (64 * 2 + VFSMS_ATTEMPT_INTS) * sizeof(int) * (size_t)n + 65536;
-    TRY(ctx_arena_reserve(ctx, need));
-    std::vector<OrbDev> R(2 * n);
-    std::vector<MatchDev> M(n);
-    // counters of all ROIs and results of all jobs live in two contiguous blocks: two D2H copies per batch
-    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * 2 * n);
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-    // ROIs of one shape next to each other: the image-sized kernels are launched per shape run (launch_orb); slot s holds job ord[s]
+    // ROIs of one shape next to each other: the image-sized kernels are launched per shape run (launch_orb); slot s holds job ord[s];
+    // every distinct strip of the batch is carved and run once (build_strip_table)
     std::vector<int> ord(n);
     for (int k = 0; k < n; k++) ord[k] = k;
     std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
         return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    StripTable T;
+    TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
+    const int u = (int)T.strips.size();
+    size_t need = 0;
+    for (int i = 0; i < u; i++) need += orb_roi_bytes(params, T.strips[i].h, T.strips[i].w, c1, c2, c);
+    need += match_bytes(c, hns) * n;
+    need += sizeof(OrbDev) * u + sizeof(MatchDev) * n + (64 * u + VFSMS_ATTEMPT_INTS * n) * sizeof(int) + 65536;
+    TRY(ctx_arena_reserve(ctx, need));
+    std::vector<OrbDev> R(u);
+    std::vector<MatchDev> M(n);
+    // counters of all strips and results of all jobs live in two contiguous blocks: two D2H copies per batch
+    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * u);
+    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
+    for (int i = 0; i < u; i++) {
+        const StripTable::Strip &S = T.strips[i];
+        TRY(orb_roi_carve(ctx, &R[i], S.p, S.stride, S.h, S.w, params, c1, c2, c));
+        OrbDev &r = R[i];
+        r.counters = cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
+    }
     for (int s_ = 0; s_ < n; s_++) {
         const int k = ord[s_];
-        const uint8_t *pa, *pb; int sa, sb;
-        TRY(resolve_job(ctx, jobs[k], &pa, &sa, &pb, &sb));
-        TRY(orb_roi_carve(ctx, &R[2 * s_], pa, sa, jobs[k].h, jobs[k].w, params, c1, c2, c));
-        TRY(orb_roi_carve(ctx, &R[2 * s_ + 1], pb, sb, jobs[k].h, jobs[k].w, params, c1, c2, c));
-        for (int e = 0; e < 2; e++) {
-            OrbDev &r = R[2 * s_ + e];
-            r.counters = cblock + 64 * (2 * s_ + e); r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
-        }
+        const OrbDev &A = R[T.a[s_]], &B = R[T.b[s_]];
         memset(&M[s_], 0, sizeof(MatchDev));
         TRY(match_carve(ctx, &M[s_], c, 32, hns));
         M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-        M[s_].q = (const float *)R[2 * s_].desc; M[s_].t = (const float *)R[2 * s_ + 1].desc;
-        M[s_].nq_ptr = R[2 * s_].counters + 1; M[s_].nt_ptr = R[2 * s_ + 1].counters + 1;
-        M[s_].kq = R[2 * s_].kps_xy; M[s_].kt = R[2 * s_ + 1].kps_xy;
+        M[s_].q = (const float *)A.desc; M[s_].t = (const float *)B.desc;
+        M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
+        M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
     }
     ctx->pinned_off = 0;
     OrbDev *dR; MatchDev *dM;
-    TRY(upload_pinned(ctx, R.data(), sizeof(OrbDev) * 2 * n, (void **)&dR));
+    TRY(upload_pinned(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
     TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-    TRY(launch_orb(ctx, dR, R.data(), 2 * n, params));
+    TRY(launch_orb(ctx, dR, R.data(), u, params));
     TRY(launch_hamming_mode(ctx, dM, n, c, hns, max_dist, offset_evaluate));
-    std::vector<int> counters((size_t)64 * 2 * n);
-    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 64 * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<int> counters((size_t)64 * u);
+    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 64 * u, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2 * n; k++)
-        if (counters[(size_t)64 * k + 2]) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in ROI %d", k); return VFSMS_ERR_CAPACITY; }
+    for (int i = 0; i < u; i++)
+        if (counters[(size_t)64 * i + 2]) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", i, u); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
 }
