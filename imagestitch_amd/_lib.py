@@ -394,13 +394,21 @@ class Engine:
         img = _u8_2d(img)
         h, w = img.shape
         params = params or self.orb_params()
+        auto = not cap
         cap = cap or (2 * params.n_features + 2048)
-        kxy = np.empty((cap, 2), np.float32)
-        desc = np.empty((cap, 32), np.uint8)
-        kfull = np.empty(cap, KP_DTYPE) if full else None
-        n = C.c_int()
-        self._check(self.lib.vfsms_orb_detect_describe(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params),
-                                                       _ptr(kxy), _ptr(desc), _ptr(kfull), cap, C.byref(n)))
+        n = C.c_int(-1)
+        while True:
+            kxy = np.empty((cap, 2), np.float32)
+            desc = np.empty((cap, 32), np.uint8)
+            kfull = np.empty(cap, KP_DTYPE) if full else None
+            rc = self.lib.vfsms_orb_detect_describe(self.ctx, _ptr(img), h, w, img.strides[0], C.byref(params),
+                                                    _ptr(kxy), _ptr(desc), _ptr(kfull), cap, C.byref(n))
+            # ties keep more than n_features: with no cap given, run once more with the count the library reports
+            if auto and rc == VFSMS_ERR_CAPACITY and n.value > cap:
+                auto, cap = False, n.value
+                continue
+            self._check(rc)
+            break
         n = n.value
         if full:
             return kxy[:n].copy(), desc[:n].copy(), kfull[:n].copy()

@@ -1869,6 +1869,14 @@ static void orb_caps(const vfsms_orb_params *p, int *cap1, int *cap2, int *cap)
     const int q0 = (int)lrintf(p->n_features * (1 - factor) / (1 - powf(factor, (float)p->n_levels)));
     *cap1 = 4 * q0 + 2048; *cap2 = 2 * q0 + 1024; *cap = 2 * p->n_features + 2048;
 }
+// after an overflow: capacities that hold every keypoint of the strip whose counters these are.  counters[4 + l] is the true number of
+// survivors of level l's FAST-score cut (counted before any clamp); the quota cut keeps at most that many, the output at most their sum.
+static void orb_grow_caps(const int *counters, int nlevels, int *cap1, int *cap2, int *cap)
+{
+    int m = 0; long long sum = 0;
+    for (int l = 0; l < nlevels; l++) { m = std::max(m, counters[4 + l]); sum += counters[4 + l]; }
+    *cap1 = std::max(*cap1, m); *cap2 = std::max(*cap2, m); *cap = (int)std::max<long long>(*cap, sum);
+}
 
 extern "C" int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride,
                                          const vfsms_orb_params *params, float *kps_xy, uint8_t *desc,
@@ -1879,18 +1887,22 @@ extern "C" int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int
     TRY(ctx_prepare_orb(ctx, params));
     int c1, c2, c;
     orb_caps(params, &c1, &c2, &c);
-    TRY(ctx_arena_reserve(ctx, (size_t)h * w + orb_roi_bytes(params, h, w, c1, c2, c) + 65536));
-    uint8_t *d_img;
-    TRY(upload_image(ctx, img, h, w, stride, &d_img));
     OrbDev R;
-    TRY(orb_roi_carve(ctx, &R, d_img, w, h, w, params, c1, c2, c));
-    OrbDev *dR;
-    TRY(upload_array(ctx, &R, 1, &dR));
-    TRY(launch_orb(ctx, dR, &R, 1, params));
     int counters[16];
-    HIP_TRY(hipMemcpyAsync(counters, R.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (counters[2]) { vfsms_set_error("orb: internal keypoint capacity exceeded"); return VFSMS_ERR_CAPACITY; }
+    for (int pass = 0;; pass++) {          // ties can overflow the default capacities: one more run with exact ones, never a truncation
+        TRY(ctx_arena_reserve(ctx, (size_t)h * w + orb_roi_bytes(params, h, w, c1, c2, c) + 65536));
+        uint8_t *d_img;
+        TRY(upload_image(ctx, img, h, w, stride, &d_img));
+        TRY(orb_roi_carve(ctx, &R, d_img, w, h, w, params, c1, c2, c));
+        OrbDev *dR;
+        TRY(upload_array(ctx, &R, 1, &dR));
+        TRY(launch_orb(ctx, dR, &R, 1, params));
+        HIP_TRY(hipMemcpyAsync(counters, R.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (!counters[2]) break;
+        if (pass > 0) { vfsms_set_error("orb: internal keypoint capacity exceeded"); return VFSMS_ERR_CAPACITY; }
+        orb_grow_caps(counters, params->n_levels, &c1, &c2, &c);
+    }
     const int n = counters[1];
     *n_out = n;
     if (n > cap) { vfsms_set_error("orb: %d keypoints exceed the caller's capacity %d", n, cap); return VFSMS_ERR_CAPACITY; }
@@ -1938,9 +1950,6 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
     TRY(ctx_prepare_orb(ctx, params));
     int c1, c2, c;
     orb_caps(params, &c1, &c2, &c);
-    // a wave owns 64 queries and walks its share of the trains: split the trains so that a batch fills the chip a few times over
-    const long long hwaves = (long long)((c + 63) / 64) * n;
-    const int hns = (int)std::max<long long>(1, std::min<long long>(8, (8192 + hwaves - 1) / hwaves));
     // ROIs of one shape next to each other: the image-sized kernels are launched per shape run (launch_orb); slot s holds job ord[s];
     // every distinct strip of the batch is carved and run once (build_strip_table)
     std::vector<int> ord(n);
@@ -1950,43 +1959,52 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
     StripTable T;
     TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
     const int u = (int)T.strips.size();
-    size_t need = 0;
-    for (int i = 0; i < u; i++) need += orb_roi_bytes(params, T.strips[i].h, T.strips[i].w, c1, c2, c);
-    need += match_bytes(c, hns) * n;
-    need += sizeof(OrbDev) * u + sizeof(MatchDev) * n + (64 * u + VFSMS_ATTEMPT_INTS * n) * sizeof(int) + 65536;
-    TRY(ctx_arena_reserve(ctx, need));
-    std::vector<OrbDev> R(u);
-    std::vector<MatchDev> M(n);
-    // counters of all strips and results of all jobs live in two contiguous blocks: two D2H copies per batch
-    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * u);
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-    for (int i = 0; i < u; i++) {
-        const StripTable::Strip &S = T.strips[i];
-        TRY(orb_roi_carve(ctx, &R[i], S.p, S.stride, S.h, S.w, params, c1, c2, c));
-        OrbDev &r = R[i];
-        r.counters = cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
+    // ties can overflow the default capacities: the batch runs once more with capacities that hold every strip's keypoints
+    for (int pass = 0;; pass++) {
+        // a wave owns 64 queries and walks its share of the trains: split the trains so that a batch fills the chip a few times over
+        const long long hwaves = (long long)((c + 63) / 64) * n;
+        const int hns = (int)std::max<long long>(1, std::min<long long>(8, (8192 + hwaves - 1) / hwaves));
+        size_t need = 0;
+        for (int i = 0; i < u; i++) need += orb_roi_bytes(params, T.strips[i].h, T.strips[i].w, c1, c2, c);
+        need += match_bytes(c, hns) * n;
+        need += sizeof(OrbDev) * u + sizeof(MatchDev) * n + (64 * u + VFSMS_ATTEMPT_INTS * n) * sizeof(int) + 65536;
+        TRY(ctx_arena_reserve(ctx, need));
+        std::vector<OrbDev> R(u);
+        std::vector<MatchDev> M(n);
+        // counters of all strips and results of all jobs live in two contiguous blocks: two D2H copies per batch
+        int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * u);
+        int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
+        for (int i = 0; i < u; i++) {
+            const StripTable::Strip &S = T.strips[i];
+            TRY(orb_roi_carve(ctx, &R[i], S.p, S.stride, S.h, S.w, params, c1, c2, c));
+            OrbDev &r = R[i];
+            r.counters = cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
+        }
+        for (int s_ = 0; s_ < n; s_++) {
+            const int k = ord[s_];
+            const OrbDev &A = R[T.a[s_]], &B = R[T.b[s_]];
+            memset(&M[s_], 0, sizeof(MatchDev));
+            TRY(match_carve(ctx, &M[s_], c, 32, hns));
+            M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
+            M[s_].q = (const float *)A.desc; M[s_].t = (const float *)B.desc;
+            M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
+            M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
+        }
+        ctx->pinned_off = 0;
+        OrbDev *dR; MatchDev *dM;
+        TRY(upload_pinned(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
+        TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
+        TRY(launch_orb(ctx, dR, R.data(), u, params));
+        TRY(launch_hamming_mode(ctx, dM, n, c, hns, max_dist, offset_evaluate));
+        std::vector<int> counters((size_t)64 * u);
+        HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 64 * u, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        int over = -1;
+        for (int i = 0; i < u; i++)
+            if (counters[(size_t)64 * i + 2]) { over = i; if (pass == 0) orb_grow_caps(&counters[(size_t)64 * i], params->n_levels, &c1, &c2, &c); }
+        if (over < 0) break;
+        if (pass > 0) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", over, u); return VFSMS_ERR_CAPACITY; }
     }
-    for (int s_ = 0; s_ < n; s_++) {
-        const int k = ord[s_];
-        const OrbDev &A = R[T.a[s_]], &B = R[T.b[s_]];
-        memset(&M[s_], 0, sizeof(MatchDev));
-        TRY(match_carve(ctx, &M[s_], c, 32, hns));
-        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-        M[s_].q = (const float *)A.desc; M[s_].t = (const float *)B.desc;
-        M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
-        M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
-    }
-    ctx->pinned_off = 0;
-    OrbDev *dR; MatchDev *dM;
-    TRY(upload_pinned(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
-    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-    TRY(launch_orb(ctx, dR, R.data(), u, params));
-    TRY(launch_hamming_mode(ctx, dM, n, c, hns, max_dist, offset_evaluate));
-    std::vector<int> counters((size_t)64 * u);
-    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 64 * u, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < u; i++)
-        if (counters[(size_t)64 * i + 2]) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", i, u); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
 }

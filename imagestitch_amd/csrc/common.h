@@ -124,7 +124,8 @@ struct OrbDev {
     uint8_t *bl[VFSMS_ORB_MAX_LEVELS];                                    // blurred levels (descriptor sampling)
     uint8_t *score[VFSMS_ORB_MAX_LEVELS]; uint8_t *nms[VFSMS_ORB_MAX_LEVELS];
     int *hist;                        // [levels][256] FAST score histogram of NMS survivors
-    int *counters;                    // [1] keypoints, [2] overflow; thr1 / n1 / n2 live in the same block
+    int *counters;                    // [1] keypoints, [2] overflow, [4 + level] survivors of the FAST-score cut before any capacity
+                                      // clamp; thr1 / n1 / n2 live in the same block
     int *thr1; int *n1; int *n2;
     int cap1, cap2, cap;
     int *k1_xy; float *k1_resp;       // per level: survivors of the FAST-score cut (+ Harris response)

@@ -223,22 +223,42 @@ __global__ void k_orb_threshold(const OrbDev *rois, int nrois, int nlevels, cons
         if (acc >= n && n > 0) { thr = s; break; }
     }
     if (n == 0) thr = 256;                              // retainBest(0) keeps nothing
-    R.thr1[level] = thr;
+    bool empty = false;                                 // a level of 0 rows or columns (upstream's resize asserts): no keypoints at all
+    for (int l = 0; l < nlevels; l++) empty |= R.lw[l] <= 0 || R.lh[l] <= 0;
+    R.thr1[level] = empty ? 256 : thr;
 }
 
 // ---- ordered compaction (row-major) of survivors + Harris response: one 1024-lane workgroup per (roi, level) ------------------------
-__device__ __forceinline__ float harris_response(g_cu8 img, int st, int x0, int y0)
+// a level read through its reflect-101 extension (upstream samples its bordered pyramid): small edge thresholds put the Harris window
+// (4 px) and the rotated pattern (18.4 px for patch 31) beyond the level
+__device__ __forceinline__ int at101(g_cu8 img, int st, int h, int w, int y, int x)
+{
+    if ((unsigned)y >= (unsigned)h || (unsigned)x >= (unsigned)w) { y = reflect101(y, h); x = reflect101(x, w); }
+    return img[(size_t)y * st + x];
+}
+__device__ __forceinline__ float harris_response(g_cu8 img, int st, int h, int w, int x0, int y0)
 {
     const int r = 3, bs = 7;
     const float scale = 1.f / ((1 << 2) * bs * 255.f);
     const float scale_sq_sq = scale * scale * scale * scale;
-    g_cu8 ptr0 = img + (size_t)(y0 - r) * st + x0 - r;
     int a = 0, b = 0, c = 0;
-    for (int k = 0; k < bs * bs; k++) {
-        g_cu8 p = ptr0 + (k / bs) * st + (k % bs);
-        const int Ix = (p[1] - p[-1]) * 2 + (p[-st + 1] - p[-st - 1]) + (p[st + 1] - p[st - 1]);
-        const int Iy = (p[st] - p[-st]) * 2 + (p[st - 1] - p[-st - 1]) + (p[st + 1] - p[-st + 1]);
-        a += Ix * Ix; b += Iy * Iy; c += Ix * Iy;
+    if (x0 - r - 1 >= 0 && y0 - r - 1 >= 0 && x0 + r + 1 < w && y0 + r + 1 < h) {
+        g_cu8 ptr0 = img + (size_t)(y0 - r) * st + x0 - r;
+        for (int k = 0; k < bs * bs; k++) {
+            g_cu8 p = ptr0 + (k / bs) * st + (k % bs);
+            const int Ix = (p[1] - p[-1]) * 2 + (p[-st + 1] - p[-st - 1]) + (p[st + 1] - p[st - 1]);
+            const int Iy = (p[st] - p[-st]) * 2 + (p[st - 1] - p[-st - 1]) + (p[st + 1] - p[-st + 1]);
+            a += Ix * Ix; b += Iy * Iy; c += Ix * Iy;
+        }
+    } else {
+        for (int k = 0; k < bs * bs; k++) {
+            const int y = y0 - r + k / bs, x = x0 - r + k % bs;
+#define P(dy, dx) at101(img, st, h, w, y + (dy), x + (dx))
+            const int Ix = (P(0, 1) - P(0, -1)) * 2 + (P(-1, 1) - P(-1, -1)) + (P(1, 1) - P(1, -1));
+            const int Iy = (P(1, 0) - P(-1, 0)) * 2 + (P(1, -1) - P(-1, -1)) + (P(1, 1) - P(-1, 1));
+#undef P
+            a += Ix * Ix; b += Iy * Iy; c += Ix * Iy;
+        }
     }
     return ((float)a * b - (float)c * c - 0.04f * ((float)a + b) * ((float)a + b)) * scale_sq_sq;
 }
@@ -291,6 +311,7 @@ __global__ __launch_bounds__(256) void k_orb_chunk_scan(const OrbDev *rois, int 
     if (threadIdx.x < ORB_CHUNKS) R.hist[level * 256 + threadIdx.x] = off;
     if (threadIdx.x == 255) {
         const int total = off + c;
+        R.counters[4 + level] = total;                  // the true count: the host re-carves exact capacities after an overflow
         if (total > R.cap1) R.counters[2] = 1;
         R.n1[level] = min(total, R.cap1);
     }
@@ -347,7 +368,7 @@ __global__ __launch_bounds__(256) void k_orb_harris(const OrbDev *rois, int nlev
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= R.n1[level]) return;
     const int *xy = R.k1_xy + (size_t)level * R.cap1 * 2;
-    R.k1_resp[(size_t)level * R.cap1 + idx] = harris_response((g_cu8)R.lv[level], R.ls[level], xy[2 * idx], xy[2 * idx + 1]);
+    R.k1_resp[(size_t)level * R.cap1 + idx] = harris_response((g_cu8)R.lv[level], R.ls[level], R.lh[level], R.lw[level], xy[2 * idx], xy[2 * idx + 1]);
 }
 
 // ---- second retainBest (quota) by Harris response, IC angle, ordered compaction: one workgroup per (roi, level) ----------------------
@@ -502,17 +523,22 @@ __global__ __launch_bounds__(256) void k_orb_describe(const OrbDev *rois, int nl
     double sd, cd;
     det_sincos((double)angle, &sd, &cd);                       // the oracle evaluates the same explicit algorithm (detmath.h)
     const float a = (float)cd, b = (float)sd;
-    const int w = R.lw[level];
-    g_cu8 center = (g_cu8)R.bl[level] + (size_t)cy * w + cx;
+    const int w = R.lw[level], h = R.lh[level];
+    g_cu8 blv = (g_cu8)R.bl[level];
     const int *pat = T->pattern + byte * 32;
+    // pattern coordinates lie in [-15, 15]: rotated, they stay within 22 px; only keypoints nearer the edge reflect their sample
+    // positions (the positions, not the loads, branch: the 16 loads stay one unconditional batch)
+    const bool inside = cx >= 22 && cy >= 22 && cx + 22 < w && cy + 22 < h;
     int val = 0;
 #pragma unroll
     for (int bit = 0; bit < 8; bit++) {
         const int p0x = pat[4 * bit], p0y = pat[4 * bit + 1], p1x = pat[4 * bit + 2], p1y = pat[4 * bit + 3];
         const float x0 = p0x * a - p0y * b, y0 = p0x * b + p0y * a;
         const float x1 = p1x * a - p1y * b, y1 = p1x * b + p1y * a;
-        const int t0 = center[cv_round_f(y0) * w + cv_round_f(x0)];
-        const int t1 = center[cv_round_f(y1) * w + cv_round_f(x1)];
+        int sy0 = cy + cv_round_f(y0), sx0 = cx + cv_round_f(x0), sy1 = cy + cv_round_f(y1), sx1 = cx + cv_round_f(x1);
+        if (!inside) { sy0 = reflect101(sy0, h); sx0 = reflect101(sx0, w); sy1 = reflect101(sy1, h); sx1 = reflect101(sx1, w); }
+        const int t0 = blv[(size_t)sy0 * w + sx0];
+        const int t1 = blv[(size_t)sy1 * w + sx1];
         val |= (t0 < t1) << bit;
     }
     const int o = off + kidx;

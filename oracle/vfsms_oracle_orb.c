@@ -181,18 +181,21 @@ static int retain_best(orb_kp *kp, int n, int n_points)
     return m;
 }
 
-/* orb.cpp HarrisResponses (blockSize 7, k = 0.04) on the un-blurred level image */
+/* orb.cpp HarrisResponses (blockSize 7, k = 0.04) on the un-blurred level image, read through its reflect-101 extension (upstream's
+ * bordered pyramid): the 9 x 9 window reaches 4 px beyond the keypoint, further than edge_threshold when that is small */
+static inline int px101(const level_img *img, int y, int x) { return img->data[(size_t)reflect101(y, img->h) * img->w + reflect101(x, img->w)]; }
 static float harris_response(const level_img *img, int x0, int y0)
 {
-    const int step = img->w, r = 3, bs = 7;
+    const int r = 3, bs = 7;
     float scale = 1.f / ((1 << 2) * bs * 255.f);
     float scale_sq_sq = scale * scale * scale * scale;
-    const uint8_t *ptr0 = img->data + (size_t)(y0 - r) * step + x0 - r;
     int a = 0, b = 0, c = 0;
     for (int k = 0; k < bs * bs; k++) {
-        const uint8_t *ptr = ptr0 + (k / bs) * step + (k % bs);
-        int Ix = (ptr[1] - ptr[-1]) * 2 + (ptr[-step + 1] - ptr[-step - 1]) + (ptr[step + 1] - ptr[step - 1]);
-        int Iy = (ptr[step] - ptr[-step]) * 2 + (ptr[step - 1] - ptr[-step - 1]) + (ptr[step + 1] - ptr[-step + 1]);
+        const int y = y0 - r + k / bs, x = x0 - r + k % bs;
+        int Ix = (px101(img, y, x + 1) - px101(img, y, x - 1)) * 2 + (px101(img, y - 1, x + 1) - px101(img, y - 1, x - 1)) +
+                 (px101(img, y + 1, x + 1) - px101(img, y + 1, x - 1));
+        int Iy = (px101(img, y + 1, x) - px101(img, y - 1, x)) * 2 + (px101(img, y + 1, x - 1) - px101(img, y - 1, x - 1)) +
+                 (px101(img, y + 1, x + 1) - px101(img, y - 1, x + 1));
         a += Ix * Ix; b += Iy * Iy; c += Ix * Iy;
     }
     return ((float)a * b - (float)c * c - 0.04f * ((float)a + b) * ((float)a + b)) * scale_sq_sq;
@@ -302,12 +305,14 @@ int orc_orb_detect_describe(const uint8_t *image, int h, int w, int stride,
             ++v0;
         }
     }
+    int any_empty = 0;     /* a level of 0 rows or columns: upstream's resize asserts; no keypoints at all here */
+    for (int l = 0; l < nlevels; l++) any_empty |= lv[l].w <= 0 || lv[l].h <= 0;
     int total = 0, allcap = 4096;
     orb_kp *all = (orb_kp *)malloc(sizeof(orb_kp) * allcap);
     for (int l = 0; l < nlevels; l++) {
         orb_kp *kp = NULL;
         int n = 0;
-        if (lv[l].w > 6 && lv[l].h > 6) n = fast16(&lv[l], fastThreshold, &kp);
+        if (!any_empty && lv[l].w > 6 && lv[l].h > 6) n = fast16(&lv[l], fastThreshold, &kp);
         /* runByImageBorder(edgeThreshold): Rect(border, border, w-2*border, h-2*border).contains(pt) */
         int m = 0;
         for (int i = 0; i < n; i++)
@@ -364,8 +369,8 @@ int orc_orb_detect_describe(const uint8_t *image, int h, int w, int stride,
             det_sincos((double)angle, &sd, &cd);
             float a = (float)cd, b = (float)sd;
             const level_img *L = &bl[k->level];
-            const uint8_t *center = L->data + (size_t)cv_round_f(py * inv) * L->w + cv_round_f(px * inv);
-            const int step = L->w;
+            /* the rotated pattern reaches 18.4 px (patch 31): samples read the reflect-101 extension of the blurred level */
+            const int cy = cv_round_f(py * inv), cx = cv_round_f(px * inv);
             uint8_t *d = desc + (size_t)j * 32;
             const int32_t *pat = pattern;
             for (int i = 0; i < 32; ++i, pat += 32) {
@@ -374,8 +379,8 @@ int orc_orb_detect_describe(const uint8_t *image, int h, int w, int stride,
                     int p0x = pat[4 * bit], p0y = pat[4 * bit + 1], p1x = pat[4 * bit + 2], p1y = pat[4 * bit + 3];
                     float x0 = p0x * a - p0y * b, y0 = p0x * b + p0y * a;
                     float x1 = p1x * a - p1y * b, y1 = p1x * b + p1y * a;
-                    int t0 = center[cv_round_f(y0) * step + cv_round_f(x0)];
-                    int t1 = center[cv_round_f(y1) * step + cv_round_f(x1)];
+                    int t0 = px101(L, cy + cv_round_f(y0), cx + cv_round_f(x0));
+                    int t1 = px101(L, cy + cv_round_f(y1), cx + cv_round_f(x1));
                     val |= (t0 < t1) << bit;
                 }
                 d[i] = (uint8_t)val;

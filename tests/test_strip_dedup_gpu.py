@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the strip table of a fused SURF batch (csrc/api.hip: build_strip_table): a strip that several slots of one batch
+"""GPU tests (-m gpu) of the strip table of a fused SURF or ORB batch (csrc/api.hip: build_strip_table): a strip that several slots of one batch
 name -- the turn of the serpentine path (pair p in direction 1 next to pair p + 1 in direction 3), the same job twice, a job whose A strip
 is another job's B strip, one buffer behind two tile handles -- is detected and described once and read by every job that uses it.  Every
 row of such a batch must equal the row of the same job evaluated alone in its own call, plain and with equalised / CLAHE'd strips, and
@@ -54,13 +54,13 @@ def _attempt(engine, jobs, spec):
     return engine.attempt_surf_batch_enhanced(jobs, None, 0.75, 3, spec)
 
 
-def _rows_of(engine, tiles, spec, names=None):
+def _rows_of(engine, tiles, spec, names=None, attempt=_attempt):
     shapes = [t.shape for t in tiles]
     hs = [engine.tile_upload(t) for t in tiles]
     try:
         bs = _batches(hs, shapes)
-        return {k: _attempt(engine, v, spec).tolist() for k, v in bs.items() if names is None or k in names}, \
-               {k: [_attempt(engine, [j], spec)[0].tolist() for j in v] for k, v in bs.items() if names is None or k in names}
+        return {k: attempt(engine, v, spec).tolist() for k, v in bs.items() if names is None or k in names}, \
+               {k: [attempt(engine, [j], spec)[0].tolist() for j in v] for k, v in bs.items() if names is None or k in names}
     finally:
         for h in hs:
             engine.tile_free(h)
@@ -72,6 +72,20 @@ def test_repeated_strips_give_the_rows_of_jobs_alone(engine, spec):
     for name in batched:
         assert batched[name] == alone[name], (name, spec)
     assert any(r[0] == 1 for r in alone["mixed"]) and all(r[4] > 0 and r[5] > 0 for r in alone["mixed"])
+
+
+def _attempt_orb(engine, jobs, spec):
+    return engine.attempt_orb_batch(jobs)
+
+
+def test_orb_repeated_strips_give_the_rows_of_jobs_alone(engine):
+    """vfsms_attempt_orb_batch reads the same strip table: every row of the named batches equals the job alone, and a strip per slot
+    (VFSMS_STRIP_DEDUP=0, child process) gives the same rows"""
+    batched, alone = _rows_of(engine, _tiles(), SPECS[0], attempt=_attempt_orb)
+    for name in batched:
+        assert batched[name] == alone[name], name
+    assert any(r[0] == 1 for r in alone["mixed"]) and all(r[4] > 0 and r[5] > 0 for r in alone["mixed"])
+    assert _child(["orb"], dict(VFSMS_STRIP_DEDUP="0"), 300) == batched
 
 
 def test_one_buffer_behind_two_handles(engine):
@@ -141,6 +155,8 @@ def _main(argv):
     if argv[0] == "batch":
         batched, _ = _rows_of(eng, _tiles(), SPECS[0], names=("mixed",))
         out = batched
+    elif argv[0] == "orb":
+        out, _ = _rows_of(eng, _tiles(), SPECS[0], attempt=_attempt_orb)
     else:
         tiles = np.load(argv[1], mmap_mode="r")
         hs = [eng.tile_upload(np.ascontiguousarray(t)) for t in tiles]
