@@ -72,6 +72,7 @@ _SIGNATURES = {
     "vfsms_ctx_sync_uploads": (C.c_int, [C.c_void_p]),
     "vfsms_ctx_stream": (C.c_void_p, [C.c_void_p]),
     "vfsms_ctx_set_keypoint_capacity": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfsms_ctx_set_offset_estimator": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "vfsms_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_profile_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "vfsms_tile_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -109,6 +110,8 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_mode_offset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                     C.c_int, C.c_void_p]),
+    "vfsms_consensus_offset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p]),
     "vfsms_phase_correlate_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p]),
     "vfsms_fuse_fade_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -243,6 +246,14 @@ class Engine:
 
     def set_keypoint_capacity(self, cap):
         self._check(self.lib.vfsms_ctx_set_keypoint_capacity(self.ctx, int(cap)))
+
+    OFFSET_ESTIMATORS = {"mode": 0, "ransac": 1, "consensus": 1}
+
+    def set_offset_estimator(self, kind="mode", tol=3):
+        """How the fused paths (attempt batches, pairs_offsets, features_match_offset) turn matches into an offset: "mode" (default) or
+        "ransac" / "consensus" (consensus_offset with tolerance `tol` px, 0..64); 0 / 1 as in include/vfsms.h."""
+        est = self.OFFSET_ESTIMATORS[kind] if isinstance(kind, str) else int(kind)
+        self._check(self.lib.vfsms_ctx_set_offset_estimator(self.ctx, est, int(tol)))
 
     def profile_enable(self, on=True):
         self._check(self.lib.vfsms_profile_enable(self.ctx, int(bool(on))))
@@ -508,6 +519,16 @@ class Engine:
         out = np.zeros(4, np.int32)
         self._check(self.lib.vfsms_mode_offset(self.ctx, _ptr(kpsA), len(kpsA), _ptr(kpsB), len(kpsB), _ptr(pairs), len(pairs),
                                                int(offset_evaluate), _ptr(out)))
+        return bool(out[0]), [int(out[1]), int(out[2])], int(out[3])
+
+    def consensus_offset(self, kpsA, kpsB, pairs, tol=3, offset_evaluate=3):
+        """Method.getOffsetByRansac's estimator (tests/consensus_ref.py) -> (status, [dx, dy], support)."""
+        kpsA = np.ascontiguousarray(kpsA, np.float32).reshape(-1, 2)
+        kpsB = np.ascontiguousarray(kpsB, np.float32).reshape(-1, 2)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros(4, np.int32)
+        self._check(self.lib.vfsms_consensus_offset(self.ctx, _ptr(kpsA), len(kpsA), _ptr(kpsB), len(kpsB), _ptr(pairs), len(pairs),
+                                                    int(tol), int(offset_evaluate), _ptr(out)))
         return bool(out[0]), [int(out[1]), int(out[2])], int(out[3])
 
     def phase_correlate(self, a, b):

@@ -285,6 +285,16 @@ extern "C" int vfsms_ctx_set_keypoint_capacity(vfsms_ctx *ctx, int cap)
     ctx->kp_cap_override = cap;
     return VFSMS_OK;
 }
+extern "C" int vfsms_ctx_set_offset_estimator(vfsms_ctx *ctx, int estimator, int tol_px)
+{
+    if (!ctx) return VFSMS_ERR_BAD_ARG;
+    if ((estimator != VFSMS_OFFSET_MODE && estimator != VFSMS_OFFSET_CONSENSUS) || tol_px < 0 || tol_px > VFSMS_CONSENSUS_MAX_TOL) {
+        vfsms_set_error("set_offset_estimator: estimator %d / tolerance %d (0 mode or 1 consensus; 0..%d px)", estimator, tol_px, VFSMS_CONSENSUS_MAX_TOL);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    ctx->offset_estimator = estimator; ctx->offset_tol = tol_px;
+    return VFSMS_OK;
+}
 static int kp_capacity(vfsms_ctx *ctx, int h, int w)
 {
     if (ctx->kp_cap_override > 0) return ctx->kp_cap_override;
@@ -928,16 +938,17 @@ extern "C" int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, con
     return VFSMS_OK;
 }
 
-extern "C" int vfsms_mode_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
-                                 const int32_t *pairs, int m, int offset_evaluate, int32_t *out4)
+// vfsms_mode_offset / vfsms_consensus_offset: one job of explicit matches through the vote tail of the named estimator
+static int offset_from_pairs(vfsms_ctx *ctx, const char *what, const float *kpsA, int nA, const float *kpsB, int nB,
+                             const int32_t *pairs, int m, int estimator, int tol, int offset_evaluate, int32_t *out4)
 {
     CTX_ENTER(ctx);
-    if (!out4 || m < 0 || nA < 0 || nB < 0) { vfsms_set_error("mode_offset: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (!out4 || m < 0 || nA < 0 || nB < 0) { vfsms_set_error("%s: bad arguments", what); return VFSMS_ERR_BAD_ARG; }
     out4[0] = out4[1] = out4[2] = out4[3] = 0;
     if (m == 0) return VFSMS_OK;
     for (int k = 0; k < m; k++)
         if (pairs[2 * k] < 0 || pairs[2 * k] >= nB || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= nA) {
-            vfsms_set_error("mode_offset: match index out of range"); return VFSMS_ERR_BAD_ARG;
+            vfsms_set_error("%s: match index out of range", what); return VFSMS_ERR_BAD_ARG;
         }
     TRY(ctx_arena_reserve(ctx, sizeof(float) * 2 * ((size_t)nA + nB) + match_bytes(m, 1) + 65536));
     MatchDev M; memset(&M, 0, sizeof(M));
@@ -951,12 +962,25 @@ extern "C" int vfsms_mode_offset(vfsms_ctx *ctx, const float *kpsA, int nA, cons
     HIP_TRY(hipMemcpyAsync(M.pairs, pairs, sizeof(int32_t) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
     MatchDev *dM;
     TRY(upload_array(ctx, &M, 1, &dM));
-    TRY(launch_mode_only(ctx, dM, 1, m, offset_evaluate));
+    TRY(launch_mode_only(ctx, dM, 1, m, estimator, tol, offset_evaluate));
     int32_t res[VFSMS_ATTEMPT_INTS];
     HIP_TRY(hipMemcpyAsync(res, M.result, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 4; k++) out4[k] = res[k];
     return VFSMS_OK;
+}
+
+extern "C" int vfsms_mode_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
+                                 const int32_t *pairs, int m, int offset_evaluate, int32_t *out4)
+{
+    return offset_from_pairs(ctx, "mode_offset", kpsA, nA, kpsB, nB, pairs, m, VFSMS_OFFSET_MODE, 0, offset_evaluate, out4);
+}
+
+extern "C" int vfsms_consensus_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
+                                      const int32_t *pairs, int m, int tol_px, int offset_evaluate, int32_t *out4)
+{
+    if (tol_px < 0 || tol_px > VFSMS_CONSENSUS_MAX_TOL) { vfsms_set_error("consensus_offset: tolerance %d outside 0..%d", tol_px, VFSMS_CONSENSUS_MAX_TOL); return VFSMS_ERR_BAD_ARG; }
+    return offset_from_pairs(ctx, "consensus_offset", kpsA, nA, kpsB, nB, pairs, m, VFSMS_OFFSET_CONSENSUS, tol_px, offset_evaluate, out4);
 }
 
 // ---- phase correlation ---------------------------------------------------------------------------------------------------

@@ -183,6 +183,7 @@ struct vfsms_ctx {
     // pinned staging for small results
     char *pinned; size_t pinned_size; size_t pinned_off;
     int kp_cap_override;
+    int offset_estimator = VFSMS_OFFSET_MODE, offset_tol = 3;   // the vote tail of every fused path (vfsms_ctx_set_offset_estimator)
     // SURF tables
     vfsms_surf_params cur_params; bool tables_valid;
     LayerPat *d_layers; int n_layers;
@@ -253,10 +254,12 @@ int launch_bf_l2(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, in
 int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq);
 int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio);
 int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate);
-int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int offset_evaluate);
+int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int estimator, int tol, int offset_evaluate);
 int launch_bf_hamming(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes,
                       int *best_idx, int *best_dist);
 int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate);
+// consensus_kernels.hip
+int launch_consensus(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int tol, int offset_evaluate);
 // orb_kernels.hip
 int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p);
 size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2, int cap);

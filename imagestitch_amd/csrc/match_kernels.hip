@@ -855,7 +855,7 @@ __global__ __launch_bounds__(1024) void k_match_scan(const MatchDev *jobs)
     if (threadIdx.x == 0) { J.mcount[0] = carry_m; J.mcount[1] = carry_v; J.mcount[2] = 0; J.mcount[3] = 0; }
 }
 
-// votes from an explicit (trainIdx, queryIdx) list (per-operator entry point vfsms_mode_offset)
+// votes from an explicit (trainIdx, queryIdx) list (per-operator entry points vfsms_mode_offset, vfsms_consensus_offset)
 __global__ __launch_bounds__(256) void k_votes_from_pairs(const MatchDev *jobs, int m)
 {
     const MatchDev &J = jobs[blockIdx.y];
@@ -1111,10 +1111,15 @@ int launch_bf_l2(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, in
     return VFSMS_OK;
 }
 
-// compaction + mode vote + result record: one workgroup per job
-static int launch_vote_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate)
+// compaction + vote + result record.  Mode: one workgroup per job (k_scan_mode).  Consensus (Method.offsetCaculate = "ransac"):
+// the same order-preserving compaction (k_match_scan), then support + pick (consensus_kernels.hip)
+static int launch_vote_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int estimator, int tol, int offset_evaluate)
 {
-    (void)capq;
+    if (estimator == VFSMS_OFFSET_CONSENSUS) {
+        hipLaunchKernelGGL(k_match_scan, dim3(njobs), dim3(1024), 0, ctx->stream, d_jobs);
+        HIP_TRY(hipGetLastError());
+        return launch_consensus(ctx, d_jobs, njobs, capq, tol, offset_evaluate);
+    }
     hipLaunchKernelGGL(k_scan_mode, dim3(njobs), dim3(1024), 0, ctx->stream, d_jobs, offset_evaluate);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
@@ -1125,7 +1130,7 @@ int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int cap
     if (njobs <= 0) return VFSMS_OK;
     ProfScope ps(ctx, "vote");
     hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, ratio, 1);
-    return launch_vote_tail(ctx, d_jobs, njobs, capq, offset_evaluate);
+    return launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate);
 }
 
 int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio)
@@ -1148,15 +1153,16 @@ int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq
 {
     if (njobs <= 0) return VFSMS_OK;
     ProfScope ps(ctx, "vote");
-    return launch_vote_tail(ctx, d_jobs, njobs, capq, offset_evaluate);
+    return launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate);
 }
 
-int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int offset_evaluate)
+// the per-operator entry points name their estimator: the context's setting governs the fused paths only
+int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int estimator, int tol, int offset_evaluate)
 {
     if (njobs <= 0) return VFSMS_OK;
     if (capm > 0)
         hipLaunchKernelGGL(k_votes_from_pairs, dim3((capm + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, capm);
-    return launch_vote_tail(ctx, d_jobs, njobs, capm, offset_evaluate);
+    return launch_vote_tail(ctx, d_jobs, njobs, capm, estimator, tol, offset_evaluate);
 }
 
 int launch_bf_hamming(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes,

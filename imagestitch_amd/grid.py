@@ -17,7 +17,7 @@ while keeping the GPU full:
 """
 import numpy as np
 
-from .utility import roi_rect
+from .utility import roi_rect, offset_estimator
 
 RESULT_INTS = 6   # status, dx, dy, direction, i, votes
 
@@ -33,7 +33,7 @@ def _rotate(direction, incre):
 
 class GridRegistrar:
     def __init__(self, engine, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=3, directIncre=1,
-                 surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0)):
+                 surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0), offsetCaculate="mode", ransacThreshold=3):
         self.eng = engine
         self.method = method
         self.roiRatio = roiRatio
@@ -44,6 +44,10 @@ class GridRegistrar:
         self.phaseThr = phaseResponseThreshold
         self.window = max(1, int(window))
         self.enhance = tuple(enhance)                     # (mode, clipLimit, tileSize) of Method.isEnhance (Stitcher.py:327-334)
+        # Method.offsetCaculate: "ransac" puts the engine's vote tail on the consensus of getOffsetByRansac around this registrar's own
+        # calls (_estimator) and back on mode afterwards; "mode" makes no such call
+        self.offsetCaculate = offsetCaculate if method in ("surf", "orb") else "mode"
+        self.ransacThreshold = int(ransacThreshold)
         self.stats = dict(attempts=0, batches=0, sum_nq_nt=0, sum_nq_plus_nt=0, sum_nq=0, roi_px=0)
         # Path memory: the accepted directions of the last path this registrar registered are the PREDICTION for the next one of the same
         # length (a session shoots one scan pattern after the other: Main.py loops over its datasets with one setting) -- they drive the
@@ -73,6 +77,9 @@ class GridRegistrar:
             out.append(ring)
         return out
 
+    def _estimator(self):
+        return offset_estimator(self.eng, self.offsetCaculate, self.ransacThreshold)
+
     # -- one batch of attempts -----------------------------------------------------------------------------------
     def _attempts(self, handles, shapes, items):
         """items: [(pair index k, direction, i)] -> [(status, raw_dx, raw_dy, votes)]"""
@@ -87,14 +94,16 @@ class GridRegistrar:
         self.stats["attempts"] += len(jobs)
         self.stats["batches"] += 1
         if self.method == "surf":
-            rows = self._surf_batch(jobs)
+            with self._estimator():
+                rows = self._surf_batch(jobs)
             nq = rows[:, 4].astype(np.int64); nt = rows[:, 5].astype(np.int64)
             self.stats["sum_nq_nt"] += int((nq * nt).sum())
             self.stats["sum_nq_plus_nt"] += int((nq + nt).sum())
             self.stats["sum_nq"] += int(nq.sum())
             return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
         if self.method == "orb":
-            rows = self.eng.attempt_orb_batch(jobs, self.params, getattr(self, "orbMaxDistance", -1), self.offsetEvaluate)
+            with self._estimator():
+                rows = self.eng.attempt_orb_batch(jobs, self.params, getattr(self, "orbMaxDistance", -1), self.offsetEvaluate)
             return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
         if self.method == "phase":
             rows = self.eng.attempt_phase_batch(jobs)
@@ -376,7 +385,8 @@ class GridRegistrar:
         mem = self._memory_prediction(P, hint)
         hint = self._prediction(P, hint)
         if self.native and hasattr(self.eng, "pairs_offsets"):
-            out, d, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), 0, P, direction, False, stop_on_fail)
+            with self._estimator():
+                out, d, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), 0, P, direction, False, stop_on_fail)
             self._native_stats(st)
         else:
             out, d = self.chain(handles, shapes, 0, P, direction, stop_on_fail=stop_on_fail, hint=hint)
@@ -475,7 +485,8 @@ class GridRegistrar:
         memo, cache = {}, {}
         if len(dirs) > 1 and hi > lo and self.native and hasattr(self.eng, "pairs_offsets_blind"):
             # the four blind chains inside the library (csrc/grid.hip: the same machine, shared cache and memo)
-            res, dn, st = self.eng.pairs_offsets_blind(handles, shapes, self._grid_params(), lo, hi, per)
+            with self._estimator():
+                res, dn, st = self.eng.pairs_offsets_blind(handles, shapes, self._grid_params(), lo, hi, per)
             self._native_stats(st)
             return np.concatenate([np.asarray(res, np.int32).reshape(-1), np.asarray(dn, np.int32)])
         if len(dirs) > 1 and hi > lo:
@@ -485,7 +496,8 @@ class GridRegistrar:
                 cache[it] = r
         for d_in in dirs:
             if hi > lo and len(dirs) == 1 and self.native and hasattr(self.eng, "pairs_offsets"):
-                res, dn, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), lo, hi, d_in, rank > 0, False)
+                with self._estimator():
+                    res, dn, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), lo, hi, d_in, rank > 0, False)
                 self._native_stats(st)
                 table[d_in - 1, :hi - lo] = res
             elif hi > lo:

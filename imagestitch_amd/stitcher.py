@@ -15,7 +15,7 @@ import numpy as np
 
 from . import utility as Utility
 from . import fusion as ImageFusion
-from .utility import roi_rect
+from .utility import roi_rect, offset_estimator
 
 CANNOT_MATCH = "  The two images can not match"
 
@@ -183,7 +183,7 @@ class Stitcher(Utility.Method):
             return self.featureMethod
         if fn is Stitcher.calculateOffsetForPhaseCorrleateIncre and not self.phaseSignFix:
             return "phase"
-        if fn is Stitcher.calculateOffsetForFeatureSearch and self._usesStockOperators() and self.offsetCaculate == "mode":
+        if fn is Stitcher.calculateOffsetForFeatureSearch and self._usesStockOperators() and self.offsetCaculate in ("mode", "ransac"):
             if self.featureMethod == "surf" and hasattr(self.engine, "features_surf_batch"):
                 return "surf_full"
             if self.featureMethod == "orb" and not self.isEnhance and hasattr(self.engine, "attempt_orb_batch"):
@@ -198,7 +198,8 @@ class Stitcher(Utility.Method):
         reg = GridRegistrar(self.engine, method="surf" if method == "surf_full" else "orb" if method == "orb_full" else method, roiRatio=self.roiRatio,
                             searchRatio=self.searchRatio, offsetEvaluate=self.offsetEvaluate, directIncre=self.directIncre, surfParams=params,
                             phaseResponseThreshold=self.phaseResponseThreshold, window=48,
-                            enhance=self._enhanceSpec() if method in ("surf", "surf_full") else (0, 0.0, 0))
+                            enhance=self._enhanceSpec() if method in ("surf", "surf_full") else (0, 0.0, 0),
+                            offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold)
         reg.orbMaxDistance = self.orbMaxDistance if self.isGPUAvailable else -1
         reg.path_memory = self.__dict__.get("_pathMemory")
         reg.path_suspect = bool(self.__dict__.get("_pathSuspect", False))
@@ -279,7 +280,8 @@ class Stitcher(Utility.Method):
         eng = self.engine
         feats, counts = eng.features_surf_batch(handles, self._surfParams(), self._enhanceSpec())
         try:
-            rows = eng.features_match_offset_batch(feats[:-1], feats[1:], self.searchRatio, self.offsetEvaluate)
+            with self._offsetEstimator():
+                rows = eng.features_match_offset_batch(feats[:-1], feats[1:], self.searchRatio, self.offsetEvaluate)
         finally:
             for f in feats:
                 if f:
@@ -302,7 +304,9 @@ class Stitcher(Utility.Method):
         table = []
         for c0 in range(0, len(handles) - 1, chunk):
             jobs = [(handles[k], handles[k + 1], 0, 0, 0, 0, shapes[k][0], shapes[k][1]) for k in range(c0, min(c0 + chunk, len(handles) - 1))]
-            for r in eng.attempt_orb_batch(jobs, self._orbParams(), max_dist, self.offsetEvaluate):
+            with self._offsetEstimator():
+                rows = eng.attempt_orb_batch(jobs, self._orbParams(), max_dist, self.offsetEvaluate)
+            for r in rows:
                 ok = bool(r[0]) and r[4] > 0 and r[5] > 0          # an image without keypoints: featuresX is None, status stays False
                 table.append([int(ok), int(r[1]), int(r[2]), 0, 0, int(r[3])])
                 if not ok:
@@ -474,9 +478,14 @@ class Stitcher(Utility.Method):
 
     def _usesStockOperators(self):
         c = type(self)
+        stock_offset = ((self.offsetCaculate == "mode" and c.getOffsetByMode is Utility.Method.getOffsetByMode)
+                        or (self.offsetCaculate == "ransac" and c.getOffsetByRansac is Utility.Method.getOffsetByRansac))
         return (c.detectAndDescribe is Utility.Method.detectAndDescribe and c.matchDescriptors is Utility.Method.matchDescriptors
-                and c.getOffsetByMode is Utility.Method.getOffsetByMode and (not self.isEnhance or self.featureMethod == "surf")
-                and self.featureMethod in ("surf", "orb") and self.offsetCaculate == "mode")
+                and stock_offset and (not self.isEnhance or self.featureMethod == "surf") and self.featureMethod in ("surf", "orb"))
+
+    def _offsetEstimator(self):
+        """scope of a fused engine call: with offsetCaculate = "ransac" its vote tail is the consensus of getOffsetByRansac"""
+        return offset_estimator(self.engine, self.offsetCaculate, self.ransacThreshold)
 
     def _enhanceSpec(self):
         """(mode, clipLimit, tileSize) of Stitcher.py:269-276 / 327-334: 0 none, 1 cv2.equalizeHist, 2 cv2.createCLAHE(...).apply."""
@@ -496,13 +505,14 @@ class Stitcher(Utility.Method):
             if ra[2:] == rb[2:] and ra[2] > 0 and ra[3] > 0:
                 ha, hb = self._tileHandles([imageA, imageB])
                 job = (ha, hb, ra[0], ra[1], rb[0], rb[1], ra[2], ra[3])
-                if self.featureMethod == "orb":
-                    max_dist = self.orbMaxDistance if self.isGPUAvailable else -1
-                    row = self.engine.attempt_orb_batch([job], self._orbParams(), max_dist, self.offsetEvaluate)[0]
-                elif self.isEnhance:
-                    row = self.engine.attempt_surf_batch_enhanced([job], self._surfParams(), self.searchRatio, self.offsetEvaluate, self._enhanceSpec())[0]
-                else:
-                    row = self.engine.attempt_surf_batch([job], self._surfParams(), self.searchRatio, self.offsetEvaluate)[0]
+                with self._offsetEstimator():
+                    if self.featureMethod == "orb":
+                        max_dist = self.orbMaxDistance if self.isGPUAvailable else -1
+                        row = self.engine.attempt_orb_batch([job], self._orbParams(), max_dist, self.offsetEvaluate)[0]
+                    elif self.isEnhance:
+                        row = self.engine.attempt_surf_batch_enhanced([job], self._surfParams(), self.searchRatio, self.offsetEvaluate, self._enhanceSpec())[0]
+                    else:
+                        row = self.engine.attempt_surf_batch([job], self._surfParams(), self.searchRatio, self.offsetEvaluate)[0]
                 if row[4] == 0 or row[5] == 0:
                     return None                      # featuresA is None or featuresB is None: status untouched
                 return (bool(row[0]), [int(row[1]), int(row[2])])
@@ -639,7 +649,8 @@ class Stitcher(Utility.Method):
         status, offset = False, [0, 0]
         try:
             if featA.n and featB.n:
-                row = eng.features_match_offset(featA.handle, featB.handle, self.searchRatio, self.offsetEvaluate)
+                with self._offsetEstimator():
+                    row = eng.features_match_offset(featA.handle, featB.handle, self.searchRatio, self.offsetEvaluate)
                 status, offset = bool(row[0]), [int(row[1]), int(row[2])]
         finally:
             featA.release()                                     # A's set is never needed again (B's lives on in the cache)

@@ -5,6 +5,7 @@ Same class / attribute / method names, argument meaning and return conventions a
 unchanged; every operator dispatches into libvfsms.so (hand-written HIP for MI355X) through
 imagestitch_amd._lib.Engine.  There is no cv2 and no CPU fallback behind these methods.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -33,6 +34,20 @@ def roi_rect(shape, direction=1, order="first", searchRatio=0.1):
             return (0, 0, row, col)
         return (0, col - n, row, n) if at_end else (0, 0, row, n)
     return (0, 0, row, col)
+
+
+@contextlib.contextmanager
+def offset_estimator(engine, offsetCaculate="mode", ransacThreshold=3):
+    """The engine's fused paths vote by consensus (getOffsetByRansac) inside the block when offsetCaculate is "ransac", and by mode again
+    after it, also when it raises.  "mode" makes no engine call: mode is the engine's default."""
+    if offsetCaculate != "ransac":
+        yield
+        return
+    engine.set_offset_estimator("ransac", ransacThreshold)
+    try:
+        yield
+    finally:
+        engine.set_offset_estimator("mode")
 
 
 class Method():
@@ -81,6 +96,7 @@ class Method():
     # ---- registration (ImageUtility.py:42-44) ----
     offsetCaculate = "mode"     # "mode" or "ransac"
     offsetEvaluate = 3
+    ransacThreshold = 3         # "ransac": Chebyshev tolerance in px (0..64) around a vote (getOffsetByRansac)
 
     # ---- enhancement (ImageUtility.py:46-50; CLAHE/equalizeHist are out of the hot-path scope) ----
     isEnhance = False
@@ -129,9 +145,16 @@ class Method():
         return (status, off)
 
     def getOffsetByRansac(self, kpsA, kpsB, matches, offsetEvaluate=100):
-        """ImageUtility.py:180-210 is marked incomplete by the reference (its getAffineTransform call raises
-        for != 3 points) and Main.py never selects it; not part of the accelerated path."""
-        raise NotImplementedError("offsetCaculate='ransac' is outside the VFSMS hot path (reference: ImageUtility.py:180-210, incomplete)")
+        """offsetCaculate = "ransac" -> (status, [dx, dy], adjustH) like ImageUtility.py:180-210's tuple (adjustH = np.eye(3) when status
+        is true, else 0).  The reference's version fits a homography and then breaks, so the specification is the project's own,
+        tests/consensus_ref.py: a deterministic consensus over one-point translation hypotheses.  The votes are getOffsetByMode's; a vote's
+        support counts the votes within `ransacThreshold` px of it on both axes; the first vote of largest support wins, and the offset is the
+        lower median of its inliers per axis; status = support >= offsetEvaluate.  At ransacThreshold = 0 it equals getOffsetByMode."""
+        if len(matches) == 0:
+            return (False, [0, 0], 0)
+        status, off, _support = self.engine.consensus_offset(np.asarray(kpsA, np.float32), np.asarray(kpsB, np.float32),
+                                                             np.asarray(matches, np.int32), self.ransacThreshold, offsetEvaluate)
+        return (status, off, np.eye(3) if status else 0)
 
     # -- array adapters of the DLL path (ImageUtility.py:212-246): kept for API compatibility ------------
     def npToListForKeypoints(self, array):

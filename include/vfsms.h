@@ -97,6 +97,14 @@ int vfsms_ctx_sync_uploads(vfsms_ctx *ctx);
 void *vfsms_ctx_stream(vfsms_ctx *ctx);
 /* Max SURF candidates per ROI (default: h*w/24 + 4096).  0 restores the default.                  */
 int vfsms_ctx_set_keypoint_capacity(vfsms_ctx *ctx, int cap);
+/* How the fused paths turn matches into an offset (Method.offsetCaculate): VFSMS_OFFSET_MODE (the default, getOffsetByMode) or
+ * VFSMS_OFFSET_CONSENSUS (vfsms_consensus_offset with tolerance tol_px, 0..VFSMS_CONSENSUS_MAX_TOL).  Governs vfsms_attempt_surf_batch,
+ * _enhanced, vfsms_attempt_orb_batch, vfsms_pairs_offsets, _blind, vfsms_features_match_offset and _batch; rows keep their layout.
+ * vfsms_mode_offset always votes by mode.  Anything else returns VFSMS_ERR_BAD_ARG and leaves the setting as it was.                */
+#define VFSMS_OFFSET_MODE 0
+#define VFSMS_OFFSET_CONSENSUS 1
+#define VFSMS_CONSENSUS_MAX_TOL 64
+int vfsms_ctx_set_offset_estimator(vfsms_ctx *ctx, int estimator, int tol_px);
 
 /* Per-stage timing with HIP events recorded on the context's own stream around each kernel group
  * ("integral", "hessian", "nms", "sort", "orientation", "describe", "bf_l2", "vote", "phase", "fuse", ...).
@@ -225,6 +233,11 @@ int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t 
 /* Method.getOffsetByMode (ImageUtility.py:139-178).  kps: float32[n][2]=(x,y); out4={status,dx,dy,votes} */
 int vfsms_mode_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
                       const int32_t *pairs, int m, int offset_evaluate, int32_t *out4);
+/* Method.getOffsetByRansac (offsetCaculate = "ransac"), specified by tests/consensus_ref.py: the votes of vfsms_mode_offset, the
+ * support of each = the votes within a Chebyshev window of tol_px (0..VFSMS_CONSENSUS_MAX_TOL) around it, the first vote of largest
+ * support wins, offset = the lower median of its inliers per axis.  out4={status,dx,dy,support}; tol_px = 0 is vfsms_mode_offset. */
+int vfsms_consensus_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
+                           const int32_t *pairs, int m, int tol_px, int offset_evaluate, int32_t *out4);
 
 /* cv2.phaseCorrelate(np.float64(a), np.float64(b)) (Stitcher.py:230): out3 = {x, y, response}     */
 int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
