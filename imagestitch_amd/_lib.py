@@ -102,6 +102,7 @@ _SIGNATURES = {
     "vfsms_sift_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SiftParams),
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_attempt_orb_batch": (C.c_int, [C.c_void_p, C.POINTER(RoiPair), C.c_int, C.POINTER(OrbParams), C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_attempt_sift_batch": (C.c_int, [C.c_void_p, C.POINTER(RoiPair), C.c_int, C.POINTER(SiftParams), C.c_double, C.c_int, C.c_void_p]),
     "vfsms_bf_l2_knn2_ratio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                          C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_bf_l2_knn2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -481,6 +482,17 @@ class Engine:
         arr = jobs if isinstance(jobs, C.Array) else self.make_jobs(jobs)
         params = params or self.orb_params()
         self._check(self.lib.vfsms_attempt_orb_batch(self.ctx, arr, n, C.byref(params), int(max_dist), int(offset_evaluate), _ptr(out)))
+        return out
+
+    def attempt_sift_batch(self, jobs, params=None, ratio=0.75, offset_evaluate=3):
+        """n fused SIFT + BF-L2 + ratio + vote attempts on resident tiles: int32[n][ATTEMPT_INTS] rows laid out as attempt_surf_batch's"""
+        n = len(jobs)
+        out = np.zeros((n, ATTEMPT_INTS), np.int32)
+        if n == 0:
+            return out
+        arr = jobs if isinstance(jobs, C.Array) else self.make_jobs(jobs)
+        params = params or self.sift_params()
+        self._check(self.lib.vfsms_attempt_sift_batch(self.ctx, arr, n, C.byref(params), float(ratio), int(offset_evaluate), _ptr(out)))
         return out
 
     def bf_l2_ratio_matches(self, q, t, ratio=0.75):

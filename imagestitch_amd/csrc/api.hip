@@ -256,6 +256,7 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
     if (ctx->sift_scratch) hipFree(ctx->sift_scratch);
     if (ctx->sift_kp) hipFree(ctx->sift_kp);
+    sift_pool_free(ctx);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->d_layers) hipFree(ctx->d_layers);
     if (ctx->d_tables) hipFree(ctx->d_tables);
@@ -1963,6 +1964,103 @@ extern "C" int vfsms_sift_pyramid(vfsms_ctx *ctx, const uint8_t *img, int h, int
     uint8_t *d_img;
     TRY(upload_image(ctx, img, h, w, stride, &d_img));
     return sift_pyramid_device(ctx, d_img, h, w, params, gauss, dog, cap_floats, shapes, shapes_cap, n_octaves);
+}
+
+// ---- fused SIFT + BF + ratio + vote attempts --------------------------------------------------------------------------------------
+// The distinct strips of the batch (build_strip_table) are detected and described once, shape run after shape run, in groups whose
+// pyramids fit the context's byte budget (sift_group_strips); a group costs two host syncs whatever its size, and every array is sized
+// from the counts read there, so nothing can overflow.  Only positions, descriptors and their packed int8 rows outlive a group
+// (ctx->sift_pool).  The 2-NN search is the integer matrix-core kernel (k_bf_i8_d128, exact); VFSMS_BF_EXACT=1 takes k_bf_l2_gen<128>.
+extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
+                                        const vfsms_sift_params *params, double ratio, int offset_evaluate, int32_t *out)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n && (!jobs || !out)) || !params) { vfsms_set_error("attempt_sift: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(sift_check_params(params));
+    if (n == 0) return VFSMS_OK;
+    std::vector<int> ord(n);
+    for (int k = 0; k < n; k++) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
+        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    StripTable T;
+    TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
+    const int u = (int)T.strips.size();
+    ctx->pinned_off = 0;                                        // entry points are synchronous: the staging buffer is free again
+    sift_pool_reset(ctx);
+    int *cblock = (int *)sift_pool_alloc(ctx, sizeof(int) * 4 * u);          // per strip: candidates, keypoints before dedup, keypoints
+    if (!cblock) return VFSMS_ERR_CAPACITY;
+    std::vector<SiftStripOut> S(u);
+    const bool exact = bf_force_exact();
+    // detect + describe (+ pack): the strips are in shape order already
+    for (int i0 = 0; i0 < u;) {
+        const int h = T.strips[i0].h, w = T.strips[i0].w;
+        int i1 = i0;
+        while (i1 < u && T.strips[i1].h == h && T.strips[i1].w == w) i1++;
+        int gmax = 1;
+        TRY(sift_group_strips(ctx, h, w, params, &gmax));
+        for (int a = i0; a < i1; a += gmax) {
+            const int g = std::min(gmax, i1 - a);
+            TRY(ctx_arena_reserve(ctx, (sizeof(SiftSrcHost) + 2 * 64 + sizeof(PackJob) + 1024) * (size_t)g + 65536));
+            std::vector<SiftSrcHost> src(g);
+            for (int k = 0; k < g; k++) { src[k].p = T.strips[a + k].p; src[k].stride = T.strips[a + k].stride; }
+            ProfScope ps(ctx, "sift_group");
+            TRY(sift_group_device(ctx, src.data(), g, h, w, params, cblock + 4 * a, &S[a], nullptr));
+            if (!exact) {
+                std::vector<PackJob> pj; int maxn = 0;
+                for (int k = 0; k < g; k++) {
+                    const SiftStripOut &o = S[a + k];
+                    if (o.n == 0) continue;
+                    pj.push_back(PackJob{o.desc, cblock + 4 * (a + k) + 2, o.d8, o.nrm});
+                    maxn = std::max(maxn, o.n);
+                }
+                if (!pj.empty()) {
+                    PackJob *dP;
+                    TRY(upload_pinned(ctx, pj.data(), sizeof(PackJob) * pj.size(), (void **)&dP));
+                    TRY(launch_pack_i8_d128(ctx, dP, (int)pj.size(), maxn));
+                }
+            }
+        }
+        i0 = i1;
+    }
+    // match + vote: capacities are the exact counts
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                 // the last group's launch records have left the staging buffer, reset below
+    int maxcap = 1; long long waves = 0;
+    std::vector<int> caps(n);
+    for (int s_ = 0; s_ < n; s_++) {
+        caps[s_] = std::max(S[T.a[s_]].n, 1);
+        maxcap = std::max(maxcap, caps[s_]);
+        waves += (caps[s_] + 63) / 64;
+    }
+    int maxt = 1;
+    for (int s_ = 0; s_ < n; s_++) maxt = std::max(maxt, S[T.b[s_]].n);
+    const int ns = exact ? pick_nsplit(maxcap, maxt, n, 128)
+                         : (int)std::max<long long>(1, std::min<long long>({8, (4096 + waves - 1) / waves, (long long)(maxt + 255) / 256}));
+    size_t need = 0;
+    for (int s_ = 0; s_ < n; s_++) need += match_bytes(caps[s_], ns);
+    need += sizeof(MatchDev) * n + (64 + VFSMS_ATTEMPT_INTS * sizeof(int32_t)) * (size_t)n + 65536;
+    TRY(ctx_arena_reserve(ctx, need));
+    ctx->pinned_off = 0;
+    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
+    std::vector<MatchDev> M(n);
+    for (int s_ = 0; s_ < n; s_++) {
+        const int k = ord[s_], ia = T.a[s_], ib = T.b[s_];
+        const SiftStripOut &A = S[ia], &B = S[ib];
+        memset(&M[s_], 0, sizeof(MatchDev));
+        TRY(match_carve(ctx, &M[s_], caps[s_], 128, ns));
+        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
+        M[s_].q = A.desc; M[s_].t = B.desc;
+        M[s_].q8 = A.d8; M[s_].t8 = B.d8; M[s_].qn2 = A.nrm; M[s_].tn2 = B.nrm;
+        M[s_].nq_ptr = cblock + 4 * ia + 2; M[s_].nt_ptr = cblock + 4 * ib + 2;
+        M[s_].kq = A.xy; M[s_].kt = B.xy;
+    }
+    MatchDev *dM;
+    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
+    if (exact) { TRY(launch_bf_l2(ctx, dM, n, maxcap, ns, 128)); }
+    else { TRY(launch_bf_i8_d128(ctx, dM, n, maxcap, ns)); }
+    TRY(launch_ratio_mode(ctx, dM, n, maxcap, ratio, offset_evaluate));
+    HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
 }
 
 extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,

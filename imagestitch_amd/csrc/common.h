@@ -154,6 +154,9 @@ struct MatchDev {
     uint2 *c_ent; int *c_cnt;
     float2 *c_m12;                    // per (list, query): best / second-best hi-only score of the bounds pass
     unsigned short *q16, *t16;        // split-bf16 operands of the filter (k_bf_split16): BF16_ROW uint16 per descriptor row
+    // integer 2-NN (fused SIFT path, k_bf_i8_d128): descriptors as int8 (element - 128), 128 bytes per row, and the squared norms of those
+    // rows; rows padded to whole 64-row tiles (zero rows, norm BFI_PAD_NORM)
+    const int8_t *q8, *t8; const int *qn2, *tn2;
     // merged
     float *d1; float *d2; int *i1;
     int *match_flag; int *match_pos;
@@ -174,6 +177,7 @@ struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; 
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct ProfRec { int id; hipEvent_t a, b; };
+struct SiftChunk { char *p; size_t bytes, off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
 
 struct vfsms_ctx {
     int device;
@@ -205,6 +209,8 @@ struct vfsms_ctx {
     void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;
     void *sift_scratch = nullptr; size_t sift_scratch_bytes = 0;   // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
+    std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
+    size_t sift_group_bytes = (size_t)4 << 30;                     // pyramid bytes resident at once in a fused SIFT batch (VFSMS_SIFT_GROUP_BYTES overrides)
     CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a batch (vfsms_features_surf_batch), freed with its last set
@@ -251,6 +257,10 @@ size_t match_filter_bytes(int capq, int capt, int cns);
 int match_filter_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int capt, int cns);
 int launch_bf_l2_filtered(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int capt, int cns);
 int launch_bf_l2(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int dim);
+#define BFI_PAD_NORM 0x3fffffff
+struct PackJob { const float *src; const int *n_ptr; int8_t *dst; int *nrm; };   // one strip's descriptors -> int8 rows + norms
+int launch_pack_i8_d128(vfsms_ctx *ctx, const PackJob *d_jobs, int njobs, int max_rows);
+int launch_bf_i8_d128(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit);
 int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq);
 int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio);
 int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate);
@@ -296,6 +306,15 @@ int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r
 #define VFSMS_SIFT_MAX_LAYERS 8
 #define VFSMS_SIFT_MAX_OCT 16
 int sift_check_params(const vfsms_sift_params *p);
+struct SiftSrcHost { const uint8_t *p; int stride; };
+struct SiftStripOut { int n; int cand0; float *xy; float *desc; int8_t *d8; int *nrm; };   // n keypoints: positions, float descriptors, packed rows + norms (sift_pad_rows(n) rows)
+static inline size_t sift_pad_rows(int n) { return ((size_t)n + 63) & ~(size_t)63; }
+void sift_pool_reset(vfsms_ctx *ctx);
+void sift_pool_free(vfsms_ctx *ctx);
+void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes);
+int sift_group_strips(vfsms_ctx *ctx, int h, int w, const vfsms_sift_params *p, int *g_out);
+int sift_group_device(vfsms_ctx *ctx, const SiftSrcHost *srcs, int g, int h, int w, const vfsms_sift_params *p, int *counts,
+                      SiftStripOut *out, const vfsms_keypoint **kp_tmp);
 int sift_detect_describe_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
                                 float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out);
 int sift_pyramid_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,

@@ -138,6 +138,120 @@ __global__ __launch_bounds__(256) void k_bf_l2_gen(const MatchDev *jobs)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Exact matrix-core 2-NN for 128-d descriptors with integer elements 0..255 (the fused SIFT attempt path).
+//
+// Every element k_sift_describe writes is an integer 0..255, so a squared distance is an integer <= 128 * 255^2 = 8 323 200 < 2^24:
+// float accumulation gives it exactly in any order, and so does |q'|^2 + |t'|^2 - 2 q'.t' in int32 with q' = q - 128, t' = t - 128 (the
+// shift cancels in q - t; |q'|^2 <= 2^21, |q'.t'| <= 2^21).  The dot products run on v_mfma_i32_16x16x64_i8; the float of the integer
+// distance IS the dsq k_bf_l2_gen<128> forms, and it goes through the same knn_update (sqrtf, strict <), so (i1, d1, d2) come out
+// bit for bit -- no verification pass.
+// k_pack_i8_d128 writes a strip's rows once (per strip, not per job).  k_bf_i8_d128: a wave keeps 64 queries as the B operands of four
+// 16-column tiles (8 x 4 VGPRs) and streams 16-train tiles as the A operand straight from memory (the four waves of a workgroup
+// walk the same trains, 2 KB a tile); lane l then holds, for query column l & 15, the trains 4 (l >> 4) .. + 3 of the tile.  A lane
+// compares the integer score |t'|^2 - 2 q'.t' with its own integer threshold (second best so far - |q'|^2) and only enters knn_update
+// for a train that beats it.  A lane sees its trains in ascending order, so its list is the reference's over its subset; the four
+// lanes of a query column are merged by (distance, index), which is what the ascending scan gives over the union; train splits are
+// whole ranges, merged by k_merge_ratio in ascending order as for every other kernel here.
+// ---------------------------------------------------------------------------------------------------
+typedef int i4v __attribute__((ext_vector_type(4)));
+
+// one workgroup per 64 rows of a strip, 4 lanes per row; rows at and beyond the strip's count (up to the 64-row tile) become zero rows
+// with the norm BFI_PAD_NORM
+__global__ __launch_bounds__(256) void k_pack_i8_d128(const PackJob *jobs)
+{
+    const PackJob J = jobs[blockIdx.y];
+    const int n = *J.n_ptr, r0 = blockIdx.x * 64;
+    if (r0 >= n) return;
+    const int row = r0 + (threadIdx.x >> 2), part = threadIdx.x & 3;
+    int nrm = 0;
+    unsigned w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = 0;
+    if (row < n) {
+        const float4 *src = (const float4 *)(J.src + (size_t)row * 128 + part * 32);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const float4 v = src[i];
+            const int a = (int)v.x - 128, b = (int)v.y - 128, c = (int)v.z - 128, d = (int)v.w - 128;
+            nrm += a * a + b * b + c * c + d * d;
+            w[i] = (unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24);
+        }
+    }
+    nrm += __shfl_xor(nrm, 1, 64);
+    nrm += __shfl_xor(nrm, 2, 64);
+    uint4 *dst = (uint4 *)(J.dst + (size_t)row * 128 + part * 32);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    if (part == 0) J.nrm[row] = row < n ? nrm : BFI_PAD_NORM;
+}
+
+__device__ __forceinline__ void knn_merge(float &b1, float &b2, int &i1, float ob1, float ob2, int oi1)
+{
+    if (ob1 < b1 || (ob1 == b1 && (unsigned)oi1 < (unsigned)i1)) { b2 = fminf(ob2, b1); b1 = ob1; i1 = oi1; }
+    else b2 = fminf(b2, ob1);
+}
+
+// block = 256 threads = 4 waves x 64 queries; grid (query blocks, train splits, jobs)
+__global__ __launch_bounds__(256) void k_bf_i8_d128(const MatchDev *jobs)
+{
+    const MatchDev &J = jobs[blockIdx.z];
+    const int nq = __builtin_amdgcn_readfirstlane(*J.nq_ptr), nt = __builtin_amdgcn_readfirstlane(*J.nt_ptr);
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int qw = blockIdx.x * 256 + (threadIdx.x >> 6) * 64;
+    if (qw >= nq) return;
+    // whole 16-train tiles per split
+    const int nsplit = gridDim.y, sp = blockIdx.y;
+    const int tiles = (nt + 15) >> 4, tchunk = (tiles + nsplit - 1) / nsplit;
+    const int t0 = sp * tchunk * 16, t1 = min(tiles * 16, t0 + tchunk * 16);
+    i4v qb[4][2];
+    int qn[4], thr[4], i1[4];
+    float b1[4], b2[4], b1s[4], b2s[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int q = qw + 16 * u + c;                                  // < sift_pad_rows(nq): packed (zero) rows exist up to there
+        const i4v *qp = (const i4v *)(J.q8 + (size_t)q * 128);
+        qb[u][0] = qp[g]; qb[u][1] = qp[4 + g];
+        qn[u] = J.qn2[q];
+        thr[u] = 0x7fffffff; i1[u] = -1;
+        b1[u] = b2[u] = b1s[u] = b2s[u] = INFINITY;
+    }
+    for (int jt = t0; jt < t1; jt += 16) {
+        const i4v *tp = (const i4v *)(J.t8 + (size_t)(jt + c) * 128);
+        const i4v a0 = tp[g], a1 = tp[4 + g];
+        const i4v tn = *(const i4v *)(J.tn2 + jt + 4 * g);
+        const int j0 = jt + 4 * g;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            i4v acc = {0, 0, 0, 0};
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, qb[u][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, qb[u][1], acc, 0, 0, 0);
+            const int s0 = tn[0] - 2 * acc[0], s1 = tn[1] - 2 * acc[1], s2 = tn[2] - 2 * acc[2], s3 = tn[3] - 2 * acc[3];
+            if (min(min(s0, s1), min(s2, s3)) < thr[u]) {
+                // ascending train order; a padded row (j >= nt) never counts
+                if (s0 < thr[u] && j0 < nt) knn_update((float)(s0 + qn[u]), j0, b1[u], b2[u], i1[u], b1s[u], b2s[u]);
+                if (s1 < thr[u] && j0 + 1 < nt) knn_update((float)(s1 + qn[u]), j0 + 1, b1[u], b2[u], i1[u], b1s[u], b2s[u]);
+                if (s2 < thr[u] && j0 + 2 < nt) knn_update((float)(s2 + qn[u]), j0 + 2, b1[u], b2[u], i1[u], b1s[u], b2s[u]);
+                if (s3 < thr[u] && j0 + 3 < nt) knn_update((float)(s3 + qn[u]), j0 + 3, b1[u], b2[u], i1[u], b1s[u], b2s[u]);
+                thr[u] = b2s[u] == INFINITY ? 0x7fffffff : (int)b2s[u] - qn[u];
+            }
+        }
+    }
+    const size_t o = (size_t)sp * J.capq;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        float B1 = b1[u], B2 = b2[u]; int I1 = i1[u];
+#pragma unroll
+        for (int d = 16; d <= 32; d <<= 1) {
+            const float ob1 = __shfl_xor(B1, d, 64), ob2 = __shfl_xor(B2, d, 64);
+            const int oi1 = __shfl_xor(I1, d, 64);
+            knn_merge(B1, B2, I1, ob1, ob2, oi1);
+        }
+        const int q = qw + 16 * u + c;
+        if (g == 0 && q < nq) { J.p_d1[o + q] = B1; J.p_d2[o + q] = B2; J.p_i1[o + q] = I1; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // MFMA candidate filter + exact verification (DIM = 64, descriptors of norm <= 1: the fused SURF attempt path).
 //
 // The 2-NN of a query under the reference's float arithmetic are, with a wide safety margin, among the trains whose
@@ -1107,6 +1221,25 @@ int launch_bf_l2(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, in
         vfsms_set_error("bf_l2: descriptor dim %d unsupported (64, 128, 32)", dim);
         return VFSMS_ERR_UNSUPPORTED;
     }
+    HIP_TRY(hipGetLastError());
+    return VFSMS_OK;
+}
+
+int launch_pack_i8_d128(vfsms_ctx *ctx, const PackJob *d_jobs, int njobs, int max_rows)
+{
+    if (njobs <= 0 || max_rows <= 0) return VFSMS_OK;
+    ProfScope ps(ctx, "pack_i8");
+    hipLaunchKernelGGL(k_pack_i8_d128, dim3((max_rows + 63) / 64, njobs), dim3(256), 0, ctx->stream, d_jobs);
+    HIP_TRY(hipGetLastError());
+    return VFSMS_OK;
+}
+
+// integer 2-NN of jobs whose q8 / t8 / qn2 / tn2 were packed by k_pack_i8_d128 (jobs carved with the same nsplit)
+int launch_bf_i8_d128(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit)
+{
+    if (njobs <= 0 || capq <= 0) return VFSMS_OK;
+    ProfScope ps(ctx, "bf_i8");
+    hipLaunchKernelGGL(k_bf_i8_d128, dim3((capq + 255) / 256, nsplit, njobs), dim3(256), 0, ctx->stream, d_jobs);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }

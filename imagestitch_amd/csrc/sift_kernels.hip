@@ -6,19 +6,22 @@
 // ascending order; exp / powf through det_exp (detmath.h); the 3 x 3 solve by Cramer's rule over the float determinant; histogram bins
 // summed in raster sample order; duplicates resolved to the first keypoint in detection order; descriptor norms summed k = 0 .. 127.
 //
-// Launches of one call:
+// Launches of one group of strips (their number follows octaves x levels, not the number of strips):
 //   pyramid   upsample rows + columns (exact), then per level a row blur and a column blur that also writes the DoG against the level
 //             below; each octave's level 0 is the INTER_NEAREST decimation of the previous octave's level nOctaveLayers
-//   extrema   per octave a counting pass (26-neighbour test + adjustLocalExtrema + contrast / edge tests), one scan over the
-//             (octave, layer, row) counts, the single host sync (the candidate count sizes what follows), then the writing pass, which
-//             recomputes and places the survivors of a row in column order -> candidates in detection order without atomics
+//   extrema   per octave a counting pass (26-neighbour test + adjustLocalExtrema + contrast / edge tests), one scan per strip over its
+//             (octave, layer, row) counts, the group's first host sync (the candidate counts size what follows), then the writing pass,
+//             which recomputes and places the survivors of a row in column order -> candidates in detection order without atomics
 //   orientation  one wave per candidate: the window's (bin, weight * magnitude) samples are staged in LDS 64 at a time and the lane that
 //             owns a bin adds its samples in raster order; smoothing, peaks, parabolic interpolation
 //   keypoints scan of the per-candidate peak counts, emit, duplicate flags (each keypoint against every earlier one, LDS tiles), scan,
-//             compaction with the firstOctave adjustment
+//             compaction with the firstOctave adjustment; the group's second host sync (the keypoint counts size what is kept)
 //   descriptor one wave per keypoint: samples staged in LDS; the lane that owns one of the 6 x 6 spatial cells adds the two orientation
 //             bins a sample gives that cell, in sample order; wrap, clamp at 0.2 |h|, renormalise to 512, saturate to u8
-// Scratch lives in the context (sift_scratch, sift_kp) and grows to the largest call seen.
+// Every kernel is batched over the strips of a group (blockIdx.z, or blockIdx.x for the scans): the strips of a group have one shape,
+// so one plan serves them all and strip z's planes sit z * zs floats behind strip 0's.  The single-image entry points run the group of
+// one.  A group's pyramids live in ctx->sift_scratch, its candidates and keypoints in ctx->sift_kp (both grow to the largest group
+// seen); what outlives the group -- keypoint positions, descriptors, their packed int8 form -- is taken from ctx->sift_pool.
 #include "common.h"
 #include "detmath.h"
 #include <math.h>
@@ -40,6 +43,9 @@ struct SiftOct {                            // one octave's levels
 };
 struct SiftCand { float x, y, size, response; int octave, o, layer, r, c; };
 struct SiftCfg { int L; float thr, contrast, edge, sigma; };
+struct SiftSrc { const uint8_t *p; int stride; };                       // one strip's pixels, read in place
+// one strip's share of a group's candidate / keypoint arrays (SIFT_MAX_PEAKS keypoint slots per candidate) and where its results go
+struct SiftSeg { int cand0, ncand; float *desc; float *xy; };
 
 __device__ __forceinline__ int sift_reflect101(int i, int n)
 {
@@ -73,19 +79,22 @@ __device__ __forceinline__ float sift_atan2_deg(float y, float x)   // cv::fastA
 
 // ---- pyramid ---------------------------------------------------------------------------------------------------------------------
 // INTER_LINEAR 2x along rows: out[y][d] = a * w0 + b * w1 with a = src[x0], b = src[x0 + 1] clamped, (w0, w1) = (0.25, 0.75) for even d
-__global__ void k_sift_up_rows(const uint8_t *src, int h, int w, float *dst)
+__global__ void k_sift_up_rows(const SiftSrc *srcs, int h, int w, float *dst, size_t zs)
 {
     const int d = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (d >= 2 * w) return;
+    const uint8_t *src = srcs[blockIdx.z].p; const size_t ss = (size_t)srcs[blockIdx.z].stride;
+    dst += blockIdx.z * zs;
     const int x0 = (d & 1) ? d >> 1 : (d >> 1) - 1;
     const float w0 = (d & 1) ? 0.75f : 0.25f, w1 = (d & 1) ? 0.25f : 0.75f;
-    const float a = (float)src[(size_t)y * w + min(max(x0, 0), w - 1)], b = (float)src[(size_t)y * w + min(max(x0 + 1, 0), w - 1)];
+    const float a = (float)src[(size_t)y * ss + min(max(x0, 0), w - 1)], b = (float)src[(size_t)y * ss + min(max(x0 + 1, 0), w - 1)];
     dst[(size_t)y * 2 * w + d] = a * w0 + b * w1;
 }
-__global__ void k_sift_up_cols(const float *src, int h, int W, float *dst)
+__global__ void k_sift_up_cols(const float *src, int h, int W, float *dst, size_t zs)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, d = blockIdx.y;
     if (x >= W) return;
+    src += blockIdx.z * zs; dst += blockIdx.z * zs;
     const int y0 = (d & 1) ? d >> 1 : (d >> 1) - 1;
     const float w0 = (d & 1) ? 0.75f : 0.25f, w1 = (d & 1) ? 0.25f : 0.75f;
     const float a = src[(size_t)min(max(y0, 0), h - 1) * W + x], b = src[(size_t)min(max(y0 + 1, 0), h - 1) * W + x];
@@ -94,9 +103,10 @@ __global__ void k_sift_up_cols(const float *src, int h, int W, float *dst)
 
 // row pass of the separable Gaussian: acc = t[0] * s[x - r], then acc + t[k] * s[x - r + k], REFLECT_101
 #define SIFT_ROW_TILE 256
-__global__ __launch_bounds__(256) void k_sift_blur_rows(const float *src, float *dst, int R, int C, SiftTaps T)
+__global__ __launch_bounds__(256) void k_sift_blur_rows(const float *src, float *dst, int R, int C, SiftTaps T, size_t zs)
 {
     __shared__ float s[SIFT_ROW_TILE + 2 * SIFT_MAX_TAPS];
+    src += blockIdx.z * zs; dst += blockIdx.z * zs;
     const int y = blockIdx.y, x0 = blockIdx.x * SIFT_ROW_TILE, r = T.n >> 1;
     const float *row = src + (size_t)y * C;
     for (int q = threadIdx.x; q < SIFT_ROW_TILE + 2 * r; q += blockDim.x) {
@@ -111,10 +121,12 @@ __global__ __launch_bounds__(256) void k_sift_blur_rows(const float *src, float 
     dst[(size_t)y * C + x] = acc;
 }
 // column pass; with prev != null also dog = out - prev (the DoG of the level below)
-__global__ __launch_bounds__(256) void k_sift_blur_cols(const float *src, float *dst, const float *prev, float *dog, int R, int C, SiftTaps T)
+__global__ __launch_bounds__(256) void k_sift_blur_cols(const float *src, float *dst, const float *prev, float *dog, int R, int C, SiftTaps T, size_t zs)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, r = T.n >> 1;
     if (x >= C) return;
+    src += blockIdx.z * zs; dst += blockIdx.z * zs;
+    if (prev) { prev += blockIdx.z * zs; dog += blockIdx.z * zs; }
     float acc = T.t[0] * src[(size_t)sift_reflect101(y - r, R) * C + x];
     for (int k = 1; k < T.n; k++) acc = acc + T.t[k] * src[(size_t)sift_reflect101(y - r + k, R) * C + x];
     const size_t o = (size_t)y * C + x;
@@ -122,28 +134,30 @@ __global__ __launch_bounds__(256) void k_sift_blur_cols(const float *src, float 
     if (prev) dog[o] = acc - prev[o];
 }
 // INTER_NEAREST to (R / 2, C / 2): source floor(d * if) in double, clamped
-__global__ void k_sift_decimate(const float *src, int R, int C, float *dst, int dR, int dC, double ify, double ifx)
+__global__ void k_sift_decimate(const float *src, int R, int C, float *dst, int dR, int dC, double ify, double ifx, size_t zs)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= dC) return;
+    src += blockIdx.z * zs; dst += blockIdx.z * zs;
     const int sy = min((int)floor((double)y * ify), R - 1), sx = min((int)floor((double)x * ifx), C - 1);
     dst[(size_t)y * dC + x] = src[(size_t)sy * C + sx];
 }
 
 // ---- extrema ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sift_at(const SiftOct &O, int l, int r, int c) { return O.d[l][(size_t)r * O.C + c]; }
+// O names strip 0's planes; Z is the float offset of the strip at hand
+__device__ __forceinline__ float sift_at(const SiftOct &O, size_t Z, int l, int r, int c) { return O.d[l][Z + (size_t)r * O.C + c]; }
 
 // the 26-neighbour test, then adjustLocalExtrema and the contrast / edge tests; true -> *out filled
-__device__ bool sift_candidate(const SiftOct &O, const SiftCfg &P, int o, int l, int r, int c, SiftCand *out)
+__device__ bool sift_candidate(const SiftOct &O, size_t Z, const SiftCfg &P, int o, int l, int r, int c, SiftCand *out)
 {
-    const float val = sift_at(O, l, r, c);
+    const float val = sift_at(O, Z, l, r, c);
     if (!(fabsf(val) > P.thr)) return false;
     bool ge = true, le = true;
     for (int dl = -1; dl <= 1; dl++)
         for (int dr = -1; dr <= 1; dr++)
             for (int dc = -1; dc <= 1; dc++) {
                 if (dl == 0 && dr == 0 && dc == 0) continue;
-                const float nb = sift_at(O, l + dl, r + dr, c + dc);
+                const float nb = sift_at(O, Z, l + dl, r + dr, c + dc);
                 ge = ge && val >= nb; le = le && val <= nb;
             }
     if (!((val > 0 && ge) || (val < 0 && le))) return false;
@@ -152,15 +166,15 @@ __device__ bool sift_candidate(const SiftOct &O, const SiftCfg &P, int o, int l,
     float xi = 0, xr = 0, xc = 0;
     int step = 0;
     for (; step < SIFT_MAX_STEPS; step++) {
-        const float v = sift_at(O, l, r, c);
-        const float xp = sift_at(O, l, r, c + 1), xm = sift_at(O, l, r, c - 1), yp = sift_at(O, l, r + 1, c), ym = sift_at(O, l, r - 1, c);
-        const float sp = sift_at(O, l + 1, r, c), sm = sift_at(O, l - 1, r, c);
+        const float v = sift_at(O, Z, l, r, c);
+        const float xp = sift_at(O, Z, l, r, c + 1), xm = sift_at(O, Z, l, r, c - 1), yp = sift_at(O, Z, l, r + 1, c), ym = sift_at(O, Z, l, r - 1, c);
+        const float sp = sift_at(O, Z, l + 1, r, c), sm = sift_at(O, Z, l - 1, r, c);
         const float b0 = (xp - xm) * deriv_scale, b1 = (yp - ym) * deriv_scale, b2 = (sp - sm) * deriv_scale;
         const float v2 = v * 2.f;
         const float dxx = ((xp + xm) - v2) * second_scale, dyy = ((yp + ym) - v2) * second_scale, dss = ((sp + sm) - v2) * second_scale;
-        const float dxy = (((sift_at(O, l, r + 1, c + 1) - sift_at(O, l, r + 1, c - 1)) - sift_at(O, l, r - 1, c + 1)) + sift_at(O, l, r - 1, c - 1)) * cross_scale;
-        const float dxs = (((sift_at(O, l + 1, r, c + 1) - sift_at(O, l + 1, r, c - 1)) - sift_at(O, l - 1, r, c + 1)) + sift_at(O, l - 1, r, c - 1)) * cross_scale;
-        const float dys = (((sift_at(O, l + 1, r + 1, c) - sift_at(O, l + 1, r - 1, c)) - sift_at(O, l - 1, r + 1, c)) + sift_at(O, l - 1, r - 1, c)) * cross_scale;
+        const float dxy = (((sift_at(O, Z, l, r + 1, c + 1) - sift_at(O, Z, l, r + 1, c - 1)) - sift_at(O, Z, l, r - 1, c + 1)) + sift_at(O, Z, l, r - 1, c - 1)) * cross_scale;
+        const float dxs = (((sift_at(O, Z, l + 1, r, c + 1) - sift_at(O, Z, l + 1, r, c - 1)) - sift_at(O, Z, l - 1, r, c + 1)) + sift_at(O, Z, l - 1, r, c - 1)) * cross_scale;
+        const float dys = (((sift_at(O, Z, l + 1, r + 1, c) - sift_at(O, Z, l + 1, r - 1, c)) - sift_at(O, Z, l - 1, r + 1, c)) + sift_at(O, Z, l - 1, r - 1, c)) * cross_scale;
         // Matx33f H(dxx, dxy, dxs, dxy, dyy, dys, dxs, dys, dss).solve(dD, DECOMP_LU): Cramer's rule over the float determinant
         const float a00 = dxx, a01 = dxy, a02 = dxs, a10 = dxy, a11 = dyy, a12 = dys, a20 = dxs, a21 = dys, a22 = dss;
         const float det = (a00 * (a11 * a22 - a21 * a12) - a01 * (a10 * a22 - a20 * a12)) + a02 * (a10 * a21 - a20 * a11);
@@ -179,16 +193,16 @@ __device__ bool sift_candidate(const SiftOct &O, const SiftCfg &P, int o, int l,
         if (l < 1 || l > L || c < SIFT_BORDER || c >= C - SIFT_BORDER || r < SIFT_BORDER || r >= R - SIFT_BORDER) return false;
     }
     if (step >= SIFT_MAX_STEPS) return false;
-    const float v = sift_at(O, l, r, c);
-    const float xp = sift_at(O, l, r, c + 1), xm = sift_at(O, l, r, c - 1), yp = sift_at(O, l, r + 1, c), ym = sift_at(O, l, r - 1, c);
-    const float sp = sift_at(O, l + 1, r, c), sm = sift_at(O, l - 1, r, c);
+    const float v = sift_at(O, Z, l, r, c);
+    const float xp = sift_at(O, Z, l, r, c + 1), xm = sift_at(O, Z, l, r, c - 1), yp = sift_at(O, Z, l, r + 1, c), ym = sift_at(O, Z, l, r - 1, c);
+    const float sp = sift_at(O, Z, l + 1, r, c), sm = sift_at(O, Z, l - 1, r, c);
     const float b0 = (xp - xm) * deriv_scale, b1 = (yp - ym) * deriv_scale, b2 = (sp - sm) * deriv_scale;
     const float t = ((0.f + b0 * xc) + b1 * xr) + b2 * xi;
     const float contr = v * img_scale + t * 0.5f;
     if (fabsf(contr) * (float)L < P.contrast) return false;
     const float v2 = v * 2.f;
     const float dxx = ((xp + xm) - v2) * second_scale, dyy = ((yp + ym) - v2) * second_scale;
-    const float dxy = (((sift_at(O, l, r + 1, c + 1) - sift_at(O, l, r + 1, c - 1)) - sift_at(O, l, r - 1, c + 1)) + sift_at(O, l, r - 1, c - 1)) * cross_scale;
+    const float dxy = (((sift_at(O, Z, l, r + 1, c + 1) - sift_at(O, Z, l, r + 1, c - 1)) - sift_at(O, Z, l, r - 1, c + 1)) + sift_at(O, Z, l, r - 1, c - 1)) * cross_scale;
     const float tr = dxx + dyy, dt = dxx * dyy - dxy * dxy, e = P.edge;
     if (dt <= 0 || tr * tr * e >= (e + 1.f) * (e + 1.f) * dt) return false;
     const float s = (float)(1 << o);
@@ -204,9 +218,15 @@ __device__ bool sift_candidate(const SiftOct &O, const SiftCfg &P, int o, int l,
 
 // one workgroup per (row, layer) of an octave: how many candidates the row gives (pass 0), or the candidates themselves in column order
 // at cand + base[row slot] (pass 1)
-__global__ __launch_bounds__(256) void k_sift_extrema(SiftOct O, SiftCfg P, int o, int *counts, const int *base, SiftCand *cand)
+// strip blockIdx.z: its counts / bases zs ints behind strip 0's, its candidates at cand + segs[z].cand0
+__global__ __launch_bounds__(256) void k_sift_extrema(SiftOct O, SiftCfg P, int o, int *counts, const int *base, SiftCand *cand, size_t zs,
+                                                      const SiftSeg *segs)
 {
     __shared__ int wsum[4];
+    const size_t Z = blockIdx.z * zs;
+    if (counts) counts += Z;
+    if (base) base += Z;
+    if (cand) cand += segs[blockIdx.z].cand0;
     const int r = blockIdx.x, l = blockIdx.y + 1, slot = (l - 1) * O.R + r;
     const bool row_ok = r >= SIFT_BORDER && r < O.R - SIFT_BORDER;
     int running = base ? base[slot] : 0, total = 0;
@@ -214,7 +234,7 @@ __global__ __launch_bounds__(256) void k_sift_extrema(SiftOct O, SiftCfg P, int 
     for (int c0 = SIFT_BORDER; row_ok && c0 < O.C - SIFT_BORDER; c0 += 256) {
         const int c = c0 + threadIdx.x;
         SiftCand k;
-        const bool hit = c < O.C - SIFT_BORDER && sift_candidate(O, P, o, l, r, c, &k);
+        const bool hit = c < O.C - SIFT_BORDER && sift_candidate(O, Z, P, o, l, r, c, &k);
         const unsigned long long m = __ballot(hit);
         if (lane == 0) wsum[wv] = __popcll(m);
         __syncthreads();
@@ -228,10 +248,20 @@ __global__ __launch_bounds__(256) void k_sift_extrema(SiftOct O, SiftCfg P, int 
 }
 
 // exclusive scan of n ints (n_dev overrides n) by one workgroup of 1024; out[n] = total, *total_out too
-__global__ __launch_bounds__(1024) void k_sift_scan(const int *in, int *out, int n, const int *n_dev, int *total_out)
+// strip blockIdx.x: arrays zs ints behind strip 0's (segs == null), or at its segment (per_cand slots per candidate, + 1 per strip for
+// the total); its counters are the 4 ints at tot + 4 z: n is read from tot[n_at] when n_at >= 0, the total goes to tot[tot_at]
+__global__ __launch_bounds__(1024) void k_sift_scan(const int *in, int *out, int n, size_t zs, const SiftSeg *segs, int per_cand,
+                                                    int *tot, int n_at, int tot_at)
 {
     __shared__ int s[1024];
-    if (n_dev) n = *n_dev;
+    const int z = blockIdx.x;
+    tot += 4 * z;
+    if (segs) {
+        const size_t o = (size_t)segs[z].cand0 * per_cand + z;
+        in += o; out += o;
+        n = segs[z].ncand;
+    } else { in += z * zs; out += z * zs; }
+    if (n_at >= 0) n = tot[n_at];
     const int t = threadIdx.x, per = (n + 1023) / 1024, a = min(t * per, n), b = min(a + per, n);
     int sum = 0;
     for (int i = a; i < b; i++) sum += in[i];
@@ -245,22 +275,24 @@ __global__ __launch_bounds__(1024) void k_sift_scan(const int *in, int *out, int
     }
     int run = s[t] - sum;
     for (int i = a; i < b; i++) { const int v = in[i]; out[i] = run; run += v; }
-    if (t == 1023) { out[n] = s[1023]; if (total_out) *total_out = s[1023]; }
+    if (t == 1023) { out[n] = s[1023]; tot[tot_at] = s[1023]; }
 }
 
 // ---- orientation: one wave per candidate -----------------------------------------------------------------------------------------
 struct SiftOcts { SiftOct o[VFSMS_SIFT_MAX_OCT]; };
 
-__global__ __launch_bounds__(64) void k_sift_orient(const SiftOcts *Os, const SiftCand *cand, int ncand, float *angles, int *npk)
+__global__ __launch_bounds__(64) void k_sift_orient(const SiftOcts *Os, size_t zs, const SiftSeg *segs, const SiftCand *cand, float *angles, int *npk)
 {
     __shared__ int sbin[64];
     __shared__ float sval[64];
     __shared__ float th[SIFT_ORI_BINS], hs[SIFT_ORI_BINS];
-    const int k = blockIdx.x, lane = threadIdx.x;
-    if (k >= ncand) return;
+    const int k = blockIdx.x, lane = threadIdx.x, z = blockIdx.z;
+    const SiftSeg S = segs[z];
+    if (k >= S.ncand) return;
+    cand += S.cand0; angles += (size_t)S.cand0 * SIFT_MAX_PEAKS; npk += S.cand0 + z;
     const SiftCand K = cand[k];
     const SiftOct &O = Os->o[K.o];
-    const float *img = O.g[K.layer];
+    const float *img = O.g[K.layer] + z * zs;
     const int R = O.R, C = O.C, px = K.c, py = K.r;
     const float scl = (K.size * 0.5f) / (float)(1 << K.o);
     const int radius = (int)rintf(4.5f * scl);
@@ -318,10 +350,13 @@ __global__ __launch_bounds__(64) void k_sift_orient(const SiftOcts *Os, const Si
 }
 
 // keypoints in detection order (before removeDuplicated and the firstOctave adjustment)
-__global__ void k_sift_emit(const SiftCand *cand, int ncand, const float *angles, const int *npk, const int *pos, vfsms_keypoint *kp)
+__global__ void k_sift_emit(const SiftSeg *segs, const SiftCand *cand, const float *angles, const int *npk, const int *pos, vfsms_keypoint *kp)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ncand) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.z;
+    const SiftSeg S = segs[z];
+    if (k >= S.ncand) return;
+    cand += S.cand0; angles += (size_t)S.cand0 * SIFT_MAX_PEAKS; npk += S.cand0 + z; pos += S.cand0 + z;
+    kp += (size_t)S.cand0 * SIFT_MAX_PEAKS;
     const SiftCand K = cand[k];
     for (int q = 0; q < npk[k]; q++) {
         vfsms_keypoint o;
@@ -332,11 +367,13 @@ __global__ void k_sift_emit(const SiftCand *cand, int ncand, const float *angles
 }
 
 // keep[k] = no earlier keypoint has the same (x, y, size, angle)
-__global__ __launch_bounds__(256) void k_sift_dedup(const vfsms_keypoint *kp, const int *n_dev, int *keep)
+__global__ __launch_bounds__(256) void k_sift_dedup(const SiftSeg *segs, const vfsms_keypoint *kp, const int *tot, int *keep)
 {
     __shared__ float4 s[256];
-    const int n = *n_dev, start = blockIdx.x * 256, k = start + threadIdx.x;
+    const int z = blockIdx.z;
+    const int n = tot[4 * z + 1], start = blockIdx.x * 256, k = start + threadIdx.x;
     if (start >= n) return;
+    kp += (size_t)segs[z].cand0 * SIFT_MAX_PEAKS; keep += (size_t)segs[z].cand0 * SIFT_MAX_PEAKS + z;
     float4 me = make_float4(0.f, 0.f, 0.f, 0.f);
     if (k < n) { const vfsms_keypoint q = kp[k]; me = make_float4(q.x, q.y, q.size, q.angle); }
     bool dup = false;
@@ -356,20 +393,21 @@ __global__ __launch_bounds__(256) void k_sift_dedup(const vfsms_keypoint *kp, co
 }
 
 // survivors, compacted, with the firstOctave = -1 adjustment (pt and size * 0.5, octave byte - 1)
-__global__ void k_sift_compact(const vfsms_keypoint *kp, const int *n_dev, const int *keep, const int *pos, vfsms_keypoint *out, float *xy)
+__global__ void k_sift_compact(const SiftSeg *segs, const vfsms_keypoint *kp, const int *tot, const int *keep, const int *pos, vfsms_keypoint *out)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= *n_dev || !keep[k]) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.z;
+    const size_t o = (size_t)segs[z].cand0 * SIFT_MAX_PEAKS;
+    kp += o; out += o; keep += o + z; pos += o + z;
+    if (k >= tot[4 * z + 1] || !keep[k]) return;
     vfsms_keypoint q = kp[k];
     q.x = q.x * 0.5f; q.y = q.y * 0.5f; q.size = q.size * 0.5f;
     q.octave = (q.octave & ~255) | ((q.octave - 1) & 255);
-    const int p = pos[k];
-    out[p] = q;
-    xy[2 * p] = q.x; xy[2 * p + 1] = q.y;
+    out[pos[k]] = q;
 }
 
 // ---- descriptor: one wave per keypoint -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_sift_describe(const SiftOcts *Os, const vfsms_keypoint *kps, const int *n_dev, int cap, float *desc)
+// also writes the keypoint's position to the strip's xy array (what the vote reads)
+__global__ __launch_bounds__(64) void k_sift_describe(const SiftOcts *Os, size_t zs, const SiftSeg *segs, const vfsms_keypoint *kps, const int *tot)
 {
     constexpr int d = 4, n = 8, HN = (d + 2) * (d + 2) * (n + 2);
     __shared__ float hist[HN];
@@ -377,16 +415,20 @@ __global__ __launch_bounds__(64) void k_sift_describe(const SiftOcts *Os, const 
     __shared__ float sv[64][8];
     __shared__ float dst[128];
     __shared__ float s_scale;
-    const int k = blockIdx.x, lane = threadIdx.x;
-    if (k >= *n_dev || k >= cap) return;
+    const int k = blockIdx.x, lane = threadIdx.x, z = blockIdx.z;
+    if (k >= tot[4 * z + 2]) return;
+    const SiftSeg S = segs[z];
+    kps += (size_t)S.cand0 * SIFT_MAX_PEAKS;
+    float *desc = S.desc;
     const vfsms_keypoint K = kps[k];
+    if (lane == 0) { S.xy[2 * k] = K.x; S.xy[2 * k + 1] = K.y; }
     int octv = K.octave & 255;
     const int layer = (K.octave >> 8) & 255;
     octv = octv < 128 ? octv : (-128 | octv);
     const float scale = octv >= 0 ? 1.f / (float)(1 << octv) : (float)(1 << -octv);
     const float size = K.size * scale, ptx = K.x * scale, pty = K.y * scale;
     const SiftOct &O = Os->o[octv + 1];
-    const float *img = O.g[layer];
+    const float *img = O.g[layer] + z * zs;
     const int rows = O.R, cols = O.C;
     float ang = 360.f - K.angle;
     if (fabsf(ang - 360.f) < FLT_EPSILON) ang = 0.f;
@@ -578,41 +620,70 @@ static void sift_octs(const SiftPlan &P, float *pyr, SiftOcts *Os)
 
 static inline size_t sift_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// the pyramid into ctx->sift_scratch: [pyramid][2 planes of the largest level][counts + scan]
-static int sift_build_pyramid(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const SiftPlan &P, float **pyr_out, int **counts_out)
+// ---- memory that outlives a group: chunks kept by the context, handed out by a bump pointer, all free again at the next call ----------
+void sift_pool_reset(vfsms_ctx *ctx) { for (auto &c : ctx->sift_pool) c.off = 0; }
+void sift_pool_free(vfsms_ctx *ctx)
 {
-    const size_t bytes = sift_align(P.pyr_floats * 4) + 2 * sift_align(P.max_plane * 4) + sift_align(((size_t)P.nslots + 1) * 8) + 4096;
-    TRY(sift_grow(&ctx->sift_scratch, &ctx->sift_scratch_bytes, bytes, ctx->stream));
+    for (auto &c : ctx->sift_pool) if (c.p) hipFree(c.p);
+    ctx->sift_pool.clear();
+}
+void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes)
+{
+    bytes = sift_align(bytes ? bytes : 1);
+    for (auto &c : ctx->sift_pool)
+        if (c.off + bytes <= c.bytes) { void *r = c.p + c.off; c.off += bytes; return r; }
+    SiftChunk c;
+    c.bytes = std::max(bytes, (size_t)256 << 20); c.off = bytes; c.p = nullptr;
+    if (hipMalloc((void **)&c.p, c.bytes) != hipSuccess) { vfsms_set_error("sift: out of device memory (%zu bytes)", c.bytes); return nullptr; }
+    ctx->sift_pool.push_back(c);
+    return c.p;
+}
+
+// bytes of one strip's block in ctx->sift_scratch: [pyramid][2 planes of the largest level][row counts + their scan]
+static size_t sift_strip_bytes(const SiftPlan &P)
+{
+    return sift_align(P.pyr_floats * 4) + 2 * sift_align(P.max_plane * 4) + sift_align(((size_t)P.nslots + 1) * 8);
+}
+
+// the pyramids of g strips of one shape into ctx->sift_scratch; *zs_out: floats (= ints) between the blocks of two strips
+static int sift_build_pyramid(vfsms_ctx *ctx, const SiftSrc *d_srcs, int g, int h, int w, const SiftPlan &P, float **pyr_out, int **counts_out,
+                              size_t *zs_out)
+{
+    const size_t sb = sift_strip_bytes(P);
+    TRY(sift_grow(&ctx->sift_scratch, &ctx->sift_scratch_bytes, sb * g + 4096, ctx->stream));
     char *base = (char *)ctx->sift_scratch;
     float *pyr = (float *)base; base += sift_align(P.pyr_floats * 4);
     float *t0 = (float *)base; base += sift_align(P.max_plane * 4);
     float *t1 = (float *)base; base += sift_align(P.max_plane * 4);
     *counts_out = (int *)base;
     *pyr_out = pyr;
+    const size_t zs = sb / 4;
+    *zs_out = zs;
     if (P.no == 0) return VFSMS_OK;
     SiftOcts Os;
     sift_octs(P, pyr, &Os);
     hipStream_t st = ctx->stream;
     const int W2 = 2 * w, H2 = 2 * h;
-    k_sift_up_rows<<<dim3((W2 + 255) / 256, h), 256, 0, st>>>(d_img, h, w, t1);
-    k_sift_up_cols<<<dim3((W2 + 255) / 256, H2), 256, 0, st>>>(t1, h, W2, t0);
+    const unsigned G = (unsigned)g;
+    k_sift_up_rows<<<dim3((W2 + 255) / 256, h, G), 256, 0, st>>>(d_srcs, h, w, t1, zs);
+    k_sift_up_cols<<<dim3((W2 + 255) / 256, H2, G), 256, 0, st>>>(t1, h, W2, t0, zs);
     SiftTaps T;
     for (int o = 0; o < P.no; o++) {
         const int R = P.R[o], C = P.C[o];
-        const dim3 rg((C + SIFT_ROW_TILE - 1) / SIFT_ROW_TILE, R), cg((C + 255) / 256, R);
+        const dim3 rg((C + SIFT_ROW_TILE - 1) / SIFT_ROW_TILE, R, G), cg((C + 255) / 256, R, G);
         float *g0 = (float *)Os.o[o].g[0];
         if (o == 0) {
             sift_taps(P.sig0, &T);
-            k_sift_blur_rows<<<rg, 256, 0, st>>>(t0, t1, R, C, T);
-            k_sift_blur_cols<<<cg, 256, 0, st>>>(t1, g0, nullptr, nullptr, R, C, T);
+            k_sift_blur_rows<<<rg, 256, 0, st>>>(t0, t1, R, C, T, zs);
+            k_sift_blur_cols<<<cg, 256, 0, st>>>(t1, g0, nullptr, nullptr, R, C, T, zs);
         } else {
             const int pr = P.R[o - 1], pc = P.C[o - 1];
-            k_sift_decimate<<<cg, 256, 0, st>>>(Os.o[o - 1].g[P.L], pr, pc, g0, R, C, 1.0 / ((double)R / pr), 1.0 / ((double)C / pc));
+            k_sift_decimate<<<cg, 256, 0, st>>>(Os.o[o - 1].g[P.L], pr, pc, g0, R, C, 1.0 / ((double)R / pr), 1.0 / ((double)C / pc), zs);
         }
         for (int i = 1; i < P.L + 3; i++) {
             sift_taps(P.sig[i], &T);
-            k_sift_blur_rows<<<rg, 256, 0, st>>>(Os.o[o].g[i - 1], t1, R, C, T);
-            k_sift_blur_cols<<<cg, 256, 0, st>>>(t1, (float *)Os.o[o].g[i], Os.o[o].g[i - 1], (float *)Os.o[o].d[i - 1], R, C, T);
+            k_sift_blur_rows<<<rg, 256, 0, st>>>(Os.o[o].g[i - 1], t1, R, C, T, zs);
+            k_sift_blur_cols<<<cg, 256, 0, st>>>(t1, (float *)Os.o[o].g[i], Os.o[o].g[i - 1], (float *)Os.o[o].d[i - 1], R, C, T, zs);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -633,8 +704,10 @@ int sift_pyramid_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, cons
     }
     if (!gauss && !dog) return VFSMS_OK;
     if (gf > cap_floats) { vfsms_set_error("sift_pyramid: %zu floats exceed the capacity %zu", gf, cap_floats); return VFSMS_ERR_CAPACITY; }
-    float *pyr; int *counts;
-    TRY(sift_build_pyramid(ctx, d_img, h, w, P, &pyr, &counts));
+    float *pyr; int *counts; size_t zs;
+    SiftSrc src = {d_img, w}, *d_src;
+    TRY(ctx_upload_small(ctx, &src, sizeof(src), (void **)&d_src));
+    TRY(sift_build_pyramid(ctx, d_src, 1, h, w, P, &pyr, &counts, &zs));
     size_t go = 0, dgo = 0;
     for (int o = 0; o < P.no; o++) {
         const size_t pl = (size_t)P.R[o] * P.C[o];
@@ -646,79 +719,142 @@ int sift_pyramid_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, cons
     return VFSMS_OK;
 }
 
-int sift_detect_describe_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
-                                float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out)
+// How many strips of (h, w) one group may hold under the context's pyramid budget (at least one)
+int sift_group_strips(vfsms_ctx *ctx, int h, int w, const vfsms_sift_params *p, int *g_out)
 {
     SiftPlan P;
     TRY(sift_plan(h, w, p, &P));
-    *n_out = 0;
-    if (P.no == 0) return VFSMS_OK;
-    float *pyr; int *counts;
-    TRY(sift_build_pyramid(ctx, d_img, h, w, P, &pyr, &counts));
+    static const long long env = getenv("VFSMS_SIFT_GROUP_BYTES") ? atoll(getenv("VFSMS_SIFT_GROUP_BYTES")) : 0;
+    const size_t budget = env > 0 ? (size_t)env : ctx->sift_group_bytes;
+    *g_out = (int)std::max<size_t>(1, std::min<size_t>(budget / std::max<size_t>(sift_strip_bytes(P), 1), 32768));
+    return VFSMS_OK;
+}
+
+// Detect and describe g strips of one shape (one group: their pyramids are resident together).  The caller arena holds the launch
+// records (a few hundred bytes per strip).  counts: 4 ints per strip in device memory that outlives the group -- [0] candidates,
+// [1] keypoints before removeDuplicated, [2] keypoints.  Two host syncs per group, whatever g is: the candidate counts size the
+// candidate and keypoint arrays, the keypoint counts size what is kept (out[k]: exact, from ctx->sift_pool).  kp_tmp (optional):
+// the group's full keypoint records in ctx->sift_kp, strip k's at kp_tmp + SIFT_MAX_PEAKS * cand0[k]; valid until the next group.
+int sift_group_device(vfsms_ctx *ctx, const SiftSrcHost *srcs, int g, int h, int w, const vfsms_sift_params *p, int *counts,
+                      SiftStripOut *out, const vfsms_keypoint **kp_tmp)
+{
+    SiftPlan P;
+    TRY(sift_plan(h, w, p, &P));
     hipStream_t st = ctx->stream;
+    for (int k = 0; k < g; k++) { out[k].n = 0; out[k].xy = nullptr; out[k].desc = nullptr; out[k].d8 = nullptr; out[k].nrm = nullptr; out[k].cand0 = 0; }
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int) * 4 * g, st));
+    if (P.no == 0) return VFSMS_OK;
+    std::vector<SiftSrc> hs(g);
+    for (int k = 0; k < g; k++) { hs[k].p = srcs[k].p; hs[k].stride = srcs[k].stride; }
+    SiftSrc *d_srcs;
+    TRY(ctx_upload_small(ctx, hs.data(), sizeof(SiftSrc) * g, (void **)&d_srcs));
+    float *pyr; int *rowc; size_t zs;
+    TRY(sift_build_pyramid(ctx, d_srcs, g, h, w, P, &pyr, &rowc, &zs));
     SiftOcts Os;
     sift_octs(P, pyr, &Os);
     SiftCfg cfg;
     cfg.L = P.L;
     cfg.thr = (float)(int)floor(0.5 * p->contrast_threshold / P.L * 255);
     cfg.contrast = (float)p->contrast_threshold; cfg.edge = (float)p->edge_threshold; cfg.sigma = (float)p->sigma;
-    int *pos = counts + P.nslots + 1;
-    int *d_total = (int *)ctx_arena_alloc(ctx, 4 * sizeof(int));
-    if (!d_total) { vfsms_set_error("sift: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    int *pos = rowc + P.nslots + 1;
+    const unsigned G = (unsigned)g;
     int slot0 = 0;
     for (int o = 0; o < P.no; o++) {
-        k_sift_extrema<<<dim3(P.R[o], P.L), 256, 0, st>>>(Os.o[o], cfg, o, counts + slot0, nullptr, nullptr);
+        k_sift_extrema<<<dim3(P.R[o], P.L, G), 256, 0, st>>>(Os.o[o], cfg, o, rowc + slot0, nullptr, nullptr, zs, nullptr);
         slot0 += P.L * P.R[o];
     }
-    k_sift_scan<<<1, 1024, 0, st>>>(counts, pos, P.nslots, nullptr, d_total);
-    int ncand = 0;
-    HIP_TRY(hipMemcpyAsync(&ncand, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                               // the one sync: the candidate count sizes the rest
+    k_sift_scan<<<G, 1024, 0, st>>>(rowc, pos, P.nslots, zs, nullptr, 0, counts, -1, 0);
+    HIP_TRY(hipGetLastError());
+    std::vector<int> hc((size_t)4 * g);
+    HIP_TRY(hipMemcpyAsync(hc.data(), counts, sizeof(int) * 4 * g, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                               // sync 1 of the group: the candidate counts size the rest
+    std::vector<SiftSeg> segs(g);
+    size_t ncand = 0; int maxc = 0;
+    for (int k = 0; k < g; k++) {
+        segs[k].cand0 = (int)ncand; segs[k].ncand = hc[4 * k]; segs[k].desc = nullptr; segs[k].xy = nullptr;
+        out[k].cand0 = (int)ncand;
+        ncand += hc[4 * k]; maxc = std::max(maxc, hc[4 * k]);
+        if (ncand * SIFT_MAX_PEAKS > (size_t)INT_MAX / 2) { vfsms_set_error("sift: too many candidates in one group (%zu)", ncand); return VFSMS_ERR_CAPACITY; }
+    }
     if (ncand == 0) return VFSMS_OK;
-    const size_t nkp_max = (size_t)ncand * SIFT_MAX_PEAKS, ndesc = std::min<size_t>(nkp_max, (size_t)std::max(cap, 0));
-    const size_t kbytes = sift_align(sizeof(SiftCand) * ncand) + sift_align(sizeof(float) * nkp_max) + 2 * sift_align(sizeof(int) * (ncand + 1)) +
-                          2 * sift_align(sizeof(vfsms_keypoint) * nkp_max) + 2 * sift_align(sizeof(int) * (nkp_max + 1)) +
-                          sift_align(sizeof(float) * 2 * nkp_max) + sift_align(sizeof(float) * 128 * std::max<size_t>(ndesc, 1)) +
-                          4096;
+    const size_t nkp_max = ncand * SIFT_MAX_PEAKS;
+    const size_t kbytes = sift_align(sizeof(SiftCand) * ncand) + sift_align(sizeof(float) * nkp_max) + 2 * sift_align(sizeof(int) * (ncand + g)) +
+                          2 * sift_align(sizeof(vfsms_keypoint) * nkp_max) + 2 * sift_align(sizeof(int) * (nkp_max + g)) + 4096;
     TRY(sift_grow(&ctx->sift_kp, &ctx->sift_kp_bytes, kbytes, st));
     char *b = (char *)ctx->sift_kp;
     auto take = [&](size_t bytes) { char *r = b; b += sift_align(bytes); return (void *)r; };
     SiftCand *cand = (SiftCand *)take(sizeof(SiftCand) * ncand);
     float *angles = (float *)take(sizeof(float) * nkp_max);
-    int *npk = (int *)take(sizeof(int) * (ncand + 1));
-    int *kpos = (int *)take(sizeof(int) * (ncand + 1));
+    int *npk = (int *)take(sizeof(int) * (ncand + g));
+    int *kpos = (int *)take(sizeof(int) * (ncand + g));
     vfsms_keypoint *kp0 = (vfsms_keypoint *)take(sizeof(vfsms_keypoint) * nkp_max);
     vfsms_keypoint *kp1 = (vfsms_keypoint *)take(sizeof(vfsms_keypoint) * nkp_max);
-    int *keep = (int *)take(sizeof(int) * (nkp_max + 1));
-    int *keep_pos = (int *)take(sizeof(int) * (nkp_max + 1));
-    float *xy = (float *)take(sizeof(float) * 2 * nkp_max);
-    float *d_desc = (float *)take(sizeof(float) * 128 * std::max<size_t>(ndesc, 1));
-    SiftOcts *d_os;
+    int *keep = (int *)take(sizeof(int) * (nkp_max + g));
+    int *keep_pos = (int *)take(sizeof(int) * (nkp_max + g));
+    SiftOcts *d_os; SiftSeg *d_segs;
     TRY(ctx_upload_small(ctx, &Os, sizeof(SiftOcts), (void **)&d_os));
+    TRY(ctx_upload_small(ctx, segs.data(), sizeof(SiftSeg) * g, (void **)&d_segs));
     slot0 = 0;
     for (int o = 0; o < P.no; o++) {
-        k_sift_extrema<<<dim3(P.R[o], P.L), 256, 0, st>>>(Os.o[o], cfg, o, nullptr, pos + slot0, cand);
+        k_sift_extrema<<<dim3(P.R[o], P.L, G), 256, 0, st>>>(Os.o[o], cfg, o, nullptr, pos + slot0, cand, zs, d_segs);
         slot0 += P.L * P.R[o];
     }
-    k_sift_orient<<<ncand, 64, 0, st>>>(d_os, cand, ncand, angles, npk);
-    k_sift_scan<<<1, 1024, 0, st>>>(npk, kpos, ncand, nullptr, d_total + 1);
-    k_sift_emit<<<(ncand + 255) / 256, 256, 0, st>>>(cand, ncand, angles, npk, kpos, kp0);
-    const int gk = (int)((nkp_max + 255) / 256);
-    k_sift_dedup<<<gk, 256, 0, st>>>(kp0, d_total + 1, keep);
-    k_sift_scan<<<1, 1024, 0, st>>>(keep, keep_pos, 0, d_total + 1, d_total + 2);
-    k_sift_compact<<<gk, 256, 0, st>>>(kp0, d_total + 1, keep, keep_pos, kp1, xy);
-    if (ndesc) k_sift_describe<<<(unsigned)ndesc, 64, 0, st>>>(d_os, kp1, d_total + 2, cap, d_desc);
+    // grids cover the largest strip of the group; workgroups beyond a strip's own counts leave at once
+    const unsigned gk = (unsigned)(((size_t)maxc * SIFT_MAX_PEAKS + 255) / 256);
+    k_sift_orient<<<dim3(maxc, 1, G), 64, 0, st>>>(d_os, zs, d_segs, cand, angles, npk);
+    k_sift_scan<<<G, 1024, 0, st>>>(npk, kpos, 0, 0, d_segs, 1, counts, -1, 1);
+    k_sift_emit<<<dim3((maxc + 255) / 256, 1, G), 256, 0, st>>>(d_segs, cand, angles, npk, kpos, kp0);
+    k_sift_dedup<<<dim3(gk, 1, G), 256, 0, st>>>(d_segs, kp0, counts, keep);
+    k_sift_scan<<<G, 1024, 0, st>>>(keep, keep_pos, 0, 0, d_segs, SIFT_MAX_PEAKS, counts, 1, 2);
+    k_sift_compact<<<dim3(gk, 1, G), 256, 0, st>>>(d_segs, kp0, counts, keep, keep_pos, kp1);
     HIP_TRY(hipGetLastError());
-    int n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, d_total + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_out = n;
-    if (n > cap) { vfsms_set_error("sift: %d keypoints exceed the caller's capacity %d", n, cap); return VFSMS_ERR_CAPACITY; }
-    if (n > 0) {
-        if (kps_xy) HIP_TRY(hipMemcpyAsync(kps_xy, xy, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
-        if (desc) HIP_TRY(hipMemcpyAsync(desc, d_desc, sizeof(float) * 128 * (size_t)n, hipMemcpyDeviceToHost, st));
-        if (kps_full) HIP_TRY(hipMemcpyAsync(kps_full, kp1, sizeof(vfsms_keypoint) * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(hc.data(), counts, sizeof(int) * 4 * g, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                               // sync 2 of the group: the keypoint counts size what is kept
+    int maxn = 0;
+    for (int k = 0; k < g; k++) {
+        const int n = hc[4 * k + 2];
+        out[k].n = n; maxn = std::max(maxn, n);
+        if (n == 0) continue;
+        const size_t npad = sift_pad_rows(n);
+        out[k].xy = (float *)sift_pool_alloc(ctx, sizeof(float) * 2 * n);
+        out[k].desc = (float *)sift_pool_alloc(ctx, sizeof(float) * 128 * (size_t)n);
+        out[k].d8 = (int8_t *)sift_pool_alloc(ctx, 128 * npad);
+        out[k].nrm = (int *)sift_pool_alloc(ctx, sizeof(int) * npad);
+        if (!out[k].xy || !out[k].desc || !out[k].d8 || !out[k].nrm) return VFSMS_ERR_CAPACITY;
+        segs[k].desc = out[k].desc; segs[k].xy = out[k].xy;
     }
+    if (kp_tmp) *kp_tmp = kp1;
+    if (maxn == 0) return VFSMS_OK;
+    TRY(ctx_upload_small(ctx, segs.data(), sizeof(SiftSeg) * g, (void **)&d_segs));
+    k_sift_describe<<<dim3(maxn, 1, G), 64, 0, st>>>(d_os, zs, d_segs, kp1, counts);
+    HIP_TRY(hipGetLastError());
+    return VFSMS_OK;
+}
+
+int sift_detect_describe_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
+                                float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out)
+{
+    *n_out = 0;
+    sift_pool_reset(ctx);
+    int *counts = (int *)sift_pool_alloc(ctx, sizeof(int) * 4);
+    if (!counts) return VFSMS_ERR_CAPACITY;
+    SiftSrcHost src = {d_img, w};
+    SiftStripOut o;
+    const vfsms_keypoint *kp1 = nullptr;
+    TRY(sift_group_device(ctx, &src, 1, h, w, p, counts, &o, &kp1));
+    hipStream_t st = ctx->stream;
+    const int n = o.n;
+    *n_out = n;
+    if (n > cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        vfsms_set_error("sift: %d keypoints exceed the caller's capacity %d", n, cap);
+        return VFSMS_ERR_CAPACITY;
+    }
+    if (n > 0) {
+        if (kps_xy) HIP_TRY(hipMemcpyAsync(kps_xy, o.xy, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
+        if (desc) HIP_TRY(hipMemcpyAsync(desc, o.desc, sizeof(float) * 128 * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (kps_full) HIP_TRY(hipMemcpyAsync(kps_full, kp1, sizeof(vfsms_keypoint) * n, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return VFSMS_OK;
 }

@@ -33,20 +33,23 @@ def _rotate(direction, incre):
 
 class GridRegistrar:
     def __init__(self, engine, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=3, directIncre=1,
-                 surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0), offsetCaculate="mode", ransacThreshold=3):
+                 surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0), offsetCaculate="mode", ransacThreshold=3,
+                 siftParams=None):
         self.eng = engine
         self.method = method
         self.roiRatio = roiRatio
         self.searchRatio = searchRatio
         self.offsetEvaluate = offsetEvaluate
         self.directIncre = directIncre
-        self.params = surfParams
+        self.params = siftParams if method == "sift" else surfParams      # the parameter record of the method's fused batch (None: its defaults)
+        if method == "sift":
+            self.native = False       # vfsms_pairs_offsets knows methods 0..2 (vfsms_grid_params has no SIFT record): the chain runs here, on attempt_sift_batch
         self.phaseThr = phaseResponseThreshold
         self.window = max(1, int(window))
         self.enhance = tuple(enhance)                     # (mode, clipLimit, tileSize) of Method.isEnhance (Stitcher.py:327-334)
         # Method.offsetCaculate: "ransac" puts the engine's vote tail on the consensus of getOffsetByRansac around this registrar's own
         # calls (_estimator) and back on mode afterwards; "mode" makes no such call
-        self.offsetCaculate = offsetCaculate if method in ("surf", "orb") else "mode"
+        self.offsetCaculate = offsetCaculate if method in ("surf", "orb", "sift") else "mode"
         self.ransacThreshold = int(ransacThreshold)
         self.stats = dict(attempts=0, batches=0, sum_nq_nt=0, sum_nq_plus_nt=0, sum_nq=0, roi_px=0)
         # Path memory: the accepted directions of the last path this registrar registered are the PREDICTION for the next one of the same
@@ -104,6 +107,10 @@ class GridRegistrar:
         if self.method == "orb":
             with self._estimator():
                 rows = self.eng.attempt_orb_batch(jobs, self.params, getattr(self, "orbMaxDistance", -1), self.offsetEvaluate)
+            return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
+        if self.method == "sift":
+            with self._estimator():
+                rows = self.eng.attempt_sift_batch(jobs, self.params, self.searchRatio, self.offsetEvaluate)
             return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
         if self.method == "phase":
             rows = self.eng.attempt_phase_batch(jobs)

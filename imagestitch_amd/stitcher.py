@@ -194,12 +194,13 @@ class Stitcher(Utility.Method):
         """the GridRegistrar of one file list, primed with what the previous dataset taught this stitcher (accepted directions, same number of
         tiles: GridRegistrar.path_memory; Main.py runs its datasets through ONE Stitcher with one setting) or with the operator's pathHint"""
         from .grid import GridRegistrar
-        params = None if method == "phase" else (self._orbParams() if method in ("orb", "orb_full") else self._surfParams())
+        params = None if method in ("phase", "sift") else (self._orbParams() if method in ("orb", "orb_full") else self._surfParams())
+        sift = self._siftParams() if method == "sift" else None
         reg = GridRegistrar(self.engine, method="surf" if method == "surf_full" else "orb" if method == "orb_full" else method, roiRatio=self.roiRatio,
                             searchRatio=self.searchRatio, offsetEvaluate=self.offsetEvaluate, directIncre=self.directIncre, surfParams=params,
                             phaseResponseThreshold=self.phaseResponseThreshold, window=48,
                             enhance=self._enhanceSpec() if method in ("surf", "surf_full") else (0, 0.0, 0),
-                            offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold)
+                            offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold, siftParams=sift)
         reg.orbMaxDistance = self.orbMaxDistance if self.isGPUAvailable else -1
         reg.path_memory = self.__dict__.get("_pathMemory")
         reg.path_suspect = bool(self.__dict__.get("_pathSuspect", False))
@@ -481,7 +482,15 @@ class Stitcher(Utility.Method):
         stock_offset = ((self.offsetCaculate == "mode" and c.getOffsetByMode is Utility.Method.getOffsetByMode)
                         or (self.offsetCaculate == "ransac" and c.getOffsetByRansac is Utility.Method.getOffsetByRansac))
         return (c.detectAndDescribe is Utility.Method.detectAndDescribe and c.matchDescriptors is Utility.Method.matchDescriptors
-                and stock_offset and (not self.isEnhance or self.featureMethod == "surf") and self.featureMethod in ("surf", "orb"))
+                and stock_offset and (not self.isEnhance or self.featureMethod == "surf") and self.featureMethod in ("surf", "orb", "sift")
+                and (self.featureMethod != "sift" or self._engineFusesSift()))
+
+    def _engineFusesSift(self):
+        """the engine offers attempt_sift_batch, and its detector is that same engine's: a wrapper that substitutes its own
+        sift_detect_describe (and hands everything else through) is a user's operator like an overridden detectAndDescribe, and keeps the
+        generic path"""
+        batch, detect = getattr(self.engine, "attempt_sift_batch", None), getattr(self.engine, "sift_detect_describe", None)
+        return batch is not None and detect is not None and getattr(batch, "__self__", None) is getattr(detect, "__self__", None)
 
     def _offsetEstimator(self):
         """scope of a fused engine call: with offsetCaculate = "ransac" its vote tail is the consensus of getOffsetByRansac"""
@@ -509,6 +518,8 @@ class Stitcher(Utility.Method):
                     if self.featureMethod == "orb":
                         max_dist = self.orbMaxDistance if self.isGPUAvailable else -1
                         row = self.engine.attempt_orb_batch([job], self._orbParams(), max_dist, self.offsetEvaluate)[0]
+                    elif self.featureMethod == "sift":
+                        row = self.engine.attempt_sift_batch([job], self._siftParams(), self.searchRatio, self.offsetEvaluate)[0]
                     elif self.isEnhance:
                         row = self.engine.attempt_surf_batch_enhanced([job], self._surfParams(), self.searchRatio, self.offsetEvaluate, self._enhanceSpec())[0]
                     else:

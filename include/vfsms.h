@@ -99,7 +99,7 @@ void *vfsms_ctx_stream(vfsms_ctx *ctx);
 int vfsms_ctx_set_keypoint_capacity(vfsms_ctx *ctx, int cap);
 /* How the fused paths turn matches into an offset (Method.offsetCaculate): VFSMS_OFFSET_MODE (the default, getOffsetByMode) or
  * VFSMS_OFFSET_CONSENSUS (vfsms_consensus_offset with tolerance tol_px, 0..VFSMS_CONSENSUS_MAX_TOL).  Governs vfsms_attempt_surf_batch,
- * _enhanced, vfsms_attempt_orb_batch, vfsms_pairs_offsets, _blind, vfsms_features_match_offset and _batch; rows keep their layout.
+ * _enhanced, vfsms_attempt_orb_batch, vfsms_attempt_sift_batch, vfsms_pairs_offsets, _blind, vfsms_features_match_offset and _batch; rows keep their layout.
  * vfsms_mode_offset always votes by mode.  Anything else returns VFSMS_ERR_BAD_ARG and leaves the setting as it was.                */
 #define VFSMS_OFFSET_MODE 0
 #define VFSMS_OFFSET_CONSENSUS 1
@@ -287,6 +287,11 @@ int vfsms_attempt_surf_batch_enhanced(vfsms_ctx *ctx, const vfsms_roi_pair *jobs
 /* same with ORB + BF-Hamming 1-NN (max_dist < 0: no distance threshold, the cv2 path; else distance < max_dist, the DLL path) */
 int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
                             const vfsms_orb_params *params, int max_dist, int offset_evaluate, int32_t *out);
+/* same with SIFT (vfsms_sift_detect_describe's arithmetic, every distinct strip detected once and kept on the device) + BF-L2 2-NN +
+ * ratio + vote.  Strips are processed in groups whose pyramids fit a byte budget (4 GiB; VFSMS_SIFT_GROUP_BYTES overrides); results do
+ * not depend on the grouping.  params->n_features > 0 returns VFSMS_ERR_UNSUPPORTED as in vfsms_sift_detect_describe.          */
+int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
+                             const vfsms_sift_params *params, double ratio, int offset_evaluate, int32_t *out);
 /* same for phase correlation (Stitcher.py:224-235): out: double[n][3] = {x, y, response}           */
 int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out);
 
