@@ -1081,7 +1081,7 @@ extern "C" int vfsms_debug_desc_trips(unsigned long long *out) { return hipMemcp
 #endif
 #ifndef DESC_WBUF
 #define DESC_WBUF 15360       // (round 6: 16384 -> 15360 makes room for the sixth workgroup of a CU: 6 x 26.2 KB of LDS)
-#endif                            // LDS bytes for the staged descriptor window (win <= 128) / band chunk
+#endif                            // LDS bytes for the staged descriptor window (win <= 123) / strip chunk + column sums
 // start, start + d, (start + d) + d, ... : the reference's running float sum (one rounding per step, so the chain cannot be split), four
 // links per trip -- the trip overhead (counter, compare, branch, address) was four fifths of the instructions of this single-lane loop
 __device__ __forceinline__ void origin_chain(float *row, float s, const float d, const int n)
@@ -1411,15 +1411,24 @@ __device__ __forceinline__ float area_row_tab_w(const uint8_t *S, const AreaRec 
         if (t + i < nmax) buf += (float)p[t + i] * w[i];
     return buf;
 }
+// the output pixel from the finished column sum of its cell (mode 2: scale == 2, 1: integer scale, 0: float table)
+__device__ __forceinline__ uint8_t area_out(const float sum, const int mode, const float inv_area)
+{
+    if (mode == 2) return (uint8_t)(((int)sum + 2) >> 2);
+    if (mode == 1) return sat_u8(sum * inv_area);
+    return sat_u8(sum);
+}
 // one output pixel from the row sums rb[0], rb[21], ... of its n source rows (sum = beta * buf, then sum += beta * buf)
 __device__ __forceinline__ uint8_t area_col_tab(const float *rb, const AreaRec &c, const int mode, const float inv_area)
 {
     float sum = c.a0 * rb[0];
     for (int t = 1; t < c.n; t++) sum += (t < c.n - 1 ? c.af : c.al) * rb[t * 21];
-    if (mode == 2) return (uint8_t)(((int)sum + 2) >> 2);
-    if (mode == 1) return sat_u8(sum * inv_area);
-    return sat_u8(sum);
+    return area_out(sum, mode, inv_area);
 }
+// Windows that do not fit the LDS buffer whole stream through it in chunks of whole 8-row strips; the running column sums of the
+// 21 x 21 output pixels sit at the buffer's tail, behind the largest chunk.
+#define DESC_ACC_OFF (DESC_WBUF - 441 * 4)
+#define DESC_PASS 36                  // window rows per row-sum pass: 36 x 21 sums are three rounds of the workgroup (`rowsum` holds 40)
 
 // band >= 0: only row `band` of the 21 x 21 patch (tickets of the largest windows are split by output row, see k_desc_plan)
 __device__ void describe_one(const RoiDev &R, const SurfTables *T, const AreaRec *area_tab, const DescRec &rec, int extended, int upright, const int band)
@@ -1464,7 +1473,7 @@ __device__ void describe_one(const RoiDev &R, const SurfTables *T, const AreaRec
     DT_MARK(0);
 
     // The rotated window is staged through LDS so that every bilinear sample is produced exactly once: the whole
-    // window when it fits (win <= 128), otherwise as many rows of output cells as fit.  INTER_AREA then runs from LDS as two
+    // window when it fits (win <= 123), otherwise as a stream of 8-row strips (below).  INTER_AREA then runs from LDS as two
     // table-driven passes in cv::resize's accumulation order: buf[dx] of every staged source row (one (row, cell) per lane, uniform
     // trip counts), then the output pixels from those row sums -- in chunks of whole output rows whose source rows fit `rowsum`.
     // rows_lo .. rows_hi of WINBUF row index 0 hold window rows st_lo ..; reduce the output rows [dyA, dyB_end)
@@ -1502,41 +1511,53 @@ __device__ void describe_one(const RoiDev &R, const SurfTables *T, const AreaRec
         reduce_rows(0, 0, dsz);
         DT_MARK(2);
     } else {
-        const int dy_end = band >= 0 ? band + 1 : dsz;
-        const int crows = max(DESC_WBUF / win, 1);                 // window rows the LDS buffer holds (>= 22 for win <= 739)
-        for (int dy = band >= 0 ? band : 0; dy < dy_end;) {
-            const int rlo = REC[dy].j0, nrows = REC[dy].n;         // <= scale + 2 <= 39
-            if (nrows <= crows) {
-                // Super-band: the buffer is filled with the source rows of as many consecutive output rows as fit.  A band on
-                // its own is only scale + 2 (8-38) rows tall -- one or two 8-row strips, a third of their lanes idle, and every row
-                // shared by two bands sampled twice; a full buffer is sampled in whole strips and its shared rows once.
-                int d_stop = dy + 1;
-                while (d_stop < dy_end && REC[d_stop].j0 + REC[d_stop].n - rlo <= crows) d_stop++;
-                const int end = REC[d_stop - 1].j0 + REC[d_stop - 1].n - 1;
-                stage_rows<4>(G, sx_row, sy_row, rlo, end - rlo + 1, WINBUF, STRIP_IN);
-                __syncthreads();
-                DT_MARK(3);
-                reduce_rows(rlo, dy, d_stop);
-                DT_MARK(4);
-                dy = d_stop;
-            } else {
-                // a band taller than the buffer (win > 409): staged in chunks of its own, row sums collected over the chunks
-                for (int c0 = 0; c0 < nrows; c0 += crows) {
-                    const int cn = min(crows, nrows - c0);
-                    stage_rows<4>(G, sx_row, sy_row, rlo + c0, cn, WINBUF, STRIP_IN);
-                    __syncthreads();
-                    DT_MARK(3);
-                    for (int e = threadIdx.x; e < cn * 21; e += 256) {
-                        const int r = (int)(((uint32_t)e * 3121u) >> 16), dx = e - 21 * r;
-                        rowsum[c0 * 21 + e] = area_row_tab(WINBUF + r * win, REC[dx], nmin, nmax);
-                    }
-                    __syncthreads();
+        // The window as a stream of full 8-row strips: chunks of as many strips as the buffer holds in front of the column sums, so every
+        // window row is sampled once and only the last chunk ends in a partial strip.  INTER_AREA is folded into the stream in
+        // ResizeArea_Invoker's order: the row sums buf[dx] of each pass of rows, then, per output pixel, sum = beta * buf for its first source
+        // row and sum += beta * buf for the others, in source-row order -- a row on the boundary of two output rows feeds both from the
+        // same buf.  An output pixel is rounded into PATCH when its last source row has passed; until then its sum waits in `acc`.
+        float *acc = (float *)(WINBUF + DESC_ACC_OFF);
+        const int dyA = band >= 0 ? band : 0, dyB = band >= 0 ? band + 1 : dsz;
+        const int rlo = REC[dyA].j0, rhi = REC[dyB - 1].j0 + REC[dyB - 1].n;
+        const int crows = (DESC_ACC_OFF / win) & ~7;               // >= 16 for win <= 739
+        for (int c0 = rlo; c0 < rhi; c0 += crows) {
+            const int cn = min(crows, rhi - c0);
+            stage_rows<4>(G, sx_row, sy_row, c0, cn, WINBUF, STRIP_IN);
+            __syncthreads();
+            DT_MARK(3);
+            for (int p0 = 0; p0 < cn; p0 += DESC_PASS) {
+                const int pn = min(DESC_PASS, cn - p0);
+                for (int e = threadIdx.x; e < pn * 21; e += 256) {
+                    const int r = (int)(((uint32_t)e * 3121u) >> 16), dx = e - 21 * r;      // e / 21, exact for e < 43690
+                    if (tail_ok) {
+                        const AreaRec cx = REC[dx];
+                        float w[AREA_TAIL];
+                        area_tail_weights(cx, nmin, w);
+                        rowsum[e] = area_row_tab_w(WINBUF + (p0 + r) * win, cx, nmin, nmax, w);
+                    } else
+                        rowsum[e] = area_row_tab(WINBUF + (p0 + r) * win, REC[dx], nmin, nmax);
                 }
-                if (threadIdx.x < dsz) PATCH[dy][threadIdx.x] = area_col_tab(rowsum + threadIdx.x, REC[dy], mode, inv_area);
                 __syncthreads();
-                DT_MARK(4);
-                dy++;
+                const int s0 = c0 + p0, s1 = s0 + pn;                  // window rows of this pass
+                for (int o = threadIdx.x; o < 441; o += 256) {
+                    const int dy = (int)(((uint32_t)o * 3121u) >> 16), dx = o - 21 * dy;
+                    const AreaRec ry = REC[dy];
+                    const int a = max(ry.j0, s0), b = min(ry.j0 + ry.n, s1);
+                    if (dy < dyA || dy >= dyB || a >= b) continue;
+                    float sum = a == ry.j0 ? 0.f : acc[o];
+                    for (int s = a; s < b; s++) {
+                        const int t = s - ry.j0;
+                        const float rb = rowsum[(s - s0) * 21 + dx];
+                        if (t == 0) sum = ry.a0 * rb;
+                        else sum += (t < ry.n - 1 ? ry.af : ry.al) * rb;
+                    }
+                    if (b == ry.j0 + ry.n) PATCH[dy][dx] = area_out(sum, mode, inv_area);
+                    else acc[o] = sum;
+                }
+                // (after a chunk's last pass the next chunk's staging barrier separates these reads from the next row sums)
+                if (p0 + DESC_PASS < cn) __syncthreads();
             }
+            DT_MARK(4);
         }
     }
     __syncthreads();
