@@ -73,6 +73,8 @@ _SIGNATURES = {
     "vfsms_ctx_stream": (C.c_void_p, [C.c_void_p]),
     "vfsms_ctx_set_keypoint_capacity": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_ctx_set_offset_estimator": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "vfsms_ctx_set_offset_verifier": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    "vfsms_verify_ncc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_profile_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "vfsms_tile_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -255,6 +257,26 @@ class Engine:
         "ransac" / "consensus" (consensus_offset with tolerance `tol` px, 0..64); 0 / 1 as in include/vfsms.h."""
         est = self.OFFSET_ESTIMATORS[kind] if isinstance(kind, str) else int(kind)
         self._check(self.lib.vfsms_ctx_set_offset_estimator(self.ctx, est, int(tol)))
+
+    OFFSET_VERIFIERS = {"none": 0, "ncc": 1}
+    VERIFY_FIXED_ONE = 1 << 20
+
+    def set_offset_verifier(self, kind="none", threshold=0.0, min_pixels=0):
+        """The acceptance check behind the vote of the fused paths (attempt batches, pairs_offsets): "none" (default) or "ncc", the
+        normalised cross-correlation of the raw pixels the two strips share under the voted offset (tests/verify_ref.py); a row keeps
+        status 1 iff score >= threshold, int 7 of the row is the fixed-point score; 0 / 1 as in include/vfsms.h."""
+        ver = self.OFFSET_VERIFIERS[kind] if isinstance(kind, str) else int(kind)
+        self._check(self.lib.vfsms_ctx_set_offset_verifier(self.ctx, ver, float(threshold), int(min_pixels)))
+
+    def verify_ncc(self, a, b, dx, dy, min_pixels=0):
+        """vfsms_verify_ncc on two host strips of one shape and a raw vote (dx, dy) -> ((N, Sa, Sb, Saa, Sbb, Sab), score, fixed-point score)"""
+        a = _u8_2d(a); b = _u8_2d(b)
+        if a.shape != b.shape:
+            raise ValueError("verify_ncc: shapes differ")
+        out = np.zeros(8, np.int64)
+        self._check(self.lib.vfsms_verify_ncc(self.ctx, _ptr(a), a.strides[0], _ptr(b), b.strides[0], a.shape[0], a.shape[1],
+                                              int(dx), int(dy), int(min_pixels), _ptr(out)))
+        return tuple(int(v) for v in out[:6]), float(out[6:7].view(np.float64)[0]), int(out[7])
 
     def profile_enable(self, on=True):
         self._check(self.lib.vfsms_profile_enable(self.ctx, int(bool(on))))

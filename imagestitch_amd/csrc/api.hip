@@ -296,6 +296,16 @@ extern "C" int vfsms_ctx_set_offset_estimator(vfsms_ctx *ctx, int estimator, int
     ctx->offset_estimator = estimator; ctx->offset_tol = tol_px;
     return VFSMS_OK;
 }
+extern "C" int vfsms_ctx_set_offset_verifier(vfsms_ctx *ctx, int verifier, double threshold, int min_pixels)
+{
+    if (!ctx) return VFSMS_ERR_BAD_ARG;
+    if ((verifier != VFSMS_VERIFY_NONE && verifier != VFSMS_VERIFY_NCC) || !(threshold >= -1.0 && threshold <= 1.0) || min_pixels < 0) {
+        vfsms_set_error("set_offset_verifier: verifier %d / threshold %g / min_pixels %d (0 none or 1 ncc; -1..1; >= 0)", verifier, threshold, min_pixels);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    ctx->offset_verifier = verifier; ctx->verify_threshold = threshold; ctx->verify_min_pixels = min_pixels;
+    return VFSMS_OK;
+}
 static int kp_capacity(vfsms_ctx *ctx, int h, int w)
 {
     if (ctx->kp_cap_override > 0) return ctx->kp_cap_override;
@@ -984,6 +994,31 @@ extern "C" int vfsms_consensus_offset(vfsms_ctx *ctx, const float *kpsA, int nA,
     return offset_from_pairs(ctx, "consensus_offset", kpsA, nA, kpsB, nB, pairs, m, VFSMS_OFFSET_CONSENSUS, tol_px, offset_evaluate, out4);
 }
 
+// vfsms_verify_ncc: the verifier's three kernels on one job whose result row names the vote as accepted; the decision is the caller's
+extern "C" int vfsms_verify_ncc(vfsms_ctx *ctx, const uint8_t *a, int a_stride, const uint8_t *b, int b_stride, int h, int w,
+                                int dx, int dy, int min_pixels, int64_t *out8)
+{
+    CTX_ENTER(ctx);
+    if (!a || !b || !out8 || h <= 0 || w <= 0 || a_stride < w || b_stride < w || min_pixels < 0) { vfsms_set_error("verify_ncc: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(ctx_arena_reserve(ctx, 2 * (size_t)h * w + 65536));
+    ctx->pinned_off = 0;
+    uint8_t *da, *db;
+    TRY(upload_image(ctx, a, h, w, a_stride, &da));
+    TRY(upload_image(ctx, b, h, w, b_stride, &db));
+    MatchDev M; memset(&M, 0, sizeof(M));
+    int32_t row[VFSMS_ATTEMPT_INTS] = {1, dx, dy, 0, 0, 0, 0, 0};
+    TRY(upload_array(ctx, row, VFSMS_ATTEMPT_INTS, &M.result));
+    M.vsum = (unsigned long long *)ctx_arena_alloc(ctx, 64);
+    if (!M.vsum) { vfsms_set_error("verify_ncc: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    M.va = da; M.vb = db; M.vsa = w; M.vsb = w; M.vh = h; M.vw = w;
+    MatchDev *dM;
+    TRY(upload_array(ctx, &M, 1, &dM));
+    TRY(launch_verify(ctx, dM, 1, -1.0, min_pixels));
+    HIP_TRY(hipMemcpyAsync(out8, M.vsum, 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 // ---- phase correlation ---------------------------------------------------------------------------------------------------
 extern "C" int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
                                         int stride_a, int stride_b, double *out3)
@@ -1034,6 +1069,11 @@ struct StripTable {
     std::vector<int> a, b;                   // per slot: its A / B strip
     int u0 = 0;                              // strips of part 0 (the first u0)
 };
+// the raw pixels of a job's two strips, for the overlap check behind the vote (verify_kernels.hip)
+static void match_set_strips(MatchDev *m, const StripTable::Strip &A, const StripTable::Strip &B)
+{
+    m->va = A.p; m->vsa = A.stride; m->vb = B.p; m->vsb = B.stride; m->vh = A.h; m->vw = A.w;
+}
 static int build_strip_table(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, const int *ord, int n, int n0, StripTable *T)
 {
     static const bool dedup = !(getenv("VFSMS_STRIP_DEDUP") && atoi(getenv("VFSMS_STRIP_DEDUP")) == 0);
@@ -1204,6 +1244,7 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         M[s_].q = A.desc; M[s_].t = B.desc;
         M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
         M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
+        match_set_strips(&M[s_], T.strips[T.a[s_]], T.strips[T.b[s_]]);      // the tile's pixels, not the enhanced copy
     }
     RoiDev *dR; MatchDev *dM;
     TRY(upload_pinned(ctx, R.data(), sizeof(RoiDev) * u, (void **)&dR));
@@ -1450,12 +1491,22 @@ static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n,
     return VFSMS_OK;
 }
 
+// a feature set does not own its tile's pixels, so its vote cannot be verified on the device: refuse rather than skip the check
+static int features_refuse_verifier(vfsms_ctx *ctx, const char *what)
+{
+    if (ctx->offset_verifier == VFSMS_VERIFY_NONE) return VFSMS_OK;
+    vfsms_set_error("%s: feature sets carry no pixels, so the offset verifier cannot judge their vote -- set VFSMS_VERIFY_NONE around this "
+                    "call and check the offset with vfsms_verify_ncc on the two tiles", what);
+    return VFSMS_ERR_UNSUPPORTED;
+}
+
 // matchDescriptors + getOffsetByMode of n (query set A_k, train set B_k) jobs as ONE batch: out[8 * k ..] as vfsms_features_match_offset
 extern "C" int vfsms_features_match_offset_batch(vfsms_ctx *ctx, const int64_t *feat_a, const int64_t *feat_b, int n, double ratio,
                                                  int offset_evaluate, int32_t *out)
 {
     CTX_ENTER(ctx);
     if (n < 0 || (n && (!feat_a || !feat_b || !out))) { vfsms_set_error("features_match_batch: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(features_refuse_verifier(ctx, "features_match_batch"));
     std::vector<const FeatRec *> A(n), B(n);
     std::vector<int> live;
     int maxq = 0, maxt = 0, dim = 0;
@@ -1551,6 +1602,7 @@ extern "C" int vfsms_features_match_offset(vfsms_ctx *ctx, int64_t feat_a, int64
     CTX_ENTER(ctx);
     auto ia = ctx->feats.find(feat_a), ib = ctx->feats.find(feat_b);
     if (ia == ctx->feats.end() || ib == ctx->feats.end() || !out) { vfsms_set_error("features_match: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    TRY(features_refuse_verifier(ctx, "features_match"));
     const FeatRec &A = ia->second, &B = ib->second;
     if (A.dim != B.dim || A.is_orb != B.is_orb) { vfsms_set_error("features_match: descriptor kinds differ"); return VFSMS_ERR_BAD_ARG; }
     for (int k = 0; k < VFSMS_ATTEMPT_INTS; k++) out[k] = 0;
@@ -2052,6 +2104,7 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
         M[s_].q8 = A.d8; M[s_].t8 = B.d8; M[s_].qn2 = A.nrm; M[s_].tn2 = B.nrm;
         M[s_].nq_ptr = cblock + 4 * ia + 2; M[s_].nt_ptr = cblock + 4 * ib + 2;
         M[s_].kq = A.xy; M[s_].kt = B.xy;
+        match_set_strips(&M[s_], T.strips[ia], T.strips[ib]);
     }
     MatchDev *dM;
     TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
@@ -2111,6 +2164,7 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
             M[s_].q = (const float *)A.desc; M[s_].t = (const float *)B.desc;
             M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
             M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
+            match_set_strips(&M[s_], T.strips[T.a[s_]], T.strips[T.b[s_]]);
         }
         ctx->pinned_off = 0;
         OrbDev *dR; MatchDev *dM;

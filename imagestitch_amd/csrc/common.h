@@ -165,6 +165,10 @@ struct MatchDev {
     int *mcount;                      // [0] n matches, [1] n votes
     int32_t *result;                  // VFSMS_ATTEMPT_INTS
     int pairs_given;                  // pairs[] supplied by the caller (vfsms_mode_offset): do not rewrite
+    // overlap verification (verify_kernels.hip): the job's two strips as RAW tile pixels (query strip A, train strip B; also when the
+    // detector saw an enhanced copy), their common size, and the job's sums + score (8 x uint64, layout in verify_kernels.hip)
+    const uint8_t *va; const uint8_t *vb; int vsa, vsb, vh, vw;
+    unsigned long long *vsum;
 };
 
 // ---- context ------------------------------------------------------------------------------------------
@@ -188,6 +192,7 @@ struct vfsms_ctx {
     char *pinned; size_t pinned_size; size_t pinned_off;
     int kp_cap_override;
     int offset_estimator = VFSMS_OFFSET_MODE, offset_tol = 3;   // the vote tail of every fused path (vfsms_ctx_set_offset_estimator)
+    int offset_verifier = VFSMS_VERIFY_NONE, verify_min_pixels = 0; double verify_threshold = 0.0;   // the acceptance check behind that tail (vfsms_ctx_set_offset_verifier)
     // SURF tables
     vfsms_surf_params cur_params; bool tables_valid;
     LayerPat *d_layers; int n_layers;
@@ -270,6 +275,8 @@ int launch_bf_hamming(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t
 int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate);
 // consensus_kernels.hip
 int launch_consensus(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int tol, int offset_evaluate);
+// verify_kernels.hip
+int launch_verify(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, double threshold, int min_pixels);
 // orb_kernels.hip
 int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p);
 size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2, int cap);

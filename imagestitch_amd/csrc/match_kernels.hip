@@ -1116,7 +1116,7 @@ size_t match_bytes(int capq, int nsplit)
 {
     size_t b = 3 * al(sizeof(float) * (size_t)capq * nsplit);
     b += 3 * al(sizeof(float) * capq) + 2 * al(sizeof(int) * capq);
-    b += al(sizeof(int32_t) * 2 * capq) + al(sizeof(int32_t) * 4 * capq) + al(64) + al(64);
+    b += al(sizeof(int32_t) * 2 * capq) + al(sizeof(int32_t) * 4 * capq) + al(64) + al(64) + al(64);
     return b + 4096;
 }
 
@@ -1134,6 +1134,7 @@ int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit)
     m->pairs = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 2 * capq);
     m->votes = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * capq);
     m->mcount = (int *)ctx_arena_alloc(ctx, 64);
+    m->vsum = (unsigned long long *)ctx_arena_alloc(ctx, 64);
     m->result = (int32_t *)ctx_arena_alloc(ctx, 64);
     if (!m->result) { vfsms_set_error("arena exhausted while carving a match job"); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
@@ -1258,12 +1259,22 @@ static int launch_vote_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, i
     return VFSMS_OK;
 }
 
+// the context's acceptance check behind the vote of the fused paths (vfsms_ctx_set_offset_verifier); off: nothing is launched
+static int verify_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs)
+{
+    if (ctx->offset_verifier != VFSMS_VERIFY_NCC) return VFSMS_OK;
+    return launch_verify(ctx, d_jobs, njobs, ctx->verify_threshold, ctx->verify_min_pixels);
+}
+
 int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate)
 {
     if (njobs <= 0) return VFSMS_OK;
-    ProfScope ps(ctx, "vote");
-    hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, ratio, 1);
-    return launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate);
+    {
+        ProfScope ps(ctx, "vote");
+        hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, ratio, 1);
+        TRY(launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate));
+    }
+    return verify_tail(ctx, d_jobs, njobs);
 }
 
 int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio)
@@ -1285,8 +1296,11 @@ int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int cap
 int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate)
 {
     if (njobs <= 0) return VFSMS_OK;
-    ProfScope ps(ctx, "vote");
-    return launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate);
+    {
+        ProfScope ps(ctx, "vote");
+        TRY(launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate));
+    }
+    return verify_tail(ctx, d_jobs, njobs);
 }
 
 // the per-operator entry points name their estimator: the context's setting governs the fused paths only

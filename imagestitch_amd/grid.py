@@ -17,7 +17,7 @@ while keeping the GPU full:
 """
 import numpy as np
 
-from .utility import roi_rect, offset_estimator
+from .utility import roi_rect, vote_tail
 
 RESULT_INTS = 6   # status, dx, dy, direction, i, votes
 
@@ -34,7 +34,7 @@ def _rotate(direction, incre):
 class GridRegistrar:
     def __init__(self, engine, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=3, directIncre=1,
                  surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0), offsetCaculate="mode", ransacThreshold=3,
-                 siftParams=None):
+                 siftParams=None, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0):
         self.eng = engine
         self.method = method
         self.roiRatio = roiRatio
@@ -51,6 +51,10 @@ class GridRegistrar:
         # calls (_estimator) and back on mode afterwards; "mode" makes no such call
         self.offsetCaculate = offsetCaculate if method in ("surf", "orb", "sift") else "mode"
         self.ransacThreshold = int(ransacThreshold)
+        # Method.offsetVerify: "ncc" makes the engine check every voted offset by overlap correlation around the same calls and switches
+        # the check off afterwards; "none" makes no such call.  Phase correlation has its own response gate.
+        self.offsetVerify = offsetVerify if method in ("surf", "orb", "sift") else "none"
+        self.verifyThreshold, self.verifyMinPixels = float(verifyThreshold), int(verifyMinPixels)
         self.stats = dict(attempts=0, batches=0, sum_nq_nt=0, sum_nq_plus_nt=0, sum_nq=0, roi_px=0)
         # Path memory: the accepted directions of the last path this registrar registered are the PREDICTION for the next one of the same
         # length (a session shoots one scan pattern after the other: Main.py loops over its datasets with one setting) -- they drive the
@@ -81,7 +85,7 @@ class GridRegistrar:
         return out
 
     def _estimator(self):
-        return offset_estimator(self.eng, self.offsetCaculate, self.ransacThreshold)
+        return vote_tail(self.eng, self.offsetCaculate, self.ransacThreshold, self.offsetVerify, self.verifyThreshold, self.verifyMinPixels)
 
     # -- one batch of attempts -----------------------------------------------------------------------------------
     def _attempts(self, handles, shapes, items):

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import utility as Utility
 from . import fusion as ImageFusion
-from .utility import roi_rect, offset_estimator
+from .utility import roi_rect, offset_estimator, vote_tail
 
 CANNOT_MATCH = "  The two images can not match"
 
@@ -183,7 +183,10 @@ class Stitcher(Utility.Method):
             return self.featureMethod
         if fn is Stitcher.calculateOffsetForPhaseCorrleateIncre and not self.phaseSignFix:
             return "phase"
-        if fn is Stitcher.calculateOffsetForFeatureSearch and self._usesStockOperators() and self.offsetCaculate in ("mode", "ransac"):
+        # (with offsetVerify the line scans stay pair by pair: whole-tile feature sets carry no pixels, calculateOffsetForFeatureSearch
+        # checks the two tiles themselves after the vote)
+        if fn is Stitcher.calculateOffsetForFeatureSearch and self._usesStockOperators() and self.offsetCaculate in ("mode", "ransac") \
+                and self.offsetVerify == "none":
             if self.featureMethod == "surf" and hasattr(self.engine, "features_surf_batch"):
                 return "surf_full"
             if self.featureMethod == "orb" and not self.isEnhance and hasattr(self.engine, "attempt_orb_batch"):
@@ -200,7 +203,9 @@ class Stitcher(Utility.Method):
                             searchRatio=self.searchRatio, offsetEvaluate=self.offsetEvaluate, directIncre=self.directIncre, surfParams=params,
                             phaseResponseThreshold=self.phaseResponseThreshold, window=48,
                             enhance=self._enhanceSpec() if method in ("surf", "surf_full") else (0, 0.0, 0),
-                            offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold, siftParams=sift)
+                            offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold, siftParams=sift,
+                            offsetVerify=self.offsetVerify if method != "phase" else "none", verifyThreshold=self.verifyThreshold,
+                            verifyMinPixels=self.verifyMinPixels)
         reg.orbMaxDistance = self.orbMaxDistance if self.isGPUAvailable else -1
         reg.path_memory = self.__dict__.get("_pathMemory")
         reg.path_suspect = bool(self.__dict__.get("_pathSuspect", False))
@@ -496,6 +501,17 @@ class Stitcher(Utility.Method):
         """scope of a fused engine call: with offsetCaculate = "ransac" its vote tail is the consensus of getOffsetByRansac"""
         return offset_estimator(self.engine, self.offsetCaculate, self.ransacThreshold)
 
+    def _voteTail(self):
+        """scope of a fused ATTEMPT call (its jobs name the strips' pixels): the estimator, and with offsetVerify = "ncc" the overlap check
+        behind its vote"""
+        return vote_tail(self.engine, self.offsetCaculate, self.ransacThreshold, self.offsetVerify, self.verifyThreshold, self.verifyMinPixels)
+
+    def _verified(self, status, offset, rawA, rawB):
+        """the host operators' vote behind Method.verifyOffset on the raw pixels; offsetVerify = "none" makes no call"""
+        if status and self.offsetVerify != "none":
+            status = self.verifyOffset(rawA, rawB, offset)[0]
+        return status
+
     def _enhanceSpec(self):
         """(mode, clipLimit, tileSize) of Stitcher.py:269-276 / 327-334: 0 none, 1 cv2.equalizeHist, 2 cv2.createCLAHE(...).apply."""
         if not self.isEnhance:
@@ -514,7 +530,7 @@ class Stitcher(Utility.Method):
             if ra[2:] == rb[2:] and ra[2] > 0 and ra[3] > 0:
                 ha, hb = self._tileHandles([imageA, imageB])
                 job = (ha, hb, ra[0], ra[1], rb[0], rb[1], ra[2], ra[3])
-                with self._offsetEstimator():
+                with self._voteTail():
                     if self.featureMethod == "orb":
                         max_dist = self.orbMaxDistance if self.isGPUAvailable else -1
                         row = self.engine.attempt_orb_batch([job], self._orbParams(), max_dist, self.offsetEvaluate)[0]
@@ -529,6 +545,7 @@ class Stitcher(Utility.Method):
                 return (bool(row[0]), [int(row[1]), int(row[2])])
         roiImageA = self.getROIRegionForIncreMethod(imageA, direction=direction, order="first", searchRatio=searchRatio)
         roiImageB = self.getROIRegionForIncreMethod(imageB, direction=direction, order="second", searchRatio=searchRatio)
+        rawA, rawB = roiImageA, roiImageB
         if self.isEnhance:                                     # Stitcher.py:327-334
             roiImageA = self._enhance(roiImageA)
             roiImageB = self._enhance(roiImageB)
@@ -537,9 +554,10 @@ class Stitcher(Utility.Method):
         if featuresA is not None and featuresB is not None:
             matches = self.matchDescriptors(featuresA, featuresB)
             if self.offsetCaculate == "mode":
-                return self.getOffsetByMode(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
-            (status, offset, _adjustH) = self.getOffsetByRansac(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
-            return (status, offset)
+                (status, offset) = self.getOffsetByMode(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
+            else:
+                (status, offset, _adjustH) = self.getOffsetByRansac(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
+            return (self._verified(status, offset, rawA, rawB), offset)
         return None
 
     def _phaseCorrelate(self, roiImageA, roiImageB):
@@ -602,6 +620,7 @@ class Stitcher(Utility.Method):
         status = False
         if self._usesStockOperators() and self.featureMethod == "surf" and hasattr(self.engine, "features_surf"):
             return self._featureSearchResident(imageA, imageB)
+        rawA, rawB = imageA, imageB
         if self.isEnhance == True:                              # Stitcher.py:269-276
             imageA = self._enhance(imageA)
             imageB = self._enhance(imageB)
@@ -621,6 +640,7 @@ class Stitcher(Utility.Method):
                 (status, offset) = self.getOffsetByMode(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
             elif self.offsetCaculate == "ransac":
                 (status, offset, adjustH) = self.getOffsetByRansac(kpsA, kpsB, matches, offsetEvaluate=self.offsetEvaluate)
+            status = self._verified(status, offset, rawA, rawB)
         if status == False:
             self.tempImageFeature.isBreak = True
             return (status, CANNOT_MATCH)
@@ -663,6 +683,7 @@ class Stitcher(Utility.Method):
                 with self._offsetEstimator():
                     row = eng.features_match_offset(featA.handle, featB.handle, self.searchRatio, self.offsetEvaluate)
                 status, offset = bool(row[0]), [int(row[1]), int(row[2])]
+                status = self._verified(status, offset, imageA, imageB)      # the sets carry no pixels: the two tiles are checked here
         finally:
             featA.release()                                     # A's set is never needed again (B's lives on in the cache)
             if not featB.n:

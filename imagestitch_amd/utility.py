@@ -50,6 +50,27 @@ def offset_estimator(engine, offsetCaculate="mode", ransacThreshold=3):
         engine.set_offset_estimator("mode")
 
 
+@contextlib.contextmanager
+def offset_verifier(engine, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0):
+    """The engine's fused paths check every voted offset by overlap correlation (Method.offsetVerify = "ncc") inside the block, and not at
+    all after it, also when it raises.  "none" makes no engine call: no check is the engine's default."""
+    if offsetVerify == "none":
+        yield
+        return
+    engine.set_offset_verifier(offsetVerify, verifyThreshold, verifyMinPixels)
+    try:
+        yield
+    finally:
+        engine.set_offset_verifier("none")
+
+
+@contextlib.contextmanager
+def vote_tail(engine, offsetCaculate="mode", ransacThreshold=3, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0):
+    """offset_estimator and offset_verifier around one fused engine call"""
+    with offset_estimator(engine, offsetCaculate, ransacThreshold), offset_verifier(engine, offsetVerify, verifyThreshold, verifyMinPixels):
+        yield
+
+
 class Method():
     # ---- logging (ImageUtility.py:8-12) ----
     outputAddress = "result/"
@@ -97,6 +118,15 @@ class Method():
     offsetCaculate = "mode"     # "mode" or "ransac"
     offsetEvaluate = 3
     ransacThreshold = 3         # "ransac": Chebyshev tolerance in px (0..64) around a vote (getOffsetByRansac)
+
+    # ---- acceptance check behind the vote (no reference counterpart; tests/verify_ref.py): "ncc" keeps a voted offset only when the
+    # normalised cross-correlation of the RAW pixels the two strips share under it reaches verifyThreshold.  The threshold is measured
+    # (tests/test_verify_host.py): on the committed real strips every true accept scores 0.844 .. 0.995 and every
+    # false accept -0.105 .. 0.026; 0.5 lies between, far from both.  verifyMinPixels is a condition, not a measurement: fewer shared
+    # pixels than a 64 x 64 patch cannot be judged and are rejected (the thinnest true overlap there, 39 rows of a 640-px crop, has 24921)
+    offsetVerify = "none"       # "none" or "ncc"
+    verifyThreshold = 0.5
+    verifyMinPixels = 4096
 
     # ---- enhancement (ImageUtility.py:46-50; CLAHE/equalizeHist are out of the hot-path scope) ----
     isEnhance = False
@@ -155,6 +185,14 @@ class Method():
         status, off, _support = self.engine.consensus_offset(np.asarray(kpsA, np.float32), np.asarray(kpsB, np.float32),
                                                              np.asarray(matches, np.int32), self.ransacThreshold, offsetEvaluate)
         return (status, off, np.eye(3) if status else 0)
+
+    def verifyOffset(self, roiA, roiB, offset):
+        """offsetVerify = "ncc" -> (ok, score): the normalised cross-correlation of the pixels roiA and roiB (uint8, one shape, the raw
+        pixels) share under the RAW vote `offset` = [dx, dy] of getOffsetByMode / getOffsetByRansac on them -- roiB's pixel (r, c) meets
+        roiA's pixel (r + dx, c + dy) -- and ok = score >= verifyThreshold.  Fewer than verifyMinPixels shared pixels or a flat side
+        score 0.  Specified by tests/verify_ref.py."""
+        _sums, score, _fixed = self.engine.verify_ncc(np.asarray(roiA), np.asarray(roiB), int(offset[0]), int(offset[1]), self.verifyMinPixels)
+        return (bool(score >= self.verifyThreshold), score)
 
     # -- array adapters of the DLL path (ImageUtility.py:212-246): kept for API compatibility ------------
     def npToListForKeypoints(self, array):

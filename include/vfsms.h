@@ -105,6 +105,20 @@ int vfsms_ctx_set_keypoint_capacity(vfsms_ctx *ctx, int cap);
 #define VFSMS_OFFSET_CONSENSUS 1
 #define VFSMS_CONSENSUS_MAX_TOL 64
 int vfsms_ctx_set_offset_estimator(vfsms_ctx *ctx, int estimator, int tol_px);
+/* A second, optional acceptance criterion behind that vote (Method.offsetVerify; the reference has no such step, the specification is
+ * tests/verify_ref.py): VFSMS_VERIFY_NONE (the default: nothing runs, rows as before) or VFSMS_VERIFY_NCC, the normalised
+ * cross-correlation of the RAW pixels (also under isEnhance) the two ROI strips share under the voted (dx, dy): strip-B pixel (r, c) meets
+ * strip-A pixel (r + dx, c + dy).  A row whose vote was accepted keeps status 1 iff score >= threshold (-1..1); fewer than min_pixels
+ * (>= 0) shared pixels or a flat side score 0.  Int 7 of the row = floor(score * VFSMS_VERIFY_FIXED_ONE + 0.5), 0 for rows the vote
+ * did not accept; dx, dy and the counts stay.  Governs vfsms_attempt_surf_batch, _enhanced, vfsms_attempt_orb_batch,
+ * vfsms_attempt_sift_batch and methods 0 / 1 of vfsms_pairs_offsets, _blind (a rejected candidate is a failed attempt: the search goes
+ * on).  Method 2 (phase) ignores it: it has its own response gate.  vfsms_mode_offset and vfsms_consensus_offset never verify.
+ * vfsms_features_match_offset and _batch carry no pixels: with the verifier on they return VFSMS_ERR_UNSUPPORTED.
+ * Anything else returns VFSMS_ERR_BAD_ARG and leaves the setting as it was.                                                      */
+#define VFSMS_VERIFY_NONE 0
+#define VFSMS_VERIFY_NCC 1
+#define VFSMS_VERIFY_FIXED_ONE 1048576
+int vfsms_ctx_set_offset_verifier(vfsms_ctx *ctx, int verifier, double threshold, int min_pixels);
 
 /* Per-stage timing with HIP events recorded on the context's own stream around each kernel group
  * ("integral", "hessian", "nms", "sort", "orientation", "describe", "bf_l2", "vote", "phase", "fuse", ...).
@@ -238,6 +252,12 @@ int vfsms_mode_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kp
  * support wins, offset = the lower median of its inliers per axis.  out4={status,dx,dy,support}; tol_px = 0 is vfsms_mode_offset. */
 int vfsms_consensus_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const float *kpsB, int nB,
                            const int32_t *pairs, int m, int tol_px, int offset_evaluate, int32_t *out4);
+
+/* The check of vfsms_ctx_set_offset_verifier on two host strips of h x w (u8, row strides in bytes) and a raw vote (dx, dy):
+ * out8 = {N, Sa, Sb, Saa, Sbb, Sab, the bits of the double score, floor(score * VFSMS_VERIFY_FIXED_ONE + 0.5)} over the N shared pixels
+ * (a = the strip-A pixel, b = its strip-B partner).  The caller compares the score with its threshold (Method.verifyOffset).       */
+int vfsms_verify_ncc(vfsms_ctx *ctx, const uint8_t *a, int a_stride, const uint8_t *b, int b_stride, int h, int w,
+                     int dx, int dy, int min_pixels, int64_t *out8);
 
 /* cv2.phaseCorrelate(np.float64(a), np.float64(b)) (Stitcher.py:230): out3 = {x, y, response}     */
 int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
