@@ -158,6 +158,9 @@ _SIGNATURES = {
     "vfsms_fuse_multiband_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p]),
     "vfsms_canvas_set_multiband_levels": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+    "vfsms_fuse_seam_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_canvas_set_seam_blend": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "vfsms_features_surf_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_features_match_offset_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "vfsms_canvas_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
@@ -616,6 +619,28 @@ class Engine:
         self._check(self.lib.vfsms_fuse_multiband_i64(self.ctx, _ptr(A), _ptr(B), r, c, ch, int(dx), int(dy), int(levels), _ptr(out), _ptr(info)))
         return (out, info) if return_info else out
 
+    SEAM_BLENDS = {"none": 0, "multiBandBlending": 1}
+
+    def fuse_seam_i64(self, A, B, dx, dy, blend="none", levels=4, return_info=False, return_seam=False):
+        """optimalSeamLine on int64 regions (-1 = empty) -> uint8: a minimum-cost seam inside the fade's geometry; blend "none" takes every
+        pixel from one input, "multiBandBlending" feeds the label plane to the pyramid blend with `levels` levels (vfsms_fuse_seam_i64; the
+        arithmetic is the library's own, tests/seam_ref.py).  return_seam: also the int32 [r + c] seam (the vertical seam's column per row,
+        then the horizontal seam's row per column, -1 where a seam does not exist)."""
+        if blend not in self.SEAM_BLENDS:
+            raise ValueError("seamLineBlend must be 'none' or 'multiBandBlending'")
+        A = np.ascontiguousarray(A, np.int64); B = np.ascontiguousarray(B, np.int64)
+        if A.shape != B.shape:
+            raise ValueError("fuse: shapes differ")
+        r, c = A.shape[:2]
+        ch = 1 if A.ndim == 2 else A.shape[2]
+        out = np.empty(A.shape, np.uint8)
+        info = np.zeros(4, np.int32)
+        seam = np.empty(r + c, np.int32)
+        self._check(self.lib.vfsms_fuse_seam_i64(self.ctx, _ptr(A), _ptr(B), r, c, ch, int(dx), int(dy), self.SEAM_BLENDS[blend], int(levels),
+                                                 _ptr(out), _ptr(info), _ptr(seam) if return_seam else None))
+        res = (out,) + ((info,) if return_info else ()) + ((seam,) if return_seam else ())
+        return res if len(res) > 1 else out
+
     def fuse_ramps_i64(self, A, dx, dy, force_corner=False):
         """-> ((wA_r, wB_r, wA_c, wB_c), info): the separable float32 ramps of the fade blend / getWeightsMatrix."""
         A = np.ascontiguousarray(A, np.int64)
@@ -778,7 +803,8 @@ class Engine:
         self._check(self.lib.vfsms_canvas_paste(self.ctx, C.c_int64(handle), _ptr(tile), tile.shape[0], tile.shape[1], int(y0), int(x0)))
 
     def canvas_fuse_tile(self, handle, tile, y0, x0, roi, dx, dy, method=0):
-        """method 0: fadeInAndFadeOut, 1: trigonometric, 2: multiBandBlending (levels: canvas_set_multiband_levels)"""
+        """method 0: fadeInAndFadeOut, 1: trigonometric, 2: multiBandBlending (levels: canvas_set_multiband_levels), 3: optimalSeamLine (blend:
+        canvas_set_seam_blend)"""
         tile = np.ascontiguousarray(tile, np.uint8)
         info = np.zeros(4, np.int32)
         ry0, rx0, ry1, rx1 = [int(v) for v in roi]
@@ -805,7 +831,7 @@ class Engine:
 
     def canvas_fuse_tile_resident(self, handle, tile_handle, y0, x0, roi, dx, dy, want_info=False, method=0):
         """want_info=False: the call only enqueues work; geometry errors surface in canvas_download.  method 0: fadeInAndFadeOut, 1: trigonometric,
-        2: multiBandBlending"""
+        2: multiBandBlending, 3: optimalSeamLine"""
         info = np.zeros(4, np.int32) if want_info else None
         ry0, rx0, ry1, rx1 = [int(v) for v in roi]
         self._check(self.lib.vfsms_canvas_fuse_tile_resident_m(self.ctx, C.c_int64(handle), C.c_int64(tile_handle), int(y0), int(x0),
@@ -814,8 +840,8 @@ class Engine:
 
     def canvas_assemble_resident(self, handle, tile_handles, geom):
         """The mosaic walk over resident tiles as one call.  geom: int32 [n][9] = y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode
-        (mode -1 paste, 0 fadeInAndFadeOut, 1 trigonometric, 2 / 3 / 4 average / maximum / minimum, 6 multiBandBlending); enqueue only, geometry
-        errors surface in canvas_download."""
+        (mode -1 paste, 0 fadeInAndFadeOut, 1 trigonometric, 2 / 3 / 4 average / maximum / minimum, 6 multiBandBlending, 7 optimalSeamLine).
+        Enqueue only: geometry errors surface in canvas_download."""
         th = np.ascontiguousarray(tile_handles, np.int64)
         g = np.ascontiguousarray(geom, np.int32).reshape(-1, 9)
         if len(th) != len(g):
@@ -825,6 +851,13 @@ class Engine:
     def canvas_set_multiband_levels(self, handle, levels):
         """pyramid levels (1..8) of the canvas's multiBandBlending fuses (default 4)"""
         self._check(self.lib.vfsms_canvas_set_multiband_levels(self.ctx, C.c_int64(handle), int(levels)))
+
+    def canvas_set_seam_blend(self, handle, blend):
+        """how the canvas's optimalSeamLine fuses merge the seam's two sides: "none" (default) or "multiBandBlending" (levels:
+        canvas_set_multiband_levels)"""
+        if blend not in self.SEAM_BLENDS:
+            raise ValueError("seamLineBlend must be 'none' or 'multiBandBlending'")
+        self._check(self.lib.vfsms_canvas_set_seam_blend(self.ctx, C.c_int64(handle), self.SEAM_BLENDS[blend]))
 
     def canvas_download(self, handle, rows, cols, ch):
         out = np.empty((rows, cols, ch) if ch > 1 else (rows, cols), np.uint8)

@@ -9,7 +9,7 @@
 #include <tuple>
 
 int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy,
-                    uint8_t *d_out, int32_t *info, int method = 0, int levels = 4);
+                    uint8_t *d_out, int32_t *info, int method = 0, int levels = 4, int seam_blend = 0, int32_t *d_seam = nullptr);
 
 // ---- errors -------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -254,6 +254,7 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
+    if (ctx->seam_scratch) hipFree(ctx->seam_scratch);
     if (ctx->sift_scratch) hipFree(ctx->sift_scratch);
     if (ctx->sift_kp) hipFree(ctx->sift_kp);
     sift_pool_free(ctx);
@@ -1686,6 +1687,37 @@ extern "C" int vfsms_fuse_multiband_i64(vfsms_ctx *ctx, const int64_t *A, const 
     return VFSMS_OK;
 }
 
+// optimalSeamLine on the reference's own array representation: the fade's geometry decisions (degenerate corner geometries fail as the
+// fade's do), then energy, seam and label of seam_kernels.hip; blend 0: every pixel from one input, 1: the label plane as the mask of the
+// pyramid blend with `levels`.  seam_out (optional): r + c ints
+extern "C" int vfsms_fuse_seam_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
+                                   int dx, int dy, int blend, int levels, uint8_t *out, int32_t *info, int32_t *seam_out)
+{
+    CTX_ENTER(ctx);
+    if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_seam_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (blend < 0 || blend > 1) { vfsms_set_error("fuse_seam_i64: blend must be 0 (none) or 1 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
+    if (blend == 1 && (levels < 1 || levels > VFSMS_MB_MAX_LEVELS)) { vfsms_set_error("fuse_seam_i64: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    const size_t nel = (size_t)r * c * ch;
+    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 5 * ((size_t)r + c) + 65536));
+    long long *dA, *dB;
+    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
+    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
+    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
+    int32_t *d_seam = seam_out ? (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * ((size_t)r + c)) : nullptr;
+    if (seam_out && !d_seam) { vfsms_set_error("arena exhausted in fuse_seam"); return VFSMS_ERR_CAPACITY; }
+    const int rc = fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, 3, levels, blend, d_seam);
+    if (rc != VFSMS_OK) {                                      // a refused geometry: info[0] = -1, output zero, no seam
+        if (info) info[0] = -1;
+        memset(out, 0, nel);
+        if (seam_out) for (size_t k = 0; k < (size_t)r + c; k++) seam_out[k] = -1;
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
+    if (seam_out) HIP_TRY(hipMemcpyAsync(seam_out, d_seam, sizeof(int32_t) * ((size_t)r + c), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 int fuse_i64_ramps(vfsms_ctx *ctx, const long long *dA, int r, int c, int ch, int dx, int dy, int force_corner,
                    float *h_ramps, int32_t *info);
 
@@ -1708,7 +1740,7 @@ extern "C" int vfsms_canvas_create(vfsms_ctx *ctx, int rows, int cols, int ch, i
     if (!handle || rows <= 0 || cols <= 0 || ch < 1 || ch > 4) { vfsms_set_error("canvas_create: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec cv; cv.rows = rows; cv.cols = cols; cv.ch = ch;
     if (ctx->has_spare_canvas && ctx->spare_canvas.rows == rows && ctx->spare_canvas.cols == cols && ctx->spare_canvas.ch == ch) {
-        cv = ctx->spare_canvas; cv.placed.clear(); cv.mb_levels = 4;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
+        cv = ctx->spare_canvas; cv.placed.clear(); cv.mb_levels = 4; cv.seam_blend = 0;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
         ctx->has_spare_canvas = false;
     } else {
         HIP_TRY(hipMalloc((void **)&cv.pix, (size_t)rows * cols * ch));
@@ -1765,7 +1797,7 @@ extern "C" int vfsms_canvas_fuse_tile_m(vfsms_ctx *ctx, int64_t canvas, const ui
                                         int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 2) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric) or 2 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
+    if (method < 0 || method > 3) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric), 2 (multiBandBlending) or 3 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec *cv;
     TRY(canvas_tile_args(ctx, canvas, tile, h, w, y0, x0, &cv));
     if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + h || rx1 > x0 + w)) {
@@ -1830,7 +1862,7 @@ extern "C" int vfsms_canvas_fuse_tile_resident_m(vfsms_ctx *ctx, int64_t canvas,
                                                  int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 2) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric) or 2 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
+    if (method < 0 || method > 3) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric), 2 (multiBandBlending) or 3 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
     CanvasRec *cv; TileRec *tr;
     TRY(canvas_resident_args(ctx, canvas, tile, y0, x0, &cv, &tr));
     const int h = tr->h, w = tr->w;
@@ -1864,7 +1896,7 @@ extern "C" int vfsms_canvas_fuse_tile_resident(vfsms_ctx *ctx, int64_t canvas, i
 }
 // The whole mosaic walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over resident tiles as ONE call: per tile nine ints
 // [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode] with mode -1 = paste (the first tile, notFuse), 0 = fadeInAndFadeOut, 1 = trigonometric,
-// 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending (5 is not a mode).
+// 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending, 7 = optimalSeamLine (5 is not a mode).
 // Enqueue only (one library call per mosaic instead of one per tile; the device chain stays two launches per tile); geometry errors are latched
 // in the canvas and reported by the download, as with vfsms_canvas_fuse_tile_resident(info = NULL).
 extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, int n, const int64_t *tiles, const int32_t *geom)
@@ -1873,7 +1905,7 @@ extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, in
     if (n < 0 || (n > 0 && (!tiles || !geom))) { vfsms_set_error("canvas_assemble_resident: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     for (int i = 0; i < n; i++) {                       // everything is checked before anything is enqueued
         const int32_t *g = geom + 9 * (size_t)i;
-        if (g[8] < -1 || g[8] > 6 || g[8] == 5) { vfsms_set_error("canvas_assemble_resident: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum), 6 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
+        if (g[8] < -1 || g[8] > 7 || g[8] == 5) { vfsms_set_error("canvas_assemble_resident: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum), 6 (multiBandBlending), 7 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
         CanvasRec *cv; TileRec *tr;
         TRY(canvas_resident_args(ctx, canvas, tiles[i], g[0], g[1], &cv, &tr));
         if (g[8] >= 0 && g[4] > g[2] && g[5] > g[3] && (g[2] < g[0] || g[3] < g[1] || g[4] > g[0] + tr->h || g[5] > g[1] + tr->w)) {
@@ -1883,7 +1915,7 @@ extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, in
     for (int i = 0; i < n; i++) {
         const int32_t *g = geom + 9 * (size_t)i;
         if (g[8] < 0) TRY(vfsms_canvas_paste_tile(ctx, canvas, tiles[i], g[0], g[1]));
-        else if (g[8] == 6) TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], 2, nullptr));
+        else if (g[8] >= 6) TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8] - 4, nullptr));
         else if (g[8] >= 2) TRY(vfsms_canvas_blend_tile_resident(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[8] - 2));
         else TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], nullptr));
     }
@@ -1897,6 +1929,17 @@ extern "C" int vfsms_canvas_set_multiband_levels(vfsms_ctx *ctx, int64_t canvas,
     if (it == ctx->canvases.end()) { vfsms_set_error("canvas_set_multiband_levels: unknown handle"); return VFSMS_ERR_BAD_ARG; }
     if (levels < 1 || levels > VFSMS_MB_MAX_LEVELS) { vfsms_set_error("canvas_set_multiband_levels: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
     it->second.mb_levels = levels;
+    return VFSMS_OK;
+}
+// how the canvas's optimalSeamLine fuses (method 3 / geom mode 7) merge the two sides of the seam: 0 none (every pixel from one input),
+// 1 multiBandBlending with the canvas's level count; a new canvas starts at 0
+extern "C" int vfsms_canvas_set_seam_blend(vfsms_ctx *ctx, int64_t canvas, int blend)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->canvases.find(canvas);
+    if (it == ctx->canvases.end()) { vfsms_set_error("canvas_set_seam_blend: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    if (blend < 0 || blend > 1) { vfsms_set_error("canvas_set_seam_blend: blend must be 0 (none) or 1 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
+    it->second.seam_blend = blend;
     return VFSMS_OK;
 }
 extern "C" int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out)

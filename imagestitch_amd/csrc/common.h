@@ -177,7 +177,7 @@ struct MatchDev {
 struct TileRec { uint8_t *ptr; int h, w, stride; bool owned; hipEvent_t ready; bool pending; int ch = 1; size_t bytes = 0; int fill = 0; };
 struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device staging of one decoded source image (vfsms_tile_fill_pair)
 struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
-struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; };   // d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; };   // d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct ProfRec { int id; hipEvent_t a, b; };
@@ -212,6 +212,7 @@ struct vfsms_ctx {
     std::vector<hipEvent_t> event_pool;
     std::unordered_map<int64_t, CanvasRec> canvases;
     void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;
+    void *seam_scratch = nullptr; size_t seam_scratch_bytes = 0;   // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
     void *sift_scratch = nullptr; size_t sift_scratch_bytes = 0;   // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
@@ -308,6 +309,12 @@ struct SeamGeom;
 int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
                     const SeamGeom &G, int levels);
 int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, const SeamGeom &G, int levels, uint8_t *d_out);
+// seam_kernels.hip: fuseMethod "optimalSeamLine".  hostkind 1 / 2: a strip the host decided on, 0: geometry from mode[] on the device; wmax:
+// an upper bound of a seam's positions; blend 0 none, 1 multiBandBlending with `levels`
+int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
+                     int dx, int dy, int hostkind, const int *mode, int wmax, int blend, int levels);
+int seam_fuse_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy, const int *mode,
+                  int blend, int levels, uint8_t *d_out, int32_t *d_seam);
 
 // sift_kernels.hip
 #define VFSMS_SIFT_MAX_LAYERS 8

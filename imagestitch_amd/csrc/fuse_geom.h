@@ -1,5 +1,5 @@
-// fuse_geom.h -- the fade blend's per-pixel weight geometry, shared by the fade kernels (fuse_kernels.hip) and the multi-band
-// blend's seam mask (multiband_kernels.hip).
+// fuse_geom.h -- the fade blend's per-pixel weight geometry, shared by the fade kernels (fuse_kernels.hip), the multi-band
+// blend's seam mask (multiband_kernels.hip) and the optimal seam's hand-over to that blend (seam_kernels.hip).
 #pragma once
 #include "common.h"
 
@@ -27,18 +27,27 @@ struct AnalyticRamps {
     __device__ __forceinline__ float a_row(int i) const { return kind == 2 ? ratio(dx <= 0 ? i : r - i, r) : 1.f; }
     __device__ __forceinline__ float b_row(int i) const { return kind == 2 ? ratio(dx <= 0 ? r - 1 - i : i + 1, r) : 1.f; }
 };
+// the index range [lo, lo + W) on which a corner ramp is written (corner_b above), W = 0: none.  `at` = rowIndex / colIndex, n = r / c
+__host__ __device__ inline void seam_arm(int n, int at, bool up, int &lo, int &W)
+{
+    if (up) { lo = 0; W = at >= 1 ? (at < n - 1 ? at : n - 1) + 1 : 0; }
+    else { lo = at > 0 ? at : 0; W = n - lo > 0 ? n - lo : 0; }
+}
 // The multi-band blend's seam: M0 = 1 where the fade gives tile A at least tile B's weight (wA >= wB), 0 elsewhere.  wA and wB are
 // formed exactly as the fade kernels form them (k_fuse_apply / k_i64_apply), from one of three geometry sources:
 //   kind 0: the separable ramp arrays of the statistics kernels, mode[0] = corner flag (wB = wBr wBc, wA = 1 - wB; else wAr wAc, wBr wBc)
 //   kind 1 / 2: the strip ramps in closed form (AnalyticRamps, along the columns / rows)
 //   kind 3: getWeightsMatrix's corner ramps from the device-side pick {., ., index, rowIndex, colIndex} in mode[0..4]
+//   kind 4: an explicit mask plane, label[r][c] != 0 -> A (the optimal seam's label plane, seam_kernels.hip)
 struct SeamGeom {
     int kind, r, c, dx, dy;
     const int *mode;
     const float *wAr, *wAc, *wBr, *wBc;
+    const uint8_t *label;
     __device__ __forceinline__ float m0(int i, int j) const
     {
         float wA, wB;
+        if (kind == 4) return label[(size_t)i * c + j] ? 1.f : 0.f;
         if (kind == 0) {
             wB = wBr[i] * wBc[j];
             wA = mode[0] ? 1 - wB : wAr[i] * wAc[j];

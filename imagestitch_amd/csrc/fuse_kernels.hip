@@ -722,6 +722,7 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int
         const double nel = (double)r * c * cv->ch;
         if ((double)valid / nel > 0.65) {
             if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{c <= r ? 1 : 2, r, c, dx, dy}, cv->mb_levels));
+            else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, c <= r ? 1 : 2, nullptr, std::min(r, c), cv->seam_blend, cv->mb_levels));
             else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
                                     (const int *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, c <= r ? 1 : 2);
             HIP_TRY(hipGetLastError());
@@ -781,12 +782,21 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int
             P.rowIndex[index] = rowIndex; P.colIndex[index] = colIndex; P.err[index] = err;
         }
         hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err, wx_n);
+        int seam_wmax = 1;                                // the widest arm any of the four picks can give the optimal seam (sizes its planes)
+        for (int index = 0; index < 4 && method == 3; index++) {
+            if (P.err[index]) continue;
+            int lo, W;
+            seam_arm(r, P.rowIndex[index], index == 2 || index == 1, lo, W); seam_wmax = std::max(seam_wmax, W);
+            seam_arm(c, P.colIndex[index], index == 2 || index == 3, lo, W); seam_wmax = std::max(seam_wmax, W);
+        }
         if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{3, r, c, dx, dy, S.out}, cv->mb_levels));
+        else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, 0, S.out, seam_wmax, cv->seam_blend, cv->mb_levels));
         else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
                            (const int *)S.out, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, 3);
     } else {
         hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, dx, dy, cv->d_err, wx_n);
         if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{0, r, c, dx, dy, S.out, S.wAr, S.wAc, S.wBr, S.wBc}, cv->mb_levels));
+        else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, 0, S.out, std::max(r, c), cv->seam_blend, cv->mb_levels));
         else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
                            d_tile, h, w, y0, x0, ry0, rx0, r, c, (const int *)S.out, (const float *)S.wAr, (const float *)S.wAc, (const float *)S.wBr, (const float *)S.wBc, TG, 0);
     }
@@ -816,9 +826,10 @@ int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv)
     return VFSMS_OK;
 }
 
-// A, B: device int64 [r][c][ch]; out: device u8.  method 0 fade, 1 trigonometric, 2 multi-band with `levels` (its seam from the fade's ramps)
+// A, B: device int64 [r][c][ch]; out: device u8.  method 0 fade, 1 trigonometric, 2 multi-band with `levels` (its seam from the fade's ramps),
+// 3 optimal seam line (seam_blend 0 none / 1 multi-band with `levels`; d_seam: optional r + c seam entries on the device)
 int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy,
-                    uint8_t *d_out, int32_t *info, int method, int levels)
+                    uint8_t *d_out, int32_t *info, int method, int levels, int seam_blend, int32_t *d_seam)
 {
     FuseScratch S;
     TRY(fuse_scratch(ctx, r, c, &S));
@@ -828,6 +839,7 @@ int fuse_i64_device(vfsms_ctx *ctx, const long long *dA, const long long *dB, in
     hipLaunchKernelGGL(k_i64_stats_cols, dim3((c + 255) / 256), dim3(256), 0, ctx->stream, V, r, c, S.colFirst, S.colLast);
     TRY(launch_weights(ctx, S, r, c, ch, dx, dy));
     if (method == 2) TRY(mb_blend_i64(ctx, dA, dB, r, c, ch, SeamGeom{0, r, c, dx, dy, S.out, S.wAr, S.wAc, S.wBr, S.wBc}, levels, d_out));
+    else if (method == 3) TRY(seam_fuse_i64(ctx, dA, dB, r, c, ch, dx, dy, S.out, seam_blend, levels, d_out, d_seam));
     else hipLaunchKernelGGL(k_i64_apply, dim3((c + 255) / 256, r), dim3(256), 0, ctx->stream, V, r, c, S.out,
                             S.wAr, S.wAc, S.wBr, S.wBc, d_out, TrigGeom{method == 1, r, c, dx, dy});
     HIP_TRY(hipGetLastError());

@@ -4,7 +4,7 @@ Stitcher.getStitchByOffset hands to fuseImage (Stitcher.py:434-436,475-483).
 
 On the hot path (north_star): fuseByFadeInAndFadeOut + getWeightsMatrix -> HIP (csrc/fuse_kernels.hip); fuseByTrigonometric
 shares their kernels (scope row f-4); fuseByMultiBandBlending takes its seam from the same geometry and blends with the pyramid
-kernels of csrc/multiband_kernels.hip.  fuseByAverage / Maximum / Minimum are numpy one-liners as array operators (inside
+kernels of csrc/multiband_kernels.hip; fuseByOptimalSeamLine routes a minimum-cost seam through the same geometry (csrc/seam_kernels.hip).  fuseByAverage / Maximum / Minimum are numpy one-liners as array operators (inside
 Stitcher.getStitchByOffset they run on the device canvas: vfsms_canvas_blend_tile).
 """
 import numpy as np
@@ -81,5 +81,20 @@ class ImageFusion(Utility.Method):
         imageA[hole] = imageB[hole]
         return out
 
-    def fuseByOptimalSeamLine(self, images, direction="horizontal"):
-        raise NotImplementedError("optimal seam line (ImageFusion.py:377-492, interactive cv2.imshow) is outside the VFSMS hot path")
+    # ---- optimal seam line ---------------------------------------------------------------------------------------------------
+    def fuseByOptimalSeamLine(self, images, dx=0, dy=0):
+        """The overlap cut along a minimum-cost connected seam, gray or colour, on the device (vfsms_fuse_seam_i64): an integer energy
+        of the tiles' difference and its central differences, dynamic programming inside the fade's geometry (one seam across a strip;
+        a horizontal and a vertical seam inside the corner ramps' arms in corner mode; geometries the fade refuses are refused the same
+        way).  self.seamLineBlend "none": every output pixel is a pixel of one tile; "multiBandBlending": the seam's label plane is the
+        mask of the pyramid blend with self.multiBandLevels levels.  The arithmetic is this project's own specification
+        (tests/seam_ref.py), NOT a restatement of the reference's interactive, gray-only ImageFusion.py:377-492.
+        Like the fade, empty pixels of imageA are filled from imageB IN PLACE."""
+        (imageA, imageB) = images
+        eng = self.engine
+        if not hasattr(eng, "fuse_seam_i64"):
+            raise NotImplementedError("fuseMethod 'optimalSeamLine' needs an engine with fuse_seam_i64")
+        out = eng.fuse_seam_i64(imageA, imageB, dx, dy, blend=str(self.seamLineBlend), levels=int(self.multiBandLevels))
+        hole = imageA < 0
+        imageA[hole] = imageB[hole]
+        return out

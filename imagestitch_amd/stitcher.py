@@ -240,7 +240,8 @@ class Stitcher(Utility.Method):
         reg = self._makeRegistrar(method, len(fileList))
         device_fuse = (self.fuseMethod in ("notFuse", "fadeInAndFadeOut", "trigonometric") and hasattr(eng, "canvas_fuse_tile_resident")) or \
                       (self.fuseMethod in ("average", "maximum", "minimum") and hasattr(eng, "canvas_blend_tile_resident")) or \
-                      (self.fuseMethod == "multiBandBlending" and hasattr(eng, "canvas_fuse_tile_resident") and hasattr(eng, "canvas_set_multiband_levels"))
+                      (self.fuseMethod == "multiBandBlending" and hasattr(eng, "canvas_fuse_tile_resident") and hasattr(eng, "canvas_set_multiband_levels")) or \
+                      (self.fuseMethod == "optimalSeamLine" and hasattr(eng, "canvas_fuse_tile_resident") and hasattr(eng, "canvas_set_seam_blend"))
         # the tiles the mosaic is assembled from stay in HBM: the registration planes themselves for gray mosaics, and for colour mosaics
         # (Main.py:14's default) the B G R tiles the SAME decode produced -- every file is decoded exactly once (Stitcher.py:68-69, 382-403)
         color = bool(self.isColorMode) and device_fuse and hasattr(eng, "tile_fill_pair")
@@ -775,8 +776,10 @@ class Stitcher(Utility.Method):
         resident = self.__dict__.pop("_resident", None) or {}
         # multiBandBlending runs on the canvas with engines that can set its level count (the CPU test doubles blend through fuseImage)
         multiband = self.fuseMethod == "multiBandBlending" and hasattr(eng, "canvas_set_multiband_levels")
-        device_fuse = self.fuseMethod in ("notFuse", "fadeInAndFadeOut", "trigonometric") or multiband
-        fmethod = 1 if self.fuseMethod == "trigonometric" else 2 if multiband else 0
+        # optimalSeamLine likewise with engines that can set the canvas's seam blend
+        seamline = self.fuseMethod == "optimalSeamLine" and hasattr(eng, "canvas_set_seam_blend")
+        device_fuse = self.fuseMethod in ("notFuse", "fadeInAndFadeOut", "trigonometric") or multiband or seamline
+        fmethod = 1 if self.fuseMethod == "trigonometric" else 2 if multiband else 3 if seamline else 0
         simple = {"average": 0, "maximum": 1, "minimum": 2}.get(self.fuseMethod)
         if simple is not None and not hasattr(eng, "canvas_blend_tile"):
             simple = None
@@ -823,6 +826,10 @@ class Stitcher(Utility.Method):
             try:
                 if multiband:
                     eng.canvas_set_multiband_levels(canvas, int(self.multiBandLevels))
+                if seamline:
+                    eng.canvas_set_seam_blend(canvas, str(self.seamLineBlend))
+                    if hasattr(eng, "canvas_set_multiband_levels"):
+                        eng.canvas_set_multiband_levels(canvas, int(self.multiBandLevels))
                 one_call = use_res and hasattr(eng, "canvas_assemble_resident")
                 if one_call:
                     # every tile is resident: the walk below as ONE library call (the per-tile calls cost the host more than
@@ -837,7 +844,7 @@ class Stitcher(Utility.Method):
                         else:
                             geom[i] = (oy, ox, max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]), min(oy + th, rangeX[i - 1][1]),
                                        min(ox + tw, rangeY[i - 1][1]), originOffsetList[i][0], originOffsetList[i][1],
-                                       (6 if multiband else fmethod) if simple is None else 2 + simple)
+                                       (6 if multiband else 7 if seamline else fmethod) if simple is None else 2 + simple)
                     eng.canvas_assemble_resident(canvas, handles, geom)
                 for i in range(n if one_call else 0, n):
                     self.printAndWrite("  stitching " + str(fileList[i]))
@@ -960,9 +967,10 @@ class Stitcher(Utility.Method):
         """Stitcher.py:488-525: dispatch on fuseMethod (int64 regions with -1 = empty)."""
         self.imageFusion.isColorMode = self.isColorMode
         self.imageFusion.multiBandLevels = self.multiBandLevels
+        self.imageFusion.seamLineBlend = self.seamLineBlend
         self.imageFusion._engine = self._engine
         (imageA, imageB) = images
-        if self.fuseMethod not in ("fadeInAndFadeOut", "trigonometric", "multiBandBlending"):
+        if self.fuseMethod not in ("fadeInAndFadeOut", "trigonometric", "multiBandBlending", "optimalSeamLine"):
             imageA[imageA == -1] = 0
             imageB[imageB == -1] = 0
             imageA[imageA == 0] = imageB[imageA == 0]
@@ -983,5 +991,7 @@ class Stitcher(Utility.Method):
             # the raw -1 regions, not zero-filled: the seam comes from A's -1 pattern as in the fade
             return self.imageFusion.fuseByMultiBandBlending(images, dx, dy)
         if self.fuseMethod == "optimalSeamLine":
-            raise NotImplementedError("fuseMethod %r is outside the VFSMS hot path (interactive in the reference, ImageFusion.py:377-492)" % self.fuseMethod)
+            # the raw -1 regions: geometry and the seam's free passage through holes come from the -1 patterns (an engine without
+            # fuse_seam_i64 cannot run the method: fuseByOptimalSeamLine raises NotImplementedError before anything is touched)
+            return self.imageFusion.fuseByOptimalSeamLine(images, dx, dy)
         return np.zeros(imageA.shape, np.uint8)

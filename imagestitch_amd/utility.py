@@ -136,6 +136,9 @@ class Method():
 
     # ---- fusion (fuseMethod "multiBandBlending": pyramid levels, ImageFusion.fuseByMultiBandBlending / the device canvas) ----
     multiBandLevels = 4
+    # fuseMethod "optimalSeamLine": how the two sides of the seam are merged -- "none" (every pixel from one tile) or "multiBandBlending"
+    # (the seam's label plane as the mask of the pyramid blend with multiBandLevels levels)
+    seamLineBlend = "none"
 
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None

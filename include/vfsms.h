@@ -286,6 +286,17 @@ int vfsms_fuse_trig_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int 
 int vfsms_fuse_multiband_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
                              int dx, int dy, int levels, uint8_t *out, int32_t *info);
 
+/* optimalSeamLine([A,B],dx,dy), same representation: the overlap is cut along a minimum-cost connected seam (an integer energy of the
+ * difference A' - B' and its central differences, dynamic programming with lowest-index tie-breaks) inside the fade's geometry: one
+ * seam across a strip, a horizontal and a vertical seam inside the corner ramps' arms in corner mode.  blend 0: every output pixel is a
+ * pixel of one input; blend 1: the label plane replaces the fade-tie mask of the multi-band blend with `levels` (1..8) levels.
+ * seam_out (optional, r + c ints): the vertical seam's column per row, then the horizontal seam's row per column, -1 where that seam
+ * does not exist.  The arithmetic is this library's own specification (tests/seam_ref.py), not a restatement of the reference's
+ * interactive ImageFusion.fuseByOptimalSeamLine.  info and the degenerate corner geometries that fail: as vfsms_fuse_fade_i64 (then
+ * info[0] = -1, out is zero, seam_out is -1).                                                                                        */
+int vfsms_fuse_seam_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
+                        int dx, int dy, int blend, int levels, uint8_t *out, int32_t *info, int32_t *seam_out);
+
 /* The separable float32 ramps behind that blend, without blending: ramps = [wA_r(r) | wB_r(r) | wA_c(c) | wB_c(c)].
  * force_corner != 0 -> ImageFusion.getWeightsMatrix (ImageFusion.py:43-190): weightMatB = wB_r x wB_c,
  * weightMatA = 1 - weightMatB.  Otherwise the mode fuseByFadeInAndFadeOut itself would pick (info[0]).   */
@@ -405,7 +416,8 @@ int vfsms_canvas_fuse_tile(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, 
                            int y0, int x0, int ry0, int rx0, int ry1, int rx1,
                            int dx, int dy, int32_t *info);
 /* the same with the blend chosen by `method`: 0 fadeInAndFadeOut, 1 trigonometric (Stitcher.fuseImage, Stitcher.py:488-525),
- * 2 multiBandBlending (vfsms_fuse_multiband_i64 on the canvas, levels from vfsms_canvas_set_multiband_levels)                 */
+ * 2 multiBandBlending (vfsms_fuse_multiband_i64 on the canvas, levels from vfsms_canvas_set_multiband_levels),
+ * 3 optimalSeamLine (vfsms_fuse_seam_i64 on the canvas, blend from vfsms_canvas_set_seam_blend)                                  */
 int vfsms_canvas_fuse_tile_m(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, int h, int w,
                              int y0, int x0, int ry0, int rx0, int ry1, int rx1,
                              int dx, int dy, int method, int32_t *info);
@@ -430,11 +442,14 @@ int vfsms_canvas_fuse_tile_resident_m(vfsms_ctx *ctx, int64_t canvas, int64_t ti
                                       int dx, int dy, int method, int32_t *info);
 /* The canvas walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over n resident tiles in one call.
  * geom: n x 9 ints [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode], mode -1 = paste (first tile / notFuse),
- * 0 = fadeInAndFadeOut, 1 = trigonometric, 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending (5 is refused).  Enqueue only: errors of a
+ * 0 = fadeInAndFadeOut, 1 = trigonometric, 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending, 7 = optimalSeamLine (5 is refused).  Enqueue only: errors of a
  * tile's geometry surface in the download. */
 int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, int n, const int64_t *tiles, const int32_t *geom);
 /* pyramid levels (1..8) of the canvas's multiBandBlending fuses; a new canvas starts at 4                                      */
 int vfsms_canvas_set_multiband_levels(vfsms_ctx *ctx, int64_t canvas, int levels);
+/* how the canvas's optimalSeamLine fuses merge the two sides of the seam: 0 none, 1 multiBandBlending (with the canvas's level count);
+ * a new canvas starts at 0                                                                                                          */
+int vfsms_canvas_set_seam_blend(vfsms_ctx *ctx, int64_t canvas, int blend);
 /* final image: empty -> 0 (Stitcher.py:485-486).  out: u8 [rows][cols][ch]                           */
 int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out);
 /* rows [row0, row0 + nrows) of the same image: a multi-GB mosaic leaves the device band by band and can be handed to an

@@ -1,0 +1,186 @@
+"""fuseMethod "optimalSeamLine" as specified for this project: the overlap is cut along a minimum-cost connected seam found by dynamic
+programming; each side of the seam keeps one input's pixels.  Plain numpy, integer arithmetic only, so the HIP kernels
+(imagestitch_amd/csrc/seam_kernels.hip) must equal it byte for byte -- the pixels AND the seam itself.
+
+This docstring IS the specification.  It is not claimed to match the reference's interactive, gray-only
+ImageFusion.fuseByOptimalSeamLine (ImageFusion.py:377-492), which cannot be run here.
+
+Inputs: int64 regions A, B of shape r x c or r x c x ch, -1 = empty; the pair's offset (dx, dy).
+
+Validity (per pixel, as the fade's kernels count it): a gray pixel is valid where it is not -1, a colour pixel where the sum of its
+channels is not -3.  B's validity is judged by the same rule.
+
+Fill (per element, multiband_ref.fill): A' = A where A >= 0 else B;  B' = B where B >= 0 else A';  empty in both -> 0.
+
+Energy (integer, per pixel): with d_k = A'_k - B'_k,
+    E(i, j) = sum_k |d_k(i, j)| + sum_k (|d_k(i, j + 1) - d_k(i, j - 1)| + |d_k(i + 1, j) - d_k(i - 1, j)|)
+neighbours outside the region replicated (index clamped to the region; in corner mode too the energy is that of the WHOLE region and
+an arm only selects cells of it).  E = 0 where A or B is not valid.  At most 1275 per channel, 5100 for ch <= 4.
+
+Geometry (the fade's, from A's -1 pattern): more than 65 % of A's elements > -1 -> a strip, along the columns when c <= r (kind 1),
+else along the rows (kind 2); otherwise corner mode with getWeightsMatrix's (index, rowIndex, colIndex), refused (IndexError) where the
+fade refuses.
+
+Strip seam on an L x W energy plane (L steps, W positions): one position s(t) per step, |s(t) - s(t - 1)| <= 1, minimising
+sum_t E(t, s(t)).  Forward pass: C(0, p) = E(0, p);  C(t, p) = E(t, p) + min(C(t - 1, p - 1), C(t - 1, p), C(t - 1, p + 1)) over the
+positions that exist, the predecessor being the LOWEST-index minimum.  The end cell is the lowest-index minimum of C(L - 1, .); the seam
+is the chain of predecessors from it.  Cumulative costs are int32: a region with 5100 * max(r, c) > 2^31 - 1 is refused (ValueError)
+whichever seams it has, so no real cost reaches 2^31 - 1, the value the device uses for "no such neighbour".
+
+Kind 1: steps = rows, positions = columns, one column s(i) per row.  A's side is j < s(i) for dy >= 0, j > s(i) for dy < 0 (where the
+fade's a_col is larger).  Kind 2: the transpose, one row s(j) per column; A's side is i > s(j) for dx <= 0, i < s(j) for dx > 0 (where
+a_row is larger).  The seam pixel itself is B.
+
+Corner mode: two independent seams.  The row arm / column arm is the index range on which the fade's corner ramp cb_row / cb_col
+(AnalyticRamps, fuse_geom.h) is written, with `at` = rowIndex / colIndex and n = r / c:
+    ramp counting up   (rows: index 2 or 1; columns: index 2 or 3):  [0, at] when at >= 1, else no arm
+    ramp counting down (the other indices):                          [max(at, 0), n - 1]
+A horizontal seam (one row per column, all c columns) is solved on the rows of the row arm, a vertical seam (one column per row, all r
+rows) on the columns of the column arm, each exactly as a strip on the arm's cells of E.  A's side of a seam is toward the region edge
+where the ramp gives B weight 0: below the seam's index for a ramp counting up, above it for one counting down.  An arm that does not
+exist contributes no seam and no A side.
+
+Label: a pixel is A iff it is A-valid and on A's side of either seam (strip: of the one seam).
+
+Output, blend "none": A' where labelled A, B' elsewhere, as uint8.
+Output, blend "multiBandBlending": multiband_ref.blend_planes(A', B', M0 = label as float32, levels), rounded half to even and clamped.
+
+seam_out (int32, r + c entries): the vertical seam's column per row, then the horizontal seam's row per column (region coordinates),
+-1 where that seam does not exist."""
+import numpy as np
+
+import multiband_ref as MB
+
+E_MAX = 5100
+INF = np.int64(1) << 40
+
+
+def pixel_valid(X):
+    X = np.asarray(X, np.int64)
+    if X.ndim == 2:
+        return X != -1
+    if X.shape[2] == 1:
+        return X[:, :, 0] != -1
+    return X.sum(axis=2) != -3
+
+
+def energy(A, B):
+    """int64 [r][c]"""
+    A = np.asarray(A, np.int64); B = np.asarray(B, np.int64)
+    A1, B1 = MB.fill(A, B)
+    d = A1 - B1
+    if d.ndim == 2:
+        d = d[:, :, None]
+    r, c = d.shape[:2]
+    ip, im = np.minimum(np.arange(r) + 1, r - 1), np.maximum(np.arange(r) - 1, 0)
+    jp, jm = np.minimum(np.arange(c) + 1, c - 1), np.maximum(np.arange(c) - 1, 0)
+    E = np.abs(d).sum(2) + np.abs(d[:, jp] - d[:, jm]).sum(2) + np.abs(d[ip] - d[im]).sum(2)
+    E[~(pixel_valid(A) & pixel_valid(B))] = 0
+    return E
+
+
+def strip_seam(E):
+    """E: [L][W] -> (s int64 [L], total cost): the seam of the docstring, one position per step"""
+    E = np.asarray(E, np.int64)
+    L, W = E.shape
+    if E_MAX * L > 2 ** 31 - 1:
+        raise ValueError("seam too long for int32 cumulative costs")
+    cost = E[0].copy()
+    pred = np.zeros((L, W), np.int8)
+    for t in range(1, L):
+        left = np.concatenate(([INF], cost[:-1]))
+        right = np.concatenate((cost[1:], [INF]))
+        best, d = left.copy(), np.full(W, -1, np.int8)
+        m = cost < best
+        best[m] = cost[m]; d[m] = 0
+        m = right < best
+        best[m] = right[m]; d[m] = 1
+        pred[t] = d
+        cost = best + E[t]
+    s = np.empty(L, np.int64)
+    p = int(np.argmin(cost))
+    total = int(cost[p])
+    for t in range(L - 1, -1, -1):
+        s[t] = p
+        p += int(pred[t, p])
+    return s, total
+
+
+def _arm(n, at, counting_up):
+    """-> (lo, hi) or None"""
+    if counting_up:
+        return (0, min(at, n - 1)) if at >= 1 else None
+    lo = max(at, 0)
+    return (lo, n - 1) if lo <= n - 1 else None
+
+
+def geometry(A, dx, dy, corner_ramps):
+    """-> (vertical, horizontal): each None or (lo, hi, a_low): the seam's positions lie in [lo, hi]; a_low: A's side is below the seam's index"""
+    A = np.asarray(A, np.int64)
+    r, c = A.shape[:2]
+    if np.count_nonzero(A > -1) / A.size > 0.65:
+        if c <= r:
+            return (0, c - 1, dy >= 0), None
+        return None, (0, r - 1, dx > 0)
+    _wr, _wc, info = corner_ramps(A)                     # raises IndexError where the fade refuses
+    index, rowIndex, colIndex = int(info[1]), int(info[2]), int(info[3])
+    row_up, col_up = index in (2, 1), index in (2, 3)
+    ra, ca = _arm(r, rowIndex, row_up), _arm(c, colIndex, col_up)
+    return (None if ca is None else ca + (col_up,)), (None if ra is None else ra + (row_up,))
+
+
+def seams(A, B, dx, dy, corner_ramps):
+    """-> (sv int64 [r] or None, sh int64 [c] or None, label bool [r][c], (cost_v, cost_h))"""
+    A = np.asarray(A, np.int64)
+    r, c = A.shape[:2]
+    if E_MAX * max(r, c) > 2 ** 31 - 1:
+        raise ValueError("region too long for int32 cumulative costs")
+    V, H = geometry(A, dx, dy, corner_ramps)
+    E = energy(A, B)
+    side = np.zeros((r, c), bool)
+    sv = sh = None
+    cv = ch = None
+    if V is not None:
+        lo, hi, a_low = V
+        s, cv = strip_seam(E[:, lo:hi + 1])
+        sv = s + lo
+        j = np.arange(c)[None, :]
+        side |= (j < sv[:, None]) if a_low else (j > sv[:, None])
+    if H is not None:
+        lo, hi, a_low = H
+        s, ch = strip_seam(E[lo:hi + 1, :].T)
+        sh = s + lo
+        i = np.arange(r)[:, None]
+        side |= (i < sh[None, :]) if a_low else (i > sh[None, :])
+    return sv, sh, side & pixel_valid(A), (cv, ch)
+
+
+def seam_out(sv, sh, r, c):
+    out = np.full(r + c, -1, np.int32)
+    if sv is not None:
+        out[:r] = sv
+    if sh is not None:
+        out[r:] = sh
+    return out
+
+
+def seam_fuse(A, B, dx, dy, blend="none", levels=4, corner_ramps=None, return_seam=False):
+    """int64 regions A, B -> uint8 fuse (and seam_out)"""
+    if corner_ramps is None:
+        from oracle import oracle as O
+        corner_ramps = O.corner_ramps
+    if blend not in ("none", "multiBandBlending"):
+        raise ValueError("seamLineBlend must be 'none' or 'multiBandBlending'")
+    if blend != "none" and not 1 <= levels <= 8:
+        raise ValueError("levels must be 1..8")
+    A = np.asarray(A, np.int64); B = np.asarray(B, np.int64)
+    r, c = A.shape[:2]
+    sv, sh, label, _cost = seams(A, B, dx, dy, corner_ramps)
+    A1, B1 = MB.fill(A, B)
+    if blend == "none":
+        lab = label if A.ndim == 2 else label[:, :, None]
+        out = np.where(lab, A1, B1).astype(np.uint8)
+    else:
+        O0 = MB.blend_planes(A1.astype(MB.F), B1.astype(MB.F), label.astype(MB.F), levels)
+        out = np.clip(np.rint(O0), 0, 255).astype(np.uint8)
+    return (out, seam_out(sv, sh, r, c)) if return_seam else out
