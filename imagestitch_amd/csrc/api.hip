@@ -816,7 +816,7 @@ static int pick_nsplit(int nq, int nt, int njobs, int dim)
 // train splits of the MFMA filter: a wave holds 64 queries and two waves share a SIMD, so aim at >= 4 rounds of the
 // 2048 wave slots; more splits mean more candidate lists to verify, hence the cap
 // Round 6: and at least one split per BFM_SPLIT_TRAINS trains.  The candidate lists hold BFM_CAPL = 32 entries per (list, query); what a
-// list admits grows with the trains it covers (the threshold window of the bounds pass is an absolute 1.7e-2 in squared distance), and a
+// list admits grows with the trains it covers (the threshold window of the bounds pass is an absolute 5e-3 in squared distance; 1.7e-2 when these figures were taken), and a
 // query whose list overflows is verified by an exhaustive scan of ALL trains.  configs[4]'s strips (37 k keypoints, large batches: the
 // wave count alone asked for ONE split) spent 11 ms per launch in k_bf_verify_d64 against 0.24 ms at the headline's 8.7 k; with the
 // train rule 4.1 ms (one split per 10240 trains; 5120: another 3 % off the search, profiles/r06_ab_bf_split_4096.txt).

@@ -153,7 +153,7 @@ struct MatchDev {
     // MFMA candidate filter (fused SURF path): per (query, split, lane half) lists of (score bits, train index) + their counts
     uint2 *c_ent; int *c_cnt;
     float2 *c_m12;                    // per (list, query): best / second-best hi-only score of the bounds pass
-    unsigned short *q16, *t16;        // split-bf16 operands of the filter (k_bf_split16): BF16_ROW uint16 per descriptor row
+    unsigned short *q16, *t16;        // fp16 operands of the filter (k_bf_split16): BF16_ROW uint16 per descriptor row
     // integer 2-NN (fused SIFT path, k_bf_i8_d128): descriptors as int8 (element - 128), 128 bytes per row, and the squared norms of those
     // rows; rows padded to whole 64-row tiles (zero rows, norm BFI_PAD_NORM)
     const int8_t *q8, *t8; const int *qn2, *tn2;

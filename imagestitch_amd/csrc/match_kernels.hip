@@ -379,28 +379,35 @@ __global__ __launch_bounds__(256, 2) void k_bf_mfma_d64(const MatchDev *jobs)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The same filter on the bf16 matrix pipe (16x the f32-MFMA rate) with SPLIT operands: every descriptor element x is stored as
-// hi = bf16(x) and lo = bf16(x - hi), and q.t is taken as hi.hi + hi.lo + lo.hi (three v_mfma_f32_32x32x16_bf16 products per 16
-// dims, f32 accumulation).  What is dropped is lo.lo (<= 2^-16 |q_i t_i| per term) and the rounding of lo (2^-17 relative): for
-// norms <= 1 the score is within ~3e-5 of the f32 score -- BFM_MARGIN is 30x that -- and the scores only select WHICH distances the
-// verifier computes exactly.  |t|^2 rides along as one more k-slot (its own hi + lo against 1.0 on the query side).
-// k_bf_split16 writes the operands once per ROI.  Queries (each wave loads its 64 once): row = [dims 0-31: hi x 32 | lo x 32 |
-// dims 32-63: hi x 32 | lo x 32 | 1, 1, 0...].  Trains (every wave streams all of them) are stored in MFMA FRAGMENT order: per
-// 32-train tile nine 1 KB fragments -- hi of k-steps 0..3, lo of k-steps 0..3, the |t|^2 slot -- each holding the 16 bytes of lane 0,
-// lane 1, ... lane 63, so that one load instruction of a wave reads 8 consecutive cache lines instead of one line per lane (the
-// row-major layout kept the texture-address path, not the matrix pipe, busy: 64 lines per load).
+// The same filter on the 16-bit matrix pipe (16x the f32-MFMA rate) with fp16 operands: every descriptor element is stored once as
+// fp16 (round to nearest even; queries pre-scaled by -2, exact) and q.t is ONE v_mfma_f32_32x32x16_f16 product per 16 dims with
+// f32 accumulation.  |t|^2 rides along as one more k-slot: its own two-term fp16 sum hi + lo against 1.0 on the query side, so the
+// norm adds no first-order error.  The scores only select WHICH distances the verifier computes exactly.
+//
+// Error of a score against the exact s = |t|^2 - 2 q.t of the float descriptors (norms^2 <= 1.0001: bf_l2_host checks, SURF's are
+// L2-normalised), BFM_F16_ERR:
+//   - relative: fp16 keeps 11 significand bits, unit roundoff u = 2^-11; a product of two rounded elements is off by at most
+//     ((1 + u)^2 - 1) |a b| (the 22-bit product itself is exact in f32), and sum |2 q_i t_i| <= 2 |q||t| (Cauchy-Schwarz):
+//     2 ((1 + 2^-11)^2 - 1) * 1.0001                                                                               = 1.9538e-3
+//   - absolute: an element below fp16's normal range (|x| < 2^-14 = 6.1e-5, subnormals and zero) is off by up to half the subnormal
+//     spacing, eta = 2^-25, instead of u |x|; a'b' - ab = (a' - a) b' + a (b' - b) adds eta (|b'| + |a|) <= 3 eta per term with
+//     |t_i| <= 1, |2 q_i| <= 2 (the issue's 2^-25 x 64 x 2 counts the query side only): 64 * 3 * 2^-25                = 5.8e-6
+//   - f32 accumulation over the 65 k-slots: partial sums stay below 2 |q||t| + |t|^2 <= 3.01, one rounding of at most 2^-23
+//     relative per slot (2^-24 if the pipe rounds to nearest; the bound does not rely on it): 65 * 2^-23 * 3.01       = 2.33e-5
+//   - the norm slot: |t|^2 summed in f32 by k_bf_split16 (64 additions, <= 64 * 2^-24 * 1.0001 = 3.8e-6) and hi + lo of it (lo
+//     rounds a residual <= 2^-11: 2^-22)                                                                              = 4.1e-6
+//   total 1.987e-3 <= BFM_F16_ERR = 2.0e-3.  tests/test_bf_fp16_host.py emulates the scores in numpy and checks the bound.
+//
+// k_bf_split16 writes the operands once per ROI.  Queries (each wave loads its 64 once): row = [dims 0-31 | dims 32-63 | 1, 1,
+// 0...].  Trains (every wave streams all of them) are stored in MFMA FRAGMENT order: per 32-train tile five 1 KB fragments -- k-steps
+// 0..3, the |t|^2 slot -- each holding the 16 bytes of lane 0, lane 1, ... lane 63, so that one load instruction of a wave reads 8
+// consecutive cache lines instead of one line per lane (the row-major layout kept the texture-address path, not the matrix pipe,
+// busy: 64 lines per load).
 // ---------------------------------------------------------------------------------------------------
-#define BF16_ROW 144                 // uint16 per descriptor row: 2 x (32 hi + 32 lo) + 16 for the norm slot
-#define BF16_FRAGS 9                 // per train tile: 4 hi + 4 lo + norm fragments of 64 lanes x 8 uint16
-typedef short s8v __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned short bf16_rne(float x)
-{
-    unsigned u = __float_as_uint(x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+#define BF16_ROW 80                  // uint16 per descriptor row: 2 x 32 fp16 + 16 for the norm slot
+#define BF16_FRAGS 5                 // per train tile: 4 dimension fragments + the norm fragment, 64 lanes x 8 fp16 each
+#define BFM_F16_ERR 2.0e-3f          // >= |fp16 score - exact score|, derived above
+typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
 // one thread per (descriptor row, 32-dim half); grid (ceil(cap / 128), 2 [q | t], jobs)
 __global__ __launch_bounds__(256) void k_bf_split16(const MatchDev *jobs, float scale_q)
@@ -411,58 +418,55 @@ __global__ __launch_bounds__(256) void k_bf_split16(const MatchDev *jobs, float 
     const int row = blockIdx.x * 128 + (threadIdx.x >> 1), half = threadIdx.x & 1;
     if (row >= n) return;
     const float *src = (is_t ? J.t : J.q) + (size_t)row * 64 + 32 * half;
-    const float sc = is_t ? 1.f : scale_q;                      // queries carry the factor -2 (exact in bf16)
+    const float sc = is_t ? 1.f : scale_q;                      // queries carry the factor -2 (exact; |x| <= 2.0001, no overflow)
     float part = 0.f;
-    s8v hi[4], lo[4];
+    h8v el[4];
 #pragma unroll
     for (int d = 0; d < 32; d++) {
         const float x = src[d];
         part += x * x;
-        const float xs = x * sc;
-        const unsigned short h = bf16_rne(xs);
-        hi[d >> 3][d & 7] = (short)h;
-        lo[d >> 3][d & 7] = (short)bf16_rne(xs - bf16_to_f32(h));
+        el[d >> 3][d & 7] = (_Float16)(x * sc);                 // v_cvt_f16_f32: round to nearest even, subnormals kept
     }
     // norm slot (trains: |t|^2 as hi + lo; queries: 1, 1): k-slots 0 and 1 of the fifth MFMA step, lane half 0 only
     const float tot = part + __shfl_xor(part, 1, 64);
-    s8v ns = {0, 0, 0, 0, 0, 0, 0, 0};
+    h8v ns = {0, 0, 0, 0, 0, 0, 0, 0};
     if (half == 0) {
-        unsigned short a = 0x3f80, b = 0x3f80;                    // 1.0
-        if (is_t) { a = bf16_rne(tot); b = bf16_rne(tot - bf16_to_f32(a)); }
-        ns[0] = (short)a; ns[1] = (short)b;
+        _Float16 a = (_Float16)1.f, b = (_Float16)1.f;
+        if (is_t) { a = (_Float16)tot; b = (_Float16)(tot - (float)a); }
+        ns[0] = a; ns[1] = b;
     }
     if (is_t) {
-        s8v *dst = reinterpret_cast<s8v *>(J.t16) + (size_t)(row >> 5) * (BF16_FRAGS * 64) + (row & 31) + 32 * half;
+        h8v *dst = reinterpret_cast<h8v *>(J.t16) + (size_t)(row >> 5) * (BF16_FRAGS * 64) + (row & 31) + 32 * half;
 #pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) { dst[s4 * 64] = hi[s4]; dst[(4 + s4) * 64] = lo[s4]; }
-        dst[8 * 64] = ns;
+        for (int s4 = 0; s4 < 4; s4++) dst[s4 * 64] = el[s4];
+        dst[4 * 64] = ns;
     } else {
-        s8v *dst = reinterpret_cast<s8v *>(J.q16 + (size_t)row * BF16_ROW + 64 * half);
+        h8v *dst = reinterpret_cast<h8v *>(J.q16 + (size_t)row * BF16_ROW + 32 * half);
 #pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) { dst[s4] = hi[s4]; dst[4 + s4] = lo[s4]; }
-        if (half == 0) *reinterpret_cast<s8v *>(J.q16 + (size_t)row * BF16_ROW + 128) = ns;
+        for (int s4 = 0; s4 < 4; s4++) dst[s4] = el[s4];
+        if (half == 0) *reinterpret_cast<h8v *>(J.q16 + (size_t)row * BF16_ROW + 64) = ns;
     }
 }
 
-// Two launches.  PASS 0 (bounds): hi.hi products only (5 MFMAs per accumulator and tile) and a branch-free running (best, second
-// best) per lane, written per (list, query).  Its scores are within BFM_HI_ERR of the split scores, so
-//     thr(q) = second best over all lists + BFM_HI_ERR + BFM_MARGIN
-// is an upper bound of the true second-best score plus the margin, known BEFORE the second sweep.  PASS 1 (candidates): full split
-// products; a train is listed when its score is <= thr(q) -- a handful per query instead of the ~2 ln(n) records per list that a
-// running threshold admits, so the append branch is almost never taken (one min3 tree + one ballot per accumulator decides) and
-// the verifier has a few distances to evaluate instead of ~200.
-// (measured, round 6: skipping the eight correction k-steps of tiles whose hi.hi scores all lie above the thresholds made pass 1 8 % SLOWER --
-//  0.652 -> 0.703 ms on the 16-pair batch, profiles/r06_ab_bf_skip.txt: the extra minimum tree and the wave-uniform branch break the MFMA
-//  chain, and the matrix pipe was only 0.54 busy to begin with; kept behind the switch)
-#ifndef VFSMS_BF_SKIP
-#define VFSMS_BF_SKIP 0
-#endif
+// Two launches over the same five k-steps per tile (four of dimensions + the norm slot), so both see the SAME scores (same
+// instructions in the same order).  PASS 0 (bounds): a branch-free running (best, second best) per lane, written per (list, query);
+// m2(q), the second best over all lists, is >= the second smallest fp16 score of the query.  PASS 1 (candidates): a train is listed
+// when its score is <= thr(q) = m2(q) + 2 BFM_F16_ERR + BFM_MARGIN, known BEFORE the sweep -- a handful per query instead of the
+// ~2 ln(n) records per list that a running threshold admits, so the append branch is almost never taken (one min3 tree + one ballot
+// per accumulator decides).
+// Superset: write S for exact scores, s for fp16 scores, |s - S| <= E = BFM_F16_ERR, and S2 / s2 for the second smallest of each
+// over the trains.  The two trains of smallest s have S <= s2 + E, so S2 <= s2 + E.  The reference's float distances order the
+// trains like S up to its own rounding, which BFM_MARGIN covers 40-fold: a train that can come out best or second best has
+// S <= S2 + BFM_MARGIN, hence s <= S2 + BFM_MARGIN + E <= s2 + 2 E + BFM_MARGIN <= thr(q).  Every such train is listed; the verifier
+// applies the same window around the s2 it reads back from the lists (they hold the two smallest scores, so that s2 is the true one).
+// (The split-bf16 form of rounds 2-6 -- hi.hi + hi.lo + lo.hi, 13 k-steps and nine fragments in pass 1 -- and its switch that skipped
+//  the correction k-steps per tile, 8 % slower, are gone: profiles/r06_ab_bf_skip.txt)
 #ifndef BFM_GLDS
 #define BFM_GLDS 1                // round 6: train tiles reach LDS by LDS-DMA (global_load_lds_dwordx4), not through registers
 #endif
-#define BFM_HI_ERR 1.6e-2f           // >= 2 * ((1 + 2^-8)^2 - 1) * |q||t| = 1.57e-2 (bf16 keeps 8 significand bits: RNE unit roundoff 2^-8) + the split filter's own 3e-5
+#define BFM_WINDOW (2.f * BFM_F16_ERR + BFM_MARGIN)      // what a listed fp16 score may lie above the second-best fp16 score (superset argument above)
 #define GASM __attribute__((address_space(1)))
-typedef GASM const s8v *g_cs8v;
+typedef GASM const h8v *g_cs8v;
 typedef float f2v __attribute__((ext_vector_type(2)));
 
 #ifdef VFSMS_DESC_TIMING
@@ -496,43 +500,40 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
     const int tchunk = (ntiles + nsplit - 1) / nsplit;
     const int tile0 = sp * tchunk, tile1 = min(ntiles, tile0 + tchunk);
     const int col = lane & 31, half = lane >> 5;
-    const s8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    // B operands (queries, resident): per 16-dim step s the lane's 8 hi and 8 lo values of dims 32*half + 8*s .. + 7
-    s8v bh0[4], bl0[4], bh1[4], bl1[4], bn0, bn1;
+    const h8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // B operands (queries, resident): per 16-dim step s the lane's 8 values of dims 32*half + 8*s .. + 7
+    h8v bh0[4], bh1[4], bn0, bn1;
     {
-        g_cs8v p0 = (g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 64 * half);
-        g_cs8v p1 = (g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 64 * half);
+        g_cs8v p0 = (g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 32 * half);
+        g_cs8v p1 = (g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 32 * half);
 #pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) {
-            bh0[s4] = p0[s4]; bh1[s4] = p1[s4];
-            if (PASS == 1) { bl0[s4] = p0[4 + s4]; bl1[s4] = p1[4 + s4]; } else { bl0[s4] = zero; bl1[s4] = zero; }
-        }
-        bn0 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 128) : zero;
-        bn1 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 128) : zero;
+        for (int s4 = 0; s4 < 4; s4++) { bh0[s4] = p0[s4]; bh1[s4] = p1[s4]; }
+        bn0 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 64) : zero;
+        bn1 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 64) : zero;
     }
     // Train tiles go through LDS: the four waves of a workgroup sweep the SAME tiles (for different queries), so one cooperative
-    // copy per tile (2.25 x 16 B per thread, straight in fragment order) replaces four sets of per-wave loads, and the operands
+    // copy per tile (1.25 x 16 B per thread, straight in fragment order) replaces four sets of per-wave loads, and the operands
     // arrive by ds_read_b128 instead of waiting on L2.  The waves meet once per UNIT of BFM_UNIT tiles (they sit on four SIMDs, each
     // shared with other workgroups: every meeting waits for the slowest): two buffers of one unit each; unit u + 1 is put into the
     // buffer that unit u - 1 vacated right after the barrier (it was fetched into registers an iteration ago), unit u + 2 is fetched
     // before the MFMAs of unit u.
-    constexpr int NFR = PASS == 0 ? 5 : BF16_FRAGS;      // fragments staged: hi x 4 (+ lo x 4) + norm
+    constexpr int NFR = BF16_FRAGS;                      // fragments staged: dimensions x 4 + norm
     constexpr int BFM_UNIT = 2;                          // train tiles per meeting (four in pass 0 -- twice the bytes in flight -- changed nothing)
-    __shared__ s8v stage[2][BFM_UNIT][NFR * 64];
-    g_cs8v T = (g_cs8v)J.t16;                            // fragment order: tile * 9 fragments * 64 lanes (k_bf_split16)
+    __shared__ h8v stage[2][BFM_UNIT][NFR * 64];
+    g_cs8v T = (g_cs8v)J.t16;                            // fragment order: tile * 5 fragments * 64 lanes (k_bf_split16)
     const int tid = threadIdx.x; (void)tid;
     // Units are fetched BFM_SETS + 1 ahead of their MFMAs into BFM_SETS register sets (pass 0 has the registers for two: its iteration --
     // ten MFMAs per tile -- is shorter than a trip to memory, and half of its wave cycles were the wait in front of the put).
 #if BFM_GLDS
     // Round 6: a tile's fragments are ONE lane-linear block in global memory (k_bf_split16 writes them in fragment order) and the same block
-    // in LDS, so the copy is LDS-DMA: wave w issues global_load_lds_dwordx4 for the 1 KB chunks w and 4 + w (wave 0 also the norm
-    // fragment) -- two or three instructions per tile and wave, no staging registers (24 VGPRs), no ds_write pass.  Unit u + 1 is
+    // in LDS, so the copy is LDS-DMA: wave w issues global_load_lds_dwordx4 for the 1 KB chunk w (wave 0 also the norm
+    // fragment) -- one or two instructions per tile and wave, no staging registers (24 VGPRs), no ds_write pass.  Unit u + 1 is
     // requested right behind the barrier that frees its buffer and has the whole of unit u's MFMAs to land; the barrier's vmcnt(0)
     // (hipcc drains the DMA in front of __syncthreads) is what makes it visible.  (profiles/r06_glds_probe.txt: the instruction takes
     // 4-byte-aligned global addresses and partial EXEC.)
     constexpr int NSET = 1;
     const int wv_u = __builtin_amdgcn_readfirstlane(wave);
-    auto glds16 = [&](g_cs8v src, const s8v *dst) {
+    auto glds16 = [&](g_cs8v src, const h8v *dst) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
     };
     auto fetch = [&](int unit, int b) {
@@ -541,21 +542,18 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
             const int tl = min(tile0 + unit * BFM_UNIT + u, tile1 - 1);
             g_cs8v pn = T + (size_t)tl * (BF16_FRAGS * 64);
             glds16(pn + 64 * wv_u + lane, &stage[b][u][64 * wv_u]);
-            if (PASS == 1) {
-                glds16(pn + 256 + 64 * wv_u + lane, &stage[b][u][256 + 64 * wv_u]);
-                if (wv_u == 0) glds16(pn + 512 + lane, &stage[b][u][PASS == 1 ? 512 : 0]);
-            } else if (wv_u == 0) glds16(pn + 512 + lane, &stage[b][u][256]);
+            if (wv_u == 0) glds16(pn + 256 + lane, &stage[b][u][256]);
         }
     };
     const int nunits = (tile1 - tile0 + BFM_UNIT - 1) / BFM_UNIT;
     if (nunits > 0) fetch(0, 0);
 #else
     constexpr int NSET = PASS == 0 ? 2 : 1;
-    s8v g0[NSET][BFM_UNIT], g1[NSET][BFM_UNIT], g2[NSET][BFM_UNIT];
+    h8v g0[NSET][BFM_UNIT], g1[NSET][BFM_UNIT];
 #pragma unroll
     for (int e = 0; e < NSET; e++)
 #pragma unroll
-        for (int u = 0; u < BFM_UNIT; u++) { g0[e][u] = zero; g1[e][u] = zero; g2[e][u] = zero; }
+        for (int u = 0; u < BFM_UNIT; u++) { g0[e][u] = zero; g1[e][u] = zero; }
     const int nunits = (tile1 - tile0 + BFM_UNIT - 1) / BFM_UNIT;
     // (no branch around a load: beyond the chunk the last tile is fetched again and never used, every thread fetches a norm fragment lane --
     //  with a fixed number of loads per fetch the compiler waits for exactly the set it is about to put, not for everything outstanding)
@@ -565,16 +563,14 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
             const int tl = min(tile0 + unit * BFM_UNIT + u, tile1 - 1);
             g_cs8v pn = T + (size_t)tl * (BF16_FRAGS * 64);
             g0[e][u] = pn[tid];
-            if (PASS == 1) { g1[e][u] = pn[256 + tid]; g2[e][u] = pn[512 + (tid & 63)]; }
-            else g1[e][u] = pn[512 + (tid & 63)];
+            g1[e][u] = pn[256 + (tid & 63)];
         }
     };
     auto put = [&](int b, int e) {
 #pragma unroll
         for (int u = 0; u < BFM_UNIT; u++) {
             stage[b][u][tid] = g0[e][u];
-            if (PASS == 1) { stage[b][u][256 + tid] = g1[e][u]; if (tid < 64) stage[b][u][512 + tid] = g2[e][u]; }
-            else if (tid < 64) stage[b][u][256 + tid] = g1[e][u];
+            if (tid < 64) stage[b][u][256 + tid] = g1[e][u];
         }
     };
     if (nunits > 0) fetch(0, 0);                     // under way while the query operands and the thresholds arrive
@@ -582,10 +578,7 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
     // Pin the query operands as "defined here": the compiler otherwise carries their load waits into the tile loop as in-order
     // vmcnt counts, which also drain the train prefetch issued at the top of every iteration (a full L2 round trip per tile).
 #pragma unroll
-    for (int s4 = 0; s4 < 4; s4++) {
-        asm volatile("" : "+v"(bh0[s4]), "+v"(bh1[s4]));
-        if (PASS == 1) asm volatile("" : "+v"(bl0[s4]), "+v"(bl1[s4]));
-    }
+    for (int s4 = 0; s4 < 4; s4++) asm volatile("" : "+v"(bh0[s4]), "+v"(bh1[s4]));
     asm volatile("" : "+v"(bn0), "+v"(bn1));
     const bool va = q0 + col < nq, vb = q0 + 32 + col < nq;
     const size_t pitch = (size_t)J.capq;
@@ -610,8 +603,8 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
                 b2 = fminf(fminf(b2, ub[k].y), fmaxf(b1, ub[k].x)); b1 = fminf(b1, ub[k].x);
             }
         }
-        if (va) thra = a2 + (BFM_HI_ERR + BFM_MARGIN);
-        if (vb) thrb = b2 + (BFM_HI_ERR + BFM_MARGIN);
+        if (va) thra = a2 + BFM_WINDOW;
+        if (vb) thrb = b2 + BFM_WINDOW;
     }
     // (global address space: a generic pointer makes the append a flat_store, which the compiler orders behind every LDS-DMA in flight)
     GASM unsigned long long *lista = (GASM unsigned long long *)J.c_ent + (size_t)lst * BFM_CAPL * pitch + (q0 + col), *listb = lista + 32;   // uint2 (score bits, train) as one 64-bit word
@@ -648,75 +641,17 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
         for (int u = 0; u < BFM_UNIT; u++) {
             const int tl = tile0 + unit * BFM_UNIT + u;
             if (tl >= tile1) break;
-            const s8v *st = stage[b][u];
+            const h8v *st = stage[b][u];
             f16v acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
-#if VFSMS_BF_SKIP
-            // Round 6 (pass 1): hi.hi + |t|^2 first -- the five k-steps of the bounds pass -- and the eight correction steps (hi.lo, lo.hi)
-            // only for an accumulator in which some query could still reach its threshold: the correction moves a score by at most
-            // BFM_HI_ERR, so a tile whose hi.hi scores all lie above thr + BFM_HI_ERR + BFM_MARGIN lists nothing.  Thresholds sit a hair
-            // above a query's second-best score: most 32 x 32 tiles hold no such train.  (The order of the k-steps changes the rounding of
-            // a listed score by ~1e-6, far inside BFM_MARGIN; what the verifier computes from the lists is exact either way.)
-            if (PASS == 1) {
-                s8v ah[4];
 #pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    ah[s] = st[s * 64 + lane];
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh0[s], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh1[s], acc1, 0, 0, 0);
-                }
-                const s8v na = st[(NFR - 1) * 64 + lane];
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(na, bn0, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(na, bn1, acc1, 0, 0, 0);
-                float pa = fminf(fminf(acc0[0], acc0[1]), fminf(acc0[2], acc0[3])), pb = fminf(fminf(acc1[0], acc1[1]), fminf(acc1[2], acc1[3]));
-#pragma unroll
-                for (int i = 4; i < 16; i += 3) {
-                    pa = fminf(pa, fminf(acc0[i], fminf(acc0[i + 1], acc0[i + 2])));
-                    pb = fminf(pb, fminf(acc1[i], fminf(acc1[i + 1], acc1[i + 2])));
-                }
-                const bool need0 = __any(pa <= thra + (BFM_HI_ERR + BFM_MARGIN)), need1 = __any(pb <= thrb + (BFM_HI_ERR + BFM_MARGIN));
-                if (!need0 && !need1) continue;
-                if (need0) {
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        const s8v al = st[(4 + s) * 64 + lane];
-                        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl0[s], acc0, 0, 0, 0);
-                        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0[s], acc0, 0, 0, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; i++) acc0[i] = BFM_FAR;
-                }
-                if (need1) {
-#pragma unroll
-                    for (int s = 0; s < 4; s++) {
-                        const s8v al = st[(4 + s) * 64 + lane];
-                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl1[s], acc1, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh1[s], acc1, 0, 0, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; i++) acc1[i] = BFM_FAR;
-                }
-            } else
-#endif
-            {
-#pragma unroll
-            for (int s = 0; s < 4; s++) {            // fragment s = hi, 4 + s = lo of the lane's dims 8s .. 8s + 7
-                const s8v ah = st[s * 64 + lane];
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh0[s], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh1[s], acc1, 0, 0, 0);
-                if (PASS == 1) {
-                    const s8v al = st[(4 + s) * 64 + lane];
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl0[s], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl1[s], acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh0[s], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh1[s], acc1, 0, 0, 0);
-                }
+            for (int s = 0; s < 4; s++) {            // fragment s = the lane's dims 8s .. 8s + 7
+                const h8v at = st[s * 64 + lane];
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at, bh0[s], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at, bh1[s], acc1, 0, 0, 0);
             }
-            const s8v na = st[(NFR - 1) * 64 + lane];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(na, bn0, acc0, 0, 0, 0);      // + |t|^2 (hi + lo in both passes)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(na, bn1, acc1, 0, 0, 0);
-            }
+            const h8v na = st[(NFR - 1) * 64 + lane];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(na, bn0, acc0, 0, 0, 0);       // + |t|^2 (hi + lo)
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(na, bn1, acc1, 0, 0, 0);
             if (tl * 32 + 31 >= nt) {                // train rows beyond nt never qualify
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
@@ -789,8 +724,9 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
 
 // One THREAD per query (no cross-lane traffic; list reads are coalesced across the queries of a wave).  Sweep 1 takes
 // the second smallest score S2 over the query's lists (the lists hold the true 2-NN, so S2 bounds their scores up to the
-// MFMA rounding); sweep 2 parks the entries within BFM_MARGIN of S2 -- typically two or three -- in a per-thread LDS
-// column; the exact distances are then evaluated hit by hit, all lanes in step, with the arithmetic of k_bf_l2_d64 and
+// MFMA rounding); sweep 2 parks the entries within `window` of S2 in a per-thread LDS column -- BFM_MARGIN for the f32 filter, whose
+// scores are within ~1e-5 of the exact ones, BFM_WINDOW = 2 BFM_F16_ERR + BFM_MARGIN for the fp16 filter, whose listed scores carry
+// their own error (superset argument at k_bf_mfma16_d64) --; the exact distances are then evaluated hit by hit, all lanes in step, with the arithmetic of k_bf_l2_d64 and
 // the semantics of knn_update over ascending train indices (best = lowest index among the smallest sqrt-domain
 // distances; second = next smallest value), which is order-independent in this form.
 #define BFV_HITS 12
@@ -817,7 +753,7 @@ __device__ __forceinline__ void bfv_exact(const float *__restrict__ Qr, const fl
     else B2 = fminf(B2, d);
 }
 
-__global__ __launch_bounds__(256) void k_bf_verify_d64(const MatchDev *jobs, int cns)
+__global__ __launch_bounds__(256) void k_bf_verify_d64(const MatchDev *jobs, int cns, float window)
 {
     const MatchDev &J = jobs[blockIdx.y];
     const int nq = __builtin_amdgcn_readfirstlane(*J.nq_ptr), nt = __builtin_amdgcn_readfirstlane(*J.nt_ptr);
@@ -832,6 +768,7 @@ __global__ __launch_bounds__(256) void k_bf_verify_d64(const MatchDev *jobs, int
         for (int L = 0; L < nl; L++) {
             const int c = J.c_cnt[(size_t)L * pitch + q];
             overflow = overflow || c > BFM_CAPL;
+            BFV_STAT(2, min(c, BFM_CAPL));
             const uint2 *e = J.c_ent + (size_t)L * BFM_CAPL * pitch + q;
             for (int k = 0; k < min(c, BFM_CAPL); k++) {
                 const float v = __uint_as_float(e[k * pitch].x);
@@ -839,7 +776,7 @@ __global__ __launch_bounds__(256) void k_bf_verify_d64(const MatchDev *jobs, int
                 s1 = fminf(s1, v);
             }
         }
-    const float cut = s2 + BFM_MARGIN;
+    const float cut = s2 + window;
     if (live) { BFV_STAT(0, 1); BFV_STAT(1, overflow ? 1 : 0); }
     const float *Qr = J.q + (size_t)min(q, nq - 1) * 64;
     float B1 = INFINITY, B2 = INFINITY; int I1 = -1;
@@ -1185,7 +1122,7 @@ static bool bf_f32_filter()
 }
 
 // MFMA-filtered exact 2-NN for 64-d descriptors of norm <= 1 (jobs carved with nsplit == 1 plus match_filter_carve).
-// Default: split-bf16 filter on the bf16 matrix pipe; VFSMS_BF_F32FILTER=1 keeps round 1's f32-MFMA filter.
+// Default: fp16 filter on the 16-bit matrix pipe; VFSMS_BF_F32FILTER=1 keeps round 1's f32-MFMA filter.
 int launch_bf_l2_filtered(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int capt, int cns)
 {
     if (njobs <= 0 || capq <= 0) return VFSMS_OK;
@@ -1202,7 +1139,7 @@ int launch_bf_l2_filtered(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int
     }
     {
         ProfScope ps(ctx, "bf_verify");
-        hipLaunchKernelGGL(k_bf_verify_d64, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, cns);
+        hipLaunchKernelGGL(k_bf_verify_d64, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, cns, bf_f32_filter() ? BFM_MARGIN : BFM_WINDOW);
     }
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;

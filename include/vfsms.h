@@ -232,7 +232,7 @@ int vfsms_sift_pyramid(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int str
  * pairs: int32[cap][2] = (trainIdx, queryIdx) in query order.
  * Results are those of the reference's float arithmetic (4-wide accumulation of (a-b)^2, sqrt-domain compares, ties to the
  * lower train index) for every input.  64-d inputs whose rows all have norm <= 1 (SURF descriptors are L2-normalised; checked
- * on the device) are searched with the split-bf16 MFMA candidate filter + exact verification, anything else with the exhaustive
+ * on the device) are searched with the fp16 MFMA candidate filter + exact verification, anything else with the exhaustive
  * kernel; VFSMS_BF_EXACT=1 in the environment forces the exhaustive kernel.                                                  */
 int vfsms_bf_l2_knn2_ratio(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim,
                            double ratio, int32_t *pairs, int cap, int *m_out);
