@@ -166,6 +166,11 @@ _SIGNATURES = {
     "vfsms_canvas_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "vfsms_canvas_download_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_tile_upload_ch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_shading_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_shading_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "vfsms_shading_free": (C.c_int, [C.c_void_p, C.c_int64]),
 }
 
 _lib = None
@@ -298,19 +303,19 @@ class Engine:
         img = _u8_2d(img)
         h = C.c_int64()
         self._check(self.lib.vfsms_tile_upload(self.ctx, _ptr(img), img.shape[0], img.shape[1], img.strides[0], C.byref(h)))
-        return h.value
+        return self._note_tile(h.value, img.shape)
 
     def tile_reserve(self, h, w):
         """handle of a gray tile whose pixels a decoder thread delivers later (tile_fill); batch calls wait for exactly the tiles they name"""
         hd = C.c_int64()
         self._check(self.lib.vfsms_tile_reserve(self.ctx, int(h), int(w), C.byref(hd)))
-        return hd.value
+        return self._note_tile(hd.value, (int(h), int(w)))
 
     def tile_reserve_color(self, h, w, ch=3):
         """tile_reserve for an interleaved tile of `ch` channels (the mosaic's colour tiles)"""
         hd = C.c_int64()
         self._check(self.lib.vfsms_tile_reserve_ch(self.ctx, int(h), int(w), int(ch), C.byref(hd)))
-        return hd.value
+        return self._note_tile(hd.value, (int(h), int(w), int(ch)))
 
     def tile_fill(self, handle, img):
         """deliver (img: u8 (h, w) or (h, w, ch) array, C-contiguous rows) or give up on (img is None) a reserved tile; safe from any thread"""
@@ -350,7 +355,7 @@ class Engine:
         h = C.c_int64()
         self._check(self.lib.vfsms_tile_upload_async(self.ctx, _ptr(img), img.shape[0], img.shape[1], img.strides[0], C.byref(h)))
         self.__dict__.setdefault("_inflight", []).append(img)
-        return h.value
+        return self._note_tile(h.value, img.shape)
 
     def tile_upload_color(self, img, asynchronous=False):
         """Interleaved colour tile (h, w, ch) u8 for the mosaic canvas (vfsms_tile_upload_ch); asynchronous like tile_upload_async."""
@@ -362,7 +367,7 @@ class Engine:
                                                   1 if asynchronous else 0, C.byref(h)))
         if asynchronous:
             self.__dict__.setdefault("_inflight", []).append(img)
-        return h.value
+        return self._note_tile(h.value, img.shape)
 
     def pinned_empty(self, shape, dtype=np.uint8):
         """numpy array over pinned host memory (vfsms_host_alloc); freed when the engine closes."""
@@ -376,10 +381,16 @@ class Engine:
     def tile_wrap(self, device_ptr, h, w, stride):
         hd = C.c_int64()
         self._check(self.lib.vfsms_tile_wrap(self.ctx, C.c_void_p(int(device_ptr)), int(h), int(w), int(stride), C.byref(hd)))
-        return hd.value
+        return self._note_tile(hd.value, (int(h), int(w)))
 
     def tile_free(self, handle):
         self._check(self.lib.vfsms_tile_free(self.ctx, C.c_int64(handle)))
+        self.__dict__.get("_shapes", {}).pop(("tile", handle), None)
+
+    def _note_tile(self, handle, shape):
+        """the shape behind a tile handle: shading_download sizes its arrays by it (the C ABI reports no shapes)"""
+        self.__dict__.setdefault("_shapes", {})[("tile", handle)] = tuple(int(v) for v in shape)
+        return handle
 
     # -- operators -------------------------------------------------------------------------------------------
     def integral(self, img):
@@ -858,6 +869,50 @@ class Engine:
         if blend not in self.SEAM_BLENDS:
             raise ValueError("seamLineBlend must be 'none' or 'multiBandBlending'")
         self._check(self.lib.vfsms_canvas_set_seam_blend(self.ctx, C.c_int64(handle), self.SEAM_BLENDS[blend]))
+
+    # -- shading correction (tests/shading_ref.py is the specification) -----------------------------------------------------
+    def shading_estimate(self, handles, percentile=50, radius=32):
+        """A shading field from resident tiles of one shape (vfsms_shading_estimate): the `percentile` order statistic over the stack,
+        smoothed by two box passes of `radius`, as a Q12 gain -> field handle (shading_apply, shading_download, shading_free)."""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        f = C.c_int64()
+        self._check(self.lib.vfsms_shading_estimate(self.ctx, len(th), _ptr(th), int(percentile), int(radius), C.byref(f)))
+        shapes = self.__dict__.setdefault("_shapes", {})
+        shapes[("field", f.value)] = shapes.get(("tile", int(th[0])))
+        return f.value
+
+    def shading_from_gain(self, gain):
+        """A field from a gain measured elsewhere (a blank-slide image): uint16 Q12 of shape (h, w) or (h, w, ch)."""
+        gain = np.asarray(gain)
+        if gain.dtype != np.uint16 or gain.ndim not in (2, 3):
+            raise ValueError("shading_from_gain takes a uint16 (h, w) or (h, w, ch) array, got %s %s" % (gain.dtype, gain.shape))
+        gain = np.ascontiguousarray(gain)
+        f = C.c_int64()
+        self._check(self.lib.vfsms_shading_from_gain(self.ctx, _ptr(gain), gain.shape[0], gain.shape[1], gain.shape[2] if gain.ndim == 3 else 1,
+                                                     C.byref(f)))
+        self.__dict__.setdefault("_shapes", {})[("field", f.value)] = gain.shape
+        return f.value
+
+    def shading_download(self, field, with_profile=False):
+        """-> gain (uint16 Q12), or with_profile: (gain, smoothed Q8 field uint16, profile uint8), each of the tile shape; the last two are
+        zeros for a field from shading_from_gain."""
+        shape = self.__dict__.get("_shapes", {}).get(("field", field))
+        if shape is None:
+            raise ValueError("shading_download: not a field of this engine's shading_estimate / shading_from_gain")
+        gain = np.empty(shape, np.uint16)
+        q8 = np.empty(shape, np.uint16) if with_profile else None
+        prof = np.empty(shape, np.uint8) if with_profile else None
+        self._check(self.lib.vfsms_shading_download(self.ctx, C.c_int64(field), _ptr(gain), _ptr(q8), _ptr(prof)))
+        return (gain, q8, prof) if with_profile else gain
+
+    def shading_apply(self, field, handles):
+        """the tiles corrected in place by the field's gain (vfsms_shading_apply); owned tiles of the field's shape, each named once"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        self._check(self.lib.vfsms_shading_apply(self.ctx, C.c_int64(field), len(th), _ptr(th)))
+
+    def shading_free(self, field):
+        self._check(self.lib.vfsms_shading_free(self.ctx, C.c_int64(field)))
+        self.__dict__.get("_shapes", {}).pop(("field", field), None)
 
     def canvas_download(self, handle, rows, cols, ch):
         out = np.empty((rows, cols, ch) if ch > 1 else (rows, cols), np.uint8)

@@ -255,6 +255,8 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
     if (ctx->seam_scratch) hipFree(ctx->seam_scratch);
+    if (ctx->shade_scratch) hipFree(ctx->shade_scratch);
+    for (auto &kv : ctx->shade_fields) hipFree(kv.second.gain);
     if (ctx->sift_scratch) hipFree(ctx->sift_scratch);
     if (ctx->sift_kp) hipFree(ctx->sift_kp);
     sift_pool_free(ctx);
@@ -1978,6 +1980,118 @@ extern "C" int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int ro
         vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
         return VFSMS_ERR_BAD_ARG;
     }
+    return VFSMS_OK;
+}
+
+// ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------
+// the tiles of a shading call: known, handed over (tile_ready) and of one shape
+static int shade_tiles(vfsms_ctx *ctx, const char *what, int n, const int64_t *tiles, std::vector<TileRec *> &T)
+{
+    if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles) { vfsms_set_error("%s: 1..%d tiles", what, VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
+    T.resize(n);
+    for (int i = 0; i < n; i++) {
+        auto it = ctx->tiles.find(tiles[i]);
+        if (it == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", what); return VFSMS_ERR_BAD_ARG; }
+        T[i] = &it->second;
+        if (T[i]->h != T[0]->h || T[i]->w != T[0]->w || T[i]->ch != T[0]->ch) {
+            vfsms_set_error("%s: tile %d is %d x %d x %d, tile 0 is %d x %d x %d", what, i, T[i]->h, T[i]->w, T[i]->ch, T[0]->h, T[0]->w, T[0]->ch);
+            return VFSMS_ERR_BAD_ARG;
+        }
+    }
+    for (int i = 0; i < n; i++) TRY(tile_ready(ctx, *T[i]));
+    return VFSMS_OK;
+}
+static int shade_field_new(vfsms_ctx *ctx, int h, int w, int ch, bool estimated, ShadeRec *F)
+{
+    const size_t P = (size_t)h * w * ch, Pa = (P + 127) & ~(size_t)127;      // the three planes stay 256-byte aligned
+    F->h = h; F->w = w; F->ch = ch; F->estimated = estimated; F->q8 = nullptr; F->prof = nullptr;
+    HIP_TRY(hipMalloc((void **)&F->gain, estimated ? Pa * 5 : Pa * 2));
+    if (estimated) { F->q8 = F->gain + Pa; F->prof = (uint8_t *)(F->q8 + Pa); }
+    return VFSMS_OK;
+}
+extern "C" int vfsms_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *tiles, int percentile, int radius, int64_t *field)
+{
+    CTX_ENTER(ctx);
+    if (!field || percentile < 0 || percentile > 100 || radius < 1 || radius > VFSMS_SHADE_MAX_RADIUS) {
+        vfsms_set_error("shading_estimate: percentile %d / radius %d (0..100; 1..%d)", percentile, radius, VFSMS_SHADE_MAX_RADIUS);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    std::vector<TileRec *> T;
+    TRY(shade_tiles(ctx, "shading_estimate", n, tiles, T));
+    std::vector<ShadeTileHost> H(n);
+    for (int i = 0; i < n; i++) { H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride; }
+    TRY(ctx_arena_reserve(ctx, sizeof(ShadeTileHost) * 2 * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    ShadeRec F;
+    TRY(shade_field_new(ctx, T[0]->h, T[0]->w, T[0]->ch, true, &F));
+    int rc = shade_estimate_device(ctx, H.data(), n, F.h, F.w, F.ch, percentile, radius, F.gain, F.q8, F.prof);
+    if (rc == VFSMS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { vfsms_set_error("shading_estimate: the kernels failed"); rc = VFSMS_ERR_HIP; }
+    if (rc != VFSMS_OK) { hipFree(F.gain); return rc; }
+    *field = ctx->next_handle++;
+    ctx->shade_fields[*field] = F;
+    return VFSMS_OK;
+}
+extern "C" int vfsms_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int h, int w, int ch, int64_t *field)
+{
+    CTX_ENTER(ctx);
+    if (!gain || !field || h <= 0 || w <= 0 || ch < 1 || ch > 4) { vfsms_set_error("shading_from_gain: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    ShadeRec F;
+    TRY(shade_field_new(ctx, h, w, ch, false, &F));
+    if (hipMemcpy(F.gain, gain, sizeof(uint16_t) * (size_t)h * w * ch, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(F.gain); vfsms_set_error("shading_from_gain: the upload failed"); return VFSMS_ERR_HIP;
+    }
+    *field = ctx->next_handle++;
+    ctx->shade_fields[*field] = F;
+    return VFSMS_OK;
+}
+extern "C" int vfsms_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *gain, uint16_t *smooth_q8, uint8_t *profile)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->shade_fields.find(field);
+    if (it == ctx->shade_fields.end()) { vfsms_set_error("shading_download: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    if (!gain) { vfsms_set_error("shading_download: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    const ShadeRec &F = it->second;
+    const size_t P = (size_t)F.h * F.w * F.ch;
+    HIP_TRY(hipMemcpyAsync(gain, F.gain, sizeof(uint16_t) * P, hipMemcpyDeviceToHost, ctx->stream));
+    if (smooth_q8) { if (F.estimated) HIP_TRY(hipMemcpyAsync(smooth_q8, F.q8, sizeof(uint16_t) * P, hipMemcpyDeviceToHost, ctx->stream)); else memset(smooth_q8, 0, sizeof(uint16_t) * P); }
+    if (profile) { if (F.estimated) HIP_TRY(hipMemcpyAsync(profile, F.prof, P, hipMemcpyDeviceToHost, ctx->stream)); else memset(profile, 0, P); }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *tiles)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->shade_fields.find(field);
+    if (it == ctx->shade_fields.end()) { vfsms_set_error("shading_apply: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    const ShadeRec &F = it->second;
+    std::vector<TileRec *> T;
+    TRY(shade_tiles(ctx, "shading_apply", n, tiles, T));
+    if (T[0]->h != F.h || T[0]->w != F.w || T[0]->ch != F.ch) {
+        vfsms_set_error("shading_apply: the tiles are %d x %d x %d, the field is %d x %d x %d", T[0]->h, T[0]->w, T[0]->ch, F.h, F.w, F.ch);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    std::vector<int64_t> seen(tiles, tiles + n);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("shading_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
+    std::vector<ShadeTileHost> H(n);
+    for (int i = 0; i < n; i++) {
+        if (!T[i]->owned) { vfsms_set_error("shading_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
+        H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride;
+    }
+    TRY(ctx_arena_reserve(ctx, sizeof(ShadeTileHost) * 2 * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    TRY(shade_apply_device(ctx, H.data(), n, F.h, F.w, F.ch, F.gain));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // the tile table went through the pinned staging buffer: synchronous like every call that uses it
+    return VFSMS_OK;
+}
+extern "C" int vfsms_shading_free(vfsms_ctx *ctx, int64_t field)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->shade_fields.find(field);
+    if (it == ctx->shade_fields.end()) { vfsms_set_error("shading_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipFree(it->second.gain));
+    ctx->shade_fields.erase(it);
     return VFSMS_OK;
 }
 

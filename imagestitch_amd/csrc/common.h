@@ -181,6 +181,7 @@ struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; 
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct ProfRec { int id; hipEvent_t a, b; };
+struct ShadeRec { int h, w, ch; uint16_t *gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
 struct SiftChunk { char *p; size_t bytes, off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
 
 struct vfsms_ctx {
@@ -213,6 +214,8 @@ struct vfsms_ctx {
     std::unordered_map<int64_t, CanvasRec> canvases;
     void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;
     void *seam_scratch = nullptr; size_t seam_scratch_bytes = 0;   // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
+    void *shade_scratch = nullptr; size_t shade_scratch_bytes = 0; // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
+    std::unordered_map<int64_t, ShadeRec> shade_fields;
     void *sift_scratch = nullptr; size_t sift_scratch_bytes = 0;   // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
@@ -315,6 +318,13 @@ int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h
                      int dx, int dy, int hostkind, const int *mode, int wmax, int blend, int levels);
 int seam_fuse_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy, const int *mode,
                   int blend, int levels, uint8_t *d_out, int32_t *d_seam);
+// shading_kernels.hip: Method.shadingCorrection.  Tiles as (pointer, row stride in bytes); h rows of w * ch bytes
+#define VFSMS_SHADE_MAX_TILES 4096
+#define VFSMS_SHADE_MAX_RADIUS 127
+struct ShadeTileHost { uint8_t *ptr; int stride; };
+int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, int percentile, int radius,
+                          uint16_t *gain, uint16_t *q8, uint8_t *prof);
+int shade_apply_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, const uint16_t *gain);
 
 // sift_kernels.hip
 #define VFSMS_SIFT_MAX_LAYERS 8

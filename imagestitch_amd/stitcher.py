@@ -817,6 +817,8 @@ class Stitcher(Utility.Method):
                         resident[(i, fileList[i])] = (hnd, im.shape)
                     handles = [resident[(i, fileList[i])][0] for i in range(n)]
                     use_res = True
+            if self.shadingCorrection != "none":
+                self._correctShading(handles if use_res else None, shapes)
             offsetList, rangeX, rangeY, resultRow, resultCol = self._layout(shapes, originOffsetList)
             self.printAndWrite("  The rectified offsetList is " + str(offsetList))
             if not device_fuse and simple is None:
@@ -885,6 +887,33 @@ class Stitcher(Utility.Method):
                 eng.sync_uploads()                           # the host tiles of asynchronous uploads may be released now
             for h, _shape in resident.values():
                 eng.tile_free(h)
+
+    def _correctShading(self, handles, shapes):
+        """Method.shadingCorrection on the mosaic's resident tiles, in place (tests/shading_ref.py): a field estimated over exactly these
+        tiles, or Method.shadingGain uploaded, applied and freed.  Registration is over by now, and getStitchByOffset frees these handles
+        itself, so nothing else sees the corrected pixels."""
+        eng = self.engine
+        if self.shadingCorrection != "estimate":
+            raise ValueError("shadingCorrection must be 'none' or 'estimate'")
+        if not hasattr(eng, "shading_estimate") or handles is None:
+            raise NotImplementedError("shadingCorrection needs an engine with shading_estimate and device-resident tiles")
+        if len({tuple(s_) for s_ in shapes}) != 1:
+            raise ValueError("shadingCorrection needs tiles of one shape, got %s" % sorted({tuple(s_) for s_ in shapes}))
+        tiles = list(dict.fromkeys(handles))                   # (a file listed twice is one resident tile: corrected once)
+        if self.shadingGain is not None:
+            gain = np.asarray(self.shadingGain)
+            if gain.dtype != np.uint16 or gain.shape != tuple(shapes[0]):
+                raise ValueError("shadingGain must be a uint16 Q12 array of the tile shape %s, got %s %s" % (tuple(shapes[0]), gain.dtype, gain.shape))
+            field = eng.shading_from_gain(gain)
+        elif len(tiles) < int(self.shadingMinTiles):
+            self.printAndWrite("  shading correction skipped: %d tiles, shadingMinTiles is %d" % (len(tiles), int(self.shadingMinTiles)))
+            return
+        else:
+            field = eng.shading_estimate(tiles, int(self.shadingPercentile), int(self.shadingRadius))
+        try:
+            eng.shading_apply(field, tiles)
+        finally:
+            eng.shading_free(field)
 
     def _ingestForMosaic(self, files, color):
         """The mosaic's tiles from their files into reserved device tiles through a pool of decoder threads (one decode per file, the

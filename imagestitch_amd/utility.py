@@ -140,6 +140,18 @@ class Method():
     # (the seam's label plane as the mask of the pyramid blend with multiBandLevels levels)
     seamLineBlend = "none"
 
+    # ---- flat-field shading correction before the mosaic is built (no reference counterpart; tests/shading_ref.py): "estimate" takes the
+    # shadingPercentile order statistic of every sample over the mosaic's own tiles, smooths it with two box passes of shadingRadius and
+    # divides the tiles by it (registration never sees corrected pixels).  shadingRadius = 32 and the two passes rest on nothing measured
+    # at production size: they come from a 256 x 256 synthetic stack (tests/test_shading_host.py).  shadingMinTiles is a condition, not a
+    # measurement: a median over a handful of tiles is their content, not the optics, so fewer tiles are left uncorrected.  shadingGain: a
+    # uint16 Q12 array of the tile shape measured elsewhere (a blank-slide image), used instead of the estimate whatever the tile count
+    shadingCorrection = "none"  # "none" or "estimate"
+    shadingPercentile = 50
+    shadingRadius = 32
+    shadingMinTiles = 8
+    shadingGain = None
+
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None
 

@@ -456,6 +456,25 @@ int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out);
  * incremental writer (the reference holds the whole int64 canvas and the u8 copy in host memory, Stitcher.py:434-436, 485-486) */
 int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, uint8_t *out);
 
+/* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
+ * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
+/* A shading field from n (1..4096) resident tiles of one shape and channel count (any row stride): per sample the k-th smallest byte
+ * over the tiles, k = (n - 1) * percentile / 100 (percentile 0..100), as Q8 smoothed by two rounded (2 radius + 1)^2 box passes with
+ * replicated borders (radius 1..127), turned into a Q12 gain min(65535, (mean * 4096 + Q / 2) / Q) per channel (4096 where Q == 0)
+ * (tests/shading_ref.py).  Waits for reserved / pending tiles like every batch call; the tiles are only read.                  */
+int vfsms_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *tiles, int percentile, int radius, int64_t *field);
+/* a field measured elsewhere (a blank-slide image): gain is uint16 Q12 [h][w][ch], used as it is (tests/shading_ref.py: apply)  */
+int vfsms_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int h, int w, int ch, int64_t *field);
+/* gain: uint16 [h][w][ch]; smooth_q8 (may be NULL): the smoothed Q8 field, uint16; profile (may be NULL): the order statistic, u8;
+ * both are zeros for a field from vfsms_shading_from_gain (tests/shading_ref.py: estimate returns the three planes)             */
+int vfsms_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *gain, uint16_t *smooth_q8, uint8_t *profile);
+/* out = min(255, (p * gain + 2048) >> 12) in place on n resident tiles of the field's shape (tests/shading_ref.py: apply).  Refused:
+ * a tile from vfsms_tile_wrap (the library does not own that memory and must not rewrite it), a tile named twice in one call (it
+ * would be corrected twice), a shape other than the field's.  Waits for reserved / pending tiles.                                */
+int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *tiles);
+/* releases a field of vfsms_shading_estimate / vfsms_shading_from_gain (tests/shading_ref.py has no state to free)              */
+int vfsms_shading_free(vfsms_ctx *ctx, int64_t field);
+
 #ifdef __cplusplus
 }
 #endif
