@@ -250,7 +250,6 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
     for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); }
     if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); ctx->has_spare_canvas = false; }
-    for (auto &kv : ctx->feats) if (!kv.second.block) { if (kv.second.kps_xy) hipFree(kv.second.kps_xy); if (kv.second.desc) hipFree(kv.second.desc); }
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
@@ -705,8 +704,6 @@ static int upload_array(vfsms_ctx *ctx, const T *src, size_t n, T **d)
 
 // small host->device uploads of launch records through one pinned staging buffer (a pageable hipMemcpyAsync is staged by
 // the runtime and costs a synchronisation each); safe to reuse because every entry point is synchronous at return
-int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);
-static int upload_pinned(vfsms_ctx *ctx, const void *src, size_t bytes, void **d) { return ctx_upload_small(ctx, src, bytes, d); }
 int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d)
 {
     *d = ctx_arena_alloc(ctx, bytes ? bytes : 1);
@@ -748,6 +745,82 @@ extern "C" int vfsms_integral_u8_i32(vfsms_ctx *ctx, const uint8_t *img, int h, 
     return VFSMS_OK;
 }
 
+// ---- one SURF run: n sources detected (and described) in fused launches ------------------------------------------------------------
+// Every entry point that runs SURF goes through these phases, in this order: surf_run_bytes into the caller's ONE ctx_arena_reserve (it
+// resets the arena), surf_run_carve, surf_run_prepare, surf_run_launch over one or more ranges of the sources, surf_run_readback, the caller's own
+// hipStreamSynchronize (it may enqueue copies of its own first), surf_run_check.
+struct SurfSrc { const uint8_t *p; int stride, h, w, cap; };      // pixels on the device, keypoint capacity of the source
+struct SurfEnh { int mode; double clip_limit; int tile_grid; };   // equalizeHist / CLAHE before detection (mode 0: none)
+struct SurfRun {
+    std::vector<RoiDev> R; RoiDev *dR = nullptr;                  // host and device copies of the ROI records
+    std::vector<EnhJob> E;
+    int *cblock = nullptr;                                        // 16 counters per source, one contiguous block: one memset, one copy back
+    std::vector<int> counters;
+};
+static size_t surf_run_bytes(vfsms_ctx *ctx, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
+{
+    size_t need = 0;
+    for (int i = 0; i < n; i++) {
+        need += surf_roi_bytes(S[i].h, S[i].w, S[i].cap, ctx->n_layers, p->n_octaves, p->extended ? 128 : 64);
+        if (enh.mode) need += enhance_scratch_bytes(S[i].h, S[i].w, enh.mode, enh.tile_grid) + sizeof(EnhJob) + 512;
+    }
+    return need + (sizeof(RoiDev) + 64) * (size_t)n + 1024;       // the records, the counters, their alignment
+}
+static int surf_run_carve(vfsms_ctx *ctx, SurfRun *run, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
+{
+    run->R.resize(n); run->E.resize(enh.mode ? n : 0);
+    run->cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * n);
+    if (!run->cblock) { vfsms_set_error("arena exhausted (SURF counters)"); return VFSMS_ERR_CAPACITY; }
+    for (int i = 0; i < n; i++) {
+        const uint8_t *px = S[i].p; int stride = S[i].stride;
+        if (enh.mode) {            // Stitcher.py:327-334: the ROI strips are equalised / CLAHE'd before detectAndDescribe
+            TRY(enhance_carve(ctx, &run->E[i], px, stride, S[i].h, S[i].w, enh.mode, enh.tile_grid));
+            px = run->E[i].dst; stride = S[i].w;
+        }
+        TRY(surf_roi_carve(ctx, &run->R[i], px, stride, S[i].h, S[i].w, S[i].cap, p));
+        run->R[i].counters = run->cblock + 16 * i;
+    }
+    return ctx_upload_small(ctx, run->R.data(), sizeof(RoiDev) * n, (void **)&run->dR);
+}
+// the enhancement and the zeroed counters, enqueued behind every record upload of the call (a fused batch uploads its match records
+// in between: copies next to copies, then the device work)
+static int surf_run_prepare(vfsms_ctx *ctx, SurfRun *run, const SurfEnh &enh)
+{
+    const int n = (int)run->R.size();
+    if (enh.mode) {
+        EnhJob *dE;
+        TRY(ctx_upload_small(ctx, run->E.data(), sizeof(EnhJob) * n, (void **)&dE));
+        TRY(launch_enhance(ctx, dE, run->E.data(), n, enh.mode, enh.clip_limit, enh.tile_grid));
+    }
+    HIP_TRY(hipMemsetAsync(run->cblock, 0, sizeof(int) * 16 * n, ctx->stream));
+    return VFSMS_OK;
+}
+static int surf_run_launch(vfsms_ctx *ctx, const SurfRun &run, int first, int count, bool describe, const vfsms_surf_params *p)
+{
+    TRY(launch_surf_detect(ctx, run.dR + first, run.R.data() + first, count, p));
+    if (describe) TRY(launch_surf_describe(ctx, run.dR + first, run.R.data() + first, count, p));
+    return VFSMS_OK;
+}
+static int surf_run_readback(vfsms_ctx *ctx, SurfRun *run)
+{
+    run->counters.resize(16 * run->R.size());
+    HIP_TRY(hipMemcpyAsync(run->counters.data(), run->cblock, sizeof(int) * run->counters.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return VFSMS_OK;
+}
+// after the caller's synchronisation; source i is reported as `unit` index0 + i of `total`
+static int surf_run_check(const SurfRun &run, const char *who, const char *unit, int index0, int total)
+{
+    for (size_t i = 0; i < run.R.size(); i++)
+        if (run.counters[16 * i + 2] || run.counters[16 * i] > run.R[i].cap) {
+            vfsms_set_error("%s: %s %d of %d (%d x %d) exceeded %d keypoint candidates (raise with vfsms_ctx_set_keypoint_capacity)",
+                            who, unit, index0 + (int)i, total, run.R[i].h, run.R[i].w, run.R[i].cap);
+            return VFSMS_ERR_CAPACITY;
+        }
+    return VFSMS_OK;
+}
+// kept keypoints of described source i
+static int surf_run_count(const SurfRun &run, int i) { return run.counters[16 * (size_t)i + 1]; }
+
 // ---- SURF (host buffers) ------------------------------------------------------------------------------------------
 static int surf_host(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride, const vfsms_surf_params *params,
                      float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out, bool describe)
@@ -756,27 +829,22 @@ static int surf_host(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int strid
     if (!img || !params || !n_out || h <= 0 || w <= 0 || stride < w || cap < 0) { vfsms_set_error("surf: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     TRY(ctx_prepare_surf(ctx, params));
     const int dim = params->extended ? 128 : 64;
-    const int dcap = kp_capacity(ctx, h, w);
-    TRY(ctx_arena_reserve(ctx, (size_t)h * w + surf_roi_bytes(h, w, dcap, ctx->n_layers, params->n_octaves, dim) + 65536));
+    const SurfEnh plain{0, 0.0, 0};
+    SurfSrc src{nullptr, w, h, w, kp_capacity(ctx, h, w)};
+    TRY(ctx_arena_reserve(ctx, (size_t)h * w + surf_run_bytes(ctx, &src, 1, params, plain) + 65536));
+    ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
     uint8_t *d_img;
     TRY(upload_image(ctx, img, h, w, stride, &d_img));
-    RoiDev R;
-    TRY(surf_roi_carve(ctx, &R, d_img, w, h, w, dcap, params));
-    RoiDev *d_R;
-    TRY(upload_array(ctx, &R, 1, &d_R));
-    HIP_TRY(hipMemsetAsync(R.counters, 0, 16 * sizeof(int), ctx->stream));
-    TRY(launch_surf_detect(ctx, d_R, &R, 1, params));
-    int counters[16];
-    if (describe) {
-        TRY(launch_surf_describe(ctx, d_R, &R, 1, params));
-    }
-    HIP_TRY(hipMemcpyAsync(counters, R.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+    src.p = d_img;
+    SurfRun run;
+    TRY(surf_run_carve(ctx, &run, &src, 1, params, plain));
+    TRY(surf_run_prepare(ctx, &run, plain));
+    TRY(surf_run_launch(ctx, run, 0, 1, describe, params));
+    TRY(surf_run_readback(ctx, &run));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (counters[2] || counters[0] > dcap) {
-        vfsms_set_error("surf: more than %d keypoint candidates (raise with vfsms_ctx_set_keypoint_capacity)", dcap);
-        return VFSMS_ERR_CAPACITY;
-    }
-    const int n = describe ? counters[1] : counters[0];
+    TRY(surf_run_check(run, "surf", "image", 0, 1));
+    const RoiDev &R = run.R[0];
+    const int n = describe ? surf_run_count(run, 0) : run.counters[0];      // undescribed: the candidates
     *n_out = n;
     if (n > cap) { vfsms_set_error("surf: %d keypoints exceed the caller's capacity %d", n, cap); return VFSMS_ERR_CAPACITY; }
     if (n > 0) {
@@ -853,7 +921,7 @@ static int bf_l2_host(vfsms_ctx *ctx, const float *q, int nq, const float *t, in
     TRY(upload_array(ctx, t, (size_t)nt * dim, &dt));
     int cnt[2] = {nq, nt}; int *dcnt;
     ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
-    TRY(upload_pinned(ctx, cnt, sizeof(cnt), (void **)&dcnt));   // copied into pinned staging now: `cnt` may leave scope before the stream runs
+    TRY(ctx_upload_small(ctx, cnt, sizeof(cnt), (void **)&dcnt));   // copied into pinned staging now: `cnt` may leave scope before the stream runs
     // descriptors of norm <= 1 (SURF's are L2-normalised) take the MFMA-filtered search; anything else the exhaustive kernel
     bool filtered = false;
     if (try_filter) {
@@ -1101,33 +1169,114 @@ static int build_strip_table(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, const i
     return VFSMS_OK;
 }
 
+// ---- jobs of one ROI shape next to each other ------------------------------------------------------------------------------------
+// The kernels whose grid follows the image size are launched per run of equal shapes (surf_kernels.hip: shape_runs), and a batched
+// transform takes one shape: every batch puts its jobs in the stable (h, w) order.  Slot s holds job ord[s]; results go to the job's row.
+static std::vector<int> shape_order(const vfsms_roi_pair *jobs, int n)
+{
+    std::vector<int> ord(n);
+    for (int k = 0; k < n; k++) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) {
+        return jobs[x].h != jobs[y].h ? jobs[x].h < jobs[y].h : jobs[x].w < jobs[y].w; });
+    return ord;
+}
+// the run of equal shapes that starts at position g0 of n ends before the position returned; shape_at(k) -> (h, w) of position k
+template <typename ShapeAt>
+static int shape_run_end(int g0, int n, ShapeAt shape_at)
+{
+    int g1 = g0 + 1;
+    while (g1 < n && shape_at(g1) == shape_at(g0)) g1++;
+    return g1;
+}
+
+// ---- one 2-NN search + vote run: n (query set, train set) jobs in fused launches ------------------------------------------------------
+// The phases mirror a SURF run's: match_run_bytes into the caller's ONE ctx_arena_reserve, match_run_carve (wires and uploads the
+// records), match_run_launch over one or more ranges of the jobs, match_run_readback in front of the caller's synchronisation.
+struct MatchPlan { bool filtered; int ns, cns; };    // filtered: MFMA candidate filter (cns train splits) + exact verification; else ns splits
+struct MatchJob {
+    const float *q, *t, *kq, *kt;                    // descriptors and keypoint positions of the query and the train set
+    const int *nq_ptr, *nt_ptr;                      // their counts, on the device
+    int capq, capt;                                  // what the job's arrays are sized for
+    int row;                                         // the job's row of the result block
+    const int8_t *q8, *t8; const int *qn2, *tn2;     // optional: int8 rows and their norms (k_bf_i8_d128)
+    const StripTable::Strip *sa, *sb;                // optional: the raw pixels of the two strips, for the verifier behind the vote
+};
+struct MatchRun { MatchPlan P; int dim; std::vector<MatchDev> M; MatchDev *dM = nullptr; int32_t *rblock = nullptr; };
+enum MatchSearch { SEARCH_FLOAT, SEARCH_I8_D128 };   // k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows
+// 64-d descriptors leave the descriptor kernel with norm <= 1: their 2-NN search runs as an MFMA candidate filter plus exact verification
+// (match_kernels.hip); other widths, or VFSMS_BF_EXACT=1, take the exhaustive VALU kernel.  The split counts follow the set sizes the
+// CALLER expects, (fq, ft) for the filter and (eq, et) for the exhaustive kernel: the true counts of feature sets, the typical occupancy
+// of the capacity in a fused batch.
+static MatchPlan match_plan_float(int dim, int njobs, int fq, int ft, int eq, int et)
+{
+    MatchPlan P;
+    P.filtered = dim == 64 && !bf_force_exact();
+    P.cns = pick_filter_nsplit(fq, njobs, ft);
+    P.ns = P.filtered ? 1 : pick_nsplit(eq, et, njobs, dim);
+    return P;
+}
+static size_t match_run_bytes(const MatchJob *J, int n, const MatchPlan &P)
+{
+    size_t need = 0;
+    for (int k = 0; k < n; k++)
+        need += match_bytes(J[k].capq, P.ns) + (P.filtered ? match_filter_bytes(J[k].capq, J[k].capt, P.cns) : 0);
+    return need + (sizeof(MatchDev) + 64 + sizeof(int32_t) * VFSMS_ATTEMPT_INTS) * (size_t)n + 1024;
+}
+static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
+{
+    run->P = P; run->dim = dim; run->M.resize(n);
+    run->rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);     // all rows in one block: one copy back
+    if (!run->rblock) { vfsms_set_error("arena exhausted (match results)"); return VFSMS_ERR_CAPACITY; }
+    for (int k = 0; k < n; k++) {
+        MatchDev &m = run->M[k];
+        memset(&m, 0, sizeof(m));
+        TRY(match_carve(ctx, &m, J[k].capq, dim, P.ns));
+        if (P.filtered) TRY(match_filter_carve(ctx, &m, J[k].capq, J[k].capt, P.cns));
+        m.result = run->rblock + VFSMS_ATTEMPT_INTS * J[k].row;
+        m.q = J[k].q; m.t = J[k].t; m.kq = J[k].kq; m.kt = J[k].kt; m.nq_ptr = J[k].nq_ptr; m.nt_ptr = J[k].nt_ptr;
+        m.q8 = J[k].q8; m.t8 = J[k].t8; m.qn2 = J[k].qn2; m.tn2 = J[k].tn2;
+        if (J[k].sa) match_set_strips(&m, *J[k].sa, *J[k].sb);
+    }
+    return ctx_upload_small(ctx, run->M.data(), sizeof(MatchDev) * n, (void **)&run->dM);
+}
+// search + ratio test + vote of jobs [first, first + count); maxq / maxt: the largest query / train set the launch has to cover
+static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search,
+                            double ratio, int offset_evaluate)
+{
+    const MatchDev *dM = run.dM + first;
+    if (search == SEARCH_I8_D128) { TRY(launch_bf_i8_d128(ctx, dM, count, maxq, run.P.ns)); }
+    else if (run.P.filtered) { TRY(launch_bf_l2_filtered(ctx, dM, count, maxq, maxt, run.P.cns)); }
+    else { TRY(launch_bf_l2(ctx, dM, count, maxq, run.P.ns, run.dim)); }
+    return launch_ratio_mode(ctx, dM, count, maxq, ratio, offset_evaluate);
+}
+static int match_run_readback(vfsms_ctx *ctx, const MatchRun &run, int32_t *rows)
+{
+    HIP_TRY(hipMemcpyAsync(rows, run.rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * run.M.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return VFSMS_OK;
+}
+
 extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out)
 {
     CTX_ENTER(ctx);
     if (n < 0 || (n && (!jobs || !out))) { vfsms_set_error("attempt_phase: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     if (n == 0) return VFSMS_OK;
     // attempts of one ROI size (all of them, in practice) run as ONE batched transform; other sizes follow group by group
-    std::vector<int> order(n);
-    for (int k = 0; k < n; k++) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-        return jobs[x].h != jobs[y].h ? jobs[x].h < jobs[y].h : jobs[x].w < jobs[y].w; });
+    const std::vector<int> order = shape_order(jobs, n);
+    auto shape_at = [&](int k) { return std::make_pair(jobs[order[k]].h, jobs[order[k]].w); };
     size_t need = 0;
-    for (int g0 = 0; g0 < n;) {
-        int g1 = g0;
-        while (g1 < n && jobs[order[g1]].h == jobs[order[g0]].h && jobs[order[g1]].w == jobs[order[g0]].w) g1++;
+    for (int g0 = 0, g1; g0 < n; g0 = g1) {
+        g1 = shape_run_end(g0, n, shape_at);
         size_t pb = 0;
         TRY(phase_bytes(ctx, jobs[order[g0]].h, jobs[order[g0]].w, g1 - g0, &pb));
         need = std::max(need, pb);
-        g0 = g1;
     }
     TRY(ctx_arena_reserve(ctx, need + sizeof(double) * 3 * n + 65536));
     ctx->pinned_off = 0;
     double *d_out = (double *)ctx_arena_alloc(ctx, sizeof(double) * 3 * n);   // in group order; un-permuted on the host
     const size_t mark = ctx->arena_off;
     std::vector<PhaseJobHost> pj(n);
-    for (int g0 = 0; g0 < n;) {
-        int g1 = g0;
-        while (g1 < n && jobs[order[g1]].h == jobs[order[g0]].h && jobs[order[g1]].w == jobs[order[g0]].w) g1++;
+    for (int g0 = 0, g1; g0 < n; g0 = g1) {
+        g1 = shape_run_end(g0, n, shape_at);
         for (int k = g0; k < g1; k++) {
             const uint8_t *pa, *pb; int sa, sb;
             TRY(resolve_job(ctx, jobs[order[k]], &pa, &sa, &pb, &sb));
@@ -1135,7 +1284,6 @@ extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *j
         }
         ctx->arena_off = mark;                               // stream order makes scratch reuse safe
         TRY(phase_correlate_batch_device(ctx, pj.data() + g0, g1 - g0, jobs[order[g0]].h, jobs[order[g0]].w, d_out + 3 * g0));
-        g0 = g1;
     }
     std::vector<double> tmp((size_t)3 * n);
     HIP_TRY(hipMemcpyAsync(tmp.data(), d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1177,16 +1325,9 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     TRY(ctx_prepare_surf(ctx, params));
     const int dim = params->extended ? 128 : 64;
     int maxcap = 0;
-    std::vector<int> caps(n);
-    for (int k = 0; k < n; k++) {
-        caps[k] = kp_capacity(ctx, jobs[k].h, jobs[k].w);
-        maxcap = std::max(maxcap, caps[k]);
-    }
-    // 64-d descriptors leave the descriptor kernel with norm <= 1: their 2-NN search runs as an MFMA candidate filter plus
-    // exact verification (match_kernels.hip); other widths, or VFSMS_BF_EXACT=1, take the exhaustive VALU kernel.
-    const bool filtered = dim == 64 && !bf_force_exact();
-    const int cns = pick_filter_nsplit(maxcap * 2 / 3, n, maxcap * 2 / 3);   // the registrar sizes the capacity at 1.5x the largest ROI seen
-    const int ns = filtered ? 1 : pick_nsplit(maxcap / 3, maxcap / 3, n, dim);   // typical occupancy of the capacity
+    for (int k = 0; k < n; k++) maxcap = std::max(maxcap, kp_capacity(ctx, jobs[k].h, jobs[k].w));
+    // (the registrar sizes the capacity at 1.5x the largest ROI seen: the filter is split for 2/3 of it, the exhaustive kernel for its typical occupancy)
+    const MatchPlan P = match_plan_float(dim, n, maxcap * 2 / 3, maxcap * 2 / 3, maxcap / 3, maxcap / 3);
     // Two pipes at once -- built, measured, OFF by default.  The 2-NN search lives on the matrix cores (k_bf_mfma16_d64: MFMA pipe 55-65 %
     // busy, VALU idle), detection on the VALU and the texture-address path.  With VFSMS_OVERLAP=1 a large batch is cut in two parts of
     // slots: part 0 (VFSMS_OVERLAP_PCT, default 70 %) is detected and described, then its search + ratio + vote run on the second stream
@@ -1199,68 +1340,36 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     // instead cannot happen at all -- k_describe holds 6 x 80 of a SIMD's 512 VGPRs, a k_bf_mfma16_d64<1> wave needs 168.
     static const bool overlap_on = getenv("VFSMS_OVERLAP") && atoi(getenv("VFSMS_OVERLAP")) != 0;
     static const int overlap_pct = getenv("VFSMS_OVERLAP_PCT") ? atoi(getenv("VFSMS_OVERLAP_PCT")) : 70;
-    const int n0 = (overlap_on && filtered && n >= 12) ? std::min(n - 2, std::max(2, n * overlap_pct / 100)) : n;
-    // ROIs of one shape next to each other (the column strips, then the strips of the turn candidates): the kernels whose grid follows the
-    // image size are launched per shape run (surf_kernels.hip: shape_runs).  Slot s of the batch holds job ord[s]; results go to the job's row.
-    std::vector<int> ord(n);
-    for (int k = 0; k < n; k++) ord[k] = k;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
-        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    const int n0 = (overlap_on && P.filtered && n >= 12) ? std::min(n - 2, std::max(2, n * overlap_pct / 100)) : n;
+    const std::vector<int> ord = shape_order(jobs, n);       // the column strips, then the strips of the turn candidates
     StripTable T;
     TRY(build_strip_table(ctx, jobs, ord.data(), n, n0, &T));
     const int u = (int)T.strips.size(), u0 = T.u0;
-    std::vector<int> scap(u);
-    size_t need = 0;
+    std::vector<SurfSrc> S(u);
     for (int i = 0; i < u; i++) {
-        const StripTable::Strip &S = T.strips[i];
-        scap[i] = kp_capacity(ctx, S.h, S.w);
-        need += surf_roi_bytes(S.h, S.w, scap[i], ctx->n_layers, params->n_octaves, dim);
-        if (enh_mode) need += enhance_scratch_bytes(S.h, S.w, enh_mode, tile_grid) + sizeof(EnhJob) + 256;
+        const StripTable::Strip &s = T.strips[i];
+        S[i] = SurfSrc{s.p, s.stride, s.h, s.w, kp_capacity(ctx, s.h, s.w)};
     }
-    for (int k = 0; k < n; k++) need += match_bytes(caps[k], ns) + (filtered ? match_filter_bytes(caps[k], caps[k], cns) : 0);
-    need += sizeof(RoiDev) * u + sizeof(MatchDev) * n + 64 * (u + n) + 65536;
-    TRY(ctx_arena_reserve(ctx, need));
-    ctx->pinned_off = 0;
-    std::vector<RoiDev> R(u);
-    std::vector<EnhJob> E(enh_mode ? u : 0);
-    std::vector<MatchDev> M(n);
-    // counters of all strips and results of all jobs live in two contiguous blocks: one memset, two D2H copies per batch
-    int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * u);
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-    for (int i = 0; i < u; i++) {
-        const StripTable::Strip &S = T.strips[i];
-        const uint8_t *p = S.p; int stride = S.stride;
-        if (enh_mode) {            // Stitcher.py:327-334: the ROI strips are equalised / CLAHE'd before detectAndDescribe
-            TRY(enhance_carve(ctx, &E[i], p, stride, S.h, S.w, enh_mode, tile_grid));
-            p = E[i].dst; stride = S.w;
-        }
-        TRY(surf_roi_carve(ctx, &R[i], p, stride, S.h, S.w, scap[i], params));
-        R[i].counters = cblock + 16 * i;
-    }
+    std::vector<MatchJob> J(n, MatchJob{});
     for (int s_ = 0; s_ < n; s_++) {
-        const int k = ord[s_];
-        const RoiDev &A = R[T.a[s_]], &B = R[T.b[s_]];
-        memset(&M[s_], 0, sizeof(MatchDev));
-        TRY(match_carve(ctx, &M[s_], caps[k], dim, ns));
-        if (filtered) TRY(match_filter_carve(ctx, &M[s_], caps[k], caps[k], cns));
-        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-        M[s_].q = A.desc; M[s_].t = B.desc;
-        M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
-        M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
-        match_set_strips(&M[s_], T.strips[T.a[s_]], T.strips[T.b[s_]]);      // the tile's pixels, not the enhanced copy
+        J[s_].capq = J[s_].capt = kp_capacity(ctx, jobs[ord[s_]].h, jobs[ord[s_]].w);
+        J[s_].row = ord[s_];
+        J[s_].sa = &T.strips[T.a[s_]]; J[s_].sb = &T.strips[T.b[s_]];       // the tile's pixels, not the enhanced copy
     }
-    RoiDev *dR; MatchDev *dM;
-    TRY(upload_pinned(ctx, R.data(), sizeof(RoiDev) * u, (void **)&dR));
-    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-    if (enh_mode) {
-        EnhJob *dE;
-        TRY(upload_pinned(ctx, E.data(), sizeof(EnhJob) * u, (void **)&dE));
-        TRY(launch_enhance(ctx, dE, E.data(), u, enh_mode, clip_limit, tile_grid));
+    const SurfEnh enh{enh_mode, clip_limit, tile_grid};
+    TRY(ctx_arena_reserve(ctx, surf_run_bytes(ctx, S.data(), u, params, enh) + match_run_bytes(J.data(), n, P) + 65536));
+    ctx->pinned_off = 0;
+    SurfRun surf; MatchRun match;
+    TRY(surf_run_carve(ctx, &surf, S.data(), u, params, enh));
+    for (int s_ = 0; s_ < n; s_++) {
+        const RoiDev &A = surf.R[T.a[s_]], &B = surf.R[T.b[s_]];
+        J[s_].q = A.desc; J[s_].t = B.desc; J[s_].kq = A.kps_xy; J[s_].kt = B.kps_xy;
+        J[s_].nq_ptr = A.counters + 1; J[s_].nt_ptr = B.counters + 1;
     }
-    HIP_TRY(hipMemsetAsync(cblock, 0, sizeof(int) * 16 * u, ctx->stream));
+    TRY(match_run_carve(ctx, &match, J.data(), n, dim, P));
+    TRY(surf_run_prepare(ctx, &surf, enh));
     if (n0 < n) TRY(ctx_second_stream(ctx));
-    TRY(launch_surf_detect(ctx, dR, R.data(), u0, params));
-    TRY(launch_surf_describe(ctx, dR, R.data(), u0, params));
+    TRY(surf_run_launch(ctx, surf, 0, u0, true, params));
     SecondStreamJoin join_guard(ctx);
     if (n0 < n) {
         HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -1268,32 +1377,21 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         join_guard.armed = true;
         {
             StreamSwap on_second(ctx, ctx->stream2);              // the launchers enqueue on ctx->stream (their profiling events too)
-            TRY(launch_bf_l2_filtered(ctx, dM, n0, maxcap, maxcap, cns));
-            TRY(launch_ratio_mode(ctx, dM, n0, maxcap, ratio, offset_evaluate));
+            TRY(match_run_launch(ctx, match, 0, n0, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
             HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
         }
-        TRY(launch_surf_detect(ctx, dR + u0, R.data() + u0, u - u0, params));
-        TRY(launch_surf_describe(ctx, dR + u0, R.data() + u0, u - u0, params));
-        TRY(launch_bf_l2_filtered(ctx, dM + n0, n - n0, maxcap, maxcap, cns));
-        TRY(launch_ratio_mode(ctx, dM + n0, n - n0, maxcap, ratio, offset_evaluate));
+        TRY(surf_run_launch(ctx, surf, u0, u - u0, true, params));
+        TRY(match_run_launch(ctx, match, n0, n - n0, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         join_guard.armed = false;                        // joined in stream order: the synchronisation below covers both streams
     } else {
-        if (filtered) { TRY(launch_bf_l2_filtered(ctx, dM, n, maxcap, maxcap, cns)); }
-        else { TRY(launch_bf_l2(ctx, dM, n, maxcap, ns, dim)); }
-        TRY(launch_ratio_mode(ctx, dM, n, maxcap, ratio, offset_evaluate));
+        TRY(match_run_launch(ctx, match, 0, n, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
     }
-    std::vector<int> counters((size_t)16 * u);
-    HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 16 * u, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
+    // counters of all strips and results of all jobs live in two contiguous blocks: one memset, two D2H copies, one synchronisation per batch
+    TRY(surf_run_readback(ctx, &surf));
+    TRY(match_run_readback(ctx, match, out));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < u; i++)
-        if (counters[(size_t)16 * i + 2] || counters[(size_t)16 * i] > R[i].cap) {
-            vfsms_set_error("attempt_surf: strip %d of %d (%d x %d) exceeded %d keypoint candidates (vfsms_ctx_set_keypoint_capacity)",
-                            i, u, R[i].h, R[i].w, R[i].cap);
-            return VFSMS_ERR_CAPACITY;
-        }
-    return VFSMS_OK;
+    return surf_run_check(surf, "attempt_surf", "strip", 0, u);
 }
 
 extern "C" int vfsms_attempt_surf_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
@@ -1321,7 +1419,7 @@ extern "C" int vfsms_enhance_u8(vfsms_ctx *ctx, const uint8_t *img, int h, int w
     TRY(upload_image(ctx, img, h, w, stride, &d_img));
     EnhJob J, *dJ;
     TRY(enhance_carve(ctx, &J, d_img, w, h, w, mode, tile_grid));
-    TRY(upload_pinned(ctx, &J, sizeof(J), (void **)&dJ));
+    TRY(ctx_upload_small(ctx, &J, sizeof(J), (void **)&dJ));
     TRY(launch_enhance(ctx, dJ, &J, 1, mode, clip_limit, tile_grid));
     HIP_TRY(hipMemcpyAsync(out, J.dst, (size_t)h * w, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1329,6 +1427,38 @@ extern "C" int vfsms_enhance_u8(vfsms_ctx *ctx, const uint8_t *img, int h, int w
 }
 
 // ---- device-resident feature sets: the payload of Stitcher.tempImageFeature (Stitcher.py:14-18, 278-290) -----------------------------
+// The described sources of a run leave the arena as feature sets in ONE allocation shared by the sets (a hipMalloc / hipFree pair per set
+// costs more than describing it), released with the last of them (vfsms_features_free).  A set without keypoints owns nothing: block 0,
+// null pointers.  The copies are only enqueued: the caller synchronises before the arena is reused.
+static int feats_from_run(vfsms_ctx *ctx, const SurfRun &run, int dim, int64_t *feats, int *counts)
+{
+    const int m = (int)run.R.size();
+    auto set_bytes = [&](int k) { return (((size_t)surf_run_count(run, k) * (2 + dim) * sizeof(float)) + 255) & ~(size_t)255; };
+    size_t total = 0;
+    for (int k = 0; k < m; k++) total += set_bytes(k);
+    char *base = nullptr; int64_t blk = 0;
+    if (total) {
+        HIP_TRY(hipMalloc((void **)&base, total));
+        blk = ctx->next_handle++;
+        ctx->feat_blocks[blk] = FeatBlock{base, 0};
+    }
+    size_t off = 0;
+    for (int k = 0; k < m; k++) {
+        FeatRec F; F.n = surf_run_count(run, k); F.dim = dim; F.kps_xy = nullptr; F.desc = nullptr;
+        if (F.n > 0) {
+            F.block = blk; ctx->feat_blocks[blk].refs++;
+            F.kps_xy = (float *)(base + off); F.desc = base + off + sizeof(float) * 2 * F.n;
+            off += set_bytes(k);
+            HIP_TRY(hipMemcpyAsync(F.kps_xy, run.R[k].kps_xy, sizeof(float) * 2 * F.n, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(F.desc, run.R[k].desc, sizeof(float) * (size_t)F.n * dim, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        feats[k] = ctx->next_handle++;
+        ctx->feats[feats[k]] = F;
+        counts[k] = F.n;
+    }
+    return VFSMS_OK;
+}
+
 extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0, int h, int w, const vfsms_surf_params *params,
                                    int enhance_mode, double clip_limit, int tile_grid, int64_t *feat, int *n_out)
 {
@@ -1341,44 +1471,19 @@ extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0,
     if (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 + h > T.h || x0 + w > T.w) { vfsms_set_error("features_surf: ROI outside the tile"); return VFSMS_ERR_BAD_ARG; }
     if (enhance_mode < 0 || enhance_mode > 2) { vfsms_set_error("features_surf: enhance_mode must be 0, 1 or 2"); return VFSMS_ERR_BAD_ARG; }
     TRY(ctx_prepare_surf(ctx, params));
-    const int dim = params->extended ? 128 : 64;
-    const int dcap = kp_capacity(ctx, h, w);
-    TRY(ctx_arena_reserve(ctx, surf_roi_bytes(h, w, dcap, ctx->n_layers, params->n_octaves, dim) +
-                               (enhance_mode ? enhance_scratch_bytes(h, w, enhance_mode, tile_grid) : 0) + 65536));
+    const SurfSrc src{T.ptr + (size_t)y0 * T.stride + x0, T.stride, h, w, kp_capacity(ctx, h, w)};
+    const SurfEnh enh{enhance_mode, clip_limit, tile_grid};
+    TRY(ctx_arena_reserve(ctx, surf_run_bytes(ctx, &src, 1, params, enh) + 65536));
     ctx->pinned_off = 0;
-    const uint8_t *src = T.ptr + (size_t)y0 * T.stride + x0;
-    int sstride = T.stride;
-    if (enhance_mode) {
-        EnhJob J, *dJ;
-        TRY(enhance_carve(ctx, &J, src, sstride, h, w, enhance_mode, tile_grid));
-        TRY(upload_pinned(ctx, &J, sizeof(J), (void **)&dJ));
-        TRY(launch_enhance(ctx, dJ, &J, 1, enhance_mode, clip_limit, tile_grid));
-        src = J.dst; sstride = w;
-    }
-    RoiDev R, *d_R;
-    TRY(surf_roi_carve(ctx, &R, src, sstride, h, w, dcap, params));
-    TRY(upload_pinned(ctx, &R, sizeof(R), (void **)&d_R));
-    HIP_TRY(hipMemsetAsync(R.counters, 0, 16 * sizeof(int), ctx->stream));
-    TRY(launch_surf_detect(ctx, d_R, &R, 1, params));
-    TRY(launch_surf_describe(ctx, d_R, &R, 1, params));
-    int counters[16];
-    HIP_TRY(hipMemcpyAsync(counters, R.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+    SurfRun run;
+    TRY(surf_run_carve(ctx, &run, &src, 1, params, enh));
+    TRY(surf_run_prepare(ctx, &run, enh));
+    TRY(surf_run_launch(ctx, run, 0, 1, true, params));
+    TRY(surf_run_readback(ctx, &run));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (counters[2] || counters[0] > dcap) {
-        vfsms_set_error("features_surf: more than %d keypoint candidates (raise with vfsms_ctx_set_keypoint_capacity)", dcap);
-        return VFSMS_ERR_CAPACITY;
-    }
-    FeatRec F; F.n = counters[1]; F.dim = dim; F.is_orb = 0; F.kps_xy = nullptr; F.desc = nullptr;
-    if (F.n > 0) {
-        HIP_TRY(hipMalloc((void **)&F.kps_xy, sizeof(float) * 2 * F.n));
-        HIP_TRY(hipMalloc(&F.desc, sizeof(float) * (size_t)F.n * dim));
-        HIP_TRY(hipMemcpyAsync(F.kps_xy, R.kps_xy, sizeof(float) * 2 * F.n, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(F.desc, R.desc, sizeof(float) * (size_t)F.n * dim, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    *feat = ctx->next_handle++;
-    ctx->feats[*feat] = F;
-    *n_out = F.n;
+    TRY(surf_run_check(run, "features_surf", "rectangle", 0, 1));
+    TRY(feats_from_run(ctx, run, params->extended ? 128 : 64, feat, n_out));
+    if (*n_out > 0) HIP_TRY(hipStreamSynchronize(ctx->stream));      // the copies out of the arena have landed before the next call reuses it
     return VFSMS_OK;
 }
 
@@ -1414,80 +1519,34 @@ static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n,
     if (n < 0 || (n && (!tiles || !feats || !counts)) || !params) { vfsms_set_error("features_surf_batch: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     if (enhance_mode < 0 || enhance_mode > 2) { vfsms_set_error("features_surf_batch: enhance_mode must be 0, 1 or 2"); return VFSMS_ERR_BAD_ARG; }
     TRY(ctx_prepare_surf(ctx, params));
-    const int dim = params->extended ? 128 : 64;
+    const SurfEnh enh{enhance_mode, clip_limit, tile_grid};
     for (int k = 0; k < n; k++) feats[k] = 0;
     for (int c0 = 0; c0 < n;) {
         // a chunk: at most 16 tiles and ~6 GB of scratch
         int c1 = c0; size_t need = 0;
-        std::vector<TileRec *> T; std::vector<int> caps;
+        std::vector<TileRec *> T; std::vector<SurfSrc> S;
         while (c1 < n && c1 - c0 < 16) {
             auto it = ctx->tiles.find(tiles[c1]);
             if (it == ctx->tiles.end()) { vfsms_set_error("features_surf_batch: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
             TileRec &t = it->second;
             if (t.ch != 1) { vfsms_set_error("features_surf_batch: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
-            const int cap = kp_capacity(ctx, t.h, t.w);
-            const size_t b = surf_roi_bytes(t.h, t.w, cap, ctx->n_layers, params->n_octaves, dim) +
-                             (enhance_mode ? enhance_scratch_bytes(t.h, t.w, enhance_mode, tile_grid) + sizeof(EnhJob) + 512 : 0);
+            const SurfSrc src{t.ptr, t.stride, t.h, t.w, kp_capacity(ctx, t.h, t.w)};
+            const size_t b = surf_run_bytes(ctx, &src, 1, params, enh);
             if (c1 > c0 && need + b > ((size_t)6 << 30)) break;
-            need += b; T.push_back(&t); caps.push_back(cap); c1++;
+            need += b; T.push_back(&t); S.push_back(src); c1++;
         }
         const int m = c1 - c0;
-        TRY(ctx_arena_reserve(ctx, need + (sizeof(RoiDev) + 64) * m + 65536));
+        TRY(ctx_arena_reserve(ctx, need + 65536));
         ctx->pinned_off = 0;
-        std::vector<RoiDev> R(m);
-        std::vector<EnhJob> E(enhance_mode ? m : 0);
-        int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * m);
-        for (int k = 0; k < m; k++) {
-            TRY(tile_ready(ctx, *T[k]));
-            const uint8_t *src = T[k]->ptr; int sstride = T[k]->stride;
-            if (enhance_mode) {
-                TRY(enhance_carve(ctx, &E[k], src, sstride, T[k]->h, T[k]->w, enhance_mode, tile_grid));
-                src = E[k].dst; sstride = T[k]->w;
-            }
-            TRY(surf_roi_carve(ctx, &R[k], src, sstride, T[k]->h, T[k]->w, caps[k], params));
-            R[k].counters = cblock + 16 * k;
-        }
-        RoiDev *dR;
-        TRY(upload_pinned(ctx, R.data(), sizeof(RoiDev) * m, (void **)&dR));
-        if (enhance_mode) {
-            EnhJob *dE;
-            TRY(upload_pinned(ctx, E.data(), sizeof(EnhJob) * m, (void **)&dE));
-            TRY(launch_enhance(ctx, dE, E.data(), m, enhance_mode, clip_limit, tile_grid));
-        }
-        HIP_TRY(hipMemsetAsync(cblock, 0, sizeof(int) * 16 * m, ctx->stream));
-        TRY(launch_surf_detect(ctx, dR, R.data(), m, params));
-        TRY(launch_surf_describe(ctx, dR, R.data(), m, params));
-        std::vector<int> counters((size_t)16 * m);
-        HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 16 * m, hipMemcpyDeviceToHost, ctx->stream));
+        for (int k = 0; k < m; k++) TRY(tile_ready(ctx, *T[k]));
+        SurfRun run;
+        TRY(surf_run_carve(ctx, &run, S.data(), m, params, enh));
+        TRY(surf_run_prepare(ctx, &run, enh));
+        TRY(surf_run_launch(ctx, run, 0, m, true, params));
+        TRY(surf_run_readback(ctx, &run));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < m; k++)
-            if (counters[(size_t)16 * k + 2] || counters[(size_t)16 * k] > R[k].cap) {
-                vfsms_set_error("features_surf_batch: tile %d exceeded %d keypoint candidates (vfsms_ctx_set_keypoint_capacity)", c0 + k, R[k].cap);
-                return VFSMS_ERR_CAPACITY;
-            }
-        // ONE allocation for the sets of the chunk (a hipMalloc / hipFree pair per set costs more than describing it)
-        size_t total = 0;
-        for (int k = 0; k < m; k++) total += (((size_t)counters[(size_t)16 * k + 1] * (2 + dim) * sizeof(float)) + 255) & ~(size_t)255;
-        char *base = nullptr; int64_t blk = 0;
-        if (total) {
-            HIP_TRY(hipMalloc((void **)&base, total));
-            blk = ctx->next_handle++;
-            ctx->feat_blocks[blk] = FeatBlock{base, 0};
-        }
-        size_t off = 0;
-        for (int k = 0; k < m; k++) {
-            FeatRec F; F.n = counters[(size_t)16 * k + 1]; F.dim = dim; F.is_orb = 0; F.kps_xy = nullptr; F.desc = nullptr;
-            if (F.n > 0) {
-                F.block = blk; ctx->feat_blocks[blk].refs++;
-                F.kps_xy = (float *)(base + off); F.desc = base + off + sizeof(float) * 2 * F.n;
-                off += (((size_t)F.n * (2 + dim) * sizeof(float)) + 255) & ~(size_t)255;
-                HIP_TRY(hipMemcpyAsync(F.kps_xy, R[k].kps_xy, sizeof(float) * 2 * F.n, hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(hipMemcpyAsync(F.desc, R[k].desc, sizeof(float) * (size_t)F.n * dim, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            feats[c0 + k] = ctx->next_handle++;
-            ctx->feats[feats[c0 + k]] = F;
-            counts[c0 + k] = F.n;
-        }
+        TRY(surf_run_check(run, "features_surf_batch", "tile", c0, n));
+        TRY(feats_from_run(ctx, run, params->extended ? 128 : 64, feats + c0, counts + c0));
         HIP_TRY(hipStreamSynchronize(ctx->stream));          // the copies out of the arena have landed before the next chunk reuses it
         c0 = c1;
     }
@@ -1503,62 +1562,61 @@ static int features_refuse_verifier(vfsms_ctx *ctx, const char *what)
     return VFSMS_ERR_UNSUPPORTED;
 }
 
-// matchDescriptors + getOffsetByMode of n (query set A_k, train set B_k) jobs as ONE batch: out[8 * k ..] as vfsms_features_match_offset
-extern "C" int vfsms_features_match_offset_batch(vfsms_ctx *ctx, const int64_t *feat_a, const int64_t *feat_b, int n, double ratio,
-                                                 int offset_evaluate, int32_t *out)
+// matchDescriptors + getOffsetByMode of n (query set A_k, train set B_k) jobs as ONE batch; `who` prefixes the errors
+static int features_match_impl(vfsms_ctx *ctx, const char *who, const int64_t *feat_a, const int64_t *feat_b, int n, double ratio,
+                               int offset_evaluate, int32_t *out)
 {
-    CTX_ENTER(ctx);
-    if (n < 0 || (n && (!feat_a || !feat_b || !out))) { vfsms_set_error("features_match_batch: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    TRY(features_refuse_verifier(ctx, "features_match_batch"));
-    std::vector<const FeatRec *> A(n), B(n);
-    std::vector<int> live;
+    if (n < 0 || (n && (!feat_a || !feat_b || !out))) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    TRY(features_refuse_verifier(ctx, who));
+    std::vector<MatchJob> J;
+    std::vector<int> live, cnt;
     int maxq = 0, maxt = 0, dim = 0;
     for (int k = 0; k < n; k++) {
         auto ia = ctx->feats.find(feat_a[k]), ib = ctx->feats.find(feat_b[k]);
-        if (ia == ctx->feats.end() || ib == ctx->feats.end()) { vfsms_set_error("features_match_batch: unknown handle"); return VFSMS_ERR_BAD_ARG; }
-        A[k] = &ia->second; B[k] = &ib->second;
-        if (A[k]->dim != B[k]->dim || A[k]->is_orb || B[k]->is_orb || (dim && A[k]->dim != dim)) { vfsms_set_error("features_match_batch: descriptor kinds differ"); return VFSMS_ERR_BAD_ARG; }
-        dim = A[k]->dim;
+        if (ia == ctx->feats.end() || ib == ctx->feats.end()) { vfsms_set_error("%s: unknown handle", who); return VFSMS_ERR_BAD_ARG; }
+        const FeatRec &a = ia->second, &b = ib->second;
+        if (a.dim != b.dim || (dim && a.dim != dim)) { vfsms_set_error("%s: descriptor kinds differ", who); return VFSMS_ERR_BAD_ARG; }
+        dim = a.dim;
         for (int c = 0; c < VFSMS_ATTEMPT_INTS; c++) out[VFSMS_ATTEMPT_INTS * k + c] = 0;
-        out[VFSMS_ATTEMPT_INTS * k + 4] = A[k]->n; out[VFSMS_ATTEMPT_INTS * k + 5] = B[k]->n;
-        if (A[k]->n > 0 && B[k]->n > 0) { live.push_back(k); maxq = std::max(maxq, A[k]->n); maxt = std::max(maxt, B[k]->n); }
+        out[VFSMS_ATTEMPT_INTS * k + 4] = a.n; out[VFSMS_ATTEMPT_INTS * k + 5] = b.n;
+        if (a.n == 0 || b.n == 0) continue;
+        MatchJob j{};
+        j.q = (const float *)a.desc; j.t = (const float *)b.desc; j.kq = a.kps_xy; j.kt = b.kps_xy;
+        j.capq = a.n; j.capt = b.n; j.row = (int)live.size();
+        J.push_back(j); live.push_back(k); cnt.push_back(a.n); cnt.push_back(b.n);
+        maxq = std::max(maxq, a.n); maxt = std::max(maxt, b.n);
     }
     const int m = (int)live.size();
     if (m == 0) return VFSMS_OK;
-    const bool filtered = dim == 64 && !bf_force_exact();
-    const int cns = pick_filter_nsplit(maxq, m, maxt);
-    const int ns = filtered ? 1 : pick_nsplit(maxq, maxt, m, dim);
-    size_t need = 0;
-    for (int j = 0; j < m; j++)
-        need += match_bytes(A[live[j]]->n, ns) + (filtered ? match_filter_bytes(A[live[j]]->n, B[live[j]]->n, cns) : 0);
-    TRY(ctx_arena_reserve(ctx, need + (sizeof(MatchDev) + 64 + sizeof(int32_t) * VFSMS_ATTEMPT_INTS) * m + 65536));
+    const MatchPlan P = match_plan_float(dim, m, maxq, maxt, maxq, maxt);       // SURF descriptors are L2-normalised by construction
+    TRY(ctx_arena_reserve(ctx, match_run_bytes(J.data(), m, P) + 65536));
     ctx->pinned_off = 0;
-    std::vector<MatchDev> M(m);
-    std::vector<int> cnt(2 * m);
-    for (int j = 0; j < m; j++) { cnt[2 * j] = A[live[j]]->n; cnt[2 * j + 1] = B[live[j]]->n; }
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * m);
     int *dcnt;
-    TRY(upload_pinned(ctx, cnt.data(), sizeof(int) * 2 * m, (void **)&dcnt));
-    for (int j = 0; j < m; j++) {
-        const FeatRec &a = *A[live[j]], &b = *B[live[j]];
-        memset(&M[j], 0, sizeof(MatchDev));
-        TRY(match_carve(ctx, &M[j], a.n, dim, ns));
-        if (filtered) TRY(match_filter_carve(ctx, &M[j], a.n, b.n, cns));
-        M[j].result = rblock + VFSMS_ATTEMPT_INTS * j;
-        M[j].q = (const float *)a.desc; M[j].t = (const float *)b.desc; M[j].kq = a.kps_xy; M[j].kt = b.kps_xy;
-        M[j].nq_ptr = dcnt + 2 * j; M[j].nt_ptr = dcnt + 2 * j + 1;
-    }
-    MatchDev *dM;
-    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * m, (void **)&dM));
-    if (filtered) { TRY(launch_bf_l2_filtered(ctx, dM, m, maxq, maxt, cns)); }
-    else { TRY(launch_bf_l2(ctx, dM, m, maxq, ns, dim)); }
-    TRY(launch_ratio_mode(ctx, dM, m, maxq, ratio, offset_evaluate));
+    TRY(ctx_upload_small(ctx, cnt.data(), sizeof(int) * 2 * m, (void **)&dcnt));
+    for (int j = 0; j < m; j++) { J[j].nq_ptr = dcnt + 2 * j; J[j].nt_ptr = dcnt + 2 * j + 1; }
+    MatchRun run;
+    TRY(match_run_carve(ctx, &run, J.data(), m, dim, P));
+    TRY(match_run_launch(ctx, run, 0, m, maxq, maxt, SEARCH_FLOAT, ratio, offset_evaluate));
     std::vector<int32_t> res((size_t)VFSMS_ATTEMPT_INTS * m);
-    HIP_TRY(hipMemcpyAsync(res.data(), rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * m, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(match_run_readback(ctx, run, res.data()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int j = 0; j < m; j++)
         for (int c = 0; c < VFSMS_ATTEMPT_INTS; c++) out[VFSMS_ATTEMPT_INTS * live[j] + c] = res[(size_t)VFSMS_ATTEMPT_INTS * j + c];
     return VFSMS_OK;
+}
+// out[8 * k ..] as vfsms_features_match_offset
+extern "C" int vfsms_features_match_offset_batch(vfsms_ctx *ctx, const int64_t *feat_a, const int64_t *feat_b, int n, double ratio,
+                                                 int offset_evaluate, int32_t *out)
+{
+    CTX_ENTER(ctx);
+    return features_match_impl(ctx, "features_match_batch", feat_a, feat_b, n, ratio, offset_evaluate, out);
+}
+// matchDescriptors + getOffsetByMode on two resident sets (query = A, train = B): out[8] as in vfsms_attempt_surf_batch
+extern "C" int vfsms_features_match_offset(vfsms_ctx *ctx, int64_t feat_a, int64_t feat_b, double ratio, int offset_evaluate, int32_t *out)
+{
+    CTX_ENTER(ctx);
+    if (!ctx->feats.count(feat_a) || !ctx->feats.count(feat_b) || !out) { vfsms_set_error("features_match: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    return features_match_impl(ctx, "features_match", &feat_a, &feat_b, 1, ratio, offset_evaluate, out);
 }
 
 extern "C" int vfsms_features_free(vfsms_ctx *ctx, int64_t feat)
@@ -1566,17 +1624,11 @@ extern "C" int vfsms_features_free(vfsms_ctx *ctx, int64_t feat)
     CTX_ENTER(ctx);
     auto it = ctx->feats.find(feat);
     if (it == ctx->feats.end()) { vfsms_set_error("features_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
-    if (it->second.block) {
-        auto bt = ctx->feat_blocks.find(it->second.block);
-        if (bt != ctx->feat_blocks.end() && --bt->second.refs == 0) {
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            HIP_TRY(hipFree(bt->second.base));
-            ctx->feat_blocks.erase(bt);
-        }
-    } else {
+    auto bt = ctx->feat_blocks.find(it->second.block);       // (a set without keypoints has no block)
+    if (bt != ctx->feat_blocks.end() && --bt->second.refs == 0) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (it->second.kps_xy) HIP_TRY(hipFree(it->second.kps_xy));
-        if (it->second.desc) HIP_TRY(hipFree(it->second.desc));
+        HIP_TRY(hipFree(bt->second.base));
+        ctx->feat_blocks.erase(bt);
     }
     ctx->feats.erase(it);
     return VFSMS_OK;
@@ -1599,56 +1651,33 @@ extern "C" int vfsms_features_download(vfsms_ctx *ctx, int64_t feat, float *kps_
     return VFSMS_OK;
 }
 
-// matchDescriptors + getOffsetByMode on two resident sets (query = A, train = B): out[8] as in vfsms_attempt_surf_batch
-extern "C" int vfsms_features_match_offset(vfsms_ctx *ctx, int64_t feat_a, int64_t feat_b, double ratio, int offset_evaluate, int32_t *out)
+// ---- fuse ----------------------------------------------------------------------------------------------------------------------
+// The four int64 operators share everything behind their own argument checks: both regions up, the fade's geometry decisions + the blend of
+// `method` (fuse_i64_device: 0 fadeInAndFadeOut, 1 trigonometric, 2 multiBandBlending, 3 optimalSeamLine), the bytes (and the seam) down.
+static int fuse_i64_host(vfsms_ctx *ctx, const char *what, const int64_t *A, const int64_t *B, int r, int c, int ch, int dx, int dy,
+                         uint8_t *out, int32_t *info, int method, int levels, int blend, int32_t *seam_out)
 {
-    CTX_ENTER(ctx);
-    auto ia = ctx->feats.find(feat_a), ib = ctx->feats.find(feat_b);
-    if (ia == ctx->feats.end() || ib == ctx->feats.end() || !out) { vfsms_set_error("features_match: unknown handle"); return VFSMS_ERR_BAD_ARG; }
-    TRY(features_refuse_verifier(ctx, "features_match"));
-    const FeatRec &A = ia->second, &B = ib->second;
-    if (A.dim != B.dim || A.is_orb != B.is_orb) { vfsms_set_error("features_match: descriptor kinds differ"); return VFSMS_ERR_BAD_ARG; }
-    for (int k = 0; k < VFSMS_ATTEMPT_INTS; k++) out[k] = 0;
-    out[4] = A.n; out[5] = B.n;
-    if (A.n == 0 || B.n == 0) return VFSMS_OK;
-    const int dim = A.dim, capq = A.n;
-    const bool filtered = dim == 64 && !bf_force_exact();          // SURF descriptors are L2-normalised by construction
-    const int cns = pick_filter_nsplit(A.n, 1, B.n);
-    const int ns = filtered ? 1 : pick_nsplit(A.n, B.n, 1, dim);
-    TRY(ctx_arena_reserve(ctx, match_bytes(capq, ns) + (filtered ? match_filter_bytes(capq, B.n, cns) : 0) + 65536));
-    ctx->pinned_off = 0;
-    MatchDev M; memset(&M, 0, sizeof(M));
-    TRY(match_carve(ctx, &M, capq, dim, ns));
-    if (filtered) TRY(match_filter_carve(ctx, &M, capq, B.n, cns));
-    int cnt[2] = {A.n, B.n}; int *dcnt;
-    TRY(upload_pinned(ctx, cnt, sizeof(cnt), (void **)&dcnt));
-    M.q = (const float *)A.desc; M.t = (const float *)B.desc; M.kq = A.kps_xy; M.kt = B.kps_xy; M.nq_ptr = dcnt; M.nt_ptr = dcnt + 1;
-    MatchDev *dM;
-    TRY(upload_pinned(ctx, &M, sizeof(M), (void **)&dM));
-    if (filtered) { TRY(launch_bf_l2_filtered(ctx, dM, 1, capq, B.n, cns)); }
-    else { TRY(launch_bf_l2(ctx, dM, 1, capq, ns, dim)); }
-    TRY(launch_ratio_mode(ctx, dM, 1, capq, ratio, offset_evaluate));
-    HIP_TRY(hipMemcpyAsync(out, M.result, sizeof(int32_t) * VFSMS_ATTEMPT_INTS, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t nel = (size_t)r * c * ch, nseam = sizeof(int32_t) * ((size_t)r + c);
+    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 4 * ((size_t)r + c) + (seam_out ? nseam : 0) + 65536));
+    long long *dA, *dB;
+    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
+    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
+    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
+    int32_t *d_seam = seam_out ? (int32_t *)ctx_arena_alloc(ctx, nseam) : nullptr;
+    if (!d_out || (seam_out && !d_seam)) { vfsms_set_error("%s: arena exhausted", what); return VFSMS_ERR_CAPACITY; }
+    TRY(fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, method, levels, blend, d_seam));
+    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
+    if (seam_out) HIP_TRY(hipMemcpyAsync(seam_out, d_seam, nseam, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
 }
 
-// ---- fuse ----------------------------------------------------------------------------------------------------------------------
 extern "C" int vfsms_fuse_fade_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
                                    int dx, int dy, uint8_t *out, int32_t *info)
 {
     CTX_ENTER(ctx);
     if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    const size_t nel = (size_t)r * c * ch;
-    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 4 * ((size_t)r + c) + 65536));
-    long long *dA, *dB;
-    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
-    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
-    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
-    TRY(fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info));
-    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    return fuse_i64_host(ctx, "fuse_i64", A, B, r, c, ch, dx, dy, out, info, 0, 4, 0, nullptr);
 }
 
 // ImageFusion.fuseByTrigonometric (ImageFusion.py:246-293) on the reference's own array representation
@@ -1657,16 +1686,7 @@ extern "C" int vfsms_fuse_trig_i64(vfsms_ctx *ctx, const int64_t *A, const int64
 {
     CTX_ENTER(ctx);
     if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_trig_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    const size_t nel = (size_t)r * c * ch;
-    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 4 * ((size_t)r + c) + 65536));
-    long long *dA, *dB;
-    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
-    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
-    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
-    TRY(fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, 1));
-    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    return fuse_i64_host(ctx, "fuse_trig_i64", A, B, r, c, ch, dx, dy, out, info, 1, 4, 0, nullptr);
 }
 
 // multiBandBlending on the reference's own array representation: the seam from the fade's geometry (degenerate corner geometries
@@ -1677,16 +1697,7 @@ extern "C" int vfsms_fuse_multiband_i64(vfsms_ctx *ctx, const int64_t *A, const 
     CTX_ENTER(ctx);
     if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_multiband_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     if (levels < 1 || levels > VFSMS_MB_MAX_LEVELS) { vfsms_set_error("fuse_multiband_i64: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
-    const size_t nel = (size_t)r * c * ch;
-    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 4 * ((size_t)r + c) + 65536));
-    long long *dA, *dB;
-    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
-    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
-    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
-    TRY(fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, 2, levels));
-    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    return fuse_i64_host(ctx, "fuse_multiband_i64", A, B, r, c, ch, dx, dy, out, info, 2, levels, 0, nullptr);
 }
 
 // optimalSeamLine on the reference's own array representation: the fade's geometry decisions (degenerate corner geometries fail as the
@@ -1699,25 +1710,13 @@ extern "C" int vfsms_fuse_seam_i64(vfsms_ctx *ctx, const int64_t *A, const int64
     if (!A || !B || !out || r <= 0 || c <= 0 || ch < 1 || ch > 4) { vfsms_set_error("fuse_seam_i64: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     if (blend < 0 || blend > 1) { vfsms_set_error("fuse_seam_i64: blend must be 0 (none) or 1 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
     if (blend == 1 && (levels < 1 || levels > VFSMS_MB_MAX_LEVELS)) { vfsms_set_error("fuse_seam_i64: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
-    const size_t nel = (size_t)r * c * ch;
-    TRY(ctx_arena_reserve(ctx, nel * 17 + sizeof(float) * 4 * ((size_t)r + c) + sizeof(int) * 5 * ((size_t)r + c) + 65536));
-    long long *dA, *dB;
-    TRY(upload_array(ctx, (const long long *)A, nel, &dA));
-    TRY(upload_array(ctx, (const long long *)B, nel, &dB));
-    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, nel);
-    int32_t *d_seam = seam_out ? (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * ((size_t)r + c)) : nullptr;
-    if (seam_out && !d_seam) { vfsms_set_error("arena exhausted in fuse_seam"); return VFSMS_ERR_CAPACITY; }
-    const int rc = fuse_i64_device(ctx, dA, dB, r, c, ch, dx, dy, d_out, info, 3, levels, blend, d_seam);
-    if (rc != VFSMS_OK) {                                      // a refused geometry: info[0] = -1, output zero, no seam
+    const int rc = fuse_i64_host(ctx, "fuse_seam_i64", A, B, r, c, ch, dx, dy, out, info, 3, levels, blend, seam_out);
+    if (rc != VFSMS_OK) {                                      // a refused geometry (or a failed run): info[0] = -1, output zero, no seam
         if (info) info[0] = -1;
-        memset(out, 0, nel);
+        memset(out, 0, (size_t)r * c * ch);
         if (seam_out) for (size_t k = 0; k < (size_t)r + c; k++) seam_out[k] = -1;
-        return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out, d_out, nel, hipMemcpyDeviceToHost, ctx->stream));
-    if (seam_out) HIP_TRY(hipMemcpyAsync(seam_out, d_seam, sizeof(int32_t) * ((size_t)r + c), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    return rc;
 }
 
 int fuse_i64_ramps(vfsms_ctx *ctx, const long long *dA, int r, int c, int ch, int dx, int dy, int force_corner,
@@ -2187,10 +2186,7 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     if (n < 0 || (n && (!jobs || !out)) || !params) { vfsms_set_error("attempt_sift: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     TRY(sift_check_params(params));
     if (n == 0) return VFSMS_OK;
-    std::vector<int> ord(n);
-    for (int k = 0; k < n; k++) ord[k] = k;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
-        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    const std::vector<int> ord = shape_order(jobs, n);
     StripTable T;
     TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
     const int u = (int)T.strips.size();
@@ -2201,10 +2197,10 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     std::vector<SiftStripOut> S(u);
     const bool exact = bf_force_exact();
     // detect + describe (+ pack): the strips are in shape order already
-    for (int i0 = 0; i0 < u;) {
+    auto strip_shape = [&](int i) { return std::make_pair(T.strips[i].h, T.strips[i].w); };
+    for (int i0 = 0, i1; i0 < u; i0 = i1) {
         const int h = T.strips[i0].h, w = T.strips[i0].w;
-        int i1 = i0;
-        while (i1 < u && T.strips[i1].h == h && T.strips[i1].w == w) i1++;
+        i1 = shape_run_end(i0, u, strip_shape);
         int gmax = 1;
         TRY(sift_group_strips(ctx, h, w, params, &gmax));
         for (int a = i0; a < i1; a += gmax) {
@@ -2224,51 +2220,38 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
                 }
                 if (!pj.empty()) {
                     PackJob *dP;
-                    TRY(upload_pinned(ctx, pj.data(), sizeof(PackJob) * pj.size(), (void **)&dP));
+                    TRY(ctx_upload_small(ctx, pj.data(), sizeof(PackJob) * pj.size(), (void **)&dP));
                     TRY(launch_pack_i8_d128(ctx, dP, (int)pj.size(), maxn));
                 }
             }
         }
-        i0 = i1;
     }
     // match + vote: capacities are the exact counts
     HIP_TRY(hipStreamSynchronize(ctx->stream));                 // the last group's launch records have left the staging buffer, reset below
-    int maxcap = 1; long long waves = 0;
-    std::vector<int> caps(n);
+    int maxcap = 1, maxt = 1; long long waves = 0;
+    std::vector<MatchJob> J(n, MatchJob{});
     for (int s_ = 0; s_ < n; s_++) {
-        caps[s_] = std::max(S[T.a[s_]].n, 1);
-        maxcap = std::max(maxcap, caps[s_]);
-        waves += (caps[s_] + 63) / 64;
-    }
-    int maxt = 1;
-    for (int s_ = 0; s_ < n; s_++) maxt = std::max(maxt, S[T.b[s_]].n);
-    const int ns = exact ? pick_nsplit(maxcap, maxt, n, 128)
-                         : (int)std::max<long long>(1, std::min<long long>({8, (4096 + waves - 1) / waves, (long long)(maxt + 255) / 256}));
-    size_t need = 0;
-    for (int s_ = 0; s_ < n; s_++) need += match_bytes(caps[s_], ns);
-    need += sizeof(MatchDev) * n + (64 + VFSMS_ATTEMPT_INTS * sizeof(int32_t)) * (size_t)n + 65536;
-    TRY(ctx_arena_reserve(ctx, need));
-    ctx->pinned_off = 0;
-    int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-    std::vector<MatchDev> M(n);
-    for (int s_ = 0; s_ < n; s_++) {
-        const int k = ord[s_], ia = T.a[s_], ib = T.b[s_];
+        const int ia = T.a[s_], ib = T.b[s_];
         const SiftStripOut &A = S[ia], &B = S[ib];
-        memset(&M[s_], 0, sizeof(MatchDev));
-        TRY(match_carve(ctx, &M[s_], caps[s_], 128, ns));
-        M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-        M[s_].q = A.desc; M[s_].t = B.desc;
-        M[s_].q8 = A.d8; M[s_].t8 = B.d8; M[s_].qn2 = A.nrm; M[s_].tn2 = B.nrm;
-        M[s_].nq_ptr = cblock + 4 * ia + 2; M[s_].nt_ptr = cblock + 4 * ib + 2;
-        M[s_].kq = A.xy; M[s_].kt = B.xy;
-        match_set_strips(&M[s_], T.strips[ia], T.strips[ib]);
+        MatchJob &j = J[s_];
+        j.q = A.desc; j.t = B.desc; j.kq = A.xy; j.kt = B.xy;
+        j.q8 = A.d8; j.t8 = B.d8; j.qn2 = A.nrm; j.tn2 = B.nrm;
+        j.nq_ptr = cblock + 4 * ia + 2; j.nt_ptr = cblock + 4 * ib + 2;
+        j.capq = std::max(A.n, 1); j.capt = std::max(B.n, 1); j.row = ord[s_];
+        j.sa = &T.strips[ia]; j.sb = &T.strips[ib];
+        maxcap = std::max(maxcap, j.capq); maxt = std::max(maxt, B.n);
+        waves += (j.capq + 63) / 64;
     }
-    MatchDev *dM;
-    TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-    if (exact) { TRY(launch_bf_l2(ctx, dM, n, maxcap, ns, 128)); }
-    else { TRY(launch_bf_i8_d128(ctx, dM, n, maxcap, ns)); }
-    TRY(launch_ratio_mode(ctx, dM, n, maxcap, ratio, offset_evaluate));
-    HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
+    // a wave of the integer kernel owns 64 queries: its own split rule; the exhaustive float kernel keeps pick_nsplit
+    MatchPlan P{false, 0, 0};
+    P.ns = exact ? pick_nsplit(maxcap, maxt, n, 128)
+                 : (int)std::max<long long>(1, std::min<long long>({8, (4096 + waves - 1) / waves, (long long)(maxt + 255) / 256}));
+    TRY(ctx_arena_reserve(ctx, match_run_bytes(J.data(), n, P) + 65536));
+    ctx->pinned_off = 0;
+    MatchRun run;
+    TRY(match_run_carve(ctx, &run, J.data(), n, 128, P));
+    TRY(match_run_launch(ctx, run, 0, n, maxcap, maxt, exact ? SEARCH_FLOAT : SEARCH_I8_D128, ratio, offset_evaluate));
+    TRY(match_run_readback(ctx, run, out));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
 }
@@ -2284,10 +2267,7 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
     orb_caps(params, &c1, &c2, &c);
     // ROIs of one shape next to each other: the image-sized kernels are launched per shape run (launch_orb); slot s holds job ord[s];
     // every distinct strip of the batch is carved and run once (build_strip_table)
-    std::vector<int> ord(n);
-    for (int k = 0; k < n; k++) ord[k] = k;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a_, int b_) {
-        return jobs[a_].h != jobs[b_].h ? jobs[a_].h < jobs[b_].h : jobs[a_].w < jobs[b_].w; });
+    const std::vector<int> ord = shape_order(jobs, n);
     StripTable T;
     TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
     const int u = (int)T.strips.size();
@@ -2325,8 +2305,8 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
         }
         ctx->pinned_off = 0;
         OrbDev *dR; MatchDev *dM;
-        TRY(upload_pinned(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
-        TRY(upload_pinned(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
+        TRY(ctx_upload_small(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
+        TRY(ctx_upload_small(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
         TRY(launch_orb(ctx, dR, R.data(), u, params));
         TRY(launch_hamming_mode(ctx, dM, n, c, hns, max_dist, offset_evaluate));
         std::vector<int> counters((size_t)64 * u);

@@ -138,7 +138,7 @@ struct OrbTables { int nfeat[VFSMS_ORB_MAX_LEVELS]; int umax[34]; int half_patch
 struct EnhJob { const uint8_t *src; int stride, h, w, eh, ew; uint8_t *dst; int *hist; uint8_t *lut; };   // eh, ew: size extended to the CLAHE grid
 
 // ---- device-resident feature set (keypoints + descriptors of one image; Stitcher.tempImageFeature's payload) ---------------
-struct FeatRec { float *kps_xy; void *desc; int n, dim, is_orb; int64_t block = 0; };   // block != 0: kps_xy / desc point into a shared allocation (feat_blocks)
+struct FeatRec { float *kps_xy; void *desc; int n, dim; int64_t block = 0; };   // kps_xy / desc point into the shared allocation `block` (feat_blocks); a set without keypoints: block 0, null pointers
 struct FeatBlock { void *base; int refs; };
 
 // ---- one (query ROI, train ROI) matching job --------------------------------------------------------
@@ -222,7 +222,7 @@ struct vfsms_ctx {
     size_t sift_group_bytes = (size_t)4 << 30;                     // pyramid bytes resident at once in a fused SIFT batch (VFSMS_SIFT_GROUP_BYTES overrides)
     CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
-    std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a batch (vfsms_features_surf_batch), freed with its last set
+    std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a call (vfsms_features_surf, one set; vfsms_features_surf_batch, a chunk's), freed with its last set
     int64_t next_handle;
     std::list<FftPlan> plans;            // list: get_plan hands out stable pointers
     std::vector<std::pair<int, void *>> fft_tabs;   // twiddle tables exp(-2 pi i q / L) of the LDS transforms of phase_kernels.hip, one per length
