@@ -58,6 +58,10 @@ class RoiPair(C.Structure):
                 ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class NccJob(C.Structure):
+    _fields_ = [("tile_a", C.c_int64), ("tile_b", C.c_int64), ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
 KP_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"),
                      ("response", "f4"), ("octave", "i4"), ("class_id", "i4")])
 
@@ -75,6 +79,7 @@ _SIGNATURES = {
     "vfsms_ctx_set_offset_estimator": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "vfsms_ctx_set_offset_verifier": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
     "vfsms_verify_ncc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_ncc_search_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_profile_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "vfsms_tile_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -285,6 +290,36 @@ class Engine:
         self._check(self.lib.vfsms_verify_ncc(self.ctx, _ptr(a), a.strides[0], _ptr(b), b.strides[0], a.shape[0], a.shape[1],
                                               int(dx), int(dy), int(min_pixels), _ptr(out)))
         return tuple(int(v) for v in out[:6]), float(out[6:7].view(np.float64)[0]), int(out[7])
+
+    def ncc_search_batch(self, jobs, radius, min_pixels, want_surface=False):
+        """vfsms_ncc_search_batch: jobs = sequence of (tile_a, tile_b, dx, dy) over resident gray tiles of one shape per job; every offset
+        (dx + i, dy + j), i, j in [-radius, radius] (radius 1..16), scored as verify_ncc scores one (tests/ncc_search_ref.py).
+        -> int32[n, 4] = (i, j, fixed-point score, shared pixels) of the best candidate per job [, int32[n, 2 radius + 1, 2 radius + 1], the
+        fixed-point score of every candidate, with want_surface]"""
+        n = len(jobs)
+        side = 2 * int(radius) + 1
+        best = np.zeros((n, 4), np.int32)
+        surface = np.zeros((n, side, side), np.int32) if want_surface else None
+        arr = (NccJob * max(n, 1))()
+        for k, j in enumerate(jobs):
+            arr[k] = NccJob(*[int(v) for v in j])
+        self._check(self.lib.vfsms_ncc_search_batch(self.ctx, arr, n, int(radius), int(min_pixels), _ptr(best), _ptr(surface)))
+        return (best, surface) if want_surface else best
+
+    def ncc_search(self, a, b, dx, dy, radius, min_pixels):
+        """ncc_search_batch for two host arrays (uint8, one shape), uploaded for the call -> ((i, j), score / VERIFY_FIXED_ONE as the
+        fixed-point integer, shared pixels, int32 surface)"""
+        a = _u8_2d(a); b = _u8_2d(b)
+        ha = self.tile_upload(a)
+        try:
+            hb = self.tile_upload(b)
+            try:
+                best, surface = self.ncc_search_batch([(ha, hb, dx, dy)], radius, min_pixels, want_surface=True)
+            finally:
+                self.tile_free(hb)
+        finally:
+            self.tile_free(ha)
+        return (int(best[0, 0]), int(best[0, 1])), int(best[0, 2]), int(best[0, 3]), surface[0]
 
     def profile_enable(self, on=True):
         self._check(self.lib.vfsms_profile_enable(self.ctx, int(bool(on))))

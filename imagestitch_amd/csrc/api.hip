@@ -1090,6 +1090,44 @@ extern "C" int vfsms_verify_ncc(vfsms_ctx *ctx, const uint8_t *a, int a_stride, 
     return VFSMS_OK;
 }
 
+// vfsms_ncc_search_batch: the window search of adjust_kernels.hip over pairs of resident tiles; every launch of the batch is enqueued
+// before the one synchronisation that brings the results back
+extern "C" int vfsms_ncc_search_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int radius, int min_pixels, int32_t *best4, int32_t *surface)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!jobs || !best4)) || min_pixels < 0) { vfsms_set_error("ncc_search: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (radius < 1 || radius > VFSMS_ADJUST_MAX_RADIUS) { vfsms_set_error("ncc_search: radius %d outside 1..%d", radius, VFSMS_ADJUST_MAX_RADIUS); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    std::vector<AdjJob> H(n);
+    for (int k = 0; k < n; k++) {
+        auto ia = ctx->tiles.find(jobs[k].tile_a), ib = ctx->tiles.find(jobs[k].tile_b);
+        if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("ncc_search: job %d names an unknown tile handle", k); return VFSMS_ERR_BAD_ARG; }
+        TileRec &A = ia->second, &B = ib->second;
+        if (A.ch != 1 || B.ch != 1) { vfsms_set_error("ncc_search: job %d names a colour tile; the search takes single-channel tiles", k); return VFSMS_ERR_BAD_ARG; }
+        if (A.h != B.h || A.w != B.w) { vfsms_set_error("ncc_search: the tiles of job %d are %d x %d and %d x %d", k, A.h, A.w, B.h, B.w); return VFSMS_ERR_BAD_ARG; }
+        TRY(tile_ready(ctx, A)); TRY(tile_ready(ctx, B));
+        H[k].a = A.ptr; H[k].b = B.ptr; H[k].sa = A.stride; H[k].sb = B.stride; H[k].h = A.h; H[k].w = A.w; H[k].dx = jobs[k].dx; H[k].dy = jobs[k].dy;
+    }
+    const size_t CC = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    const int part = 32768;                                  // jobs per launch (a grid dimension holds 65535)
+    const size_t sums_bytes = adjust_sums_bytes(std::min(n, part), radius);
+    TRY(ctx_arena_reserve(ctx, sizeof(AdjJob) * (size_t)n + sums_bytes + sizeof(int32_t) * (size_t)n * (4 + (surface ? CC : 0)) + 65536));
+    ctx->pinned_off = 0;
+    AdjJob *dJ;
+    TRY(ctx_upload_small(ctx, H.data(), sizeof(AdjJob) * (size_t)n, (void **)&dJ));
+    unsigned long long *d_sums = (unsigned long long *)ctx_arena_alloc(ctx, sums_bytes);
+    int32_t *d_best = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * (size_t)n);
+    int32_t *d_surf = surface ? (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * CC * (size_t)n) : nullptr;
+    if (!d_sums || !d_best || (surface && !d_surf)) { vfsms_set_error("ncc_search: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    for (int k0 = 0; k0 < n; k0 += part)                     // (stream order: a part's sums are cleared after the part before it was scored)
+        TRY(launch_adjust_search(ctx, dJ + k0, H.data() + k0, std::min(part, n - k0), radius, min_pixels, d_sums, d_best + 4 * (size_t)k0,
+                                 d_surf ? d_surf + CC * (size_t)k0 : nullptr));
+    HIP_TRY(hipMemcpyAsync(best4, d_best, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (surface) HIP_TRY(hipMemcpyAsync(surface, d_surf, sizeof(int32_t) * CC * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 // ---- phase correlation ---------------------------------------------------------------------------------------------------
 extern "C" int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
                                         int stride_a, int stride_b, double *out3)

@@ -281,6 +281,13 @@ int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq
 int launch_consensus(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int tol, int offset_evaluate);
 // verify_kernels.hip
 int launch_verify(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, double threshold, int min_pixels);
+// adjust_kernels.hip: the offset search of Method.globalAdjust = "ncc".  One job: two whole tiles of one shape (pointers, row strides in
+// bytes) and the predicted offset the window is centred on (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy))
+#define VFSMS_ADJUST_MAX_RADIUS 16
+struct AdjJob { const uint8_t *a, *b; int sa, sb, h, w, dx, dy; };
+size_t adjust_sums_bytes(int njobs, int radius);
+int launch_adjust_search(vfsms_ctx *ctx, const AdjJob *d_jobs, const AdjJob *h_jobs, int njobs, int radius, int min_pixels,
+                         unsigned long long *d_sums, int32_t *d_best4, int32_t *d_surface);
 // orb_kernels.hip
 int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p);
 size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2, int cap);

@@ -11,35 +11,12 @@
 //   k_verify_decide  (one lane per job)        -> result[7] = fixed-point score, result[0] = 0 when score < threshold
 // The result row is read on the device: no host synchronisation inside a batch.
 #include "common.h"
+#include "verify_math.h"
 #include <algorithm>
 
 #define VERIFY_WG 64         // workgroups per job at most: 256 waves, a wave per overlap row
 
 // vsum layout (MatchDev::vsum, 8 x uint64): [0] N, [1] Sa, [2] Sb, [3] Saa, [4] Sbb, [5] Sab, [6] bits of the double score, [7] fixed point
-struct Overlap { int r0, r1, c0, c1; };
-__device__ __forceinline__ Overlap verify_overlap(int h, int w, int dx, int dy)
-{
-    Overlap o;
-    o.r0 = max(0, -dx); o.r1 = min(h, h - dx);
-    o.c0 = max(0, -dy); o.c1 = min(w, w - dy);
-    return o;
-}
-
-// tests/verify_ref.py: score() -- every operation is one correctly rounded IEEE double operation, in this order
-__device__ __forceinline__ double verify_score(long long N, long long Sa, long long Sb, long long Saa, long long Sbb, long long Sab, int min_pixels)
-{
-    if (N <= 0 || N < (long long)min_pixels) return 0.0;
-    const double n = (double)N, sa = (double)Sa, sb = (double)Sb;
-    const double ma = sa / n, mb = sb / n;
-    const double va = (double)Saa - sa * ma;
-    const double vb = (double)Sbb - sb * mb;
-    const double cab = (double)Sab - sa * mb;
-    if (!(va > 0.0) || !(vb > 0.0)) return 0.0;
-    const double s = cab / (sqrt(va) * sqrt(vb));
-    return fmin(1.0, fmax(-1.0, s));
-}
-__device__ __forceinline__ int verify_fixed(double score) { return (int)floor(score * (double)VFSMS_VERIFY_FIXED_ONE + 0.5); }
-
 __global__ __launch_bounds__(64) void k_verify_clear(const MatchDev *jobs, int njobs)
 {
     const int j = blockIdx.x * 64 + threadIdx.x;

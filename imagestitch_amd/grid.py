@@ -405,6 +405,19 @@ class GridRegistrar:
             self._learn(out, mem, direction)
         return out, d
 
+    def adjust(self, handles, shapes, table_or_offsets, radius=4, threshold=0.5, min_pixels=4096):
+        """Global placement of a registered path (adjust.adjust_offsets): `table_or_offsets` is the table of register() -- every pair
+        registered -- or a list of [dx, dy]; -> (adjusted [[dx, dy], ...], report).  The offsets of side neighbours ACROSS the path are
+        measured too, by a correlation search around the offset the path predicts, and all tiles are placed by one least-squares fit.
+        Needs every tile resident on this registrar's engine: a chunk of the pair-sharded form cannot be adjusted on its own."""
+        from .adjust import adjust_offsets
+        t = np.asarray(table_or_offsets, np.int64)
+        if t.ndim == 2 and t.shape[1] == RESULT_INTS:
+            if not bool(np.all(t[:, 0] == 1)):
+                raise ValueError("adjust: the table holds a pair that was not registered; adjust each segment (split_segments) on its own")
+            t = t[:, 1:3]
+        return adjust_offsets(self.eng, handles, shapes, t.reshape(-1, 2), radius, threshold, min_pixels)
+
     # -- pair-sharded ---------------------------------------------------------------------------------------------------
     BLIND_START_COST = 3.0     # a chunk entered with an unknown direction tries four first candidates instead of one
 

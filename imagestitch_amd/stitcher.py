@@ -127,6 +127,8 @@ class Stitcher(Utility.Method):
             self.releaseTiles()                     # an operator that raises must not leave the pair's tiles in HBM
             raise
         self.releaseTiles()
+        if self.globalAdjust != "none" and batched is None:
+            offsetList = self._globalAdjust(fileList[:len(offsetList) + 1], offsetList)
         endTime = time.time()
         self.printAndWrite("The time of registering is " + str(endTime - startTime) + "s")
         self.printAndWrite("start stitching")
@@ -260,6 +262,13 @@ class Stitcher(Utility.Method):
                 # (what this path taught, incl. "nothing": a memory that mispredicted twice in a row is dropped, GridRegistrar._learn)
                 self._pathMemory, self._pathSuspect = reg.path_memory, reg.path_suspect
                 self._pathMemoryDropped = had_memory and reg.path_memory is None
+            adjusted = None
+            if self.globalAdjust != "none":                  # while the registration planes are still resident (finish releases them)
+                n_ok = 0
+                while n_ok < len(table) and table[n_ok][0]:
+                    n_ok += 1
+                voted = [[int(table[k][1]), int(table[k][2])] for k in range(n_ok)]
+                adjusted = self._globalAdjust(fileList[:n_ok + 1], voted, handles[:n_ok + 1], shapes[:n_ok + 1], log=False)
         except BaseException:
             job.failed = True
             raise
@@ -277,7 +286,42 @@ class Stitcher(Utility.Method):
             self.printAndWrite("  The offset of stitching: dx is " + str(int(row[1])) + " dy is " + str(int(row[2])))
             offsetList.append([int(row[1]), int(row[2])])
             endfileIndex = k + 1
+        if adjusted is not None and adjusted[1] is not None:
+            self.printAndWrite(adjusted[1])
+            offsetList = adjusted[0]
         return (status, endfileIndex, offsetList, describtion)
+
+    def _globalAdjust(self, fileList, offsetList, handles=None, shapes=None, log=True):
+        """globalAdjust = "ncc" for one registered segment (adjust.adjust_offsets): the adjusted offsetList, or the list as it is for a
+        segment of fewer than 3 tiles or tiles of different sizes.  handles / shapes: the segment's resident gray tiles; without them the
+        files are decoded and uploaded for the call.  log=False returns (offsetList, the line to log or None) instead of logging."""
+        from .adjust import adjust_offsets
+        if self.globalAdjust != "ncc":
+            raise ValueError("globalAdjust must be 'none' or 'ncc'")
+        line, own = None, []
+        if len(offsetList) >= 2:
+            try:
+                if handles is None:
+                    shapes = []
+                    for f in fileList:
+                        img = _imread(f, False)
+                        shapes.append(img.shape[:2])
+                        own.append(self.engine.tile_upload(img))
+                    handles = own
+                if any(tuple(s[:2]) != tuple(shapes[0][:2]) for s in shapes):
+                    line = "  The tiles are of different sizes: the offsetList is not adjusted"
+                else:
+                    offsetList, self.adjustReport = adjust_offsets(self.engine, handles, [tuple(s[:2]) for s in shapes], offsetList, self.adjustRadius,
+                                                                   self.adjustThreshold, self.adjustMinPixels)
+                    line = "  The adjusted offsetList is " + str(offsetList)
+            finally:
+                for h in own:
+                    self.engine.tile_free(h)
+        if not log:
+            return offsetList, line
+        if line is not None:
+            self.printAndWrite(line)
+        return offsetList
 
     def _fullImageTable(self, handles):
         """calculateOffsetForFeatureSearch (Stitcher.py:260-304) over consecutive resident tiles, batched: every tile is described once

@@ -128,6 +128,19 @@ class Method():
     verifyThreshold = 0.5
     verifyMinPixels = 4096
 
+    # ---- global placement (no reference counterpart; adjust.py, tests/ncc_search_ref.py): "ncc" also measures the offsets of side
+    # neighbours ACROSS the shooting path -- the same statistic as offsetVerify, searched over a window of +-adjustRadius px around the
+    # offset the path predicts -- and places all tiles of a segment by one least-squares fit before the mosaic is laid out.  An edge counts
+    # when its best score reaches adjustThreshold and the peak lies inside the window.  The threshold is the verifier's (DESIGN.md section
+    # 3): tests/golden holds STRIPS of the real tiles only, no whole tiles, so the ranges measured there stand -- true 0.844 .. 0.995,
+    # false -0.105 .. 0.026 -- and whole tiles were measured on the three synthetic grids of tests/adjust_cases.py (36 edges): at the true
+    # offset 0.9968 .. 0.9981; the BEST score of a 9 x 9 window that does not hold it (143 windows centred 29 .. 40 px off, >= 4096 shared
+    # pixels) -0.108 .. 0.276 -- a maximum over 81 candidates, hence higher than a single false vote, and still far below 0.5.
+    globalAdjust = "none"       # "none" or "ncc"
+    adjustRadius = 4            # 1..16
+    adjustThreshold = 0.5
+    adjustMinPixels = 4096
+
     # ---- enhancement (ImageUtility.py:46-50; CLAHE/equalizeHist are out of the hot-path scope) ----
     isEnhance = False
     isClahe = False

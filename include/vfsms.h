@@ -259,6 +259,19 @@ int vfsms_consensus_offset(vfsms_ctx *ctx, const float *kpsA, int nA, const floa
 int vfsms_verify_ncc(vfsms_ctx *ctx, const uint8_t *a, int a_stride, const uint8_t *b, int b_stride, int h, int w,
                      int dx, int dy, int min_pixels, int64_t *out8);
 
+/* The same statistic SEARCHED over a window of offsets, for n pairs of resident single-channel tiles (Method.globalAdjust = "ncc"; no
+ * reference counterpart, the specification is tests/ncc_search_ref.py and the device equals it bit for bit).  A job names two whole tiles
+ * of ONE shape and a predicted offset: tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy) -- for consecutive tiles of a path
+ * exactly the entry of offsetList.  Every candidate (dx + i, dy + j), i, j in [-radius, radius], is scored as vfsms_verify_ncc scores
+ * one; an empty overlap or fewer than min_pixels (>= 0) shared pixels score 0.  best4: int32[n][4] = {i, j, floor(score *
+ * VFSMS_VERIFY_FIXED_ONE + 0.5), shared pixels} of the candidate with the largest double score, ties to the smallest i * i + j * j, then
+ * the smallest i, then the smallest j (a flat pair gives (0, 0)); surface (may be NULL): int32[n][2 radius + 1][2 radius + 1], the
+ * fixed-point score of candidate (i, j) at [i + radius][j + radius].  One launch sequence for all jobs.  VFSMS_ERR_BAD_ARG: tiles of
+ * different shapes in a job, a colour tile, an unknown handle, a radius outside 1..16.                                              */
+typedef struct { int64_t tile_a, tile_b; int32_t dx, dy; } vfsms_ncc_job;
+int vfsms_ncc_search_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int radius, int min_pixels,
+                           int32_t *best4, int32_t *surface);
+
 /* cv2.phaseCorrelate(np.float64(a), np.float64(b)) (Stitcher.py:230): out3 = {x, y, response}     */
 int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
                              int stride_a, int stride_b, double *out3);
