@@ -836,6 +836,13 @@ class Engine:
         return out
 
     # -- canvas ----------------------------------------------------------------------------------------------------
+    # How a tile goes onto the canvas: fuseMethod -> the `mode` of a geometry row (vfsms_canvas_mode in include/vfsms.h; 5 is not a mode).
+    # The per-tile calls keep their older arguments: `method` 0..3 of canvas_fuse_tile*, `mode` 0..2 of canvas_blend_tile*.
+    CANVAS_MODES = {"notFuse": -1, "fadeInAndFadeOut": 0, "trigonometric": 1, "average": 2, "maximum": 3, "minimum": 4,
+                    "multiBandBlending": 6, "optimalSeamLine": 7}
+    CANVAS_FUSE_METHODS = {0: 0, 1: 1, 6: 2, 7: 3}       # row mode -> method
+    CANVAS_BLEND_MODES = {2: 0, 3: 1, 4: 2}              # row mode -> blend mode
+
     def canvas_create(self, rows, cols, ch):
         h = C.c_int64()
         self._check(self.lib.vfsms_canvas_create(self.ctx, int(rows), int(cols), int(ch), C.byref(h)))
@@ -885,9 +892,8 @@ class Engine:
         return info
 
     def canvas_assemble_resident(self, handle, tile_handles, geom):
-        """The mosaic walk over resident tiles as one call.  geom: int32 [n][9] = y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode
-        (mode -1 paste, 0 fadeInAndFadeOut, 1 trigonometric, 2 / 3 / 4 average / maximum / minimum, 6 multiBandBlending, 7 optimalSeamLine).
-        Enqueue only: geometry errors surface in canvas_download."""
+        """The mosaic walk over resident tiles as one call.  geom: int32 [n][9] = y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode (mode: a value of
+        CANVAS_MODES; Stitcher._placements builds the rows).  Enqueue only: geometry errors surface in canvas_download."""
         th = np.ascontiguousarray(tile_handles, np.int64)
         g = np.ascontiguousarray(geom, np.int32).reshape(-1, 9)
         if len(th) != len(g):

@@ -1795,61 +1795,131 @@ extern "C" int vfsms_canvas_create(vfsms_ctx *ctx, int rows, int cols, int ch, i
     ctx->canvases[*handle] = cv;
     return VFSMS_OK;
 }
+// the canvas behind a handle; `who`: the entry point, for the message
+static int canvas_find(vfsms_ctx *ctx, const char *who, int64_t canvas, CanvasRec **cv)
+{
+    auto it = ctx->canvases.find(canvas);
+    if (it == ctx->canvases.end()) { vfsms_set_error("%s: unknown canvas handle", who); return VFSMS_ERR_BAD_ARG; }
+    *cv = &it->second;
+    return VFSMS_OK;
+}
 extern "C" int vfsms_canvas_free(vfsms_ctx *ctx, int64_t handle)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->canvases.find(handle);
-    if (it == ctx->canvases.end()) { vfsms_set_error("canvas_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, "canvas_free", handle, &cv));
     if (ctx->has_spare_canvas) {                               // one spare at a time: the older one goes back to the device
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         CanvasRec &o = ctx->spare_canvas;
         HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch));
     }
-    ctx->spare_canvas = it->second; ctx->has_spare_canvas = true;      // kept for a canvas of the same size (stream order makes the reuse safe)
-    ctx->canvases.erase(it);
+    ctx->spare_canvas = *cv; ctx->has_spare_canvas = true;      // kept for a canvas of the same size (stream order makes the reuse safe)
+    ctx->canvases.erase(handle);
     return VFSMS_OK;
 }
-static int canvas_tile_args(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, int h, int w, int y0, int x0, CanvasRec **cv)
+
+// ---- one tile onto the canvas: every entry point below is translate -> check -> place (Placement: common.h) ---------------------------------
+// the `method` of vfsms_canvas_fuse_tile*_m and the `mode` of vfsms_canvas_blend_tile* as the one mode code (vfsms_canvas_mode)
+static int canvas_mode_of_method(int method, int *mode)
 {
-    auto it = ctx->canvases.find(canvas);
-    if (it == ctx->canvases.end()) { vfsms_set_error("canvas: unknown handle"); return VFSMS_ERR_BAD_ARG; }
-    *cv = &it->second;
-    if (!tile || h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 + h > (*cv)->rows || x0 + w > (*cv)->cols) {
-        vfsms_set_error("canvas: tile rectangle outside the canvas"); return VFSMS_ERR_BAD_ARG;
+    static const int modes[4] = {VFSMS_CANVAS_FADE, VFSMS_CANVAS_TRIG, VFSMS_CANVAS_MULTIBAND, VFSMS_CANVAS_SEAMLINE};
+    if (method < 0 || method > 3) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric), 2 (multiBandBlending) or 3 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
+    *mode = modes[method];
+    return VFSMS_OK;
+}
+static int canvas_mode_of_blend(int blend, int *mode)
+{
+    static const int modes[3] = {VFSMS_CANVAS_AVERAGE, VFSMS_CANVAS_MAXIMUM, VFSMS_CANVAS_MINIMUM};
+    if (blend < 0 || blend > 2) { vfsms_set_error("canvas_blend_tile: mode must be 0 (average), 1 (maximum) or 2 (minimum)"); return VFSMS_ERR_BAD_ARG; }
+    *mode = modes[blend];
+    return VFSMS_OK;
+}
+static bool canvas_mode_fuses(int mode)        // the fade family: statistics + operator (canvas_fuse_device), with ramps in the arena's budget
+{
+    return mode == VFSMS_CANVAS_FADE || mode == VFSMS_CANVAS_TRIG || mode == VFSMS_CANVAS_MULTIBAND || mode == VFSMS_CANVAS_SEAMLINE;
+}
+// the only place a placement is judged: mode, tile rectangle inside the canvas, ROI inside the tile rectangle
+static int canvas_check(const char *who, const CanvasRec *cv, const Placement &p)
+{
+    if (p.mode != VFSMS_CANVAS_PASTE && !canvas_mode_fuses(p.mode) &&
+        p.mode != VFSMS_CANVAS_AVERAGE && p.mode != VFSMS_CANVAS_MAXIMUM && p.mode != VFSMS_CANVAS_MINIMUM) {
+        vfsms_set_error("%s: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum), 6 (multiBandBlending), 7 (optimalSeamLine)", who);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    if (p.h <= 0 || p.w <= 0 || p.y0 < 0 || p.x0 < 0 || p.y0 + p.h > cv->rows || p.x0 + p.w > cv->cols) {
+        vfsms_set_error("%s: tile rectangle outside the canvas", who); return VFSMS_ERR_BAD_ARG;
+    }
+    if (p.mode != VFSMS_CANVAS_PASTE && p.ry1 > p.ry0 && p.rx1 > p.rx0 &&
+        (p.ry0 < p.y0 || p.rx0 < p.x0 || p.ry1 > p.y0 + p.h || p.rx1 > p.x0 + p.w)) {
+        vfsms_set_error("%s: fuse ROI must lie inside the tile rectangle", who); return VFSMS_ERR_BAD_ARG;
     }
     return VFSMS_OK;
 }
+// the ramps a fuse may put into the arena, ahead of its launches (and behind a host tile's upload)
+static size_t canvas_arena_bytes(const Placement &p)
+{
+    return (canvas_mode_fuses(p.mode) ? sizeof(float) * 8 * ((size_t)p.r() + p.c()) : 0) + 65536;
+}
+// a checked placement -> its launcher.  Enqueue only, unless a fuse is asked for `info`
+static int canvas_place(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, int32_t *info)
+{
+    if (p.mode == VFSMS_CANVAS_PASTE) return canvas_paste_device(ctx, cv, d_tile, p);
+    if (canvas_mode_fuses(p.mode)) return canvas_fuse_device(ctx, cv, d_tile, p, info);
+    return canvas_blend_device(ctx, cv, d_tile, p);
+}
+// a tile from host memory: uploaded into the arena, placed, and the call returns when the canvas holds it
+static int canvas_place_host(vfsms_ctx *ctx, const char *who, int64_t canvas, const uint8_t *tile, const Placement &p, int32_t *info)
+{
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    if (!tile) { vfsms_set_error("%s: null tile", who); return VFSMS_ERR_BAD_ARG; }
+    TRY(canvas_check(who, cv, p));
+    const size_t nb = (size_t)p.h * p.w * cv->ch;
+    TRY(ctx_arena_reserve(ctx, nb + canvas_arena_bytes(p)));
+    uint8_t *d_tile;
+    TRY(upload_array(ctx, tile, nb, &d_tile));
+    TRY(canvas_place(ctx, cv, d_tile, p, info));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+// a resident tile of the canvas's channel count: known, handed over (tile_ready) and densely packed; its shape completes the placement
+static int canvas_resident_tile(vfsms_ctx *ctx, const char *who, const CanvasRec *cv, int64_t tile, Placement *p, const uint8_t **d_tile)
+{
+    auto jt = ctx->tiles.find(tile);
+    if (jt == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", who); return VFSMS_ERR_BAD_ARG; }
+    TileRec &tr = jt->second;
+    TRY(tile_ready(ctx, tr));
+    if (cv->ch != tr.ch || tr.stride != tr.w * tr.ch) {
+        vfsms_set_error("%s: a resident tile must have the canvas's channel count and be densely packed (stride == w * ch)", who); return VFSMS_ERR_BAD_ARG;
+    }
+    p->h = tr.h; p->w = tr.w; *d_tile = tr.ptr;
+    return VFSMS_OK;
+}
+// enqueued only (resident tiles need no host synchronisation; stream order keeps the canvas consistent), unless `info` is read back
+static int canvas_place_resident(vfsms_ctx *ctx, const char *who, int64_t canvas, int64_t tile, Placement p, int32_t *info)
+{
+    CanvasRec *cv; const uint8_t *d_tile;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    TRY(canvas_resident_tile(ctx, who, cv, tile, &p, &d_tile));
+    TRY(canvas_check(who, cv, p));
+    if (canvas_mode_fuses(p.mode)) TRY(ctx_arena_reserve(ctx, canvas_arena_bytes(p)));
+    TRY(canvas_place(ctx, cv, d_tile, p, info));
+    if (info) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 extern "C" int vfsms_canvas_paste(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, int h, int w, int y0, int x0)
 {
     CTX_ENTER(ctx);
-    CanvasRec *cv;
-    TRY(canvas_tile_args(ctx, canvas, tile, h, w, y0, x0, &cv));
-    const size_t nb = (size_t)h * w * cv->ch;
-    TRY(ctx_arena_reserve(ctx, nb + 65536));
-    uint8_t *d_tile;
-    TRY(upload_array(ctx, tile, nb, &d_tile));
-    TRY(canvas_paste_device(ctx, cv, d_tile, h, w, y0, x0));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    return canvas_place_host(ctx, "canvas_paste", canvas, tile, Placement{h, w, y0, x0, 0, 0, 0, 0, 0, 0, VFSMS_CANVAS_PASTE}, nullptr);
 }
 extern "C" int vfsms_canvas_fuse_tile_m(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, int h, int w,
                                         int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 3) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric), 2 (multiBandBlending) or 3 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
-    CanvasRec *cv;
-    TRY(canvas_tile_args(ctx, canvas, tile, h, w, y0, x0, &cv));
-    if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + h || rx1 > x0 + w)) {
-        vfsms_set_error("canvas_fuse_tile: fuse ROI must lie inside the tile rectangle"); return VFSMS_ERR_BAD_ARG;
-    }
-    const size_t nb = (size_t)h * w * cv->ch;
-    const int r = std::max(ry1 - ry0, 0), c = std::max(rx1 - rx0, 0);
-    TRY(ctx_arena_reserve(ctx, nb + sizeof(float) * 8 * ((size_t)r + c) + 65536));
-    uint8_t *d_tile;
-    TRY(upload_array(ctx, tile, nb, &d_tile));
-    TRY(canvas_fuse_device(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, ry1, rx1, dx, dy, info, method));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
+    int mode;
+    TRY(canvas_mode_of_method(method, &mode));
+    return canvas_place_host(ctx, "canvas_fuse_tile", canvas, tile, Placement{h, w, y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode}, info);
 }
 extern "C" int vfsms_canvas_fuse_tile(vfsms_ctx *ctx, int64_t canvas, const uint8_t *tile, int h, int w,
                                       int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info)
@@ -1860,164 +1930,114 @@ extern "C" int vfsms_canvas_blend_tile(vfsms_ctx *ctx, int64_t canvas, const uin
                                        int y0, int x0, int ry0, int rx0, int ry1, int rx1, int mode)
 {
     CTX_ENTER(ctx);
-    CanvasRec *cv;
-    TRY(canvas_tile_args(ctx, canvas, tile, h, w, y0, x0, &cv));
-    if (mode < 0 || mode > 2) { vfsms_set_error("canvas_blend_tile: mode must be 0 (average), 1 (maximum) or 2 (minimum)"); return VFSMS_ERR_BAD_ARG; }
-    if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + h || rx1 > x0 + w)) {
-        vfsms_set_error("canvas_blend_tile: fuse ROI must lie inside the tile rectangle"); return VFSMS_ERR_BAD_ARG;
-    }
-    const size_t nb = (size_t)h * w * cv->ch;
-    TRY(ctx_arena_reserve(ctx, nb + 65536));
-    uint8_t *d_tile;
-    TRY(upload_array(ctx, tile, nb, &d_tile));
-    TRY(canvas_blend_device(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, ry1, rx1, mode));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VFSMS_OK;
-}
-static int canvas_resident_args(vfsms_ctx *ctx, int64_t canvas, int64_t tile, int y0, int x0, CanvasRec **cv, TileRec **tr)
-{
-    auto it = ctx->canvases.find(canvas);
-    auto jt = ctx->tiles.find(tile);
-    if (it == ctx->canvases.end() || jt == ctx->tiles.end()) { vfsms_set_error("canvas: unknown canvas or tile handle"); return VFSMS_ERR_BAD_ARG; }
-    *cv = &it->second; *tr = &jt->second;
-    TRY(tile_ready(ctx, jt->second));
-    if ((*cv)->ch != (*tr)->ch || (*tr)->stride != (*tr)->w * (*tr)->ch) {
-        vfsms_set_error("canvas: a resident tile must have the canvas's channel count and be densely packed (stride == w * ch)"); return VFSMS_ERR_BAD_ARG;
-    }
-    if (y0 < 0 || x0 < 0 || y0 + (*tr)->h > (*cv)->rows || x0 + (*tr)->w > (*cv)->cols) {
-        vfsms_set_error("canvas: tile rectangle outside the canvas"); return VFSMS_ERR_BAD_ARG;
-    }
-    return VFSMS_OK;
+    TRY(canvas_mode_of_blend(mode, &mode));
+    return canvas_place_host(ctx, "canvas_blend_tile", canvas, tile, Placement{h, w, y0, x0, ry0, rx0, ry1, rx1, 0, 0, mode}, nullptr);
 }
 extern "C" int vfsms_canvas_paste_tile(vfsms_ctx *ctx, int64_t canvas, int64_t tile, int y0, int x0)
 {
     CTX_ENTER(ctx);
-    CanvasRec *cv; TileRec *tr;
-    TRY(canvas_resident_args(ctx, canvas, tile, y0, x0, &cv, &tr));
-    TRY(canvas_paste_device(ctx, cv, tr->ptr, tr->h, tr->w, y0, x0));
-    return VFSMS_OK;                                       // enqueued only: resident tiles need no host synchronisation
+    return canvas_place_resident(ctx, "canvas_paste_tile", canvas, tile, Placement{0, 0, y0, x0, 0, 0, 0, 0, 0, 0, VFSMS_CANVAS_PASTE}, nullptr);
 }
 extern "C" int vfsms_canvas_fuse_tile_resident_m(vfsms_ctx *ctx, int64_t canvas, int64_t tile,
                                                  int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int method, int32_t *info)
 {
     CTX_ENTER(ctx);
-    if (method < 0 || method > 3) { vfsms_set_error("canvas_fuse_tile: method must be 0 (fadeInAndFadeOut), 1 (trigonometric), 2 (multiBandBlending) or 3 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
-    CanvasRec *cv; TileRec *tr;
-    TRY(canvas_resident_args(ctx, canvas, tile, y0, x0, &cv, &tr));
-    const int h = tr->h, w = tr->w;
-    if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + h || rx1 > x0 + w)) {
-        vfsms_set_error("canvas_fuse_tile: fuse ROI must lie inside the tile rectangle"); return VFSMS_ERR_BAD_ARG;
-    }
-    const int r = std::max(ry1 - ry0, 0), c = std::max(rx1 - rx0, 0);
-    TRY(ctx_arena_reserve(ctx, sizeof(float) * 8 * ((size_t)r + c) + 65536));
-    TRY(canvas_fuse_device(ctx, cv, tr->ptr, h, w, y0, x0, ry0, rx0, ry1, rx1, dx, dy, info, method));
-    if (info) HIP_TRY(hipStreamSynchronize(ctx->stream));   // without a readback the call only enqueues (stream order keeps the canvas consistent)
-    return VFSMS_OK;
+    int mode;
+    TRY(canvas_mode_of_method(method, &mode));
+    return canvas_place_resident(ctx, "canvas_fuse_tile", canvas, tile, Placement{0, 0, y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode}, info);
 }
-// fuseMethod "average" / "maximum" / "minimum" (mode 0 / 1 / 2) with a resident tile; enqueue only
+// fuseMethod "average" / "maximum" / "minimum" (mode 0 / 1 / 2) with a resident tile
 extern "C" int vfsms_canvas_blend_tile_resident(vfsms_ctx *ctx, int64_t canvas, int64_t tile,
                                                 int y0, int x0, int ry0, int rx0, int ry1, int rx1, int mode)
 {
     CTX_ENTER(ctx);
-    if (mode < 0 || mode > 2) { vfsms_set_error("canvas_blend_tile: mode must be 0 (average), 1 (maximum) or 2 (minimum)"); return VFSMS_ERR_BAD_ARG; }
-    CanvasRec *cv; TileRec *tr;
-    TRY(canvas_resident_args(ctx, canvas, tile, y0, x0, &cv, &tr));
-    if (ry1 > ry0 && rx1 > rx0 && (ry0 < y0 || rx0 < x0 || ry1 > y0 + tr->h || rx1 > x0 + tr->w)) {
-        vfsms_set_error("canvas_blend_tile: fuse ROI must lie inside the tile rectangle"); return VFSMS_ERR_BAD_ARG;
-    }
-    TRY(canvas_blend_device(ctx, cv, tr->ptr, tr->h, tr->w, y0, x0, ry0, rx0, ry1, rx1, mode));
-    return VFSMS_OK;
+    TRY(canvas_mode_of_blend(mode, &mode));
+    return canvas_place_resident(ctx, "canvas_blend_tile", canvas, tile, Placement{0, 0, y0, x0, ry0, rx0, ry1, rx1, 0, 0, mode}, nullptr);
 }
 extern "C" int vfsms_canvas_fuse_tile_resident(vfsms_ctx *ctx, int64_t canvas, int64_t tile,
                                                int y0, int x0, int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info)
 {
     return vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tile, y0, x0, ry0, rx0, ry1, rx1, dx, dy, 0, info);
 }
-// The whole mosaic walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over resident tiles as ONE call: per tile nine ints
-// [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode] with mode -1 = paste (the first tile, notFuse), 0 = fadeInAndFadeOut, 1 = trigonometric,
-// 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending, 7 = optimalSeamLine (5 is not a mode).
+// The whole mosaic walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over resident tiles as ONE call: per tile the nine ints
+// [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode] of a Placement, mode a vfsms_canvas_mode.
 // Enqueue only (one library call per mosaic instead of one per tile; the device chain stays two launches per tile); geometry errors are latched
 // in the canvas and reported by the download, as with vfsms_canvas_fuse_tile_resident(info = NULL).
 extern "C" int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, int n, const int64_t *tiles, const int32_t *geom)
 {
     CTX_ENTER(ctx);
-    if (n < 0 || (n > 0 && (!tiles || !geom))) { vfsms_set_error("canvas_assemble_resident: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    const char *who = "canvas_assemble_resident";
+    if (n < 0 || (n > 0 && (!tiles || !geom))) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    struct Row { Placement p; const uint8_t *d_tile; };
+    std::vector<Row> rows(n);
     for (int i = 0; i < n; i++) {                       // everything is checked before anything is enqueued
         const int32_t *g = geom + 9 * (size_t)i;
-        if (g[8] < -1 || g[8] > 7 || g[8] == 5) { vfsms_set_error("canvas_assemble_resident: mode must be -1 (paste), 0 (fadeInAndFadeOut), 1 (trigonometric), 2 / 3 / 4 (average / maximum / minimum), 6 (multiBandBlending), 7 (optimalSeamLine)"); return VFSMS_ERR_BAD_ARG; }
-        CanvasRec *cv; TileRec *tr;
-        TRY(canvas_resident_args(ctx, canvas, tiles[i], g[0], g[1], &cv, &tr));
-        if (g[8] >= 0 && g[4] > g[2] && g[5] > g[3] && (g[2] < g[0] || g[3] < g[1] || g[4] > g[0] + tr->h || g[5] > g[1] + tr->w)) {
-            vfsms_set_error("canvas_assemble_resident: fuse ROI must lie inside the tile rectangle"); return VFSMS_ERR_BAD_ARG;
-        }
+        rows[i].p = Placement{0, 0, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8]};
+        TRY(canvas_resident_tile(ctx, who, cv, tiles[i], &rows[i].p, &rows[i].d_tile));
+        TRY(canvas_check(who, cv, rows[i].p));
     }
-    for (int i = 0; i < n; i++) {
-        const int32_t *g = geom + 9 * (size_t)i;
-        if (g[8] < 0) TRY(vfsms_canvas_paste_tile(ctx, canvas, tiles[i], g[0], g[1]));
-        else if (g[8] >= 6) TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8] - 4, nullptr));
-        else if (g[8] >= 2) TRY(vfsms_canvas_blend_tile_resident(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[8] - 2));
-        else TRY(vfsms_canvas_fuse_tile_resident_m(ctx, canvas, tiles[i], g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], nullptr));
+    for (const Row &row : rows) {
+        if (canvas_mode_fuses(row.p.mode)) TRY(ctx_arena_reserve(ctx, canvas_arena_bytes(row.p)));
+        TRY(canvas_place(ctx, cv, row.d_tile, row.p, nullptr));
     }
     return VFSMS_OK;
 }
-// the level count of the canvas's multiBandBlending fuses (method 2 / geom mode 6); a new canvas starts at 4
+// the level count of the canvas's multiBandBlending fuses; a new canvas starts at 4
 extern "C" int vfsms_canvas_set_multiband_levels(vfsms_ctx *ctx, int64_t canvas, int levels)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->canvases.find(canvas);
-    if (it == ctx->canvases.end()) { vfsms_set_error("canvas_set_multiband_levels: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, "canvas_set_multiband_levels", canvas, &cv));
     if (levels < 1 || levels > VFSMS_MB_MAX_LEVELS) { vfsms_set_error("canvas_set_multiband_levels: levels must be 1..%d", VFSMS_MB_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
-    it->second.mb_levels = levels;
+    cv->mb_levels = levels;
     return VFSMS_OK;
 }
-// how the canvas's optimalSeamLine fuses (method 3 / geom mode 7) merge the two sides of the seam: 0 none (every pixel from one input),
+// how the canvas's optimalSeamLine fuses merge the two sides of the seam: 0 none (every pixel from one input),
 // 1 multiBandBlending with the canvas's level count; a new canvas starts at 0
 extern "C" int vfsms_canvas_set_seam_blend(vfsms_ctx *ctx, int64_t canvas, int blend)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->canvases.find(canvas);
-    if (it == ctx->canvases.end()) { vfsms_set_error("canvas_set_seam_blend: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, "canvas_set_seam_blend", canvas, &cv));
     if (blend < 0 || blend > 1) { vfsms_set_error("canvas_set_seam_blend: blend must be 0 (none) or 1 (multiBandBlending)"); return VFSMS_ERR_BAD_ARG; }
-    it->second.seam_blend = blend;
+    cv->seam_blend = blend;
     return VFSMS_OK;
 }
-extern "C" int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out)
+// rows [row0, row0 + nrows) of the canvas to the host, with the sticky error flag of the fuses that ran without a readback.  Never-written
+// pixels are still 0 (the canvas is zero-initialised), exactly Stitcher.py:485
+static int canvas_read_rows(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, uint8_t *out)
 {
-    CTX_ENTER(ctx);
-    auto it = ctx->canvases.find(canvas);
-    if (it == ctx->canvases.end() || !out) { vfsms_set_error("canvas_download: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    const CanvasRec &cv = it->second;
-    // never-written pixels are still 0 (the canvas is zero-initialised), exactly Stitcher.py:485
+    const size_t pitch = (size_t)cv->cols * cv->ch;
     int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, cv.d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, cv.pix, (size_t)cv.rows * cv.cols * cv.ch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&err, cv->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, cv->pix + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (err) {
         vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
         return VFSMS_ERR_BAD_ARG;
     }
     return VFSMS_OK;
+}
+extern "C" int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out)
+{
+    CTX_ENTER(ctx);
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, "canvas_download", canvas, &cv));
+    if (!out) { vfsms_set_error("canvas_download: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    return canvas_read_rows(ctx, cv, 0, cv->rows, out);
 }
 
 // rows [row0, row0 + nrows) of the canvas: a multi-GB mosaic leaves the device band by band (streamed write-out, Stitcher.py:174-179)
 extern "C" int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, uint8_t *out)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->canvases.find(canvas);
-    if (it == ctx->canvases.end() || !out || row0 < 0 || nrows <= 0 || row0 + nrows > it->second.rows) {
-        vfsms_set_error("canvas_download_rows: bad arguments"); return VFSMS_ERR_BAD_ARG;
-    }
-    const CanvasRec &cv = it->second;
-    const size_t pitch = (size_t)cv.cols * cv.ch;
-    int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, cv.d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, cv.pix + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (err) {
-        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
-        return VFSMS_ERR_BAD_ARG;
-    }
-    return VFSMS_OK;
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, "canvas_download_rows", canvas, &cv));
+    if (!out || row0 < 0 || nrows <= 0 || row0 + nrows > cv->rows) { vfsms_set_error("canvas_download_rows: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    return canvas_read_rows(ctx, cv, row0, nrows, out);
 }
 
 // ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------

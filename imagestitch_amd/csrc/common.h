@@ -305,24 +305,29 @@ int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);  
 size_t enhance_scratch_bytes(int h, int w, int mode, int tiles);
 int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles);
 int launch_enhance(vfsms_ctx *ctx, const EnhJob *d_jobs, const EnhJob *h_jobs, int n, int mode, double clip_limit, int tiles);
-// fuse_kernels.hip
-int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
-                       int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info, int method = 0);   // method 0 fadeInAndFadeOut, 1 trigonometric, 2 multiBandBlending
-int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
-                        int ry0, int rx0, int ry1, int rx1, int mode);
-int canvas_paste_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0);
+// fuse_kernels.hip.  Placement: how one tile goes onto a canvas -- the nine ints of a geometry row of vfsms_canvas_assemble_resident plus
+// the tile's shape.  The tile rectangle is h x w at canvas (y0, x0); the fuse ROI is [ry0, ry1) x [rx0, rx1) in canvas coordinates (empty: a
+// plain paste); (dx, dy) is the tile's offset from its predecessor; mode is a vfsms_canvas_mode.  api.hip checks a record once (canvas_check)
+// and the launchers below trust it.
+struct Placement {
+    int h, w, y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode;
+    int r() const { return ry1 > ry0 ? ry1 - ry0 : 0; }
+    int c() const { return rx1 > rx0 ? rx1 - rx0 : 0; }
+};
+int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, int32_t *info);   // FADE, TRIG, MULTIBAND, SEAMLINE
+int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p);                 // AVERAGE, MAXIMUM, MINIMUM
+int canvas_paste_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p);
 size_t canvas_scratch_bytes(int rows, int cols);
 int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv);
 // multiband_kernels.hip (SeamGeom: fuse_geom.h)
 #define VFSMS_MB_MAX_LEVELS 8
 struct SeamGeom;
-int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
-                    const SeamGeom &G, int levels);
+int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, const SeamGeom &G, int levels);
 int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, const SeamGeom &G, int levels, uint8_t *d_out);
 // seam_kernels.hip: fuseMethod "optimalSeamLine".  hostkind 1 / 2: a strip the host decided on, 0: geometry from mode[] on the device; wmax:
 // an upper bound of a seam's positions; blend 0 none, 1 multiBandBlending with `levels`
-int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
-                     int dx, int dy, int hostkind, const int *mode, int wmax, int blend, int levels);
+int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, int hostkind, const int *mode, int wmax,
+                     int blend, int levels);
 int seam_fuse_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy, const int *mode,
                   int blend, int levels, uint8_t *d_out, int32_t *d_seam);
 // shading_kernels.hip: Method.shadingCorrection.  Tiles as (pointer, row stride in bytes); h rows of w * ch bytes

@@ -42,6 +42,10 @@ struct I64View {
     __device__ long long b_val(int i, int j, int k) const { return B[((size_t)i * c + j) * ch + k]; }
 };
 
+// a tile rectangle on its canvas as the paste / blend kernels take it: canvas planes, tile (th x tw at canvas (y0, x0)) and the fuse ROI
+// (r x c at canvas (ry0, rx0)); tile_on_canvas builds it from a Placement
+struct TileOnCanvas { uint8_t *pix, *mask; int ccols, ch; const uint8_t *tile; int th, tw, y0, x0, ry0, rx0, r, c; };
+
 typedef uint32_t u32u1 __attribute__((aligned(1)));
 
 // the blend: writes the whole tile rectangle (outside the ROI: plain paste) and marks it valid
@@ -82,12 +86,13 @@ __device__ __forceinline__ uint8_t trig_px(const TrigGeom &G, bool corner, int i
     return (uint8_t)res;
 }
 // (bx, by): the block of the tile this workgroup blends -- blockIdx for the per-tile launch, a drawn index inside k_mosaic_walk
-__device__ __forceinline__ void fuse_apply_block(uint8_t *pix, uint8_t *mask, int ccols, int ch,
-                                                 const uint8_t *tile, int th, int tw, int y0, int x0,
-                                                 int ry0, int rx0, int r, int c, const int *mode,
+__device__ __forceinline__ void fuse_apply_block(const TileOnCanvas &T, const int *mode,
                                                  const float *wAr, const float *wAc, const float *wBr, const float *wBc, const TrigGeom &TG,
                                                  unsigned bx, unsigned by, int analytic = 0)
 {
+    uint8_t *const pix = T.pix, *const mask = T.mask;
+    const uint8_t *const tile = T.tile;
+    const int ccols = T.ccols, ch = T.ch, tw = T.tw, y0 = T.y0, x0 = T.x0, ry0 = T.ry0, rx0 = T.rx0, r = T.r, c = T.c;
     const int y = (int)by;
     const int cy = y0 + y;
     const int i = cy - ry0;
@@ -156,17 +161,17 @@ __device__ __forceinline__ void fuse_apply_block(uint8_t *pix, uint8_t *mask, in
     mask[co] = 1;
 }
 
-__global__ __launch_bounds__(256) void k_fuse_apply(uint8_t *pix, uint8_t *mask, int ccols, int ch,
-                                                    const uint8_t *tile, int th, int tw, int y0, int x0,
-                                                    int ry0, int rx0, int r, int c, const int *mode,
+__global__ __launch_bounds__(256) void k_fuse_apply(TileOnCanvas T, const int *mode,
                                                     const float *wAr, const float *wAc, const float *wBr, const float *wBc, TrigGeom TG, int analytic)
 {
-    fuse_apply_block(pix, mask, ccols, ch, tile, th, tw, y0, x0, ry0, rx0, r, c, mode, wAr, wAc, wBr, wBc, TG, blockIdx.x, blockIdx.y, analytic);
+    fuse_apply_block(T, mode, wAr, wAc, wBr, wBc, TG, blockIdx.x, blockIdx.y, analytic);
 }
 
-__device__ __forceinline__ void paste_block(uint8_t *pix, uint8_t *mask, int ccols, int ch,
-                                            const uint8_t *tile, int th, int tw, int y0, int x0, unsigned bx, unsigned by)
+__device__ __forceinline__ void paste_block(const TileOnCanvas &T, unsigned bx, unsigned by)
 {
+    uint8_t *const pix = T.pix, *const mask = T.mask;
+    const uint8_t *const tile = T.tile;
+    const int ccols = T.ccols, ch = T.ch, tw = T.tw, y0 = T.y0, x0 = T.x0;
     const int x = (int)(bx * 256 + threadIdx.x);
     const int y = (int)by;
     if (x >= tw) return;
@@ -174,10 +179,9 @@ __device__ __forceinline__ void paste_block(uint8_t *pix, uint8_t *mask, int cco
     for (int k = 0; k < ch; k++) pix[co * ch + k] = tile[((size_t)y * tw + x) * ch + k];
     mask[co] = 1;
 }
-__global__ __launch_bounds__(256) void k_paste(uint8_t *pix, uint8_t *mask, int ccols, int ch,
-                                               const uint8_t *tile, int th, int tw, int y0, int x0)
+__global__ __launch_bounds__(256) void k_paste(TileOnCanvas T)
 {
-    paste_block(pix, mask, ccols, ch, tile, th, tw, y0, x0, blockIdx.x, blockIdx.y);
+    paste_block(T, blockIdx.x, blockIdx.y);
 }
 
 // ---- int64 compatibility path (the reference's own array representation) -----------------------------
@@ -630,9 +634,11 @@ static int finish_weights(vfsms_ctx *ctx, const FuseScratch &S, int r, int c, in
 // average / maximum / minimum (ImageFusion.py:12-41) behind fuseImage's pre-processing (Stitcher.py:498-504): empty (-1) and zero
 // elements of A are filled from B, then zero elements of B from the updated A, element by element; outside the ROI the tile is
 // pasted.  mode: 0 average = uint8((A + B) / 2), 1 maximum, 2 minimum.
-__global__ __launch_bounds__(256) void k_fuse_simple(uint8_t *pix, uint8_t *mask, int ccols, int ch, const uint8_t *tile, int h, int w,
-                                                     int y0, int x0, int ry0, int rx0, int r, int c, int mode)
+__global__ __launch_bounds__(256) void k_fuse_simple(TileOnCanvas T, int mode)
 {
+    uint8_t *const pix = T.pix, *const mask = T.mask;
+    const uint8_t *const tile = T.tile;
+    const int ccols = T.ccols, ch = T.ch, h = T.th, w = T.tw, y0 = T.y0, x0 = T.x0, ry0 = T.ry0, rx0 = T.rx0, r = T.r, c = T.c;
     const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
     if (j >= w || i >= h) return;
     const int cy = y0 + i, cx = x0 + j;
@@ -659,9 +665,9 @@ __global__ __launch_bounds__(256) void k_fuse_simple(uint8_t *pix, uint8_t *mask
 // its corner branch (ImageFusion.py:201: count / size > 0.65); the strip branch then needs nothing else from the canvas -- its ramps are closed
 // forms of (row, col, dx, dy).  The host therefore counts the valid pixels of the ROI from the rectangle list (exact: coordinate compression
 // over the few rectangles that meet the ROI), and a strip tile is ONE launch (k_fuse_apply with analytic ramps) instead of statistics + blend.
-static void canvas_mark(CanvasRec *cv, int y0, int x0, int h, int w)
+static void canvas_mark(CanvasRec *cv, const Placement &p)
 {
-    const int32_t q[4] = {std::max(y0, 0), std::max(x0, 0), std::min(y0 + h, cv->rows), std::min(x0 + w, cv->cols)};
+    const int32_t q[4] = {std::max(p.y0, 0), std::max(p.x0, 0), std::min(p.y0 + p.h, cv->rows), std::min(p.x0 + p.w, cv->cols)};
     if (q[2] > q[0] && q[3] > q[1]) cv->placed.insert(cv->placed.end(), q, q + 4);
 }
 
@@ -684,125 +690,156 @@ static long long canvas_valid_area(const CanvasRec *cv, int ry0, int rx0, int ry
     return area;
 }
 
-int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
-                        int ry0, int rx0, int ry1, int rx1, int mode)
+static TileOnCanvas tile_on_canvas(const CanvasRec *cv, const uint8_t *d_tile, const Placement &p)
 {
-    const int r = ry1 - ry0 > 0 ? ry1 - ry0 : 0, c = rx1 - rx0 > 0 ? rx1 - rx0 : 0;
+    return TileOnCanvas{cv->pix, cv->mask, cv->cols, cv->ch, d_tile, p.h, p.w, p.y0, p.x0, p.ry0, p.rx0, p.r(), p.c()};
+}
+
+int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p)
+{
     ProfScope ps(ctx, "fuse");
-    hipLaunchKernelGGL(k_fuse_simple, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
-                       d_tile, h, w, y0, x0, ry0, rx0, r, c, mode);
+    hipLaunchKernelGGL(k_fuse_simple, dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, tile_on_canvas(cv, d_tile, p),
+                       p.mode - VFSMS_CANVAS_AVERAGE);            // the kernel's operator index: 0 average, 1 maximum, 2 minimum
     HIP_TRY(hipGetLastError());
-    canvas_mark(cv, y0, x0, h, w);
+    canvas_mark(cv, p);
     return VFSMS_OK;
 }
 
-int canvas_paste_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0)
+int canvas_paste_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p)
 {
-    hipLaunchKernelGGL(k_paste, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
-                       d_tile, h, w, y0, x0);
+    hipLaunchKernelGGL(k_paste, dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, tile_on_canvas(cv, d_tile, p));
     HIP_TRY(hipGetLastError());
-    canvas_mark(cv, y0, x0, h, w);
+    canvas_mark(cv, p);
     return VFSMS_OK;
 }
 
-int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0,
-                       int ry0, int rx0, int ry1, int rx1, int dx, int dy, int32_t *info, int method)
+// ---- the fade family on the canvas (FADE, TRIG, MULTIBAND, SEAMLINE) ------------------------------------------------------------------------
+// Where an operator's geometry comes from -- the `kind` tag SeamGeom and k_fuse_apply's `analytic` share (fuse_geom.h)
+enum FuseGeomKind {
+    GEOM_RAMPS = 0,        // ramp arrays + status ints of the statistics kernel (k_fuse_stats_weights)
+    GEOM_STRIP_COLS = 1,   // a strip the host decided on, ramps along the columns (col <= row) ...
+    GEOM_STRIP_ROWS = 2,   // ... or along the rows: closed forms, nothing read from the device
+    GEOM_PICKS = 3         // a corner whose (index, rowIndex, colIndex) k_fuse_counts_pick publishes from the host's four picks
+};
+
+// The canvas's own scratch (allocated with it, initialised once): out | done | row and column records | ramps | statistics slots.  The one
+// place that knows the layout: -> the bytes it takes for a canvas of rows x cols; S (optional): the pointers into `scratch`
+static size_t canvas_scratch_layout(void *scratch, int rows, int cols, FuseCanvasScratch *S)
 {
-    const int r = ry1 - ry0, c = rx1 - rx0;
-    if (r <= 0 || c <= 0) return canvas_paste_device(ctx, cv, d_tile, h, w, y0, x0);
-    ProfScope ps(ctx, "fuse");
-    const TrigGeom TG = {method == 1, r, c, dx, dy};
-    const dim3 agrid(cv->ch == 1 ? (w + 1023) / 1024 : (w + 255) / 256, h);
-    const char *env_an = getenv("VFSMS_FUSE_ANALYTIC");                      // 0: always run the statistics kernel (A/B runs, tests)
-    const bool analytic_on = !(env_an && atoi(env_an) == 0);
-    if (analytic_on) {
-        // fuseByFadeInAndFadeOut's own test (ImageFusion.py:201), on the count the statistics kernel would have produced: valid elements = valid
-        // pixels x channels
-        const long long valid = canvas_valid_area(cv, ry0, rx0, ry1, rx1) * cv->ch;
-        const double nel = (double)r * c * cv->ch;
-        if ((double)valid / nel > 0.65) {
-            if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{c <= r ? 1 : 2, r, c, dx, dy}, cv->mb_levels));
-            else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, c <= r ? 1 : 2, nullptr, std::min(r, c), cv->seam_blend, cv->mb_levels));
-            else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
-                                    (const int *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, c <= r ? 1 : 2);
-            HIP_TRY(hipGetLastError());
-            canvas_mark(cv, y0, x0, h, w);
-            if (info) { info[0] = 0; info[1] = -1; info[2] = 0; info[3] = 0; }      // what the ramp kernel reports for a strip: mode 0, no corner index
-            return VFSMS_OK;
-        }
+    const size_t n = (size_t)rows + cols, o_rec = 256, o_ramp = o_rec + sizeof(int) * 2 * n, o_slot = o_ramp + sizeof(float) * 2 * n;
+    const size_t slots = ((size_t)rows / FUSE_SB + 2) * ((size_t)cols / 1024 + 2);       // >= workgroups of any ROI inside the canvas, every wave layout
+    if (S) {
+        char *base = (char *)scratch;
+        S->out = (int *)(base + 64); S->done = (unsigned *)(base + 128);
+        S->rowFirstEnc = (int *)(base + o_rec); S->rowLast = S->rowFirstEnc + rows; S->colFirstEnc = S->rowLast + rows; S->colLast = S->colFirstEnc + cols;
+        S->wAr = (float *)(base + o_ramp); S->wBr = S->wAr + rows; S->wAc = S->wBr + rows; S->wBc = S->wAc + cols;
+        S->slots = (unsigned *)(base + o_slot);            // 8 dwords per statistics workgroup
     }
-    // the canvas's own scratch (allocated and initialised once: canvas_scratch_bytes / canvas_scratch_init): st | out | done | rows | cols | ramps
+    return o_slot + 32 * slots + 256;
+}
+size_t canvas_scratch_bytes(int rows, int cols) { return canvas_scratch_layout(nullptr, rows, cols, nullptr); }
+int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv)
+{
     FuseCanvasScratch S;
-    char *base = (char *)cv->scratch;
-    S.out = (int *)(base + 64); S.done = (unsigned *)(base + 128);
-    int *ib = (int *)(base + 256);
-    S.rowFirstEnc = ib; S.rowLast = ib + cv->rows; S.colFirstEnc = ib + 2 * (size_t)cv->rows; S.colLast = S.colFirstEnc + cv->cols;
-    float *fb = (float *)(S.colLast + cv->cols);
-    S.wAr = fb; S.wBr = fb + cv->rows; S.wAc = fb + 2 * (size_t)cv->rows; S.wBc = S.wAc + cv->cols;
-    S.slots = (unsigned *)(S.wBc + cv->cols);          // 8 dwords per statistics workgroup (canvas_scratch_bytes bounds their number)
-    CanvasView V;
-    V.pix = cv->pix; V.mask = cv->mask; V.ccols = cv->cols; V.ch = cv->ch; V.ry0 = ry0; V.rx0 = rx0;
-    V.tile = d_tile; V.tw = w; V.ty0 = ry0 - y0; V.tx0 = rx0 - x0;
-    const int wx_n = c <= 256 ? 1 : c <= 512 ? 2 : 4, wy_n = FUSE_NW / wx_n;
-    const dim3 sgrid((c + 256 * wx_n - 1) / (256 * wx_n), (r + FUSE_SB * wy_n - 1) / (FUSE_SB * wy_n));
-    if (analytic_on) {
-        // a corner ROI: first / last valid column of every row and first / last valid row of every column from the rectangles that meet the ROI,
-        // then getWeightsMatrix's scan (fuse_weights_body) for each of the four quadrants `index` could turn out to be
-        std::vector<int> rec((size_t)2 * r + 2 * c, -1);
-        int *rowF = rec.data(), *rowL = rowF + r, *colF = rowL + r, *colL = colF + c;
-        for (size_t k = 0; k + 3 < cv->placed.size(); k += 4) {
-            const int a0 = std::max(cv->placed[k], ry0) - ry0, b0 = std::max(cv->placed[k + 1], rx0) - rx0;
-            const int a1 = std::min(cv->placed[k + 2], ry1) - ry0, b1 = std::min(cv->placed[k + 3], rx1) - rx0;
-            if (a1 <= a0 || b1 <= b0) continue;
-            for (int i = a0; i < a1; i++) { rowF[i] = rowF[i] < 0 ? b0 : std::min(rowF[i], b0); rowL[i] = std::max(rowL[i], b1 - 1); }
-            for (int jj = b0; jj < b1; jj++) { colF[jj] = colF[jj] < 0 ? a0 : std::min(colF[jj], a0); colL[jj] = std::max(colL[jj], a1 - 1); }
-        }
-        CornerPick P;
-        for (int index = 0; index < 4; index++) {
-            const bool from_right = index == 2 || index == 3, by_last = index == 2 || index == 1;
-            int rowIndex = 0, colIndex = 0, err = 0;
-            for (int jj = from_right ? 1 : 0; jj < c; jj++) {
-                const int col = from_right ? c - jj : jj;
-                int cand = 0;
-                if (by_last) { if (colL[col] >= 0) cand = colL[col] + 1; }
-                else         { if (colF[col] >= 0) cand = colF[col] - 1; }
-                if (cand != 0) { rowIndex = cand; break; }
-            }
-            if (rowIndex >= r) err = 1;
-            else {
-                const int rr = rowIndex < 0 ? rowIndex + r : rowIndex;
-                if (from_right) { if (rowL[rr] >= 0) colIndex = rowL[rr] + 1; }
-                else            { if (rowF[rr] >= 0) colIndex = rowF[rr] - 1; }
-            }
-            if (!err) {                                  // the degenerate cases of the ramp loops (fuse_weights_body)
-                const int ri = rowIndex == 0 ? 1 : rowIndex, ci = colIndex == 0 ? 1 : colIndex;
-                if (by_last) { if (ri >= r) err = 1; } else if (rowIndex < r && r - ri - 1 == 0) err = 1;
-                if (from_right) { if (ci >= c) err = 1; } else if (colIndex < c && c - ci - 1 == 0) err = 1;
-            }
-            P.rowIndex[index] = rowIndex; P.colIndex[index] = colIndex; P.err[index] = err;
-        }
-        hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err, wx_n);
-        int seam_wmax = 1;                                // the widest arm any of the four picks can give the optimal seam (sizes its planes)
-        for (int index = 0; index < 4 && method == 3; index++) {
-            if (P.err[index]) continue;
-            int lo, W;
-            seam_arm(r, P.rowIndex[index], index == 2 || index == 1, lo, W); seam_wmax = std::max(seam_wmax, W);
-            seam_arm(c, P.colIndex[index], index == 2 || index == 3, lo, W); seam_wmax = std::max(seam_wmax, W);
-        }
-        if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{3, r, c, dx, dy, S.out}, cv->mb_levels));
-        else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, 0, S.out, seam_wmax, cv->seam_blend, cv->mb_levels));
-        else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch, d_tile, h, w, y0, x0, ry0, rx0, r, c,
-                           (const int *)S.out, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, TG, 3);
-    } else {
-        hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, dx, dy, cv->d_err, wx_n);
-        if (method == 2) TRY(mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, SeamGeom{0, r, c, dx, dy, S.out, S.wAr, S.wAc, S.wBr, S.wBc}, cv->mb_levels));
-        else if (method == 3) TRY(seam_fuse_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, dx, dy, 0, S.out, std::max(r, c), cv->seam_blend, cv->mb_levels));
-        else hipLaunchKernelGGL(k_fuse_apply, agrid, dim3(256), 0, ctx->stream, cv->pix, cv->mask, cv->cols, cv->ch,
-                           d_tile, h, w, y0, x0, ry0, rx0, r, c, (const int *)S.out, (const float *)S.wAr, (const float *)S.wAc, (const float *)S.wBr, (const float *)S.wBc, TG, 0);
+    canvas_scratch_layout(cv->scratch, cv->rows, cv->cols, &S);
+    HIP_TRY(hipMemsetAsync(cv->scratch, 0, (char *)S.rowFirstEnc - (char *)cv->scratch, ctx->stream));               // out, done
+    HIP_TRY(hipMemsetAsync(S.rowFirstEnc, 0xff, (char *)S.wAr - (char *)S.rowFirstEnc, ctx->stream));             // every record starts at -1
+    return VFSMS_OK;
+}
+
+// 1. strip or corner: fuseByFadeInAndFadeOut's own test (ImageFusion.py:201) on the count the statistics kernel would have produced (valid
+// elements = valid pixels x channels), from the rectangle list.  VFSMS_FUSE_ANALYTIC=0: always run the statistics kernel (A/B runs, tests);
+// read on every call
+static FuseGeomKind fuse_geom_kind(const CanvasRec *cv, const Placement &p)
+{
+    const char *env_an = getenv("VFSMS_FUSE_ANALYTIC");
+    if (env_an && atoi(env_an) == 0) return GEOM_RAMPS;
+    const long long valid = canvas_valid_area(cv, p.ry0, p.rx0, p.ry1, p.rx1) * cv->ch;
+    const double nel = (double)p.r() * p.c() * cv->ch;
+    if ((double)valid / nel > 0.65) return p.c() <= p.r() ? GEOM_STRIP_COLS : GEOM_STRIP_ROWS;
+    return GEOM_PICKS;
+}
+
+// 2. the corner picks of a ROI from the rectangle list: first / last valid column of every row and first / last valid row of every column
+// from the rectangles that meet the ROI, then getWeightsMatrix's scan (fuse_weights_body) for each of the four quadrants `index` could turn
+// out to be
+static CornerPick corner_picks(const CanvasRec *cv, const Placement &p)
+{
+    const int r = p.r(), c = p.c();
+    std::vector<int> rec((size_t)2 * r + 2 * c, -1);
+    int *rowF = rec.data(), *rowL = rowF + r, *colF = rowL + r, *colL = colF + c;
+    for (size_t k = 0; k + 3 < cv->placed.size(); k += 4) {
+        const int a0 = std::max(cv->placed[k], p.ry0) - p.ry0, b0 = std::max(cv->placed[k + 1], p.rx0) - p.rx0;
+        const int a1 = std::min(cv->placed[k + 2], p.ry1) - p.ry0, b1 = std::min(cv->placed[k + 3], p.rx1) - p.rx0;
+        if (a1 <= a0 || b1 <= b0) continue;
+        for (int i = a0; i < a1; i++) { rowF[i] = rowF[i] < 0 ? b0 : std::min(rowF[i], b0); rowL[i] = std::max(rowL[i], b1 - 1); }
+        for (int jj = b0; jj < b1; jj++) { colF[jj] = colF[jj] < 0 ? a0 : std::min(colF[jj], a0); colL[jj] = std::max(colL[jj], a1 - 1); }
     }
-    HIP_TRY(hipGetLastError());
-    canvas_mark(cv, y0, x0, h, w);
-    if (!info) return VFSMS_OK;          // no readback wanted: a degenerate geometry is latched in the canvas and reported by the download
+    CornerPick P;
+    for (int index = 0; index < 4; index++) {
+        const bool from_right = index == 2 || index == 3, by_last = index == 2 || index == 1;
+        int rowIndex = 0, colIndex = 0, err = 0;
+        for (int jj = from_right ? 1 : 0; jj < c; jj++) {
+            const int col = from_right ? c - jj : jj;
+            int cand = 0;
+            if (by_last) { if (colL[col] >= 0) cand = colL[col] + 1; }
+            else         { if (colF[col] >= 0) cand = colF[col] - 1; }
+            if (cand != 0) { rowIndex = cand; break; }
+        }
+        if (rowIndex >= r) err = 1;
+        else {
+            const int rr = rowIndex < 0 ? rowIndex + r : rowIndex;
+            if (from_right) { if (rowL[rr] >= 0) colIndex = rowL[rr] + 1; }
+            else            { if (rowF[rr] >= 0) colIndex = rowF[rr] - 1; }
+        }
+        if (!err) {                                  // the degenerate cases of the ramp loops (fuse_weights_body)
+            const int ri = rowIndex == 0 ? 1 : rowIndex, ci = colIndex == 0 ? 1 : colIndex;
+            if (by_last) { if (ri >= r) err = 1; } else if (rowIndex < r && r - ri - 1 == 0) err = 1;
+            if (from_right) { if (ci >= c) err = 1; } else if (colIndex < c && c - ci - 1 == 0) err = 1;
+        }
+        P.rowIndex[index] = rowIndex; P.colIndex[index] = colIndex; P.err[index] = err;
+    }
+    return P;
+}
+// the widest arm any of the four picks can give the optimal seam (sizes its planes)
+static int corner_picks_wmax(const CornerPick &P, int r, int c)
+{
+    int wmax = 1;
+    for (int index = 0; index < 4; index++) {
+        if (P.err[index]) continue;
+        int lo, W;
+        seam_arm(r, P.rowIndex[index], index == 2 || index == 1, lo, W); wmax = std::max(wmax, W);
+        seam_arm(c, P.colIndex[index], index == 2 || index == 3, lo, W); wmax = std::max(wmax, W);
+    }
+    return wmax;
+}
+
+// 3. the placement's operator, its geometry from `kind`: a host strip reads nothing from the device, the other two read the status ints the
+// statistics launch before this one publishes in S.out, GEOM_RAMPS its ramp arrays too.  seam_wmax: an upper bound of a seam's positions
+static int fuse_apply_operator(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, FuseGeomKind kind,
+                               const FuseCanvasScratch &S, int seam_wmax)
+{
+    const int r = p.r(), c = p.c();
+    const bool strip = kind == GEOM_STRIP_COLS || kind == GEOM_STRIP_ROWS, ramps = kind == GEOM_RAMPS;
+    const int *mode = strip ? nullptr : S.out;
+    const float *wAr = ramps ? S.wAr : nullptr, *wAc = ramps ? S.wAc : nullptr, *wBr = ramps ? S.wBr : nullptr, *wBc = ramps ? S.wBc : nullptr;
+    if (p.mode == VFSMS_CANVAS_MULTIBAND)
+        return mb_blend_canvas(ctx, cv, d_tile, p, SeamGeom{kind, r, c, p.dx, p.dy, mode, wAr, wAc, wBr, wBc}, cv->mb_levels);
+    if (p.mode == VFSMS_CANVAS_SEAMLINE)
+        return seam_fuse_canvas(ctx, cv, d_tile, p, strip ? kind : 0, mode, seam_wmax, cv->seam_blend, cv->mb_levels);
+    const TrigGeom TG = {p.mode == VFSMS_CANVAS_TRIG, r, c, p.dx, p.dy};
+    hipLaunchKernelGGL(k_fuse_apply, dim3(cv->ch == 1 ? (p.w + 1023) / 1024 : (p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream,
+                       tile_on_canvas(cv, d_tile, p), mode, wAr, wAc, wBr, wBc, TG, (int)kind);
+    return VFSMS_OK;
+}
+
+// 4. the optional readback: (mode, quadrant, rowIndex, colIndex) and the verdict on a degenerate geometry.  Synchronises, except for a host strip
+static int fuse_read_info(vfsms_ctx *ctx, const FuseCanvasScratch &S, FuseGeomKind kind, int32_t *info)
+{
+    if (kind == GEOM_STRIP_COLS || kind == GEOM_STRIP_ROWS) {                 // what the ramp kernel reports for a strip: mode 0, no corner index
+        info[0] = 0; info[1] = -1; info[2] = 0; info[3] = 0;
+        return VFSMS_OK;
+    }
     int out[8];
     HIP_TRY(hipMemcpyAsync(out, S.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -814,16 +851,35 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int
     return VFSMS_OK;
 }
 
-size_t canvas_scratch_bytes(int rows, int cols)
+int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, int32_t *info)
 {
-    const size_t slots = ((size_t)rows / FUSE_SB + 2) * ((size_t)cols / 1024 + 2);       // >= workgroups of any ROI inside the canvas, every wave layout
-    return 256 + (sizeof(int) * 2 + sizeof(float) * 2) * ((size_t)rows + cols) + 32 * slots + 256;
-}
-int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv)
-{
-    HIP_TRY(hipMemsetAsync(cv->scratch, 0, 256, ctx->stream));
-    HIP_TRY(hipMemsetAsync((char *)cv->scratch + 256, 0xff, sizeof(int) * 2 * ((size_t)cv->rows + cv->cols), ctx->stream));
-    return VFSMS_OK;
+    const int r = p.r(), c = p.c();
+    if (r <= 0 || c <= 0) return canvas_paste_device(ctx, cv, d_tile, p);
+    ProfScope ps(ctx, "fuse");
+    const FuseGeomKind kind = fuse_geom_kind(cv, p);
+    FuseCanvasScratch S;
+    canvas_scratch_layout(cv->scratch, cv->rows, cv->cols, &S);
+    int seam_wmax = std::min(r, c);
+    if (kind == GEOM_RAMPS || kind == GEOM_PICKS) {       // one statistics launch ahead of the operator
+        CanvasView V;
+        V.pix = cv->pix; V.mask = cv->mask; V.ccols = cv->cols; V.ch = cv->ch; V.ry0 = p.ry0; V.rx0 = p.rx0;
+        V.tile = d_tile; V.tw = p.w; V.ty0 = p.ry0 - p.y0; V.tx0 = p.rx0 - p.x0;
+        const int wx_n = c <= 256 ? 1 : c <= 512 ? 2 : 4, wy_n = FUSE_NW / wx_n;
+        const dim3 sgrid((c + 256 * wx_n - 1) / (256 * wx_n), (r + FUSE_SB * wy_n - 1) / (FUSE_SB * wy_n));
+        if (kind == GEOM_PICKS) {
+            const CornerPick P = corner_picks(cv, p);
+            hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err, wx_n);
+            seam_wmax = p.mode == VFSMS_CANVAS_SEAMLINE ? corner_picks_wmax(P, r, c) : 1;
+        } else {
+            hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, p.dx, p.dy, cv->d_err, wx_n);
+            seam_wmax = std::max(r, c);
+        }
+    }
+    TRY(fuse_apply_operator(ctx, cv, d_tile, p, kind, S, seam_wmax));
+    HIP_TRY(hipGetLastError());
+    canvas_mark(cv, p);
+    if (!info) return VFSMS_OK;          // no readback wanted: a degenerate geometry is latched in the canvas and reported by the download
+    return fuse_read_info(ctx, S, kind, info);
 }
 
 // A, B: device int64 [r][c][ch]; out: device u8.  method 0 fade, 1 trigonometric, 2 multi-band with `levels` (its seam from the fade's ramps),

@@ -278,31 +278,28 @@ static int mb_pyramid(vfsms_ctx *ctx, const MbPyr &P, const Src0 &S0)
 }
 
 template <int CH>
-static int mb_canvas_ch(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
-                        const SeamGeom &G, const MbPyr &P)
+static int mb_canvas_ch(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, const SeamGeom &G, const MbPyr &P)
 {
-    const Mb0Canvas<CH> S0 = {cv->pix, cv->mask, cv->cols, ry0, rx0, d_tile, w, ry0 - y0, rx0 - x0, G};
+    const Mb0Canvas<CH> S0 = {cv->pix, cv->mask, cv->cols, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0, G};
     TRY(mb_pyramid<CH>(ctx, P, S0));
-    hipLaunchKernelGGL((k_mb_up_canvas<CH>), dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, S0, MbPlane<CH>{P.ga[1], P.w[1]},
-                       MbPlane<CH>{P.gb[1], P.w[1]}, mb_coarse_o<CH>(P, 1), P.h[1], P.w[1], cv->pix, cv->mask, y0, x0, h, w, r, c);
+    hipLaunchKernelGGL((k_mb_up_canvas<CH>), dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, S0, MbPlane<CH>{P.ga[1], P.w[1]},
+                       MbPlane<CH>{P.gb[1], P.w[1]}, mb_coarse_o<CH>(P, 1), P.h[1], P.w[1], cv->pix, cv->mask, p.y0, p.x0, p.h, p.w, p.r(), p.c());
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }
 
-// The canvas ROI [ry0, ry0 + r) x [rx0, rx0 + c) blended with the tile (h x w at (y0, x0)), the tile pasted around it.  Enqueue only;
-// the caller marks the rectangle in the canvas's list.
-int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
-                    const SeamGeom &G, int levels)
+// The placement's ROI blended with the tile, the tile pasted around it.  Enqueue only; the caller marks the rectangle in the canvas's list.
+int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, const SeamGeom &G, int levels)
 {
     ProfScope ps(ctx, "fuse_multiband");
     MbPyr P;
-    TRY(mb_reserve(ctx, mb_layout(r, c, cv->ch, levels, &P, nullptr)));
-    mb_layout(r, c, cv->ch, levels, &P, (char *)ctx->mb_scratch);
+    TRY(mb_reserve(ctx, mb_layout(p.r(), p.c(), cv->ch, levels, &P, nullptr)));
+    mb_layout(p.r(), p.c(), cv->ch, levels, &P, (char *)ctx->mb_scratch);
     switch (cv->ch) {
-    case 1: return mb_canvas_ch<1>(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, G, P);
-    case 2: return mb_canvas_ch<2>(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, G, P);
-    case 3: return mb_canvas_ch<3>(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, G, P);
-    case 4: return mb_canvas_ch<4>(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, G, P);
+    case 1: return mb_canvas_ch<1>(ctx, cv, d_tile, p, G, P);
+    case 2: return mb_canvas_ch<2>(ctx, cv, d_tile, p, G, P);
+    case 3: return mb_canvas_ch<3>(ctx, cv, d_tile, p, G, P);
+    case 4: return mb_canvas_ch<4>(ctx, cv, d_tile, p, G, P);
     }
     vfsms_set_error("fuse_multiband: 1 to 4 channels");
     return VFSMS_ERR_BAD_ARG;

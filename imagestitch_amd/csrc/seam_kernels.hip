@@ -410,15 +410,15 @@ static int seam_solve(vfsms_ctx *ctx, const SeamRun &R)
     return VFSMS_OK;
 }
 
-// The canvas ROI [ry0, ry0 + r) x [rx0, rx0 + c) cut along its seam between the canvas and the tile (h x w at (y0, x0)), the tile pasted around
-// it.  hostkind / mode as SeamArgs.  blend 0: none, 1: the label plane into the pyramid blend with `levels`.  Enqueue only; the caller marks
-// the rectangle in the canvas's list.
-int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h, int w, int y0, int x0, int ry0, int rx0, int r, int c,
-                     int dx, int dy, int hostkind, const int *mode, int wmax, int blend, int levels)
+// The placement's ROI cut along its seam between the canvas and the tile, the tile pasted around it.  hostkind / mode as SeamArgs.  blend 0:
+// none, 1: the label plane into the pyramid blend with `levels`.  Enqueue only; the caller marks the rectangle in the canvas's list.
+int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, int hostkind, const int *mode, int wmax,
+                     int blend, int levels)
 {
+    const int r = p.r(), c = p.c();
     SeamRun R;
-    TRY(seam_setup(ctx, hostkind, r, c, dx, dy, mode, wmax, blend != 0, &R));
-    const SeamCanvas S = {cv->pix, cv->mask, cv->cols, cv->ch, ry0, rx0, d_tile, w, ry0 - y0, rx0 - x0};
+    TRY(seam_setup(ctx, hostkind, r, c, p.dx, p.dy, mode, wmax, blend != 0, &R));
+    const SeamCanvas S = {cv->pix, cv->mask, cv->cols, cv->ch, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0};
     const dim3 rgrid((c + 255) / 256, r);
     {
         ProfScope ps(ctx, "seam_energy");
@@ -430,12 +430,12 @@ int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, int h
             ProfScope ps(ctx, "seam_apply");
             hipLaunchKernelGGL(k_seam_label<SeamCanvas>, rgrid, dim3(256), 0, ctx->stream, S, R.a, R.label);
         }
-        SeamGeom G = {4, r, c, dx, dy};
+        SeamGeom G = {4, r, c, p.dx, p.dy};
         G.label = R.label;
-        return mb_blend_canvas(ctx, cv, d_tile, h, w, y0, x0, ry0, rx0, r, c, G, levels);
+        return mb_blend_canvas(ctx, cv, d_tile, p, G, levels);
     }
     ProfScope ps(ctx, "seam_apply");
-    hipLaunchKernelGGL(k_seam_apply_canvas, dim3((w + 255) / 256, h), dim3(256), 0, ctx->stream, S, R.a, cv->pix, cv->mask, y0, x0, h, w);
+    hipLaunchKernelGGL(k_seam_apply_canvas, dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, S, R.a, cv->pix, cv->mask, p.y0, p.x0, p.h, p.w);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }

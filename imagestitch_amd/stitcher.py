@@ -16,6 +16,7 @@ import numpy as np
 from . import utility as Utility
 from . import fusion as ImageFusion
 from .utility import roi_rect, offset_estimator, vote_tail
+from ._lib import Engine
 
 CANNOT_MATCH = "  The two images can not match"
 
@@ -810,6 +811,36 @@ class Stitcher(Utility.Method):
                     resultCol = size
         return offsetList, rangeX, rangeY, resultRow, resultCol
 
+    @staticmethod
+    def _placements(shapes, originOffsetList, offsetList, rangeX, rangeY, mode):
+        """The canvas walk of Stitcher.py:434-483 as data: int32 [n][9] rows y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode -- the geometry rows
+        of Engine.canvas_assemble_resident.  offsetList, rangeX, rangeY: from _layout; mode: a value of Engine.CANVAS_MODES.  The first
+        tile, and every tile under notFuse, is a paste row; the ROI of any other is the tile rectangle cut by its predecessor's bounding box."""
+        paste = Engine.CANVAS_MODES["notFuse"]
+        rows = np.zeros((len(offsetList), 9), np.int32)
+        for i in range(len(offsetList)):
+            th, tw = shapes[i][0], shapes[i][1]
+            oy, ox = offsetList[i][0], offsetList[i][1]
+            if i == 0 or mode == paste:
+                rows[i] = (oy, ox, 0, 0, 0, 0, 0, 0, paste)
+            else:
+                rows[i] = (oy, ox, max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]), min(oy + th, rangeX[i - 1][1]),
+                           min(ox + tw, rangeY[i - 1][1]), originOffsetList[i][0], originOffsetList[i][1], mode)
+        return rows
+
+    @staticmethod
+    def _placeTile(eng, canvas, tile, resident, row):
+        """One row of _placements through the per-tile Engine call for its mode; tile: a handle (resident) or a host array."""
+        y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode = (int(v) for v in row)
+        if mode == Engine.CANVAS_MODES["notFuse"]:
+            (eng.canvas_paste_tile if resident else eng.canvas_paste)(canvas, tile, y0, x0)
+        elif mode in Engine.CANVAS_BLEND_MODES:
+            (eng.canvas_blend_tile_resident if resident else eng.canvas_blend_tile)(canvas, tile, y0, x0, (ry0, rx0, ry1, rx1),
+                                                                                    Engine.CANVAS_BLEND_MODES[mode])
+        else:
+            (eng.canvas_fuse_tile_resident if resident else eng.canvas_fuse_tile)(canvas, tile, y0, x0, (ry0, rx0, ry1, rx1), dx, dy,
+                                                                                  method=Engine.CANVAS_FUSE_METHODS[mode])
+
     def getStitchByOffset(self, fileList, originOffsetList):
         """Stitcher.py:369-486.  NB: like the reference this inserts [0, 0] at the head of the caller's list."""
         color = self.isColorMode
@@ -823,16 +854,14 @@ class Stitcher(Utility.Method):
         # optimalSeamLine likewise with engines that can set the canvas's seam blend
         seamline = self.fuseMethod == "optimalSeamLine" and hasattr(eng, "canvas_set_seam_blend")
         device_fuse = self.fuseMethod in ("notFuse", "fadeInAndFadeOut", "trigonometric") or multiband or seamline
-        fmethod = 1 if self.fuseMethod == "trigonometric" else 2 if multiband else 3 if seamline else 0
-        simple = {"average": 0, "maximum": 1, "minimum": 2}.get(self.fuseMethod)
-        if simple is not None and not hasattr(eng, "canvas_blend_tile"):
-            simple = None
+        mode = Engine.CANVAS_MODES.get(self.fuseMethod)        # how every tile but the first goes onto the canvas
+        simple = mode in Engine.CANVAS_BLEND_MODES and hasattr(eng, "canvas_blend_tile")
         handles = imageList = None
-        use_res = (device_fuse or (simple is not None and hasattr(eng, "canvas_blend_tile_resident"))) and \
+        use_res = (device_fuse or (simple and hasattr(eng, "canvas_blend_tile_resident"))) and \
             all(fileList[i] in resident and (len(resident[fileList[i]][1]) == 3) == color for i in range(n))
         try:
-            if not use_res and (device_fuse or simple is not None) and hasattr(eng, "tile_reserve") and hasattr(eng, "tile_fill_pair") and \
-                    (simple is None or hasattr(eng, "canvas_blend_tile_resident")):
+            if not use_res and (device_fuse or simple) and hasattr(eng, "tile_reserve") and hasattr(eng, "tile_fill_pair") and \
+                    (not simple or hasattr(eng, "canvas_blend_tile_resident")):
                 # not (all) resident -- a custom registration method ran pair by pair on host arrays: the mosaic's tiles go straight from a
                 # pool of decoder threads into reserved device tiles, never as a list on the host (the reference holds all of them,
                 # Stitcher.py:382-403)
@@ -865,7 +894,7 @@ class Stitcher(Utility.Method):
                 self._correctShading(handles if use_res else None, shapes)
             offsetList, rangeX, rangeY, resultRow, resultCol = self._layout(shapes, originOffsetList)
             self.printAndWrite("  The rectified offsetList is " + str(offsetList))
-            if not device_fuse and simple is None:
+            if not device_fuse and not simple:
                 return self._stitchWithHostFuse(fileList, imageList, originOffsetList, offsetList, rangeX, rangeY, resultRow, resultCol)
             ch = 3 if color else 1
             canvas = eng.canvas_create(resultRow, resultCol, ch)
@@ -876,42 +905,15 @@ class Stitcher(Utility.Method):
                     eng.canvas_set_seam_blend(canvas, str(self.seamLineBlend))
                     if hasattr(eng, "canvas_set_multiband_levels"):
                         eng.canvas_set_multiband_levels(canvas, int(self.multiBandLevels))
+                rows = self._placements(shapes, originOffsetList, offsetList, rangeX, rangeY, mode)
+                # every tile resident: the walk as ONE library call (the per-tile calls cost the host more than their two launches cost the device)
                 one_call = use_res and hasattr(eng, "canvas_assemble_resident")
-                if one_call:
-                    # every tile is resident: the walk below as ONE library call (the per-tile calls cost the host more than
-                    # their two launches cost the device)
-                    geom = np.zeros((n, 9), np.int32)
-                    for i in range(0, n):
-                        self.printAndWrite("  stitching " + str(fileList[i]))
-                        th, tw = shapes[i][0], shapes[i][1]
-                        oy, ox = offsetList[i][0], offsetList[i][1]
-                        if i == 0 or self.fuseMethod == "notFuse":
-                            geom[i] = (oy, ox, 0, 0, 0, 0, 0, 0, -1)
-                        else:
-                            geom[i] = (oy, ox, max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]), min(oy + th, rangeX[i - 1][1]),
-                                       min(ox + tw, rangeY[i - 1][1]), originOffsetList[i][0], originOffsetList[i][1],
-                                       (6 if multiband else 7 if seamline else fmethod) if simple is None else 2 + simple)
-                    eng.canvas_assemble_resident(canvas, handles, geom)
-                for i in range(n if one_call else 0, n):
+                for i in range(n):
                     self.printAndWrite("  stitching " + str(fileList[i]))
-                    th, tw = shapes[i][0], shapes[i][1]
-                    oy, ox = offsetList[i][0], offsetList[i][1]
-                    if i == 0 or self.fuseMethod == "notFuse":
-                        if use_res:
-                            eng.canvas_paste_tile(canvas, handles[i], oy, ox)
-                        else:
-                            eng.canvas_paste(canvas, imageList[i], oy, ox)
-                        continue
-                    roi = (max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]),
-                           min(oy + th, rangeX[i - 1][1]), min(ox + tw, rangeY[i - 1][1]))
-                    if simple is not None and use_res:
-                        eng.canvas_blend_tile_resident(canvas, handles[i], oy, ox, roi, simple)
-                    elif simple is not None:
-                        eng.canvas_blend_tile(canvas, imageList[i], oy, ox, roi, simple)
-                    elif use_res:
-                        eng.canvas_fuse_tile_resident(canvas, handles[i], oy, ox, roi, originOffsetList[i][0], originOffsetList[i][1], method=fmethod)
-                    else:
-                        eng.canvas_fuse_tile(canvas, imageList[i], oy, ox, roi, originOffsetList[i][0], originOffsetList[i][1], method=fmethod)
+                    if not one_call:
+                        self._placeTile(eng, canvas, handles[i] if use_res else imageList[i], use_res, rows[i])
+                if one_call:
+                    eng.canvas_assemble_resident(canvas, handles, rows)
                 sink = getattr(self, "mosaicSink", None)
                 if sink is not None and hasattr(eng, "canvas_download_bands"):
                     # streamed write-out: the mosaic leaves the device band by band and is never whole in host memory

@@ -453,10 +453,22 @@ int vfsms_canvas_fuse_tile_resident(vfsms_ctx *ctx, int64_t canvas, int64_t tile
 int vfsms_canvas_fuse_tile_resident_m(vfsms_ctx *ctx, int64_t canvas, int64_t tile,
                                       int y0, int x0, int ry0, int rx0, int ry1, int rx1,
                                       int dx, int dy, int method, int32_t *info);
+/* How a tile goes onto the canvas: the `mode` of a geometry row, and the one code the library speaks inside.  The numbers are ABI
+ * (5 is not a mode).  The `method` 0..3 of vfsms_canvas_fuse_tile*_m is FADE, TRIG, MULTIBAND, SEAMLINE in that order, the `mode`
+ * 0..2 of vfsms_canvas_blend_tile* is AVERAGE, MAXIMUM, MINIMUM.                                                              */
+enum vfsms_canvas_mode {
+    VFSMS_CANVAS_PASTE = -1,      /* the first tile, fuseMethod "notFuse" */
+    VFSMS_CANVAS_FADE = 0,        /* fadeInAndFadeOut */
+    VFSMS_CANVAS_TRIG = 1,        /* trigonometric */
+    VFSMS_CANVAS_AVERAGE = 2,
+    VFSMS_CANVAS_MAXIMUM = 3,
+    VFSMS_CANVAS_MINIMUM = 4,
+    VFSMS_CANVAS_MULTIBAND = 6,   /* multiBandBlending */
+    VFSMS_CANVAS_SEAMLINE = 7     /* optimalSeamLine */
+};
 /* The canvas walk of Stitcher.getStitchByOffset (Stitcher.py:434-483) over n resident tiles in one call.
- * geom: n x 9 ints [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode], mode -1 = paste (first tile / notFuse),
- * 0 = fadeInAndFadeOut, 1 = trigonometric, 2 / 3 / 4 = average / maximum / minimum, 6 = multiBandBlending, 7 = optimalSeamLine (5 is refused).  Enqueue only: errors of a
- * tile's geometry surface in the download. */
+ * geom: n x 9 ints [y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode], mode a vfsms_canvas_mode.  Every row is checked before anything is
+ * enqueued.  Enqueue only: errors of a tile's geometry surface in the download. */
 int vfsms_canvas_assemble_resident(vfsms_ctx *ctx, int64_t canvas, int n, const int64_t *tiles, const int32_t *geom);
 /* pyramid levels (1..8) of the canvas's multiBandBlending fuses; a new canvas starts at 4                                      */
 int vfsms_canvas_set_multiband_levels(vfsms_ctx *ctx, int64_t canvas, int levels);

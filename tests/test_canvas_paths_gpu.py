@@ -1,0 +1,264 @@
+"""The mosaic canvas path end to end, through public Engine methods only: the three forms of the walk (host-tile calls, resident per-tile
+calls, the one-call walk) against each other for every mode code, the fade against the oracle walk, average / maximum / minimum against a
+numpy restatement of the reference walk, and the refusals.  Small two-row mosaics placed by their true offsets: a wide strip, a tall strip
+and corner ROIs, both signs of dx and dy, ROI widths in all three ranges the statistics kernel distinguishes (<= 256, <= 512, > 512)."""
+import os
+
+import numpy as np
+import pytest
+
+import imagestitch_amd as isa
+from imagestitch_amd._lib import VFSMS_ERR_BAD_ARG
+from imagestitch_amd.synthetic import SyntheticGrid
+
+PASTE, FADE, TRIG, AVERAGE, MAXIMUM, MINIMUM, MULTIBAND, SEAMLINE = -1, 0, 1, 2, 3, 4, 6, 7
+MODES = (PASTE, FADE, TRIG, AVERAGE, MAXIMUM, MINIMUM, MULTIBAND, SEAMLINE)
+FUSE_METHOD = {FADE: 0, TRIG: 1, MULTIBAND: 2, SEAMLINE: 3}       # the `method` of the per-tile fuse calls
+BLEND_MODE = {AVERAGE: 0, MAXIMUM: 1, MINIMUM: 2}                 # the `mode` of the per-tile blend calls
+GRIDS = {448: (2, 3, 192, 448), 576: (2, 3, 192, 576)}
+# among the ROI shapes of the five fused tiles: a wide strip, a tall strip, two corner ROIs
+ROI_SHAPES = {448: {(36, 446), (176, 72), (192, 438), (192, 448)}, 576: {(36, 574), (176, 91), (192, 566), (192, 576)}}
+_cache = {}
+
+
+def _mosaic(width, colour=False):
+    """tiles, geometry rows with mode 0 (restated from Stitcher.py:440-465, not taken from the package), canvas size"""
+    key = (width, colour)
+    if key not in _cache:
+        g = SyntheticGrid(*GRIDS[width], overlap=0.15)
+        tiles = g.tiles(threads=2)
+        if colour:
+            tiles = [np.ascontiguousarray(np.stack([t, 255 - t, (t // 2) + 17], -1).astype(np.uint8)) for t in tiles]
+        offs = [[0, 0]] + [list(map(int, o)) for o in g.true_offsets()]
+        offsetList, rangeX, rangeY, rows, cols = isa.Stitcher._layout([t.shape[:2] for t in tiles], offs)
+        geom = np.zeros((len(tiles), 9), np.int32)
+        for i, t in enumerate(tiles):
+            oy, ox = offsetList[i]
+            if i == 0:
+                geom[i] = (oy, ox, 0, 0, 0, 0, 0, 0, PASTE)
+            else:
+                geom[i] = (oy, ox, max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]), min(oy + t.shape[0], rangeX[i - 1][1]),
+                           min(ox + t.shape[1], rangeY[i - 1][1]), offs[i][0], offs[i][1], FADE)
+        geom.setflags(write=False)
+        _cache[key] = (tiles, geom, rows, cols)
+    return _cache[key]
+
+
+def _with_mode(geom, mode):
+    g = geom.copy()
+    if mode == PASTE:
+        g[:, 2:] = (0, 0, 0, 0, 0, 0, PASTE)
+    else:
+        g[1:, 8] = mode
+    return g
+
+
+def _place(engine, cv, tile, resident, row, infos=None):
+    y0, x0, ry0, rx0, ry1, rx1, dx, dy, mode = [int(v) for v in row]
+    roi = (ry0, rx0, ry1, rx1)
+    if mode == PASTE:
+        (engine.canvas_paste_tile if resident else engine.canvas_paste)(cv, tile, y0, x0)
+    elif mode in BLEND_MODE:
+        (engine.canvas_blend_tile_resident if resident else engine.canvas_blend_tile)(cv, tile, y0, x0, roi, BLEND_MODE[mode])
+    elif resident:
+        info = engine.canvas_fuse_tile_resident(cv, tile, y0, x0, roi, dx, dy, want_info=infos is not None, method=FUSE_METHOD[mode])
+        if infos is not None:
+            infos.append([int(v) for v in info])
+    else:
+        engine.canvas_fuse_tile(cv, tile, y0, x0, roi, dx, dy, method=FUSE_METHOD[mode])
+
+
+def _walk(engine, form, tiles, handles, geom, rows, cols, infos=None):
+    """-> the canvas bytes, or "refused" when the library refused a geometry (at a call or at the download)"""
+    ch = tiles[0].shape[2] if tiles[0].ndim == 3 else 1
+    cv = engine.canvas_create(rows, cols, ch)
+    try:
+        if form == "one_call":
+            engine.canvas_assemble_resident(cv, handles, geom)
+        else:
+            for i in range(len(tiles)):
+                _place(engine, cv, handles[i] if form == "resident" else tiles[i], form == "resident", geom[i], infos)
+        return engine.canvas_download(cv, rows, cols, ch)
+    except isa.VfsmsError as e:
+        assert "error %d:" % VFSMS_ERR_BAD_ARG in str(e), e
+        return "refused"
+    finally:
+        engine.canvas_free(cv)
+
+
+class _Analytic:
+    """VFSMS_FUSE_ANALYTIC for the block: None = unset, "0" = always the statistics kernel"""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        self.keep = os.environ.pop("VFSMS_FUSE_ANALYTIC", None)
+        if self.value is not None:
+            os.environ["VFSMS_FUSE_ANALYTIC"] = self.value
+
+    def __exit__(self, *exc):
+        os.environ.pop("VFSMS_FUSE_ANALYTIC", None)
+        if self.keep is not None:
+            os.environ["VFSMS_FUSE_ANALYTIC"] = self.keep
+
+
+def _upload(engine, tiles):
+    return [engine.tile_upload_color(t) if t.ndim == 3 else engine.tile_upload(t) for t in tiles]
+
+
+def _same(a, b):
+    return (isinstance(a, str) and isinstance(b, str) and a == b) or \
+        (not isinstance(a, str) and not isinstance(b, str) and a.shape == b.shape and np.array_equal(a, b))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width,colour", [(448, False), (576, False), (448, True)])
+def test_host_resident_and_one_call_walks_agree_for_every_mode(engine, width, colour):
+    tiles, geom0, rows, cols = _mosaic(width, colour)
+    handles = _upload(engine, tiles)
+    try:
+        for flag in (None, "0"):
+            with _Analytic(flag):
+                for mode in MODES:
+                    geom = _with_mode(geom0, mode)
+                    infos = [] if mode == FADE else None
+                    got = {form: _walk(engine, form, tiles, handles, geom, rows, cols, infos if form == "resident" else None)
+                           for form in ("host", "resident", "one_call")}
+                    tag = (width, colour, flag, mode)
+                    print(tag, {f: (v if isinstance(v, str) else "ok") for f, v in got.items()}, infos)
+                    assert _same(got["host"], got["resident"]), tag
+                    assert _same(got["host"], got["one_call"]), tag
+                    if infos is not None:
+                        # the strip-or-corner mix of the mosaic, from the info rows (first int: 0 strip, 1 corner)
+                        shapes = [(int(g[4] - g[2]), int(g[5] - g[3])) for g in geom[1:]]
+                        assert ROI_SHAPES[width] <= set(shapes), shapes
+                        # ImageFusion.py:201: a strip when more than 65 % of the ROI is valid, from the rectangles placed before the tile
+                        valid = np.zeros((rows, cols), bool)
+                        share = []
+                        for t, g in zip(tiles, geom):
+                            if g[8] != PASTE:
+                                share.append(float(valid[g[2]:g[4], g[3]:g[5]].mean()))
+                            valid[g[0]:g[0] + t.shape[0], g[1]:g[1] + t.shape[1]] = True
+                        assert [i[0] for i in infos] == [0 if s > 0.65 else 1 for s in share], (infos, share)
+                        corners = sorted(sh for sh, s in zip(shapes, share) if s <= 0.65)          # the two whole-tile-high ROIs after the turn
+                        assert corners == sorted(sh for sh in ROI_SHAPES[width] if sh[0] == 192) and len(share) - len(corners) == 3, (shapes, share)
+                        assert {g[6] < 0 for g in geom[1:]} == {True, False} and {g[7] < 0 for g in geom[1:]} == {True, False}
+    finally:
+        for h in handles:
+            engine.tile_free(h)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [448, 576])
+def test_fade_walk_equals_the_oracle_walk(engine, oracle, width):
+    from fakes import OracleEngine
+    tiles, geom, rows, cols = _mosaic(width)
+    handles = _upload(engine, tiles)
+    try:
+        got = _walk(engine, "one_call", tiles, handles, geom, rows, cols)
+    finally:
+        for h in handles:
+            engine.tile_free(h)
+    ref = OracleEngine(oracle)
+    want = _walk(ref, "host", tiles, None, geom, rows, cols)
+    assert not isinstance(got, str) and got.shape == want.shape and np.array_equal(got, want)
+
+
+def _reference_simple_walk(tiles, geom, rows, cols, mode):
+    """Stitcher.py:434-486 with fuseImage's fill-in (Stitcher.py:498-504) and ImageFusion.py:12-41, in numpy"""
+    cv = np.zeros((rows, cols) + tiles[0].shape[2:], np.int64) - 1
+    for t, g in zip(tiles, geom):
+        y0, x0, ry0, rx0, ry1, rx1 = [int(v) for v in g[:6]]
+        A = cv[ry0:ry1, rx0:rx1].copy()
+        cv[y0:y0 + t.shape[0], x0:x0 + t.shape[1]] = t
+        if g[8] == PASTE:
+            continue
+        B = cv[ry0:ry1, rx0:rx1].copy()
+        A[A == -1] = 0
+        B[B == -1] = 0
+        A[A == 0] = B[A == 0]
+        B[B == 0] = A[B == 0]
+        cv[ry0:ry1, rx0:rx1] = np.uint8((A + B) / 2) if mode == AVERAGE else np.maximum(A, B) if mode == MAXIMUM else np.minimum(A, B)
+    cv[cv == -1] = 0
+    return cv.astype(np.uint8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("colour", [False, True])
+def test_simple_blends_equal_the_reference_walk(engine, colour):
+    for width in ((448,) if colour else (448, 576)):
+        tiles, geom0, rows, cols = _mosaic(width, colour)
+        handles = _upload(engine, tiles)
+        try:
+            for mode in (AVERAGE, MAXIMUM, MINIMUM):
+                geom = _with_mode(geom0, mode)
+                got = _walk(engine, "one_call", tiles, handles, geom, rows, cols)
+                want = _reference_simple_walk(tiles, geom, rows, cols, mode)
+                assert not isinstance(got, str) and got.shape == want.shape and np.array_equal(got, want), (width, colour, mode)
+        finally:
+            for h in handles:
+                engine.tile_free(h)
+
+
+@pytest.mark.gpu
+def test_refusals_are_bad_arg_and_leave_the_canvas_alone(engine):
+    tiles, geom, rows, cols = _mosaic(448)
+    handles = _upload(engine, tiles)
+    t, h = tiles[1], handles[1]
+    th, tw = t.shape
+    y0, x0, ry0, rx0, ry1, rx1, dx, dy = [int(v) for v in geom[1][:8]]
+    roi = (ry0, rx0, ry1, rx1)
+    roi_out = [(y0 - 1, rx0, ry1, rx1), (ry0, x0 - 1, ry1, rx1), (ry0, rx0, y0 + th + 1, rx1), (ry0, rx0, ry1, x0 + tw + 1)]
+    rect_out = [(rows - th + 1, x0), (y0, cols - tw + 1), (-1, x0), (y0, -1)]
+    calls = []
+    for r in roi_out:
+        calls += [lambda cv, r=r: engine.canvas_fuse_tile(cv, t, y0, x0, r, dx, dy),
+                  lambda cv, r=r: engine.canvas_blend_tile(cv, t, y0, x0, r, 0),
+                  lambda cv, r=r: engine.canvas_fuse_tile_resident(cv, h, y0, x0, r, dx, dy),
+                  lambda cv, r=r: engine.canvas_fuse_tile_resident(cv, h, y0, x0, r, dx, dy, want_info=True, method=2),
+                  lambda cv, r=r: engine.canvas_blend_tile_resident(cv, h, y0, x0, r, 1),
+                  lambda cv, r=r: engine.canvas_assemble_resident(cv, [h], [(y0, x0) + r + (dx, dy, SEAMLINE)])]
+    for (by, bx) in rect_out:
+        sh = (ry0 + by - y0, rx0 + bx - x0, ry1 + by - y0, rx1 + bx - x0)        # the ROI moved with the rectangle
+        calls += [lambda cv, by=by, bx=bx: engine.canvas_paste(cv, t, by, bx),
+                  lambda cv, by=by, bx=bx, sh=sh: engine.canvas_fuse_tile(cv, t, by, bx, sh, dx, dy, method=1),
+                  lambda cv, by=by, bx=bx, sh=sh: engine.canvas_blend_tile(cv, t, by, bx, sh, 2),
+                  lambda cv, by=by, bx=bx: engine.canvas_paste_tile(cv, h, by, bx),
+                  lambda cv, by=by, bx=bx, sh=sh: engine.canvas_fuse_tile_resident(cv, h, by, bx, sh, dx, dy),
+                  lambda cv, by=by, bx=bx, sh=sh: engine.canvas_blend_tile_resident(cv, h, by, bx, sh, 0),
+                  lambda cv, by=by, bx=bx, sh=sh: engine.canvas_assemble_resident(cv, [h], [(by, bx) + sh + (dx, dy, FADE)])]
+    for m in (4, -1):
+        calls += [lambda cv, m=m: engine.canvas_fuse_tile(cv, t, y0, x0, roi, dx, dy, method=m),
+                  lambda cv, m=m: engine.canvas_fuse_tile_resident(cv, h, y0, x0, roi, dx, dy, method=m)]
+    calls += [lambda cv: engine.canvas_blend_tile(cv, t, y0, x0, roi, 3), lambda cv: engine.canvas_blend_tile_resident(cv, h, y0, x0, roi, 3)]
+    for m in (5, 8, -2):
+        calls += [lambda cv, m=m: engine.canvas_assemble_resident(cv, [h], [(y0, x0) + roi + (dx, dy, m)])]
+    cv = engine.canvas_create(rows, cols, 1)
+    try:
+        engine.canvas_paste(cv, tiles[0], int(geom[0][0]), int(geom[0][1]))
+        before = engine.canvas_download(cv, rows, cols, 1)
+        assert before.any()
+        for k, call in enumerate(calls):
+            with pytest.raises(isa.VfsmsError) as e:
+                call(cv)
+            assert "error %d:" % VFSMS_ERR_BAD_ARG in str(e.value), (k, e.value)
+            assert np.array_equal(engine.canvas_download(cv, rows, cols, 1), before), k
+    finally:
+        engine.canvas_free(cv)
+    # a one-call walk whose LAST row is bad: nothing was enqueued, a fresh canvas stays all zero
+    try:
+        for bad in ((y0, x0) + roi_out[0] + (dx, dy, FADE), (y0, x0) + roi + (dx, dy, 5), (rows, x0) + roi + (dx, dy, FADE)):
+            g = [tuple(int(v) for v in row) for row in geom]
+            g[-1] = bad
+            cv = engine.canvas_create(rows, cols, 1)
+            try:
+                with pytest.raises(isa.VfsmsError) as e:
+                    engine.canvas_assemble_resident(cv, handles, g)
+                assert "error %d:" % VFSMS_ERR_BAD_ARG in str(e.value), e.value
+                assert not engine.canvas_download(cv, rows, cols, 1).any(), bad
+            finally:
+                engine.canvas_free(cv)
+    finally:
+        for hd in handles:
+            engine.tile_free(hd)

@@ -1063,3 +1063,114 @@ def test_bench_dump_outputs_and_synthesis_pool(tmp_path):
     for argv in (["--steps", "0"], ["--method", "fuse", "--dump-outputs", str(tmp_path / "f")]):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
         assert out.returncode == 2 and "error" in out.stderr, (argv, out.stderr)
+
+
+# ---- the canvas walk as data: Stitcher._placements and the per-tile dispatcher ---------------------------------------------------------
+# fuseMethod -> (mode of a geometry row, per-tile call family, its method / mode argument): include/vfsms.h, restated
+CANVAS_TABLE = {"notFuse": (-1, "paste", None), "fadeInAndFadeOut": (0, "fuse", 0), "trigonometric": (1, "fuse", 1),
+                "average": (2, "blend", 0), "maximum": (3, "blend", 1), "minimum": (4, "blend", 2),
+                "multiBandBlending": (6, "fuse", 2), "optimalSeamLine": (7, "fuse", 3)}
+
+
+def _bench_rows(grid, mode):
+    """the geometry rows as bench.py's bench_fuse writes them out, with `mode` in place of its 0 (notFuse: every row a paste)"""
+    n = grid.n_tiles
+    offs = [[0, 0]] + [list(map(int, o)) for o in grid.true_offsets()]
+    shapes = [(grid.th, grid.tw)] * n
+    offsetList, rangeX, rangeY, rows, cols = isa.Stitcher._layout(shapes, offs)
+    rois = []
+    for i in range(1, n):
+        oy, ox = offsetList[i]
+        rois.append((max(oy, rangeX[i - 1][0]), max(ox, rangeY[i - 1][0]), min(oy + grid.th, rangeX[i - 1][1]), min(ox + grid.tw, rangeY[i - 1][1])))
+    geom = [(offsetList[0][0], offsetList[0][1], 0, 0, 0, 0, 0, 0, -1)]
+    if mode == -1:
+        geom += [(offsetList[i][0], offsetList[i][1], 0, 0, 0, 0, 0, 0, -1) for i in range(1, n)]
+    else:
+        geom += [(offsetList[i][0], offsetList[i][1]) + tuple(rois[i - 1]) + (offs[i][0], offs[i][1], mode) for i in range(1, n)]
+    return geom, offs, shapes, rows, cols
+
+
+def test_placements_equal_the_bench_row_formula():
+    from imagestitch_amd.synthetic import SyntheticGrid
+    assert {k: v[0] for k, v in CANVAS_TABLE.items()} == isa.Engine.CANVAS_MODES
+    for grid in (SyntheticGrid(2, 3, 192, 448, overlap=0.15), SyntheticGrid(3, 3, 128)):
+        for name, (mode, _family, _arg) in CANVAS_TABLE.items():
+            want, offs, shapes, _rows, _cols = _bench_rows(grid, mode)
+            offsetList, rangeX, rangeY, _r, _c = isa.Stitcher._layout(shapes, offs)
+            got = isa.Stitcher._placements(shapes, offs, offsetList, rangeX, rangeY, isa.Engine.CANVAS_MODES[name])
+            assert got.dtype == np.int32 and got.shape == (grid.n_tiles, 9)
+            assert got.tolist() == [list(r) for r in want], name
+
+
+class _RecordingEngine:
+    """An engine that offers exactly `names` and records every call"""
+
+    def __init__(self, names, rows, cols):
+        self._names, self._shape, self.calls = set(names), (rows, cols), []
+
+    def __getattr__(self, name):
+        if name.startswith("_") or name not in self._names:
+            raise AttributeError(name)
+
+        def call(*a, **k):
+            self.calls.append((name, a, k))
+            return 7 if name == "canvas_create" else np.zeros(self._shape, np.uint8) if name == "canvas_download" else None
+        return call
+
+
+def test_get_stitch_by_offset_issues_the_expected_canvas_calls(tmp_path):
+    from imagestitch_amd.synthetic import SyntheticGrid
+    grid = SyntheticGrid(2, 3, 192, 448, overlap=0.15)
+    tiles = grid.tiles(threads=2)
+    files = _write_tiles(tmp_path, tiles, "rec")
+    n = len(tiles)
+    common = ["canvas_create", "canvas_free", "canvas_download", "canvas_set_multiband_levels", "canvas_set_seam_blend", "tile_free"]
+    per_tile_res = ["canvas_paste_tile", "canvas_fuse_tile_resident", "canvas_blend_tile", "canvas_blend_tile_resident"]
+    capabilities = {"one_call": common + per_tile_res + ["canvas_assemble_resident"], "resident": common + per_tile_res,
+                    "host": common + ["canvas_paste", "canvas_fuse_tile", "canvas_blend_tile"]}
+    per_tile = {("paste", True): "canvas_paste_tile", ("paste", False): "canvas_paste", ("fuse", True): "canvas_fuse_tile_resident",
+                ("fuse", False): "canvas_fuse_tile", ("blend", True): "canvas_blend_tile_resident", ("blend", False): "canvas_blend_tile"}
+    try:
+        for form, names in capabilities.items():
+            for fuse_method, (mode, family, arg) in CANVAS_TABLE.items():
+                geom, offs, shapes, rows, cols = _bench_rows(grid, mode)
+                eng = _RecordingEngine(names, rows, cols)
+                s = isa.Stitcher()
+                s._engine = eng
+                s.printAndWrite = lambda c: None
+                s.isColorMode = False
+                isa.Stitcher.isColorMode = False
+                s.fuseMethod = fuse_method
+                if form != "host":
+                    s._resident = {files[i]: (100 + i, shapes[i]) for i in range(n)}
+                s.getStitchByOffset(files, [list(o) for o in offs[1:]])
+                want = [("canvas_create", (rows, cols, 1), {})]
+                if fuse_method == "multiBandBlending":
+                    want.append(("canvas_set_multiband_levels", (7, int(s.multiBandLevels)), {}))
+                if fuse_method == "optimalSeamLine":
+                    want += [("canvas_set_seam_blend", (7, str(s.seamLineBlend)), {}), ("canvas_set_multiband_levels", (7, int(s.multiBandLevels)), {})]
+                if form == "one_call":
+                    want.append(("canvas_assemble_resident", (7, [100 + i for i in range(n)], [list(g) for g in geom]), {}))
+                for i, g in enumerate(geom if form != "one_call" else []):
+                    res = form == "resident"
+                    fam = "paste" if g[8] == -1 else family
+                    tile = 100 + i if res else i
+                    if fam == "paste":
+                        want.append((per_tile[(fam, res)], (7, tile, g[0], g[1]), {}))
+                    elif fam == "blend":
+                        want.append((per_tile[(fam, res)], (7, tile, g[0], g[1], tuple(g[2:6]), arg), {}))
+                    else:
+                        want.append((per_tile[(fam, res)], (7, tile, g[0], g[1], tuple(g[2:6]), g[6], g[7]), {"method": arg}))
+                want += [("canvas_download", (7, rows, cols, 1), {}), ("canvas_free", (7,), {})]
+
+                def plain(v):
+                    if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.ndim == 2:       # a host tile -> its index
+                        return [k for k, t in enumerate(tiles) if t.shape == v.shape and np.array_equal(t, v)][0]
+                    if isinstance(v, np.ndarray):
+                        return v.tolist()
+                    return tuple(plain(x) for x in v) if isinstance(v, tuple) else v
+                got = [(name, tuple(plain(x) for x in a), k) for name, a, k in eng.calls if name.startswith("canvas_")]
+                assert got == want, (form, fuse_method)
+                assert [a[0] for name, a, k in eng.calls if name == "tile_free"] == ([] if form == "host" else [100 + i for i in range(n)])
+    finally:
+        isa.Stitcher.isColorMode = True
