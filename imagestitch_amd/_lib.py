@@ -206,6 +206,13 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _path_arrays(shapes, handles=None):
+    """what the pairs_offsets entry points take of a path -> (tile count, int32[n, 2] shapes, int64[n] tile handles or None)"""
+    sh = np.ascontiguousarray(np.array([[s[0], s[1]] for s in shapes], np.int32))
+    hs = None if handles is None else np.array([h if h is not None else 0 for h in handles], np.int64)
+    return len(shapes), sh, hs
+
+
 def _u8_2d(img):
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim != 2:
@@ -741,7 +748,7 @@ class Engine:
             p._hint_keepalive = arr                          # the struct only holds the address
             p.path_hint = arr.ctypes.data_as(C.POINTER(C.c_int32))
             p.path_hint_len = len(arr)
-        p.method = {"surf": 0, "orb": 1, "phase": 2}[method]
+        p.method = {"surf": 0, "orb": 1, "phase": 2, "sift": 3}[method]     # 3: evaluator-supplied only (pairs_offsets_eval, _blind_eval)
         p.offset_evaluate, p.direct_incre, p.window, p.orb_max_dist = int(offsetEvaluate), int(directIncre), int(window), int(orbMaxDistance)
         p.enhance_mode, p.clip_limit, p.tile_grid = int(enhance[0]), float(enhance[1]), int(enhance[2])
         p.roi_ratio, p.search_ratio, p.phase_threshold = float(roiRatio), float(searchRatio), float(phaseResponseThreshold)
@@ -752,10 +759,8 @@ class Engine:
     def pairs_offsets(self, handles, shapes, params, first=0, last=None, direction=1, midpath=False, stop_on_fail=False):
         """vfsms_pairs_offsets: every pair of [first, last) of the path through the library's own candidate state machine.
         -> (int32[last-first, 6] = status, dx, dy, direction, i, votes; direction out; (attempts, batches, capacity retries))."""
-        n = len(shapes)
+        n, sh, hs = _path_arrays(shapes, handles)
         last = n - 1 if last is None else last
-        hs = np.array([h if h is not None else 0 for h in handles], np.int64)
-        sh = np.ascontiguousarray(np.array([[s[0], s[1]] for s in shapes], np.int32))
         out = np.zeros((max(last - first, 0), 6), np.int32)
         d_out = C.c_int32()
         stats = np.zeros(8, np.int64)
@@ -765,9 +770,7 @@ class Engine:
 
     def pairs_offsets_blind(self, handles, shapes, params, first, last, per):
         """vfsms_pairs_offsets_blind: the chunk [first, last) for every possible incoming direction -> (int32[4, per, 6], int32[4] directions out, stats)."""
-        n = len(shapes)
-        hs = np.array([h if h is not None else 0 for h in handles], np.int64)
-        sh = np.ascontiguousarray(np.array([[s[0], s[1]] for s in shapes], np.int32))
+        n, sh, hs = _path_arrays(shapes, handles)
         out = np.zeros((4, max(per, 1), 6), np.int32)
         d_out = np.zeros(4, np.int32)
         stats = np.zeros(8, np.int64)
@@ -1087,34 +1090,37 @@ def default_engine():
     return _default_engine
 
 
-def pairs_offsets_blind_eval(attempts, shapes, params, first, last, per):
-    """vfsms_pairs_offsets_blind_eval over a Python evaluator (needs no GPU) -> (int32[4, per, 6], int32[4], stats)."""
+def _call_with_evaluator(attempts, call):
+    """call(vfsms_attempt_eval) -> return code, with the Python evaluator `attempts` behind the C callback: attempts(items) with
+    items = [(pair, direction, i), ...] -> int32[n, <= 8] rows {status, raw dx, raw dy, votes, nA, nB, ...} (include/vfsms.h).  What
+    `attempts` raises comes out of here as that same exception, once the library has unwound; a library error raises VfsmsError."""
     lib = load_library()
-    n = len(shapes)
     err = []
 
     def cb(_user, items, count, rows):
         try:
-            res = attempts([(items[k].pair, items[k].direction, items[k].i) for k in range(count)])
-            for k, r in enumerate(res):
-                for c in range(min(len(r), ATTEMPT_INTS)):
-                    rows[k * ATTEMPT_INTS + c] = int(r[c])
-            return 0
+            res = np.asarray(attempts([(items[k].pair, items[k].direction, items[k].i) for k in range(count)]), np.int32).reshape(count, -1)
+            np.ctypeslib.as_array(rows, (count, ATTEMPT_INTS))[:, :res.shape[1]] = res[:, :ATTEMPT_INTS]       # columns the evaluator leaves out stay 0
+            return VFSMS_OK
         except Exception as e:            # never let an exception cross the C frame
             err.append(e)
-            return -1
-    sh = np.ascontiguousarray(np.array([[s[0], s[1]] for s in shapes], np.int32))
-    out = np.zeros((4, max(per, 1), 6), np.int32)
-    d_out = np.zeros(4, np.int32)
-    stats = np.zeros(8, np.int64)
-    rc = lib.vfsms_pairs_offsets_blind_eval(ATTEMPT_EVAL(cb), None, _ptr(sh), n, int(first), int(last), int(max(per, 1)), C.byref(params),
-                                            _ptr(out), _ptr(d_out), _ptr(stats))
+            return VFSMS_ERR_BAD_ARG
+    rc = call(ATTEMPT_EVAL(cb))
     if err:
         raise err[0]
     if rc != VFSMS_OK:
-        buf = C.create_string_buffer(512)
-        lib.vfsms_last_error(buf, 512)
-        raise VfsmsError("libvfsms error %d: %s" % (rc, buf.value.decode(errors="replace")))
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+
+
+def pairs_offsets_blind_eval(attempts, shapes, params, first, last, per):
+    """vfsms_pairs_offsets_blind_eval over a Python evaluator (needs no GPU) -> (int32[4, per, 6], int32[4], stats)."""
+    lib = load_library()
+    n, sh, _hs = _path_arrays(shapes)
+    out = np.zeros((4, max(per, 1), 6), np.int32)
+    d_out = np.zeros(4, np.int32)
+    stats = np.zeros(8, np.int64)
+    _call_with_evaluator(attempts, lambda ev: lib.vfsms_pairs_offsets_blind_eval(ev, None, _ptr(sh), n, int(first), int(last), int(max(per, 1)),
+                                                                                 C.byref(params), _ptr(out), _ptr(d_out), _ptr(stats)))
     return out[:, :per], d_out, tuple(int(v) for v in stats)
 
 
@@ -1122,30 +1128,12 @@ def pairs_offsets_eval(attempts, shapes, params, first=0, last=None, direction=1
     """vfsms_pairs_offsets_eval: the library's candidate state machine over a Python evaluator of fused batches (needs no GPU).
     attempts(items) with items = [(pair, direction, i), ...] -> rows [[status, raw dx, raw dy, votes, nA, nB, ...], ...]."""
     lib = load_library()
-    n = len(shapes)
+    n, sh, _hs = _path_arrays(shapes)
     last = n - 1 if last is None else last
-    err = []
-
-    def cb(_user, items, count, rows):
-        try:
-            res = attempts([(items[k].pair, items[k].direction, items[k].i) for k in range(count)])
-            for k, r in enumerate(res):
-                for c in range(min(len(r), ATTEMPT_INTS)):
-                    rows[k * ATTEMPT_INTS + c] = int(r[c])
-            return 0
-        except Exception as e:            # never let an exception cross the C frame
-            err.append(e)
-            return -1
-    sh = np.ascontiguousarray(np.array([[s[0], s[1]] for s in shapes], np.int32))
     out = np.zeros((max(last - first, 0), 6), np.int32)
     d_out = C.c_int32()
     stats = np.zeros(8, np.int64)
-    rc = lib.vfsms_pairs_offsets_eval(ATTEMPT_EVAL(cb), None, _ptr(sh), n, int(first), int(last), int(direction), int(bool(midpath)),
-                                      int(bool(stop_on_fail)), C.byref(params), _ptr(out), C.byref(d_out), _ptr(stats))
-    if err:
-        raise err[0]
-    if rc != VFSMS_OK:
-        buf = C.create_string_buffer(512)
-        lib.vfsms_last_error(buf, 512)
-        raise VfsmsError("libvfsms error %d: %s" % (rc, buf.value.decode(errors="replace")))
+    _call_with_evaluator(attempts, lambda ev: lib.vfsms_pairs_offsets_eval(ev, None, _ptr(sh), n, int(first), int(last), int(direction),
+                                                                           int(bool(midpath)), int(bool(stop_on_fail)), C.byref(params),
+                                                                           _ptr(out), C.byref(d_out), _ptr(stats)))
     return out, d_out.value, tuple(int(v) for v in stats)

@@ -3,9 +3,11 @@
 // consecutive pair of a shooting path (the loop of Stitcher.flowStitch, Stitcher.py:64-79) with speculative fused batches.
 //
 // Host-side C++ (no kernels here): it decides WHICH (pair, direction, i) attempts go into the next fused device batch and selects
-// results in the reference's candidate order, exactly like imagestitch_amd/grid.py:GridRegistrar.chain, whose behaviour it
-// reproduces decision for decision (tests/test_grid_registrar.py runs both against the sequential search on random truth tables
-// through vfsms_pairs_offsets_eval, which takes the attempt evaluator as a callback and needs no GPU).
+// results in the reference's candidate order.  This is the only copy of that machine: every route of imagestitch_amd/grid.py runs it,
+// over the device evaluator below (vfsms_pairs_offsets, _blind) or over a caller's evaluator (vfsms_pairs_offsets_eval, _blind_eval:
+// operators without a device evaluator such as SIFT, and the CPU tests).  Its specification is tests/chain_ref.py, a plain Python
+// chain that never loads the library; tests/test_grid_registrar.py holds the two to the same rows, the same attempts in the same
+// order and the same batch count on random truth tables, and both to the sequential search.
 //
 //   * an attempt is a pure function of (pair, direction, i): what is evaluated together is free, the accepted candidate is always
 //     the first one in the order  for i in 1..maxI-1 { d = d0; do { (d, i); d = rotate(d) } while (d != d0) }   (Stitcher.py:319-351);
@@ -82,9 +84,8 @@ struct Chain {
         n_attempts += (long long)todo.size(); n_batches += 1;
         for (size_t n = 0; n < todo.size(); n++) {
             const int32_t *r = &rows[n * VFSMS_ATTEMPT_INTS];
-            Attempt a;
-            if (P->method == 2) { a.ok = r[0] != 0; a.a = r[1]; a.b = r[2]; a.v = 0; }                 // phase: evaluator applied the response gate
-            else { a.ok = r[0] != 0 && r[4] > 0 && r[5] > 0; a.a = r[1]; a.b = r[2]; a.v = r[3]; }   // features: an image without keypoints never matches
+            // one rule for every method: an image without keypoints never matches (a phase evaluator reports nA = nB = 1, votes 0)
+            Attempt a; a.ok = r[0] != 0 && r[4] > 0 && r[5] > 0; a.a = r[1]; a.b = r[2]; a.v = r[3];
             cache[Key(todo[n].pair, todo[n].direction, todo[n].i)] = a;
         }
         return VFSMS_OK;
@@ -140,7 +141,7 @@ struct Chain {
                 std::vector<Key> items;
                 if (P->path_hint && P->path_hint_len > 0) {
                     // the predicted directions as the plan itself: the run at the current direction up to the predicted change, the candidate
-                    // ring of that pair up to the predicted new direction, the next run, ... (grid.py: plan_hint)
+                    // ring of that pair up to the predicted new direction, the next run, ...
                     int cd = d;
                     for (int kk = k; kk < last && kk < (int)P->path_hint_len && (int)items.size() < window; kk++) {
                         const int hd = P->path_hint[kk];
@@ -317,7 +318,7 @@ int device_eval(void *user, const vfsms_attempt_key *items, int n, int32_t *rows
         }
         return VFSMS_OK;
     }
-    vfsms_set_error("pairs_offsets: method must be 0 (surf), 1 (orb) or 2 (phase)");
+    vfsms_set_error("pairs_offsets: the device evaluator knows methods 0 (surf), 1 (orb) and 2 (phase); 3 (sift) needs a caller's evaluator");
     return VFSMS_ERR_BAD_ARG;
 }
 
@@ -387,26 +388,32 @@ extern "C" int vfsms_pairs_offsets_blind_eval(vfsms_attempt_eval eval, void *use
     return VFSMS_OK;
 }
 
-extern "C" int vfsms_pairs_offsets_blind(vfsms_ctx *ctx, const int64_t *tiles, const int32_t *shapes_hw, int n_tiles, int first_pair, int last_pair,
-                                         int per, const vfsms_grid_params *p, int32_t *out, int32_t *direction_out, int64_t *stats)
+// the device-evaluated entry points: `chain` is the matching *_eval entry point bound to its remaining arguments
+template <class F>
+static int with_device_eval(vfsms_ctx *ctx, const int64_t *tiles, const int32_t *shapes_hw, const vfsms_grid_params *p, int64_t *stats, F chain)
 {
     if (!ctx || !tiles) { vfsms_set_error("pairs_offsets: null context / tiles"); return VFSMS_ERR_BAD_ARG; }
     DeviceEval E; E.ctx = ctx; E.tiles = tiles; E.shapes = shapes_hw; E.P = p;
     g_ready_for_next_chain = device_ready;
-    const int rc = vfsms_pairs_offsets_blind_eval(device_eval, &E, shapes_hw, n_tiles, first_pair, last_pair, per, p, out, direction_out, stats);
+    const int rc = chain(&E);
     if (stats) { stats[2] = E.cap_retries; stats[3] = E.sum_nq_nt; stats[4] = E.sum_nq_plus_nt; stats[5] = E.roi_px; }
     return rc;
+}
+
+extern "C" int vfsms_pairs_offsets_blind(vfsms_ctx *ctx, const int64_t *tiles, const int32_t *shapes_hw, int n_tiles, int first_pair, int last_pair,
+                                         int per, const vfsms_grid_params *p, int32_t *out, int32_t *direction_out, int64_t *stats)
+{
+    return with_device_eval(ctx, tiles, shapes_hw, p, stats, [&](void *E) {
+        return vfsms_pairs_offsets_blind_eval(device_eval, E, shapes_hw, n_tiles, first_pair, last_pair, per, p, out, direction_out, stats);
+    });
 }
 
 extern "C" int vfsms_pairs_offsets(vfsms_ctx *ctx, const int64_t *tiles, const int32_t *shapes_hw, int n_tiles, int first_pair, int last_pair,
                                    int direction_in, int midpath, int stop_on_fail, const vfsms_grid_params *p, int32_t *out,
                                    int32_t *direction_out, int64_t *stats)
 {
-    if (!ctx || !tiles) { vfsms_set_error("pairs_offsets: null context / tiles"); return VFSMS_ERR_BAD_ARG; }
-    DeviceEval E; E.ctx = ctx; E.tiles = tiles; E.shapes = shapes_hw; E.P = p;
-    g_ready_for_next_chain = device_ready;
-    const int rc = vfsms_pairs_offsets_eval(device_eval, &E, shapes_hw, n_tiles, first_pair, last_pair, direction_in, midpath, stop_on_fail, p, out,
-                                            direction_out, stats);
-    if (stats) { stats[2] = E.cap_retries; stats[3] = E.sum_nq_nt; stats[4] = E.sum_nq_plus_nt; stats[5] = E.roi_px; }
-    return rc;
+    return with_device_eval(ctx, tiles, shapes_hw, p, stats, [&](void *E) {
+        return vfsms_pairs_offsets_eval(device_eval, E, shapes_hw, n_tiles, first_pair, last_pair, direction_in, midpath, stop_on_fail, p, out,
+                                        direction_out, stats);
+    });
 }

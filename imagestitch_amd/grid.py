@@ -17,6 +17,7 @@ while keeping the GPU full:
 """
 import numpy as np
 
+from ._lib import Engine, pairs_offsets_blind_eval, pairs_offsets_eval
 from .utility import roi_rect, vote_tail
 
 RESULT_INTS = 6   # status, dx, dy, direction, i, votes
@@ -43,7 +44,7 @@ class GridRegistrar:
         self.directIncre = directIncre
         self.params = siftParams if method == "sift" else surfParams      # the parameter record of the method's fused batch (None: its defaults)
         if method == "sift":
-            self.native = False       # vfsms_pairs_offsets knows methods 0..2 (vfsms_grid_params has no SIFT record): the chain runs here, on attempt_sift_batch
+            self.native = False       # the library's device evaluator knows methods 0..2: its machine runs over attempt_sift_batch (_attempts)
         self.phaseThr = phaseResponseThreshold
         self.window = max(1, int(window))
         self.enhance = tuple(enhance)                     # (mode, clipLimit, tileSize) of Method.isEnhance (Stitcher.py:327-334)
@@ -89,7 +90,8 @@ class GridRegistrar:
 
     # -- one batch of attempts -----------------------------------------------------------------------------------
     def _attempts(self, handles, shapes, items):
-        """items: [(pair index k, direction, i)] -> [(status, raw_dx, raw_dy, votes)]"""
+        """items: [(pair index k, direction, i)] -> int32[n, 8] evaluator rows {status, raw dx, raw dy, votes, nA, nB, ...} (the layout
+        vfsms_attempt_eval defines, include/vfsms.h)"""
         jobs = []
         for (k, d, i) in items:
             ra = roi_rect(shapes[k], d, "first", i * self.roiRatio)
@@ -100,27 +102,23 @@ class GridRegistrar:
             self.stats["roi_px"] += 2 * ra[2] * ra[3]
         self.stats["attempts"] += len(jobs)
         self.stats["batches"] += 1
+        if self.method == "phase":
+            # offset = [int(y), int(x)] (truncation); accepted when response > threshold (Stitcher.py:231-236); votes 0, nA = nB = 1
+            return np.array([[r[2] > self.phaseThr, int(r[1]), int(r[0]), 0, 1, 1, 0, 0] for r in self.eng.attempt_phase_batch(jobs)],
+                            np.int32).reshape(len(jobs), 8)
+        batch = {"surf": self._surf_batch,
+                 "orb": lambda j: self.eng.attempt_orb_batch(j, self.params, getattr(self, "orbMaxDistance", -1), self.offsetEvaluate),
+                 "sift": lambda j: self.eng.attempt_sift_batch(j, self.params, self.searchRatio, self.offsetEvaluate)}.get(self.method)
+        if batch is None:
+            raise ValueError("method %r" % (self.method,))
+        with self._estimator():
+            rows = batch(jobs)
         if self.method == "surf":
-            with self._estimator():
-                rows = self._surf_batch(jobs)
             nq = rows[:, 4].astype(np.int64); nt = rows[:, 5].astype(np.int64)
             self.stats["sum_nq_nt"] += int((nq * nt).sum())
             self.stats["sum_nq_plus_nt"] += int((nq + nt).sum())
             self.stats["sum_nq"] += int(nq.sum())
-            return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
-        if self.method == "orb":
-            with self._estimator():
-                rows = self.eng.attempt_orb_batch(jobs, self.params, getattr(self, "orbMaxDistance", -1), self.offsetEvaluate)
-            return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
-        if self.method == "sift":
-            with self._estimator():
-                rows = self.eng.attempt_sift_batch(jobs, self.params, self.searchRatio, self.offsetEvaluate)
-            return [(bool(r[0]) and r[4] > 0 and r[5] > 0, int(r[1]), int(r[2]), int(r[3])) for r in rows]
-        if self.method == "phase":
-            rows = self.eng.attempt_phase_batch(jobs)
-            # offset = [int(y), int(x)] (truncation); accepted when response > threshold (Stitcher.py:231-236)
-            return [(bool(r[2] > self.phaseThr), int(r[1]), int(r[0]), 0) for r in rows]
-        raise ValueError("method %r" % (self.method,))
+        return rows
 
     def _surf_batch(self, jobs):
         """Fused batch with an adaptive keypoint capacity: kernels are launched over capacity-sized grids (no host
@@ -159,178 +157,32 @@ class GridRegistrar:
             return self.eng.attempt_surf_batch_enhanced(jobs, self.params, self.searchRatio, self.offsetEvaluate, self.enhance)
         return self.eng.attempt_surf_batch(jobs, self.params, self.searchRatio, self.offsetEvaluate)
 
-    def _correct(self, raw, d, i, shapeA, shapeB):
-        """Stitcher.py:352-360: ROI-relative vote -> full-tile offset."""
-        dx, dy = raw
-        if d == 1:
-            dx = dx + shapeA[0] - int(i * self.roiRatio * shapeA[0])
-        elif d == 2:
-            dy = dy + shapeA[1] - int(i * self.roiRatio * shapeA[1])
-        elif d == 3:
-            dx = dx - (shapeB[0] - int(i * self.roiRatio * shapeB[0]))
-        elif d == 4:
-            dy = dy - (shapeB[1] - int(i * self.roiRatio * shapeB[1]))
-        return dx, dy
-
     # -- sequentially-equivalent chain over pairs [first, last) ------------------------------------------------------
-    def chain(self, handles, shapes, first, last, d_in, memo=None, cache=None, midpath=False, stop_on_fail=False, hint=None):
-        """-> (int32[last-first, 6], d_out).
+    native = True      # True: chains evaluated on the device inside the library (vfsms_pairs_offsets*) where the engine offers them;
+    #                    False, or an engine without them: the same machine of the library over this registrar's _attempts
 
-        An attempt is a pure function of (pair, direction, i), so WHICH attempts are evaluated together is free;
-        the result is always selected in the reference's candidate order.  What is batched is chosen by a small
-        predictor fed with the history of this chain: the length of the run of pairs that kept the direction
-        (shooting paths are serpentines: long run, turn, long run, ...) bounds the speculation window, a predicted
-        turn gets its whole first candidate ring in one batch, and the ring position that resolved the last turn
-        from the same incoming direction bounds the first resolve batch.
-        memo: {(k, d): (row, d_next)} and cache: {(k, d, i): attempt} may be shared between chains."""
-        memo = {} if memo is None else memo
-        cache = {} if cache is None else cache
-        out = np.zeros((last - first, RESULT_INTS), np.int32)
+    def chain(self, handles, shapes, first, last, d_in, midpath=False, stop_on_fail=False, hint=None):
+        """-> (int32[last-first, 6], d_out): the library's candidate state machine (csrc/grid.hip; specification: tests/chain_ref.py) over
+        the engine's fused attempt batches.  The attempts and batches are counted by _attempts, not a second time from the library's."""
+        out, d_out, _st = pairs_offsets_eval(lambda items: self._attempts(handles, shapes, items), shapes, self._grid_params(hint, device=False),
+                                             first, last, d_in, midpath, stop_on_fail)
+        return out, d_out
 
-        def evaluate(items):
-            todo = [it for it in dict.fromkeys(items) if it not in cache and it[0] < last]
-            if todo:
-                for it, r in zip(todo, self._attempts(handles, shapes, todo)):
-                    cache[it] = r
+    def _one_chain(self, handles, shapes, first, last, d_in, midpath=False, stop_on_fail=False, hint=None):
+        """the chain of [first, last) by the route `native` selects"""
+        if not (self.native and hasattr(self.eng, "pairs_offsets")):
+            return self.chain(handles, shapes, first, last, d_in, midpath, stop_on_fail, hint)
+        with self._estimator():
+            out, d_out, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), first, last, d_in, midpath, stop_on_fail)
+        self._native_stats(st)
+        return out, d_out
 
-        runs, run_len, slow, ring_hint = [], 0, 1, {}
-        trans2 = {}                                   # (direction before, direction) -> direction the next turn led to
-        prev_d = 0
-        if hint is not None and len(hint) and first > 0:
-            # a chain that starts inside the path: prime the predictor with the history the predicted directions imply for the pairs
-            # before `first` (csrc/grid.hip does the same); bookkeeping only
-            hd = int(hint[0])
-            for kk in range(min(first, len(hint))):
-                nd = int(hint[kk])
-                if not (1 <= hd <= 4 and 1 <= nd <= 4):
-                    break
-                if nd == hd:
-                    run_len += 1
-                    slow = min(2 * slow, self.window)
-                else:
-                    runs.append(run_len)
-                    run_len, slow = 1, 1
-                    trans2[(prev_d, hd)] = nd
-                    ring0 = [c[0] for c in self.rings(hd)[0]]
-                    if nd in ring0:
-                        ring_hint[hd] = ring0.index(nd)
-                    prev_d = hd
-                hd = nd
-            if hd != d_in:                            # entered differently than predicted: no basis
-                runs, run_len, slow, ring_hint, trans2, prev_d = [], 0, 1, {}, {}, 0
-        d = d_in
-        k = first
-
-        def plan(k0, d0, p0):
-            """Predicted continuation of the path as one batch (up to `window` attempts): the rest of the current run, the
-            candidate ring of the predicted turn up to the direction it led to last time, the following run(s), ..."""
-            items, R, rl, cd, cp, kk = [], list(runs), run_len, d0, p0, k0
-            while kk < last and len(items) < self.window:
-                pred = R[-2] if len(R) >= 2 else None
-                if pred is None:
-                    break
-                remaining = pred - rl
-                if remaining < 0:
-                    break                                  # this run already outlived the prediction: no basis for a turn, slow start instead
-                if remaining >= 1:
-                    n = min(remaining, self.window - len(items), last - kk)
-                    items += [(kk + t, cd, 1) for t in range(n)]
-                    kk += n; rl += n
-                    if n < remaining:
-                        break
-                    continue
-                ring = self.rings(cd)[0]
-                nd = trans2.get((cp, cd))
-                if nd is None or all(c[0] != nd for c in ring):
-                    items += [(kk,) + c for c in ring[:ring_hint.get(cd, len(ring) - 1) + 1]]
-                    break
-                upto = [c[0] for c in ring].index(nd)
-                items += [(kk,) + c for c in ring[:upto + 1]]
-                R.append(rl); rl = 1
-                cp, cd = cd, nd
-                kk += 1
-            return items
-
-        def plan_hint(k0, d0):
-            """The predicted directions as the plan itself: the run at the current direction up to the predicted change, the candidate ring
-            of that pair up to the predicted new direction, the next run, ... -- what the history-driven plan arrives at after two
-            serpentine periods, available from the first pair on."""
-            items, cd, kk = [], d0, k0
-            while kk < last and kk < len(hint) and len(items) < self.window:
-                hd = int(hint[kk])
-                if not 1 <= hd <= 4:
-                    break
-                ring = self.rings(cd)[0]
-                ds = [c[0] for c in ring]
-                if hd == cd or hd not in ds:
-                    items.append((kk, cd, 1))
-                else:
-                    items += [(kk,) + c for c in ring[:ds.index(hd) + 1]]
-                    cd = hd
-                kk += 1
-            return items
-
-        while k < last:
-            if (k, d) in memo:
-                row, d_next = memo[(k, d)]
-            else:
-                rings = self.rings(d)
-                if (k, d, 1) not in cache:
-                    items = plan_hint(k, d) if hint is not None and len(hint) else []
-                    if not items:
-                        items = plan(k, d, prev_d)
-                    if not items:                              # no history yet: slow start
-                        items = [(kk, d, 1) for kk in range(k, min(k + slow, last)) if (kk, d) not in memo]
-                    evaluate(items)
-                    if (k, d, 1) not in cache:
-                        evaluate([(k, d, 1)])
-                found = None
-                for ri, ring in enumerate(rings):
-                    pos = 0
-                    while pos < len(ring) and found is None:
-                        if (k,) + ring[pos] not in cache:
-                            h = ring_hint.get(d, len(ring) - 1) if ri == 0 else len(ring) - 1
-                            stop = max(pos, min(h, len(ring) - 1))
-                            evaluate([(k,) + c for c in ring[pos:stop + 1]])
-                        st, a, b, v = cache[(k,) + ring[pos]]
-                        if st:
-                            found = ring[pos] + (a, b, v)
-                            if ri == 0:
-                                ring_hint[d] = pos
-                        pos += 1
-                    if found is not None:
-                        break
-                if found is not None:
-                    dd, ii, a, b, v = found
-                    dx, dy = self._correct((a, b), dd, ii, shapes[k], shapes[k + 1])
-                    row = np.array([1, dx, dy, dd, ii, v], np.int32)
-                    d_next = dd                       # self.direction = localDirection
-                else:
-                    row = np.array([0, 0, 0, d, 0, 0], np.int32)
-                    d_next = d                        # a failed pair leaves self.direction untouched
-                memo[(k, d)] = (row, d_next)
-            # predictor bookkeeping
-            if row[0] and d_next == d:
-                run_len += 1
-                # a chain that starts in the middle of a path sees a truncated run and a turn soon after: until it has seen two
-                # runs, an overshoot past that turn is all waste, so it speculates at most 4 pairs ahead
-                slow = min(2 * slow, 4 if (midpath and len(runs) < 2) else self.window)
-            elif row[0]:
-                runs.append(run_len)
-                run_len, slow = 1, 1
-                trans2[(prev_d, d)] = d_next
-                prev_d = d
-            out[k - first] = row
-            d = d_next
-            k += 1
-            if stop_on_fail and not row[0]:
-                break                             # flowStitch discards everything behind the first break (Stitcher.py:74-76)
-        return out, d
-
-    native = True      # run whole chains inside the library (vfsms_pairs_offsets) when the engine offers it; chain() is the same machine in Python
-
-    def _grid_params(self, hint=None):
+    def _grid_params(self, hint=None, device=True):
         kw = dict(hint=hint) if hint is not None else {}
+        if not device:
+            # for the library's machine over _attempts: the chain reads what it is given here and nothing else, the operator's parameters
+            # stay with _attempts.  Engine.grid_params is a staticmethod, so engines without grid_params of their own take this route too.
+            return Engine.grid_params(method=self.method, roiRatio=self.roiRatio, directIncre=self.directIncre, window=self.window, **kw)
         return self.eng.grid_params(method=self.method, roiRatio=self.roiRatio, searchRatio=self.searchRatio, offsetEvaluate=self.offsetEvaluate,
                                     directIncre=self.directIncre, window=self.window, surf=self.params if self.method == "surf" else None,
                                     orb=self.params if self.method == "orb" else None, phaseResponseThreshold=self.phaseThr,
@@ -395,12 +247,7 @@ class GridRegistrar:
         P = len(handles) - 1
         mem = self._memory_prediction(P, hint)
         hint = self._prediction(P, hint)
-        if self.native and hasattr(self.eng, "pairs_offsets"):
-            with self._estimator():
-                out, d, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), 0, P, direction, False, stop_on_fail)
-            self._native_stats(st)
-        else:
-            out, d = self.chain(handles, shapes, 0, P, direction, stop_on_fail=stop_on_fail, hint=hint)
+        out, d = self._one_chain(handles, shapes, 0, P, direction, stop_on_fail=stop_on_fail, hint=hint)
         if not stop_on_fail or bool(np.all(out[:, 0] == 1)):
             self._learn(out, mem, direction)
         return out, d
@@ -504,32 +351,25 @@ class GridRegistrar:
         dirs = [direction] if (self.directIncre == 0 or rank == 0) else [1, 2, 3, 4]
         if len(dirs) > 1 and hint is not None and not blind and 0 < lo <= len(hint) and int(hint[lo - 1]) in (1, 2, 3, 4):
             dirs = [int(hint[lo - 1])]
+        if hi <= lo:                                         # an empty chunk hands every direction through
+            d_out = np.zeros(4, np.int32)
+            d_out[[d - 1 for d in dirs]] = dirs
+            return np.concatenate([np.zeros(4 * per * RESULT_INTS, np.int32), d_out])
+        if len(dirs) > 1:
+            # the four blind chains inside the library (csrc/grid.hip: one head batch, shared cache and memo)
+            if self.native and hasattr(self.eng, "pairs_offsets_blind"):
+                with self._estimator():
+                    res, dn, st = self.eng.pairs_offsets_blind(handles, shapes, self._grid_params(), lo, hi, per)
+                self._native_stats(st)
+            else:
+                res, dn, _st = pairs_offsets_blind_eval(lambda items: self._attempts(handles, shapes, items), shapes, self._grid_params(device=False), lo, hi, per)
+            return np.concatenate([np.asarray(res, np.int32).reshape(-1), np.asarray(dn, np.int32)])
+        d_in = dirs[0]
+        res, dn = self._one_chain(handles, shapes, lo, hi, d_in, midpath=rank > 0, hint=hint)
         table = np.zeros((4, per, RESULT_INTS), np.int32)
         d_out = np.zeros(4, np.int32)
-        memo, cache = {}, {}
-        if len(dirs) > 1 and hi > lo and self.native and hasattr(self.eng, "pairs_offsets_blind"):
-            # the four blind chains inside the library (csrc/grid.hip: the same machine, shared cache and memo)
-            with self._estimator():
-                res, dn, st = self.eng.pairs_offsets_blind(handles, shapes, self._grid_params(), lo, hi, per)
-            self._native_stats(st)
-            return np.concatenate([np.asarray(res, np.int32).reshape(-1), np.asarray(dn, np.int32)])
-        if len(dirs) > 1 and hi > lo:
-            # the incoming direction is unknown here: every chain needs its own first candidate of the first pair, so all four
-            # are evaluated as one batch instead of being discovered one chain after the other
-            for it, r in zip([(lo, d, 1) for d in dirs], self._attempts(handles, shapes, [(lo, d, 1) for d in dirs])):
-                cache[it] = r
-        for d_in in dirs:
-            if hi > lo and len(dirs) == 1 and self.native and hasattr(self.eng, "pairs_offsets"):
-                with self._estimator():
-                    res, dn, st = self.eng.pairs_offsets(handles, shapes, self._grid_params(hint), lo, hi, d_in, rank > 0, False)
-                self._native_stats(st)
-                table[d_in - 1, :hi - lo] = res
-            elif hi > lo:
-                res, dn = self.chain(handles, shapes, lo, hi, d_in, memo, cache, midpath=rank > 0, hint=hint if len(dirs) == 1 else None)
-                table[d_in - 1, :hi - lo] = res
-            else:
-                dn = d_in
-            d_out[d_in - 1] = dn
+        table[d_in - 1, :hi - lo] = res
+        d_out[d_in - 1] = dn
         return np.concatenate([table.reshape(-1), d_out])
 
     def assemble(self, gathered, n_pairs, world, direction, weights=None, missing=None, hint=None):

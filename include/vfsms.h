@@ -352,7 +352,9 @@ int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
  * stop_on_fail != 0: stop behind the first pair that cannot be registered (flowStitch breaks there, Stitcher.py:74-76).              */
 typedef struct { int32_t pair, direction, i; } vfsms_attempt_key;
 typedef struct {
-    int32_t method;                  /* 0 SURF + BF-L2 + ratio + mode, 1 ORB + BF-Hamming + mode, 2 FP64 phase correlation        */
+    int32_t method;                  /* 0 SURF + BF-L2 + ratio + mode, 1 ORB + BF-Hamming + mode, 2 FP64 phase correlation,
+                                      * 3 SIFT; evaluator-supplied only (the *_eval entry points: the chain itself never reads `method`,
+                                      * vfsms_pairs_offsets and _blind refuse it)                                                   */
     int32_t offset_evaluate;         /* Method.offsetEvaluate                                                                      */
     int32_t direct_incre;            /* Stitcher.directIncre: 1, 0 or -1                                                           */
     int32_t window;                  /* speculation window (attempts per fused batch)                                              */
@@ -377,7 +379,9 @@ int vfsms_pairs_offsets(vfsms_ctx *ctx, const int64_t *tiles, const int32_t *sha
                         int direction_in, int midpath, int stop_on_fail, const vfsms_grid_params *p, int32_t *out,
                         int32_t *direction_out, int64_t *stats);
 /* The same state machine over a caller-supplied evaluator of fused batches (other operators; the CPU tests): eval fills
- * rows[n][VFSMS_ATTEMPT_INTS] = {status, raw dx, raw dy, votes, nA, nB, ...} for n attempts and returns VFSMS_OK.                   */
+ * rows[n][VFSMS_ATTEMPT_INTS] = {status, raw dx, raw dy, votes, nA, nB, ...} for n attempts and returns VFSMS_OK.  An attempt is
+ * accepted when status != 0 && nA > 0 && nB > 0, whatever the method: a phase evaluator applies its response gate itself (status =
+ * response > threshold, raw offsets truncated towards zero) and reports votes = 0, nA = nB = 1.                                     */
 typedef int (*vfsms_attempt_eval)(void *user, const vfsms_attempt_key *items, int n, int32_t *rows);
 int vfsms_pairs_offsets_eval(vfsms_attempt_eval eval, void *user, const int32_t *shapes_hw, int n_tiles, int first_pair, int last_pair,
                              int direction_in, int midpath, int stop_on_fail, const vfsms_grid_params *p, int32_t *out,

@@ -11,6 +11,7 @@ import pytest
 
 import imagestitch_amd as isa
 from imagestitch_amd.grid import GridRegistrar, split_segments
+from chain_ref import ChainRef
 from scripted import ScriptedAttemptEngine, random_truth
 
 SHAPE = (1000, 1400)
@@ -24,6 +25,20 @@ class SeqStitcher(isa.Stitcher):
         ra = isa.roi_rect(SHAPE, direction, "first", searchRatio); rb = isa.roi_rect(SHAPE, direction, "second", searchRatio)
         row = self.eng2.attempt_surf_batch([(self.k, self.k + 1, ra[0], ra[1], rb[0], rb[1], ra[2], ra[3])])[0]
         return (bool(row[0]), [int(row[1]), int(row[2])])
+
+
+def scripted_rows(accept, log):
+    """the truth table as an evaluator of fused batches (the rows ScriptedAttemptEngine answers), logging every attempt in order"""
+    def attempts(items):
+        rows = []
+        for (k, d, i) in items:
+            log.append((k, d, i))
+            acc = accept[k]
+            ok = (d, i) in acc
+            raw = acc[(d, i)] if ok else (7, -3)
+            rows.append([int(ok), raw[0], raw[1], 5 if ok else 1, 100, 100, 10, 0])
+        return rows
+    return attempts
 
 
 def sequential(accept, roiRatio, incre, d0):
@@ -119,7 +134,8 @@ def test_eight_process_gloo_config4_path(tmp_path):
 def test_native_pairs_offsets_state_machine_equals_python_and_sequential():
     """vfsms_pairs_offsets_eval -- the candidate state machine inside libvfsms.so (csrc/grid.hip), fed by a scripted evaluator through
     a C callback (no GPU): on random truth tables with failures, late successes and false-positive directions it must return the
-    rows of the sequential search AND evaluate exactly the batches the Python registrar evaluates (same attempts, same order)."""
+    rows of the sequential search AND evaluate exactly the batches its specification (tests/chain_ref.py) evaluates (same attempts, same
+    order)."""
     import imagestitch_amd as isa
     from imagestitch_amd._lib import pairs_offsets_eval, Engine
     for seed in range(40):
@@ -131,25 +147,15 @@ def test_native_pairs_offsets_state_machine_equals_python_and_sequential():
         d0 = int(rng.integers(1, 5))
         accept = random_truth(rng, P, roiRatio)
         seq, d_end, _ = sequential(accept, roiRatio, incre, d0)
-        eng = ScriptedAttemptEngine(SHAPE, roiRatio, accept)
-        reg = GridRegistrar(eng, roiRatio=roiRatio, directIncre=incre, window=window)
-        res_py, d_py = reg.chain(list(range(P + 1)), [SHAPE] * (P + 1), 0, P, d0)
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), [SHAPE] * (P + 1), roiRatio, incre, window)
+        res_py, d_py = ref.chain(0, P, d0)
         log = []
-
-        def attempts(items, accept=accept, log=log):
-            rows = []
-            for (k, d, i) in items:
-                log.append((k, d, i))
-                acc = accept[k]
-                ok = (d, i) in acc
-                raw = acc[(d, i)] if ok else (7, -3)
-                rows.append([int(ok), raw[0], raw[1], 5 if ok else 1, 100, 100, 10, 0])
-            return rows
         params = Engine.grid_params(method="surf", roiRatio=roiRatio, directIncre=incre, window=window)
-        res_c, d_c, st = pairs_offsets_eval(attempts, [SHAPE] * (P + 1), params, 0, P, d0)
+        res_c, d_c, st = pairs_offsets_eval(scripted_rows(accept, log), [SHAPE] * (P + 1), params, 0, P, d0)
         assert [list(r[:4]) for r in res_c.tolist()] == seq and d_c == d_end, (seed, res_c.tolist(), seq)
         assert np.array_equal(res_c, res_py) and d_c == d_py
-        assert log == eng.log and st[0] == len(log) == reg.stats["attempts"] and st[1] == reg.stats["batches"], (seed, len(log), len(eng.log))
+        assert log == ref_log and st[0] == len(log) == ref.stats["attempts"] and st[1] == ref.stats["batches"], (seed, len(log), len(ref_log))
     # stop_on_fail: nothing behind the first break is reported
     accept = [{(1, 1): (3, 3)}, {}, {(1, 1): (4, 4)}]
     res, d, _st = pairs_offsets_eval(lambda items: [[int((dd, i) in accept[k])] + ([3, 3, 5] if (dd, i) in accept[k] else [0, 0, 0]) + [9, 9, 4, 0] for (k, dd, i) in items],
@@ -159,7 +165,7 @@ def test_native_pairs_offsets_state_machine_equals_python_and_sequential():
 
 def test_native_blind_chains_equal_python_twin():
     """vfsms_pairs_offsets_blind_eval (csrc/grid.hip) -- the chunk of a rank > 0, registered for all four possible incoming directions with a
-    shared attempt cache and (pair, direction) memo -- against GridRegistrar.shard_payload's Python twin on random truth tables: the same
+    shared attempt cache and (pair, direction) memo -- against its specification (ChainRef.blind_payload) on random truth tables: the same
     payload (4 x per x 6 rows + 4 end directions), the same attempts in the same order, the same batch count; and the chain of the TRUE
     incoming direction equals the sequential search of that chunk."""
     from imagestitch_amd._lib import pairs_offsets_blind_eval, Engine
@@ -172,30 +178,19 @@ def test_native_blind_chains_equal_python_twin():
         rank = int(rng.integers(1, world))
         window = int(rng.choice([3, 8, 24]))
         accept = random_truth(rng, P, roiRatio)
-        eng = ScriptedAttemptEngine(SHAPE, roiRatio, accept)
-        reg = GridRegistrar(eng, roiRatio=roiRatio, directIncre=incre, window=window)
-        reg.native = False
         shapes = [SHAPE] * (P + 1)
-        pay_py = reg.shard_payload(list(range(P + 1)), shapes, 1, rank, world)
         bounds = GridRegistrar.chunk_bounds(P, world)
         lo, hi = bounds[rank]
         per = max(b - a for a, b in bounds)
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), shapes, roiRatio, incre, window)
+        pay_py = ref.blind_payload(lo, hi, per)
         log = []
-
-        def attempts(items, accept=accept, log=log):
-            rows = []
-            for (k, d, i) in items:
-                log.append((k, d, i))
-                acc = accept[k]
-                ok = (d, i) in acc
-                raw = acc[(d, i)] if ok else (7, -3)
-                rows.append([int(ok), raw[0], raw[1], 5 if ok else 1, 100, 100, 10, 0])
-            return rows
         params = Engine.grid_params(method="surf", roiRatio=roiRatio, directIncre=incre, window=window)
-        res, dn, st = pairs_offsets_blind_eval(attempts, shapes, params, lo, hi, per)
+        res, dn, st = pairs_offsets_blind_eval(scripted_rows(accept, log), shapes, params, lo, hi, per)
         pay_c = np.concatenate([np.asarray(res, np.int32).reshape(-1), np.asarray(dn, np.int32)])
         assert np.array_equal(pay_c, pay_py), (seed, lo, hi)
-        assert log == eng.log and st[0] == len(log) == reg.stats["attempts"] and st[1] == reg.stats["batches"], (seed, len(log), len(eng.log))
+        assert log == ref_log and st[0] == len(log) == ref.stats["attempts"] and st[1] == ref.stats["batches"], (seed, len(log), len(ref_log))
         for d_in in (1, 2, 3, 4):                              # every chain is the sequential search of the chunk entered with d_in
             seq, d_end, _ = sequential(accept[lo:hi], roiRatio, incre, d_in)
             assert [list(r[:4]) for r in res[d_in - 1][:hi - lo].tolist()] == seq and int(dn[d_in - 1]) == d_end, (seed, d_in)
@@ -259,7 +254,7 @@ def test_hint_removes_the_blind_start_cost_on_the_serpentine():
     """BASELINE configs[1]'s path (10 x 9 column serpentine, 89 pairs) over 8 ranks: with the scan pattern as hint the ranks together
     evaluate exactly the attempts of the sequential search (no blind starts, no slow speculation inside a chunk) and the busiest rank
     stays within 20 % of the mean -- 162 attempts, busiest 22 against a mean of 15.4 sequential, without the hint.  The native chains
-    (csrc/grid.hip through vfsms_pairs_offsets_eval) take the same decisions as the Python twin."""
+    (csrc/grid.hip through vfsms_pairs_offsets_eval) take the same decisions as the specification, whose attempt count is the one-GPU figure."""
     accept, dirs = [], []
     for c in range(9):
         d_col = 1 if c % 2 == 0 else 3
@@ -272,9 +267,8 @@ def test_hint_removes_the_blind_start_cost_on_the_serpentine():
         outs, regs = _lockstep_sharded(accept, 0.2, 1, 1, 8, 48, hint)
         assert all([list(r[:4]) for r in full.tolist()] == seq for full, _d in outs)
         res[hint is not None] = [r.stats["attempts"] for r in regs]
-    ref = GridRegistrar(ScriptedAttemptEngine(SHAPE, 0.2, accept), roiRatio=0.2, directIncre=1, window=48)
-    ref.native = False
-    ref.chain(list(range(90)), [SHAPE] * 90, 0, 89, 1)
+    ref = ChainRef(scripted_rows(accept, []), [SHAPE] * 90, 0.2, 1, 48)
+    ref.chain(0, 89, 1)
     one_gpu = ref.stats["attempts"]
     # with the prediction the ranks together evaluate exactly the attempts of the pair-by-pair search (the history-driven chain of one GPU
     # throws away two speculative ones while it learns the pattern)
@@ -283,7 +277,7 @@ def test_hint_removes_the_blind_start_cost_on_the_serpentine():
 
 
 def test_native_midpath_chain_primed_by_hint_equals_python_twin():
-    """vfsms_grid_params.path_hint (csrc/grid.hip) against GridRegistrar.chain(hint=...): a chain that starts inside the path with its
+    """vfsms_grid_params.path_hint (csrc/grid.hip) against ChainRef.chain(hint=...): a chain that starts inside the path with its
     predictor primed by the predicted history evaluates the same batches in the same order in both, and the rows are the sequential
     search of the chunk -- for right and for wrong hints."""
     from imagestitch_amd._lib import pairs_offsets_eval, Engine
@@ -297,24 +291,14 @@ def test_native_midpath_chain_primed_by_hint_equals_python_twin():
         hint = true_dirs if seed % 3 else [int(rng.integers(1, 5)) for _ in range(P)]
         lo = int(rng.integers(1, P - 2)); hi = int(rng.integers(lo + 1, P + 1))
         d_in = true_dirs[lo - 1]
-        eng = ScriptedAttemptEngine(SHAPE, roiRatio, accept)
-        reg = GridRegistrar(eng, roiRatio=roiRatio, directIncre=incre, window=window)
-        res_py, d_py = reg.chain(list(range(P + 1)), [SHAPE] * (P + 1), lo, hi, d_in, midpath=True, hint=hint)
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), [SHAPE] * (P + 1), roiRatio, incre, window)
+        res_py, d_py = ref.chain(lo, hi, d_in, midpath=True, hint=hint)
         log = []
-
-        def attempts(items, accept=accept, log=log):
-            rows = []
-            for (k, d, i) in items:
-                log.append((k, d, i))
-                acc = accept[k]
-                ok = (d, i) in acc
-                raw = acc[(d, i)] if ok else (7, -3)
-                rows.append([int(ok), raw[0], raw[1], 5 if ok else 1, 100, 100, 10, 0])
-            return rows
         params = Engine.grid_params(method="surf", roiRatio=roiRatio, directIncre=incre, window=window, hint=hint)
-        res_c, d_c, st = pairs_offsets_eval(attempts, [SHAPE] * (P + 1), params, lo, hi, d_in, True)
+        res_c, d_c, st = pairs_offsets_eval(scripted_rows(accept, log), [SHAPE] * (P + 1), params, lo, hi, d_in, True)
         assert np.array_equal(res_c, res_py) and d_c == d_py, seed
-        assert log == eng.log and st[1] == reg.stats["batches"], (seed, len(log), len(eng.log))
+        assert log == ref_log and st[1] == ref.stats["batches"], (seed, len(log), len(ref_log))
         assert [list(r[:4]) for r in res_c.tolist()] == seq[lo:hi]
 
 
@@ -454,7 +438,7 @@ def test_sharded_ranks_put_a_memory_on_probation_alike():
     each with a registrar of its own that lives from path to path -- must stay in step: same memory, same suspicion, same count of
     mispredictions after every path of the sequence A, A, B, A, B, A (10 x 9 and 9 x 10 serpentines: the same 89 pairs, turns elsewhere),
     and every path's table equals its sequential search whatever the memory said (repair rounds included).  Four ranks on threads with an
-    in-process all-gather, Python twin and native chains."""
+    in-process all-gather, evaluator route and device-evaluated chains."""
     import threading
     A, B = _serpentine_accept(10, 9), _serpentine_accept(9, 10)
     P, world = len(A), 4
@@ -562,3 +546,120 @@ def test_probation_bookkeeping_round_6():
     reg2.register(list(range(7)), [SHAPE] * 7, 3)
     reg2.register(list(range(7)), [SHAPE] * 7, 3)
     assert reg2.mispredictions == 0 and not reg2.path_suspect
+
+
+# ---- the production evaluator route: the library's machine over GridRegistrar._attempts ------------------------------------------------
+def test_registrar_evaluator_route_equals_the_specification():
+    """GridRegistrar(engine without pairs_offsets).register: the library's machine over the engine's fused batches gives the rows and the
+    end direction of tests/chain_ref.py, the engine sees the same attempts in the same order, and the registrar's attempt and batch counts
+    are the specification's (the library's own counts are not added a second time)."""
+    for seed in range(40):
+        rng = np.random.default_rng(1000 + seed)
+        roiRatio = float(rng.choice([0.1, 0.2]))
+        incre = int(rng.choice([-1, 0, 1]))
+        P = int(rng.integers(1, 40))
+        window = int(rng.choice([1, 3, 8, 24]))
+        d0 = int(rng.integers(1, 5))
+        accept = random_truth(rng, P, roiRatio)
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), [SHAPE] * (P + 1), roiRatio, incre, window)
+        res_ref, d_ref = ref.chain(0, P, d0)
+        eng = ScriptedAttemptEngine(SHAPE, roiRatio, accept)
+        reg = GridRegistrar(eng, roiRatio=roiRatio, directIncre=incre, window=window)
+        res, d = reg.register(list(range(P + 1)), [SHAPE] * (P + 1), d0)
+        assert np.array_equal(res, res_ref) and d == d_ref, seed
+        assert eng.log == ref_log, seed
+        assert (reg.stats["attempts"], reg.stats["batches"]) == (ref.stats["attempts"], ref.stats["batches"]), (seed, reg.stats, ref.stats)
+
+
+def test_registrar_blind_payload_equals_the_specification():
+    """shard_payload of a rank > 0 on the evaluator route against ChainRef.blind_payload: payload, attempt log and counts."""
+    for seed in range(30):
+        rng = np.random.default_rng(7000 + seed)
+        roiRatio = float(rng.choice([0.1, 0.2]))
+        incre = int(rng.choice([-1, 1]))
+        P = int(rng.integers(4, 60))
+        world = int(rng.integers(2, 5))
+        rank = int(rng.integers(1, world))
+        window = int(rng.choice([3, 8, 24]))
+        accept = random_truth(rng, P, roiRatio)
+        shapes = [SHAPE] * (P + 1)
+        bounds = GridRegistrar.chunk_bounds(P, world)
+        lo, hi = bounds[rank]
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), shapes, roiRatio, incre, window)
+        pay_ref = ref.blind_payload(lo, hi, max(b - a for a, b in bounds))
+        eng = ScriptedAttemptEngine(SHAPE, roiRatio, accept)
+        reg = GridRegistrar(eng, roiRatio=roiRatio, directIncre=incre, window=window)
+        pay = reg.shard_payload(list(range(P + 1)), shapes, 1, rank, world)
+        assert np.array_equal(pay, pay_ref), (seed, lo, hi)
+        assert eng.log == ref_log, seed
+        assert (reg.stats["attempts"], reg.stats["batches"]) == (ref.stats["attempts"], ref.stats["batches"]), (seed, reg.stats, ref.stats)
+
+
+def test_an_exception_of_the_engine_crosses_the_library_as_itself():
+    """what an engine's batch raises inside the library's callback comes out of register() as that very object, not wrapped in a
+    VfsmsError; the registrar registers the next path as usual"""
+    accept = [{(1, 1): (3, 3)}, {(1, 1): (4, 4)}, {(1, 1): (5, 5)}]
+    boom = KeyError("the engine's own exception")
+
+    class Failing(ScriptedAttemptEngine):
+        fail = True
+
+        def attempt_surf_batch(self, jobs, params=None, ratio=0.75, offset_evaluate=3):
+            if self.fail:
+                raise boom
+            return super().attempt_surf_batch(jobs, params, ratio, offset_evaluate)
+    eng = Failing(SHAPE, 0.2, accept)
+    reg = GridRegistrar(eng, roiRatio=0.2, directIncre=1, window=8)
+    with pytest.raises(KeyError) as caught:
+        reg.register(list(range(4)), [SHAPE] * 4, 1)
+    assert caught.value is boom
+    eng.fail = False
+    res, d = reg.register(list(range(4)), [SHAPE] * 4, 1)
+    assert [list(r[:4]) for r in res.tolist()] == sequential(accept, 0.2, 1, 1)[0] and d == 1
+
+
+def test_phase_rows_apply_the_response_gate_and_truncate():
+    """method "phase" on the evaluator route (Stitcher.py:231-236): accepted when response > threshold -- a response equal to the threshold
+    is rejected, the next float above it accepted -- and offset = [int(y), int(x)], truncated towards zero: raw (y, x) = (-3.7, 2.9) is
+    (dx, dy) = (-3, 2) before the direction's correction."""
+    thr = 0.15
+    H, W = 100, 120
+
+    class PhaseEngine:
+        def __init__(self, response):
+            self.response, self.jobs = response, 0
+
+        def attempt_phase_batch(self, jobs):
+            self.jobs += len(jobs)
+            return np.array([[2.9, -3.7, self.response]] * len(jobs), np.float64)      # x, y, response
+    for response, ok in ((thr, False), (float(np.nextafter(thr, 1.0)), True)):
+        eng = PhaseEngine(response)
+        reg = GridRegistrar(eng, method="phase", roiRatio=0.2, directIncre=1, phaseResponseThreshold=thr, window=4)
+        res, d = reg.register([1, 2], [(H, W)] * 2, 1)
+        if ok:
+            assert res.tolist() == [[1, -3 + H - int(0.2 * H), 2, 1, 1, 0]] and d == 1 and eng.jobs == 1
+        else:
+            assert res.tolist() == [[0, 0, 0, 1, 0, 0]] and d == 1 and eng.jobs == 4 * (reg.maxI() - 1)     # every candidate tried, none accepted
+        assert reg.stats["attempts"] == eng.jobs
+
+
+def test_sift_registrar_runs_the_library_machine_over_the_sift_batch():
+    """method "sift" (native = False: no device evaluator) on the fake of tests/test_sift_batch_host.py: the attempts the engine sees are
+    the specification's, in its order"""
+    from test_sift_batch_host import ScriptedSiftEngine
+    for seed in range(6):
+        rng = np.random.default_rng(300 + seed)
+        roiRatio = float(rng.choice([0.1, 0.2])); incre = int(rng.choice([-1, 1])); d0 = int(rng.integers(1, 5))
+        P = int(rng.integers(1, 40)); window = int(rng.choice([1, 8, 24]))
+        accept = random_truth(rng, P, roiRatio)
+        ref_log = []
+        ref = ChainRef(scripted_rows(accept, ref_log), [SHAPE] * (P + 1), roiRatio, incre, window)
+        res_ref, d_ref = ref.chain(0, P, d0)
+        eng = ScriptedSiftEngine(SHAPE, roiRatio, accept)
+        reg = GridRegistrar(eng, method="sift", roiRatio=roiRatio, directIncre=incre, window=window)
+        assert not reg.native
+        res, d = reg.register(list(range(P + 1)), [SHAPE] * (P + 1), d0)
+        assert np.array_equal(res, res_ref) and d == d_ref and eng.log == ref_log, seed
+        assert (reg.stats["attempts"], reg.stats["batches"]) == (ref.stats["attempts"], len(eng.calls)) == (len(ref_log), ref.stats["batches"])

@@ -195,11 +195,12 @@ class GenericOnly:
         return getattr(self.base, name)
 
 
-def test_registrar_equals_the_per_pair_walk(engine):
-    from imagestitch_amd.grid import GridRegistrar
+@pytest.fixture(scope="module")
+def serpentine(engine):
+    """the 3 x 3 serpentine of 1024-px tiles, resident on the engine, and the per-pair SIFT walk over it (computed once)
+    -> (tiles, handles, shapes, truth, walk rows, end direction of the walk, the walking Stitcher)"""
     g = SyntheticGrid(3, 3, 1024)
     tiles = g.tiles(threads=4)
-    truth = g.true_offsets()
     st = isa.Stitcher(); st._engine = GenericOnly(engine)
     st.featureMethod = "sift"; st.roiRatio = 0.2; st.isPrintLog = False; st.direction = 1
     assert not st._usesStockOperators()
@@ -209,18 +210,48 @@ def test_registrar_equals_the_per_pair_walk(engine):
         assert ok, k
         walk.append([1, int(off[0]), int(off[1]), st.direction])
     hs = [engine.tile_upload(t) for t in tiles]
-    try:
-        reg = GridRegistrar(engine, method="sift", roiRatio=0.2, searchRatio=st.searchRatio, offsetEvaluate=st.offsetEvaluate,
-                            directIncre=st.directIncre, siftParams=st._siftParams())
-        table, d = reg.register(hs, [t.shape for t in tiles], 1)
-        again, _d = reg.register(hs, [t.shape for t in tiles], 1)                # with the path memory of the first run
-    finally:
-        for h in hs:
-            engine.tile_free(h)
-    assert [list(r[:4]) for r in table.tolist()] == walk and d == st.direction
+    yield tiles, hs, [t.shape for t in tiles], g.true_offsets(), walk, st.direction, st
+    for h in hs:
+        engine.tile_free(h)
+
+
+def _sift_registrar(engine, st):
+    from imagestitch_amd.grid import GridRegistrar
+    return GridRegistrar(engine, method="sift", roiRatio=0.2, searchRatio=st.searchRatio, offsetEvaluate=st.offsetEvaluate,
+                         directIncre=st.directIncre, siftParams=st._siftParams())
+
+
+def test_registrar_equals_the_per_pair_walk(engine, serpentine):
+    _tiles, hs, shapes, truth, walk, d_walk, st = serpentine
+    reg = _sift_registrar(engine, st)
+    table, d = reg.register(hs, shapes, 1)
+    again, _d = reg.register(hs, shapes, 1)                # with the path memory of the first run
+    assert [list(r[:4]) for r in table.tolist()] == walk and d == d_walk
     assert np.array_equal(table, again)
     for k, r in enumerate(table.tolist()):
         assert abs(r[1] - truth[k][0]) <= 1 and abs(r[2] - truth[k][1]) <= 1, (k, r, truth[k])
+
+
+def test_both_routes_of_the_registrar_run_one_machine(engine, serpentine):
+    """GridRegistrar.native selects the evaluator, never the machine: device-evaluated chains (vfsms_pairs_offsets) and the library's
+    machine over the engine's fused batches (vfsms_pairs_offsets_eval over GridRegistrar._attempts) give the same table, the same end
+    direction and the same attempt and batch counts for SURF, ORB and phase correlation, cold and with the path memory of the first run;
+    SIFT, which has the evaluator route only, gives the per-pair walk."""
+    from imagestitch_amd.grid import GridRegistrar
+    _tiles, hs, shapes, _truth, walk, d_walk, st = serpentine
+    for method in ("surf", "orb", "phase"):
+        got = []
+        for native in (True, False):
+            reg = GridRegistrar(engine, method=method, roiRatio=0.2, directIncre=1, window=8)
+            reg.native = native
+            runs = [reg.register(hs, shapes, 1) for _ in range(2)]
+            got.append(([t.tolist() for t, _d in runs], [int(d) for _t, d in runs], reg.stats["attempts"], reg.stats["batches"]))
+        print("%s: %d of %d pairs registered, %d attempts in %d batches over two runs" % (method, sum(r[0] for r in got[0][0][0]), len(hs) - 1, got[0][2], got[0][3]))
+        assert got[0] == got[1], (method, got)
+    reg = _sift_registrar(engine, st)
+    assert not reg.native
+    table, d = reg.register(hs, shapes, 1)
+    assert [list(r[:4]) for r in table.tolist()] == walk and d == d_walk
 
 
 def test_dendritic_pairs_through_the_fused_attempt(engine, golden_dir):
