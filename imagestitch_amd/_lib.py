@@ -170,6 +170,7 @@ _SIGNATURES = {
     "vfsms_features_match_offset_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "vfsms_canvas_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "vfsms_canvas_download_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_canvas_download_rows_pyramid": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "vfsms_tile_upload_ch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -992,6 +993,58 @@ class Engine:
             n = min(band_rows, rows - r0)
             out = ring[k % self.BAND_RING][:n * cols * ch].reshape((n, cols, ch) if ch > 1 else (n, cols))
             yield r0, self.canvas_download_rows(handle, r0, n, cols, ch, out=out)
+
+    @staticmethod
+    def pyramid_band_shapes(row0, nrows, cols, ch, levels):
+        """shapes of levels 1 .. levels of the band [row0, row0 + nrows) as vfsms_canvas_download_rows_pyramid lays them out"""
+        shapes, c = [], cols
+        for k in range(1, levels + 1):
+            c = (c + 1) >> 1
+            n = ((row0 + nrows + (1 << k) - 1) >> k) - (row0 >> k)
+            shapes.append((n, c, ch) if ch > 1 else (n, c))
+        return shapes
+
+    def _pyramid_rows(self, handle, row0, nrows, cols, ch, levels, band, buf):
+        """one vfsms_canvas_download_rows_pyramid call: rows into `band` (None: levels only), the levels into the u8 vector `buf` -> views"""
+        self._check(self.lib.vfsms_canvas_download_rows_pyramid(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(levels),
+                                                                _ptr(band), _ptr(buf), C.c_size_t(buf.size)))
+        out, off = [], 0
+        for shape in self.pyramid_band_shapes(row0, nrows, cols, ch, levels):
+            n = int(np.prod(shape))
+            out.append(buf[off:off + n].reshape(shape)); off += n
+        return out
+
+    def canvas_pyramid(self, handle, rows, cols, ch, levels):
+        """levels 1 .. levels of the whole mosaic (tests/pyramid_ref.py: pyramid_levels of canvas_download), formed on the device in one
+        call over all rows; level 0 is not downloaded."""
+        if not 1 <= int(levels) <= 10:
+            raise ValueError("canvas_pyramid: levels must be 1..10")
+        need = sum(int(np.prod(s_)) for s_ in self.pyramid_band_shapes(0, rows, cols, ch, int(levels)))
+        return self._pyramid_rows(handle, 0, rows, cols, ch, int(levels), None, np.empty(need, np.uint8))
+
+    def canvas_download_pyramid_bands(self, handle, rows, cols, ch, levels, band_rows=4096, transient=False):
+        """Generator of (row0, band, [level-1 rows, ..., level-`levels` rows]) over the whole mosaic: canvas_download_bands plus the reduced
+        levels of every band, formed on the device while the band is in HBM anyway (vfsms_canvas_download_rows_pyramid).  band_rows must be
+        a multiple of 2^levels, so that every band forms complete level rows.  With `transient` band and levels are views of ONE slot of the
+        ring of BAND_RING pinned buffers and valid as long as a band of canvas_download_bands is."""
+        levels, band_rows = int(levels), int(band_rows)
+        if not 1 <= levels <= 10:
+            raise ValueError("canvas_download_pyramid_bands: levels must be 1..10")
+        if band_rows <= 0 or band_rows % (1 << levels):
+            raise ValueError("canvas_download_pyramid_bands: band_rows = %d is not a multiple of 2^levels = %d" % (band_rows, 1 << levels))
+        shape = lambda n: (n, cols, ch) if ch > 1 else (n, cols)
+        nb0 = min(band_rows, rows) * cols * ch
+        need = nb0 + sum(int(np.prod(s_)) for s_ in self.pyramid_band_shapes(0, min(band_rows, rows), cols, ch, levels))
+        ring = None
+        if transient:
+            ring = self.__dict__.get("_band_ring")
+            if ring is None or ring[0].size < need:
+                ring = self.__dict__["_band_ring"] = [self.pinned_empty((need,)) for _ in range(self.BAND_RING)]
+        for k, r0 in enumerate(range(0, rows, band_rows)):
+            n = min(band_rows, rows - r0)
+            slot = ring[k % self.BAND_RING] if transient else np.empty(need, np.uint8)
+            band = slot[:n * cols * ch].reshape(shape(n))
+            yield r0, band, self._pyramid_rows(handle, r0, n, cols, ch, levels, band, slot[nb0:])
 
 
 _default_engine = None

@@ -248,8 +248,8 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     if (ctx->stream2) { hipStreamSynchronize(ctx->stream2); hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); }
-    if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); ctx->has_spare_canvas = false; }
+    for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); hipFree(kv.second.pyr); }
+    if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); hipFree(ctx->spare_canvas.pyr); ctx->has_spare_canvas = false; }
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
@@ -1811,7 +1811,7 @@ extern "C" int vfsms_canvas_free(vfsms_ctx *ctx, int64_t handle)
     if (ctx->has_spare_canvas) {                               // one spare at a time: the older one goes back to the device
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         CanvasRec &o = ctx->spare_canvas;
-        HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch));
+        HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch)); HIP_TRY(hipFree(o.pyr));
     }
     ctx->spare_canvas = *cv; ctx->has_spare_canvas = true;      // kept for a canvas of the same size (stream order makes the reuse safe)
     ctx->canvases.erase(handle);
@@ -2013,7 +2013,7 @@ static int canvas_read_rows(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int n
     const size_t pitch = (size_t)cv->cols * cv->ch;
     int err = 0;
     HIP_TRY(hipMemcpyAsync(&err, cv->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out, cv->pix + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
+    if (nrows > 0) HIP_TRY(hipMemcpyAsync(out, cv->pix + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (err) {
         vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
@@ -2038,6 +2038,39 @@ extern "C" int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int ro
     TRY(canvas_find(ctx, "canvas_download_rows", canvas, &cv));
     if (!out || row0 < 0 || nrows <= 0 || row0 + nrows > cv->rows) { vfsms_set_error("canvas_download_rows: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     return canvas_read_rows(ctx, cv, row0, nrows, out);
+}
+
+// the same rows (out0 may be NULL) and levels 1 .. `levels` of them (pyramid_kernels.hip, specified by tests/pyramid_ref.py) back to back in
+// out_levels: what a pyramidal writer needs of a band, with the canvas bytes read from HBM once and one synchronisation at the end.  The
+// band must produce complete level rows that depend on no other band: it starts at a multiple of 2^levels and is a multiple of 2^levels
+// rows long unless it ends at the last row
+extern "C" int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels,
+                                                  uint8_t *out0, uint8_t *out_levels, size_t cap_levels)
+{
+    CTX_ENTER(ctx);
+    const char *who = "canvas_download_rows_pyramid";
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    if (!out_levels || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    if (levels < 1 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 1..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    const int step = 1 << levels;
+    if (row0 % step) { vfsms_set_error("%s: row0 = %d is not a multiple of 2^levels = %d", who, row0, step); return VFSMS_ERR_BAD_ARG; }
+    if (nrows % step && row0 + nrows != cv->rows) {
+        vfsms_set_error("%s: nrows = %d is not a multiple of 2^levels = %d and the band does not end at the last row", who, nrows, step);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    const size_t need = pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, levels);
+    if (cap_levels < need) { vfsms_set_error("%s: the levels take %zu bytes, out_levels holds %zu", who, need, cap_levels); return VFSMS_ERR_BAD_ARG; }
+    if (cv->pyr_bytes < need) {                                 // first use, or a larger band than before
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipFree(cv->pyr)); cv->pyr = nullptr; cv->pyr_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&cv->pyr, need));
+        cv->pyr_bytes = need;
+    }
+    TRY(pyramid_band_device(ctx, cv, row0, nrows, levels, cv->pyr));
+    HIP_TRY(hipMemcpyAsync(out_levels, cv->pyr, need, hipMemcpyDeviceToHost, ctx->stream));
+    if (out0) return canvas_read_rows(ctx, cv, row0, nrows, out0);
+    return canvas_read_rows(ctx, cv, 0, 0, nullptr);             // (the sticky flag and the synchronisation alone)
 }
 
 // ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------

@@ -177,7 +177,7 @@ struct MatchDev {
 struct TileRec { uint8_t *ptr; int h, w, stride; bool owned; hipEvent_t ready; bool pending; int ch = 1; size_t bytes = 0; int fill = 0; };
 struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device staging of one decoded source image (vfsms_tile_fill_pair)
 struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
-struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; };   // d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; uint8_t *pyr = nullptr; size_t pyr_bytes = 0; };   // pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct ProfRec { int id; hipEvent_t a, b; };
@@ -337,6 +337,9 @@ struct ShadeTileHost { uint8_t *ptr; int stride; };
 int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, int percentile, int radius,
                           uint16_t *gain, uint16_t *q8, uint8_t *prof);
 int shade_apply_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, const uint16_t *gain);
+// pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
+size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
+int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);
 
 // sift_kernels.hip
 #define VFSMS_SIFT_MAX_LAYERS 8

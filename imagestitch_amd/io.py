@@ -269,6 +269,180 @@ class TiffBandWriter:
         self._f = None
 
 
+PYRAMID_MAX_LEVELS = 10
+
+
+def default_levels(rows, cols, tile):
+    """reduced levels of a pyramidal file: the smallest K >= 0 whose level K fits one tile, at most PYRAMID_MAX_LEVELS (tests/pyramid_ref.py)"""
+    K = 0
+    while K < PYRAMID_MAX_LEVELS and max(rows, cols) > tile:
+        rows, cols, K = (rows + 1) >> 1, (cols + 1) >> 1, K + 1
+    return K
+
+
+def _usable_cpus():
+    """host CPUs this process may use: its affinity set, capped by OMP_NUM_THREADS where the host sets it (os.cpu_count() reports the
+    whole machine, also to a process that was given a share of it)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
+    try:
+        cap = int(os.environ.get("OMP_NUM_THREADS") or 0)
+    except ValueError:
+        cap = 0
+    return max(1, min(n, cap) if cap > 0 else n)
+
+
+class PyramidTiffBandWriter:
+    """A `Stitcher.mosaicSink` for tiled pyramidal TIFF (BigTIFF beyond 4 GB), the layout OpenSlide, libvips, QuPath and GDAL read: level 0
+    in tiles of `tile` x `tile`, then levels 1 .. K as reduced-resolution pages (NewSubfileType 1), every level in an IFD of its own,
+    chained.  The levels are NOT computed here: they arrive with their band (`sink(row0, band, full_shape, levels=[...])`, formed on the
+    device by Engine.canvas_download_pyramid_bands; arithmetic: tests/pyramid_ref.py) and `pyramid_levels(full_shape)` tells the caller how
+    many to send -- `levels`, or the smallest count whose last level fits one tile.  Per level the rows that do not fill a tile row yet are
+    carried (a copy), a complete tile row is written at once, the directories behind the last band.  Tiles are row-major, edge tiles
+    padded with zeros; compression "none" or "deflate" (every tile a zlib stream, level 1, compressed on the encoder pool).  Bands are
+    B G R like the canvas; the file is R G B.  The file is written under a hidden name beside `path` and renamed when it is complete."""
+
+    transient_bands = True      # done with a band (and its levels) when the call returns
+
+    def __init__(self, path, tile=512, levels=None, compression="none", force_big=False):
+        if int(tile) <= 0 or int(tile) % 16:
+            raise ValueError("PyramidTiffBandWriter: tile must be a positive multiple of 16 (TIFF 6.0, TileWidth), got %r" % (tile,))
+        if compression not in ("none", "deflate"):
+            raise ValueError("PyramidTiffBandWriter: compression must be 'none' or 'deflate', got %r" % (compression,))
+        if levels is not None and not 0 <= int(levels) <= PYRAMID_MAX_LEVELS:
+            raise ValueError("PyramidTiffBandWriter: levels must be None or 0..%d, got %r" % (PYRAMID_MAX_LEVELS, levels))
+        self.path, self.tile, self.levels, self.compression, self.force_big = path, int(tile), levels, compression, force_big
+        self._f = None
+
+    def pyramid_levels(self, full_shape):
+        return int(self.levels) if self.levels is not None else default_levels(int(full_shape[0]), int(full_shape[1]), self.tile)
+
+    @property
+    def _part(self):
+        d, name = os.path.split(self.path)
+        return os.path.join(d, "." + name + ".part")
+
+    def _open(self, full_shape, K):
+        import struct
+        rows, cols = int(full_shape[0]), int(full_shape[1])
+        self._ch = int(full_shape[2]) if len(full_shape) == 3 else 1
+        if self._ch not in (1, 3):
+            raise ValueError("PyramidTiffBandWriter holds 1- or 3-channel images (this one: %s)" % (tuple(full_shape),))
+        T = self.tile
+        self._sizes = [(rows, cols)]
+        for _ in range(K):
+            r, c = self._sizes[-1]
+            self._sizes.append(((r + 1) >> 1, (c + 1) >> 1))
+        padded = sum(-(-r // T) * -(-c // T) * T * T * self._ch for r, c in self._sizes)
+        self._big = bool(self.force_big) or padded + (1 << 20) >= (1 << 32)
+        d = os.path.dirname(self.path)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        self._f = open(self._part, "wb")
+        self._f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 0) if self._big else struct.pack("<2sHI", b"II", 42, 0))
+        self._carry = [None] * (K + 1)
+        self._rows_in = [0] * (K + 1)
+        self._tiles = [[] for _ in range(K + 1)]                 # (offset, byte count) per tile, row-major
+
+    def _tile_row(self, k, strip):
+        """one row of tiles of level k from `strip` (<= tile rows, the level's full width, R G B), edge tiles zero-padded"""
+        import zlib
+        T, ch, f = self.tile, self._ch, self._f
+        ntx = -(-self._sizes[k][1] // T)
+        pad = np.zeros((T, ntx * T, ch), np.uint8)
+        pad[:strip.shape[0], :strip.shape[1]] = strip.reshape(strip.shape[0], strip.shape[1], ch)
+        tiles = np.ascontiguousarray(pad.reshape(T, ntx, T, ch).transpose(1, 0, 2, 3))          # [ntx][T][T][ch]
+        if self.compression == "none":
+            pos, nb = f.tell(), T * T * ch
+            f.write(tiles.data)
+            self._tiles[k] += [(pos + j * nb, nb) for j in range(ntx)]
+            return
+        pool = _encoder_pool(min(_usable_cpus(), 32))
+        for data in pool.map(lambda t: zlib.compress(t, 1), [tiles[j].data for j in range(ntx)]):
+            self._tiles[k].append((f.tell(), len(data)))
+            f.write(data)
+
+    def _feed(self, k, arr):
+        R, T = self._sizes[k][0], self.tile
+        arr = np.asarray(arr)
+        assert arr.shape[1] == self._sizes[k][1] and self._rows_in[k] + arr.shape[0] <= R, "level %d: rows beyond the level's size" % k
+        if arr.ndim == 3:
+            arr = arr[:, :, ::-1]
+        self._rows_in[k] += arr.shape[0]
+        last = self._rows_in[k] >= R
+        if self._carry[k] is not None:
+            arr = np.concatenate([self._carry[k], arr], 0)
+            self._carry[k] = None
+        full = arr.shape[0] if last else (arr.shape[0] // T) * T
+        for r in range(0, full, T):
+            self._tile_row(k, arr[r:min(r + T, full)])
+        if full < arr.shape[0]:
+            self._carry[k] = arr[full:].copy()                   # (the band's memory is the caller's again after this call)
+
+    def _directories(self):
+        import struct
+        f, big, ch = self._f, self._big, self._ch
+        ltype, lfmt, lsize = (16, "Q", 8) if big else (4, "I", 4)
+        field = 8 if big else 4
+        fmts = {3: "H", 4: "I", 16: "Q"}
+        ifds = []
+        for k, (rows, cols) in enumerate(self._sizes):
+            n = len(self._tiles[k])
+            assert n == -(-rows // self.tile) * -(-cols // self.tile), "level %d: %d tiles written" % (k, n)
+            tags = [(254, 4, [1 if k else 0]), (256, ltype, [cols]), (257, ltype, [rows]), (258, 3, [8] * ch),
+                    (259, 3, [8 if self.compression == "deflate" else 1]), (262, 3, [2 if ch == 3 else 1]), (277, 3, [ch]), (284, 3, [1]),
+                    (322, ltype, [self.tile]), (323, ltype, [self.tile]), (324, ltype, [o for o, _c in self._tiles[k]]),
+                    (325, ltype, [c for _o, c in self._tiles[k]])]
+            entries = []
+            for tag, ty, vals in tags:
+                data = struct.pack("<%d%s" % (len(vals), fmts[ty]), *vals)
+                # a value that fits the field sits IN it, left-justified (BitsPerSample 8, 8, 8: 6 bytes -- behind the tiles in classic TIFF, in
+                # the 8-byte field of BigTIFF, as TiffBandWriter documents); anything longer is stored in front of the directories
+                if len(data) > field:
+                    if f.tell() & 1:
+                        f.write(b"\0")
+                    pos = f.tell(); f.write(data)
+                    data = struct.pack("<" + lfmt, pos)
+                entries.append(struct.pack("<HH" + lfmt, tag, ty, len(vals)) + data.ljust(field, b"\0"))
+            ifds.append(entries)
+        if f.tell() & 1:
+            f.write(b"\0")
+        first = pos = f.tell()
+        for k, entries in enumerate(ifds):
+            size = (8 if big else 2) + len(entries) * (20 if big else 12) + lsize
+            nxt = pos + size if k + 1 < len(ifds) else 0
+            f.write(struct.pack("<Q" if big else "<H", len(entries))); f.write(b"".join(entries)); f.write(struct.pack("<" + lfmt, nxt))
+            pos += size
+        if not big and f.tell() >= (1 << 32):
+            raise ValueError("PyramidTiffBandWriter: the file outgrew classic TIFF's 4 GB; write it with force_big=True")
+        f.seek(8 if big else 4); f.write(struct.pack("<" + lfmt, first))
+
+    def __call__(self, row0, band, full_shape, levels=None):
+        levels = list(levels) if levels is not None else []
+        try:
+            if self._f is None:
+                K = self.pyramid_levels(full_shape)
+                if len(levels) != K:
+                    raise ValueError("PyramidTiffBandWriter: %d reduced levels expected with every band (pyramid_levels), got %d" % (K, len(levels)))
+                self._open(full_shape, K)
+            if len(levels) != len(self._sizes) - 1 or row0 != self._rows_in[0]:
+                raise ValueError("PyramidTiffBandWriter: bands arrive in order, each with its %d levels" % (len(self._sizes) - 1))
+            for k, arr in enumerate([band] + levels):
+                self._feed(k, arr)
+            if self._rows_in[0] < self._sizes[0][0]:
+                return
+            self._directories()
+            self._f.close()
+            self._f = None
+            os.replace(self._part, self.path)
+        except BaseException:
+            if self._f is not None:
+                self._f.close()
+                self._f = None
+            if os.path.exists(self._part):
+                os.remove(self._part)
+            raise
+
+
 def _native_jpeg_encoder():
     """does the library encode JPEG on this host (libjpeg.so.8 present, not switched off)?"""
     if os.environ.get("VFSMS_NATIVE_JPEG", "1") == "0":
@@ -280,10 +454,12 @@ def _native_jpeg_encoder():
         return False
 
 
-def band_writer_for(path):
+def band_writer_for(path, pyramid=None):
     """the streaming encoder for an output file name, or None when its format has none here (JPEG without libjpeg.so.8 on the host: written
-    whole through Pillow)"""
+    whole through Pillow).  pyramid: a dict of PyramidTiffBandWriter's keyword arguments -> the pyramidal writer for .tif / .tiff"""
     ext = os.path.splitext(path)[1].lower()
+    if pyramid is not None:
+        return PyramidTiffBandWriter(path, **pyramid) if ext in (".tif", ".tiff") else None
     if ext in (".jpg", ".jpeg"):
         return JpegBandWriter(path) if _native_jpeg_encoder() else None
     return PngBandWriter(path) if ext == ".png" else TiffBandWriter(path) if ext in (".tif", ".tiff") else NpyBandWriter(path) if ext == ".npy" else None

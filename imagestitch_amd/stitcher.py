@@ -63,7 +63,7 @@ class ResidentFeatures:
 from .ingest import (_imread, _imread_gray_pointer, _PillowBlocks, _decoder_pool, _decode_once, _fill_from_jpeg, _ycc_to_bgr, _imshape,  # noqa: F401
                      _list_images, TileIngest)
 from .io import (_imwrite, _imwrite_jpeg_stripes, NpyBandWriter, PngBandWriter, JpegBandWriter, TiffBandWriter, _NoNativeJpeg,  # noqa: F401
-                 _native_jpeg_encoder, band_writer_for)
+                 _native_jpeg_encoder, band_writer_for, PyramidTiffBandWriter)
 
 
 def _join(base, *parts):
@@ -152,23 +152,65 @@ class Stitcher(Utility.Method):
         if "mosaicSink" in self.__dict__:                    # the user streams the mosaics somewhere else (stitcher.mosaicSink = NpyBandWriter(...)): leave it alone
             return None
         probe = pattern % 0 if pattern else paths[0]
-        if band_writer_for(probe) is None:
+        # outputPyramid: every mosaic through the pyramidal writer, which takes the reduced levels of a band beside it
+        wkw = {"pyramid": self._pyramidOptions()} if self.outputPyramid else {}
+        first = band_writer_for(probe, **wkw)
+        if first is None:
             return None
         state = {"w": None, "n": 0}
 
-        def sink(row0, band, full_shape):
+        def sink(row0, band, full_shape, **lkw):
             if state["w"] is None:
                 path = (pattern % state["n"]) if pattern else paths[state["n"]]
                 if pattern:
                     paths.append(path)
                 state["n"] += 1
-                state["w"] = band_writer_for(path)
-            state["w"](row0, band, full_shape)
+                state["w"] = band_writer_for(path, **wkw)
+            state["w"](row0, band, full_shape, **lkw)
             if row0 + band.shape[0] >= full_shape[0]:
                 state["w"] = None
-        sink.transient_bands = bool(getattr(band_writer_for(probe), "transient_bands", False))
+        sink.transient_bands = bool(getattr(first, "transient_bands", False))
+        if hasattr(first, "pyramid_levels"):
+            sink.pyramid_levels = first.pyramid_levels
         self.mosaicSink = sink
         return sink
+
+    def _pyramidOptions(self):
+        """Method.pyramid* as PyramidTiffBandWriter's keyword arguments"""
+        return {"tile": self.pyramidTile, "levels": self.pyramidLevels, "compression": self.pyramidCompression}
+
+    def _checkPyramidOutput(self, outputfileExtension):
+        """Method.outputPyramid, judged before a file is listed or a tile decoded"""
+        if not self.outputPyramid:
+            return
+        if str(outputfileExtension).lower() not in ("tif", "tiff"):
+            raise ValueError("outputPyramid needs a .tif or .tiff output, got outputfileExtension = %r" % (outputfileExtension,))
+        if not self.streamOutput:
+            raise ValueError("outputPyramid needs streamOutput: the levels are formed from the bands as they leave the device")
+        if not hasattr(self.engine, "canvas_download_pyramid_bands"):
+            raise NotImplementedError("outputPyramid needs an engine with canvas_download_pyramid_bands")
+        PyramidTiffBandWriter("", **self._pyramidOptions())       # (pyramidTile, pyramidLevels, pyramidCompression: the writer's own refusals)
+        if self.pyramidLevels is not None:
+            self._pyramidBandRows(int(self.pyramidLevels))
+
+    def _pyramidBandRows(self, levels):
+        """mosaicBandRows for a pyramid of `levels` reduced levels: every band must form complete rows of every level"""
+        band_rows = int(getattr(self, "mosaicBandRows", 4096))
+        if band_rows <= 0 or band_rows % (1 << levels):
+            raise ValueError("a pyramid of %d reduced levels needs mosaicBandRows to be a multiple of %d, got %d" % (levels, 1 << levels, band_rows))
+        return band_rows
+
+    def _pyramidLevelsOf(self, full_shape):
+        """how many reduced levels the installed mosaicSink wants with every band of a mosaic of `full_shape` (a sink with `pyramid_levels`:
+        PyramidTiffBandWriter, or the user's own), or None: an ordinary sink, or none"""
+        sink = getattr(self, "mosaicSink", None)
+        if sink is None or not hasattr(sink, "pyramid_levels"):
+            return None
+        if not hasattr(self.engine, "canvas_download_pyramid_bands"):
+            raise NotImplementedError("a mosaicSink with pyramid_levels needs an engine with canvas_download_pyramid_bands")
+        levels = int(sink.pyramid_levels(full_shape))
+        self._pyramidBandRows(levels)
+        return levels
 
     def _decoderThreads(self, n_files):
         """size of the decoder pool: `decodeThreads`, or one per host core up to 32 when the library decodes JPEGs itself (measured on the
@@ -411,6 +453,7 @@ class Stitcher(Utility.Method):
 
     def imageSetStitch(self, projectAddress, outputAddress, fileNum, caculateOffsetMethod, startNum=1, fileExtension="jpg", outputfileExtension="jpg"):
         """Stitcher.py:129-151."""
+        self._checkPyramidOutput(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             fileList = _list_images(_join(projectAddress, i), fileExtension)
             outDir = outputAddress.replace("\\", os.sep)
@@ -443,6 +486,7 @@ class Stitcher(Utility.Method):
 
     def imageSetStitchWithMutiple(self, projectAddress, outputAddress, fileNum, caculateOffsetMethod, startNum=1, fileExtension="jpg", outputfileExtension="jpg"):
         """Stitcher.py:153-182 (the entry point Main.py:20-51 uses)."""
+        self._checkPyramidOutput(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             startTime = time.time()
             fileAddress = _join(projectAddress, i)
@@ -897,6 +941,8 @@ class Stitcher(Utility.Method):
             if not device_fuse and not simple:
                 return self._stitchWithHostFuse(fileList, imageList, originOffsetList, offsetList, rangeX, rangeY, resultRow, resultCol)
             ch = 3 if color else 1
+            full_shape = (resultRow, resultCol, ch) if ch > 1 else (resultRow, resultCol)
+            pyramid = self._pyramidLevelsOf(full_shape)         # (refuses before anything is fused)
             canvas = eng.canvas_create(resultRow, resultCol, ch)
             try:
                 if multiband:
@@ -922,8 +968,14 @@ class Stitcher(Utility.Method):
                     #  band; VFSMS_PINNED_BANDS=0 turns it off)
                     transient = bool(getattr(sink, "transient_bands", False)) and os.environ.get("VFSMS_PINNED_BANDS", "1") == "1"
                     kw = {"transient": True} if transient else {}
-                    for r0, band in eng.canvas_download_bands(canvas, resultRow, resultCol, ch, int(getattr(self, "mosaicBandRows", 4096)), **kw):
-                        sink(r0, band, (resultRow, resultCol, ch) if ch > 1 else (resultRow, resultCol))
+                    band_rows = int(getattr(self, "mosaicBandRows", 4096))
+                    if pyramid:                                  # a pyramidal sink: every band with its reduced levels, formed on the device
+                        for r0, band, levels in eng.canvas_download_pyramid_bands(canvas, resultRow, resultCol, ch, pyramid, band_rows, **kw):
+                            sink(r0, band, full_shape, levels=levels)
+                        return None
+                    lkw = {"levels": []} if pyramid is not None else {}     # (a mosaic that fits one tile: a pyramid of level 0 alone)
+                    for r0, band in eng.canvas_download_bands(canvas, resultRow, resultCol, ch, band_rows, **kw):
+                        sink(r0, band, full_shape, **lkw)
                     return None
                 return eng.canvas_download(canvas, resultRow, resultCol, ch)
             finally:

@@ -165,6 +165,16 @@ class Method():
     shadingMinTiles = 8
     shadingGain = None
 
+    # ---- pyramidal output (no reference counterpart; tests/pyramid_ref.py): imageSetStitch* write every mosaic as ONE tiled pyramidal
+    # TIFF (PyramidTiffBandWriter: level 0 in pyramidTile x pyramidTile tiles, then reduced-resolution pages, each half the size of the one
+    # before) that slide and micrograph viewers open without reading all of it.  The levels are formed on the device from the band that
+    # is leaving it anyway.  pyramidLevels None: as many as it takes for the last level to fit one tile (at most 10); pyramidCompression
+    # "none" or "deflate".  Needs a .tif / .tiff output, streamOutput, and mosaicBandRows a multiple of 2^levels
+    outputPyramid = False
+    pyramidTile = 512
+    pyramidLevels = None
+    pyramidCompression = "none"
+
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None
 

@@ -484,6 +484,18 @@ int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out);
 /* rows [row0, row0 + nrows) of the same image: a multi-GB mosaic leaves the device band by band and can be handed to an
  * incremental writer (the reference holds the whole int64 canvas and the u8 copy in host memory, Stitcher.py:434-436, 485-486) */
 int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, uint8_t *out);
+/* for writers of tiled multi-resolution files (Stitcher.outputPyramid, PyramidTiffBandWriter): the same rows to out0 (NULL: levels only)
+ * and reduced levels 1 .. levels of them to out_levels, back to back, level k as u8 [ceil((row0 + nrows) / 2^k) - (row0 >> k)][C_k][ch]
+ * with C_k = (C_{k-1} + 1) >> 1.  A sample of level k is (a + b + c + d + 2) >> 2 of the 2 x 2 block of level k - 1, edges replicated
+ * at every level against that level's own size, every level rounded once from the rounded level below.  No reference counterpart: the
+ * arithmetic, all integer, is this library's own specification, tests/pyramid_ref.py, and every level equals it exactly.  The levels
+ * are formed on the device in one pass over the band (pyramid_kernels.hip); one stream synchronisation ends the call.
+ * VFSMS_ERR_BAD_ARG: levels outside 1..VFSMS_PYRAMID_MAX_LEVELS, row0 not a multiple of 2^levels, nrows not a multiple of 2^levels unless
+ * the band ends at the last row (such a band forms complete level rows that depend on no other band), cap_levels (bytes of out_levels)
+ * too small, an unknown canvas; the sticky geometry flag as vfsms_canvas_download_rows                                                */
+#define VFSMS_PYRAMID_MAX_LEVELS 10
+int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels,
+                                       uint8_t *out0, uint8_t *out_levels, size_t cap_levels);
 
 /* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
  * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
