@@ -78,6 +78,10 @@ _SIGNATURES = {
     "vfsms_ctx_set_keypoint_capacity": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_ctx_set_offset_estimator": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "vfsms_ctx_set_offset_verifier": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    "vfsms_ctx_set_phase_resolver": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]),
+    "vfsms_attempt_phase_resolve_batch": (C.c_int, [C.c_void_p, C.POINTER(RoiPair), C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_phase_resolve_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_verify_ncc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_ncc_search_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -288,6 +292,38 @@ class Engine:
         status 1 iff score >= threshold, int 7 of the row is the fixed-point score; 0 / 1 as in include/vfsms.h."""
         ver = self.OFFSET_VERIFIERS[kind] if isinstance(kind, str) else int(kind)
         self._check(self.lib.vfsms_ctx_set_offset_verifier(self.ctx, ver, float(threshold), int(min_pixels)))
+
+    PHASE_RESOLVERS = {"none": 0, "ncc": 1}
+    PHASE_MAX_PEAKS = 8
+
+    def set_phase_resolver(self, kind="none", peaks=2, threshold=0.5, min_pixels=4096):
+        """How method "phase" of pairs_offsets / pairs_offsets_blind reads a correlation surface: "none" (default: the reference's arg-max,
+        sign and response gate) or "ncc" (tests/phase_resolve_ref.py: the `peaks` largest peaks, every circular reading scored by overlap
+        correlation, status = score >= threshold); 0 / 1 as in include/vfsms.h."""
+        res = self.PHASE_RESOLVERS[kind] if isinstance(kind, str) else int(kind)
+        self._check(self.lib.vfsms_ctx_set_phase_resolver(self.ctx, res, int(peaks), float(threshold), int(min_pixels)))
+
+    def attempt_phase_resolve_batch(self, jobs, peaks=2, threshold=0.5, min_pixels=4096):
+        """vfsms_attempt_phase_resolve_batch over resident tiles -> (rows int32[n, 8] = status, dx, dy, 0, 1, 1, winning candidate, fixed-point
+        score; cands int32[n, 4 peaks, 4] = dx, dy, fixed-point score, shared pixels; peak positions int32[n, peaks, 2] = uy, ux)"""
+        n, K = len(jobs), int(peaks)
+        rows = np.zeros((n, ATTEMPT_INTS), np.int32)
+        cands = np.zeros((n, 4 * max(K, 0), 4), np.int32)
+        pk = np.zeros((n, max(K, 0), 2), np.int32)
+        arr = jobs if isinstance(jobs, C.Array) else self.make_jobs(jobs) if n else None
+        self._check(self.lib.vfsms_attempt_phase_resolve_batch(self.ctx, arr, n, K, float(threshold), int(min_pixels), _ptr(rows), _ptr(cands), _ptr(pk)))
+        return rows, cands, pk
+
+    def phase_resolve(self, a, b, peaks=2, threshold=0.5, min_pixels=4096):
+        """vfsms_phase_resolve_u8 on two host strips of one shape -> (row int32[8], cands int32[4 peaks, 4], peak positions int32[peaks, 2])"""
+        a = _u8_2d(a); b = _u8_2d(b)
+        if a.shape != b.shape:
+            raise ValueError("phase_resolve: shapes differ")
+        K = int(peaks)
+        row = np.zeros(ATTEMPT_INTS, np.int32); cands = np.zeros((4 * max(K, 0), 4), np.int32); pk = np.zeros((max(K, 0), 2), np.int32)
+        self._check(self.lib.vfsms_phase_resolve_u8(self.ctx, _ptr(a), _ptr(b), a.shape[0], a.shape[1], a.strides[0], b.strides[0], K, float(threshold),
+                                                    int(min_pixels), _ptr(row), _ptr(cands), _ptr(pk)))
+        return row, cands, pk
 
     def verify_ncc(self, a, b, dx, dy, min_pixels=0):
         """vfsms_verify_ncc on two host strips of one shape and a raw vote (dx, dy) -> ((N, Sa, Sb, Saa, Sbb, Sab), score, fixed-point score)"""

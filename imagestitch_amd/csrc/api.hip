@@ -1,5 +1,6 @@
 // api.hip -- context management and the extern "C" entry points declared in include/vfsms.h.
 #include "common.h"
+#include "phase_resolve_math.h"
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -306,6 +307,17 @@ extern "C" int vfsms_ctx_set_offset_verifier(vfsms_ctx *ctx, int verifier, doubl
         return VFSMS_ERR_BAD_ARG;
     }
     ctx->offset_verifier = verifier; ctx->verify_threshold = threshold; ctx->verify_min_pixels = min_pixels;
+    return VFSMS_OK;
+}
+extern "C" int vfsms_ctx_set_phase_resolver(vfsms_ctx *ctx, int resolver, int peaks, double threshold, int min_pixels)
+{
+    if (!ctx) return VFSMS_ERR_BAD_ARG;
+    if (!phase_resolver_ok(resolver) || !phase_resolve_params_ok(peaks, threshold, min_pixels)) {
+        vfsms_set_error("set_phase_resolver: resolver %d / peaks %d / threshold %g / min_pixels %d (0 none or 1 ncc; 1..%d; -1..1; >= 0)", resolver, peaks,
+                        threshold, min_pixels, VFSMS_PHASE_MAX_PEAKS);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    ctx->phase_resolver = resolver; ctx->phase_peaks = peaks; ctx->phase_threshold = threshold; ctx->phase_min_pixels = min_pixels;
     return VFSMS_OK;
 }
 static int kp_capacity(vfsms_ctx *ctx, int h, int w)
@@ -1148,6 +1160,61 @@ extern "C" int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const 
     return VFSMS_OK;
 }
 
+// ---- phase correlation resolved by overlap correlation (phase_resolve_kernels.hip) -----------------------------------------------------
+// arena bytes of nb jobs of one strip shape, beyond the results
+static int phase_resolve_bytes(vfsms_ctx *ctx, int h, int w, int nb, int K, size_t *bytes)
+{
+    size_t pb = 0;
+    TRY(phase_bytes(ctx, h, w, nb, &pb));
+    *bytes = pb + phase_peaks_bytes(h, w, nb, K) + sizeof(double) * 3 * (size_t)nb + sizeof(PhasePeak) * (size_t)nb * K + phase_resolve_sums_bytes(nb, K) +
+             sizeof(PhaseJobHost) * (size_t)nb + 4096;
+    return VFSMS_OK;
+}
+// nb jobs of one strip shape: correlation with the peak sink, then the candidates; results at d_rows / d_cands / d_pk (device, nb records each)
+static int phase_resolve_group(vfsms_ctx *ctx, const PhaseJobHost *pj, int nb, int h, int w, int K, double threshold, int min_pixels,
+                               int32_t *d_rows, int32_t *d_cands, int32_t *d_pk)
+{
+    double *d_out3 = (double *)ctx_arena_alloc(ctx, sizeof(double) * 3 * (size_t)nb);
+    PhasePeak *d_peaks = (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)nb * K);
+    unsigned long long *d_sums = (unsigned long long *)ctx_arena_alloc(ctx, phase_resolve_sums_bytes(nb, K));
+    if (!d_out3 || !d_peaks || !d_sums) { vfsms_set_error("phase_resolve: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    PhaseJobHost *d_jobs = nullptr;
+    TRY(ctx_upload_small(ctx, pj, sizeof(PhaseJobHost) * (size_t)nb, (void **)&d_jobs));
+    const PhasePeakSink sink = {K, d_peaks};
+    TRY(phase_correlate_batch_device(ctx, pj, nb, h, w, d_out3, &sink));
+    int oM, oN;
+    phase_surface_size(h, w, &oM, &oN);
+    return launch_phase_resolve(ctx, d_jobs, d_peaks, nb, K, oM, oN, h, w, threshold, min_pixels, d_sums, d_rows, d_cands, d_pk);
+}
+
+extern "C" int vfsms_phase_resolve_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w, int stride_a, int stride_b,
+                                      int peaks, double threshold, int min_pixels, int32_t *row8, int32_t *cands, int32_t *peaks_out)
+{
+    CTX_ENTER(ctx);
+    if (!a || !b || !row8 || h <= 0 || w <= 0 || stride_a < w || stride_b < w || !phase_resolve_params_ok(peaks, threshold, min_pixels)) {
+        vfsms_set_error("phase_resolve: bad arguments"); return VFSMS_ERR_BAD_ARG;
+    }
+    size_t need = 0;
+    TRY(phase_resolve_bytes(ctx, h, w, 1, peaks, &need));
+    const size_t res = sizeof(int32_t) * (VFSMS_ATTEMPT_INTS + 16 * (size_t)peaks + 2 * (size_t)peaks);
+    TRY(ctx_arena_reserve(ctx, 2 * (size_t)h * w + need + res + 65536));
+    ctx->pinned_off = 0;
+    uint8_t *da, *db;
+    TRY(upload_image(ctx, a, h, w, stride_a, &da));
+    TRY(upload_image(ctx, b, h, w, stride_b, &db));
+    int32_t *d_rows = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS);
+    int32_t *d_cands = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 16 * (size_t)peaks);
+    int32_t *d_pk = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 2 * (size_t)peaks);
+    if (!d_rows || !d_cands || !d_pk) { vfsms_set_error("phase_resolve: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    PhaseJobHost j; j.a = da; j.b = db; j.sa = w; j.sb = w;
+    TRY(phase_resolve_group(ctx, &j, 1, h, w, peaks, threshold, min_pixels, d_rows, d_cands, d_pk));
+    HIP_TRY(hipMemcpyAsync(row8, d_rows, sizeof(int32_t) * VFSMS_ATTEMPT_INTS, hipMemcpyDeviceToHost, ctx->stream));
+    if (cands) HIP_TRY(hipMemcpyAsync(cands, d_cands, sizeof(int32_t) * 16 * (size_t)peaks, hipMemcpyDeviceToHost, ctx->stream));
+    if (peaks_out) HIP_TRY(hipMemcpyAsync(peaks_out, d_pk, sizeof(int32_t) * 2 * (size_t)peaks, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 static int resolve_job(vfsms_ctx *ctx, const vfsms_roi_pair &j, const uint8_t **pa, int *sa, const uint8_t **pb, int *sb)
 {
     auto ia = ctx->tiles.find(j.tile_a), ib = ctx->tiles.find(j.tile_b);
@@ -1327,6 +1394,58 @@ extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *j
     HIP_TRY(hipMemcpyAsync(tmp.data(), d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < n; k++) for (int c = 0; c < 3; c++) out[3 * order[k] + c] = tmp[3 * k + c];
+    return VFSMS_OK;
+}
+
+extern "C" int vfsms_attempt_phase_resolve_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, int peaks, double threshold, int min_pixels,
+                                                 int32_t *rows, int32_t *cands, int32_t *peaks_out)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n && (!jobs || !rows)) || !phase_resolve_params_ok(peaks, threshold, min_pixels)) {
+        vfsms_set_error("attempt_phase_resolve: bad arguments (peaks 1..%d, threshold -1..1, min_pixels >= 0)", VFSMS_PHASE_MAX_PEAKS); return VFSMS_ERR_BAD_ARG;
+    }
+    if (n == 0) return VFSMS_OK;
+    const int K = peaks;
+    const size_t RI = VFSMS_ATTEMPT_INTS, CI = 16 * (size_t)K, PI = 2 * (size_t)K;
+    const std::vector<int> order = shape_order(jobs, n);
+    auto shape_at = [&](int k) { return std::make_pair(jobs[order[k]].h, jobs[order[k]].w); };
+    size_t need = 0;
+    for (int g0 = 0, g1; g0 < n; g0 = g1) {
+        g1 = shape_run_end(g0, n, shape_at);
+        size_t pb = 0;
+        TRY(phase_resolve_bytes(ctx, jobs[order[g0]].h, jobs[order[g0]].w, g1 - g0, K, &pb));
+        need = std::max(need, pb);
+    }
+    TRY(ctx_arena_reserve(ctx, need + sizeof(int32_t) * (RI + CI + PI) * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    int32_t *d_rows = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * RI * n);      // in group order; un-permuted on the host
+    int32_t *d_cands = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * CI * n);
+    int32_t *d_pk = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * PI * n);
+    if (!d_rows || !d_cands || !d_pk) { vfsms_set_error("attempt_phase_resolve: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    const size_t mark = ctx->arena_off;
+    std::vector<PhaseJobHost> pj(n);
+    for (int g0 = 0, g1; g0 < n; g0 = g1) {
+        g1 = shape_run_end(g0, n, shape_at);
+        for (int k = g0; k < g1; k++) {
+            const uint8_t *pa, *pb; int sa, sb;
+            TRY(resolve_job(ctx, jobs[order[k]], &pa, &sa, &pb, &sb));
+            pj[k].a = pa; pj[k].b = pb; pj[k].sa = sa; pj[k].sb = sb;
+        }
+        ctx->arena_off = mark;                               // stream order makes scratch reuse safe
+        TRY(phase_resolve_group(ctx, pj.data() + g0, g1 - g0, jobs[order[g0]].h, jobs[order[g0]].w, K, threshold, min_pixels,
+                                d_rows + RI * g0, d_cands + CI * g0, d_pk + PI * g0));
+    }
+    std::vector<int32_t> tmp((RI + CI + PI) * (size_t)n);
+    int32_t *t_rows = tmp.data(), *t_cands = t_rows + RI * n, *t_pk = t_cands + CI * n;
+    HIP_TRY(hipMemcpyAsync(t_rows, d_rows, sizeof(int32_t) * RI * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (cands) HIP_TRY(hipMemcpyAsync(t_cands, d_cands, sizeof(int32_t) * CI * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (peaks_out) HIP_TRY(hipMemcpyAsync(t_pk, d_pk, sizeof(int32_t) * PI * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; k++) {
+        memcpy(rows + RI * order[k], t_rows + RI * k, sizeof(int32_t) * RI);
+        if (cands) memcpy(cands + CI * order[k], t_cands + CI * k, sizeof(int32_t) * CI);
+        if (peaks_out) memcpy(peaks_out + PI * order[k], t_pk + PI * k, sizeof(int32_t) * PI);
+    }
     return VFSMS_OK;
 }
 

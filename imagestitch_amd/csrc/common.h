@@ -180,6 +180,10 @@ struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed ti
 struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; uint8_t *pyr = nullptr; size_t pyr_bytes = 0; };   // pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
+struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent
+// where a correlation batch leaves the K largest peaks of every job's surface (phase_resolve_kernels.hip): peaks [nb][K]; the chunks' scratch
+// comes from the arena (phase_peaks_bytes)
+struct PhasePeakSink { int K; PhasePeak *peaks; };
 struct ProfRec { int id; hipEvent_t a, b; };
 struct ShadeRec { int h, w, ch; uint16_t *gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
 struct SiftChunk { char *p; size_t bytes, off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
@@ -194,6 +198,7 @@ struct vfsms_ctx {
     int kp_cap_override;
     int offset_estimator = VFSMS_OFFSET_MODE, offset_tol = 3;   // the vote tail of every fused path (vfsms_ctx_set_offset_estimator)
     int offset_verifier = VFSMS_VERIFY_NONE, verify_min_pixels = 0; double verify_threshold = 0.0;   // the acceptance check behind that tail (vfsms_ctx_set_offset_verifier)
+    int phase_resolver = VFSMS_PHASE_RESOLVE_NONE, phase_peaks = 2, phase_min_pixels = 4096; double phase_threshold = 0.5;   // method 2 of vfsms_pairs_offsets (vfsms_ctx_set_phase_resolver)
     // SURF tables
     vfsms_surf_params cur_params; bool tables_valid;
     LayerPat *d_layers; int n_layers;
@@ -298,8 +303,16 @@ int launch_hamming_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int c
 // phase_kernels.hip
 int phase_correlate_device(vfsms_ctx *ctx, const uint8_t *a, int stride_a, const uint8_t *b, int stride_b,
                            int h, int w, double *d_out3);
-int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3);
+int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink = nullptr);
 int phase_bytes(vfsms_ctx *ctx, int h, int w, int nb, size_t *bytes);
+size_t phase_peaks_bytes(int h, int w, int nb, int K);            // what a batch with a sink takes from the arena beyond phase_bytes
+void phase_surface_size(int h, int w, int *M, int *N);            // the padded size of the surface of an h x w strip, in the strip's own orientation
+// phase_resolve_kernels.hip: RE holds njobs stored planes of SM x SN (tr: each the transpose of its surface); partial: njobs * phase_peaks_blocks(SM) * K records
+int phase_peaks_blocks(int SM);
+int launch_phase_peaks(vfsms_ctx *ctx, const double *RE, int njobs, int SM, int SN, int tr, int K, PhasePeak *partial, PhasePeak *peaks);
+size_t phase_resolve_sums_bytes(int njobs, int K);
+int launch_phase_resolve(vfsms_ctx *ctx, const PhaseJobHost *d_jobs, const PhasePeak *d_peaks, int njobs, int K, int oM, int oN, int h, int w,
+                         double threshold, int min_pixels, unsigned long long *d_sums, int32_t *d_rows, int32_t *d_cands, int32_t *d_peaks_out);
 int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);   // launch records through the pinned staging buffer
 // enhance_kernels.hip
 size_t enhance_scratch_bytes(int h, int w, int mode, int tiles);

@@ -308,6 +308,10 @@ int device_eval(void *user, const vfsms_attempt_key *items, int n, int32_t *rows
     }
     if (P->method == 1)
         return vfsms_attempt_orb_batch(E->ctx, jobs.data(), n, &P->orb, P->orb_max_dist, P->offset_evaluate, rows);
+    if (P->method == 2 && E->ctx->phase_resolver == VFSMS_PHASE_RESOLVE_NCC)
+        // the rows of the resolver are attempt rows already: a raw vote in the feature path's convention, status = its own score gate
+        return vfsms_attempt_phase_resolve_batch(E->ctx, jobs.data(), n, E->ctx->phase_peaks, E->ctx->phase_threshold, E->ctx->phase_min_pixels, rows,
+                                                 nullptr, nullptr);
     if (P->method == 2) {
         std::vector<double> ph((size_t)3 * n);
         TRY(vfsms_attempt_phase_batch(E->ctx, jobs.data(), n, ph.data()));

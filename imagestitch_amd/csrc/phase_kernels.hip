@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <math.h>
 #include <vector>
+#include <memory>
 
 #define PHASE_MAX_CHUNK 32
 
@@ -850,7 +851,7 @@ static size_t own_bytes(const OwnShape &S, int h, int w, int nb)
            al256(sizeof(ArgMax) * c * S.M) + 65536;
 }
 
-static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3)
+static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink)
 {
     if (ctx->fft_tabs.empty()) {                               // first use on this context (= this device): > 64 KB of dynamic LDS must be asked for
         HIP_TRY(hipFuncSetAttribute((const void *)k_phase_rows_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, PHASE_LDS_MAX));
@@ -866,7 +867,8 @@ static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost
     cplx *CP = (cplx *)ctx_arena_alloc(ctx, sizeof(cplx) * cmax * cpl);
     uint8_t *TB = S.tr ? (uint8_t *)ctx_arena_alloc(ctx, 2 * (size_t)cmax * h * w) : nullptr;
     ArgMax *partial = (ArgMax *)ctx_arena_alloc(ctx, sizeof(ArgMax) * cmax * nparts);
-    if (!RE || !FQ || !CP || !partial || (S.tr && !TB)) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
+    PhasePeak *ppart = sink ? (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)cmax * phase_peaks_blocks(M) * sink->K) : nullptr;
+    if (!RE || !FQ || !CP || !partial || (S.tr && !TB) || (sink && !ppart)) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
     // job records: the caller's strips, then (transposed orientation) the scratch copies the row kernel reads instead, chunk-relative
     std::vector<PhaseJob> hj((size_t)nb + (S.tr ? cmax : 0));
     for (int k = 0; k < nb; k++) { hj[k].a = jobs[k].a; hj[k].b = jobs[k].b; hj[k].sa = jobs[k].sa; hj[k].sb = jobs[k].sb; }
@@ -879,9 +881,12 @@ static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost
     TRY(get_tab(ctx, N, &tabN));
     TRY(get_tab(ctx, M, &tabM));
     const FftSched SR = make_sched(S.H, N), SC = make_sched(M, M);
-    ProfScope ps(ctx, "phase");
+    // without a sink one "phase" record spans the batch, as ever; with one, a record per chunk, so that the peak scan behind a chunk's
+    // inverse transforms (the planes are reused by the next chunk) is booked under its own stage
+    std::unique_ptr<ProfScope> whole(sink ? nullptr : new ProfScope(ctx, "phase"));
     for (int done = 0; done < nb;) {
         const int c = std::min(cmax, nb - done);
+        std::unique_ptr<ProfScope> chunk(sink ? new ProfScope(ctx, "phase") : nullptr);
         const PhaseJob *rowjobs = dj + done;
         if (S.tr) {
             hipLaunchKernelGGL(k_phase_transpose_u8, dim3((w + 63) / 64, (h + 63) / 64, 2 * c), dim3(256), 0, ctx->stream, dj + done, h, w, TB);
@@ -895,6 +900,8 @@ static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost
         const int oM = S.tr ? N : M, oN = S.tr ? M : N;
         hipLaunchKernelGGL(k_peak_centroid, dim3(c), dim3(64), 0, ctx->stream, (const double *)RE, oM, oN, (long long)(S.tr ? 1 : N), (long long)(S.tr ? N : 1),
                            (const ArgMax *)partial, nparts, d_out3 + 3 * (size_t)done);
+        chunk.reset();
+        if (sink) TRY(launch_phase_peaks(ctx, RE, c, M, N, S.tr, sink->K, ppart, sink->peaks + (size_t)done * sink->K));
         done += c;
     }
     HIP_TRY(hipGetLastError());
@@ -922,13 +929,23 @@ int phase_bytes(vfsms_ctx *ctx, int h, int w, int nb, size_t *bytes)
     return VFSMS_OK;
 }
 
+// the peak scan's per-chunk partial lists (launch_phase_peaks), in either path
+size_t phase_peaks_bytes(int h, int w, int nb, int K)
+{
+    OwnShape own;
+    const int SM = phase_own_shape(h, w, &own) ? own.M : optimal_dft_size(h);
+    const size_t c = (size_t)plan_batch(std::min(nb, PHASE_MAX_CHUNK));
+    return al256(sizeof(PhasePeak) * c * phase_peaks_blocks(SM) * K) + 256;
+}
+void phase_surface_size(int h, int w, int *M, int *N) { *M = optimal_dft_size(h); *N = optimal_dft_size(w); }
+
 // nb attempts of one ROI size h x w.  jobs: HOST array of device pointers / strides.  d_out3: device double[3 * nb].
 // Scratch comes from the context arena (caller reserved phase_bytes(h, w, nb)).  Stream-ordered, no host sync.
-int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3)
+int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink)
 {
     if (nb <= 0) return VFSMS_OK;
     OwnShape own;
-    if (phase_own_shape(h, w, &own)) return phase_own_batch(ctx, own, jobs, nb, h, w, d_out3);
+    if (phase_own_shape(h, w, &own)) return phase_own_batch(ctx, own, jobs, nb, h, w, d_out3, sink);
     const int M = optimal_dft_size(h), N = optimal_dft_size(w);
     const int Nc = N / 2 + 1;
     const size_t real = (size_t)M * N, cpl = (size_t)M * Nc;
@@ -941,7 +958,8 @@ int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int n
     for (int k = 0; k < nb; k++) { hj[k].a = jobs[k].a; hj[k].b = jobs[k].b; hj[k].sa = jobs[k].sa; hj[k].sb = jobs[k].sb; }
     PhaseJob *dj = nullptr;
     TRY(ctx_upload_small(ctx, hj.data(), sizeof(PhaseJob) * nb, (void **)&dj));
-    if (!RE || !FQ || !CP || !partial) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
+    PhasePeak *ppart = sink ? (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)cmax * phase_peaks_blocks(M) * sink->K) : nullptr;
+    if (!RE || !FQ || !CP || !partial || (sink && !ppart)) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
     // chunks of at most PHASE_MAX_CHUNK attempts: plans first, so one work buffer serves every chunk
     std::vector<FftPlan *> chunks;
     std::vector<int> chunk_jobs;
@@ -956,9 +974,10 @@ int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int n
     }
     void *work = wbytes ? ctx_arena_alloc(ctx, wbytes) : nullptr;
     if (wbytes && !work) { vfsms_set_error("arena exhausted (rocFFT work buffer, %zu bytes)", wbytes); return VFSMS_ERR_CAPACITY; }
-    ProfScope ps(ctx, "phase");
+    std::unique_ptr<ProfScope> whole(sink ? nullptr : new ProfScope(ctx, "phase"));      // as in phase_own_batch
     int done = 0;
     for (size_t ci = 0; ci < chunks.size(); ci++) {
+        std::unique_ptr<ProfScope> chunk(sink ? new ProfScope(ctx, "phase") : nullptr);
         FftPlan *P = chunks[ci];
         const int c = chunk_jobs[ci];                                   // real jobs; the plan transforms P->nb >= c planes
         hipLaunchKernelGGL(k_pad_u8_f64, dim3((N + 255) / 256, M, c), dim3(256), 0, ctx->stream, dj + done, h, w, M, N, RE);
@@ -975,6 +994,8 @@ int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int n
         }
         hipLaunchKernelGGL(k_argmax_partial, dim3(PHASE_NBLK, c), dim3(256), 0, ctx->stream, RE, M, N, partial);
         hipLaunchKernelGGL(k_argmax_centroid, dim3(c), dim3(64), 0, ctx->stream, RE, M, N, partial, d_out3 + 3 * (size_t)done);
+        chunk.reset();
+        if (sink) TRY(launch_phase_peaks(ctx, RE, c, M, N, 0, sink->K, ppart, sink->peaks + (size_t)done * sink->K));      // the inverse plan leaves job k's surface at RE + k M N
         done += c;                                                      // the scratch planes are reused by the next chunk (stream order)
     }
     HIP_TRY(hipGetLastError());

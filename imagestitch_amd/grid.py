@@ -18,7 +18,7 @@ while keeping the GPU full:
 import numpy as np
 
 from ._lib import Engine, pairs_offsets_blind_eval, pairs_offsets_eval
-from .utility import roi_rect, vote_tail
+from .utility import phase_resolver, roi_rect, vote_tail
 
 RESULT_INTS = 6   # status, dx, dy, direction, i, votes
 
@@ -35,7 +35,8 @@ def _rotate(direction, incre):
 class GridRegistrar:
     def __init__(self, engine, method="surf", roiRatio=0.2, searchRatio=0.75, offsetEvaluate=3, directIncre=1,
                  surfParams=None, phaseResponseThreshold=0.15, window=16, enhance=(0, 0.0, 0), offsetCaculate="mode", ransacThreshold=3,
-                 siftParams=None, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0):
+                 siftParams=None, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0, phaseResolve="none", phasePeaks=2,
+                 phaseResolveThreshold=0.5, phaseResolveMinPixels=4096):
         self.eng = engine
         self.method = method
         self.roiRatio = roiRatio
@@ -56,6 +57,12 @@ class GridRegistrar:
         # the check off afterwards; "none" makes no such call.  Phase correlation has its own response gate.
         self.offsetVerify = offsetVerify if method in ("surf", "orb", "sift") else "none"
         self.verifyThreshold, self.verifyMinPixels = float(verifyThreshold), int(verifyMinPixels)
+        # Stitcher.phaseResolve: "ncc" reads every correlation surface through the resolver (tests/phase_resolve_ref.py) instead of the
+        # reference's arg-max, sign and response gate; method "phase" only
+        if phaseResolve not in ("none", "ncc"):
+            raise ValueError("phaseResolve must be 'none' or 'ncc'")
+        self.phaseResolve = phaseResolve if method == "phase" else "none"
+        self.phasePeaks, self.phaseResolveThreshold, self.phaseResolveMinPixels = int(phasePeaks), float(phaseResolveThreshold), int(phaseResolveMinPixels)
         self.stats = dict(attempts=0, batches=0, sum_nq_nt=0, sum_nq_plus_nt=0, sum_nq=0, roi_px=0)
         # Path memory: the accepted directions of the last path this registrar registered are the PREDICTION for the next one of the same
         # length (a session shoots one scan pattern after the other: Main.py loops over its datasets with one setting) -- they drive the
@@ -86,6 +93,9 @@ class GridRegistrar:
         return out
 
     def _estimator(self):
+        """scope of an engine call of this registrar: the vote tail of the feature methods, the resolver of method "phase" """
+        if self.phaseResolve != "none":
+            return phase_resolver(self.eng, self.phaseResolve, self.phasePeaks, self.phaseResolveThreshold, self.phaseResolveMinPixels)
         return vote_tail(self.eng, self.offsetCaculate, self.ransacThreshold, self.offsetVerify, self.verifyThreshold, self.verifyMinPixels)
 
     # -- one batch of attempts -----------------------------------------------------------------------------------
@@ -102,6 +112,12 @@ class GridRegistrar:
             self.stats["roi_px"] += 2 * ra[2] * ra[3]
         self.stats["attempts"] += len(jobs)
         self.stats["batches"] += 1
+        if self.method == "phase" and self.phaseResolve != "none":
+            batch = getattr(self.eng, "attempt_phase_resolve_batch", None)
+            if batch is None:
+                raise NotImplementedError("this engine has no phase resolver (phaseResolve = %r)" % (self.phaseResolve,))
+            # the resolver's rows are evaluator rows: a raw vote in the feature path's convention, status = its own score gate, nA = nB = 1
+            return np.asarray(batch(jobs, self.phasePeaks, self.phaseResolveThreshold, self.phaseResolveMinPixels)[0], np.int32).reshape(len(jobs), 8)
         if self.method == "phase":
             # offset = [int(y), int(x)] (truncation); accepted when response > threshold (Stitcher.py:231-236); votes 0, nA = nB = 1
             return np.array([[r[2] > self.phaseThr, int(r[1]), int(r[0]), 0, 1, 1, 0, 0] for r in self.eng.attempt_phase_batch(jobs)],

@@ -81,6 +81,15 @@ class Stitcher(Utility.Method):
     # iron gives [1400, 0] where the true offset is [1699, -1]).  The default reproduces the reference as written; True negates
     # the raw shift before the axis correction (iron -> [1698, 0]).  The batched registrar follows the reference only.
     phaseSignFix = False
+    # "ncc": every correlation surface is read by the resolver of tests/phase_resolve_ref.py instead -- the phasePeaks (1..8) largest peaks of
+    # the unshifted surface, each of their four circular readings scored by the overlap correlation of offsetVerify, the best one kept and
+    # accepted when its score reaches phaseResolveThreshold.  Neither the sign question, nor the wrap of the circular transform, nor the
+    # response gate is left: phaseSignFix and phaseResponseThreshold are not consulted.  The threshold and the pixel minimum are
+    # offsetVerify's defaults (the same statistic on the same kind of pixels).  Pair by pair and batched alike.
+    phaseResolve = "none"       # "none" or "ncc"
+    phasePeaks = 2
+    phaseResolveThreshold = 0.5
+    phaseResolveMinPixels = 4096
     tempImageFeature = ImageFeature()
 
     imageFusion = ImageFusion.ImageFusion()
@@ -226,7 +235,7 @@ class Stitcher(Utility.Method):
             return None
         if fn is Stitcher.calculateOffsetForFeatureSearchIncre and self._usesStockOperators():
             return self.featureMethod
-        if fn is Stitcher.calculateOffsetForPhaseCorrleateIncre and not self.phaseSignFix:
+        if fn is Stitcher.calculateOffsetForPhaseCorrleateIncre and (not self.phaseSignFix or self.phaseResolve != "none"):
             return "phase"
         # (with offsetVerify the line scans stay pair by pair: whole-tile feature sets carry no pixels, calculateOffsetForFeatureSearch
         # checks the two tiles themselves after the vote)
@@ -250,7 +259,8 @@ class Stitcher(Utility.Method):
                             enhance=self._enhanceSpec() if method in ("surf", "surf_full") else (0, 0.0, 0),
                             offsetCaculate=self.offsetCaculate if method != "phase" else "mode", ransacThreshold=self.ransacThreshold, siftParams=sift,
                             offsetVerify=self.offsetVerify if method != "phase" else "none", verifyThreshold=self.verifyThreshold,
-                            verifyMinPixels=self.verifyMinPixels)
+                            verifyMinPixels=self.verifyMinPixels, phaseResolve=self.phaseResolve, phasePeaks=self.phasePeaks,
+                            phaseResolveThreshold=self.phaseResolveThreshold, phaseResolveMinPixels=self.phaseResolveMinPixels)
         reg.orbMaxDistance = self.orbMaxDistance if self.isGPUAvailable else -1
         reg.path_memory = self.__dict__.get("_pathMemory")
         reg.path_suspect = bool(self.__dict__.get("_pathSuspect", False))
@@ -650,6 +660,16 @@ class Stitcher(Utility.Method):
             return (self._verified(status, offset, rawA, rawB), offset)
         return None
 
+    def _phaseResolve(self, roiImageA, roiImageB):
+        """phaseResolve = "ncc" on two ROI strips -> (status, [dx, dy]), a raw vote in the feature path's convention (tests/phase_resolve_ref.py)"""
+        if self.phaseResolve != "ncc":
+            raise ValueError("phaseResolve must be 'none' or 'ncc'")
+        fn = getattr(self.engine, "phase_resolve", None)
+        if fn is None:
+            raise NotImplementedError("this engine has no phase resolver (phaseResolve = %r)" % (self.phaseResolve,))
+        row = fn(np.asarray(roiImageA), np.asarray(roiImageB), self.phasePeaks, self.phaseResolveThreshold, self.phaseResolveMinPixels)[0]
+        return (bool(row[0]), [int(row[1]), int(row[2])])
+
     def _phaseCorrelate(self, roiImageA, roiImageB):
         """cv2.phaseCorrelate(np.float64(a), np.float64(b)) at Stitcher.py:230 -> ((x, y), response)."""
         return self.engine.phase_correlate(roiImageA, roiImageB)
@@ -681,13 +701,16 @@ class Stitcher(Utility.Method):
             while True:
                 roiImageA = self.getROIRegionForIncreMethod(imageA, direction=localDirection, order="first", searchRatio=i * self.roiRatio)
                 roiImageB = self.getROIRegionForIncreMethod(imageB, direction=localDirection, order="second", searchRatio=i * self.roiRatio)
-                (offsetTemp, response) = self._phaseCorrelate(roiImageA, roiImageB)
-                offset[0] = int(offsetTemp[1])
-                offset[1] = int(offsetTemp[0])
-                if self.phaseSignFix:                  # opt-in, not the reference's behaviour: see the class attribute
-                    offset[0], offset[1] = -offset[0], -offset[1]
-                if response > self.phaseResponseThreshold:
-                    status = True
+                if self.phaseResolve != "none":        # opt-in, no reference counterpart: see the class attribute
+                    (status, offset) = self._phaseResolve(roiImageA, roiImageB)
+                else:
+                    (offsetTemp, response) = self._phaseCorrelate(roiImageA, roiImageB)
+                    offset[0] = int(offsetTemp[1])
+                    offset[1] = int(offsetTemp[0])
+                    if self.phaseSignFix:                  # opt-in, not the reference's behaviour: see the class attribute
+                        offset[0], offset[1] = -offset[0], -offset[1]
+                    if response > self.phaseResponseThreshold:
+                        status = True
                 if status == True:
                     break
                 else:

@@ -65,6 +65,25 @@ def offset_verifier(engine, offsetVerify="none", verifyThreshold=0.0, verifyMinP
 
 
 @contextlib.contextmanager
+def phase_resolver(engine, phaseResolve="none", phasePeaks=2, phaseResolveThreshold=0.5, phaseResolveMinPixels=4096):
+    """The engine's phase chains (pairs_offsets with method "phase") resolve every correlation surface by overlap correlation
+    (Stitcher.phaseResolve = "ncc") inside the block, and read it the reference's way again after it, also when it raises.  "none" makes
+    no engine call: that is the engine's default.  An engine without the resolver raises NotImplementedError."""
+    if phaseResolve == "none":
+        yield
+        return
+    if phaseResolve != "ncc":
+        raise ValueError("phaseResolve must be 'none' or 'ncc'")
+    if not hasattr(engine, "set_phase_resolver"):
+        raise NotImplementedError("this engine has no phase resolver (phaseResolve = %r)" % (phaseResolve,))
+    engine.set_phase_resolver(phaseResolve, phasePeaks, phaseResolveThreshold, phaseResolveMinPixels)
+    try:
+        yield
+    finally:
+        engine.set_phase_resolver("none")
+
+
+@contextlib.contextmanager
 def vote_tail(engine, offsetCaculate="mode", ransacThreshold=3, offsetVerify="none", verifyThreshold=0.0, verifyMinPixels=0):
     """offset_estimator and offset_verifier around one fused engine call"""
     with offset_estimator(engine, offsetCaculate, ransacThreshold), offset_verifier(engine, offsetVerify, verifyThreshold, verifyMinPixels):

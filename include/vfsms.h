@@ -112,13 +112,24 @@ int vfsms_ctx_set_offset_estimator(vfsms_ctx *ctx, int estimator, int tol_px);
  * (>= 0) shared pixels or a flat side score 0.  Int 7 of the row = floor(score * VFSMS_VERIFY_FIXED_ONE + 0.5), 0 for rows the vote
  * did not accept; dx, dy and the counts stay.  Governs vfsms_attempt_surf_batch, _enhanced, vfsms_attempt_orb_batch,
  * vfsms_attempt_sift_batch and methods 0 / 1 of vfsms_pairs_offsets, _blind (a rejected candidate is a failed attempt: the search goes
- * on).  Method 2 (phase) ignores it: it has its own response gate.  vfsms_mode_offset and vfsms_consensus_offset never verify.
+ * on).  Method 2 (phase) ignores it: it has its own response gate, or vfsms_ctx_set_phase_resolver's score.  vfsms_mode_offset and vfsms_consensus_offset never verify.
  * vfsms_features_match_offset and _batch carry no pixels: with the verifier on they return VFSMS_ERR_UNSUPPORTED.
  * Anything else returns VFSMS_ERR_BAD_ARG and leaves the setting as it was.                                                      */
 #define VFSMS_VERIFY_NONE 0
 #define VFSMS_VERIFY_NCC 1
 #define VFSMS_VERIFY_FIXED_ONE 1048576
 int vfsms_ctx_set_offset_verifier(vfsms_ctx *ctx, int verifier, double threshold, int min_pixels);
+/* How method 2 (phase) of vfsms_pairs_offsets and _blind turns a correlation surface into an attempt row (Stitcher.phaseResolve; the
+ * reference has no such step, the specification is tests/phase_resolve_ref.py): VFSMS_PHASE_RESOLVE_NONE (the default: the reference's
+ * one arg-max, its sign and its response gate, rows as before) or VFSMS_PHASE_RESOLVE_NCC: the `peaks` (1..VFSMS_PHASE_MAX_PEAKS) largest
+ * peaks of the unshifted surface, the four circular readings of each scored like vfsms_verify_ncc scores a vote, the best one kept; the
+ * row is vfsms_attempt_phase_resolve_batch's, its dx, dy a raw vote in the feature path's convention (the axis correction applies as for
+ * methods 0 and 1), status = score >= threshold (-1..1); fewer than min_pixels (>= 0) shared pixels score 0.  grid_params.phase_threshold
+ * plays no part then.  Anything else returns VFSMS_ERR_BAD_ARG and leaves the setting as it was.                                        */
+#define VFSMS_PHASE_RESOLVE_NONE 0
+#define VFSMS_PHASE_RESOLVE_NCC 1
+#define VFSMS_PHASE_MAX_PEAKS 8
+int vfsms_ctx_set_phase_resolver(vfsms_ctx *ctx, int resolver, int peaks, double threshold, int min_pixels);
 
 /* Per-stage timing with HIP events recorded on the context's own stream around each kernel group
  * ("integral", "hessian", "nms", "sort", "orientation", "describe", "bf_l2", "vote", "phase", "fuse", ...).
@@ -280,6 +291,10 @@ int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b,
  *          column length M, row length N (the padded sizes in the orientation used), columns per workgroup, rows per workgroup,
  *          threads of a row workgroup, threads of a column workgroup}; no device work                                           */
 int vfsms_phase_plan(int h, int w, int32_t *info8);
+/* vfsms_attempt_phase_resolve_batch (below) for two host strips: row8 = one attempt row, cands (may be NULL) int32[4 * peaks][4],
+ * peaks_out (may be NULL) int32[peaks][2]                                                                                           */
+int vfsms_phase_resolve_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w, int stride_a, int stride_b,
+                           int peaks, double threshold, int min_pixels, int32_t *row8, int32_t *cands, int32_t *peaks_out);
 
 /* ImageFusion.fuseByFadeInAndFadeOut([A,B],dx,dy) (ImageFusion.py:192-244) on the reference's own
  * representation: int64 [r][c][ch] with -1 = empty (Stitcher.py:434-436).  out: uint8 [r][c][ch].
@@ -338,6 +353,15 @@ int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
                              const vfsms_sift_params *params, double ratio, int offset_evaluate, int32_t *out);
 /* same for phase correlation (Stitcher.py:224-235): out: double[n][3] = {x, y, response}           */
 int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out);
+/* the same correlation resolved by overlap correlation (tests/phase_resolve_ref.py): strip-B pixel (r, c) meets strip-A pixel (r + dx,
+ * c + dy).  rows: int32[n][VFSMS_ATTEMPT_INTS] = {status, dx, dy, 0, 1, 1, index of the winning candidate, floor(score *
+ * VFSMS_VERIFY_FIXED_ONE + 0.5)}; a row with status 0 still names the best candidate.  cands (may be NULL): int32[n][4 * peaks][4] =
+ * {dx, dy, fixed-point score, shared pixels} of candidate 4 * peak + reading, readings (uy, ux), (uy - M, ux), (uy, ux - N),
+ * (uy - M, ux - N) of the peak at (uy, ux) of the M x N surface; a reading under which the strips share no pixel scores 0 over 0
+ * pixels, the readings of an absent peak are zeros.  peaks_out (may be NULL): int32[n][peaks][2] = {uy, ux}, (-1, -1) when absent.
+ * peaks 1..VFSMS_PHASE_MAX_PEAKS, threshold -1..1, min_pixels >= 0.  One launch sequence per strip shape, one synchronisation.     */
+int vfsms_attempt_phase_resolve_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, int peaks, double threshold, int min_pixels,
+                                      int32_t *rows, int32_t *cands, int32_t *peaks_out);
 
 /* ---- whole shooting paths behind one call (the pair loop of Stitcher.flowStitch, Stitcher.py:64-79, around the incremental search of
  * Stitcher.py:306-367 / 205-258) -------------------------------------------------------------------------------------------------
