@@ -381,8 +381,9 @@ __global__ __launch_bounds__(256, 2) void k_bf_mfma_d64(const MatchDev *jobs)
 // ---------------------------------------------------------------------------------------------------
 // The same filter on the 16-bit matrix pipe (16x the f32-MFMA rate) with fp16 operands: every descriptor element is stored once as
 // fp16 (round to nearest even; queries pre-scaled by -2, exact) and q.t is ONE v_mfma_f32_32x32x16_f16 product per 16 dims with
-// f32 accumulation.  |t|^2 rides along as one more k-slot: its own two-term fp16 sum hi + lo against 1.0 on the query side, so the
-// norm adds no first-order error.  The scores only select WHICH distances the verifier computes exactly.
+// f32 accumulation.  |t|^2 enters as the INITIAL VALUE of the accumulator (the C operand of the first k-step), as the f32 that
+// k_bf_split16 sums: it costs no matrix instruction and no rounding of its own.  The scores only select WHICH distances the verifier
+// computes exactly.
 //
 // Error of a score against the exact s = |t|^2 - 2 q.t of the float descriptors (norms^2 <= 1.0001: bf_l2_host checks, SURF's are
 // L2-normalised), BFM_F16_ERR:
@@ -391,21 +392,23 @@ __global__ __launch_bounds__(256, 2) void k_bf_mfma_d64(const MatchDev *jobs)
 //     2 ((1 + 2^-11)^2 - 1) * 1.0001                                                                               = 1.9538e-3
 //   - absolute: an element below fp16's normal range (|x| < 2^-14 = 6.1e-5, subnormals and zero) is off by up to half the subnormal
 //     spacing, eta = 2^-25, instead of u |x|; a'b' - ab = (a' - a) b' + a (b' - b) adds eta (|b'| + |a|) <= 3 eta per term with
-//     |t_i| <= 1, |2 q_i| <= 2 (the issue's 2^-25 x 64 x 2 counts the query side only): 64 * 3 * 2^-25                = 5.8e-6
-//   - f32 accumulation over the 65 k-slots: partial sums stay below 2 |q||t| + |t|^2 <= 3.01, one rounding of at most 2^-23
-//     relative per slot (2^-24 if the pipe rounds to nearest; the bound does not rely on it): 65 * 2^-23 * 3.01       = 2.33e-5
-//   - the norm slot: |t|^2 summed in f32 by k_bf_split16 (64 additions, <= 64 * 2^-24 * 1.0001 = 3.8e-6) and hi + lo of it (lo
-//     rounds a residual <= 2^-11: 2^-22)                                                                              = 4.1e-6
-//   total 1.987e-3 <= BFM_F16_ERR = 2.0e-3.  tests/test_bf_fp16_host.py emulates the scores in numpy and checks the bound.
+//     |t_i| <= 1, |2 q_i| <= 2: 64 * 3 * 2^-25                                                                        = 5.8e-6
+//   - f32 accumulation of the 64 product slots onto the initial value: partial sums stay below 2 |q||t| + |t|^2 <= 3.01, one
+//     rounding of at most 2^-23 relative per slot (2^-24 if the pipe rounds to nearest; the bound does not rely on it):
+//     64 * 2^-23 * 3.01                                                                                              = 2.30e-5
+//   - the initial value: |t|^2 summed in f32 by k_bf_split16 (64 additions, <= 64 * 2^-24 * 1.0001)                   = 3.8e-6
+//   total 1.986e-3 <= BFM_F16_ERR = 2.0e-3.  tests/test_bf_filter_norm_init_host.py emulates the scores in numpy and checks the
+//   bound (tests/test_bf_fp16_host.py: the same for the hi + lo norm slot of the previous form, whose total was 1.987e-3).
 //
-// k_bf_split16 writes the operands once per ROI.  Queries (each wave loads its 64 once): row = [dims 0-31 | dims 32-63 | 1, 1,
-// 0...].  Trains (every wave streams all of them) are stored in MFMA FRAGMENT order: per 32-train tile five 1 KB fragments -- k-steps
-// 0..3, the |t|^2 slot -- each holding the 16 bytes of lane 0, lane 1, ... lane 63, so that one load instruction of a wave reads 8
-// consecutive cache lines instead of one line per lane (the row-major layout kept the texture-address path, not the matrix pipe,
-// busy: 64 lines per load).
+// k_bf_split16 writes the operands once per ROI.  Queries (each wave loads its 64 once): row = [dims 0-31 | dims 32-63].  Trains
+// (every wave streams all of them) are stored in MFMA FRAGMENT order: per 32-train tile four 1 KB fragments -- k-steps 0..3 -- each
+// holding the 16 bytes of lane 0, lane 1, ... lane 63, so that one load instruction of a wave reads 8 consecutive cache lines instead
+// of one line per lane (the row-major layout kept the texture-address path, not the matrix pipe, busy: 64 lines per load), and behind
+// them the tile's 32 |t|^2 as f32 (128 bytes).
 // ---------------------------------------------------------------------------------------------------
-#define BF16_ROW 80                  // uint16 per descriptor row: 2 x 32 fp16 + 16 for the norm slot
-#define BF16_FRAGS 5                 // per train tile: 4 dimension fragments + the norm fragment, 64 lanes x 8 fp16 each
+#define BF16_ROW 64                  // uint16 per query row: 2 x 32 fp16
+#define BF16_FRAGS 4                 // dimension fragments per train tile, 64 lanes x 8 fp16 each
+#define BF16_TILE (BF16_FRAGS * 64 + 8)    // 16-byte units per train tile: the fragments + 32 f32 |t|^2 (4.125 KB)
 #define BFM_F16_ERR 2.0e-3f          // >= |fp16 score - exact score|, derived above
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
@@ -427,28 +430,22 @@ __global__ __launch_bounds__(256) void k_bf_split16(const MatchDev *jobs, float 
         part += x * x;
         el[d >> 3][d & 7] = (_Float16)(x * sc);                 // v_cvt_f16_f32: round to nearest even, subnormals kept
     }
-    // norm slot (trains: |t|^2 as hi + lo; queries: 1, 1): k-slots 0 and 1 of the fifth MFMA step, lane half 0 only
-    const float tot = part + __shfl_xor(part, 1, 64);
-    h8v ns = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (half == 0) {
-        _Float16 a = (_Float16)1.f, b = (_Float16)1.f;
-        if (is_t) { a = (_Float16)tot; b = (_Float16)(tot - (float)a); }
-        ns[0] = a; ns[1] = b;
-    }
     if (is_t) {
-        h8v *dst = reinterpret_cast<h8v *>(J.t16) + (size_t)(row >> 5) * (BF16_FRAGS * 64) + (row & 31) + 32 * half;
+        h8v *tile = reinterpret_cast<h8v *>(J.t16) + (size_t)(row >> 5) * BF16_TILE;
+        h8v *dst = tile + (row & 31) + 32 * half;
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) dst[s4 * 64] = el[s4];
-        dst[4 * 64] = ns;
+        // |t|^2: the f32 sum of the two halves (a + b == b + a: either thread holds the same value), behind the tile's fragments
+        const float tot = part + __shfl_xor(part, 1, 64);
+        if (half == 0) reinterpret_cast<float *>(tile + BF16_FRAGS * 64)[row & 31] = tot;
     } else {
         h8v *dst = reinterpret_cast<h8v *>(J.q16 + (size_t)row * BF16_ROW + 32 * half);
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) dst[s4] = el[s4];
-        if (half == 0) *reinterpret_cast<h8v *>(J.q16 + (size_t)row * BF16_ROW + 64) = ns;
     }
 }
 
-// Two launches over the same five k-steps per tile (four of dimensions + the norm slot), so both see the SAME scores (same
+// Two launches over the same four k-steps per tile, the first one starting from |t|^2, so both see the SAME scores (same
 // instructions in the same order).  PASS 0 (bounds): a branch-free running (best, second best) per lane, written per (list, query);
 // m2(q), the second best over all lists, is >= the second smallest fp16 score of the query.  PASS 1 (candidates): a train is listed
 // when its score is <= thr(q) = m2(q) + 2 BFM_F16_ERR + BFM_MARGIN, known BEFORE the sweep -- a handful per query instead of the
@@ -459,10 +456,12 @@ __global__ __launch_bounds__(256) void k_bf_split16(const MatchDev *jobs, float 
 // trains like S up to its own rounding, which BFM_MARGIN covers 40-fold: a train that can come out best or second best has
 // S <= S2 + BFM_MARGIN, hence s <= S2 + BFM_MARGIN + E <= s2 + 2 E + BFM_MARGIN <= thr(q).  Every such train is listed; the verifier
 // applies the same window around the s2 it reads back from the lists (they hold the two smallest scores, so that s2 is the true one).
+// Pass 0 visits only every BFM_P0_STRIDE-th tile of a chunk, and its last: m2(q) is then the second smallest over a subset of the
+// trains, hence still >= s2 -- thr(q) only grows, pass 1 lists more.
 // (The split-bf16 form of rounds 2-6 -- hi.hi + hi.lo + lo.hi, 13 k-steps and nine fragments in pass 1 -- and its switch that skipped
 //  the correction k-steps per tile, 8 % slower, are gone: profiles/r06_ab_bf_skip.txt)
-#ifndef BFM_GLDS
-#define BFM_GLDS 1                // round 6: train tiles reach LDS by LDS-DMA (global_load_lds_dwordx4), not through registers
+#ifndef BFM_P0_STRIDE
+#define BFM_P0_STRIDE 2           // 1, 2 or 4: pass 0 sweeps tiles tile0, tile0 + stride, ... and the chunk's last (profiles/r10_ab_bf_trim.txt)
 #endif
 #define BFM_WINDOW (2.f * BFM_F16_ERR + BFM_MARGIN)      // what a listed fp16 score may lie above the second-best fp16 score (superset argument above)
 #define GASM __attribute__((address_space(1)))
@@ -470,7 +469,7 @@ typedef GASM const h8v *g_cs8v;
 typedef float f2v __attribute__((ext_vector_type(2)));
 
 #ifdef VFSMS_DESC_TIMING
-// debug build: per-wave cycles of the filter sweeps, [pass][0 prologue, 1 barrier wait, 2 put + fetch issue, 3 LDS reads + MFMAs + minimum tree, 4 append, 5 whole kernel, 6 waves]
+// debug build: per-wave cycles of the filter sweeps, [pass][0 prologue, 1 barrier wait, 2 fetch issue, 3 LDS reads + MFMAs + minimum tree, 4 append, 5 whole kernel, 6 waves]
 __device__ unsigned long long g_bf_cycles[2][8];
 extern "C" int vfsms_debug_bf_cycles(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bf_cycles), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -3; }
 #define BT_DECL unsigned long long _bt[5] = {0, 0, 0, 0, 0}, _bt0 = clock64(), _btl = _bt0
@@ -485,6 +484,7 @@ extern "C" int vfsms_debug_bf_cycles(unsigned long long *out) { return hipMemcpy
 template <int PASS>
 __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, int qblocks, int nsplit, int njobs)
 {
+    static_assert(BFM_P0_STRIDE == 1 || BFM_P0_STRIDE == 2 || BFM_P0_STRIDE == 4, "BFM_P0_STRIDE is 1, 2 or 4");
     // a (job, train chunk) and its 0.3 MB of split descriptors stay on one XCD (xcd_roi_map): every query block of the unit re-reads them
     unsigned unit, qb;
     xcd_roi_map(blockIdx.x, (unsigned)qblocks, (unsigned)(nsplit * njobs), unit, qb);
@@ -499,87 +499,51 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
     const int ntiles = (nt + 31) >> 5;
     const int tchunk = (ntiles + nsplit - 1) / nsplit;
     const int tile0 = sp * tchunk, tile1 = min(ntiles, tile0 + tchunk);
+    // the sweep's k-th tile: pass 1 takes every tile of the chunk; pass 0 every STRIDE-th and, whatever the stride, the last one -- no
+    // tile twice ((nvis - 2) * STRIDE < tile1 - 1 - tile0), and a chunk of one or two tiles is swept whole, so a query has two scores
+    // whenever it has two trains
+    constexpr int STRIDE = PASS == 0 ? BFM_P0_STRIDE : 1;
+    const int nvis = tile1 > tile0 ? (tile1 - tile0 - 1 + STRIDE - 1) / STRIDE + 1 : 0;
+    auto tile_of = [&](int k) { return min(tile0 + k * STRIDE, tile1 - 1); };
     const int col = lane & 31, half = lane >> 5;
-    const h8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
     // B operands (queries, resident): per 16-dim step s the lane's 8 values of dims 32*half + 8*s .. + 7
-    h8v bh0[4], bh1[4], bn0, bn1;
+    h8v bh0[4], bh1[4];
     {
         g_cs8v p0 = (g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 32 * half);
         g_cs8v p1 = (g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 32 * half);
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) { bh0[s4] = p0[s4]; bh1[s4] = p1[s4]; }
-        bn0 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + col, nq - 1) * BF16_ROW + 64) : zero;
-        bn1 = half == 0 ? *(g_cs8v)(J.q16 + (size_t)min(q0 + 32 + col, nq - 1) * BF16_ROW + 64) : zero;
     }
     // Train tiles go through LDS: the four waves of a workgroup sweep the SAME tiles (for different queries), so one cooperative
-    // copy per tile (1.25 x 16 B per thread, straight in fragment order) replaces four sets of per-wave loads, and the operands
-    // arrive by ds_read_b128 instead of waiting on L2.  The waves meet once per UNIT of BFM_UNIT tiles (they sit on four SIMDs, each
-    // shared with other workgroups: every meeting waits for the slowest): two buffers of one unit each; unit u + 1 is put into the
-    // buffer that unit u - 1 vacated right after the barrier (it was fetched into registers an iteration ago), unit u + 2 is fetched
-    // before the MFMAs of unit u.
-    constexpr int NFR = BF16_FRAGS;                      // fragments staged: dimensions x 4 + norm
+    // copy per tile replaces four sets of per-wave loads, and the operands arrive by ds_read_b128 instead of waiting on L2.  The
+    // waves meet once per UNIT of BFM_UNIT tiles (they sit on four SIMDs, each shared with other workgroups: every meeting waits
+    // for the slowest): two buffers of one unit each.
     constexpr int BFM_UNIT = 2;                          // train tiles per meeting (four in pass 0 -- twice the bytes in flight -- changed nothing)
-    __shared__ h8v stage[2][BFM_UNIT][NFR * 64];
-    g_cs8v T = (g_cs8v)J.t16;                            // fragment order: tile * 5 fragments * 64 lanes (k_bf_split16)
-    const int tid = threadIdx.x; (void)tid;
-    // Units are fetched BFM_SETS + 1 ahead of their MFMAs into BFM_SETS register sets (pass 0 has the registers for two: its iteration --
-    // ten MFMAs per tile -- is shorter than a trip to memory, and half of its wave cycles were the wait in front of the put).
-#if BFM_GLDS
-    // Round 6: a tile's fragments are ONE lane-linear block in global memory (k_bf_split16 writes them in fragment order) and the same block
-    // in LDS, so the copy is LDS-DMA: wave w issues global_load_lds_dwordx4 for the 1 KB chunk w (wave 0 also the norm
-    // fragment) -- one or two instructions per tile and wave, no staging registers (24 VGPRs), no ds_write pass.  Unit u + 1 is
-    // requested right behind the barrier that frees its buffer and has the whole of unit u's MFMAs to land; the barrier's vmcnt(0)
-    // (hipcc drains the DMA in front of __syncthreads) is what makes it visible.  (profiles/r06_glds_probe.txt: the instruction takes
-    // 4-byte-aligned global addresses and partial EXEC.)
-    constexpr int NSET = 1;
+    __shared__ h8v stage[2][BFM_UNIT][BF16_TILE];
+    g_cs8v T = (g_cs8v)J.t16;                            // tile * BF16_TILE: four fragments of 64 lanes, then 32 f32 |t|^2 (k_bf_split16)
+    // A tile is ONE lane-linear block in global memory (k_bf_split16 writes it in fragment order) and the same block in LDS, so the
+    // copy is LDS-DMA: wave w issues global_load_lds_dwordx4 for the 1 KB fragment w, and lanes 0-7 of wave 0 one more for the 128
+    // bytes of |t|^2 -- one or two instructions per tile and wave, no staging registers, no ds_write pass.  Unit u + 1 is requested
+    // right behind the barrier that frees its buffer and has the whole of unit u's MFMAs to land.  (profiles/r06_glds_probe.txt: the
+    // instruction takes 4-byte-aligned global addresses and partial EXEC, and writes LDS only for the lanes that are on.)
     const int wv_u = __builtin_amdgcn_readfirstlane(wave);
     auto glds16 = [&](g_cs8v src, const h8v *dst) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
     };
+    const int nunits = (nvis + BFM_UNIT - 1) / BFM_UNIT;
     auto fetch = [&](int unit, int b) {
 #pragma unroll
         for (int u = 0; u < BFM_UNIT; u++) {
-            const int tl = min(tile0 + unit * BFM_UNIT + u, tile1 - 1);
-            g_cs8v pn = T + (size_t)tl * (BF16_FRAGS * 64);
+            g_cs8v pn = T + (size_t)tile_of(min(unit * BFM_UNIT + u, nvis - 1)) * BF16_TILE;
             glds16(pn + 64 * wv_u + lane, &stage[b][u][64 * wv_u]);
-            if (wv_u == 0) glds16(pn + 256 + lane, &stage[b][u][256]);
+            if (wv_u == 0 && lane < 8) glds16(pn + BF16_FRAGS * 64 + lane, &stage[b][u][BF16_FRAGS * 64]);
         }
     };
-    const int nunits = (tile1 - tile0 + BFM_UNIT - 1) / BFM_UNIT;
     if (nunits > 0) fetch(0, 0);
-#else
-    constexpr int NSET = PASS == 0 ? 2 : 1;
-    h8v g0[NSET][BFM_UNIT], g1[NSET][BFM_UNIT];
-#pragma unroll
-    for (int e = 0; e < NSET; e++)
-#pragma unroll
-        for (int u = 0; u < BFM_UNIT; u++) { g0[e][u] = zero; g1[e][u] = zero; }
-    const int nunits = (tile1 - tile0 + BFM_UNIT - 1) / BFM_UNIT;
-    // (no branch around a load: beyond the chunk the last tile is fetched again and never used, every thread fetches a norm fragment lane --
-    //  with a fixed number of loads per fetch the compiler waits for exactly the set it is about to put, not for everything outstanding)
-    auto fetch = [&](int unit, int e) {
-#pragma unroll
-        for (int u = 0; u < BFM_UNIT; u++) {
-            const int tl = min(tile0 + unit * BFM_UNIT + u, tile1 - 1);
-            g_cs8v pn = T + (size_t)tl * (BF16_FRAGS * 64);
-            g0[e][u] = pn[tid];
-            g1[e][u] = pn[256 + (tid & 63)];
-        }
-    };
-    auto put = [&](int b, int e) {
-#pragma unroll
-        for (int u = 0; u < BFM_UNIT; u++) {
-            stage[b][u][tid] = g0[e][u];
-            if (tid < 64) stage[b][u][256 + tid] = g1[e][u];
-        }
-    };
-    if (nunits > 0) fetch(0, 0);                     // under way while the query operands and the thresholds arrive
-#endif
     // Pin the query operands as "defined here": the compiler otherwise carries their load waits into the tile loop as in-order
     // vmcnt counts, which also drain the train prefetch issued at the top of every iteration (a full L2 round trip per tile).
 #pragma unroll
     for (int s4 = 0; s4 < 4; s4++) asm volatile("" : "+v"(bh0[s4]), "+v"(bh1[s4]));
-    asm volatile("" : "+v"(bn0), "+v"(bn1));
     const bool va = q0 + col < nq, vb = q0 + 32 + col < nq;
     const size_t pitch = (size_t)J.capq;
     const int lst = sp * 2 + half, nl = 2 * nsplit;
@@ -608,51 +572,41 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
     }
     // (global address space: a generic pointer makes the append a flat_store, which the compiler orders behind every LDS-DMA in flight)
     GASM unsigned long long *lista = (GASM unsigned long long *)J.c_ent + (size_t)lst * BFM_CAPL * pitch + (q0 + col), *listb = lista + 32;   // uint2 (score bits, train) as one 64-bit word
-#if !BFM_GLDS
-    if (nunits > 0) {
-        put(0, 0);
-#pragma unroll
-        for (int k = 1; k <= NSET; k++) fetch(min(k, nunits - 1), k % NSET);
-    }
-#endif
     BT_MARK(0);
-    for (int unit0 = 0; unit0 < nunits; unit0 += NSET) {
-#pragma unroll
-      for (int v = 0; v < NSET; v++) {                 // unrolled: the register set of unit + 1 is (v + 1) % NSET, a constant
-        const int unit = unit0 + v;
-        if (unit >= nunits) break;
+    for (int unit = 0; unit < nunits; unit++) {
         const int b = unit & 1;
-#if BFM_GLDS
         // this wave's LDS-DMA of the unit has landed (hipcc 7.2 does NOT put this wait in front of the barrier by itself: the ISA showed
         // `s_waitcnt lgkmcnt(0); s_barrier` only) -- behind the barrier every wave's has
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         __syncthreads();
         BT_MARK(1);
-#if BFM_GLDS
         if (unit + 1 < nunits) fetch(unit + 1, b ^ 1);
-#else
-        if (unit + 1 < nunits) put(b ^ 1, (v + 1) % NSET);
-        fetch(min(unit + 1 + NSET, nunits - 1), (v + 1) % NSET);
-#endif
         BT_MARK(2);
         if (!live) continue;
 #pragma unroll
         for (int u = 0; u < BFM_UNIT; u++) {
-            const int tl = tile0 + unit * BFM_UNIT + u;
-            if (tl >= tile1) break;
+            if (unit * BFM_UNIT + u >= nvis) break;
+            const int tl = tile_of(unit * BFM_UNIT + u);
             const h8v *st = stage[b][u];
-            f16v acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
+            // both accumulators of a lane hold the train rows 4 * half + (i & 3) + 8 * (i >> 2): one set of 16 |t|^2 (four ds_read_b128,
+            // the same address across a lane half) starts both
+            const float4 *tn = reinterpret_cast<const float4 *>(st + BF16_FRAGS * 64) + half;
+            f16v cinit;
 #pragma unroll
-            for (int s = 0; s < 4; s++) {            // fragment s = the lane's dims 8s .. 8s + 7
+            for (int j = 0; j < 4; j++) {
+                const float4 n4 = tn[2 * j];
+                cinit[4 * j] = n4.x; cinit[4 * j + 1] = n4.y; cinit[4 * j + 2] = n4.z; cinit[4 * j + 3] = n4.w;
+            }
+            const h8v at0 = st[lane];                // fragment s = the lane's dims 8s .. 8s + 7
+            f16v acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at0, bh0[0], cinit, 0, 0, 0);       // |t|^2 - 2 q.t, dims of k-step 0
+            f16v acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at0, bh1[0], cinit, 0, 0, 0);
+#pragma unroll
+            for (int s = 1; s < 4; s++) {
                 const h8v at = st[s * 64 + lane];
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at, bh0[s], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(at, bh1[s], acc1, 0, 0, 0);
             }
-            const h8v na = st[(NFR - 1) * 64 + lane];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(na, bn0, acc0, 0, 0, 0);       // + |t|^2 (hi + lo)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(na, bn1, acc1, 0, 0, 0);
-            if (tl * 32 + 31 >= nt) {                // train rows beyond nt never qualify
+            if (tl * 32 + 31 >= nt) {                // train rows beyond nt never qualify (k_bf_split16 writes nothing for them)
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const bool past = tl * 32 + 4 * half + (i & 3) + 8 * (i >> 2) >= nt;
@@ -709,7 +663,6 @@ __global__ __launch_bounds__(256, 3) void k_bf_mfma16_d64(const MatchDev *jobs, 
             }
             if (PASS == 0) BT_MARK(3);
         }
-      }
     }
     BT_FLUSH(PASS);
     if (PASS == 0) {
@@ -1100,7 +1053,7 @@ int launch_max_norm2_d64(vfsms_ctx *ctx, const float *a, int n, unsigned *d_out)
 size_t match_filter_bytes(int capq, int capt, int cns)
 {
     return al(sizeof(uint2) * (size_t)capq * cns * 2 * BFM_CAPL) + al(sizeof(int) * (size_t)capq * cns * 2) +
-           al(sizeof(unsigned short) * BF16_ROW * (size_t)capq) + al(sizeof(unsigned short) * BF16_ROW * ((size_t)capt + 32)) +
+           al(sizeof(unsigned short) * BF16_ROW * (size_t)capq) + al(sizeof(h8v) * BF16_TILE * ((size_t)capt / 32 + 1)) +
            al(sizeof(float2) * (size_t)capq * cns * 2) + 1024;
 }
 
@@ -1109,7 +1062,7 @@ int match_filter_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int capt, int cns)
     m->c_ent = (uint2 *)ctx_arena_alloc(ctx, sizeof(uint2) * (size_t)capq * cns * 2 * BFM_CAPL);
     m->c_cnt = (int *)ctx_arena_alloc(ctx, sizeof(int) * (size_t)capq * cns * 2);
     m->q16 = (unsigned short *)ctx_arena_alloc(ctx, sizeof(unsigned short) * BF16_ROW * (size_t)capq);
-    m->t16 = (unsigned short *)ctx_arena_alloc(ctx, sizeof(unsigned short) * BF16_ROW * ((size_t)capt + 32));   // whole 32-train tiles
+    m->t16 = (unsigned short *)ctx_arena_alloc(ctx, sizeof(h8v) * BF16_TILE * ((size_t)capt / 32 + 1));   // whole 32-train tiles
     m->c_m12 = (float2 *)ctx_arena_alloc(ctx, sizeof(float2) * (size_t)capq * cns * 2);
     if (!m->c_cnt || !m->t16 || !m->c_m12) { vfsms_set_error("arena exhausted while carving a match filter"); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
