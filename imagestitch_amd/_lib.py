@@ -181,6 +181,8 @@ _SIGNATURES = {
     "vfsms_shading_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_shading_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "vfsms_shading_free": (C.c_int, [C.c_void_p, C.c_int64]),
+    "vfsms_overlap_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_exposure_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -994,6 +996,29 @@ class Engine:
     def shading_free(self, field):
         self._check(self.lib.vfsms_shading_free(self.ctx, C.c_int64(field)))
         self.__dict__.get("_shapes", {}).pop(("field", field), None)
+
+    # -- exposure compensation (tests/exposure_ref.py is the specification) -------------------------------------------------
+    def overlap_stats_batch(self, jobs, lo, hi):
+        """vfsms_overlap_stats_batch: jobs = sequence of (tile_a, tile_b, dx, dy) over resident tiles (gray or colour, one channel count
+        per job, any shapes); tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy).  -> int64[n, 3] = (N, Sa, Sb) over the samples
+        of the overlap with lo <= a <= hi and lo <= b <= hi"""
+        n = len(jobs)
+        out = np.zeros((n, 3), np.int64)
+        arr = (NccJob * max(n, 1))()
+        for k, j in enumerate(jobs):
+            arr[k] = NccJob(*[int(v) for v in j])
+        self._check(self.lib.vfsms_overlap_stats_batch(self.ctx, arr, n, int(lo), int(hi), _ptr(out)))
+        return out
+
+    def exposure_apply(self, handles, gains):
+        """the tiles corrected in place, tile i by the Q12 gain gains[i] (vfsms_exposure_apply): out = min(255, (p * Q + 2048) >> 12);
+        owned tiles, each named once; a tile whose gain is 4096 is left alone"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        g = np.asarray(gains).reshape(-1)
+        if len(g) != len(th) or (len(g) and (g.min() < 0 or g.max() > 65535)):
+            raise ValueError("exposure_apply: one Q12 gain in 0..65535 per tile")
+        g = np.ascontiguousarray(g, np.uint16)
+        self._check(self.lib.vfsms_exposure_apply(self.ctx, len(th), _ptr(th), _ptr(g)))
 
     def canvas_download(self, handle, rows, cols, ch):
         out = np.empty((rows, cols, ch) if ch > 1 else (rows, cols), np.uint8)

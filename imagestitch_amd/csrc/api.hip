@@ -2304,6 +2304,59 @@ extern "C" int vfsms_shading_free(vfsms_ctx *ctx, int64_t field)
     return VFSMS_OK;
 }
 
+// ---- exposure compensation (Method.exposureCompensation; exposure_kernels.hip, specified by tests/exposure_ref.py) -----------------------
+// vfsms_overlap_stats_batch: every launch of the batch is enqueued before the one synchronisation that brings the sums back
+extern "C" int vfsms_overlap_stats_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int lo, int hi, int64_t *out3)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!jobs || !out3))) { vfsms_set_error("overlap_stats: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (lo < 0 || hi > 255 || lo > hi) { vfsms_set_error("overlap_stats: band %d..%d (0 <= lo <= hi <= 255)", lo, hi); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    std::vector<ExpPairHost> H(n);
+    for (int k = 0; k < n; k++) {
+        auto ia = ctx->tiles.find(jobs[k].tile_a), ib = ctx->tiles.find(jobs[k].tile_b);
+        if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("overlap_stats: job %d names an unknown tile handle", k); return VFSMS_ERR_BAD_ARG; }
+        TileRec &A = ia->second, &B = ib->second;
+        if (A.ch != B.ch) { vfsms_set_error("overlap_stats: the tiles of job %d have %d and %d channels", k, A.ch, B.ch); return VFSMS_ERR_BAD_ARG; }
+        TRY(tile_ready(ctx, A)); TRY(tile_ready(ctx, B));
+        H[k] = ExpPairHost{A.ptr, B.ptr, A.stride, B.stride, A.h, A.w * A.ch, B.h, B.w * B.ch, A.ch, jobs[k].dx, jobs[k].dy};
+    }
+    const size_t out_bytes = sizeof(unsigned long long) * 3 * (size_t)n;
+    TRY(ctx_arena_reserve(ctx, sizeof(ExpJob) * (size_t)n + out_bytes + 65536));
+    ctx->pinned_off = 0;
+    unsigned long long *d_out = (unsigned long long *)ctx_arena_alloc(ctx, out_bytes);
+    if (!d_out) { vfsms_set_error("overlap_stats: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    TRY(overlap_stats_device(ctx, H.data(), n, lo, hi, d_out));
+    HIP_TRY(hipMemcpyAsync(out3, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_exposure_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, const uint16_t *gain_q12)
+{
+    CTX_ENTER(ctx);
+    if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles || !gain_q12) { vfsms_set_error("exposure_apply: 1..%d tiles and a gain for each", VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
+    std::vector<int64_t> seen(tiles, tiles + n);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("exposure_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
+    std::vector<ExpTileHost> H(n);
+    std::vector<TileRec *> T(n);
+    for (int i = 0; i < n; i++) {
+        auto it = ctx->tiles.find(tiles[i]);
+        if (it == ctx->tiles.end()) { vfsms_set_error("exposure_apply: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
+        T[i] = &it->second;
+        if (!T[i]->owned) { vfsms_set_error("exposure_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
+    }
+    for (int i = 0; i < n; i++) {
+        TRY(tile_ready(ctx, *T[i]));
+        H[i] = ExpTileHost{T[i]->ptr, T[i]->stride, T[i]->h, T[i]->w * T[i]->ch};
+    }
+    TRY(ctx_arena_reserve(ctx, sizeof(ExpTileHost) * 2 * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    TRY(exposure_apply_device(ctx, H.data(), n, gain_q12));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // the tile table went through the pinned staging buffer: synchronous like every call that uses it
+    return VFSMS_OK;
+}
+
 // ---- ORB -------------------------------------------------------------------------------------------------------------------------
 static void orb_caps(const vfsms_orb_params *p, int *cap1, int *cap2, int *cap)
 {

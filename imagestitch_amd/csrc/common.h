@@ -350,6 +350,14 @@ struct ShadeTileHost { uint8_t *ptr; int stride; };
 int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, int percentile, int radius,
                           uint16_t *gain, uint16_t *q8, uint8_t *prof);
 int shade_apply_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, const uint16_t *gain);
+// exposure_kernels.hip: Method.exposureCompensation.  A pair: two whole tiles (pointers, row strides in bytes, rows, row lengths in
+// BYTES = w * ch) of one channel count and the offset in pixels (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)).  ExpJob is
+// what the kernel reads: the rectangle of B that has a partner in A, cut on the host in 64 bits, everything in bytes
+struct ExpPairHost { const uint8_t *a, *b; int sa, sb, ha, wa, hb, wb, ch, dx, dy; };
+struct ExpJob { const uint8_t *a, *b; int sa, sb, wa, wb, r0, nrows, c0, c1, dx, dyb; };
+struct ExpTileHost { uint8_t *ptr; int stride, h, wb; };
+int overlap_stats_device(vfsms_ctx *ctx, const ExpPairHost *pairs, int n, int lo, int hi, unsigned long long *d_out3);   // d_out3: [n][3] = N, Sa, Sb
+int exposure_apply_device(vfsms_ctx *ctx, const ExpTileHost *tiles, int n, const uint16_t *gain_q12);
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
 size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);

@@ -959,6 +959,8 @@ class Stitcher(Utility.Method):
                     use_res = True
             if self.shadingCorrection != "none":
                 self._correctShading(handles if use_res else None, shapes)
+            if self.exposureCompensation != "none":
+                self._compensateExposure(handles if use_res else None, shapes, originOffsetList)
             offsetList, rangeX, rangeY, resultRow, resultCol = self._layout(shapes, originOffsetList)
             self.printAndWrite("  The rectified offsetList is " + str(offsetList))
             if not device_fuse and not simple:
@@ -1035,6 +1037,21 @@ class Stitcher(Utility.Method):
             eng.shading_apply(field, tiles)
         finally:
             eng.shading_free(field)
+
+    def _compensateExposure(self, handles, shapes, originOffsetList):
+        """Method.exposureCompensation on the mosaic's resident tiles, in place (exposure.compensate, tests/exposure_ref.py): one gain per
+        tile from the overlaps under the offsets the mosaic is laid out by (originOffsetList carries the leading [0, 0]; a globalAdjust
+        result arrives here like any other list).  Runs behind the shading correction, on its output."""
+        eng = self.engine
+        if self.exposureCompensation != "gain":
+            raise ValueError("exposureCompensation must be 'none' or 'gain'")
+        if not hasattr(eng, "overlap_stats_batch") or not hasattr(eng, "exposure_apply") or handles is None:
+            raise NotImplementedError("exposureCompensation needs an engine with overlap_stats_batch / exposure_apply and device-resident tiles")
+        from .exposure import compensate
+        _gains, self.exposureReport = compensate(eng, handles, shapes, originOffsetList[1:], band=tuple(self.exposureBand),
+                                                 min_pixels=int(self.exposureMinPixels), max_gain=float(self.exposureMaxGain))
+        self.printAndWrite("  exposure compensation: %d edges, gains %.4f .. %.4f" %
+                           (self.exposureReport["edges"], self.exposureReport["gain_min"], self.exposureReport["gain_max"]))
 
     def _ingestForMosaic(self, files, color):
         """The mosaic's tiles from their files into reserved device tiles through a pool of decoder threads (one decode per file, the

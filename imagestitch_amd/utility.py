@@ -184,6 +184,21 @@ class Method():
     shadingMinTiles = 8
     shadingGain = None
 
+    # ---- per-tile exposure compensation after the shading correction, before the mosaic is laid out (no reference counterpart;
+    # exposure.py, tests/exposure_ref.py): "gain" sums, over every overlap of two tiles of the mosaic, the samples that are unclipped in
+    # both, fits one gain per tile by weighted least squares in the log domain and multiplies the resident tiles by it (registration
+    # never sees corrected pixels).  The fit has no constants; the attributes below are conditions, none of them tuned:
+    exposureCompensation = "none"   # "none" or "gain"
+    # the samples that count, lo <= p <= hi in both tiles: everything but the two clipped codes of an 8-bit sensor -- a sample at 0 or
+    # 255 has lost its value, so its ratio to the other tile says nothing about exposure
+    exposureBand = (1, 254)
+    # an overlap with fewer shared pixels is no edge, and an edge with fewer unclipped samples is not measured: the value of
+    # adjustMinPixels, for the same reason (smaller than a 64 x 64 patch cannot be judged)
+    exposureMinPixels = 4096
+    # a condition, not a measurement: exposure drift within a scan is a matter of per cent; a gain beyond 2 means the overlap statistic
+    # is not an exposure ratio (a wrong offset, different content), and the tile is held at the bound
+    exposureMaxGain = 2.0
+
     # ---- pyramidal output (no reference counterpart; tests/pyramid_ref.py): imageSetStitch* write every mosaic as ONE tiled pyramidal
     # TIFF (PyramidTiffBandWriter: level 0 in pyramidTile x pyramidTile tiles, then reduced-resolution pages, each half the size of the one
     # before) that slide and micrograph viewers open without reading all of it.  The levels are formed on the device from the band that

@@ -540,6 +540,20 @@ int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *til
 /* releases a field of vfsms_shading_estimate / vfsms_shading_from_gain (tests/shading_ref.py has no state to free)              */
 int vfsms_shading_free(vfsms_ctx *ctx, int64_t field);
 
+/* ---- per-tile exposure compensation (Method.exposureCompensation).  No reference counterpart: the specification is
+ * tests/exposure_ref.py; the sums and the corrected bytes are integers and equal it exactly. ------------------------------------ */
+/* The overlap statistic of n pairs of resident tiles (gray or interleaved colour, both tiles of a job of one channel count, any
+ * shapes, any row strides).  A job is a vfsms_ncc_job: tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy).  Over every sample
+ * (a byte of a pixel) of the B pixels whose partner lies inside A, with lo <= a <= hi and lo <= b <= hi (0 <= lo <= hi <= 255): out3 =
+ * int64[n][3] = {N, Sa, Sb}, the number of such samples and the sums of the A and of the B samples; an empty rectangle gives zeros.
+ * One launch sequence for all jobs.  Waits for reserved / pending tiles like every batch call; the tiles are only read.
+ * VFSMS_ERR_BAD_ARG: an unknown handle, different channel counts in a job, lo > hi or a bound outside 0..255.  n = 0 is fine.      */
+int vfsms_overlap_stats_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int lo, int hi, int64_t *out3);
+/* out = min(255, (p * gain_q12[i] + 2048) >> 12) in place on every sample of tile i, n (1..4096) resident tiles of any shapes
+ * (tests/exposure_ref.py: apply); a tile whose gain is 4096 is not touched.  Refused like vfsms_shading_apply: a tile from
+ * vfsms_tile_wrap, a tile named twice in one call.  Waits for reserved / pending tiles.                                            */
+int vfsms_exposure_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, const uint16_t *gain_q12);
+
 #ifdef __cplusplus
 }
 #endif
