@@ -1,7 +1,8 @@
 """The mosaic canvas path end to end, through public Engine methods only: the three forms of the walk (host-tile calls, resident per-tile
 calls, the one-call walk) against each other for every mode code, the fade against the oracle walk, average / maximum / minimum against a
 numpy restatement of the reference walk, and the refusals.  Small two-row mosaics placed by their true offsets: a wide strip, a tall strip
-and corner ROIs, both signs of dx and dy, ROI widths in all three ranges the statistics kernel distinguishes (<= 256, <= 512, > 512)."""
+and corner ROIs, both signs of dx and dy, ROI widths in all three ranges the statistics kernel distinguishes (<= 256, <= 512, > 512).
+Irregular layouts (random placements, edge sizes) meet the reference in tests/test_canvas_reference_gpu.py."""
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 import imagestitch_amd as isa
 from imagestitch_amd._lib import VFSMS_ERR_BAD_ARG
 from imagestitch_amd.synthetic import SyntheticGrid
+from canvas_cases import reference_simple_walk as _reference_simple_walk      # Stitcher.py:434-486 + 498-504 + ImageFusion.py:12-41 in numpy
 
 PASTE, FADE, TRIG, AVERAGE, MAXIMUM, MINIMUM, MULTIBAND, SEAMLINE = -1, 0, 1, 2, 3, 4, 6, 7
 MODES = (PASTE, FADE, TRIG, AVERAGE, MAXIMUM, MINIMUM, MULTIBAND, SEAMLINE)
@@ -163,25 +165,6 @@ def test_fade_walk_equals_the_oracle_walk(engine, oracle, width):
     ref = OracleEngine(oracle)
     want = _walk(ref, "host", tiles, None, geom, rows, cols)
     assert not isinstance(got, str) and got.shape == want.shape and np.array_equal(got, want)
-
-
-def _reference_simple_walk(tiles, geom, rows, cols, mode):
-    """Stitcher.py:434-486 with fuseImage's fill-in (Stitcher.py:498-504) and ImageFusion.py:12-41, in numpy"""
-    cv = np.zeros((rows, cols) + tiles[0].shape[2:], np.int64) - 1
-    for t, g in zip(tiles, geom):
-        y0, x0, ry0, rx0, ry1, rx1 = [int(v) for v in g[:6]]
-        A = cv[ry0:ry1, rx0:rx1].copy()
-        cv[y0:y0 + t.shape[0], x0:x0 + t.shape[1]] = t
-        if g[8] == PASTE:
-            continue
-        B = cv[ry0:ry1, rx0:rx1].copy()
-        A[A == -1] = 0
-        B[B == -1] = 0
-        A[A == 0] = B[A == 0]
-        B[B == 0] = A[B == 0]
-        cv[ry0:ry1, rx0:rx1] = np.uint8((A + B) / 2) if mode == AVERAGE else np.maximum(A, B) if mode == MAXIMUM else np.minimum(A, B)
-    cv[cv == -1] = 0
-    return cv.astype(np.uint8)
 
 
 @pytest.mark.gpu

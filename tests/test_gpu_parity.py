@@ -1892,7 +1892,8 @@ def test_random_placements_fused_from_the_rectangle_list_equal_the_statistics_pa
     """The host-side geometry of round 6 (valid count, getWeightsMatrix's rowIndex / colIndex for the four quadrants, the degenerate cases) against
     the statistics kernel on placements no serpentine produces: tiles dropped left of, above, below and across earlier ones (all four `index`
     quadrants, scans from both sides, negative dx / dy), ROI = tile rectangle cut by the bounding box of what lies there (Stitcher.py:446-457)
-    or a random sub-rectangle of the tile.  Same bytes, and the same verdict on a degenerate geometry (both raise or neither)."""
+    or a random sub-rectangle of the tile.  Same bytes, and the same verdict on a degenerate geometry (both raise or neither).
+    Path against path only: tests/test_canvas_reference_gpu.py holds these layouts (tests/canvas_cases.random_canvases) to the reference walk."""
     rng = np.random.default_rng(20190158)
     keep = os.environ.get("VFSMS_FUSE_ANALYTIC")
     n_err = n_corner = 0
