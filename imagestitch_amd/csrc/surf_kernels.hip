@@ -626,22 +626,52 @@ __device__ __forceinline__ bool interpolate_keypoint(const float N9[3][9], int d
     return ok;
 }
 
-// One launch covers every octave: blockIdx.x walks the 64 x 64-cell tiles of octave 0, then those of octave 1, ... (NmsPlan), so
-// the small coarse octaves fill the tail of the fine one instead of paying a launch each; blockIdx.y = roi * n_middle + middle layer.
-// A wave streams NMS_RW rows of a 64-column strip with the three rows it needs in registers (the +-1 column taps are unaligned
-// loads of the same lines, L1 hits): no LDS tile, no barrier in the scan.  A cell above the threshold that beats its 8 own-layer
-// neighbours -- a fraction of a per cent of the cells -- is queued in the wave's LDS queue (ballot + prefix count); afterwards the
-// queue is examined one cell per lane against the layers below and above, so the 18 extra taps and the 3 x 3 solve run on full waves.
-#define NMS_RW 16
-#ifndef NMS_PF
-#define NMS_PF 3               // rows in flight ahead of the compared row
+// One launch covers every octave: blockIdx.x walks the tiles of octave 0 (NMS_TW evaluated columns x NMS_TH rows), then those of
+// octave 1, ... (NmsPlan), so the small coarse octaves fill the tail of the fine one instead of paying a launch each; blockIdx.y =
+// roi * n_middle + middle layer.  A wave streams NMS_RW rows of a 64-column strip: no LDS tile, no barrier in the scan.
+//
+// The scan.  A lane loads ONE value per row, its own column; the left and right neighbours come from the neighbouring lanes
+// (v_mov_b32_dpp wave_shr:1 / wave_shl:1), so lanes 0 and 63 are halo -- they load columns but evaluate none -- and a tile evaluates
+// NMS_TW = 62 columns.  (Until the candidate-path round every lane issued three loads per row, the +-1 taps as unaligned loads of the
+// same lines: L1 hits, but three texture-addresser requests per cell where one does.)  The nine strict compares are a maximum tree:
+// h = max3(left, centre, right) is formed once per loaded row and serves as the row above, then as the row below; a cell is queued
+// when v > max3(h_up, h_down, max3(left_mid, right_mid, hessianThreshold)).  For values that are not NaN, v > max(a, b, ...) is exactly
+// v > a && v > b && ... (the maximum IS one of its operands; -0 and +0 compare alike), and the determinants are finite by
+// construction: integer box sums times finite weights.  An evaluated cell has all eight neighbours inside the region its layer's
+// Hessian kernel wrote; lanes and rows outside the evaluated range may combine unwritten cells and stay masked (a threshold of
+// +inf, the row bound).
+// With one register per row instead of three, 18 rows are in flight per lane (NMS_PF) and a wave scans 32 rows instead of 16 (NMS_RW).
+//
+// A cell above the threshold that beats its 8 own-layer neighbours -- a fraction of a per cent of the cells -- is queued in the
+// wave's LDS queue (ballot + prefix count); afterwards the queue is examined one cell per lane against the layers below and above,
+// so the 18 extra taps and the 3 x 3 solve run on full waves.
+// v_max3_f32 spelled out: fmaxf() compiles to the same maximum behind one canonicalising v_max_f32 x, x per operand (IEEE mode: a
+// signalling NaN would have to be quieted), which doubles the scan's arithmetic for values that are finite by construction.
+__device__ __forceinline__ float nms_max3(float a, float b, float c)
+{
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// NMS_RW: rows a wave scans.  16 -> 32 is -8 % on the launch: half the workgroups, 34 rows loaded per 32 instead of 18 per 16.
+// NMS_PF: rows in flight ahead of the compared row; 3 / 7 / 16 measured at 16 rows per wave (profiles/r11_microbench_variants.txt).
+#ifndef NMS_RW
+#define NMS_RW 32
 #endif
+#ifndef NMS_PF
+#define NMS_PF 16
+#endif
+#define NMS_TW 62              // evaluated columns per tile: lanes 1 .. 62 (lanes 0 and 63 hold the halo columns)
 #define NMS_TH (4 * NMS_RW)
 #define NMS_LOCAL 192
+// A queue entry is (row << 8) | lane in 16 bits, and the queue holds one entry per 2 x 2 block of a strip's 64 columns.
+static_assert(NMS_RW % 2 == 0 && NMS_RW <= 256, "k_nms: queue entries keep the row in 8 bits; the queue bound pairs the rows");
+static_assert(NMS_TW + 2 == 64, "k_nms: one wave = the evaluated columns + two halo lanes");
 struct NmsPlan { int noct; int first[VFSMS_MAX_OCTAVES + 1]; int tiles_x[VFSMS_MAX_OCTAVES]; };
 
-__global__ __launch_bounds__(256) void k_nms(const RoiDev *rois, const LayerPat *pats, int layers_per_octave,
-                                             int n_middle, NmsPlan plan, float hessianThreshold)
+// (amdgpu_waves_per_eu: 32 rows per wave would otherwise take 65 registers, one over what eight waves per SIMD allow)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void k_nms(const RoiDev *rois, const LayerPat *pats, int layers_per_octave, int n_middle, NmsPlan plan, float hessianThreshold)
 {
     int octave = 0;
     while (octave + 1 < plan.noct && (int)blockIdx.x >= plan.first[octave + 1]) octave++;
@@ -657,9 +687,11 @@ __global__ __launch_bounds__(256) void k_nms(const RoiDev *rois, const LayerPat 
     const int margin = (pats[li + 1].size / 2) / ss + 1;
     if (pats[li + 1].size > R.h || pats[li + 1].size > R.w) return;   // upper layer not computed: nothing readable
     const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y), tid = wave * 64 + lane;
-    const int j0 = margin + bx * 64, i0 = margin + by * NMS_TH;
-    if (j0 >= lcols - margin || i0 >= lrows - margin) return;        // (whole workgroup)
-    __shared__ unsigned short queue[4][NMS_RW * 64];
+    const int j0 = margin - 1 + bx * NMS_TW, i0 = margin + by * NMS_TH;   // j0: the column of lane 0 (halo)
+    if (j0 + 1 >= lcols - margin || i0 >= lrows - margin) return;    // (whole workgroup)
+    // Strict maxima over 8 neighbours are never adjacent, diagonals included: at most one per 2 x 2 block, NMS_RW / 2 x 32 per
+    // strip.  (With 32 rows per wave the full-size queue would be 16 KB per workgroup.)
+    __shared__ unsigned short queue[4][NMS_RW * 16];
     __shared__ int cn, cbase;
     __shared__ Cand local[NMS_LOCAL];
     if (tid == 0) cn = 0;
@@ -670,29 +702,39 @@ __global__ __launch_bounds__(256) void k_nms(const RoiDev *rois, const LayerPat 
     const int ia = i0 + wave * NMS_RW;
     int nq = 0;
     if (ia < lrows - margin) {
-        // evaluated cells have all 8 neighbours inside the layer; the clamps only keep the loads of the other lanes in bounds
-        const int jl = min(j - 1, lcols - 1), jc = min(j, lcols - 1), jr = min(j + 1, lcols - 1);
-        const bool jev = j < lcols - margin;
-        // Round 6: the rows are requested NMS_PF rows AHEAD of the row they are compared in.  The scan was one dependent round trip per
-        // row (three loads, compare, next row): a workgroup needs 16 of them and a CU holds eight workgroups, which is what the launch
-        // lasted (PMC: the waves waited 82 % of their cycles).  rw[k] = row ia - 1 + k of the strip (18 rows: the 16 scanned + one above, one below).
-        float rw[NMS_RW + 2][3];
+        // evaluated cells have all 8 neighbours inside the layer; the clamps only keep the loads of the other lanes and rows in bounds
+        const uint32_t joff = (uint32_t)min(j, lcols - 1) * 4u;
+        // a lane that evaluates no column (halo, or past the layer's last evaluated column) compares against +inf instead of the threshold
+        const float thr = (lane >= 1 && lane <= NMS_TW && j < lcols - margin) ? hessianThreshold : __builtin_inff();
+        // The rows are requested NMS_PF rows AHEAD of the row they are compared in (round 6: the scan was one dependent round trip per
+        // row, and the waves waited 82 % of their cycles).  cv[k] = row ia - 1 + k of the strip (the NMS_RW scanned + one above,
+        // one below), hm[k] = the maximum of its three columns around this lane.  Row base scalar, column offset 32-bit.
+        float cv[NMS_RW + 2], hm[NMS_RW + 2], lr[NMS_RW + 2];
         auto load_row = [&](int k) {
-            g_cf32 rp = d2 + (size_t)min(ia - 1 + k, lrows - 1) * st;
-            rw[k][0] = rp[jl]; rw[k][1] = rp[jc]; rw[k][2] = rp[jr];
+            const GAS char *rp = (const GAS char *)(d2 + (size_t)min(ia - 1 + k, lrows - 1) * st);
+            cv[k] = *(g_cf32)(rp + joff);
+        };
+        // wave_shr:1: lane n takes lane n - 1's value (its left neighbour); wave_shl:1: lane n + 1's
+        auto spread_row = [&](int k) {
+            const int c = __float_as_int(cv[k]);
+            const float lf = __int_as_float(__builtin_amdgcn_update_dpp(0, c, 0x138, 0xf, 0xf, true));      // (lane 0 takes 0: halo)
+            const float rt = __int_as_float(__builtin_amdgcn_update_dpp(0, c, 0x130, 0xf, 0xf, true));      // (lane 63 takes 0: halo)
+            lr[k] = nms_max3(lf, rt, thr);
+            hm[k] = nms_max3(lf, cv[k], rt);
         };
 #pragma unroll
-        for (int k = 0; k < 2 + NMS_PF; k++) load_row(k);
+        for (int k = 0; k < 2 + NMS_PF && k < NMS_RW + 2; k++) load_row(k);
+        spread_row(0); spread_row(1);
         const unsigned long long below = (1ull << lane) - 1ull;
+        const int nrows = lrows - margin - ia;           // (scalar) the layer's last evaluated row may lie inside this strip
 #pragma unroll
         for (int r = 0; r < NMS_RW; r++) {
-            const int i = ia + r;
             if (r + 2 + NMS_PF < NMS_RW + 2) load_row(r + 2 + NMS_PF);
-            const float *up = rw[r], *mid = rw[r + 1], *dn = rw[r + 2];
-            const float v = mid[1];
-            const bool c2 = jev && i < lrows - margin && v > hessianThreshold &&
-                            v > up[0] && v > up[1] && v > up[2] && v > mid[0] && v > mid[2] && v > dn[0] && v > dn[1] && v > dn[2];
-            const unsigned long long m = __ballot(c2);
+            spread_row(r + 2);
+            const float v = cv[r + 1], nb = nms_max3(hm[r], hm[r + 2], lr[r + 1]);
+            const bool c2 = v > nb;
+            // m: the compare's own lane mask (the compiler sinks c2's second v_cmp into the rare branch below: one per row otherwise)
+            const unsigned long long m = r < nrows ? __builtin_amdgcn_fcmpf(v, nb, 2 /* ordered > */) : 0ull;
             if (m) {
                 if (c2) queue[wave][nq + __popcll(m & below)] = (unsigned short)((r << 8) | lane);
                 nq += __popcll(m);
@@ -865,31 +907,95 @@ __global__ __launch_bounds__(1024) void k_bucket_sort(const RoiDev *rois)
     R.keep_pos[tid] = base[tid]; R.order[tid] = hist[tid];
 }
 
-// rank of every candidate inside its bucket (a few dozen to a few hundred full KeypointGreater compares), 256 candidates per workgroup
+// rank of every candidate inside its bucket (a few dozen to a few hundred full KeypointGreater compares), 256 candidates per workgroup.
+// A workgroup ranks 256 consecutive positions of the bucket-sorted list, and the buckets those positions belong to form ONE contiguous
+// span of records: from the start of the first position's bucket to the end of the last position's.  The span's k1 keys are staged in
+// LDS (coalesced over the records) and every lane walks its bucket there, four reads in flight.  k2 / k3 are read from the records
+// only on a k1 tie with ANOTHER candidate (equal response, size and octave: rare outside periodic images); the candidate's own record
+// ties with itself, counts nothing and is skipped.
+// Until the candidate-path round the walk read the records themselves: one 8-byte load at a lane-private address and a full wait per
+// compare, as many dependent round trips as the largest bucket among a wave's lanes holds (122 on a production strip), with the
+// texture addresser busy two thirds of the launch on the scattered addresses.
+// A span beyond BRANK_STAGE keys (periodic images: one bucket of 1524) takes the direct walk for that workgroup.
+#define BRANK_STAGE 1024
 __global__ __launch_bounds__(256) void k_bucket_rank(const RoiDev *rois, const LayerPat *pats)
 {
     const RoiDev &R = rois[blockIdx.y];
     const int n = min(R.counters[0], R.cap);
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const SortRec *S = reinterpret_cast<const SortRec *>(R.patch);
-    const SortRec me = S[p];
-    const int b = sort_bucket(me.k1);
-    const int lo = R.keep_pos[b], hi = lo + R.order[b];
+    const int p0 = blockIdx.x * 256;
+    if (p0 >= n) return;                                              // (whole workgroup)
+    const int p = p0 + (int)threadIdx.x;
+    const bool live = p < n;
+    // SortRec q = words 4 q .. 4 q + 3: k1, k2, k3, (idx, pad)
+    const GAS unsigned long long *S = (const GAS unsigned long long *)R.patch;
+    static_assert(sizeof(SortRec) == 32, "k_bucket_rank reads the records as four 64-bit words");
+    g_ci32 bpos = (g_ci32)R.keep_pos, bcnt = (g_ci32)R.order;
+    __shared__ unsigned long long key1[BRANK_STAGE];
+    __shared__ int span[2];
+    SortRec me; me.k1 = me.k2 = me.k3 = 0; me.idx = 0;
+    int lo = 0, hi = 0;
+    if (live) {
+        me.k1 = S[4 * p]; me.k2 = S[4 * p + 1]; me.k3 = S[4 * p + 2]; me.idx = (int)(uint32_t)S[4 * p + 3];
+        const int b = sort_bucket(me.k1);
+        lo = bpos[b]; hi = lo + bcnt[b];
+        // buckets lie in position order: the first position's starts the span, the last position's ends it
+        if (threadIdx.x == 0) span[0] = lo;
+        if (p == min(p0 + 255, n - 1)) span[1] = hi;
+    }
+    __syncthreads();
+    const int s0 = span[0], s1 = span[1];
     int rank = lo;
-    for (int q = lo; q < hi; q++) {
-        const unsigned long long a1 = S[q].k1;
-        if (a1 > me.k1) rank++;
-        else if (a1 == me.k1) {
-            const unsigned long long a2 = S[q].k2, a3 = S[q].k3;
-            rank += (a2 < me.k2 || (a2 == me.k2 && a3 < me.k3)) ? 1 : 0;
+    auto tie = [&](int q) {                           // equal k1 at record q != p: KeypointGreater's y, x, then (layer, i, j)
+        const unsigned long long a2 = S[4 * q + 1], a3 = S[4 * q + 2];
+        return (a2 < me.k2 || (a2 == me.k2 && a3 < me.k3)) ? 1 : 0;
+    };
+    if (s1 - s0 <= BRANK_STAGE) {                                     // (whole workgroup)
+        for (int q = s0 + (int)threadIdx.x; q < s1; q += 256) key1[q - s0] = S[4 * q];
+        __syncthreads();
+        if (live) {
+            int q = lo;
+            for (; q + 4 <= hi; q += 4) {
+                unsigned long long a[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) a[u] = key1[q - s0 + u];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    rank += (a[u] > me.k1) ? 1 : 0;
+                    if (a[u] == me.k1 && q + u != p) rank += tie(q + u);
+                }
+            }
+            for (; q < hi; q++) {
+                const unsigned long long a1 = key1[q - s0];
+                rank += (a1 > me.k1) ? 1 : 0;
+                if (a1 == me.k1 && q != p) rank += tie(q);
+            }
+        }
+    } else if (live) {
+        for (int q = lo; q < hi; q++) {
+            const unsigned long long a1 = S[4 * q];
+            rank += (a1 > me.k1) ? 1 : 0;
+            if (a1 == me.k1 && q != p) rank += tie(q);
         }
     }
-    const Cand c = R.cand[me.idx];
+    if (!live) return;
+    Cand c;
+    {
+        constexpr int CW = sizeof(Cand) / 4;
+        g_ci32 src = (g_ci32)R.cand + (size_t)me.idx * CW;
+        int32_t *cw = (int32_t *)&c;
+#pragma unroll
+        for (int w = 0; w < CW; w++) cw[w] = src[w];
+    }
     vfsms_keypoint kp;
     kp.x = c.x; kp.y = c.y; kp.size = c.size; kp.angle = -1.f; kp.response = c.response;
     kp.octave = c.octave; kp.class_id = cand_class_id(R, pats, c);
-    R.kps[rank] = kp;
+    {
+        constexpr int KW = sizeof(vfsms_keypoint) / 4;
+        g_i32 dst = (g_i32)R.kps + (size_t)rank * KW;
+        const int32_t *kw = (const int32_t *)&kp;
+#pragma unroll
+        for (int w = 0; w < KW; w++) dst[w] = kw[w];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2129,7 +2235,7 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
             int step = 1;
             for (int o = 0; o < p->n_octaves && o < VFSMS_MAX_OCTAVES; o++) {
                 const int lrows = q.h / step, lcols = q.w / step;
-                const int tx = (lcols + 63) / 64, ty = (lrows + NMS_TH - 1) / NMS_TH;
+                const int tx = (lcols + NMS_TW - 1) / NMS_TW, ty = (lrows + NMS_TH - 1) / NMS_TH;      // (an upper bound: the margins come off in the kernel)
                 plan.tiles_x[o] = tx > 0 ? tx : 1;
                 plan.first[o + 1] = plan.first[o] + tx * ty;
                 plan.noct = o + 1;
