@@ -22,9 +22,9 @@
 // Heads and tails.  The overlap's columns depend on j, so a chunk is INTERIOR when all its 16 columns are shared under every shift of the
 // tile, else an EDGE chunk: at most four per row (two at each end), processed in a second loop over (row, edge slot) items with the
 // same data path plus a byte mask per (chunk, shift) that zeroes both operands outside the shared columns.  Nothing is restricted to a
-// common core.  An aligned dword is loaded only when it holds at least one byte of the row, so no load leaves the page of a valid byte.
+// common core.  The masks, the guarded loader of A's bytes and the workgroup reduction are overlap_sums.h's.
 #include "common.h"
-#include "verify_math.h"
+#include "overlap_sums.h"
 #include <algorithm>
 
 #define ADJ_JT 9             // column shifts per workgroup: 9 x 5 lane sums
@@ -33,17 +33,6 @@
 #define ADJ_LANE_ITEMS 32    // chunks a lane should get, at least, before the grid grows
 #define ADJ_LANE_CAP 1024    // chunks a lane may get per loop, at most: 2 x 1024 x 4 x 4 x 255^2 < 2^32
 #define ADJ_MAX_GX 64
-
-struct AdjAcc { uint32_t a, b, aa, bb, ab; };
-
-// bit b of a nibble -> byte b of a dword (0xff / 0x00)
-__device__ __forceinline__ uint32_t adj_byte_mask(uint32_t nib) { return ((nib * 0x00204081u) & 0x01010101u) * 0xffu; }
-// the bits p of [0, n) whose position x0 + p lies in [0, w)
-__device__ __forceinline__ uint32_t adj_range_bits(int x0, int w, int n)
-{
-    const int lo = min(max(-x0, 0), n), hi = min(max(w - x0, 0), n);
-    return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
-}
 
 // the chunks of B row r for a workgroup whose shared columns are [cl, ch) (under any shift of its tile) and [kl, kh) (under all of them):
 // chunk k covers the columns [c0 + 16 k, c0 + 16 k + 16), k in [0, nk); [ki0, ki1) are interior
@@ -59,20 +48,7 @@ __device__ __forceinline__ AdjRow adj_row(const AdjJob &J, int r, int cl, int ch
     return g;
 }
 
-// the 24 bytes of A from address `pa` on as six dwords: the aligned dwords around them, those that hold a column of [0, w) of the row
-// (`ca` is the column of pa[0]; an interior chunk passes the end of the bytes it needs for w), funnel-shifted by pa's alignment
-__device__ __forceinline__ void adj_load_a(uintptr_t pa, int ca, int w, uint32_t e[6])
-{
-    const unsigned m = (unsigned)(pa & 3u);
-    const uint32_t *a4 = reinterpret_cast<const uint32_t *>(pa - m);
-    const int cq = ca - (int)m;
-    uint32_t d[7];
-#pragma unroll
-    for (int q = 0; q < 7; q++) d[q] = (cq + 4 * q + 3 >= 0 && cq + 4 * q < w) ? a4[q] : 0u;
-#pragma unroll
-    for (int q = 0; q < 6; q++) e[q] = __builtin_amdgcn_alignbyte(d[q + 1], d[q], m);
-}
-// dword t of the chunk's partner bytes under column shift jj of the tile
+// dword t of the chunk's partner bytes under column shift JJ of the tile; e: the 24 bytes of A that the tile's shifts cover (load_partner<6>)
 template <int JJ>
 __device__ __forceinline__ uint32_t adj_shifted(const uint32_t e[6], int t)
 {
@@ -82,10 +58,10 @@ __device__ __forceinline__ uint32_t adj_shifted(const uint32_t e[6], int t)
 }
 
 template <int JJ>
-__device__ __forceinline__ void adj_interior(const uint32_t e[6], const uint4 &bv, AdjAcc acc[ADJ_JT])
+__device__ __forceinline__ void adj_interior(const uint32_t e[6], const uint4 &bv, Sums5 acc[ADJ_JT])
 {
     const uint32_t b[4] = {bv.x, bv.y, bv.z, bv.w};
-    AdjAcc &s = acc[JJ];
+    Sums5 &s = acc[JJ];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         const uint32_t a = adj_shifted<JJ>(e, t);
@@ -97,19 +73,14 @@ __device__ __forceinline__ void adj_interior(const uint32_t e[6], const uint4 &b
 }
 
 template <int JJ>
-__device__ __forceinline__ void adj_edge(const uint32_t e[6], const uint32_t b[4], uint32_t mB, uint32_t mA, AdjAcc acc[ADJ_JT])
+__device__ __forceinline__ void adj_edge(const uint32_t e[6], const uint32_t b[4], uint32_t mB, uint32_t mA, Sums5 acc[ADJ_JT])
 {
     const uint32_t m16 = mB & (mA >> JJ);
-    AdjAcc &s = acc[JJ];
+    Sums5 &s = acc[JJ];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-        const uint32_t bm = adj_byte_mask((m16 >> (4 * t)) & 15u);
-        const uint32_t a = adj_shifted<JJ>(e, t) & bm, bb = b[t] & bm;
-        s.a = __builtin_amdgcn_sad_u8(a, 0u, s.a);
-        s.b = __builtin_amdgcn_sad_u8(bb, 0u, s.b);
-        s.aa = __builtin_amdgcn_udot4(a, a, s.aa, false);
-        s.bb = __builtin_amdgcn_udot4(bb, bb, s.bb, false);
-        s.ab = __builtin_amdgcn_udot4(a, bb, s.ab, false);
+        const uint32_t bm = byte_mask((m16 >> (4 * t)) & 15u);
+        acc4(adj_shifted<JJ>(e, t) & bm, b[t] & bm, s);
     }
     if constexpr (JJ + 1 < ADJ_JT) adj_edge<JJ + 1>(e, b, mB, mA, acc);
 }
@@ -132,7 +103,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_adjust_sums(const AdjJob *jobs,
     const int nrows = r1 - r0;
     const int stride = (int)gridDim.x * ADJ_THREADS, first = (int)blockIdx.x * ADJ_THREADS + (int)threadIdx.x;
 
-    AdjAcc acc[ADJ_JT];
+    Sums5 acc[ADJ_JT];
 #pragma unroll
     for (int q = 0; q < ADJ_JT; q++) acc[q] = {0u, 0u, 0u, 0u, 0u};
     uint32_t sbI = 0u, sbbI = 0u;                         // Sb, Sbb of the interior chunks: the same for every shift of the tile
@@ -150,7 +121,7 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_adjust_sums(const AdjJob *jobs,
                 const int c = g.c0 + (k << 4);
                 const uint4 bv = *reinterpret_cast<const uint4 *>(g.pb + c);
                 uint32_t e[6];
-                adj_load_a((uintptr_t)(J.a + (size_t)(r + di) * J.sa) + (uintptr_t)(intptr_t)(c + dj0), c + dj0, min(w, c + dj0 + jte + 15), e);
+                load_partner<6>((uintptr_t)(J.a + (size_t)(r + di) * J.sa) + (uintptr_t)(intptr_t)(c + dj0), c + dj0, min(w, c + dj0 + jte + 15), e);
                 sbI = __builtin_amdgcn_sad_u8(bv.x, 0u, sbI); sbI = __builtin_amdgcn_sad_u8(bv.y, 0u, sbI);
                 sbI = __builtin_amdgcn_sad_u8(bv.z, 0u, sbI); sbI = __builtin_amdgcn_sad_u8(bv.w, 0u, sbI);
                 sbbI = __builtin_amdgcn_udot4(bv.x, bv.x, sbbI, false); sbbI = __builtin_amdgcn_udot4(bv.y, bv.y, sbbI, false);
@@ -174,30 +145,18 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_adjust_sums(const AdjJob *jobs,
 #pragma unroll
             for (int t = 0; t < 4; t++) b[t] = (c + 4 * t + 3 >= 0 && c + 4 * t < w) ? b4[t] : 0u;
             uint32_t e[6];
-            adj_load_a((uintptr_t)(J.a + (size_t)(r + di) * J.sa) + (uintptr_t)(intptr_t)(c + dj0), c + dj0, w, e);
-            adj_edge<0>(e, b, adj_range_bits(c, w, 16), adj_range_bits(c + dj0, w, 24), acc);
+            load_partner<6>((uintptr_t)(J.a + (size_t)(r + di) * J.sa) + (uintptr_t)(intptr_t)(c + dj0), c + dj0, w, e);
+            adj_edge<0>(e, b, range_bits(c, 0, w, 16), range_bits(c + dj0, 0, w, 24), acc);
         }
     }
 
-    __shared__ unsigned long long part[ADJ_THREADS / 64][ADJ_JT * 5];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long v[ADJ_JT * 5];
 #pragma unroll
     for (int jj = 0; jj < ADJ_JT; jj++) {
-        const unsigned long long v5[5] = {acc[jj].a, (unsigned long long)acc[jj].b + sbI, acc[jj].aa, (unsigned long long)acc[jj].bb + sbbI, acc[jj].ab};
-#pragma unroll
-        for (int q = 0; q < 5; q++) {
-            unsigned long long v = v5[q];
-            for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-            if (lane == 0) part[wid][jj * 5 + q] = v;
-        }
+        v[jj * 5] = acc[jj].a; v[jj * 5 + 1] = (unsigned long long)acc[jj].b + sbI; v[jj * 5 + 2] = acc[jj].aa;
+        v[jj * 5 + 3] = (unsigned long long)acc[jj].bb + sbbI; v[jj * 5 + 4] = acc[jj].ab;
     }
-    __syncthreads();
-    if ((int)threadIdx.x < jte * 5) {
-        unsigned long long v = 0ull;
-#pragma unroll
-        for (int q = 0; q < ADJ_THREADS / 64; q++) v += part[q][threadIdx.x];
-        if (v) atomicAdd(sums + ((size_t)(blockIdx.z * C + ci) * (size_t)(njt * ADJ_JT) + (size_t)(jt * ADJ_JT)) * 5 + threadIdx.x, v);
-    }
+    wg_add_u64<ADJ_JT * 5, ADJ_THREADS / 64>(v, sums + ((size_t)(blockIdx.z * C + ci) * (size_t)(njt * ADJ_JT) + (size_t)(jt * ADJ_JT)) * 5, jte * 5);
 }
 
 // A workgroup per job: score every candidate in the specification's order of operations, keep the best double score; ties go to the
@@ -210,10 +169,8 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_adjust_pick(const AdjJob *jobs,
     double bs = -2.0; int bd2 = 0x7fffffff, bc = 0x7fffffff;
     for (int cidx = threadIdx.x; cidx < CC; cidx += ADJ_THREADS) {
         const int ci = cidx / C, cj = cidx - ci * C, i = ci - R, j = cj - R;
-        const Overlap o = verify_overlap(J.h, J.w, J.dx + i, J.dy + j);
-        const long long N = (long long)max(0, o.r1 - o.r0) * (long long)max(0, o.c1 - o.c0);
-        const unsigned long long *s = sums + ((size_t)(blockIdx.x * C + ci) * (size_t)(njt * ADJ_JT) + cj) * 5;
-        const double score = verify_score(N, (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], min_pixels);
+        long long N;
+        const double score = overlap_score(J.h, J.w, J.dx + i, J.dy + j, sums + ((size_t)(blockIdx.x * C + ci) * (size_t)(njt * ADJ_JT) + cj) * 5, min_pixels, &N);
         if (surface) surface[(size_t)blockIdx.x * CC + cidx] = verify_fixed(score);
         const int d2 = i * i + j * j;
         if (score > bs || (score == bs && (d2 < bd2 || (d2 == bd2 && cidx < bc)))) { bs = score; bd2 = d2; bc = cidx; }
@@ -231,8 +188,8 @@ __global__ __launch_bounds__(ADJ_THREADS) void k_adjust_pick(const AdjJob *jobs,
     }
     if (threadIdx.x == 0) {
         const int cidx = s_c[0], ci = cidx / C, cj = cidx - ci * C;
-        const Overlap o = verify_overlap(J.h, J.w, J.dx + ci - R, J.dy + cj - R);
-        const long long N = (long long)max(0, o.r1 - o.r0) * (long long)max(0, o.c1 - o.c0);
+        long long N;                                          // the winner's shared pixels; its score is s_s[0]
+        (void)overlap_score(J.h, J.w, J.dx + ci - R, J.dy + cj - R, sums + ((size_t)(blockIdx.x * C + ci) * (size_t)(njt * ADJ_JT) + cj) * 5, min_pixels, &N);
         int32_t *out = best4 + 4 * (size_t)blockIdx.x;
         out[0] = ci - R; out[1] = cj - R; out[2] = verify_fixed(s_s[0]); out[3] = (int32_t)N;
     }

@@ -389,6 +389,15 @@ static int tile_ready(vfsms_ctx *ctx, TileRec &t)
     if (t.pending) { HIP_TRY(hipStreamWaitEvent(ctx->stream, t.ready, 0)); t.pending = false; }
     return VFSMS_OK;
 }
+// the two resident tiles a job of `who` names, handed over (tile_ready); what else they must satisfy is the caller's to check
+static int resident_pair(vfsms_ctx *ctx, const char *who, int k, const vfsms_ncc_job &j, TileRec **A, TileRec **B)
+{
+    auto ia = ctx->tiles.find(j.tile_a), ib = ctx->tiles.find(j.tile_b);
+    if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("%s: job %d names an unknown tile handle", who, k); return VFSMS_ERR_BAD_ARG; }
+    *A = &ia->second; *B = &ib->second;
+    TRY(tile_ready(ctx, **A)); TRY(tile_ready(ctx, **B));
+    return VFSMS_OK;
+}
 // non-blocking: has the tile's image been handed over (or was it never a reserved tile)?  An unknown handle counts as ready: the
 // evaluator reports it.  (csrc/grid.hip sizes speculative batches by this while decoder threads are still filling tiles.)
 int tile_is_filled(vfsms_ctx *ctx, int64_t handle)
@@ -1112,12 +1121,11 @@ extern "C" int vfsms_ncc_search_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs,
     if (n == 0) return VFSMS_OK;
     std::vector<AdjJob> H(n);
     for (int k = 0; k < n; k++) {
-        auto ia = ctx->tiles.find(jobs[k].tile_a), ib = ctx->tiles.find(jobs[k].tile_b);
-        if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("ncc_search: job %d names an unknown tile handle", k); return VFSMS_ERR_BAD_ARG; }
-        TileRec &A = ia->second, &B = ib->second;
+        TileRec *pA, *pB;
+        TRY(resident_pair(ctx, "ncc_search", k, jobs[k], &pA, &pB));
+        const TileRec &A = *pA, &B = *pB;
         if (A.ch != 1 || B.ch != 1) { vfsms_set_error("ncc_search: job %d names a colour tile; the search takes single-channel tiles", k); return VFSMS_ERR_BAD_ARG; }
         if (A.h != B.h || A.w != B.w) { vfsms_set_error("ncc_search: the tiles of job %d are %d x %d and %d x %d", k, A.h, A.w, B.h, B.w); return VFSMS_ERR_BAD_ARG; }
-        TRY(tile_ready(ctx, A)); TRY(tile_ready(ctx, B));
         H[k].a = A.ptr; H[k].b = B.ptr; H[k].sa = A.stride; H[k].sb = B.stride; H[k].h = A.h; H[k].w = A.w; H[k].dx = jobs[k].dx; H[k].dy = jobs[k].dy;
     }
     const size_t CC = (size_t)(2 * radius + 1) * (2 * radius + 1);
@@ -1360,36 +1368,56 @@ static int match_run_readback(vfsms_ctx *ctx, const MatchRun &run, int32_t *rows
     return VFSMS_OK;
 }
 
-extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out)
+// ---- the phase batches: one driver over the runs of equal shapes ------------------------------------------------------------------------
+// Attempts of one ROI size (all of them, in practice) run as ONE batched transform; other sizes follow group by group.  ONE
+// ctx_arena_reserve: the results of all n jobs (result_bytes, *d_results, set before the first group runs) and behind them the scratch of
+// the largest group (bytes_of(h, w, nb, &bytes)), rewound for every group -- stream order makes the reuse safe.  run_group(pj, nb, h, w, g0)
+// enqueues the nb jobs of a group whose strips are pj; its results go to slots g0.. of the result block, which is in GROUP order: slot k
+// holds job order[k], and the caller un-permutes on the host behind its one synchronisation.
+template <typename BytesOf, typename RunGroup>
+static int phase_shape_groups(vfsms_ctx *ctx, const char *who, const vfsms_roi_pair *jobs, int n, size_t result_bytes, BytesOf bytes_of, RunGroup run_group,
+                              std::vector<int> *order, void **d_results)
 {
-    CTX_ENTER(ctx);
-    if (n < 0 || (n && (!jobs || !out))) { vfsms_set_error("attempt_phase: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    if (n == 0) return VFSMS_OK;
-    // attempts of one ROI size (all of them, in practice) run as ONE batched transform; other sizes follow group by group
-    const std::vector<int> order = shape_order(jobs, n);
-    auto shape_at = [&](int k) { return std::make_pair(jobs[order[k]].h, jobs[order[k]].w); };
+    *order = shape_order(jobs, n);
+    const std::vector<int> &ord = *order;
+    auto shape_at = [&](int k) { return std::make_pair(jobs[ord[k]].h, jobs[ord[k]].w); };
     size_t need = 0;
     for (int g0 = 0, g1; g0 < n; g0 = g1) {
         g1 = shape_run_end(g0, n, shape_at);
-        size_t pb = 0;
-        TRY(phase_bytes(ctx, jobs[order[g0]].h, jobs[order[g0]].w, g1 - g0, &pb));
-        need = std::max(need, pb);
+        size_t gb = 0;
+        TRY(bytes_of(jobs[ord[g0]].h, jobs[ord[g0]].w, g1 - g0, &gb));
+        need = std::max(need, gb);
     }
-    TRY(ctx_arena_reserve(ctx, need + sizeof(double) * 3 * n + 65536));
+    TRY(ctx_arena_reserve(ctx, need + result_bytes + 65536));
     ctx->pinned_off = 0;
-    double *d_out = (double *)ctx_arena_alloc(ctx, sizeof(double) * 3 * n);   // in group order; un-permuted on the host
+    *d_results = ctx_arena_alloc(ctx, result_bytes);
+    if (!*d_results) { vfsms_set_error("%s: arena exhausted", who); return VFSMS_ERR_CAPACITY; }
     const size_t mark = ctx->arena_off;
     std::vector<PhaseJobHost> pj(n);
     for (int g0 = 0, g1; g0 < n; g0 = g1) {
         g1 = shape_run_end(g0, n, shape_at);
         for (int k = g0; k < g1; k++) {
             const uint8_t *pa, *pb; int sa, sb;
-            TRY(resolve_job(ctx, jobs[order[k]], &pa, &sa, &pb, &sb));
+            TRY(resolve_job(ctx, jobs[ord[k]], &pa, &sa, &pb, &sb));
             pj[k].a = pa; pj[k].b = pb; pj[k].sa = sa; pj[k].sb = sb;
         }
-        ctx->arena_off = mark;                               // stream order makes scratch reuse safe
-        TRY(phase_correlate_batch_device(ctx, pj.data() + g0, g1 - g0, jobs[order[g0]].h, jobs[order[g0]].w, d_out + 3 * g0));
+        ctx->arena_off = mark;
+        TRY(run_group(pj.data() + g0, g1 - g0, jobs[ord[g0]].h, jobs[ord[g0]].w, g0));
     }
+    return VFSMS_OK;
+}
+
+extern "C" int vfsms_attempt_phase_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, double *out)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n && (!jobs || !out))) { vfsms_set_error("attempt_phase: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    std::vector<int> order;
+    double *d_out = nullptr;
+    TRY(phase_shape_groups(ctx, "attempt_phase", jobs, n, sizeof(double) * 3 * n,
+                           [&](int h, int w, int nb, size_t *bytes) { return phase_bytes(ctx, h, w, nb, bytes); },
+                           [&](const PhaseJobHost *pj, int nb, int h, int w, int g0) { return phase_correlate_batch_device(ctx, pj, nb, h, w, d_out + 3 * g0); },
+                           &order, (void **)&d_out));
     std::vector<double> tmp((size_t)3 * n);
     HIP_TRY(hipMemcpyAsync(tmp.data(), d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1407,34 +1435,16 @@ extern "C" int vfsms_attempt_phase_resolve_batch(vfsms_ctx *ctx, const vfsms_roi
     if (n == 0) return VFSMS_OK;
     const int K = peaks;
     const size_t RI = VFSMS_ATTEMPT_INTS, CI = 16 * (size_t)K, PI = 2 * (size_t)K;
-    const std::vector<int> order = shape_order(jobs, n);
-    auto shape_at = [&](int k) { return std::make_pair(jobs[order[k]].h, jobs[order[k]].w); };
-    size_t need = 0;
-    for (int g0 = 0, g1; g0 < n; g0 = g1) {
-        g1 = shape_run_end(g0, n, shape_at);
-        size_t pb = 0;
-        TRY(phase_resolve_bytes(ctx, jobs[order[g0]].h, jobs[order[g0]].w, g1 - g0, K, &pb));
-        need = std::max(need, pb);
-    }
-    TRY(ctx_arena_reserve(ctx, need + sizeof(int32_t) * (RI + CI + PI) * (size_t)n + 65536));
-    ctx->pinned_off = 0;
-    int32_t *d_rows = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * RI * n);      // in group order; un-permuted on the host
-    int32_t *d_cands = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * CI * n);
-    int32_t *d_pk = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * PI * n);
-    if (!d_rows || !d_cands || !d_pk) { vfsms_set_error("attempt_phase_resolve: arena exhausted"); return VFSMS_ERR_CAPACITY; }
-    const size_t mark = ctx->arena_off;
-    std::vector<PhaseJobHost> pj(n);
-    for (int g0 = 0, g1; g0 < n; g0 = g1) {
-        g1 = shape_run_end(g0, n, shape_at);
-        for (int k = g0; k < g1; k++) {
-            const uint8_t *pa, *pb; int sa, sb;
-            TRY(resolve_job(ctx, jobs[order[k]], &pa, &sa, &pb, &sb));
-            pj[k].a = pa; pj[k].b = pb; pj[k].sa = sa; pj[k].sb = sb;
-        }
-        ctx->arena_off = mark;                               // stream order makes scratch reuse safe
-        TRY(phase_resolve_group(ctx, pj.data() + g0, g1 - g0, jobs[order[g0]].h, jobs[order[g0]].w, K, threshold, min_pixels,
-                                d_rows + RI * g0, d_cands + CI * g0, d_pk + PI * g0));
-    }
+    // the result block on the device and its copy on the host: [n] rows, [n] candidate tables, [n] peak positions
+    std::vector<int> order;
+    int32_t *d_rows = nullptr;
+    TRY(phase_shape_groups(ctx, "attempt_phase_resolve", jobs, n, sizeof(int32_t) * (RI + CI + PI) * (size_t)n,
+                           [&](int h, int w, int nb, size_t *bytes) { return phase_resolve_bytes(ctx, h, w, nb, K, bytes); },
+                           [&](const PhaseJobHost *pj, int nb, int h, int w, int g0) {
+                               return phase_resolve_group(ctx, pj, nb, h, w, K, threshold, min_pixels, d_rows + RI * g0, d_rows + RI * n + CI * g0,
+                                                          d_rows + (RI + CI) * n + PI * g0); },
+                           &order, (void **)&d_rows));
+    const int32_t *d_cands = d_rows + RI * n, *d_pk = d_cands + CI * n;
     std::vector<int32_t> tmp((RI + CI + PI) * (size_t)n);
     int32_t *t_rows = tmp.data(), *t_cands = t_rows + RI * n, *t_pk = t_cands + CI * n;
     HIP_TRY(hipMemcpyAsync(t_rows, d_rows, sizeof(int32_t) * RI * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2314,11 +2324,10 @@ extern "C" int vfsms_overlap_stats_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jo
     if (n == 0) return VFSMS_OK;
     std::vector<ExpPairHost> H(n);
     for (int k = 0; k < n; k++) {
-        auto ia = ctx->tiles.find(jobs[k].tile_a), ib = ctx->tiles.find(jobs[k].tile_b);
-        if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("overlap_stats: job %d names an unknown tile handle", k); return VFSMS_ERR_BAD_ARG; }
-        TileRec &A = ia->second, &B = ib->second;
+        TileRec *pA, *pB;
+        TRY(resident_pair(ctx, "overlap_stats", k, jobs[k], &pA, &pB));
+        const TileRec &A = *pA, &B = *pB;
         if (A.ch != B.ch) { vfsms_set_error("overlap_stats: the tiles of job %d have %d and %d channels", k, A.ch, B.ch); return VFSMS_ERR_BAD_ARG; }
-        TRY(tile_ready(ctx, A)); TRY(tile_ready(ctx, B));
         H[k] = ExpPairHost{A.ptr, B.ptr, A.stride, B.stride, A.h, A.w * A.ch, B.h, B.w * B.ch, A.ch, jobs[k].dx, jobs[k].dy};
     }
     const size_t out_bytes = sizeof(unsigned long long) * 3 * (size_t)n;

@@ -18,14 +18,15 @@
 // (row, chunk) items of the group, a chunk being 16 bytes of a B row cut at B's 16-byte ADDRESS boundaries -- so a row's first and last
 // chunk are ragged, and a 16-bit column mask zeroes what lies outside the rectangle: nothing is restricted to an aligned core.  A chunk
 // that lies inside the row is one aligned uint4 load, a ragged one the aligned dwords that hold a byte of the row.  The 16 partner bytes
-// of A come from the five aligned dwords around them, those that hold a byte of A's row, funnel-shifted (alignbyte) by their alignment,
-// as in adjust_kernels.hip: no load touches a dword without a byte of a row, so none leaves the page of a valid byte.  The band is a
+// of A come from the five aligned dwords around them, those that hold a byte of A's row, funnel-shifted (alignbyte) by their alignment
+// (load_partner of overlap_sums.h, which also holds the masks and the workgroup reduction).  The band is a
 // byte mask computed four bytes at a time (exp_band) on both operands; N is the population count of the combined mask / 8.
 //
 // 32-bit lane sums.  A lane sees at most EXP_LANE_CAP chunks of 16 bytes: its sums are at most 65536 * 16 * 255 = 267 386 880 and its
 // mask bits 65536 * 128 = 8 388 608, both < 2^32.  overlap_stats_device sizes the grid for about EXP_LANE_ITEMS chunks per lane and refuses
 // a job that would exceed the cap.  64 bits from the wave reduction on; one 64-bit vector atomic add per workgroup and sum.
 #include "common.h"
+#include "overlap_sums.h"
 #include <algorithm>
 
 #define EXP_THREADS 256
@@ -45,14 +46,6 @@ __host__ __device__ __forceinline__ int exp_rows_per_group(int nrows, int cpr, i
 // chunks of any row of a rectangle whose byte columns are [c0, c1), at most: the first chunk may start up to 15 bytes before c0
 __host__ __device__ __forceinline__ int exp_chunks_per_row(int c0, int c1) { return ((c1 - c0 + 15) >> 4) + 1; }
 
-// bit b of a nibble -> byte b of a dword (0xff / 0x00)
-__device__ __forceinline__ uint32_t exp_byte_mask(uint32_t nib) { return ((nib * 0x00204081u) & 0x01010101u) * 0xffu; }
-// the bits p of [0, 16) whose column x0 + p lies in [c0, c1)
-__device__ __forceinline__ uint32_t exp_range_bits(int x0, int c0, int c1)
-{
-    const int lo = min(max(c0 - x0, 0), 16), hi = min(max(c1 - x0, 0), 16);
-    return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
-}
 // 0xff in every byte x of v with lo <= x <= hi.  Two bytes at a time in 16-bit fields: bit 8 of x + (256 - lo) is set iff x >= lo, bit 8
 // of (256 + hi) - x iff x <= hi (both stay below 512, so no field reaches its neighbour); klo = (256 - lo) * 0x00010001, khi = (256 + hi) * 0x00010001
 __device__ __forceinline__ uint32_t exp_band(uint32_t v, uint32_t klo, uint32_t khi)
@@ -81,7 +74,7 @@ __global__ __launch_bounds__(EXP_THREADS) void k_overlap_stats(const ExpJob *job
         const uintptr_t pb = (uintptr_t)(J.b + (size_t)r * J.sb);
         const int c = J.c0 - (int)((pb + (uintptr_t)J.c0) & 15u) + (k << 4);      // the chunk's first column: pb + c is 16-byte aligned
         if (c >= J.c1) continue;
-        const uint32_t m16 = exp_range_bits(c, J.c0, J.c1);
+        const uint32_t m16 = range_bits(c, J.c0, J.c1, 16);
         // B: the chunk's four dwords, those that hold a byte of the row
         uint32_t b[4];
         const uintptr_t qb = pb + (uintptr_t)(intptr_t)c;
@@ -96,38 +89,20 @@ __global__ __launch_bounds__(EXP_THREADS) void k_overlap_stats(const ExpJob *job
         // A: the 16 partner bytes from the aligned dwords around them, those that hold a byte of A's row
         const int ca = c + J.dyb;
         const uintptr_t pa = (uintptr_t)(J.a + (size_t)(r + J.dx) * J.sa) + (uintptr_t)(intptr_t)ca;
-        const unsigned m = (unsigned)(pa & 3u);
-        const uint32_t *a4 = reinterpret_cast<const uint32_t *>(pa - m);
-        const int cq = ca - (int)m;
-        uint32_t d[5];
-#pragma unroll
-        for (int q = 0; q < 5; q++) d[q] = (cq + 4 * q + 3 >= 0 && cq + 4 * q < J.wa) ? a4[q] : 0u;
+        uint32_t e[4];
+        load_partner<4>(pa, ca, J.wa, e);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            const uint32_t a = __builtin_amdgcn_alignbyte(d[t + 1], d[t], m);
-            const uint32_t keep = exp_byte_mask((m16 >> (4 * t)) & 15u) & exp_band(a, klo, khi) & exp_band(b[t], klo, khi);
+            const uint32_t a = e[t];
+            const uint32_t keep = byte_mask((m16 >> (4 * t)) & 15u) & exp_band(a, klo, khi) & exp_band(b[t], klo, khi);
             bits += __popc(keep);
             sa = __builtin_amdgcn_sad_u8(a & keep, 0u, sa);
             sb = __builtin_amdgcn_sad_u8(b[t] & keep, 0u, sb);
         }
     }
 
-    __shared__ unsigned long long part[EXP_THREADS / 64][3];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const unsigned long long v3[3] = {bits >> 3, sa, sb};
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        unsigned long long v = v3[q];
-        for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-        if (lane == 0) part[wid][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long v = 0ull;
-#pragma unroll
-        for (int q = 0; q < EXP_THREADS / 64; q++) v += part[q][threadIdx.x];
-        if (v) atomicAdd(out3 + 3 * (size_t)blockIdx.y + threadIdx.x, v);
-    }
+    wg_add_u64<3, EXP_THREADS / 64>(v3, out3 + 3 * (size_t)blockIdx.y);
 }
 
 // ---- apply -------------------------------------------------------------------------------------------------------------------------------------

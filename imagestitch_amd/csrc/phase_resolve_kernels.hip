@@ -10,11 +10,11 @@
 //   k_phase_peaks_merge  (one wave per job)    -> the job's K peaks {value, row-major index in the ORIGINAL orientation} (a tail kernel: no
 //                                                 hand-off between workgroups inside a launch)
 //   k_phase_cand_sums    (row blocks x 4 K x jobs) -> Sa, Sb, Saa, Sbb, Sab of every kept reading over the RAW u8 strips; the row body is
-//                                                 k_verify_ncc's, restated here so that verify_kernels.hip compiles to what it did
+//                                                 k_verify_ncc's (overlap_rows_sums of overlap_sums.h)
 //   k_phase_cand_pick    (one lane per job)    -> scores, the winner, the attempt row, the candidate table, the peak positions
 // All on the context's stream, no host synchronisation; scratch from the arena; profiler stage "phase_resolve".
 #include "common.h"
-#include "verify_math.h"
+#include "overlap_sums.h"
 #include "phase_resolve_math.h"
 #include <algorithm>
 
@@ -147,21 +147,9 @@ int launch_phase_peaks(vfsms_ctx *ctx, const double *RE, int njobs, int SM, int 
 int phase_peaks_blocks(int SM) { return (SM + PEAK_ROWS - 1) / PEAK_ROWS; }
 
 // ---- the candidates' sums ------------------------------------------------------------------------------------------------------------
-struct Sums { uint32_t a, b, aa, bb, ab; };
-__device__ __forceinline__ void acc4(uint32_t a, uint32_t b, Sums &s)
-{
-    s.a = __builtin_amdgcn_sad_u8(a, 0u, s.a);
-    s.b = __builtin_amdgcn_sad_u8(b, 0u, s.b);
-    s.aa = __builtin_amdgcn_udot4(a, a, s.aa, false);
-    s.bb = __builtin_amdgcn_udot4(b, b, s.bb, false);
-    s.ab = __builtin_amdgcn_udot4(a, b, s.ab, false);
-}
-
 #define CAND_WG 32           // row blocks per candidate at most: 128 waves, a wave per overlap row
 
-// grid (row blocks, 4 K candidates, jobs).  A wave per overlap row; strip B's row is cut at its 16-byte boundaries: the body is read as aligned
-// uint4, the partner bytes of strip A as the five aligned dwords around them, funnel-shifted into place; heads and tails (< 16 bytes each)
-// are single bytes on the first lanes (k_verify_ncc's row body).  sums: [job][4 K][5] uint64, zeroed by the launcher.
+// grid (row blocks, 4 K candidates, jobs).  A wave per overlap row (overlap_rows_sums).  sums: [job][4 K][5] uint64, zeroed by the launcher.
 __global__ __launch_bounds__(256) void k_phase_cand_sums(const PhaseJobHost *__restrict__ jobs, const PhasePeak *__restrict__ peaks, int K, int oM, int oN,
                                                           int h, int w, unsigned long long *__restrict__ sums)
 {
@@ -173,43 +161,7 @@ __global__ __launch_bounds__(256) void k_phase_cand_sums(const PhaseJobHost *__r
     const Overlap o = verify_overlap(h, w, dx, dy);
     if (o.r1 <= o.r0 || o.c1 <= o.c0) return;
     const PhaseJobHost J = jobs[job];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int L = o.c1 - o.c0;
-    unsigned long long t[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    for (int r = o.r0 + (int)blockIdx.x * 4 + wid; r < o.r1; r += (int)gridDim.x * 4) {
-        const uint8_t *pb = J.b + (size_t)r * J.sb + o.c0;
-        const uint8_t *pa = J.a + (size_t)(r + dx) * J.sa + (o.c0 + dy);
-        const int head = min(L, (int)((16u - (unsigned)((uintptr_t)pb & 15u)) & 15u));
-        const int nb = (L - head) >> 4, tail = L - head - (nb << 4);
-        Sums s = {0u, 0u, 0u, 0u, 0u};
-        const unsigned m = (unsigned)((uintptr_t)(pa + head) & 3u);          // the same for every chunk of the row
-        for (int k = lane; k < nb; k += 64) {
-            const uint4 b = *reinterpret_cast<const uint4 *>(pb + head + 16 * (size_t)k);
-            const uint32_t *a4 = reinterpret_cast<const uint32_t *>(pa + head + 16 * (size_t)k - m);
-            const uint32_t d0 = a4[0], d1 = a4[1], d2 = a4[2], d3 = a4[3], d4 = m ? a4[4] : 0u;   // a4[4] holds bytes of the chunk when m != 0
-            acc4(__builtin_amdgcn_alignbyte(d1, d0, m), b.x, s);
-            acc4(__builtin_amdgcn_alignbyte(d2, d1, m), b.y, s);
-            acc4(__builtin_amdgcn_alignbyte(d3, d2, m), b.z, s);
-            acc4(__builtin_amdgcn_alignbyte(d4, d3, m), b.w, s);
-        }
-        int e = -1;                                       // head byte `lane`, tail byte `lane - 32`
-        if (lane < head) e = lane;
-        else if (lane >= 32 && lane - 32 < tail) e = head + (nb << 4) + lane - 32;
-        if (e >= 0) acc4((uint32_t)pa[e], (uint32_t)pb[e], s);
-        t[0] += s.a; t[1] += s.b; t[2] += s.aa; t[3] += s.bb; t[4] += s.ab;
-    }
-    __shared__ unsigned long long part[4][5];
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        unsigned long long v = t[q];
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-        if (lane == 0) part[wid][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (v) atomicAdd(sums + ((size_t)job * 4 * K + cand) * 5 + threadIdx.x, v);
-    }
+    overlap_rows_sums(J.a, J.sa, J.b, J.sb, o, dx, dy, sums + ((size_t)job * 4 * K + cand) * 5);
 }
 
 // rows: [job][VFSMS_ATTEMPT_INTS]; cands: [job][4 K][4] = {dx, dy, fixed score, shared pixels}; peaks_out: [job][K][2] = {uy, ux}
@@ -232,10 +184,8 @@ __global__ __launch_bounds__(64) void k_phase_cand_pick(const PhasePeak *__restr
         }
         o[0] = C.dx; o[1] = C.dy; o[2] = 0; o[3] = 0;
         if (!C.kept) continue;
-        const Overlap ov = verify_overlap(h, w, C.dx, C.dy);
-        const long long N = (long long)max(0, ov.r1 - ov.r0) * (long long)max(0, ov.c1 - ov.c0);
-        const unsigned long long *s = sums + ((size_t)j * 4 * K + c) * 5;
-        const double score = verify_score(N, (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3], (long long)s[4], min_pixels);
+        long long N;
+        const double score = overlap_score(h, w, C.dx, C.dy, sums + ((size_t)j * 4 * K + c) * 5, min_pixels, &N);
         const int fx = verify_fixed(score);
         o[2] = fx; o[3] = (int32_t)N;
         if (best < 0 || score > bscore) { best = c; bscore = score; bdx = C.dx; bdy = C.dy; bfx = fx; }
