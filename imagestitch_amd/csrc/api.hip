@@ -922,6 +922,13 @@ static int pick_filter_nsplit(int nq, int njobs, int nt = 0)
     return std::max(1, std::min(ns, 8));
 }
 
+// Hamming search: a wave owns 64 queries and walks its share of the trains: split the trains so that a batch fills the chip a few times over
+static int pick_hamming_nsplit(int capq, int njobs)
+{
+    const long long waves = (long long)((capq + 63) / 64) * njobs;
+    return (int)std::max<long long>(1, std::min<long long>(8, (8192 + waves - 1) / waves));
+}
+
 static bool bf_force_exact()
 {
     static const bool v = getenv("VFSMS_BF_EXACT") && atoi(getenv("VFSMS_BF_EXACT")) != 0;
@@ -1019,15 +1026,24 @@ extern "C" int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, con
     if (!m_out || nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) { vfsms_set_error("bf_hamming: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     *m_out = 0;
     if (nq == 0 || nt == 0) return VFSMS_OK;
-    TRY(ctx_arena_reserve(ctx, ((size_t)nq + nt) * nbytes + sizeof(int) * 2 * (size_t)nq + 65536));
+    if (nbytes != 32) { vfsms_set_error("bf_hamming: only 32-byte descriptors supported"); return VFSMS_ERR_UNSUPPORTED; }
+    // one job of the batched matcher without keypoints, hence without votes: the merged 1-NN comes back and the pair list is built here
+    const int ns = pick_hamming_nsplit(nq, 1);
+    TRY(ctx_arena_reserve(ctx, ((size_t)nq + nt) * 32 + match_bytes(nq, ns) + 65536));
     uint8_t *dq, *dt;
-    TRY(upload_array(ctx, q, (size_t)nq * nbytes, &dq));
-    TRY(upload_array(ctx, t, (size_t)nt * nbytes, &dt));
-    int *bi = (int *)ctx_arena_alloc(ctx, sizeof(int) * nq), *bd = (int *)ctx_arena_alloc(ctx, sizeof(int) * nq);
-    TRY(launch_bf_hamming(ctx, dq, nq, dt, nt, nbytes, bi, bd));
-    std::vector<int> hi(nq), hd(nq);
-    HIP_TRY(hipMemcpyAsync(hi.data(), bi, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hd.data(), bd, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(upload_array(ctx, q, (size_t)nq * 32, &dq));
+    TRY(upload_array(ctx, t, (size_t)nt * 32, &dt));
+    int cnt[2] = {nq, nt}; int *dcnt;
+    ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
+    TRY(ctx_upload_small(ctx, cnt, sizeof(cnt), (void **)&dcnt));
+    MatchDev M, *dM; memset(&M, 0, sizeof(M));
+    TRY(match_carve(ctx, &M, nq, 32, ns));
+    M.q = (const float *)dq; M.t = (const float *)dt; M.nq_ptr = dcnt; M.nt_ptr = dcnt + 1;
+    TRY(upload_array(ctx, &M, 1, &dM));
+    TRY(launch_bf_hamming(ctx, dM, 1, nq, ns, max_dist));
+    std::vector<int> hi(nq); std::vector<float> hd(nq);
+    HIP_TRY(hipMemcpyAsync(hi.data(), M.i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hd.data(), M.d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int m = 0;
     for (int i = 0; i < nq; i++) {
@@ -1283,7 +1299,7 @@ static int build_strip_table(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, const i
 }
 
 // ---- jobs of one ROI shape next to each other ------------------------------------------------------------------------------------
-// The kernels whose grid follows the image size are launched per run of equal shapes (surf_kernels.hip: shape_runs), and a batched
+// The kernels whose grid follows the image size are launched per run of equal shapes (common.h: shape_runs), and a batched
 // transform takes one shape: every batch puts its jobs in the stable (h, w) order.  Slot s holds job ord[s]; results go to the job's row.
 static std::vector<int> shape_order(const vfsms_roi_pair *jobs, int n)
 {
@@ -1315,7 +1331,9 @@ struct MatchJob {
     const StripTable::Strip *sa, *sb;                // optional: the raw pixels of the two strips, for the verifier behind the vote
 };
 struct MatchRun { MatchPlan P; int dim; std::vector<MatchDev> M; MatchDev *dM = nullptr; int32_t *rblock = nullptr; };
-enum MatchSearch { SEARCH_FLOAT, SEARCH_I8_D128 };   // k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows
+// k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows / k_bf_hamming_jobs on 32-byte rows behind q, t
+enum MatchSearch { SEARCH_FLOAT, SEARCH_I8_D128, SEARCH_HAMMING };
+struct MatchTail { double ratio; int max_dist; int offset_evaluate; };   // the ratio test (L2) or the distance bound (Hamming), the vote's threshold
 // 64-d descriptors leave the descriptor kernel with norm <= 1: their 2-NN search runs as an MFMA candidate filter plus exact verification
 // (match_kernels.hip); other widths, or VFSMS_BF_EXACT=1, take the exhaustive VALU kernel.  The split counts follow the set sizes the
 // CALLER expects, (fq, ft) for the filter and (eq, et) for the exhaustive kernel: the true counts of feature sets, the typical occupancy
@@ -1352,15 +1370,18 @@ static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int
     }
     return ctx_upload_small(ctx, run->M.data(), sizeof(MatchDev) * n, (void **)&run->dM);
 }
-// search + ratio test + vote of jobs [first, first + count); maxq / maxt: the largest query / train set the launch has to cover
-static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search,
-                            double ratio, int offset_evaluate)
+// search + ratio test (Hamming: distance bound) + vote of jobs [first, first + count); maxq / maxt: the largest query / train set to cover
+static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search, const MatchTail &tail)
 {
     const MatchDev *dM = run.dM + first;
+    if (search == SEARCH_HAMMING) {
+        TRY(launch_bf_hamming(ctx, dM, count, maxq, run.P.ns, tail.max_dist));
+        return launch_scan_mode(ctx, dM, count, maxq, tail.offset_evaluate);
+    }
     if (search == SEARCH_I8_D128) { TRY(launch_bf_i8_d128(ctx, dM, count, maxq, run.P.ns)); }
     else if (run.P.filtered) { TRY(launch_bf_l2_filtered(ctx, dM, count, maxq, maxt, run.P.cns)); }
     else { TRY(launch_bf_l2(ctx, dM, count, maxq, run.P.ns, run.dim)); }
-    return launch_ratio_mode(ctx, dM, count, maxq, ratio, offset_evaluate);
+    return launch_ratio_mode(ctx, dM, count, maxq, tail.ratio, tail.offset_evaluate);
 }
 static int match_run_readback(vfsms_ctx *ctx, const MatchRun &run, int32_t *rows)
 {
@@ -1524,6 +1545,7 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         J[s_].sa = &T.strips[T.a[s_]]; J[s_].sb = &T.strips[T.b[s_]];       // the tile's pixels, not the enhanced copy
     }
     const SurfEnh enh{enh_mode, clip_limit, tile_grid};
+    const MatchTail tail{ratio, -1, offset_evaluate};
     TRY(ctx_arena_reserve(ctx, surf_run_bytes(ctx, S.data(), u, params, enh) + match_run_bytes(J.data(), n, P) + 65536));
     ctx->pinned_off = 0;
     SurfRun surf; MatchRun match;
@@ -1544,15 +1566,15 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         join_guard.armed = true;
         {
             StreamSwap on_second(ctx, ctx->stream2);              // the launchers enqueue on ctx->stream (their profiling events too)
-            TRY(match_run_launch(ctx, match, 0, n0, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
+            TRY(match_run_launch(ctx, match, 0, n0, maxcap, maxcap, SEARCH_FLOAT, tail));
             HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
         }
         TRY(surf_run_launch(ctx, surf, u0, u - u0, true, params));
-        TRY(match_run_launch(ctx, match, n0, n - n0, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
+        TRY(match_run_launch(ctx, match, n0, n - n0, maxcap, maxcap, SEARCH_FLOAT, tail));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         join_guard.armed = false;                        // joined in stream order: the synchronisation below covers both streams
     } else {
-        TRY(match_run_launch(ctx, match, 0, n, maxcap, maxcap, SEARCH_FLOAT, ratio, offset_evaluate));
+        TRY(match_run_launch(ctx, match, 0, n, maxcap, maxcap, SEARCH_FLOAT, tail));
     }
     // counters of all strips and results of all jobs live in two contiguous blocks: one memset, two D2H copies, one synchronisation per batch
     TRY(surf_run_readback(ctx, &surf));
@@ -1763,7 +1785,7 @@ static int features_match_impl(vfsms_ctx *ctx, const char *who, const int64_t *f
     for (int j = 0; j < m; j++) { J[j].nq_ptr = dcnt + 2 * j; J[j].nt_ptr = dcnt + 2 * j + 1; }
     MatchRun run;
     TRY(match_run_carve(ctx, &run, J.data(), m, dim, P));
-    TRY(match_run_launch(ctx, run, 0, m, maxq, maxt, SEARCH_FLOAT, ratio, offset_evaluate));
+    TRY(match_run_launch(ctx, run, 0, m, maxq, maxt, SEARCH_FLOAT, MatchTail{ratio, -1, offset_evaluate}));
     std::vector<int32_t> res((size_t)VFSMS_ATTEMPT_INTS * m);
     TRY(match_run_readback(ctx, run, res.data()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2383,6 +2405,64 @@ static void orb_grow_caps(const int *counters, int nlevels, int *cap1, int *cap2
     *cap1 = std::max(*cap1, m); *cap2 = std::max(*cap2, m); *cap = (int)std::max<long long>(*cap, sum);
 }
 
+// ---- one ORB run: n sources detected and described in fused launches ----------------------------------------------------------------------
+// The phases of a SURF run: orb_run_bytes into the caller's ONE ctx_arena_reserve, orb_run_carve (wires and uploads the records), orb_run_launch,
+// then orb_run_retry's orb_run_readback, synchronisation and orb_run_overflow.  A source is a strip of a batch's table or a whole image.
+struct OrbRun {
+    std::vector<OrbDev> R; OrbDev *dR = nullptr;                  // host and device copies of the ROI records
+    int *cblock = nullptr;                                        // 64 ints per source, one contiguous block: counters, thr1, n1, n2 at +0, +16, +32, +48
+    std::vector<int> counters;
+};
+static size_t orb_run_bytes(const vfsms_orb_params *p, const StripTable::Strip *S, int n, int cap1, int cap2, int cap)
+{
+    size_t need = 0;
+    for (int i = 0; i < n; i++) need += orb_roi_bytes(p, S[i].h, S[i].w, cap1, cap2, cap);
+    return need + (sizeof(OrbDev) + sizeof(int) * 64) * (size_t)n + 1024;     // the records, the counters, their alignment
+}
+static int orb_run_carve(vfsms_ctx *ctx, OrbRun *run, const StripTable::Strip *S, int n, const vfsms_orb_params *p, int cap1, int cap2, int cap)
+{
+    run->R.resize(n);
+    run->cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * n);
+    if (!run->cblock) { vfsms_set_error("arena exhausted (ORB counters)"); return VFSMS_ERR_CAPACITY; }
+    for (int i = 0; i < n; i++) {
+        OrbDev &r = run->R[i];
+        TRY(orb_roi_carve(ctx, &r, S[i].p, S[i].stride, S[i].h, S[i].w, p, cap1, cap2, cap));
+        r.counters = run->cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
+    }
+    return ctx_upload_small(ctx, run->R.data(), sizeof(OrbDev) * n, (void **)&run->dR);
+}
+// no prepare phase: k_orb_clear zeroes the counters
+static int orb_run_launch(vfsms_ctx *ctx, const OrbRun &run, const vfsms_orb_params *p) { return launch_orb(ctx, run.dR, run.R.data(), (int)run.R.size(), p); }
+static int orb_run_readback(vfsms_ctx *ctx, OrbRun *run)
+{
+    run->counters.resize(64 * run->R.size());
+    HIP_TRY(hipMemcpyAsync(run->counters.data(), run->cblock, sizeof(int) * run->counters.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return VFSMS_OK;
+}
+// after the synchronisation: the last source whose keypoints exceeded a capacity, or -1; the capacities grow to hold every such source
+static int orb_run_overflow(const OrbRun &run, int nlevels, int *cap1, int *cap2, int *cap)
+{
+    int over = -1;
+    for (size_t i = 0; i < run.R.size(); i++)
+        if (run.counters[64 * i + 2]) { over = (int)i; orb_grow_caps(&run.counters[64 * i], nlevels, cap1, cap2, cap); }
+    return over;
+}
+// Ties can overflow the default capacities: the run happens once more with capacities that hold every keypoint, never a truncation.
+// enqueue(cap1, cap2, cap) reserves, carves and launches `run` (and what reads it); *over: what orb_run_overflow says of the last run
+template <typename Enqueue>
+static int orb_run_retry(vfsms_ctx *ctx, const vfsms_orb_params *p, OrbRun *run, int *over, Enqueue enqueue)
+{
+    int c1, c2, c;
+    orb_caps(p, &c1, &c2, &c);
+    for (int pass = 0;; pass++) {
+        TRY(enqueue(c1, c2, c));
+        TRY(orb_run_readback(ctx, run));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *over = orb_run_overflow(*run, p->n_levels, &c1, &c2, &c);
+        if (*over < 0 || pass > 0) return VFSMS_OK;
+    }
+}
+
 extern "C" int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int stride,
                                          const vfsms_orb_params *params, float *kps_xy, uint8_t *desc,
                                          vfsms_keypoint *kps_full, int cap, int *n_out)
@@ -2390,25 +2470,20 @@ extern "C" int vfsms_orb_detect_describe(vfsms_ctx *ctx, const uint8_t *img, int
     CTX_ENTER(ctx);
     if (!img || !params || !n_out || h <= 0 || w <= 0 || stride < w || cap < 0) { vfsms_set_error("orb: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     TRY(ctx_prepare_orb(ctx, params));
-    int c1, c2, c;
-    orb_caps(params, &c1, &c2, &c);
-    OrbDev R;
-    int counters[16];
-    for (int pass = 0;; pass++) {          // ties can overflow the default capacities: one more run with exact ones, never a truncation
-        TRY(ctx_arena_reserve(ctx, (size_t)h * w + orb_roi_bytes(params, h, w, c1, c2, c) + 65536));
+    OrbRun run; int over;
+    TRY(orb_run_retry(ctx, params, &run, &over, [&](int c1, int c2, int c) -> int {
+        StripTable::Strip src{nullptr, w, h, w};
+        TRY(ctx_arena_reserve(ctx, (size_t)h * w + orb_run_bytes(params, &src, 1, c1, c2, c) + 65536));
+        ctx->pinned_off = 0;                                // entry points are synchronous: the staging buffer is free again
         uint8_t *d_img;
         TRY(upload_image(ctx, img, h, w, stride, &d_img));
-        TRY(orb_roi_carve(ctx, &R, d_img, w, h, w, params, c1, c2, c));
-        OrbDev *dR;
-        TRY(upload_array(ctx, &R, 1, &dR));
-        TRY(launch_orb(ctx, dR, &R, 1, params));
-        HIP_TRY(hipMemcpyAsync(counters, R.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (!counters[2]) break;
-        if (pass > 0) { vfsms_set_error("orb: internal keypoint capacity exceeded"); return VFSMS_ERR_CAPACITY; }
-        orb_grow_caps(counters, params->n_levels, &c1, &c2, &c);
-    }
-    const int n = counters[1];
+        src.p = d_img;
+        TRY(orb_run_carve(ctx, &run, &src, 1, params, c1, c2, c));
+        return orb_run_launch(ctx, run, params);
+    }));
+    if (over >= 0) { vfsms_set_error("orb: internal keypoint capacity exceeded"); return VFSMS_ERR_CAPACITY; }
+    const OrbDev &R = run.R[0];
+    const int n = run.counters[1];
     *n_out = n;
     if (n > cap) { vfsms_set_error("orb: %d keypoints exceed the caller's capacity %d", n, cap); return VFSMS_ERR_CAPACITY; }
     if (n > 0) {
@@ -2469,10 +2544,8 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     std::vector<SiftStripOut> S(u);
     const bool exact = bf_force_exact();
     // detect + describe (+ pack): the strips are in shape order already
-    auto strip_shape = [&](int i) { return std::make_pair(T.strips[i].h, T.strips[i].w); };
-    for (int i0 = 0, i1; i0 < u; i0 = i1) {
-        const int h = T.strips[i0].h, w = T.strips[i0].w;
-        i1 = shape_run_end(i0, u, strip_shape);
+    for (const ShapeRun &q : shape_runs(T.strips.data(), u)) {
+        const int h = q.h, w = q.w, i0 = q.first, i1 = q.first + q.count;
         int gmax = 1;
         TRY(sift_group_strips(ctx, h, w, params, &gmax));
         for (int a = i0; a < i1; a += gmax) {
@@ -2522,7 +2595,7 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     ctx->pinned_off = 0;
     MatchRun run;
     TRY(match_run_carve(ctx, &run, J.data(), n, 128, P));
-    TRY(match_run_launch(ctx, run, 0, n, maxcap, maxt, exact ? SEARCH_FLOAT : SEARCH_I8_D128, ratio, offset_evaluate));
+    TRY(match_run_launch(ctx, run, 0, n, maxcap, maxt, exact ? SEARCH_FLOAT : SEARCH_I8_D128, MatchTail{ratio, -1, offset_evaluate}));
     TRY(match_run_readback(ctx, run, out));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
@@ -2535,61 +2608,34 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
     if (n < 0 || (n && (!jobs || !out)) || !params) { vfsms_set_error("attempt_orb: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     if (n == 0) return VFSMS_OK;
     TRY(ctx_prepare_orb(ctx, params));
-    int c1, c2, c;
-    orb_caps(params, &c1, &c2, &c);
     // ROIs of one shape next to each other: the image-sized kernels are launched per shape run (launch_orb); slot s holds job ord[s];
     // every distinct strip of the batch is carved and run once (build_strip_table)
     const std::vector<int> ord = shape_order(jobs, n);
     StripTable T;
     TRY(build_strip_table(ctx, jobs, ord.data(), n, n, &T));
     const int u = (int)T.strips.size();
-    // ties can overflow the default capacities: the batch runs once more with capacities that hold every strip's keypoints
-    for (int pass = 0;; pass++) {
-        // a wave owns 64 queries and walks its share of the trains: split the trains so that a batch fills the chip a few times over
-        const long long hwaves = (long long)((c + 63) / 64) * n;
-        const int hns = (int)std::max<long long>(1, std::min<long long>(8, (8192 + hwaves - 1) / hwaves));
-        size_t need = 0;
-        for (int i = 0; i < u; i++) need += orb_roi_bytes(params, T.strips[i].h, T.strips[i].w, c1, c2, c);
-        need += match_bytes(c, hns) * n;
-        need += sizeof(OrbDev) * u + sizeof(MatchDev) * n + (64 * u + VFSMS_ATTEMPT_INTS * n) * sizeof(int) + 65536;
-        TRY(ctx_arena_reserve(ctx, need));
-        std::vector<OrbDev> R(u);
-        std::vector<MatchDev> M(n);
-        // counters of all strips and results of all jobs live in two contiguous blocks: two D2H copies per batch
-        int *cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * u);
-        int32_t *rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);
-        for (int i = 0; i < u; i++) {
-            const StripTable::Strip &S = T.strips[i];
-            TRY(orb_roi_carve(ctx, &R[i], S.p, S.stride, S.h, S.w, params, c1, c2, c));
-            OrbDev &r = R[i];
-            r.counters = cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
-        }
+    OrbRun orb; int over;
+    TRY(orb_run_retry(ctx, params, &orb, &over, [&](int c1, int c2, int c) -> int {
+        std::vector<MatchJob> J(n, MatchJob{});
         for (int s_ = 0; s_ < n; s_++) {
-            const int k = ord[s_];
-            const OrbDev &A = R[T.a[s_]], &B = R[T.b[s_]];
-            memset(&M[s_], 0, sizeof(MatchDev));
-            TRY(match_carve(ctx, &M[s_], c, 32, hns));
-            M[s_].result = rblock + VFSMS_ATTEMPT_INTS * k;
-            M[s_].q = (const float *)A.desc; M[s_].t = (const float *)B.desc;
-            M[s_].nq_ptr = A.counters + 1; M[s_].nt_ptr = B.counters + 1;
-            M[s_].kq = A.kps_xy; M[s_].kt = B.kps_xy;
-            match_set_strips(&M[s_], T.strips[T.a[s_]], T.strips[T.b[s_]]);
+            J[s_].capq = J[s_].capt = c; J[s_].row = ord[s_];
+            J[s_].sa = &T.strips[T.a[s_]]; J[s_].sb = &T.strips[T.b[s_]];
         }
+        const MatchPlan P{false, pick_hamming_nsplit(c, n), 0};
+        TRY(ctx_arena_reserve(ctx, orb_run_bytes(params, T.strips.data(), u, c1, c2, c) + match_run_bytes(J.data(), n, P) + 65536));
         ctx->pinned_off = 0;
-        OrbDev *dR; MatchDev *dM;
-        TRY(ctx_upload_small(ctx, R.data(), sizeof(OrbDev) * u, (void **)&dR));
-        TRY(ctx_upload_small(ctx, M.data(), sizeof(MatchDev) * n, (void **)&dM));
-        TRY(launch_orb(ctx, dR, R.data(), u, params));
-        TRY(launch_hamming_mode(ctx, dM, n, c, hns, max_dist, offset_evaluate));
-        std::vector<int> counters((size_t)64 * u);
-        HIP_TRY(hipMemcpyAsync(counters.data(), cblock, sizeof(int) * 64 * u, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out, rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        int over = -1;
-        for (int i = 0; i < u; i++)
-            if (counters[(size_t)64 * i + 2]) { over = i; if (pass == 0) orb_grow_caps(&counters[(size_t)64 * i], params->n_levels, &c1, &c2, &c); }
-        if (over < 0) break;
-        if (pass > 0) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", over, u); return VFSMS_ERR_CAPACITY; }
-    }
+        MatchRun match;
+        TRY(orb_run_carve(ctx, &orb, T.strips.data(), u, params, c1, c2, c));
+        for (int s_ = 0; s_ < n; s_++) {
+            const OrbDev &A = orb.R[T.a[s_]], &B = orb.R[T.b[s_]];
+            J[s_].q = (const float *)A.desc; J[s_].t = (const float *)B.desc; J[s_].kq = A.kps_xy; J[s_].kt = B.kps_xy;
+            J[s_].nq_ptr = A.counters + 1; J[s_].nt_ptr = B.counters + 1;
+        }
+        TRY(match_run_carve(ctx, &match, J.data(), n, 32, P));
+        TRY(orb_run_launch(ctx, orb, params));
+        TRY(match_run_launch(ctx, match, 0, n, c, c, SEARCH_HAMMING, MatchTail{0.0, max_dist, offset_evaluate}));
+        return match_run_readback(ctx, match, out);       // results of all jobs, counters of all strips: two contiguous blocks, two D2H copies per run
+    }));
+    if (over >= 0) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", over, u); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
 }

@@ -252,6 +252,23 @@ int ctx_arena_reserve(vfsms_ctx *ctx, size_t bytes);             // ensure capac
 void *ctx_arena_alloc(vfsms_ctx *ctx, size_t bytes, size_t align = 256);
 int ctx_prepare_surf(vfsms_ctx *ctx, const vfsms_surf_params *p);
 
+// ---- runs of consecutive records of one shape -----------------------------------------------------------------
+// Kernels whose grid is cut from the image size are launched once per RUN of consecutive ROIs of one shape: a batch of the incremental search
+// mixes the 409 x 2048 strips of the column pairs with the 2048 x 409 strips of the turn candidates, and a grid sized for the largest height
+// AND the largest width of the batch dispatched five times the workgroups either shape needs (empty ones exit at once, but a batch of 96 ROIs
+// paid 1.3 ms per launch for dispatching them).  Callers order their ROIs by shape (api.hip: shape_order).  Rec: any record with h and w.
+struct ShapeRun { int first, count, h, w; };
+template <typename Rec>
+static std::vector<ShapeRun> shape_runs(const Rec *recs, int n)
+{
+    std::vector<ShapeRun> runs;
+    for (int r = 0; r < n; r++) {
+        if (!runs.empty() && runs.back().h == recs[r].h && runs.back().w == recs[r].w) runs.back().count++;
+        else runs.push_back(ShapeRun{r, 1, recs[r].h, recs[r].w});
+    }
+    return runs;
+}
+
 // ---- kernel launchers (each is stream-ordered, no host sync) --------------------------------------------
 // surf_kernels.hip
 size_t surf_roi_bytes(int h, int w, int cap, int nlayers_total, int noctaves, int dim);
@@ -279,8 +296,7 @@ int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int cap
 int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio);
 int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate);
 int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int estimator, int tol, int offset_evaluate);
-int launch_bf_hamming(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes,
-                      int *best_idx, int *best_dist);
+int launch_bf_hamming(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int max_dist);   // 32-byte rows: search + merge
 int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate);
 // consensus_kernels.hip
 int launch_consensus(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int tol, int offset_evaluate);
@@ -299,7 +315,6 @@ size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2
 int orb_roi_carve(vfsms_ctx *ctx, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p,
                   int cap1, int cap2, int cap);
 int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int nrois, const vfsms_orb_params *p);
-int launch_hamming_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int max_dist, int offset_evaluate);
 // phase_kernels.hip
 int phase_correlate_device(vfsms_ctx *ctx, const uint8_t *a, int stride_a, const uint8_t *b, int stride_b,
                            int h, int w, double *d_out3);

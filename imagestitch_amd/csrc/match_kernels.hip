@@ -974,27 +974,61 @@ __global__ __launch_bounds__(1024) void k_scan_mode(const MatchDev *jobs, int of
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Hamming 1-NN: lanes own queries (32 bytes = 8 dwords in VGPRs), trains stream through the scalar path
+// Hamming 1-NN for a batch of jobs + votes (BFMatcher("BruteForce-Hamming").match, ImageUtility.py:297-302)
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bf_hamming32(const uint32_t *__restrict__ q, int nq,
-                                                      const uint32_t *__restrict__ t, int nt,
-                                                      int *best_idx, int *best_dist)
+// lanes own queries (8 dwords in VGPRs), trains stream through the scalar path like the L2 matcher
+typedef const uint32_t __attribute__((address_space(4))) cu32c;
+// trains are split over blockIdx.z (ascending ranges); per-split first minima land in p_d1 / p_i1 and are merged in split order
+__global__ __launch_bounds__(256) void k_bf_hamming_jobs(const MatchDev *jobs)
 {
-    const int qi = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.x * 256 >= nq) return;
-    const uint32_t *pq = q + (size_t)min(qi, nq - 1) * 8;
+    const MatchDev &J = jobs[blockIdx.y];
+    const int nq = __builtin_amdgcn_readfirstlane(*J.nq_ptr), nt = __builtin_amdgcn_readfirstlane(*J.nt_ptr);
+    if ((int)(blockIdx.x * 256) >= nq) return;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t *pq = reinterpret_cast<const uint32_t *>(J.q) + (size_t)min(max(q, 0), nq - 1) * 8;
     uint32_t v[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) v[k] = pq[k];
+    const int nsplit = gridDim.z, sp = blockIdx.z;
+    const int chunk = (nt + nsplit - 1) / nsplit;
+    const int t0 = sp * chunk, t1 = min(nt, t0 + chunk);
     int best = 0x7fffffff, bi = -1;
-    for (int j = 0; j < nt; j++) {
-        const uint32_t *__restrict__ tr = t + (size_t)j * 8;
+    cu32c *T = (cu32c *)(uintptr_t)J.t;
+    for (int j = t0; j < t1; j++) {
+        cu32c *tr = T + (size_t)j * 8;
         int d = 0;
 #pragma unroll
         for (int k = 0; k < 8; k++) d += __popc(v[k] ^ tr[k]);
-        if (d < best) { best = d; bi = j; }
+        if (d < best) { best = d; bi = j; }              // first minimum wins
     }
-    if (qi < nq) { best_idx[qi] = bi; best_dist[qi] = best; }
+    if (q >= nq) return;
+    J.p_d1[(size_t)sp * J.capq + q] = (float)best; J.p_i1[(size_t)sp * J.capq + q] = bi;
+}
+
+__global__ __launch_bounds__(256) void k_hamming_merge(const MatchDev *jobs, int nsplit, int max_dist)
+{
+    const MatchDev &J = jobs[blockIdx.y];
+    const int nq = *J.nq_ptr;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    int best = 0x7fffffff, bi = -1;
+    for (int s = 0; s < nsplit; s++) {
+        const int i = J.p_i1[(size_t)s * J.capq + q];
+        const int d = i >= 0 ? (int)J.p_d1[(size_t)s * J.capq + q] : 0x7fffffff;
+        if (d < best) { best = d; bi = i; }              // splits are ascending train ranges: the first minimum still wins
+    }
+    J.i1[q] = bi; J.d1[q] = (float)best; J.d2[q] = 0.f;
+    int ok = bi >= 0 && (max_dist < 0 || best < max_dist);
+    int vote = 0;
+    if (ok && J.kq) {
+        float ay = J.kq[2 * q + 1], ax = J.kq[2 * q];
+        float by = J.kt[2 * bi + 1], bx = J.kt[2 * bi];
+        int dx = (int)(ay - by), dy = (int)(ax - bx);
+        vote = !(dx == 0 && dy == 0);
+        J.votes[2 * (size_t)(J.capq + q)] = dx;
+        J.votes[2 * (size_t)(J.capq + q) + 1] = dy;
+    }
+    J.match_flag[q] = ok | (vote << 1);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1202,13 +1236,13 @@ int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm
     return launch_vote_tail(ctx, d_jobs, njobs, capm, estimator, tol, offset_evaluate);
 }
 
-int launch_bf_hamming(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes,
-                      int *best_idx, int *best_dist)
+// Hamming search over nsplit train ranges + merge of jobs carved with that nsplit: i1 / d1, match flags and (jobs with keypoints) votes
+int launch_bf_hamming(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int max_dist)
 {
-    if (nbytes != 32) { vfsms_set_error("bf_hamming: only 32-byte descriptors supported"); return VFSMS_ERR_UNSUPPORTED; }
-    if (nq <= 0) return VFSMS_OK;
-    hipLaunchKernelGGL(k_bf_hamming32, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream,
-                       (const uint32_t *)q, nq, (const uint32_t *)t, nt, best_idx, best_dist);
+    if (njobs <= 0) return VFSMS_OK;
+    ProfScope ps(ctx, "bf_hamming");
+    hipLaunchKernelGGL(k_bf_hamming_jobs, dim3((capq + 255) / 256, njobs, nsplit), dim3(256), 0, ctx->stream, d_jobs);
+    hipLaunchKernelGGL(k_hamming_merge, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, nsplit, max_dist);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }

@@ -554,62 +554,6 @@ __global__ __launch_bounds__(256) void k_orb_describe(const OrbDev *rois, int nl
     } else if (byte == 0) R.counters[2] = 1;
 }
 
-// ---- Hamming 1-NN for a batch of jobs + votes (BFMatcher("BruteForce-Hamming").match, ImageUtility.py:297-302) ------------------------
-// lanes own queries (8 dwords in VGPRs), trains stream through the scalar path like the L2 matcher
-typedef const uint32_t __attribute__((address_space(4))) cu32c;
-// trains are split over blockIdx.z (ascending ranges); per-split first minima land in p_d1 / p_i1 and are merged in split order
-__global__ __launch_bounds__(256) void k_bf_hamming_jobs(const MatchDev *jobs)
-{
-    const MatchDev &J = jobs[blockIdx.y];
-    const int nq = __builtin_amdgcn_readfirstlane(*J.nq_ptr), nt = __builtin_amdgcn_readfirstlane(*J.nt_ptr);
-    if ((int)(blockIdx.x * 256) >= nq) return;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t *pq = reinterpret_cast<const uint32_t *>(J.q) + (size_t)min(max(q, 0), nq - 1) * 8;
-    uint32_t v[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = pq[k];
-    const int nsplit = gridDim.z, sp = blockIdx.z;
-    const int chunk = (nt + nsplit - 1) / nsplit;
-    const int t0 = sp * chunk, t1 = min(nt, t0 + chunk);
-    int best = 0x7fffffff, bi = -1;
-    cu32c *T = (cu32c *)(uintptr_t)J.t;
-    for (int j = t0; j < t1; j++) {
-        cu32c *tr = T + (size_t)j * 8;
-        int d = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) d += __popc(v[k] ^ tr[k]);
-        if (d < best) { best = d; bi = j; }              // first minimum wins
-    }
-    if (q >= nq) return;
-    J.p_d1[(size_t)sp * J.capq + q] = (float)best; J.p_i1[(size_t)sp * J.capq + q] = bi;
-}
-
-__global__ __launch_bounds__(256) void k_hamming_merge(const MatchDev *jobs, int nsplit, int max_dist)
-{
-    const MatchDev &J = jobs[blockIdx.y];
-    const int nq = *J.nq_ptr;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= nq) return;
-    int best = 0x7fffffff, bi = -1;
-    for (int s = 0; s < nsplit; s++) {
-        const int i = J.p_i1[(size_t)s * J.capq + q];
-        const int d = i >= 0 ? (int)J.p_d1[(size_t)s * J.capq + q] : 0x7fffffff;
-        if (d < best) { best = d; bi = i; }              // splits are ascending train ranges: the first minimum still wins
-    }
-    J.i1[q] = bi; J.d1[q] = (float)best; J.d2[q] = 0.f;
-    int ok = bi >= 0 && (max_dist < 0 || best < max_dist);
-    int vote = 0;
-    if (ok && J.kq) {
-        float ay = J.kq[2 * q + 1], ax = J.kq[2 * q];
-        float by = J.kt[2 * bi + 1], bx = J.kt[2 * bi];
-        int dx = (int)(ay - by), dy = (int)(ax - bx);
-        vote = !(dx == 0 && dy == 0);
-        J.votes[2 * (size_t)(J.capq + q)] = dx;
-        J.votes[2 * (size_t)(J.capq + q) + 1] = dy;
-    }
-    J.match_flag[q] = ok | (vote << 1);
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -668,39 +612,26 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
 {
     if (nrois <= 0) return VFSMS_OK;
     const int nl = p->n_levels;
-    int maxw = 0, maxh = 0, maxcap2 = 0;
-    for (int r = 0; r < nrois; r++) {
-        maxw = h_rois[r].w > maxw ? h_rois[r].w : maxw; maxh = h_rois[r].h > maxh ? h_rois[r].h : maxh;
-        maxcap2 = h_rois[r].cap2 > maxcap2 ? h_rois[r].cap2 : maxcap2;
-    }
-    int maxcap1 = 0;
-    for (int r = 0; r < nrois; r++) maxcap1 = h_rois[r].cap1 > maxcap1 ? h_rois[r].cap1 : maxcap1;
-    // Runs of consecutive ROIs of one shape: the kernels whose grid is cut from the image size are launched once per run (a batch of the
-    // incremental search mixes 409 x 2048 and 2048 x 409 strips; a grid for the largest height AND width dispatched five times the
-    // workgroups either shape needs).  vfsms_attempt_orb_batch orders its ROIs by shape.
-    struct Run { int first, count, h, w; };
-    std::vector<Run> runs;
-    for (int r = 0; r < nrois; r++) {
-        if (!runs.empty() && runs.back().h == h_rois[r].h && runs.back().w == h_rois[r].w) runs.back().count++;
-        else { Run q; q.first = r; q.count = 1; q.h = h_rois[r].h; q.w = h_rois[r].w; runs.push_back(q); }
-    }
-    (void)maxw; (void)maxh;
+    int maxcap1 = 0, maxcap2 = 0;
+    for (int r = 0; r < nrois; r++) { maxcap1 = std::max(maxcap1, h_rois[r].cap1); maxcap2 = std::max(maxcap2, h_rois[r].cap2); }
+    // The kernels whose grid is cut from the image size are launched once per run of consecutive ROIs of one shape (common.h: shape_runs); a
+    // run's level sizes are those of its first record (orb_roi_carve).  An ORB run of api.hip hands over one image (vfsms_orb_detect_describe)
+    // or the distinct strips of a batch in shape order (vfsms_attempt_orb_batch).
+    const std::vector<ShapeRun> runs = shape_runs(h_rois, nrois);
     hipLaunchKernelGGL(k_orb_clear, dim3(nrois), dim3(256), 0, ctx->stream, d_rois, nl);
     {
         ProfScope ps(ctx, "orb_pyramid");
         for (int l = 1; l < nl; l++)
-            for (const Run &q : runs) {
-                int lw[VFSMS_ORB_MAX_LEVELS], lh[VFSMS_ORB_MAX_LEVELS]; float ls[VFSMS_ORB_MAX_LEVELS];
-                orb_level_dims(p, q.h, q.w, lw, lh, ls);
+            for (const ShapeRun &q : runs) {
+                const int *lw = h_rois[q.first].lw, *lh = h_rois[q.first].lh;
                 if (lw[l] <= 0 || lh[l] <= 0) continue;
                 hipLaunchKernelGGL(k_orb_resize, dim3((lw[l] + 256) / 256, lh[l] + 1, q.count), dim3(256), 0, ctx->stream, d_rois + q.first, l);
             }
     }
     {
         ProfScope ps(ctx, "orb_fast");
-        for (const Run &q : runs) {
-            int lw[VFSMS_ORB_MAX_LEVELS], lh[VFSMS_ORB_MAX_LEVELS]; float ls[VFSMS_ORB_MAX_LEVELS];
-            orb_level_dims(p, q.h, q.w, lw, lh, ls);
+        for (const ShapeRun &q : runs) {
+            const int *lw = h_rois[q.first].lw, *lh = h_rois[q.first].lh;
             OrbPlan plan; plan.first[0] = 0;
             for (int l = 0; l < nl; l++) {
                 const int tx = std::max((lw[l] + FT_W - 1) / FT_W, 1), ty = std::max((lh[l] + FT_H - 1) / FT_H, 0);
@@ -723,9 +654,8 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
     }
     {
         ProfScope ps(ctx, "orb_describe");
-        for (const Run &q : runs) {
-            int lw[VFSMS_ORB_MAX_LEVELS], lh[VFSMS_ORB_MAX_LEVELS]; float ls[VFSMS_ORB_MAX_LEVELS];
-            orb_level_dims(p, q.h, q.w, lw, lh, ls);
+        for (const ShapeRun &q : runs) {
+            const int *lw = h_rois[q.first].lw, *lh = h_rois[q.first].lh;
             OrbPlan plan; plan.first[0] = 0;
             for (int l = 0; l < nl; l++) {
                 const int tx = std::max((lw[l] + 31) / 32, 1), ty = std::max((lh[l] + 31) / 32, 0);
@@ -738,18 +668,6 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
     }
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
-}
-
-int launch_hamming_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int max_dist, int offset_evaluate)
-{
-    if (njobs <= 0) return VFSMS_OK;
-    {
-        ProfScope ps(ctx, "bf_hamming");
-        hipLaunchKernelGGL(k_bf_hamming_jobs, dim3((capq + 255) / 256, njobs, nsplit), dim3(256), 0, ctx->stream, d_jobs);
-        hipLaunchKernelGGL(k_hamming_merge, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, nsplit, max_dist);
-    }
-    HIP_TRY(hipGetLastError());
-    return launch_scan_mode(ctx, d_jobs, njobs, capq, offset_evaluate);
 }
 
 // ---- tables: per-level quotas, umax, fixed-point Gaussian, sampling pattern (uploaded when the parameters change) --------------------

@@ -202,21 +202,6 @@ __global__ __launch_bounds__(256) void k_integral_final(const RoiDev *rois)
     }
 }
 
-// Kernels whose grid is cut from the image size are launched once per RUN of consecutive ROIs of one shape: a batch of the incremental search
-// mixes the 409 x 2048 strips of the column pairs with the 2048 x 409 strips of the turn candidates, and a grid sized for the largest height
-// AND the largest width of the batch dispatched five times the workgroups either shape needs (empty ones exit at once, but a batch of 96 ROIs
-// paid 1.3 ms per launch for dispatching them).  Callers order their ROIs by shape (attempt_surf_impl).
-struct ShapeRun { int first, count, h, w; };
-static std::vector<ShapeRun> shape_runs(const RoiDev *h_rois, int nrois)
-{
-    std::vector<ShapeRun> runs;
-    for (int r = 0; r < nrois; r++) {
-        if (!runs.empty() && runs.back().h == h_rois[r].h && runs.back().w == h_rois[r].w) runs.back().count++;
-        else { ShapeRun q; q.first = r; q.count = 1; q.h = h_rois[r].h; q.w = h_rois[r].w; runs.push_back(q); }
-    }
-    return runs;
-}
-
 int launch_integral(vfsms_ctx *ctx, const RoiDev *d_rois, int nrois, int maxh, int maxw)
 {
     if (nrois <= 0) return VFSMS_OK;

@@ -155,3 +155,71 @@ def test_attempt_batch_equals_the_reference_chain(engine, oracle):
     finally:
         for h in hs:
             engine.tile_free(h)
+
+
+def test_batch_retry_with_overflowing_strips_of_two_shapes(engine, oracle):
+    """nfeatures = 100: capacities cap1 = 2136, cap2 = 1068, cap = 2248.  The 256 x 1024 lattice (2937 keypoints, 2880 on level 0) exceeds
+    all of them, the 640 x 256 one (1784, 1728 on level 0) the level-0 capacity cap2 alone, the 256 x 768 one of period 12 (1041, 944) none:
+    the batch runs once more with capacities grown over BOTH overflowing shapes, and the single image takes the same retry"""
+    p = OC.params(nfeatures=100)
+    tiles = [OC.lattice(256, 1024, 8, 3), OC.lattice(256, 1024, 8, 5), OC.lattice(640, 256, 8, 3), OC.lattice(640, 256, 8, 5),
+             OC.lattice(256, 768, 12, 3), OC.lattice(256, 768, 12, 5)]
+    refs = [R.detect_describe(t, **p) for t in tiles]
+    assert [len(refs[i][0]) for i in (0, 2, 4)] == [2937, 1784, 1041]
+    assert [int((refs[i][0]["octave"] == 0).sum()) for i in (0, 2, 4)] == [2880, 1728, 944]
+
+    def ref(tile):
+        return refs[next(i for i, t in enumerate(tiles) if t is tile)]
+
+    hs = [engine.tile_upload(t) for t in tiles]
+    try:
+        pairs = [(0, 1), (4, 5), (2, 3), (0, 1)]                      # mixed shapes; the first overflowing strip is named by two jobs
+        jobs = [(hs[a], hs[b], 0, 0, 0, 0) + tiles[a].shape for a, b in pairs]
+        for max_dist, oe in ((-1, 3), (30, 10)):
+            rows = engine.attempt_orb_batch(jobs, _params(p), max_dist, oe)
+            for (a, b), row in zip(pairs, rows):
+                assert list(row[:7]) == _chain(oracle, ref, tiles[a], tiles[b], max_dist, oe), (a, b, max_dist, oe, row[:7])
+            assert [int(rows[k][4]) for k in (0, 2, 3)] == [2937, 1784, 2937]
+    finally:
+        for h in hs:
+            engine.tile_free(h)
+    _assert_same("lattice 256x1024", _device(engine, tiles[0], p), refs[0])
+    with pytest.raises(isa.VfsmsError):
+        engine.orb_detect_describe(tiles[0], _params(p), cap=100)
+
+
+# ---- Hamming 1-NN (vfsms_bf_hamming_nn): one job of the batched matcher, trains in up to eight ascending ranges ------------------------------
+def _hamming_sets(nq, nt, seed):
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, 256, (nq, 32), dtype=np.uint8), rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+
+
+def test_hamming_ties_across_train_splits_keep_the_lowest_train(engine, oracle):
+    """300 queries against 70 trains: eight splits of nine trains.  Trains 35.. repeat trains 0..34, so EVERY query's minimum is tied
+    between two splits; trains 5, 23, 33 (hence 40, 58, 68) are one row and so are 8 | 9 on either side of a split boundary.  The pair
+    list is the oracle's, and the tied blocks name the lowest train whatever the oracle says"""
+    q, t = _hamming_sets(300, 70, 11)
+    t[9] = t[8]
+    t[23] = t[33] = t[5]
+    t[35:] = t[:35]
+    assert all(np.array_equal(t[5], t[j]) for j in (23, 68)) and np.array_equal(t[8], t[9])
+    assert -(-70 // 8) == 9                                           # the split's train range: 8 | 9 is a boundary
+    q[100:140] = t[5]
+    q[200:220] = t[8]
+    for max_dist in (-1, 30):
+        got = engine.bf_hamming_matches(q, t, max_dist)
+        assert np.array_equal(got, oracle.bf_hamming_matches(q, t, max_dist)[0]), max_dist
+        train_of = dict((int(qi), int(ti)) for ti, qi in got)
+        assert all(train_of[i] == 5 for i in range(100, 140)) and all(train_of[i] == 8 for i in range(200, 220))
+        assert len(got) == (300 if max_dist < 0 else 60) and got[:, 0].max() < 35
+
+
+@pytest.mark.parametrize("nq,nt", [(1, 1), (1, 3), (257, 3), (64, 8)])
+def test_hamming_edge_shapes(engine, oracle, nq, nt):
+    """fewer trains than splits leave splits empty; 257 queries leave one lane of a second workgroup"""
+    q, t = _hamming_sets(nq, nt, 100 * nq + nt)
+    q[nq - 1] = t[nt - 1]                                             # one exact match survives max_dist = 30
+    for max_dist in (-1, 30):
+        got = engine.bf_hamming_matches(q, t, max_dist)
+        assert np.array_equal(got, oracle.bf_hamming_matches(q, t, max_dist)[0]), max_dist
+        assert len(got) >= 1 and tuple(got[-1]) == (np.nonzero((t == t[nt - 1]).all(1))[0][0], nq - 1)
