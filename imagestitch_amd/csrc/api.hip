@@ -1592,7 +1592,7 @@ extern "C" int vfsms_attempt_surf_batch_enhanced(vfsms_ctx *ctx, const vfsms_roi
                                                  double ratio, int offset_evaluate, int enhance_mode, double clip_limit, int tile_grid,
                                                  int32_t *out)
 {
-    if (enhance_mode < 0 || enhance_mode > 2) { vfsms_set_error("attempt_surf: enhance_mode must be 0, 1 or 2"); return VFSMS_ERR_BAD_ARG; }
+    TRY(enhance_check_args("attempt_surf", enhance_mode, tile_grid));
     return attempt_surf_impl(ctx, jobs, n, params, ratio, offset_evaluate, enhance_mode, clip_limit, tile_grid, out);
 }
 
@@ -1602,6 +1602,7 @@ extern "C" int vfsms_enhance_u8(vfsms_ctx *ctx, const uint8_t *img, int h, int w
 {
     CTX_ENTER(ctx);
     if (!img || !out || h <= 0 || w <= 0 || stride < w || mode < 1 || mode > 2) { vfsms_set_error("enhance: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(enhance_check_args("enhance", mode, tile_grid));
     TRY(ctx_arena_reserve(ctx, (size_t)h * w + enhance_scratch_bytes(h, w, mode, tile_grid) + 65536));
     ctx->pinned_off = 0;
     uint8_t *d_img;
@@ -1658,7 +1659,7 @@ extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0,
     if (T.ch != 1) { vfsms_set_error("features_surf: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
     TRY(tile_ready(ctx, T));
     if (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 + h > T.h || x0 + w > T.w) { vfsms_set_error("features_surf: ROI outside the tile"); return VFSMS_ERR_BAD_ARG; }
-    if (enhance_mode < 0 || enhance_mode > 2) { vfsms_set_error("features_surf: enhance_mode must be 0, 1 or 2"); return VFSMS_ERR_BAD_ARG; }
+    TRY(enhance_check_args("features_surf", enhance_mode, tile_grid));
     TRY(ctx_prepare_surf(ctx, params));
     const SurfSrc src{T.ptr + (size_t)y0 * T.stride + x0, T.stride, h, w, kp_capacity(ctx, h, w)};
     const SurfEnh enh{enhance_mode, clip_limit, tile_grid};
@@ -1706,7 +1707,7 @@ static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n,
 {
     CTX_ENTER(ctx);
     if (n < 0 || (n && (!tiles || !feats || !counts)) || !params) { vfsms_set_error("features_surf_batch: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    if (enhance_mode < 0 || enhance_mode > 2) { vfsms_set_error("features_surf_batch: enhance_mode must be 0, 1 or 2"); return VFSMS_ERR_BAD_ARG; }
+    TRY(enhance_check_args("features_surf_batch", enhance_mode, tile_grid));
     TRY(ctx_prepare_surf(ctx, params));
     const SurfEnh enh{enhance_mode, clip_limit, tile_grid};
     for (int k = 0; k < n; k++) feats[k] = 0;

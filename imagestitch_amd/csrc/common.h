@@ -330,6 +330,7 @@ int launch_phase_resolve(vfsms_ctx *ctx, const PhaseJobHost *d_jobs, const Phase
                          double threshold, int min_pixels, unsigned long long *d_sums, int32_t *d_rows, int32_t *d_cands, int32_t *d_peaks_out);
 int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);   // launch records through the pinned staging buffer
 // enhance_kernels.hip
+int enhance_check_args(const char *who, int mode, int tiles);
 size_t enhance_scratch_bytes(int h, int w, int mode, int tiles);
 int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles);
 int launch_enhance(vfsms_ctx *ctx, const EnhJob *d_jobs, const EnhJob *h_jobs, int n, int mode, double clip_limit, int tiles);

@@ -145,6 +145,16 @@ __global__ __launch_bounds__(256) void k_enh_apply(const EnhJob *jobs, int mode,
     ((uint8_t GAS *)J.dst)[(size_t)y * J.w + x] = o;
 }
 
+// The one check of (mode, grid): every entry point that takes them calls it BEFORE enhance_scratch_bytes / enhance_carve see the grid
+// (they form tiles * tiles and w % tiles: a grid of 0 is a division by zero on the host, a huge one overflows int).  mode 0 and 1 do not
+// look at the grid (the Stitcher passes 0 with equalizeHist).
+int enhance_check_args(const char *who, int mode, int tiles)
+{
+    if (mode < 0 || mode > 2) { vfsms_set_error("%s: enhance mode must be 0 (none), 1 (equalizeHist) or 2 (CLAHE)", who); return VFSMS_ERR_BAD_ARG; }
+    if (mode == 2 && (tiles < 1 || tiles > 64)) { vfsms_set_error("%s: CLAHE tile grid must be 1..64, got %d", who, tiles); return VFSMS_ERR_BAD_ARG; }
+    return VFSMS_OK;
+}
+
 size_t enhance_scratch_bytes(int h, int w, int mode, int tiles)
 {
     const int nt = mode == 2 ? tiles * tiles : 1;
@@ -168,8 +178,7 @@ int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int
 int launch_enhance(vfsms_ctx *ctx, const EnhJob *d_jobs, const EnhJob *h_jobs, int n, int mode, double clip_limit, int tiles)
 {
     if (n <= 0 || mode == 0) return VFSMS_OK;
-    if (mode != 1 && mode != 2) { vfsms_set_error("enhance: mode must be 0 (none), 1 (equalizeHist) or 2 (CLAHE)"); return VFSMS_ERR_BAD_ARG; }
-    if (mode == 2 && (tiles < 1 || tiles > 64)) { vfsms_set_error("enhance: CLAHE tile grid must be 1..64"); return VFSMS_ERR_BAD_ARG; }
+    TRY(enhance_check_args("enhance", mode, tiles));
     ProfScope ps(ctx, "enhance");
     const int nt = mode == 2 ? tiles * tiles : 1;
     int maxh = 0, maxw = 0;

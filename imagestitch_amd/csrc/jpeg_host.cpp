@@ -262,7 +262,9 @@ int jpeg_decode_raw420_host(const unsigned char *jpeg, size_t nbytes, unsigned c
     const JpegApi &A = api();
     if (!A.ok || !A.read_raw) { vfsms_set_error("jpeg: no raw-data decode on this host"); return VFSMS_ERR_UNSUPPORTED; }
     int sh = 0, sw = 0, snc = 0, samp[3] = {0, 0, 0};
-    if (!jpeg || !sof_size(jpeg, nbytes, &sh, &sw, &snc, samp) || snc != 3 || samp[0] != 0x22 || samp[1] != 0x11 || samp[2] != 0x11 || sw < 4 || sh < 2) {
+    // sw < 5: jdsample.c takes h2v2_fancy_upsample only when do_fancy_upsampling && compptr->downsampled_width > 2; a file of 3 or 4 columns
+    // (2 chroma columns) gets h2v2_upsample, plain replication, which k_ingest_420 does not restate -- the full decode takes those files
+    if (!jpeg || !sof_size(jpeg, nbytes, &sh, &sw, &snc, samp) || snc != 3 || samp[0] != 0x22 || samp[1] != 0x11 || samp[2] != 0x11 || sw < 5 || sh < 2) {
         vfsms_set_error("jpeg: not a 4:2:0 Y Cb Cr file"); return VFSMS_ERR_UNSUPPORTED;
     }
     const size_t pw = ((size_t)sw + 15) & ~(size_t)15, ph = ((size_t)sh + 15) & ~(size_t)15;

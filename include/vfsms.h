@@ -339,7 +339,8 @@ int vfsms_attempt_surf_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n,
                              const vfsms_surf_params *params, double ratio, int offset_evaluate,
                              int32_t *out);
 /* the same with the reference's pre-enhancement of every ROI strip (Method.isEnhance, Stitcher.py:327-334):
- * enhance_mode 1 = cv2.equalizeHist, 2 = cv2.createCLAHE(clip_limit, (tile_grid, tile_grid)).apply, 0 = none                  */
+ * enhance_mode 1 = cv2.equalizeHist, 2 = cv2.createCLAHE(clip_limit, (tile_grid, tile_grid)).apply, 0 = none; with mode 2 a
+ * tile_grid outside 1..64 is VFSMS_ERR_BAD_ARG from every entry point that takes the three (modes 0 and 1 ignore it)            */
 int vfsms_attempt_surf_batch_enhanced(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, const vfsms_surf_params *params,
                                       double ratio, int offset_evaluate, int enhance_mode, double clip_limit, int tile_grid,
                                       int32_t *out);

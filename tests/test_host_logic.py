@@ -527,15 +527,7 @@ def test_raw_420_planes_and_the_restated_fancy_upsampler_equal_the_library():
     if _lib.jpeg_decode(_jpeg_bytes(base), False) is None:
         pytest.skip("no libjpeg.so.8 on this host: the Stitcher decodes with Pillow")
 
-    def fancy(plane, H, W):
-        dh, dw = (H + 1) // 2, (W + 1) // 2
-        p = plane[:dh, :dw].astype(np.int32)
-        up = np.vstack([p[:1], p[:-1]]); dn = np.vstack([p[1:], p[-1:]])
-        rows = np.empty((2 * dh, dw), np.int32); rows[0::2] = 3 * p + up; rows[1::2] = 3 * p + dn
-        left = np.hstack([rows[:, :1], rows[:, :-1]]); right = np.hstack([rows[:, 1:], rows[:, -1:]])
-        out = np.empty((2 * dh, 2 * dw), np.int32)
-        out[:, 0::2] = (3 * rows + left + 8) >> 4; out[:, 1::2] = (3 * rows + right + 7) >> 4
-        return out[:H, :W].astype(np.uint8)
+    from ingest_ref import fancy_h2v2 as fancy                 # the triangle filter as stated above (tests/ingest_ref.py)
     for (w, h), kw in (((613, 407), dict(quality=90)), ((333, 7), dict(quality=70)), ((1021, 767), dict(quality=85, progressive=True)),
                        ((64, 48), dict(quality=95)), ((5, 3), dict(quality=90)), ((2048, 2048), dict(quality=90))):
         img = np.asarray(Image.fromarray(base).resize((w, h), Image.BICUBIC))
