@@ -57,6 +57,15 @@ void *ctx_arena_alloc(vfsms_ctx *ctx, size_t bytes, size_t align)
     ctx->arena_off = off + bytes;
     return ctx->arena + off;
 }
+// a record's layout function carves from a walk that starts where the arena stands (arena_walk.h) ...
+ArenaWalk ctx_arena_walk(vfsms_ctx *ctx) { return ArenaWalk{ctx->arena, ctx->arena_off, ctx->arena_size}; }
+// ... and the arena moves on only when every take of the walk fitted; `what`: the error string of a walk that did not
+int ctx_arena_commit(vfsms_ctx *ctx, const ArenaWalk &a, const char *what)
+{
+    if (!a.ok) { vfsms_set_error("%s", what); return VFSMS_ERR_CAPACITY; }
+    ctx->arena_off = a.off;
+    return VFSMS_OK;
+}
 
 // ---- per-stage profiling with HIP events on the context stream --------------------------------------------
 int prof_begin(vfsms_ctx *ctx, const char *name)
@@ -729,6 +738,11 @@ int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d)
 {
     *d = ctx_arena_alloc(ctx, bytes ? bytes : 1);
     if (!*d) { vfsms_set_error("arena exhausted (record upload)"); return VFSMS_ERR_CAPACITY; }
+    return ctx_copy_small(ctx, src, bytes, *d);
+}
+// the same to an array the caller's layout walk took
+int ctx_copy_small(vfsms_ctx *ctx, const void *src, size_t bytes, void *d)
+{
     if (ctx->pinned_off + bytes > ctx->pinned_size) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));                 // earlier copies out of the old buffer have landed
         if (ctx->pinned) HIP_TRY(hipHostFree(ctx->pinned));
@@ -738,7 +752,7 @@ int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d)
         ctx->pinned_off = 0;
     }
     memcpy(ctx->pinned + ctx->pinned_off, src, bytes);
-    HIP_TRY(hipMemcpyAsync(*d, ctx->pinned + ctx->pinned_off, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d, ctx->pinned + ctx->pinned_off, bytes, hipMemcpyHostToDevice, ctx->stream));
     ctx->pinned_off += (bytes + 255) & ~(size_t)255;
     return VFSMS_OK;
 }
@@ -770,38 +784,40 @@ extern "C" int vfsms_integral_u8_i32(vfsms_ctx *ctx, const uint8_t *img, int h, 
 // Every entry point that runs SURF goes through these phases, in this order: surf_run_bytes into the caller's ONE ctx_arena_reserve (it
 // resets the arena), surf_run_carve, surf_run_prepare, surf_run_launch over one or more ranges of the sources, surf_run_readback, the caller's own
 // hipStreamSynchronize (it may enqueue copies of its own first), surf_run_check.
-struct SurfSrc { const uint8_t *p; int stride, h, w, cap; };      // pixels on the device, keypoint capacity of the source
-struct SurfEnh { int mode; double clip_limit; int tile_grid; };   // equalizeHist / CLAHE before detection (mode 0: none)
-struct SurfRun {
-    std::vector<RoiDev> R; RoiDev *dR = nullptr;                  // host and device copies of the ROI records
-    std::vector<EnhJob> E;
-    int *cblock = nullptr;                                        // 16 counters per source, one contiguous block: one memset, one copy back
-    std::vector<int> counters;
-};
-static size_t surf_run_bytes(vfsms_ctx *ctx, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
-{
-    size_t need = 0;
-    for (int i = 0; i < n; i++) {
-        need += surf_roi_bytes(S[i].h, S[i].w, S[i].cap, ctx->n_layers, p->n_octaves, p->extended ? 128 : 64);
-        if (enh.mode) need += enhance_scratch_bytes(S[i].h, S[i].w, enh.mode, enh.tile_grid) + sizeof(EnhJob) + 512;
-    }
-    return need + (sizeof(RoiDev) + 64) * (size_t)n + 1024;       // the records, the counters, their alignment
-}
-static int surf_run_carve(vfsms_ctx *ctx, SurfRun *run, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
+// The one place that knows a run's arena block: the counters, per source its enhancement job and its ROI, the uploaded records
+void surf_run_layout(ArenaWalk &a, SurfRun *run, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
 {
     run->R.resize(n); run->E.resize(enh.mode ? n : 0);
-    run->cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 16 * n);
-    if (!run->cblock) { vfsms_set_error("arena exhausted (SURF counters)"); return VFSMS_ERR_CAPACITY; }
+    run->cblock = a.take<int>(16 * (size_t)n);
     for (int i = 0; i < n; i++) {
         const uint8_t *px = S[i].p; int stride = S[i].stride;
         if (enh.mode) {            // Stitcher.py:327-334: the ROI strips are equalised / CLAHE'd before detectAndDescribe
-            TRY(enhance_carve(ctx, &run->E[i], px, stride, S[i].h, S[i].w, enh.mode, enh.tile_grid));
+            enhance_layout(a, &run->E[i], px, stride, S[i].h, S[i].w, enh.mode, enh.tile_grid);
             px = run->E[i].dst; stride = S[i].w;
         }
-        TRY(surf_roi_carve(ctx, &run->R[i], px, stride, S[i].h, S[i].w, S[i].cap, p));
-        run->R[i].counters = run->cblock + 16 * i;
+        surf_roi_layout(a, &run->R[i], px, stride, S[i].h, S[i].w, S[i].cap, p);
+        run->R[i].counters = run->cblock ? run->cblock + 16 * i : nullptr;
     }
-    return ctx_upload_small(ctx, run->R.data(), sizeof(RoiDev) * n, (void **)&run->dR);
+    run->dR = a.take<RoiDev>(n);
+    run->dE = enh.mode ? a.take<EnhJob>(n) : nullptr;
+}
+// with the work lists of the describe launches over the sources [0, split) and [split, n) (launch_surf_describe carves them when it runs)
+static size_t surf_run_bytes(const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh, int split = 0)
+{
+    ArenaWalk a; SurfRun run; DescWork W;
+    surf_run_layout(a, &run, S, n, p, enh);
+    size_t cap0 = 0, cap1 = 0;
+    for (int i = 0; i < n; i++) (i < split ? cap0 : cap1) += (size_t)S[i].cap;
+    if (split > 0) surf_describe_layout(a, &W, cap0);
+    if (split < n) surf_describe_layout(a, &W, cap1);
+    return a.off;
+}
+static int surf_run_carve(vfsms_ctx *ctx, SurfRun *run, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh)
+{
+    ArenaWalk a = ctx_arena_walk(ctx);
+    surf_run_layout(a, run, S, n, p, enh);
+    TRY(ctx_arena_commit(ctx, a, "arena exhausted while carving a SURF run"));
+    return ctx_copy_small(ctx, run->R.data(), sizeof(RoiDev) * n, run->dR);
 }
 // the enhancement and the zeroed counters, enqueued behind every record upload of the call (a fused batch uploads its match records
 // in between: copies next to copies, then the device work)
@@ -809,9 +825,8 @@ static int surf_run_prepare(vfsms_ctx *ctx, SurfRun *run, const SurfEnh &enh)
 {
     const int n = (int)run->R.size();
     if (enh.mode) {
-        EnhJob *dE;
-        TRY(ctx_upload_small(ctx, run->E.data(), sizeof(EnhJob) * n, (void **)&dE));
-        TRY(launch_enhance(ctx, dE, run->E.data(), n, enh.mode, enh.clip_limit, enh.tile_grid));
+        TRY(ctx_copy_small(ctx, run->E.data(), sizeof(EnhJob) * n, run->dE));
+        TRY(launch_enhance(ctx, run->dE, run->E.data(), n, enh.mode, enh.clip_limit, enh.tile_grid));
     }
     HIP_TRY(hipMemsetAsync(run->cblock, 0, sizeof(int) * 16 * n, ctx->stream));
     return VFSMS_OK;
@@ -852,7 +867,7 @@ static int surf_host(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int strid
     const int dim = params->extended ? 128 : 64;
     const SurfEnh plain{0, 0.0, 0};
     SurfSrc src{nullptr, w, h, w, kp_capacity(ctx, h, w)};
-    TRY(ctx_arena_reserve(ctx, (size_t)h * w + surf_run_bytes(ctx, &src, 1, params, plain) + 65536));
+    TRY(ctx_arena_reserve(ctx, (size_t)h * w + surf_run_bytes(&src, 1, params, plain) + 65536));
     ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
     uint8_t *d_img;
     TRY(upload_image(ctx, img, h, w, stride, &d_img));
@@ -1185,30 +1200,37 @@ extern "C" int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const 
 }
 
 // ---- phase correlation resolved by overlap correlation (phase_resolve_kernels.hip) -----------------------------------------------------
-// arena bytes of nb jobs of one strip shape, beyond the results
+// The one place that knows what nb jobs of one strip shape take from the arena beyond the results and ahead of the correlation's own
+// scratch (phase_layout): the correlation's output, the peaks, the candidates' sums, the uploaded strips
+void phase_resolve_layout(ArenaWalk &a, PhaseResolveDev *d, int nb, int K)
+{
+    d->out3 = a.take<double>(3 * (size_t)nb);
+    d->peaks = a.take<PhasePeak>((size_t)nb * K);
+    d->sums = a.take<unsigned long long>(phase_resolve_sums_bytes(nb, K) / sizeof(unsigned long long));
+    d->jobs = a.take<PhaseJobHost>(nb);
+}
 static int phase_resolve_bytes(vfsms_ctx *ctx, int h, int w, int nb, int K, size_t *bytes)
 {
-    size_t pb = 0;
-    TRY(phase_bytes(ctx, h, w, nb, &pb));
-    *bytes = pb + phase_peaks_bytes(h, w, nb, K) + sizeof(double) * 3 * (size_t)nb + sizeof(PhasePeak) * (size_t)nb * K + phase_resolve_sums_bytes(nb, K) +
-             sizeof(PhaseJobHost) * (size_t)nb + 4096;
+    ArenaWalk a; PhaseResolveDev d; PhaseScratch sc;
+    phase_resolve_layout(a, &d, nb, K);
+    TRY(phase_layout(ctx, a, &sc, h, w, nb, K));
+    *bytes = a.off;
     return VFSMS_OK;
 }
 // nb jobs of one strip shape: correlation with the peak sink, then the candidates; results at d_rows / d_cands / d_pk (device, nb records each)
 static int phase_resolve_group(vfsms_ctx *ctx, const PhaseJobHost *pj, int nb, int h, int w, int K, double threshold, int min_pixels,
                                int32_t *d_rows, int32_t *d_cands, int32_t *d_pk)
 {
-    double *d_out3 = (double *)ctx_arena_alloc(ctx, sizeof(double) * 3 * (size_t)nb);
-    PhasePeak *d_peaks = (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)nb * K);
-    unsigned long long *d_sums = (unsigned long long *)ctx_arena_alloc(ctx, phase_resolve_sums_bytes(nb, K));
-    if (!d_out3 || !d_peaks || !d_sums) { vfsms_set_error("phase_resolve: arena exhausted"); return VFSMS_ERR_CAPACITY; }
-    PhaseJobHost *d_jobs = nullptr;
-    TRY(ctx_upload_small(ctx, pj, sizeof(PhaseJobHost) * (size_t)nb, (void **)&d_jobs));
-    const PhasePeakSink sink = {K, d_peaks};
-    TRY(phase_correlate_batch_device(ctx, pj, nb, h, w, d_out3, &sink));
+    ArenaWalk a = ctx_arena_walk(ctx);
+    PhaseResolveDev d;
+    phase_resolve_layout(a, &d, nb, K);
+    TRY(ctx_arena_commit(ctx, a, "phase_resolve: arena exhausted"));
+    TRY(ctx_copy_small(ctx, pj, sizeof(PhaseJobHost) * (size_t)nb, d.jobs));
+    const PhasePeakSink sink = {K, d.peaks};
+    TRY(phase_correlate_batch_device(ctx, pj, nb, h, w, d.out3, &sink));
     int oM, oN;
     phase_surface_size(h, w, &oM, &oN);
-    return launch_phase_resolve(ctx, d_jobs, d_peaks, nb, K, oM, oN, h, w, threshold, min_pixels, d_sums, d_rows, d_cands, d_pk);
+    return launch_phase_resolve(ctx, d.jobs, d.peaks, nb, K, oM, oN, h, w, threshold, min_pixels, d.sums, d_rows, d_cands, d_pk);
 }
 
 extern "C" int vfsms_phase_resolve_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w, int stride_a, int stride_b,
@@ -1263,12 +1285,6 @@ static int resolve_job(vfsms_ctx *ctx, const vfsms_roi_pair &j, const uint8_t **
 // before part 0's search, in stream order -- and never the other way round.  Slots run in (shape) order and a strip has its job's shape,
 // so the order of first use is already the (part, shape) order the shape-run launchers need.
 // VFSMS_STRIP_DEDUP=0 carves every slot a strip of its own (2s, 2s + 1: the layout before the table) for A/B runs.
-struct StripTable {
-    struct Strip { const uint8_t *p; int stride, h, w; };
-    std::vector<Strip> strips;               // distinct strips in launch order
-    std::vector<int> a, b;                   // per slot: its A / B strip
-    int u0 = 0;                              // strips of part 0 (the first u0)
-};
 // the raw pixels of a job's two strips, for the overlap check behind the vote (verify_kernels.hip)
 static void match_set_strips(MatchDev *m, const StripTable::Strip &A, const StripTable::Strip &B)
 {
@@ -1321,16 +1337,6 @@ static int shape_run_end(int g0, int n, ShapeAt shape_at)
 // ---- one 2-NN search + vote run: n (query set, train set) jobs in fused launches ------------------------------------------------------
 // The phases mirror a SURF run's: match_run_bytes into the caller's ONE ctx_arena_reserve, match_run_carve (wires and uploads the
 // records), match_run_launch over one or more ranges of the jobs, match_run_readback in front of the caller's synchronisation.
-struct MatchPlan { bool filtered; int ns, cns; };    // filtered: MFMA candidate filter (cns train splits) + exact verification; else ns splits
-struct MatchJob {
-    const float *q, *t, *kq, *kt;                    // descriptors and keypoint positions of the query and the train set
-    const int *nq_ptr, *nt_ptr;                      // their counts, on the device
-    int capq, capt;                                  // what the job's arrays are sized for
-    int row;                                         // the job's row of the result block
-    const int8_t *q8, *t8; const int *qn2, *tn2;     // optional: int8 rows and their norms (k_bf_i8_d128)
-    const StripTable::Strip *sa, *sb;                // optional: the raw pixels of the two strips, for the verifier behind the vote
-};
-struct MatchRun { MatchPlan P; int dim; std::vector<MatchDev> M; MatchDev *dM = nullptr; int32_t *rblock = nullptr; };
 // k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows / k_bf_hamming_jobs on 32-byte rows behind q, t
 enum MatchSearch { SEARCH_FLOAT, SEARCH_I8_D128, SEARCH_HAMMING };
 struct MatchTail { double ratio; int max_dist; int offset_evaluate; };   // the ratio test (L2) or the distance bound (Hamming), the vote's threshold
@@ -1346,29 +1352,29 @@ static MatchPlan match_plan_float(int dim, int njobs, int fq, int ft, int eq, in
     P.ns = P.filtered ? 1 : pick_nsplit(eq, et, njobs, dim);
     return P;
 }
-static size_t match_run_bytes(const MatchJob *J, int n, const MatchPlan &P)
+// The one place that knows a run's arena block: the result rows (one block: one copy back), per job its arrays, the uploaded records
+void match_run_layout(ArenaWalk &a, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
 {
-    size_t need = 0;
-    for (int k = 0; k < n; k++)
-        need += match_bytes(J[k].capq, P.ns) + (P.filtered ? match_filter_bytes(J[k].capq, J[k].capt, P.cns) : 0);
-    return need + (sizeof(MatchDev) + 64 + sizeof(int32_t) * VFSMS_ATTEMPT_INTS) * (size_t)n + 1024;
-}
-static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
-{
-    run->P = P; run->dim = dim; run->M.resize(n);
-    run->rblock = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * n);     // all rows in one block: one copy back
-    if (!run->rblock) { vfsms_set_error("arena exhausted (match results)"); return VFSMS_ERR_CAPACITY; }
+    run->P = P; run->dim = dim; run->M.assign(n, MatchDev{});
+    run->rblock = a.take<int32_t>(VFSMS_ATTEMPT_INTS * (size_t)n);
     for (int k = 0; k < n; k++) {
         MatchDev &m = run->M[k];
-        memset(&m, 0, sizeof(m));
-        TRY(match_carve(ctx, &m, J[k].capq, dim, P.ns));
-        if (P.filtered) TRY(match_filter_carve(ctx, &m, J[k].capq, J[k].capt, P.cns));
-        m.result = run->rblock + VFSMS_ATTEMPT_INTS * J[k].row;
+        match_layout(a, &m, J[k].capq, dim, P.ns);
+        if (P.filtered) match_filter_layout(a, &m, J[k].capq, J[k].capt, P.cns);
+        m.result = run->rblock ? run->rblock + VFSMS_ATTEMPT_INTS * J[k].row : nullptr;
         m.q = J[k].q; m.t = J[k].t; m.kq = J[k].kq; m.kt = J[k].kt; m.nq_ptr = J[k].nq_ptr; m.nt_ptr = J[k].nt_ptr;
         m.q8 = J[k].q8; m.t8 = J[k].t8; m.qn2 = J[k].qn2; m.tn2 = J[k].tn2;
         if (J[k].sa) match_set_strips(&m, *J[k].sa, *J[k].sb);
     }
-    return ctx_upload_small(ctx, run->M.data(), sizeof(MatchDev) * n, (void **)&run->dM);
+    run->dM = a.take<MatchDev>(n);
+}
+static size_t match_run_bytes(const MatchJob *J, int n, const MatchPlan &P) { ArenaWalk a; MatchRun run; match_run_layout(a, &run, J, n, 0, P); return a.off; }
+static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
+{
+    ArenaWalk a = ctx_arena_walk(ctx);
+    match_run_layout(a, run, J, n, dim, P);
+    TRY(ctx_arena_commit(ctx, a, "arena exhausted while carving a match run"));
+    return ctx_copy_small(ctx, run->M.data(), sizeof(MatchDev) * n, run->dM);
 }
 // search + ratio test (Hamming: distance bound) + vote of jobs [first, first + count); maxq / maxt: the largest query / train set to cover
 static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search, const MatchTail &tail)
@@ -1546,7 +1552,7 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
     }
     const SurfEnh enh{enh_mode, clip_limit, tile_grid};
     const MatchTail tail{ratio, -1, offset_evaluate};
-    TRY(ctx_arena_reserve(ctx, surf_run_bytes(ctx, S.data(), u, params, enh) + match_run_bytes(J.data(), n, P) + 65536));
+    TRY(ctx_arena_reserve(ctx, surf_run_bytes(S.data(), u, params, enh, u0) + match_run_bytes(J.data(), n, P) + 65536));
     ctx->pinned_off = 0;
     SurfRun surf; MatchRun match;
     TRY(surf_run_carve(ctx, &surf, S.data(), u, params, enh));
@@ -1663,7 +1669,7 @@ extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0,
     TRY(ctx_prepare_surf(ctx, params));
     const SurfSrc src{T.ptr + (size_t)y0 * T.stride + x0, T.stride, h, w, kp_capacity(ctx, h, w)};
     const SurfEnh enh{enhance_mode, clip_limit, tile_grid};
-    TRY(ctx_arena_reserve(ctx, surf_run_bytes(ctx, &src, 1, params, enh) + 65536));
+    TRY(ctx_arena_reserve(ctx, surf_run_bytes(&src, 1, params, enh) + 65536));
     ctx->pinned_off = 0;
     SurfRun run;
     TRY(surf_run_carve(ctx, &run, &src, 1, params, enh));
@@ -1721,7 +1727,7 @@ static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n,
             TileRec &t = it->second;
             if (t.ch != 1) { vfsms_set_error("features_surf_batch: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
             const SurfSrc src{t.ptr, t.stride, t.h, t.w, kp_capacity(ctx, t.h, t.w)};
-            const size_t b = surf_run_bytes(ctx, &src, 1, params, enh);
+            const size_t b = surf_run_bytes(&src, 1, params, enh);
             if (c1 > c0 && need + b > ((size_t)6 << 30)) break;
             need += b; T.push_back(&t); S.push_back(src); c1++;
         }
@@ -2409,28 +2415,29 @@ static void orb_grow_caps(const int *counters, int nlevels, int *cap1, int *cap2
 // ---- one ORB run: n sources detected and described in fused launches ----------------------------------------------------------------------
 // The phases of a SURF run: orb_run_bytes into the caller's ONE ctx_arena_reserve, orb_run_carve (wires and uploads the records), orb_run_launch,
 // then orb_run_retry's orb_run_readback, synchronisation and orb_run_overflow.  A source is a strip of a batch's table or a whole image.
-struct OrbRun {
-    std::vector<OrbDev> R; OrbDev *dR = nullptr;                  // host and device copies of the ROI records
-    int *cblock = nullptr;                                        // 64 ints per source, one contiguous block: counters, thr1, n1, n2 at +0, +16, +32, +48
-    std::vector<int> counters;
-};
+// The one place that knows a run's arena block: the counters (64 ints per source: counters, thr1, n1, n2 at +0, +16, +32, +48), the
+// sources' ROIs, the uploaded records
+void orb_run_layout(ArenaWalk &a, OrbRun *run, const StripTable::Strip *S, int n, const vfsms_orb_params *p, int cap1, int cap2, int cap)
+{
+    run->R.resize(n);
+    run->cblock = a.take<int>(64 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        OrbDev &r = run->R[i];
+        orb_roi_layout(a, &r, S[i].p, S[i].stride, S[i].h, S[i].w, p, cap1, cap2, cap);
+        if (run->cblock) { r.counters = run->cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48; }
+    }
+    run->dR = a.take<OrbDev>(n);
+}
 static size_t orb_run_bytes(const vfsms_orb_params *p, const StripTable::Strip *S, int n, int cap1, int cap2, int cap)
 {
-    size_t need = 0;
-    for (int i = 0; i < n; i++) need += orb_roi_bytes(p, S[i].h, S[i].w, cap1, cap2, cap);
-    return need + (sizeof(OrbDev) + sizeof(int) * 64) * (size_t)n + 1024;     // the records, the counters, their alignment
+    ArenaWalk a; OrbRun run; orb_run_layout(a, &run, S, n, p, cap1, cap2, cap); return a.off;
 }
 static int orb_run_carve(vfsms_ctx *ctx, OrbRun *run, const StripTable::Strip *S, int n, const vfsms_orb_params *p, int cap1, int cap2, int cap)
 {
-    run->R.resize(n);
-    run->cblock = (int *)ctx_arena_alloc(ctx, sizeof(int) * 64 * n);
-    if (!run->cblock) { vfsms_set_error("arena exhausted (ORB counters)"); return VFSMS_ERR_CAPACITY; }
-    for (int i = 0; i < n; i++) {
-        OrbDev &r = run->R[i];
-        TRY(orb_roi_carve(ctx, &r, S[i].p, S[i].stride, S[i].h, S[i].w, p, cap1, cap2, cap));
-        r.counters = run->cblock + 64 * i; r.thr1 = r.counters + 16; r.n1 = r.counters + 32; r.n2 = r.counters + 48;
-    }
-    return ctx_upload_small(ctx, run->R.data(), sizeof(OrbDev) * n, (void **)&run->dR);
+    ArenaWalk a = ctx_arena_walk(ctx);
+    orb_run_layout(a, run, S, n, p, cap1, cap2, cap);
+    TRY(ctx_arena_commit(ctx, a, "arena exhausted while carving an ORB run"));
+    return ctx_copy_small(ctx, run->R.data(), sizeof(OrbDev) * n, run->dR);
 }
 // no prepare phase: k_orb_clear zeroes the counters
 static int orb_run_launch(vfsms_ctx *ctx, const OrbRun &run, const vfsms_orb_params *p) { return launch_orb(ctx, run.dR, run.R.data(), (int)run.R.size(), p); }

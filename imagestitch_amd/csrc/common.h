@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/vfsms.h"
+#include "arena_walk.h"
 
 #define VFSMS_MAX_LAYERS 32      // (nOctaveLayers + 2) * nOctaves
 #define VFSMS_MAX_WIN 768        // SURF descriptor window side upper bound (size <= 264 -> 739)
@@ -249,7 +250,9 @@ struct ProfScope {
 };
 
 int ctx_arena_reserve(vfsms_ctx *ctx, size_t bytes);             // ensure capacity (may sync + realloc), reset offset
-void *ctx_arena_alloc(vfsms_ctx *ctx, size_t bytes, size_t align = 256);
+void *ctx_arena_alloc(vfsms_ctx *ctx, size_t bytes, size_t align = 256);   // one-off allocations; a record's arrays come from its layout function:
+ArenaWalk ctx_arena_walk(vfsms_ctx *ctx);                        // a carving walk that starts where the arena stands
+int ctx_arena_commit(vfsms_ctx *ctx, const ArenaWalk &a, const char *what);   // move the arena behind a walk that fitted; else `what` is the error, VFSMS_ERR_CAPACITY
 int ctx_prepare_surf(vfsms_ctx *ctx, const vfsms_surf_params *p);
 
 // ---- runs of consecutive records of one shape -----------------------------------------------------------------
@@ -271,9 +274,10 @@ static std::vector<ShapeRun> shape_runs(const Rec *recs, int n)
 
 // ---- kernel launchers (each is stream-ordered, no host sync) --------------------------------------------
 // surf_kernels.hip
-size_t surf_roi_bytes(int h, int w, int cap, int nlayers_total, int noctaves, int dim);
-int surf_roi_carve(vfsms_ctx *ctx, RoiDev *r, const uint8_t *img, int stride, int h, int w, int cap,
-                   const vfsms_surf_params *p);
+// every record's device arrays are described ONCE, by X_layout(ArenaWalk &, XDev *, shape): X_bytes counts with it, X_carve carves with it
+void surf_roi_layout(ArenaWalk &a, RoiDev *r, const uint8_t *img, int stride, int h, int w, int cap, const vfsms_surf_params *p);
+struct DescWork { int *tickets; DescPlan *plan; DescRec *rec_big, *rec_small; };     // the work list of one describe launch
+void surf_describe_layout(ArenaWalk &a, DescWork *d, size_t capsum);
 int launch_integral(vfsms_ctx *ctx, const RoiDev *d_rois, int nrois, int maxh, int maxw);
 size_t integral_carry_bytes(int h, int w);
 int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_rois, int nrois,
@@ -281,6 +285,8 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
 int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_rois, int nrois,
                          const vfsms_surf_params *p);
 // match_kernels.hip
+void match_layout(ArenaWalk &a, MatchDev *m, int capq, int dim, int nsplit);
+void match_filter_layout(ArenaWalk &a, MatchDev *m, int capq, int capt, int cns);
 size_t match_bytes(int capq, int nsplit);
 int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit);
 int launch_max_norm2_d64(vfsms_ctx *ctx, const float *a, int n, unsigned *d_out);
@@ -311,14 +317,16 @@ int launch_adjust_search(vfsms_ctx *ctx, const AdjJob *d_jobs, const AdjJob *h_j
                          unsigned long long *d_sums, int32_t *d_best4, int32_t *d_surface);
 // orb_kernels.hip
 int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p);
-size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2, int cap);
-int orb_roi_carve(vfsms_ctx *ctx, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p,
-                  int cap1, int cap2, int cap);
+void orb_roi_layout(ArenaWalk &a, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p, int cap1, int cap2, int cap);
 int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int nrois, const vfsms_orb_params *p);
 // phase_kernels.hip
 int phase_correlate_device(vfsms_ctx *ctx, const uint8_t *a, int stride_a, const uint8_t *b, int stride_b,
                            int h, int w, double *d_out3);
 int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink = nullptr);
+// scratch of a batch (the spectra, partial maxima and job records are typed in phase_kernels.hip); work: rocFFT's, when its plans ask for one
+struct PhaseScratch { double *RE; void *FQ, *CP; uint8_t *TB; void *partial; PhasePeak *ppart; void *jobs; void *work; size_t work_bytes; };
+int phase_layout(vfsms_ctx *ctx, ArenaWalk &a, PhaseScratch *s, int h, int w, int nb, int K);
+void phase_peaks_layout(ArenaWalk &a, PhaseScratch *s, int h, int w, int nb, int K);
 int phase_bytes(vfsms_ctx *ctx, int h, int w, int nb, size_t *bytes);
 size_t phase_peaks_bytes(int h, int w, int nb, int K);            // what a batch with a sink takes from the arena beyond phase_bytes
 void phase_surface_size(int h, int w, int *M, int *N);            // the padded size of the surface of an h x w strip, in the strip's own orientation
@@ -329,8 +337,10 @@ size_t phase_resolve_sums_bytes(int njobs, int K);
 int launch_phase_resolve(vfsms_ctx *ctx, const PhaseJobHost *d_jobs, const PhasePeak *d_peaks, int njobs, int K, int oM, int oN, int h, int w,
                          double threshold, int min_pixels, unsigned long long *d_sums, int32_t *d_rows, int32_t *d_cands, int32_t *d_peaks_out);
 int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);   // launch records through the pinned staging buffer
+int ctx_copy_small(vfsms_ctx *ctx, const void *src, size_t bytes, void *d);      // the same into an array a layout walk took
 // enhance_kernels.hip
 int enhance_check_args(const char *who, int mode, int tiles);
+void enhance_layout(ArenaWalk &a, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles);
 size_t enhance_scratch_bytes(int h, int w, int mode, int tiles);
 int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles);
 int launch_enhance(vfsms_ctx *ctx, const EnhJob *d_jobs, const EnhJob *h_jobs, int n, int mode, double clip_limit, int tiles);
@@ -388,6 +398,8 @@ static inline size_t sift_pad_rows(int n) { return ((size_t)n + 63) & ~(size_t)6
 void sift_pool_reset(vfsms_ctx *ctx);
 void sift_pool_free(vfsms_ctx *ctx);
 void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes);
+struct SiftStripDev { float *pyr, *t0, *t1; int *counts; };     // one strip's block of ctx->sift_scratch
+void sift_strip_layout(ArenaWalk &a, SiftStripDev *d, size_t pyr_floats, size_t max_plane, int nslots);
 int sift_group_strips(vfsms_ctx *ctx, int h, int w, const vfsms_sift_params *p, int *g_out);
 int sift_group_device(vfsms_ctx *ctx, const SiftSrcHost *srcs, int g, int h, int w, const vfsms_sift_params *p, int *counts,
                       SiftStripOut *out, const vfsms_keypoint **kp_tmp);
@@ -395,6 +407,42 @@ int sift_detect_describe_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int
                                 float *kps_xy, float *desc, vfsms_keypoint *kps_full, int cap, int *n_out);
 int sift_pyramid_device(vfsms_ctx *ctx, const uint8_t *d_img, int h, int w, const vfsms_sift_params *p,
                         float *gauss, float *dog, size_t cap_floats, int32_t *shapes, int shapes_cap, int *n_oct);
+
+// ---- runs (api.hip): n sources or jobs in fused launches, their device arrays one block of the arena ---------------------------------
+struct SurfSrc { const uint8_t *p; int stride, h, w, cap; };      // pixels on the device, keypoint capacity of the source
+struct SurfEnh { int mode; double clip_limit; int tile_grid; };   // equalizeHist / CLAHE before detection (mode 0: none)
+struct SurfRun {
+    std::vector<RoiDev> R; RoiDev *dR = nullptr;                  // host and device copies of the ROI records
+    std::vector<EnhJob> E; EnhJob *dE = nullptr;
+    int *cblock = nullptr;                                        // 16 counters per source, one contiguous block: one memset, one copy back
+    std::vector<int> counters;
+};
+struct StripTable {                                               // the distinct strips of a fused batch (api.hip: build_strip_table)
+    struct Strip { const uint8_t *p; int stride, h, w; };
+    std::vector<Strip> strips;               // distinct strips in launch order
+    std::vector<int> a, b;                   // per slot: its A / B strip
+    int u0 = 0;                              // strips of part 0 (the first u0)
+};
+struct MatchPlan { bool filtered; int ns, cns; };    // filtered: MFMA candidate filter (cns train splits) + exact verification; else ns splits
+struct MatchJob {
+    const float *q, *t, *kq, *kt;                    // descriptors and keypoint positions of the query and the train set
+    const int *nq_ptr, *nt_ptr;                      // their counts, on the device
+    int capq, capt;                                  // what the job's arrays are sized for
+    int row;                                         // the job's row of the result block
+    const int8_t *q8, *t8; const int *qn2, *tn2;     // optional: int8 rows and their norms (k_bf_i8_d128)
+    const StripTable::Strip *sa, *sb;                // optional: the raw pixels of the two strips, for the verifier behind the vote
+};
+struct MatchRun { MatchPlan P; int dim; std::vector<MatchDev> M; MatchDev *dM = nullptr; int32_t *rblock = nullptr; };
+struct OrbRun {
+    std::vector<OrbDev> R; OrbDev *dR = nullptr;                  // host and device copies of the ROI records
+    int *cblock = nullptr;                                        // 64 ints per source, one contiguous block
+    std::vector<int> counters;
+};
+void surf_run_layout(ArenaWalk &a, SurfRun *run, const SurfSrc *S, int n, const vfsms_surf_params *p, const SurfEnh &enh);
+void match_run_layout(ArenaWalk &a, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P);
+struct PhaseResolveDev { double *out3; PhasePeak *peaks; unsigned long long *sums; PhaseJobHost *jobs; };   // a phase_resolve group, ahead of phase_layout's scratch
+void phase_resolve_layout(ArenaWalk &a, PhaseResolveDev *d, int nb, int K);
+void orb_run_layout(ArenaWalk &a, OrbRun *run, const StripTable::Strip *S, int n, const vfsms_orb_params *p, int cap1, int cap2, int cap);
 
 #ifdef __HIPCC__
 // Speed only (placement is not a contract): workgroups are observed to land on XCD (linear block id % 8), each XCD with a private

@@ -155,23 +155,24 @@ int enhance_check_args(const char *who, int mode, int tiles)
     return VFSMS_OK;
 }
 
-size_t enhance_scratch_bytes(int h, int w, int mode, int tiles)
+// The one place that knows a job's record: a counting walk gives its bytes, a carving walk its device arrays -- the enhanced image
+// (contiguous h x w), its histograms and its LUTs
+void enhance_layout(ArenaWalk &a, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles)
 {
-    const int nt = mode == 2 ? tiles * tiles : 1;
-    return (((size_t)h * w + 255) & ~(size_t)255) + (((size_t)nt * 256 * 4 + 255) & ~(size_t)255) + (((size_t)nt * 256 + 255) & ~(size_t)255);
-}
-
-// Fill the device-side fields of one job: the enhanced image (contiguous h x w), its histograms and LUTs come out of the arena.
-int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles)
-{
-    const int nt = mode == 2 ? tiles * tiles : 1;
+    const size_t nt = mode == 2 ? (size_t)tiles * tiles : 1;
     J->src = src; J->stride = stride; J->h = h; J->w = w; J->eh = h; J->ew = w;
     if (mode == 2 && !(w % tiles == 0 && h % tiles == 0)) { J->eh = h + (tiles - h % tiles); J->ew = w + (tiles - w % tiles); }
-    J->dst = (uint8_t *)ctx_arena_alloc(ctx, (size_t)h * w);
-    J->hist = (int *)ctx_arena_alloc(ctx, (size_t)nt * 256 * sizeof(int));
-    J->lut = (uint8_t *)ctx_arena_alloc(ctx, (size_t)nt * 256);
-    if (!J->dst || !J->hist || !J->lut) { vfsms_set_error("arena exhausted (enhancement)"); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    J->dst = a.take<uint8_t>((size_t)h * w);
+    J->hist = a.take<int>(nt * 256);
+    J->lut = a.take<uint8_t>(nt * 256);
+}
+
+size_t enhance_scratch_bytes(int h, int w, int mode, int tiles) { ArenaWalk a; EnhJob J; enhance_layout(a, &J, nullptr, w, h, w, mode, tiles); return a.off; }
+int enhance_carve(vfsms_ctx *ctx, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles)
+{
+    ArenaWalk a = ctx_arena_walk(ctx);
+    enhance_layout(a, J, src, stride, h, w, mode, tiles);
+    return ctx_arena_commit(ctx, a, "arena exhausted (enhancement)");
 }
 
 // h_jobs: carved jobs (host copy); d_jobs: the same array on the device.  Stream-ordered, no host sync.

@@ -1034,34 +1034,31 @@ __global__ __launch_bounds__(256) void k_hamming_merge(const MatchDev *jobs, int
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t match_bytes(int capq, int nsplit)
-{
-    size_t b = 3 * al(sizeof(float) * (size_t)capq * nsplit);
-    b += 3 * al(sizeof(float) * capq) + 2 * al(sizeof(int) * capq);
-    b += al(sizeof(int32_t) * 2 * capq) + al(sizeof(int32_t) * 4 * capq) + al(64) + al(64) + al(64);
-    return b + 4096;
-}
-
-int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit)
+// The one place that knows a match job's device arrays: a counting walk gives their bytes (match_bytes), a carving walk the arrays
+void match_layout(ArenaWalk &a, MatchDev *m, int capq, int dim, int nsplit)
 {
     m->capq = capq; m->dim = dim; m->nsplit = nsplit;
-    m->p_d1 = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)capq * nsplit);
-    m->p_d2 = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)capq * nsplit);
-    m->p_i1 = (int *)ctx_arena_alloc(ctx, sizeof(int) * (size_t)capq * nsplit);
-    m->d1 = (float *)ctx_arena_alloc(ctx, sizeof(float) * capq);
-    m->d2 = (float *)ctx_arena_alloc(ctx, sizeof(float) * capq);
-    m->i1 = (int *)ctx_arena_alloc(ctx, sizeof(int) * capq);
-    m->match_flag = (int *)ctx_arena_alloc(ctx, sizeof(int) * capq);
-    m->match_pos = (int *)ctx_arena_alloc(ctx, sizeof(int) * capq);
-    m->pairs = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 2 * capq);
-    m->votes = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * capq);
-    m->mcount = (int *)ctx_arena_alloc(ctx, 64);
-    m->vsum = (unsigned long long *)ctx_arena_alloc(ctx, 64);
-    m->result = (int32_t *)ctx_arena_alloc(ctx, 64);
-    if (!m->result) { vfsms_set_error("arena exhausted while carving a match job"); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    m->p_d1 = a.take<float>((size_t)capq * nsplit);
+    m->p_d2 = a.take<float>((size_t)capq * nsplit);
+    m->p_i1 = a.take<int>((size_t)capq * nsplit);
+    m->d1 = a.take<float>(capq);
+    m->d2 = a.take<float>(capq);
+    m->i1 = a.take<int>(capq);
+    m->match_flag = a.take<int>(capq);
+    m->match_pos = a.take<int>(capq);
+    m->pairs = a.take<int32_t>(2 * (size_t)capq);
+    m->votes = a.take<int32_t>(4 * (size_t)capq);
+    m->mcount = a.take<int>(16);
+    m->vsum = a.take<unsigned long long>(8);
+    m->result = a.take<int32_t>(16);              // a run points the job at its row of the run's result block instead (api.hip)
+}
+
+size_t match_bytes(int capq, int nsplit) { ArenaWalk a; MatchDev m; match_layout(a, &m, capq, 0, nsplit); return a.off; }
+int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit)
+{
+    ArenaWalk a = ctx_arena_walk(ctx);
+    match_layout(a, m, capq, dim, nsplit);
+    return ctx_arena_commit(ctx, a, "arena exhausted while carving a match job");
 }
 
 // largest squared row norm of an n x 64 array (one wave per row): decides whether host-supplied descriptors qualify
@@ -1084,22 +1081,22 @@ int launch_max_norm2_d64(vfsms_ctx *ctx, const float *a, int n, unsigned *d_out)
     return VFSMS_OK;
 }
 
-size_t match_filter_bytes(int capq, int capt, int cns)
+// The device arrays of a job's MFMA candidate filter, likewise
+void match_filter_layout(ArenaWalk &a, MatchDev *m, int capq, int capt, int cns)
 {
-    return al(sizeof(uint2) * (size_t)capq * cns * 2 * BFM_CAPL) + al(sizeof(int) * (size_t)capq * cns * 2) +
-           al(sizeof(unsigned short) * BF16_ROW * (size_t)capq) + al(sizeof(h8v) * BF16_TILE * ((size_t)capt / 32 + 1)) +
-           al(sizeof(float2) * (size_t)capq * cns * 2) + 1024;
+    m->c_ent = a.take<uint2>((size_t)capq * cns * 2 * BFM_CAPL);
+    m->c_cnt = a.take<int>((size_t)capq * cns * 2);
+    m->q16 = a.take<unsigned short>(BF16_ROW * (size_t)capq);
+    m->t16 = (unsigned short *)a.take<h8v>(BF16_TILE * ((size_t)capt / 32 + 1));      // whole 32-train tiles
+    m->c_m12 = a.take<float2>((size_t)capq * cns * 2);
 }
 
+size_t match_filter_bytes(int capq, int capt, int cns) { ArenaWalk a; MatchDev m; match_filter_layout(a, &m, capq, capt, cns); return a.off; }
 int match_filter_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int capt, int cns)
 {
-    m->c_ent = (uint2 *)ctx_arena_alloc(ctx, sizeof(uint2) * (size_t)capq * cns * 2 * BFM_CAPL);
-    m->c_cnt = (int *)ctx_arena_alloc(ctx, sizeof(int) * (size_t)capq * cns * 2);
-    m->q16 = (unsigned short *)ctx_arena_alloc(ctx, sizeof(unsigned short) * BF16_ROW * (size_t)capq);
-    m->t16 = (unsigned short *)ctx_arena_alloc(ctx, sizeof(h8v) * BF16_TILE * ((size_t)capt / 32 + 1));   // whole 32-train tiles
-    m->c_m12 = (float2 *)ctx_arena_alloc(ctx, sizeof(float2) * (size_t)capq * cns * 2);
-    if (!m->c_cnt || !m->t16 || !m->c_m12) { vfsms_set_error("arena exhausted while carving a match filter"); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    ArenaWalk a = ctx_arena_walk(ctx);
+    match_filter_layout(a, m, capq, capt, cns);
+    return ctx_arena_commit(ctx, a, "arena exhausted while carving a match filter");
 }
 
 static bool bf_f32_filter()

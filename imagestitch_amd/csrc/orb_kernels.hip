@@ -555,8 +555,6 @@ __global__ __launch_bounds__(256) void k_orb_describe(const OrbDev *rois, int nl
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int orb_level_dims(const vfsms_orb_params *p, int h, int w, int *lw, int *lh, float *lscale)
 {
     for (int l = 0; l < p->n_levels; l++) {
@@ -567,20 +565,9 @@ int orb_level_dims(const vfsms_orb_params *p, int h, int w, int *lw, int *lh, fl
     return VFSMS_OK;
 }
 
-size_t orb_roi_bytes(const vfsms_orb_params *p, int h, int w, int cap1, int cap2, int cap)
-{
-    int lw[VFSMS_ORB_MAX_LEVELS], lh[VFSMS_ORB_MAX_LEVELS]; float ls[VFSMS_ORB_MAX_LEVELS];
-    orb_level_dims(p, h, w, lw, lh, ls);
-    size_t b = 0;
-    for (int l = 0; l < p->n_levels; l++) b += 4 * al((size_t)(lw[l] > 0 ? lw[l] : 1) * (lh[l] > 0 ? lh[l] : 1));
-    b += al(sizeof(int) * 256 * p->n_levels) + al(256);
-    b += p->n_levels * (al(sizeof(int) * 2 * cap1) + al(sizeof(float) * cap1) + al(sizeof(int) * 2 * cap2) + 2 * al(sizeof(float) * cap2));
-    b += al(sizeof(float) * 2 * cap) + al((size_t)32 * cap) + al(sizeof(vfsms_keypoint) * cap);
-    return b + 8192;
-}
-
-int orb_roi_carve(vfsms_ctx *ctx, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p,
-                  int cap1, int cap2, int cap)
+// The one place that knows an ORB ROI's record: a counting walk gives its bytes, a carving walk its device arrays.  The counters block
+// (counters, thr1, n1, n2) belongs to the run (api.hip), one block for all its ROIs.
+void orb_roi_layout(ArenaWalk &a, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p, int cap1, int cap2, int cap)
 {
     memset(r, 0, sizeof(*r));
     r->h = h; r->w = w; r->cap1 = cap1; r->cap2 = cap2; r->cap = cap;
@@ -588,24 +575,20 @@ int orb_roi_carve(vfsms_ctx *ctx, OrbDev *r, const uint8_t *img, int stride, int
     for (int l = 0; l < p->n_levels; l++) {
         const size_t n = (size_t)(r->lw[l] > 0 ? r->lw[l] : 1) * (r->lh[l] > 0 ? r->lh[l] : 1);
         if (l == p->first_level) { r->lv[l] = const_cast<uint8_t *>(img); r->ls[l] = stride; }
-        else { r->lv[l] = (uint8_t *)ctx_arena_alloc(ctx, n); r->ls[l] = r->lw[l]; }
-        r->bl[l] = (uint8_t *)ctx_arena_alloc(ctx, n);
-        r->score[l] = (uint8_t *)ctx_arena_alloc(ctx, n);
-        r->nms[l] = (uint8_t *)ctx_arena_alloc(ctx, n);
+        else { r->lv[l] = a.take<uint8_t>(n); r->ls[l] = r->lw[l]; }
+        r->bl[l] = a.take<uint8_t>(n);
+        r->score[l] = a.take<uint8_t>(n);
+        r->nms[l] = a.take<uint8_t>(n);
     }
-    r->hist = (int *)ctx_arena_alloc(ctx, sizeof(int) * 256 * p->n_levels);
-    r->counters = (int *)ctx_arena_alloc(ctx, 64 * sizeof(int));
-    r->thr1 = r->counters + 16; r->n1 = r->counters + 32; r->n2 = r->counters + 48;
-    r->k1_xy = (int *)ctx_arena_alloc(ctx, sizeof(int) * 2 * (size_t)cap1 * p->n_levels);
-    r->k1_resp = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)cap1 * p->n_levels);
-    r->k2_xy = (int *)ctx_arena_alloc(ctx, sizeof(int) * 2 * (size_t)cap2 * p->n_levels);
-    r->k2_resp = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)cap2 * p->n_levels);
-    r->k2_angle = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)cap2 * p->n_levels);
-    r->kps_xy = (float *)ctx_arena_alloc(ctx, sizeof(float) * 2 * cap);
-    r->desc = (uint8_t *)ctx_arena_alloc(ctx, (size_t)32 * cap);
-    r->kps_out = (vfsms_keypoint *)ctx_arena_alloc(ctx, sizeof(vfsms_keypoint) * cap);
-    if (!r->kps_out) { vfsms_set_error("arena exhausted while carving an ORB ROI"); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    r->hist = a.take<int>((size_t)256 * p->n_levels);
+    r->k1_xy = a.take<int>(2 * (size_t)cap1 * p->n_levels);
+    r->k1_resp = a.take<float>((size_t)cap1 * p->n_levels);
+    r->k2_xy = a.take<int>(2 * (size_t)cap2 * p->n_levels);
+    r->k2_resp = a.take<float>((size_t)cap2 * p->n_levels);
+    r->k2_angle = a.take<float>((size_t)cap2 * p->n_levels);
+    r->kps_xy = a.take<float>(2 * (size_t)cap);
+    r->desc = a.take<uint8_t>((size_t)32 * cap);
+    r->kps_out = a.take<vfsms_keypoint>(cap);
 }
 
 int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int nrois, const vfsms_orb_params *p)
@@ -615,7 +598,7 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
     int maxcap1 = 0, maxcap2 = 0;
     for (int r = 0; r < nrois; r++) { maxcap1 = std::max(maxcap1, h_rois[r].cap1); maxcap2 = std::max(maxcap2, h_rois[r].cap2); }
     // The kernels whose grid is cut from the image size are launched once per run of consecutive ROIs of one shape (common.h: shape_runs); a
-    // run's level sizes are those of its first record (orb_roi_carve).  An ORB run of api.hip hands over one image (vfsms_orb_detect_describe)
+    // run's level sizes are those of its first record (orb_roi_layout).  An ORB run of api.hip hands over one image (vfsms_orb_detect_describe)
     // or the distinct strips of a batch in shape order (vfsms_attempt_orb_batch).
     const std::vector<ShapeRun> runs = shape_runs(h_rois, nrois);
     hipLaunchKernelGGL(k_orb_clear, dim3(nrois), dim3(256), 0, ctx->stream, d_rois, nl);

@@ -716,8 +716,6 @@ int phase_destroy_plans(vfsms_ctx *ctx)
     return VFSMS_OK;
 }
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // rocFFT plans are cached per (M, N, batch): the registrar's speculative batches come in every size from 1 to 32, and a plan costs tens
 // of milliseconds to create -- inside a timed call.  Batches are therefore rounded up to ten sizes; the surplus transforms run over
 // scratch planes nobody reads (the pad / cross-power / arg-max kernels only cover the real jobs).
@@ -843,15 +841,49 @@ extern "C" int vfsms_phase_plan(int h, int w, int32_t *info8)
     return VFSMS_OK;
 }
 
-static size_t own_bytes(const OwnShape &S, int h, int w, int nb)
+// the jobs of a batch run in chunks of at most this many; VFSMS_PHASE_CHUNK lowers it on the LDS path
+static int own_chunk(int nb) { return std::min(nb, std::max(1, std::min(PHASE_MAX_CHUNK, env_int("VFSMS_PHASE_CHUNK", PHASE_MAX_CHUNK)))); }
+
+// the peak scan's per-chunk partial lists (launch_phase_peaks), in either path: c jobs of SM stored rows
+static void peaks_layout(ArenaWalk &a, PhaseScratch *s, int c, int SM, int K) { s->ppart = a.take<PhasePeak>((size_t)c * phase_peaks_blocks(SM) * K); }
+
+// The one place that knows the scratch of a batch of nb jobs of one strip shape, in either path (phase_bytes counts with it,
+// phase_correlate_batch_device carves with it).  K > 0: with the partial lists of a peak sink.  The LDS path does not look at ctx.
+int phase_layout(vfsms_ctx *ctx, ArenaWalk &a, PhaseScratch *s, int h, int w, int nb, int K)
 {
-    const size_t c = (size_t)std::min(nb, PHASE_MAX_CHUNK);
-    const size_t cpl = sizeof(cplx) * (size_t)S.M * (((S.H + 1 + S.C - 1) / S.C) * S.C);
-    return al256(c * sizeof(double) * S.M * S.N) + al256(2 * c * cpl) + al256(c * cpl) + al256(2 * c * (size_t)h * w) + al256(sizeof(PhaseJob) * 2 * nb) +
-           al256(sizeof(ArgMax) * c * S.M) + 65536;
+    memset(s, 0, sizeof(*s));
+    OwnShape S;
+    if (phase_own_shape(h, w, &S)) {
+        const size_t c = (size_t)own_chunk(nb);
+        const size_t cpl = (size_t)S.M * (((S.H + 1 + S.C - 1) / S.C) * S.C);                      // spectra in column tiles of C
+        s->RE = a.take<double>(c * S.M * S.N);
+        s->FQ = a.take<cplx>(2 * c * cpl);
+        s->CP = a.take<cplx>(c * cpl);
+        if (S.tr) s->TB = a.take<uint8_t>(2 * c * h * w);
+        s->partial = a.take<ArgMax>(c * ((S.M + S.RPW - 1) / S.RPW));
+        if (K) peaks_layout(a, s, (int)c, S.M, K);
+        s->jobs = a.take<PhaseJob>((size_t)nb + (S.tr ? c : 0));     // the caller's strips, then (transposed) the chunk's scratch copies
+        return VFSMS_OK;
+    }
+    const int M = optimal_dft_size(h), N = optimal_dft_size(w);
+    const size_t c = (size_t)plan_batch(std::min(nb, PHASE_MAX_CHUNK)), cpl = (size_t)M * (N / 2 + 1);
+    size_t wbytes = 0;                                                  // one work buffer serves every chunk: the largest its (cached) plans ask for
+    for (int left = nb; left > 0; left -= std::min(left, PHASE_MAX_CHUNK)) {
+        FftPlan *P;
+        TRY(get_plan(ctx, M, N, plan_batch(std::min(left, PHASE_MAX_CHUNK)), &P));
+        wbytes = std::max(wbytes, std::max(P->fwd_work, P->inv_work));
+    }
+    s->RE = a.take<double>(2 * c * M * N);
+    s->FQ = a.take<cplx>(2 * c * cpl);
+    s->CP = a.take<cplx>(c * cpl);
+    s->partial = a.take<ArgMax>(PHASE_NBLK * c);
+    s->jobs = a.take<PhaseJob>(nb);
+    if (K) peaks_layout(a, s, (int)c, M, K);
+    if (wbytes) { s->work = a.take<char>(wbytes); s->work_bytes = wbytes; }
+    return VFSMS_OK;
 }
 
-static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink)
+static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseScratch &sc, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink)
 {
     if (ctx->fft_tabs.empty()) {                               // first use on this context (= this device): > 64 KB of dynamic LDS must be asked for
         HIP_TRY(hipFuncSetAttribute((const void *)k_phase_rows_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, PHASE_LDS_MAX));
@@ -859,24 +891,17 @@ static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost
         HIP_TRY(hipFuncSetAttribute((const void *)k_phase_rows_inv, hipFuncAttributeMaxDynamicSharedMemorySize, PHASE_LDS_MAX));
     }
     const int M = S.M, N = S.N, Nc = S.H + 1;
-    const int cmax = std::min(nb, std::max(1, std::min(PHASE_MAX_CHUNK, env_int("VFSMS_PHASE_CHUNK", PHASE_MAX_CHUNK))));
-    const size_t real = (size_t)M * N, cpl = (size_t)M * (((Nc + S.C - 1) / S.C) * S.C);          // spectra in column tiles of C
+    const int cmax = own_chunk(nb);
     const int nparts = (M + S.RPW - 1) / S.RPW;
-    double *RE = (double *)ctx_arena_alloc(ctx, sizeof(double) * cmax * real);
-    cplx *FQ = (cplx *)ctx_arena_alloc(ctx, sizeof(cplx) * 2 * cmax * cpl);
-    cplx *CP = (cplx *)ctx_arena_alloc(ctx, sizeof(cplx) * cmax * cpl);
-    uint8_t *TB = S.tr ? (uint8_t *)ctx_arena_alloc(ctx, 2 * (size_t)cmax * h * w) : nullptr;
-    ArgMax *partial = (ArgMax *)ctx_arena_alloc(ctx, sizeof(ArgMax) * cmax * nparts);
-    PhasePeak *ppart = sink ? (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)cmax * phase_peaks_blocks(M) * sink->K) : nullptr;
-    if (!RE || !FQ || !CP || !partial || (S.tr && !TB) || (sink && !ppart)) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
+    double *RE = sc.RE; cplx *FQ = (cplx *)sc.FQ, *CP = (cplx *)sc.CP; uint8_t *TB = sc.TB; ArgMax *partial = (ArgMax *)sc.partial; PhasePeak *ppart = sc.ppart;
     // job records: the caller's strips, then (transposed orientation) the scratch copies the row kernel reads instead, chunk-relative
     std::vector<PhaseJob> hj((size_t)nb + (S.tr ? cmax : 0));
     for (int k = 0; k < nb; k++) { hj[k].a = jobs[k].a; hj[k].b = jobs[k].b; hj[k].sa = jobs[k].sa; hj[k].sb = jobs[k].sb; }
     for (int k = 0; S.tr && k < cmax; k++) {
         hj[nb + k].a = TB + (size_t)(2 * k) * h * w; hj[nb + k].b = TB + (size_t)(2 * k + 1) * h * w; hj[nb + k].sa = h; hj[nb + k].sb = h;
     }
-    PhaseJob *dj = nullptr;
-    TRY(ctx_upload_small(ctx, hj.data(), sizeof(PhaseJob) * hj.size(), (void **)&dj));
+    PhaseJob *dj = (PhaseJob *)sc.jobs;
+    TRY(ctx_copy_small(ctx, hj.data(), sizeof(PhaseJob) * hj.size(), dj));
     const cplx *tabN = nullptr, *tabM = nullptr;
     TRY(get_tab(ctx, N, &tabN));
     TRY(get_tab(ctx, M, &tabM));
@@ -911,32 +936,20 @@ static int phase_own_batch(vfsms_ctx *ctx, const OwnShape &S, const PhaseJobHost
 // arena bytes for nb attempts of one ROI size; the rocFFT work buffer is whatever the (cached) plans of the chunks ask for
 int phase_bytes(vfsms_ctx *ctx, int h, int w, int nb, size_t *bytes)
 {
-    OwnShape own;
-    if (phase_own_shape(h, w, &own)) { *bytes = own_bytes(own, h, w, nb); return VFSMS_OK; }
-    const int M = optimal_dft_size(h), N = optimal_dft_size(w);
-    const size_t real = sizeof(double) * (size_t)M * N, cp = sizeof(double) * 2 * (size_t)M * (N / 2 + 1);
-    const size_t chunk = (size_t)plan_batch(std::min(nb, PHASE_MAX_CHUNK));
-    size_t wbytes = 0;
-    for (int left = nb; left > 0;) {
-        const int c = std::min(left, PHASE_MAX_CHUNK);
-        FftPlan *P;
-        TRY(get_plan(ctx, M, N, plan_batch(c), &P));
-        wbytes = std::max(wbytes, std::max(P->fwd_work, P->inv_work));
-        left -= c;
-    }
-    *bytes = al256(2 * chunk * real) + al256(2 * chunk * cp) + al256(chunk * cp) + al256(wbytes) +
-             al256(sizeof(PhaseJob) * nb) + al256(sizeof(ArgMax) * PHASE_NBLK * chunk) + 65536;
+    ArenaWalk a; PhaseScratch s;
+    TRY(phase_layout(ctx, a, &s, h, w, nb, 0));
+    *bytes = a.off;
     return VFSMS_OK;
 }
 
-// the peak scan's per-chunk partial lists (launch_phase_peaks), in either path
-size_t phase_peaks_bytes(int h, int w, int nb, int K)
+// the same lists on their own: what a batch with a sink takes beyond phase_bytes
+void phase_peaks_layout(ArenaWalk &a, PhaseScratch *s, int h, int w, int nb, int K)
 {
     OwnShape own;
-    const int SM = phase_own_shape(h, w, &own) ? own.M : optimal_dft_size(h);
-    const size_t c = (size_t)plan_batch(std::min(nb, PHASE_MAX_CHUNK));
-    return al256(sizeof(PhasePeak) * c * phase_peaks_blocks(SM) * K) + 256;
+    const bool lds = phase_own_shape(h, w, &own);
+    peaks_layout(a, s, lds ? own_chunk(nb) : plan_batch(std::min(nb, PHASE_MAX_CHUNK)), lds ? own.M : optimal_dft_size(h), K);
 }
+size_t phase_peaks_bytes(int h, int w, int nb, int K) { ArenaWalk a; PhaseScratch s; phase_peaks_layout(a, &s, h, w, nb, K); return a.off; }
 void phase_surface_size(int h, int w, int *M, int *N) { *M = optimal_dft_size(h); *N = optimal_dft_size(w); }
 
 // nb attempts of one ROI size h x w.  jobs: HOST array of device pointers / strides.  d_out3: device double[3 * nb].
@@ -944,42 +957,26 @@ void phase_surface_size(int h, int w, int *M, int *N) { *M = optimal_dft_size(h)
 int phase_correlate_batch_device(vfsms_ctx *ctx, const PhaseJobHost *jobs, int nb, int h, int w, double *d_out3, const PhasePeakSink *sink)
 {
     if (nb <= 0) return VFSMS_OK;
+    ArenaWalk a = ctx_arena_walk(ctx);
+    PhaseScratch sc;
+    TRY(phase_layout(ctx, a, &sc, h, w, nb, sink ? sink->K : 0));
+    TRY(ctx_arena_commit(ctx, a, "arena exhausted in phase correlation"));
     OwnShape own;
-    if (phase_own_shape(h, w, &own)) return phase_own_batch(ctx, own, jobs, nb, h, w, d_out3, sink);
+    if (phase_own_shape(h, w, &own)) return phase_own_batch(ctx, own, sc, jobs, nb, h, w, d_out3, sink);
     const int M = optimal_dft_size(h), N = optimal_dft_size(w);
     const int Nc = N / 2 + 1;
-    const size_t real = (size_t)M * N, cpl = (size_t)M * Nc;
-    const int cmax = plan_batch(std::min(nb, PHASE_MAX_CHUNK));
-    double *RE = (double *)ctx_arena_alloc(ctx, sizeof(double) * 2 * cmax * real);
-    cplx *FQ = (cplx *)ctx_arena_alloc(ctx, sizeof(cplx) * 2 * cmax * cpl);
-    cplx *CP = (cplx *)ctx_arena_alloc(ctx, sizeof(cplx) * cmax * cpl);
-    ArgMax *partial = (ArgMax *)ctx_arena_alloc(ctx, sizeof(ArgMax) * PHASE_NBLK * cmax);
+    double *RE = sc.RE; cplx *FQ = (cplx *)sc.FQ, *CP = (cplx *)sc.CP; ArgMax *partial = (ArgMax *)sc.partial; PhasePeak *ppart = sc.ppart;
     std::vector<PhaseJob> hj(nb);
     for (int k = 0; k < nb; k++) { hj[k].a = jobs[k].a; hj[k].b = jobs[k].b; hj[k].sa = jobs[k].sa; hj[k].sb = jobs[k].sb; }
-    PhaseJob *dj = nullptr;
-    TRY(ctx_upload_small(ctx, hj.data(), sizeof(PhaseJob) * nb, (void **)&dj));
-    PhasePeak *ppart = sink ? (PhasePeak *)ctx_arena_alloc(ctx, sizeof(PhasePeak) * (size_t)cmax * phase_peaks_blocks(M) * sink->K) : nullptr;
-    if (!RE || !FQ || !CP || !partial || (sink && !ppart)) { vfsms_set_error("arena exhausted in phase correlation"); return VFSMS_ERR_CAPACITY; }
-    // chunks of at most PHASE_MAX_CHUNK attempts: plans first, so one work buffer serves every chunk
-    std::vector<FftPlan *> chunks;
-    std::vector<int> chunk_jobs;
-    size_t wbytes = 0;
-    for (int left = nb; left > 0;) {
-        const int c = std::min(left, PHASE_MAX_CHUNK);
+    PhaseJob *dj = (PhaseJob *)sc.jobs;
+    TRY(ctx_copy_small(ctx, hj.data(), sizeof(PhaseJob) * nb, dj));
+    void *work = sc.work; const size_t wbytes = sc.work_bytes;                   // one work buffer serves every chunk
+    std::unique_ptr<ProfScope> whole(sink ? nullptr : new ProfScope(ctx, "phase"));      // as in phase_own_batch
+    for (int done = 0; done < nb;) {                                    // chunks of at most PHASE_MAX_CHUNK attempts
+        std::unique_ptr<ProfScope> chunk(sink ? new ProfScope(ctx, "phase") : nullptr);
+        const int c = std::min(nb - done, PHASE_MAX_CHUNK);             // real jobs; the plan transforms P->nb >= c planes
         FftPlan *P;
         TRY(get_plan(ctx, M, N, plan_batch(c), &P));
-        chunks.push_back(P); chunk_jobs.push_back(c);
-        wbytes = std::max(wbytes, std::max(P->fwd_work, P->inv_work));
-        left -= c;
-    }
-    void *work = wbytes ? ctx_arena_alloc(ctx, wbytes) : nullptr;
-    if (wbytes && !work) { vfsms_set_error("arena exhausted (rocFFT work buffer, %zu bytes)", wbytes); return VFSMS_ERR_CAPACITY; }
-    std::unique_ptr<ProfScope> whole(sink ? nullptr : new ProfScope(ctx, "phase"));      // as in phase_own_batch
-    int done = 0;
-    for (size_t ci = 0; ci < chunks.size(); ci++) {
-        std::unique_ptr<ProfScope> chunk(sink ? new ProfScope(ctx, "phase") : nullptr);
-        FftPlan *P = chunks[ci];
-        const int c = chunk_jobs[ci];                                   // real jobs; the plan transforms P->nb >= c planes
         hipLaunchKernelGGL(k_pad_u8_f64, dim3((N + 255) / 256, M, c), dim3(256), 0, ctx->stream, dj + done, h, w, M, N, RE);
         void *in[1] = {RE}, *outb[1] = {FQ};
         if (wbytes) rocfft_execution_info_set_work_buffer((rocfft_execution_info)P->fwd_info, work, wbytes);

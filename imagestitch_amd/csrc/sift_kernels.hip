@@ -618,8 +618,6 @@ static void sift_octs(const SiftPlan &P, float *pyr, SiftOcts *Os)
     }
 }
 
-static inline size_t sift_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- memory that outlives a group: chunks kept by the context, handed out by a bump pointer, all free again at the next call ----------
 void sift_pool_reset(vfsms_ctx *ctx) { for (auto &c : ctx->sift_pool) c.off = 0; }
 void sift_pool_free(vfsms_ctx *ctx)
@@ -629,7 +627,7 @@ void sift_pool_free(vfsms_ctx *ctx)
 }
 void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes)
 {
-    bytes = sift_align(bytes ? bytes : 1);
+    bytes = ((bytes ? bytes : 1) + 255) & ~(size_t)255;
     for (auto &c : ctx->sift_pool)
         if (c.off + bytes <= c.bytes) { void *r = c.p + c.off; c.off += bytes; return r; }
     SiftChunk c;
@@ -639,11 +637,17 @@ void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes)
     return c.p;
 }
 
-// bytes of one strip's block in ctx->sift_scratch: [pyramid][2 planes of the largest level][row counts + their scan]
-static size_t sift_strip_bytes(const SiftPlan &P)
+// The one place that knows one strip's block in ctx->sift_scratch: [pyramid][2 planes of the largest level][row counts + their scan],
+// padded to the distance between the blocks of two strips
+void sift_strip_layout(ArenaWalk &a, SiftStripDev *d, size_t pyr_floats, size_t max_plane, int nslots)
 {
-    return sift_align(P.pyr_floats * 4) + 2 * sift_align(P.max_plane * 4) + sift_align(((size_t)P.nslots + 1) * 8);
+    d->pyr = a.take<float>(pyr_floats);
+    d->t0 = a.take<float>(max_plane);
+    d->t1 = a.take<float>(max_plane);
+    d->counts = a.take<int>(2 * ((size_t)nslots + 1));
+    a.pad();
 }
+static size_t sift_strip_bytes(const SiftPlan &P) { ArenaWalk a; SiftStripDev d; sift_strip_layout(a, &d, P.pyr_floats, P.max_plane, P.nslots); return a.off; }
 
 // the pyramids of g strips of one shape into ctx->sift_scratch; *zs_out: floats (= ints) between the blocks of two strips
 static int sift_build_pyramid(vfsms_ctx *ctx, const SiftSrc *d_srcs, int g, int h, int w, const SiftPlan &P, float **pyr_out, int **counts_out,
@@ -651,11 +655,11 @@ static int sift_build_pyramid(vfsms_ctx *ctx, const SiftSrc *d_srcs, int g, int 
 {
     const size_t sb = sift_strip_bytes(P);
     TRY(sift_grow(&ctx->sift_scratch, &ctx->sift_scratch_bytes, sb * g + 4096, ctx->stream));
-    char *base = (char *)ctx->sift_scratch;
-    float *pyr = (float *)base; base += sift_align(P.pyr_floats * 4);
-    float *t0 = (float *)base; base += sift_align(P.max_plane * 4);
-    float *t1 = (float *)base; base += sift_align(P.max_plane * 4);
-    *counts_out = (int *)base;
+    ArenaWalk a{(char *)ctx->sift_scratch, 0, ctx->sift_scratch_bytes}; SiftStripDev d;
+    sift_strip_layout(a, &d, P.pyr_floats, P.max_plane, P.nslots);           // the first strip's; strip k's lies k * sb behind
+    if (!a.ok) { vfsms_set_error("sift: pyramid scratch too small"); return VFSMS_ERR_CAPACITY; }
+    float *pyr = d.pyr, *t0 = d.t0, *t1 = d.t1;
+    *counts_out = d.counts;
     *pyr_out = pyr;
     const size_t zs = sb / 4;
     *zs_out = zs;
@@ -778,19 +782,20 @@ int sift_group_device(vfsms_ctx *ctx, const SiftSrcHost *srcs, int g, int h, int
     }
     if (ncand == 0) return VFSMS_OK;
     const size_t nkp_max = ncand * SIFT_MAX_PEAKS;
-    const size_t kbytes = sift_align(sizeof(SiftCand) * ncand) + sift_align(sizeof(float) * nkp_max) + 2 * sift_align(sizeof(int) * (ncand + g)) +
-                          2 * sift_align(sizeof(vfsms_keypoint) * nkp_max) + 2 * sift_align(sizeof(int) * (nkp_max + g)) + 4096;
-    TRY(sift_grow(&ctx->sift_kp, &ctx->sift_kp_bytes, kbytes, st));
-    char *b = (char *)ctx->sift_kp;
-    auto take = [&](size_t bytes) { char *r = b; b += sift_align(bytes); return (void *)r; };
-    SiftCand *cand = (SiftCand *)take(sizeof(SiftCand) * ncand);
-    float *angles = (float *)take(sizeof(float) * nkp_max);
-    int *npk = (int *)take(sizeof(int) * (ncand + g));
-    int *kpos = (int *)take(sizeof(int) * (ncand + g));
-    vfsms_keypoint *kp0 = (vfsms_keypoint *)take(sizeof(vfsms_keypoint) * nkp_max);
-    vfsms_keypoint *kp1 = (vfsms_keypoint *)take(sizeof(vfsms_keypoint) * nkp_max);
-    int *keep = (int *)take(sizeof(int) * (nkp_max + g));
-    int *keep_pos = (int *)take(sizeof(int) * (nkp_max + g));
+    // the group's candidates and keypoints in ctx->sift_kp: one description, walked to size the buffer and to carve it
+    SiftCand *cand; float *angles; int *npk, *kpos, *keep, *keep_pos; vfsms_keypoint *kp0, *kp1;
+    auto kp_layout = [&](ArenaWalk &a) {
+        cand = a.take<SiftCand>(ncand); angles = a.take<float>(nkp_max);
+        npk = a.take<int>(ncand + g); kpos = a.take<int>(ncand + g);
+        kp0 = a.take<vfsms_keypoint>(nkp_max); kp1 = a.take<vfsms_keypoint>(nkp_max);
+        keep = a.take<int>(nkp_max + g); keep_pos = a.take<int>(nkp_max + g);
+    };
+    ArenaWalk count;
+    kp_layout(count);
+    TRY(sift_grow(&ctx->sift_kp, &ctx->sift_kp_bytes, count.off + 4096, st));
+    ArenaWalk a{(char *)ctx->sift_kp, 0, ctx->sift_kp_bytes};
+    kp_layout(a);
+    if (!a.ok) { vfsms_set_error("sift: keypoint scratch too small"); return VFSMS_ERR_CAPACITY; }
     SiftOcts *d_os; SiftSeg *d_segs;
     TRY(ctx_upload_small(ctx, &Os, sizeof(SiftOcts), (void **)&d_os));
     TRY(ctx_upload_small(ctx, segs.data(), sizeof(SiftSeg) * g, (void **)&d_segs));

@@ -1434,7 +1434,7 @@ __device__ __forceinline__ void stage_rows(const WinGeom &G, const float *sx_row
                 const int cx = inside[u] ? ix : rx, cy = inside[u] ? iy : ry;
                 // An inside sample has ix + 1 <= w - 1: its dword is the four taps, as in the interior rounds.  An outside sample only uses
                 // the low byte, pixel (cy, cx); at cx = w - 1 the dword runs into the next row's first element -- or, on the last row, into
-                // the 8 bytes of slack behind the pair image (surf_roi_carve) -- whose bytes are never looked at.
+                // the 8 bytes of slack behind the pair image (surf_roi_layout) -- whose bytes are never looked at.
                 top[u] = *(GAS const uint32_t *)(ubase + (((uint32_t)__umul24((uint32_t)cy, pw) + (uint32_t)cx) << 1));
             }
 #pragma unroll
@@ -2107,51 +2107,40 @@ __global__ __launch_bounds__(256) void k_desc_tail(const RoiDev *rois, const Sur
 // ---------------------------------------------------------------------------------------------------
 // host side: arena carving and launch sequences
 // ---------------------------------------------------------------------------------------------------
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t surf_roi_bytes(int h, int w, int cap, int nlayers_total, int noctaves, int dim)
-{
-    size_t b = al(sizeof(int32_t) * (size_t)(h + 1) * (w + 1)) + al(integral_carry_bytes(h, w)) + al(sizeof(uint16_t) * (size_t)h * w + 8);
-    int lpo = nlayers_total / noctaves;
-    for (int o = 0; o < noctaves; o++) {
-        size_t n = (size_t)(h >> o) * (w >> o);
-        b += lpo * al(sizeof(float) * (n ? n : 1));
-    }
-    b += al(16 * sizeof(int)) + al(sizeof(Cand) * cap) + al(sizeof(vfsms_keypoint) * cap) + al((size_t)cap * VFSMS_PATCH_ROW);
-    b += 2 * al(sizeof(int) * cap) + al(sizeof(float) * 2 * cap) + al(sizeof(float) * (size_t)cap * dim) + al(sizeof(vfsms_keypoint) * cap);
-    b += 2 * al(sizeof(DescRec) * (size_t)cap);               // this ROI's share of the launch's two record arrays (launch_surf_describe)
-    return b + 4096;
-}
-
-int surf_roi_carve(vfsms_ctx *ctx, RoiDev *r, const uint8_t *img, int stride, int h, int w, int cap,
-                   const vfsms_surf_params *p)
+// The one place that knows a SURF ROI's record: a counting walk gives its bytes, a carving walk its device arrays.  The counters belong
+// to the run (api.hip), one block for all its ROIs.
+void surf_roi_layout(ArenaWalk &a, RoiDev *r, const uint8_t *img, int stride, int h, int w, int cap, const vfsms_surf_params *p)
 {
     const int lpo = p->n_octave_layers + 2;
     memset(r, 0, sizeof(*r));
-    r->img = img; r->stride = stride; r->h = h; r->w = w; r->cap = cap;
-    r->sum = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * (size_t)(h + 1) * (w + 1));
-    r->ipitch = (w + 3) & ~3;
-    r->icarry = (int32_t *)ctx_arena_alloc(ctx, integral_carry_bytes(h, w));
-    r->pair = (uint16_t *)ctx_arena_alloc(ctx, sizeof(uint16_t) * (size_t)h * w + 8);
+    r->img = img; r->stride = stride; r->h = h; r->w = w; r->cap = cap; r->ipitch = (w + 3) & ~3;
+    r->sum = a.take<int32_t>((size_t)(h + 1) * (w + 1));
+    r->icarry = a.take<int32_t>(integral_carry_bytes(h, w) / sizeof(int32_t));
+    r->pair = a.take<uint16_t>((size_t)h * w + 4);
     int step = 1;
     for (int o = 0; o < p->n_octaves; o++) {
-        size_t n = (size_t)(h / step) * (w / step);
-        for (int l = 0; l < lpo; l++) {
-            r->det[o * lpo + l] = (float *)ctx_arena_alloc(ctx, sizeof(float) * (n ? n : 1));
-        }
+        const size_t n = (size_t)(h / step) * (w / step);
+        for (int l = 0; l < lpo; l++) r->det[o * lpo + l] = a.take<float>(n);
         step *= 2;
     }
-    r->counters = (int *)ctx_arena_alloc(ctx, 16 * sizeof(int));
-    r->cand = (Cand *)ctx_arena_alloc(ctx, sizeof(Cand) * cap);
-    r->kps = (vfsms_keypoint *)ctx_arena_alloc(ctx, sizeof(vfsms_keypoint) * cap);
-    r->patch = (uint8_t *)ctx_arena_alloc(ctx, (size_t)cap * VFSMS_PATCH_ROW);
-    r->keep_pos = (int *)ctx_arena_alloc(ctx, sizeof(int) * cap);
-    r->order = (int *)ctx_arena_alloc(ctx, sizeof(int) * cap);
-    r->kps_xy = (float *)ctx_arena_alloc(ctx, sizeof(float) * 2 * cap);
-    r->desc = (float *)ctx_arena_alloc(ctx, sizeof(float) * (size_t)cap * (p->extended ? 128 : 64));
-    r->kps_out = (vfsms_keypoint *)ctx_arena_alloc(ctx, sizeof(vfsms_keypoint) * cap);
-    if (!r->kps_out) { vfsms_set_error("arena exhausted while carving a SURF ROI"); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    r->cand = a.take<Cand>(cap);
+    r->kps = a.take<vfsms_keypoint>(cap);
+    r->patch = a.take<uint8_t>((size_t)cap * VFSMS_PATCH_ROW);
+    r->keep_pos = a.take<int>(cap);
+    r->order = a.take<int>(cap);
+    r->kps_xy = a.take<float>(2 * (size_t)cap);
+    r->desc = a.take<float>((size_t)cap * (p->extended ? 128 : 64));
+    r->kps_out = a.take<vfsms_keypoint>(cap);
+}
+
+// the work list of one describe launch over ROIs of `capsum` keypoints in all: ticket heads (8 counters per kernel, 256 B apart), the
+// launch's plan and its two record arrays
+void surf_describe_layout(ArenaWalk &a, DescWork *d, size_t capsum)
+{
+    d->tickets = a.take<int>(2 * DESC_HEADS * DESC_HEAD_STRIDE);
+    d->plan = a.take<DescPlan>(1);
+    d->rec_big = a.take<DescRec>(capsum);
+    d->rec_small = a.take<DescRec>(capsum);
 }
 
 int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_rois, int nrois,
@@ -2313,25 +2302,21 @@ int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_r
     }
     {
         ProfScope ps(ctx, "describe");
-        // ticket heads (8 counters per kernel, 256 B apart), the launch's plan and its two record arrays out of the call's arena (surf_roi_bytes
-        // counts the records of every ROI; callers reserve 64 KB of slack for the rest)
-        int *tickets = (int *)ctx_arena_alloc(ctx, sizeof(int) * 2 * DESC_HEADS * DESC_HEAD_STRIDE);
-        DescPlan *plan = (DescPlan *)ctx_arena_alloc(ctx, sizeof(DescPlan));
         size_t capsum = 0;
         for (int r = 0; r < nrois; r++) capsum += (size_t)h_rois[r].cap;
-        DescRec *rec_big = (DescRec *)ctx_arena_alloc(ctx, sizeof(DescRec) * capsum);
-        DescRec *rec_small = (DescRec *)ctx_arena_alloc(ctx, sizeof(DescRec) * capsum);
-        if (!tickets || !plan || !rec_big || !rec_small) { vfsms_set_error("arena exhausted (descriptor work list)"); return VFSMS_ERR_CAPACITY; }
-        HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(int) * 2 * DESC_HEADS * DESC_HEAD_STRIDE, ctx->stream));
+        ArenaWalk a = ctx_arena_walk(ctx); DescWork W;
+        surf_describe_layout(a, &W, capsum);
+        TRY(ctx_arena_commit(ctx, a, "arena exhausted (descriptor work list)"));
+        HIP_TRY(hipMemsetAsync(W.tickets, 0, sizeof(int) * 2 * DESC_HEADS * DESC_HEAD_STRIDE, ctx->stream));
         for (const ShapeRun &q : shape_runs(h_rois, nrois))
             hipLaunchKernelGGL(k_pair_rows, dim3((q.w + 1023) / 1024, q.h, q.count), dim3(256), 0, ctx->stream, d_rois + q.first);
         hipLaunchKernelGGL(k_desc_order, dim3(nrois), dim3(1024), 0, ctx->stream, d_rois);
-        hipLaunchKernelGGL(k_desc_plan, dim3(1), dim3(256), 0, ctx->stream, d_rois, nrois, plan, 256 * DESC_WGS);
-        hipLaunchKernelGGL(k_desc_recs, dim3((maxcap + 255) / 256, nrois), dim3(256), 0, ctx->stream, d_rois, plan, rec_big, rec_small, p->upright);
-        hipLaunchKernelGGL(k_describe, dim3(256 * DESC_WGS), dim3(256), 0, ctx->stream, d_rois, plan, rec_big, tickets,
+        hipLaunchKernelGGL(k_desc_plan, dim3(1), dim3(256), 0, ctx->stream, d_rois, nrois, W.plan, 256 * DESC_WGS);
+        hipLaunchKernelGGL(k_desc_recs, dim3((maxcap + 255) / 256, nrois), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_big, W.rec_small, p->upright);
+        hipLaunchKernelGGL(k_describe, dim3(256 * DESC_WGS), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_big, W.tickets,
                            ctx->d_tables, (const AreaRec *)ctx->d_area_tab, p->extended, p->upright);
-        hipLaunchKernelGGL(k_describe_small, dim3(256 * DESC_SMALL_WGS), dim3(256), 0, ctx->stream, d_rois, plan, rec_small,
-                           tickets + DESC_HEADS * DESC_HEAD_STRIDE, (const AreaRec *)ctx->d_area_tab, p->upright);
+        hipLaunchKernelGGL(k_describe_small, dim3(256 * DESC_SMALL_WGS), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_small,
+                           W.tickets + DESC_HEADS * DESC_HEAD_STRIDE, (const AreaRec *)ctx->d_area_tab, p->upright);
         hipLaunchKernelGGL(k_desc_tail, dim3((maxcap + 15) / 16, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_tables, p->extended);
     }
     HIP_TRY(hipGetLastError());
