@@ -95,6 +95,9 @@ _SIGNATURES = {
     "vfsms_tile_fill_jpeg": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]),
     "vfsms_jpeg_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vfsms_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vfsms_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vfsms_jpeg_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vfsms_canvas_encode_jpeg_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vfsms_jpeg_join": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vfsms_canvas_blend_tile_resident": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vfsms_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -1107,8 +1110,77 @@ class Engine:
             band = slot[:n * cols * ch].reshape(shape(n))
             yield r0, band, self._pyramid_rows(handle, r0, n, cols, ch, levels, band, slot[nb0:])
 
+    def jpeg_encode_device(self, img, bgr=True, quality=95, restart_mcus=0):
+        """vfsms_jpeg_encode_device: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> a complete baseline JPEG as a u8
+        array, encoded on the device: the bytes of tests/jpeg_enc_ref.py's encode(), which at restart_mcus = 0 (the image is one restart
+        interval: at most 65535 MCUs) are libjpeg's.  restart_mcus = R: a restart interval of R MCUs."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != img.shape[2]) or img.strides[0] < 0:
+            raise ValueError("jpeg_encode_device: a u8 (h, w) or (h, w, ch) array whose rows are contiguous")
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        cap = max(1 << 16, h * w * ch // 4)
+        n = C.c_size_t()
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            rc = self.lib.vfsms_jpeg_encode_device(self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(quality),
+                                                   int(restart_mcus), _ptr(out), cap, C.byref(n))
+            if rc != VFSMS_ERR_CAPACITY:
+                self._check(rc)
+                return out[:n.value]
+            cap = n.value
+        raise VfsmsError("jpeg_encode_device: the stream did not fit the size the library asked for")
+
+    def canvas_encode_jpeg_rows(self, handle, row0, nrows, quality, restart_mcus, out):
+        """one vfsms_canvas_encode_jpeg_rows call into the u8 vector `out` -> (return code, bytes needed); VFSMS_ERR_CAPACITY is returned, not
+        raised (nothing was written: call again with room), any other error raises"""
+        n = C.c_size_t()
+        rc = self.lib.vfsms_canvas_encode_jpeg_rows(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(quality), int(restart_mcus),
+                                                    _ptr(out), C.c_size_t(out.size), C.byref(n))
+        if rc != VFSMS_ERR_CAPACITY:
+            self._check(rc)
+        return rc, n.value
+
+    def canvas_encode_jpeg_bands(self, handle, rows, cols, ch, quality, restart_mcus, band_rows):
+        """Generator of (row0, nrows, bytes-view) over the whole mosaic: every band of `band_rows` rows as the entropy-coded bytes of a
+        baseline JPEG (vfsms_canvas_encode_jpeg_rows), encoded on the device -- behind jpeg_header(...) and in front of FF D9 they are the
+        file (imagestitch_amd.io.DeviceJpegFile).  band_rows must keep the band contract: a multiple of the MCU height (16 colour, 8 gray)
+        whose MCUs are a multiple of restart_mcus.  The views belong to a ring of BAND_RING pinned buffers, sized from the first band's
+        answer with room to spare and regrown when a later band needs more; a view is valid until BAND_RING - 1 further bands were asked for."""
+        rows, cols, ch, band_rows = int(rows), int(cols), int(ch), int(band_rows)
+        if band_rows <= 0:
+            raise ValueError("canvas_encode_jpeg_bands: band_rows must be positive")
+        ring = self.__dict__.get("_jpeg_ring")
+        if ring is None:
+            ring = self.__dict__["_jpeg_ring"] = [self.pinned_empty((1 << 16,)) for _ in range(self.BAND_RING)]
+        for k, r0 in enumerate(range(0, rows, band_rows)):
+            n = min(band_rows, rows - r0)
+            slot = k % self.BAND_RING
+            rc, need = self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, ring[slot])
+            if rc == VFSMS_ERR_CAPACITY:
+                size = need + need // 4 + (1 << 16)                                      # the band's answer with room for denser bands
+                for j in range(self.BAND_RING):                                           # (outgrown buffers stay valid: they are freed with the engine)
+                    if ring[j].size < size:
+                        ring[j] = self.pinned_empty((size,))
+                rc, need = self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, ring[slot])
+                if rc != VFSMS_OK:
+                    raise VfsmsError("canvas_encode_jpeg_bands: the band did not fit the size the library asked for")
+            yield r0, n, ring[slot][:need]
+
 
 _default_engine = None
+
+
+def jpeg_header(rows, cols, ch, quality=95, restart_mcus=0):
+    """vfsms_jpeg_header: SOI .. the SOS header of a baseline JPEG in libjpeg's layout (with a DRI segment when restart_mcus > 0), as bytes:
+    what goes in front of Engine.canvas_encode_jpeg_bands' payloads.  No GPU involved.  The refusals of tests/jpeg_enc_ref.py raise VfsmsError."""
+    lib = load_library()
+    out = np.empty(1024, np.uint8)
+    n = C.c_size_t()
+    rc = lib.vfsms_jpeg_header(int(rows), int(cols), int(ch), int(quality), int(restart_mcus), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if rc != VFSMS_OK:
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+    return out[:n.value].tobytes()
 
 
 def jpeg_decode(data, want_planes=False):

@@ -258,8 +258,9 @@ extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
     if (ctx->stream2) { hipStreamSynchronize(ctx->stream2); hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); hipFree(kv.second.pyr); }
-    if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); hipFree(ctx->spare_canvas.pyr); ctx->has_spare_canvas = false; }
+    for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); hipFree(kv.second.pyr); jpeg_scratch_free(&kv.second.jpeg); }
+    if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); hipFree(ctx->spare_canvas.pyr); jpeg_scratch_free(&ctx->spare_canvas.jpeg); ctx->has_spare_canvas = false; }
+    jpeg_scratch_free(&ctx->jpeg_scratch);
     for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
     if (ctx->arena) hipFree(ctx->arena);
     if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
@@ -1969,7 +1970,7 @@ extern "C" int vfsms_canvas_free(vfsms_ctx *ctx, int64_t handle)
     if (ctx->has_spare_canvas) {                               // one spare at a time: the older one goes back to the device
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         CanvasRec &o = ctx->spare_canvas;
-        HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch)); HIP_TRY(hipFree(o.pyr));
+        HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch)); HIP_TRY(hipFree(o.pyr)); jpeg_scratch_free(&o.jpeg);
     }
     ctx->spare_canvas = *cv; ctx->has_spare_canvas = true;      // kept for a canvas of the same size (stream order makes the reuse safe)
     ctx->canvases.erase(handle);
@@ -2229,6 +2230,68 @@ extern "C" int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas
     HIP_TRY(hipMemcpyAsync(out_levels, cv->pyr, need, hipMemcpyDeviceToHost, ctx->stream));
     if (out0) return canvas_read_rows(ctx, cv, row0, nrows, out0);
     return canvas_read_rows(ctx, cv, 0, 0, nullptr);             // (the sticky flag and the synchronisation alone)
+}
+
+// ---- the JPEG encoder on the device (Method.jpegEncoder = "device"; jpeg_enc_kernels.hip, specified by tests/jpeg_enc_ref.py) ------------
+// The entropy-coded bytes of rows [row0, row0 + nrows) of the canvas -- never-written pixels are 0, as canvas_read_rows defines the image --
+// with an RSTn behind every restart interval but the image's last.  The band contract: row0 is a multiple of the MCU height (16 colour, 8
+// gray); the MCUs in front of the band are a multiple of the interval, and so are the band's own unless it ends at the last row.  Then the
+// bytes of all bands behind vfsms_jpeg_header and in front of FF D9 are the file.  *nbytes = the size, also on VFSMS_ERR_CAPACITY
+extern "C" int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int quality, int restart_mcus,
+                                             uint8_t *out, size_t cap, size_t *nbytes)
+{
+    CTX_ENTER(ctx);
+    const char *who = "canvas_encode_jpeg_rows";
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    if (!nbytes || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    int interval = 0;
+    TRY(jpeg_check_geometry(who, cv->rows, cv->cols, cv->ch, quality, restart_mcus, &interval));
+    const int mcu = cv->ch == 3 ? 16 : 8, mw = (cv->cols + mcu - 1) / mcu;
+    const bool last = row0 + nrows == cv->rows;
+    if (row0 % mcu || (!last && nrows % mcu)) { vfsms_set_error("%s: rows [%d, %d) do not start and end on MCU rows of %d", who, row0, row0 + nrows, mcu); return VFSMS_ERR_BAD_ARG; }
+    if (((long long)(row0 / mcu) * mw) % interval || (!last && ((long long)(nrows / mcu) * mw) % interval)) {
+        vfsms_set_error("%s: rows [%d, %d) of %d MCUs each are not whole restart intervals of %d MCUs", who, row0, row0 + nrows, mw, interval);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    int err = 0;                                                   // the sticky geometry flag, as vfsms_canvas_download_rows reads it
+    HIP_TRY(hipMemcpyAsync(&err, cv->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TRY(jpeg_encode_band_device(ctx, &cv->jpeg, cv->pix, cv->rows, cv->cols, cv->ch, (size_t)cv->cols * cv->ch, 1, row0, nrows, quality, interval, out, cap, nbytes));
+    if (err) {
+        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
+        return VFSMS_ERR_BAD_ARG;
+    }
+    return VFSMS_OK;
+}
+
+// A whole image on the host (1 channel, or 3: B G R with bgr != 0, else R G B; rows `stride` bytes apart) -> a complete file, the bytes of
+// tests/jpeg_enc_ref.py's encode().  *nbytes = the size, also on VFSMS_ERR_CAPACITY
+extern "C" int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int quality, int restart_mcus,
+                                        uint8_t *out, size_t cap, size_t *nbytes)
+{
+    CTX_ENTER(ctx);
+    const char *who = "jpeg_encode_device";
+    if (!img || !nbytes) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    int interval = 0;
+    TRY(jpeg_check_geometry(who, h, w, ch, quality, restart_mcus, &interval));
+    if (stride < w * ch) { vfsms_set_error("%s: stride %d is less than a row's %d bytes", who, stride, w * ch); return VFSMS_ERR_BAD_ARG; }
+    size_t hn = 0, bn = 0;
+    TRY(vfsms_jpeg_header(h, w, ch, quality, restart_mcus, out, out ? cap : 0, &hn) == VFSMS_ERR_BAD_ARG ? VFSMS_ERR_BAD_ARG : VFSMS_OK);
+    JpegScratch *s = &ctx->jpeg_scratch;
+    const size_t pitch = (size_t)w * ch, bytes = pitch * h;
+    if (s->img_bytes < bytes) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipFree(s->img)); s->img = nullptr; s->img_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&s->img, bytes));
+        s->img_bytes = bytes;
+    }
+    HIP_TRY(hipMemcpy2DAsync(s->img, pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    const bool room = out && cap > hn + 2;
+    const int rc = jpeg_encode_band_device(ctx, s, s->img, h, w, ch, pitch, bgr != 0, 0, h, quality, interval, room ? out + hn : nullptr, room ? cap - hn - 2 : 0, &bn);
+    *nbytes = hn + bn + 2;
+    if (rc != VFSMS_OK) return rc;
+    out[hn + bn] = 0xFF; out[hn + bn + 1] = 0xD9;
+    return VFSMS_OK;
 }
 
 // ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------

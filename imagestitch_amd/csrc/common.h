@@ -178,7 +178,10 @@ struct MatchDev {
 struct TileRec { uint8_t *ptr; int h, w, stride; bool owned; hipEvent_t ready; bool pending; int ch = 1; size_t bytes = 0; int fill = 0; };
 struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device staging of one decoded source image (vfsms_tile_fill_pair)
 struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
-struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; uint8_t *pyr = nullptr; size_t pyr_bytes = 0; };   // pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+// device scratch of the JPEG encoder (jpeg_enc_kernels.hip), grown to the largest band seen: quantised coefficients, interval sizes + offsets,
+// the coded stream, and (vfsms_jpeg_encode_device only) the staged image
+struct JpegScratch { int16_t *coef = nullptr; size_t coef_bytes = 0; void *sizes = nullptr; size_t sizes_bytes = 0; uint8_t *out = nullptr; size_t out_bytes = 0; uint8_t *img = nullptr; size_t img_bytes = 0; };
+struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; uint8_t *pyr = nullptr; size_t pyr_bytes = 0; JpegScratch jpeg; };   // jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent
@@ -226,6 +229,7 @@ struct vfsms_ctx {
     void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
     size_t sift_group_bytes = (size_t)4 << 30;                     // pyramid bytes resident at once in a fused SIFT batch (VFSMS_SIFT_GROUP_BYTES overrides)
+    JpegScratch jpeg_scratch;                                      // vfsms_jpeg_encode_device's scratch, freed with the context
     CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a call (vfsms_features_surf, one set; vfsms_features_surf_batch, a chunk's), freed with its last set
@@ -384,6 +388,14 @@ struct ExpJob { const uint8_t *a, *b; int sa, sb, wa, wb, r0, nrows, c0, c1, dx,
 struct ExpTileHost { uint8_t *ptr; int stride, h, wb; };
 int overlap_stats_device(vfsms_ctx *ctx, const ExpPairHost *pairs, int n, int lo, int hi, unsigned long long *d_out3);   // d_out3: [n][3] = N, Sa, Sb
 int exposure_apply_device(vfsms_ctx *ctx, const ExpTileHost *tiles, int n, const uint16_t *gain_q12);
+// jpeg_host.cpp / jpeg_enc_kernels.hip: the device JPEG encoder (tests/jpeg_enc_ref.py)
+const uint8_t *jpeg_std_huff_bits(int ac, int chroma);
+const uint8_t *jpeg_std_huff_vals(int ac, int chroma);
+void jpeg_quant_tables(int quality, uint8_t q[2][64]);
+int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality, int restart_mcus, int *interval);
+void jpeg_scratch_free(JpegScratch *s);
+int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
+                            int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes);
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
 size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);

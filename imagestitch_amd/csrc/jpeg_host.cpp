@@ -503,3 +503,93 @@ extern "C" int vfsms_jpeg_join(const uint8_t *const *streams, const size_t *size
     *o++ = 0xFF; *o++ = 0xD9;
     return (size_t)(o - out) == need ? VFSMS_OK : VFSMS_ERR_BAD_ARG;
 }
+
+// ---- the device encoder's host half (jpeg_enc_kernels.hip; specified by tests/jpeg_enc_ref.py) -----------------------------------------------
+namespace {
+const uint8_t kQuantLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kQuantChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// Annex K: codes per length, then the symbols
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+const uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1,
+     0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+     0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a,
+     0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+     0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3,
+     0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1,
+     0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+     0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+     0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+     0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca,
+     0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+}  // namespace
+
+const uint8_t *jpeg_std_huff_bits(int ac, int chroma) { return ac ? kAcBits[chroma] : kDcBits[chroma]; }
+const uint8_t *jpeg_std_huff_vals(int ac, int chroma) { return ac ? kAcVals[chroma] : kDcVals; }
+
+// jpeg_quality_scaling + jpeg_add_quant_table(force_baseline): q[0] luminance, q[1] chrominance, natural order, 1..255
+void jpeg_quant_tables(int quality, uint8_t q[2][64])
+{
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int k = 0; k < 64; k++) {
+        const int l = (kQuantLuma[k] * scale + 50) / 100, c = (kQuantChroma[k] * scale + 50) / 100;
+        q[0][k] = (uint8_t)(l < 1 ? 1 : l > 255 ? 255 : l);
+        q[1][k] = (uint8_t)(c < 1 ? 1 : c > 255 ? 255 : c);
+    }
+}
+
+// the refusals every entry of the device encoder shares (tests/jpeg_enc_ref.py: _geometry): 1 or 3 channels, at most 65500 pixels a side, at
+// most 65535 MCUs in an interval -- restart_mcus = 0 is "the image is one interval".  *interval: the interval in MCUs
+int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality, int restart_mcus, int *interval)
+{
+    if (ch != 1 && ch != 3) { vfsms_set_error("%s: 1 or 3 channels, got %d", who, ch); return VFSMS_ERR_BAD_ARG; }
+    if (rows < 1 || cols < 1 || rows > 65500 || cols > 65500) { vfsms_set_error("%s: 1..65500 pixels a side, got %d x %d", who, rows, cols); return VFSMS_ERR_BAD_ARG; }
+    if (quality < 1 || quality > 100) { vfsms_set_error("%s: quality must be 1..100, got %d", who, quality); return VFSMS_ERR_BAD_ARG; }
+    if (restart_mcus < 0 || restart_mcus > 65535) { vfsms_set_error("%s: restart_mcus must be 0..65535, got %d", who, restart_mcus); return VFSMS_ERR_BAD_ARG; }
+    const int mcu = ch == 3 ? 16 : 8;
+    const long long n = (long long)((cols + mcu - 1) / mcu) * ((rows + mcu - 1) / mcu);
+    if (restart_mcus == 0 && n > 65535) { vfsms_set_error("%s: an image of %lld MCUs cannot be one restart interval (at most 65535)", who, n); return VFSMS_ERR_BAD_ARG; }
+    if (interval) *interval = restart_mcus ? restart_mcus : (int)n;
+    return VFSMS_OK;
+}
+
+// SOI, JFIF APP0, DQT per table, SOF0, DHT per table, DRI (restart_mcus > 0), SOS header: libjpeg's layout byte for byte, so the entropy-coded
+// bytes of the device (vfsms_canvas_encode_jpeg_rows) behind it and FF D9 behind them are a file.  Host only.  *nbytes = the size, also on
+// VFSMS_ERR_CAPACITY
+extern "C" int vfsms_jpeg_header(int rows, int cols, int ch, int quality, int restart_mcus, uint8_t *out, size_t cap, size_t *nbytes)
+{
+    if (!nbytes) { vfsms_set_error("jpeg_header: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(jpeg_check_geometry("jpeg_header", rows, cols, ch, quality, restart_mcus, nullptr));
+    uint8_t b[700]; size_t n = 0;
+    auto seg = [&](int marker, size_t payload) { b[n++] = 0xFF; b[n++] = (uint8_t)marker; b[n++] = (uint8_t)((payload + 2) >> 8); b[n++] = (uint8_t)(payload + 2); };
+    b[n++] = 0xFF; b[n++] = 0xD8;
+    static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    seg(0xE0, 14); memcpy(b + n, jfif, 14); n += 14;
+    uint8_t q[2][64];
+    jpeg_quant_tables(quality, q);
+    const int ntab = ch == 3 ? 2 : 1;
+    for (int t = 0; t < ntab; t++) { seg(0xDB, 65); b[n++] = (uint8_t)t; for (int k = 0; k < 64; k++) b[n++] = q[t][kZigzag[k]]; }
+    seg(0xC0, 6 + 3 * (size_t)ch);
+    b[n++] = 8; b[n++] = (uint8_t)(rows >> 8); b[n++] = (uint8_t)rows; b[n++] = (uint8_t)(cols >> 8); b[n++] = (uint8_t)cols; b[n++] = (uint8_t)ch;
+    for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = (ch == 3 && c == 0) ? 0x22 : 0x11; b[n++] = c ? 1 : 0; }
+    for (int t = 0; t < ntab; t++) {
+        seg(0xC4, 1 + 16 + 12); b[n++] = (uint8_t)t; memcpy(b + n, kDcBits[t], 16); n += 16; memcpy(b + n, kDcVals, 12); n += 12;
+        seg(0xC4, 1 + 16 + 162); b[n++] = (uint8_t)(0x10 | t); memcpy(b + n, kAcBits[t], 16); n += 16; memcpy(b + n, kAcVals[t], 162); n += 162;
+    }
+    if (restart_mcus) { seg(0xDD, 2); b[n++] = (uint8_t)(restart_mcus >> 8); b[n++] = (uint8_t)restart_mcus; }
+    seg(0xDA, 4 + 2 * (size_t)ch);
+    b[n++] = (uint8_t)ch;
+    for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = c ? 0x11 : 0x00; }
+    b[n++] = 0; b[n++] = 0x3F; b[n++] = 0;
+    *nbytes = n;
+    if (!out || cap < n) { vfsms_set_error("jpeg_header: output buffer too small"); return VFSMS_ERR_CAPACITY; }
+    memcpy(out, b, n);
+    return VFSMS_OK;
+}

@@ -9,6 +9,9 @@ import os
 import numpy as np
 
 def _imwrite(path, img):
+    """cv2.imwrite's stand-in for a mosaic that is whole in host memory (streamOutput = False, or a format without a band encoder).  It
+    always encodes on the host, also with Method.jpegEncoder = "device": the pixels have crossed the link by then, and sending them back
+    to be encoded would move them twice more."""
     if img is None:                                          # streamed to Stitcher.mosaicSink instead
         return
     from PIL import Image
@@ -206,6 +209,45 @@ class JpegBandWriter:
                     pass
             self._reset()
             raise
+
+
+class DeviceJpegFile:
+    """The file side of Method.jpegEncoder = "device": the header (`_lib.jpeg_header`: libjpeg's layout with a DRI segment), then the
+    entropy-coded bytes of the bands as Engine.canvas_encode_jpeg_bands hands them out, appended in order, then EOI.  Creates the directory;
+    refuses what JPEG cannot hold before anything is written."""
+
+    def __init__(self, path, full_shape, quality=95, restart_mcus=8):
+        rows, cols = int(full_shape[0]), int(full_shape[1])
+        ch = int(full_shape[2]) if len(full_shape) == 3 else 1
+        if ch not in (1, 3) or max(rows, cols) > 65500:
+            raise ValueError("JPEG holds 1- or 3-channel images of at most 65500 pixels a side (this one: %s)" % (tuple(full_shape),))
+        from . import _lib
+        head = _lib.jpeg_header(rows, cols, ch, quality, restart_mcus)
+        d = os.path.dirname(path)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        self.path, self.bytes_written = path, 0
+        self._f = open(path, "wb")
+        self._write(head)
+
+    def _write(self, data):
+        self._f.write(data)
+        self.bytes_written += len(data)
+
+    def append(self, payload):
+        self._write(memoryview(payload))
+
+    def close(self):
+        self._write(b"\xFF\xD9")
+        self._f.close()
+        self._f = None
+
+    def abort(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+        if os.path.exists(self.path):
+            os.remove(self.path)
 
 
 class TiffBandWriter:

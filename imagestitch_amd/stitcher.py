@@ -63,7 +63,7 @@ class ResidentFeatures:
 from .ingest import (_imread, _imread_gray_pointer, _PillowBlocks, _decoder_pool, _decode_once, _fill_from_jpeg, _ycc_to_bgr, _imshape,  # noqa: F401
                      _list_images, TileIngest)
 from .io import (_imwrite, _imwrite_jpeg_stripes, NpyBandWriter, PngBandWriter, JpegBandWriter, TiffBandWriter, _NoNativeJpeg,  # noqa: F401
-                 _native_jpeg_encoder, band_writer_for, PyramidTiffBandWriter)
+                 _native_jpeg_encoder, band_writer_for, PyramidTiffBandWriter, DeviceJpegFile)
 
 
 def _join(base, *parts):
@@ -161,6 +161,30 @@ class Stitcher(Utility.Method):
         if "mosaicSink" in self.__dict__:                    # the user streams the mosaics somewhere else (stitcher.mosaicSink = NpyBandWriter(...)): leave it alone
             return None
         probe = pattern % 0 if pattern else paths[0]
+        if self._deviceJpeg(os.path.splitext(probe)[1][1:]):
+            # jpegEncoder "device": the sink takes the bands' entropy-coded bytes, not their pixels (getStitchByOffset asks the engine for them)
+            state = {"f": None, "n": 0}
+
+            def payload_sink(row0, nrows, payload, full_shape):
+                try:
+                    if state["f"] is None:
+                        path = (pattern % state["n"]) if pattern else paths[state["n"]]
+                        if pattern:
+                            paths.append(path)
+                        state["n"] += 1
+                        state["f"] = DeviceJpegFile(path, full_shape, int(self.jpegQuality), int(self.jpegRestartMcus))
+                    state["f"].append(payload)
+                    if row0 + nrows >= full_shape[0]:
+                        state["f"].close()
+                        state["f"] = None
+                except BaseException:
+                    if state["f"] is not None:
+                        state["f"].abort()
+                        state["f"] = None
+                    raise
+            payload_sink.device_jpeg = True
+            self.mosaicSink = payload_sink
+            return payload_sink
         # outputPyramid: every mosaic through the pyramidal writer, which takes the reduced levels of a band beside it
         wkw = {"pyramid": self._pyramidOptions()} if self.outputPyramid else {}
         first = band_writer_for(probe, **wkw)
@@ -183,6 +207,34 @@ class Stitcher(Utility.Method):
             sink.pyramid_levels = first.pyramid_levels
         self.mosaicSink = sink
         return sink
+
+    def _deviceJpeg(self, outputfileExtension):
+        """does this output go through the device's JPEG encoder (Method.jpegEncoder = "device" with streamOutput and a .jpg / .jpeg result)?
+        Judged -- with the engine's support and mosaicBandRows -- before a file is listed or a tile decoded.  Everything else (other formats,
+        outputPyramid, streamOutput = False, a mosaicSink of the user's) is written as with "host"."""
+        if self.jpegEncoder not in ("host", "device"):
+            raise ValueError("jpegEncoder must be 'host' or 'device', got %r" % (self.jpegEncoder,))
+        if self.jpegEncoder != "device" or not self.streamOutput or self.outputPyramid or str(outputfileExtension).lower() not in ("jpg", "jpeg"):
+            return False
+        if "mosaicSink" in self.__dict__ and not getattr(self.__dict__["mosaicSink"], "device_jpeg", False):
+            return False
+        if not hasattr(self.engine, "canvas_encode_jpeg_bands"):
+            raise NotImplementedError("jpegEncoder = 'device' needs an engine with canvas_encode_jpeg_bands")
+        if not 1 <= int(self.jpegQuality) <= 100:
+            raise ValueError("jpegQuality must be 1..100, got %r" % (self.jpegQuality,))
+        self._jpegBandRows()
+        return True
+
+    def _jpegBandRows(self):
+        """mosaicBandRows for the device's JPEG encoder: every band must be whole restart intervals whatever the mosaic's width, so it is a
+        multiple of the MCU height (16 rows in colour, 8 in gray) times jpegRestartMcus"""
+        band_rows, R = int(getattr(self, "mosaicBandRows", 4096)), int(self.jpegRestartMcus)
+        if not 1 <= R <= 65535:
+            raise ValueError("jpegRestartMcus must be 1..65535, got %r" % (self.jpegRestartMcus,))
+        step = (16 if self.isColorMode else 8) * R
+        if band_rows <= 0 or band_rows % step:
+            raise ValueError("restart intervals of %d MCUs need mosaicBandRows to be a multiple of %d, got %d" % (R, step, band_rows))
+        return band_rows
 
     def _pyramidOptions(self):
         """Method.pyramid* as PyramidTiffBandWriter's keyword arguments"""
@@ -464,6 +516,7 @@ class Stitcher(Utility.Method):
     def imageSetStitch(self, projectAddress, outputAddress, fileNum, caculateOffsetMethod, startNum=1, fileExtension="jpg", outputfileExtension="jpg"):
         """Stitcher.py:129-151."""
         self._checkPyramidOutput(outputfileExtension)
+        self._deviceJpeg(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             fileList = _list_images(_join(projectAddress, i), fileExtension)
             outDir = outputAddress.replace("\\", os.sep)
@@ -497,6 +550,7 @@ class Stitcher(Utility.Method):
     def imageSetStitchWithMutiple(self, projectAddress, outputAddress, fileNum, caculateOffsetMethod, startNum=1, fileExtension="jpg", outputfileExtension="jpg"):
         """Stitcher.py:153-182 (the entry point Main.py:20-51 uses)."""
         self._checkPyramidOutput(outputfileExtension)
+        self._deviceJpeg(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             startTime = time.time()
             fileAddress = _join(projectAddress, i)
@@ -986,6 +1040,12 @@ class Stitcher(Utility.Method):
                 if one_call:
                     eng.canvas_assemble_resident(canvas, handles, rows)
                 sink = getattr(self, "mosaicSink", None)
+                if sink is not None and getattr(sink, "device_jpeg", False):
+                    # jpegEncoder "device": the bands leave as their entropy-coded bytes (csrc/jpeg_enc_kernels.hip); the sink appends them
+                    for r0, nr, payload in eng.canvas_encode_jpeg_bands(canvas, resultRow, resultCol, ch, int(self.jpegQuality),
+                                                                        int(self.jpegRestartMcus), self._jpegBandRows()):
+                        sink(r0, nr, payload, full_shape)
+                    return None
                 if sink is not None and hasattr(eng, "canvas_download_bands"):
                     # streamed write-out: the mosaic leaves the device band by band and is never whole in host memory
                     # (a sink that is done with a band two bands later -- `transient_bands`: JpegBandWriter -- gets views of the engine's

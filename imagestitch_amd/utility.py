@@ -209,6 +209,20 @@ class Method():
     pyramidLevels = None
     pyramidCompression = "none"
 
+    # ---- JPEG results encoded on the device (no reference counterpart; tests/jpeg_enc_ref.py).  jpegEncoder "host" (the default: nothing
+    # changes -- the bands cross the link as pixels and libjpeg-turbo encodes them on a host thread pool, JpegBandWriter) or "device": with
+    # streamOutput, a .jpg / .jpeg result and no mosaicSink of the user's, colour conversion, DCT, quantisation and Huffman coding run where
+    # the mosaic is (csrc/jpeg_enc_kernels.hip) and a band leaves as its entropy-coded bytes, which the host only appends to the file
+    # (DeviceJpegFile).  The file decodes to the pixels of the host encoder's file; its bytes are tests/jpeg_enc_ref.py's.
+    # jpegQuality: cv2.imwrite's default, the one the host path uses (Stitcher.py:149 passes no flags).
+    # jpegRestartMcus: MCUs (16 x 16 pixels, 8 x 8 gray) per restart interval = per device lane.  Shorter intervals mean more lanes and two
+    # marker bytes plus up to seven padding bits each; 8 keeps that below half a per cent of a quality-95 mosaic.  PROVISIONAL: the sweep
+    # of tools/bench_jpeg_device.py over {1 .. 64} has not been run on the device yet (README).  mosaicBandRows must
+    # be a multiple of the MCU height times jpegRestartMcus, so that every band is whole intervals whatever the mosaic's width.
+    jpegEncoder = "host"
+    jpegQuality = 95
+    jpegRestartMcus = 8
+
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None
 

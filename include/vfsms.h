@@ -199,6 +199,16 @@ int vfsms_jpeg_encode(const uint8_t *rows, int n_rows, int cols, int channels, i
                       uint8_t *out, size_t cap, size_t *nbytes);
 int vfsms_jpeg_join(const uint8_t *const *streams, const size_t *sizes, int n_stripes, int stripe_rows, int total_rows,
                     uint8_t *out, size_t cap, size_t *nbytes);
+/* The encoder on the device (Method.jpegEncoder = "device"; csrc/jpeg_enc_kernels.hip).  Its bytes are those of tests/jpeg_enc_ref.py --
+ * libjpeg's baseline encoder with jpeg_set_defaults + jpeg_set_quality(quality, force_baseline), byte for byte libjpeg's file when the image
+ * is one restart interval -- with a restart interval of `restart_mcus` MCUs (16 x 16 pixels for 3 channels, 4:2:0; 8 x 8 for 1).  One rule
+ * for every entry: an interval holds at most 65535 MCUs, and restart_mcus = 0 means "the image is one interval", so it is refused for an
+ * image of more MCUs than that.  VFSMS_ERR_BAD_ARG for that, for restart_mcus > 65535, a side beyond 65500, channels other than 1 and 3.
+ * vfsms_jpeg_header (host only, no context): SOI .. the SOS header in libjpeg's layout; *nbytes = the size, also on VFSMS_ERR_CAPACITY.
+ * vfsms_jpeg_encode_device: an image on the host (B G R with bgr != 0, else R G B) -> a complete file; *nbytes likewise.                  */
+int vfsms_jpeg_header(int rows, int cols, int ch, int quality, int restart_mcus, uint8_t *out, size_t cap, size_t *nbytes);
+int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int quality, int restart_mcus,
+                             uint8_t *out, size_t cap, size_t *nbytes);
 /* pinned host staging memory for tiles (decoders write into it; uploads from it are asynchronous DMA)                          */
 int vfsms_host_alloc(vfsms_ctx *ctx, size_t bytes, void **ptr);
 int vfsms_host_free(vfsms_ctx *ctx, void *ptr);
@@ -521,6 +531,14 @@ int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nro
 #define VFSMS_PYRAMID_MAX_LEVELS 10
 int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels,
                                        uint8_t *out0, uint8_t *out_levels, size_t cap_levels);
+/* Rows [row0, row0 + nrows) of the mosaic as the entropy-coded bytes of a baseline JPEG (see vfsms_jpeg_header above), so a band leaves
+ * the device compressed and the host only appends it to a file.  The band contract: row0 is a multiple of the MCU height; the MCUs in
+ * front of the band are a multiple of the restart interval, and so are the band's own unless it ends at the last row (VFSMS_ERR_BAD_ARG
+ * otherwise).  An RSTn follows every interval but the image's last: the bytes of all bands, behind vfsms_jpeg_header's and in front of
+ * FF D9, are the file.  *nbytes = the size needed, also on VFSMS_ERR_CAPACITY (nothing is written then; the call may be repeated).  The
+ * sticky geometry flag as vfsms_canvas_download_rows.                                                                                   */
+int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int quality, int restart_mcus,
+                                  uint8_t *out, size_t cap, size_t *nbytes);
 
 /* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
  * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
