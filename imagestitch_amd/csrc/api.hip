@@ -39,26 +39,19 @@ extern "C" int vfsms_device_count(void)
 int ctx_arena_reserve(vfsms_ctx *ctx, size_t bytes)
 {
     bytes += 1 << 20;
-    if (bytes > ctx->arena_size) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->arena) HIP_TRY(hipFree(ctx->arena));
-        ctx->arena = nullptr; ctx->arena_size = 0;
-        size_t want = bytes + bytes / 4;
-        HIP_TRY(hipMalloc((void **)&ctx->arena, want));
-        ctx->arena_size = want;
-    }
+    TRY(ctx->arena.reserve(bytes, ctx->stream, bytes / 4));
     ctx->arena_off = 0;
     return VFSMS_OK;
 }
 void *ctx_arena_alloc(vfsms_ctx *ctx, size_t bytes, size_t align)
 {
     size_t off = (ctx->arena_off + align - 1) & ~(align - 1);
-    if (off + bytes > ctx->arena_size) return nullptr;
+    if (off + bytes > ctx->arena.bytes()) return nullptr;
     ctx->arena_off = off + bytes;
-    return ctx->arena + off;
+    return ctx->arena.as<char>() + off;
 }
 // a record's layout function carves from a walk that starts where the arena stands (arena_walk.h) ...
-ArenaWalk ctx_arena_walk(vfsms_ctx *ctx) { return ArenaWalk{ctx->arena, ctx->arena_off, ctx->arena_size}; }
+ArenaWalk ctx_arena_walk(vfsms_ctx *ctx) { return ArenaWalk{ctx->arena.as<char>(), ctx->arena_off, ctx->arena.bytes()}; }
 // ... and the arena moves on only when every take of the walk fitted; `what`: the error string of a walk that did not
 int ctx_arena_commit(vfsms_ctx *ctx, const ArenaWalk &a, const char *what)
 {
@@ -207,10 +200,10 @@ int ctx_prepare_surf(vfsms_ctx *ctx, const vfsms_surf_params *p)
     for (int i = 0; i < 20; i++)
         for (int j = 0; j < 20; j++) T.DW[i * 20 + j] = G_desc[i] * G_desc[j];
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!ctx->d_layers) HIP_TRY(hipMalloc((void **)&ctx->d_layers, sizeof(LayerPat) * VFSMS_MAX_LAYERS));
-    if (!ctx->d_tables) HIP_TRY(hipMalloc((void **)&ctx->d_tables, sizeof(SurfTables)));
-    HIP_TRY(hipMemcpy(ctx->d_layers, L.data(), sizeof(LayerPat) * nl, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->d_tables, &T, sizeof(T), hipMemcpyHostToDevice));
+    TRY(ctx->d_layers.reserve(sizeof(LayerPat) * VFSMS_MAX_LAYERS, ctx->stream));
+    TRY(ctx->d_tables.reserve(sizeof(SurfTables), ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->d_layers.as<void>(), L.data(), sizeof(LayerPat) * nl, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_tables.as<void>(), &T, sizeof(T), hipMemcpyHostToDevice));
     ctx->n_layers = nl;
     ctx->cur_params = *p;
     ctx->tables_valid = true;
@@ -226,11 +219,7 @@ extern "C" int vfsms_ctx_create(int device, vfsms_ctx **out)
     if (device < 0 || device >= n) { vfsms_set_error("device %d out of range (%d visible)", device, n); return VFSMS_ERR_BAD_ARG; }
     HIP_TRY(hipSetDevice(device));
     vfsms_ctx *c = new vfsms_ctx();
-    c->device = device; c->arena = nullptr; c->arena_size = 0; c->arena_off = 0;
-    c->pinned = nullptr; c->pinned_size = 0; c->pinned_off = 0; c->kp_cap_override = 0;
-    c->tables_valid = false; c->d_layers = nullptr; c->d_tables = nullptr; c->n_layers = 0; c->next_handle = 1;
-    c->prof_on = false; c->orb_valid = false; c->d_orb_tables = nullptr;
-    memset(&c->cur_params, 0, sizeof(c->cur_params));
+    c->device = device;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { vfsms_set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete c; return VFSMS_ERR_HIP; }
@@ -240,41 +229,38 @@ extern "C" int vfsms_ctx_create(int device, vfsms_ctx **out)
 
 int phase_destroy_plans(vfsms_ctx *ctx);
 
+// the pools whose entries stayed raw pointers (they move between a record and a pool, and carry events): each is freed here and nowhere else
+static void tile_pools_free(vfsms_ctx *ctx)
+{
+    for (auto &kv : ctx->tiles) { if (kv.second.owned) hipFree(kv.second.ptr); if (kv.second.ready) hipEventDestroy(kv.second.ready); }
+    for (auto &pe : ctx->tile_pool) { hipFree(pe.ptr); if (pe.idle) hipEventDestroy(pe.idle); }
+    ctx->tiles.clear(); ctx->tile_pool.clear(); ctx->tile_pool_bytes = 0;
+}
+static void stage_pools_free(vfsms_ctx *ctx)
+{
+    for (auto &sb : ctx->stage_pool) hipFree(sb.ptr);
+    for (auto &pb : ctx->pin_pool) hipHostFree(pb.ptr);
+    ctx->stage_pool.clear(); ctx->pin_pool.clear();
+}
+// Only what has an order is written out: nothing may run when memory goes, the plans and the profile want live streams, and the members
+// (device_buf.h) free themselves behind all of it
 extern "C" int vfsms_ctx_destroy(vfsms_ctx *ctx)
 {
     if (!ctx) return VFSMS_ERR_BAD_ARG;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
+    hipStreamSynchronize(ctx->copy_stream);
+    if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
     phase_destroy_plans(ctx);
     prof_collect(ctx);
     for (hipEvent_t e : ctx->prof_pool) hipEventDestroy(e);
-    hipStreamSynchronize(ctx->copy_stream);
-    for (auto &kv : ctx->tiles) { if (kv.second.owned) hipFree(kv.second.ptr); if (kv.second.ready) hipEventDestroy(kv.second.ready); }
-    for (auto &pe : ctx->tile_pool) { hipFree(pe.ptr); if (pe.idle) hipEventDestroy(pe.idle); }
-    for (auto &sb : ctx->stage_pool) hipFree(sb.ptr);
-    for (auto &pb : ctx->pin_pool) hipHostFree(pb.ptr);
+    tile_pools_free(ctx);
+    stage_pools_free(ctx);
     for (hipEvent_t ev : ctx->event_pool) hipEventDestroy(ev);
-    hipStreamDestroy(ctx->copy_stream);
-    if (ctx->stream2) { hipStreamSynchronize(ctx->stream2); hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    for (auto &kv : ctx->canvases) { hipFree(kv.second.pix); hipFree(kv.second.mask); hipFree(kv.second.d_err); hipFree(kv.second.scratch); hipFree(kv.second.pyr); jpeg_scratch_free(&kv.second.jpeg); }
-    if (ctx->has_spare_canvas) { hipFree(ctx->spare_canvas.pix); hipFree(ctx->spare_canvas.mask); hipFree(ctx->spare_canvas.d_err); hipFree(ctx->spare_canvas.scratch); hipFree(ctx->spare_canvas.pyr); jpeg_scratch_free(&ctx->spare_canvas.jpeg); ctx->has_spare_canvas = false; }
-    jpeg_scratch_free(&ctx->jpeg_scratch);
-    for (auto &kv : ctx->feat_blocks) hipFree(kv.second.base);
-    if (ctx->arena) hipFree(ctx->arena);
-    if (ctx->mb_scratch) hipFree(ctx->mb_scratch);
-    if (ctx->seam_scratch) hipFree(ctx->seam_scratch);
-    if (ctx->shade_scratch) hipFree(ctx->shade_scratch);
-    for (auto &kv : ctx->shade_fields) hipFree(kv.second.gain);
-    if (ctx->sift_scratch) hipFree(ctx->sift_scratch);
-    if (ctx->sift_kp) hipFree(ctx->sift_kp);
-    sift_pool_free(ctx);
-    if (ctx->pinned) hipHostFree(ctx->pinned);
-    if (ctx->d_layers) hipFree(ctx->d_layers);
-    if (ctx->d_tables) hipFree(ctx->d_tables);
-    if (ctx->d_area_tab) hipFree(ctx->d_area_tab);
-    if (ctx->d_orb_tables) hipFree(ctx->d_orb_tables);
+    hipStreamDestroy(ctx->copy_stream);
+    if (ctx->stream2) hipStreamDestroy(ctx->stream2);
     hipStreamDestroy(ctx->stream);
     delete ctx;
     return VFSMS_OK;
@@ -744,16 +730,14 @@ int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d)
 // the same to an array the caller's layout walk took
 int ctx_copy_small(vfsms_ctx *ctx, const void *src, size_t bytes, void *d)
 {
-    if (ctx->pinned_off + bytes > ctx->pinned_size) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                 // earlier copies out of the old buffer have landed
-        if (ctx->pinned) HIP_TRY(hipHostFree(ctx->pinned));
-        ctx->pinned = nullptr;
-        ctx->pinned_size = std::max<size_t>(4 * (ctx->pinned_off + bytes), (size_t)1 << 20);
-        HIP_TRY(hipHostMalloc((void **)&ctx->pinned, ctx->pinned_size, hipHostMallocDefault));
+    const size_t need = ctx->pinned_off + bytes;
+    if (need > ctx->pinned.bytes()) {                               // (the synchronisation of the growth: earlier copies out of the old buffer have landed)
+        TRY(ctx->pinned.reserve(need, ctx->stream, std::max<size_t>(4 * need, (size_t)1 << 20) - need));
         ctx->pinned_off = 0;
     }
-    memcpy(ctx->pinned + ctx->pinned_off, src, bytes);
-    HIP_TRY(hipMemcpyAsync(d, ctx->pinned + ctx->pinned_off, bytes, hipMemcpyHostToDevice, ctx->stream));
+    char *stage = ctx->pinned.as<char>() + ctx->pinned_off;
+    memcpy(stage, src, bytes);
+    HIP_TRY(hipMemcpyAsync(d, stage, bytes, hipMemcpyHostToDevice, ctx->stream));
     ctx->pinned_off += (bytes + 255) & ~(size_t)255;
     return VFSMS_OK;
 }
@@ -1635,15 +1619,17 @@ static int feats_from_run(vfsms_ctx *ctx, const SurfRun &run, int dim, int64_t *
     for (int k = 0; k < m; k++) total += set_bytes(k);
     char *base = nullptr; int64_t blk = 0;
     if (total) {
-        HIP_TRY(hipMalloc((void **)&base, total));
+        DevBuf mem;
+        TRY(mem.reserve(total, ctx->stream));
+        base = mem.as<char>();
         blk = ctx->next_handle++;
-        ctx->feat_blocks[blk] = FeatBlock{base, 0};
+        ctx->feat_blocks.emplace(blk, FeatBlock{std::move(mem), 0});
     }
     size_t off = 0;
     for (int k = 0; k < m; k++) {
         FeatRec F; F.n = surf_run_count(run, k); F.dim = dim; F.kps_xy = nullptr; F.desc = nullptr;
         if (F.n > 0) {
-            F.block = blk; ctx->feat_blocks[blk].refs++;
+            F.block = blk; ctx->feat_blocks.at(blk).refs++;
             F.kps_xy = (float *)(base + off); F.desc = base + off + sizeof(float) * 2 * F.n;
             off += set_bytes(k);
             HIP_TRY(hipMemcpyAsync(F.kps_xy, run.R[k].kps_xy, sizeof(float) * 2 * F.n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1823,8 +1809,7 @@ extern "C" int vfsms_features_free(vfsms_ctx *ctx, int64_t feat)
     if (it == ctx->feats.end()) { vfsms_set_error("features_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
     auto bt = ctx->feat_blocks.find(it->second.block);       // (a set without keypoints has no block)
     if (bt != ctx->feat_blocks.end() && --bt->second.refs == 0) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipFree(bt->second.base));
+        TRY(bt->second.base.release(ctx->stream));
         ctx->feat_blocks.erase(bt);
     }
     ctx->feats.erase(it);
@@ -1932,26 +1917,45 @@ extern "C" int vfsms_fuse_ramps_i64(vfsms_ctx *ctx, const int64_t *A, int r, int
     return VFSMS_OK;
 }
 
+// a canvas that enqueued work may still read, back to the device: one synchronisation, then the record's own destructor
+static int canvas_release(vfsms_ctx *ctx, CanvasRec &cv)
+{
+    if (cv.pix) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    cv = CanvasRec();
+    return VFSMS_OK;
+}
+// the buffers of a rows x cols x ch canvas (the spare's, when it is of that size) in their initial state.  Enqueue only
+static int canvas_build(vfsms_ctx *ctx, CanvasRec &cv, int rows, int cols, int ch)
+{
+    if (ctx->spare_canvas.rows == rows && ctx->spare_canvas.cols == cols && ctx->spare_canvas.ch == ch) {
+        cv = std::move(ctx->spare_canvas); ctx->spare_canvas = CanvasRec();
+        cv.placed.clear(); cv.mb_levels = 4; cv.seam_blend = 0;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
+    } else {
+        TRY(canvas_release(ctx, ctx->spare_canvas));             // a spare of another size goes first: the two never stand side by side
+        cv.rows = rows; cv.cols = cols; cv.ch = ch;
+        TRY(cv.pix.reserve((size_t)rows * cols * ch, ctx->stream));
+        TRY(cv.mask.reserve((size_t)rows * cols, ctx->stream));
+        TRY(cv.d_err.reserve(sizeof(int), ctx->stream));
+        TRY(cv.scratch.reserve(canvas_scratch_bytes(rows, cols), ctx->stream));
+    }
+    TRY(canvas_scratch_init(ctx, &cv));
+    HIP_TRY(hipMemsetAsync(cv.d_err.as<void>(), 0, sizeof(int), ctx->stream));
+    HIP_TRY(hipMemsetAsync(cv.pix.as<void>(), 0, (size_t)rows * cols * ch, ctx->stream));
+    HIP_TRY(hipMemsetAsync(cv.mask.as<void>(), 0, (size_t)rows * cols, ctx->stream));
+    return VFSMS_OK;
+}
 extern "C" int vfsms_canvas_create(vfsms_ctx *ctx, int rows, int cols, int ch, int64_t *handle)
 {
     CTX_ENTER(ctx);
     if (!handle || rows <= 0 || cols <= 0 || ch < 1 || ch > 4) { vfsms_set_error("canvas_create: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    CanvasRec cv; cv.rows = rows; cv.cols = cols; cv.ch = ch;
-    if (ctx->has_spare_canvas && ctx->spare_canvas.rows == rows && ctx->spare_canvas.cols == cols && ctx->spare_canvas.ch == ch) {
-        cv = ctx->spare_canvas; cv.placed.clear(); cv.mb_levels = 4; cv.seam_blend = 0;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
-        ctx->has_spare_canvas = false;
-    } else {
-        HIP_TRY(hipMalloc((void **)&cv.pix, (size_t)rows * cols * ch));
-        HIP_TRY(hipMalloc((void **)&cv.mask, (size_t)rows * cols));
-        HIP_TRY(hipMalloc((void **)&cv.d_err, sizeof(int)));
-        HIP_TRY(hipMalloc(&cv.scratch, canvas_scratch_bytes(rows, cols)));
+    CanvasRec cv;
+    const int rc = canvas_build(ctx, cv, rows, cols, ch);
+    if (rc != VFSMS_OK) {                                      // a half-built canvas goes back whole; its initialisation may be enqueued already
+        hipStreamSynchronize(ctx->stream);
+        return rc;
     }
-    TRY(canvas_scratch_init(ctx, &cv));
-    HIP_TRY(hipMemsetAsync(cv.d_err, 0, sizeof(int), ctx->stream));
-    HIP_TRY(hipMemsetAsync(cv.pix, 0, (size_t)rows * cols * ch, ctx->stream));
-    HIP_TRY(hipMemsetAsync(cv.mask, 0, (size_t)rows * cols, ctx->stream));
     *handle = ctx->next_handle++;
-    ctx->canvases[*handle] = cv;
+    ctx->canvases.emplace(*handle, std::move(cv));
     return VFSMS_OK;
 }
 // the canvas behind a handle; `who`: the entry point, for the message
@@ -1967,12 +1971,8 @@ extern "C" int vfsms_canvas_free(vfsms_ctx *ctx, int64_t handle)
     CTX_ENTER(ctx);
     CanvasRec *cv;
     TRY(canvas_find(ctx, "canvas_free", handle, &cv));
-    if (ctx->has_spare_canvas) {                               // one spare at a time: the older one goes back to the device
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        CanvasRec &o = ctx->spare_canvas;
-        HIP_TRY(hipFree(o.pix)); HIP_TRY(hipFree(o.mask)); HIP_TRY(hipFree(o.d_err)); HIP_TRY(hipFree(o.scratch)); HIP_TRY(hipFree(o.pyr)); jpeg_scratch_free(&o.jpeg);
-    }
-    ctx->spare_canvas = *cv; ctx->has_spare_canvas = true;      // kept for a canvas of the same size (stream order makes the reuse safe)
+    TRY(canvas_release(ctx, ctx->spare_canvas));               // one spare at a time: the older one goes back to the device
+    ctx->spare_canvas = std::move(*cv);                        // kept for a canvas of the same size (stream order makes the reuse safe)
     ctx->canvases.erase(handle);
     return VFSMS_OK;
 }
@@ -2171,8 +2171,8 @@ static int canvas_read_rows(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int n
 {
     const size_t pitch = (size_t)cv->cols * cv->ch;
     int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, cv->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (nrows > 0) HIP_TRY(hipMemcpyAsync(out, cv->pix + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&err, cv->d_err.as<int>(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (nrows > 0) HIP_TRY(hipMemcpyAsync(out, cv->pix.as<uint8_t>() + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (err) {
         vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
@@ -2220,14 +2220,9 @@ extern "C" int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas
     }
     const size_t need = pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, levels);
     if (cap_levels < need) { vfsms_set_error("%s: the levels take %zu bytes, out_levels holds %zu", who, need, cap_levels); return VFSMS_ERR_BAD_ARG; }
-    if (cv->pyr_bytes < need) {                                 // first use, or a larger band than before
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipFree(cv->pyr)); cv->pyr = nullptr; cv->pyr_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&cv->pyr, need));
-        cv->pyr_bytes = need;
-    }
-    TRY(pyramid_band_device(ctx, cv, row0, nrows, levels, cv->pyr));
-    HIP_TRY(hipMemcpyAsync(out_levels, cv->pyr, need, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(cv->pyr.reserve(need, ctx->stream));                    // first use, or a larger band than before
+    TRY(pyramid_band_device(ctx, cv, row0, nrows, levels, cv->pyr.as<uint8_t>()));
+    HIP_TRY(hipMemcpyAsync(out_levels, cv->pyr.as<uint8_t>(), need, hipMemcpyDeviceToHost, ctx->stream));
     if (out0) return canvas_read_rows(ctx, cv, row0, nrows, out0);
     return canvas_read_rows(ctx, cv, 0, 0, nullptr);             // (the sticky flag and the synchronisation alone)
 }
@@ -2255,8 +2250,8 @@ extern "C" int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int
         return VFSMS_ERR_BAD_ARG;
     }
     int err = 0;                                                   // the sticky geometry flag, as vfsms_canvas_download_rows reads it
-    HIP_TRY(hipMemcpyAsync(&err, cv->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TRY(jpeg_encode_band_device(ctx, &cv->jpeg, cv->pix, cv->rows, cv->cols, cv->ch, (size_t)cv->cols * cv->ch, 1, row0, nrows, quality, interval, out, cap, nbytes));
+    HIP_TRY(hipMemcpyAsync(&err, cv->d_err.as<int>(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TRY(jpeg_encode_band_device(ctx, &cv->jpeg, cv->pix.as<uint8_t>(), cv->rows, cv->cols, cv->ch, (size_t)cv->cols * cv->ch, 1, row0, nrows, quality, interval, out, cap, nbytes));
     if (err) {
         vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
         return VFSMS_ERR_BAD_ARG;
@@ -2279,15 +2274,10 @@ extern "C" int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int 
     TRY(vfsms_jpeg_header(h, w, ch, quality, restart_mcus, out, out ? cap : 0, &hn) == VFSMS_ERR_BAD_ARG ? VFSMS_ERR_BAD_ARG : VFSMS_OK);
     JpegScratch *s = &ctx->jpeg_scratch;
     const size_t pitch = (size_t)w * ch, bytes = pitch * h;
-    if (s->img_bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipFree(s->img)); s->img = nullptr; s->img_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&s->img, bytes));
-        s->img_bytes = bytes;
-    }
-    HIP_TRY(hipMemcpy2DAsync(s->img, pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    TRY(s->img.reserve(bytes, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(s->img.as<void>(), pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     const bool room = out && cap > hn + 2;
-    const int rc = jpeg_encode_band_device(ctx, s, s->img, h, w, ch, pitch, bgr != 0, 0, h, quality, interval, room ? out + hn : nullptr, room ? cap - hn - 2 : 0, &bn);
+    const int rc = jpeg_encode_band_device(ctx, s, s->img.as<uint8_t>(), h, w, ch, pitch, bgr != 0, 0, h, quality, interval, room ? out + hn : nullptr, room ? cap - hn - 2 : 0, &bn);
     *nbytes = hn + bn + 2;
     if (rc != VFSMS_OK) return rc;
     out[hn + bn] = 0xFF; out[hn + bn + 1] = 0xD9;
@@ -2316,8 +2306,8 @@ static int shade_field_new(vfsms_ctx *ctx, int h, int w, int ch, bool estimated,
 {
     const size_t P = (size_t)h * w * ch, Pa = (P + 127) & ~(size_t)127;      // the three planes stay 256-byte aligned
     F->h = h; F->w = w; F->ch = ch; F->estimated = estimated; F->q8 = nullptr; F->prof = nullptr;
-    HIP_TRY(hipMalloc((void **)&F->gain, estimated ? Pa * 5 : Pa * 2));
-    if (estimated) { F->q8 = F->gain + Pa; F->prof = (uint8_t *)(F->q8 + Pa); }
+    TRY(F->gain.reserve(estimated ? Pa * 5 : Pa * 2, ctx->stream));
+    if (estimated) { F->q8 = F->gain.as<uint16_t>() + Pa; F->prof = (uint8_t *)(F->q8 + Pa); }
     return VFSMS_OK;
 }
 extern "C" int vfsms_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *tiles, int percentile, int radius, int64_t *field)
@@ -2335,11 +2325,11 @@ extern "C" int vfsms_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *tile
     ctx->pinned_off = 0;
     ShadeRec F;
     TRY(shade_field_new(ctx, T[0]->h, T[0]->w, T[0]->ch, true, &F));
-    int rc = shade_estimate_device(ctx, H.data(), n, F.h, F.w, F.ch, percentile, radius, F.gain, F.q8, F.prof);
+    int rc = shade_estimate_device(ctx, H.data(), n, F.h, F.w, F.ch, percentile, radius, F.gain.as<uint16_t>(), F.q8, F.prof);
     if (rc == VFSMS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { vfsms_set_error("shading_estimate: the kernels failed"); rc = VFSMS_ERR_HIP; }
-    if (rc != VFSMS_OK) { hipFree(F.gain); return rc; }
+    if (rc != VFSMS_OK) { hipStreamSynchronize(ctx->stream); return rc; }      // (the field goes with F; nothing enqueued may still write it)
     *field = ctx->next_handle++;
-    ctx->shade_fields[*field] = F;
+    ctx->shade_fields.emplace(*field, std::move(F));
     return VFSMS_OK;
 }
 extern "C" int vfsms_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int h, int w, int ch, int64_t *field)
@@ -2348,11 +2338,11 @@ extern "C" int vfsms_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int
     if (!gain || !field || h <= 0 || w <= 0 || ch < 1 || ch > 4) { vfsms_set_error("shading_from_gain: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     ShadeRec F;
     TRY(shade_field_new(ctx, h, w, ch, false, &F));
-    if (hipMemcpy(F.gain, gain, sizeof(uint16_t) * (size_t)h * w * ch, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(F.gain); vfsms_set_error("shading_from_gain: the upload failed"); return VFSMS_ERR_HIP;
+    if (hipMemcpy(F.gain.as<void>(), gain, sizeof(uint16_t) * (size_t)h * w * ch, hipMemcpyHostToDevice) != hipSuccess) {
+        vfsms_set_error("shading_from_gain: the upload failed"); return VFSMS_ERR_HIP;
     }
     *field = ctx->next_handle++;
-    ctx->shade_fields[*field] = F;
+    ctx->shade_fields.emplace(*field, std::move(F));
     return VFSMS_OK;
 }
 extern "C" int vfsms_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *gain, uint16_t *smooth_q8, uint8_t *profile)
@@ -2363,7 +2353,7 @@ extern "C" int vfsms_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *g
     if (!gain) { vfsms_set_error("shading_download: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     const ShadeRec &F = it->second;
     const size_t P = (size_t)F.h * F.w * F.ch;
-    HIP_TRY(hipMemcpyAsync(gain, F.gain, sizeof(uint16_t) * P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(gain, F.gain.as<uint16_t>(), sizeof(uint16_t) * P, hipMemcpyDeviceToHost, ctx->stream));
     if (smooth_q8) { if (F.estimated) HIP_TRY(hipMemcpyAsync(smooth_q8, F.q8, sizeof(uint16_t) * P, hipMemcpyDeviceToHost, ctx->stream)); else memset(smooth_q8, 0, sizeof(uint16_t) * P); }
     if (profile) { if (F.estimated) HIP_TRY(hipMemcpyAsync(profile, F.prof, P, hipMemcpyDeviceToHost, ctx->stream)); else memset(profile, 0, P); }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2391,7 +2381,7 @@ extern "C" int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const i
     }
     TRY(ctx_arena_reserve(ctx, sizeof(ShadeTileHost) * 2 * (size_t)n + 65536));
     ctx->pinned_off = 0;
-    TRY(shade_apply_device(ctx, H.data(), n, F.h, F.w, F.ch, F.gain));
+    TRY(shade_apply_device(ctx, H.data(), n, F.h, F.w, F.ch, F.gain.as<uint16_t>()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));            // the tile table went through the pinned staging buffer: synchronous like every call that uses it
     return VFSMS_OK;
 }
@@ -2400,8 +2390,7 @@ extern "C" int vfsms_shading_free(vfsms_ctx *ctx, int64_t field)
     CTX_ENTER(ctx);
     auto it = ctx->shade_fields.find(field);
     if (it == ctx->shade_fields.end()) { vfsms_set_error("shading_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipFree(it->second.gain));
+    TRY(it->second.gain.release(ctx->stream));
     ctx->shade_fields.erase(it);
     return VFSMS_OK;
 }

@@ -10,25 +10,10 @@
 #include <vector>
 #include "../../include/vfsms.h"
 #include "arena_walk.h"
+#include "device_buf.h"                // with hip_try.h: vfsms_set_error, HIP_TRY, TRY
 
 #define VFSMS_MAX_LAYERS 32      // (nOctaveLayers + 2) * nOctaves
 #define VFSMS_MAX_WIN 768        // SURF descriptor window side upper bound (size <= 264 -> 739)
-
-// ---- error plumbing ------------------------------------------------------------------------------
-void vfsms_set_error(const char *fmt, ...);
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            vfsms_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return VFSMS_ERR_HIP;                                                             \
-        }                                                                                     \
-    } while (0)
-#define TRY(expr)                  \
-    do {                           \
-        int _r = (expr);           \
-        if (_r != VFSMS_OK) return _r; \
-    } while (0)
 
 // ---- fast-Hessian layer description (host-built, device-resident table) ---------------------------
 #define VFSMS_MAX_OCTAVES 8
@@ -140,7 +125,7 @@ struct EnhJob { const uint8_t *src; int stride, h, w, eh, ew; uint8_t *dst; int 
 
 // ---- device-resident feature set (keypoints + descriptors of one image; Stitcher.tempImageFeature's payload) ---------------
 struct FeatRec { float *kps_xy; void *desc; int n, dim; int64_t block = 0; };   // kps_xy / desc point into the shared allocation `block` (feat_blocks); a set without keypoints: block 0, null pointers
-struct FeatBlock { void *base; int refs; };
+struct FeatBlock { DevBuf base; int refs; };
 
 // ---- one (query ROI, train ROI) matching job --------------------------------------------------------
 struct MatchDev {
@@ -180,8 +165,10 @@ struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device st
 struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
 // device scratch of the JPEG encoder (jpeg_enc_kernels.hip), grown to the largest band seen: quantised coefficients, interval sizes + offsets,
 // the coded stream, and (vfsms_jpeg_encode_device only) the staged image
-struct JpegScratch { int16_t *coef = nullptr; size_t coef_bytes = 0; void *sizes = nullptr; size_t sizes_bytes = 0; uint8_t *out = nullptr; size_t out_bytes = 0; uint8_t *img = nullptr; size_t img_bytes = 0; };
-struct CanvasRec { uint8_t *pix; uint8_t *mask; int rows, cols, ch; int *d_err; void *scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; uint8_t *pyr = nullptr; size_t pyr_bytes = 0; JpegScratch jpeg; };   // jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct JpegScratch { DevBuf coef, sizes, out, img; };
+// move-only: the record owns its buffers wherever it lies (the canvas map, the context's spare slot, a canvas under construction); an
+// empty record owns nothing.  Destroying one frees without a synchronisation: api.hip's canvas_release synchronises first
+struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; };   // jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent
@@ -189,31 +176,31 @@ struct PhasePeak { double v; long long idx; };                      // a peak of
 // comes from the arena (phase_peaks_bytes)
 struct PhasePeakSink { int K; PhasePeak *peaks; };
 struct ProfRec { int id; hipEvent_t a, b; };
-struct ShadeRec { int h, w, ch; uint16_t *gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
-struct SiftChunk { char *p; size_t bytes, off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
+struct ShadeRec { int h, w, ch; DevBuf gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
+struct SiftChunk { DevBuf mem; size_t off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
 
 struct vfsms_ctx {
-    int device;
-    hipStream_t stream;
+    int device = 0;
+    hipStream_t stream = nullptr;
     // bump arena for per-call scratch
-    char *arena; size_t arena_size; size_t arena_off;
+    DevBuf arena; size_t arena_off = 0;
     // pinned staging for small results
-    char *pinned; size_t pinned_size; size_t pinned_off;
-    int kp_cap_override;
+    PinBuf pinned; size_t pinned_off = 0;
+    int kp_cap_override = 0;
     int offset_estimator = VFSMS_OFFSET_MODE, offset_tol = 3;   // the vote tail of every fused path (vfsms_ctx_set_offset_estimator)
     int offset_verifier = VFSMS_VERIFY_NONE, verify_min_pixels = 0; double verify_threshold = 0.0;   // the acceptance check behind that tail (vfsms_ctx_set_offset_verifier)
     int phase_resolver = VFSMS_PHASE_RESOLVE_NONE, phase_peaks = 2, phase_min_pixels = 4096; double phase_threshold = 0.5;   // method 2 of vfsms_pairs_offsets (vfsms_ctx_set_phase_resolver)
     // SURF tables
-    vfsms_surf_params cur_params; bool tables_valid;
-    LayerPat *d_layers; int n_layers;
-    SurfTables *d_tables;
-    void *d_area_tab = nullptr;          // INTER_AREA tables of every descriptor-window size (ctx_prepare_area_tab)
-    vfsms_orb_params cur_orb; bool orb_valid; OrbTables *d_orb_tables;
+    vfsms_surf_params cur_params = {}; bool tables_valid = false;
+    DevBuf d_layers; int n_layers = 0;   // LayerPat[VFSMS_MAX_LAYERS]
+    DevBuf d_tables;                     // SurfTables
+    DevBuf d_area_tab;                   // INTER_AREA tables of every descriptor-window size (ctx_prepare_area_tab)
+    vfsms_orb_params cur_orb = {}; bool orb_valid = false; DevBuf d_orb_tables;   // OrbTables
     std::unordered_map<int64_t, TileRec> tiles;
     std::mutex tiles_mu; std::condition_variable tiles_cv;   // reserved tiles are filled by other threads (vfsms_tile_fill*): they look tiles up and write TileRec::fill / pending under this mutex and enqueue on the copy stream; the map's structure, the buffer / event pools and the arena belong to the context's own thread
     std::mutex stage_mu; std::vector<StageBuf> stage_pool;   // device staging buffers of the decoder threads (vfsms_tile_fill_pair), the pools they share
     std::vector<StageBuf> pin_pool;                          // pinned host staging of the same threads (also under stage_mu)
-    hipStream_t copy_stream;                                  // H2D uploads of tiles, overlapped with compute (vfsms_tile_upload_async)
+    hipStream_t copy_stream = nullptr;                            // H2D uploads of tiles, overlapped with compute (vfsms_tile_upload_async)
     // second compute stream: the MFMA-bound 2-NN search of the first part of a batch runs on it beside the VALU / TA-bound detect stage of
     // the second part (attempt_surf_impl); created on first use, always joined back into `stream` before a call returns
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -221,23 +208,23 @@ struct vfsms_ctx {
     size_t tile_pool_bytes = 0;
     std::vector<hipEvent_t> event_pool;
     std::unordered_map<int64_t, CanvasRec> canvases;
-    void *mb_scratch = nullptr; size_t mb_scratch_bytes = 0;
-    void *seam_scratch = nullptr; size_t seam_scratch_bytes = 0;   // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
-    void *shade_scratch = nullptr; size_t shade_scratch_bytes = 0; // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
+    DevBuf mb_scratch;                                             // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
+    DevBuf seam_scratch;                                           // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
+    DevBuf shade_scratch;                                          // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
     std::unordered_map<int64_t, ShadeRec> shade_fields;
-    void *sift_scratch = nullptr; size_t sift_scratch_bytes = 0;   // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
-    void *sift_kp = nullptr; size_t sift_kp_bytes = 0;             // SIFT candidates, keypoints and descriptors, likewise   // fp32 pyramid planes of the multi-band blend (multiband_kernels.hip): grown to the largest blend, freed with the context
+    DevBuf sift_scratch;                                           // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
+    DevBuf sift_kp;                                                // SIFT candidates, keypoints and descriptors, likewise
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
     size_t sift_group_bytes = (size_t)4 << 30;                     // pyramid bytes resident at once in a fused SIFT batch (VFSMS_SIFT_GROUP_BYTES overrides)
     JpegScratch jpeg_scratch;                                      // vfsms_jpeg_encode_device's scratch, freed with the context
-    CanvasRec spare_canvas; bool has_spare_canvas = false;   // the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
+    CanvasRec spare_canvas;                                  // (or an empty record) the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a call (vfsms_features_surf, one set; vfsms_features_surf_batch, a chunk's), freed with its last set
-    int64_t next_handle;
+    int64_t next_handle = 1;
     std::list<FftPlan> plans;            // list: get_plan hands out stable pointers
-    std::vector<std::pair<int, void *>> fft_tabs;   // twiddle tables exp(-2 pi i q / L) of the LDS transforms of phase_kernels.hip, one per length
+    std::vector<std::pair<int, DevBuf>> fft_tabs;   // twiddle tables exp(-2 pi i q / L) of the LDS transforms of phase_kernels.hip, one per length
     // optional per-stage timing with HIP events on this context's stream (vfsms_profile_*)
-    bool prof_on;
+    bool prof_on = false;
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
     std::vector<std::string> prof_names;
@@ -393,7 +380,6 @@ const uint8_t *jpeg_std_huff_bits(int ac, int chroma);
 const uint8_t *jpeg_std_huff_vals(int ac, int chroma);
 void jpeg_quant_tables(int quality, uint8_t q[2][64]);
 int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality, int restart_mcus, int *interval);
-void jpeg_scratch_free(JpegScratch *s);
 int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
                             int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes);
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
@@ -408,7 +394,6 @@ struct SiftSrcHost { const uint8_t *p; int stride; };
 struct SiftStripOut { int n; int cand0; float *xy; float *desc; int8_t *d8; int *nrm; };   // n keypoints: positions, float descriptors, packed rows + norms (sift_pad_rows(n) rows)
 static inline size_t sift_pad_rows(int n) { return ((size_t)n + 63) & ~(size_t)63; }
 void sift_pool_reset(vfsms_ctx *ctx);
-void sift_pool_free(vfsms_ctx *ctx);
 void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes);
 struct SiftStripDev { float *pyr, *t0, *t1; int *counts; };     // one strip's block of ctx->sift_scratch
 void sift_strip_layout(ArenaWalk &a, SiftStripDev *d, size_t pyr_floats, size_t max_plane, int nslots);

@@ -692,7 +692,7 @@ static long long canvas_valid_area(const CanvasRec *cv, int ry0, int rx0, int ry
 
 static TileOnCanvas tile_on_canvas(const CanvasRec *cv, const uint8_t *d_tile, const Placement &p)
 {
-    return TileOnCanvas{cv->pix, cv->mask, cv->cols, cv->ch, d_tile, p.h, p.w, p.y0, p.x0, p.ry0, p.rx0, p.r(), p.c()};
+    return TileOnCanvas{cv->pix.as<uint8_t>(), cv->mask.as<uint8_t>(), cv->cols, cv->ch, d_tile, p.h, p.w, p.y0, p.x0, p.ry0, p.rx0, p.r(), p.c()};
 }
 
 int canvas_blend_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p)
@@ -741,8 +741,8 @@ size_t canvas_scratch_bytes(int rows, int cols) { return canvas_scratch_layout(n
 int canvas_scratch_init(vfsms_ctx *ctx, CanvasRec *cv)
 {
     FuseCanvasScratch S;
-    canvas_scratch_layout(cv->scratch, cv->rows, cv->cols, &S);
-    HIP_TRY(hipMemsetAsync(cv->scratch, 0, (char *)S.rowFirstEnc - (char *)cv->scratch, ctx->stream));               // out, done
+    canvas_scratch_layout(cv->scratch.as<void>(), cv->rows, cv->cols, &S);
+    HIP_TRY(hipMemsetAsync(cv->scratch.as<void>(), 0, (char *)S.rowFirstEnc - (char *)cv->scratch.as<void>(), ctx->stream));               // out, done
     HIP_TRY(hipMemsetAsync(S.rowFirstEnc, 0xff, (char *)S.wAr - (char *)S.rowFirstEnc, ctx->stream));             // every record starts at -1
     return VFSMS_OK;
 }
@@ -858,20 +858,20 @@ int canvas_fuse_device(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, con
     ProfScope ps(ctx, "fuse");
     const FuseGeomKind kind = fuse_geom_kind(cv, p);
     FuseCanvasScratch S;
-    canvas_scratch_layout(cv->scratch, cv->rows, cv->cols, &S);
+    canvas_scratch_layout(cv->scratch.as<void>(), cv->rows, cv->cols, &S);
     int seam_wmax = std::min(r, c);
     if (kind == GEOM_RAMPS || kind == GEOM_PICKS) {       // one statistics launch ahead of the operator
         CanvasView V;
-        V.pix = cv->pix; V.mask = cv->mask; V.ccols = cv->cols; V.ch = cv->ch; V.ry0 = p.ry0; V.rx0 = p.rx0;
+        V.pix = cv->pix.as<uint8_t>(); V.mask = cv->mask.as<uint8_t>(); V.ccols = cv->cols; V.ch = cv->ch; V.ry0 = p.ry0; V.rx0 = p.rx0;
         V.tile = d_tile; V.tw = p.w; V.ty0 = p.ry0 - p.y0; V.tx0 = p.rx0 - p.x0;
         const int wx_n = c <= 256 ? 1 : c <= 512 ? 2 : 4, wy_n = FUSE_NW / wx_n;
         const dim3 sgrid((c + 256 * wx_n - 1) / (256 * wx_n), (r + FUSE_SB * wy_n - 1) / (FUSE_SB * wy_n));
         if (kind == GEOM_PICKS) {
             const CornerPick P = corner_picks(cv, p);
-            hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err, wx_n);
+            hipLaunchKernelGGL((k_fuse_counts_pick<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, P, cv->d_err.as<int>(), wx_n);
             seam_wmax = p.mode == VFSMS_CANVAS_SEAMLINE ? corner_picks_wmax(P, r, c) : 1;
         } else {
-            hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, p.dx, p.dy, cv->d_err, wx_n);
+            hipLaunchKernelGGL((k_fuse_stats_weights<FUSE_SB, FUSE_SB>), sgrid, dim3(FUSE_NW * 64), 0, ctx->stream, V, r, c, S, p.dx, p.dy, cv->d_err.as<int>(), wx_n);
             seam_wmax = std::max(r, c);
         }
     }

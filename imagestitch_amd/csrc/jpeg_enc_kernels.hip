@@ -378,23 +378,7 @@ void huff_derive(const uint8_t *bits, const uint8_t *vals, uint32_t *table)
     }
 }
 
-int grow(void **p, size_t *have, size_t need, hipStream_t stream)
-{
-    if (*have >= need) return VFSMS_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipFree(*p)); *p = nullptr; *have = 0;
-    HIP_TRY(hipMalloc(p, need));
-    *have = need;
-    return VFSMS_OK;
-}
-
 }  // namespace
-
-void jpeg_scratch_free(JpegScratch *s)
-{
-    hipFree(s->coef); hipFree(s->sizes); hipFree(s->out); hipFree(s->img);
-    *s = JpegScratch();
-}
 
 // The entropy-coded bytes of rows [row0, row0 + nrows) of the rows x cols x ch image at d_img (256-byte aligned, `pitch` bytes a row) into
 // `out` on the host.  api.hip has checked the band contract: row0 is a multiple of the MCU height, the MCUs in front of the band are whole
@@ -423,15 +407,15 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     const int n_int = (int)((n_mcu + interval - 1) / interval);
     const bool last = row0 + nrows >= rows;
 
-    TRY(grow((void **)&s->coef, &s->coef_bytes, (size_t)n_mcu * bpm * 128, ctx->stream));
-    TRY(grow((void **)&s->sizes, &s->sizes_bytes, (size_t)n_int * 4 + 256 + ((size_t)n_int + 1) * 8 + sizeof(int), ctx->stream));
-    uint32_t *d_sizes = (uint32_t *)s->sizes;
-    unsigned long long *d_offs = (unsigned long long *)((char *)s->sizes + (((size_t)n_int * 4 + 255) & ~(size_t)255));
+    TRY(s->coef.reserve((size_t)n_mcu * bpm * 128, ctx->stream));
+    TRY(s->sizes.reserve((size_t)n_int * 4 + 256 + ((size_t)n_int + 1) * 8 + sizeof(int), ctx->stream));
+    uint32_t *d_sizes = s->sizes.as<uint32_t>();
+    unsigned long long *d_offs = (unsigned long long *)(s->sizes.as<char>() + (((size_t)n_int * 4 + 255) & ~(size_t)255));
     int *d_err = (int *)(d_offs + n_int + 1);
 
     JpegXformArgs x;
     x.src = d_img; x.src_bytes = (size_t)rows * pitch; x.pitch = pitch; x.rows = rows; x.cols = cols; x.row0 = row0; x.mw = mw; x.bgr = bgr;
-    x.coef = s->coef;
+    x.coef = s->coef.as<int16_t>();
     uint8_t q[2][64];
     jpeg_quant_tables(quality, q);
     for (int t = 0; t < 2; t++) for (int k = 0; k < 64; k++) {
@@ -447,7 +431,7 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
         HIP_TRY(hipGetLastError());
     }
     JpegEntropyArgs e;
-    e.coef = s->coef; e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = n_int; e.first_int = (int)(((long long)(row0 / mcu) * mw) / interval);
+    e.coef = s->coef.as<int16_t>(); e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = n_int; e.first_int = (int)(((long long)(row0 / mcu) * mw) / interval);
     e.last_marker = last ? 0 : 1; e.bpm = bpm; e.sizes = d_sizes; e.offs = d_offs; e.out = nullptr; e.cap = 0; e.err = d_err;
     unsigned long long total = 0;
     {
@@ -460,8 +444,8 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *nbytes = (size_t)total;
     if (!out || cap < total) { vfsms_set_error("jpeg_encode: the band takes %llu bytes, the buffer holds %zu", total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
-    TRY(grow((void **)&s->out, &s->out_bytes, ((size_t)total + 15) & ~(size_t)15, ctx->stream));
-    e.out = s->out; e.cap = s->out_bytes;
+    TRY(s->out.reserve(((size_t)total + 15) & ~(size_t)15, ctx->stream));
+    e.out = s->out.as<uint8_t>(); e.cap = s->out.bytes();
     int err = 0;
     {
         ProfScope ps(ctx, "jpeg_encode.entropy");
@@ -472,9 +456,9 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     {
         ProfScope ps(ctx, "jpeg_encode.copy");
         HIP_TRY(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out, s->out, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out, s->out.as<uint8_t>(), (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (err) { vfsms_set_error("jpeg_encode: the coded band outgrew the %zu bytes counted for it", s->out_bytes); return VFSMS_ERR_CAPACITY; }
+    if (err) { vfsms_set_error("jpeg_encode: the coded band outgrew the %zu bytes counted for it", s->out.bytes()); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
 }

@@ -236,19 +236,6 @@ static size_t mb_layout(int r, int c, int ch, int N, MbPyr *P, char *base)
     return off;
 }
 
-static int mb_reserve(vfsms_ctx *ctx, size_t bytes)
-{
-    if (ctx->mb_scratch_bytes >= bytes) return VFSMS_OK;
-    if (ctx->mb_scratch) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));           // enqueued blends may still read the old planes
-        HIP_TRY(hipFree(ctx->mb_scratch));
-        ctx->mb_scratch = nullptr; ctx->mb_scratch_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&ctx->mb_scratch, bytes));
-    ctx->mb_scratch_bytes = bytes;
-    return VFSMS_OK;
-}
-
 template <int CH>
 static MbCoarseO<CH> mb_coarse_o(const MbPyr &P, int k)      // O of level k (k >= 1) as the reconstruct of level k - 1 reads it
 {
@@ -280,10 +267,10 @@ static int mb_pyramid(vfsms_ctx *ctx, const MbPyr &P, const Src0 &S0)
 template <int CH>
 static int mb_canvas_ch(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const Placement &p, const SeamGeom &G, const MbPyr &P)
 {
-    const Mb0Canvas<CH> S0 = {cv->pix, cv->mask, cv->cols, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0, G};
+    const Mb0Canvas<CH> S0 = {cv->pix.as<uint8_t>(), cv->mask.as<uint8_t>(), cv->cols, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0, G};
     TRY(mb_pyramid<CH>(ctx, P, S0));
     hipLaunchKernelGGL((k_mb_up_canvas<CH>), dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, S0, MbPlane<CH>{P.ga[1], P.w[1]},
-                       MbPlane<CH>{P.gb[1], P.w[1]}, mb_coarse_o<CH>(P, 1), P.h[1], P.w[1], cv->pix, cv->mask, p.y0, p.x0, p.h, p.w, p.r(), p.c());
+                       MbPlane<CH>{P.gb[1], P.w[1]}, mb_coarse_o<CH>(P, 1), P.h[1], P.w[1], cv->pix.as<uint8_t>(), cv->mask.as<uint8_t>(), p.y0, p.x0, p.h, p.w, p.r(), p.c());
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }
@@ -293,8 +280,8 @@ int mb_blend_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const 
 {
     ProfScope ps(ctx, "fuse_multiband");
     MbPyr P;
-    TRY(mb_reserve(ctx, mb_layout(p.r(), p.c(), cv->ch, levels, &P, nullptr)));
-    mb_layout(p.r(), p.c(), cv->ch, levels, &P, (char *)ctx->mb_scratch);
+    TRY(ctx->mb_scratch.reserve(mb_layout(p.r(), p.c(), cv->ch, levels, &P, nullptr), ctx->stream));
+    mb_layout(p.r(), p.c(), cv->ch, levels, &P, ctx->mb_scratch.as<char>());
     switch (cv->ch) {
     case 1: return mb_canvas_ch<1>(ctx, cv, d_tile, p, G, P);
     case 2: return mb_canvas_ch<2>(ctx, cv, d_tile, p, G, P);
@@ -321,8 +308,8 @@ int mb_blend_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r
 {
     ProfScope ps(ctx, "fuse_multiband");
     MbPyr P;
-    TRY(mb_reserve(ctx, mb_layout(r, c, ch, levels, &P, nullptr)));
-    mb_layout(r, c, ch, levels, &P, (char *)ctx->mb_scratch);
+    TRY(ctx->mb_scratch.reserve(mb_layout(r, c, ch, levels, &P, nullptr), ctx->stream));
+    mb_layout(r, c, ch, levels, &P, ctx->mb_scratch.as<char>());
     switch (ch) {
     case 1: return mb_i64_ch<1>(ctx, dA, dB, r, c, G, P, d_out);
     case 2: return mb_i64_ch<2>(ctx, dA, dB, r, c, G, P, d_out);

@@ -624,7 +624,7 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
                 hipLaunchKernelGGL(k_orb_fast_nms, dim3(plan.first[nl], q.count), dim3(256), 0, ctx->stream, d_rois + q.first, nl,
                                    p->fast_threshold < 0 ? 0 : p->fast_threshold > 255 ? 255 : p->fast_threshold, p->edge_threshold, plan);
         }
-        hipLaunchKernelGGL(k_orb_threshold, dim3((nrois * nl + 63) / 64), dim3(64), 0, ctx->stream, d_rois, nrois, nl, ctx->d_orb_tables);
+        hipLaunchKernelGGL(k_orb_threshold, dim3((nrois * nl + 63) / 64), dim3(64), 0, ctx->stream, d_rois, nrois, nl, ctx->d_orb_tables.as<OrbTables>());
     }
     {
         ProfScope ps(ctx, "orb_select");
@@ -632,8 +632,8 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
         hipLaunchKernelGGL(k_orb_chunk_scan, dim3(nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl);
         hipLaunchKernelGGL(k_orb_scatter, dim3(ORB_CHUNKS, nrois * nl), dim3(1024), 0, ctx->stream, d_rois, nl);
         hipLaunchKernelGGL(k_orb_harris, dim3((maxcap1 + 255) / 256, nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl);
-        hipLaunchKernelGGL(k_orb_select2, dim3(nrois * nl), dim3(1024), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables);
-        hipLaunchKernelGGL(k_orb_angle, dim3((maxcap2 + 3) / 4, nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables);
+        hipLaunchKernelGGL(k_orb_select2, dim3(nrois * nl), dim3(1024), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables.as<OrbTables>());
+        hipLaunchKernelGGL(k_orb_angle, dim3((maxcap2 + 3) / 4, nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables.as<OrbTables>());
     }
     {
         ProfScope ps(ctx, "orb_describe");
@@ -645,9 +645,9 @@ int launch_orb(vfsms_ctx *ctx, const OrbDev *d_rois, const OrbDev *h_rois, int n
                 plan.tiles_x[l] = tx; plan.first[l + 1] = plan.first[l] + tx * ty;
             }
             if (plan.first[nl] > 0)
-                hipLaunchKernelGGL(k_orb_blur, dim3(plan.first[nl], q.count), dim3(256), 0, ctx->stream, d_rois + q.first, nl, ctx->d_orb_tables, plan);
+                hipLaunchKernelGGL(k_orb_blur, dim3(plan.first[nl], q.count), dim3(256), 0, ctx->stream, d_rois + q.first, nl, ctx->d_orb_tables.as<OrbTables>(), plan);
         }
-        hipLaunchKernelGGL(k_orb_describe, dim3((maxcap2 + 7) / 8, 1, nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables);
+        hipLaunchKernelGGL(k_orb_describe, dim3((maxcap2 + 7) / 8, 1, nrois * nl), dim3(256), 0, ctx->stream, d_rois, nl, ctx->d_orb_tables.as<OrbTables>());
     }
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
@@ -703,8 +703,8 @@ int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p)
         }
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!ctx->d_orb_tables) HIP_TRY(hipMalloc((void **)&ctx->d_orb_tables, sizeof(OrbTables)));
-    HIP_TRY(hipMemcpy(ctx->d_orb_tables, &T, sizeof(T), hipMemcpyHostToDevice));
+    TRY(ctx->d_orb_tables.reserve(sizeof(OrbTables), ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->d_orb_tables.as<OrbTables>(), &T, sizeof(T), hipMemcpyHostToDevice));
     ctx->cur_orb = *p; ctx->orb_valid = true;
     return VFSMS_OK;
 }

@@ -711,8 +711,6 @@ int phase_destroy_plans(vfsms_ctx *ctx)
         rocfft_execution_info_destroy((rocfft_execution_info)p.fwd_info); rocfft_execution_info_destroy((rocfft_execution_info)p.inv_info);
     }
     ctx->plans.clear();
-    for (auto &t : ctx->fft_tabs) hipFree(t.second);
-    ctx->fft_tabs.clear();
     return VFSMS_OK;
 }
 
@@ -807,7 +805,7 @@ static FftSched make_sched(int L, int Ltab)      // Ltab: length of the twiddle 
 // exp(-2 pi i q / L), q = 0 .. L-1, rounded from long double; cached per length for the life of the context
 static int get_tab(vfsms_ctx *ctx, int L, const cplx **out)
 {
-    for (auto &t : ctx->fft_tabs) if (t.first == L) { *out = (const cplx *)t.second; return VFSMS_OK; }
+    for (auto &t : ctx->fft_tabs) if (t.first == L) { *out = t.second.as<cplx>(); return VFSMS_OK; }
     std::vector<cplx> h(L);
     const long double tau = 6.283185307179586476925286766559005768L;
     for (int q = 0; q < L; q++) {
@@ -819,11 +817,11 @@ static int get_tab(vfsms_ctx *ctx, int L, const cplx **out)
         if (4 * q == 3 * L) { h[q].x = 0.0; h[q].y = 1.0; }
     }
     h[0].x = 1.0; h[0].y = 0.0;
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(cplx) * L));
-    HIP_TRY(hipMemcpy(d, h.data(), sizeof(cplx) * L, hipMemcpyHostToDevice));
-    ctx->fft_tabs.push_back({L, d});
-    *out = (const cplx *)d;
+    DevBuf d;
+    TRY(d.reserve(sizeof(cplx) * L, ctx->stream));
+    HIP_TRY(hipMemcpy(d.as<void>(), h.data(), sizeof(cplx) * L, hipMemcpyHostToDevice));
+    *out = d.as<cplx>();
+    ctx->fft_tabs.emplace_back(L, std::move(d));
     return VFSMS_OK;
 }
 

@@ -194,7 +194,7 @@ int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows
     }
     ProfScope ps(ctx, "pyramid");
     PyrArgs a;
-    a.src = cv->pix; a.src_bytes = (size_t)cv->rows * cv->cols * cv->ch; a.src_row0 = 0;
+    a.src = cv->pix.as<uint8_t>(); a.src_bytes = (size_t)cv->rows * cv->cols * cv->ch; a.src_row0 = 0;
     a.R0 = cv->rows; a.C0 = cv->cols; a.row_begin = row0; a.row_end = row0 + nrows;
     a.nl = levels < PYR_MAX_STEP ? levels : PYR_MAX_STEP;
     for (int k = 0; k < PYR_MAX_STEP; k++) a.dst[k] = k < a.nl ? lvl[k + 1] : nullptr;

@@ -346,19 +346,6 @@ __global__ __launch_bounds__(256) void k_seam_apply_canvas(SeamCanvas S, SeamArg
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------
-static int seam_reserve(vfsms_ctx *ctx, size_t bytes)
-{
-    if (ctx->seam_scratch_bytes >= bytes) return VFSMS_OK;
-    if (ctx->seam_scratch) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));           // enqueued seams may still use the old planes
-        HIP_TRY(hipFree(ctx->seam_scratch));
-        ctx->seam_scratch = nullptr; ctx->seam_scratch_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&ctx->seam_scratch, bytes));
-    ctx->seam_scratch_bytes = bytes;
-    return VFSMS_OK;
-}
-
 // the register path's cap (VFSMS_SEAM_REG_CAP lowers it, 0 = wide kernel only: tests, A/B runs)
 static int seam_kcap()
 {
@@ -383,8 +370,8 @@ static int seam_setup(vfsms_ctx *ctx, int hostkind, int r, int c, int dx, int dy
     const size_t oP0 = take(v ? (size_t)r * pitch : 0), oP1 = take(h ? (size_t)c * pitch : 0);
     const size_t oS = take(sizeof(int) * ((size_t)r + c)), oEnd = take(sizeof(int) * 2);
     const size_t oWide = take(R->K ? 0 : sizeof(int) * 4 * pitch), oLab = take(want_label ? (size_t)r * c : 0);
-    TRY(seam_reserve(ctx, off));
-    char *base = (char *)ctx->seam_scratch;
+    TRY(ctx->seam_scratch.reserve(off, ctx->stream));
+    char *base = ctx->seam_scratch.as<char>();
     SeamArgs &a = R->a;
     a.hostkind = hostkind; a.r = r; a.c = c; a.dx = dx; a.dy = dy; a.mode = mode;
     a.E[0] = (uint16_t *)(base + oE0); a.E[1] = (uint16_t *)(base + oE1);
@@ -418,7 +405,7 @@ int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const
     const int r = p.r(), c = p.c();
     SeamRun R;
     TRY(seam_setup(ctx, hostkind, r, c, p.dx, p.dy, mode, wmax, blend != 0, &R));
-    const SeamCanvas S = {cv->pix, cv->mask, cv->cols, cv->ch, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0};
+    const SeamCanvas S = {cv->pix.as<uint8_t>(), cv->mask.as<uint8_t>(), cv->cols, cv->ch, p.ry0, p.rx0, d_tile, p.w, p.ry0 - p.y0, p.rx0 - p.x0};
     const dim3 rgrid((c + 255) / 256, r);
     {
         ProfScope ps(ctx, "seam_energy");
@@ -435,7 +422,7 @@ int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const
         return mb_blend_canvas(ctx, cv, d_tile, p, G, levels);
     }
     ProfScope ps(ctx, "seam_apply");
-    hipLaunchKernelGGL(k_seam_apply_canvas, dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, S, R.a, cv->pix, cv->mask, p.y0, p.x0, p.h, p.w);
+    hipLaunchKernelGGL(k_seam_apply_canvas, dim3((p.w + 255) / 256, p.h), dim3(256), 0, ctx->stream, S, R.a, cv->pix.as<uint8_t>(), cv->mask.as<uint8_t>(), p.y0, p.x0, p.h, p.w);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
 }

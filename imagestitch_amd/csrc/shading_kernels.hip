@@ -172,19 +172,6 @@ __global__ __launch_bounds__(256) void k_shade_apply(const ShadeTile *tiles, int
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------------
-static int shade_scratch(vfsms_ctx *ctx, size_t bytes)
-{
-    if (ctx->shade_scratch_bytes >= bytes) return VFSMS_OK;
-    if (ctx->shade_scratch) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipFree(ctx->shade_scratch));
-        ctx->shade_scratch = nullptr; ctx->shade_scratch_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&ctx->shade_scratch, bytes));
-    ctx->shade_scratch_bytes = bytes;
-    return VFSMS_OK;
-}
-
 static int shade_table(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int wb, size_t align, ShadeTile **d_tiles, int *dense)
 {
     std::vector<ShadeTile> T(n);
@@ -205,9 +192,9 @@ int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int
     if (total64 > 0x7fffffffu || h > 65535) { vfsms_set_error("shading_estimate: tiles of more than 2^31 - 1 bytes or 65535 rows are not supported"); return VFSMS_ERR_UNSUPPORTED; }
     const unsigned total = (unsigned)total64;
     // scratch: the uint32 row sums, then 4 channel sums and 4 channel means
-    TRY(shade_scratch(ctx, total64 * 4 + 256));
-    uint32_t *rows = (uint32_t *)ctx->shade_scratch;
-    unsigned long long *sums = (unsigned long long *)((char *)ctx->shade_scratch + ((total64 * 4 + 63) & ~(size_t)63));
+    TRY(ctx->shade_scratch.reserve(total64 * 4 + 256, ctx->stream));
+    uint32_t *rows = ctx->shade_scratch.as<uint32_t>();
+    unsigned long long *sums = (unsigned long long *)(ctx->shade_scratch.as<char>() + ((total64 * 4 + 63) & ~(size_t)63));
     uint32_t *mean = (uint32_t *)(sums + 4);
     ShadeTile *d_tiles; int dense;
     TRY(shade_table(ctx, tiles, n, wb, 4, &d_tiles, &dense));

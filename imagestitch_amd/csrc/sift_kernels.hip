@@ -596,16 +596,6 @@ static int sift_plan(int h, int w, const vfsms_sift_params *p, SiftPlan *P)
     return VFSMS_OK;
 }
 
-static int sift_grow(void **buf, size_t *have, size_t need, hipStream_t st)
-{
-    if (*have >= need) return VFSMS_OK;
-    if (*buf) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(*buf)); *buf = nullptr; *have = 0; }
-    const size_t want = need + need / 4;
-    HIP_TRY(hipMalloc(buf, want));
-    *have = want;
-    return VFSMS_OK;
-}
-
 static void sift_octs(const SiftPlan &P, float *pyr, SiftOcts *Os)
 {
     memset(Os, 0, sizeof(*Os));
@@ -620,21 +610,17 @@ static void sift_octs(const SiftPlan &P, float *pyr, SiftOcts *Os)
 
 // ---- memory that outlives a group: chunks kept by the context, handed out by a bump pointer, all free again at the next call ----------
 void sift_pool_reset(vfsms_ctx *ctx) { for (auto &c : ctx->sift_pool) c.off = 0; }
-void sift_pool_free(vfsms_ctx *ctx)
-{
-    for (auto &c : ctx->sift_pool) if (c.p) hipFree(c.p);
-    ctx->sift_pool.clear();
-}
 void *sift_pool_alloc(vfsms_ctx *ctx, size_t bytes)
 {
     bytes = ((bytes ? bytes : 1) + 255) & ~(size_t)255;
     for (auto &c : ctx->sift_pool)
-        if (c.off + bytes <= c.bytes) { void *r = c.p + c.off; c.off += bytes; return r; }
+        if (c.off + bytes <= c.mem.bytes()) { void *r = c.mem.as<char>() + c.off; c.off += bytes; return r; }
     SiftChunk c;
-    c.bytes = std::max(bytes, (size_t)256 << 20); c.off = bytes; c.p = nullptr;
-    if (hipMalloc((void **)&c.p, c.bytes) != hipSuccess) { vfsms_set_error("sift: out of device memory (%zu bytes)", c.bytes); return nullptr; }
-    ctx->sift_pool.push_back(c);
-    return c.p;
+    const size_t want = std::max(bytes, (size_t)256 << 20);
+    c.off = bytes;
+    if (c.mem.reserve(want, ctx->stream) != VFSMS_OK) { vfsms_set_error("sift: out of device memory (%zu bytes)", want); return nullptr; }
+    ctx->sift_pool.push_back(std::move(c));
+    return ctx->sift_pool.back().mem.as<void>();
 }
 
 // The one place that knows one strip's block in ctx->sift_scratch: [pyramid][2 planes of the largest level][row counts + their scan],
@@ -654,8 +640,8 @@ static int sift_build_pyramid(vfsms_ctx *ctx, const SiftSrc *d_srcs, int g, int 
                               size_t *zs_out)
 {
     const size_t sb = sift_strip_bytes(P);
-    TRY(sift_grow(&ctx->sift_scratch, &ctx->sift_scratch_bytes, sb * g + 4096, ctx->stream));
-    ArenaWalk a{(char *)ctx->sift_scratch, 0, ctx->sift_scratch_bytes}; SiftStripDev d;
+    TRY(ctx->sift_scratch.reserve(sb * g + 4096, ctx->stream, (sb * g + 4096) / 4));
+    ArenaWalk a{ctx->sift_scratch.as<char>(), 0, ctx->sift_scratch.bytes()}; SiftStripDev d;
     sift_strip_layout(a, &d, P.pyr_floats, P.max_plane, P.nslots);           // the first strip's; strip k's lies k * sb behind
     if (!a.ok) { vfsms_set_error("sift: pyramid scratch too small"); return VFSMS_ERR_CAPACITY; }
     float *pyr = d.pyr, *t0 = d.t0, *t1 = d.t1;
@@ -792,8 +778,8 @@ int sift_group_device(vfsms_ctx *ctx, const SiftSrcHost *srcs, int g, int h, int
     };
     ArenaWalk count;
     kp_layout(count);
-    TRY(sift_grow(&ctx->sift_kp, &ctx->sift_kp_bytes, count.off + 4096, st));
-    ArenaWalk a{(char *)ctx->sift_kp, 0, ctx->sift_kp_bytes};
+    TRY(ctx->sift_kp.reserve(count.off + 4096, st, (count.off + 4096) / 4));
+    ArenaWalk a{ctx->sift_kp.as<char>(), 0, ctx->sift_kp.bytes()};
     kp_layout(a);
     if (!a.ok) { vfsms_set_error("sift: keypoint scratch too small"); return VFSMS_ERR_CAPACITY; }
     SiftOcts *d_os; SiftSeg *d_segs;

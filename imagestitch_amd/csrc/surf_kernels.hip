@@ -2168,9 +2168,9 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
                     const int lrows = q.h / step, lcols = q.w / step;
                     if (lrows > 0 && lcols > 0) {
                         if (o == 0)
-                            hipLaunchKernelGGL((k_hessian_lds<1, 64, 4>), dim3((lcols + 63) / 64, (lrows + 15) / 16, q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers, lpo, o);
+                            hipLaunchKernelGGL((k_hessian_lds<1, 64, 4>), dim3((lcols + 63) / 64, (lrows + 15) / 16, q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers.as<LayerPat>(), lpo, o);
                         else
-                            hipLaunchKernelGGL((k_hessian_lds<2, 32, HESS_O1_WAVES>), dim3((lcols + 31) / 32, (lrows + 15) / 16, q.count), dim3(64, HESS_O1_WAVES), 0, ctx->stream, dq, ctx->d_layers, lpo, o);
+                            hipLaunchKernelGGL((k_hessian_lds<2, 32, HESS_O1_WAVES>), dim3((lcols + 31) / 32, (lrows + 15) / 16, q.count), dim3(64, HESS_O1_WAVES), 0, ctx->stream, dq, ctx->d_layers.as<LayerPat>(), lpo, o);
                     }
                     step *= 2;
                 }
@@ -2180,7 +2180,7 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
                 const int s0 = 36;                                           // the octave's smallest layer has the most samples
                 if (q.h >= s0 && q.w >= s0) {
                     const int tiles_i = ((q.h - s0) / 4 + 1 + 1) / 2, tiles_j = ((q.w - s0) / 4 + 1 + 127) / 128;
-                    hipLaunchKernelGGL(k_hessian_rows2, dim3((unsigned)(tiles_i * tiles_j * 5 * q.count)), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers, lpo,
+                    hipLaunchKernelGGL(k_hessian_rows2, dim3((unsigned)(tiles_i * tiles_j * 5 * q.count)), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers.as<LayerPat>(), lpo,
                                        tiles_i, tiles_j, q.count);
                 }
                 o++; step *= 2;
@@ -2196,9 +2196,9 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
             }
             if (plan.noct > 0 && plan.first[plan.noct] > 0) {
                 if (lpo == 5 && plan.o0 >= 2 && plan.o0 + plan.noct <= 4 && !generic)       // the stock pyramid: constant-offset taps
-                    hipLaunchKernelGGL(k_hessian_coarse, dim3((unsigned)plan.first[plan.noct] * lpo * q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers, lpo, plan, q.count);
+                    hipLaunchKernelGGL(k_hessian_coarse, dim3((unsigned)plan.first[plan.noct] * lpo * q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers.as<LayerPat>(), lpo, plan, q.count);
                 else
-                    hipLaunchKernelGGL(k_hessian, dim3((unsigned)plan.first[plan.noct] * lpo * q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers, lpo, plan, q.count);
+                    hipLaunchKernelGGL(k_hessian, dim3((unsigned)plan.first[plan.noct] * lpo * q.count), dim3(64, 4), 0, ctx->stream, dq, ctx->d_layers.as<LayerPat>(), lpo, plan, q.count);
             }
         }
     }
@@ -2217,7 +2217,7 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
             }
             if (plan.noct > 0 && plan.first[plan.noct] > 0)
                 hipLaunchKernelGGL(k_nms, dim3(plan.first[plan.noct], q.count * p->n_octave_layers), dim3(64, 4), 0, ctx->stream, d_rois + q.first,
-                                   ctx->d_layers, lpo, p->n_octave_layers, plan, p->hessian_threshold);
+                                   ctx->d_layers.as<LayerPat>(), lpo, p->n_octave_layers, plan, p->hessian_threshold);
         }
     }
     {
@@ -2225,10 +2225,10 @@ int launch_surf_detect(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_roi
         static const bool n2sort = getenv("VFSMS_SORT_N2") && atoi(getenv("VFSMS_SORT_N2")) != 0;
         int mincap = maxcap;
         for (int r = 0; r < nrois; r++) mincap = h_rois[r].cap < mincap ? h_rois[r].cap : mincap;
-        if (n2sort || mincap < SORT_BUCKETS) hipLaunchKernelGGL(k_rank_sort, dim3((maxcap + 63) / 64, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_layers);
+        if (n2sort || mincap < SORT_BUCKETS) hipLaunchKernelGGL(k_rank_sort, dim3((maxcap + 63) / 64, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_layers.as<LayerPat>());
         else {
             hipLaunchKernelGGL(k_bucket_sort, dim3(nrois), dim3(1024), 0, ctx->stream, d_rois);
-            hipLaunchKernelGGL(k_bucket_rank, dim3((maxcap + 255) / 256, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_layers);
+            hipLaunchKernelGGL(k_bucket_rank, dim3((maxcap + 255) / 256, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_layers.as<LayerPat>());
         }
     }
     HIP_TRY(hipGetLastError());
@@ -2279,8 +2279,8 @@ int ctx_prepare_area_tab(vfsms_ctx *ctx)
         rec[21].mode = !fast ? 0 : iscale == 2 ? 2 : 1;
     }
     for (int win = 0; win < dsz; win++) memcpy(tab.data() + (size_t)win * AREA_RECS, tab.data() + (size_t)dsz * AREA_RECS, sizeof(AreaRec) * AREA_RECS);
-    HIP_TRY(hipMalloc((void **)&ctx->d_area_tab, sizeof(AreaRec) * tab.size()));
-    HIP_TRY(hipMemcpy(ctx->d_area_tab, tab.data(), sizeof(AreaRec) * tab.size(), hipMemcpyHostToDevice));
+    TRY(ctx->d_area_tab.reserve(sizeof(AreaRec) * tab.size(), ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->d_area_tab.as<void>(), tab.data(), sizeof(AreaRec) * tab.size(), hipMemcpyHostToDevice));
     return VFSMS_OK;
 }
 
@@ -2294,7 +2294,7 @@ int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_r
     for (int r = 0; r < nrois; r++) maxcap = h_rois[r].cap > maxcap ? h_rois[r].cap : maxcap;
     {
         ProfScope ps(ctx, "orientation");
-        hipLaunchKernelGGL(k_orientation, dim3((maxcap + ORI_KP - 1) / ORI_KP, nrois), dim3(ORI_KP * 128), 0, ctx->stream, d_rois, ctx->d_tables, p->upright);
+        hipLaunchKernelGGL(k_orientation, dim3((maxcap + ORI_KP - 1) / ORI_KP, nrois), dim3(ORI_KP * 128), 0, ctx->stream, d_rois, ctx->d_tables.as<SurfTables>(), p->upright);
     }
     {
         ProfScope ps(ctx, "compact");
@@ -2314,10 +2314,10 @@ int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_r
         hipLaunchKernelGGL(k_desc_plan, dim3(1), dim3(256), 0, ctx->stream, d_rois, nrois, W.plan, 256 * DESC_WGS);
         hipLaunchKernelGGL(k_desc_recs, dim3((maxcap + 255) / 256, nrois), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_big, W.rec_small, p->upright);
         hipLaunchKernelGGL(k_describe, dim3(256 * DESC_WGS), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_big, W.tickets,
-                           ctx->d_tables, (const AreaRec *)ctx->d_area_tab, p->extended, p->upright);
+                           ctx->d_tables.as<SurfTables>(), ctx->d_area_tab.as<AreaRec>(), p->extended, p->upright);
         hipLaunchKernelGGL(k_describe_small, dim3(256 * DESC_SMALL_WGS), dim3(256), 0, ctx->stream, d_rois, W.plan, W.rec_small,
-                           W.tickets + DESC_HEADS * DESC_HEAD_STRIDE, (const AreaRec *)ctx->d_area_tab, p->upright);
-        hipLaunchKernelGGL(k_desc_tail, dim3((maxcap + 15) / 16, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_tables, p->extended);
+                           W.tickets + DESC_HEADS * DESC_HEAD_STRIDE, ctx->d_area_tab.as<AreaRec>(), p->upright);
+        hipLaunchKernelGGL(k_desc_tail, dim3((maxcap + 15) / 16, nrois), dim3(256), 0, ctx->stream, d_rois, ctx->d_tables.as<SurfTables>(), p->extended);
     }
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;

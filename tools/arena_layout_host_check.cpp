@@ -4,11 +4,12 @@
 //       -I/opt/rocm/include -I imagestitch_amd/csrc tools/arena_layout_host_check.cpp -o /tmp/alhc -L imagestitch_amd/lib -lvfsms \
 //       -Wl,-rpath,$PWD/imagestitch_amd/lib -Wl,-rpath,/opt/rocm/lib && /tmp/alhc
 // (the sanitizer runtimes are linked into the program, so it runs as it is, with nothing preloaded; tests/test_arena_layout_host.py does this)
-// No HIP call, no GPU: a context here is three fields around a malloc'ed buffer.  For every record and shape: the counting walk gives
+// No GPU, and no HIP runtime at work: a context here is its arena, a DevBuf whose allocation is hip_host_stubs.h's malloc.  For every record and shape: the counting walk gives
 // `bytes`; a carve into exactly `bytes` succeeds, ends at `bytes` and leaves every pointer inside the buffer; a carve into
 // bytes - 256 latches ok == false and ctx_arena_commit answers VFSMS_ERR_CAPACITY without moving the arena.
 // Left out: the rocFFT path of phase_layout (a shape phase_own_shape refuses) -- its work buffer size comes from a rocFFT plan, which
 // needs a device; its counting and carving halves are the same function as the LDS path's, and its peak lists are checked here.
+#include "hip_host_stubs.h"
 #include "common.h"
 #include <math.h>
 #include <stdio.h>
@@ -30,22 +31,20 @@ static int check_record(const char *what, const std::function<void(ArenaWalk &, 
     CHECK(c.ok && c.base == nullptr && c.off > 0 && !p.empty());
     for (const void *q : p) CHECK(q == nullptr);                       // a counting walk hands out nothing to dereference
     const size_t bytes = c.off;
-    char *buf = (char *)malloc(bytes);
-    vfsms_ctx ctx;
-    ctx.arena = buf; ctx.arena_size = bytes; ctx.arena_off = 0;
+    vfsms_ctx ctx, small;
+    CHECK(ctx.arena.reserve(bytes, nullptr) == VFSMS_OK && small.arena.reserve(bytes > 256 ? bytes - 256 : bytes - 1, nullptr) == VFSMS_OK);
+    const char *buf = ctx.arena.as<char>();
     ArenaWalk a = ctx_arena_walk(&ctx);
     p.clear();
     layout(a, p);
     CHECK(a.ok && a.off == bytes);
     CHECK(ctx_arena_commit(&ctx, a, what) == VFSMS_OK && ctx.arena_off == bytes);
     for (const void *q : p) CHECK(q != nullptr && (const char *)q >= buf && (const char *)q < buf + bytes);
-    ctx.arena_size = bytes > 256 ? bytes - 256 : bytes - 1; ctx.arena_off = 0;
-    ArenaWalk s = ctx_arena_walk(&ctx);
+    ArenaWalk s = ctx_arena_walk(&small);
     p.clear();
     layout(s, p);
-    CHECK(!s.ok && s.off <= ctx.arena_size);
-    CHECK(ctx_arena_commit(&ctx, s, what) == VFSMS_ERR_CAPACITY && ctx.arena_off == 0);
-    free(buf);
+    CHECK(!s.ok && s.off <= small.arena.bytes());
+    CHECK(ctx_arena_commit(&small, s, what) == VFSMS_ERR_CAPACITY && small.arena_off == 0);
     g_records++;
     return 0;
 }
@@ -143,13 +142,10 @@ int main()
         if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_filter_layout(a, &m, s[0], s[1], s[2]); p.insert(p.end(), {m.c_ent, m.c_cnt, m.q16, m.t16, m.c_m12}); })) return 1;
         // the carve entry points answer for themselves: exactly enough, then 256 bytes short
         const size_t bytes = match_filter_bytes(s[0], s[1], s[2]);
-        char *buf = (char *)malloc(bytes);
-        vfsms_ctx ctx; MatchDev m = {};
-        ctx.arena = buf; ctx.arena_size = bytes; ctx.arena_off = 0;
+        vfsms_ctx ctx, small; MatchDev m = {};
+        CHECK(ctx.arena.reserve(bytes, nullptr) == VFSMS_OK && small.arena.reserve(bytes - 256, nullptr) == VFSMS_OK);
         CHECK(match_filter_carve(&ctx, &m, s[0], s[1], s[2]) == VFSMS_OK && ctx.arena_off == bytes && m.c_m12 != nullptr);
-        ctx.arena_size = bytes - 256; ctx.arena_off = 0;
-        CHECK(match_filter_carve(&ctx, &m, s[0], s[1], s[2]) == VFSMS_ERR_CAPACITY && ctx.arena_off == 0);
-        free(buf);
+        CHECK(match_filter_carve(&small, &m, s[0], s[1], s[2]) == VFSMS_ERR_CAPACITY && small.arena_off == 0);
     }
     // ORB ROI
     const int orb_shapes[][4] = {{31, 31, 8, 5000}, {64, 2048, 8, 5000}, {31, 31, 1, 5000}, {64, 2048, 8, 1}, {64, 2048, 1, 1}};
