@@ -935,22 +935,97 @@ static bool bf_force_exact()
     return v;
 }
 
-static int bf_l2_host(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim, MatchDev *M, bool with_ratio, double ratio)
+// ---- one 2-NN search + vote run: n (query set, train set) jobs in fused launches ------------------------------------------------------
+// The phases mirror a SURF run's: match_run_bytes into the caller's ONE ctx_arena_reserve, match_run_carve (wires and uploads the
+// records), match_run_launch over one or more ranges of the jobs, match_run_readback in front of the caller's synchronisation.
+// k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows / k_bf_hamming_jobs on 32-byte rows behind q, t
+// SEARCH_NONE: the caller has filled the jobs' pairs (MatchJob::pairs_given), and the tail starts from them
+enum MatchSearch { SEARCH_NONE, SEARCH_FLOAT, SEARCH_I8_D128, SEARCH_HAMMING };
+// 64-d descriptors leave the descriptor kernel with norm <= 1: their 2-NN search runs as an MFMA candidate filter plus exact verification
+// (match_kernels.hip); other widths, or VFSMS_BF_EXACT=1, take the exhaustive VALU kernel.  The split counts follow the set sizes the
+// CALLER expects, (fq, ft) for the filter and (eq, et) for the exhaustive kernel: the true counts of feature sets, the typical occupancy
+// of the capacity in a fused batch.
+static MatchPlan match_plan_float(int dim, int njobs, int fq, int ft, int eq, int et)
 {
-    const int capq = std::max(nq, 1);
-    const int ns_exact = pick_nsplit(nq, nt, 1, dim);
-    const int cns = pick_filter_nsplit(nq, 1, nt);
+    MatchPlan P;
+    P.filtered = dim == 64 && !bf_force_exact();
+    P.cns = pick_filter_nsplit(fq, njobs, ft);
+    P.ns = P.filtered ? 1 : pick_nsplit(eq, et, njobs, dim);
+    return P;
+}
+// the raw pixels of a job's two strips, for the overlap check behind the vote (verify_kernels.hip)
+static void match_set_strips(MatchDev *m, const StripTable::Strip &A, const StripTable::Strip &B)
+{
+    m->va = A.p; m->vsa = A.stride; m->vb = B.p; m->vsb = B.stride; m->vh = A.h; m->vw = A.w;
+}
+// The one place that knows a run's arena block: the result rows (one block: one copy back), per job its arrays, the uploaded records
+void match_run_layout(ArenaWalk &a, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
+{
+    run->P = P; run->dim = dim; run->M.assign(n, MatchDev{});
+    run->rblock = a.take<int32_t>(VFSMS_ATTEMPT_INTS * (size_t)n);
+    for (int k = 0; k < n; k++) {
+        MatchDev &m = run->M[k];
+        match_layout(a, &m, J[k].capq, dim, P.ns);
+        if (P.filtered) match_filter_layout(a, &m, J[k].capq, J[k].capt, P.cns);
+        m.result = run->rblock ? run->rblock + VFSMS_ATTEMPT_INTS * J[k].row : nullptr;
+        m.q = J[k].q; m.t = J[k].t; m.kq = J[k].kq; m.kt = J[k].kt; m.nq_ptr = J[k].nq_ptr; m.nt_ptr = J[k].nt_ptr;
+        m.q8 = J[k].q8; m.t8 = J[k].t8; m.qn2 = J[k].qn2; m.tn2 = J[k].tn2; m.pairs_given = J[k].pairs_given;
+        if (J[k].sa) match_set_strips(&m, *J[k].sa, *J[k].sb);
+    }
+    run->dM = a.take<MatchDev>(n);
+}
+static size_t match_run_bytes(const MatchJob *J, int n, const MatchPlan &P) { ArenaWalk a; MatchRun run; match_run_layout(a, &run, J, n, 0, P); return a.off; }
+static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
+{
+    ArenaWalk a = ctx_arena_walk(ctx);
+    match_run_layout(a, run, J, n, dim, P);
+    TRY(ctx_arena_commit(ctx, a, "arena exhausted while carving a match run"));
+    return ctx_copy_small(ctx, run->M.data(), sizeof(MatchDev) * n, run->dM);
+}
+// the search of `search`, then the tail (common.h: MatchTailKind), of jobs [first, first + count); maxq / maxt: the largest query / train set to cover
+static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search, const MatchTail &tail)
+{
+    const MatchDev *dM = run.dM + first;
+    if (search == SEARCH_HAMMING) { TRY(launch_bf_hamming(ctx, dM, count, maxq, run.P.ns, tail.max_dist)); }
+    else if (search == SEARCH_I8_D128) { TRY(launch_bf_i8_d128(ctx, dM, count, maxq, run.P.ns)); }
+    else if (search == SEARCH_FLOAT && run.P.filtered) { TRY(launch_bf_l2_filtered(ctx, dM, count, maxq, maxt, run.P.cns)); }
+    else if (search == SEARCH_FLOAT) { TRY(launch_bf_l2(ctx, dM, count, maxq, run.P.ns, run.dim)); }
+    return launch_match_tail(ctx, dM, count, maxq, tail);
+}
+static int match_run_readback(vfsms_ctx *ctx, const MatchRun &run, int32_t *rows)
+{
+    HIP_TRY(hipMemcpyAsync(rows, run.rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * run.M.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return VFSMS_OK;
+}
+
+// the (nq, nt) of n jobs, on the device behind J[k].nq_ptr / nt_ptr.  Through the pinned staging buffer (free again: entry points are
+// synchronous), which takes its copy NOW: cnt may leave scope before the stream runs
+static int match_upload_counts(vfsms_ctx *ctx, MatchJob *J, int n, const int *cnt)
+{
+    int *d;
+    ctx->pinned_off = 0;
+    TRY(ctx_upload_small(ctx, cnt, sizeof(int) * 2 * n, (void **)&d));
+    for (int k = 0; k < n; k++) { J[k].nq_ptr = d + 2 * k; J[k].nt_ptr = d + 2 * k + 1; }
+    return VFSMS_OK;
+}
+
+// ---- the matcher operators: one job each, on a match run ----------------------------------------------------------------------------
+// vfsms_bf_l2_knn2 / _ratio: one job of host descriptors.  Rows of norm <= 1 (SURF's are L2-normalised) take the MFMA-filtered plan,
+// anything else the exhaustive one: a probe in front of the run decides, and ONE reservation covers the larger of the two
+static int bf_l2_host(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim, MatchRun *run, const MatchTail &tail)
+{
+    MatchJob J{};
+    J.capq = std::max(nq, 1); J.capt = std::max(nt, 1);
+    const MatchPlan exhaustive{false, pick_nsplit(nq, nt, 1, dim), 0}, filter{true, 1, pick_filter_nsplit(nq, 1, nt)};
     const bool try_filter = dim == 64 && nq > 0 && nt > 0 && !bf_force_exact();
-    TRY(ctx_arena_reserve(ctx, sizeof(float) * ((size_t)nq + nt) * dim + match_bytes(capq, ns_exact) +
-                               (try_filter ? match_filter_bytes(capq, std::max(nt, 1), cns) : 0) + 65536));
-    memset(M, 0, sizeof(*M));
+    TRY(ctx_arena_reserve(ctx, sizeof(float) * ((size_t)nq + nt) * dim +
+                               std::max(match_run_bytes(&J, 1, exhaustive), try_filter ? match_run_bytes(&J, 1, filter) : 0) + 65536));
     float *dq, *dt;
     TRY(upload_array(ctx, q, (size_t)nq * dim, &dq));
     TRY(upload_array(ctx, t, (size_t)nt * dim, &dt));
-    int cnt[2] = {nq, nt}; int *dcnt;
-    ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
-    TRY(ctx_upload_small(ctx, cnt, sizeof(cnt), (void **)&dcnt));   // copied into pinned staging now: `cnt` may leave scope before the stream runs
-    // descriptors of norm <= 1 (SURF's are L2-normalised) take the MFMA-filtered search; anything else the exhaustive kernel
+    J.q = dq; J.t = dt;
+    const int cnt[2] = {nq, nt};
+    TRY(match_upload_counts(ctx, &J, 1, cnt));
     bool filtered = false;
     if (try_filter) {
         unsigned *d_max = (unsigned *)ctx_arena_alloc(ctx, sizeof(unsigned));
@@ -963,20 +1038,8 @@ static int bf_l2_host(vfsms_ctx *ctx, const float *q, int nq, const float *t, in
         float m; memcpy(&m, &bits, sizeof(m));
         filtered = m <= 1.0001f;
     }
-    const int ns = filtered ? 1 : ns_exact;
-    TRY(match_carve(ctx, M, capq, dim, ns));
-    if (filtered) TRY(match_filter_carve(ctx, M, capq, std::max(nt, 1), cns));
-    M->q = dq; M->t = dt; M->nq_ptr = dcnt; M->nt_ptr = dcnt + 1; M->kq = nullptr; M->kt = nullptr;
-    MatchDev *dM;
-    TRY(upload_array(ctx, M, 1, &dM));
-    if (filtered) { TRY(launch_bf_l2_filtered(ctx, dM, 1, capq, std::max(nt, 1), cns)); }
-    else { TRY(launch_bf_l2(ctx, dM, 1, capq, ns, dim)); }
-    if (with_ratio) {
-        TRY(launch_ratio_only(ctx, dM, 1, capq, ratio));
-    } else {
-        TRY(launch_merge_only(ctx, dM, 1, capq));
-    }
-    return VFSMS_OK;
+    TRY(match_run_carve(ctx, run, &J, 1, dim, filtered ? filter : exhaustive));
+    return match_run_launch(ctx, *run, 0, 1, J.capq, J.capt, SEARCH_FLOAT, tail);
 }
 
 extern "C" int vfsms_bf_l2_knn2_ratio(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim,
@@ -986,8 +1049,9 @@ extern "C" int vfsms_bf_l2_knn2_ratio(vfsms_ctx *ctx, const float *q, int nq, co
     if (!m_out || nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) { vfsms_set_error("bf_l2: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     *m_out = 0;
     if (nq == 0 || nt == 0) return VFSMS_OK;
-    MatchDev M;
-    TRY(bf_l2_host(ctx, q, nq, t, nt, dim, &M, true, ratio));
+    MatchRun run;
+    TRY(bf_l2_host(ctx, q, nq, t, nt, dim, &run, MatchTail{TAIL_PAIRS, ratio, -1, 0}));
+    const MatchDev &M = run.M[0];
     int mc[4];
     HIP_TRY(hipMemcpyAsync(mc, M.mcount, sizeof(mc), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1010,8 +1074,9 @@ extern "C" int vfsms_bf_l2_knn2(vfsms_ctx *ctx, const float *q, int nq, const fl
         for (int i = 0; i < nq; i++) { if (idx1) idx1[i] = -1; if (d1) d1[i] = INFINITY; if (d2) d2[i] = INFINITY; }
         return VFSMS_OK;
     }
-    MatchDev M;
-    TRY(bf_l2_host(ctx, q, nq, t, nt, dim, &M, false, 0.0));
+    MatchRun run;
+    TRY(bf_l2_host(ctx, q, nq, t, nt, dim, &run, MatchTail{TAIL_KNN, 0.0, -1, 0}));
+    const MatchDev &M = run.M[0];
     if (idx1) HIP_TRY(hipMemcpyAsync(idx1, M.i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
     if (d1) HIP_TRY(hipMemcpyAsync(d1, M.d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
     if (d2) HIP_TRY(hipMemcpyAsync(d2, M.d2, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
@@ -1028,22 +1093,22 @@ extern "C" int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, con
     if (nq == 0 || nt == 0) return VFSMS_OK;
     if (nbytes != 32) { vfsms_set_error("bf_hamming: only 32-byte descriptors supported"); return VFSMS_ERR_UNSUPPORTED; }
     // one job of the batched matcher without keypoints, hence without votes: the merged 1-NN comes back and the pair list is built here
-    const int ns = pick_hamming_nsplit(nq, 1);
-    TRY(ctx_arena_reserve(ctx, ((size_t)nq + nt) * 32 + match_bytes(nq, ns) + 65536));
+    MatchJob J{};
+    J.capq = nq; J.capt = nt;
+    const MatchPlan P{false, pick_hamming_nsplit(nq, 1), 0};
+    TRY(ctx_arena_reserve(ctx, ((size_t)nq + nt) * 32 + match_run_bytes(&J, 1, P) + 65536));
     uint8_t *dq, *dt;
     TRY(upload_array(ctx, q, (size_t)nq * 32, &dq));
     TRY(upload_array(ctx, t, (size_t)nt * 32, &dt));
-    int cnt[2] = {nq, nt}; int *dcnt;
-    ctx->pinned_off = 0;                                    // entry points are synchronous: the staging buffer is free again
-    TRY(ctx_upload_small(ctx, cnt, sizeof(cnt), (void **)&dcnt));
-    MatchDev M, *dM; memset(&M, 0, sizeof(M));
-    TRY(match_carve(ctx, &M, nq, 32, ns));
-    M.q = (const float *)dq; M.t = (const float *)dt; M.nq_ptr = dcnt; M.nt_ptr = dcnt + 1;
-    TRY(upload_array(ctx, &M, 1, &dM));
-    TRY(launch_bf_hamming(ctx, dM, 1, nq, ns, max_dist));
+    J.q = (const float *)dq; J.t = (const float *)dt;
+    const int cnt[2] = {nq, nt};
+    TRY(match_upload_counts(ctx, &J, 1, cnt));
+    MatchRun run;
+    TRY(match_run_carve(ctx, &run, &J, 1, 32, P));
+    TRY(match_run_launch(ctx, run, 0, 1, nq, nt, SEARCH_HAMMING, MatchTail{TAIL_KNN, 0.0, max_dist, 0, true}));
     std::vector<int> hi(nq); std::vector<float> hd(nq);
-    HIP_TRY(hipMemcpyAsync(hi.data(), M.i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hd.data(), M.d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hi.data(), run.M[0].i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hd.data(), run.M[0].d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int m = 0;
     for (int i = 0; i < nq; i++) {
@@ -1057,7 +1122,7 @@ extern "C" int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, con
     return VFSMS_OK;
 }
 
-// vfsms_mode_offset / vfsms_consensus_offset: one job of explicit matches through the vote tail of the named estimator
+// vfsms_mode_offset / vfsms_consensus_offset: one job of the caller's matches, no search, through the tail of the named estimator
 static int offset_from_pairs(vfsms_ctx *ctx, const char *what, const float *kpsA, int nA, const float *kpsB, int nB,
                              const int32_t *pairs, int m, int estimator, int tol, int offset_evaluate, int32_t *out4)
 {
@@ -1069,21 +1134,22 @@ static int offset_from_pairs(vfsms_ctx *ctx, const char *what, const float *kpsA
         if (pairs[2 * k] < 0 || pairs[2 * k] >= nB || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= nA) {
             vfsms_set_error("%s: match index out of range", what); return VFSMS_ERR_BAD_ARG;
         }
-    TRY(ctx_arena_reserve(ctx, sizeof(float) * 2 * ((size_t)nA + nB) + match_bytes(m, 1) + 65536));
-    MatchDev M; memset(&M, 0, sizeof(M));
+    MatchJob J{};
+    J.capq = J.capt = m; J.pairs_given = 1;
+    const MatchPlan P{false, 1, 0};
+    TRY(ctx_arena_reserve(ctx, sizeof(float) * 2 * ((size_t)nA + nB) + match_run_bytes(&J, 1, P) + 65536));
     float *dA, *dB;
     TRY(upload_array(ctx, kpsA, (size_t)2 * nA, &dA));
     TRY(upload_array(ctx, kpsB, (size_t)2 * nB, &dB));
-    int cnt[2] = {m, m}; int *dcnt;
-    TRY(upload_array(ctx, cnt, 2, &dcnt));
-    TRY(match_carve(ctx, &M, m, 64, 1));
-    M.kq = dA; M.kt = dB; M.nq_ptr = dcnt; M.nt_ptr = dcnt + 1; M.pairs_given = 1;
-    HIP_TRY(hipMemcpyAsync(M.pairs, pairs, sizeof(int32_t) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
-    MatchDev *dM;
-    TRY(upload_array(ctx, &M, 1, &dM));
-    TRY(launch_mode_only(ctx, dM, 1, m, estimator, tol, offset_evaluate));
+    J.kq = dA; J.kt = dB;
+    const int cnt[2] = {m, m};
+    TRY(match_upload_counts(ctx, &J, 1, cnt));
+    MatchRun run;
+    TRY(match_run_carve(ctx, &run, &J, 1, 64, P));
+    HIP_TRY(hipMemcpyAsync(run.M[0].pairs, pairs, sizeof(int32_t) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
+    TRY(match_run_launch(ctx, run, 0, 1, m, m, SEARCH_NONE, MatchTail{TAIL_GIVEN_PAIRS, 0.0, -1, offset_evaluate, false, estimator, tol}));
     int32_t res[VFSMS_ATTEMPT_INTS];
-    HIP_TRY(hipMemcpyAsync(res, M.result, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+    TRY(match_run_readback(ctx, run, res));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 4; k++) out4[k] = res[k];
     return VFSMS_OK;
@@ -1270,11 +1336,6 @@ static int resolve_job(vfsms_ctx *ctx, const vfsms_roi_pair &j, const uint8_t **
 // before part 0's search, in stream order -- and never the other way round.  Slots run in (shape) order and a strip has its job's shape,
 // so the order of first use is already the (part, shape) order the shape-run launchers need.
 // VFSMS_STRIP_DEDUP=0 carves every slot a strip of its own (2s, 2s + 1: the layout before the table) for A/B runs.
-// the raw pixels of a job's two strips, for the overlap check behind the vote (verify_kernels.hip)
-static void match_set_strips(MatchDev *m, const StripTable::Strip &A, const StripTable::Strip &B)
-{
-    m->va = A.p; m->vsa = A.stride; m->vb = B.p; m->vsb = B.stride; m->vh = A.h; m->vw = A.w;
-}
 static int build_strip_table(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, const int *ord, int n, int n0, StripTable *T)
 {
     static const bool dedup = !(getenv("VFSMS_STRIP_DEDUP") && atoi(getenv("VFSMS_STRIP_DEDUP")) == 0);
@@ -1317,67 +1378,6 @@ static int shape_run_end(int g0, int n, ShapeAt shape_at)
     int g1 = g0 + 1;
     while (g1 < n && shape_at(g1) == shape_at(g0)) g1++;
     return g1;
-}
-
-// ---- one 2-NN search + vote run: n (query set, train set) jobs in fused launches ------------------------------------------------------
-// The phases mirror a SURF run's: match_run_bytes into the caller's ONE ctx_arena_reserve, match_run_carve (wires and uploads the
-// records), match_run_launch over one or more ranges of the jobs, match_run_readback in front of the caller's synchronisation.
-// k_bf_l2* on the float descriptors (filtered or not: the plan) / k_bf_i8_d128 on the int8 rows / k_bf_hamming_jobs on 32-byte rows behind q, t
-enum MatchSearch { SEARCH_FLOAT, SEARCH_I8_D128, SEARCH_HAMMING };
-struct MatchTail { double ratio; int max_dist; int offset_evaluate; };   // the ratio test (L2) or the distance bound (Hamming), the vote's threshold
-// 64-d descriptors leave the descriptor kernel with norm <= 1: their 2-NN search runs as an MFMA candidate filter plus exact verification
-// (match_kernels.hip); other widths, or VFSMS_BF_EXACT=1, take the exhaustive VALU kernel.  The split counts follow the set sizes the
-// CALLER expects, (fq, ft) for the filter and (eq, et) for the exhaustive kernel: the true counts of feature sets, the typical occupancy
-// of the capacity in a fused batch.
-static MatchPlan match_plan_float(int dim, int njobs, int fq, int ft, int eq, int et)
-{
-    MatchPlan P;
-    P.filtered = dim == 64 && !bf_force_exact();
-    P.cns = pick_filter_nsplit(fq, njobs, ft);
-    P.ns = P.filtered ? 1 : pick_nsplit(eq, et, njobs, dim);
-    return P;
-}
-// The one place that knows a run's arena block: the result rows (one block: one copy back), per job its arrays, the uploaded records
-void match_run_layout(ArenaWalk &a, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
-{
-    run->P = P; run->dim = dim; run->M.assign(n, MatchDev{});
-    run->rblock = a.take<int32_t>(VFSMS_ATTEMPT_INTS * (size_t)n);
-    for (int k = 0; k < n; k++) {
-        MatchDev &m = run->M[k];
-        match_layout(a, &m, J[k].capq, dim, P.ns);
-        if (P.filtered) match_filter_layout(a, &m, J[k].capq, J[k].capt, P.cns);
-        m.result = run->rblock ? run->rblock + VFSMS_ATTEMPT_INTS * J[k].row : nullptr;
-        m.q = J[k].q; m.t = J[k].t; m.kq = J[k].kq; m.kt = J[k].kt; m.nq_ptr = J[k].nq_ptr; m.nt_ptr = J[k].nt_ptr;
-        m.q8 = J[k].q8; m.t8 = J[k].t8; m.qn2 = J[k].qn2; m.tn2 = J[k].tn2;
-        if (J[k].sa) match_set_strips(&m, *J[k].sa, *J[k].sb);
-    }
-    run->dM = a.take<MatchDev>(n);
-}
-static size_t match_run_bytes(const MatchJob *J, int n, const MatchPlan &P) { ArenaWalk a; MatchRun run; match_run_layout(a, &run, J, n, 0, P); return a.off; }
-static int match_run_carve(vfsms_ctx *ctx, MatchRun *run, const MatchJob *J, int n, int dim, const MatchPlan &P)
-{
-    ArenaWalk a = ctx_arena_walk(ctx);
-    match_run_layout(a, run, J, n, dim, P);
-    TRY(ctx_arena_commit(ctx, a, "arena exhausted while carving a match run"));
-    return ctx_copy_small(ctx, run->M.data(), sizeof(MatchDev) * n, run->dM);
-}
-// search + ratio test (Hamming: distance bound) + vote of jobs [first, first + count); maxq / maxt: the largest query / train set to cover
-static int match_run_launch(vfsms_ctx *ctx, const MatchRun &run, int first, int count, int maxq, int maxt, MatchSearch search, const MatchTail &tail)
-{
-    const MatchDev *dM = run.dM + first;
-    if (search == SEARCH_HAMMING) {
-        TRY(launch_bf_hamming(ctx, dM, count, maxq, run.P.ns, tail.max_dist));
-        return launch_scan_mode(ctx, dM, count, maxq, tail.offset_evaluate);
-    }
-    if (search == SEARCH_I8_D128) { TRY(launch_bf_i8_d128(ctx, dM, count, maxq, run.P.ns)); }
-    else if (run.P.filtered) { TRY(launch_bf_l2_filtered(ctx, dM, count, maxq, maxt, run.P.cns)); }
-    else { TRY(launch_bf_l2(ctx, dM, count, maxq, run.P.ns, run.dim)); }
-    return launch_ratio_mode(ctx, dM, count, maxq, tail.ratio, tail.offset_evaluate);
-}
-static int match_run_readback(vfsms_ctx *ctx, const MatchRun &run, int32_t *rows)
-{
-    HIP_TRY(hipMemcpyAsync(rows, run.rblock, sizeof(int32_t) * VFSMS_ATTEMPT_INTS * run.M.size(), hipMemcpyDeviceToHost, ctx->stream));
-    return VFSMS_OK;
 }
 
 // ---- the phase batches: one driver over the runs of equal shapes ------------------------------------------------------------------------
@@ -1536,7 +1536,7 @@ static int attempt_surf_impl(vfsms_ctx *ctx, const vfsms_roi_pair *jobs, int n, 
         J[s_].sa = &T.strips[T.a[s_]]; J[s_].sb = &T.strips[T.b[s_]];       // the tile's pixels, not the enhanced copy
     }
     const SurfEnh enh{enh_mode, clip_limit, tile_grid};
-    const MatchTail tail{ratio, -1, offset_evaluate};
+    const MatchTail tail{TAIL_VOTE, ratio, -1, offset_evaluate};
     TRY(ctx_arena_reserve(ctx, surf_run_bytes(S.data(), u, params, enh, u0) + match_run_bytes(J.data(), n, P) + 65536));
     ctx->pinned_off = 0;
     SurfRun surf; MatchRun match;
@@ -1773,13 +1773,10 @@ static int features_match_impl(vfsms_ctx *ctx, const char *who, const int64_t *f
     if (m == 0) return VFSMS_OK;
     const MatchPlan P = match_plan_float(dim, m, maxq, maxt, maxq, maxt);       // SURF descriptors are L2-normalised by construction
     TRY(ctx_arena_reserve(ctx, match_run_bytes(J.data(), m, P) + 65536));
-    ctx->pinned_off = 0;
-    int *dcnt;
-    TRY(ctx_upload_small(ctx, cnt.data(), sizeof(int) * 2 * m, (void **)&dcnt));
-    for (int j = 0; j < m; j++) { J[j].nq_ptr = dcnt + 2 * j; J[j].nt_ptr = dcnt + 2 * j + 1; }
+    TRY(match_upload_counts(ctx, J.data(), m, cnt.data()));
     MatchRun run;
     TRY(match_run_carve(ctx, &run, J.data(), m, dim, P));
-    TRY(match_run_launch(ctx, run, 0, m, maxq, maxt, SEARCH_FLOAT, MatchTail{ratio, -1, offset_evaluate}));
+    TRY(match_run_launch(ctx, run, 0, m, maxq, maxt, SEARCH_FLOAT, MatchTail{TAIL_VOTE, ratio, -1, offset_evaluate}));
     std::vector<int32_t> res((size_t)VFSMS_ATTEMPT_INTS * m);
     TRY(match_run_readback(ctx, run, res.data()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2655,7 +2652,7 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     ctx->pinned_off = 0;
     MatchRun run;
     TRY(match_run_carve(ctx, &run, J.data(), n, 128, P));
-    TRY(match_run_launch(ctx, run, 0, n, maxcap, maxt, exact ? SEARCH_FLOAT : SEARCH_I8_D128, MatchTail{ratio, -1, offset_evaluate}));
+    TRY(match_run_launch(ctx, run, 0, n, maxcap, maxt, exact ? SEARCH_FLOAT : SEARCH_I8_D128, MatchTail{TAIL_VOTE, ratio, -1, offset_evaluate}));
     TRY(match_run_readback(ctx, run, out));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
@@ -2693,7 +2690,7 @@ extern "C" int vfsms_attempt_orb_batch(vfsms_ctx *ctx, const vfsms_roi_pair *job
         }
         TRY(match_run_carve(ctx, &match, J.data(), n, 32, P));
         TRY(orb_run_launch(ctx, orb, params));
-        TRY(match_run_launch(ctx, match, 0, n, c, c, SEARCH_HAMMING, MatchTail{0.0, max_dist, offset_evaluate}));
+        TRY(match_run_launch(ctx, match, 0, n, c, c, SEARCH_HAMMING, MatchTail{TAIL_VOTE, 0.0, max_dist, offset_evaluate, true}));
         return match_run_readback(ctx, match, out);       // results of all jobs, counters of all strips: two contiguous blocks, two D2H copies per run
     }));
     if (over >= 0) { vfsms_set_error("attempt_orb: internal keypoint capacity exceeded in strip %d of %d", over, u); return VFSMS_ERR_CAPACITY; }

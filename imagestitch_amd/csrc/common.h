@@ -278,23 +278,31 @@ int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_r
 // match_kernels.hip
 void match_layout(ArenaWalk &a, MatchDev *m, int capq, int dim, int nsplit);
 void match_filter_layout(ArenaWalk &a, MatchDev *m, int capq, int capt, int cns);
-size_t match_bytes(int capq, int nsplit);
-int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit);
 int launch_max_norm2_d64(vfsms_ctx *ctx, const float *a, int n, unsigned *d_out);
-size_t match_filter_bytes(int capq, int capt, int cns);
-int match_filter_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int capt, int cns);
 int launch_bf_l2_filtered(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int capt, int cns);
 int launch_bf_l2(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int dim);
 #define BFI_PAD_NORM 0x3fffffff
 struct PackJob { const float *src; const int *n_ptr; int8_t *dst; int *nrm; };   // one strip's descriptors -> int8 rows + norms
 int launch_pack_i8_d128(vfsms_ctx *ctx, const PackJob *d_jobs, int njobs, int max_rows);
 int launch_bf_i8_d128(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit);
-int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq);
-int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio);
-int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate);
-int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int estimator, int tol, int offset_evaluate);
 int launch_bf_hamming(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int nsplit, int max_dist);   // 32-byte rows: search + merge
-int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate);
+// What follows a search, or the caller's own pairs.  The fused paths VOTE: the context's estimator and verifier apply.  The operators
+// behind a user's own matchDescriptors / getOffsetByMode take one of the other three, which never look at the context's settings.
+enum MatchTailKind {
+    TAIL_VOTE,          // ratio test, the CONTEXT's estimator + tolerance, the CONTEXT's verifier -> the job's result row
+    TAIL_PAIRS,         // ratio test, order-preserving compaction (k_match_scan) -> pairs, mcount
+    TAIL_KNN,           // merge only -> d1, d2, i1
+    TAIL_GIVEN_PAIRS    // votes of the caller's pairs, the estimator + tolerance NAMED HERE, no verifier -> the job's result row
+};
+struct MatchTail {
+    MatchTailKind kind;
+    double ratio;                             // the ratio test of an L2 search
+    int max_dist;                             // the distance bound of a Hamming search
+    int offset_evaluate;                      // the vote's threshold
+    bool merged = false;                      // the search has merged and flagged already (launch_bf_hamming): no k_merge_ratio
+    int estimator = VFSMS_OFFSET_MODE, tol = 0;
+};
+int launch_match_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, const MatchTail &tail);
 // consensus_kernels.hip
 int launch_consensus(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int tol, int offset_evaluate);
 // verify_kernels.hip
@@ -428,6 +436,7 @@ struct MatchJob {
     int row;                                         // the job's row of the result block
     const int8_t *q8, *t8; const int *qn2, *tn2;     // optional: int8 rows and their norms (k_bf_i8_d128)
     const StripTable::Strip *sa, *sb;                // optional: the raw pixels of the two strips, for the verifier behind the vote
+    int pairs_given;                                 // the caller has filled the job's pairs[] (TAIL_GIVEN_PAIRS): the compaction leaves them alone
 };
 struct MatchRun { MatchPlan P; int dim; std::vector<MatchDev> M; MatchDev *dM = nullptr; int32_t *rblock = nullptr; };
 struct OrbRun {

@@ -1034,7 +1034,7 @@ __global__ __launch_bounds__(256) void k_hamming_merge(const MatchDev *jobs, int
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-// The one place that knows a match job's device arrays: a counting walk gives their bytes (match_bytes), a carving walk the arrays
+// The one place that knows a match job's device arrays: a counting walk gives their bytes, a carving walk the arrays (api.hip: match_run_layout)
 void match_layout(ArenaWalk &a, MatchDev *m, int capq, int dim, int nsplit)
 {
     m->capq = capq; m->dim = dim; m->nsplit = nsplit;
@@ -1051,14 +1051,6 @@ void match_layout(ArenaWalk &a, MatchDev *m, int capq, int dim, int nsplit)
     m->mcount = a.take<int>(16);
     m->vsum = a.take<unsigned long long>(8);
     m->result = a.take<int32_t>(16);              // a run points the job at its row of the run's result block instead (api.hip)
-}
-
-size_t match_bytes(int capq, int nsplit) { ArenaWalk a; MatchDev m; match_layout(a, &m, capq, 0, nsplit); return a.off; }
-int match_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int dim, int nsplit)
-{
-    ArenaWalk a = ctx_arena_walk(ctx);
-    match_layout(a, m, capq, dim, nsplit);
-    return ctx_arena_commit(ctx, a, "arena exhausted while carving a match job");
 }
 
 // largest squared row norm of an n x 64 array (one wave per row): decides whether host-supplied descriptors qualify
@@ -1091,21 +1083,13 @@ void match_filter_layout(ArenaWalk &a, MatchDev *m, int capq, int capt, int cns)
     m->c_m12 = a.take<float2>((size_t)capq * cns * 2);
 }
 
-size_t match_filter_bytes(int capq, int capt, int cns) { ArenaWalk a; MatchDev m; match_filter_layout(a, &m, capq, capt, cns); return a.off; }
-int match_filter_carve(vfsms_ctx *ctx, MatchDev *m, int capq, int capt, int cns)
-{
-    ArenaWalk a = ctx_arena_walk(ctx);
-    match_filter_layout(a, m, capq, capt, cns);
-    return ctx_arena_commit(ctx, a, "arena exhausted while carving a match filter");
-}
-
 static bool bf_f32_filter()
 {
     static const bool v = getenv("VFSMS_BF_F32FILTER") && atoi(getenv("VFSMS_BF_F32FILTER")) != 0;
     return v;
 }
 
-// MFMA-filtered exact 2-NN for 64-d descriptors of norm <= 1 (jobs carved with nsplit == 1 plus match_filter_carve).
+// MFMA-filtered exact 2-NN for 64-d descriptors of norm <= 1 (jobs of a filtered MatchPlan: nsplit == 1 plus match_filter_layout).
 // Default: fp16 filter on the 16-bit matrix pipe; VFSMS_BF_F32FILTER=1 keeps round 1's f32-MFMA filter.
 int launch_bf_l2_filtered(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int capt, int cns)
 {
@@ -1187,50 +1171,28 @@ static int verify_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs)
     return launch_verify(ctx, d_jobs, njobs, ctx->verify_threshold, ctx->verify_min_pixels);
 }
 
-int launch_ratio_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio, int offset_evaluate)
+// The one tail behind every search, and behind pairs that were given (common.h: MatchTailKind); capq: the largest query set, or pair list
+int launch_match_tail(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, const MatchTail &tail)
 {
     if (njobs <= 0) return VFSMS_OK;
-    {
-        ProfScope ps(ctx, "vote");
-        hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, ratio, 1);
-        TRY(launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate));
+    const dim3 per_query((capq + 255) / 256, njobs);
+    if (tail.kind == TAIL_VOTE) {
+        {
+            ProfScope ps(ctx, "vote");
+            if (!tail.merged) hipLaunchKernelGGL(k_merge_ratio, per_query, dim3(256), 0, ctx->stream, d_jobs, tail.ratio, 1);
+            TRY(launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, tail.offset_evaluate));
+        }
+        return verify_tail(ctx, d_jobs, njobs);
     }
-    return verify_tail(ctx, d_jobs, njobs);
-}
-
-int launch_ratio_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, double ratio)
-{
-    hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, ratio, 1);
-    hipLaunchKernelGGL(k_match_scan, dim3(njobs), dim3(1024), 0, ctx->stream, d_jobs);
+    if (tail.kind == TAIL_GIVEN_PAIRS) {
+        if (capq > 0) hipLaunchKernelGGL(k_votes_from_pairs, per_query, dim3(256), 0, ctx->stream, d_jobs, capq);
+        return launch_vote_tail(ctx, d_jobs, njobs, capq, tail.estimator, tail.tol, tail.offset_evaluate);
+    }
+    const int pairs = tail.kind == TAIL_PAIRS;                // TAIL_KNN: the merge without the ratio test
+    if (!tail.merged) hipLaunchKernelGGL(k_merge_ratio, per_query, dim3(256), 0, ctx->stream, d_jobs, tail.ratio, pairs);
+    if (pairs) hipLaunchKernelGGL(k_match_scan, dim3(njobs), dim3(1024), 0, ctx->stream, d_jobs);
     HIP_TRY(hipGetLastError());
     return VFSMS_OK;
-}
-
-int launch_merge_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq)
-{
-    hipLaunchKernelGGL(k_merge_ratio, dim3((capq + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, 0.0, 0);
-    HIP_TRY(hipGetLastError());
-    return VFSMS_OK;
-}
-
-// flags / votes already written per query (Hamming matcher): compaction + mode vote
-int launch_scan_mode(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capq, int offset_evaluate)
-{
-    if (njobs <= 0) return VFSMS_OK;
-    {
-        ProfScope ps(ctx, "vote");
-        TRY(launch_vote_tail(ctx, d_jobs, njobs, capq, ctx->offset_estimator, ctx->offset_tol, offset_evaluate));
-    }
-    return verify_tail(ctx, d_jobs, njobs);
-}
-
-// the per-operator entry points name their estimator: the context's setting governs the fused paths only
-int launch_mode_only(vfsms_ctx *ctx, const MatchDev *d_jobs, int njobs, int capm, int estimator, int tol, int offset_evaluate)
-{
-    if (njobs <= 0) return VFSMS_OK;
-    if (capm > 0)
-        hipLaunchKernelGGL(k_votes_from_pairs, dim3((capm + 255) / 256, njobs), dim3(256), 0, ctx->stream, d_jobs, capm);
-    return launch_vote_tail(ctx, d_jobs, njobs, capm, estimator, tol, offset_evaluate);
 }
 
 // Hamming search over nsplit train ranges + merge of jobs carved with that nsplit: i1 / d1, match flags and (jobs with keypoints) votes

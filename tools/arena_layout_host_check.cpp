@@ -23,7 +23,8 @@ static int g_records = 0;
 typedef std::vector<const void *> Ptrs;
 
 // layout(a, p): the record's layout function over walk a, then every device pointer it set appended to p
-static int check_record(const char *what, const std::function<void(ArenaWalk &, Ptrs &)> &layout)
+// distinct: no two of the listed pointers may be equal (a record whose list names no array twice)
+static int check_record(const char *what, const std::function<void(ArenaWalk &, Ptrs &)> &layout, bool distinct = false)
 {
     g_what = what;
     ArenaWalk c; Ptrs p;
@@ -40,6 +41,7 @@ static int check_record(const char *what, const std::function<void(ArenaWalk &, 
     CHECK(a.ok && a.off == bytes);
     CHECK(ctx_arena_commit(&ctx, a, what) == VFSMS_OK && ctx.arena_off == bytes);
     for (const void *q : p) CHECK(q != nullptr && (const char *)q >= buf && (const char *)q < buf + bytes);
+    if (distinct) for (size_t i = 0; i < p.size(); i++) for (size_t j = 0; j < i; j++) CHECK(p[i] != p[j]);
     ArenaWalk s = ctx_arena_walk(&small);
     p.clear();
     layout(s, p);
@@ -128,24 +130,38 @@ int main()
     const int match_shapes[][2] = {{1, 1}, {6000, 8}};
     for (auto &s : match_shapes) {
         snprintf(what, sizeof(what), "match %d x %d", s[0], s[1]);
-        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_layout(a, &m, s[0], 64, s[1]); list(p, m, false); })) return 1;
-        ArenaWalk c; MatchDev m;
-        match_layout(c, &m, s[0], 64, s[1]);
-        g_what = what;
-        CHECK(match_bytes(s[0], s[1]) == c.off);
+        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_layout(a, &m, s[0], 64, s[1]); list(p, m, false); }, true)) return 1;
+        // a run of this one job, exhaustive plan: the job's count plus the run's result row (the job's `result` points there) and its uploaded record
+        const MatchPlan P = {false, s[1], 0};
+        MatchJob J = {}; J.capq = J.capt = s[0];
+        snprintf(what, sizeof(what), "match run of one, %d x %d", s[0], s[1]);
+        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchRun run; match_run_layout(a, &run, &J, 1, 64, P); p.push_back(run.dM); list(p, run.M[0], false); }, true)) return 1;
+        ArenaWalk c, r; MatchDev m; MatchRun run;
+        c.take<int32_t>(VFSMS_ATTEMPT_INTS); match_layout(c, &m, s[0], 64, s[1]); c.take<MatchDev>(1);
+        match_run_layout(r, &run, &J, 1, 64, P);
+        CHECK(r.ok && r.off == c.off);
     }
     const int filter_shapes[][3] = {{1, 1, 1}, {256, 31, 1}, {256, 32, 2}, {257, 33, 4}};
     for (auto &s : filter_shapes) {
         snprintf(what, sizeof(what), "match + filter %d, %d, %d", s[0], s[1], s[2]);
-        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_layout(a, &m, s[0], 64, 1); match_filter_layout(a, &m, s[0], s[1], s[2]); list(p, m, true); })) return 1;
+        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_layout(a, &m, s[0], 64, 1); match_filter_layout(a, &m, s[0], s[1], s[2]); list(p, m, true); }, true)) return 1;
         snprintf(what, sizeof(what), "filter %d, %d, %d", s[0], s[1], s[2]);
-        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_filter_layout(a, &m, s[0], s[1], s[2]); p.insert(p.end(), {m.c_ent, m.c_cnt, m.q16, m.t16, m.c_m12}); })) return 1;
-        // the carve entry points answer for themselves: exactly enough, then 256 bytes short
-        const size_t bytes = match_filter_bytes(s[0], s[1], s[2]);
-        vfsms_ctx ctx, small; MatchDev m = {};
+        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchDev m = {}; match_filter_layout(a, &m, s[0], s[1], s[2]); p.insert(p.end(), {m.c_ent, m.c_cnt, m.q16, m.t16, m.c_m12}); }, true)) return 1;
+        // a run of this one job, filtered plan, answers for itself: exactly enough, then 256 bytes short
+        const MatchPlan P = {true, 1, s[2]};
+        MatchJob J = {}; J.capq = s[0]; J.capt = s[1];
+        snprintf(what, sizeof(what), "filtered match run of one, %d, %d, %d", s[0], s[1], s[2]);
+        if (check_record(what, [&](ArenaWalk &a, Ptrs &p) { MatchRun run; match_run_layout(a, &run, &J, 1, 64, P); p.push_back(run.dM); list(p, run.M[0], true); }, true)) return 1;
+        ArenaWalk c; MatchRun run;
+        match_run_layout(c, &run, &J, 1, 64, P);
+        const size_t bytes = c.off;
+        vfsms_ctx ctx, small;
         CHECK(ctx.arena.reserve(bytes, nullptr) == VFSMS_OK && small.arena.reserve(bytes - 256, nullptr) == VFSMS_OK);
-        CHECK(match_filter_carve(&ctx, &m, s[0], s[1], s[2]) == VFSMS_OK && ctx.arena_off == bytes && m.c_m12 != nullptr);
-        CHECK(match_filter_carve(&small, &m, s[0], s[1], s[2]) == VFSMS_ERR_CAPACITY && small.arena_off == 0);
+        ArenaWalk a = ctx_arena_walk(&ctx), b = ctx_arena_walk(&small);
+        match_run_layout(a, &run, &J, 1, 64, P);
+        CHECK(ctx_arena_commit(&ctx, a, what) == VFSMS_OK && ctx.arena_off == bytes && run.M[0].c_m12 != nullptr && run.dM != nullptr);
+        match_run_layout(b, &run, &J, 1, 64, P);
+        CHECK(ctx_arena_commit(&small, b, what) == VFSMS_ERR_CAPACITY && small.arena_off == 0);
     }
     // ORB ROI
     const int orb_shapes[][4] = {{31, 31, 8, 5000}, {64, 2048, 8, 5000}, {31, 31, 1, 5000}, {64, 2048, 8, 1}, {64, 2048, 1, 1}};
@@ -225,9 +241,9 @@ int main()
             if (check_record(what, [&](ArenaWalk &a, Ptrs &p) {
                     MatchRun run;
                     match_run_layout(a, &run, J.data(), n, 64, P);
-                    p.push_back(run.rblock); p.push_back(run.dM);
+                    p.push_back(run.dM);                                  // (run.rblock is the result row of the job of row 0)
                     for (int i = 0; i < n; i++) list(p, run.M[i], filtered != 0);
-                })) return 1;
+                }, true)) return 1;
         }
         int c1, c2, c;
         orb_caps(OP, &c1, &c2, &c);
