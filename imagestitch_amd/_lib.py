@@ -93,6 +93,10 @@ _SIGNATURES = {
     "vfsms_tile_reserve_ch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_tile_fill_pair": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int]),
     "vfsms_tile_fill_jpeg": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]),
+    "vfsms_tile_fill_jpeg_dct": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]),
+    "vfsms_jpeg_coefficients": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "vfsms_jpeg_idct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "vfsms_jpeg_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vfsms_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vfsms_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -427,6 +431,31 @@ class Engine:
             return False
         self._check(rc)
         return True
+
+    def tile_fill_jpeg_dct(self, gray_handle, color_handle, data):
+        """tile_fill_jpeg with the device half of the decoder (vfsms_tile_fill_jpeg_dct, Method.jpegDecoder = "device"): the host stops behind
+        the entropy decode, dequantisation and inverse DCT run on the device (csrc/jpeg_dec_kernels.hip).  Same bytes in the tiles, same
+        answer: True when they are filled, False when this path does not take the file -- the tiles are STILL RESERVED, tile_fill_jpeg is
+        next.  Safe from any thread."""
+        rc = self.lib.vfsms_tile_fill_jpeg_dct(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
+        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
+            return False
+        self._check(rc)
+        return True
+
+    def jpeg_idct(self, coef, quant, pitch=None):
+        """vfsms_jpeg_idct, the bare operator: `coef` int16 (block_rows, block_cols, 64), quantised coefficients in natural order, and `quant`
+        uint16 (64,) -> the u8 plane (block_rows * 8, block_cols * 8) of tests/jpeg_dec_ref.py's idct_plane (rows `pitch` bytes apart when
+        given: the plane is a view of a wider array)."""
+        coef = np.ascontiguousarray(coef, np.int16)
+        quant = np.ascontiguousarray(quant, np.uint16)
+        if coef.ndim != 3 or coef.shape[2] != 64 or quant.shape != (64,):
+            raise ValueError("jpeg_idct: coef (block_rows, block_cols, 64) int16 and quant (64,) uint16")
+        br, bc = coef.shape[:2]
+        pitch = bc * 8 if pitch is None else int(pitch)
+        out = np.zeros((br * 8, max(pitch, 1)), np.uint8)
+        self._check(self.lib.vfsms_jpeg_idct(self.ctx, _ptr(coef), _ptr(quant), br, bc, _ptr(out), pitch))
+        return out[:, :bc * 8]
 
     def tile_fill_ptr(self, handle, address, stride):
         """tile_fill from a raw host address (rows `stride` bytes apart); the caller keeps the memory alive until this returns"""
@@ -1214,6 +1243,31 @@ def jpeg_decode_raw420(data):
         return None
     n = pw * ph
     return out[:n].reshape(ph, pw), out[n:n + n // 4].reshape(ph // 2, pw // 2), out[n + n // 4:].reshape(ph // 2, pw // 2), h.value, w.value
+
+
+def jpeg_coefficients(data):
+    """vfsms_jpeg_coefficients: the host half of Method.jpegDecoder = "device", no GPU involved -- the quantised DCT coefficients of a JPEG
+    file as the entropy decode leaves them (what vfsms_tile_fill_jpeg_dct stages for the device's inverse transform) -> (h, w, comps), comps a
+    list of (coef int16 (block_rows, block_cols, 64) in natural order, quant uint16 (64,) in natural order) per component, the block grids on
+    whole iMCUs.  None when the file is not taken (not 8-bit gray / 4:2:0 Y Cb Cr, damaged, no libjpeg.so.8)."""
+    lib = load_library()
+    h, w, nc, need = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    grid = (C.c_int * 6)()
+    rc = lib.vfsms_jpeg_coefficients(data, len(data), None, 0, C.byref(h), C.byref(w), C.byref(nc), grid, C.byref(need))
+    if rc != VFSMS_ERR_CAPACITY:
+        return None
+    out = np.empty(need.value, np.uint8)
+    rc = lib.vfsms_jpeg_coefficients(data, len(data), out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(h), C.byref(w), C.byref(nc), grid, C.byref(need))
+    if rc != VFSMS_OK:
+        return None
+    n = nc.value
+    comps, off = [], 128 * n
+    for k in range(n):
+        br, bc = grid[2 * k], grid[2 * k + 1]
+        nb = br * bc * 128
+        comps.append((out[off:off + nb].view(np.int16).reshape(br, bc, 64), out[128 * k:128 * (k + 1)].view(np.uint16)))
+        off += nb
+    return h.value, w.value, comps
 
 
 def _last_error(lib):

@@ -549,6 +549,37 @@ static int fill_pair_lookup(vfsms_ctx *ctx, int64_t gray, int64_t color, bool gi
     *ev = tg ? tg->ready : tc->ready; *dg = tg ? tg->ptr : nullptr; *dc = tc ? tc->ptr : nullptr;
     return VFSMS_OK;
 }
+// a device staging buffer of the decoder threads: a small pool of its own (the tile pool belongs to the context thread)
+static hipError_t stage_device_get(vfsms_ctx *ctx, size_t need, StageBuf *sb)
+{
+    sb->ptr = nullptr; sb->bytes = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->stage_mu);
+        for (size_t k = 0; k < ctx->stage_pool.size(); k++)
+            if (ctx->stage_pool[k].bytes >= need) { *sb = ctx->stage_pool[k]; ctx->stage_pool.erase(ctx->stage_pool.begin() + k); return hipSuccess; }
+    }
+    const hipError_t e = hipMalloc((void **)&sb->ptr, need);
+    sb->bytes = need;
+    if (e != hipSuccess) sb->ptr = nullptr;
+    return e;
+}
+static void stage_device_put(vfsms_ctx *ctx, StageBuf sb)
+{
+    if (!sb.ptr) return;
+    std::lock_guard<std::mutex> lk(ctx->stage_mu);
+    if (ctx->stage_pool.size() < 64) ctx->stage_pool.push_back(sb); else hipFree(sb.ptr);
+}
+// the end of a pair fill: both tiles filled, or both given up
+static void fill_pair_settle(vfsms_ctx *ctx, int64_t gray, int64_t color, bool ok)
+{
+    std::lock_guard<std::mutex> lk(ctx->tiles_mu);
+    for (int64_t hd : { gray, color }) {
+        if (!hd) continue;
+        auto it = ctx->tiles.find(hd);
+        if (it != ctx->tiles.end()) { it->second.fill = ok ? 0 : 2; it->second.pending = false; }
+    }
+    ctx->tiles_cv.notify_all();
+}
 // `host` (h * w pixels of `format`, densely packed; pinned when `host_pinned`) -> the device staging buffer -> the split kernel -> both tiles
 // complete (or both given up, on an error) when this returns
 #define VFSMS_SRC_YCC420_RAW 100      // internal: the raw planes of a 4:2:0 JPEG on the iMCU grid (jpeg_decode_raw420_host) -> k_ingest_420
@@ -563,12 +594,7 @@ static int fill_pair_upload(vfsms_ctx *ctx, int64_t gray, int64_t color, const u
     StageBuf sb{nullptr, 0};
     if (format == VFSMS_SRC_GRAY8 && !dc) e = hipMemcpyAsync(dg, host, need, hipMemcpyHostToDevice, ctx->copy_stream);      // nothing to convert
     else {
-        {   // staging buffer for the packed source rows: a small pool of its own (the tile pool belongs to the context thread)
-            std::lock_guard<std::mutex> lk(ctx->stage_mu);
-            for (size_t k = 0; k < ctx->stage_pool.size(); k++)
-                if (ctx->stage_pool[k].bytes >= need) { sb = ctx->stage_pool[k]; ctx->stage_pool.erase(ctx->stage_pool.begin() + k); break; }
-        }
-        if (!sb.ptr) { e = hipMalloc((void **)&sb.ptr, need); sb.bytes = need; if (e != hipSuccess) sb.ptr = nullptr; }
+        e = stage_device_get(ctx, need, &sb);
         if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
         if (e == hipSuccess) rc = format == VFSMS_SRC_YCC420_RAW ? launch_ingest_420(ctx->copy_stream, sb.ptr, pw, ph, h, w, dg, dc)
                                                                  : launch_ingest_split(ctx->copy_stream, sb.ptr, dg, dc, (long long)h * w, format);
@@ -576,20 +602,8 @@ static int fill_pair_upload(vfsms_ctx *ctx, int64_t gray, int64_t color, const u
     if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
     if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
     if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
-    if (sb.ptr) {
-        std::lock_guard<std::mutex> lk(ctx->stage_mu);
-        if (ctx->stage_pool.size() < 64) ctx->stage_pool.push_back(sb); else hipFree(sb.ptr);
-    }
-    const bool ok = e == hipSuccess && rc == VFSMS_OK;
-    {
-        std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-        for (int64_t hd : { gray, color }) {
-            if (!hd) continue;
-            auto it = ctx->tiles.find(hd);
-            if (it != ctx->tiles.end()) { it->second.fill = ok ? 0 : 2; it->second.pending = false; }
-        }
-        ctx->tiles_cv.notify_all();
-    }
+    stage_device_put(ctx, sb);
+    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
     if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
     return rc;
 }
@@ -648,6 +662,102 @@ extern "C" int vfsms_tile_fill_jpeg(vfsms_ctx *ctx, int64_t gray, int64_t color,
         rc = fill_pair_upload(ctx, gray, color, host, h, w, comp == 420 ? VFSMS_SRC_YCC420_RAW : comp == 3 ? VFSMS_SRC_YCC24 : VFSMS_SRC_GRAY8, ev, dg, dc, "tile_fill_jpeg");
     stage_pinned_put(ctx, pb);
     return rc;
+}
+
+// Method.jpegDecoder = "device": the same contract as vfsms_tile_fill_jpeg, but the host stops behind the ENTROPY decode
+// (jpeg_coefficients_host: jpeg_read_coefficients into pinned staging) and dequantisation, inverse DCT, level shift and range limit run on the
+// device (k_jpeg_idct, csrc/jpeg_dec_kernels.hip), stream-ordered on the copy stream like everything else of the ingest.  Gray wanted alone:
+// the luma blocks alone cross the link and the kernel writes the gray tile itself, cropped.  Colour wanted, a 4:2:0 file: the three planes go
+// to a device scratch in the layout of jpeg_decode_raw420_host and k_ingest_420 runs on it unchanged.  Colour wanted, a one-component file:
+// the plane is replicated as vfsms_tile_fill_pair replicates it.  A file this path does not take leaves BOTH TILES RESERVED.
+extern "C" int vfsms_tile_fill_jpeg_dct(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes)
+{
+    CTX_ENTER(ctx);
+    const char *who = "tile_fill_jpeg_dct";
+    if (!jpeg || !nbytes) { vfsms_set_error("%s: no data", who); return VFSMS_ERR_BAD_ARG; }
+    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
+    TRY(fill_pair_lookup(ctx, gray, color, false, who, &h, &w, &ev, &dg, &dc));
+    // (the staging buffer is sized for any file of the tiles' size this path takes: three tables, the luma grid on whole 16 x 16 iMCUs at two
+    // bytes a sample, and half as much again for the two chroma grids when a colour tile is wanted)
+    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
+    const size_t cap = 3 * (size_t)VFSMS_JPEG_COEF_TABLE_BYTES + (size_t)pw * ph * (dc ? 3 : 2);
+    StageBuf pb{nullptr, 0};
+    std::vector<uint8_t> pageable;
+    uint8_t *host = nullptr;
+    if (stage_pinned_get(ctx, cap, &pb) == VFSMS_OK) host = pb.ptr;
+    else { pb.ptr = nullptr; pageable.resize(cap); host = pageable.data(); }
+    int jh = 0, jw = 0, nc = 0, grid[6] = {0, 0, 0, 0, 0, 0}; size_t need = 0;
+    int rc = jpeg_coefficients_host(jpeg, nbytes, dc == nullptr, host, cap, &jh, &jw, &nc, grid, &need);
+    if (rc == VFSMS_ERR_CAPACITY || (rc == VFSMS_OK && (jh != h || jw != w))) {
+        vfsms_set_error("%s: the file is %d x %d, the reserved tiles %d x %d", who, jh, jw, h, w); rc = VFSMS_ERR_BAD_ARG;
+    }
+    if (rc == VFSMS_OK && nc == 3 && dc && (grid[0] * 8 != ph || grid[1] * 8 != pw || grid[2] * 16 != ph || grid[3] * 16 != pw || grid[4] != grid[2] || grid[5] != grid[3])) {
+        vfsms_set_error("%s: the block grid is not the raw 4:2:0 layout's", who); rc = VFSMS_ERR_UNSUPPORTED;      // (cannot happen: both follow from h, w and 2x2, 1x1, 1x1)
+    }
+    if (rc != VFSMS_OK) { stage_pinned_put(ctx, pb); return rc; }
+    // from here on the tiles end filled or given up
+    const bool planes = nc == 3 && dc;                           // the three planes -> scratch -> k_ingest_420
+    const bool via_scratch = planes || (nc == 1 && !dg);         // (a colour tile alone from a gray file: the plane has no tile of its own)
+    const size_t scratch_bytes = planes ? (size_t)pw * ph * 3 / 2 : (size_t)h * w;
+    StageBuf sb{nullptr, 0}, sp{nullptr, 0};
+    hipError_t e = stage_device_get(ctx, need, &sb);
+    if (e == hipSuccess && via_scratch) e = stage_device_get(ctx, scratch_bytes, &sp);
+    if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
+    if (e == hipSuccess) {
+        JpegIdctArgs A; memset(&A, 0, sizeof(A));
+        const int16_t *blocks = (const int16_t *)(sb.ptr + (size_t)nc * VFSMS_JPEG_COEF_TABLE_BYTES);
+        A.ncomp = planes ? 3 : 1;
+        for (int k = 0; k < A.ncomp; k++) {
+            JpegIdctComp &C = A.c[k];
+            C.coef = blocks + (size_t)A.total * 64; C.quant = (const uint16_t *)(sb.ptr + (size_t)k * VFSMS_JPEG_COEF_TABLE_BYTES);
+            C.bcols = grid[2 * k + 1]; C.first = A.total;
+            if (planes) {                                            // Y at pitch pw, then Cb, then Cr at pitch pw / 2: the whole grid, nothing cropped
+                C.dst = k == 0 ? sp.ptr : sp.ptr + (size_t)pw * ph + (size_t)(k - 1) * (pw / 2) * (ph / 2);
+                C.pitch = k == 0 ? pw : pw / 2; C.rows = grid[2 * k] * 8; C.cols = grid[2 * k + 1] * 8;
+            } else { C.dst = dg ? dg : sp.ptr; C.pitch = w; C.rows = h; C.cols = w; }
+            A.total += (unsigned)grid[2 * k] * (unsigned)grid[2 * k + 1];
+        }
+        rc = launch_jpeg_idct(ctx->copy_stream, A);
+        if (rc == VFSMS_OK && planes) rc = launch_ingest_420(ctx->copy_stream, sp.ptr, pw, ph, h, w, dg, dc);
+        else if (rc == VFSMS_OK && dc) rc = launch_ingest_split(ctx->copy_stream, dg ? dg : sp.ptr, nullptr, dc, (long long)h * w, VFSMS_SRC_GRAY8);
+    }
+    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
+    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
+    if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
+    stage_device_put(ctx, sb); stage_device_put(ctx, sp);
+    stage_pinned_put(ctx, pb);
+    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
+    if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
+    return rc;
+}
+
+// the bare operator behind it: block_rows x block_cols blocks of 64 int16 (natural order, block-row-major) and one uint16[64] table in, the
+// plane of block_rows * 8 rows of block_cols * 8 samples out, `pitch` bytes apart.  Profile stage "jpeg_decode"
+extern "C" int vfsms_jpeg_idct(vfsms_ctx *ctx, const int16_t *coef, const uint16_t *quant, int block_rows, int block_cols, uint8_t *out, int pitch)
+{
+    CTX_ENTER(ctx);
+    if (!coef || !quant || !out || block_rows < 1 || block_cols < 1 || block_rows > 8192 || block_cols > 8192 || pitch < block_cols * 8) {
+        vfsms_set_error("jpeg_idct: bad arguments (1..8192 blocks a side, pitch >= block_cols * 8)"); return VFSMS_ERR_BAD_ARG;
+    }
+    const size_t nblk = (size_t)block_rows * block_cols, cbytes = nblk * 128, pbytes = nblk * 64;
+    TRY(ctx_arena_reserve(ctx, cbytes + pbytes + 128 + 4096));
+    int16_t *d_coef = (int16_t *)ctx_arena_alloc(ctx, cbytes);
+    uint16_t *d_q = (uint16_t *)ctx_arena_alloc(ctx, 128);
+    uint8_t *d_out = (uint8_t *)ctx_arena_alloc(ctx, pbytes);
+    if (!d_coef || !d_q || !d_out) { vfsms_set_error("arena exhausted (jpeg_idct)"); return VFSMS_ERR_CAPACITY; }
+    HIP_TRY(hipMemcpyAsync(d_coef, coef, cbytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_q, quant, 128, hipMemcpyHostToDevice, ctx->stream));
+    JpegIdctArgs A; memset(&A, 0, sizeof(A));
+    A.ncomp = 1; A.total = (unsigned)nblk;
+    A.c[0].coef = d_coef; A.c[0].quant = d_q; A.c[0].dst = d_out; A.c[0].pitch = block_cols * 8; A.c[0].bcols = block_cols;
+    A.c[0].rows = block_rows * 8; A.c[0].cols = block_cols * 8; A.c[0].first = 0;
+    {
+        ProfScope ps(ctx, "jpeg_decode");
+        TRY(launch_jpeg_idct(ctx->stream, A));
+    }
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)pitch, d_out, (size_t)block_cols * 8, (size_t)block_cols * 8, (size_t)block_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
 }
 
 extern "C" int vfsms_host_alloc(vfsms_ctx *ctx, size_t bytes, void **ptr)

@@ -390,6 +390,14 @@ void jpeg_quant_tables(int quality, uint8_t q[2][64]);
 int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality, int restart_mcus, int *interval);
 int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
                             int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes);
+// jpeg_host.cpp / jpeg_dec_kernels.hip: the device half of the JPEG decoder (tests/jpeg_dec_ref.py).  A component of one launch: its blocks
+// (64 int16 each, natural order, block-row-major on a grid `bcols` wide), its table (uint16[64], natural order), the plane it becomes (`rows`
+// x `cols` samples kept of the grid, `pitch` bytes apart) and the index of its first block among the launch's `total`
+struct JpegIdctComp { const int16_t *coef; const uint16_t *quant; uint8_t *dst; int pitch, bcols, rows, cols; unsigned first; };
+struct JpegIdctArgs { JpegIdctComp c[3]; int ncomp; unsigned total; };
+int launch_jpeg_idct(hipStream_t stream, const JpegIdctArgs &A);
+int jpeg_coefficients_host(const unsigned char *jpeg, size_t nbytes, int luma_only, unsigned char *out, size_t cap, int *h, int *w, int *ncomp,
+                           int *grid6, size_t *need);
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
 size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);

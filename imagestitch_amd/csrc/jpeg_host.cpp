@@ -17,6 +17,9 @@
 // likes and joins their entropy-coded segments into ONE file as restart intervals (vfsms_jpeg_join: DRI = the MCUs of a stripe, an RSTn
 // marker between two stripes).  The coefficients, hence the decoded pixels, are those of the one-thread encode of the whole image.
 //
+// A third entry stops even earlier, for Method.jpegDecoder = "device": jpeg_coefficients_host hands out the quantised DCT coefficients
+// (jpeg_read_coefficients: the entropy decode and nothing else) and the file's quantisation tables; csrc/jpeg_dec_kernels.hip does the rest.
+//
 // ABI knowledge used (libjpeg 8 / libjpeg-turbo 2.x on x86-64, `boolean` = int): the public head of jpeg_decompress_struct up to
 // output_scanline and the layout of jpeg_error_mgr -- restated below field by field.  Two guards make a mismatch a clean refusal
 // (VFSMS_ERR_UNSUPPORTED -> the host falls back to Pillow) instead of a wrong image: the struct SIZE is taken from the library itself
@@ -72,7 +75,7 @@ struct jcomp_head_abi {                 // struct jpeg_compress_struct, its publ
 static_assert(offsetof(jcomp_head_abi, image_width) == 48 && offsetof(jcomp_head_abi, in_color_space) == 60, "jpeg_compress_struct head: unexpected layout");
 enum { JCS_GRAYSCALE_ = 1, JCS_RGB_ = 2, JCS_YCbCr_ = 3 };
 #define JPEG_ABI_VERSION 80
-#define JPEG_CINFO_BYTES 2048           // room for the whole struct (632 bytes in libjpeg-turbo 2.1, ABI 8)
+#define JPEG_CINFO_BYTES 2048           // room for the whole struct (the library reports its size: 656 bytes in libjpeg-turbo 2.1, ABI 8)
 
 struct JpegApi {
     jerr_abi *(*std_error)(jerr_abi *);
@@ -82,6 +85,7 @@ struct JpegApi {
     int (*start)(void *);
     unsigned (*read_scanlines)(void *, unsigned char **, unsigned);
     unsigned (*read_raw)(void *, unsigned char ***, unsigned);          // jpeg_read_raw_data (may be absent: the raw 4:2:0 path is then off)
+    void **(*read_coef)(void *);                                        // jpeg_read_coefficients (may be absent: the coefficient path is then off)
     int (*finish)(void *);
     void (*destroy)(void *);
     size_t cinfo_size;                  // as the library reports it
@@ -124,6 +128,7 @@ const JpegApi &api()
         a.start = (int (*)(void *))dlsym(h, "jpeg_start_decompress");
         a.read_scanlines = (unsigned (*)(void *, unsigned char **, unsigned))dlsym(h, "jpeg_read_scanlines");
         a.read_raw = (unsigned (*)(void *, unsigned char ***, unsigned))dlsym(h, "jpeg_read_raw_data");
+        a.read_coef = (void **(*)(void *))dlsym(h, "jpeg_read_coefficients");
         a.finish = (int (*)(void *))dlsym(h, "jpeg_finish_decompress");
         a.destroy = (void (*)(void *))dlsym(h, "jpeg_destroy_decompress");
         if (!a.std_error || !a.create || !a.mem_src || !a.read_header || !a.start || !a.read_scanlines || !a.finish || !a.destroy) return a;
@@ -160,6 +165,10 @@ const JpegApi &api()
     }();
     return A;
 }
+
+// zig-zag position -> natural (row-major) position of a coefficient
+const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // (rows, cols, components) from the first SOFn marker: the independent witness for the struct offsets
 bool sof_size(const unsigned char *p, size_t n, int *h, int *w, int *nc, int *samp = nullptr)
@@ -325,6 +334,154 @@ extern "C" int vfsms_jpeg_decode(const uint8_t *jpeg, size_t nbytes, int want_pl
         return jpeg_decode_raw420_host(jpeg, nbytes, out, cap, h, w);
     }
     return jpeg_decode_host(jpeg, nbytes, want_planes, out, cap, h, w, comp);
+}
+
+// ---- the host half of Method.jpegDecoder = "device" (jpeg_dec_kernels.hip; specified by tests/jpeg_dec_ref.py) --------------------------
+// More ABI knowledge: struct jpeg_memory_mgr opens with its method pointers -- alloc_small, alloc_large, alloc_sarray, alloc_barray,
+// request_virt_sarray, request_virt_barray, realize_virt_arrays, access_virt_sarray, access_virt_barray -- a layout that has not changed from
+// libjpeg 6b to libjpeg-turbo 3.  The ninth is the only way to the coefficient arrays of jpeg_read_coefficients:
+//     JBLOCKARRAY access_virt_barray(cinfo, jvirt_barray_ptr, start_row, num_rows, writable)         num_rows <= the component's v_samp_factor
+// The guard against a library laid out otherwise: the pointer read from that slot must lie in the same loaded object as
+// jpeg_read_coefficients (dladdr), else the path is refused before anything is called through it.
+namespace {
+struct FrameInfo {
+    int precision, h, w, nc, progressive;
+    int hs[4], vs[4], tq[4];
+    bool have[4];                       // quantisation table slot defined in front of the first scan
+    uint16_t q[4][64];                  // natural order
+    size_t sos;                         // where the first scan header starts
+};
+// SOI .. the first SOS: the frame header and every DQT segment (8- and 16-bit entries, zig-zag order in the file)
+bool parse_frame(const unsigned char *p, size_t n, FrameInfo *f)
+{
+    memset(f, 0, sizeof(*f));
+    if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return false;
+    size_t q = 2; bool sof = false;
+    while (q + 4 <= n) {
+        if (p[q] != 0xFF) return false;
+        const unsigned m = p[q + 1];
+        if (m == 0xFF) { q++; continue; }
+        if ((m >= 0xD0 && m <= 0xD9) || m == 0x01) { q += 2; continue; }
+        const size_t seg = ((size_t)p[q + 2] << 8) | p[q + 3];
+        if (seg < 2 || q + 2 + seg > n) return false;
+        if (m == 0xDA) { f->sos = q; return sof; }
+        if (m == 0xDB) {
+            size_t s = q + 4; const size_t end = q + 2 + seg;
+            while (s < end) {
+                const int pq = p[s] >> 4, t = p[s] & 15; s++;
+                if (t > 3 || pq > 1 || s + (pq ? 128 : 64) > end) return false;
+                for (int k = 0; k < 64; k++) {
+                    f->q[t][kZigzag[k]] = pq ? (uint16_t)((p[s] << 8) | p[s + 1]) : p[s];
+                    s += pq ? 2 : 1;
+                }
+                f->have[t] = true;
+            }
+        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            if (sof || seg < 8) return false;
+            f->precision = p[q + 4]; f->h = (p[q + 5] << 8) | p[q + 6]; f->w = (p[q + 7] << 8) | p[q + 8]; f->nc = p[q + 9];
+            f->progressive = m == 0xC2;
+            if (m > 0xC2 || f->nc < 1 || f->nc > 4 || seg < 8 + 3u * f->nc) { f->nc = 0; sof = true; q += 2 + seg; continue; }   // (a frame this path does not take: nc = 0)
+            for (int k = 0; k < f->nc; k++) { f->hs[k] = p[q + 11 + 3 * k] >> 4; f->vs[k] = p[q + 11 + 3 * k] & 15; f->tq[k] = p[q + 12 + 3 * k]; }
+            sof = true;
+        }
+        q += 2 + seg;
+    }
+    return false;
+}
+}  // namespace
+
+// The quantised DCT coefficients of a file, for the device's inverse transform.  `out` (the staging layout, include/vfsms.h): one uint16[64]
+// table per component in natural order, then per component its blocks in block-row-major order, 64 int16 each in natural order, on the grid
+// grid6 = (block rows, block columns) per component: ceil(h * v / (vmax * 8)) rounded up to a multiple of v by ceil(w * hs / (hmax * 8))
+// rounded up to a multiple of hs -- whole iMCUs.  luma_only: the blocks of component 0 alone (every table still).  *need: the bytes written,
+// also on VFSMS_ERR_CAPACITY (h, w, ncomp, grid6 are set then too).  Taken: 8-bit baseline / extended / progressive Huffman files of one
+// component, or of three (Y Cb Cr) sampled 2x2, 1x1, 1x1 with w >= 5 and h >= 2 -- the raw 4:2:0 path's condition, for its reason (k_ingest_420
+// follows).  VFSMS_ERR_UNSUPPORTED for anything else, VFSMS_ERR_BAD_ARG for a damaged file (any decoder warning).
+int jpeg_coefficients_host(const unsigned char *jpeg, size_t nbytes, int luma_only, unsigned char *out, size_t cap, int *h_out, int *w_out, int *ncomp,
+                           int *grid6, size_t *need_out)
+{
+    const JpegApi &A = api();
+    if (!A.ok || !A.read_coef) { vfsms_set_error("jpeg: no coefficient decode on this host"); return VFSMS_ERR_UNSUPPORTED; }
+    FrameInfo F;
+    if (!jpeg || !parse_frame(jpeg, nbytes, &F) || F.h <= 0 || F.w <= 0 || F.precision != 8 || (F.nc != 1 && F.nc != 3)) {
+        vfsms_set_error("jpeg: not an 8-bit 1- or 3-component Huffman JPEG"); return VFSMS_ERR_UNSUPPORTED;
+    }
+    if (F.nc == 3 && (F.hs[0] != 2 || F.vs[0] != 2 || F.hs[1] != 1 || F.vs[1] != 1 || F.hs[2] != 1 || F.vs[2] != 1 || F.w < 5 || F.h < 2)) {
+        vfsms_set_error("jpeg: not a 4:2:0 Y Cb Cr file"); return VFSMS_ERR_UNSUPPORTED;
+    }
+    // (a lone component's sampling factors only pad its grid: up to 2 the padded grid stays within the 16 x 16 iMCUs the callers size staging for)
+    if (F.nc == 1 && (F.hs[0] < 1 || F.hs[0] > 2 || F.vs[0] < 1 || F.vs[0] > 2)) { vfsms_set_error("jpeg: sampling factors beyond 2"); return VFSMS_ERR_UNSUPPORTED; }
+    for (int k = 0; k < F.nc; k++)
+        if (F.tq[k] > 3 || !F.have[F.tq[k]]) { vfsms_set_error("jpeg: a quantisation table is not defined in front of the first scan"); return VFSMS_ERR_UNSUPPORTED; }
+    // a table redefined between two scans would apply to the components that start later: the tables above would not be theirs.  In
+    // entropy-coded data FF is followed by 00 or RSTn only, so FF DB behind the first scan header is such a segment: the full decode takes it
+    for (const unsigned char *s = jpeg + F.sos, *e = jpeg + nbytes - 1; s < e && (s = (const unsigned char *)memchr(s, 0xFF, (size_t)(e - s))) != nullptr; s++)
+        if (s[1] == 0xDB) { vfsms_set_error("jpeg: quantisation tables redefined between scans"); return VFSMS_ERR_UNSUPPORTED; }
+    const int hmax = F.hs[0], vmax = F.vs[0];                    // (one component, or 2x2 in front of 1x1, 1x1: component 0 holds the maxima)
+    size_t need = (size_t)F.nc * VFSMS_JPEG_COEF_TABLE_BYTES;
+    const int ncopy = luma_only ? 1 : F.nc;
+    for (int k = 0; k < F.nc; k++) {
+        const long long br = ((long long)F.h * F.vs[k] + vmax * 8 - 1) / (vmax * 8), bc = ((long long)F.w * F.hs[k] + hmax * 8 - 1) / (hmax * 8);
+        grid6[2 * k] = (int)((br + F.vs[k] - 1) / F.vs[k] * F.vs[k]); grid6[2 * k + 1] = (int)((bc + F.hs[k] - 1) / F.hs[k] * F.hs[k]);
+        if (k < ncopy) need += (size_t)grid6[2 * k] * grid6[2 * k + 1] * 128;
+    }
+    *h_out = F.h; *w_out = F.w; *ncomp = F.nc; *need_out = need;
+    if (!out || cap < need) { vfsms_set_error("jpeg: output buffer too small"); return VFSMS_ERR_CAPACITY; }
+    alignas(16) unsigned char cinfo[JPEG_CINFO_BYTES]; memset(cinfo, 0, sizeof(cinfo));
+    jerr_abi err; memset(&err, 0, sizeof(err));
+    Guard g; memset(&g.code, 0, sizeof(g) - offsetof(Guard, code));
+    jdec_head_abi *c = (jdec_head_abi *)cinfo;
+    volatile bool created = false;
+    if (setjmp(g.jb)) {
+        if (created) A.destroy(cinfo);
+        vfsms_set_error("jpeg: %s", g.text[0] ? g.text : "decode error");
+        return VFSMS_ERR_BAD_ARG;
+    }
+    c->err = A.std_error(&err);
+    err.error_exit = on_error; err.output_message = on_message;
+    c->client_data = &g;
+    A.create(cinfo, JPEG_ABI_VERSION, A.cinfo_size);
+    created = true;
+    c->client_data = &g;
+    A.mem_src(cinfo, jpeg, (unsigned long)nbytes);
+    A.read_header(cinfo, 1);
+    if ((int)c->image_height != F.h || (int)c->image_width != F.w || c->num_components != F.nc || c->jpeg_color_space != (F.nc == 3 ? JCS_YCbCr_ : JCS_GRAYSCALE_)) {
+        A.destroy(cinfo);
+        vfsms_set_error("jpeg: not a gray / Y Cb Cr file (or an unexpected struct layout)");
+        return VFSMS_ERR_UNSUPPORTED;
+    }
+    typedef short (**barray_rows)[64];
+    typedef barray_rows (*access_fn)(void *, void *, unsigned, unsigned, int);
+    const access_fn access = c->mem ? (access_fn)((void **)c->mem)[8] : nullptr;
+    Dl_info da, db;
+    if (!access || !dladdr((void *)access, &da) || !dladdr((void *)A.read_coef, &db) || da.dli_fbase != db.dli_fbase) {
+        A.destroy(cinfo);
+        vfsms_set_error("jpeg: libjpeg.so.8 does not have the expected memory manager layout");
+        return VFSMS_ERR_UNSUPPORTED;
+    }
+    void **arrays = A.read_coef(cinfo);
+    if (!arrays) { A.destroy(cinfo); vfsms_set_error("jpeg: no coefficient arrays"); return VFSMS_ERR_BAD_ARG; }      // (suspension: cannot happen with a memory source)
+    for (int k = 0; k < F.nc; k++) memcpy(out + (size_t)k * VFSMS_JPEG_COEF_TABLE_BYTES, F.q[F.tq[k]], VFSMS_JPEG_COEF_TABLE_BYTES);
+    unsigned char *o = out + (size_t)F.nc * VFSMS_JPEG_COEF_TABLE_BYTES;
+    for (int k = 0; k < ncopy; k++) {
+        const size_t row_bytes = (size_t)grid6[2 * k + 1] * 128;
+        for (int r0 = 0; r0 < grid6[2 * k]; r0 += F.vs[k]) {                                   // one iMCU row of the component per access
+            barray_rows rows = access(cinfo, arrays[k], (unsigned)r0, (unsigned)F.vs[k], 0);
+            for (int r = 0; r < F.vs[k]; r++) { memcpy(o, rows[r], row_bytes); o += row_bytes; }
+        }
+    }
+    A.finish(cinfo);
+    const long warnings = err.num_warnings;
+    A.destroy(cinfo);
+    if (warnings) { vfsms_set_error("jpeg: truncated or damaged file (%ld decoder warnings)", warnings); return VFSMS_ERR_BAD_ARG; }
+    return VFSMS_OK;
+}
+
+// host-only entry (no context, no GPU), beside vfsms_jpeg_decode: the staging layout into the caller's memory
+extern "C" int vfsms_jpeg_coefficients(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t cap, int *h, int *w, int *ncomp, int *grid6, size_t *need)
+{
+    if (!h || !w || !ncomp || !grid6 || !need) { vfsms_set_error("jpeg_coefficients: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    return jpeg_coefficients_host(jpeg, nbytes, 0, out, cap, h, w, ncomp, grid6, need);
 }
 
 // ---- encode -----------------------------------------------------------------------------------------------------------------------------
@@ -510,8 +667,6 @@ const uint8_t kQuantLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 
                                 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
 const uint8_t kQuantChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
                                   99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 // Annex K: codes per length, then the symbols
 const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
 const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};

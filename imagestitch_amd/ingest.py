@@ -123,11 +123,13 @@ def _decode_once(path, want_color):
     return None, shape, ("arrays", gray, bgr)
 
 
-def _fill_from_jpeg(eng, path, gray_handle, color_handle):
+def _fill_from_jpeg(eng, path, gray_handle, color_handle, decoder="host"):
     """JPEG files are decoded by the library itself when it can (vfsms_tile_fill_jpeg: the system's libjpeg-turbo writes into pinned staging
     memory that is reused from tile to tile, outside the interpreter lock; one decode, colour conversion on the GPU) -> True, both tiles
     filled.  False: not a JPEG, an engine without the entry point, a file this decoder does not take (CMYK, RGB-coded, damaged, ...), or
-    VFSMS_NATIVE_JPEG=0 -- the tiles are still reserved and `_decode_once` (Pillow) decodes the file."""
+    VFSMS_NATIVE_JPEG=0 -- the tiles are still reserved and `_decode_once` (Pillow) decodes the file.
+    decoder "device" (Method.jpegDecoder): vfsms_tile_fill_jpeg_dct is tried first -- the host stops behind the entropy decode, the inverse
+    DCT runs on the device -> "dct" (true) when it filled the tiles; a file it does not take goes on exactly as above."""
     fill = getattr(eng, "tile_fill_jpeg", None)
     if fill is None or os.environ.get("VFSMS_NATIVE_JPEG", "1") == "0":
         return False
@@ -135,6 +137,8 @@ def _fill_from_jpeg(eng, path, gray_handle, color_handle):
         data = f.read()
     if data[:2] != b"\xff\xd8":
         return False
+    if decoder == "device" and eng.tile_fill_jpeg_dct(gray_handle, color_handle, data):
+        return "dct"
     return bool(fill(gray_handle, color_handle, data))
 
 
@@ -221,6 +225,7 @@ class TileIngest:
         from . import stitcher as ST                      # (the decode helpers are looked up there at call time: tests swap them)
         st, eng, fileList, shapes, color = self.st, self.eng, self.fileList, self.shapes, self.color
         handles, chandles = self.handles, self.chandles
+        device_dct = st._jpegDecoderOnDevice()            # (a choice the engine cannot serve raises before anything is reserved)
         if not hasattr(eng, "tile_reserve"):
             handles.extend(eng.tile_upload(ST._imread(f, False)) for f in fileList)
             return handles
@@ -251,9 +256,13 @@ class TileIngest:
             hc = chandles[k] if color else 0
             try:
                 t0 = time.perf_counter()
-                if ST._fill_from_jpeg(eng, fileList[k], handles[k], hc):
+                # ("host" makes the call it always made: whatever stands in for _fill_from_jpeg sees no new argument)
+                took = ST._fill_from_jpeg(eng, fileList[k], handles[k], hc, "device") if device_dct else ST._fill_from_jpeg(eng, fileList[k], handles[k], hc)
+                if took:
                     with istats_mu:
                         istats["tiles"] += 1; istats["native"] = istats.get("native", 0) + 1; istats["decode_s"] += time.perf_counter() - t0
+                        if took == "dct":
+                            istats["dct"] = istats.get("dct", 0) + 1
                     return
                 owner, shape, parts = ST._decode_once(fileList[k], color)
                 t1 = time.perf_counter()

@@ -273,6 +273,16 @@ class Stitcher(Utility.Method):
         self._pyramidBandRows(levels)
         return levels
 
+    def _jpegDecoderOnDevice(self):
+        """does the ingest try the device half of the JPEG decoder first (Method.jpegDecoder = "device")?"""
+        if self.jpegDecoder not in ("host", "device"):
+            raise ValueError("jpegDecoder must be 'host' or 'device', got %r" % (self.jpegDecoder,))
+        if self.jpegDecoder != "device":
+            return False
+        if not hasattr(self.engine, "tile_fill_jpeg_dct"):
+            raise NotImplementedError("jpegDecoder = 'device' needs an engine with tile_fill_jpeg_dct")
+        return True
+
     def _decoderThreads(self, n_files):
         """size of the decoder pool: `decodeThreads`, or one per host core up to 32 when the library decodes JPEGs itself (measured on the
         256-thread host of the MI355X box, colour 2048 x 2048: 1354 tiles/s at 16 threads, 1804 at 32; Pillow: 1094 at 16 and no more beyond)"""
@@ -1119,6 +1129,7 @@ class Stitcher(Utility.Method):
         eng = self.engine
         if len(set(files)) != len(files):                    # (a file listed twice: the host path keys nothing by name)
             return None
+        device_dct = self._jpegDecoderOnDevice()
         shapes = [_imshape(f) for f in files]
         handles = []
         try:
@@ -1127,7 +1138,7 @@ class Stitcher(Utility.Method):
 
             def ingest(k):
                 try:
-                    if _fill_from_jpeg(eng, files[k], 0 if color else handles[k], handles[k] if color else 0):
+                    if _fill_from_jpeg(eng, files[k], 0 if color else handles[k], handles[k] if color else 0, *(("device",) if device_dct else ())):
                         return
                     owner, shape, parts = _decode_once(files[k], color)
                     if tuple(shape) != tuple(shapes[k]):

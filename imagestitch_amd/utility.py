@@ -223,6 +223,15 @@ class Method():
     jpegQuality = 95
     jpegRestartMcus = 8
 
+    # ---- JPEG tiles decoded on the device (no reference counterpart; tests/jpeg_dec_ref.py).  jpegDecoder "host" (the default: nothing
+    # changes -- libjpeg-turbo decodes a file up to its sample planes on a decoder thread, vfsms_tile_fill_jpeg) or "device": the decoder
+    # thread stops behind the entropy decode (jpeg_read_coefficients) and dequantisation, the inverse DCT, the level shift and the clamp run
+    # where the tile is going (csrc/jpeg_dec_kernels.hip), followed by the chroma upsampling and colour conversion that run there already.
+    # The tiles hold the same bytes either way.  Taken: 8-bit gray and 4:2:0 Y Cb Cr files, baseline or progressive; any other file goes
+    # the "host" way, then Pillow's, decoded once.  Twice the bytes cross the link (2 per sample instead of 1), and the host's share is not
+    # gone: the library buffers the whole image's coefficients before they are copied -- README says what tools/bench_jpeg_decode.py measured.
+    jpegDecoder = "host"
+
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)
     _engine = None
 

@@ -187,6 +187,28 @@ int vfsms_tile_fill_jpeg(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint
  * then Cb and Cr (pitch pw / 2, ph / 2 rows) -- pw * ph * 3 / 2 bytes; what vfsms_tile_fill_jpeg stages when the device does the chroma
  * upsampling (VFSMS_ERR_UNSUPPORTED for any other sampling).                                                                            */
 int vfsms_jpeg_decode(const uint8_t *jpeg, size_t nbytes, int want_planes, uint8_t *out, size_t cap, int *h, int *w, int *comp);
+/* Method.jpegDecoder = "device" (csrc/jpeg_dec_kernels.hip; specified by tests/jpeg_dec_ref.py): the host stops behind the ENTROPY decode and
+ * the device does the rest of libjpeg's default decoder -- dequantisation, the integer inverse DCT of jidctint.c (JDCT_ISLOW), + 128, the clamp
+ * to 0..255 -- then, for a colour tile, what vfsms_tile_fill_jpeg's device half does already (k_ingest_420 / the gray replication).  Same
+ * bytes in both tiles as vfsms_tile_fill_jpeg, same contract, same return codes: any thread, returns when both tiles are complete, and
+ * VFSMS_ERR_UNSUPPORTED / VFSMS_ERR_BAD_ARG leave BOTH TILES RESERVED.  Taken: 8-bit Huffman files, baseline or progressive, of one component
+ * or of three (Y Cb Cr) sampled 2x2, 1x1, 1x1 with width >= 5 and height >= 2; anything else is VFSMS_ERR_UNSUPPORTED (vfsms_tile_fill_jpeg
+ * takes it), a damaged file -- any decoder warning -- VFSMS_ERR_BAD_ARG.
+ * The staging layout (vfsms_jpeg_coefficients writes it, host only: no context, no GPU): first one quantisation table per component,
+ * uint16[64] in NATURAL (row-major) order, VFSMS_JPEG_COEF_TABLE_BYTES each; then per component its blocks in block-row-major order, each
+ * block 64 int16 in natural order.  A component sampled hs x vs in a frame whose maxima are hmax x vmax has
+ *     grid6[2 k]     = ceil(h * vs / (vmax * 8)) rounded up to a multiple of vs     block rows
+ *     grid6[2 k + 1] = ceil(w * hs / (hmax * 8)) rounded up to a multiple of hs     block columns
+ * -- whole iMCUs: the luma grid of a 4:2:0 file covers exactly the pw x ph plane of the raw 4:2:0 layout below, the chroma grids its pw / 2 x
+ * ph / 2 planes.  *need = the bytes of the layout, also on VFSMS_ERR_CAPACITY (*h, *w, *ncomp, grid6 are set then too): call with out ==
+ * NULL to ask for the size.
+ * vfsms_jpeg_idct: the bare operator.  block_rows x block_cols blocks and ONE table in, host arrays; the plane out, block_rows * 8 rows of
+ * block_cols * 8 bytes, `pitch` bytes apart.  Exact while every intermediate of both passes fits int32 and every column-pass output int16
+ * (any coefficients a file holds are far inside; beyond, libjpeg's own C and SIMD transforms part ways).  Profile stage "jpeg_decode".    */
+#define VFSMS_JPEG_COEF_TABLE_BYTES 128
+int vfsms_tile_fill_jpeg_dct(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes);
+int vfsms_jpeg_coefficients(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t cap, int *h, int *w, int *ncomp, int *grid6, size_t *need);
+int vfsms_jpeg_idct(vfsms_ctx *ctx, const int16_t *coef, const uint16_t *quant, int block_rows, int block_cols, uint8_t *out, int pitch);
 /* The way out, for the mosaic: replaces cv2.imwrite(path, result) for .jpg results (Stitcher.py:149, 175-179; Main.py:21-51 writes every
  * result as jpg).  vfsms_jpeg_encode: n_rows x cols pixels of 1 or 3 channels (R G B, or B G R -- the canvas order -- with bgr != 0), rows
  * `stride_bytes` apart -> a complete baseline JPEG stream with cv2.imwrite's settings (libjpeg defaults, `quality`: 95).  No context, no GPU,
