@@ -97,6 +97,10 @@ _SIGNATURES = {
     "vfsms_jpeg_coefficients": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "vfsms_jpeg_idct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "vfsms_tile_fill_jpeg_huff": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]),
+    "vfsms_jpeg_scan": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vfsms_jpeg_entropy_decode": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "vfsms_jpeg_decode": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vfsms_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vfsms_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -442,6 +446,41 @@ class Engine:
             return False
         self._check(rc)
         return True
+
+    def tile_fill_jpeg_huff(self, gray_handle, color_handle, data):
+        """tile_fill_jpeg with the whole decoder on the device (vfsms_tile_fill_jpeg_huff, Method.jpegDecoder = "device-entropy"): the host scans
+        the file for its markers, the compressed bytes cross the link, Huffman decode, DC prediction, dequantisation and inverse DCT run on the
+        device (csrc/jpeg_huff_kernels.hip, csrc/jpeg_dec_kernels.hip).  Same bytes in the tiles, same answer: True when they are filled, False
+        when this path does not take the file -- the tiles are STILL RESERVED, tile_fill_jpeg_dct or tile_fill_jpeg is next.  Any thread."""
+        rc = self.lib.vfsms_tile_fill_jpeg_huff(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
+        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
+            return False
+        self._check(rc)
+        return True
+
+    def jpeg_scan(self, data):
+        """the module's jpeg_scan (vfsms_jpeg_scan: host only, no GPU): the scan record of a file as a dict, or its refusal code"""
+        return jpeg_scan(data)
+
+    def jpeg_entropy_decode(self, data, max_rounds=-1):
+        """vfsms_jpeg_entropy_decode, the bare operator: file bytes -> (rc, h, w, comps, rounds_used), comps as jpeg_coefficients returns them
+        -- [(coef int16 (block_rows, block_cols, 64), quant uint16 (64,))] -- decoded by the device.  rc: VFSMS_OK, or VFSMS_ERR_UNSUPPORTED /
+        VFSMS_ERR_BAD_ARG with comps None (a file not taken or not in step after max_rounds repair rounds / a damaged file).  max_rounds -1:
+        as many as there are subsequences."""
+        h, w, nc, need, used = C.c_int(), C.c_int(), C.c_int(), C.c_size_t(), C.c_int()
+        grid = (C.c_int * 6)()
+        args = (C.byref(h), C.byref(w), C.byref(nc), grid, C.byref(need), C.byref(used))
+        rc = self.lib.vfsms_jpeg_entropy_decode(self.ctx, data, len(data), int(max_rounds), None, 0, *args)
+        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
+            return rc, 0, 0, None, 0
+        if rc != VFSMS_ERR_CAPACITY:
+            self._check(rc)
+        out = np.empty(need.value, np.uint8)
+        rc = self.lib.vfsms_jpeg_entropy_decode(self.ctx, data, len(data), int(max_rounds), out.ctypes.data_as(C.c_void_p), out.nbytes, *args)
+        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
+            return rc, h.value, w.value, None, 0
+        self._check(rc)
+        return rc, h.value, w.value, _coefficient_layout(out, nc.value, grid), used.value
 
     def jpeg_idct(self, coef, quant, pitch=None):
         """vfsms_jpeg_idct, the bare operator: `coef` int16 (block_rows, block_cols, 64), quantised coefficients in natural order, and `quant`
@@ -1245,6 +1284,55 @@ def jpeg_decode_raw420(data):
     return out[:n].reshape(ph, pw), out[n:n + n // 4].reshape(ph // 2, pw // 2), out[n + n // 4:].reshape(ph // 2, pw // 2), h.value, w.value
 
 
+def _coefficient_layout(out, n, grid):
+    """the bytes of vfsms_jpeg_coefficients' layout -> [(coef int16 (block_rows, block_cols, 64), quant uint16 (64,))] per component"""
+    comps, off = [], 128 * n
+    for k in range(n):
+        br, bc = grid[2 * k], grid[2 * k + 1]
+        nb = br * bc * 128
+        comps.append((out[off:off + nb].view(np.int16).reshape(br, bc, 64), out[128 * k:128 * (k + 1)].view(np.uint16)))
+        off += nb
+    return comps
+
+
+SCAN_HEADER_FIELDS = ("h", "w", "ncomp", "grid0", "grid1", "grid2", "grid3", "grid4", "grid5", "restart_interval", "nseg", "nsub", "mcus",
+                      "blocks_per_mcu", "sub_bits", "stream_bytes", "off_quant", "off_tables", "off_stream", "off_seg", "off_subseg", "total_bytes")
+HUFF_TABLE_BYTES = 2 * 512 + 4 * 17 + 4 * 17 + 256 + 16
+
+
+def jpeg_scan(data):
+    """vfsms_jpeg_scan: the host half of Method.jpegDecoder = "device-entropy", no GPU and no libjpeg involved -- the file read once for its
+    markers -> dict(the header fields of SCAN_HEADER_FIELDS, grid6, quant = [uint16 (64,) natural order per component],
+    dht = [(counts uint8 (16,), values uint8 (n,)) per component DC then AC], segments = [(bytes, first MCU, first subsequence)] unstuffed,
+    subseg = uint32 (nsub,), record = the raw bytes).  A file not taken: the int return code (VFSMS_ERR_UNSUPPORTED / VFSMS_ERR_BAD_ARG)."""
+    lib = load_library()
+    need = C.c_size_t()
+    rc = lib.vfsms_jpeg_scan(data, len(data), None, 0, C.byref(need))
+    if rc != VFSMS_ERR_CAPACITY:
+        return rc
+    rec = np.zeros(need.value, np.uint8)
+    rc = lib.vfsms_jpeg_scan(data, len(data), rec.ctypes.data_as(C.c_void_p), rec.nbytes, C.byref(need))
+    if rc != VFSMS_OK:
+        return rc
+    rec = rec[:need.value]
+    head = rec[:4 * len(SCAN_HEADER_FIELDS)].view(np.uint32)
+    out = {k: int(v) for k, v in zip(SCAN_HEADER_FIELDS, head)}
+    nc = out["ncomp"]
+    out["grid6"] = [out["grid%d" % k] for k in range(6)]
+    out["quant"] = [rec[out["off_quant"] + 128 * k:out["off_quant"] + 128 * (k + 1)].view(np.uint16).copy() for k in range(nc)]
+    out["dht"] = []
+    for k in range(2 * nc):
+        t = rec[out["off_tables"] + k * HUFF_TABLE_BYTES:out["off_tables"] + (k + 1) * HUFF_TABLE_BYTES]
+        counts = t[-16:].copy()
+        out["dht"].append((counts, t[-272:-16][:int(counts.sum())].copy()))
+    segs = rec[out["off_seg"]:out["off_seg"] + 16 * out["nseg"]].view(np.uint32).reshape(-1, 4)
+    base = out["off_stream"]
+    out["segments"] = [(rec[base + int(o):base + int(o) + int(n)].tobytes(), int(m), int(s0)) for o, n, m, s0 in segs]
+    out["subseg"] = rec[out["off_subseg"]:out["off_subseg"] + 4 * out["nsub"]].view(np.uint32).copy()
+    out["record"] = rec
+    return out
+
+
 def jpeg_coefficients(data):
     """vfsms_jpeg_coefficients: the host half of Method.jpegDecoder = "device", no GPU involved -- the quantised DCT coefficients of a JPEG
     file as the entropy decode leaves them (what vfsms_tile_fill_jpeg_dct stages for the device's inverse transform) -> (h, w, comps), comps a
@@ -1260,14 +1348,7 @@ def jpeg_coefficients(data):
     rc = lib.vfsms_jpeg_coefficients(data, len(data), out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(h), C.byref(w), C.byref(nc), grid, C.byref(need))
     if rc != VFSMS_OK:
         return None
-    n = nc.value
-    comps, off = [], 128 * n
-    for k in range(n):
-        br, bc = grid[2 * k], grid[2 * k + 1]
-        nb = br * bc * 128
-        comps.append((out[off:off + nb].view(np.int16).reshape(br, bc, 64), out[128 * k:128 * (k + 1)].view(np.uint16)))
-        off += nb
-    return h.value, w.value, comps
+    return h.value, w.value, _coefficient_layout(out, nc.value, grid)
 
 
 def _last_error(lib):

@@ -1,5 +1,6 @@
 // api.hip -- context management and the extern "C" entry points declared in include/vfsms.h.
 #include "common.h"
+#include "jpeg_huff_core.h"
 #include "phase_resolve_math.h"
 #include <math.h>
 #include <stdarg.h>
@@ -664,6 +665,32 @@ extern "C" int vfsms_tile_fill_jpeg(vfsms_ctx *ctx, int64_t gray, int64_t color,
     return rc;
 }
 
+// the device end of both device decoders: the coefficients of a file lie on the device (`blocks`: per wanted component its grid of blocks,
+// back to back; `quant`: a table per component) -> k_jpeg_idct -> the gray tile itself, or the three planes in `scratch` -> k_ingest_420, or
+// the gray replication.  Stream-ordered on the copy stream
+static int jpeg_coefficients_to_tiles(vfsms_ctx *ctx, const uint16_t *quant, const int16_t *blocks, int nc, const int *grid, int h, int w,
+                                      uint8_t *dg, uint8_t *dc, uint8_t *scratch)
+{
+    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
+    const bool planes = nc == 3 && dc;
+    JpegIdctArgs A; memset(&A, 0, sizeof(A));
+    A.ncomp = planes ? 3 : 1;
+    for (int k = 0; k < A.ncomp; k++) {
+        JpegIdctComp &C = A.c[k];
+        C.coef = blocks + (size_t)A.total * 64; C.quant = quant + (size_t)k * (VFSMS_JPEG_COEF_TABLE_BYTES / 2);
+        C.bcols = grid[2 * k + 1]; C.first = A.total;
+        if (planes) {                                            // Y at pitch pw, then Cb, then Cr at pitch pw / 2: the whole grid, nothing cropped
+            C.dst = k == 0 ? scratch : scratch + (size_t)pw * ph + (size_t)(k - 1) * (pw / 2) * (ph / 2);
+            C.pitch = k == 0 ? pw : pw / 2; C.rows = grid[2 * k] * 8; C.cols = grid[2 * k + 1] * 8;
+        } else { C.dst = dg ? dg : scratch; C.pitch = w; C.rows = h; C.cols = w; }
+        A.total += (unsigned)grid[2 * k] * (unsigned)grid[2 * k + 1];
+    }
+    int rc = launch_jpeg_idct(ctx->copy_stream, A);
+    if (rc == VFSMS_OK && planes) rc = launch_ingest_420(ctx->copy_stream, scratch, pw, ph, h, w, dg, dc);
+    else if (rc == VFSMS_OK && dc) rc = launch_ingest_split(ctx->copy_stream, dg ? dg : scratch, nullptr, dc, (long long)h * w, VFSMS_SRC_GRAY8);
+    return rc;
+}
+
 // Method.jpegDecoder = "device": the same contract as vfsms_tile_fill_jpeg, but the host stops behind the ENTROPY decode
 // (jpeg_coefficients_host: jpeg_read_coefficients into pinned staging) and dequantisation, inverse DCT, level shift and range limit run on the
 // device (k_jpeg_idct, csrc/jpeg_dec_kernels.hip), stream-ordered on the copy stream like everything else of the ingest.  Gray wanted alone:
@@ -704,22 +731,7 @@ extern "C" int vfsms_tile_fill_jpeg_dct(vfsms_ctx *ctx, int64_t gray, int64_t co
     if (e == hipSuccess && via_scratch) e = stage_device_get(ctx, scratch_bytes, &sp);
     if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
     if (e == hipSuccess) {
-        JpegIdctArgs A; memset(&A, 0, sizeof(A));
-        const int16_t *blocks = (const int16_t *)(sb.ptr + (size_t)nc * VFSMS_JPEG_COEF_TABLE_BYTES);
-        A.ncomp = planes ? 3 : 1;
-        for (int k = 0; k < A.ncomp; k++) {
-            JpegIdctComp &C = A.c[k];
-            C.coef = blocks + (size_t)A.total * 64; C.quant = (const uint16_t *)(sb.ptr + (size_t)k * VFSMS_JPEG_COEF_TABLE_BYTES);
-            C.bcols = grid[2 * k + 1]; C.first = A.total;
-            if (planes) {                                            // Y at pitch pw, then Cb, then Cr at pitch pw / 2: the whole grid, nothing cropped
-                C.dst = k == 0 ? sp.ptr : sp.ptr + (size_t)pw * ph + (size_t)(k - 1) * (pw / 2) * (ph / 2);
-                C.pitch = k == 0 ? pw : pw / 2; C.rows = grid[2 * k] * 8; C.cols = grid[2 * k + 1] * 8;
-            } else { C.dst = dg ? dg : sp.ptr; C.pitch = w; C.rows = h; C.cols = w; }
-            A.total += (unsigned)grid[2 * k] * (unsigned)grid[2 * k + 1];
-        }
-        rc = launch_jpeg_idct(ctx->copy_stream, A);
-        if (rc == VFSMS_OK && planes) rc = launch_ingest_420(ctx->copy_stream, sp.ptr, pw, ph, h, w, dg, dc);
-        else if (rc == VFSMS_OK && dc) rc = launch_ingest_split(ctx->copy_stream, dg ? dg : sp.ptr, nullptr, dc, (long long)h * w, VFSMS_SRC_GRAY8);
+        rc = jpeg_coefficients_to_tiles(ctx, (const uint16_t *)sb.ptr, (const int16_t *)(sb.ptr + (size_t)nc * VFSMS_JPEG_COEF_TABLE_BYTES), nc, grid, h, w, dg, dc, sp.ptr);
     }
     if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
     if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
@@ -757,6 +769,115 @@ extern "C" int vfsms_jpeg_idct(vfsms_ctx *ctx, const int16_t *coef, const uint16
     }
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)pitch, d_out, (size_t)block_cols * 8, (size_t)block_cols * 8, (size_t)block_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
+// Method.jpegDecoder = "device-entropy": the contract of vfsms_tile_fill_jpeg_dct, but the host only scans the file for its markers
+// (jpeg_scan_host: no libjpeg) and the entropy decode runs on the device too (csrc/jpeg_huff_kernels.hip), into a device buffer in the layout
+// the inverse transform takes.  The compressed bytes alone cross the link.  The decode waits for the device between its stages (the round
+// flags, the damage flags) on an event of its own; the tiles are written only after the damage flags came back clean.
+extern "C" int vfsms_tile_fill_jpeg_huff(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes)
+{
+    CTX_ENTER(ctx);
+    const char *who = "tile_fill_jpeg_huff";
+    if (!jpeg || !nbytes) { vfsms_set_error("%s: no data", who); return VFSMS_ERR_BAD_ARG; }
+    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
+    TRY(fill_pair_lookup(ctx, gray, color, false, who, &h, &w, &ev, &dg, &dc));
+    size_t bound = 0, need = 0;
+    int rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, nullptr, 0, &bound);
+    if (rc != VFSMS_ERR_CAPACITY) return rc;
+    const size_t flags_at = (bound + 15) & ~(size_t)15, cap = flags_at + (VFSMS_JPEG_HUFF_MAX_ROUNDS + 2) * sizeof(uint32_t);
+    StageBuf pb{nullptr, 0};
+    std::vector<uint8_t> pageable;
+    uint8_t *host = nullptr;
+    if (stage_pinned_get(ctx, cap, &pb) == VFSMS_OK) host = pb.ptr;
+    else { pb.ptr = nullptr; pageable.resize(cap); host = pageable.data(); }
+    rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, host, bound, &need);
+    JpegScanHeader H; memset(&H, 0, sizeof(H));
+    if (rc == VFSMS_OK) {
+        memcpy(&H, host, sizeof(H));
+        if (H.h != h || H.w != w) { vfsms_set_error("%s: the file is %d x %d, the reserved tiles %d x %d", who, H.h, H.w, h, w); rc = VFSMS_ERR_BAD_ARG; }
+    }
+    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
+    const int *grid = H.grid6;
+    if (rc == VFSMS_OK && H.ncomp == 3 && dc && (grid[0] * 8 != ph || grid[1] * 8 != pw || grid[2] * 16 != ph || grid[3] * 16 != pw || grid[4] != grid[2] || grid[5] != grid[3])) {
+        vfsms_set_error("%s: the block grid is not the raw 4:2:0 layout's", who); rc = VFSMS_ERR_UNSUPPORTED;      // (cannot happen: both follow from h, w and 2x2, 1x1, 1x1)
+    }
+    if (rc != VFSMS_OK) { stage_pinned_put(ctx, pb); return rc; }
+    const int nc = H.ncomp;
+    const bool planes = nc == 3 && dc, via_scratch = planes || (nc == 1 && !dg);
+    const size_t scratch_bytes = planes ? (size_t)pw * ph * 3 / 2 : (size_t)h * w;
+    size_t coef_bytes = 0;
+    for (int k = 0; k < (dc ? nc : 1); k++) coef_bytes += (size_t)grid[2 * k] * grid[2 * k + 1] * 128;
+    StageBuf sb{nullptr, 0}, sw{nullptr, 0}, sc{nullptr, 0}, sp{nullptr, 0};
+    hipEvent_t sync = nullptr;
+    hipError_t e = stage_device_get(ctx, need, &sb);
+    if (e == hipSuccess) e = stage_device_get(ctx, jpeg_huff_work_bytes(H, VFSMS_JPEG_HUFF_MAX_ROUNDS), &sw);
+    if (e == hipSuccess) e = stage_device_get(ctx, coef_bytes, &sc);
+    if (e == hipSuccess && via_scratch) e = stage_device_get(ctx, scratch_bytes, &sp);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&sync, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
+    bool refused = false;
+    if (e == hipSuccess) {
+        int used = 0;
+        rc = jpeg_huff_decode_device(ctx->copy_stream, sync, H, sb.ptr, sw.ptr, (uint32_t *)(host + flags_at), VFSMS_JPEG_HUFF_MAX_ROUNDS, dc == nullptr,
+                                     (int16_t *)sc.ptr, &used, nullptr);
+        // a file handed back -- the decoders not in step, damage -- has touched no tile, and the decode has waited for all it launched
+        refused = rc == VFSMS_ERR_UNSUPPORTED || rc == VFSMS_ERR_BAD_ARG;
+        if (rc == VFSMS_OK) rc = jpeg_coefficients_to_tiles(ctx, (const uint16_t *)(sb.ptr + H.off_quant), (const int16_t *)sc.ptr, nc, grid, h, w, dg, dc, sp.ptr);
+    }
+    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
+    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
+    if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
+    if (sync) hipEventDestroy(sync);
+    stage_device_put(ctx, sb); stage_device_put(ctx, sw); stage_device_put(ctx, sc); stage_device_put(ctx, sp);
+    stage_pinned_put(ctx, pb);
+    if (refused && e == hipSuccess) return rc;                                        // both tiles stay reserved
+    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
+    if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
+    return rc;
+}
+
+// the bare operator behind it: file bytes in, the layout of vfsms_jpeg_coefficients out, to a host array.  Profile stage "jpeg_entropy"
+extern "C" int vfsms_jpeg_entropy_decode(vfsms_ctx *ctx, const uint8_t *jpeg, size_t nbytes, int max_rounds, uint8_t *out, size_t cap, int *h, int *w, int *ncomp,
+                                         int *grid6, size_t *need, int *rounds_used)
+{
+    CTX_ENTER(ctx);
+    if (!jpeg || !nbytes || !h || !w || !ncomp || !grid6 || !need) { vfsms_set_error("jpeg_entropy_decode: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    size_t bound = 0, rec_bytes = 0;
+    int rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, nullptr, 0, &bound);
+    if (rc != VFSMS_ERR_CAPACITY) return rc;
+    std::vector<uint8_t> rec(bound);
+    TRY(jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, rec.data(), bound, &rec_bytes));
+    JpegScanHeader H; memcpy(&H, rec.data(), sizeof(H));
+    size_t coef_bytes = 0;
+    for (int k = 0; k < H.ncomp; k++) { grid6[2 * k] = H.grid6[2 * k]; grid6[2 * k + 1] = H.grid6[2 * k + 1]; coef_bytes += (size_t)H.grid6[2 * k] * H.grid6[2 * k + 1] * 128; }
+    const size_t tables = (size_t)H.ncomp * VFSMS_JPEG_COEF_TABLE_BYTES;
+    *h = H.h; *w = H.w; *ncomp = H.ncomp; *need = tables + coef_bytes;
+    if (!out || cap < *need) { vfsms_set_error("jpeg_entropy_decode: output buffer too small"); return VFSMS_ERR_CAPACITY; }
+    const int rounds = max_rounds < 0 || max_rounds > H.nsub ? H.nsub : max_rounds;
+    const size_t work = jpeg_huff_work_bytes(H, rounds);
+    TRY(ctx_arena_reserve(ctx, rec_bytes + work + coef_bytes + 4096));
+    uint8_t *d_rec = (uint8_t *)ctx_arena_alloc(ctx, rec_bytes), *d_work = (uint8_t *)ctx_arena_alloc(ctx, work);
+    int16_t *d_coef = (int16_t *)ctx_arena_alloc(ctx, coef_bytes);
+    if (!d_rec || !d_work || !d_coef) { vfsms_set_error("arena exhausted (jpeg_entropy_decode)"); return VFSMS_ERR_CAPACITY; }
+    std::vector<uint32_t> flags((size_t)rounds + 2);
+    hipEvent_t sync = nullptr;
+    HIP_TRY(hipEventCreateWithFlags(&sync, hipEventDisableTiming));
+    hipError_t e = hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, ctx->stream);
+    int used = 0;
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "jpeg_entropy");
+        rc = jpeg_huff_decode_device(ctx->stream, sync, H, d_rec, d_work, flags.data(), rounds, 0, d_coef, &used, ctx);
+    }
+    if (e == hipSuccess && rc == VFSMS_OK) e = hipMemcpyAsync(out + tables, d_coef, coef_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    hipEventDestroy(sync);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { vfsms_set_error("jpeg_entropy_decode: %s", hipGetErrorString(e)); return VFSMS_ERR_HIP; }
+    if (rc != VFSMS_OK) return rc;
+    memcpy(out, rec.data() + H.off_quant, tables);
+    if (rounds_used) *rounds_used = used;
     return VFSMS_OK;
 }
 

@@ -398,6 +398,12 @@ struct JpegIdctArgs { JpegIdctComp c[3]; int ncomp; unsigned total; };
 int launch_jpeg_idct(hipStream_t stream, const JpegIdctArgs &A);
 int jpeg_coefficients_host(const unsigned char *jpeg, size_t nbytes, int luma_only, unsigned char *out, size_t cap, int *h, int *w, int *ncomp,
                            int *grid6, size_t *need);
+// jpeg_host.cpp / jpeg_huff_kernels.hip: the entropy decode on the device (tests/jpeg_huff_ref.py; the records are csrc/jpeg_huff_core.h's)
+struct JpegScanHeader;
+int jpeg_scan_host(const unsigned char *jpeg, size_t nbytes, int sub_bits, unsigned char *out, size_t cap, size_t *need);
+size_t jpeg_huff_work_bytes(const JpegScanHeader &H, int max_rounds);
+int jpeg_huff_decode_device(hipStream_t stream, hipEvent_t sync, const JpegScanHeader &H, const uint8_t *d_rec, uint8_t *d_work, uint32_t *h_flags,
+                            int max_rounds, int luma_only, int16_t *d_coef, int *rounds_used, vfsms_ctx *prof);
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
 size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);

@@ -26,6 +26,7 @@
 // (jpeg_CreateDecompress is first called with a wrong size; its JERR_BAD_STRUCT_SIZE error carries the size the library expects), and
 // after jpeg_read_header the image size read through these offsets must equal the size this file parses from the SOF marker itself.
 #include "common.h"
+#include "jpeg_huff_core.h"
 #include <dlfcn.h>
 #include <setjmp.h>
 #include <string.h>
@@ -482,6 +483,187 @@ extern "C" int vfsms_jpeg_coefficients(const uint8_t *jpeg, size_t nbytes, uint8
 {
     if (!h || !w || !ncomp || !grid6 || !need) { vfsms_set_error("jpeg_coefficients: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     return jpeg_coefficients_host(jpeg, nbytes, 0, out, cap, h, w, ncomp, grid6, need);
+}
+
+// ---- the host half of Method.jpegDecoder = "device-entropy" (jpeg_huff_kernels.hip; specified by tests/jpeg_huff_ref.py: parse) ------------
+// No libjpeg here and no GPU: the file is read once for its markers.  SOI .. SOS give the frame, the quantisation tables, the Huffman tables
+// (built into their decoding form by jh_build_table) and the restart interval; the entropy-coded data behind the scan header is copied with
+// its FF 00 stuffing removed, cut at the RSTn markers into segments that each start on a dword and are padded with FF to one, up to EOI.
+// UNSUPPORTED: a file the device decoder does not take.  BAD_ARG: one it would take, damaged.
+namespace {
+struct ScanFrame {
+    int precision, h, w, nc, ri;
+    int cid[3], hs[3], vs[3], tq[3], td[3], ta[3];
+    bool haveq[4], haveh[2][4];
+    uint16_t q[4][64];                  // natural order
+    uint8_t hcounts[2][4][16], hvals[2][4][256];
+    size_t data;                        // the first byte behind the scan header
+};
+int scan_refuse(int rc, const char *what) { vfsms_set_error("jpeg_scan: %s", what); return rc; }
+#define SCAN_UNSUPPORTED(what) return scan_refuse(VFSMS_ERR_UNSUPPORTED, what)
+#define SCAN_DAMAGED(what) return scan_refuse(VFSMS_ERR_BAD_ARG, what)
+int scan_headers(const unsigned char *p, size_t n, ScanFrame *F)
+{
+    memset(F, 0, sizeof(*F));
+    if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) SCAN_UNSUPPORTED("no SOI");
+    size_t q = 2; bool sof = false; int nc_frame = 0;
+    const unsigned char *seg = nullptr; size_t len = 0;
+    for (;;) {
+        if (q + 4 > n) SCAN_DAMAGED("no scan");
+        if (p[q] != 0xFF) SCAN_DAMAGED("marker expected");
+        const unsigned m = p[q + 1];
+        if (m == 0xFF) { q++; continue; }
+        if ((m >= 0xD0 && m <= 0xD7) || m == 0x01) { q += 2; continue; }
+        if (m == 0xD8 || m == 0xD9) SCAN_DAMAGED("SOI / EOI in front of the scan");
+        const size_t sl = ((size_t)p[q + 2] << 8) | p[q + 3];
+        if (sl < 2 || q + 2 + sl > n) SCAN_DAMAGED("segment beyond the file");
+        seg = p + q + 4; len = sl - 2;
+        if (m == 0xDB) {
+            size_t s = 0;
+            while (s < len) {
+                const int pq = seg[s] >> 4, t = seg[s] & 15; s++;
+                if (pq > 1 || t > 3 || s + (pq ? 128 : 64) > len) SCAN_DAMAGED("DQT");
+                for (int k = 0; k < 64; k++) { F->q[t][kZigzag[k]] = pq ? (uint16_t)((seg[s] << 8) | seg[s + 1]) : seg[s]; s += pq ? 2 : 1; }
+                F->haveq[t] = true;
+            }
+        } else if (m == 0xC4) {
+            size_t s = 0;
+            while (s < len) {
+                if (s + 17 > len) SCAN_DAMAGED("DHT");
+                const int tc = seg[s] >> 4, th = seg[s] & 15;
+                size_t nv = 0;
+                for (int k = 0; k < 16; k++) nv += seg[s + 1 + k];
+                if (tc > 1 || th > 3 || nv > 256 || s + 17 + nv > len) SCAN_DAMAGED("DHT");
+                JpegHuffTable T;
+                bool ok = jh_build_table(seg + s + 1, seg + s + 17, &T);
+                for (size_t k = 0; ok && tc == 0 && k < nv; k++) ok = seg[s + 17 + k] <= 15;
+                if (!ok) SCAN_DAMAGED("DHT: no prefix code");
+                memcpy(F->hcounts[tc][th], seg + s + 1, 16);
+                memset(F->hvals[tc][th], 0, 256); memcpy(F->hvals[tc][th], seg + s + 17, nv);
+                F->haveh[tc][th] = true;
+                s += 17 + nv;
+            }
+        } else if (m == 0xDD) {
+            if (sl != 4) SCAN_DAMAGED("DRI");
+            F->ri = (seg[0] << 8) | seg[1];
+        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            if (sof) SCAN_UNSUPPORTED("two frames");
+            if (m > 0xC1) SCAN_UNSUPPORTED("not a baseline / extended sequential Huffman file");
+            if (sl < 8 || sl != 8 + 3u * seg[5]) SCAN_DAMAGED("SOF");
+            F->precision = seg[0]; F->h = (seg[1] << 8) | seg[2]; F->w = (seg[3] << 8) | seg[4]; nc_frame = seg[5];
+            for (int k = 0; k < nc_frame && k < 3; k++) { F->cid[k] = seg[6 + 3 * k]; F->hs[k] = seg[7 + 3 * k] >> 4; F->vs[k] = seg[7 + 3 * k] & 15; F->tq[k] = seg[8 + 3 * k]; }
+            sof = true;
+        } else if (m == 0xDA) { q += 2 + sl; break; }
+        q += 2 + sl;
+    }
+    if (!sof) SCAN_DAMAGED("a scan without a frame");
+    if (F->precision != 8 || F->h <= 0 || F->w <= 0 || (nc_frame != 1 && nc_frame != 3)) SCAN_UNSUPPORTED("not 8 bits, 1 or 3 components");
+    F->nc = nc_frame;
+    if (F->nc == 3 && (F->hs[0] != 2 || F->vs[0] != 2 || F->hs[1] != 1 || F->vs[1] != 1 || F->hs[2] != 1 || F->vs[2] != 1 || F->w < 5 || F->h < 2))
+        SCAN_UNSUPPORTED("not a 4:2:0 Y Cb Cr file");
+    if (F->nc == 1 && (F->hs[0] < 1 || F->hs[0] > 2 || F->vs[0] < 1 || F->vs[0] > 2)) SCAN_UNSUPPORTED("sampling factors beyond 2");
+    if (len < 1 || seg[0] != F->nc || len != 4 + 2u * F->nc) SCAN_UNSUPPORTED("several scans");           // (a scan that does not hold every component)
+    for (int k = 0; k < F->nc; k++) {
+        if (seg[1 + 2 * k] != F->cid[k]) SCAN_UNSUPPORTED("scan components out of frame order");
+        F->td[k] = seg[2 + 2 * k] >> 4; F->ta[k] = seg[2 + 2 * k] & 15;
+        if (F->tq[k] > 3 || !F->haveq[F->tq[k]] || F->td[k] > 3 || F->ta[k] > 3 || !F->haveh[0][F->td[k]] || !F->haveh[1][F->ta[k]])
+            SCAN_UNSUPPORTED("a table is not defined in front of the scan");
+    }
+    if (seg[1 + 2 * F->nc] != 0 || seg[2 + 2 * F->nc] != 63 || seg[3 + 2 * F->nc] != 0) SCAN_UNSUPPORTED("not a sequential scan");
+    F->data = q;
+    return VFSMS_OK;
+}
+size_t scan_align(size_t v) { return (v + 15) & ~(size_t)15; }
+}  // namespace
+
+// The scan record of a file (csrc/jpeg_huff_core.h: JpegScanHeader and what its offsets name) into `out`.  *need: with VFSMS_OK the bytes
+// written; with VFSMS_ERR_CAPACITY (out == NULL asks) a bound on them that holds for this file, from its headers and its size alone.
+int jpeg_scan_host(const unsigned char *jpeg, size_t nbytes, int sub_bits, unsigned char *out, size_t cap, size_t *need)
+{
+    if (!jpeg || !need || sub_bits < 64 || sub_bits > (1 << 20) || (sub_bits & 31)) { vfsms_set_error("jpeg_scan: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (nbytes > ((size_t)1 << 28)) SCAN_UNSUPPORTED("a file beyond 256 MiB");                            // (bit positions stay below 2^31)
+    ScanFrame F;
+    TRY(scan_headers(jpeg, nbytes, &F));
+    JpegScanHeader H; memset(&H, 0, sizeof(H));
+    H.h = F.h; H.w = F.w; H.ncomp = F.nc; H.restart_interval = F.ri; H.sub_bits = sub_bits;
+    const int hmax = F.hs[0], vmax = F.vs[0];
+    for (int k = 0; k < F.nc; k++) {
+        const long long br = ((long long)F.h * F.vs[k] + vmax * 8 - 1) / (vmax * 8), bc = ((long long)F.w * F.hs[k] + hmax * 8 - 1) / (hmax * 8);
+        H.grid6[2 * k] = (int)((br + F.vs[k] - 1) / F.vs[k] * F.vs[k]); H.grid6[2 * k + 1] = (int)((bc + F.hs[k] - 1) / F.hs[k] * F.hs[k]);
+    }
+    H.blocks_per_mcu = F.nc == 3 ? 6 : 1;
+    H.mcus = F.nc == 3 ? H.grid6[2] * H.grid6[3] : ((F.h + 7) / 8) * ((F.w + 7) / 8);
+    const size_t entropy = nbytes - F.data;
+    const size_t want = F.ri ? ((size_t)H.mcus + F.ri - 1) / F.ri : 1;
+    if (want > entropy + 1) SCAN_DAMAGED("fewer bytes than restart intervals");
+    H.nseg = (int)want;
+    H.off_quant = (uint32_t)scan_align(sizeof(JpegScanHeader));
+    H.off_tables = (uint32_t)scan_align(H.off_quant + (size_t)F.nc * VFSMS_JPEG_COEF_TABLE_BYTES);
+    H.off_seg = (uint32_t)scan_align(H.off_tables + 2 * (size_t)F.nc * sizeof(JpegHuffTable));
+    H.off_stream = (uint32_t)scan_align(H.off_seg + want * sizeof(JpegHuffSeg));
+    const size_t stream_cap = scan_align(entropy + 4 * want + 16);
+    const size_t bound = scan_align(H.off_stream + stream_cap) + 4 * (stream_cap * 8 / (size_t)sub_bits + want + 1);
+    *need = bound;
+    if (!out || cap < bound) { vfsms_set_error("jpeg_scan: output buffer too small"); return VFSMS_ERR_CAPACITY; }
+    memset(out, 0, H.off_stream);
+    for (int k = 0; k < F.nc; k++) {
+        memcpy(out + H.off_quant + (size_t)k * VFSMS_JPEG_COEF_TABLE_BYTES, F.q[F.tq[k]], VFSMS_JPEG_COEF_TABLE_BYTES);
+        JpegHuffTable T;
+        jh_build_table(F.hcounts[0][F.td[k]], F.hvals[0][F.td[k]], &T); memcpy(out + H.off_tables + (size_t)(2 * k) * sizeof(T), &T, sizeof(T));
+        jh_build_table(F.hcounts[1][F.ta[k]], F.hvals[1][F.ta[k]], &T); memcpy(out + H.off_tables + (size_t)(2 * k + 1) * sizeof(T), &T, sizeof(T));
+    }
+    // the entropy-coded data: FF 00 is the data byte FF, FF RSTn ends a segment, FF FF is fill, any other marker ends the scan
+    unsigned char *stream = out + H.off_stream;
+    JpegHuffSeg *segs = (JpegHuffSeg *)(out + H.off_seg);
+    size_t o = 0, seg_start = 0, nseg = 0, nsub = 0, s = F.data;
+    int end_marker = -1;
+    auto close_segment = [&]() -> bool {
+        if (nseg >= want) return false;
+        JpegHuffSeg &S = segs[nseg];
+        S.byte_off = (uint32_t)seg_start; S.byte_count = (uint32_t)(o - seg_start); S.first_mcu = (uint32_t)(nseg * (size_t)F.ri); S.sub0 = (uint32_t)nsub;
+        const size_t bits = (size_t)S.byte_count * 8;
+        nsub += bits ? (bits + sub_bits - 1) / sub_bits : 1;
+        while (o & 3) stream[o++] = 0xFF;
+        seg_start = o; nseg++;
+        return true;
+    };
+    while (s < nbytes) {
+        const unsigned char *f = (const unsigned char *)memchr(jpeg + s, 0xFF, nbytes - s);
+        const size_t run = f ? (size_t)(f - (jpeg + s)) : nbytes - s;
+        if (o + run + 8 > stream_cap) SCAN_DAMAGED("stream beyond its bound");                           // (cannot happen: the bound counts every byte)
+        memcpy(stream + o, jpeg + s, run); o += run; s += run;
+        if (!f || s + 1 >= nbytes) break;
+        const unsigned m = jpeg[s + 1];
+        if (m == 0) { stream[o++] = 0xFF; s += 2; }
+        else if (m == 0xFF) s += 1;
+        else if (m >= 0xD0 && m <= 0xD7) {
+            if (m != 0xD0 + (nseg & 7)) SCAN_DAMAGED("restart markers out of order");
+            if (!close_segment()) SCAN_DAMAGED("more restart intervals than the frame holds");
+            s += 2;
+        } else { end_marker = (int)m; break; }
+    }
+    if (end_marker < 0) SCAN_DAMAGED("no EOI");
+    if (end_marker != 0xD9) SCAN_UNSUPPORTED("several scans, or tables behind SOS");
+    if (!close_segment() || nseg != want) SCAN_DAMAGED("the restart intervals do not add up to the frame's MCUs");
+    H.stream_bytes = (uint32_t)o; H.nsub = (int)nsub;
+    H.off_subseg = (uint32_t)scan_align(H.off_stream + o);
+    H.total_bytes = (uint32_t)(H.off_subseg + 4 * nsub);
+    if (H.total_bytes > bound) SCAN_DAMAGED("record beyond its bound");                                  // (cannot happen)
+    memset(stream + o, 0xFF, H.off_subseg - H.off_stream - o);
+    uint32_t *subseg = (uint32_t *)(out + H.off_subseg);
+    for (size_t k = 0; k < nseg; k++) {
+        const size_t last = k + 1 < nseg ? segs[k + 1].sub0 : nsub;
+        for (size_t j = segs[k].sub0; j < last; j++) subseg[j] = (uint32_t)k;
+    }
+    memcpy(out, &H, sizeof(H));
+    *need = H.total_bytes;
+    return VFSMS_OK;
+}
+
+// host-only entry (no context, no GPU, no libjpeg): the scan record at VFSMS_JPEG_HUFF_SUB_BITS into the caller's memory
+extern "C" int vfsms_jpeg_scan(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t cap, size_t *need)
+{
+    return jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, out, cap, need);
 }
 
 // ---- encode -----------------------------------------------------------------------------------------------------------------------------

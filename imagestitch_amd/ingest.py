@@ -129,7 +129,9 @@ def _fill_from_jpeg(eng, path, gray_handle, color_handle, decoder="host"):
     filled.  False: not a JPEG, an engine without the entry point, a file this decoder does not take (CMYK, RGB-coded, damaged, ...), or
     VFSMS_NATIVE_JPEG=0 -- the tiles are still reserved and `_decode_once` (Pillow) decodes the file.
     decoder "device" (Method.jpegDecoder): vfsms_tile_fill_jpeg_dct is tried first -- the host stops behind the entropy decode, the inverse
-    DCT runs on the device -> "dct" (true) when it filled the tiles; a file it does not take goes on exactly as above."""
+    DCT runs on the device -> "dct" (true) when it filled the tiles; a file it does not take goes on exactly as above.
+    decoder "device-entropy": vfsms_tile_fill_jpeg_huff is tried in front of that -- the host only scans the file for its markers, the
+    entropy decode runs on the device too -> "huff"; a file it does not take goes on exactly as "device" does."""
     fill = getattr(eng, "tile_fill_jpeg", None)
     if fill is None or os.environ.get("VFSMS_NATIVE_JPEG", "1") == "0":
         return False
@@ -137,7 +139,9 @@ def _fill_from_jpeg(eng, path, gray_handle, color_handle, decoder="host"):
         data = f.read()
     if data[:2] != b"\xff\xd8":
         return False
-    if decoder == "device" and eng.tile_fill_jpeg_dct(gray_handle, color_handle, data):
+    if decoder == "device-entropy" and eng.tile_fill_jpeg_huff(gray_handle, color_handle, data):
+        return "huff"
+    if decoder in ("device", "device-entropy") and hasattr(eng, "tile_fill_jpeg_dct") and eng.tile_fill_jpeg_dct(gray_handle, color_handle, data):
         return "dct"
     return bool(fill(gray_handle, color_handle, data))
 
@@ -257,12 +261,12 @@ class TileIngest:
             try:
                 t0 = time.perf_counter()
                 # ("host" makes the call it always made: whatever stands in for _fill_from_jpeg sees no new argument)
-                took = ST._fill_from_jpeg(eng, fileList[k], handles[k], hc, "device") if device_dct else ST._fill_from_jpeg(eng, fileList[k], handles[k], hc)
+                took = ST._fill_from_jpeg(eng, fileList[k], handles[k], hc, device_dct) if device_dct else ST._fill_from_jpeg(eng, fileList[k], handles[k], hc)
                 if took:
                     with istats_mu:
                         istats["tiles"] += 1; istats["native"] = istats.get("native", 0) + 1; istats["decode_s"] += time.perf_counter() - t0
-                        if took == "dct":
-                            istats["dct"] = istats.get("dct", 0) + 1
+                        if took in ("dct", "huff"):
+                            istats[took] = istats.get(took, 0) + 1
                     return
                 owner, shape, parts = ST._decode_once(fileList[k], color)
                 t1 = time.perf_counter()

@@ -274,14 +274,16 @@ class Stitcher(Utility.Method):
         return levels
 
     def _jpegDecoderOnDevice(self):
-        """does the ingest try the device half of the JPEG decoder first (Method.jpegDecoder = "device")?"""
-        if self.jpegDecoder not in ("host", "device"):
-            raise ValueError("jpegDecoder must be 'host' or 'device', got %r" % (self.jpegDecoder,))
-        if self.jpegDecoder != "device":
+        """which device decoder does the ingest try first (Method.jpegDecoder)?  False for "host", else the value itself: "device" (the
+        inverse DCT on the device) or "device-entropy" (the entropy decode too)"""
+        if self.jpegDecoder not in ("host", "device", "device-entropy"):
+            raise ValueError("jpegDecoder must be 'host', 'device' or 'device-entropy', got %r" % (self.jpegDecoder,))
+        if self.jpegDecoder == "host":
             return False
-        if not hasattr(self.engine, "tile_fill_jpeg_dct"):
-            raise NotImplementedError("jpegDecoder = 'device' needs an engine with tile_fill_jpeg_dct")
-        return True
+        entry = "tile_fill_jpeg_dct" if self.jpegDecoder == "device" else "tile_fill_jpeg_huff"
+        if not hasattr(self.engine, entry):
+            raise NotImplementedError("jpegDecoder = %r needs an engine with %s" % (self.jpegDecoder, entry))
+        return self.jpegDecoder
 
     def _decoderThreads(self, n_files):
         """size of the decoder pool: `decodeThreads`, or one per host core up to 32 when the library decodes JPEGs itself (measured on the
@@ -1138,7 +1140,7 @@ class Stitcher(Utility.Method):
 
             def ingest(k):
                 try:
-                    if _fill_from_jpeg(eng, files[k], 0 if color else handles[k], handles[k] if color else 0, *(("device",) if device_dct else ())):
+                    if _fill_from_jpeg(eng, files[k], 0 if color else handles[k], handles[k] if color else 0, *((device_dct,) if device_dct else ())):
                         return
                     owner, shape, parts = _decode_once(files[k], color)
                     if tuple(shape) != tuple(shapes[k]):

@@ -230,6 +230,12 @@ class Method():
     # The tiles hold the same bytes either way.  Taken: 8-bit gray and 4:2:0 Y Cb Cr files, baseline or progressive; any other file goes
     # the "host" way, then Pillow's, decoded once.  Twice the bytes cross the link (2 per sample instead of 1), and the host's share is not
     # gone: the library buffers the whole image's coefficients before they are copied -- README says what tools/bench_jpeg_decode.py measured.
+    # "device-entropy": the entropy decode runs on the device too (csrc/jpeg_huff_kernels.hip; tests/jpeg_huff_ref.py).  The decoder thread
+    # reads the file and scans it once for its markers -- no libjpeg --, the compressed bytes alone cross the link (about 0.5 B per pixel at
+    # quality 90), and Huffman decode, DC prediction and everything "device" does run in device memory.  Taken: 8-bit baseline files with one
+    # scan, gray or 4:2:0, with or without restart markers; any other file (progressive, several scans, damaged, or one whose bits are so
+    # dense that the parallel decoders do not fall in step within VFSMS_JPEG_HUFF_MAX_ROUNDS rounds) goes the "device" way, then "host",
+    # then Pillow's, decoded once.
     jpegDecoder = "host"
 
     # engine injection point (tests substitute fakes; production resolves the per-process GPU engine)

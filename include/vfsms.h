@@ -209,6 +209,38 @@ int vfsms_jpeg_decode(const uint8_t *jpeg, size_t nbytes, int want_planes, uint8
 int vfsms_tile_fill_jpeg_dct(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes);
 int vfsms_jpeg_coefficients(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t cap, int *h, int *w, int *ncomp, int *grid6, size_t *need);
 int vfsms_jpeg_idct(vfsms_ctx *ctx, const int16_t *coef, const uint16_t *quant, int block_rows, int block_cols, uint8_t *out, int pitch);
+/* Method.jpegDecoder = "device-entropy" (csrc/jpeg_huff_kernels.hip, csrc/jpeg_huff_core.h; specified by tests/jpeg_huff_ref.py): the ENTROPY
+ * decode runs on the device too.  The host reads the file once for its markers and nothing but the compressed bytes cross the link; Huffman
+ * decode, DC prediction, then everything vfsms_tile_fill_jpeg_dct does on the device.  No libjpeg is involved.
+ * Taken: 8-bit Huffman baseline / extended sequential files (SOF0, SOF1) with ONE scan holding every component, of one component or of three
+ * (Y Cb Cr) sampled 2x2, 1x1, 1x1 with width >= 5 and height >= 2, every table defined in front of the scan.  VFSMS_ERR_UNSUPPORTED: anything
+ * else -- progressive, arithmetic, 12-bit, several scans, other samplings, CMYK, a table or a scan behind SOS -- and a file whose parallel
+ * decoders are not in step after the repair rounds allowed.  VFSMS_ERR_BAD_ARG: a damaged file -- broken markers, restart intervals that do
+ * not add up to the frame, no EOI, and in the true sequential decode an undefined code, a coefficient beyond index 63 or bits exhausted in
+ * front of the blocks.
+ * vfsms_jpeg_scan (host only: no context, no GPU, no libjpeg): the scan record, in one pass over the file.  It opens with 22 int32 / uint32
+ * (JpegScanHeader, csrc/jpeg_huff_core.h): h, w, ncomp, grid6[6] (as vfsms_jpeg_coefficients), restart interval, segments, subsequences, MCUs,
+ * blocks per MCU, subsequence bits, stream bytes, then the byte offsets in the record of: the quantisation tables (uint16[64] natural order per
+ * component), the Huffman tables (per component DC then AC, JpegHuffTable: a 9-bit look-up, maxcode / value offsets per length, the
+ * symbols, the DHT counts[16]), the unstuffed stream, the segment table (uint32 x 4: byte offset in the stream -- a multiple of 4, the segment
+ * padded with FF to one --, byte count, first MCU, first subsequence), the segment of every subsequence (uint32), and the record's size.
+ * *need: with VFSMS_OK the bytes written; with VFSMS_ERR_CAPACITY (out == NULL asks) a bound on them.
+ * The stream of a segment is cut into subsequences of VFSMS_JPEG_HUFF_SUB_BITS bits, one thread each; a thread that did not start at a code
+ * boundary falls in step with the true decode after a while, and repair rounds carry the true states forward until nothing changes (at most
+ * subsequences - 1 rounds; VFSMS_JPEG_HUFF_MAX_ROUNDS in the fill path: dense noise at quality 100 is practically sequential and goes back).
+ * vfsms_jpeg_entropy_decode: the bare operator.  File bytes in, the layout of vfsms_jpeg_coefficients out to a host array, byte for byte
+ * (*need, *h, *w, *ncomp, grid6 as there; out == NULL asks).  max_rounds: repair rounds allowed, -1 = the subsequence count.  *rounds_used:
+ * the rounds that changed something.  Profile stage "jpeg_entropy" (and jpeg_entropy_sync / _rounds / _scan / _write inside it).
+ * vfsms_tile_fill_jpeg_huff: vfsms_tile_fill_jpeg_dct's contract, thread rules, pools, stream ordering and return codes; on any refusal BOTH
+ * TILES STAY RESERVED and nothing was written to them.                                                                                   */
+#ifndef VFSMS_JPEG_HUFF_SUB_BITS      /* (a build with another size: tools/bench_jpeg_decode.py --sweep) */
+#define VFSMS_JPEG_HUFF_SUB_BITS 1024
+#endif
+#define VFSMS_JPEG_HUFF_MAX_ROUNDS 48
+int vfsms_jpeg_scan(const uint8_t *jpeg, size_t nbytes, uint8_t *out, size_t cap, size_t *need);
+int vfsms_jpeg_entropy_decode(vfsms_ctx *ctx, const uint8_t *jpeg, size_t nbytes, int max_rounds, uint8_t *out, size_t cap, int *h, int *w, int *ncomp,
+                              int *grid6, size_t *need, int *rounds_used);
+int vfsms_tile_fill_jpeg_huff(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes);
 /* The way out, for the mosaic: replaces cv2.imwrite(path, result) for .jpg results (Stitcher.py:149, 175-179; Main.py:21-51 writes every
  * result as jpg).  vfsms_jpeg_encode: n_rows x cols pixels of 1 or 3 channels (R G B, or B G R -- the canvas order -- with bgr != 0), rows
  * `stride_bytes` apart -> a complete baseline JPEG stream with cv2.imwrite's settings (libjpeg defaults, `quality`: 95).  No context, no GPU,

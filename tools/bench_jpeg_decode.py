@@ -1,5 +1,5 @@
-"""JPEG tiles decoded on the device (Method.jpegDecoder = "device") against the host decoder, decode inclusive, on the headline grid, gray and
-colour, in one process.
+"""JPEG tiles decoded on the device (Method.jpegDecoder = "device", "device-entropy") against the host decoder, decode inclusive, on the
+headline grid, gray and colour, in one process.
 
 The grid of bench.py (10 x 9 tiles of 2048 x 2048, 10 % overlap) is written as JPEG files (quality 90; gray files, and 4:2:0 colour files
 tinted as bench.py --from-files --color tints them) and registered through the Stitcher's own ingest (Stitcher._registerBatched: tiles
@@ -7,19 +7,25 @@ reserved up front, a pool of decoder threads fills them while the registrar work
 decoder-pool size (4 and 16 threads: 16 is what a job on a shared GPU host is granted; the pool is never sized by os.cpu_count()) the legs
   A  host:   vfsms_tile_fill_jpeg      (libjpeg-turbo up to the sample planes on the decoder thread)
   B  device: vfsms_tile_fill_jpeg_dct  (libjpeg-turbo up to the coefficients; dequantisation + inverse DCT in k_jpeg_idct)
-are alternated A B A B after warm-up.  Recorded per leg: warm pairs/s, and the decoder threads' summed host seconds per tile
+  C  device-entropy: vfsms_tile_fill_jpeg_huff  (a marker scan on the decoder thread; Huffman decode, DC prediction, inverse DCT on the device)
+are alternated A B C A B C after warm-up.  Recorded per leg: warm pairs/s, and the decoder threads' summed host seconds per tile
 (Stitcher._ingestStats: wall time inside the fill call, which includes the upload and the wait for the device).
 Then, with the library's event profiler on, the "jpeg_decode" stage on the coefficients of one tile of each mode (Engine.jpeg_idct per
 component) against the bytes the kernel must move -- 2 B in, 1 B out per sample -- as a fraction of the 8 TB/s HBM figure the other
 benchmarks use; and the bytes that cross the link per tile either way.
-Writes profiles/jpeg_decode_bench.json and prints the same JSON line.
+Then the bare entropy operator (Engine.jpeg_entropy_decode) over every file of the grid: the stages "jpeg_entropy_sync / _rounds / _scan /
+_write" (the DC prefix is part of the scan), rounds_used, and the write pass against its compulsory bytes -- 2 B per coefficient slot zeroed
+plus the stream read once.  --sweep 512=LIB,2048=LIB repeats that probe in a child process per library built with another
+VFSMS_JPEG_HUFF_SUB_BITS (VFSMS_LIB).
+Writes profiles/jpeg_entropy_bench.json (profiles/jpeg_decode_bench.json is the two-leg record of the change before) and prints the same line.
 
-    python tools/bench_jpeg_decode.py [--rows 10 --cols 9 --tile 2048 --steps 8 --warmup 1 --threads 4,16]
+    python tools/bench_jpeg_decode.py [--rows 10 --cols 9 --tile 2048 --steps 8 --warmup 1 --threads 4,16 --sweep 512=a.so,2048=b.so]
 """
 import argparse
 import json
 import os
 import shutil
+import subprocess
 import sys
 import tempfile
 import time
@@ -29,6 +35,38 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_GBPS = 8000.0
+LEGS = ("host", "device", "device-entropy")
+TOOK = {"host": None, "device": "dct", "device-entropy": "huff"}
+
+
+def entropy_probe(eng, paths, reps=3):
+    """the bare operator over `paths` with the event profiler on -> the stage split per file (ms), rounds_used, bytes"""
+    import numpy as np
+    from imagestitch_amd import _lib
+    datas = [open(f, "rb").read() for f in paths]
+    rounds, slots, stream, record, nsub = [], 0, 0, 0, 0
+    for d in datas:                                             # warm: the arena has grown, the kernels are loaded
+        rc, h, w, comps, used = eng.jpeg_entropy_decode(d, -1)
+        assert rc == 0, rc
+        rounds.append(used)
+        rec = _lib.jpeg_scan(d)
+        slots += sum(int(c.size) for c, _ in comps); stream += rec["stream_bytes"]; record += rec["total_bytes"]; nsub += rec["nsub"]
+    sub_bits = rec["sub_bits"]
+    eng.profile_enable(True)
+    eng.profile_read(reset=True)
+    for _ in range(reps):
+        for d in datas:
+            eng.jpeg_entropy_decode(d, -1)
+    prof = eng.profile_read(reset=True)
+    eng.profile_enable(False)
+    n = len(datas) * reps
+    stages = {k: round(prof.get(k, (0.0, 0))[0] / n, 4) for k in ("jpeg_entropy", "jpeg_entropy_sync", "jpeg_entropy_rounds", "jpeg_entropy_scan", "jpeg_entropy_write")}
+    compulsory = (2 * slots + stream) / len(datas)
+    wr = stages["jpeg_entropy_write"]
+    return {"sub_bits": sub_bits, "files": len(datas), "ms_per_file": stages, "rounds_used": {"min": int(min(rounds)), "median": float(np.median(rounds)), "max": int(max(rounds))},
+            "subsequences_per_file": round(nsub / len(datas), 1), "record_bytes_per_file": round(record / len(datas)),
+            "write_pass": {"compulsory_MB": round(compulsory / 1e6, 3), "GBps_of_compulsory": round(compulsory / wr / 1e6, 1) if wr > 0 else None,
+                           "fraction_of_hbm": round(compulsory / wr / 1e6 / HBM_GBPS, 4) if wr > 0 else None}}
 
 
 def main():
@@ -42,8 +80,18 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="timed repetitions per leg (at least 2)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--dir", default=None, help="where the tiles are written (default: a temporary directory)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_entropy_bench.json"))
+    ap.add_argument("--sweep", default="", help="BITS=LIBRARY,...: the entropy probe again per library built with another VFSMS_JPEG_HUFF_SUB_BITS")
+    ap.add_argument("--probe", default=None, help="(internal) a file listing JPEG paths: run the entropy probe over them, print its JSON, stop")
     args = ap.parse_args()
+    if args.probe:
+        import imagestitch_amd as isa
+        eng = isa.Engine(0)
+        try:
+            print(json.dumps(entropy_probe(eng, [ln.strip() for ln in open(args.probe) if ln.strip()])))
+        finally:
+            eng.close()
+        return
     args.steps = max(args.steps, 2)
     pools = [int(v) for v in args.threads.split(",") if v]
 
@@ -72,7 +120,8 @@ def main():
     eng = isa.Engine(0)
     P, n = grid.n_pairs, grid.n_tiles
     res = {"metric": "decode-inclusive registration of the headline grid from JPEG files: host decoder (A, vfsms_tile_fill_jpeg) against the device "
-                     "half of the decoder (B, vfsms_tile_fill_jpeg_dct), legs alternated A B A B in one process",
+                     "half of the decoder (B, vfsms_tile_fill_jpeg_dct) and the whole decoder on the device (C, vfsms_tile_fill_jpeg_huff), legs "
+                     "alternated A B C A B C in one process",
            "grid": [args.rows, args.cols, args.tile], "pairs": P, "tiles": n, "quality": args.quality, "usable_cpus": cpus,
            "os_cpu_count": os.cpu_count(), "decoder_threads": pools, "steps": args.steps, "warmup": args.warmup, "hbm_GBps": HBM_GBPS}
     names = ("direction", "directIncre", "roiRatio", "featureMethod", "offsetEvaluate", "isColorMode", "fuseMethod")
@@ -99,16 +148,16 @@ def main():
                         eng.tile_free(h)
                     ist = dict(s._ingestStats)
                     assert status and end == P, (decoder, status, end)
-                    assert ist.get("dct", 0) == (n if decoder == "device" else 0) and ist.get("native", 0) == n, (decoder, ist)
+                    assert ist.get("native", 0) == n and all(ist.get(v, 0) == (n if v == TOOK[decoder] else 0) for v in ("dct", "huff")), (decoder, ist)
                     worst = max(max(abs(o[0] - t_[0]), abs(o[1] - t_[1])) for o, t_ in zip(offs, truth))
                     return dt, ist["decode_s"] / n, worst, [[int(v) for v in o] for o in offs]
-                runs = {"host": [], "device": []}
+                runs = {d: [] for d in LEGS}
                 for k in range(args.warmup + args.steps):
-                    for decoder in ("host", "device"):
+                    for decoder in LEGS:
                         r = leg(decoder)
                         if k >= args.warmup:
                             runs[decoder].append(r)
-                assert runs["host"][0][3] == runs["device"][0][3]                      # the same offsets either way
+                assert runs["host"][0][3] == runs["device"][0][3] == runs["device-entropy"][0][3]       # the same offsets every way
                 entry = {}
                 for decoder, rr in runs.items():
                     dts = np.array([r[0] for r in rr])
@@ -116,9 +165,10 @@ def main():
                                       "pairs_per_s_worst": round(P / float(dts.max()), 1), "ms_per_step": [round(float(v) * 1e3, 1) for v in dts],
                                       "host_ms_per_tile_summed_over_threads": round(float(np.median([r[1] for r in rr])) * 1e3, 3),
                                       "max_abs_offset_error_px": int(max(r[2] for r in rr))}
-                entry["device_over_host_pairs_per_s"] = round(entry["device"]["pairs_per_s_median"] / entry["host"]["pairs_per_s_median"], 3)
-                entry["device_over_host_host_ms_per_tile"] = round(entry["device"]["host_ms_per_tile_summed_over_threads"] /
-                                                                   entry["host"]["host_ms_per_tile_summed_over_threads"], 3)
+                for d, key in (("device", "device"), ("device-entropy", "entropy")):
+                    entry[key + "_over_host_pairs_per_s"] = round(entry[d]["pairs_per_s_median"] / entry["host"]["pairs_per_s_median"], 3)
+                    entry[key + "_over_host_host_ms_per_tile"] = round(entry[d]["host_ms_per_tile_summed_over_threads"] /
+                                                                       entry["host"]["host_ms_per_tile_summed_over_threads"], 3)
                 res[mode]["threads_%d" % nthreads] = entry
             # the kernel alone, on one tile's coefficients: every component the request needs (gray: luma; colour: all three)
             with open(files[mode][n // 2], "rb") as fh:
@@ -145,7 +195,21 @@ def main():
                 "fraction_of_hbm": round(3 * samples / stage_ms / 1e6 / HBM_GBPS, 3) if stage_ms > 0 else None,
                 "bound": "memory: 2 B in + 1 B out per sample against about 110 integer operations; the figure is event time around launches "
                          "of 12 and 3 MB, so launch latency weighs on it"}
-            res[mode]["link_bytes_per_pixel"] = {"host": 1.5 if color else 1.0, "device": round((2 * samples + 128 * len(comps)) / px, 3)}
+            res[mode]["jpeg_entropy"] = entropy_probe(eng, files[mode])
+            res[mode]["link_bytes_per_pixel"] = {"host": 1.5 if color else 1.0, "device": round((2 * samples + 128 * len(comps)) / px, 3),
+                                                 "device-entropy": round(res[mode]["jpeg_entropy"]["record_bytes_per_file"] / px, 3)}
+            if args.sweep:
+                listing = os.path.join(outdir, mode + "_files.txt")
+                with open(listing, "w") as fh:
+                    fh.write("\n".join(files[mode]) + "\n")
+                res[mode]["jpeg_entropy_sweep"] = {}
+                for item in args.sweep.split(","):
+                    bits, lib = item.split("=", 1)
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--probe", listing], env=dict(os.environ, VFSMS_LIB=lib),
+                                         capture_output=True, text=True, timeout=600)
+                    assert out.returncode == 0, out.stderr
+                    res[mode]["jpeg_entropy_sweep"][bits] = json.loads(out.stdout.strip().splitlines()[-1])
+                    assert res[mode]["jpeg_entropy_sweep"][bits]["sub_bits"] == int(bits)
     finally:
         for k, v in old.items():
             setattr(isa.Stitcher, k, v)
