@@ -186,6 +186,11 @@ _SIGNATURES = {
     "vfsms_canvas_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "vfsms_canvas_download_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_canvas_download_rows_pyramid": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "vfsms_tiff_jpeg_tables": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vfsms_jpeg_encode_tiles_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                 C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
+    "vfsms_canvas_encode_pyramid_tiles": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                    C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_tile_upload_ch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -1235,8 +1240,97 @@ class Engine:
                     raise VfsmsError("canvas_encode_jpeg_bands: the band did not fit the size the library asked for")
             yield r0, n, ring[slot][:need]
 
+    def jpeg_encode_tiles_device(self, img, tile, bgr=True, quality=95, restart_mcus=0):
+        """vfsms_jpeg_encode_tiles_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload u8,
+        offsets uint64 [n_tiles + 1]): the abbreviated JPEG streams of the image's tile x tile tiles, row-major and back to back -- level 0 of
+        tests/tiff_jpeg_ref.py's file_tiles.  Tile t is payload[offsets[t]:offsets[t + 1]]."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != img.shape[2]) or img.strides[0] < 0:
+            raise ValueError("jpeg_encode_tiles_device: a u8 (h, w) or (h, w, ch) array whose rows are contiguous")
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        T = max(int(tile), 1)
+        offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
+        cap = max(1 << 16, h * w * ch // 4)
+        n = C.c_size_t()
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            rc = self.lib.vfsms_jpeg_encode_tiles_device(self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile),
+                                                         int(quality), int(restart_mcus), _ptr(out), cap, C.byref(n), _ptr(offsets), offsets.size)
+            if rc != VFSMS_ERR_CAPACITY:
+                self._check(rc)
+                return out[:n.value], offsets
+            cap = n.value
+        raise VfsmsError("jpeg_encode_tiles_device: the tiles did not fit the size the library asked for")
+
+    @staticmethod
+    def pyramid_tiles_index(rows, cols, levels, tile, row0, nrows):
+        """the (level, tile number in the level) pairs whose streams the band [row0, row0 + nrows) of a rows x cols mosaic completes, in the
+        order vfsms_canvas_encode_pyramid_tiles returns them (level after level, a level's tiles row-major): level k's tile rows from the
+        one row0 >> k lies in up to the last one that ceil((row0 + nrows) / 2^k) rows fill -- every remaining one when the band ends at the
+        last row (tests/pyramid_ref.py: band_of_level)"""
+        out, last = [], row0 + nrows >= rows
+        r, c = int(rows), int(cols)
+        for k in range(int(levels) + 1):
+            ntx = -(-c // tile)
+            first = (row0 >> k) // tile
+            end = -(-r // tile) if last else ((row0 + nrows + (1 << k) - 1) >> k) // tile
+            out += [(k, t) for t in range(first * ntx, end * ntx)]
+            r, c = (r + 1) >> 1, (c + 1) >> 1
+        return out
+
+    def canvas_encode_pyramid_tiles_rows(self, handle, row0, nrows, levels, tile, quality, restart_mcus, out, index):
+        """one vfsms_canvas_encode_pyramid_tiles call into the u8 vector `out` and the int64 (n, 4) array `index` -> (return code, bytes
+        needed, records needed); VFSMS_ERR_CAPACITY is returned, not raised (nothing was written or consumed: call again with room)"""
+        n, ni = C.c_size_t(), C.c_int()
+        rc = self.lib.vfsms_canvas_encode_pyramid_tiles(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(levels), int(tile), int(quality),
+                                                        int(restart_mcus), _ptr(out), C.c_size_t(out.size), C.byref(n), _ptr(index), len(index), C.byref(ni))
+        if rc != VFSMS_ERR_CAPACITY:
+            self._check(rc)
+        return rc, n.value, ni.value
+
+    def canvas_encode_pyramid_tiles(self, handle, rows, cols, ch, levels, tile, quality, restart_mcus, band_rows):
+        """Generator of (row0, nrows, bytes-view, index) over the whole mosaic: of every band of `band_rows` rows the finished JPEG tile
+        streams of level 0 and of reduced levels 1 .. levels that the band completes (vfsms_canvas_encode_pyramid_tiles: levels formed,
+        carried and encoded on the device), and int64 records (level, tile number, offset in the view, bytes) in the view's order -- what
+        PyramidTiffBandWriter(compression="jpeg").tiles takes.  band_rows must be a multiple of the tile and of 2^levels.  The views belong
+        to a ring of BAND_RING pinned buffers, regrown when a band needs more; a view is valid until BAND_RING - 1 further bands were asked for."""
+        rows, cols, ch, levels, tile, band_rows = int(rows), int(cols), int(ch), int(levels), int(tile), int(band_rows)
+        if tile <= 0 or band_rows <= 0 or band_rows % tile or band_rows % (1 << levels):
+            raise ValueError("canvas_encode_pyramid_tiles: band_rows = %d is not a positive multiple of the tile = %d and of 2^levels = %d" % (band_rows, tile, 1 << levels))
+        ring = self.__dict__.get("_jpeg_ring")
+        if ring is None:
+            ring = self.__dict__["_jpeg_ring"] = [self.pinned_empty((1 << 16,)) for _ in range(self.BAND_RING)]
+        for k, r0 in enumerate(range(0, rows, band_rows)):
+            n = min(band_rows, rows - r0)
+            slot = k % self.BAND_RING
+            index = np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)
+            rc, need, ni = self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, ring[slot], index)
+            if rc == VFSMS_ERR_CAPACITY:
+                size = need + need // 4 + (1 << 16)                                      # the band's answer with room for denser bands
+                for j in range(self.BAND_RING):                                           # (outgrown buffers stay valid: they are freed with the engine)
+                    if ring[j].size < size:
+                        ring[j] = self.pinned_empty((size,))
+                index = np.empty((ni, 4), np.int64)
+                rc, need, ni = self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, ring[slot], index)
+                if rc != VFSMS_OK:
+                    raise VfsmsError("canvas_encode_pyramid_tiles: the band did not fit the size the library asked for")
+            yield r0, n, ring[slot][:need], index[:ni]
+
 
 _default_engine = None
+
+
+def tiff_jpeg_tables(ch, quality=95):
+    """vfsms_tiff_jpeg_tables: the JPEGTables datastream of a TIFF with device-encoded JPEG tiles (SOI, DQT .., DHT .., EOI:
+    tests/tiff_jpeg_ref.py's tables), as bytes.  No GPU involved."""
+    lib = load_library()
+    out = np.empty(1024, np.uint8)
+    n = C.c_size_t()
+    rc = lib.vfsms_tiff_jpeg_tables(int(ch), int(quality), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if rc != VFSMS_OK:
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+    return out[:n.value].tobytes()
 
 
 def jpeg_header(rows, cols, ch, quality=95, restart_mcus=0):

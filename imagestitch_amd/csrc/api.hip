@@ -2157,7 +2157,7 @@ static int canvas_build(vfsms_ctx *ctx, CanvasRec &cv, int rows, int cols, int c
 {
     if (ctx->spare_canvas.rows == rows && ctx->spare_canvas.cols == cols && ctx->spare_canvas.ch == ch) {
         cv = std::move(ctx->spare_canvas); ctx->spare_canvas = CanvasRec();
-        cv.placed.clear(); cv.mb_levels = 4; cv.seam_blend = 0;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
+        cv.placed.clear(); cv.mb_levels = 4; cv.seam_blend = 0; cv.pend.levels = -1;     // same size as the canvas freed last: its buffers, re-initialised below in stream order
     } else {
         TRY(canvas_release(ctx, ctx->spare_canvas));             // a spare of another size goes first: the two never stand side by side
         cv.rows = rows; cv.cols = cols; cv.ch = ch;
@@ -2509,6 +2509,153 @@ extern "C" int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int 
     *nbytes = hn + bn + 2;
     if (rc != VFSMS_OK) return rc;
     out[hn + bn] = 0xFF; out[hn + bn + 1] = 0xD9;
+    return VFSMS_OK;
+}
+
+// ---- JPEG tiles for pyramidal TIFF (Method.pyramidCompression = "jpeg"; jpeg_enc_kernels.hip in tile order, specified by tests/tiff_jpeg_ref.py) --
+// A whole image on the host -> the abbreviated streams of its tile x tile tiles (SOI, SOF0, DRI, SOS, scan, EOI; the tables are
+// vfsms_tiff_jpeg_tables'), row-major and back to back in `out`; offsets[0 .. n_tiles]: where every stream starts, the last being the total.
+// Samples beyond the last row or column repeat it.  *nbytes = the size needed, also on VFSMS_ERR_CAPACITY (nothing is written then)
+extern "C" int vfsms_jpeg_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int tile, int quality,
+                                              int restart_mcus, uint8_t *out, size_t cap, size_t *nbytes, uint64_t *offsets, int offsets_cap)
+{
+    CTX_ENTER(ctx);
+    const char *who = "jpeg_encode_tiles_device";
+    if (!img || !nbytes || !offsets || h < 1 || w < 1) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    int interval = 0;
+    TRY(jpeg_check_tile_geometry(who, tile, ch, quality, restart_mcus, &interval));
+    if ((long long)stride < (long long)w * ch) { vfsms_set_error("%s: stride %d is less than a row's %lld bytes", who, stride, (long long)w * ch); return VFSMS_ERR_BAD_ARG; }
+    const long long tr = (h + tile - 1) / tile, n_tiles = tr * ((w + tile - 1) / tile);
+    if (tr * (tile / 8) > 65535) { vfsms_set_error("%s: %d rows are more tile rows than one call takes", who, h); return VFSMS_ERR_BAD_ARG; }
+    if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
+    JpegScratch *s = &ctx->jpeg_scratch;
+    const size_t pitch = (size_t)w * ch;
+    TRY(s->img.reserve(pitch * h, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(s->img.as<void>(), pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    const JpegTileJob job = {s->img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
+    JpegTilesRun run;
+    TRY(jpeg_tiles_count_device(ctx, s, &job, 1, ch, bgr != 0, tile, quality, restart_mcus, interval, nullptr, nullptr, &run));
+    const unsigned long long total = run.tile_offs[(size_t)run.n_tiles];
+    *nbytes = (size_t)total;
+    if (!out || cap < total) { vfsms_set_error("%s: the tiles take %llu bytes, the buffer holds %zu", who, total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
+    TRY(jpeg_tiles_write_device(ctx, s, &run, out));
+    for (int t = 0; t <= run.n_tiles; t++) offsets[t] = run.tile_offs[(size_t)t];
+    return VFSMS_OK;
+}
+
+// Every tile row of level 0 and of levels 1 .. levels that the band [row0, row0 + nrows) of the canvas COMPLETES, as finished tile streams
+// back to back in `out`, with int64 records {level, tile number in the level (row-major), offset in `out`, bytes} in `index` in that order:
+// level after level, a level's tiles row-major.  The band contract: vfsms_canvas_download_rows_pyramid's (levels may be 0 here), row0 a
+// multiple of the tile, nrows a multiple of the tile unless the band ends at the last row, bands in order from row 0 with one tile and level
+// count.  The rows of a reduced level that do not fill a tile row yet wait in the canvas record on the device (PyrPending) for the
+// bands that complete it; the last band flushes them.  Nothing of the reduced levels crosses the link as pixels.  One counting pass, one
+// scan, one writing pass and one copy over all levels together; the sizes come back in one synchronisation, the payload in the one that
+// ends the call.  *nbytes, *n_index = the sizes needed, also on VFSMS_ERR_CAPACITY (nothing is written and no row is consumed then: the
+// call may be repeated).  The sticky geometry flag as vfsms_canvas_download_rows
+extern "C" int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile, int quality, int restart_mcus,
+                                                 uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index)
+{
+    CTX_ENTER(ctx);
+    const char *who = "canvas_encode_pyramid_tiles";
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    if (!nbytes || !n_index || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    if (levels < 0 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 0..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    int interval = 0;
+    TRY(jpeg_check_tile_geometry(who, tile, cv->ch, quality, restart_mcus, &interval));
+    const bool last = row0 + nrows == cv->rows;
+    const int step = 1 << levels;
+    if (row0 % step) { vfsms_set_error("%s: row0 = %d is not a multiple of 2^levels = %d", who, row0, step); return VFSMS_ERR_BAD_ARG; }
+    if (nrows % step && !last) {
+        vfsms_set_error("%s: nrows = %d is not a multiple of 2^levels = %d and the band does not end at the last row", who, nrows, step);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    if (row0 % tile) { vfsms_set_error("%s: row0 = %d is not a multiple of the tile = %d", who, row0, tile); return VFSMS_ERR_BAD_ARG; }
+    if (nrows % tile && !last) {
+        vfsms_set_error("%s: nrows = %d is not a multiple of the tile = %d and the band does not end at the last row", who, nrows, tile);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    PyrPending &P = cv->pend;
+    const int ch = cv->ch;
+    int Rk[VFSMS_PYRAMID_MAX_LEVELS + 1], Ck[VFSMS_PYRAMID_MAX_LEVELS + 1];
+    Rk[0] = cv->rows; Ck[0] = cv->cols;
+    for (int k = 1; k <= levels; k++) { Rk[k] = (Rk[k - 1] + 1) >> 1; Ck[k] = (Ck[k - 1] + 1) >> 1; }
+    if (row0 == 0) {                                              // a new walk over the canvas: nothing is pending, the buffer is sized for this band
+        size_t off = 0;
+        for (int k = 1; k <= levels; k++) {
+            P.off[k] = off; P.base[k] = 0; P.have[k] = 0;
+            off += ((size_t)(tile - 1 + ((nrows + (1 << k) - 1) >> k)) * Ck[k] * ch + 255) & ~(size_t)255;
+        }
+        TRY(P.buf.reserve(off, ctx->stream));
+        P.tile = tile; P.levels = levels; P.band = nrows; P.next = 0;
+    } else if (P.tile != tile || P.levels != levels || P.next != row0) {
+        vfsms_set_error("%s: bands arrive in order from row 0 with one tile and level count (expected row0 = %d, got %d)", who, P.levels < 0 ? 0 : P.next, row0);
+        return VFSMS_ERR_BAD_ARG;
+    } else if (nrows > P.band) {                                  // a longer band than the buffer was sized for: a larger one takes the pending rows over
+        DevBuf grown; size_t noff[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, off = 0;
+        for (int k = 1; k <= levels; k++) { noff[k] = off; off += ((size_t)(tile - 1 + ((nrows + (1 << k) - 1) >> k)) * Ck[k] * ch + 255) & ~(size_t)255; }
+        TRY(grown.reserve(off, ctx->stream));
+        for (int k = 1; k <= levels; k++)
+            if (P.have[k]) HIP_TRY(hipMemcpyAsync(grown.as<uint8_t>() + noff[k], P.buf.as<uint8_t>() + P.off[k], (size_t)P.have[k] * Ck[k] * ch, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                // (the old buffer is freed by the move)
+        P.buf = std::move(grown);
+        for (int k = 1; k <= levels; k++) P.off[k] = noff[k];
+        P.band = nrows;
+    }
+    // what the band completes: level 0's tile rows, and of level k the whole tile rows of its pending rows plus the band's share
+    JpegTileJob jobs[VFSMS_PYRAMID_MAX_LEVELS + 1]; int job_level[VFSMS_PYRAMID_MAX_LEVELS + 1], full[VFSMS_PYRAMID_MAX_LEVELS + 1], total[VFSMS_PYRAMID_MAX_LEVELS + 1];
+    int n_jobs = 0; long long n_tiles = 0, mrows = 0;
+    uint8_t *lvl[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
+    for (int k = 0; k <= levels; k++) {
+        JpegTileJob J;
+        const size_t pitch = (size_t)Ck[k] * ch;
+        if (k == 0) { J = {cv->pix.as<uint8_t>(), (size_t)cv->rows * pitch, pitch, 0, Rk[0], Ck[0], row0, (nrows + tile - 1) / tile}; full[0] = total[0] = nrows; }
+        else {
+            lvl[k] = P.buf.as<uint8_t>() + P.off[k] + (size_t)P.have[k] * pitch;
+            total[k] = P.have[k] + (int)((((long long)row0 + nrows + (1 << k) - 1) >> k) - (row0 >> k));
+            full[k] = last ? total[k] : total[k] / tile * tile;
+            J = {P.buf.as<uint8_t>() + P.off[k], (size_t)total[k] * pitch, pitch, P.base[k], Rk[k], Ck[k], P.base[k], (full[k] + tile - 1) / tile};
+        }
+        if (J.tile_rows == 0) continue;
+        jobs[n_jobs] = J; job_level[n_jobs++] = k;
+        n_tiles += (long long)J.tile_rows * ((Ck[k] + tile - 1) / tile);
+        mrows = std::max(mrows, (long long)J.tile_rows * (tile / 8));
+    }
+    if (mrows > 65535 || n_tiles > 0x7fffffff) { vfsms_set_error("%s: a band of %d rows is more tile rows than one call takes", who, nrows); return VFSMS_ERR_BAD_ARG; }
+    *n_index = (int)n_tiles;
+    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, lvl, "pyramid_jpeg.levels"));
+    JpegTilesRun run;
+    int err = 0;                                                   // the sticky geometry flag, as vfsms_canvas_download_rows reads it
+    TRY(jpeg_tiles_count_device(ctx, &cv->jpeg, jobs, n_jobs, ch, 1, tile, quality, restart_mcus, interval, cv->d_err.as<int>(), &err, &run));
+    if (err) {
+        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
+        return VFSMS_ERR_BAD_ARG;
+    }
+    const unsigned long long bytes = run.tile_offs[(size_t)run.n_tiles];
+    *nbytes = (size_t)bytes;
+    if (!out || cap < bytes || !index || index_cap < n_tiles) {
+        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
+        return VFSMS_ERR_CAPACITY;
+    }
+    // the coefficients hold everything the streams need: the rows behind the encoded tile rows move to the front for the next band
+    for (int k = 1; k <= levels; k++) {
+        const size_t pitch = (size_t)Ck[k] * ch;
+        const int rem = total[k] - full[k];
+        if (rem > 0 && full[k] > 0)
+            HIP_TRY(hipMemcpyAsync(P.buf.as<uint8_t>() + P.off[k], P.buf.as<uint8_t>() + P.off[k] + (size_t)full[k] * pitch, (size_t)rem * pitch, hipMemcpyDeviceToDevice, ctx->stream));
+        P.base[k] += full[k]; P.have[k] = rem;
+    }
+    P.next = row0 + nrows;
+    TRY(jpeg_tiles_write_device(ctx, &cv->jpeg, &run, out));
+    size_t g = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const int k = job_level[j], ntx = (Ck[k] + tile - 1) / tile;
+        const long long first = (long long)(jobs[j].row0 / tile) * ntx;
+        for (long long t = 0; t < (long long)jobs[j].tile_rows * ntx; t++, g++) {
+            index[4 * g] = k; index[4 * g + 1] = first + t;
+            index[4 * g + 2] = (int64_t)run.tile_offs[g]; index[4 * g + 3] = (int64_t)(run.tile_offs[g + 1] - run.tile_offs[g]);
+        }
+    }
     return VFSMS_OK;
 }
 

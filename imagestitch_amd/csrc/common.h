@@ -166,9 +166,17 @@ struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed ti
 // device scratch of the JPEG encoder (jpeg_enc_kernels.hip), grown to the largest band seen: quantised coefficients, interval sizes + offsets,
 // the coded stream, and (vfsms_jpeg_encode_device only) the staged image
 struct JpegScratch { DevBuf coef, sizes, out, img; };
+// tile order (Method.pyramidCompression = "jpeg"): the tile rows of one level that a call encodes.  Row y of the rows x cols level lies at
+// src + (y - src_row0) * pitch (src 256-byte aligned, src_bytes readable); `tile_rows` rows of tiles from row0 (a multiple of the tile side) on
+struct JpegTileJob { const uint8_t *src; size_t src_bytes, pitch; int src_row0, rows, cols, row0, tile_rows; };
+// what the counting half of a tile-order encode leaves for the writing half; tile_offs[0 .. n_tiles]: the tiles' offsets in the payload
+struct JpegTilesRun { int n_tiles, n_int, ipt, interval, bpm, plen; uint8_t prefix[44]; uint32_t *d_sizes; unsigned long long *d_offs; int *d_err; std::vector<unsigned long long> tile_offs; };
+// the pending rows of levels 1 .. levels between the bands of vfsms_canvas_encode_pyramid_tiles: level k's rows [base[k], base[k] + have[k])
+// (fewer than a tile row of them) at buf + off[k], with room for the share of a band of `band` rows behind them; next: the row0 expected
+struct PyrPending { DevBuf buf; int tile = 0, levels = -1, band = 0, next = 0; int base[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, have[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; size_t off[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; };
 // move-only: the record owns its buffers wherever it lies (the canvas map, the context's spare slot, a canvas under construction); an
 // empty record owns nothing.  Destroying one frees without a synchronisation: api.hip's canvas_release synchronises first
-struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; };   // jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; PyrPending pend; };   // pend: the rows of the reduced levels that do not fill a tile row yet (vfsms_canvas_encode_pyramid_tiles), sized at the first band, released with the canvas; jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent
@@ -390,6 +398,13 @@ void jpeg_quant_tables(int quality, uint8_t q[2][64]);
 int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality, int restart_mcus, int *interval);
 int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
                             int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes);
+// the same encoder in tile order (tests/tiff_jpeg_ref.py): the refusals every entry shares, *interval = MCUs per restart interval; the
+// prefix of every tile stream (SOI, SOF0, DRI when restart_mcus > 0, SOS: at most 41 bytes) -> its length; the two halves of a call
+int jpeg_check_tile_geometry(const char *who, int tile, int ch, int quality, int restart_mcus, int *interval);
+int jpeg_tile_prefix(int tile, int ch, int restart_mcus, uint8_t *out);
+int jpeg_tiles_count_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTileJob *jobs, int n_jobs, int ch, int bgr, int tile, int quality, int restart_mcus,
+                            int interval, const int *d_flag, int *flag, JpegTilesRun *run);
+int jpeg_tiles_write_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTilesRun *run, uint8_t *out);
 // jpeg_host.cpp / jpeg_dec_kernels.hip: the device half of the JPEG decoder (tests/jpeg_dec_ref.py).  A component of one launch: its blocks
 // (64 int16 each, natural order, block-row-major on a grid `bcols` wide), its table (uint16[64], natural order), the plane it becomes (`rows`
 // x `cols` samples kept of the grid, `pitch` bytes apart) and the index of its first block among the launch's `total`
@@ -407,6 +422,8 @@ int jpeg_huff_decode_device(hipStream_t stream, hipEvent_t sync, const JpegScanH
 // pyramid_kernels.hip: the reduced levels of a band of the canvas (Stitcher.outputPyramid), back to back in d_levels
 size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int levels);
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels);
+// the same with a place of its own for every level: level k's rows of the band at lvl[k] (any alignment), k = 1 .. levels; profile stage `stage`
+int pyramid_band_device_at(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *const *lvl, const char *stage);
 
 // sift_kernels.hip
 #define VFSMS_SIFT_MAX_LAYERS 8

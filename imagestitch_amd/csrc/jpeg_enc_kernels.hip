@@ -13,6 +13,9 @@
 //                      flushes the window with 16-byte stores (the bytes a window shares with its neighbours' 16-byte units go out one by one)
 // The sizes are exact, so the output buffer is allocated after the counting pass and cannot overflow; the writing pass still takes its
 // capacity and raises a flag instead of storing beyond it.
+// Tile order (the TILES instantiations; Method.pyramidCompression = "jpeg", specified by tests/tiff_jpeg_ref.py): the same two kernels over the
+// tiles of a pyramid level, every tile an image of its own -- edges replicated, its prefix (SOI .. SOS) in front and EOI behind -- so that
+// a band leaves as finished tile streams.  Profile stages "pyramid_jpeg.transform", ".entropy", ".copy".
 #include "common.h"
 #include <string.h>
 
@@ -45,6 +48,11 @@ struct JpegXformArgs {
     int bgr;                                // colour: B G R (else R G B)
     int16_t *coef;                          // [band MCU][blocks per MCU][64]
     JpegQuant qt;
+    // tile order (k_jpeg_transform<.., true>): the image is a pyramid level cut into tm x tm MCU tiles, ntx of them in a row; `mw` is the
+    // tile-padded MCU count ntx * tm, row0 a multiple of the tile side, and row y of the level lies at src + (y - src_row0) * pitch
+    int src_row0;
+    int tm, ntx;
+    long long mcu_base;                     // MCUs in front of this launch's first tile in `coef`
 };
 
 // the aligned dword at byte `a` of the image, bytes beyond its end read as 0
@@ -87,7 +95,10 @@ __device__ inline int je_cb(int r, int g, int b) { return (-11059 * r - 21709 * 
 __device__ inline int je_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
 
 // COLOR: 16 MCUs of 16 x 16 (Y00 Y01 Y10 Y11 Cb Cr); else 96 MCUs of one 8 x 8 block.  grid: (strips of an MCU row, MCU rows of the band)
-template <bool COLOR>
+// TILES: every tile is an image of its own (tests/tiff_jpeg_ref.py).  The MCU grid is the tile grid's, so MCU rows and columns may lie wholly
+// beyond the level: source rows and columns are clamped to the level's last (a strip that starts beyond the last column holds that column
+// alone), there are no dummy blocks, and an MCU goes to [tile in the row of tiles][MCU row in tile][MCU column in tile]
+template <bool COLOR, bool TILES>
 __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
 {
     constexpr int CH = COLOR ? 3 : 1, MCU = COLOR ? 16 : 8, MPW = COLOR ? 16 : 96, BPM = COLOR ? 6 : 1, SW = JE_ROWB / CH;
@@ -100,8 +111,9 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
     const int mx0 = blockIdx.x * MPW, my = blockIdx.y;
     const int x0 = mx0 * MCU, y0 = a.row0 + my * MCU;
     const int nvalid = min(MPW, a.mw - mx0);                                  // MCUs of this strip
-    const int nb = (min(x0 + SW, a.cols) - x0) * CH;                          // bytes of a strip row that exist
-    const int nrow = min(MCU, a.rows - y0);                                   // rows that exist
+    const int sx0 = TILES ? min(x0, a.cols - 1) : x0;                         // the strip's first source column
+    const int nb = (min(sx0 + SW, a.cols) - sx0) * CH;                        // bytes of a strip row that exist
+    const int nrow = TILES ? MCU : min(MCU, a.rows - y0);                     // rows that exist (TILES: every row, clamped when it is loaded)
 
     // ---- the rows into LDS: dword d of a row = bytes [4 d, 4 d + 4) of the strip row, from the two aligned dwords that hold them
     {
@@ -109,7 +121,8 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
         for (int e = tid; e < nrow * (JE_ROWB / 4); e += 256) {
             const int r = e / (JE_ROWB / 4), d = e % (JE_ROWB / 4);
             if (d >= nd) continue;
-            const size_t g = (size_t)(y0 + r) * a.pitch + (size_t)x0 * CH + 4 * (size_t)d;
+            const int sr = TILES ? min(y0 + r, a.rows - 1) - a.src_row0 : y0 + r;
+            const size_t g = (size_t)sr * a.pitch + (size_t)sx0 * CH + 4 * (size_t)d;
             const size_t al = g & ~(size_t)3;
             const int sh = (int)(g & 3) * 8;
             uint32_t v = je_dword(a.src, al, a.src_bytes);
@@ -121,7 +134,7 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
 
     // ---- samples: Y (and the 2 x 2 chroma box) of the 16 x 256 strip, columns clamped to the image (the right edge repeats), rows likewise
     if (COLOR) {
-        const int xmax = a.cols - 1 - x0;                                     // last column that exists, strip-relative
+        const int xmax = a.cols - 1 - sx0;                                    // last column that exists, strip-relative
         const int cj_last = ((a.rows + 1) >> 1) - 1;                          // last chroma row the image has (jcprepct.c: rows repeat to an even count first)
         const int ro = a.bgr ? 2 : 0, bo = a.bgr ? 0 : 2;
         for (int q = tid; q < 8 * 128; q += 256) {
@@ -136,7 +149,7 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
             // chroma row j of the image is the box of rows 2 j, 2 j + 1 (the last row repeated when there is no 2 j + 1); below the image's
             // last chroma row that row repeats
             const int j = min((y0 >> 1) + qy, cj_last);
-            const int ca = min(2 * j, a.rows - 1) - y0, cb_ = min(2 * j + 1, a.rows - 1) - y0;
+            const int ca = TILES ? 2 * qy : min(2 * j, a.rows - 1) - y0, cb_ = TILES ? 2 * qy + 1 : min(2 * j + 1, a.rows - 1) - y0;
             const uint8_t *ua = raw + ca * JE_PITCH, *ub = raw + cb_ * JE_PITCH;
             const int bias = 1 + (qx & 1);
             const int sb = je_cb(ua[xa + ro], ua[xa + 1], ua[xa + bo]) + je_cb(ua[xb + ro], ua[xb + 1], ua[xb + bo]) +
@@ -160,7 +173,7 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
             for (int k = 0; k < 4; k++) { d[k] = (int)((v.x >> (8 * k)) & 255) - 128; d[4 + k] = (int)((v.y >> (8 * k)) & 255) - 128; }
         } else {
             const uint8_t *p = raw + min(r, nrow - 1) * JE_PITCH;
-            const int xmax = a.cols - 1 - x0;
+            const int xmax = a.cols - 1 - sx0;
             for (int k = 0; k < 8; k++) d[k] = (int)p[min(blk * 8 + k, xmax)] - 128;
         }
         je_fdct8<true>(d);
@@ -187,7 +200,7 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
     __syncthreads();
 
     // ---- jccoefct.c: the Y blocks of an MCU that lie beyond the image's block grid carry no AC and the DC of the block in front of them
-    if (COLOR) {
+    if (COLOR && !TILES) {
         const int bw = (a.cols + 7) >> 3, bh = (a.rows + 7) >> 3;
         const int by0 = y0 >> 3;
         if (tid < nvalid && ((mx0 + tid) * 2 + 1 >= bw || by0 + 1 >= bh)) {
@@ -202,8 +215,16 @@ __global__ void __launch_bounds__(256) k_jpeg_transform(const JpegXformArgs a)
         __syncthreads();
     }
 
-    // ---- out: the strip's MCUs are consecutive in the coefficient array
-    {
+    // ---- out: the strip's MCUs are consecutive in the coefficient array; in tile order every MCU has its own place
+    if (TILES) {
+        const uint4 *s = (const uint4 *)out;
+        for (int e = tid; e < nvalid * BPM * 8; e += 256) {
+            const int m = e / (BPM * 8), q = e % (BPM * 8);
+            const int mx = mx0 + m;
+            const size_t dm = (size_t)a.mcu_base + (((size_t)(my / a.tm) * a.ntx + mx / a.tm) * a.tm + my % a.tm) * a.tm + mx % a.tm;
+            ((uint4 *)(a.coef + dm * BPM * 64))[q] = s[e];
+        }
+    } else {
         uint4 *dst = (uint4 *)(a.coef + ((size_t)my * a.mw + mx0) * BPM * 64);
         const uint4 *s = (const uint4 *)out;
         for (int e = tid; e < nvalid * BPM * 8; e += 256) dst[e] = s[e];
@@ -222,6 +243,10 @@ struct JpegEntropyArgs {
     const unsigned long long *offs;         // [n_int + 1] their exclusive scan
     uint8_t *out; unsigned long long cap;   // the output stream and its capacity
     int *err;                               // set when the stream would not fit `cap`
+    // tile order (k_jpeg_entropy<.., true>): `ipt` intervals per tile; a tile's first interval is preceded by the tile prefix (SOI, SOF0,
+    // DRI, SOS: the same bytes for every tile of a file), its last is followed by EOI instead of an RSTn, and RSTn counts within the tile
+    int ipt;
+    int plen; uint8_t prefix[44];
 };
 
 // one lane's coder
@@ -247,18 +272,22 @@ struct JeLane {
 };
 
 // WRITE = false: sizes[i] = the bytes of interval i.  WRITE = true: the bytes, at offs[i].  One wave per workgroup, one lane per interval
-template <bool WRITE>
+// TILES: the tile streams of tests/tiff_jpeg_ref.py back to back in interval order, so a tile's stream starts at offs[its first interval]
+template <bool WRITE, bool TILES>
 __global__ void __launch_bounds__(64) k_jpeg_entropy(const JpegEntropyArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t win[WRITE ? JE_WINDOW : 16];
+    __shared__ uint8_t pre[TILES ? 64 : 1];
     const int lane = threadIdx.x;
+    if (TILES) { pre[lane] = lane < a.plen ? a.prefix[lane] : 0; __syncthreads(); }
     const int i0 = blockIdx.x * 64, i = i0 + lane;
     const bool live = i < a.n_int;
     const int m0 = live ? i * a.interval : 0;
     const int nblk = live ? (min(m0 + a.interval, a.n_mcu) - m0) * a.bpm : 0;
     const int16_t *cf = a.coef + (size_t)m0 * a.bpm * 64;
-    const bool marker = live && (i + 1 < a.n_int || a.last_marker);
-    const uint32_t rst = 0xFFD0u | (uint32_t)((a.first_int + i) & 7);
+    const int it = TILES ? i % a.ipt : 0;                                      // the interval within its tile
+    const bool marker = TILES ? live : live && (i + 1 < a.n_int || a.last_marker);
+    const uint32_t rst = TILES ? (it + 1 == a.ipt ? 0xFFD9u : 0xFFD0u | (uint32_t)(it & 7)) : 0xFFD0u | (uint32_t)((a.first_int + i) & 7);
 
     JeLane<WRITE> L;
     L.win = win;
@@ -271,14 +300,21 @@ __global__ void __launch_bounds__(64) k_jpeg_entropy(const JpegEntropyArgs a)
     const unsigned long long A0 = B0 & ~15ull;
     const int rounds = WRITE ? (int)((B1 - A0 + JE_WINDOW - 1) / JE_WINDOW) : 1;
 
-    // the coder's place: block, coefficient, zero run, predictors; stage 0 coding, 1 padded, 2 marker bytes, 3 done
+    // the coder's place: block, coefficient, zero run, predictors; stage -1 the tile prefix, 0 coding, 1 padded, 2 marker bytes, 3 done
     int blk = 0, k = 0, run = 0, pred[3] = {0, 0, 0}, stage = live ? 0 : 3, rawn = 0;
+    if (TILES && live && it == 0) { stage = -1; rawn = a.plen; }
     uint4 v8 = make_uint4(0, 0, 0, 0);
 
     for (int round = 0; round < rounds; round++) {
         L.wbeg = A0 + (unsigned long long)round * JE_WINDOW;
         L.wend = WRITE ? L.wbeg + JE_WINDOW : ~0ull;
         while (stage < 3) {
+            if (TILES && stage < 0) {                                         // the prefix: bytes as they are, like the marker's
+                while (rawn > 0 && !(WRITE && L.pos >= L.wend)) { L.put(pre[a.plen - rawn]); rawn--; }
+                if (rawn > 0) break;
+                stage = 0;
+                continue;
+            }
             if (stage == 2) {                                                 // the marker: two bytes as they are
                 while (rawn > 0 && !(WRITE && L.pos >= L.wend)) { L.put((rst >> (8 * (rawn - 1))) & 255u); rawn--; }
                 if (rawn > 0) break;
@@ -378,14 +414,15 @@ void huff_derive(const uint8_t *bits, const uint8_t *vals, uint32_t *table)
     }
 }
 
-}  // namespace
+// tile_offs[t] = offs[t * ipt], t = 0 .. n_tiles: where every tile's stream starts, and the total
+__global__ void __launch_bounds__(256) k_jpeg_tile_offsets(const unsigned long long *offs, int ipt, int n_tiles, unsigned long long *tile_offs)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t <= n_tiles) tile_offs[t] = offs[(size_t)t * ipt];
+}
 
-// The entropy-coded bytes of rows [row0, row0 + nrows) of the rows x cols x ch image at d_img (256-byte aligned, `pitch` bytes a row) into
-// `out` on the host.  api.hip has checked the band contract: row0 is a multiple of the MCU height, the MCUs in front of the band are whole
-// intervals and so are the band's own unless it ends at the last row.  *nbytes = the size, also on VFSMS_ERR_CAPACITY (nothing is copied
-// then).  Synchronises the stream.
-int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
-                            int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes)
+// the Annex K tables in constant memory, once per process and device
+int huff_tables_up(vfsms_ctx *ctx)
 {
     static bool tables_up = false;                                            // (per process: one device image of the library per device in use)
     static int tables_dev = -1;
@@ -400,6 +437,29 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_huff), &h, sizeof(h)));
         tables_up = true; tables_dev = ctx->device;
     }
+    return VFSMS_OK;
+}
+
+void quant_args(int quality, JpegQuant *qt)
+{
+    uint8_t q[2][64];
+    jpeg_quant_tables(quality, q);
+    for (int t = 0; t < 2; t++) for (int k = 0; k < 64; k++) {
+        qt->q[t][k] = q[t][k];
+        qt->recip[t][k] = (uint32_t)((((unsigned long long)1 << 32) + 8ull * q[t][k] - 1) / (8ull * q[t][k]));
+    }
+}
+
+}  // namespace
+
+// The entropy-coded bytes of rows [row0, row0 + nrows) of the rows x cols x ch image at d_img (256-byte aligned, `pitch` bytes a row) into
+// `out` on the host.  api.hip has checked the band contract: row0 is a multiple of the MCU height, the MCUs in front of the band are whole
+// intervals and so are the band's own unless it ends at the last row.  *nbytes = the size, also on VFSMS_ERR_CAPACITY (nothing is copied
+// then).  Synchronises the stream.
+int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img, int rows, int cols, int ch, size_t pitch, int bgr,
+                            int row0, int nrows, int quality, int interval, uint8_t *out, size_t cap, size_t *nbytes)
+{
+    TRY(huff_tables_up(ctx));
     const int mcu = ch == 3 ? 16 : 8, bpm = ch == 3 ? 6 : 1;
     const int mw = (cols + mcu - 1) / mcu;
     const int mrows = (nrows + mcu - 1) / mcu;
@@ -416,27 +476,24 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     JpegXformArgs x;
     x.src = d_img; x.src_bytes = (size_t)rows * pitch; x.pitch = pitch; x.rows = rows; x.cols = cols; x.row0 = row0; x.mw = mw; x.bgr = bgr;
     x.coef = s->coef.as<int16_t>();
-    uint8_t q[2][64];
-    jpeg_quant_tables(quality, q);
-    for (int t = 0; t < 2; t++) for (int k = 0; k < 64; k++) {
-        x.qt.q[t][k] = q[t][k];
-        x.qt.recip[t][k] = (uint32_t)((((unsigned long long)1 << 32) + 8ull * q[t][k] - 1) / (8ull * q[t][k]));
-    }
+    x.src_row0 = 0; x.tm = 0; x.ntx = 0; x.mcu_base = 0;
+    quant_args(quality, &x.qt);
     {
         ProfScope ps(ctx, "jpeg_encode.transform");
         const int mpw = ch == 3 ? 16 : 96;
         const dim3 grid((unsigned)((mw + mpw - 1) / mpw), (unsigned)mrows);
-        if (ch == 3) hipLaunchKernelGGL(k_jpeg_transform<true>, grid, dim3(256), 0, ctx->stream, x);
-        else hipLaunchKernelGGL(k_jpeg_transform<false>, grid, dim3(256), 0, ctx->stream, x);
+        if (ch == 3) hipLaunchKernelGGL((k_jpeg_transform<true, false>), grid, dim3(256), 0, ctx->stream, x);
+        else hipLaunchKernelGGL((k_jpeg_transform<false, false>), grid, dim3(256), 0, ctx->stream, x);
         HIP_TRY(hipGetLastError());
     }
     JpegEntropyArgs e;
     e.coef = s->coef.as<int16_t>(); e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = n_int; e.first_int = (int)(((long long)(row0 / mcu) * mw) / interval);
     e.last_marker = last ? 0 : 1; e.bpm = bpm; e.sizes = d_sizes; e.offs = d_offs; e.out = nullptr; e.cap = 0; e.err = d_err;
+    e.ipt = 0; e.plen = 0; memset(e.prefix, 0, sizeof(e.prefix));
     unsigned long long total = 0;
     {
         ProfScope ps(ctx, "jpeg_encode.entropy");
-        hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
+        hipLaunchKernelGGL((k_jpeg_entropy<false, false>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
         hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, ctx->stream, d_sizes, n_int, d_offs);
         HIP_TRY(hipGetLastError());
     }
@@ -450,7 +507,7 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     {
         ProfScope ps(ctx, "jpeg_encode.entropy");
         HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
+        hipLaunchKernelGGL((k_jpeg_entropy<true, false>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -460,5 +517,94 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (err) { vfsms_set_error("jpeg_encode: the coded band outgrew the %zu bytes counted for it", s->out.bytes()); return VFSMS_ERR_CAPACITY; }
+    return VFSMS_OK;
+}
+
+// ---- tile order: the JPEG tiles of a pyramidal TIFF (Method.pyramidCompression = "jpeg"; specified by tests/tiff_jpeg_ref.py) ---------------
+// Counting half: the tile rows of `n_jobs` levels (api.hip has checked tile, interval and the jobs) are transformed into s->coef, tile after
+// tile in job order, one launch per job; ONE counting pass and ONE scan over all their intervals follow, and the tiles' offsets
+// (tile_offs[0 .. n_tiles], the last being the total) come to the host with `d_flag` (an int on the device, may be NULL) in *flag.
+// Synchronises the stream.
+int jpeg_tiles_count_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTileJob *jobs, int n_jobs, int ch, int bgr, int tile, int quality, int restart_mcus,
+                            int interval, const int *d_flag, int *flag, JpegTilesRun *run)
+{
+    TRY(huff_tables_up(ctx));
+    const int mcu = ch == 3 ? 16 : 8, bpm = ch == 3 ? 6 : 1, tm = tile / mcu, mpt = tm * tm, ipt = mpt / interval;
+    long long n_tiles = 0;
+    for (int j = 0; j < n_jobs; j++) n_tiles += (long long)jobs[j].tile_rows * ((jobs[j].cols + tile - 1) / tile);
+    const long long n_mcu = n_tiles * mpt, n_int = n_tiles * ipt;
+    if (n_tiles < 1 || n_int > 0x7fffffff - 64 || n_mcu > 0x7fffffff) { vfsms_set_error("jpeg tiles: %lld tiles of %d intervals are more than one call takes", n_tiles, ipt); return VFSMS_ERR_BAD_ARG; }
+    run->n_tiles = (int)n_tiles; run->n_int = (int)n_int; run->ipt = ipt; run->interval = interval; run->bpm = bpm;
+    run->plen = jpeg_tile_prefix(tile, ch, restart_mcus, run->prefix);
+
+    TRY(s->coef.reserve((size_t)n_mcu * bpm * 128, ctx->stream));
+    const size_t o_offs = ((size_t)n_int * 4 + 255) & ~(size_t)255, o_err = o_offs + ((size_t)n_int + 1) * 8;
+    const size_t o_toffs = (o_err + sizeof(int) + 255) & ~(size_t)255;
+    TRY(s->sizes.reserve(o_toffs + ((size_t)n_tiles + 1) * 8, ctx->stream));
+    run->d_sizes = s->sizes.as<uint32_t>();
+    run->d_offs = (unsigned long long *)(s->sizes.as<char>() + o_offs);
+    run->d_err = (int *)(s->sizes.as<char>() + o_err);
+    unsigned long long *d_toffs = (unsigned long long *)(s->sizes.as<char>() + o_toffs);
+
+    {
+        ProfScope ps(ctx, "pyramid_jpeg.transform");
+        JpegXformArgs x;
+        quant_args(quality, &x.qt);
+        x.coef = s->coef.as<int16_t>(); x.bgr = bgr; x.tm = tm;
+        long long base = 0;
+        const int mpw = ch == 3 ? 16 : 96;
+        for (int j = 0; j < n_jobs; j++) {
+            const JpegTileJob &J = jobs[j];
+            x.src = J.src; x.src_bytes = J.src_bytes; x.pitch = J.pitch; x.rows = J.rows; x.cols = J.cols; x.row0 = J.row0; x.src_row0 = J.src_row0;
+            x.ntx = (J.cols + tile - 1) / tile; x.mw = x.ntx * tm; x.mcu_base = base;
+            const dim3 grid((unsigned)((x.mw + mpw - 1) / mpw), (unsigned)(J.tile_rows * tm));
+            if (ch == 3) hipLaunchKernelGGL((k_jpeg_transform<true, true>), grid, dim3(256), 0, ctx->stream, x);
+            else hipLaunchKernelGGL((k_jpeg_transform<false, true>), grid, dim3(256), 0, ctx->stream, x);
+            base += (long long)J.tile_rows * x.ntx * mpt;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    JpegEntropyArgs e;
+    e.coef = s->coef.as<int16_t>(); e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = (int)n_int; e.first_int = 0; e.last_marker = 0; e.bpm = bpm;
+    e.sizes = run->d_sizes; e.offs = run->d_offs; e.out = nullptr; e.cap = 0; e.err = run->d_err;
+    e.ipt = ipt; e.plen = run->plen; memset(e.prefix, 0, sizeof(e.prefix)); memcpy(e.prefix, run->prefix, (size_t)run->plen);
+    {
+        ProfScope ps(ctx, "pyramid_jpeg.entropy");
+        hipLaunchKernelGGL((k_jpeg_entropy<false, true>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
+        hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, ctx->stream, run->d_sizes, (int)n_int, run->d_offs);
+        hipLaunchKernelGGL(k_jpeg_tile_offsets, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0, ctx->stream, run->d_offs, ipt, (int)n_tiles, d_toffs);
+        HIP_TRY(hipGetLastError());
+    }
+    run->tile_offs.resize((size_t)n_tiles + 1);
+    HIP_TRY(hipMemcpyAsync(run->tile_offs.data(), d_toffs, ((size_t)n_tiles + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (d_flag) HIP_TRY(hipMemcpyAsync(flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
+// Writing half: the streams the counting half measured into `out` on the host (cap >= run->tile_offs[n_tiles], checked by the caller): one
+// writing pass, one copy.  Synchronises the stream.
+int jpeg_tiles_write_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTilesRun *run, uint8_t *out)
+{
+    const unsigned long long total = run->tile_offs[(size_t)run->n_tiles];
+    TRY(s->out.reserve(((size_t)total + 15) & ~(size_t)15, ctx->stream));
+    JpegEntropyArgs e;
+    e.coef = s->coef.as<int16_t>(); e.n_mcu = run->n_int * run->interval; e.interval = run->interval; e.n_int = run->n_int; e.first_int = 0; e.last_marker = 0;
+    e.bpm = run->bpm; e.sizes = run->d_sizes; e.offs = run->d_offs; e.out = s->out.as<uint8_t>(); e.cap = s->out.bytes(); e.err = run->d_err;
+    e.ipt = run->ipt; e.plen = run->plen; memset(e.prefix, 0, sizeof(e.prefix)); memcpy(e.prefix, run->prefix, (size_t)run->plen);
+    int err = 0;
+    {
+        ProfScope ps(ctx, "pyramid_jpeg.entropy");
+        HIP_TRY(hipMemsetAsync(run->d_err, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL((k_jpeg_entropy<true, true>), dim3((unsigned)((run->n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, "pyramid_jpeg.copy");
+        HIP_TRY(hipMemcpyAsync(&err, run->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out, s->out.as<uint8_t>(), (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (err) { vfsms_set_error("jpeg tiles: the coded tiles outgrew the %zu bytes counted for them", s->out.bytes()); return VFSMS_ERR_CAPACITY; }
     return VFSMS_OK;
 }

@@ -897,6 +897,82 @@ int jpeg_check_geometry(const char *who, int rows, int cols, int ch, int quality
     return VFSMS_OK;
 }
 
+// the refusals of the tile-order entries (tests/tiff_jpeg_ref.py: geometry): the tile a positive multiple of 16, its MCUs a whole number of
+// restart intervals of at most 65535 MCUs -- restart_mcus = 0 is "the tile is one interval".  *interval: the interval in MCUs
+int jpeg_check_tile_geometry(const char *who, int tile, int ch, int quality, int restart_mcus, int *interval)
+{
+    if (ch != 1 && ch != 3) { vfsms_set_error("%s: 1 or 3 channels, got %d", who, ch); return VFSMS_ERR_BAD_ARG; }
+    if (tile <= 0 || tile % 16 || tile > 65500) { vfsms_set_error("%s: the tile must be a positive multiple of 16 (at most 65500), got %d", who, tile); return VFSMS_ERR_BAD_ARG; }
+    if (quality < 1 || quality > 100) { vfsms_set_error("%s: quality must be 1..100, got %d", who, quality); return VFSMS_ERR_BAD_ARG; }
+    if (restart_mcus < 0 || restart_mcus > 65535) { vfsms_set_error("%s: restart_mcus must be 0..65535, got %d", who, restart_mcus); return VFSMS_ERR_BAD_ARG; }
+    const int tm = tile / (ch == 3 ? 16 : 8);
+    const long long n = (long long)tm * tm, iv = restart_mcus ? restart_mcus : n;
+    if (n % iv) { vfsms_set_error("%s: the %lld MCUs of a tile are not a whole number of restart intervals of %lld MCUs", who, n, iv); return VFSMS_ERR_BAD_ARG; }
+    if (iv > 65535) { vfsms_set_error("%s: a tile of %lld MCUs cannot be one restart interval (at most 65535)", who, n); return VFSMS_ERR_BAD_ARG; }
+    if (interval) *interval = (int)iv;
+    return VFSMS_OK;
+}
+
+// the segments of vfsms_jpeg_header, so that the abbreviated streams of TIFF (tables here, frame and scan headers there) repeat its bytes
+namespace {
+struct SegWriter {
+    uint8_t *b; size_t n = 0;
+    void seg(int marker, size_t payload) { b[n++] = 0xFF; b[n++] = (uint8_t)marker; b[n++] = (uint8_t)((payload + 2) >> 8); b[n++] = (uint8_t)(payload + 2); }
+    void soi() { b[n++] = 0xFF; b[n++] = 0xD8; }
+    void dqt(int quality, int ch)
+    {
+        uint8_t q[2][64];
+        jpeg_quant_tables(quality, q);
+        for (int t = 0; t < (ch == 3 ? 2 : 1); t++) { seg(0xDB, 65); b[n++] = (uint8_t)t; for (int k = 0; k < 64; k++) b[n++] = q[t][kZigzag[k]]; }
+    }
+    void sof0(int rows, int cols, int ch)
+    {
+        seg(0xC0, 6 + 3 * (size_t)ch);
+        b[n++] = 8; b[n++] = (uint8_t)(rows >> 8); b[n++] = (uint8_t)rows; b[n++] = (uint8_t)(cols >> 8); b[n++] = (uint8_t)cols; b[n++] = (uint8_t)ch;
+        for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = (ch == 3 && c == 0) ? 0x22 : 0x11; b[n++] = c ? 1 : 0; }
+    }
+    void dht(int ch)
+    {
+        for (int t = 0; t < (ch == 3 ? 2 : 1); t++) {
+            seg(0xC4, 1 + 16 + 12); b[n++] = (uint8_t)t; memcpy(b + n, kDcBits[t], 16); n += 16; memcpy(b + n, kDcVals, 12); n += 12;
+            seg(0xC4, 1 + 16 + 162); b[n++] = (uint8_t)(0x10 | t); memcpy(b + n, kAcBits[t], 16); n += 16; memcpy(b + n, kAcVals[t], 162); n += 162;
+        }
+    }
+    void dri(int restart_mcus) { if (restart_mcus) { seg(0xDD, 2); b[n++] = (uint8_t)(restart_mcus >> 8); b[n++] = (uint8_t)restart_mcus; } }
+    void sos(int ch)
+    {
+        seg(0xDA, 4 + 2 * (size_t)ch);
+        b[n++] = (uint8_t)ch;
+        for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = c ? 0x11 : 0x00; }
+        b[n++] = 0; b[n++] = 0x3F; b[n++] = 0;
+    }
+};
+}  // namespace
+
+// SOI, SOF0 (tile x tile), DRI (restart_mcus > 0), SOS header into out[44] -> the length (tests/tiff_jpeg_ref.py: tile_prefix)
+int jpeg_tile_prefix(int tile, int ch, int restart_mcus, uint8_t *out)
+{
+    SegWriter w{out};
+    w.soi(); w.sof0(tile, tile, ch); w.dri(restart_mcus); w.sos(ch);
+    return (int)w.n;
+}
+
+// The JPEGTables datastream of a TIFF whose tiles the device encodes (tests/tiff_jpeg_ref.py: tables): SOI, the DQT and DHT segments of
+// vfsms_jpeg_header in its order, EOI.  Host only.  *nbytes = the size, also on VFSMS_ERR_CAPACITY
+extern "C" int vfsms_tiff_jpeg_tables(int ch, int quality, uint8_t *out, size_t cap, size_t *nbytes)
+{
+    if (!nbytes) { vfsms_set_error("tiff_jpeg_tables: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(jpeg_check_geometry("tiff_jpeg_tables", 16, 16, ch, quality, 0, nullptr));
+    uint8_t b[700];
+    SegWriter w{b};
+    w.soi(); w.dqt(quality, ch); w.dht(ch);
+    b[w.n++] = 0xFF; b[w.n++] = 0xD9;
+    *nbytes = w.n;
+    if (!out || cap < w.n) { vfsms_set_error("tiff_jpeg_tables: output buffer too small"); return VFSMS_ERR_CAPACITY; }
+    memcpy(out, b, w.n);
+    return VFSMS_OK;
+}
+
 // SOI, JFIF APP0, DQT per table, SOF0, DHT per table, DRI (restart_mcus > 0), SOS header: libjpeg's layout byte for byte, so the entropy-coded
 // bytes of the device (vfsms_canvas_encode_jpeg_rows) behind it and FF D9 behind them are a file.  Host only.  *nbytes = the size, also on
 // VFSMS_ERR_CAPACITY
@@ -904,27 +980,13 @@ extern "C" int vfsms_jpeg_header(int rows, int cols, int ch, int quality, int re
 {
     if (!nbytes) { vfsms_set_error("jpeg_header: bad arguments"); return VFSMS_ERR_BAD_ARG; }
     TRY(jpeg_check_geometry("jpeg_header", rows, cols, ch, quality, restart_mcus, nullptr));
-    uint8_t b[700]; size_t n = 0;
-    auto seg = [&](int marker, size_t payload) { b[n++] = 0xFF; b[n++] = (uint8_t)marker; b[n++] = (uint8_t)((payload + 2) >> 8); b[n++] = (uint8_t)(payload + 2); };
-    b[n++] = 0xFF; b[n++] = 0xD8;
+    uint8_t b[700];
+    SegWriter w{b};
+    w.soi();
     static const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-    seg(0xE0, 14); memcpy(b + n, jfif, 14); n += 14;
-    uint8_t q[2][64];
-    jpeg_quant_tables(quality, q);
-    const int ntab = ch == 3 ? 2 : 1;
-    for (int t = 0; t < ntab; t++) { seg(0xDB, 65); b[n++] = (uint8_t)t; for (int k = 0; k < 64; k++) b[n++] = q[t][kZigzag[k]]; }
-    seg(0xC0, 6 + 3 * (size_t)ch);
-    b[n++] = 8; b[n++] = (uint8_t)(rows >> 8); b[n++] = (uint8_t)rows; b[n++] = (uint8_t)(cols >> 8); b[n++] = (uint8_t)cols; b[n++] = (uint8_t)ch;
-    for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = (ch == 3 && c == 0) ? 0x22 : 0x11; b[n++] = c ? 1 : 0; }
-    for (int t = 0; t < ntab; t++) {
-        seg(0xC4, 1 + 16 + 12); b[n++] = (uint8_t)t; memcpy(b + n, kDcBits[t], 16); n += 16; memcpy(b + n, kDcVals, 12); n += 12;
-        seg(0xC4, 1 + 16 + 162); b[n++] = (uint8_t)(0x10 | t); memcpy(b + n, kAcBits[t], 16); n += 16; memcpy(b + n, kAcVals[t], 162); n += 162;
-    }
-    if (restart_mcus) { seg(0xDD, 2); b[n++] = (uint8_t)(restart_mcus >> 8); b[n++] = (uint8_t)restart_mcus; }
-    seg(0xDA, 4 + 2 * (size_t)ch);
-    b[n++] = (uint8_t)ch;
-    for (int c = 0; c < ch; c++) { b[n++] = (uint8_t)(c + 1); b[n++] = c ? 0x11 : 0x00; }
-    b[n++] = 0; b[n++] = 0x3F; b[n++] = 0;
+    w.seg(0xE0, 14); memcpy(b + w.n, jfif, 14); w.n += 14;
+    w.dqt(quality, ch); w.sof0(rows, cols, ch); w.dht(ch); w.dri(restart_mcus); w.sos(ch);
+    const size_t n = w.n;
     *nbytes = n;
     if (!out || cap < n) { vfsms_set_error("jpeg_header: output buffer too small"); return VFSMS_ERR_CAPACITY; }
     memcpy(out, b, n);

@@ -185,14 +185,18 @@ size_t pyramid_band_bytes(int rows, int cols, int ch, int row0, int nrows, int l
 // band: row0 % 2^levels == 0, and nrows % 2^levels == 0 unless the band ends at the last row
 int pyramid_band_device(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *d_levels)
 {
-    uint8_t *lvl[VFSMS_PYRAMID_MAX_LEVELS + 1]; size_t lvl_bytes[VFSMS_PYRAMID_MAX_LEVELS + 1];
-    size_t off = 0;
-    for (int k = 1; k <= levels; k++) {
-        lvl[k] = d_levels + off;
-        lvl_bytes[k] = pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, k) - off;
-        off += lvl_bytes[k];
-    }
-    ProfScope ps(ctx, "pyramid");
+    uint8_t *lvl[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
+    for (int k = 1; k <= levels; k++) lvl[k] = d_levels + pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, k - 1);
+    return pyramid_band_device_at(ctx, cv, row0, nrows, levels, lvl, "pyramid");
+}
+
+// the same band with every level at a place of its own: level k's rows, densely packed, from lvl[k] on (k = 1 .. levels)
+int pyramid_band_device_at(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, int levels, uint8_t *const *lvl, const char *stage)
+{
+    size_t lvl_bytes[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
+    for (int k = 1; k <= levels; k++)
+        lvl_bytes[k] = pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, k) - pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, k - 1);
+    ProfScope ps(ctx, stage);
     PyrArgs a;
     a.src = cv->pix.as<uint8_t>(); a.src_bytes = (size_t)cv->rows * cv->cols * cv->ch; a.src_row0 = 0;
     a.R0 = cv->rows; a.C0 = cv->cols; a.row_begin = row0; a.row_end = row0 + nrows;

@@ -341,19 +341,44 @@ class PyramidTiffBandWriter:
     many to send -- `levels`, or the smallest count whose last level fits one tile.  Per level the rows that do not fill a tile row yet are
     carried (a copy), a complete tile row is written at once, the directories behind the last band.  Tiles are row-major, edge tiles
     padded with zeros; compression "none" or "deflate" (every tile a zlib stream, level 1, compressed on the encoder pool).  Bands are
-    B G R like the canvas; the file is R G B.  The file is written under a hidden name beside `path` and renamed when it is complete."""
+    B G R like the canvas; the file is R G B.  The file is written under a hidden name beside `path` and renamed when it is complete.
+
+    compression "jpeg" (TIFF compression 7, what slide viewers expect; tests/tiff_jpeg_ref.py): the writer takes no pixels at all.  It
+    declares `device_tiles`, and `tiles(row0, nrows, payload, index, full_shape)` takes the finished tile streams of a band as
+    Engine.canvas_encode_pyramid_tiles hands them out -- encoded on the device at `quality` with `restart_mcus` MCUs per restart interval
+    (0: one interval per tile), edge tiles replicating the level's last row and column -- appends the payload with one write and notes
+    (offset, count) per tile from the index.  The tables go into JPEGTables once per directory; colour is Y Cb Cr 4:2:0 (Photometric 6).
+    There is no host encoder behind it: pixel bands are refused."""
 
     transient_bands = True      # done with a band (and its levels) when the call returns
 
-    def __init__(self, path, tile=512, levels=None, compression="none", force_big=False):
+    def __init__(self, path, tile=512, levels=None, compression="none", force_big=False, quality=95, restart_mcus=8):
         if int(tile) <= 0 or int(tile) % 16:
             raise ValueError("PyramidTiffBandWriter: tile must be a positive multiple of 16 (TIFF 6.0, TileWidth), got %r" % (tile,))
-        if compression not in ("none", "deflate"):
-            raise ValueError("PyramidTiffBandWriter: compression must be 'none' or 'deflate', got %r" % (compression,))
+        if compression not in ("none", "deflate", "jpeg"):
+            raise ValueError("PyramidTiffBandWriter: compression must be 'none', 'deflate' or 'jpeg', got %r" % (compression,))
         if levels is not None and not 0 <= int(levels) <= PYRAMID_MAX_LEVELS:
             raise ValueError("PyramidTiffBandWriter: levels must be None or 0..%d, got %r" % (PYRAMID_MAX_LEVELS, levels))
         self.path, self.tile, self.levels, self.compression, self.force_big = path, int(tile), levels, compression, force_big
+        self.quality, self.restart_mcus = int(quality), int(restart_mcus)
+        self.device_tiles = compression == "jpeg"                # the bands arrive as finished tile streams (`tiles`), not as pixels
+        if self.device_tiles:
+            self.check_jpeg_geometry(3)                          # (what holds for colour's (tile / 16)^2 MCUs holds for gray's (tile / 8)^2)
         self._f = None
+
+    def check_jpeg_geometry(self, ch):
+        """the refusals of tests/tiff_jpeg_ref.py's geometry for tiles of `ch` channels"""
+        if ch not in (1, 3):
+            raise ValueError("PyramidTiffBandWriter: JPEG tiles hold 1 or 3 channels, got %d" % ch)
+        if not 1 <= self.quality <= 100:
+            raise ValueError("PyramidTiffBandWriter: quality must be 1..100, got %r" % (self.quality,))
+        if not 0 <= self.restart_mcus <= 65535:
+            raise ValueError("PyramidTiffBandWriter: restart_mcus must be 0..65535, got %r" % (self.restart_mcus,))
+        n = (self.tile // (16 if ch == 3 else 8)) ** 2
+        interval = self.restart_mcus or n
+        if n % interval or interval > 65535:
+            raise ValueError("PyramidTiffBandWriter: the %d MCUs of a %d x %d tile are not whole restart intervals of %d MCUs (at most 65535 each)"
+                             % (n, self.tile, self.tile, interval))
 
     def pyramid_levels(self, full_shape):
         return int(self.levels) if self.levels is not None else default_levels(int(full_shape[0]), int(full_shape[1]), self.tile)
@@ -384,6 +409,10 @@ class PyramidTiffBandWriter:
         self._carry = [None] * (K + 1)
         self._rows_in = [0] * (K + 1)
         self._tiles = [[] for _ in range(K + 1)]                 # (offset, byte count) per tile, row-major
+        if self.device_tiles:
+            from . import _lib
+            self.check_jpeg_geometry(self._ch)
+            self._tables = _lib.tiff_jpeg_tables(self._ch, self.quality)
 
     def _tile_row(self, k, strip):
         """one row of tiles of level k from `strip` (<= tile rows, the level's full width, R G B), edge tiles zero-padded"""
@@ -425,15 +454,18 @@ class PyramidTiffBandWriter:
         f, big, ch = self._f, self._big, self._ch
         ltype, lfmt, lsize = (16, "Q", 8) if big else (4, "I", 4)
         field = 8 if big else 4
-        fmts = {3: "H", 4: "I", 16: "Q"}
+        fmts = {3: "H", 4: "I", 7: "B", 16: "Q"}
+        jpeg = self.device_tiles
         ifds = []
         for k, (rows, cols) in enumerate(self._sizes):
             n = len(self._tiles[k])
             assert n == -(-rows // self.tile) * -(-cols // self.tile), "level %d: %d tiles written" % (k, n)
             tags = [(254, 4, [1 if k else 0]), (256, ltype, [cols]), (257, ltype, [rows]), (258, 3, [8] * ch),
-                    (259, 3, [8 if self.compression == "deflate" else 1]), (262, 3, [2 if ch == 3 else 1]), (277, 3, [ch]), (284, 3, [1]),
-                    (322, ltype, [self.tile]), (323, ltype, [self.tile]), (324, ltype, [o for o, _c in self._tiles[k]]),
+                    (259, 3, [7 if jpeg else 8 if self.compression == "deflate" else 1]), (262, 3, [1 if ch == 1 else 6 if jpeg else 2]), (277, 3, [ch]),
+                    (284, 3, [1]), (322, ltype, [self.tile]), (323, ltype, [self.tile]), (324, ltype, [o for o, _c in self._tiles[k]]),
                     (325, ltype, [c for _o, c in self._tiles[k]])]
+            if jpeg:                                             # JPEGTables (UNDEFINED bytes); YCbCrSubSampling 2, 2: the coder's 4:2:0
+                tags += [(347, 7, list(self._tables))] + ([(530, 3, [2, 2])] if ch == 3 else [])
             entries = []
             for tag, ty, vals in tags:
                 data = struct.pack("<%d%s" % (len(vals), fmts[ty]), *vals)
@@ -458,9 +490,48 @@ class PyramidTiffBandWriter:
             raise ValueError("PyramidTiffBandWriter: the file outgrew classic TIFF's 4 GB; write it with force_big=True")
         f.seek(8 if big else 4); f.write(struct.pack("<" + lfmt, first))
 
+    def _finish(self):
+        self._directories()
+        self._f.close()
+        self._f = None
+        os.replace(self._part, self.path)
+
+    def _abort(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+        if os.path.exists(self._part):
+            os.remove(self._part)
+
+    def tiles(self, row0, nrows, payload, index, full_shape):
+        """compression "jpeg": the tile streams that the band [row0, row0 + nrows) completes (Engine.canvas_encode_pyramid_tiles): `payload`
+        holds them back to back, `index` is (n, 4) integers (level, tile number in the level, offset in payload, bytes) in file order"""
+        try:
+            if not self.device_tiles:
+                raise ValueError("PyramidTiffBandWriter: tile streams go to compression 'jpeg', this writer's is %r" % (self.compression,))
+            if self._f is None:
+                self._open(full_shape, self.pyramid_levels(full_shape))
+            if row0 != self._rows_in[0] or nrows <= 0 or row0 + nrows > self._sizes[0][0]:
+                raise ValueError("PyramidTiffBandWriter: bands arrive in order (row %d expected, got %d)" % (self._rows_in[0], row0))
+            payload = memoryview(payload)
+            pos = self._f.tell()
+            for k, t, off, cnt in np.asarray(index, np.int64).reshape(-1, 4).tolist():
+                if not 0 <= k < len(self._tiles) or t != len(self._tiles[k]) or off < 0 or cnt <= 0 or off + cnt > len(payload):
+                    raise ValueError("PyramidTiffBandWriter: tile %d of level %d is out of order or outside the payload" % (t, k))
+                self._tiles[k].append((pos + off, cnt))
+            self._f.write(payload)
+            self._rows_in[0] += nrows
+            if self._rows_in[0] >= self._sizes[0][0]:
+                self._finish()
+        except BaseException:
+            self._abort()
+            raise
+
     def __call__(self, row0, band, full_shape, levels=None):
         levels = list(levels) if levels is not None else []
         try:
+            if self.device_tiles:
+                raise ValueError("PyramidTiffBandWriter: compression 'jpeg' takes finished tile streams (tiles), there is no host encoder for pixel bands")
             if self._f is None:
                 K = self.pyramid_levels(full_shape)
                 if len(levels) != K:
@@ -472,16 +543,9 @@ class PyramidTiffBandWriter:
                 self._feed(k, arr)
             if self._rows_in[0] < self._sizes[0][0]:
                 return
-            self._directories()
-            self._f.close()
-            self._f = None
-            os.replace(self._part, self.path)
+            self._finish()
         except BaseException:
-            if self._f is not None:
-                self._f.close()
-                self._f = None
-            if os.path.exists(self._part):
-                os.remove(self._part)
+            self._abort()
             raise
 
 

@@ -202,9 +202,26 @@ class Stitcher(Utility.Method):
             state["w"](row0, band, full_shape, **lkw)
             if row0 + band.shape[0] >= full_shape[0]:
                 state["w"] = None
+        def tiles(row0, nrows, payload, index, full_shape):
+            # pyramidCompression "jpeg": the bands' finished tile streams, not their pixels (getStitchByOffset asks the engine for them)
+            if state["w"] is None:
+                path = (pattern % state["n"]) if pattern else paths[state["n"]]
+                if pattern:
+                    paths.append(path)
+                state["n"] += 1
+                state["w"] = band_writer_for(path, **wkw)
+            try:
+                state["w"].tiles(row0, nrows, payload, index, full_shape)
+            except BaseException:
+                state["w"] = None
+                raise
+            if row0 + nrows >= full_shape[0]:
+                state["w"] = None
         sink.transient_bands = bool(getattr(first, "transient_bands", False))
         if hasattr(first, "pyramid_levels"):
             sink.pyramid_levels = first.pyramid_levels
+        if getattr(first, "device_tiles", False):
+            sink.device_tiles, sink.tiles = True, tiles
         self.mosaicSink = sink
         return sink
 
@@ -238,7 +255,8 @@ class Stitcher(Utility.Method):
 
     def _pyramidOptions(self):
         """Method.pyramid* as PyramidTiffBandWriter's keyword arguments"""
-        return {"tile": self.pyramidTile, "levels": self.pyramidLevels, "compression": self.pyramidCompression}
+        return {"tile": self.pyramidTile, "levels": self.pyramidLevels, "compression": self.pyramidCompression,
+                "quality": self.jpegQuality, "restart_mcus": self.jpegRestartMcus}
 
     def _checkPyramidOutput(self, outputfileExtension):
         """Method.outputPyramid, judged before a file is listed or a tile decoded"""
@@ -248,9 +266,18 @@ class Stitcher(Utility.Method):
             raise ValueError("outputPyramid needs a .tif or .tiff output, got outputfileExtension = %r" % (outputfileExtension,))
         if not self.streamOutput:
             raise ValueError("outputPyramid needs streamOutput: the levels are formed from the bands as they leave the device")
-        if not hasattr(self.engine, "canvas_download_pyramid_bands"):
-            raise NotImplementedError("outputPyramid needs an engine with canvas_download_pyramid_bands")
-        PyramidTiffBandWriter("", **self._pyramidOptions())       # (pyramidTile, pyramidLevels, pyramidCompression: the writer's own refusals)
+        jpeg = self.pyramidCompression == "jpeg"                 # the tiles are encoded on the device (csrc/jpeg_enc_kernels.hip in tile order)
+        need = "canvas_encode_pyramid_tiles" if jpeg else "canvas_download_pyramid_bands"
+        if not hasattr(self.engine, need):
+            raise NotImplementedError("outputPyramid%s needs an engine with %s" % (" with pyramidCompression = 'jpeg'" if jpeg else "", need))
+        writer = PyramidTiffBandWriter("", **self._pyramidOptions())       # (pyramidTile, pyramidLevels, pyramidCompression, jpegQuality, jpegRestartMcus: the writer's own refusals)
+        if jpeg:
+            if "mosaicSink" in self.__dict__:
+                raise ValueError("pyramidCompression = 'jpeg' writes the tile streams the device encodes; a mosaicSink of the user's takes pixel bands")
+            writer.check_jpeg_geometry(3 if self.isColorMode else 1)
+            band_rows = int(getattr(self, "mosaicBandRows", 4096))
+            if band_rows <= 0 or band_rows % writer.tile:
+                raise ValueError("JPEG tiles of %d rows need mosaicBandRows to be a multiple of %d, got %d" % (writer.tile, writer.tile, band_rows))
         if self.pyramidLevels is not None:
             self._pyramidBandRows(int(self.pyramidLevels))
 
@@ -267,8 +294,9 @@ class Stitcher(Utility.Method):
         sink = getattr(self, "mosaicSink", None)
         if sink is None or not hasattr(sink, "pyramid_levels"):
             return None
-        if not hasattr(self.engine, "canvas_download_pyramid_bands"):
-            raise NotImplementedError("a mosaicSink with pyramid_levels needs an engine with canvas_download_pyramid_bands")
+        need = "canvas_encode_pyramid_tiles" if getattr(sink, "device_tiles", False) else "canvas_download_pyramid_bands"
+        if not hasattr(self.engine, need):
+            raise NotImplementedError("a mosaicSink with pyramid_levels needs an engine with %s" % need)
         levels = int(sink.pyramid_levels(full_shape))
         self._pyramidBandRows(levels)
         return levels
@@ -1057,6 +1085,14 @@ class Stitcher(Utility.Method):
                     for r0, nr, payload in eng.canvas_encode_jpeg_bands(canvas, resultRow, resultCol, ch, int(self.jpegQuality),
                                                                         int(self.jpegRestartMcus), self._jpegBandRows()):
                         sink(r0, nr, payload, full_shape)
+                    return None
+                if sink is not None and getattr(sink, "device_tiles", False):
+                    # pyramidCompression "jpeg": every band leaves as the finished tile streams of level 0 and of the reduced levels it
+                    # completes (a mosaic that fits one tile: zero reduced levels); the sink appends them
+                    for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, resultRow, resultCol, ch, pyramid or 0, int(self.pyramidTile),
+                                                                                  int(self.jpegQuality), int(self.jpegRestartMcus),
+                                                                                  int(getattr(self, "mosaicBandRows", 4096))):
+                        sink.tiles(r0, nr, payload, index, full_shape)
                     return None
                 if sink is not None and hasattr(eng, "canvas_download_bands"):
                     # streamed write-out: the mosaic leaves the device band by band and is never whole in host memory

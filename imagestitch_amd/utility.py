@@ -203,7 +203,12 @@ class Method():
     # TIFF (PyramidTiffBandWriter: level 0 in pyramidTile x pyramidTile tiles, then reduced-resolution pages, each half the size of the one
     # before) that slide and micrograph viewers open without reading all of it.  The levels are formed on the device from the band that
     # is leaving it anyway.  pyramidLevels None: as many as it takes for the last level to fit one tile (at most 10); pyramidCompression
-    # "none" or "deflate".  Needs a .tif / .tiff output, streamOutput, and mosaicBandRows a multiple of 2^levels
+    # "none", "deflate", or "jpeg": TIFF compression 7 with shared tables in JPEGTables, what slide viewers expect and a tenth of the
+    # bytes (tests/tiff_jpeg_ref.py).  With "jpeg" the tiles of every level are encoded on the device (csrc/jpeg_enc_kernels.hip in tile
+    # order) at jpegQuality with jpegRestartMcus MCUs per restart interval (0: one interval per tile; the MCUs of a tile -- (pyramidTile /
+    # 16)^2 in colour, (pyramidTile / 8)^2 in gray -- must be whole intervals); edge tiles repeat the level's last row and column instead
+    # of padding with zeros; mosaicBandRows must also be a multiple of pyramidTile; there is no host encoder behind it, so a mosaicSink of
+    # the user's is refused.  Needs a .tif / .tiff output, streamOutput, and mosaicBandRows a multiple of 2^levels
     outputPyramid = False
     pyramidTile = 512
     pyramidLevels = None

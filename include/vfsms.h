@@ -593,6 +593,29 @@ int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas, int row0,
  * sticky geometry flag as vfsms_canvas_download_rows.                                                                                   */
 int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int quality, int restart_mcus,
                                   uint8_t *out, size_t cap, size_t *nbytes);
+/* ---- JPEG tiles for pyramidal TIFF (Method.pyramidCompression = "jpeg": TIFF compression 7, shared tables in JPEGTables), encoded on the
+ * device in tile order.  Specification: tests/tiff_jpeg_ref.py (on tests/jpeg_enc_ref.py and tests/pyramid_ref.py); bytes equal it exactly.
+ * A tile is a whole tile x tile image to the coder: samples beyond the level's last row or column repeat it, DC predictors and RSTn
+ * numbering start at 0, no RSTn follows the last interval.  Its stream is abbreviated: SOI, SOF0, DRI (restart_mcus > 0), SOS, scan, EOI.
+ * Refused everywhere (VFSMS_ERR_BAD_ARG): a tile that is no positive multiple of 16, restart_mcus outside 0..65535 (0: one interval per
+ * tile), MCUs of a tile -- (tile / 16)^2 colour, (tile / 8)^2 gray -- that are no whole number of intervals or more than 65535 in one,
+ * quality outside 1..100, channels other than 1 or 3.
+ * vfsms_tiff_jpeg_tables (host only, no context): the JPEGTables datastream -- SOI, the DQT and DHT segments of vfsms_jpeg_header, EOI.
+ * vfsms_jpeg_encode_tiles_device: an image on the host -> all its tile streams, row-major and back to back; offsets[0 .. n_tiles] (the
+ * last being the total; offsets_cap counts entries).  *nbytes = the size needed, also on VFSMS_ERR_CAPACITY.                         */
+int vfsms_tiff_jpeg_tables(int ch, int quality, uint8_t *out, size_t cap, size_t *nbytes);
+int vfsms_jpeg_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int tile, int quality,
+                                   int restart_mcus, uint8_t *out, size_t cap, size_t *nbytes, uint64_t *offsets, int offsets_cap);
+/* Every tile row of level 0 and of reduced levels 1 .. levels (0..VFSMS_PYRAMID_MAX_LEVELS) that the band [row0, row0 + nrows) of the
+ * mosaic completes, as finished tile streams back to back in `out`; index: int64 records {level, tile number in the level (row-major),
+ * offset in out, bytes}, index_cap counts records, in the payload's order: level after level, a level's tiles row-major.  Band contract
+ * (VFSMS_ERR_BAD_ARG otherwise): vfsms_canvas_download_rows_pyramid's; row0 a multiple of the tile; nrows a multiple of the tile unless
+ * the band ends at the last row; bands in order from row 0 (row0 = 0 starts over), with one tile and level count.  Rows of a reduced level that do not fill a tile row yet stay on the device until a later band completes it; the last band
+ * flushes them: nothing of the reduced levels crosses the link as pixels.  *nbytes, *n_index = the sizes needed, also on
+ * VFSMS_ERR_CAPACITY (nothing is written and no row consumed: repeat the call with room).  The sticky geometry flag as
+ * vfsms_canvas_download_rows.                                                                                                         */
+int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile, int quality, int restart_mcus,
+                                      uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index);
 
 /* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
  * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
