@@ -430,38 +430,34 @@ class Engine:
         self._check(self.lib.vfsms_tile_fill_pair(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0),
                                                   C.c_void_p(address) if address is not None else None, int(stride_bytes), int(fmt)))
 
+    def _fill_from_file(self, entry, gray_handle, color_handle, data):
+        """one of the three JPEG hand-overs: True when the tiles are filled, False when the entry hands the file back (tiles still reserved)"""
+        rc = getattr(self.lib, entry)(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
+        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
+            return False
+        self._check(rc)
+        return True
+
     def tile_fill_jpeg(self, gray_handle, color_handle, data):
         """A JPEG file's bytes -> the reserved gray tile and / or the reserved BGR tile, decoded by the library itself (vfsms_tile_fill_jpeg:
         libjpeg-turbo into pinned staging, colour conversion on the device).  True when the tiles are filled; False when this decoder does
         not take the file (no libjpeg.so.8, an unusual colour space, a damaged file, a size other than the tiles'): the tiles are STILL
         RESERVED and the caller decodes some other way.  Safe from any thread."""
-        rc = self.lib.vfsms_tile_fill_jpeg(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
-        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
-            return False
-        self._check(rc)
-        return True
+        return self._fill_from_file("vfsms_tile_fill_jpeg", gray_handle, color_handle, data)
 
     def tile_fill_jpeg_dct(self, gray_handle, color_handle, data):
         """tile_fill_jpeg with the device half of the decoder (vfsms_tile_fill_jpeg_dct, Method.jpegDecoder = "device"): the host stops behind
         the entropy decode, dequantisation and inverse DCT run on the device (csrc/jpeg_dec_kernels.hip).  Same bytes in the tiles, same
         answer: True when they are filled, False when this path does not take the file -- the tiles are STILL RESERVED, tile_fill_jpeg is
         next.  Safe from any thread."""
-        rc = self.lib.vfsms_tile_fill_jpeg_dct(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
-        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
-            return False
-        self._check(rc)
-        return True
+        return self._fill_from_file("vfsms_tile_fill_jpeg_dct", gray_handle, color_handle, data)
 
     def tile_fill_jpeg_huff(self, gray_handle, color_handle, data):
         """tile_fill_jpeg with the whole decoder on the device (vfsms_tile_fill_jpeg_huff, Method.jpegDecoder = "device-entropy"): the host scans
         the file for its markers, the compressed bytes cross the link, Huffman decode, DC prediction, dequantisation and inverse DCT run on the
         device (csrc/jpeg_huff_kernels.hip, csrc/jpeg_dec_kernels.hip).  Same bytes in the tiles, same answer: True when they are filled, False
         when this path does not take the file -- the tiles are STILL RESERVED, tile_fill_jpeg_dct or tile_fill_jpeg is next.  Any thread."""
-        rc = self.lib.vfsms_tile_fill_jpeg_huff(self.ctx, C.c_int64(gray_handle or 0), C.c_int64(color_handle or 0), data, len(data))
-        if rc in (VFSMS_ERR_UNSUPPORTED, VFSMS_ERR_BAD_ARG):
-            return False
-        self._check(rc)
-        return True
+        return self._fill_from_file("vfsms_tile_fill_jpeg_huff", gray_handle, color_handle, data)
 
     def jpeg_scan(self, data):
         """the module's jpeg_scan (vfsms_jpeg_scan: host only, no GPU): the scan record of a file as a dict, or its refusal code"""

@@ -1,5 +1,6 @@
 // api.hip -- context management and the extern "C" entry points declared in include/vfsms.h.
 #include "common.h"
+#include "ingest_fill.h"
 #include "jpeg_huff_core.h"
 #include "phase_resolve_math.h"
 #include <math.h>
@@ -231,17 +232,12 @@ extern "C" int vfsms_ctx_create(int device, vfsms_ctx **out)
 int phase_destroy_plans(vfsms_ctx *ctx);
 
 // the pools whose entries stayed raw pointers (they move between a record and a pool, and carry events): each is freed here and nowhere else
+// (the staging pools of the ingest: stage_pools_free, ingest_fill.h)
 static void tile_pools_free(vfsms_ctx *ctx)
 {
     for (auto &kv : ctx->tiles) { if (kv.second.owned) hipFree(kv.second.ptr); if (kv.second.ready) hipEventDestroy(kv.second.ready); }
     for (auto &pe : ctx->tile_pool) { hipFree(pe.ptr); if (pe.idle) hipEventDestroy(pe.idle); }
     ctx->tiles.clear(); ctx->tile_pool.clear(); ctx->tile_pool_bytes = 0;
-}
-static void stage_pools_free(vfsms_ctx *ctx)
-{
-    for (auto &sb : ctx->stage_pool) hipFree(sb.ptr);
-    for (auto &pb : ctx->pin_pool) hipHostFree(pb.ptr);
-    ctx->stage_pool.clear(); ctx->pin_pool.clear();
 }
 // Only what has an order is written out: nothing may run when memory goes, the plans and the profile want live streams, and the members
 // (device_buf.h) free themselves behind all of it
@@ -430,40 +426,8 @@ extern "C" int vfsms_tile_upload_ch(vfsms_ctx *ctx, const uint8_t *img, int h, i
 }
 // ---- tiles whose pixels arrive later, from other threads: the ingest pipeline (Stitcher.py:68-69 decodes file after file BEFORE the
 // first pair is registered; here the registration of tiles 0, 1, ... starts while tile k is still being decoded) -------------------------
-// Pinned host staging for the decoder threads' hand-overs (vfsms_tile_fill*): the decoder's own memory is pageable, and an asynchronous copy
-// from pageable memory makes the runtime pin it on the fly (a trip through the kernel's memory-map lock per tile, contended by every
-// decoder thread and by the registrar's launches).  The rows are packed into a pinned buffer by the calling thread (a memcpy, in parallel
-// across the decoders) and leave by true DMA.  The pool is shared by the fill threads under stage_mu.
-static int stage_pinned_get(vfsms_ctx *ctx, size_t need, StageBuf *out)
-{
-    {
-        std::lock_guard<std::mutex> lk(ctx->stage_mu);
-        for (size_t k = 0; k < ctx->pin_pool.size(); k++)
-            if (ctx->pin_pool[k].bytes >= need) { *out = ctx->pin_pool[k]; ctx->pin_pool.erase(ctx->pin_pool.begin() + k); return VFSMS_OK; }
-    }
-    out->ptr = nullptr; out->bytes = need;
-    const hipError_t e = hipHostMalloc((void **)&out->ptr, need, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        // the caller falls back to the pageable hand-over: the runtime's sticky "last error" must not outlive this call, or the launch
-        // check of that very fallback (hipGetLastError behind k_ingest_split) would report THIS failure and give the tile up
-        (void)hipGetLastError();
-        out->ptr = nullptr;
-        vfsms_set_error("%s:%d hipHostMalloc(%zu) -> %s", __FILE__, __LINE__, need, hipGetErrorString(e));
-        return VFSMS_ERR_HIP;
-    }
-    return VFSMS_OK;
-}
-static void stage_pinned_put(vfsms_ctx *ctx, StageBuf b)
-{
-    if (!b.ptr) return;
-    std::lock_guard<std::mutex> lk(ctx->stage_mu);
-    if (ctx->pin_pool.size() < 64) ctx->pin_pool.push_back(b); else hipHostFree(b.ptr);
-}
-static void pack_rows(uint8_t *dst, const uint8_t *src, int stride, size_t row_bytes, int h)
-{
-    if ((size_t)stride == row_bytes) { memcpy(dst, src, row_bytes * h); return; }
-    for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * row_bytes, src + (size_t)y * stride, row_bytes);
-}
+// Every hand-over below is one TileFill (ingest_fill.h): it looks the tiles up, leases the staging and ends the tiles filled, given up or
+// still reserved; the entries say what is staged and what is launched.
 static int tile_reserve_impl(vfsms_ctx *ctx, int h, int w, int ch, int64_t *handle)
 {
     if (!handle || h <= 0 || w <= 0 || ch < 1 || ch > 4) { vfsms_set_error("tile_reserve: bad arguments"); return VFSMS_ERR_BAD_ARG; }
@@ -499,33 +463,13 @@ extern "C" int vfsms_tile_reserve_ch(vfsms_ctx *ctx, int h, int w, int ch, int64
 extern "C" int vfsms_tile_fill(vfsms_ctx *ctx, int64_t handle, const uint8_t *img, int stride)
 {
     CTX_ENTER(ctx);
-    hipEvent_t ev; uint8_t *dst; int h, w;
-    {
-        std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-        auto it = ctx->tiles.find(handle);
-        if (it == ctx->tiles.end() || it->second.fill != 1) { vfsms_set_error("tile_fill: not a reserved tile"); return VFSMS_ERR_BAD_ARG; }
-        if (!img) { it->second.fill = 2; ctx->tiles_cv.notify_all(); return VFSMS_OK; }
-        if (stride < it->second.w * it->second.ch) { vfsms_set_error("tile_fill: stride smaller than a row of the tile"); return VFSMS_ERR_BAD_ARG; }
-        ev = it->second.ready; dst = it->second.ptr; h = it->second.h; w = it->second.w * it->second.ch;
-    }
-    StageBuf pb{nullptr, 0};
-    hipError_t e = hipSuccess;
-    if (stage_pinned_get(ctx, (size_t)w * h, &pb) == VFSMS_OK) {
-        pack_rows(pb.ptr, img, stride, (size_t)w, h);
-        e = hipMemcpyAsync(dst, pb.ptr, (size_t)w * h, hipMemcpyHostToDevice, ctx->copy_stream);
-    } else e = hipMemcpy2DAsync(dst, w, img, stride, w, h, hipMemcpyHostToDevice, ctx->copy_stream);   // no pinned memory left: straight from the caller's
-    if (e == hipSuccess) e = hipEventRecord(ev, ctx->copy_stream);
-    if (e == hipSuccess) e = hipEventSynchronize(ev);
-    else hipStreamSynchronize(ctx->copy_stream);
-    stage_pinned_put(ctx, pb);
-    {
-        std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-        auto it = ctx->tiles.find(handle);
-        if (it != ctx->tiles.end()) { it->second.fill = e == hipSuccess ? 0 : 2; it->second.pending = false; }   // (the copy has landed: no stream wait needed)
-        ctx->tiles_cv.notify_all();
-    }
-    if (e != hipSuccess) { vfsms_set_error("tile_fill: %s", hipGetErrorString(e)); return VFSMS_ERR_HIP; }
-    return VFSMS_OK;
+    TileFill f(ctx);
+    TRY(f.begin_one(handle, "tile_fill", img == nullptr));
+    if (!img) return VFSMS_OK;
+    const size_t row = (size_t)f.w * f.ch;
+    if (stride < f.w * f.ch) { vfsms_set_error("tile_fill: stride smaller than a row of the tile"); return f.refuse(VFSMS_ERR_BAD_ARG); }
+    f.copy(f.dg, f.pack(img, stride, row, f.h), row * f.h);
+    return f.finish();
 }
 // One decode, both planes (csrc/ingest_kernels.hip): `src` is what the decoder produced ONCE -- format 0: 8-bit gray, 1: Y Cb Cr interleaved,
 // 2: Y Cb Cr X (4 bytes per pixel) -- and fills the reserved gray tile `gray` (the registration plane, cv2.imdecode(..., 0) of Stitcher.py:68-69)
@@ -534,100 +478,29 @@ extern "C" int vfsms_tile_fill(vfsms_ctx *ctx, int64_t handle, const uint8_t *im
 // both tiles are complete.  Any thread.  src == NULL gives both tiles up.
 int ingest_source_pixel_bytes(int format);
 int launch_ingest_split(hipStream_t stream, const uint8_t *src, uint8_t *gray, uint8_t *bgr, long long n, int format);
-// the reserved tiles of a pair fill, looked up under the lock: 0 and the geometry, or an error with both tiles left as they were
-static int fill_pair_lookup(vfsms_ctx *ctx, int64_t gray, int64_t color, bool give_up, const char *who, int *h, int *w, hipEvent_t *ev, uint8_t **dg, uint8_t **dc)
-{
-    std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-    TileRec *tg = nullptr, *tc = nullptr;
-    if (gray) { auto it = ctx->tiles.find(gray); if (it != ctx->tiles.end() && it->second.fill == 1 && it->second.ch == 1) tg = &it->second; }
-    if (color) { auto it = ctx->tiles.find(color); if (it != ctx->tiles.end() && it->second.fill == 1 && it->second.ch == 3) tc = &it->second; }
-    if ((gray && !tg) || (color && !tc) || (!tg && !tc)) {
-        vfsms_set_error("%s: needs a reserved 1-channel tile and / or a reserved 3-channel tile", who); return VFSMS_ERR_BAD_ARG;
-    }
-    if (give_up) { if (tg) tg->fill = 2; if (tc) tc->fill = 2; ctx->tiles_cv.notify_all(); *h = *w = 0; return VFSMS_OK; }
-    if (tg && tc && (tg->h != tc->h || tg->w != tc->w)) { vfsms_set_error("%s: the two tiles differ in size", who); return VFSMS_ERR_BAD_ARG; }
-    *h = tg ? tg->h : tc->h; *w = tg ? tg->w : tc->w;
-    *ev = tg ? tg->ready : tc->ready; *dg = tg ? tg->ptr : nullptr; *dc = tc ? tc->ptr : nullptr;
-    return VFSMS_OK;
-}
-// a device staging buffer of the decoder threads: a small pool of its own (the tile pool belongs to the context thread)
-static hipError_t stage_device_get(vfsms_ctx *ctx, size_t need, StageBuf *sb)
-{
-    sb->ptr = nullptr; sb->bytes = 0;
-    {
-        std::lock_guard<std::mutex> lk(ctx->stage_mu);
-        for (size_t k = 0; k < ctx->stage_pool.size(); k++)
-            if (ctx->stage_pool[k].bytes >= need) { *sb = ctx->stage_pool[k]; ctx->stage_pool.erase(ctx->stage_pool.begin() + k); return hipSuccess; }
-    }
-    const hipError_t e = hipMalloc((void **)&sb->ptr, need);
-    sb->bytes = need;
-    if (e != hipSuccess) sb->ptr = nullptr;
-    return e;
-}
-static void stage_device_put(vfsms_ctx *ctx, StageBuf sb)
-{
-    if (!sb.ptr) return;
-    std::lock_guard<std::mutex> lk(ctx->stage_mu);
-    if (ctx->stage_pool.size() < 64) ctx->stage_pool.push_back(sb); else hipFree(sb.ptr);
-}
-// the end of a pair fill: both tiles filled, or both given up
-static void fill_pair_settle(vfsms_ctx *ctx, int64_t gray, int64_t color, bool ok)
-{
-    std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-    for (int64_t hd : { gray, color }) {
-        if (!hd) continue;
-        auto it = ctx->tiles.find(hd);
-        if (it != ctx->tiles.end()) { it->second.fill = ok ? 0 : 2; it->second.pending = false; }
-    }
-    ctx->tiles_cv.notify_all();
-}
-// `host` (h * w pixels of `format`, densely packed; pinned when `host_pinned`) -> the device staging buffer -> the split kernel -> both tiles
-// complete (or both given up, on an error) when this returns
 #define VFSMS_SRC_YCC420_RAW 100      // internal: the raw planes of a 4:2:0 JPEG on the iMCU grid (jpeg_decode_raw420_host) -> k_ingest_420
 int launch_ingest_420(hipStream_t stream, const uint8_t *src, int pw, int ph, int h, int w, uint8_t *gray, uint8_t *bgr);
-static int fill_pair_upload(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *host, int h, int w, int format, hipEvent_t ev, uint8_t *dg, uint8_t *dc,
-                            const char *who)
+// `host` (h * w pixels of `format`, densely packed) -> a device staging buffer -> the split kernel -> both tiles
+static void fill_pair_upload(TileFill &f, const uint8_t *host, int format)
 {
-    const int spx = ingest_source_pixel_bytes(format);
-    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
-    const size_t need = format == VFSMS_SRC_YCC420_RAW ? (size_t)pw * ph * 3 / 2 : (size_t)h * w * spx;
-    hipError_t e = hipSuccess; int rc = VFSMS_OK;
-    StageBuf sb{nullptr, 0};
-    if (format == VFSMS_SRC_GRAY8 && !dc) e = hipMemcpyAsync(dg, host, need, hipMemcpyHostToDevice, ctx->copy_stream);      // nothing to convert
-    else {
-        e = stage_device_get(ctx, need, &sb);
-        if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
-        if (e == hipSuccess) rc = format == VFSMS_SRC_YCC420_RAW ? launch_ingest_420(ctx->copy_stream, sb.ptr, pw, ph, h, w, dg, dc)
-                                                                 : launch_ingest_split(ctx->copy_stream, sb.ptr, dg, dc, (long long)h * w, format);
-    }
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
-    if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
-    stage_device_put(ctx, sb);
-    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
-    if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
-    return rc;
+    const int h = f.h, w = f.w, pw = pad16(w), ph = pad16(h);
+    const size_t need = format == VFSMS_SRC_YCC420_RAW ? (size_t)pw * ph * 3 / 2 : (size_t)h * w * ingest_source_pixel_bytes(format);
+    if (format == VFSMS_SRC_GRAY8 && !f.dc) { f.copy(f.dg, host, need); return; }      // nothing to convert
+    uint8_t *src = f.device(need);
+    f.copy(src, host, need);
+    f.run([&] { return format == VFSMS_SRC_YCC420_RAW ? launch_ingest_420(f.ctx->copy_stream, src, pw, ph, h, w, f.dg, f.dc)
+                                                      : launch_ingest_split(f.ctx->copy_stream, src, f.dg, f.dc, (long long)h * w, format); });
 }
 extern "C" int vfsms_tile_fill_pair(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *src, int stride_bytes, int format)
 {
     CTX_ENTER(ctx);
-    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
+    TileFill f(ctx);
     const int spx = ingest_source_pixel_bytes(format);
-    TRY(fill_pair_lookup(ctx, gray, color, src == nullptr, "tile_fill_pair", &h, &w, &ev, &dg, &dc));
+    TRY(f.begin_pair(gray, color, "tile_fill_pair", src == nullptr));
     if (!src) return VFSMS_OK;
-    if (!spx || stride_bytes < w * spx) { vfsms_set_error("tile_fill_pair: unknown format or stride smaller than a source row"); return VFSMS_ERR_BAD_ARG; }
-    const size_t need = (size_t)h * w * spx;
-    StageBuf pb{nullptr, 0};
-    const uint8_t *host = src;
-    std::vector<uint8_t> packed;
-    if (stage_pinned_get(ctx, need, &pb) == VFSMS_OK) { pack_rows(pb.ptr, src, stride_bytes, (size_t)w * spx, h); host = pb.ptr; }
-    else if ((size_t)stride_bytes != (size_t)w * spx) {      // no pinned memory left: straight from the caller's rows, packed first when they are strided
-        pb.ptr = nullptr;
-        packed.resize(need); pack_rows(packed.data(), src, stride_bytes, (size_t)w * spx, h); host = packed.data();
-    } else pb.ptr = nullptr;
-    const int rc = fill_pair_upload(ctx, gray, color, host, h, w, format, ev, dg, dc, "tile_fill_pair");
-    stage_pinned_put(ctx, pb);
-    return rc;
+    if (!spx || stride_bytes < f.w * spx) { vfsms_set_error("tile_fill_pair: unknown format or stride smaller than a source row"); return f.refuse(VFSMS_ERR_BAD_ARG); }
+    fill_pair_upload(f, f.pack(src, stride_bytes, (size_t)f.w * spx, f.h), format);
+    return f.finish();
 }
 
 // A JPEG file's bytes -> the reserved gray tile and / or the reserved B G R tile, ONE decode (csrc/jpeg_host.cpp: the system's libjpeg-turbo,
@@ -637,57 +510,70 @@ extern "C" int vfsms_tile_fill_pair(vfsms_ctx *ctx, int64_t gray, int64_t color,
 // is not the tiles') BOTH TILES STAY RESERVED: the caller decodes some other way and fills them, or gives them up.
 int jpeg_decode_host(const unsigned char *jpeg, size_t nbytes, int want_planes, unsigned char *out, size_t cap, int *h_out, int *w_out, int *comp_out);
 int jpeg_decode_raw420_host(const unsigned char *jpeg, size_t nbytes, unsigned char *out, size_t cap, int *h_out, int *w_out);
+// what the three JPEG routes answer to a file of another size than the tiles' (CAPACITY: the decoder met it first); any other rc as it is
+static int jpeg_size_check(const TileFill &f, int rc, int jh, int jw)
+{
+    if (rc != VFSMS_ERR_CAPACITY && (rc != VFSMS_OK || (jh == f.h && jw == f.w))) return rc;
+    vfsms_set_error("%s: the file is %d x %d, the reserved tiles %d x %d", f.who, jh, jw, f.h, f.w);
+    return VFSMS_ERR_BAD_ARG;
+}
 extern "C" int vfsms_tile_fill_jpeg(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes)
 {
     CTX_ENTER(ctx);
     if (!jpeg || !nbytes) { vfsms_set_error("tile_fill_jpeg: no data"); return VFSMS_ERR_BAD_ARG; }
-    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
-    TRY(fill_pair_lookup(ctx, gray, color, false, "tile_fill_jpeg", &h, &w, &ev, &dg, &dc));
+    TileFill f(ctx);
+    TRY(f.begin_pair(gray, color, "tile_fill_jpeg", false));
     // (the staging buffer is sized for either form: the interleaved planes are 3 bytes per pixel, the raw 4:2:0 planes 1.5 on the iMCU grid)
-    const size_t cap = std::max((size_t)h * w * (dc ? 3 : 1), dc ? (size_t)((w + 15) & ~15) * ((h + 15) & ~15) * 3 / 2 : (size_t)0);
-    StageBuf pb{nullptr, 0};
-    std::vector<uint8_t> pageable;
-    uint8_t *host = nullptr;
-    if (stage_pinned_get(ctx, cap, &pb) == VFSMS_OK) host = pb.ptr;
-    else { pb.ptr = nullptr; pageable.resize(cap); host = pageable.data(); }
+    const size_t cap = std::max((size_t)f.h * f.w * (f.dc ? 3 : 1), f.dc ? (size_t)pad16(f.w) * pad16(f.h) * 3 / 2 : (size_t)0);
+    uint8_t *host = f.host(cap);
     int jh = 0, jw = 0, comp = 0;
     // Colour wanted and a 4:2:0 file: the host stops behind the IDCT, the device upsamples the chroma and converts (k_ingest_420).
     static const bool raw420 = !(getenv("VFSMS_JPEG_RAW420") && atoi(getenv("VFSMS_JPEG_RAW420")) == 0);
     int rc = VFSMS_ERR_UNSUPPORTED;
-    if (dc && raw420) { rc = jpeg_decode_raw420_host(jpeg, nbytes, host, cap, &jh, &jw); comp = 420; }
-    if (rc == VFSMS_ERR_UNSUPPORTED) rc = jpeg_decode_host(jpeg, nbytes, dc != nullptr, host, cap, &jh, &jw, &comp);
-    if (rc == VFSMS_ERR_CAPACITY || (rc == VFSMS_OK && (jh != h || jw != w))) {
-        vfsms_set_error("tile_fill_jpeg: the file is %d x %d, the reserved tiles %d x %d", jh, jw, h, w); rc = VFSMS_ERR_BAD_ARG;
-    }
-    if (rc == VFSMS_OK)
-        rc = fill_pair_upload(ctx, gray, color, host, h, w, comp == 420 ? VFSMS_SRC_YCC420_RAW : comp == 3 ? VFSMS_SRC_YCC24 : VFSMS_SRC_GRAY8, ev, dg, dc, "tile_fill_jpeg");
-    stage_pinned_put(ctx, pb);
-    return rc;
+    if (f.dc && raw420) { rc = jpeg_decode_raw420_host(jpeg, nbytes, host, cap, &jh, &jw); comp = 420; }
+    if (rc == VFSMS_ERR_UNSUPPORTED) rc = jpeg_decode_host(jpeg, nbytes, f.dc != nullptr, host, cap, &jh, &jw, &comp);
+    rc = jpeg_size_check(f, rc, jh, jw);
+    if (rc != VFSMS_OK) return f.refuse(rc);
+    fill_pair_upload(f, host, comp == 420 ? VFSMS_SRC_YCC420_RAW : comp == 3 ? VFSMS_SRC_YCC24 : VFSMS_SRC_GRAY8);
+    return f.finish();
 }
 
+// What both device decoders derive from a file's component count and block grid and the tiles that are wanted: the padded size, whether the
+// three planes go through a scratch in the layout of jpeg_decode_raw420_host (`planes`) or a lone plane does (a colour tile alone from a gray
+// file: the plane has no tile of its own), the scratch's size and the coefficients'
+struct JpegTilePlan { int nc; const int *grid; int pw, ph; bool planes, via_scratch; size_t scratch_bytes, coef_bytes; };
+static int jpeg_tile_plan(const TileFill &f, int nc, const int *grid, JpegTilePlan *P)
+{
+    const int pw = pad16(f.w), ph = pad16(f.h);
+    const bool planes = nc == 3 && f.dc;
+    *P = JpegTilePlan{nc, grid, pw, ph, planes, planes || (nc == 1 && !f.dg), planes ? (size_t)pw * ph * 3 / 2 : (size_t)f.h * f.w, 0};
+    for (int k = 0; k < (f.dc ? nc : 1); k++) P->coef_bytes += (size_t)grid[2 * k] * grid[2 * k + 1] * 128;
+    if (planes && (grid[0] * 8 != ph || grid[1] * 8 != pw || grid[2] * 16 != ph || grid[3] * 16 != pw || grid[4] != grid[2] || grid[5] != grid[3])) {
+        vfsms_set_error("%s: the block grid is not the raw 4:2:0 layout's", f.who); return VFSMS_ERR_UNSUPPORTED;      // (cannot happen: both follow from h, w and 2x2, 1x1, 1x1)
+    }
+    return VFSMS_OK;
+}
 // the device end of both device decoders: the coefficients of a file lie on the device (`blocks`: per wanted component its grid of blocks,
 // back to back; `quant`: a table per component) -> k_jpeg_idct -> the gray tile itself, or the three planes in `scratch` -> k_ingest_420, or
 // the gray replication.  Stream-ordered on the copy stream
-static int jpeg_coefficients_to_tiles(vfsms_ctx *ctx, const uint16_t *quant, const int16_t *blocks, int nc, const int *grid, int h, int w,
-                                      uint8_t *dg, uint8_t *dc, uint8_t *scratch)
+static int jpeg_coefficients_to_tiles(const TileFill &f, const JpegTilePlan &P, const uint16_t *quant, const int16_t *blocks, uint8_t *scratch)
 {
-    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
-    const bool planes = nc == 3 && dc;
+    const int h = f.h, w = f.w;
     JpegIdctArgs A; memset(&A, 0, sizeof(A));
-    A.ncomp = planes ? 3 : 1;
+    A.ncomp = P.planes ? 3 : 1;
     for (int k = 0; k < A.ncomp; k++) {
         JpegIdctComp &C = A.c[k];
         C.coef = blocks + (size_t)A.total * 64; C.quant = quant + (size_t)k * (VFSMS_JPEG_COEF_TABLE_BYTES / 2);
-        C.bcols = grid[2 * k + 1]; C.first = A.total;
-        if (planes) {                                            // Y at pitch pw, then Cb, then Cr at pitch pw / 2: the whole grid, nothing cropped
-            C.dst = k == 0 ? scratch : scratch + (size_t)pw * ph + (size_t)(k - 1) * (pw / 2) * (ph / 2);
-            C.pitch = k == 0 ? pw : pw / 2; C.rows = grid[2 * k] * 8; C.cols = grid[2 * k + 1] * 8;
-        } else { C.dst = dg ? dg : scratch; C.pitch = w; C.rows = h; C.cols = w; }
-        A.total += (unsigned)grid[2 * k] * (unsigned)grid[2 * k + 1];
+        C.bcols = P.grid[2 * k + 1]; C.first = A.total;
+        if (P.planes) {                                          // Y at pitch pw, then Cb, then Cr at pitch pw / 2: the whole grid, nothing cropped
+            C.dst = k == 0 ? scratch : scratch + (size_t)P.pw * P.ph + (size_t)(k - 1) * (P.pw / 2) * (P.ph / 2);
+            C.pitch = k == 0 ? P.pw : P.pw / 2; C.rows = P.grid[2 * k] * 8; C.cols = P.grid[2 * k + 1] * 8;
+        } else { C.dst = f.dg ? f.dg : scratch; C.pitch = w; C.rows = h; C.cols = w; }
+        A.total += (unsigned)P.grid[2 * k] * (unsigned)P.grid[2 * k + 1];
     }
-    int rc = launch_jpeg_idct(ctx->copy_stream, A);
-    if (rc == VFSMS_OK && planes) rc = launch_ingest_420(ctx->copy_stream, scratch, pw, ph, h, w, dg, dc);
-    else if (rc == VFSMS_OK && dc) rc = launch_ingest_split(ctx->copy_stream, dg ? dg : scratch, nullptr, dc, (long long)h * w, VFSMS_SRC_GRAY8);
+    int rc = launch_jpeg_idct(f.ctx->copy_stream, A);
+    if (rc == VFSMS_OK && P.planes) rc = launch_ingest_420(f.ctx->copy_stream, scratch, P.pw, P.ph, h, w, f.dg, f.dc);
+    else if (rc == VFSMS_OK && f.dc) rc = launch_ingest_split(f.ctx->copy_stream, f.dg ? f.dg : scratch, nullptr, f.dc, (long long)h * w, VFSMS_SRC_GRAY8);
     return rc;
 }
 
@@ -700,47 +586,22 @@ static int jpeg_coefficients_to_tiles(vfsms_ctx *ctx, const uint16_t *quant, con
 extern "C" int vfsms_tile_fill_jpeg_dct(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes)
 {
     CTX_ENTER(ctx);
-    const char *who = "tile_fill_jpeg_dct";
-    if (!jpeg || !nbytes) { vfsms_set_error("%s: no data", who); return VFSMS_ERR_BAD_ARG; }
-    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
-    TRY(fill_pair_lookup(ctx, gray, color, false, who, &h, &w, &ev, &dg, &dc));
+    if (!jpeg || !nbytes) { vfsms_set_error("tile_fill_jpeg_dct: no data"); return VFSMS_ERR_BAD_ARG; }
+    TileFill f(ctx);
+    TRY(f.begin_pair(gray, color, "tile_fill_jpeg_dct", false));
     // (the staging buffer is sized for any file of the tiles' size this path takes: three tables, the luma grid on whole 16 x 16 iMCUs at two
     // bytes a sample, and half as much again for the two chroma grids when a colour tile is wanted)
-    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
-    const size_t cap = 3 * (size_t)VFSMS_JPEG_COEF_TABLE_BYTES + (size_t)pw * ph * (dc ? 3 : 2);
-    StageBuf pb{nullptr, 0};
-    std::vector<uint8_t> pageable;
-    uint8_t *host = nullptr;
-    if (stage_pinned_get(ctx, cap, &pb) == VFSMS_OK) host = pb.ptr;
-    else { pb.ptr = nullptr; pageable.resize(cap); host = pageable.data(); }
-    int jh = 0, jw = 0, nc = 0, grid[6] = {0, 0, 0, 0, 0, 0}; size_t need = 0;
-    int rc = jpeg_coefficients_host(jpeg, nbytes, dc == nullptr, host, cap, &jh, &jw, &nc, grid, &need);
-    if (rc == VFSMS_ERR_CAPACITY || (rc == VFSMS_OK && (jh != h || jw != w))) {
-        vfsms_set_error("%s: the file is %d x %d, the reserved tiles %d x %d", who, jh, jw, h, w); rc = VFSMS_ERR_BAD_ARG;
-    }
-    if (rc == VFSMS_OK && nc == 3 && dc && (grid[0] * 8 != ph || grid[1] * 8 != pw || grid[2] * 16 != ph || grid[3] * 16 != pw || grid[4] != grid[2] || grid[5] != grid[3])) {
-        vfsms_set_error("%s: the block grid is not the raw 4:2:0 layout's", who); rc = VFSMS_ERR_UNSUPPORTED;      // (cannot happen: both follow from h, w and 2x2, 1x1, 1x1)
-    }
-    if (rc != VFSMS_OK) { stage_pinned_put(ctx, pb); return rc; }
+    const size_t cap = 3 * (size_t)VFSMS_JPEG_COEF_TABLE_BYTES + (size_t)pad16(f.w) * pad16(f.h) * (f.dc ? 3 : 2);
+    uint8_t *host = f.host(cap);
+    int jh = 0, jw = 0, nc = 0, grid[6] = {0, 0, 0, 0, 0, 0}; size_t need = 0; JpegTilePlan P;
+    int rc = jpeg_size_check(f, jpeg_coefficients_host(jpeg, nbytes, f.dc == nullptr, host, cap, &jh, &jw, &nc, grid, &need), jh, jw);
+    if (rc == VFSMS_OK) rc = jpeg_tile_plan(f, nc, grid, &P);
+    if (rc != VFSMS_OK) return f.refuse(rc);
     // from here on the tiles end filled or given up
-    const bool planes = nc == 3 && dc;                           // the three planes -> scratch -> k_ingest_420
-    const bool via_scratch = planes || (nc == 1 && !dg);         // (a colour tile alone from a gray file: the plane has no tile of its own)
-    const size_t scratch_bytes = planes ? (size_t)pw * ph * 3 / 2 : (size_t)h * w;
-    StageBuf sb{nullptr, 0}, sp{nullptr, 0};
-    hipError_t e = stage_device_get(ctx, need, &sb);
-    if (e == hipSuccess && via_scratch) e = stage_device_get(ctx, scratch_bytes, &sp);
-    if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
-    if (e == hipSuccess) {
-        rc = jpeg_coefficients_to_tiles(ctx, (const uint16_t *)sb.ptr, (const int16_t *)(sb.ptr + (size_t)nc * VFSMS_JPEG_COEF_TABLE_BYTES), nc, grid, h, w, dg, dc, sp.ptr);
-    }
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
-    if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
-    stage_device_put(ctx, sb); stage_device_put(ctx, sp);
-    stage_pinned_put(ctx, pb);
-    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
-    if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
-    return rc;
+    uint8_t *coef = f.device(need), *scratch = P.via_scratch ? f.device(P.scratch_bytes) : nullptr;
+    f.copy(coef, host, need);
+    f.run([&] { return jpeg_coefficients_to_tiles(f, P, (const uint16_t *)coef, (const int16_t *)(coef + (size_t)nc * VFSMS_JPEG_COEF_TABLE_BYTES), scratch); });
+    return f.finish();
 }
 
 // the bare operator behind it: block_rows x block_cols blocks of 64 int16 (natural order, block-row-major) and one uint16[64] table in, the
@@ -772,69 +633,53 @@ extern "C" int vfsms_jpeg_idct(vfsms_ctx *ctx, const int16_t *coef, const uint16
     return VFSMS_OK;
 }
 
-// Method.jpegDecoder = "device-entropy": the contract of vfsms_tile_fill_jpeg_dct, but the host only scans the file for its markers
-// (jpeg_scan_host: no libjpeg) and the entropy decode runs on the device too (csrc/jpeg_huff_kernels.hip), into a device buffer in the layout
-// the inverse transform takes.  The compressed bytes alone cross the link.  The decode waits for the device between its stages (the round
+// the marker scan of a file (jpeg_scan_host: no libjpeg), once for the record's bound and once into the buffer that `buffer(bound)` yields
+// for it: the record, its size and its header, or the scan's refusal with nothing written
+template <typename Buffer>
+static int jpeg_scan_record(const uint8_t *jpeg, size_t nbytes, Buffer buffer, uint8_t **rec, size_t *rec_bytes, JpegScanHeader *H)
+{
+    size_t bound = 0;
+    const int rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, nullptr, 0, &bound);
+    if (rc != VFSMS_ERR_CAPACITY) return rc;
+    *rec = buffer(bound);
+    TRY(jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, *rec, bound, rec_bytes));
+    memcpy(H, *rec, sizeof(*H));
+    return VFSMS_OK;
+}
+// Method.jpegDecoder = "device-entropy": the contract of vfsms_tile_fill_jpeg_dct, but the host only scans the file for its markers and the
+// entropy decode runs on the device too (csrc/jpeg_huff_kernels.hip), into a device buffer in the layout the inverse transform takes.  The
+// compressed bytes alone cross the link.  The decode waits for the device between its stages (the round
 // flags, the damage flags) on an event of its own; the tiles are written only after the damage flags came back clean.
 extern "C" int vfsms_tile_fill_jpeg_huff(vfsms_ctx *ctx, int64_t gray, int64_t color, const uint8_t *jpeg, size_t nbytes)
 {
     CTX_ENTER(ctx);
-    const char *who = "tile_fill_jpeg_huff";
-    if (!jpeg || !nbytes) { vfsms_set_error("%s: no data", who); return VFSMS_ERR_BAD_ARG; }
-    hipEvent_t ev = nullptr; uint8_t *dg = nullptr, *dc = nullptr; int h = 0, w = 0;
-    TRY(fill_pair_lookup(ctx, gray, color, false, who, &h, &w, &ev, &dg, &dc));
-    size_t bound = 0, need = 0;
-    int rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, nullptr, 0, &bound);
-    if (rc != VFSMS_ERR_CAPACITY) return rc;
-    const size_t flags_at = (bound + 15) & ~(size_t)15, cap = flags_at + (VFSMS_JPEG_HUFF_MAX_ROUNDS + 2) * sizeof(uint32_t);
-    StageBuf pb{nullptr, 0};
-    std::vector<uint8_t> pageable;
-    uint8_t *host = nullptr;
-    if (stage_pinned_get(ctx, cap, &pb) == VFSMS_OK) host = pb.ptr;
-    else { pb.ptr = nullptr; pageable.resize(cap); host = pageable.data(); }
-    rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, host, bound, &need);
-    JpegScanHeader H; memset(&H, 0, sizeof(H));
-    if (rc == VFSMS_OK) {
-        memcpy(&H, host, sizeof(H));
-        if (H.h != h || H.w != w) { vfsms_set_error("%s: the file is %d x %d, the reserved tiles %d x %d", who, H.h, H.w, h, w); rc = VFSMS_ERR_BAD_ARG; }
-    }
-    const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
-    const int *grid = H.grid6;
-    if (rc == VFSMS_OK && H.ncomp == 3 && dc && (grid[0] * 8 != ph || grid[1] * 8 != pw || grid[2] * 16 != ph || grid[3] * 16 != pw || grid[4] != grid[2] || grid[5] != grid[3])) {
-        vfsms_set_error("%s: the block grid is not the raw 4:2:0 layout's", who); rc = VFSMS_ERR_UNSUPPORTED;      // (cannot happen: both follow from h, w and 2x2, 1x1, 1x1)
-    }
-    if (rc != VFSMS_OK) { stage_pinned_put(ctx, pb); return rc; }
-    const int nc = H.ncomp;
-    const bool planes = nc == 3 && dc, via_scratch = planes || (nc == 1 && !dg);
-    const size_t scratch_bytes = planes ? (size_t)pw * ph * 3 / 2 : (size_t)h * w;
-    size_t coef_bytes = 0;
-    for (int k = 0; k < (dc ? nc : 1); k++) coef_bytes += (size_t)grid[2 * k] * grid[2 * k + 1] * 128;
-    StageBuf sb{nullptr, 0}, sw{nullptr, 0}, sc{nullptr, 0}, sp{nullptr, 0};
+    if (!jpeg || !nbytes) { vfsms_set_error("tile_fill_jpeg_huff: no data"); return VFSMS_ERR_BAD_ARG; }
+    TileFill f(ctx);
+    TRY(f.begin_pair(gray, color, "tile_fill_jpeg_huff", false));
+    size_t flags_at = 0, need = 0; uint8_t *host = nullptr;
+    JpegScanHeader H; memset(&H, 0, sizeof(H)); JpegTilePlan P;
+    // pinned staging with the decode's flag words behind the record
+    auto staging = [&](size_t bound) { flags_at = (bound + 15) & ~(size_t)15; return f.host(flags_at + (VFSMS_JPEG_HUFF_MAX_ROUNDS + 2) * sizeof(uint32_t)); };
+    int rc = jpeg_scan_record(jpeg, nbytes, staging, &host, &need, &H);
+    rc = jpeg_size_check(f, rc, H.h, H.w);
+    if (rc == VFSMS_OK) rc = jpeg_tile_plan(f, H.ncomp, H.grid6, &P);
+    if (rc != VFSMS_OK) return f.refuse(rc);
+    uint8_t *rec = f.device(need), *work = f.device(jpeg_huff_work_bytes(H, VFSMS_JPEG_HUFF_MAX_ROUNDS)), *coef = f.device(P.coef_bytes);
+    uint8_t *scratch = P.via_scratch ? f.device(P.scratch_bytes) : nullptr;
     hipEvent_t sync = nullptr;
-    hipError_t e = stage_device_get(ctx, need, &sb);
-    if (e == hipSuccess) e = stage_device_get(ctx, jpeg_huff_work_bytes(H, VFSMS_JPEG_HUFF_MAX_ROUNDS), &sw);
-    if (e == hipSuccess) e = stage_device_get(ctx, coef_bytes, &sc);
-    if (e == hipSuccess && via_scratch) e = stage_device_get(ctx, scratch_bytes, &sp);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sync, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemcpyAsync(sb.ptr, host, need, hipMemcpyHostToDevice, ctx->copy_stream);
+    if (f.ok()) f.e = hipEventCreateWithFlags(&sync, hipEventDisableTiming);
+    f.copy(rec, host, need);
     bool refused = false;
-    if (e == hipSuccess) {
+    f.run([&] {
         int used = 0;
-        rc = jpeg_huff_decode_device(ctx->copy_stream, sync, H, sb.ptr, sw.ptr, (uint32_t *)(host + flags_at), VFSMS_JPEG_HUFF_MAX_ROUNDS, dc == nullptr,
-                                     (int16_t *)sc.ptr, &used, nullptr);
+        int r = jpeg_huff_decode_device(ctx->copy_stream, sync, H, rec, work, (uint32_t *)(host + flags_at), VFSMS_JPEG_HUFF_MAX_ROUNDS, f.dc == nullptr,
+                                        (int16_t *)coef, &used, nullptr);
         // a file handed back -- the decoders not in step, damage -- has touched no tile, and the decode has waited for all it launched
-        refused = rc == VFSMS_ERR_UNSUPPORTED || rc == VFSMS_ERR_BAD_ARG;
-        if (rc == VFSMS_OK) rc = jpeg_coefficients_to_tiles(ctx, (const uint16_t *)(sb.ptr + H.off_quant), (const int16_t *)sc.ptr, nc, grid, h, w, dg, dc, sp.ptr);
-    }
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventRecord(ev, ctx->copy_stream);
-    if (e == hipSuccess && rc == VFSMS_OK) e = hipEventSynchronize(ev);
-    if (e != hipSuccess || rc != VFSMS_OK) hipStreamSynchronize(ctx->copy_stream);   // nothing may still read the staging buffers when they are reused
+        refused = r == VFSMS_ERR_UNSUPPORTED || r == VFSMS_ERR_BAD_ARG;
+        return r != VFSMS_OK ? r : jpeg_coefficients_to_tiles(f, P, (const uint16_t *)(rec + H.off_quant), (const int16_t *)coef, scratch);
+    });
+    rc = refused ? f.refuse(f.rc) : f.finish();                  // refused: both tiles stay reserved
     if (sync) hipEventDestroy(sync);
-    stage_device_put(ctx, sb); stage_device_put(ctx, sw); stage_device_put(ctx, sc); stage_device_put(ctx, sp);
-    stage_pinned_put(ctx, pb);
-    if (refused && e == hipSuccess) return rc;                                        // both tiles stay reserved
-    fill_pair_settle(ctx, gray, color, e == hipSuccess && rc == VFSMS_OK);
-    if (e != hipSuccess) { vfsms_set_error("%s: %s", who, hipGetErrorString(e)); return VFSMS_ERR_HIP; }
     return rc;
 }
 
@@ -844,12 +689,10 @@ extern "C" int vfsms_jpeg_entropy_decode(vfsms_ctx *ctx, const uint8_t *jpeg, si
 {
     CTX_ENTER(ctx);
     if (!jpeg || !nbytes || !h || !w || !ncomp || !grid6 || !need) { vfsms_set_error("jpeg_entropy_decode: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    size_t bound = 0, rec_bytes = 0;
-    int rc = jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, nullptr, 0, &bound);
-    if (rc != VFSMS_ERR_CAPACITY) return rc;
-    std::vector<uint8_t> rec(bound);
-    TRY(jpeg_scan_host(jpeg, nbytes, VFSMS_JPEG_HUFF_SUB_BITS, rec.data(), bound, &rec_bytes));
-    JpegScanHeader H; memcpy(&H, rec.data(), sizeof(H));
+    size_t rec_bytes = 0; std::vector<uint8_t> rec; uint8_t *rec_at = nullptr;
+    JpegScanHeader H;
+    int rc = jpeg_scan_record(jpeg, nbytes, [&](size_t bound) { rec.resize(bound); return rec.data(); }, &rec_at, &rec_bytes, &H);
+    if (rc != VFSMS_OK) return rc;
     size_t coef_bytes = 0;
     for (int k = 0; k < H.ncomp; k++) { grid6[2 * k] = H.grid6[2 * k]; grid6[2 * k + 1] = H.grid6[2 * k + 1]; coef_bytes += (size_t)H.grid6[2 * k] * H.grid6[2 * k + 1] * 128; }
     const size_t tables = (size_t)H.ncomp * VFSMS_JPEG_COEF_TABLE_BYTES;

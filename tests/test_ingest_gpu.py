@@ -154,3 +154,98 @@ def test_tile_fill_jpeg_420_equals_the_two_decodes(engine, jpeg_cases):
                 for t in (hg, hc):
                     if t:
                         engine.tile_free(t)
+
+
+# ---- the five hand-over routes at once ----------------------------------------------------------------------------------------------------
+def test_mixed_fills_from_many_threads(engine, tmp_path):
+    """The five routes -- tile_fill, tile_fill_pair, tile_fill_jpeg, tile_fill_jpeg_dct, tile_fill_jpeg_huff -- share one tail and lease from
+    the same two pools at different sizes: 60 fills from 8 threads cycle over the routes, over four files (the smallest the device routes
+    take, sides that are no multiples of 16, a larger one, a one-component one) and over both tiles / gray alone / colour alone; every sixth
+    job is a file the device routes hand back (the entropy route all of them, the dct route its own refused set), so leases return on
+    refusals while other threads hold theirs.  Every filled tile equals
+    Pillow's decode byte for byte.  Then the same 60 jobs again on the warm pools: leases are reused across routes and sizes."""
+    from concurrent.futures import ThreadPoolExecutor
+    import jpeg_huff_cases as K
+    from imagestitch_amd import stitcher as ST
+    _jpeg_or_skip(engine)
+
+    def decodes(name, data):
+        p = str(tmp_path / (name + ".jpg"))
+        with open(p, "wb") as f:
+            f.write(data)
+        return p, np.ascontiguousarray(ST._imread(p, False)), np.ascontiguousarray(ST._imread(p, True))
+
+    taken = {c[0]: c for c in K.taken_set()}
+    files = []
+    for name in ("c420_2x5_q90", "c420_45x61_plain", "c420_200x328_q85", "gray_37x29_q75"):
+        _, h, w, nc, data = taken[name]
+        files.append((name, h, w, data) + decodes(name, data))
+    assert [f[0] for f in files[:3]] == ["c420_2x5_q90", "c420_45x61_plain", "c420_200x328_q85"] and taken["gray_37x29_q75"][3] == 1
+    refused = []
+    for name, h, w, data in K.refused_set():
+        try:                                                     # what tile_fill_jpeg must leave where it takes the file; damaged files: no claim
+            want = decodes(name, data) if name not in ("truncated", "two_scans") else None
+        except Exception:
+            want = None
+        refused.append((name, h, w, data, want))
+    dct_refuses = {c[0] for c in K.D.refused_set()}
+    routes = ("fill", "pair", "jpeg", "dct", "huff")
+
+    def job(j, hg, hc):
+        """-> (gray expected | None, colour expected | None) of the tiles it filled; None, None when it gave them up"""
+        if j % 6 == 5:
+            name, h, w, data, want = refused[(j // 6) % len(refused)]
+            assert engine.tile_fill_jpeg_huff(hg, hc, data) is False, (j, name)
+            took = engine.tile_fill_jpeg_dct(hg, hc, data)        # (what only the entropy route hands back -- progressive, two scans -- it may take)
+            assert took is False or name not in dct_refuses, (j, name)
+            if took or engine.tile_fill_jpeg(hg, hc, data):
+                return (want[1], want[2]) if want else ("any", "any")
+            engine.tile_fill_pair(hg, hc, None, 0, 0)
+            return None, None
+        name, h, w, data, path, gray, bgr = files[j % 4]
+        route = routes[j % 5]
+        if route == "fill":
+            if hg:
+                engine.tile_fill(hg, gray)
+            if hc:
+                engine.tile_fill(hc, bgr)
+        elif route == "pair":
+            owner, shape, parts = ST._decode_once(path, bool(hc))
+            assert shape == (h, w) and parts[0] == "src", (j, name)
+            engine.tile_fill_pair(hg, hc, parts[1], parts[2], parts[3])
+            del owner
+        else:
+            fill = {"jpeg": engine.tile_fill_jpeg, "dct": engine.tile_fill_jpeg_dct, "huff": engine.tile_fill_jpeg_huff}[route]
+            assert fill(hg, hc, data) is True, (j, name, route)
+        return gray, bgr
+
+    def shape_of(j):
+        return refused[(j // 6) % len(refused)][1:3] if j % 6 == 5 else files[j % 4][1:3]
+
+    for warm in (False, True):
+        tiles = []
+        for j in range(60):                                      # reserved on the context's own thread, filled from the pool's
+            h, w = shape_of(j)
+            which = ("both", "gray", "color")[(j + j // 6) % 3]      # (j % 3 alone would give every handed-back file the colour tile)
+            tiles.append((engine.tile_reserve(h, w) if which != "color" else 0, engine.tile_reserve_color(h, w, 3) if which != "gray" else 0))
+        try:
+            with ThreadPoolExecutor(8) as pool:
+                futures = [pool.submit(job, j, *tiles[j]) for j in range(60)]
+                results = [f.result() for f in futures]
+            filled = must = 0
+            for j, ((hg, hc), (gray, bgr)) in enumerate(zip(tiles, results)):
+                h, w = shape_of(j)
+                must += (bool(hg) + bool(hc)) * (j % 6 != 5)
+                if hg and gray is not None and not isinstance(gray, str):
+                    assert np.array_equal(_tile_bytes(engine, hg, h, w, 1), gray), (warm, j, "gray")
+                    filled += 1
+                if hc and bgr is not None and not isinstance(bgr, str):
+                    got = _tile_bytes(engine, hc, h, w, 3)
+                    assert np.array_equal(got, bgr), (warm, j, "colour", int((got != bgr).any(-1).sum()))
+                    filled += 1
+            assert filled >= must >= 50, (filled, must)           # every tile of the 50 jobs on taken files, at the least
+        finally:
+            for hg, hc in tiles:
+                for t in (hg, hc):
+                    if t:
+                        engine.tile_free(t)
