@@ -1109,22 +1109,59 @@ class Engine:
 
     BAND_RING = 3
 
+    # ---- the band walk of the four write-out routes: the walk itself, the ring of pinned buffers the bands land in, the one retry -----
+    @staticmethod
+    def _bands(rows, band_rows):
+        """(k, row0, nrows) of every band of `band_rows` rows over `rows` rows"""
+        for k, r0 in enumerate(range(0, rows, band_rows)):
+            yield k, r0, min(band_rows, rows - r0)
+
+    def _ring(self, name, need):
+        """the ring `name` of BAND_RING pinned u8 buffers kept by the engine, every slot of at least `need` bytes: a slot that is smaller
+        is replaced (outgrown buffers stay valid: they are freed with the engine)"""
+        ring = self.__dict__.setdefault(name, [None] * self.BAND_RING)
+        for j in range(self.BAND_RING):
+            if ring[j] is None or ring[j].size < need:
+                ring[j] = self.pinned_empty((need,))
+        return ring
+
+    def _encode_ring(self, need=0):
+        """the ring of the two encode routes: 64 KiB a slot at first, then a band's answer `need` with room for denser bands"""
+        return self._ring("_jpeg_ring", need + need // 4 + (1 << 16))
+
+    def _capacity_or(self, rc):
+        """rc, with every error but VFSMS_ERR_CAPACITY raised: that one means nothing was written -- call again with room"""
+        if rc != VFSMS_ERR_CAPACITY:
+            self._check(rc)
+        return rc
+
+    def _fitted(self, who, what, call, buf, grown):
+        """call(buf) -> (return code, bytes needed, ...) as _capacity_or leaves it.  On VFSMS_ERR_CAPACITY once more, with the buffer
+        grown(bytes needed, ...) gives -> (the buffer that held the result, bytes needed, ...)"""
+        ans = call(buf)
+        if ans[0] == VFSMS_ERR_CAPACITY:
+            buf = grown(*ans[1:])
+            ans = call(buf)
+            if ans[0] != VFSMS_OK:
+                raise VfsmsError("%s: the %s did not fit the size the library asked for" % (who, what))
+        return (buf,) + tuple(ans[1:])
+
+    @staticmethod
+    def _u8_image(img, who):
+        """a u8 (h, w) or (h, w, ch) array whose rows are contiguous (they may be strided) -> (img, h, w, ch)"""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != img.shape[2]) or img.strides[0] < 0:
+            raise ValueError("%s: a u8 (h, w) or (h, w, ch) array whose rows are contiguous" % who)
+        return img, img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2]
+
     def canvas_download_bands(self, handle, rows, cols, ch, band_rows=4096, transient=False):
         """Generator of (row0, band) over the whole mosaic, `band_rows` rows at a time (streamed write-out of large mosaics).  With
         `transient` the bands are views of a ring of BAND_RING pinned buffers kept by the engine (the copy is a DMA at link speed, no
         page faults of a fresh array per band): a band is valid until BAND_RING - 1 further bands have been requested -- for consumers
         that are done with a band by then (JpegBandWriter declares it: `transient_bands`)."""
-        if not transient:
-            for r0 in range(0, rows, band_rows):
-                yield r0, self.canvas_download_rows(handle, r0, min(band_rows, rows - r0), cols, ch)
-            return
-        need = min(band_rows, rows) * cols * ch
-        ring = self.__dict__.get("_band_ring")
-        if ring is None or ring[0].size < need:
-            ring = self.__dict__["_band_ring"] = [self.pinned_empty((need,)) for _ in range(self.BAND_RING)]      # (an outgrown ring is freed with the engine)
-        for k, r0 in enumerate(range(0, rows, band_rows)):
-            n = min(band_rows, rows - r0)
-            out = ring[k % self.BAND_RING][:n * cols * ch].reshape((n, cols, ch) if ch > 1 else (n, cols))
+        ring = self._ring("_band_ring", min(band_rows, rows) * cols * ch) if transient else None
+        for k, r0, n in self._bands(rows, band_rows):
+            out = ring[k % self.BAND_RING][:n * cols * ch].reshape((n, cols, ch) if ch > 1 else (n, cols)) if transient else None
             yield r0, self.canvas_download_rows(handle, r0, n, cols, ch, out=out)
 
     @staticmethod
@@ -1168,13 +1205,8 @@ class Engine:
         shape = lambda n: (n, cols, ch) if ch > 1 else (n, cols)
         nb0 = min(band_rows, rows) * cols * ch
         need = nb0 + sum(int(np.prod(s_)) for s_ in self.pyramid_band_shapes(0, min(band_rows, rows), cols, ch, levels))
-        ring = None
-        if transient:
-            ring = self.__dict__.get("_band_ring")
-            if ring is None or ring[0].size < need:
-                ring = self.__dict__["_band_ring"] = [self.pinned_empty((need,)) for _ in range(self.BAND_RING)]
-        for k, r0 in enumerate(range(0, rows, band_rows)):
-            n = min(band_rows, rows - r0)
+        ring = self._ring("_band_ring", need) if transient else None
+        for k, r0, n in self._bands(rows, band_rows):
             slot = ring[k % self.BAND_RING] if transient else np.empty(need, np.uint8)
             band = slot[:n * cols * ch].reshape(shape(n))
             yield r0, band, self._pyramid_rows(handle, r0, n, cols, ch, levels, band, slot[nb0:])
@@ -1183,22 +1215,12 @@ class Engine:
         """vfsms_jpeg_encode_device: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> a complete baseline JPEG as a u8
         array, encoded on the device: the bytes of tests/jpeg_enc_ref.py's encode(), which at restart_mcus = 0 (the image is one restart
         interval: at most 65535 MCUs) are libjpeg's.  restart_mcus = R: a restart interval of R MCUs."""
-        img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != img.shape[2]) or img.strides[0] < 0:
-            raise ValueError("jpeg_encode_device: a u8 (h, w) or (h, w, ch) array whose rows are contiguous")
-        h, w = img.shape[:2]
-        ch = 1 if img.ndim == 2 else img.shape[2]
-        cap = max(1 << 16, h * w * ch // 4)
+        img, h, w, ch = self._u8_image(img, "jpeg_encode_device")
         n = C.c_size_t()
-        for _ in range(2):
-            out = np.empty(cap, np.uint8)
-            rc = self.lib.vfsms_jpeg_encode_device(self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(quality),
-                                                   int(restart_mcus), _ptr(out), cap, C.byref(n))
-            if rc != VFSMS_ERR_CAPACITY:
-                self._check(rc)
-                return out[:n.value]
-            cap = n.value
-        raise VfsmsError("jpeg_encode_device: the stream did not fit the size the library asked for")
+        call = lambda out: (self._capacity_or(self.lib.vfsms_jpeg_encode_device(
+            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(quality), int(restart_mcus), _ptr(out), out.size, C.byref(n))), n.value)
+        out, size = self._fitted("jpeg_encode_device", "stream", call, np.empty(max(1 << 16, h * w * ch // 4), np.uint8), lambda need: np.empty(need, np.uint8))
+        return out[:size]
 
     def canvas_encode_jpeg_rows(self, handle, row0, nrows, quality, restart_mcus, out):
         """one vfsms_canvas_encode_jpeg_rows call into the u8 vector `out` -> (return code, bytes needed); VFSMS_ERR_CAPACITY is returned, not
@@ -1206,9 +1228,7 @@ class Engine:
         n = C.c_size_t()
         rc = self.lib.vfsms_canvas_encode_jpeg_rows(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(quality), int(restart_mcus),
                                                     _ptr(out), C.c_size_t(out.size), C.byref(n))
-        if rc != VFSMS_ERR_CAPACITY:
-            self._check(rc)
-        return rc, n.value
+        return self._capacity_or(rc), n.value
 
     def canvas_encode_jpeg_bands(self, handle, rows, cols, ch, quality, restart_mcus, band_rows):
         """Generator of (row0, nrows, bytes-view) over the whole mosaic: every band of `band_rows` rows as the entropy-coded bytes of a
@@ -1219,45 +1239,25 @@ class Engine:
         rows, cols, ch, band_rows = int(rows), int(cols), int(ch), int(band_rows)
         if band_rows <= 0:
             raise ValueError("canvas_encode_jpeg_bands: band_rows must be positive")
-        ring = self.__dict__.get("_jpeg_ring")
-        if ring is None:
-            ring = self.__dict__["_jpeg_ring"] = [self.pinned_empty((1 << 16,)) for _ in range(self.BAND_RING)]
-        for k, r0 in enumerate(range(0, rows, band_rows)):
-            n = min(band_rows, rows - r0)
+        for k, r0, n in self._bands(rows, band_rows):
             slot = k % self.BAND_RING
-            rc, need = self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, ring[slot])
-            if rc == VFSMS_ERR_CAPACITY:
-                size = need + need // 4 + (1 << 16)                                      # the band's answer with room for denser bands
-                for j in range(self.BAND_RING):                                           # (outgrown buffers stay valid: they are freed with the engine)
-                    if ring[j].size < size:
-                        ring[j] = self.pinned_empty((size,))
-                rc, need = self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, ring[slot])
-                if rc != VFSMS_OK:
-                    raise VfsmsError("canvas_encode_jpeg_bands: the band did not fit the size the library asked for")
-            yield r0, n, ring[slot][:need]
+            out, need = self._fitted("canvas_encode_jpeg_bands", "band", lambda out: self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, out),
+                                     self._encode_ring()[slot], lambda need: self._encode_ring(need)[slot])
+            yield r0, n, out[:need]
 
     def jpeg_encode_tiles_device(self, img, tile, bgr=True, quality=95, restart_mcus=0):
         """vfsms_jpeg_encode_tiles_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload u8,
         offsets uint64 [n_tiles + 1]): the abbreviated JPEG streams of the image's tile x tile tiles, row-major and back to back -- level 0 of
         tests/tiff_jpeg_ref.py's file_tiles.  Tile t is payload[offsets[t]:offsets[t + 1]]."""
-        img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != img.shape[2]) or img.strides[0] < 0:
-            raise ValueError("jpeg_encode_tiles_device: a u8 (h, w) or (h, w, ch) array whose rows are contiguous")
-        h, w = img.shape[:2]
-        ch = 1 if img.ndim == 2 else img.shape[2]
+        img, h, w, ch = self._u8_image(img, "jpeg_encode_tiles_device")
         T = max(int(tile), 1)
         offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
-        cap = max(1 << 16, h * w * ch // 4)
         n = C.c_size_t()
-        for _ in range(2):
-            out = np.empty(cap, np.uint8)
-            rc = self.lib.vfsms_jpeg_encode_tiles_device(self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile),
-                                                         int(quality), int(restart_mcus), _ptr(out), cap, C.byref(n), _ptr(offsets), offsets.size)
-            if rc != VFSMS_ERR_CAPACITY:
-                self._check(rc)
-                return out[:n.value], offsets
-            cap = n.value
-        raise VfsmsError("jpeg_encode_tiles_device: the tiles did not fit the size the library asked for")
+        call = lambda out: (self._capacity_or(self.lib.vfsms_jpeg_encode_tiles_device(
+            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile), int(quality), int(restart_mcus),
+            _ptr(out), out.size, C.byref(n), _ptr(offsets), offsets.size)), n.value)
+        out, size = self._fitted("jpeg_encode_tiles_device", "tiles", call, np.empty(max(1 << 16, h * w * ch // 4), np.uint8), lambda need: np.empty(need, np.uint8))
+        return out[:size], offsets
 
     @staticmethod
     def pyramid_tiles_index(rows, cols, levels, tile, row0, nrows):
@@ -1281,9 +1281,7 @@ class Engine:
         n, ni = C.c_size_t(), C.c_int()
         rc = self.lib.vfsms_canvas_encode_pyramid_tiles(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(levels), int(tile), int(quality),
                                                         int(restart_mcus), _ptr(out), C.c_size_t(out.size), C.byref(n), _ptr(index), len(index), C.byref(ni))
-        if rc != VFSMS_ERR_CAPACITY:
-            self._check(rc)
-        return rc, n.value, ni.value
+        return self._capacity_or(rc), n.value, ni.value
 
     def canvas_encode_pyramid_tiles(self, handle, rows, cols, ch, levels, tile, quality, restart_mcus, band_rows):
         """Generator of (row0, nrows, bytes-view, index) over the whole mosaic: of every band of `band_rows` rows the finished JPEG tile
@@ -1294,24 +1292,17 @@ class Engine:
         rows, cols, ch, levels, tile, band_rows = int(rows), int(cols), int(ch), int(levels), int(tile), int(band_rows)
         if tile <= 0 or band_rows <= 0 or band_rows % tile or band_rows % (1 << levels):
             raise ValueError("canvas_encode_pyramid_tiles: band_rows = %d is not a positive multiple of the tile = %d and of 2^levels = %d" % (band_rows, tile, 1 << levels))
-        ring = self.__dict__.get("_jpeg_ring")
-        if ring is None:
-            ring = self.__dict__["_jpeg_ring"] = [self.pinned_empty((1 << 16,)) for _ in range(self.BAND_RING)]
-        for k, r0 in enumerate(range(0, rows, band_rows)):
-            n = min(band_rows, rows - r0)
+        for k, r0, n in self._bands(rows, band_rows):
             slot = k % self.BAND_RING
-            index = np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)
-            rc, need, ni = self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, ring[slot], index)
-            if rc == VFSMS_ERR_CAPACITY:
-                size = need + need // 4 + (1 << 16)                                      # the band's answer with room for denser bands
-                for j in range(self.BAND_RING):                                           # (outgrown buffers stay valid: they are freed with the engine)
-                    if ring[j].size < size:
-                        ring[j] = self.pinned_empty((size,))
-                index = np.empty((ni, 4), np.int64)
-                rc, need, ni = self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, ring[slot], index)
-                if rc != VFSMS_OK:
-                    raise VfsmsError("canvas_encode_pyramid_tiles: the band did not fit the size the library asked for")
-            yield r0, n, ring[slot][:need], index[:ni]
+            index = [np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)]
+
+            def grown(need, ni):
+                index[0] = np.empty((ni, 4), np.int64)
+                return self._encode_ring(need)[slot]
+            out, need, ni = self._fitted("canvas_encode_pyramid_tiles", "band",
+                                         lambda out: self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, out, index[0]),
+                                         self._encode_ring()[slot], grown)
+            yield r0, n, out[:need], index[0][:ni]
 
 
 _default_engine = None

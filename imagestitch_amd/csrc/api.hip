@@ -1,5 +1,6 @@
 // api.hip -- context management and the extern "C" entry points declared in include/vfsms.h.
 #include "common.h"
+#include "canvas_band.h"
 #include "ingest_fill.h"
 #include "jpeg_huff_core.h"
 #include "phase_resolve_math.h"
@@ -2241,15 +2242,11 @@ extern "C" int vfsms_canvas_set_seam_blend(vfsms_ctx *ctx, int64_t canvas, int b
 static int canvas_read_rows(vfsms_ctx *ctx, const CanvasRec *cv, int row0, int nrows, uint8_t *out)
 {
     const size_t pitch = (size_t)cv->cols * cv->ch;
-    int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, cv->d_err.as<int>(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    int flag = 0;
+    TRY(canvas_flag_read(ctx, cv, &flag));
     if (nrows > 0) HIP_TRY(hipMemcpyAsync(out, cv->pix.as<uint8_t>() + (size_t)row0 * pitch, (size_t)nrows * pitch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (err) {
-        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
-        return VFSMS_ERR_BAD_ARG;
-    }
-    return VFSMS_OK;
+    return canvas_flag_verdict(flag);
 }
 extern "C" int vfsms_canvas_download(vfsms_ctx *ctx, int64_t canvas, uint8_t *out)
 {
@@ -2266,7 +2263,7 @@ extern "C" int vfsms_canvas_download_rows(vfsms_ctx *ctx, int64_t canvas, int ro
     CTX_ENTER(ctx);
     CanvasRec *cv;
     TRY(canvas_find(ctx, "canvas_download_rows", canvas, &cv));
-    if (!out || row0 < 0 || nrows <= 0 || row0 + nrows > cv->rows) { vfsms_set_error("canvas_download_rows: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(canvas_band_check("canvas_download_rows", out != nullptr, cv->rows, row0, nrows, {}));
     return canvas_read_rows(ctx, cv, row0, nrows, out);
 }
 
@@ -2281,14 +2278,8 @@ extern "C" int vfsms_canvas_download_rows_pyramid(vfsms_ctx *ctx, int64_t canvas
     const char *who = "canvas_download_rows_pyramid";
     CanvasRec *cv;
     TRY(canvas_find(ctx, who, canvas, &cv));
-    if (!out_levels || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     if (levels < 1 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 1..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
-    const int step = 1 << levels;
-    if (row0 % step) { vfsms_set_error("%s: row0 = %d is not a multiple of 2^levels = %d", who, row0, step); return VFSMS_ERR_BAD_ARG; }
-    if (nrows % step && row0 + nrows != cv->rows) {
-        vfsms_set_error("%s: nrows = %d is not a multiple of 2^levels = %d and the band does not end at the last row", who, nrows, step);
-        return VFSMS_ERR_BAD_ARG;
-    }
+    TRY(canvas_band_check(who, out_levels != nullptr, cv->rows, row0, nrows, {{1 << levels, "2^levels"}}));
     const size_t need = pyramid_band_bytes(cv->rows, cv->cols, cv->ch, row0, nrows, levels);
     if (cap_levels < need) { vfsms_set_error("%s: the levels take %zu bytes, out_levels holds %zu", who, need, cap_levels); return VFSMS_ERR_BAD_ARG; }
     TRY(cv->pyr.reserve(need, ctx->stream));                    // first use, or a larger band than before
@@ -2310,7 +2301,7 @@ extern "C" int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int
     const char *who = "canvas_encode_jpeg_rows";
     CanvasRec *cv;
     TRY(canvas_find(ctx, who, canvas, &cv));
-    if (!nbytes || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    TRY(canvas_band_check(who, nbytes != nullptr, cv->rows, row0, nrows, {}));     // (MCU rows and restart intervals have texts of their own, below)
     int interval = 0;
     TRY(jpeg_check_geometry(who, cv->rows, cv->cols, cv->ch, quality, restart_mcus, &interval));
     const int mcu = cv->ch == 3 ? 16 : 8, mw = (cv->cols + mcu - 1) / mcu;
@@ -2320,13 +2311,19 @@ extern "C" int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int
         vfsms_set_error("%s: rows [%d, %d) of %d MCUs each are not whole restart intervals of %d MCUs", who, row0, row0 + nrows, mw, interval);
         return VFSMS_ERR_BAD_ARG;
     }
-    int err = 0;                                                   // the sticky geometry flag, as vfsms_canvas_download_rows reads it
-    HIP_TRY(hipMemcpyAsync(&err, cv->d_err.as<int>(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    int flag = 0;                                                  // the sticky geometry flag, as vfsms_canvas_download_rows reads it
+    TRY(canvas_flag_read(ctx, cv, &flag));
     TRY(jpeg_encode_band_device(ctx, &cv->jpeg, cv->pix.as<uint8_t>(), cv->rows, cv->cols, cv->ch, (size_t)cv->cols * cv->ch, 1, row0, nrows, quality, interval, out, cap, nbytes));
-    if (err) {
-        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
-        return VFSMS_ERR_BAD_ARG;
-    }
+    return canvas_flag_verdict(flag);
+}
+
+// the caller's h x w x ch image (rows `stride` bytes apart), densely packed in the context's encoder scratch: enqueued; *pitch = a row's bytes
+static int jpeg_stage_image(vfsms_ctx *ctx, const char *who, const uint8_t *img, int h, int w, int ch, int stride, size_t *pitch)
+{
+    if ((long long)stride < (long long)w * ch) { vfsms_set_error("%s: stride %d is less than a row's %lld bytes", who, stride, (long long)w * ch); return VFSMS_ERR_BAD_ARG; }
+    *pitch = (size_t)w * ch;
+    TRY(ctx->jpeg_scratch.img.reserve(*pitch * h, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(ctx->jpeg_scratch.img.as<void>(), *pitch, img, (size_t)stride, *pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     return VFSMS_OK;
 }
 
@@ -2340,13 +2337,10 @@ extern "C" int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int 
     if (!img || !nbytes) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     int interval = 0;
     TRY(jpeg_check_geometry(who, h, w, ch, quality, restart_mcus, &interval));
-    if (stride < w * ch) { vfsms_set_error("%s: stride %d is less than a row's %d bytes", who, stride, w * ch); return VFSMS_ERR_BAD_ARG; }
-    size_t hn = 0, bn = 0;
-    TRY(vfsms_jpeg_header(h, w, ch, quality, restart_mcus, out, out ? cap : 0, &hn) == VFSMS_ERR_BAD_ARG ? VFSMS_ERR_BAD_ARG : VFSMS_OK);
     JpegScratch *s = &ctx->jpeg_scratch;
-    const size_t pitch = (size_t)w * ch, bytes = pitch * h;
-    TRY(s->img.reserve(bytes, ctx->stream));
-    HIP_TRY(hipMemcpy2DAsync(s->img.as<void>(), pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    size_t pitch = 0, hn = 0, bn = 0;
+    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
+    TRY(vfsms_jpeg_header(h, w, ch, quality, restart_mcus, out, out ? cap : 0, &hn) == VFSMS_ERR_BAD_ARG ? VFSMS_ERR_BAD_ARG : VFSMS_OK);
     const bool room = out && cap > hn + 2;
     const int rc = jpeg_encode_band_device(ctx, s, s->img.as<uint8_t>(), h, w, ch, pitch, bgr != 0, 0, h, quality, interval, room ? out + hn : nullptr, room ? cap - hn - 2 : 0, &bn);
     *nbytes = hn + bn + 2;
@@ -2367,14 +2361,12 @@ extern "C" int vfsms_jpeg_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img
     if (!img || !nbytes || !offsets || h < 1 || w < 1) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     int interval = 0;
     TRY(jpeg_check_tile_geometry(who, tile, ch, quality, restart_mcus, &interval));
-    if ((long long)stride < (long long)w * ch) { vfsms_set_error("%s: stride %d is less than a row's %lld bytes", who, stride, (long long)w * ch); return VFSMS_ERR_BAD_ARG; }
     const long long tr = (h + tile - 1) / tile, n_tiles = tr * ((w + tile - 1) / tile);
     if (tr * (tile / 8) > 65535) { vfsms_set_error("%s: %d rows are more tile rows than one call takes", who, h); return VFSMS_ERR_BAD_ARG; }
     if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
     JpegScratch *s = &ctx->jpeg_scratch;
-    const size_t pitch = (size_t)w * ch;
-    TRY(s->img.reserve(pitch * h, ctx->stream));
-    HIP_TRY(hipMemcpy2DAsync(s->img.as<void>(), pitch, img, (size_t)stride, pitch, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    size_t pitch = 0;
+    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
     const JpegTileJob job = {s->img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
     JpegTilesRun run;
     TRY(jpeg_tiles_count_device(ctx, s, &job, 1, ch, bgr != 0, tile, quality, restart_mcus, interval, nullptr, nullptr, &run));
@@ -2402,103 +2394,29 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas,
     const char *who = "canvas_encode_pyramid_tiles";
     CanvasRec *cv;
     TRY(canvas_find(ctx, who, canvas, &cv));
-    if (!nbytes || !n_index || row0 < 0 || nrows <= 0 || (long long)row0 + nrows > cv->rows) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     if (levels < 0 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 0..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
     int interval = 0;
     TRY(jpeg_check_tile_geometry(who, tile, cv->ch, quality, restart_mcus, &interval));
-    const bool last = row0 + nrows == cv->rows;
-    const int step = 1 << levels;
-    if (row0 % step) { vfsms_set_error("%s: row0 = %d is not a multiple of 2^levels = %d", who, row0, step); return VFSMS_ERR_BAD_ARG; }
-    if (nrows % step && !last) {
-        vfsms_set_error("%s: nrows = %d is not a multiple of 2^levels = %d and the band does not end at the last row", who, nrows, step);
-        return VFSMS_ERR_BAD_ARG;
-    }
-    if (row0 % tile) { vfsms_set_error("%s: row0 = %d is not a multiple of the tile = %d", who, row0, tile); return VFSMS_ERR_BAD_ARG; }
-    if (nrows % tile && !last) {
-        vfsms_set_error("%s: nrows = %d is not a multiple of the tile = %d and the band does not end at the last row", who, nrows, tile);
-        return VFSMS_ERR_BAD_ARG;
-    }
+    TRY(canvas_band_check(who, nbytes && n_index, cv->rows, row0, nrows, {{1 << levels, "2^levels"}, {tile, "the tile"}}));
     PyrPending &P = cv->pend;
-    const int ch = cv->ch;
-    int Rk[VFSMS_PYRAMID_MAX_LEVELS + 1], Ck[VFSMS_PYRAMID_MAX_LEVELS + 1];
-    Rk[0] = cv->rows; Ck[0] = cv->cols;
-    for (int k = 1; k <= levels; k++) { Rk[k] = (Rk[k - 1] + 1) >> 1; Ck[k] = (Ck[k - 1] + 1) >> 1; }
-    if (row0 == 0) {                                              // a new walk over the canvas: nothing is pending, the buffer is sized for this band
-        size_t off = 0;
-        for (int k = 1; k <= levels; k++) {
-            P.off[k] = off; P.base[k] = 0; P.have[k] = 0;
-            off += ((size_t)(tile - 1 + ((nrows + (1 << k) - 1) >> k)) * Ck[k] * ch + 255) & ~(size_t)255;
-        }
-        TRY(P.buf.reserve(off, ctx->stream));
-        P.tile = tile; P.levels = levels; P.band = nrows; P.next = 0;
-    } else if (P.tile != tile || P.levels != levels || P.next != row0) {
-        vfsms_set_error("%s: bands arrive in order from row 0 with one tile and level count (expected row0 = %d, got %d)", who, P.levels < 0 ? 0 : P.next, row0);
-        return VFSMS_ERR_BAD_ARG;
-    } else if (nrows > P.band) {                                  // a longer band than the buffer was sized for: a larger one takes the pending rows over
-        DevBuf grown; size_t noff[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, off = 0;
-        for (int k = 1; k <= levels; k++) { noff[k] = off; off += ((size_t)(tile - 1 + ((nrows + (1 << k) - 1) >> k)) * Ck[k] * ch + 255) & ~(size_t)255; }
-        TRY(grown.reserve(off, ctx->stream));
-        for (int k = 1; k <= levels; k++)
-            if (P.have[k]) HIP_TRY(hipMemcpyAsync(grown.as<uint8_t>() + noff[k], P.buf.as<uint8_t>() + P.off[k], (size_t)P.have[k] * Ck[k] * ch, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                // (the old buffer is freed by the move)
-        P.buf = std::move(grown);
-        for (int k = 1; k <= levels; k++) P.off[k] = noff[k];
-        P.band = nrows;
-    }
-    // what the band completes: level 0's tile rows, and of level k the whole tile rows of its pending rows plus the band's share
-    JpegTileJob jobs[VFSMS_PYRAMID_MAX_LEVELS + 1]; int job_level[VFSMS_PYRAMID_MAX_LEVELS + 1], full[VFSMS_PYRAMID_MAX_LEVELS + 1], total[VFSMS_PYRAMID_MAX_LEVELS + 1];
-    int n_jobs = 0; long long n_tiles = 0, mrows = 0;
-    uint8_t *lvl[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
-    for (int k = 0; k <= levels; k++) {
-        JpegTileJob J;
-        const size_t pitch = (size_t)Ck[k] * ch;
-        if (k == 0) { J = {cv->pix.as<uint8_t>(), (size_t)cv->rows * pitch, pitch, 0, Rk[0], Ck[0], row0, (nrows + tile - 1) / tile}; full[0] = total[0] = nrows; }
-        else {
-            lvl[k] = P.buf.as<uint8_t>() + P.off[k] + (size_t)P.have[k] * pitch;
-            total[k] = P.have[k] + (int)((((long long)row0 + nrows + (1 << k) - 1) >> k) - (row0 >> k));
-            full[k] = last ? total[k] : total[k] / tile * tile;
-            J = {P.buf.as<uint8_t>() + P.off[k], (size_t)total[k] * pitch, pitch, P.base[k], Rk[k], Ck[k], P.base[k], (full[k] + tile - 1) / tile};
-        }
-        if (J.tile_rows == 0) continue;
-        jobs[n_jobs] = J; job_level[n_jobs++] = k;
-        n_tiles += (long long)J.tile_rows * ((Ck[k] + tile - 1) / tile);
-        mrows = std::max(mrows, (long long)J.tile_rows * (tile / 8));
-    }
-    if (mrows > 65535 || n_tiles > 0x7fffffff) { vfsms_set_error("%s: a band of %d rows is more tile rows than one call takes", who, nrows); return VFSMS_ERR_BAD_ARG; }
-    *n_index = (int)n_tiles;
-    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, lvl, "pyramid_jpeg.levels"));
+    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream));
+    PyrPlan plan;
+    TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
+    *n_index = (int)plan.n_tiles;
+    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, plan.lvl, "pyramid_jpeg.levels"));
+    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
     JpegTilesRun run;
-    int err = 0;                                                   // the sticky geometry flag, as vfsms_canvas_download_rows reads it
-    TRY(jpeg_tiles_count_device(ctx, &cv->jpeg, jobs, n_jobs, ch, 1, tile, quality, restart_mcus, interval, cv->d_err.as<int>(), &err, &run));
-    if (err) {
-        vfsms_set_error("fuse: degenerate corner geometry in one of the fused tiles (the reference's getWeightsMatrix raises there)");
-        return VFSMS_ERR_BAD_ARG;
-    }
+    TRY(jpeg_tiles_count_device(ctx, &cv->jpeg, plan.jobs, plan.n_jobs, cv->ch, 1, tile, quality, restart_mcus, interval, cv->d_err.as<int>(), &flag, &run));
+    TRY(canvas_flag_verdict(flag));
     const unsigned long long bytes = run.tile_offs[(size_t)run.n_tiles];
     *nbytes = (size_t)bytes;
-    if (!out || cap < bytes || !index || index_cap < n_tiles) {
-        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
+    if (!out || cap < bytes || !index || index_cap < plan.n_tiles) {              // nothing is consumed: the same band may come again
+        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, plan.n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
         return VFSMS_ERR_CAPACITY;
     }
-    // the coefficients hold everything the streams need: the rows behind the encoded tile rows move to the front for the next band
-    for (int k = 1; k <= levels; k++) {
-        const size_t pitch = (size_t)Ck[k] * ch;
-        const int rem = total[k] - full[k];
-        if (rem > 0 && full[k] > 0)
-            HIP_TRY(hipMemcpyAsync(P.buf.as<uint8_t>() + P.off[k], P.buf.as<uint8_t>() + P.off[k] + (size_t)full[k] * pitch, (size_t)rem * pitch, hipMemcpyDeviceToDevice, ctx->stream));
-        P.base[k] += full[k]; P.have[k] = rem;
-    }
-    P.next = row0 + nrows;
+    TRY(P.commit(plan, ctx->stream));
     TRY(jpeg_tiles_write_device(ctx, &cv->jpeg, &run, out));
-    size_t g = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        const int k = job_level[j], ntx = (Ck[k] + tile - 1) / tile;
-        const long long first = (long long)(jobs[j].row0 / tile) * ntx;
-        for (long long t = 0; t < (long long)jobs[j].tile_rows * ntx; t++, g++) {
-            index[4 * g] = k; index[4 * g + 1] = first + t;
-            index[4 * g + 2] = (int64_t)run.tile_offs[g]; index[4 * g + 3] = (int64_t)(run.tile_offs[g + 1] - run.tile_offs[g]);
-        }
-    }
+    plan.index(run.tile_offs.data(), index);
     return VFSMS_OK;
 }
 

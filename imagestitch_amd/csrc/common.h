@@ -172,11 +172,19 @@ struct JpegTileJob { const uint8_t *src; size_t src_bytes, pitch; int src_row0, 
 // what the counting half of a tile-order encode leaves for the writing half; tile_offs[0 .. n_tiles]: the tiles' offsets in the payload
 struct JpegTilesRun { int n_tiles, n_int, ipt, interval, bpm, plen; uint8_t prefix[44]; uint32_t *d_sizes; unsigned long long *d_offs; int *d_err; std::vector<unsigned long long> tile_offs; };
 // the pending rows of levels 1 .. levels between the bands of vfsms_canvas_encode_pyramid_tiles: level k's rows [base[k], base[k] + have[k])
-// (fewer than a tile row of them) at buf + off[k], with room for the share of a band of `band` rows behind them; next: the row0 expected
-struct PyrPending { DevBuf buf; int tile = 0, levels = -1, band = 0, next = 0; int base[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, have[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; size_t off[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; };
+// (fewer than a tile row of them) at buf + off[k], with room for the share of a band of `band` rows behind them; next: the row0 expected;
+// ch, R[k] x C[k]: the canvas's levels, set when a walk starts.  The operations are canvas_band.h's: begin -> plan -> commit per band
+struct PyrPlan;
+struct PyrPending {
+    DevBuf buf; int tile = 0, levels = -1, band = 0, next = 0; int base[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, have[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; size_t off[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
+    int ch = 0, R[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, C[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
+    int begin(const char *who, int rows, int cols, int ch, int row0, int nrows, int tile, int levels, hipStream_t stream);
+    int plan(const char *who, const uint8_t *pix, int row0, int nrows, PyrPlan *p) const;
+    int commit(const PyrPlan &p, hipStream_t stream);
+};
 // move-only: the record owns its buffers wherever it lies (the canvas map, the context's spare slot, a canvas under construction); an
 // empty record owns nothing.  Destroying one frees without a synchronisation: api.hip's canvas_release synchronises first
-struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; PyrPending pend; };   // pend: the rows of the reduced levels that do not fill a tile row yet (vfsms_canvas_encode_pyramid_tiles), sized at the first band, released with the canvas; jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback; scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; PyrPending pend; };   // pend: the rows of the reduced levels that do not fill a tile row yet (vfsms_canvas_encode_pyramid_tiles; canvas_band.h has its operations and the band contract of all four write-out routes), sized at the band that starts a walk, grown by a longer band, released with the canvas; jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback, read with every band that leaves (canvas_flag_read / canvas_flag_verdict); scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent

@@ -450,6 +450,56 @@ void quant_args(int quality, JpegQuant *qt)
     }
 }
 
+// the `sizes` scratch of a call: the intervals' sizes, their offsets (the last being the total) and the error word of the writing pass; in
+// tile order the tiles' offsets behind them
+struct JpegSizes { uint32_t *sizes; unsigned long long *offs; int *err; unsigned long long *toffs; };
+int sizes_carve(vfsms_ctx *ctx, JpegScratch *s, size_t n_int, size_t n_tiles, JpegSizes *z)
+{
+    const size_t o_offs = (n_int * 4 + 255) & ~(size_t)255, o_err = o_offs + (n_int + 1) * 8;
+    const size_t o_toffs = (o_err + sizeof(int) + 255) & ~(size_t)255;
+    TRY(s->sizes.reserve(o_toffs + (n_tiles + 1) * 8, ctx->stream));
+    char *at = s->sizes.as<char>();
+    *z = {(uint32_t *)at, (unsigned long long *)(at + o_offs), (int *)(at + o_err), (unsigned long long *)(at + o_toffs)};
+    return VFSMS_OK;
+}
+
+// the arguments of a counting pass (the writing half adds `out`); band order: ipt = 0 and no prefix
+JpegEntropyArgs entropy_args(const JpegScratch *s, uint32_t *d_sizes, unsigned long long *d_offs, int *d_err, int n_mcu, int interval, int n_int,
+                             int first_int, int last_marker, int bpm, int ipt, const uint8_t *prefix, int plen)
+{
+    JpegEntropyArgs e;
+    e.coef = s->coef.as<int16_t>(); e.n_mcu = n_mcu; e.interval = interval; e.n_int = n_int; e.first_int = first_int; e.last_marker = last_marker;
+    e.bpm = bpm; e.sizes = d_sizes; e.offs = d_offs; e.out = nullptr; e.cap = 0; e.err = d_err;
+    e.ipt = ipt; e.plen = plen; memset(e.prefix, 0, sizeof(e.prefix)); if (plen) memcpy(e.prefix, prefix, (size_t)plen);
+    return e;
+}
+
+// Writing half of both orders: the `total` bytes that the counting pass `e` measured into `out` on the host (the caller has checked its
+// capacity): one writing pass, one copy.  Synchronises the stream.
+template <bool TILES>
+int entropy_write(vfsms_ctx *ctx, JpegScratch *s, JpegEntropyArgs e, unsigned long long total, uint8_t *out)
+{
+    TRY(s->out.reserve(((size_t)total + 15) & ~(size_t)15, ctx->stream));
+    e.out = s->out.as<uint8_t>(); e.cap = s->out.bytes();
+    int err = 0;
+    {
+        ProfScope ps(ctx, TILES ? "pyramid_jpeg.entropy" : "jpeg_encode.entropy");
+        HIP_TRY(hipMemsetAsync(e.err, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL((k_jpeg_entropy<true, TILES>), dim3((unsigned)((e.n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, TILES ? "pyramid_jpeg.copy" : "jpeg_encode.copy");
+        HIP_TRY(hipMemcpyAsync(&err, e.err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out, s->out.as<uint8_t>(), (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!err) return VFSMS_OK;
+    if (TILES) vfsms_set_error("jpeg tiles: the coded tiles outgrew the %zu bytes counted for them", s->out.bytes());
+    else vfsms_set_error("jpeg_encode: the coded band outgrew the %zu bytes counted for it", s->out.bytes());
+    return VFSMS_ERR_CAPACITY;
+}
+
 }  // namespace
 
 // The entropy-coded bytes of rows [row0, row0 + nrows) of the rows x cols x ch image at d_img (256-byte aligned, `pitch` bytes a row) into
@@ -468,10 +518,8 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
     const bool last = row0 + nrows >= rows;
 
     TRY(s->coef.reserve((size_t)n_mcu * bpm * 128, ctx->stream));
-    TRY(s->sizes.reserve((size_t)n_int * 4 + 256 + ((size_t)n_int + 1) * 8 + sizeof(int), ctx->stream));
-    uint32_t *d_sizes = s->sizes.as<uint32_t>();
-    unsigned long long *d_offs = (unsigned long long *)(s->sizes.as<char>() + (((size_t)n_int * 4 + 255) & ~(size_t)255));
-    int *d_err = (int *)(d_offs + n_int + 1);
+    JpegSizes z;
+    TRY(sizes_carve(ctx, s, (size_t)n_int, 0, &z));
 
     JpegXformArgs x;
     x.src = d_img; x.src_bytes = (size_t)rows * pitch; x.pitch = pitch; x.rows = rows; x.cols = cols; x.row0 = row0; x.mw = mw; x.bgr = bgr;
@@ -486,38 +534,19 @@ int jpeg_encode_band_device(vfsms_ctx *ctx, JpegScratch *s, const uint8_t *d_img
         else hipLaunchKernelGGL((k_jpeg_transform<false, false>), grid, dim3(256), 0, ctx->stream, x);
         HIP_TRY(hipGetLastError());
     }
-    JpegEntropyArgs e;
-    e.coef = s->coef.as<int16_t>(); e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = n_int; e.first_int = (int)(((long long)(row0 / mcu) * mw) / interval);
-    e.last_marker = last ? 0 : 1; e.bpm = bpm; e.sizes = d_sizes; e.offs = d_offs; e.out = nullptr; e.cap = 0; e.err = d_err;
-    e.ipt = 0; e.plen = 0; memset(e.prefix, 0, sizeof(e.prefix));
+    const JpegEntropyArgs e = entropy_args(s, z.sizes, z.offs, z.err, (int)n_mcu, interval, n_int, (int)(((long long)(row0 / mcu) * mw) / interval), last ? 0 : 1, bpm, 0, nullptr, 0);
     unsigned long long total = 0;
     {
         ProfScope ps(ctx, "jpeg_encode.entropy");
         hipLaunchKernelGGL((k_jpeg_entropy<false, false>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
-        hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, ctx->stream, d_sizes, n_int, d_offs);
+        hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, ctx->stream, z.sizes, n_int, z.offs);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(&total, d_offs + n_int, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&total, z.offs + n_int, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *nbytes = (size_t)total;
     if (!out || cap < total) { vfsms_set_error("jpeg_encode: the band takes %llu bytes, the buffer holds %zu", total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
-    TRY(s->out.reserve(((size_t)total + 15) & ~(size_t)15, ctx->stream));
-    e.out = s->out.as<uint8_t>(); e.cap = s->out.bytes();
-    int err = 0;
-    {
-        ProfScope ps(ctx, "jpeg_encode.entropy");
-        HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL((k_jpeg_entropy<true, false>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
-        HIP_TRY(hipGetLastError());
-    }
-    {
-        ProfScope ps(ctx, "jpeg_encode.copy");
-        HIP_TRY(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out, s->out.as<uint8_t>(), (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (err) { vfsms_set_error("jpeg_encode: the coded band outgrew the %zu bytes counted for it", s->out.bytes()); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    return entropy_write<false>(ctx, s, e, total, out);
 }
 
 // ---- tile order: the JPEG tiles of a pyramidal TIFF (Method.pyramidCompression = "jpeg"; specified by tests/tiff_jpeg_ref.py) ---------------
@@ -538,13 +567,9 @@ int jpeg_tiles_count_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTileJob *j
     run->plen = jpeg_tile_prefix(tile, ch, restart_mcus, run->prefix);
 
     TRY(s->coef.reserve((size_t)n_mcu * bpm * 128, ctx->stream));
-    const size_t o_offs = ((size_t)n_int * 4 + 255) & ~(size_t)255, o_err = o_offs + ((size_t)n_int + 1) * 8;
-    const size_t o_toffs = (o_err + sizeof(int) + 255) & ~(size_t)255;
-    TRY(s->sizes.reserve(o_toffs + ((size_t)n_tiles + 1) * 8, ctx->stream));
-    run->d_sizes = s->sizes.as<uint32_t>();
-    run->d_offs = (unsigned long long *)(s->sizes.as<char>() + o_offs);
-    run->d_err = (int *)(s->sizes.as<char>() + o_err);
-    unsigned long long *d_toffs = (unsigned long long *)(s->sizes.as<char>() + o_toffs);
+    JpegSizes z;
+    TRY(sizes_carve(ctx, s, (size_t)n_int, (size_t)n_tiles, &z));
+    run->d_sizes = z.sizes; run->d_offs = z.offs; run->d_err = z.err;
 
     {
         ProfScope ps(ctx, "pyramid_jpeg.transform");
@@ -564,47 +589,25 @@ int jpeg_tiles_count_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTileJob *j
         }
         HIP_TRY(hipGetLastError());
     }
-    JpegEntropyArgs e;
-    e.coef = s->coef.as<int16_t>(); e.n_mcu = (int)n_mcu; e.interval = interval; e.n_int = (int)n_int; e.first_int = 0; e.last_marker = 0; e.bpm = bpm;
-    e.sizes = run->d_sizes; e.offs = run->d_offs; e.out = nullptr; e.cap = 0; e.err = run->d_err;
-    e.ipt = ipt; e.plen = run->plen; memset(e.prefix, 0, sizeof(e.prefix)); memcpy(e.prefix, run->prefix, (size_t)run->plen);
+    const JpegEntropyArgs e = entropy_args(s, z.sizes, z.offs, z.err, (int)n_mcu, interval, (int)n_int, 0, 0, bpm, ipt, run->prefix, run->plen);
     {
         ProfScope ps(ctx, "pyramid_jpeg.entropy");
         hipLaunchKernelGGL((k_jpeg_entropy<false, true>), dim3((unsigned)((n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
         hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(1024), 0, ctx->stream, run->d_sizes, (int)n_int, run->d_offs);
-        hipLaunchKernelGGL(k_jpeg_tile_offsets, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0, ctx->stream, run->d_offs, ipt, (int)n_tiles, d_toffs);
+        hipLaunchKernelGGL(k_jpeg_tile_offsets, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0, ctx->stream, run->d_offs, ipt, (int)n_tiles, z.toffs);
         HIP_TRY(hipGetLastError());
     }
     run->tile_offs.resize((size_t)n_tiles + 1);
-    HIP_TRY(hipMemcpyAsync(run->tile_offs.data(), d_toffs, ((size_t)n_tiles + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(run->tile_offs.data(), z.toffs, ((size_t)n_tiles + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (d_flag) HIP_TRY(hipMemcpyAsync(flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
 }
 
-// Writing half: the streams the counting half measured into `out` on the host (cap >= run->tile_offs[n_tiles], checked by the caller): one
-// writing pass, one copy.  Synchronises the stream.
+// Writing half: the streams the counting half measured into `out` on the host (cap >= run->tile_offs[n_tiles], checked by the caller).
+// Synchronises the stream.
 int jpeg_tiles_write_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTilesRun *run, uint8_t *out)
 {
-    const unsigned long long total = run->tile_offs[(size_t)run->n_tiles];
-    TRY(s->out.reserve(((size_t)total + 15) & ~(size_t)15, ctx->stream));
-    JpegEntropyArgs e;
-    e.coef = s->coef.as<int16_t>(); e.n_mcu = run->n_int * run->interval; e.interval = run->interval; e.n_int = run->n_int; e.first_int = 0; e.last_marker = 0;
-    e.bpm = run->bpm; e.sizes = run->d_sizes; e.offs = run->d_offs; e.out = s->out.as<uint8_t>(); e.cap = s->out.bytes(); e.err = run->d_err;
-    e.ipt = run->ipt; e.plen = run->plen; memset(e.prefix, 0, sizeof(e.prefix)); memcpy(e.prefix, run->prefix, (size_t)run->plen);
-    int err = 0;
-    {
-        ProfScope ps(ctx, "pyramid_jpeg.entropy");
-        HIP_TRY(hipMemsetAsync(run->d_err, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL((k_jpeg_entropy<true, true>), dim3((unsigned)((run->n_int + 63) / 64)), dim3(64), 0, ctx->stream, e);
-        HIP_TRY(hipGetLastError());
-    }
-    {
-        ProfScope ps(ctx, "pyramid_jpeg.copy");
-        HIP_TRY(hipMemcpyAsync(&err, run->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out, s->out.as<uint8_t>(), (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (err) { vfsms_set_error("jpeg tiles: the coded tiles outgrew the %zu bytes counted for them", s->out.bytes()); return VFSMS_ERR_CAPACITY; }
-    return VFSMS_OK;
+    const JpegEntropyArgs e = entropy_args(s, run->d_sizes, run->d_offs, run->d_err, run->n_int * run->interval, run->interval, run->n_int, 0, 0, run->bpm, run->ipt, run->prefix, run->plen);
+    return entropy_write<true>(ctx, s, e, run->tile_offs[(size_t)run->n_tiles], out);
 }

@@ -161,18 +161,21 @@ class Stitcher(Utility.Method):
         if "mosaicSink" in self.__dict__:                    # the user streams the mosaics somewhere else (stitcher.mosaicSink = NpyBandWriter(...)): leave it alone
             return None
         probe = pattern % 0 if pattern else paths[0]
+        state = {"f": None, "w": None, "n": 0}                  # the file or writer of the mosaic at work, the mosaics begun
+
+        def next_path():
+            path = (pattern % state["n"]) if pattern else paths[state["n"]]
+            if pattern:
+                paths.append(path)
+            state["n"] += 1
+            return path
         if self._deviceJpeg(os.path.splitext(probe)[1][1:]):
-            # jpegEncoder "device": the sink takes the bands' entropy-coded bytes, not their pixels (getStitchByOffset asks the engine for them)
-            state = {"f": None, "n": 0}
+            # jpegEncoder "device": the sink takes the bands' entropy-coded bytes, not their pixels (_writeOut asks the engine for them)
 
             def payload_sink(row0, nrows, payload, full_shape):
                 try:
                     if state["f"] is None:
-                        path = (pattern % state["n"]) if pattern else paths[state["n"]]
-                        if pattern:
-                            paths.append(path)
-                        state["n"] += 1
-                        state["f"] = DeviceJpegFile(path, full_shape, int(self.jpegQuality), int(self.jpegRestartMcus))
+                        state["f"] = DeviceJpegFile(next_path(), full_shape, int(self.jpegQuality), int(self.jpegRestartMcus))
                     state["f"].append(payload)
                     if row0 + nrows >= full_shape[0]:
                         state["f"].close()
@@ -190,26 +193,17 @@ class Stitcher(Utility.Method):
         first = band_writer_for(probe, **wkw)
         if first is None:
             return None
-        state = {"w": None, "n": 0}
 
         def sink(row0, band, full_shape, **lkw):
             if state["w"] is None:
-                path = (pattern % state["n"]) if pattern else paths[state["n"]]
-                if pattern:
-                    paths.append(path)
-                state["n"] += 1
-                state["w"] = band_writer_for(path, **wkw)
+                state["w"] = band_writer_for(next_path(), **wkw)
             state["w"](row0, band, full_shape, **lkw)
             if row0 + band.shape[0] >= full_shape[0]:
                 state["w"] = None
         def tiles(row0, nrows, payload, index, full_shape):
-            # pyramidCompression "jpeg": the bands' finished tile streams, not their pixels (getStitchByOffset asks the engine for them)
+            # pyramidCompression "jpeg": the bands' finished tile streams, not their pixels (_writeOut asks the engine for them)
             if state["w"] is None:
-                path = (pattern % state["n"]) if pattern else paths[state["n"]]
-                if pattern:
-                    paths.append(path)
-                state["n"] += 1
-                state["w"] = band_writer_for(path, **wkw)
+                state["w"] = band_writer_for(next_path(), **wkw)
             try:
                 state["w"].tiles(row0, nrows, payload, index, full_shape)
             except BaseException:
@@ -235,23 +229,44 @@ class Stitcher(Utility.Method):
             return False
         if "mosaicSink" in self.__dict__ and not getattr(self.__dict__["mosaicSink"], "device_jpeg", False):
             return False
-        if not hasattr(self.engine, "canvas_encode_jpeg_bands"):
-            raise NotImplementedError("jpegEncoder = 'device' needs an engine with canvas_encode_jpeg_bands")
+        self._routeNeeds("device_jpeg", "jpegEncoder = 'device'")
         if not 1 <= int(self.jpegQuality) <= 100:
             raise ValueError("jpegQuality must be 1..100, got %r" % (self.jpegQuality,))
         self._jpegBandRows()
         return True
 
+    # The four routes a fused canvas leaves the device by, and the engine method each needs.  A sink names its route: the flags `device_jpeg`
+    # (it takes entropy-coded bands) and `device_tiles` (finished tile streams), the method `pyramid_levels` (pixel bands with reduced levels)
+    _ROUTES = {"device_jpeg": "canvas_encode_jpeg_bands", "device_tiles": "canvas_encode_pyramid_tiles",
+               "pyramid_levels": "canvas_download_pyramid_bands", "plain": "canvas_download_bands"}
+
+    @staticmethod
+    def _routeOf(sink):
+        flagged = [route for route in ("device_jpeg", "device_tiles") if getattr(sink, route, False)]
+        return flagged[0] if flagged else "pyramid_levels" if hasattr(sink, "pyramid_levels") else "plain"
+
+    def _routeNeeds(self, route, what):
+        if not hasattr(self.engine, self._ROUTES[route]):
+            raise NotImplementedError("%s needs an engine with %s" % (what, self._ROUTES[route]))
+
+    def _bandRows(self, step=0, whose=None):
+        """Method.mosaicBandRows; with `step`, a positive multiple of it or ValueError: "<whose> mosaicBandRows to be a multiple of ..." """
+        band_rows = int(getattr(self, "mosaicBandRows", 4096))
+        if step and (band_rows <= 0 or band_rows % step):
+            raise ValueError("%s mosaicBandRows to be a multiple of %d, got %d" % (whose, step, band_rows))
+        return band_rows
+
     def _jpegBandRows(self):
         """mosaicBandRows for the device's JPEG encoder: every band must be whole restart intervals whatever the mosaic's width, so it is a
         multiple of the MCU height (16 rows in colour, 8 in gray) times jpegRestartMcus"""
-        band_rows, R = int(getattr(self, "mosaicBandRows", 4096)), int(self.jpegRestartMcus)
+        R = int(self.jpegRestartMcus)
         if not 1 <= R <= 65535:
             raise ValueError("jpegRestartMcus must be 1..65535, got %r" % (self.jpegRestartMcus,))
-        step = (16 if self.isColorMode else 8) * R
-        if band_rows <= 0 or band_rows % step:
-            raise ValueError("restart intervals of %d MCUs need mosaicBandRows to be a multiple of %d, got %d" % (R, step, band_rows))
-        return band_rows
+        return self._bandRows((16 if self.isColorMode else 8) * R, "restart intervals of %d MCUs need" % R)
+
+    def _pyramidBandRows(self, levels):
+        """mosaicBandRows for a pyramid of `levels` reduced levels: every band must form complete rows of every level"""
+        return self._bandRows(1 << levels, "a pyramid of %d reduced levels needs" % levels)
 
     def _pyramidOptions(self):
         """Method.pyramid* as PyramidTiffBandWriter's keyword arguments"""
@@ -267,26 +282,15 @@ class Stitcher(Utility.Method):
         if not self.streamOutput:
             raise ValueError("outputPyramid needs streamOutput: the levels are formed from the bands as they leave the device")
         jpeg = self.pyramidCompression == "jpeg"                 # the tiles are encoded on the device (csrc/jpeg_enc_kernels.hip in tile order)
-        need = "canvas_encode_pyramid_tiles" if jpeg else "canvas_download_pyramid_bands"
-        if not hasattr(self.engine, need):
-            raise NotImplementedError("outputPyramid%s needs an engine with %s" % (" with pyramidCompression = 'jpeg'" if jpeg else "", need))
+        self._routeNeeds("device_tiles" if jpeg else "pyramid_levels", "outputPyramid" + (" with pyramidCompression = 'jpeg'" if jpeg else ""))
         writer = PyramidTiffBandWriter("", **self._pyramidOptions())       # (pyramidTile, pyramidLevels, pyramidCompression, jpegQuality, jpegRestartMcus: the writer's own refusals)
         if jpeg:
             if "mosaicSink" in self.__dict__:
                 raise ValueError("pyramidCompression = 'jpeg' writes the tile streams the device encodes; a mosaicSink of the user's takes pixel bands")
             writer.check_jpeg_geometry(3 if self.isColorMode else 1)
-            band_rows = int(getattr(self, "mosaicBandRows", 4096))
-            if band_rows <= 0 or band_rows % writer.tile:
-                raise ValueError("JPEG tiles of %d rows need mosaicBandRows to be a multiple of %d, got %d" % (writer.tile, writer.tile, band_rows))
+            self._bandRows(writer.tile, "JPEG tiles of %d rows need" % writer.tile)
         if self.pyramidLevels is not None:
             self._pyramidBandRows(int(self.pyramidLevels))
-
-    def _pyramidBandRows(self, levels):
-        """mosaicBandRows for a pyramid of `levels` reduced levels: every band must form complete rows of every level"""
-        band_rows = int(getattr(self, "mosaicBandRows", 4096))
-        if band_rows <= 0 or band_rows % (1 << levels):
-            raise ValueError("a pyramid of %d reduced levels needs mosaicBandRows to be a multiple of %d, got %d" % (levels, 1 << levels, band_rows))
-        return band_rows
 
     def _pyramidLevelsOf(self, full_shape):
         """how many reduced levels the installed mosaicSink wants with every band of a mosaic of `full_shape` (a sink with `pyramid_levels`:
@@ -294,9 +298,7 @@ class Stitcher(Utility.Method):
         sink = getattr(self, "mosaicSink", None)
         if sink is None or not hasattr(sink, "pyramid_levels"):
             return None
-        need = "canvas_encode_pyramid_tiles" if getattr(sink, "device_tiles", False) else "canvas_download_pyramid_bands"
-        if not hasattr(self.engine, need):
-            raise NotImplementedError("a mosaicSink with pyramid_levels needs an engine with %s" % need)
+        self._routeNeeds(self._routeOf(sink), "a mosaicSink with pyramid_levels")
         levels = int(sink.pyramid_levels(full_shape))
         self._pyramidBandRows(levels)
         return levels
@@ -1079,38 +1081,7 @@ class Stitcher(Utility.Method):
                         self._placeTile(eng, canvas, handles[i] if use_res else imageList[i], use_res, rows[i])
                 if one_call:
                     eng.canvas_assemble_resident(canvas, handles, rows)
-                sink = getattr(self, "mosaicSink", None)
-                if sink is not None and getattr(sink, "device_jpeg", False):
-                    # jpegEncoder "device": the bands leave as their entropy-coded bytes (csrc/jpeg_enc_kernels.hip); the sink appends them
-                    for r0, nr, payload in eng.canvas_encode_jpeg_bands(canvas, resultRow, resultCol, ch, int(self.jpegQuality),
-                                                                        int(self.jpegRestartMcus), self._jpegBandRows()):
-                        sink(r0, nr, payload, full_shape)
-                    return None
-                if sink is not None and getattr(sink, "device_tiles", False):
-                    # pyramidCompression "jpeg": every band leaves as the finished tile streams of level 0 and of the reduced levels it
-                    # completes (a mosaic that fits one tile: zero reduced levels); the sink appends them
-                    for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, resultRow, resultCol, ch, pyramid or 0, int(self.pyramidTile),
-                                                                                  int(self.jpegQuality), int(self.jpegRestartMcus),
-                                                                                  int(getattr(self, "mosaicBandRows", 4096))):
-                        sink.tiles(r0, nr, payload, index, full_shape)
-                    return None
-                if sink is not None and hasattr(eng, "canvas_download_bands"):
-                    # streamed write-out: the mosaic leaves the device band by band and is never whole in host memory
-                    # (a sink that is done with a band two bands later -- `transient_bands`: JpegBandWriter -- gets views of the engine's
-                    #  pinned band ring instead of a fresh array per band: a DMA at link speed, no page faults of a fresh 300 MB array per
-                    #  band; VFSMS_PINNED_BANDS=0 turns it off)
-                    transient = bool(getattr(sink, "transient_bands", False)) and os.environ.get("VFSMS_PINNED_BANDS", "1") == "1"
-                    kw = {"transient": True} if transient else {}
-                    band_rows = int(getattr(self, "mosaicBandRows", 4096))
-                    if pyramid:                                  # a pyramidal sink: every band with its reduced levels, formed on the device
-                        for r0, band, levels in eng.canvas_download_pyramid_bands(canvas, resultRow, resultCol, ch, pyramid, band_rows, **kw):
-                            sink(r0, band, full_shape, levels=levels)
-                        return None
-                    lkw = {"levels": []} if pyramid is not None else {}     # (a mosaic that fits one tile: a pyramid of level 0 alone)
-                    for r0, band in eng.canvas_download_bands(canvas, resultRow, resultCol, ch, band_rows, **kw):
-                        sink(r0, band, full_shape, **lkw)
-                    return None
-                return eng.canvas_download(canvas, resultRow, resultCol, ch)
+                return self._writeOut(eng, canvas, full_shape, pyramid)
             finally:
                 eng.canvas_free(canvas)
         finally:
@@ -1118,6 +1089,36 @@ class Stitcher(Utility.Method):
                 eng.sync_uploads()                           # the host tiles of asynchronous uploads may be released now
             for h, _shape in resident.values():
                 eng.tile_free(h)
+
+    def _writeOut(self, eng, canvas, full_shape, pyramid):
+        """the fused canvas out of the device by the route of the installed mosaicSink (_routeOf), band by band -- the mosaic is never whole
+        in host memory -- or whole, as the array returned, when there is no sink.  pyramid: _pyramidLevelsOf(full_shape)"""
+        rows, cols, ch = full_shape[0], full_shape[1], full_shape[2] if len(full_shape) > 2 else 1
+        sink = getattr(self, "mosaicSink", None)
+        route = self._routeOf(sink) if sink is not None else None
+        if route == "device_jpeg":                               # the sink appends the bands' entropy-coded bytes (csrc/jpeg_enc_kernels.hip)
+            for r0, nr, payload in eng.canvas_encode_jpeg_bands(canvas, rows, cols, ch, int(self.jpegQuality), int(self.jpegRestartMcus), self._jpegBandRows()):
+                sink(r0, nr, payload, full_shape)
+        elif route == "device_tiles":
+            # the finished tile streams of level 0 and of the reduced levels a band completes (a mosaic that fits one tile: zero reduced levels)
+            for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), int(self.jpegQuality),
+                                                                          int(self.jpegRestartMcus), self._bandRows()):
+                sink.tiles(r0, nr, payload, index, full_shape)
+        elif sink is not None and hasattr(eng, self._ROUTES["plain"]):
+            # pixel bands.  A sink that is done with a band two bands later (`transient_bands`: JpegBandWriter) gets views of the engine's pinned
+            # band ring: a DMA at link speed, no page faults of a fresh 300 MB array per band; VFSMS_PINNED_BANDS=0 turns it off
+            transient = bool(getattr(sink, "transient_bands", False)) and os.environ.get("VFSMS_PINNED_BANDS", "1") == "1"
+            kw = {"transient": True} if transient else {}
+            if pyramid:                                          # a pyramidal sink: every band with its reduced levels, formed on the device
+                for r0, band, levels in eng.canvas_download_pyramid_bands(canvas, rows, cols, ch, pyramid, self._bandRows(), **kw):
+                    sink(r0, band, full_shape, levels=levels)
+            else:
+                lkw = {"levels": []} if pyramid is not None else {}     # (a mosaic that fits one tile: a pyramid of level 0 alone)
+                for r0, band in eng.canvas_download_bands(canvas, rows, cols, ch, self._bandRows(), **kw):
+                    sink(r0, band, full_shape, **lkw)
+        else:
+            return eng.canvas_download(canvas, rows, cols, ch)
+        return None
 
     def _correctShading(self, handles, shapes):
         """Method.shadingCorrection on the mosaic's resident tiles, in place (tests/shading_ref.py): a field estimated over exactly these

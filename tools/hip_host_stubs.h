@@ -1,10 +1,11 @@
-// hip_host_stubs.h -- the HIP runtime calls behind csrc/device_buf.h and csrc/ingest_fill.h, defined over malloc / free / memcpy for the
-// sanitizer-built host checks (device_buf_host_check.cpp, arena_layout_host_check.cpp, ingest_fill_host_check.cpp): no GPU, no HIP runtime
+// hip_host_stubs.h -- the HIP runtime calls behind csrc/device_buf.h, csrc/ingest_fill.h and csrc/canvas_band.h, defined over malloc / free /
+// memcpy for the sanitizer-built host checks (device_buf_host_check.cpp, arena_layout_host_check.cpp, ingest_fill_host_check.cpp,
+// canvas_band_host_check.cpp): no GPU, no HIP runtime
 // at work, and ASan / LeakSanitizer see every "device" allocation and every "copy".  Include it in exactly one translation unit of a program.
 // Every call is logged (`sync(stream)`, `free(ptr)`, `malloc(n)`, `copy(dst)`, `record(event)`, `wait(event)`, ...), live allocations and
 // events are counted, and two injections make calls fail (a failing call is logged all the same): fail_at = N, the N-th allocation of either
-// kind from now; fail_call(kind, N), the N-th call of that kind from now -- "hipMalloc", "hipHostMalloc", "copy", "record", "wait",
-// "event_create".  A failed call leaves the runtime's sticky error behind until hipGetLastError takes it.
+// kind from now; fail_call(kind, N), the N-th call of that kind from now -- "hipMalloc", "hipHostMalloc", "copy", "sync", "record",
+// "wait", "event_create".  A failed call leaves the runtime's sticky error behind until hipGetLastError takes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
