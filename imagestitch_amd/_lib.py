@@ -191,6 +191,10 @@ _SIGNATURES = {
                                                  C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
     "vfsms_canvas_encode_pyramid_tiles": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vfsms_deflate_encode_tiles_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                    C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
+    "vfsms_canvas_encode_pyramid_tiles_deflate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                            C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_tile_upload_ch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -1303,6 +1307,49 @@ class Engine:
                                          lambda out: self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, out, index[0]),
                                          self._encode_ring()[slot], grown)
             yield r0, n, out[:need], index[0][:ni]
+
+    def deflate_encode_tiles_device(self, img, tile, bgr=True):
+        """vfsms_deflate_encode_tiles_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload
+        u8, offsets uint64 [n_tiles + 1]): the zlib streams (TIFF predictor 2, colour stored R G B, zero padding) of the image's tile x tile
+        tiles, row-major and back to back -- tests/deflate_ref.py's tile_streams.  Tile t is payload[offsets[t]:offsets[t + 1]]."""
+        img, h, w, ch = self._u8_image(img, "deflate_encode_tiles_device")
+        T = max(int(tile), 1)
+        offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
+        n = C.c_size_t()
+        call = lambda out: (self._capacity_or(self.lib.vfsms_deflate_encode_tiles_device(
+            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile),
+            _ptr(out), out.size, C.byref(n), _ptr(offsets), offsets.size)), n.value)
+        out, size = self._fitted("deflate_encode_tiles_device", "tiles", call, np.empty(max(1 << 16, h * w * ch), np.uint8), lambda need: np.empty(need, np.uint8))
+        return out[:size], offsets
+
+    def canvas_encode_pyramid_tiles_deflate_rows(self, handle, row0, nrows, levels, tile, out, index):
+        """one vfsms_canvas_encode_pyramid_tiles_deflate call into the u8 vector `out` and the int64 (n, 4) array `index` -> (return code, bytes
+        needed, records needed); VFSMS_ERR_CAPACITY is returned, not raised (nothing was written or consumed: call again with room)"""
+        n, ni = C.c_size_t(), C.c_int()
+        rc = self.lib.vfsms_canvas_encode_pyramid_tiles_deflate(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(levels), int(tile),
+                                                                _ptr(out), C.c_size_t(out.size), C.byref(n), _ptr(index), len(index), C.byref(ni))
+        return self._capacity_or(rc), n.value, ni.value
+
+    def canvas_encode_pyramid_tiles_deflate(self, handle, rows, cols, ch, levels, tile, band_rows):
+        """Generator of (row0, nrows, bytes-view, index) over the whole mosaic, as canvas_encode_pyramid_tiles yields them, with the lossless
+        coder (vfsms_canvas_encode_pyramid_tiles_deflate): the finished zlib tile streams of level 0 and of reduced levels 1 .. levels that
+        every band completes -- what PyramidTiffBandWriter(compression="deflate-device").tiles takes.  band_rows must be a multiple of the
+        tile and of 2^levels.  The views belong to the same ring of BAND_RING pinned buffers."""
+        rows, cols, ch, levels, tile, band_rows = int(rows), int(cols), int(ch), int(levels), int(tile), int(band_rows)
+        if tile <= 0 or band_rows <= 0 or band_rows % tile or band_rows % (1 << levels):
+            raise ValueError("canvas_encode_pyramid_tiles_deflate: band_rows = %d is not a positive multiple of the tile = %d and of 2^levels = %d" % (band_rows, tile, 1 << levels))
+        for k, r0, n in self._bands(rows, band_rows):
+            slot = k % self.BAND_RING
+            index = [np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)]
+
+            def grown(need, ni):
+                index[0] = np.empty((ni, 4), np.int64)
+                return self._encode_ring(need)[slot]
+            out, need, ni = self._fitted("canvas_encode_pyramid_tiles_deflate", "band",
+                                         lambda out: self.canvas_encode_pyramid_tiles_deflate_rows(handle, r0, n, levels, tile, out, index[0]),
+                                         self._encode_ring()[slot], grown)
+            yield r0, n, out[:need], index[0][:ni]
+
 
 
 _default_engine = None

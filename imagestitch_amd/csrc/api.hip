@@ -2399,7 +2399,7 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas,
     TRY(jpeg_check_tile_geometry(who, tile, cv->ch, quality, restart_mcus, &interval));
     TRY(canvas_band_check(who, nbytes && n_index, cv->rows, row0, nrows, {{1 << levels, "2^levels"}, {tile, "the tile"}}));
     PyrPending &P = cv->pend;
-    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream));
+    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream, VFSMS_PYR_CODEC_JPEG));
     PyrPlan plan;
     TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
     *n_index = (int)plan.n_tiles;
@@ -2416,6 +2416,71 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas,
     }
     TRY(P.commit(plan, ctx->stream));
     TRY(jpeg_tiles_write_device(ctx, &cv->jpeg, &run, out));
+    plan.index(run.tile_offs.data(), index);
+    return VFSMS_OK;
+}
+
+// ---- lossless tiles for pyramidal TIFF (Method.pyramidCompression = "deflate-device"; deflate_kernels.hip, specified by tests/deflate_ref.py) ------
+// A whole image on the host -> the zlib streams of its tile x tile tiles (TIFF predictor 2, then deflate restricted to runs at distance 1 and
+// one dynamic block a tile), row-major and back to back in `out`; offsets[0 .. n_tiles]: where every stream starts, the last being the total.
+// Colour is stored R G B (bgr != 0: the rows are B G R).  Samples beyond the last row or column are 0.  *nbytes = the size needed, also on
+// VFSMS_ERR_CAPACITY (nothing is written then)
+extern "C" int vfsms_deflate_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int tile,
+                                                 uint8_t *out, size_t cap, size_t *nbytes, uint64_t *offsets, int offsets_cap)
+{
+    CTX_ENTER(ctx);
+    const char *who = "deflate_encode_tiles_device";
+    if (!img || !nbytes || !offsets || h < 1 || w < 1) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    TRY(deflate_check_tile_geometry(who, tile, ch));
+    const long long tr = (h + tile - 1) / tile, n_tiles = tr * ((w + tile - 1) / tile);
+    if (n_tiles > 0x7fffffff) { vfsms_set_error("%s: %lld tiles are more than one call takes", who, n_tiles); return VFSMS_ERR_BAD_ARG; }
+    if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
+    size_t pitch = 0;
+    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
+    const JpegTileJob job = {ctx->jpeg_scratch.img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
+    DeflateScratch *s = &ctx->deflate_scratch;
+    DeflateTilesRun run;
+    TRY(deflate_tiles_count_device(ctx, s, &job, 1, ch, bgr != 0, tile, nullptr, nullptr, &run));
+    const unsigned long long total = run.tile_offs[(size_t)run.a.n_tiles];
+    *nbytes = (size_t)total;
+    if (!out || cap < total) { vfsms_set_error("%s: the tiles take %llu bytes, the buffer holds %zu", who, total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
+    TRY(deflate_tiles_write_device(ctx, s, &run, out));
+    for (int t = 0; t <= run.a.n_tiles; t++) offsets[t] = run.tile_offs[(size_t)t];
+    return VFSMS_OK;
+}
+
+// vfsms_canvas_encode_pyramid_tiles with the lossless coder: the same band contract, index records and capacity behaviour (on
+// VFSMS_ERR_CAPACITY nothing is consumed and the band may be repeated), over the same walk of the canvas's pending rows.  A walk belongs to
+// the coder that started it at row0 = 0: a band of this entry that continues a walk of the JPEG entry -- or the reverse -- is refused with
+// VFSMS_ERR_BAD_ARG and the walk stays as it was.  The canvas is B G R; the tiles are stored R G B, zero beyond a level's last row and column
+extern "C" int vfsms_canvas_encode_pyramid_tiles_deflate(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile,
+                                                         uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index)
+{
+    CTX_ENTER(ctx);
+    const char *who = "canvas_encode_pyramid_tiles_deflate";
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    if (levels < 0 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 0..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
+    TRY(deflate_check_tile_geometry(who, tile, cv->ch));
+    TRY(canvas_band_check(who, nbytes && n_index, cv->rows, row0, nrows, {{1 << levels, "2^levels"}, {tile, "the tile"}}));
+    PyrPending &P = cv->pend;
+    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream, VFSMS_PYR_CODEC_DEFLATE));
+    PyrPlan plan;
+    TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
+    *n_index = (int)plan.n_tiles;
+    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, plan.lvl, "pyramid_deflate.levels"));
+    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
+    DeflateTilesRun run;
+    TRY(deflate_tiles_count_device(ctx, &cv->deflate, plan.jobs, plan.n_jobs, cv->ch, 1, tile, cv->d_err.as<int>(), &flag, &run));
+    TRY(canvas_flag_verdict(flag));
+    const unsigned long long bytes = run.tile_offs[(size_t)run.a.n_tiles];
+    *nbytes = (size_t)bytes;
+    if (!out || cap < bytes || !index || index_cap < plan.n_tiles) {              // nothing is consumed: the same band may come again
+        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, plan.n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
+        return VFSMS_ERR_CAPACITY;
+    }
+    TRY(P.commit(plan, ctx->stream));                              // (the predicted bytes in scratch hold everything the streams need)
+    TRY(deflate_tiles_write_device(ctx, &cv->deflate, &run, out));
     plan.index(run.tile_offs.data(), index);
     return VFSMS_OK;
 }

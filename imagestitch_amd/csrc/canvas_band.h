@@ -1,5 +1,5 @@
 // canvas_band.h -- the band walk behind the four write-out routes of a canvas (vfsms_canvas_download_rows, .._download_rows_pyramid,
-// .._encode_jpeg_rows, .._encode_pyramid_tiles of api.hip): the one band check, the one reader of the sticky geometry flag, and the
+// .._encode_jpeg_rows, .._encode_pyramid_tiles and its lossless twin .._encode_pyramid_tiles_deflate of api.hip): the one band check, the one reader of the sticky geometry flag, and the
 // operations of PyrPending, the rows of the reduced levels that wait between the bands of the tile route.  Host C++ over common.h and the
 // runtime API, no kernels, no launchers: libvfsms and tools/canvas_band_host_check.cpp (host sanitizers, failures injected) compile the
 // same lines.
@@ -74,9 +74,9 @@ struct PyrPlan {
 };
 
 // A band at row 0 starts a walk: nothing is pending, the buffer is sized for this band.  Any other band continues one: it is the band
-// expected, with the walk's tile and level count, or it is refused and the state stays as it was; a longer band than the buffer was sized
+// expected, with the walk's coder, tile and level count, or it is refused and the state stays as it was; a longer band than the buffer was sized
 // for makes a larger buffer take the pending rows over (the record owns the old buffer with the old slots until the new one holds them)
-inline int PyrPending::begin(const char *who, int rows, int cols, int ch_, int row0, int nrows, int tile_, int levels_, hipStream_t stream)
+inline int PyrPending::begin(const char *who, int rows, int cols, int ch_, int row0, int nrows, int tile_, int levels_, hipStream_t stream, int codec_)
 {
     if (row0 == 0) {
         levels = -1;                                              // (no walk to continue if the buffer cannot be had)
@@ -84,7 +84,10 @@ inline int PyrPending::begin(const char *who, int rows, int cols, int ch_, int r
         for (int k = 1; k <= VFSMS_PYRAMID_MAX_LEVELS; k++) { R[k] = (R[k - 1] + 1) >> 1; C[k] = (C[k - 1] + 1) >> 1; }
         TRY(buf.reserve(pyr_pending_layout(C, ch, tile_, levels_, nrows, off), stream));
         for (int k = 1; k <= levels_; k++) base[k] = have[k] = 0;
-        tile = tile_; levels = levels_; band = nrows; next = 0;
+        tile = tile_; levels = levels_; band = nrows; next = 0; codec = codec_;
+    } else if (levels >= 0 && codec != codec_) {
+        vfsms_set_error("%s: the walk in progress feeds the %s coder: a band of the other coder continues no walk (row0 = 0 starts one)", who, codec == VFSMS_PYR_CODEC_DEFLATE ? "deflate" : "JPEG");
+        return VFSMS_ERR_BAD_ARG;
     } else if (tile != tile_ || levels != levels_ || next != row0) {
         vfsms_set_error("%s: bands arrive in order from row 0 with one tile and level count (expected row0 = %d, got %d)", who, levels < 0 ? 0 : next, row0);
         return VFSMS_ERR_BAD_ARG;

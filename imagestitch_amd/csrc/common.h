@@ -171,20 +171,39 @@ struct JpegScratch { DevBuf coef, sizes, out, img; };
 struct JpegTileJob { const uint8_t *src; size_t src_bytes, pitch; int src_row0, rows, cols, row0, tile_rows; };
 // what the counting half of a tile-order encode leaves for the writing half; tile_offs[0 .. n_tiles]: the tiles' offsets in the payload
 struct JpegTilesRun { int n_tiles, n_int, ipt, interval, bpm, plen; uint8_t prefix[44]; uint32_t *d_sizes; unsigned long long *d_offs; int *d_err; std::vector<unsigned long long> tile_offs; };
+// device scratch of the lossless tile coder (deflate_kernels.hip), grown to the largest call seen: the predicted bytes of the call's tiles, the
+// records per tile and per chunk (DflArgs' arrays), the coded streams
+struct DeflateScratch { DevBuf pred, meta, out; };
+// the tile rows of one level as the kernels see them (JpegTileJob's fields; ntx tiles a row, first_tile: its first tile among the call's)
+struct DflJobDev { const uint8_t *src; unsigned long long src_bytes, pitch; int src_row0, rows, cols, row0, ntx; long long first_tile; };
+// one call of the coder: n_tiles tiles of `nbytes` = tile x tile x ch bytes in `nchunks` chunks each.  Per tile: adler (the two sums), hist
+// (288 a tile), lens (288 a tile), table (288 a tile), sizes / offs (the streams' bytes and where they start, offs[n_tiles] the total), eob (the
+// bit of the stream at which the end-of-block code starts).  Per chunk: bounds (its first and last run boundary), reach (the last boundary in
+// front of it, the first behind it), chunk_bits (its tokens' bits, then where they start among the tile's).  out: the payload in words
+struct DflArgs {
+    DflJobDev job[VFSMS_PYRAMID_MAX_LEVELS + 1]; int n_jobs, tile, ch, bgr, nbytes, nchunks, n_tiles;
+    uint8_t *pred; int2 *bounds, *reach; uint32_t *adler, *hist; uint8_t *lens; uint32_t *table, *sizes; unsigned long long *offs, *eob;
+    uint32_t *chunk_bits; uint32_t *out; unsigned long long out_words; int *err;
+};
+// what the counting half of a deflate call leaves for the writing half; tile_offs[0 .. n_tiles]: the tiles' offsets in the payload
+struct DeflateTilesRun { DflArgs a; std::vector<unsigned long long> tile_offs; };
+#define VFSMS_PYR_CODEC_JPEG 0
+#define VFSMS_PYR_CODEC_DEFLATE 1
 // the pending rows of levels 1 .. levels between the bands of vfsms_canvas_encode_pyramid_tiles: level k's rows [base[k], base[k] + have[k])
 // (fewer than a tile row of them) at buf + off[k], with room for the share of a band of `band` rows behind them; next: the row0 expected;
-// ch, R[k] x C[k]: the canvas's levels, set when a walk starts.  The operations are canvas_band.h's: begin -> plan -> commit per band
+// ch, R[k] x C[k]: the canvas's levels, and codec: the coder the walk feeds (VFSMS_PYR_CODEC_*; vfsms_canvas_encode_pyramid_tiles_deflate walks
+// the same state), set when a walk starts.  The operations are canvas_band.h's: begin -> plan -> commit per band
 struct PyrPlan;
 struct PyrPending {
     DevBuf buf; int tile = 0, levels = -1, band = 0, next = 0; int base[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, have[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}; size_t off[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
-    int ch = 0, R[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, C[VFSMS_PYRAMID_MAX_LEVELS + 1] = {};
-    int begin(const char *who, int rows, int cols, int ch, int row0, int nrows, int tile, int levels, hipStream_t stream);
+    int ch = 0, R[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, C[VFSMS_PYRAMID_MAX_LEVELS + 1] = {}, codec = VFSMS_PYR_CODEC_JPEG;
+    int begin(const char *who, int rows, int cols, int ch, int row0, int nrows, int tile, int levels, hipStream_t stream, int codec);
     int plan(const char *who, const uint8_t *pix, int row0, int nrows, PyrPlan *p) const;
     int commit(const PyrPlan &p, hipStream_t stream);
 };
 // move-only: the record owns its buffers wherever it lies (the canvas map, the context's spare slot, a canvas under construction); an
 // empty record owns nothing.  Destroying one frees without a synchronisation: api.hip's canvas_release synchronises first
-struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; PyrPending pend; };   // pend: the rows of the reduced levels that do not fill a tile row yet (vfsms_canvas_encode_pyramid_tiles; canvas_band.h has its operations and the band contract of all four write-out routes), sized at the band that starts a walk, grown by a longer band, released with the canvas; jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback, read with every band that leaves (canvas_flag_read / canvas_flag_verdict); scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
+struct CanvasRec { DevBuf pix, mask; int rows = 0, cols = 0, ch = 0; DevBuf d_err, scratch; std::vector<int32_t> placed; int mb_levels = 4; int seam_blend = 0; DevBuf pyr; JpegScratch jpeg; DeflateScratch deflate; PyrPending pend; };   // deflate: the lossless tile coder's scratch for the band being encoded (vfsms_canvas_encode_pyramid_tiles_deflate), allocated on first use, released with the canvas; pend: the rows of the reduced levels that do not fill a tile row yet (vfsms_canvas_encode_pyramid_tiles; canvas_band.h has its operations and the band contract of all four write-out routes), sized at the band that starts a walk, grown by a longer band, released with the canvas; jpeg: the encoder's scratch for the band being encoded (vfsms_canvas_encode_jpeg_rows), allocated on first use, released with the canvas; pyr: the reduced levels of the band being downloaded (vfsms_canvas_download_rows_pyramid), sized on first use; d_err: sticky "degenerate fuse geometry" flag for calls made without an info readback, read with every band that leaves (canvas_flag_read / canvas_flag_verdict); scratch: the fuse's statistics records + ramps; placed: (y0, x0, y1, x1) of every tile rectangle written so far = the canvas's validity (canvas_fuse_device counts the valid pixels of a ROI from it)
 struct FftPlan { int M, N, nb; void *fwd, *inv, *fwd_info, *inv_info; size_t fwd_work, inv_work; };   // rocfft_plan / rocfft_execution_info
 struct PhaseJobHost { const uint8_t *a, *b; int sa, sb; };
 struct PhasePeak { double v; long long idx; };                      // a peak of the correlation surface: value, row-major index in the ORIGINAL (untransposed) padded surface; idx < 0: absent
@@ -233,6 +252,7 @@ struct vfsms_ctx {
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
     size_t sift_group_bytes = (size_t)4 << 30;                     // pyramid bytes resident at once in a fused SIFT batch (VFSMS_SIFT_GROUP_BYTES overrides)
     JpegScratch jpeg_scratch;                                      // vfsms_jpeg_encode_device's scratch, freed with the context
+    DeflateScratch deflate_scratch;                                // vfsms_deflate_encode_tiles_device's scratch, freed with the context
     CanvasRec spare_canvas;                                  // (or an empty record) the buffers of the last canvas freed: a session's mosaics are of one size, and hipMalloc / hipFree of a canvas (28 GB at configs[4]) cost more than the walk
     std::unordered_map<int64_t, FeatRec> feats;
     std::unordered_map<int64_t, FeatBlock> feat_blocks;      // one allocation for the sets of a call (vfsms_features_surf, one set; vfsms_features_surf_batch, a chunk's), freed with its last set
@@ -413,6 +433,12 @@ int jpeg_tile_prefix(int tile, int ch, int restart_mcus, uint8_t *out);
 int jpeg_tiles_count_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTileJob *jobs, int n_jobs, int ch, int bgr, int tile, int quality, int restart_mcus,
                             int interval, const int *d_flag, int *flag, JpegTilesRun *run);
 int jpeg_tiles_write_device(vfsms_ctx *ctx, JpegScratch *s, const JpegTilesRun *run, uint8_t *out);
+// deflate_kernels.hip: the lossless tile coder (tests/deflate_ref.py; the coder's rules are csrc/deflate_core.h's): the refusals every entry
+// shares, and the two halves of a call, shaped as the JPEG tile route's
+int deflate_check_tile_geometry(const char *who, int tile, int ch);
+int deflate_tiles_count_device(vfsms_ctx *ctx, DeflateScratch *s, const JpegTileJob *jobs, int n_jobs, int ch, int bgr, int tile, const int *d_flag, int *flag,
+                               DeflateTilesRun *run);
+int deflate_tiles_write_device(vfsms_ctx *ctx, DeflateScratch *s, const DeflateTilesRun *run, uint8_t *out);
 // jpeg_host.cpp / jpeg_dec_kernels.hip: the device half of the JPEG decoder (tests/jpeg_dec_ref.py).  A component of one launch: its blocks
 // (64 int16 each, natural order, block-row-major on a grid `bcols` wide), its table (uint16[64], natural order), the plane it becomes (`rows`
 // x `cols` samples kept of the grid, `pitch` bytes apart) and the index of its first block among the launch's `total`

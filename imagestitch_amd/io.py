@@ -348,21 +348,27 @@ class PyramidTiffBandWriter:
     Engine.canvas_encode_pyramid_tiles hands them out -- encoded on the device at `quality` with `restart_mcus` MCUs per restart interval
     (0: one interval per tile), edge tiles replicating the level's last row and column -- appends the payload with one write and notes
     (offset, count) per tile from the index.  The tables go into JPEGTables once per directory; colour is Y Cb Cr 4:2:0 (Photometric 6).
-    There is no host encoder behind it: pixel bands are refused."""
+    There is no host encoder behind it: pixel bands are refused.
+
+    compression "deflate-device" (TIFF compression 8 with Predictor = 2, lossless; tests/deflate_ref.py) takes finished tile streams in the
+    same way -- Engine.canvas_encode_pyramid_tiles_deflate's, every tile a zlib stream of its horizontally differenced samples, coded on the
+    device -- with edge tiles padded with zeros: the decoded pages equal those of "none" and "deflate", padding included.  Colour is R G B
+    (Photometric 2); there are no tables to share; `quality` and `restart_mcus` play no part; pixel bands are refused."""
 
     transient_bands = True      # done with a band (and its levels) when the call returns
 
     def __init__(self, path, tile=512, levels=None, compression="none", force_big=False, quality=95, restart_mcus=8):
         if int(tile) <= 0 or int(tile) % 16:
             raise ValueError("PyramidTiffBandWriter: tile must be a positive multiple of 16 (TIFF 6.0, TileWidth), got %r" % (tile,))
-        if compression not in ("none", "deflate", "jpeg"):
-            raise ValueError("PyramidTiffBandWriter: compression must be 'none', 'deflate' or 'jpeg', got %r" % (compression,))
+        if compression not in ("none", "deflate", "jpeg", "deflate-device"):
+            raise ValueError("PyramidTiffBandWriter: compression must be 'none', 'deflate', 'jpeg' or 'deflate-device', got %r" % (compression,))
         if levels is not None and not 0 <= int(levels) <= PYRAMID_MAX_LEVELS:
             raise ValueError("PyramidTiffBandWriter: levels must be None or 0..%d, got %r" % (PYRAMID_MAX_LEVELS, levels))
         self.path, self.tile, self.levels, self.compression, self.force_big = path, int(tile), levels, compression, force_big
         self.quality, self.restart_mcus = int(quality), int(restart_mcus)
-        self.device_tiles = compression == "jpeg"                # the bands arrive as finished tile streams (`tiles`), not as pixels
-        if self.device_tiles:
+        self.device_tiles = compression in ("jpeg", "deflate-device")      # the bands arrive as finished tile streams (`tiles`), not as pixels
+        self.tile_codec = {"jpeg": "jpeg", "deflate-device": "deflate"}.get(compression)          # which coder of the engine makes them
+        if self.tile_codec == "jpeg":
             self.check_jpeg_geometry(3)                          # (what holds for colour's (tile / 16)^2 MCUs holds for gray's (tile / 8)^2)
         self._f = None
 
@@ -409,7 +415,7 @@ class PyramidTiffBandWriter:
         self._carry = [None] * (K + 1)
         self._rows_in = [0] * (K + 1)
         self._tiles = [[] for _ in range(K + 1)]                 # (offset, byte count) per tile, row-major
-        if self.device_tiles:
+        if self.tile_codec == "jpeg":
             from . import _lib
             self.check_jpeg_geometry(self._ch)
             self._tables = _lib.tiff_jpeg_tables(self._ch, self.quality)
@@ -455,17 +461,19 @@ class PyramidTiffBandWriter:
         ltype, lfmt, lsize = (16, "Q", 8) if big else (4, "I", 4)
         field = 8 if big else 4
         fmts = {3: "H", 4: "I", 7: "B", 16: "Q"}
-        jpeg = self.device_tiles
+        jpeg = self.tile_codec == "jpeg"
         ifds = []
         for k, (rows, cols) in enumerate(self._sizes):
             n = len(self._tiles[k])
             assert n == -(-rows // self.tile) * -(-cols // self.tile), "level %d: %d tiles written" % (k, n)
             tags = [(254, 4, [1 if k else 0]), (256, ltype, [cols]), (257, ltype, [rows]), (258, 3, [8] * ch),
-                    (259, 3, [7 if jpeg else 8 if self.compression == "deflate" else 1]), (262, 3, [1 if ch == 1 else 6 if jpeg else 2]), (277, 3, [ch]),
+                    (259, 3, [7 if jpeg else 8 if self.compression in ("deflate", "deflate-device") else 1]), (262, 3, [1 if ch == 1 else 6 if jpeg else 2]), (277, 3, [ch]),
                     (284, 3, [1]), (322, ltype, [self.tile]), (323, ltype, [self.tile]), (324, ltype, [o for o, _c in self._tiles[k]]),
                     (325, ltype, [c for _o, c in self._tiles[k]])]
             if jpeg:                                             # JPEGTables (UNDEFINED bytes); YCbCrSubSampling 2, 2: the coder's 4:2:0
                 tags += [(347, 7, list(self._tables))] + ([(530, 3, [2, 2])] if ch == 3 else [])
+            if self.tile_codec == "deflate":                     # Predictor 2: horizontal differencing, undone by the reader per tile row
+                tags.insert(8, (317, 3, [2]))                  # (directory entries ascend by tag: between 284 and 322)
             entries = []
             for tag, ty, vals in tags:
                 data = struct.pack("<%d%s" % (len(vals), fmts[ty]), *vals)
@@ -504,11 +512,11 @@ class PyramidTiffBandWriter:
             os.remove(self._part)
 
     def tiles(self, row0, nrows, payload, index, full_shape):
-        """compression "jpeg": the tile streams that the band [row0, row0 + nrows) completes (Engine.canvas_encode_pyramid_tiles): `payload`
-        holds them back to back, `index` is (n, 4) integers (level, tile number in the level, offset in payload, bytes) in file order"""
+        """compression "jpeg" or "deflate-device": the tile streams that the band [row0, row0 + nrows) completes
+        (Engine.canvas_encode_pyramid_tiles, .._deflate): `payload` holds them back to back, `index` is (n, 4) integers (level, tile number in the level, offset in payload, bytes) in file order"""
         try:
             if not self.device_tiles:
-                raise ValueError("PyramidTiffBandWriter: tile streams go to compression 'jpeg', this writer's is %r" % (self.compression,))
+                raise ValueError("PyramidTiffBandWriter: tile streams go to compression 'jpeg' or 'deflate-device', this writer's is %r" % (self.compression,))
             if self._f is None:
                 self._open(full_shape, self.pyramid_levels(full_shape))
             if row0 != self._rows_in[0] or nrows <= 0 or row0 + nrows > self._sizes[0][0]:
@@ -531,7 +539,7 @@ class PyramidTiffBandWriter:
         levels = list(levels) if levels is not None else []
         try:
             if self.device_tiles:
-                raise ValueError("PyramidTiffBandWriter: compression 'jpeg' takes finished tile streams (tiles), there is no host encoder for pixel bands")
+                raise ValueError("PyramidTiffBandWriter: compression %r takes finished tile streams (tiles), there is no host encoder for pixel bands" % (self.compression,))
             if self._f is None:
                 K = self.pyramid_levels(full_shape)
                 if len(levels) != K:

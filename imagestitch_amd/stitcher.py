@@ -201,7 +201,7 @@ class Stitcher(Utility.Method):
             if row0 + band.shape[0] >= full_shape[0]:
                 state["w"] = None
         def tiles(row0, nrows, payload, index, full_shape):
-            # pyramidCompression "jpeg": the bands' finished tile streams, not their pixels (_writeOut asks the engine for them)
+            # pyramidCompression "jpeg" / "deflate-device": the bands' finished tile streams, not their pixels (_writeOut asks the engine for them)
             if state["w"] is None:
                 state["w"] = band_writer_for(next_path(), **wkw)
             try:
@@ -215,7 +215,7 @@ class Stitcher(Utility.Method):
         if hasattr(first, "pyramid_levels"):
             sink.pyramid_levels = first.pyramid_levels
         if getattr(first, "device_tiles", False):
-            sink.device_tiles, sink.tiles = True, tiles
+            sink.device_tiles, sink.tiles, sink.tile_codec = True, tiles, getattr(first, "tile_codec", "jpeg")
         self.mosaicSink = sink
         return sink
 
@@ -235,14 +235,18 @@ class Stitcher(Utility.Method):
         self._jpegBandRows()
         return True
 
-    # The four routes a fused canvas leaves the device by, and the engine method each needs.  A sink names its route: the flags `device_jpeg`
-    # (it takes entropy-coded bands) and `device_tiles` (finished tile streams), the method `pyramid_levels` (pixel bands with reduced levels)
+    # The routes a fused canvas leaves the device by, and the engine method each needs.  A sink names its route: the flags `device_jpeg`
+    # (it takes entropy-coded bands) and `device_tiles` (finished tile streams: JPEG's, or with `tile_codec` "deflate" the lossless coder's,
+    # route "device_tiles_deflate"), the method `pyramid_levels` (pixel bands with reduced levels)
     _ROUTES = {"device_jpeg": "canvas_encode_jpeg_bands", "device_tiles": "canvas_encode_pyramid_tiles",
+               "device_tiles_deflate": "canvas_encode_pyramid_tiles_deflate",
                "pyramid_levels": "canvas_download_pyramid_bands", "plain": "canvas_download_bands"}
 
     @staticmethod
     def _routeOf(sink):
         flagged = [route for route in ("device_jpeg", "device_tiles") if getattr(sink, route, False)]
+        if flagged == ["device_tiles"] and getattr(sink, "tile_codec", "jpeg") == "deflate":
+            return "device_tiles_deflate"
         return flagged[0] if flagged else "pyramid_levels" if hasattr(sink, "pyramid_levels") else "plain"
 
     def _routeNeeds(self, route, what):
@@ -282,13 +286,16 @@ class Stitcher(Utility.Method):
         if not self.streamOutput:
             raise ValueError("outputPyramid needs streamOutput: the levels are formed from the bands as they leave the device")
         jpeg = self.pyramidCompression == "jpeg"                 # the tiles are encoded on the device (csrc/jpeg_enc_kernels.hip in tile order)
-        self._routeNeeds("device_tiles" if jpeg else "pyramid_levels", "outputPyramid" + (" with pyramidCompression = 'jpeg'" if jpeg else ""))
+        deflate = self.pyramidCompression == "deflate-device"    # likewise, losslessly (csrc/deflate_kernels.hip)
+        self._routeNeeds("device_tiles" if jpeg else "device_tiles_deflate" if deflate else "pyramid_levels",
+                         "outputPyramid" + (" with pyramidCompression = %r" % (self.pyramidCompression,) if jpeg or deflate else ""))
         writer = PyramidTiffBandWriter("", **self._pyramidOptions())       # (pyramidTile, pyramidLevels, pyramidCompression, jpegQuality, jpegRestartMcus: the writer's own refusals)
-        if jpeg:
+        if jpeg or deflate:
             if "mosaicSink" in self.__dict__:
-                raise ValueError("pyramidCompression = 'jpeg' writes the tile streams the device encodes; a mosaicSink of the user's takes pixel bands")
-            writer.check_jpeg_geometry(3 if self.isColorMode else 1)
-            self._bandRows(writer.tile, "JPEG tiles of %d rows need" % writer.tile)
+                raise ValueError("pyramidCompression = %r writes the tile streams the device encodes; a mosaicSink of the user's takes pixel bands" % (self.pyramidCompression,))
+            if jpeg:
+                writer.check_jpeg_geometry(3 if self.isColorMode else 1)
+            self._bandRows(writer.tile, "%s tiles of %d rows need" % ("JPEG" if jpeg else "deflate", writer.tile))
         if self.pyramidLevels is not None:
             self._pyramidBandRows(int(self.pyramidLevels))
 
@@ -1103,6 +1110,9 @@ class Stitcher(Utility.Method):
             # the finished tile streams of level 0 and of the reduced levels a band completes (a mosaic that fits one tile: zero reduced levels)
             for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), int(self.jpegQuality),
                                                                           int(self.jpegRestartMcus), self._bandRows()):
+                sink.tiles(r0, nr, payload, index, full_shape)
+        elif route == "device_tiles_deflate":                    # the same, from the lossless coder (csrc/deflate_kernels.hip)
+            for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles_deflate(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), self._bandRows()):
                 sink.tiles(r0, nr, payload, index, full_shape)
         elif sink is not None and hasattr(eng, self._ROUTES["plain"]):
             # pixel bands.  A sink that is done with a band two bands later (`transient_bands`: JpegBandWriter) gets views of the engine's pinned

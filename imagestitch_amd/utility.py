@@ -208,7 +208,11 @@ class Method():
     # order) at jpegQuality with jpegRestartMcus MCUs per restart interval (0: one interval per tile; the MCUs of a tile -- (pyramidTile /
     # 16)^2 in colour, (pyramidTile / 8)^2 in gray -- must be whole intervals); edge tiles repeat the level's last row and column instead
     # of padding with zeros; mosaicBandRows must also be a multiple of pyramidTile; there is no host encoder behind it, so a mosaicSink of
-    # the user's is refused.  Needs a .tif / .tiff output, streamOutput, and mosaicBandRows a multiple of 2^levels
+    # the user's is refused.  "deflate-device": the lossless counterpart -- TIFF compression 8 with Predictor 2, every tile a zlib stream
+    # coded on the device (csrc/deflate_kernels.hip, tests/deflate_ref.py: horizontal differencing, then deflate restricted to runs at
+    # distance 1 and one dynamic Huffman block a tile), so nothing crosses the link as pixels; the decoded pages equal those of "none" and
+    # "deflate", zero padding included; the same conditions as "jpeg" (mosaicBandRows a multiple of pyramidTile, no mosaicSink of the
+    # user's); jpegQuality and jpegRestartMcus play no part.  Needs a .tif / .tiff output, streamOutput, and mosaicBandRows a multiple of 2^levels
     outputPyramid = False
     pyramidTile = 512
     pyramidLevels = None

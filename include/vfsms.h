@@ -617,6 +617,24 @@ int vfsms_jpeg_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h, in
 int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile, int quality, int restart_mcus,
                                       uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index);
 
+/* ---- lossless tiles for pyramidal TIFF (Method.pyramidCompression = "deflate-device": TIFF compression 8 with Predictor = 2), encoded on the
+ * device in tile order.  Specification: tests/deflate_ref.py (on tests/pyramid_ref.py); bytes equal it exactly.  A tile's stream is a plain
+ * zlib stream of its tile x tile x ch samples after horizontal differencing: colour R G B, samples beyond the level's last row or column 0
+ * (as the "none" and "deflate" writers pad, unlike the JPEG tiles); deflate restricted to runs at distance 1 and one dynamic Huffman block.
+ * Refused everywhere (VFSMS_ERR_BAD_ARG): a tile that is no positive multiple of 16 or larger than 4096, channels other than 1 or 3, more
+ * tiles (2^31 - 1) or chunks of 4096 bytes (2^24 - 1) than one call takes.
+ * vfsms_deflate_encode_tiles_device: an image on the host (B G R with bgr != 0, else R G B; rows `stride` bytes apart) -> all its tile
+ * streams, row-major and back to back; offsets[0 .. n_tiles] (the last being the total; offsets_cap counts entries).  *nbytes = the size
+ * needed, also on VFSMS_ERR_CAPACITY.                                                                                                  */
+int vfsms_deflate_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int tile,
+                                      uint8_t *out, size_t cap, size_t *nbytes, uint64_t *offsets, int offsets_cap);
+/* vfsms_canvas_encode_pyramid_tiles with the lossless coder: the same band contract, index records and capacity behaviour (on
+ * VFSMS_ERR_CAPACITY nothing is written and no row consumed: repeat the call with room), over the same walk of a canvas.  A walk belongs
+ * to the entry that started it at row0 = 0: a band of one entry that continues a walk of the other is refused with VFSMS_ERR_BAD_ARG and
+ * the walk stays as it was; row0 = 0 starts over with either.                                                                          */
+int vfsms_canvas_encode_pyramid_tiles_deflate(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile,
+                                              uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index);
+
 /* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
  * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
 /* A shading field from n (1..4096) resident tiles of one shape and channel count (any row stride): per sample the k-th smallest byte

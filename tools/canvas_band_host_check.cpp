@@ -78,11 +78,11 @@ static int flag_checks()
 }
 
 // ---- PyrPending against the model -------------------------------------------------------------------------------------------------------------------
-struct State { const void *buf; size_t bytes; int tile, levels, band, next, base[ML + 1], have[ML + 1]; size_t off[ML + 1]; };
+struct State { const void *buf; size_t bytes; int tile, levels, band, next, codec, base[ML + 1], have[ML + 1]; size_t off[ML + 1]; };
 static State state_of(const PyrPending &P)
 {
     State s; memset(&s, 0, sizeof(s));
-    s.buf = P.buf.as<void>(); s.bytes = P.buf.bytes(); s.tile = P.tile; s.levels = P.levels; s.band = P.band; s.next = P.next;
+    s.buf = P.buf.as<void>(); s.bytes = P.buf.bytes(); s.tile = P.tile; s.levels = P.levels; s.band = P.band; s.next = P.next; s.codec = P.codec;
     for (int k = 0; k <= ML; k++) { s.base[k] = P.base[k]; s.have[k] = P.have[k]; s.off[k] = P.off[k]; }
     return s;
 }
@@ -121,9 +121,9 @@ static int walk(PyrPending &P, int rows, int cols, int ch, int tile, int levels,
         if (row0 > 0) {                                           // out of order, another tile, another level count: refused, nothing changes
             const State before = state_of(P);
             const long live = g_hip.live;
-            CHECK(P.begin("walk", rows, cols, ch, row0 + tile, nrows, tile, levels, STREAM) == VFSMS_ERR_BAD_ARG && strstr(g_err, "walk: bands arrive in order from row 0 with one tile and level count (expected row0 = "));
-            CHECK(P.begin("walk", rows, cols, ch, row0, nrows, 2 * tile, levels, STREAM) == VFSMS_ERR_BAD_ARG);
-            CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels + 1, STREAM) == VFSMS_ERR_BAD_ARG);
+            CHECK(P.begin("walk", rows, cols, ch, row0 + tile, nrows, tile, levels, STREAM, 0) == VFSMS_ERR_BAD_ARG && strstr(g_err, "walk: bands arrive in order from row 0 with one tile and level count (expected row0 = "));
+            CHECK(P.begin("walk", rows, cols, ch, row0, nrows, 2 * tile, levels, STREAM, 0) == VFSMS_ERR_BAD_ARG);
+            CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels + 1, STREAM, 0) == VFSMS_ERR_BAD_ARG);
             CHECK(same(before, state_of(P)) && live == g_hip.live);
             if (inject && !injected && nrows > P.band) {          // the grow: an allocation, a copy per level with pending rows, a synchronisation
                 int copies = 0;
@@ -131,7 +131,7 @@ static int walk(PyrPending &P, int rows, int cols, int ch, int tile, int levels,
                 CHECK(copies > 0);
                 for (int pos = 0; pos < copies + 2; pos++) {
                     if (pos == 0) g_hip.fail_at = 1; else if (pos <= copies) fail_call("copy", pos); else fail_call("sync", 1);
-                    CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM) == VFSMS_ERR_HIP);
+                    CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM, 0) == VFSMS_ERR_HIP);
                     CHECK(!g_hip.fail_kind && !g_hip.fail_at);                               // (the failure was the one injected)
                     CHECK(same(before, state_of(P)) && live == g_hip.live);                  // the old buffer with the old slots; the new one is gone
                     g_injections++;
@@ -140,7 +140,7 @@ static int walk(PyrPending &P, int rows, int cols, int ch, int tile, int levels,
             }
         }
         const State before = state_of(P);
-        CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM) == VFSMS_OK);
+        CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM, 0) == VFSMS_OK);
         if (row0 > 0 && nrows <= before.band) CHECK(same(before, state_of(P)));             // a band that fits changes nothing yet
         CHECK(P.band >= nrows && P.next == row0 && P.tile == tile && P.levels == levels);
         PyrPlan plan, again;
@@ -157,7 +157,7 @@ static int walk(PyrPending &P, int rows, int cols, int ch, int tile, int levels,
             for (int y = first; y < end; y++) for (size_t i = 0; i < pitch; i++) plan.lvl[k][(size_t)(y - first) * pitch + i] = pattern(k, y, i);
         }
         // a plan without a commit -- the capacity refusal -- and the same band again: the same plan
-        CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM) == VFSMS_OK && P.plan("walk", pix.data(), row0, nrows, &again) == VFSMS_OK);
+        CHECK(P.begin("walk", rows, cols, ch, row0, nrows, tile, levels, STREAM, 0) == VFSMS_OK && P.plan("walk", pix.data(), row0, nrows, &again) == VFSMS_OK);
         CHECK(same_plan(plan, again) && same(planned, state_of(P)));
         // the jobs name exactly the tile rows that are due, level after level, ascending, each once, and their rows are the model's
         int j = 0; long long n_tiles = 0;
@@ -208,20 +208,52 @@ static int start_failure()
     g_what = "start failure";
     PyrPending P;
     PyrPlan plan;
-    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM) == VFSMS_ERR_BAD_ARG);         // (a band in the middle before any walk began)
+    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM, 0) == VFSMS_ERR_BAD_ARG);         // (a band in the middle before any walk began)
     g_hip.fail_at = 1;
-    CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 3, STREAM) == VFSMS_ERR_HIP && !P.buf && P.levels == -1 && g_hip.live == 0);
-    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM) == VFSMS_ERR_BAD_ARG && strstr(g_err, "(expected row0 = 0, got 16)"));
-    CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 3, STREAM) == VFSMS_OK && P.plan("walk", nullptr, 0, 16, &plan) == VFSMS_OK && P.commit(plan, STREAM) == VFSMS_OK);
+    CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 3, STREAM, 0) == VFSMS_ERR_HIP && !P.buf && P.levels == -1 && g_hip.live == 0);
+    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM, 0) == VFSMS_ERR_BAD_ARG && strstr(g_err, "(expected row0 = 0, got 16)"));
+    CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 3, STREAM, 0) == VFSMS_OK && P.plan("walk", nullptr, 0, 16, &plan) == VFSMS_OK && P.commit(plan, STREAM) == VFSMS_OK);
     g_hip.fail_at = 1;                                            // a new walk whose larger buffer cannot be had ends the old one too
-    CHECK(P.begin("walk", 80, 17, 3, 0, 48, 16, 3, STREAM) == VFSMS_ERR_HIP && P.levels == -1);
-    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM) == VFSMS_ERR_BAD_ARG);
+    CHECK(P.begin("walk", 80, 17, 3, 0, 48, 16, 3, STREAM, 0) == VFSMS_ERR_HIP && P.levels == -1);
+    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 3, STREAM, 0) == VFSMS_ERR_BAD_ARG);
+    return 0;
+}
+
+// a walk belongs to the coder that started it: a band of the other coder -- the expected one in every other respect -- is refused with the
+// state as it was, in the middle of a walk and at its last band; row0 = 0 starts over with either
+static int codec_refusal()
+{
+    g_what = "codec refusal";
+    const int J = VFSMS_PYR_CODEC_JPEG, D = VFSMS_PYR_CODEC_DEFLATE;
+    for (int first : {J, D}) {
+        const int other = first == J ? D : J;
+        PyrPending P;
+        PyrPlan plan;
+        std::vector<uint8_t> pix((size_t)80 * 17 * 3);
+        CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 2, STREAM, first) == VFSMS_OK && P.codec == first);
+        CHECK(P.plan("walk", pix.data(), 0, 16, &plan) == VFSMS_OK && P.commit(plan, STREAM) == VFSMS_OK);
+        for (int row0 = 16; row0 < 80; row0 += 16) {
+            const State before = state_of(P);
+            const long live = g_hip.live;
+            g_err[0] = 0;
+            CHECK(P.begin("walk", 80, 17, 3, row0, 16, 16, 2, STREAM, other) == VFSMS_ERR_BAD_ARG);
+            CHECK(strstr(g_err, first == D ? "walk: the walk in progress feeds the deflate coder" : "walk: the walk in progress feeds the JPEG coder"));
+            CHECK(P.begin("walk", 80, 17, 3, row0, 48, 16, 2, STREAM, other) == VFSMS_ERR_BAD_ARG);       // (nor does it grow the buffer)
+            CHECK(same(before, state_of(P)) && live == g_hip.live);
+            CHECK(P.begin("walk", 80, 17, 3, row0, 16, 16, 2, STREAM, first) == VFSMS_OK);
+            CHECK(P.plan("walk", pix.data(), row0, 16, &plan) == VFSMS_OK && P.commit(plan, STREAM) == VFSMS_OK);
+        }
+        CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 2, STREAM, other) == VFSMS_OK && P.codec == other && P.next == 0);   // a new walk may change the coder
+        CHECK(P.begin("walk", 80, 17, 3, 0, 16, 16, 2, STREAM, first) == VFSMS_OK && P.codec == first);
+    }
+    PyrPending P;                                                 // no walk at all: the order text, whichever coder asks
+    CHECK(P.begin("walk", 80, 17, 3, 16, 16, 16, 2, STREAM, D) == VFSMS_ERR_BAD_ARG && strstr(g_err, "(expected row0 = 0, got 16)"));
     return 0;
 }
 
 static int run()
 {
-    if (band_check_checks() || flag_checks() || start_failure()) return 1;
+    if (band_check_checks() || flag_checks() || start_failure() || codec_refusal()) return 1;
     // the sweep: one record per canvas, walked again and again with another level count and band length, as a canvas that is written twice
     for (int rows = 1; rows <= 80; rows++) for (int cols : {1, 17, 40}) for (int ch : {1, 3}) {
         PyrPending P;
