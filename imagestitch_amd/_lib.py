@@ -195,6 +195,9 @@ _SIGNATURES = {
                                                     C.POINTER(C.c_size_t), C.c_void_p, C.c_int]),
     "vfsms_canvas_encode_pyramid_tiles_deflate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                             C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "vfsms_png_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "vfsms_canvas_encode_png_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "vfsms_tile_upload_ch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "vfsms_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -1350,6 +1353,39 @@ class Engine:
                                          self._encode_ring()[slot], grown)
             yield r0, n, out[:need], index[0][:ni]
 
+    def png_encode_device(self, img, segment_rows=16, bgr=True):
+        """vfsms_png_encode_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload u8, the
+        Adler-32 of the filtered bytes): the IDAT chunks of the image's segments of `segment_rows` rows, adaptively filtered and coded on the
+        device, CRC-32 included -- tests/png_ref.py's device_payload and band_adler.  imagestitch_amd.io.DevicePngFile makes a file of them."""
+        img, h, w, ch = self._u8_image(img, "png_encode_device")
+        n, adler = C.c_size_t(), C.c_uint32()
+        call = lambda out: (self._capacity_or(self.lib.vfsms_png_encode_device(
+            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(segment_rows),
+            _ptr(out), out.size, C.byref(n), C.byref(adler))), n.value)
+        out, size = self._fitted("png_encode_device", "chunks", call, np.empty(max(1 << 16, h * w * ch), np.uint8), lambda need: np.empty(need, np.uint8))
+        return out[:size], adler.value
+
+    def canvas_encode_png_rows(self, handle, row0, nrows, segment_rows, out):
+        """one vfsms_canvas_encode_png_rows call into the u8 vector `out` -> (return code, bytes needed, the band's Adler-32);
+        VFSMS_ERR_CAPACITY is returned, not raised (nothing was written: call again with room), any other error raises"""
+        n, adler = C.c_size_t(), C.c_uint32()
+        rc = self.lib.vfsms_canvas_encode_png_rows(self.ctx, C.c_int64(handle), int(row0), int(nrows), int(segment_rows),
+                                                   _ptr(out), C.c_size_t(out.size), C.byref(n), C.byref(adler))
+        return self._capacity_or(rc), n.value, adler.value
+
+    def canvas_encode_png_bands(self, handle, rows, cols, ch, segment_rows, band_rows):
+        """Generator of (row0, nrows, bytes-view, adler) over the whole mosaic: every band of `band_rows` rows as the IDAT chunks of its
+        segments (vfsms_canvas_encode_png_rows), filtered, coded and checksummed on the device, with the Adler-32 of the band's filtered bytes
+        -- what imagestitch_amd.io.DevicePngFile.append takes.  band_rows must be a multiple of segment_rows.  The views belong to the ring of
+        BAND_RING pinned buffers of the encode routes; a view is valid until BAND_RING - 1 further bands were asked for."""
+        rows, cols, ch, segment_rows, band_rows = int(rows), int(cols), int(ch), int(segment_rows), int(band_rows)
+        if segment_rows <= 0 or band_rows <= 0 or band_rows % segment_rows:
+            raise ValueError("canvas_encode_png_bands: band_rows = %d is not a positive multiple of segment_rows = %d" % (band_rows, segment_rows))
+        for k, r0, n in self._bands(rows, band_rows):
+            slot = k % self.BAND_RING
+            out, need, adler = self._fitted("canvas_encode_png_bands", "band", lambda out: self.canvas_encode_png_rows(handle, r0, n, segment_rows, out),
+                                            self._encode_ring()[slot], lambda need, adler: self._encode_ring(need)[slot])
+            yield r0, n, out[:need], adler
 
 
 _default_engine = None

@@ -2485,6 +2485,43 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles_deflate(vfsms_ctx *ctx, int64_t
     return VFSMS_OK;
 }
 
+// ---- PNG coded on the device (Method.pngEncoder = "device"; deflate_kernels.hip over deflate_kernels.hip's passes, specified by tests/png_ref.py) ------
+// A whole image on the host (B G R with bgr != 0, else R G B; rows `stride` bytes apart) -> the IDAT chunks of its segments of `segment_rows`
+// rows, back to back, CRC-32 included, and the Adler-32 of its filtered bytes: behind the signature, IHDR and IDAT(78 01) and in front of the
+// closing IDAT and IEND they are the file.  *nbytes = the size needed, also on VFSMS_ERR_CAPACITY (nothing is written then)
+extern "C" int vfsms_png_encode_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int segment_rows,
+                                       uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler)
+{
+    CTX_ENTER(ctx);
+    const char *who = "png_encode_device";
+    if (!img || !nbytes || !adler) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
+    TRY(png_check_geometry(who, segment_rows, h, w, ch));
+    size_t pitch = 0;
+    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
+    return png_encode_band_device(ctx, &ctx->deflate_scratch, ctx->jpeg_scratch.img.as<uint8_t>(), h, w, ch, pitch, bgr != 0, 0, h, segment_rows, out, cap, nbytes, adler, nullptr, nullptr);
+}
+
+// Rows [row0, row0 + nrows) of the canvas -- never-written pixels are 0, as canvas_read_rows defines the image -- coded the same way; *adler is
+// the band's own Adler-32.  The band contract: row0 a multiple of segment_rows, nrows too unless the band ends at the last row.  The entry keeps
+// no state between bands: the row above row0 is read from the canvas, so any band may be asked for, again and in any order, and no pyramid
+// walk in progress is disturbed.  The sticky geometry flag as vfsms_canvas_download_rows
+extern "C" int vfsms_canvas_encode_png_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int segment_rows,
+                                            uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler)
+{
+    CTX_ENTER(ctx);
+    const char *who = "canvas_encode_png_rows";
+    CanvasRec *cv;
+    TRY(canvas_find(ctx, who, canvas, &cv));
+    TRY(png_check_geometry(who, segment_rows, cv->rows, cv->cols, cv->ch));
+    TRY(canvas_band_check(who, nbytes && adler, cv->rows, row0, nrows, {{segment_rows, "segment_rows"}}));
+    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
+    const int rc = png_encode_band_device(ctx, &cv->deflate, cv->pix.as<uint8_t>(), cv->rows, cv->cols, cv->ch, (size_t)cv->cols * cv->ch, 1, row0, nrows, segment_rows,
+                                          out, cap, nbytes, adler, cv->d_err.as<int>(), &flag);
+    if (rc != VFSMS_OK && rc != VFSMS_ERR_CAPACITY) return rc;
+    TRY(canvas_flag_verdict(flag));
+    return rc;
+}
+
 // ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------
 // the tiles of a shading call: known, handed over (tile_ready) and of one shape
 static int shade_tiles(vfsms_ctx *ctx, const char *what, int n, const int64_t *tiles, std::vector<TileRec *> &T)

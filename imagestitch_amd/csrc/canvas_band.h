@@ -1,5 +1,6 @@
 // canvas_band.h -- the band walk behind the four write-out routes of a canvas (vfsms_canvas_download_rows, .._download_rows_pyramid,
-// .._encode_jpeg_rows, .._encode_pyramid_tiles and its lossless twin .._encode_pyramid_tiles_deflate of api.hip): the one band check, the one reader of the sticky geometry flag, and the
+// .._encode_jpeg_rows, .._encode_pyramid_tiles and its lossless twin .._encode_pyramid_tiles_deflate of api.hip; .._encode_png_rows uses the
+// check and the flag alone: it keeps no state between bands): the one band check, the one reader of the sticky geometry flag, and the
 // operations of PyrPending, the rows of the reduced levels that wait between the bands of the tile route.  Host C++ over common.h and the
 // runtime API, no kernels, no launchers: libvfsms and tools/canvas_band_host_check.cpp (host sanitizers, failures injected) compile the
 // same lines.

@@ -173,15 +173,18 @@ struct JpegTileJob { const uint8_t *src; size_t src_bytes, pitch; int src_row0, 
 struct JpegTilesRun { int n_tiles, n_int, ipt, interval, bpm, plen; uint8_t prefix[44]; uint32_t *d_sizes; unsigned long long *d_offs; int *d_err; std::vector<unsigned long long> tile_offs; };
 // device scratch of the lossless tile coder (deflate_kernels.hip), grown to the largest call seen: the predicted bytes of the call's tiles, the
 // records per tile and per chunk (DflArgs' arrays), the coded streams
-struct DeflateScratch { DevBuf pred, meta, out; };
+struct DeflateScratch { DevBuf pred, meta, out, png; };     // png: the PNG coder's own records (deflate_kernels.hip): the rows' filter types, the segments' Adler sums
 // the tile rows of one level as the kernels see them (JpegTileJob's fields; ntx tiles a row, first_tile: its first tile among the call's)
 struct DflJobDev { const uint8_t *src; unsigned long long src_bytes, pitch; int src_row0, rows, cols, row0, ntx; long long first_tile; };
 // one call of the coder: n_tiles tiles of `nbytes` = tile x tile x ch bytes in `nchunks` chunks each.  Per tile: adler (the two sums), hist
 // (288 a tile), lens (288 a tile), table (288 a tile), sizes / offs (the streams' bytes and where they start, offs[n_tiles] the total), eob (the
 // bit of the stream at which the end-of-block code starts).  Per chunk: bounds (its first and last run boundary), reach (the last boundary in
-// front of it, the first behind it), chunk_bits (its tokens' bits, then where they start among the tile's).  out: the payload in words
+// front of it, the first behind it), chunk_bits (its tokens' bits, then where they start among the tile's).  out: the payload in words.
+// To the passes behind predict a tile is a byte string at pred + tile * nbytes (nbytes: the stride, a multiple of 16) of which `len` bytes are
+// live, `last_len` in the call's last string; a tile's are all nbytes.  head_bits: the bits in front of a string's tokens in its stream; png: the
+// strings are a PNG's segments (deflate_kernels.hip), framed as IDAT chunks
 struct DflArgs {
-    DflJobDev job[VFSMS_PYRAMID_MAX_LEVELS + 1]; int n_jobs, tile, ch, bgr, nbytes, nchunks, n_tiles;
+    DflJobDev job[VFSMS_PYRAMID_MAX_LEVELS + 1]; int n_jobs, tile, ch, bgr, nbytes, nchunks, n_tiles, len, last_len, head_bits, png;
     uint8_t *pred; int2 *bounds, *reach; uint32_t *adler, *hist; uint8_t *lens; uint32_t *table, *sizes; unsigned long long *offs, *eob;
     uint32_t *chunk_bits; uint32_t *out; unsigned long long out_words; int *err;
 };
@@ -439,6 +442,13 @@ int deflate_check_tile_geometry(const char *who, int tile, int ch);
 int deflate_tiles_count_device(vfsms_ctx *ctx, DeflateScratch *s, const JpegTileJob *jobs, int n_jobs, int ch, int bgr, int tile, const int *d_flag, int *flag,
                                DeflateTilesRun *run);
 int deflate_tiles_write_device(vfsms_ctx *ctx, DeflateScratch *s, const DeflateTilesRun *run, uint8_t *out);
+// deflate_kernels.hip: the PNG coder of Method.pngEncoder = "device" (tests/png_ref.py; the rules are csrc/png_core.h's).  Rows [row0, row0 + nrows)
+// of the rows x cols x ch image at pix (rows `pitch` bytes apart; B G R when bgr) -> the IDAT chunks of their segments of `segment_rows` rows in
+// `out` on the host, and the Adler-32 of their filtered bytes.  The row above row0 is read from the image.  *nbytes = the size, also on
+// VFSMS_ERR_CAPACITY (nothing is written then).  d_flag (an int on the device, may be NULL) comes to *flag.  Synchronises the stream
+int png_check_geometry(const char *who, int segment_rows, int rows, int cols, int ch);
+int png_encode_band_device(vfsms_ctx *ctx, DeflateScratch *s, const uint8_t *pix, int rows, int cols, int ch, size_t pitch, int bgr, int row0, int nrows,
+                           int segment_rows, uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler, const int *d_flag, int *flag);
 // jpeg_host.cpp / jpeg_dec_kernels.hip: the device half of the JPEG decoder (tests/jpeg_dec_ref.py).  A component of one launch: its blocks
 // (64 int16 each, natural order, block-row-major on a grid `bcols` wide), its table (uint16[64], natural order), the plane it becomes (`rows`
 // x `cols` samples kept of the grid, `pitch` bytes apart) and the index of its first block among the launch's `total`

@@ -184,13 +184,18 @@ DFL_HD unsigned long long dfl_stream_bytes(unsigned long long block_bits) { retu
 // the DFL_HEAD_BITS bits in front of the tokens through put(value, nbits) (first bit lowest, at most 8 bits a call): the zlib header; BFINAL = 1,
 // BTYPE = 2, HLIT = 29, HDIST = 0, HCLEN = 15; the code-length code lengths 4 for 0..15 and 0 for 16, 17, 18 (sent in RFC 1951's order 16, 17,
 // 18, 0, 8, ...), under which symbol s is the 4-bit code s; the 286 lengths and the one distance length 1
-template <class Put> DFL_HD void dfl_head(const uint8_t *lens, Put &put)
+// (dfl_block_head: the block's header alone, with BFINAL = `bfinal`: a block of png_core.h's segments is not final)
+template <class Put> DFL_HD void dfl_block_head(const uint8_t *lens, Put &put, unsigned bfinal)
 {
-    put(0x78u, 8); put(0x01u, 8);
-    put(1u, 1); put(2u, 2); put(29u, 5); put(0u, 5); put(15u, 4);
+    put(bfinal, 1); put(2u, 2); put(29u, 5); put(0u, 5); put(15u, 4);
     for (int k = 0; k < 19; k++) put(k < 3 ? 0u : 4u, 3);
     for (int s = 0; s < DFL_SYMS; s++) put(dfl_reverse(lens[s], 4), 4);
     put(dfl_reverse(1, 4), 4);
+}
+template <class Put> DFL_HD void dfl_head(const uint8_t *lens, Put &put)
+{
+    put(0x78u, 8); put(0x01u, 8);
+    dfl_block_head(lens, put, 1u);
 }
 // running Adler-32 sums of bytes d[0 .. n) of a string of `total` bytes, d[0] at position `at`: a += sum d, b += sum (total - position) d; the
 // caller reduces modulo 65521 (b grows by at most 255 * total a byte) and adds the string's own 1 and `total`

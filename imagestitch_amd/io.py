@@ -250,6 +250,71 @@ class DeviceJpegFile:
             os.remove(self.path)
 
 
+def adler_combine(adler1, adler2, len2):
+    """the Adler-32 of A || B from those of A and B and B's length (zlib's adler32_combine, which Python does not export)"""
+    M = 65521
+    rem = int(len2) % M
+    s1, s2 = adler1 & 0xFFFF, (adler1 >> 16) & 0xFFFF
+    t1, t2 = adler2 & 0xFFFF, (adler2 >> 16) & 0xFFFF
+    return ((s2 + t2 + rem * s1 + M * M - rem) % M) << 16 | (s1 + t1 + M - 1) % M
+
+
+class DevicePngFile:
+    """The file side of Method.pngEncoder = "device": the signature, IHDR and the zlib header in an IDAT of its own, then the IDAT chunks of
+    the bands as Engine.canvas_encode_png_bands hands them out (filtered, coded and checksummed on the device; every chunk ends on a byte of
+    the deflate stream), appended verbatim in order, then an IDAT with the final empty stored block and the Adler-32 of all filtered bytes,
+    folded together from the bands' own, and IEND.  Creates the directory; refuses what PNG cannot hold before anything is written."""
+
+    def __init__(self, path, full_shape, segment_rows=16):
+        import struct
+        rows, cols = int(full_shape[0]), int(full_shape[1])
+        ch = int(full_shape[2]) if len(full_shape) == 3 else 1
+        if ch not in (1, 3) or min(rows, cols) < 1 or max(rows, cols) >= 1 << 31:
+            raise ValueError("the device's PNG holds 1- or 3-channel images of 1 .. 2^31 - 1 pixels a side (this one: %s)" % (tuple(full_shape),))
+        if not 1 <= int(segment_rows) <= 4096 or int(segment_rows) * (1 + cols * ch) * 15 >= 1 << 32:
+            raise ValueError("the device's PNG takes segments of 1..4096 rows whose bytes at 15 bits each fit 32 bits (segment_rows = %r, %d bytes a row)" % (segment_rows, 1 + cols * ch))
+        d = os.path.dirname(path)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        self.path, self.bytes_written, self.segment_rows = path, 0, int(segment_rows)
+        self._rowbytes, self._rows, self._rows_in, self._adler = 1 + cols * ch, rows, 0, 1
+        self._f = open(path, "wb")
+        self._write(b"\x89PNG\r\n\x1a\n")
+        self._chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 8, 2 if ch == 3 else 0, 0, 0, 0))
+        self._chunk(b"IDAT", b"\x78\x01")
+
+    def _write(self, data):
+        self._f.write(data)
+        self.bytes_written += len(data)
+
+    def _chunk(self, tag, data):
+        import struct
+        import zlib
+        self._write(struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff))
+
+    def append(self, payload, adler, nbytes_filtered):
+        """the chunks of the next band, the Adler-32 of its filtered bytes and their number (the band's rows x (1 + cols x ch))"""
+        self._write(memoryview(payload))
+        self._adler = adler_combine(self._adler, int(adler), int(nbytes_filtered))
+        self._rows_in += int(nbytes_filtered) // self._rowbytes
+
+    def close(self):
+        import struct
+        if self._rows_in != self._rows:
+            raise ValueError("DevicePngFile: %d of %d rows were appended" % (self._rows_in, self._rows))
+        self._chunk(b"IDAT", b"\x01\x00\x00\xff\xff" + struct.pack(">I", self._adler))
+        self._chunk(b"IEND", b"")
+        self._f.close()
+        self._f = None
+
+    def abort(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+        if os.path.exists(self.path):
+            os.remove(self.path)
+
+
 class TiffBandWriter:
     """A `Stitcher.mosaicSink` for uncompressed baseline TIFF (BigTIFF beyond 4 GB): one strip per band, the directory written behind the
     last band.  R G B (or gray) 8-bit samples."""

@@ -63,7 +63,7 @@ class ResidentFeatures:
 from .ingest import (_imread, _imread_gray_pointer, _PillowBlocks, _decoder_pool, _decode_once, _fill_from_jpeg, _ycc_to_bgr, _imshape,  # noqa: F401
                      _list_images, TileIngest)
 from .io import (_imwrite, _imwrite_jpeg_stripes, NpyBandWriter, PngBandWriter, JpegBandWriter, TiffBandWriter, _NoNativeJpeg,  # noqa: F401
-                 _native_jpeg_encoder, band_writer_for, PyramidTiffBandWriter, DeviceJpegFile)
+                 _native_jpeg_encoder, band_writer_for, PyramidTiffBandWriter, DeviceJpegFile, DevicePngFile)
 
 
 def _join(base, *parts):
@@ -188,6 +188,26 @@ class Stitcher(Utility.Method):
             payload_sink.device_jpeg = True
             self.mosaicSink = payload_sink
             return payload_sink
+        if self._devicePng(os.path.splitext(probe)[1][1:]):
+            # pngEncoder "device": the sink takes the bands' finished IDAT chunks and Adler-32, not their pixels (_writeOut asks the engine for them)
+
+            def png_sink(row0, nrows, payload, adler, full_shape):
+                try:
+                    if state["f"] is None:
+                        state["f"] = DevicePngFile(next_path(), full_shape, int(self.pngSegmentRows))
+                    ch = full_shape[2] if len(full_shape) > 2 else 1
+                    state["f"].append(payload, adler, nrows * (1 + full_shape[1] * ch))
+                    if row0 + nrows >= full_shape[0]:
+                        state["f"].close()
+                        state["f"] = None
+                except BaseException:
+                    if state["f"] is not None:
+                        state["f"].abort()
+                        state["f"] = None
+                    raise
+            png_sink.device_png = True
+            self.mosaicSink = png_sink
+            return png_sink
         # outputPyramid: every mosaic through the pyramidal writer, which takes the reduced levels of a band beside it
         wkw = {"pyramid": self._pyramidOptions()} if self.outputPyramid else {}
         first = band_writer_for(probe, **wkw)
@@ -235,16 +255,37 @@ class Stitcher(Utility.Method):
         self._jpegBandRows()
         return True
 
+    def _devicePng(self, outputfileExtension):
+        """does this output go through the device's PNG coder (Method.pngEncoder = "device" with streamOutput and a .png result)?  Judged --
+        with the engine's support, pngSegmentRows and mosaicBandRows -- before a file is listed or a tile decoded.  Everything else (other
+        formats, outputPyramid, streamOutput = False, a mosaicSink of the user's) is written as with "host"."""
+        if self.pngEncoder not in ("host", "device"):
+            raise ValueError("pngEncoder must be 'host' or 'device', got %r" % (self.pngEncoder,))
+        if self.pngEncoder != "device" or not self.streamOutput or self.outputPyramid or str(outputfileExtension).lower() != "png":
+            return False
+        if "mosaicSink" in self.__dict__ and not getattr(self.__dict__["mosaicSink"], "device_png", False):
+            return False
+        self._routeNeeds("device_png", "pngEncoder = 'device'")
+        self._pngBandRows()
+        return True
+
+    def _pngBandRows(self):
+        """mosaicBandRows for the device's PNG coder: every band must be whole segments, so it is a multiple of pngSegmentRows (1..4096)"""
+        S = self.pngSegmentRows
+        if isinstance(S, bool) or not isinstance(S, int) or not 1 <= S <= 4096:
+            raise ValueError("pngSegmentRows must be an integer 1..4096, got %r" % (S,))
+        return self._bandRows(S, "segments of %d rows need" % S)
+
     # The routes a fused canvas leaves the device by, and the engine method each needs.  A sink names its route: the flags `device_jpeg`
-    # (it takes entropy-coded bands) and `device_tiles` (finished tile streams: JPEG's, or with `tile_codec` "deflate" the lossless coder's,
+    # (it takes entropy-coded bands), `device_png` (the IDAT chunks of the bands' segments) and `device_tiles` (finished tile streams: JPEG's, or with `tile_codec` "deflate" the lossless coder's,
     # route "device_tiles_deflate"), the method `pyramid_levels` (pixel bands with reduced levels)
-    _ROUTES = {"device_jpeg": "canvas_encode_jpeg_bands", "device_tiles": "canvas_encode_pyramid_tiles",
+    _ROUTES = {"device_jpeg": "canvas_encode_jpeg_bands", "device_png": "canvas_encode_png_bands", "device_tiles": "canvas_encode_pyramid_tiles",
                "device_tiles_deflate": "canvas_encode_pyramid_tiles_deflate",
                "pyramid_levels": "canvas_download_pyramid_bands", "plain": "canvas_download_bands"}
 
     @staticmethod
     def _routeOf(sink):
-        flagged = [route for route in ("device_jpeg", "device_tiles") if getattr(sink, route, False)]
+        flagged = [route for route in ("device_jpeg", "device_png", "device_tiles") if getattr(sink, route, False)]
         if flagged == ["device_tiles"] and getattr(sink, "tile_codec", "jpeg") == "deflate":
             return "device_tiles_deflate"
         return flagged[0] if flagged else "pyramid_levels" if hasattr(sink, "pyramid_levels") else "plain"
@@ -566,6 +607,7 @@ class Stitcher(Utility.Method):
         """Stitcher.py:129-151."""
         self._checkPyramidOutput(outputfileExtension)
         self._deviceJpeg(outputfileExtension)
+        self._devicePng(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             fileList = _list_images(_join(projectAddress, i), fileExtension)
             outDir = outputAddress.replace("\\", os.sep)
@@ -600,6 +642,7 @@ class Stitcher(Utility.Method):
         """Stitcher.py:153-182 (the entry point Main.py:20-51 uses)."""
         self._checkPyramidOutput(outputfileExtension)
         self._deviceJpeg(outputfileExtension)
+        self._devicePng(outputfileExtension)
         for i in range(startNum, fileNum + 1):
             startTime = time.time()
             fileAddress = _join(projectAddress, i)
@@ -1106,6 +1149,9 @@ class Stitcher(Utility.Method):
         if route == "device_jpeg":                               # the sink appends the bands' entropy-coded bytes (csrc/jpeg_enc_kernels.hip)
             for r0, nr, payload in eng.canvas_encode_jpeg_bands(canvas, rows, cols, ch, int(self.jpegQuality), int(self.jpegRestartMcus), self._jpegBandRows()):
                 sink(r0, nr, payload, full_shape)
+        elif route == "device_png":                              # the sink appends the bands' IDAT chunks (the PNG coder of csrc/deflate_kernels.hip)
+            for r0, nr, payload, adler in eng.canvas_encode_png_bands(canvas, rows, cols, ch, int(self.pngSegmentRows), self._pngBandRows()):
+                sink(r0, nr, payload, adler, full_shape)
         elif route == "device_tiles":
             # the finished tile streams of level 0 and of the reduced levels a band completes (a mosaic that fits one tile: zero reduced levels)
             for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), int(self.jpegQuality),

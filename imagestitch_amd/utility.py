@@ -232,6 +232,20 @@ class Method():
     jpegQuality = 95
     jpegRestartMcus = 8
 
+    # ---- PNG results coded on the device (no reference counterpart; tests/png_ref.py).  pngEncoder "host" (the default: nothing changes --
+    # the bands cross the link as pixels and ONE zlib stream at level 1 with filter 0 on every row codes them on one host thread,
+    # PngBandWriter) or "device": with streamOutput, a .png result, no outputPyramid and no mosaicSink of the user's, every row gets the PNG
+    # filter (None, Sub, Up, Average, Paeth) of the smallest sum of absolutes where the mosaic is, segments of pngSegmentRows rows are coded by
+    # the lossless tile coder (runs at distance 1, one dynamic Huffman block a segment) and leave as finished IDAT chunks, CRC-32 included,
+    # which the host only appends to the file (DevicePngFile, which folds the bands' Adler-32 together).  The file decodes to the pixels of
+    # the host writer's file; its bytes are tests/png_ref.py's.
+    # pngSegmentRows: rows per segment = per Huffman table and per IDAT chunk (1..4096).  Shorter segments mean more parallel strings and
+    # about 170 bytes of table and frame each.  16: in the sweep of tools/bench_png_device.py over {1 .. 256} the file no longer shrinks beyond
+    # it and the time grows (README).
+    # mosaicBandRows must be a multiple of pngSegmentRows, so that every band is whole segments.
+    pngEncoder = "host"
+    pngSegmentRows = 16
+
     # ---- JPEG tiles decoded on the device (no reference counterpart; tests/jpeg_dec_ref.py).  jpegDecoder "host" (the default: nothing
     # changes -- libjpeg-turbo decodes a file up to its sample planes on a decoder thread, vfsms_tile_fill_jpeg) or "device": the decoder
     # thread stops behind the entropy decode (jpeg_read_coefficients) and dequantisation, the inverse DCT, the level shift and the clamp run

@@ -635,6 +635,27 @@ int vfsms_deflate_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img, int h,
 int vfsms_canvas_encode_pyramid_tiles_deflate(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int levels, int tile,
                                               uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index);
 
+/* ---- PNG coded on the device (Method.pngEncoder = "device").  Specification: tests/png_ref.py (on tests/deflate_ref.py); bytes equal it exactly.
+ * Rows are cut into segments of segment_rows rows.  Every row gets the PNG filter (None, Sub, Up, Average, Paeth) of the smallest sum of
+ * absolutes, ties to the lowest type, against the raw row above it in the whole image; a segment's filter types and filtered bytes are coded
+ * by the lossless tile coder above (runs at distance 1, one dynamic Huffman block) as a block that is not final, followed by an empty stored
+ * block, and framed as one IDAT chunk with its CRC-32.  Behind the signature, IHDR and IDAT(78 01), and in front of
+ * IDAT(01 00 00 FF FF + the Adler-32 of all filtered bytes) and IEND, the chunks of all segments are the file; colour is stored R G B.
+ * Refused everywhere (VFSMS_ERR_BAD_ARG): channels other than 1 or 3, segment_rows outside 1..4096, a segment whose bytes at 15 bits each
+ * exceed 32 bits, more chunks of 4096 bytes (2^24 - 1) than one call takes.
+ * vfsms_png_encode_device: an image on the host (B G R with bgr != 0, else R G B; rows `stride` bytes apart) -> the chunks of all its segments
+ * and the Adler-32 of its filtered bytes.  *nbytes = the size needed, also on VFSMS_ERR_CAPACITY (nothing is written then; the call may be
+ * repeated).
+ * vfsms_canvas_encode_png_rows: rows [row0, row0 + nrows) of the mosaic as vfsms_canvas_download_rows hands them out, coded the same way;
+ * *adler is the band's own Adler-32 (zlib's adler32_combine joins the bands').  Band contract (VFSMS_ERR_BAD_ARG otherwise): row0 a multiple
+ * of segment_rows; nrows too unless the band ends at the last row.  The entry keeps no state between bands -- the row above row0 is read from
+ * the canvas -- so any band may be asked for, and asked for again, and a pyramid walk in progress is not disturbed.  The sticky geometry
+ * flag as vfsms_canvas_download_rows.                                                                                                  */
+int vfsms_png_encode_device(vfsms_ctx *ctx, const uint8_t *img, int h, int w, int ch, int stride, int bgr, int segment_rows,
+                            uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler);
+int vfsms_canvas_encode_png_rows(vfsms_ctx *ctx, int64_t canvas, int row0, int nrows, int segment_rows,
+                                 uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler);
+
 /* ---- flat-field shading correction (Method.shadingCorrection).  No reference counterpart: the arithmetic, all integer, is this
  * library's own specification, tests/shading_ref.py, and every stage equals it exactly. -------------------------------------- */
 /* A shading field from n (1..4096) resident tiles of one shape and channel count (any row stride): per sample the k-th smallest byte
