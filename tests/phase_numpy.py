@@ -48,8 +48,13 @@ def phase_correlate(a, b):
     R = np.fft.irfft2(C, s=(M, N)) * (M * N)                    # idft without DFT_SCALE
     ym, xm = M >> 1, N >> 1                                     # fftShift: quadrants of (N >> 1) x (M >> 1); an odd last row / column stays
     S = R.copy()
-    S[:ym, :xm] = R[ym:2 * ym, xm:2 * xm]; S[ym:2 * ym, xm:2 * xm] = R[:ym, :xm]
-    S[:ym, xm:2 * xm] = R[ym:2 * ym, :xm]; S[ym:2 * ym, :xm] = R[:ym, xm:2 * xm]
+    if ym == 0 or xm == 0:                                      # a 1 x n or n x 1 surface: its two halves swap, an odd last element stays
+        mid = (M * N) >> 1
+        flat = R.reshape(-1)
+        S = np.concatenate([flat[mid:2 * mid], flat[:mid], flat[2 * mid:]]).reshape(M, N)
+    else:
+        S[:ym, :xm] = R[ym:2 * ym, xm:2 * xm]; S[ym:2 * ym, xm:2 * xm] = R[:ym, :xm]
+        S[:ym, xm:2 * xm] = R[ym:2 * ym, :xm]; S[ym:2 * ym, :xm] = R[:ym, xm:2 * xm]
     py, px = np.unravel_index(np.argmax(S), S.shape)            # minMaxLoc: first maximum in row-major order
     r0, r1 = max(py - 2, 0), min(py + 2, M - 1)
     c0, c1 = max(px - 2, 0), min(px + 2, N - 1)

@@ -12,6 +12,7 @@ import pytest
 import imagestitch_amd as isa
 from imagestitch_amd.grid import GridRegistrar
 
+from phase_cases import resident
 import phase_resolve_cases as PC
 import phase_resolve_ref as PR
 
@@ -47,21 +48,6 @@ def reference(shape, min_pixels=PC.MIN_PIXELS):
         assert PR.peak_gap_ok(R, K) or not R.any(), (shape, name)
         out.append(r)
     return out
-
-
-def resident(engine, strips, pad=(3, 7)):
-    """every strip inside a tile of its own, at an odd corner and with a row stride that is no multiple of 16: the sums kernel's head /
-    body / tail split and the funnel shift see every alignment -> (handles, jobs)"""
-    handles, jobs = [], []
-    for k, (_n, A, B) in enumerate(strips):
-        h, w = A.shape
-        oy, ox = (pad[0] + k % 2, pad[1] + k % 5)
-        ta = np.full((h + oy + 2, w + ox + 5), 9, np.uint8); tb = np.full((h + 3, w + 11 + k % 3), 200, np.uint8)
-        ta[oy:oy + h, ox:ox + w] = A; tb[1:1 + h, 2 + k % 3:2 + k % 3 + w] = B
-        ha, hb = engine.tile_upload(ta), engine.tile_upload(tb)
-        handles += [ha, hb]
-        jobs.append((ha, hb, oy, ox, 1, 2 + k % 3, h, w))
-    return handles, jobs
 
 
 @pytest.mark.parametrize("shape", SHAPES)
