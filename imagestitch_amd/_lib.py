@@ -129,6 +129,8 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_bf_l2_knn2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_bf_l2_knn2_u8d128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_bf_hamming_nn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "vfsms_mode_offset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
@@ -708,6 +710,16 @@ class Engine:
         dim = q.shape[1] if nq else (t.shape[1] if nt else 64)
         i1 = np.empty(nq, np.int32); d1 = np.empty(nq, np.float32); d2 = np.empty(nq, np.float32)
         self._check(self.lib.vfsms_bf_l2_knn2(self.ctx, _ptr(q), nq, _ptr(t), nt, dim, _ptr(i1), _ptr(d1), _ptr(d2)))
+        return i1, d1, d2
+
+    def bf_l2_knn2_u8d128(self, q, t, nsplit=0):
+        """vfsms_bf_l2_knn2_u8d128: (i1, d1, d2) of bf_l2_knn2 from the integer matrix-core search of the fused SIFT batch, for (n, 128)
+        rows whose elements are integers 0..255 (anything else raises VfsmsError).  nsplit 1..8: that many train splits; 0: the batch's
+        own rule for one job.  A test and diagnostic operator."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 128); t = np.ascontiguousarray(t, np.float32).reshape(-1, 128)
+        nq, nt = len(q), len(t)
+        i1 = np.empty(nq, np.int32); d1 = np.empty(nq, np.float32); d2 = np.empty(nq, np.float32)
+        self._check(self.lib.vfsms_bf_l2_knn2_u8d128(self.ctx, _ptr(q), nq, _ptr(t), nt, int(nsplit), _ptr(i1), _ptr(d1), _ptr(d2)))
         return i1, d1, d2
 
     def bf_hamming_matches(self, q, t, max_dist=-1):

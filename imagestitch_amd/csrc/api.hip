@@ -1004,6 +1004,14 @@ static int pick_hamming_nsplit(int capq, int njobs)
     return (int)std::max<long long>(1, std::min<long long>(8, (8192 + waves - 1) / waves));
 }
 
+// integer 128-d search (k_bf_i8_d128): a wave owns 64 queries; `waves` over all the jobs of the launch, maxt the largest train set.  Splits
+// are whole 16-train tiles, at least 256 trains each while the chip is short of waves
+static int pick_i8_nsplit(long long waves, int maxt)
+{
+    waves = std::max<long long>(waves, 1);
+    return (int)std::max<long long>(1, std::min<long long>({8, (4096 + waves - 1) / waves, (long long)(maxt + 255) / 256}));
+}
+
 static bool bf_force_exact()
 {
     static const bool v = getenv("VFSMS_BF_EXACT") && atoi(getenv("VFSMS_BF_EXACT")) != 0;
@@ -1151,6 +1159,61 @@ extern "C" int vfsms_bf_l2_knn2(vfsms_ctx *ctx, const float *q, int nq, const fl
     }
     MatchRun run;
     TRY(bf_l2_host(ctx, q, nq, t, nt, dim, &run, MatchTail{TAIL_KNN, 0.0, -1, 0}));
+    const MatchDev &M = run.M[0];
+    if (idx1) HIP_TRY(hipMemcpyAsync(idx1, M.i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    if (d1) HIP_TRY(hipMemcpyAsync(d1, M.d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    if (d2) HIP_TRY(hipMemcpyAsync(d2, M.d2, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
+// vfsms_bf_l2_knn2_u8d128: one job of host descriptors through the integer search of the fused SIFT batch (k_pack_i8_d128 +
+// k_bf_i8_d128), the way the batch drives it: rows packed to sift_pad_rows, device counts, whole-tile splits.  A test and diagnostic
+// operator: VFSMS_BF_EXACT does not apply
+static bool u8_elements(const float *a, size_t n)
+{
+    for (size_t k = 0; k < n; k++) {
+        const float v = a[k];
+        if (!(v >= 0.f && v <= 255.f) || v != (float)(int)v) return false;       // a NaN fails the first compare
+    }
+    return true;
+}
+extern "C" int vfsms_bf_l2_knn2_u8d128(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int nsplit,
+                                       int32_t *idx1, float *d1, float *d2)
+{
+    CTX_ENTER(ctx);
+    if (nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) { vfsms_set_error("bf_l2_knn2_u8d128: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (nsplit < 0 || nsplit > 8) { vfsms_set_error("bf_l2_knn2_u8d128: nsplit %d outside 0..8", nsplit); return VFSMS_ERR_BAD_ARG; }
+    if (!u8_elements(q, (size_t)nq * 128) || !u8_elements(t, (size_t)nt * 128)) {
+        vfsms_set_error("bf_l2_knn2_u8d128: every element must be an integer in 0..255");
+        return VFSMS_ERR_BAD_ARG;
+    }
+    if (nq == 0) return VFSMS_OK;
+    if (nt == 0) {
+        for (int i = 0; i < nq; i++) { if (idx1) idx1[i] = -1; if (d1) d1[i] = INFINITY; if (d2) d2[i] = INFINITY; }
+        return VFSMS_OK;
+    }
+    MatchJob J{};
+    J.capq = nq; J.capt = nt;
+    const MatchPlan P{false, nsplit ? nsplit : pick_i8_nsplit((nq + 63) / 64, nt), 0};
+    const size_t pq = sift_pad_rows(nq), pt = sift_pad_rows(nt);
+    TRY(ctx_arena_reserve(ctx, sizeof(float) * ((size_t)nq + nt) * 128 + (128 + sizeof(int)) * (pq + pt) + match_run_bytes(&J, 1, P) + 65536));
+    float *dq, *dt;
+    TRY(upload_array(ctx, q, (size_t)nq * 128, &dq));
+    TRY(upload_array(ctx, t, (size_t)nt * 128, &dt));
+    int8_t *q8 = (int8_t *)ctx_arena_alloc(ctx, 128 * pq), *t8 = (int8_t *)ctx_arena_alloc(ctx, 128 * pt);
+    int *qn = (int *)ctx_arena_alloc(ctx, sizeof(int) * pq), *tn = (int *)ctx_arena_alloc(ctx, sizeof(int) * pt);
+    if (!q8 || !t8 || !qn || !tn) { vfsms_set_error("bf_l2_knn2_u8d128: arena exhausted (packed rows)"); return VFSMS_ERR_CAPACITY; }
+    J.q = dq; J.t = dt; J.q8 = q8; J.t8 = t8; J.qn2 = qn; J.tn2 = tn;
+    const int cnt[2] = {nq, nt};
+    TRY(match_upload_counts(ctx, &J, 1, cnt));
+    const PackJob pj[2] = {{dq, J.nq_ptr, q8, qn}, {dt, J.nt_ptr, t8, tn}};
+    PackJob *dP;
+    TRY(ctx_upload_small(ctx, pj, sizeof(pj), (void **)&dP));
+    TRY(launch_pack_i8_d128(ctx, dP, 2, std::max(nq, nt)));
+    MatchRun run;
+    TRY(match_run_carve(ctx, &run, &J, 1, 128, P));
+    TRY(match_run_launch(ctx, run, 0, 1, nq, nt, SEARCH_I8_D128, MatchTail{TAIL_KNN, 0.0, -1, 0}));
     const MatchDev &M = run.M[0];
     if (idx1) HIP_TRY(hipMemcpyAsync(idx1, M.i1, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
     if (d1) HIP_TRY(hipMemcpyAsync(d1, M.d1, sizeof(float) * nq, hipMemcpyDeviceToHost, ctx->stream));
@@ -2887,8 +2950,7 @@ extern "C" int vfsms_attempt_sift_batch(vfsms_ctx *ctx, const vfsms_roi_pair *jo
     }
     // a wave of the integer kernel owns 64 queries: its own split rule; the exhaustive float kernel keeps pick_nsplit
     MatchPlan P{false, 0, 0};
-    P.ns = exact ? pick_nsplit(maxcap, maxt, n, 128)
-                 : (int)std::max<long long>(1, std::min<long long>({8, (4096 + waves - 1) / waves, (long long)(maxt + 255) / 256}));
+    P.ns = exact ? pick_nsplit(maxcap, maxt, n, 128) : pick_i8_nsplit(waves, maxt);
     TRY(ctx_arena_reserve(ctx, match_run_bytes(J.data(), n, P) + 65536));
     ctx->pinned_off = 0;
     MatchRun run;

@@ -314,6 +314,11 @@ int vfsms_bf_l2_knn2_ratio(vfsms_ctx *ctx, const float *q, int nq, const float *
 /* raw 2-NN (for parity checks): idx1/d1 best, d2 second-best distance (+inf if nt < 2)            */
 int vfsms_bf_l2_knn2(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int dim,
                      int32_t *idx1, float *d1, float *d2);
+/* the same three arrays from the integer matrix-core search of the fused SIFT batch (vfsms_attempt_sift_batch), for parity checks and
+ * diagnosis: 128-d rows whose elements are integers 0..255 (checked on the host: anything else is VFSMS_ERR_BAD_ARG), packed and searched
+ * exactly as the batch does.  nsplit 1..8: that many train splits; 0: the batch's own rule for one job.  VFSMS_BF_EXACT does not apply. */
+int vfsms_bf_l2_knn2_u8d128(vfsms_ctx *ctx, const float *q, int nq, const float *t, int nt, int nsplit,
+                            int32_t *idx1, float *d1, float *d2);
 /* replaces matchDescriptors(featureType 3, param=orbMaxDistance) (appendix/myGpuFeatures.cpp:175-187)
  * and BFMatcher("BruteForce-Hamming").match (ImageUtility.py:297-302).  max_dist < 0: no threshold. */
 int vfsms_bf_hamming_nn(vfsms_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int nbytes,
