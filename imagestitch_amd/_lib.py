@@ -84,6 +84,8 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_verify_ncc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_ncc_search_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfsms_ncc_wide_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_overlap_sums_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_void_p]),
     "vfsms_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vfsms_profile_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "vfsms_tile_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
@@ -391,6 +393,62 @@ class Engine:
         finally:
             self.tile_free(ha)
         return (int(best[0, 0]), int(best[0, 1])), int(best[0, 2]), int(best[0, 3]), surface[0]
+
+    WIDE_MAX_RADIUS, WIDE_MAX_PEAKS = 128, 4
+
+    @staticmethod
+    def _ncc_jobs(jobs):
+        arr = (NccJob * max(len(jobs), 1))()
+        for k, j in enumerate(jobs):
+            arr[k] = NccJob(*[int(v) for v in j])
+        return arr
+
+    def ncc_wide_batch(self, jobs, radius, factor=4, peaks=2, min_pixels=4096, want_seeds=False):
+        """vfsms_ncc_wide_batch: jobs as for ncc_search_batch; the window of radius 1..128 is searched in two levels (tests/ncc_wide_ref.py):
+        on the pair reduced by factor x factor block means (factor 2, 4 or 8, ceil(radius / factor) <= 16), then at full resolution with
+        radius min(factor, radius) around the `peaks` (1..4) best coarse candidates.
+        -> int32[n, 8] = (ti, tj, fixed-point score, shared pixels, ci, cj, coarse fixed-point score of the winning seed, seeds used): the
+        offset found is (dx + ti, dy + tj) [, int32[n, 4, 6] = (ci, cj, coarse score, ti, tj, fine score) per seed, with want_seeds]"""
+        n = len(jobs)
+        out = np.zeros((n, 8), np.int32)
+        seeds = np.zeros((n, self.WIDE_MAX_PEAKS, 6), np.int32) if want_seeds else None
+        self._check(self.lib.vfsms_ncc_wide_batch(self.ctx, self._ncc_jobs(jobs), n, int(radius), int(factor), int(peaks), int(min_pixels),
+                                                  _ptr(out), _ptr(seeds), None))
+        return (out, seeds) if want_seeds else out
+
+    def ncc_wide_reduce(self, a, b, dx, dy, factor):
+        """the two reduced planes (A's, B's) that ncc_wide_batch searches first, for two host arrays (uint8, one shape) uploaded for the
+        call: the test hook of vfsms_ncc_wide_batch"""
+        a = _u8_2d(a); b = _u8_2d(b)
+        f = int(factor)
+        if a.shape != b.shape or f not in (2, 4, 8):
+            raise ValueError("ncc_wide_reduce: two arrays of one shape and a factor of 2, 4 or 8")
+        ha = self.tile_upload(a)
+        try:
+            hb = self.tile_upload(b)
+            try:
+                return self.ncc_wide_reduce_tiles(ha, hb, a.shape, dx, dy, f)
+            finally:
+                self.tile_free(hb)
+        finally:
+            self.tile_free(ha)
+
+    def ncc_wide_reduce_tiles(self, tile_a, tile_b, shape, dx, dy, factor):
+        """ncc_wide_reduce for two resident gray tiles of `shape`"""
+        f = int(factor)
+        hc, wc = (int(shape[0]) - int(dx) % f) // f, (int(shape[1]) - int(dy) % f) // f
+        red = np.zeros((2, max(hc, 0), max(wc, 0)), np.uint8)
+        out = np.zeros((1, 8), np.int32)
+        self._check(self.lib.vfsms_ncc_wide_batch(self.ctx, self._ncc_jobs([(tile_a, tile_b, dx, dy)]), 1, f, f, 1, 0, _ptr(out), None, _ptr(red)))
+        return red[0], red[1]
+
+    def overlap_sums_batch(self, jobs):
+        """vfsms_overlap_sums_batch: jobs as for ncc_search_batch -> int64[n, 6] = (N, Sa, Sb, Saa, Sbb, Sab) over the pixels the two tiles
+        share at the job's own offset (tests/verify_ref.py: sums)"""
+        n = len(jobs)
+        out = np.zeros((n, 6), np.int64)
+        self._check(self.lib.vfsms_overlap_sums_batch(self.ctx, self._ncc_jobs(jobs), n, _ptr(out)))
+        return out
 
     def profile_enable(self, on=True):
         self._check(self.lib.vfsms_profile_enable(self.ctx, int(bool(on))))

@@ -1368,6 +1368,129 @@ extern "C" int vfsms_ncc_search_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs,
     return VFSMS_OK;
 }
 
+// the resident single-channel pair of one shape that job k of `who` names -> an AdjJob
+static int adj_job_of(vfsms_ctx *ctx, const char *who, int k, const vfsms_ncc_job &j, AdjJob *out)
+{
+    TileRec *pA, *pB;
+    TRY(resident_pair(ctx, who, k, j, &pA, &pB));
+    const TileRec &A = *pA, &B = *pB;
+    if (A.ch != 1 || B.ch != 1) { vfsms_set_error("%s: job %d names a colour tile; the search takes single-channel tiles", who, k); return VFSMS_ERR_BAD_ARG; }
+    if (A.h != B.h || A.w != B.w) { vfsms_set_error("%s: the tiles of job %d are %d x %d and %d x %d", who, k, A.h, A.w, B.h, B.w); return VFSMS_ERR_BAD_ARG; }
+    *out = AdjJob{A.ptr, B.ptr, A.stride, B.stride, A.h, A.w, j.dx, j.dy};
+    return VFSMS_OK;
+}
+
+// vfsms_ncc_wide_batch: wide_kernels.hip around the search of adjust_kernels.hip; every launch of the batch is enqueued before the one
+// synchronisation that brings the results back
+extern "C" int vfsms_ncc_wide_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int radius, int factor, int peaks, int min_pixels,
+                                    int32_t *out8, int32_t *seeds, uint8_t *reduced)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!jobs || !out8)) || min_pixels < 0 || (reduced && n != 1)) { vfsms_set_error("ncc_wide: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (radius < 1 || radius > VFSMS_WIDE_MAX_RADIUS) { vfsms_set_error("ncc_wide: radius %d outside 1..%d", radius, VFSMS_WIDE_MAX_RADIUS); return VFSMS_ERR_BAD_ARG; }
+    if (factor != 2 && factor != 4 && factor != 8) { vfsms_set_error("ncc_wide: factor %d (2, 4 or 8)", factor); return VFSMS_ERR_BAD_ARG; }
+    if (peaks < 1 || peaks > VFSMS_WIDE_MAX_PEAKS) { vfsms_set_error("ncc_wide: %d peaks outside 1..%d", peaks, VFSMS_WIDE_MAX_PEAKS); return VFSMS_ERR_BAD_ARG; }
+    const int F = factor, K = peaks, Rc = (radius + F - 1) / F, rf = std::min(F, radius);
+    if (Rc > VFSMS_ADJUST_MAX_RADIUS) { vfsms_set_error("ncc_wide: radius %d at factor %d leaves a coarse radius of %d (at most %d)", radius, F, Rc, VFSMS_ADJUST_MAX_RADIUS); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    std::vector<WideJob> W(n);
+    std::vector<AdjJob> HC(n), HF((size_t)n * K);
+    size_t plane_bytes = 0;
+    for (int k = 0; k < n; k++) {
+        WideJob &J = W[k];
+        TRY(adj_job_of(ctx, "ncc_wide", k, jobs[k], &J.src));
+        J.ox = ((J.src.dx % F) + F) % F; J.oy = ((J.src.dy % F) + F) % F;
+        J.hc = (J.src.h - J.ox) / F; J.wc = (J.src.w - J.oy) / F;
+        if (J.hc < 1 || J.wc < 1) { vfsms_set_error("ncc_wide: the %d x %d tiles of job %d leave no block of %d x %d", J.src.h, J.src.w, k, F, F); return VFSMS_ERR_BAD_ARG; }
+        J.sc = (J.wc + 15) & ~15;
+        plane_bytes += 2 * ((((size_t)J.hc * J.sc + 64) + 255) & ~(size_t)255);
+        // The grid of a fine search is sized from a host job, and the centres of the fine jobs exist only on the device.  A seed's centre is
+        // (dx + cx, dy + cy) with |cx|, |cy| <= radius - rf, so its overlap has at most h - |dx + cx| + rf <= h - (|dx| - (radius - rf)) + rf
+        // rows under any candidate; the host job below has exactly that bound under the search's own formula (h - |dx'| + rf), columns alike.
+        AdjJob B = J.src;
+        B.dx = (J.src.dx < 0 ? -1 : 1) * std::max(0, std::abs(J.src.dx) - (radius - rf));
+        B.dy = (J.src.dy < 0 ? -1 : 1) * std::max(0, std::abs(J.src.dy) - (radius - rf));
+        for (int q = 0; q < K; q++) HF[(size_t)k * K + q] = B;
+    }
+    const int Cc = 2 * Rc + 1, CCc = Cc * Cc;
+    const int part = 32768 / VFSMS_WIDE_MAX_PEAKS;             // jobs per launch sequence: its part * K fine jobs fit a grid dimension's 32768
+    const int np_max = std::min(n, part);
+    const size_t sums_bytes = std::max(adjust_sums_bytes(np_max, Rc), adjust_sums_bytes(np_max * K, rf));
+    const size_t ints = (size_t)n * (8 + VFSMS_WIDE_MAX_PEAKS * 6) + (size_t)np_max * (4 + CCc + 4 * K);
+    TRY(ctx_arena_reserve(ctx, plane_bytes + sizeof(WideJob) * (size_t)n + sizeof(AdjJob) * ((size_t)n + (size_t)np_max * K) + sums_bytes + sizeof(int32_t) * ints + 65536));
+    ctx->pinned_off = 0;
+    for (int k = 0; k < n; k++) {
+        WideJob &J = W[k];
+        const size_t pb = (size_t)J.hc * J.sc + 64;             // 64 bytes behind the last row: the search loads aligned dwords
+        J.ac = (uint8_t *)ctx_arena_alloc(ctx, pb); J.bc = (uint8_t *)ctx_arena_alloc(ctx, pb);
+        if (!J.ac || !J.bc) { vfsms_set_error("ncc_wide: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+        HC[k] = AdjJob{J.ac, J.bc, J.sc, J.sc, J.hc, J.wc, (J.src.dx - J.ox) / F, (J.src.dy - J.oy) / F};
+    }
+    WideJob *dW; AdjJob *dC;
+    TRY(ctx_upload_small(ctx, W.data(), sizeof(WideJob) * (size_t)n, (void **)&dW));
+    TRY(ctx_upload_small(ctx, HC.data(), sizeof(AdjJob) * (size_t)n, (void **)&dC));
+    AdjJob *d_fine = (AdjJob *)ctx_arena_alloc(ctx, sizeof(AdjJob) * (size_t)np_max * K);
+    unsigned long long *d_sums = (unsigned long long *)ctx_arena_alloc(ctx, sums_bytes);
+    int32_t *d_out8 = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 8 * (size_t)n);
+    int32_t *d_seeds = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * VFSMS_WIDE_MAX_PEAKS * 6 * (size_t)n);
+    int32_t *d_cbest = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * (size_t)np_max);
+    int32_t *d_surf = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * (size_t)CCc * np_max);
+    int32_t *d_fbest = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * (size_t)np_max * K);
+    if (!d_fine || !d_sums || !d_out8 || !d_seeds || !d_cbest || !d_surf || !d_fbest) { vfsms_set_error("ncc_wide: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    {
+        ProfScope ps(ctx, "repair");
+        for (int k0 = 0; k0 < n; k0 += part) {                // (stream order: a part's scratch is reused after the part before it was picked)
+            const int np = std::min(part, n - k0);
+            TRY(launch_wide_reduce(ctx, dW + k0, W.data() + k0, np, F));
+            TRY(launch_adjust_search(ctx, dC + k0, HC.data() + k0, np, Rc, std::max(1, min_pixels / (F * F)), d_sums, d_cbest, d_surf));
+            TRY(launch_wide_seeds(ctx, dW + k0, np, radius, F, K, d_surf, d_fine, d_seeds + VFSMS_WIDE_MAX_PEAKS * 6 * (size_t)k0, d_out8 + 8 * (size_t)k0));
+            TRY(launch_adjust_search(ctx, d_fine, HF.data() + (size_t)k0 * K, np * K, rf, min_pixels, d_sums, d_fbest, nullptr));
+            TRY(launch_wide_pick(ctx, np, K, d_fbest, d_seeds + VFSMS_WIDE_MAX_PEAKS * 6 * (size_t)k0, d_out8 + 8 * (size_t)k0));
+        }
+    }
+    // results land in staging first: a failure below leaves the caller's arrays untouched
+    std::vector<int32_t> h_out((size_t)n * 8), h_seeds(seeds ? (size_t)n * VFSMS_WIDE_MAX_PEAKS * 6 : 0);
+    std::vector<uint8_t> h_red(reduced ? ((size_t)W[0].hc * W[0].sc) * 2 : 0);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out8, sizeof(int32_t) * h_out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (seeds) HIP_TRY(hipMemcpyAsync(h_seeds.data(), d_seeds, sizeof(int32_t) * h_seeds.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (reduced) {
+        const size_t pb = (size_t)W[0].hc * W[0].sc;
+        HIP_TRY(hipMemcpyAsync(h_red.data(), W[0].ac, pb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_red.data() + pb, W[0].bc, pb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(out8, h_out.data(), sizeof(int32_t) * h_out.size());
+    if (seeds) memcpy(seeds, h_seeds.data(), sizeof(int32_t) * h_seeds.size());
+    if (reduced) {
+        const WideJob &J = W[0];
+        for (int p = 0; p < 2; p++)
+            for (int u = 0; u < J.hc; u++) memcpy(reduced + ((size_t)p * J.hc + u) * J.wc, h_red.data() + ((size_t)p * J.hc + u) * J.sc, J.wc);
+    }
+    return VFSMS_OK;
+}
+
+// vfsms_overlap_sums_batch: overlap_rows_sums of overlap_sums.h over whole resident tiles (wide_kernels.hip: k_wide_sums)
+extern "C" int vfsms_overlap_sums_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int64_t *out6)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!jobs || !out6))) { vfsms_set_error("overlap_sums: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (n == 0) return VFSMS_OK;
+    std::vector<AdjJob> H(n);
+    for (int k = 0; k < n; k++) TRY(adj_job_of(ctx, "overlap_sums", k, jobs[k], &H[k]));
+    const size_t out_bytes = sizeof(unsigned long long) * 6 * (size_t)n;
+    TRY(ctx_arena_reserve(ctx, sizeof(AdjJob) * (size_t)n + out_bytes + 65536));
+    ctx->pinned_off = 0;
+    AdjJob *dJ;
+    TRY(ctx_upload_small(ctx, H.data(), sizeof(AdjJob) * (size_t)n, (void **)&dJ));
+    unsigned long long *d_out = (unsigned long long *)ctx_arena_alloc(ctx, out_bytes);
+    if (!d_out) { vfsms_set_error("overlap_sums: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    const int part = 32768;
+    for (int k0 = 0; k0 < n; k0 += part) TRY(launch_overlap_sums(ctx, dJ + k0, H.data() + k0, std::min(part, n - k0), d_out + 6 * (size_t)k0));
+    HIP_TRY(hipMemcpyAsync(out6, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 // ---- phase correlation ---------------------------------------------------------------------------------------------------
 extern "C" int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
                                         int stride_a, int stride_b, double *out3)

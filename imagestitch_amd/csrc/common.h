@@ -353,6 +353,14 @@ struct AdjJob { const uint8_t *a, *b; int sa, sb, h, w, dx, dy; };
 size_t adjust_sums_bytes(int njobs, int radius);
 int launch_adjust_search(vfsms_ctx *ctx, const AdjJob *d_jobs, const AdjJob *h_jobs, int njobs, int radius, int min_pixels,
                          unsigned long long *d_sums, int32_t *d_best4, int32_t *d_surface);
+// wide_kernels.hip: the two-level search of Method.failedPairRepair = "stage" (tests/ncc_wide_ref.py).  One job: the full-resolution pair
+// (src), its reduced planes in arena scratch (ac, bc: hc x wc bytes, row stride sc) and the block phase (ox, oy) = (dx, dy) mod factor
+struct WideJob { AdjJob src; uint8_t *ac, *bc; int sc, hc, wc, ox, oy; };
+int launch_wide_reduce(vfsms_ctx *ctx, const WideJob *d_jobs, const WideJob *h_jobs, int njobs, int factor);
+int launch_wide_seeds(vfsms_ctx *ctx, const WideJob *d_jobs, int njobs, int radius, int factor, int peaks, const int32_t *d_surface,
+                      AdjJob *d_fine, int32_t *d_seeds, int32_t *d_out8);
+int launch_wide_pick(vfsms_ctx *ctx, int njobs, int peaks, const int32_t *d_fine_best4, int32_t *d_seeds, int32_t *d_out8);
+int launch_overlap_sums(vfsms_ctx *ctx, const AdjJob *d_jobs, const AdjJob *h_jobs, int njobs, unsigned long long *d_out6);
 // orb_kernels.hip
 int ctx_prepare_orb(vfsms_ctx *ctx, const vfsms_orb_params *p);
 void orb_roi_layout(ArenaWalk &a, OrbDev *r, const uint8_t *img, int stride, int h, int w, const vfsms_orb_params *p, int cap1, int cap2, int cap);

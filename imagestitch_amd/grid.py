@@ -281,6 +281,14 @@ class GridRegistrar:
             t = t[:, 1:3]
         return adjust_offsets(self.eng, handles, shapes, t.reshape(-1, 2), radius, threshold, min_pixels)
 
+    def repair(self, handles, shapes, table, hint=None, **kw):
+        """The pairs of `table` (register(stop_on_fail=False)) that could not be registered, repaired from the stage model of those that
+        could (stage.repair_table; keywords: radius, factor, peaks, threshold, min_pixels, blank_ratio) -> (table, report).  hint: the scan
+        pattern's direction per pair, for the pairs whose overlap is blank.  Like adjust, it needs every tile resident on this registrar's
+        engine; the pair-sharded form is out of scope: a chunk cannot be repaired on its own."""
+        from .stage import repair_table
+        return repair_table(self.eng, handles, shapes, table, hint=hint, **kw)
+
     # -- pair-sharded ---------------------------------------------------------------------------------------------------
     BLIND_START_COST = 3.0     # a chunk entered with an unknown direction tries four first candidates instead of one
 

@@ -107,6 +107,7 @@ class Stitcher(Utility.Method):
     # ------------------------------------------------------------------------------------------------
     def flowStitch(self, fileList, caculateOffsetMethod):
         """Stitcher.py:49-94 -> ((status, endfileIndex), stitchImage)."""
+        self._checkRepairOptions()
         self.printAndWrite("Stitching the directory which have " + str(fileList[0]))
         fileNum = len(fileList)
         offsetList = []
@@ -118,6 +119,12 @@ class Stitcher(Utility.Method):
         batched = self._registerBatched(fileList, caculateOffsetMethod)
         if batched is not None:
             (status, endfileIndex, offsetList, describtion) = batched
+        # failedPairRepair = "stage" in the pair-by-pair loop: a failed pair is recorded and the loop goes on; the repair follows the loop
+        repair = self.failedPairRepair == "stage" and batched is None and fileNum >= 2
+        if repair and any(_imshape(f) != _imshape(fileList[0]) for f in fileList):
+            self.printAndWrite("  The tiles are of different sizes: pairs that can not be registered are not repaired")
+            repair = False
+        rows = []
         try:
             for fileIndex in (range(0, fileNum - 1) if batched is None else ()):
                 self.printAndWrite("stitching " + str(fileList[fileIndex]) + " and " + str(fileList[fileIndex + 1]))
@@ -128,15 +135,23 @@ class Stitcher(Utility.Method):
                 else:
                     (status, offset) = caculateOffsetMethod([imageA, imageB])
                 if status == False:
+                    if repair:
+                        rows.append([0, 0, 0, 0, 0, 0])
+                        self.tempImageFeature.isBreak = True      # the next pair describes its own tile A
+                        continue
                     describtion = "  " + str(fileList[fileIndex]) + " and " + str(fileList[fileIndex + 1]) + " can not be stitched"
                     break
                 else:
+                    if repair:
+                        rows.append([1, int(offset[0]), int(offset[1]), int(self.direction), 0, 0])
                     offsetList.append(offset)
                     endfileIndex = fileIndex + 1
         except Exception:
             self.releaseTiles()                     # an operator that raises must not leave the pair's tiles in HBM
             raise
         self.releaseTiles()
+        if repair and not all(r[0] for r in rows):
+            (status, endfileIndex, offsetList, describtion) = self._repairPairLoop(fileList, rows)
         if self.globalAdjust != "none" and batched is None:
             offsetList = self._globalAdjust(fileList[:len(offsetList) + 1], offsetList)
         endTime = time.time()
@@ -453,10 +468,16 @@ class Stitcher(Utility.Method):
                 table = self._fullImageTableOrb(handles, shapes)
             else:
                 had_memory = reg.path_memory is not None
-                table, _d = reg.register(handles, shapes, self.direction, stop_on_fail=True, hint=self._operatorHint(reg, len(shapes) - 1))
+                # failedPairRepair = "stage": every pair is reported (a failed one leaves the direction untouched), and the repair below
+                # decides where the mosaic breaks
+                table, _d = reg.register(handles, shapes, self.direction, stop_on_fail=self.failedPairRepair != "stage",
+                                         hint=self._operatorHint(reg, len(shapes) - 1))
                 # (what this path taught, incl. "nothing": a memory that mispredicted twice in a row is dropped, GridRegistrar._learn)
                 self._pathMemory, self._pathSuspect = reg.path_memory, reg.path_suspect
                 self._pathMemoryDropped = had_memory and reg.path_memory is None
+            repaired = {}
+            if self.failedPairRepair == "stage" and method not in ("surf_full", "orb_full") and not all(row[0] for row in table):
+                table, repaired = self._repairTable(handles, shapes, table, reg.repair)      # while the registration planes are resident
             adjusted = None
             if self.globalAdjust != "none":                  # while the registration planes are still resident (finish releases them)
                 n_ok = 0
@@ -476,6 +497,8 @@ class Stitcher(Utility.Method):
                 status = False
                 describtion = "  " + str(fileList[k]) + " and " + str(fileList[k + 1]) + " can not be stitched"
                 break
+            if k in repaired:
+                self.printAndWrite(self._repairLine(fileList[k], fileList[k + 1], repaired[k]))
             if method not in ("surf_full", "orb_full"):
                 self.direction = int(row[3])
             self.printAndWrite("  The offset of stitching: dx is " + str(int(row[1])) + " dy is " + str(int(row[2])))
@@ -484,6 +507,77 @@ class Stitcher(Utility.Method):
         if adjusted is not None and adjusted[1] is not None:
             self.printAndWrite(adjusted[1])
             offsetList = adjusted[0]
+        return (status, endfileIndex, offsetList, describtion)
+
+    repairReport = None          # the report of the last failedPairRepair = "stage" run (stage.repair_table)
+
+    def _checkRepairOptions(self):
+        """Method.failedPairRepair and its parameters, judged before a file is listed or a tile decoded"""
+        if self.failedPairRepair == "none":
+            return
+        if self.failedPairRepair != "stage":
+            raise ValueError("failedPairRepair must be 'none' or 'stage', got %r" % (self.failedPairRepair,))
+        R, f, K = int(self.repairRadius), int(self.repairFactor), int(self.repairPeaks)
+        if not 1 <= R <= 128:
+            raise ValueError("repairRadius must lie in 1..128, got %r" % (self.repairRadius,))
+        if f not in (2, 4, 8):
+            raise ValueError("repairFactor must be 2, 4 or 8, got %r" % (self.repairFactor,))
+        if -(-R // f) > 16:
+            raise ValueError("repairRadius %d at repairFactor %d leaves a coarse radius of %d (at most 16)" % (R, f, -(-R // f)))
+        if not 1 <= K <= 4:
+            raise ValueError("repairPeaks must lie in 1..4, got %r" % (self.repairPeaks,))
+        if int(self.repairMinPixels) < 0 or not float(self.repairBlankRatio) >= 0.0:
+            raise ValueError("repairMinPixels and repairBlankRatio must not be negative")
+        if not hasattr(self.engine, "ncc_wide_batch") or not hasattr(self.engine, "overlap_sums_batch"):
+            raise NotImplementedError("this engine has no wide correlation search (failedPairRepair = %r)" % (self.failedPairRepair,))
+
+    def _repairTable(self, handles, shapes, table, repair=None):
+        """failedPairRepair = "stage" on a result table over resident gray tiles -> (the repaired table, CUT at the first pair that stays
+        unresolved -- that row is the break, the rows behind it are zero as stop_on_fail leaves them -- and {pair: its report entry} of the
+        repaired pairs).  repair: GridRegistrar.repair of the registrar that made the table, default stage.repair_table on this engine."""
+        if repair is None:
+            from .stage import repair_table
+            repair = lambda h, s, t, **kw: repair_table(self.engine, h, s, t, **kw)      # noqa: E731
+        fixed, report = repair(handles, [tuple(s[:2]) for s in shapes], table, hint=self.pathHint, radius=int(self.repairRadius),
+                               factor=int(self.repairFactor), peaks=int(self.repairPeaks), threshold=float(self.repairThreshold),
+                               min_pixels=int(self.repairMinPixels), blank_ratio=float(self.repairBlankRatio))
+        self.repairReport = report
+        fixed = np.array(fixed, np.int32).reshape(-1, 6)
+        bad = np.flatnonzero(fixed[:, 0] != 1)
+        if len(bad):
+            fixed[bad[0]:] = 0
+        return fixed, {e["pair"]: e for e in report["pairs"] if e["kind"] != "unresolved"}
+
+    @staticmethod
+    def _repairLine(fileA, fileB, entry):
+        how = "measured, score %.3f" % entry["score"] if entry["kind"] == "measured" else "predicted"
+        return "  " + str(fileA) + " and " + str(fileB) + " can not be registered: repaired from the stage model (" + how + ")"
+
+    def _repairPairLoop(self, fileList, rows):
+        """the repair behind flowStitch's pair-by-pair loop: `rows` holds a result row per pair (failed ones zero).  The gray tiles are
+        decoded and uploaded for the call the way _globalAdjust does, and freed.  -> (status, endfileIndex, offsetList, description)"""
+        own = []
+        try:
+            shapes = []
+            for f in fileList:
+                img = _imread(f, False)
+                shapes.append(img.shape[:2])
+                own.append(self.engine.tile_upload(img))
+            table, repaired = self._repairTable(own, shapes, rows)
+        finally:
+            for h in own:
+                self.engine.tile_free(h)
+        offsetList, endfileIndex, status, describtion = [], 0, True, ""
+        for k, row in enumerate(table):
+            if not row[0]:
+                status = False
+                describtion = "  " + str(fileList[k]) + " and " + str(fileList[k + 1]) + " can not be stitched"
+                break
+            if k in repaired:
+                self.printAndWrite(self._repairLine(fileList[k], fileList[k + 1], repaired[k]))
+                self.printAndWrite("  The offset of stitching: dx is " + str(int(row[1])) + " dy is " + str(int(row[2])))
+            offsetList.append([int(row[1]), int(row[2])])
+            endfileIndex = k + 1
         return (status, endfileIndex, offsetList, describtion)
 
     def _globalAdjust(self, fileList, offsetList, handles=None, shapes=None, log=True):
@@ -608,6 +702,7 @@ class Stitcher(Utility.Method):
         self._checkPyramidOutput(outputfileExtension)
         self._deviceJpeg(outputfileExtension)
         self._devicePng(outputfileExtension)
+        self._checkRepairOptions()
         for i in range(startNum, fileNum + 1):
             fileList = _list_images(_join(projectAddress, i), fileExtension)
             outDir = outputAddress.replace("\\", os.sep)
@@ -643,6 +738,7 @@ class Stitcher(Utility.Method):
         self._checkPyramidOutput(outputfileExtension)
         self._deviceJpeg(outputfileExtension)
         self._devicePng(outputfileExtension)
+        self._checkRepairOptions()
         for i in range(startNum, fileNum + 1):
             startTime = time.time()
             fileAddress = _join(projectAddress, i)

@@ -160,6 +160,21 @@ class Method():
     adjustThreshold = 0.5
     adjustMinPixels = 4096
 
+    # ---- repair of pairs that cannot be registered (no reference counterpart; stage.py, tests/stage_ref.py, tests/ncc_wide_ref.py): "stage"
+    # keeps ONE mosaic where a featureless tile would cut it -- the typical offset per scan direction comes from the pairs that did
+    # register, a failed pair is searched by correlation within +-repairRadius px of it (two levels: tiles reduced repairFactor x
+    # repairFactor, then full resolution around the repairPeaks best coarse candidates), and a pair whose overlap carries no signal takes
+    # the model's offset as it is.  repairThreshold is the verifier's threshold (true accepts 0.844 and above, false accepts 0.026 and
+    # below on the committed real strips).  repairBlankRatio is a design choice, not a measurement: the repository holds no real blank
+    # tile; an overlap is blank when the standard deviation of one side is below that fraction of the accepted pairs' median.
+    failedPairRepair = "none"   # "none" or "stage"
+    repairRadius = 32           # 1..128
+    repairFactor = 4            # 2, 4 or 8; ceil(repairRadius / repairFactor) <= 16
+    repairPeaks = 2             # 1..4
+    repairThreshold = 0.5
+    repairMinPixels = 4096
+    repairBlankRatio = 0.25
+
     # ---- enhancement (ImageUtility.py:46-50; CLAHE/equalizeHist are out of the hot-path scope) ----
     isEnhance = False
     isClahe = False

@@ -352,6 +352,27 @@ typedef struct { int64_t tile_a, tile_b; int32_t dx, dy; } vfsms_ncc_job;
 int vfsms_ncc_search_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int radius, int min_pixels,
                            int32_t *best4, int32_t *surface);
 
+/* The same search over a WIDE window in two levels (Method.failedPairRepair = "stage"; no reference counterpart, the specification is
+ * tests/ncc_wide_ref.py and the device equals it bit for bit).  Jobs as above.  Both tiles are reduced by factor x factor block means
+ * (factor 2, 4 or 8; A's blocks start at (dx mod factor, dy mod factor) so that the blocks of the two tiles meet exactly), the reduced
+ * pair is searched with radius ceil(radius / factor) (<= 16) and max(1, min_pixels / factor^2); the `peaks` (1..4) best candidates of
+ * that surface that are no neighbours of each other (Chebyshev distance > 1; order: score, i * i + j * j, i, j) seed one full-resolution
+ * search of radius min(factor, radius) each, centred on factor x the seed, clamped so that the window stays inside [-radius, radius].
+ * out8: int32[n][8] = {ti, tj, fixed-point score, shared pixels of the winner, ci, cj, coarse fixed-point score of the winning seed,
+ * seeds used}: the offset found is (dx + ti, dy + tj); the winner has the largest fixed-point score, ties to the smallest ti * ti +
+ * tj * tj, ti, tj.  seeds (may be NULL): int32[n][VFSMS_WIDE_MAX_PEAKS][6] = {ci, cj, coarse score, ti, tj, fine score} per seed, zeros
+ * in unused rows.  reduced (may be NULL; a test hook, n == 1 only): the two reduced planes, A's then B's, hc x wc bytes each, hc =
+ * (h - dx mod factor) / factor, wc = (w - dy mod factor) / factor.  One launch sequence for all jobs.  VFSMS_ERR_BAD_ARG, with the
+ * outputs untouched: radius outside 1..VFSMS_WIDE_MAX_RADIUS, another factor, ceil(radius / factor) > 16, peaks outside
+ * 1..VFSMS_WIDE_MAX_PEAKS, a colour tile, two shapes in one job, an unknown handle, hc or wc below 1.                               */
+#define VFSMS_WIDE_MAX_RADIUS 128
+#define VFSMS_WIDE_MAX_PEAKS 4
+int vfsms_ncc_wide_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int radius, int factor, int peaks, int min_pixels,
+                         int32_t *out8, int32_t *seeds, uint8_t *reduced);
+/* The six integers of vfsms_verify_ncc at each job's own offset, for n pairs of resident single-channel tiles of one shape per job
+ * (tests/verify_ref.py: sums): out6 = int64[n][6] = {N, Sa, Sb, Saa, Sbb, Sab}; an empty overlap gives zeros.                       */
+int vfsms_overlap_sums_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int64_t *out6);
+
 /* cv2.phaseCorrelate(np.float64(a), np.float64(b)) (Stitcher.py:230): out3 = {x, y, response}     */
 int vfsms_phase_correlate_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, int h, int w,
                              int stride_a, int stride_b, double *out3);
