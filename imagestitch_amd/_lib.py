@@ -208,6 +208,8 @@ _SIGNATURES = {
     "vfsms_shading_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_shading_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "vfsms_shading_free": (C.c_int, [C.c_void_p, C.c_int64]),
+    "vfsms_focus_stack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_focus_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_overlap_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_exposure_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
@@ -1145,6 +1147,38 @@ class Engine:
     def shading_free(self, field):
         self._check(self.lib.vfsms_shading_free(self.ctx, C.c_int64(field)))
         self.__dict__.get("_shapes", {}).pop(("field", field), None)
+
+    # -- focus stacking (tests/focus_ref.py is the specification) --------------------------------------------------------------
+    FOCUS_MODES = {"pixel": 0, "plane": 1}
+
+    def focus_stack(self, handles, mode="pixel", radius=4, median=1, want_tile=False):
+        """A focus series fused into one tile (vfsms_focus_stack): 2..64 resident planes of one shape, gray or B G R.  mode "pixel": per
+        pixel the plane whose sum-modified Laplacian, summed over (2 radius + 1)^2, is largest (the lowest index on a tie), the index map
+        cleaned by one 3 x 3 median when `median`; mode "plane": the whole plane of the largest score.  -> (out, D, S): out the fused
+        array of the planes' shape, or with want_tile the handle of a NEW resident tile (tile_free); D uint8 (h, w) the plane index per
+        pixel; S int64 [n] the per-plane scores.  The planes are only read."""
+        if mode not in self.FOCUS_MODES:
+            raise ValueError("focus_stack: mode must be 'pixel' or 'plane', got %r" % (mode,))
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        shape = self.__dict__.get("_shapes", {}).get(("tile", int(th[0]))) if len(th) else None
+        if shape is None:                                     # no plane, or not a tile of this engine: the library's refusal says which
+            self._check(self.lib.vfsms_focus_stack(self.ctx, len(th), _ptr(th), self.FOCUS_MODES[mode], int(radius), int(median), None, None, None, None))
+            raise ValueError("focus_stack: the planes are tiles of this engine (tile_upload, tile_upload_color, tile_reserve, tile_wrap)")
+        out = None if want_tile else np.empty(shape, np.uint8)
+        D = np.empty(shape[:2], np.uint8)
+        S = np.zeros(len(th), np.int64)
+        tile = C.c_int64(0)
+        self._check(self.lib.vfsms_focus_stack(self.ctx, len(th), _ptr(th), self.FOCUS_MODES[mode], int(radius), int(median),
+                                               C.byref(tile) if want_tile else None, _ptr(out), _ptr(D), _ptr(S)))
+        return (self._note_tile(tile.value, shape) if want_tile else out), D, S
+
+    def focus_scores(self, handles):
+        """vfsms_focus_scores: the sum of the sum-modified Laplacian over each of 1..4096 resident tiles (any shapes, gray or B G R)
+        -> int64 [n] (tests/focus_ref.py: scores)"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        S = np.zeros(len(th), np.int64)
+        self._check(self.lib.vfsms_focus_scores(self.ctx, len(th), _ptr(th), _ptr(S)))
+        return S
 
     # -- exposure compensation (tests/exposure_ref.py is the specification) -------------------------------------------------
     def overlap_stats_batch(self, jobs, lo, hi):

@@ -2819,6 +2819,105 @@ extern "C" int vfsms_shading_free(vfsms_ctx *ctx, int64_t field)
     return VFSMS_OK;
 }
 
+// ---- focus stacking (Method.focusStack; focus_kernels.hip, specified by tests/focus_ref.py) ----------------------------------------------
+// the tiles of a focus call: known, gray or B G R, of one shape when `same`, handed over (tile_ready) -- judged before anything is enqueued
+static int focus_tiles(vfsms_ctx *ctx, const char *what, int n, int lo, int hi, const int64_t *tiles, bool same, std::vector<FocusTileHost> &H)
+{
+    if (n < lo || n > hi || !tiles) { vfsms_set_error("%s: %d..%d tiles, got %d", what, lo, hi, n); return VFSMS_ERR_BAD_ARG; }
+    std::vector<TileRec *> T(n);
+    for (int i = 0; i < n; i++) {
+        auto it = ctx->tiles.find(tiles[i]);
+        if (it == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", what); return VFSMS_ERR_BAD_ARG; }
+        T[i] = &it->second;
+        if (T[i]->ch != 1 && T[i]->ch != 3) { vfsms_set_error("%s: tile %d has %d channels (1 or 3)", what, i, T[i]->ch); return VFSMS_ERR_BAD_ARG; }
+        if (same && (T[i]->h != T[0]->h || T[i]->w != T[0]->w || T[i]->ch != T[0]->ch)) {
+            vfsms_set_error("%s: plane %d is %d x %d x %d, plane 0 is %d x %d x %d", what, i, T[i]->h, T[i]->w, T[i]->ch, T[0]->h, T[0]->w, T[0]->ch);
+            return VFSMS_ERR_BAD_ARG;
+        }
+    }
+    H.resize(n);
+    for (int i = 0; i < n; i++) {
+        TRY(tile_ready(ctx, *T[i]));
+        H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride; H[i].h = T[i]->h; H[i].w = T[i]->w; H[i].ch = T[i]->ch;
+    }
+    return VFSMS_OK;
+}
+// what a focus call enqueues between its checks and its read-back; d_out: the new tile's buffer or arena memory
+static int focus_run(vfsms_ctx *ctx, const std::vector<FocusTileHost> &H, int mode, int radius, int median, uint8_t *d_out, uint8_t *d_pre, uint8_t *d_index,
+                     unsigned long long *d_scores, uint32_t *d_partials, std::vector<unsigned long long> &S)
+{
+    const int n = (int)H.size(), h = H[0].h, w = H[0].w, ch = H[0].ch;
+    FocusPlane *d_tab;
+    TRY(focus_table_device(ctx, H.data(), n, &d_tab));
+    int const_d = -1;
+    if (mode == 0) TRY(focus_select_device(ctx, d_tab, n, h, w, ch, radius, d_pre, d_scores, d_partials));
+    else TRY(focus_scores_device(ctx, H.data(), n, d_scores));
+    HIP_TRY(hipMemcpyAsync(S.data(), d_scores, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (mode == 1) {                                         // the plane of the largest score, the first of them
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        const_d = (int)(std::max_element(S.begin(), S.end()) - S.begin());
+    }
+    TRY(focus_compose_device(ctx, d_tab, d_pre, h, w, ch, median, const_d, d_out, w * ch, d_index));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_focus_stack(vfsms_ctx *ctx, int n, const int64_t *planes, int mode, int radius, int median, int64_t *out_tile, uint8_t *out_host,
+                                 uint8_t *index, int64_t *scores)
+{
+    CTX_ENTER(ctx);
+    if ((mode != 0 && mode != 1) || radius < 1 || radius > VFSMS_FOCUS_MAX_RADIUS || (median != 0 && median != 1)) {
+        vfsms_set_error("focus_stack: mode %d / radius %d / median %d (0 pixel or 1 plane; 1..%d; 0 or 1)", mode, radius, median, VFSMS_FOCUS_MAX_RADIUS);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    std::vector<FocusTileHost> H;
+    TRY(focus_tiles(ctx, "focus_stack", n, VFSMS_FOCUS_MIN_PLANES, VFSMS_FOCUS_MAX_PLANES, planes, true, H));
+    const int h = H[0].h, w = H[0].w, ch = H[0].ch;
+    const size_t px = (size_t)h * w, bytes = px * ch;
+    const size_t pbytes = mode == 0 ? focus_partials_bytes(n, h, w) : 0;
+    TRY(ctx_arena_reserve(ctx, 2 * px + (out_tile ? 0 : bytes) + pbytes + (sizeof(FocusTileHost) * 2 + 8) * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    uint8_t *d_pre = (uint8_t *)ctx_arena_alloc(ctx, px), *d_index = (uint8_t *)ctx_arena_alloc(ctx, px);
+    unsigned long long *d_scores = (unsigned long long *)ctx_arena_alloc(ctx, sizeof(unsigned long long) * n);
+    uint8_t *d_out = out_tile ? nullptr : (uint8_t *)ctx_arena_alloc(ctx, bytes);
+    uint32_t *d_partials = (uint32_t *)ctx_arena_alloc(ctx, pbytes ? pbytes : 4);
+    if (!d_pre || !d_index || !d_scores || !d_partials || (!out_tile && !d_out)) { vfsms_set_error("arena exhausted (focus_stack)"); return VFSMS_ERR_CAPACITY; }
+    if (out_tile) TRY(tile_buffer(ctx, bytes, &d_out, ctx->stream));
+    std::vector<unsigned long long> S(n);
+    int rc = focus_run(ctx, H, mode, radius, median, d_out, d_pre, d_index, d_scores, d_partials, S);
+    if (rc == VFSMS_OK && out_host && hipMemcpy(out_host, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) { vfsms_set_error("focus_stack: the download failed"); rc = VFSMS_ERR_HIP; }
+    if (rc == VFSMS_OK && index && hipMemcpy(index, d_index, px, hipMemcpyDeviceToHost) != hipSuccess) { vfsms_set_error("focus_stack: the download failed"); rc = VFSMS_ERR_HIP; }
+    if (rc != VFSMS_OK) {
+        hipStreamSynchronize(ctx->stream);                   // (nothing enqueued may still write the buffer that goes back to the pool)
+        if (out_tile) { PoolEnt pe; pe.bytes = bytes; pe.ptr = d_out; pe.idle = nullptr; ctx->tile_pool.push_back(pe); ctx->tile_pool_bytes += bytes; }
+        return rc;
+    }
+    if (scores) for (int i = 0; i < n; i++) scores[i] = (int64_t)S[i];
+    if (out_tile) {
+        TileRec t; t.ptr = d_out; t.h = h; t.w = w; t.stride = w * ch; t.owned = true; t.ready = nullptr; t.pending = false; t.ch = ch; t.bytes = bytes;
+        std::lock_guard<std::mutex> lk(ctx->tiles_mu);
+        *out_tile = ctx->next_handle++;
+        ctx->tiles[*out_tile] = t;
+    }
+    return VFSMS_OK;
+}
+extern "C" int vfsms_focus_scores(vfsms_ctx *ctx, int n, const int64_t *tiles, int64_t *scores)
+{
+    CTX_ENTER(ctx);
+    if (!scores) { vfsms_set_error("focus_scores: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    std::vector<FocusTileHost> H;
+    TRY(focus_tiles(ctx, "focus_scores", n, 1, VFSMS_FOCUS_MAX_TILES, tiles, false, H));
+    TRY(ctx_arena_reserve(ctx, (sizeof(FocusTileHost) * 2 + 8) * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    unsigned long long *d_scores = (unsigned long long *)ctx_arena_alloc(ctx, sizeof(unsigned long long) * n);
+    if (!d_scores) { vfsms_set_error("arena exhausted (focus_scores)"); return VFSMS_ERR_CAPACITY; }
+    TRY(focus_scores_device(ctx, H.data(), n, d_scores));
+    std::vector<unsigned long long> S(n);
+    HIP_TRY(hipMemcpyAsync(S.data(), d_scores, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n; i++) scores[i] = (int64_t)S[i];
+    return VFSMS_OK;
+}
+
 // ---- exposure compensation (Method.exposureCompensation; exposure_kernels.hip, specified by tests/exposure_ref.py) -----------------------
 // vfsms_overlap_stats_batch: every launch of the batch is enqueued before the one synchronisation that brings the sums back
 extern "C" int vfsms_overlap_stats_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int lo, int hi, int64_t *out3)

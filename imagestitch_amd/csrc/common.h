@@ -430,6 +430,21 @@ struct ExpJob { const uint8_t *a, *b; int sa, sb, wa, wb, r0, nrows, c0, c1, dx,
 struct ExpTileHost { uint8_t *ptr; int stride, h, wb; };
 int overlap_stats_device(vfsms_ctx *ctx, const ExpPairHost *pairs, int n, int lo, int hi, unsigned long long *d_out3);   // d_out3: [n][3] = N, Sa, Sb
 int exposure_apply_device(vfsms_ctx *ctx, const ExpTileHost *tiles, int n, const uint16_t *gain_q12);
+// focus_kernels.hip: Method.focusStack.  Tiles as (pointer, row stride in bytes, rows, columns, channels); FocusPlane: the same as the kernels
+// read it, uploaded once per call (focus_table_device).  d_index: h x w bytes, D before the median; d_scores: n sums, set by the launchers
+#define VFSMS_FOCUS_MIN_PLANES 2
+#define VFSMS_FOCUS_MAX_PLANES 64
+#define VFSMS_FOCUS_MAX_RADIUS 31
+#define VFSMS_FOCUS_MAX_TILES 4096
+struct FocusTileHost { const uint8_t *ptr; int stride, h, w, ch; };
+struct FocusPlane;
+int focus_table_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, FocusPlane **d_tab);
+int focus_scores_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, unsigned long long *d_scores);
+size_t focus_partials_bytes(int n, int h, int w);          // d_partials of focus_select_device: the blocks' shares of the scores
+int focus_select_device(vfsms_ctx *ctx, const FocusPlane *d_tab, int n, int h, int w, int ch, int radius, uint8_t *d_index, unsigned long long *d_scores,
+                        uint32_t *d_partials);
+int focus_compose_device(vfsms_ctx *ctx, const FocusPlane *d_tab, const uint8_t *d_index, int h, int w, int ch, int median, int const_d,
+                         uint8_t *d_out, int out_stride, uint8_t *d_index_out);
 // jpeg_host.cpp / jpeg_enc_kernels.hip: the device JPEG encoder (tests/jpeg_enc_ref.py)
 const uint8_t *jpeg_std_huff_bits(int ac, int chroma);
 const uint8_t *jpeg_std_huff_vals(int ac, int chroma);

@@ -733,6 +733,22 @@ class Stitcher(Utility.Method):
             if status == False:
                 self.printAndWrite("stitching Failed")
 
+    def imageSetFocusStack(self, projectAddress, stackedAddress, fileNum, startNum=1, fileExtension="jpg", outputfileExtension="png"):
+        """Method.focusStack in front of the pipeline (no reference counterpart; focus.fuse_dataset, tests/focus_ref.py): the folders
+        projectAddress/i of imageSetStitch, each holding focusPlanes consecutive files per stage position, go to stackedAddress/i with one
+        fused tile per position, which the unchanged imageSetStitch* then reads.  -> the files written, folder by folder."""
+        from .focus import check_options, fuse_dataset
+        if self.focusStack == "none":
+            raise ValueError("imageSetFocusStack needs focusStack = 'pixel' or 'plane' (it is 'none')")
+        check_options(self.focusStack, self.focusPlanes, self.focusRadius, self.focusMedian)      # before a file is listed
+        if not hasattr(self.engine, "focus_stack"):
+            raise NotImplementedError("this engine has no focus stacking (focusStack = %r)" % (self.focusStack,))
+        written = []
+        for i in range(startNum, fileNum + 1):
+            fileList = _list_images(_join(projectAddress, i), fileExtension)
+            written.append(fuse_dataset(self, fileList, int(self.focusPlanes), _join(stackedAddress, i), outputfileExtension))
+        return written
+
     def imageSetStitchWithMutiple(self, projectAddress, outputAddress, fileNum, caculateOffsetMethod, startNum=1, fileExtension="jpg", outputfileExtension="jpg"):
         """Stitcher.py:153-182 (the entry point Main.py:20-51 uses)."""
         self._checkPyramidOutput(outputfileExtension)

@@ -199,6 +199,19 @@ class Method():
     shadingMinTiles = 8
     shadingGain = None
 
+    # ---- focus stacking in front of the pipeline (no reference counterpart; focus.py, tests/focus_ref.py): Stitcher.imageSetFocusStack
+    # fuses the focusPlanes consecutive files of every stage position into one all-in-focus tile, which imageSetStitch* then reads like
+    # any other.  "pixel": per pixel the plane whose sum-modified Laplacian, summed over (2 focusRadius + 1)^2, is largest, the index
+    # map cleaned by focusMedian passes (0 or 1) of a 3 x 3 median; "plane": the whole plane of the largest score.  focusDepthMaps also
+    # writes the index map of every position.  focusRadius = 4 and the one median pass rest on nothing measured on real material: they
+    # come from the synthetic stacks of tests/focus_cases.py only (tests/test_focus_host.py), the repository holds no real focus series.
+    # The defaults change nothing: no entry point of the pipeline reads these attributes.
+    focusStack = "none"         # "none", "pixel" or "plane"
+    focusPlanes = 1             # files per stage position, 2..64 when focusStack is not "none"
+    focusRadius = 4             # 1..31
+    focusMedian = 1             # 0 or 1
+    focusDepthMaps = False
+
     # ---- per-tile exposure compensation after the shading correction, before the mosaic is laid out (no reference counterpart;
     # exposure.py, tests/exposure_ref.py): "gain" sums, over every overlap of two tiles of the mosaic, the samples that are unclipped in
     # both, fits one gain per tile by weighted least squares in the log domain and multiplies the resident tiles by it (registration

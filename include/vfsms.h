@@ -701,6 +701,23 @@ int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *til
 /* releases a field of vfsms_shading_estimate / vfsms_shading_from_gain (tests/shading_ref.py has no state to free)              */
 int vfsms_shading_free(vfsms_ctx *ctx, int64_t field);
 
+/* ---- focus stacking (Method.focusStack).  No reference counterpart: the arithmetic, all integer, is this library's own
+ * specification, tests/focus_ref.py, and every stage equals it exactly. ----------------------------------------------------------- */
+/* n (2..64) resident planes of one shape, gray or B G R (1 or 3 channels; any row stride and base), fused into one tile.  Mode 0
+ * "pixel": the luma L = the byte or (29 B + 150 G + 77 R + 128) >> 8, the sum-modified Laplacian M = |2L - L(x-1) - L(x+1)| +
+ * |2L - L(y-1) - L(y+1)| with clamped indices, its box sum F over (2 radius + 1)^2 with clamped indices (radius 1..31), D = the
+ * smallest plane index of the largest F per pixel, with median 1 replaced once by the median of its 3 x 3 neighbourhood (clamped),
+ * out = plane[D].  Mode 1 "plane": the whole plane of the largest score, the first of them; D is constant.  scores[i] = the sum of
+ * M_i over the plane, in both modes (tests/focus_ref.py: fuse).  out_tile (may be NULL): a NEW resident tile, freed with
+ * vfsms_tile_free; out_host (may be NULL): dense [h][w][ch]; index (may be NULL): D, [h][w]; scores (may be NULL): [n].
+ * Waits for reserved / pending tiles like every batch call; the planes are only read.  VFSMS_ERR_BAD_ARG, with nothing written and
+ * no tile created: n outside 2..64, an unknown handle, planes of different shape or channel count, a channel count other than 1 or
+ * 3, radius outside 1..31, a median other than 0 or 1, a mode other than 0 or 1.                                                  */
+int vfsms_focus_stack(vfsms_ctx *ctx, int n, const int64_t *planes, int mode, int radius, int median,
+                      int64_t *out_tile, uint8_t *out_host, uint8_t *index, int64_t *scores);
+/* scores[i] = the sum of M over tile i (tests/focus_ref.py: scores): n (1..4096) resident tiles of any shapes, gray or B G R     */
+int vfsms_focus_scores(vfsms_ctx *ctx, int n, const int64_t *tiles, int64_t *scores);
+
 /* ---- per-tile exposure compensation (Method.exposureCompensation).  No reference counterpart: the specification is
  * tests/exposure_ref.py; the sums and the corrected bytes are integers and equal it exactly. ------------------------------------ */
 /* The overlap statistic of n pairs of resident tiles (gray or interleaved colour, both tiles of a job of one channel count, any
