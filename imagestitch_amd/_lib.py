@@ -212,6 +212,10 @@ _SIGNATURES = {
     "vfsms_focus_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_overlap_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_exposure_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfsms_block_ncc_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfsms_lens_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
+    "vfsms_lens_remap_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -1202,6 +1206,55 @@ class Engine:
             raise ValueError("exposure_apply: one Q12 gain in 0..65535 per tile")
         g = np.ascontiguousarray(g, np.uint16)
         self._check(self.lib.vfsms_exposure_apply(self.ctx, len(th), _ptr(th), _ptr(g)))
+
+    # -- lens correction (tests/lens_ref.py is the specification) -------------------------------------------------------------
+    LENS_INTERPOLATIONS = {"bilinear": 0, "cubic": 1}
+
+    def block_ncc_batch(self, jobs, first, block, radius, want_surface=False):
+        """vfsms_block_ncc_batch: jobs = sequence of (tile_a, tile_b, dx, dy) over resident tiles, both of a job of one shape and channel
+        count (gray or B G R); first = int64 [n + 1], the index of every job's first block and the total (lens.block_first): the library
+        checks it against the lattice.  Every block x block square of the overlap shrunk by `radius` (block 8..128 in multiples of 8,
+        radius 1..16) is scored at every (i, j) in [-radius, radius]^2 as verify_ncc scores an overlap.
+        -> int32[blocks, 4] = (i, j, fixed-point score, block^2) of the best candidate per block [, int32[blocks, 2 radius + 1,
+        2 radius + 1], the fixed-point score of every candidate, with want_surface]"""
+        n = len(jobs)
+        first = np.ascontiguousarray(first, np.int64).reshape(-1)
+        if len(first) != n + 1:
+            raise ValueError("block_ncc_batch: %d jobs need %d entries of first, got %d" % (n, n + 1, len(first)))
+        total = max(int(first[-1]), 0)
+        side = 2 * int(radius) + 1
+        best = np.zeros((total, 4), np.int32)
+        surface = np.zeros((total, side, side), np.int32) if want_surface else None
+        self._check(self.lib.vfsms_block_ncc_batch(self.ctx, self._ncc_jobs(jobs), n, int(block), int(radius), _ptr(first), _ptr(best),
+                                                   _ptr(surface)))
+        return (best, surface) if want_surface else best
+
+    def lens_apply(self, handles, a1_q30, a2_q30, centre2=(-1, -1), interpolation="cubic"):
+        """the tiles resampled in place under the radial map of tests/lens_ref.py (vfsms_lens_apply): Q30 coefficients, the centre in
+        half pixels (a coordinate below 0: every tile's own middle); owned tiles of any shapes, each named once"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        self._check(self.lib.vfsms_lens_apply(self.ctx, len(th), _ptr(th), int(a1_q30), int(a2_q30), int(centre2[0]), int(centre2[1]),
+                                              self._lens_interp(interpolation)))
+
+    def lens_remap(self, img, a1_q30, a2_q30, centre2=(-1, -1), interpolation="cubic"):
+        """vfsms_lens_remap_u8: the same map for a host array, (h, w) or (h, w, ch) uint8 with any row stride -> a new array"""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3):
+            raise ValueError("lens_remap takes an (h, w) or (h, w, ch) uint8 array, got %s %s" % (img.dtype, img.shape))
+        ch = img.shape[2] if img.ndim == 3 else 1
+        if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != ch) or img.strides[0] < img.shape[1] * ch:
+            img = np.ascontiguousarray(img)
+        out = np.empty(img.shape, np.uint8)
+        self._check(self.lib.vfsms_lens_remap_u8(self.ctx, _ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], int(a1_q30), int(a2_q30),
+                                                 int(centre2[0]), int(centre2[1]), self._lens_interp(interpolation), _ptr(out)))
+        return out
+
+    def _lens_interp(self, interpolation):
+        if isinstance(interpolation, str):
+            if interpolation not in self.LENS_INTERPOLATIONS:
+                raise ValueError("interpolation must be 'bilinear' or 'cubic', got %r" % (interpolation,))
+            return self.LENS_INTERPOLATIONS[interpolation]
+        return int(interpolation)                             # (a number goes to the library as it is: its refusal says what it takes)
 
     def canvas_download(self, handle, rows, cols, ch):
         out = np.empty((rows, cols, ch) if ch > 1 else (rows, cols), np.uint8)

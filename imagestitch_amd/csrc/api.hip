@@ -2970,6 +2970,98 @@ extern "C" int vfsms_exposure_apply(vfsms_ctx *ctx, int n, const int64_t *tiles,
     return VFSMS_OK;
 }
 
+// ---- lens correction (Method.lensCorrection; lens_kernels.hip, specified by tests/lens_ref.py) ---------------------------------------------
+// vfsms_block_ncc_batch: the launch of the batch is enqueued before the one synchronisation that brings the results back
+extern "C" int vfsms_block_ncc_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int block, int radius, const int64_t *first,
+                                     int32_t *best4, int32_t *surface)
+{
+    CTX_ENTER(ctx);
+    if (n < 0 || !first || (n > 0 && !jobs)) { vfsms_set_error("block_ncc: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    if (block < 8 || block > VFSMS_LENS_MAX_BLOCK || block % 8) { vfsms_set_error("block_ncc: block %d is no multiple of 8 in 8..%d", block, VFSMS_LENS_MAX_BLOCK); return VFSMS_ERR_BAD_ARG; }
+    if (radius < 1 || radius > VFSMS_LENS_MAX_RADIUS) { vfsms_set_error("block_ncc: radius %d outside 1..%d", radius, VFSMS_LENS_MAX_RADIUS); return VFSMS_ERR_BAD_ARG; }
+    std::vector<LensBlockHost> H(n);
+    std::vector<long long> F(n + 1, 0);
+    for (int k = 0; k < n; k++) {
+        TileRec *pA, *pB;
+        TRY(resident_pair(ctx, "block_ncc", k, jobs[k], &pA, &pB));
+        const TileRec &A = *pA, &B = *pB;
+        if (A.ch != B.ch || (A.ch != 1 && A.ch != 3)) { vfsms_set_error("block_ncc: the tiles of job %d have %d and %d channels (both 1 or both 3)", k, A.ch, B.ch); return VFSMS_ERR_BAD_ARG; }
+        if (A.h != B.h || A.w != B.w) { vfsms_set_error("block_ncc: the tiles of job %d are %d x %d and %d x %d", k, A.h, A.w, B.h, B.w); return VFSMS_ERR_BAD_ARG; }
+        H[k] = LensBlockHost{A.ptr, B.ptr, A.stride, B.stride, A.h, A.w, A.ch, jobs[k].dx, jobs[k].dy};
+        int r0, c0, nby, nbx;
+        lens_lattice(A.h, A.w, jobs[k].dx, jobs[k].dy, block, radius, &r0, &c0, &nby, &nbx);
+        F[k + 1] = F[k] + (long long)nby * nbx;
+    }
+    for (int k = 0; k <= n; k++)
+        if (first[k] != F[k]) { vfsms_set_error("block_ncc: first[%d] is %lld, the lattice gives %lld", k, (long long)first[k], F[k]); return VFSMS_ERR_BAD_ARG; }
+    const size_t total = (size_t)F[n], CC = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    if (total == 0) return VFSMS_OK;
+    if (!best4) { vfsms_set_error("block_ncc: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(ctx_arena_reserve(ctx, (sizeof(LensBlockHost) + 16) * ((size_t)n + 1) + sizeof(int32_t) * total * (4 + (surface ? CC : 0)) + 65536));
+    ctx->pinned_off = 0;
+    int32_t *d_best = (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * 4 * total);
+    int32_t *d_surf = surface ? (int32_t *)ctx_arena_alloc(ctx, sizeof(int32_t) * CC * total) : nullptr;
+    if (!d_best || (surface && !d_surf)) { vfsms_set_error("block_ncc: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    TRY(lens_blocks_device(ctx, H.data(), F.data(), n, block, radius, d_best, d_surf));
+    HIP_TRY(hipMemcpyAsync(best4, d_best, sizeof(int32_t) * 4 * total, hipMemcpyDeviceToHost, ctx->stream));
+    if (surface) HIP_TRY(hipMemcpyAsync(surface, d_surf, sizeof(int32_t) * CC * total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+// what both resampling calls refuse of their map, for an h x w image; a centre coordinate below 0 is the image's own middle
+static int lens_check_map(const char *who, int h, int w, int32_t a1_q30, int32_t a2_q30, int32_t cy2, int32_t cx2, int interp)
+{
+    if (interp != 0 && interp != 1) { vfsms_set_error("%s: interp %d (0 bilinear or 1 cubic)", who, interp); return VFSMS_ERR_BAD_ARG; }
+    if (a1_q30 < -VFSMS_LENS_MAX_COEF || a1_q30 > VFSMS_LENS_MAX_COEF || a2_q30 < -VFSMS_LENS_MAX_COEF || a2_q30 > VFSMS_LENS_MAX_COEF) {
+        vfsms_set_error("%s: coefficients %d, %d outside +-2^28 (Q30)", who, a1_q30, a2_q30); return VFSMS_ERR_BAD_ARG;
+    }
+    if (h > VFSMS_LENS_MAX_SIDE || w > VFSMS_LENS_MAX_SIDE) { vfsms_set_error("%s: an image of %d x %d (sides up to %d)", who, h, w, VFSMS_LENS_MAX_SIDE); return VFSMS_ERR_BAD_ARG; }
+    const long long ey = cy2 < 0 ? 0 : 2ll * std::abs((long long)cy2 - (h - 1)), ex = cx2 < 0 ? 0 : 2ll * std::abs((long long)cx2 - (w - 1));
+    if (ey > h - 1 || ex > w - 1) { vfsms_set_error("%s: the centre (%d, %d) / 2 lies outside the middle half of a %d x %d image", who, cy2, cx2, h, w); return VFSMS_ERR_BAD_ARG; }
+    return VFSMS_OK;
+}
+extern "C" int vfsms_lens_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, int32_t a1_q30, int32_t a2_q30, int32_t cy2, int32_t cx2, int interp)
+{
+    CTX_ENTER(ctx);
+    if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles) { vfsms_set_error("lens_apply: 1..%d tiles", VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
+    std::vector<int64_t> seen(tiles, tiles + n);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("lens_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
+    std::vector<TileRec *> T(n);
+    for (int i = 0; i < n; i++) {
+        auto it = ctx->tiles.find(tiles[i]);
+        if (it == ctx->tiles.end()) { vfsms_set_error("lens_apply: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
+        T[i] = &it->second;
+        if (!T[i]->owned) { vfsms_set_error("lens_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
+        TRY(lens_check_map("lens_apply", T[i]->h, T[i]->w, a1_q30, a2_q30, cy2, cx2, interp));
+    }
+    std::vector<LensTileHost> H(n);
+    for (int i = 0; i < n; i++) {
+        TRY(tile_ready(ctx, *T[i]));
+        H[i] = LensTileHost{T[i]->ptr, T[i]->stride, T[i]->h, T[i]->w, T[i]->ch};
+    }
+    TRY(lens_apply_device(ctx, H.data(), n, a1_q30, a2_q30, cy2, cx2, interp));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_lens_remap_u8(vfsms_ctx *ctx, const uint8_t *src, int h, int w, int ch, int src_stride, int32_t a1_q30, int32_t a2_q30,
+                                   int32_t cy2, int32_t cx2, int interp, uint8_t *dst)
+{
+    CTX_ENTER(ctx);
+    if (!src || !dst || h <= 0 || w <= 0 || ch < 1 || ch > 4 || src_stride < w * ch) { vfsms_set_error("lens_remap: bad arguments"); return VFSMS_ERR_BAD_ARG; }
+    TRY(lens_check_map("lens_remap", h, w, a1_q30, a2_q30, cy2, cx2, interp));
+    const size_t bytes = (size_t)h * w * ch;
+    TRY(ctx_arena_reserve(ctx, 2 * bytes + 65536));
+    ctx->pinned_off = 0;
+    uint8_t *d_src, *d_dst = (uint8_t *)ctx_arena_alloc(ctx, bytes);
+    if (!d_dst) { vfsms_set_error("lens_remap: arena exhausted"); return VFSMS_ERR_CAPACITY; }
+    TRY(upload_image(ctx, src, h, w * ch, src_stride, &d_src));
+    TRY(lens_remap_device(ctx, d_src, d_dst, w * ch, h, w, ch, a1_q30, a2_q30, cy2, cx2, interp));
+    HIP_TRY(hipMemcpyAsync(dst, d_dst, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VFSMS_OK;
+}
+
 // ---- ORB -------------------------------------------------------------------------------------------------------------------------
 static void orb_caps(const vfsms_orb_params *p, int *cap1, int *cap2, int *cap)
 {

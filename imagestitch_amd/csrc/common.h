@@ -250,6 +250,7 @@ struct vfsms_ctx {
     DevBuf seam_scratch;                                           // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
     DevBuf shade_scratch;                                          // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
     std::unordered_map<int64_t, ShadeRec> shade_fields;
+    DevBuf lens_scratch;                                           // the copy a tile is resampled from (lens_kernels.hip): grown to the largest tile, freed with the context
     DevBuf sift_scratch;                                           // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     DevBuf sift_kp;                                                // SIFT candidates, keypoints and descriptors, likewise
     std::vector<SiftChunk> sift_pool;                              // what a SIFT strip keeps until the match stage of its batch (positions, descriptors, their int8 form): reused from call to call, freed with the context
@@ -445,6 +446,21 @@ int focus_select_device(vfsms_ctx *ctx, const FocusPlane *d_tab, int n, int h, i
                         uint32_t *d_partials);
 int focus_compose_device(vfsms_ctx *ctx, const FocusPlane *d_tab, const uint8_t *d_index, int h, int w, int ch, int median, int const_d,
                          uint8_t *d_out, int out_stride, uint8_t *d_index_out);
+// lens_kernels.hip: Method.lensCorrection (tests/lens_ref.py).  A block job: two whole tiles of ONE shape and channel count (pointers, row
+// strides in bytes) and the offset (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)); lens_lattice: its block lattice.  A tile
+// to resample: pointer, row stride in bytes, rows, columns, channels.  A centre coordinate below 0 stands for the tile's own middle
+#define VFSMS_LENS_MAX_RADIUS 16
+#define VFSMS_LENS_MAX_BLOCK 128
+#define VFSMS_LENS_MAX_SIDE 16384
+#define VFSMS_LENS_MAX_COEF (1 << 28)
+struct LensBlockHost { const uint8_t *a, *b; int sa, sb, h, w, ch, dx, dy; };
+struct LensTileHost { uint8_t *ptr; int stride, h, w, ch; };
+void lens_lattice(int h, int w, int dx, int dy, int block, int radius, int *r0, int *c0, int *nby, int *nbx);
+int lens_blocks_device(vfsms_ctx *ctx, const LensBlockHost *jobs, const long long *h_first, int njobs, int block, int radius,
+                       int32_t *d_best4, int32_t *d_surface);
+int lens_remap_device(vfsms_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, int dstride, int h, int w, int ch, int a1_q30, int a2_q30,
+                      int cy2, int cx2, int interp);
+int lens_apply_device(vfsms_ctx *ctx, const LensTileHost *tiles, int n, int a1_q30, int a2_q30, int cy2, int cx2, int interp);
 // jpeg_host.cpp / jpeg_enc_kernels.hip: the device JPEG encoder (tests/jpeg_enc_ref.py)
 const uint8_t *jpeg_std_huff_bits(int ac, int chroma);
 const uint8_t *jpeg_std_huff_vals(int ac, int chroma);

@@ -1217,6 +1217,8 @@ class Stitcher(Utility.Method):
                     use_res = True
             if self.shadingCorrection != "none":
                 self._correctShading(handles if use_res else None, shapes)
+            if self.lensCorrection != "none":                # geometry before exposure: its statistics then see aligned overlaps
+                self._correctLens(handles if use_res else None, shapes, originOffsetList)
             if self.exposureCompensation != "none":
                 self._compensateExposure(handles if use_res else None, shapes, originOffsetList)
             offsetList, rangeX, rangeY, resultRow, resultCol = self._layout(shapes, originOffsetList)
@@ -1314,6 +1316,39 @@ class Stitcher(Utility.Method):
             eng.shading_apply(field, tiles)
         finally:
             eng.shading_free(field)
+
+    def _correctLens(self, handles, shapes, originOffsetList):
+        """Method.lensCorrection on the mosaic's resident tiles, in place (lens.correct, tests/lens_ref.py): one radial model per dataset
+        from the overlaps under the offsets the mosaic is laid out by (originOffsetList carries the leading [0, 0]), the tiles resampled,
+        and the path offsets measured again on the corrected tiles -- the entries of originOffsetList that moved are replaced.  Runs
+        behind the shading correction and in front of the exposure compensation.  After "estimate" the fitted pair is left in
+        self.lensCoefficients for a later "given" run.  The registration itself is untouched: registering on corrected planes is out of
+        scope."""
+        eng = self.engine
+        if self.lensCorrection not in ("estimate", "given"):
+            raise ValueError("lensCorrection must be 'none', 'estimate' or 'given'")
+        if not hasattr(eng, "block_ncc_batch") or not hasattr(eng, "lens_apply") or handles is None:
+            raise NotImplementedError("lensCorrection needs an engine with block_ncc_batch / lens_apply and device-resident tiles")
+        if len({tuple(s_) for s_ in shapes}) != 1:
+            raise ValueError("lensCorrection needs tiles of one shape, got %s" % sorted({tuple(s_) for s_ in shapes}))
+        from .lens import correct
+        offsets, pair, self.lensReport = correct(eng, handles, shapes, originOffsetList[1:], mode=self.lensCorrection,
+                                                 coefficients=self.lensCoefficients, centre=self.lensCentre, block=int(self.lensBlock),
+                                                 radius=int(self.lensRadius), threshold=float(self.lensThreshold),
+                                                 min_blocks=int(self.lensMinBlocks), min_shift=float(self.lensMinShift),
+                                                 interpolation=self.lensInterpolation)
+        rep = self.lensReport
+        if pair is None:
+            self.printAndWrite("  lens correction skipped: %s" % rep["reason"])
+            return
+        if self.lensCorrection == "estimate":
+            self.lensCoefficients = pair
+        for k, o in enumerate(offsets):
+            if list(originOffsetList[k + 1]) != o:
+                originOffsetList[k + 1] = o
+        self.printAndWrite("  lens correction: a1 %.6f, a2 %.6f, %.3f px at the corner, %s -> %.3f px spread over %d edges, %d offsets moved" %
+                           (pair[0], pair[1], rep["corner_px"], "%.3f" % rep["spread_before"] if "spread_before" in rep else "n/a",
+                            rep["spread_after"], rep["edges"], rep["moved"]))
 
     def _compensateExposure(self, handles, shapes, originOffsetList):
         """Method.exposureCompensation on the mosaic's resident tiles, in place (exposure.compensate, tests/exposure_ref.py): one gain per

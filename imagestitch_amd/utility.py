@@ -227,6 +227,26 @@ class Method():
     # is not an exposure ratio (a wrong offset, different content), and the tile is held at the bound
     exposureMaxGain = 2.0
 
+    # ---- radial lens correction between the shading correction and the exposure compensation (no reference counterpart; lens.py,
+    # tests/lens_ref.py): "estimate" measures the displacement of every lensBlock x lensBlock square of every overlap within
+    # +-lensRadius px of the registered offset, fits ONE radial model u(s) = s (1 + b1 rho^2) per dataset from how the displacement bows
+    # along the shared sides, resamples the resident tiles in place (lensInterpolation "cubic" or "bilinear") and measures the path
+    # offsets again; "given" skips the fit and takes lensCoefficients = (a1, a2) of s(u) = u (1 + a1 rho^2 + a2 rho^4), which an
+    # "estimate" run leaves behind for the next dataset of the session.  lensCentre: (cy, cx) in pixels, None for the tile's middle.
+    # Registration never sees corrected pixels.  lensThreshold = 0.5 is the verifier's threshold re-used: PROVISIONAL, nobody has tuned
+    # it for blocks (tools/bench_lens.py records the block-score distribution of the committed real strips).  lensMinBlocks and
+    # lensMinShift are design choices, not measurements: a fit from fewer measured blocks is not trusted, and a corner shift below a
+    # quarter pixel is left alone because resampling would only blur.
+    lensCorrection = "none"     # "none", "estimate" or "given"
+    lensCoefficients = None
+    lensCentre = None
+    lensBlock = 64              # 8..128 in multiples of 8
+    lensRadius = 8              # 1..16
+    lensThreshold = 0.5
+    lensMinBlocks = 32
+    lensMinShift = 0.25
+    lensInterpolation = "cubic"
+
     # ---- pyramidal output (no reference counterpart; tests/pyramid_ref.py): imageSetStitch* write every mosaic as ONE tiled pyramidal
     # TIFF (PyramidTiffBandWriter: level 0 in pyramidTile x pyramidTile tiles, then reduced-resolution pages, each half the size of the one
     # before) that slide and micrograph viewers open without reading all of it.  The levels are formed on the device from the band that

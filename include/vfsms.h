@@ -732,6 +732,34 @@ int vfsms_overlap_stats_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, 
  * vfsms_tile_wrap, a tile named twice in one call.  Waits for reserved / pending tiles.                                            */
 int vfsms_exposure_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, const uint16_t *gain_q12);
 
+/* ---- radial lens correction (Method.lensCorrection).  No reference counterpart: the specification is tests/lens_ref.py; the
+ * surfaces, the best candidates and the resampled bytes are integers and equal it exactly. ---------------------------------------- */
+/* The block displacement field of n pairs of resident tiles.  A job is a vfsms_ncc_job: tile B's pixel (r, c) meets tile A's pixel
+ * (r + dx, c + dy); both tiles of a job have ONE shape and channel count, gray or B G R (a colour sample is its luma
+ * (29 B + 150 G + 77 R + 128) >> 8), any row strides.  The overlap rectangle of B, shrunk by `radius` on all four sides, is cut into
+ * nby x nbx = ((r1 - r0) / block) x ((c1 - c0) / block) whole blocks from its top-left corner (none when one does not fit).  For
+ * every block and every candidate (i, j) in [-radius, radius]^2 the six sums over B's block and A's samples at (y + dx + i,
+ * x + dy + j), N = block^2, are scored as vfsms_verify_ncc scores them with min_pixels 0.  first = int64[n + 1]: first[k] the index of
+ * job k's first block (row-major by, bx), first[n] the total, computed by the caller and checked here.  best4 = int32[blocks][4] =
+ * {i, j, fixed-point score, block^2} under the tie order of vfsms_ncc_search_batch (a flat block: 0, 0, 0); surface (or NULL) =
+ * int32[blocks][2 radius + 1][2 radius + 1].  block: 8..128 in multiples of 8; radius: 1..16.  One launch for all jobs, a workgroup per
+ * block.  Waits for reserved / pending tiles like every batch call; the tiles are only read.
+ * VFSMS_ERR_BAD_ARG, nothing written: an unknown handle, two shapes or channel counts in a job, a channel count other than 1 or 3, a
+ * `first` that does not match the lattice.                                                                                          */
+int vfsms_block_ncc_batch(vfsms_ctx *ctx, const vfsms_ncc_job *jobs, int n, int block, int radius, const int64_t *first, int32_t *best4,
+                          int32_t *surface);
+/* n (1..4096) resident tiles of any shapes resampled in place under the radial map of tests/lens_ref.py: output pixel (y, x) takes the
+ * source position s = c + (p - c) (1 + a1 rho + a2 rho^2), rho = |p - c|^2 / D^2, D the half-diagonal, in integers: a1_q30, a2_q30 in
+ * Q30 (|a| <= 2^28), the centre c = (cy2 / 2, cx2 / 2) in half pixels -- a coordinate below 0 stands for every tile's own middle
+ * (h - 1, w - 1) -- positions in 1/256 px, a replicated border, channels independently.  interp 0: bilinear; 1: Catmull-Rom over 4 x 4
+ * taps with exact integer weights.  a1 = a2 = 0 changes no byte.  Every tile is read from a copy in the context's scratch.
+ * Refused like vfsms_shading_apply, nothing written: a tile from vfsms_tile_wrap, a tile named twice, a coefficient beyond 2^28, a
+ * side beyond 16384, a centre outside the middle half of an axis of any tile (2 |cy2 - (h - 1)| > h - 1), another interp.          */
+int vfsms_lens_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, int32_t a1_q30, int32_t a2_q30, int32_t cy2, int32_t cx2, int interp);
+/* the same map for a host image of h x w x ch bytes (ch 1..4, rows src_stride bytes apart) -> dst, dense; like vfsms_enhance_u8      */
+int vfsms_lens_remap_u8(vfsms_ctx *ctx, const uint8_t *src, int h, int w, int ch, int src_stride, int32_t a1_q30, int32_t a2_q30,
+                        int32_t cy2, int32_t cx2, int interp, uint8_t *dst);
+
 #ifdef __cplusplus
 }
 #endif
