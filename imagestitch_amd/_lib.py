@@ -1394,6 +1394,16 @@ class Engine:
                                                     _ptr(out), C.c_size_t(out.size), C.byref(n))
         return self._capacity_or(rc), n.value
 
+    def _encode_bands(self, who, rows, band_rows, call, regrow=lambda *more: None):
+        """The band loop of the four encode routes: generator of (row0, nrows, bytes-view, ...) with call(row0, nrows, out) -> (return code,
+        bytes needed, ...), the route's *_rows method.  Band k goes into slot k % BAND_RING of the encode ring; one that does not fit comes
+        again in the ring regrown to its answer, behind regrow(the answers beyond the bytes)"""
+        for k, r0, n in self._bands(rows, band_rows):
+            slot = k % self.BAND_RING
+            ans = self._fitted(who, "band", lambda out: call(r0, n, out), self._encode_ring()[slot],
+                               lambda need, *more: (regrow(*more), self._encode_ring(need)[slot])[1])
+            yield (r0, n, ans[0][:ans[1]]) + ans[2:]
+
     def canvas_encode_jpeg_bands(self, handle, rows, cols, ch, quality, restart_mcus, band_rows):
         """Generator of (row0, nrows, bytes-view) over the whole mosaic: every band of `band_rows` rows as the entropy-coded bytes of a
         baseline JPEG (vfsms_canvas_encode_jpeg_rows), encoded on the device -- behind jpeg_header(...) and in front of FF D9 they are the
@@ -1403,25 +1413,26 @@ class Engine:
         rows, cols, ch, band_rows = int(rows), int(cols), int(ch), int(band_rows)
         if band_rows <= 0:
             raise ValueError("canvas_encode_jpeg_bands: band_rows must be positive")
-        for k, r0, n in self._bands(rows, band_rows):
-            slot = k % self.BAND_RING
-            out, need = self._fitted("canvas_encode_jpeg_bands", "band", lambda out: self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, out),
-                                     self._encode_ring()[slot], lambda need: self._encode_ring(need)[slot])
-            yield r0, n, out[:need]
+        yield from self._encode_bands("canvas_encode_jpeg_bands", rows, band_rows, lambda r0, n, out: self.canvas_encode_jpeg_rows(handle, r0, n, quality, restart_mcus, out))
+
+    def _encode_tiles_device(self, who, entry, img, tile, bgr, first_guess, *coder_args):
+        """the image-order tile operators: entry(ctx, image, bgr, tile, *coder_args, out, ...) -> (payload u8, offsets uint64 [n_tiles + 1]);
+        the payload's first buffer is 64 KiB or the image's bytes over `first_guess`, whichever is more"""
+        img, h, w, ch = self._u8_image(img, who)
+        T = max(int(tile), 1)
+        offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
+        n = C.c_size_t()
+        call = lambda out: (self._capacity_or(entry(
+            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile), *(int(a) for a in coder_args),
+            _ptr(out), out.size, C.byref(n), _ptr(offsets), offsets.size)), n.value)
+        out, size = self._fitted(who, "tiles", call, np.empty(max(1 << 16, h * w * ch // first_guess), np.uint8), lambda need: np.empty(need, np.uint8))
+        return out[:size], offsets
 
     def jpeg_encode_tiles_device(self, img, tile, bgr=True, quality=95, restart_mcus=0):
         """vfsms_jpeg_encode_tiles_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload u8,
         offsets uint64 [n_tiles + 1]): the abbreviated JPEG streams of the image's tile x tile tiles, row-major and back to back -- level 0 of
         tests/tiff_jpeg_ref.py's file_tiles.  Tile t is payload[offsets[t]:offsets[t + 1]]."""
-        img, h, w, ch = self._u8_image(img, "jpeg_encode_tiles_device")
-        T = max(int(tile), 1)
-        offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
-        n = C.c_size_t()
-        call = lambda out: (self._capacity_or(self.lib.vfsms_jpeg_encode_tiles_device(
-            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile), int(quality), int(restart_mcus),
-            _ptr(out), out.size, C.byref(n), _ptr(offsets), offsets.size)), n.value)
-        out, size = self._fitted("jpeg_encode_tiles_device", "tiles", call, np.empty(max(1 << 16, h * w * ch // 4), np.uint8), lambda need: np.empty(need, np.uint8))
-        return out[:size], offsets
+        return self._encode_tiles_device("jpeg_encode_tiles_device", self.lib.vfsms_jpeg_encode_tiles_device, img, tile, bgr, 4, quality, restart_mcus)
 
     @staticmethod
     def pyramid_tiles_index(rows, cols, levels, tile, row0, nrows):
@@ -1456,31 +1467,27 @@ class Engine:
         rows, cols, ch, levels, tile, band_rows = int(rows), int(cols), int(ch), int(levels), int(tile), int(band_rows)
         if tile <= 0 or band_rows <= 0 or band_rows % tile or band_rows % (1 << levels):
             raise ValueError("canvas_encode_pyramid_tiles: band_rows = %d is not a positive multiple of the tile = %d and of 2^levels = %d" % (band_rows, tile, 1 << levels))
-        for k, r0, n in self._bands(rows, band_rows):
-            slot = k % self.BAND_RING
-            index = [np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)]
+        yield from self._pyramid_tile_bands("canvas_encode_pyramid_tiles", self.canvas_encode_pyramid_tiles_rows, handle, rows, cols, levels, tile, band_rows,
+                                            quality, restart_mcus)
 
-            def grown(need, ni):
-                index[0] = np.empty((ni, 4), np.int64)
-                return self._encode_ring(need)[slot]
-            out, need, ni = self._fitted("canvas_encode_pyramid_tiles", "band",
-                                         lambda out: self.canvas_encode_pyramid_tiles_rows(handle, r0, n, levels, tile, quality, restart_mcus, out, index[0]),
-                                         self._encode_ring()[slot], grown)
-            yield r0, n, out[:need], index[0][:ni]
+    def _pyramid_tile_bands(self, who, rows_method, handle, rows, cols, levels, tile, band_rows, *coder_args):
+        """the bands of a tile route over rows_method(handle, row0, nrows, levels, tile, *coder_args, out, index), one of the two *_rows
+        methods.  Every band gets an index array of its own, sized by pyramid_tiles_index, or at the library's count should the band not fit"""
+        index = [None]
+
+        def call(r0, n, out):
+            if index[0] is None:
+                index[0] = np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)
+            return rows_method(handle, r0, n, levels, tile, *coder_args, out, index[0])
+        for r0, n, view, ni in self._encode_bands(who, rows, band_rows, call, lambda ni: index.__setitem__(0, np.empty((ni, 4), np.int64))):
+            yield r0, n, view, index[0][:ni]
+            index[0] = None
 
     def deflate_encode_tiles_device(self, img, tile, bgr=True):
         """vfsms_deflate_encode_tiles_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload
         u8, offsets uint64 [n_tiles + 1]): the zlib streams (TIFF predictor 2, colour stored R G B, zero padding) of the image's tile x tile
         tiles, row-major and back to back -- tests/deflate_ref.py's tile_streams.  Tile t is payload[offsets[t]:offsets[t + 1]]."""
-        img, h, w, ch = self._u8_image(img, "deflate_encode_tiles_device")
-        T = max(int(tile), 1)
-        offsets = np.zeros(-(-h // T) * -(-w // T) + 1, np.uint64)
-        n = C.c_size_t()
-        call = lambda out: (self._capacity_or(self.lib.vfsms_deflate_encode_tiles_device(
-            self.ctx, img.ctypes.data_as(C.c_void_p), h, w, ch, img.strides[0], int(bool(bgr)), int(tile),
-            _ptr(out), out.size, C.byref(n), _ptr(offsets), offsets.size)), n.value)
-        out, size = self._fitted("deflate_encode_tiles_device", "tiles", call, np.empty(max(1 << 16, h * w * ch), np.uint8), lambda need: np.empty(need, np.uint8))
-        return out[:size], offsets
+        return self._encode_tiles_device("deflate_encode_tiles_device", self.lib.vfsms_deflate_encode_tiles_device, img, tile, bgr, 1)
 
     def canvas_encode_pyramid_tiles_deflate_rows(self, handle, row0, nrows, levels, tile, out, index):
         """one vfsms_canvas_encode_pyramid_tiles_deflate call into the u8 vector `out` and the int64 (n, 4) array `index` -> (return code, bytes
@@ -1498,17 +1505,7 @@ class Engine:
         rows, cols, ch, levels, tile, band_rows = int(rows), int(cols), int(ch), int(levels), int(tile), int(band_rows)
         if tile <= 0 or band_rows <= 0 or band_rows % tile or band_rows % (1 << levels):
             raise ValueError("canvas_encode_pyramid_tiles_deflate: band_rows = %d is not a positive multiple of the tile = %d and of 2^levels = %d" % (band_rows, tile, 1 << levels))
-        for k, r0, n in self._bands(rows, band_rows):
-            slot = k % self.BAND_RING
-            index = [np.empty((len(self.pyramid_tiles_index(rows, cols, levels, tile, r0, n)), 4), np.int64)]
-
-            def grown(need, ni):
-                index[0] = np.empty((ni, 4), np.int64)
-                return self._encode_ring(need)[slot]
-            out, need, ni = self._fitted("canvas_encode_pyramid_tiles_deflate", "band",
-                                         lambda out: self.canvas_encode_pyramid_tiles_deflate_rows(handle, r0, n, levels, tile, out, index[0]),
-                                         self._encode_ring()[slot], grown)
-            yield r0, n, out[:need], index[0][:ni]
+        yield from self._pyramid_tile_bands("canvas_encode_pyramid_tiles_deflate", self.canvas_encode_pyramid_tiles_deflate_rows, handle, rows, cols, levels, tile, band_rows)
 
     def png_encode_device(self, img, segment_rows=16, bgr=True):
         """vfsms_png_encode_device, the bare operator: u8 (h, w) or (h, w, 3) rows (B G R when `bgr`; rows may be strided) -> (payload u8, the
@@ -1538,11 +1535,7 @@ class Engine:
         rows, cols, ch, segment_rows, band_rows = int(rows), int(cols), int(ch), int(segment_rows), int(band_rows)
         if segment_rows <= 0 or band_rows <= 0 or band_rows % segment_rows:
             raise ValueError("canvas_encode_png_bands: band_rows = %d is not a positive multiple of segment_rows = %d" % (band_rows, segment_rows))
-        for k, r0, n in self._bands(rows, band_rows):
-            slot = k % self.BAND_RING
-            out, need, adler = self._fitted("canvas_encode_png_bands", "band", lambda out: self.canvas_encode_png_rows(handle, r0, n, segment_rows, out),
-                                            self._encode_ring()[slot], lambda need, adler: self._encode_ring(need)[slot])
-            yield r0, n, out[:need], adler
+        yield from self._encode_bands("canvas_encode_png_bands", rows, band_rows, lambda r0, n, out: self.canvas_encode_png_rows(handle, r0, n, segment_rows, out))
 
 
 _default_engine = None

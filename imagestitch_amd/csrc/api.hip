@@ -230,8 +230,6 @@ extern "C" int vfsms_ctx_create(int device, vfsms_ctx **out)
     return VFSMS_OK;
 }
 
-int phase_destroy_plans(vfsms_ctx *ctx);
-
 // the pools whose entries stayed raw pointers (they move between a record and a pool, and carry events): each is freed here and nowhere else
 // (the staging pools of the ingest: stage_pools_free, ingest_fill.h)
 static void tile_pools_free(vfsms_ctx *ctx)
@@ -477,10 +475,7 @@ extern "C" int vfsms_tile_fill(vfsms_ctx *ctx, int64_t handle, const uint8_t *im
 // and / or the reserved 3-channel tile `color` (B G R, cv2.imdecode(..., IMREAD_COLOR) of Stitcher.py:382-403); either handle may be 0.
 // The source rows go to a device staging buffer on the copy stream, the split / colour conversion runs there too, and the call returns when
 // both tiles are complete.  Any thread.  src == NULL gives both tiles up.
-int ingest_source_pixel_bytes(int format);
-int launch_ingest_split(hipStream_t stream, const uint8_t *src, uint8_t *gray, uint8_t *bgr, long long n, int format);
 #define VFSMS_SRC_YCC420_RAW 100      // internal: the raw planes of a 4:2:0 JPEG on the iMCU grid (jpeg_decode_raw420_host) -> k_ingest_420
-int launch_ingest_420(hipStream_t stream, const uint8_t *src, int pw, int ph, int h, int w, uint8_t *gray, uint8_t *bgr);
 // `host` (h * w pixels of `format`, densely packed) -> a device staging buffer -> the split kernel -> both tiles
 static void fill_pair_upload(TileFill &f, const uint8_t *host, int format)
 {
@@ -509,8 +504,6 @@ extern "C" int vfsms_tile_fill_pair(vfsms_ctx *ctx, int64_t gray, int64_t color,
 // otherwise, colour conversion on the device).  Any thread; blocks until the tiles are complete.  When the decode cannot be done here
 // (VFSMS_ERR_UNSUPPORTED: no libjpeg.so.8 on the host, not a 1- / 3-component JPEG; VFSMS_ERR_BAD_ARG: a damaged file, or a file whose size
 // is not the tiles') BOTH TILES STAY RESERVED: the caller decodes some other way and fills them, or gives them up.
-int jpeg_decode_host(const unsigned char *jpeg, size_t nbytes, int want_planes, unsigned char *out, size_t cap, int *h_out, int *w_out, int *comp_out);
-int jpeg_decode_raw420_host(const unsigned char *jpeg, size_t nbytes, unsigned char *out, size_t cap, int *h_out, int *w_out);
 // what the three JPEG routes answer to a file of another size than the tiles' (CAPACITY: the decoder met it first); any other rc as it is
 static int jpeg_size_check(const TileFill &f, int rc, int jh, int jw)
 {
@@ -1937,7 +1930,6 @@ extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0,
 // per 16 tiles instead of two per tile.
 static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n, const vfsms_surf_params *params,
                                     int enhance_mode, double clip_limit, int tile_grid, int64_t *feats, int *counts);
-extern "C" int vfsms_features_free(vfsms_ctx *ctx, int64_t feat);
 extern "C" int vfsms_features_surf_batch(vfsms_ctx *ctx, const int64_t *tiles, int n, const vfsms_surf_params *params,
                                          int enhance_mode, double clip_limit, int tile_grid, int64_t *feats, int *counts)
 {
@@ -2503,8 +2495,9 @@ extern "C" int vfsms_canvas_encode_jpeg_rows(vfsms_ctx *ctx, int64_t canvas, int
     return canvas_flag_verdict(flag);
 }
 
-// the caller's h x w x ch image (rows `stride` bytes apart), densely packed in the context's encoder scratch: enqueued; *pitch = a row's bytes
-static int jpeg_stage_image(vfsms_ctx *ctx, const char *who, const uint8_t *img, int h, int w, int ch, int stride, size_t *pitch)
+// the caller's h x w x ch image (rows `stride` bytes apart), densely packed in the context's staging buffer (ctx->jpeg_scratch.img, whichever
+// coder reads it): enqueued; *pitch = a row's bytes
+static int stage_host_image(vfsms_ctx *ctx, const char *who, const uint8_t *img, int h, int w, int ch, int stride, size_t *pitch)
 {
     if ((long long)stride < (long long)w * ch) { vfsms_set_error("%s: stride %d is less than a row's %lld bytes", who, stride, (long long)w * ch); return VFSMS_ERR_BAD_ARG; }
     *pitch = (size_t)w * ch;
@@ -2525,13 +2518,50 @@ extern "C" int vfsms_jpeg_encode_device(vfsms_ctx *ctx, const uint8_t *img, int 
     TRY(jpeg_check_geometry(who, h, w, ch, quality, restart_mcus, &interval));
     JpegScratch *s = &ctx->jpeg_scratch;
     size_t pitch = 0, hn = 0, bn = 0;
-    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
+    TRY(stage_host_image(ctx, who, img, h, w, ch, stride, &pitch));
     TRY(vfsms_jpeg_header(h, w, ch, quality, restart_mcus, out, out ? cap : 0, &hn) == VFSMS_ERR_BAD_ARG ? VFSMS_ERR_BAD_ARG : VFSMS_OK);
     const bool room = out && cap > hn + 2;
     const int rc = jpeg_encode_band_device(ctx, s, s->img.as<uint8_t>(), h, w, ch, pitch, bgr != 0, 0, h, quality, interval, room ? out + hn : nullptr, room ? cap - hn - 2 : 0, &bn);
     *nbytes = hn + bn + 2;
     if (rc != VFSMS_OK) return rc;
     out[hn + bn] = 0xFF; out[hn + bn + 1] = 0xD9;
+    return VFSMS_OK;
+}
+
+// ---- the two tile coders of pyramidal TIFF: the Coder of canvas_tile_band (canvas_band.h) and of the image-order operator below, over one
+// scratch; limit: what one call takes of an image
+struct JpegTileCoder {
+    static constexpr int codec = VFSMS_PYR_CODEC_JPEG;
+    vfsms_ctx *ctx; JpegScratch *s; int ch, bgr, tile, quality, restart_mcus, interval; JpegTilesRun run;
+    int limit(const char *who, int h, long long tr, long long) const { if (tr * (tile / 8) > 65535) { vfsms_set_error("%s: %d rows are more tile rows than one call takes", who, h); return VFSMS_ERR_BAD_ARG; } return VFSMS_OK; }
+    int count(const JpegTileJob *jobs, int n_jobs, const int *d_flag, int *flag) { return jpeg_tiles_count_device(ctx, s, jobs, n_jobs, ch, bgr, tile, quality, restart_mcus, interval, d_flag, flag, &run); }
+    int write(uint8_t *out) { return jpeg_tiles_write_device(ctx, s, &run, out); }
+};
+struct DeflateTileCoder {
+    static constexpr int codec = VFSMS_PYR_CODEC_DEFLATE;
+    vfsms_ctx *ctx; DeflateScratch *s; int ch, bgr, tile; DeflateTilesRun run;
+    int limit(const char *who, int, long long, long long n_tiles) const { if (n_tiles > 0x7fffffff) { vfsms_set_error("%s: %lld tiles are more than one call takes", who, n_tiles); return VFSMS_ERR_BAD_ARG; } return VFSMS_OK; }
+    int count(const JpegTileJob *jobs, int n_jobs, const int *d_flag, int *flag) { return deflate_tiles_count_device(ctx, s, jobs, n_jobs, ch, bgr, tile, d_flag, flag, &run); }
+    int write(uint8_t *out) { return deflate_tiles_write_device(ctx, s, &run, out); }
+};
+// the image-order operator behind vfsms_jpeg_encode_tiles_device and vfsms_deflate_encode_tiles_device, which have checked their pointers and
+// the coder's geometry: the image staged, one job, count, capacity (nothing is written then), write, the offsets
+template <class Coder>
+static int encode_tiles_image(vfsms_ctx *ctx, const char *who, Coder &coder, const uint8_t *img, int h, int w, int stride,
+                              uint8_t *out, size_t cap, size_t *nbytes, uint64_t *offsets, int offsets_cap)
+{
+    const long long tr = (h + coder.tile - 1) / coder.tile, n_tiles = tr * ((w + coder.tile - 1) / coder.tile);
+    TRY(coder.limit(who, h, tr, n_tiles));
+    if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
+    size_t pitch = 0;
+    TRY(stage_host_image(ctx, who, img, h, w, coder.ch, stride, &pitch));
+    const JpegTileJob job = {ctx->jpeg_scratch.img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
+    TRY(coder.count(&job, 1, nullptr, nullptr));
+    const unsigned long long total = coder.run.tile_offs[(size_t)n_tiles];
+    *nbytes = (size_t)total;
+    if (!out || cap < total) { vfsms_set_error("%s: the tiles take %llu bytes, the buffer holds %zu", who, total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
+    TRY(coder.write(out));
+    for (long long t = 0; t <= n_tiles; t++) offsets[t] = coder.run.tile_offs[(size_t)t];
     return VFSMS_OK;
 }
 
@@ -2547,21 +2577,8 @@ extern "C" int vfsms_jpeg_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *img
     if (!img || !nbytes || !offsets || h < 1 || w < 1) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     int interval = 0;
     TRY(jpeg_check_tile_geometry(who, tile, ch, quality, restart_mcus, &interval));
-    const long long tr = (h + tile - 1) / tile, n_tiles = tr * ((w + tile - 1) / tile);
-    if (tr * (tile / 8) > 65535) { vfsms_set_error("%s: %d rows are more tile rows than one call takes", who, h); return VFSMS_ERR_BAD_ARG; }
-    if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
-    JpegScratch *s = &ctx->jpeg_scratch;
-    size_t pitch = 0;
-    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
-    const JpegTileJob job = {s->img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
-    JpegTilesRun run;
-    TRY(jpeg_tiles_count_device(ctx, s, &job, 1, ch, bgr != 0, tile, quality, restart_mcus, interval, nullptr, nullptr, &run));
-    const unsigned long long total = run.tile_offs[(size_t)run.n_tiles];
-    *nbytes = (size_t)total;
-    if (!out || cap < total) { vfsms_set_error("%s: the tiles take %llu bytes, the buffer holds %zu", who, total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
-    TRY(jpeg_tiles_write_device(ctx, s, &run, out));
-    for (int t = 0; t <= run.n_tiles; t++) offsets[t] = run.tile_offs[(size_t)t];
-    return VFSMS_OK;
+    JpegTileCoder coder{ctx, &ctx->jpeg_scratch, ch, bgr != 0, tile, quality, restart_mcus, interval, {}};
+    return encode_tiles_image(ctx, who, coder, img, h, w, stride, out, cap, nbytes, offsets, offsets_cap);
 }
 
 // Every tile row of level 0 and of levels 1 .. levels that the band [row0, row0 + nrows) of the canvas COMPLETES, as finished tile streams
@@ -2584,26 +2601,9 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles(vfsms_ctx *ctx, int64_t canvas,
     int interval = 0;
     TRY(jpeg_check_tile_geometry(who, tile, cv->ch, quality, restart_mcus, &interval));
     TRY(canvas_band_check(who, nbytes && n_index, cv->rows, row0, nrows, {{1 << levels, "2^levels"}, {tile, "the tile"}}));
-    PyrPending &P = cv->pend;
-    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream, VFSMS_PYR_CODEC_JPEG));
-    PyrPlan plan;
-    TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
-    *n_index = (int)plan.n_tiles;
-    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, plan.lvl, "pyramid_jpeg.levels"));
-    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
-    JpegTilesRun run;
-    TRY(jpeg_tiles_count_device(ctx, &cv->jpeg, plan.jobs, plan.n_jobs, cv->ch, 1, tile, quality, restart_mcus, interval, cv->d_err.as<int>(), &flag, &run));
-    TRY(canvas_flag_verdict(flag));
-    const unsigned long long bytes = run.tile_offs[(size_t)run.n_tiles];
-    *nbytes = (size_t)bytes;
-    if (!out || cap < bytes || !index || index_cap < plan.n_tiles) {              // nothing is consumed: the same band may come again
-        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, plan.n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
-        return VFSMS_ERR_CAPACITY;
-    }
-    TRY(P.commit(plan, ctx->stream));
-    TRY(jpeg_tiles_write_device(ctx, &cv->jpeg, &run, out));
-    plan.index(run.tile_offs.data(), index);
-    return VFSMS_OK;
+    JpegTileCoder coder{ctx, &cv->jpeg, cv->ch, 1, tile, quality, restart_mcus, interval, {}};
+    const auto reduce = [&](uint8_t *const *lvl) { return pyramid_band_device_at(ctx, cv, row0, nrows, levels, lvl, "pyramid_jpeg.levels"); };
+    return canvas_tile_band(ctx, cv, who, row0, nrows, levels, tile, coder, reduce, out, cap, nbytes, index, index_cap, n_index);
 }
 
 // ---- lossless tiles for pyramidal TIFF (Method.pyramidCompression = "deflate-device"; deflate_kernels.hip, specified by tests/deflate_ref.py) ------
@@ -2618,21 +2618,8 @@ extern "C" int vfsms_deflate_encode_tiles_device(vfsms_ctx *ctx, const uint8_t *
     const char *who = "deflate_encode_tiles_device";
     if (!img || !nbytes || !offsets || h < 1 || w < 1) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     TRY(deflate_check_tile_geometry(who, tile, ch));
-    const long long tr = (h + tile - 1) / tile, n_tiles = tr * ((w + tile - 1) / tile);
-    if (n_tiles > 0x7fffffff) { vfsms_set_error("%s: %lld tiles are more than one call takes", who, n_tiles); return VFSMS_ERR_BAD_ARG; }
-    if (offsets_cap < n_tiles + 1) { vfsms_set_error("%s: %lld tiles need %lld offsets, `offsets` holds %d", who, n_tiles, n_tiles + 1, offsets_cap); return VFSMS_ERR_BAD_ARG; }
-    size_t pitch = 0;
-    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
-    const JpegTileJob job = {ctx->jpeg_scratch.img.as<uint8_t>(), pitch * h, pitch, 0, h, w, 0, (int)tr};
-    DeflateScratch *s = &ctx->deflate_scratch;
-    DeflateTilesRun run;
-    TRY(deflate_tiles_count_device(ctx, s, &job, 1, ch, bgr != 0, tile, nullptr, nullptr, &run));
-    const unsigned long long total = run.tile_offs[(size_t)run.a.n_tiles];
-    *nbytes = (size_t)total;
-    if (!out || cap < total) { vfsms_set_error("%s: the tiles take %llu bytes, the buffer holds %zu", who, total, out ? cap : (size_t)0); return VFSMS_ERR_CAPACITY; }
-    TRY(deflate_tiles_write_device(ctx, s, &run, out));
-    for (int t = 0; t <= run.a.n_tiles; t++) offsets[t] = run.tile_offs[(size_t)t];
-    return VFSMS_OK;
+    DeflateTileCoder coder{ctx, &ctx->deflate_scratch, ch, bgr != 0, tile, {}};
+    return encode_tiles_image(ctx, who, coder, img, h, w, stride, out, cap, nbytes, offsets, offsets_cap);
 }
 
 // vfsms_canvas_encode_pyramid_tiles with the lossless coder: the same band contract, index records and capacity behaviour (on
@@ -2649,26 +2636,9 @@ extern "C" int vfsms_canvas_encode_pyramid_tiles_deflate(vfsms_ctx *ctx, int64_t
     if (levels < 0 || levels > VFSMS_PYRAMID_MAX_LEVELS) { vfsms_set_error("%s: levels must be 0..%d", who, VFSMS_PYRAMID_MAX_LEVELS); return VFSMS_ERR_BAD_ARG; }
     TRY(deflate_check_tile_geometry(who, tile, cv->ch));
     TRY(canvas_band_check(who, nbytes && n_index, cv->rows, row0, nrows, {{1 << levels, "2^levels"}, {tile, "the tile"}}));
-    PyrPending &P = cv->pend;
-    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream, VFSMS_PYR_CODEC_DEFLATE));
-    PyrPlan plan;
-    TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
-    *n_index = (int)plan.n_tiles;
-    if (levels > 0) TRY(pyramid_band_device_at(ctx, cv, row0, nrows, levels, plan.lvl, "pyramid_deflate.levels"));
-    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
-    DeflateTilesRun run;
-    TRY(deflate_tiles_count_device(ctx, &cv->deflate, plan.jobs, plan.n_jobs, cv->ch, 1, tile, cv->d_err.as<int>(), &flag, &run));
-    TRY(canvas_flag_verdict(flag));
-    const unsigned long long bytes = run.tile_offs[(size_t)run.a.n_tiles];
-    *nbytes = (size_t)bytes;
-    if (!out || cap < bytes || !index || index_cap < plan.n_tiles) {              // nothing is consumed: the same band may come again
-        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, plan.n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
-        return VFSMS_ERR_CAPACITY;
-    }
-    TRY(P.commit(plan, ctx->stream));                              // (the predicted bytes in scratch hold everything the streams need)
-    TRY(deflate_tiles_write_device(ctx, &cv->deflate, &run, out));
-    plan.index(run.tile_offs.data(), index);
-    return VFSMS_OK;
+    DeflateTileCoder coder{ctx, &cv->deflate, cv->ch, 1, tile, {}};
+    const auto reduce = [&](uint8_t *const *lvl) { return pyramid_band_device_at(ctx, cv, row0, nrows, levels, lvl, "pyramid_deflate.levels"); };
+    return canvas_tile_band(ctx, cv, who, row0, nrows, levels, tile, coder, reduce, out, cap, nbytes, index, index_cap, n_index);
 }
 
 // ---- PNG coded on the device (Method.pngEncoder = "device"; deflate_kernels.hip over deflate_kernels.hip's passes, specified by tests/png_ref.py) ------
@@ -2683,7 +2653,7 @@ extern "C" int vfsms_png_encode_device(vfsms_ctx *ctx, const uint8_t *img, int h
     if (!img || !nbytes || !adler) { vfsms_set_error("%s: bad arguments", who); return VFSMS_ERR_BAD_ARG; }
     TRY(png_check_geometry(who, segment_rows, h, w, ch));
     size_t pitch = 0;
-    TRY(jpeg_stage_image(ctx, who, img, h, w, ch, stride, &pitch));
+    TRY(stage_host_image(ctx, who, img, h, w, ch, stride, &pitch));
     return png_encode_band_device(ctx, &ctx->deflate_scratch, ctx->jpeg_scratch.img.as<uint8_t>(), h, w, ch, pitch, bgr != 0, 0, h, segment_rows, out, cap, nbytes, adler, nullptr, nullptr);
 }
 

@@ -1,9 +1,10 @@
 // canvas_band.h -- the band walk behind the four write-out routes of a canvas (vfsms_canvas_download_rows, .._download_rows_pyramid,
-// .._encode_jpeg_rows, .._encode_pyramid_tiles and its lossless twin .._encode_pyramid_tiles_deflate of api.hip; .._encode_png_rows uses the
-// check and the flag alone: it keeps no state between bands): the one band check, the one reader of the sticky geometry flag, and the
-// operations of PyrPending, the rows of the reduced levels that wait between the bands of the tile route.  Host C++ over common.h and the
-// runtime API, no kernels, no launchers: libvfsms and tools/canvas_band_host_check.cpp (host sanitizers, failures injected) compile the
-// same lines.
+// .._encode_jpeg_rows, and the tile route .._encode_pyramid_tiles / .._encode_pyramid_tiles_deflate of api.hip; .._encode_png_rows uses the
+// check and the flag alone: it keeps no state between bands): the one band check, the one reader of the sticky geometry flag, the
+// operations of PyrPending, the rows of the reduced levels that wait between the bands of the tile route, and canvas_tile_band, the one
+// driver of a band of that route -- begin to index, the capacity protocol included -- over a coder that api.hip supplies (JPEG, deflate).
+// Host C++ over common.h and the runtime API, no kernels, no launchers: libvfsms and tools/canvas_band_host_check.cpp (host sanitizers,
+// failures injected, a stub coder) compile the same lines.
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -145,5 +146,38 @@ inline int PyrPending::commit(const PyrPlan &p, hipStream_t stream)
         base[k] += p.full[k]; have[k] = rem;
     }
     next = p.row_end;
+    return VFSMS_OK;
+}
+
+// ---- the tile route's band: one driver, whichever coder ------------------------------------------------------------------------------------------
+// A Coder is a small struct: `codec`, its VFSMS_PYR_CODEC_* tag; count(jobs, n_jobs, d_flag, &flag), the counting half, which leaves
+// run.tile_offs[0 .. n_tiles] on the host and the int at d_flag in flag behind one synchronisation; write(out), the writing half.  reduce(lvl)
+// forms the band's share of levels 1 .. levels where the plan says (the caller's launcher: none lives here).  The order of the steps is the
+// contract: 1 begin (the band continues the walk or is refused with the walk as it was), 2 plan (arithmetic only), 3 *n_index, 4 reduce,
+// 5 count, with the sticky geometry flag, 6 the flag's verdict, 7 *nbytes, 8 the capacity refusal -- both sizes reported, nothing written and
+// NOTHING CONSUMED: the same band may come again and plans the same --, 9 commit, the only step that consumes rows, behind every refusal and
+// in front of the write (the coder's scratch holds everything the streams need), 10 write, 11 index
+template <class Coder, class Reduce>
+static int canvas_tile_band(vfsms_ctx *ctx, CanvasRec *cv, const char *who, int row0, int nrows, int levels, int tile, Coder &coder, Reduce &&reduce,
+                            uint8_t *out, size_t cap, size_t *nbytes, int64_t *index, int index_cap, int *n_index)
+{
+    PyrPending &P = cv->pend;
+    PyrPlan plan;
+    TRY(P.begin(who, cv->rows, cv->cols, cv->ch, row0, nrows, tile, levels, ctx->stream, coder.codec));
+    TRY(P.plan(who, cv->pix.as<uint8_t>(), row0, nrows, &plan));
+    *n_index = (int)plan.n_tiles;
+    if (levels > 0) TRY(reduce(plan.lvl));
+    int flag = 0;                                                  // the sticky geometry flag comes back with the sizes
+    TRY(coder.count(plan.jobs, plan.n_jobs, cv->d_err.as<int>(), &flag));
+    TRY(canvas_flag_verdict(flag));
+    const unsigned long long bytes = coder.run.tile_offs[(size_t)plan.n_tiles];
+    *nbytes = (size_t)bytes;
+    if (!out || cap < bytes || !index || index_cap < plan.n_tiles) {
+        vfsms_set_error("%s: the band takes %llu bytes in %lld tiles, the buffers hold %zu bytes and %d records", who, bytes, plan.n_tiles, out ? cap : (size_t)0, index ? index_cap : 0);
+        return VFSMS_ERR_CAPACITY;
+    }
+    TRY(P.commit(plan, ctx->stream));
+    TRY(coder.write(out));
+    plan.index(coder.run.tile_offs.data(), index);
     return VFSMS_OK;
 }

@@ -376,6 +376,7 @@ int phase_layout(vfsms_ctx *ctx, ArenaWalk &a, PhaseScratch *s, int h, int w, in
 void phase_peaks_layout(ArenaWalk &a, PhaseScratch *s, int h, int w, int nb, int K);
 int phase_bytes(vfsms_ctx *ctx, int h, int w, int nb, size_t *bytes);
 size_t phase_peaks_bytes(int h, int w, int nb, int K);            // what a batch with a sink takes from the arena beyond phase_bytes
+int phase_destroy_plans(vfsms_ctx *ctx);                          // the rocFFT plans of the context, before its streams go
 void phase_surface_size(int h, int w, int *M, int *N);            // the padded size of the surface of an h x w strip, in the strip's own orientation
 // phase_resolve_kernels.hip: RE holds njobs stored planes of SM x SN (tr: each the transpose of its surface); partial: njobs * phase_peaks_blocks(SM) * K records
 int phase_peaks_blocks(int SM);
@@ -385,6 +386,11 @@ int launch_phase_resolve(vfsms_ctx *ctx, const PhaseJobHost *d_jobs, const Phase
                          double threshold, int min_pixels, unsigned long long *d_sums, int32_t *d_rows, int32_t *d_cands, int32_t *d_peaks_out);
 int ctx_upload_small(vfsms_ctx *ctx, const void *src, size_t bytes, void **d);   // launch records through the pinned staging buffer
 int ctx_copy_small(vfsms_ctx *ctx, const void *src, size_t bytes, void *d);      // the same into an array a layout walk took
+// ingest_kernels.hip: one decoded source image (format 0: 8-bit gray, 1: Y Cb Cr interleaved, 2: Y Cb Cr X; or the raw 4:2:0 planes of
+// jpeg_decode_raw420_host) -> the gray and / or the B G R tile
+int ingest_source_pixel_bytes(int format);
+int launch_ingest_split(hipStream_t stream, const uint8_t *src, uint8_t *gray, uint8_t *bgr, long long n, int format);
+int launch_ingest_420(hipStream_t stream, const uint8_t *src, int pw, int ph, int h, int w, uint8_t *gray, uint8_t *bgr);
 // enhance_kernels.hip
 int enhance_check_args(const char *who, int mode, int tiles);
 void enhance_layout(ArenaWalk &a, EnhJob *J, const uint8_t *src, int stride, int h, int w, int mode, int tiles);
@@ -488,6 +494,9 @@ int deflate_tiles_write_device(vfsms_ctx *ctx, DeflateScratch *s, const DeflateT
 int png_check_geometry(const char *who, int segment_rows, int rows, int cols, int ch);
 int png_encode_band_device(vfsms_ctx *ctx, DeflateScratch *s, const uint8_t *pix, int rows, int cols, int ch, size_t pitch, int bgr, int row0, int nrows,
                            int segment_rows, uint8_t *out, size_t cap, size_t *nbytes, uint32_t *adler, const int *d_flag, int *flag);
+// jpeg_host.cpp: the decode on the host (the system's libjpeg-turbo), into planes or into the raw 4:2:0 planes on the iMCU grid
+int jpeg_decode_host(const unsigned char *jpeg, size_t nbytes, int want_planes, unsigned char *out, size_t cap, int *h_out, int *w_out, int *comp_out);
+int jpeg_decode_raw420_host(const unsigned char *jpeg, size_t nbytes, unsigned char *out, size_t cap, int *h_out, int *w_out);
 // jpeg_host.cpp / jpeg_dec_kernels.hip: the device half of the JPEG decoder (tests/jpeg_dec_ref.py).  A component of one launch: its blocks
 // (64 int16 each, natural order, block-row-major on a grid `bcols` wide), its table (uint16[64], natural order), the plane it becomes (`rows`
 // x `cols` samples kept of the grid, `pitch` bytes apart) and the index of its first block among the launch's `total`

@@ -1266,13 +1266,11 @@ class Stitcher(Utility.Method):
         elif route == "device_png":                              # the sink appends the bands' IDAT chunks (the PNG coder of csrc/deflate_kernels.hip)
             for r0, nr, payload, adler in eng.canvas_encode_png_bands(canvas, rows, cols, ch, int(self.pngSegmentRows), self._pngBandRows()):
                 sink(r0, nr, payload, adler, full_shape)
-        elif route == "device_tiles":
-            # the finished tile streams of level 0 and of the reduced levels a band completes (a mosaic that fits one tile: zero reduced levels)
-            for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), int(self.jpegQuality),
-                                                                          int(self.jpegRestartMcus), self._bandRows()):
-                sink.tiles(r0, nr, payload, index, full_shape)
-        elif route == "device_tiles_deflate":                    # the same, from the lossless coder (csrc/deflate_kernels.hip)
-            for r0, nr, payload, index in eng.canvas_encode_pyramid_tiles_deflate(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), self._bandRows()):
+        elif route in ("device_tiles", "device_tiles_deflate"):
+            # the finished tile streams of level 0 and of the reduced levels a band completes (a mosaic that fits one tile: zero reduced levels),
+            # from the JPEG coder or the lossless one (csrc/deflate_kernels.hip)
+            coder_args = (int(self.jpegQuality), int(self.jpegRestartMcus)) if route == "device_tiles" else ()
+            for r0, nr, payload, index in getattr(eng, self._ROUTES[route])(canvas, rows, cols, ch, pyramid or 0, int(self.pyramidTile), *coder_args, self._bandRows()):
                 sink.tiles(r0, nr, payload, index, full_shape)
         elif sink is not None and hasattr(eng, self._ROUTES["plain"]):
             # pixel bands.  A sink that is done with a band two bands later (`transient_bands`: JpegBandWriter) gets views of the engine's pinned

@@ -1,7 +1,8 @@
 """The band walk behind the four write-out routes of a canvas (csrc/canvas_band.h): tools/canvas_band_host_check.cpp, built with the host
 sanitizers over malloc-backed runtime calls and run as a program of its own (no GPU, no HIP runtime, no libvfsms).  It drives the band
 check and PyrPending -- the only state of the library that survives between calls -- against a brute-force model over a sweep of canvases,
-with every refusal and with failures injected into the grow; a GPU test sees that state only through a whole walk."""
+with every refusal and with failures injected into the grow, and the driver of a band of the tile route (canvas_tile_band) over a stub coder:
+the capacity protocol, which consumes nothing when there is too little room; a GPU test sees that state only through a whole walk."""
 import os
 import re
 import subprocess
@@ -29,3 +30,9 @@ def test_band_check_and_pending_rows_against_the_model(tmp_path):
     assert walks >= canvases * 4 and bands >= sweep_bands and checks >= 12 * bands, p.stdout
     # the grow fails once at its allocation, at a copy and at its synchronisation, for levels 1..3 and both channel counts
     assert injected >= 3 * 3 * 2, p.stdout
+    # the driver of a band of the tile route over a stub coder: rows 1..80 x 2 channel counts x levels 0..3 at one width, in bands of 16 and of
+    # 48 rows; every band is refused twice for want of room (a byte, a record) before it goes through
+    m = re.search(r"injected failures, (\d+) driver bands \((\d+) capacity refusals\)", p.stdout)
+    assert m, p.stdout + p.stderr
+    driver_bands, refusals = (int(g) for g in m.groups())
+    assert driver_bands >= 2 * 4 * sum(-(-rows // n) for rows in range(1, 81) for n in (16, 48)) and refusals >= 2 * driver_bands, p.stdout

@@ -8,6 +8,9 @@
 // for each level the list of its rows, a tile row being due when all its rows exist or the canvas has ended.  The "reduction" of the check
 // writes a pattern that encodes level, row and byte where the plan says the band's share goes, so ASan judges every slot and the rows carried
 // over a commit or a grow are compared byte for byte.  Refused bands and failures injected into begin()'s grow must leave the state as it was.
+// canvas_tile_band, the driver of a band of the tile route, runs over a stub coder whose tile sizes and bytes are a fixed function of (level,
+// tile number): the capacity protocol -- too little room consumes and writes nothing, and the same band with room gives the model's records,
+// offsets and payload -- is held here, where the GPU tests see it only through whole walks.
 #include "hip_host_stubs.h"
 #include "canvas_band.h"
 #include <stdarg.h>
@@ -22,7 +25,7 @@ void vfsms_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-static long g_checks = 0, g_walks = 0, g_bands = 0, g_injections = 0;
+static long g_checks = 0, g_walks = 0, g_bands = 0, g_injections = 0, g_driver_bands = 0, g_refusals = 0;
 static std::string g_what;                                      // the scenario at work, for a failing CHECK
 #define CHECK(c) do { g_checks++; if (!(c)) { fprintf(stderr, "%s:%d: %s\n  (%s; error \"%s\")\n", __FILE__, __LINE__, #c, g_what.c_str(), g_err); return 1; } } while (0)
 static const hipStream_t STREAM = (hipStream_t)0x3000;
@@ -251,9 +254,135 @@ static int codec_refusal()
     return 0;
 }
 
+// ---- canvas_tile_band, the driver of a band of the tile route, over a stub coder ---------------------------------------------------------------------
+// The stub's stream of tile t of level k is stub_size(k, t) bytes of pattern(k, t, .).  Its count() finds a job's level by the level's width
+// (the sweep's width has another at every level), checks that the job's rows are the model's -- the reduction's, pending or fresh -- and leaves
+// the offsets; with `set_flag` it reports the sticky flag set, with `fail` it fails
+static int stub_size(int k, long long t) { return 1 + (int)((k * 37 + t * 11) % 23); }
+struct StubCoder {
+    int codec, tile, ch; const int *C;
+    int set_flag = 0, fail = VFSMS_OK, counts = 0, writes = 0, bad_rows = 0;
+    struct { std::vector<unsigned long long> tile_offs; } run; std::vector<long long> keys;   // keys: level * 1000000 + tile number, in the payload's order
+    int count(const JpegTileJob *jobs, int n_jobs, const int *d_flag, int *flag)
+    {
+        counts++;
+        if (fail != VFSMS_OK) return fail;
+        std::vector<unsigned long long> &offs = run.tile_offs;
+        offs.assign(1, 0); keys.clear();
+        for (int j = 0; j < n_jobs; j++) {
+            const JpegTileJob &J = jobs[j];
+            int k = 0;
+            while (k <= ML && C[k] != J.cols) k++;
+            if (k > ML) { bad_rows++; continue; }
+            for (int y = J.row0; y < std::min(J.row0 + J.tile_rows * tile, J.rows); y++)
+                if (y < J.src_row0 || (size_t)(y - J.src_row0 + 1) * J.pitch > J.src_bytes || !row_is(J.src + (size_t)(y - J.src_row0) * J.pitch, k, y, J.pitch)) bad_rows++;
+            const int ntx = (J.cols + tile - 1) / tile;
+            for (long long t = (long long)(J.row0 / tile) * ntx; t < (long long)(J.row0 / tile + J.tile_rows) * ntx; t++) {
+                keys.push_back(k * 1000000LL + t);
+                offs.push_back(offs.back() + stub_size(k, t));
+            }
+        }
+        *flag = set_flag ? 1 : *d_flag;
+        return VFSMS_OK;
+    }
+    int write(uint8_t *out)
+    {
+        writes++;
+        const std::vector<unsigned long long> &offs = run.tile_offs;
+        for (size_t g = 0; g < keys.size(); g++)
+            for (unsigned long long i = 0; i < offs[g + 1] - offs[g]; i++) out[offs[g] + i] = pattern((int)(keys[g] / 1000000), (int)(keys[g] % 1000000), (size_t)i);
+        return VFSMS_OK;
+    }
+};
+
+// one walk of the driver over the canvas `cv` in bands of `len` rows.  Every band comes with too little room first -- a byte, then a record
+// short: VFSMS_ERR_CAPACITY, the true sizes, the state as it was, nothing written -- on some bands with the flag set and with a failing count
+// as well, and then with room: the model's records, the running sum of the stub's sizes, the stub's pattern
+static int drive(vfsms_ctx *ctx, CanvasRec *cv, int tile, int levels, int len)
+{
+    const int rows = cv->rows, cols = cv->cols, ch = cv->ch;
+    char what[160];
+    snprintf(what, sizeof(what), "driver: %d x %d x %d, tile %d, levels %d, bands of %d", rows, cols, ch, tile, levels, len);
+    g_what = what; g_walks++;
+    int R[ML + 1], C[ML + 1], emitted[ML + 1] = {};
+    R[0] = rows; C[0] = cols;
+    for (int k = 1; k <= ML; k++) { R[k] = (R[k - 1] + 1) >> 1; C[k] = (C[k - 1] + 1) >> 1; }
+    PyrPending &P = cv->pend;
+    const int codec = ch == 3 ? VFSMS_PYR_CODEC_DEFLATE : VFSMS_PYR_CODEC_JPEG;
+    for (int row0 = 0, band_no = 0; row0 < rows; band_no++) {
+        const int nrows = std::min(len, rows - row0);
+        const bool last = row0 + nrows == rows;
+        g_driver_bands++;
+        auto reduce = [&](uint8_t *const *lvl) {                  // the band's share of every level, where the plan says
+            for (int k = 1; k <= levels; k++) {
+                const size_t pitch = (size_t)C[k] * ch;
+                const int first = row0 >> k, end = (int)(((long long)row0 + nrows + (1 << k) - 1) >> k);
+                for (int y = first; y < end; y++) for (size_t i = 0; i < pitch; i++) lvl[k][(size_t)(y - first) * pitch + i] = pattern(k, y, i);
+            }
+            return (int)VFSMS_OK;
+        };
+        // the model: the tiles due, their sizes
+        std::vector<long long> expect; std::vector<unsigned long long> offs(1, 0);
+        for (int k = 0; k <= levels; k++) {
+            const int exist = (int)(((long long)row0 + nrows + (1 << k) - 1) >> k), ntx = (C[k] + tile - 1) / tile;
+            const int upto = last ? (R[k] + tile - 1) / tile : exist / tile;
+            for (long long t = (long long)emitted[k] * ntx; t < (long long)upto * ntx; t++) { expect.push_back(k * 1000000LL + t); offs.push_back(offs.back() + stub_size(k, t)); }
+            emitted[k] = upto;
+        }
+        const size_t total = (size_t)offs.back(), n = expect.size();
+        CHECK(n > 0 && total >= n);
+        if (row0 == 0) CHECK(P.begin("drive", rows, cols, ch, 0, nrows, tile, levels, ctx->stream, codec) == VFSMS_OK);   // (row0 = 0 starts a walk: begin's own doing)
+        const State before = state_of(P);
+        const long live = g_hip.live;
+        // too little room, a flag, a failure: refused with nothing consumed and nothing written
+        struct Refusal { size_t cap_short; int index_short, set_flag, fail, rc; };
+        std::vector<Refusal> refusals = {{1, 0, 0, VFSMS_OK, VFSMS_ERR_CAPACITY}, {0, 1, 0, VFSMS_OK, VFSMS_ERR_CAPACITY}};
+        if ((rows + band_no) % 8 == 0) { refusals.push_back({0, 0, 1, VFSMS_OK, VFSMS_ERR_BAD_ARG}); refusals.push_back({0, 0, 0, VFSMS_ERR_HIP, VFSMS_ERR_HIP}); }
+        for (const Refusal &r : refusals) {
+            StubCoder stub{codec, tile, ch, C};
+            stub.set_flag = r.set_flag; stub.fail = r.fail;
+            std::vector<uint8_t> out(total - r.cap_short, 0xAB);
+            std::vector<int64_t> index((n - r.index_short) * 4, -77);
+            size_t nbytes = 0; int n_index = -1;
+            g_err[0] = 0;
+            CHECK(canvas_tile_band(ctx, cv, "drive", row0, nrows, levels, tile, stub, reduce, out.data(), out.size(), &nbytes, index.data(), (int)(n - r.index_short), &n_index) == r.rc);
+            CHECK(stub.counts == 1 && stub.writes == 0 && stub.bad_rows == 0 && n_index == (int)n);
+            if (r.rc == VFSMS_ERR_CAPACITY) { CHECK(nbytes == total && strstr(g_err, "drive: the band takes ")); g_refusals++; }
+            if (r.set_flag) CHECK(strstr(g_err, "fuse: degenerate corner geometry"));
+            CHECK(same(before, state_of(P)) && live == g_hip.live);
+            for (uint8_t b : out) CHECK(b == 0xAB);
+            for (int64_t v : index) CHECK(v == -77);
+        }
+        // with room
+        StubCoder stub{codec, tile, ch, C};
+        std::vector<uint8_t> out(total, 0xAB);
+        std::vector<int64_t> index(n * 4, -77);
+        size_t nbytes = 0; int n_index = -1;
+        CHECK(canvas_tile_band(ctx, cv, "drive", row0, nrows, levels, tile, stub, reduce, out.data(), out.size(), &nbytes, index.data(), (int)n, &n_index) == VFSMS_OK);
+        CHECK(stub.counts == 1 && stub.writes == 1 && stub.bad_rows == 0 && nbytes == total && n_index == (int)n && P.next == row0 + nrows);
+        for (size_t g = 0; g < n; g++) {
+            CHECK(index[4 * g] * 1000000LL + index[4 * g + 1] == expect[g] && index[4 * g + 2] == (int64_t)offs[g] && index[4 * g + 3] == stub_size((int)index[4 * g], index[4 * g + 1]));
+            for (size_t i = 0; i < (size_t)(offs[g + 1] - offs[g]); i++) CHECK(out[(size_t)offs[g] + i] == pattern((int)(expect[g] / 1000000), (int)(expect[g] % 1000000), i));
+        }
+        row0 += nrows;
+    }
+    for (int k = 0; k <= levels; k++) CHECK(emitted[k] == (R[k] + tile - 1) / tile);
+    return 0;
+}
+
 static int run()
 {
     if (band_check_checks() || flag_checks() || start_failure() || codec_refusal()) return 1;
+    // the driver over a sub-sweep of the canvases below: one width with another width at every level, one record per canvas walked again and again
+    for (int rows = 1; rows <= 80; rows++) for (int ch : {1, 3}) {
+        vfsms_ctx ctx; ctx.stream = STREAM;
+        CanvasRec cv; cv.rows = rows; cv.cols = 40; cv.ch = ch;
+        g_what = "driver canvas";
+        CHECK(cv.d_err.reserve(sizeof(int), STREAM) == VFSMS_OK && cv.pix.reserve((size_t)rows * 40 * ch, STREAM) == VFSMS_OK);
+        *cv.d_err.as<int>() = 0;
+        for (int y = 0; y < rows; y++) for (size_t i = 0; i < (size_t)40 * ch; i++) cv.pix.as<uint8_t>()[(size_t)y * 40 * ch + i] = pattern(0, y, i);
+        for (int levels = 0; levels <= 3; levels++) for (int len : {16, 48}) if (drive(&ctx, &cv, 16, levels, len)) return 1;
+    }
     // the sweep: one record per canvas, walked again and again with another level count and band length, as a canvas that is written twice
     for (int rows = 1; rows <= 80; rows++) for (int cols : {1, 17, 40}) for (int ch : {1, 3}) {
         PyrPending P;
@@ -282,6 +411,7 @@ int main()
 {
     if (run()) return 1;
     if (g_hip.live != 0) { fprintf(stderr, "%ld allocations still live\n", g_hip.live); return 1; }
-    printf("canvas_band_host_check: %ld checks ok, %ld walks, %ld bands, %ld injected failures\n", g_checks, g_walks, g_bands, g_injections);
+    printf("canvas_band_host_check: %ld checks ok, %ld walks, %ld bands, %ld injected failures, %ld driver bands (%ld capacity refusals)\n",
+           g_checks, g_walks, g_bands, g_injections, g_driver_bands, g_refusals);
     return 0;
 }
