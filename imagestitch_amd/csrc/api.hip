@@ -2,6 +2,7 @@
 #include "common.h"
 #include "canvas_band.h"
 #include "ingest_fill.h"
+#include "tile_table.h"
 #include "jpeg_huff_core.h"
 #include "phase_resolve_math.h"
 #include <math.h>
@@ -349,7 +350,7 @@ static int tile_upload_impl(vfsms_ctx *ctx, const uint8_t *img, int h, int w_px,
 {
     const int w = w_px * ch;                                 // bytes per row
     if (!img || !handle || h <= 0 || w_px <= 0 || ch < 1 || ch > 4 || stride < w) { vfsms_set_error("tile_upload: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    TileRec t; t.h = h; t.w = w_px; t.stride = w; t.owned = true; t.ready = nullptr; t.pending = false; t.ch = ch; t.bytes = (size_t)h * w;
+    TileRec t = tile_rec(nullptr, h, w_px, ch, w, true);
     TRY(tile_buffer(ctx, t.bytes, &t.ptr, async ? ctx->copy_stream : ctx->stream));
     if (async) {
         // the copy runs on the context's copy stream; the compute stream waits for it when a batch first names the tile
@@ -362,31 +363,15 @@ static int tile_upload_impl(vfsms_ctx *ctx, const uint8_t *img, int h, int w_px,
         HIP_TRY(hipMemcpy2DAsync(t.ptr, w, img, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    std::lock_guard<std::mutex> lk(ctx->tiles_mu);           // (decoder threads look tiles up concurrently: vfsms_tile_fill)
-    *handle = ctx->next_handle++;
-    ctx->tiles[*handle] = t;
-    return VFSMS_OK;
-}
-// make the compute stream wait for a tile's asynchronous upload (once)
-static int tile_ready(vfsms_ctx *ctx, TileRec &t)
-{
-    // `fill` and `pending` are written by decoder threads (vfsms_tile_fill*): read them under the same mutex.  Everything else in a
-    // TileRec, the tile map's structure, the buffer / event pools and the arena belong to the context's own thread (reserve, upload,
-    // free and every batch call must come from it).
-    std::unique_lock<std::mutex> lk(ctx->tiles_mu);
-    if (t.fill) {                                            // reserved: block until its decoder thread has handed the pixels over
-        ctx->tiles_cv.wait(lk, [&] { return t.fill != 1; });
-        if (t.fill == 2) { vfsms_set_error("a reserved tile was never filled (its decoder reported a failure)"); return VFSMS_ERR_BAD_ARG; }
-    }
-    if (t.pending) { HIP_TRY(hipStreamWaitEvent(ctx->stream, t.ready, 0)); t.pending = false; }
+    tile_register(ctx, t, handle);
     return VFSMS_OK;
 }
 // the two resident tiles a job of `who` names, handed over (tile_ready); what else they must satisfy is the caller's to check
 static int resident_pair(vfsms_ctx *ctx, const char *who, int k, const vfsms_ncc_job &j, TileRec **A, TileRec **B)
 {
-    auto ia = ctx->tiles.find(j.tile_a), ib = ctx->tiles.find(j.tile_b);
-    if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("%s: job %d names an unknown tile handle", who, k); return VFSMS_ERR_BAD_ARG; }
-    *A = &ia->second; *B = &ib->second;
+    if (tile_find(ctx, who, j.tile_a, A) != VFSMS_OK || tile_find(ctx, who, j.tile_b, B) != VFSMS_OK) {
+        vfsms_set_error("%s: job %d names an unknown tile handle", who, k); return VFSMS_ERR_BAD_ARG;
+    }
     TRY(tile_ready(ctx, **A)); TRY(tile_ready(ctx, **B));
     return VFSMS_OK;
 }
@@ -430,20 +415,18 @@ extern "C" int vfsms_tile_upload_ch(vfsms_ctx *ctx, const uint8_t *img, int h, i
 static int tile_reserve_impl(vfsms_ctx *ctx, int h, int w, int ch, int64_t *handle)
 {
     if (!handle || h <= 0 || w <= 0 || ch < 1 || ch > 4) { vfsms_set_error("tile_reserve: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-    TileRec t; t.h = h; t.w = w; t.stride = w * ch; t.owned = true; t.ready = nullptr; t.pending = false; t.ch = ch; t.bytes = (size_t)h * w * ch; t.fill = 1;
+    TileRec t = tile_rec(nullptr, h, w, ch, w * ch, true);
+    t.fill = 1;
     TRY(tile_buffer(ctx, t.bytes, &t.ptr, ctx->copy_stream));
     if (!ctx->event_pool.empty()) { t.ready = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
     else {
         hipError_t e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
         if (e != hipSuccess) {                               // the buffer goes back to the pool instead of leaking
-            PoolEnt pe; pe.bytes = t.bytes; pe.ptr = t.ptr; pe.idle = nullptr;
-            ctx->tile_pool.push_back(pe); ctx->tile_pool_bytes += pe.bytes;
+            (void)tile_pool_return(ctx, t.ptr, t.bytes, false);
             vfsms_set_error("tile_reserve: %s", hipGetErrorString(e)); return VFSMS_ERR_HIP;
         }
     }
-    *handle = ctx->next_handle++;
-    ctx->tiles[*handle] = t;
+    tile_register(ctx, t, handle);
     return VFSMS_OK;
 }
 extern "C" int vfsms_tile_reserve(vfsms_ctx *ctx, int h, int w, int64_t *handle)
@@ -737,36 +720,23 @@ extern "C" int vfsms_tile_wrap(vfsms_ctx *ctx, const void *device_ptr, int h, in
 {
     CTX_ENTER(ctx);
     if (!device_ptr || !handle || h <= 0 || w <= 0 || stride < w) { vfsms_set_error("tile_wrap: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    TileRec t; t.ptr = (uint8_t *)device_ptr; t.h = h; t.w = w; t.stride = stride; t.owned = false; t.ready = nullptr; t.pending = false;
-    std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-    *handle = ctx->next_handle++;
-    ctx->tiles[*handle] = t;
+    tile_register(ctx, tile_rec((uint8_t *)device_ptr, h, w, 1, stride, false), handle);
     return VFSMS_OK;
 }
 extern "C" int vfsms_tile_free(vfsms_ctx *ctx, int64_t handle)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->tiles.find(handle);
-    if (it == ctx->tiles.end()) { vfsms_set_error("tile_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    TileRec *t;
+    if (tile_find(ctx, "tile_free", handle, &t) != VFSMS_OK) { vfsms_set_error("tile_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
     {
         std::lock_guard<std::mutex> lk(ctx->tiles_mu);       // (fill is written by decoder threads)
-        if (it->second.fill == 1) { vfsms_set_error("tile_free: the tile is reserved and its decoder has not filled it yet"); return VFSMS_ERR_BAD_ARG; }
+        if (t->fill == 1) { vfsms_set_error("tile_free: the tile is reserved and its decoder has not filled it yet"); return VFSMS_ERR_BAD_ARG; }
     }
     // an upload may still be in flight; compute work on the tile may only be ENQUEUED (canvas paste / resident fuse return early)
-    if (it->second.pending) HIP_TRY(hipEventSynchronize(it->second.ready));
-    if (it->second.ready) ctx->event_pool.push_back(it->second.ready);
-    if (it->second.owned) {
-        // the pool is capped by bytes (colour tiles of a mosaic are three times a gray one) and by entries
-        if (ctx->tile_pool.size() < 256 && ctx->tile_pool_bytes + it->second.bytes <= ((size_t)8 << 30)) {
-            PoolEnt e; e.bytes = it->second.bytes; e.ptr = it->second.ptr; e.idle = nullptr;
-            if (!ctx->event_pool.empty()) { e.idle = ctx->event_pool.back(); ctx->event_pool.pop_back(); }
-            else HIP_TRY(hipEventCreateWithFlags(&e.idle, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(e.idle, ctx->stream));
-            ctx->tile_pool.push_back(e);
-            ctx->tile_pool_bytes += e.bytes;
-        } else { HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(hipFree(it->second.ptr)); }
-    }
-    { std::lock_guard<std::mutex> lk(ctx->tiles_mu); ctx->tiles.erase(it); }
+    if (t->pending) HIP_TRY(hipEventSynchronize(t->ready));
+    if (t->ready) ctx->event_pool.push_back(t->ready);
+    if (t->owned) TRY(tile_pool_return(ctx, t->ptr, t->bytes, true));
+    { std::lock_guard<std::mutex> lk(ctx->tiles_mu); ctx->tiles.erase(handle); }
     return VFSMS_OK;
 }
 
@@ -1568,9 +1538,9 @@ extern "C" int vfsms_phase_resolve_u8(vfsms_ctx *ctx, const uint8_t *a, const ui
 
 static int resolve_job(vfsms_ctx *ctx, const vfsms_roi_pair &j, const uint8_t **pa, int *sa, const uint8_t **pb, int *sb)
 {
-    auto ia = ctx->tiles.find(j.tile_a), ib = ctx->tiles.find(j.tile_b);
-    if (ia == ctx->tiles.end() || ib == ctx->tiles.end()) { vfsms_set_error("attempt: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
-    TileRec &A = ia->second, &B = ib->second;
+    TileRec *pA, *pB;
+    TRY(tile_find(ctx, "attempt", j.tile_a, &pA)); TRY(tile_find(ctx, "attempt", j.tile_b, &pB));
+    TileRec &A = *pA, &B = *pB;
     if (A.ch != 1 || B.ch != 1) { vfsms_set_error("attempt: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
     TRY(tile_ready(ctx, A)); TRY(tile_ready(ctx, B));
     if (j.h <= 0 || j.w <= 0 || j.ay0 < 0 || j.ax0 < 0 || j.by0 < 0 || j.bx0 < 0 || j.ay0 + j.h > A.h || j.ax0 + j.w > A.w ||
@@ -1900,9 +1870,9 @@ extern "C" int vfsms_features_surf(vfsms_ctx *ctx, int64_t tile, int y0, int x0,
                                    int enhance_mode, double clip_limit, int tile_grid, int64_t *feat, int *n_out)
 {
     CTX_ENTER(ctx);
-    auto it = ctx->tiles.find(tile);
-    if (it == ctx->tiles.end() || !params || !feat || !n_out) { vfsms_set_error("features_surf: bad arguments / unknown tile"); return VFSMS_ERR_BAD_ARG; }
-    TileRec &T = it->second;
+    TileRec *pT;
+    if (tile_find(ctx, "features_surf", tile, &pT) != VFSMS_OK || !params || !feat || !n_out) { vfsms_set_error("features_surf: bad arguments / unknown tile"); return VFSMS_ERR_BAD_ARG; }
+    TileRec &T = *pT;
     if (T.ch != 1) { vfsms_set_error("features_surf: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
     TRY(tile_ready(ctx, T));
     if (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 + h > T.h || x0 + w > T.w) { vfsms_set_error("features_surf: ROI outside the tile"); return VFSMS_ERR_BAD_ARG; }
@@ -1962,9 +1932,9 @@ static int features_surf_batch_impl(vfsms_ctx *ctx, const int64_t *tiles, int n,
         int c1 = c0; size_t need = 0;
         std::vector<TileRec *> T; std::vector<SurfSrc> S;
         while (c1 < n && c1 - c0 < 16) {
-            auto it = ctx->tiles.find(tiles[c1]);
-            if (it == ctx->tiles.end()) { vfsms_set_error("features_surf_batch: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
-            TileRec &t = it->second;
+            TileRec *pt;
+            TRY(tile_find(ctx, "features_surf_batch", tiles[c1], &pt));
+            TileRec &t = *pt;
             if (t.ch != 1) { vfsms_set_error("features_surf_batch: registration takes single-channel tiles"); return VFSMS_ERR_BAD_ARG; }
             const SurfSrc src{t.ptr, t.stride, t.h, t.w, kp_capacity(ctx, t.h, t.w)};
             const size_t b = surf_run_bytes(&src, 1, params, enh);
@@ -2294,9 +2264,9 @@ static int canvas_place_host(vfsms_ctx *ctx, const char *who, int64_t canvas, co
 // a resident tile of the canvas's channel count: known, handed over (tile_ready) and densely packed; its shape completes the placement
 static int canvas_resident_tile(vfsms_ctx *ctx, const char *who, const CanvasRec *cv, int64_t tile, Placement *p, const uint8_t **d_tile)
 {
-    auto jt = ctx->tiles.find(tile);
-    if (jt == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", who); return VFSMS_ERR_BAD_ARG; }
-    TileRec &tr = jt->second;
+    TileRec *pt;
+    TRY(tile_find(ctx, who, tile, &pt));
+    TileRec &tr = *pt;
     TRY(tile_ready(ctx, tr));
     if (cv->ch != tr.ch || tr.stride != tr.w * tr.ch) {
         vfsms_set_error("%s: a resident tile must have the canvas's channel count and be densely packed (stride == w * ch)", who); return VFSMS_ERR_BAD_ARG;
@@ -2679,23 +2649,12 @@ extern "C" int vfsms_canvas_encode_png_rows(vfsms_ctx *ctx, int64_t canvas, int 
 }
 
 // ---- shading correction (Method.shadingCorrection; shading_kernels.hip, specified by tests/shading_ref.py) ----------------------------
-// the tiles of a shading call: known, handed over (tile_ready) and of one shape
-static int shade_tiles(vfsms_ctx *ctx, const char *what, int n, const int64_t *tiles, std::vector<TileRec *> &T)
-{
-    if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles) { vfsms_set_error("%s: 1..%d tiles", what, VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
-    T.resize(n);
-    for (int i = 0; i < n; i++) {
-        auto it = ctx->tiles.find(tiles[i]);
-        if (it == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", what); return VFSMS_ERR_BAD_ARG; }
-        T[i] = &it->second;
-        if (T[i]->h != T[0]->h || T[i]->w != T[0]->w || T[i]->ch != T[0]->ch) {
-            vfsms_set_error("%s: tile %d is %d x %d x %d, tile 0 is %d x %d x %d", what, i, T[i]->h, T[i]->w, T[i]->ch, T[0]->h, T[0]->w, T[0]->ch);
-            return VFSMS_ERR_BAD_ARG;
-        }
-    }
-    for (int i = 0; i < n; i++) TRY(tile_ready(ctx, *T[i]));
-    return VFSMS_OK;
-}
+// what the calls that take a list of tiles ask of it (TileRule, tile_table.h: count, noun, gray or B G R, one shape, rewritten)
+static const TileRule SHADE_READ{1, VFSMS_SHADE_MAX_TILES, false, "tile", false, true, false, nullptr};
+static const TileRule SHADE_REWRITE{1, VFSMS_SHADE_MAX_TILES, false, "tile", false, true, true, nullptr};
+static const TileRule ANY_REWRITE{1, VFSMS_SHADE_MAX_TILES, false, "tile", false, false, true, nullptr};
+static const TileRule FOCUS_STACK{VFSMS_FOCUS_MIN_PLANES, VFSMS_FOCUS_MAX_PLANES, true, "plane", true, true, false, nullptr};
+static const TileRule FOCUS_SCORES{1, VFSMS_FOCUS_MAX_TILES, true, "tile", true, false, false, nullptr};
 static int shade_field_new(vfsms_ctx *ctx, int h, int w, int ch, bool estimated, ShadeRec *F)
 {
     const size_t P = (size_t)h * w * ch, Pa = (P + 127) & ~(size_t)127;      // the three planes stay 256-byte aligned
@@ -2711,14 +2670,12 @@ extern "C" int vfsms_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *tile
         vfsms_set_error("shading_estimate: percentile %d / radius %d (0..100; 1..%d)", percentile, radius, VFSMS_SHADE_MAX_RADIUS);
         return VFSMS_ERR_BAD_ARG;
     }
-    std::vector<TileRec *> T;
-    TRY(shade_tiles(ctx, "shading_estimate", n, tiles, T));
-    std::vector<ShadeTileHost> H(n);
-    for (int i = 0; i < n; i++) { H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride; }
-    TRY(ctx_arena_reserve(ctx, sizeof(ShadeTileHost) * 2 * (size_t)n + 65536));
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "shading_estimate", SHADE_READ, tiles, n, H));
+    TRY(ctx_arena_reserve(ctx, sizeof(TileView) * 2 * (size_t)n + 65536));
     ctx->pinned_off = 0;
     ShadeRec F;
-    TRY(shade_field_new(ctx, T[0]->h, T[0]->w, T[0]->ch, true, &F));
+    TRY(shade_field_new(ctx, H[0].h, H[0].w, H[0].ch, true, &F));
     int rc = shade_estimate_device(ctx, H.data(), n, F.h, F.w, F.ch, percentile, radius, F.gain.as<uint16_t>(), F.q8, F.prof);
     if (rc == VFSMS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { vfsms_set_error("shading_estimate: the kernels failed"); rc = VFSMS_ERR_HIP; }
     if (rc != VFSMS_OK) { hipStreamSynchronize(ctx->stream); return rc; }      // (the field goes with F; nothing enqueued may still write it)
@@ -2759,21 +2716,15 @@ extern "C" int vfsms_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const i
     auto it = ctx->shade_fields.find(field);
     if (it == ctx->shade_fields.end()) { vfsms_set_error("shading_apply: unknown handle"); return VFSMS_ERR_BAD_ARG; }
     const ShadeRec &F = it->second;
-    std::vector<TileRec *> T;
-    TRY(shade_tiles(ctx, "shading_apply", n, tiles, T));
-    if (T[0]->h != F.h || T[0]->w != F.w || T[0]->ch != F.ch) {
-        vfsms_set_error("shading_apply: the tiles are %d x %d x %d, the field is %d x %d x %d", T[0]->h, T[0]->w, T[0]->ch, F.h, F.w, F.ch);
+    TileRule rule = SHADE_REWRITE;
+    rule.pred = [&F](int, const TileRec &t) {                // (the tiles are of one shape: tile 0 answers for all)
+        if (t.h == F.h && t.w == F.w && t.ch == F.ch) return VFSMS_OK;
+        vfsms_set_error("shading_apply: the tiles are %d x %d x %d, the field is %d x %d x %d", t.h, t.w, t.ch, F.h, F.w, F.ch);
         return VFSMS_ERR_BAD_ARG;
-    }
-    std::vector<int64_t> seen(tiles, tiles + n);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("shading_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
-    std::vector<ShadeTileHost> H(n);
-    for (int i = 0; i < n; i++) {
-        if (!T[i]->owned) { vfsms_set_error("shading_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
-        H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride;
-    }
-    TRY(ctx_arena_reserve(ctx, sizeof(ShadeTileHost) * 2 * (size_t)n + 65536));
+    };
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "shading_apply", rule, tiles, n, H));
+    TRY(ctx_arena_reserve(ctx, sizeof(TileView) * 2 * (size_t)n + 65536));
     ctx->pinned_off = 0;
     TRY(shade_apply_device(ctx, H.data(), n, F.h, F.w, F.ch, F.gain.as<uint16_t>()));
     HIP_TRY(hipStreamSynchronize(ctx->stream));            // the tile table went through the pinned staging buffer: synchronous like every call that uses it
@@ -2790,30 +2741,8 @@ extern "C" int vfsms_shading_free(vfsms_ctx *ctx, int64_t field)
 }
 
 // ---- focus stacking (Method.focusStack; focus_kernels.hip, specified by tests/focus_ref.py) ----------------------------------------------
-// the tiles of a focus call: known, gray or B G R, of one shape when `same`, handed over (tile_ready) -- judged before anything is enqueued
-static int focus_tiles(vfsms_ctx *ctx, const char *what, int n, int lo, int hi, const int64_t *tiles, bool same, std::vector<FocusTileHost> &H)
-{
-    if (n < lo || n > hi || !tiles) { vfsms_set_error("%s: %d..%d tiles, got %d", what, lo, hi, n); return VFSMS_ERR_BAD_ARG; }
-    std::vector<TileRec *> T(n);
-    for (int i = 0; i < n; i++) {
-        auto it = ctx->tiles.find(tiles[i]);
-        if (it == ctx->tiles.end()) { vfsms_set_error("%s: unknown tile handle", what); return VFSMS_ERR_BAD_ARG; }
-        T[i] = &it->second;
-        if (T[i]->ch != 1 && T[i]->ch != 3) { vfsms_set_error("%s: tile %d has %d channels (1 or 3)", what, i, T[i]->ch); return VFSMS_ERR_BAD_ARG; }
-        if (same && (T[i]->h != T[0]->h || T[i]->w != T[0]->w || T[i]->ch != T[0]->ch)) {
-            vfsms_set_error("%s: plane %d is %d x %d x %d, plane 0 is %d x %d x %d", what, i, T[i]->h, T[i]->w, T[i]->ch, T[0]->h, T[0]->w, T[0]->ch);
-            return VFSMS_ERR_BAD_ARG;
-        }
-    }
-    H.resize(n);
-    for (int i = 0; i < n; i++) {
-        TRY(tile_ready(ctx, *T[i]));
-        H[i].ptr = T[i]->ptr; H[i].stride = T[i]->stride; H[i].h = T[i]->h; H[i].w = T[i]->w; H[i].ch = T[i]->ch;
-    }
-    return VFSMS_OK;
-}
 // what a focus call enqueues between its checks and its read-back; d_out: the new tile's buffer or arena memory
-static int focus_run(vfsms_ctx *ctx, const std::vector<FocusTileHost> &H, int mode, int radius, int median, uint8_t *d_out, uint8_t *d_pre, uint8_t *d_index,
+static int focus_run(vfsms_ctx *ctx, const std::vector<TileView> &H, int mode, int radius, int median, uint8_t *d_out, uint8_t *d_pre, uint8_t *d_index,
                      unsigned long long *d_scores, uint32_t *d_partials, std::vector<unsigned long long> &S)
 {
     const int n = (int)H.size(), h = H[0].h, w = H[0].w, ch = H[0].ch;
@@ -2839,12 +2768,12 @@ extern "C" int vfsms_focus_stack(vfsms_ctx *ctx, int n, const int64_t *planes, i
         vfsms_set_error("focus_stack: mode %d / radius %d / median %d (0 pixel or 1 plane; 1..%d; 0 or 1)", mode, radius, median, VFSMS_FOCUS_MAX_RADIUS);
         return VFSMS_ERR_BAD_ARG;
     }
-    std::vector<FocusTileHost> H;
-    TRY(focus_tiles(ctx, "focus_stack", n, VFSMS_FOCUS_MIN_PLANES, VFSMS_FOCUS_MAX_PLANES, planes, true, H));
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "focus_stack", FOCUS_STACK, planes, n, H));
     const int h = H[0].h, w = H[0].w, ch = H[0].ch;
     const size_t px = (size_t)h * w, bytes = px * ch;
     const size_t pbytes = mode == 0 ? focus_partials_bytes(n, h, w) : 0;
-    TRY(ctx_arena_reserve(ctx, 2 * px + (out_tile ? 0 : bytes) + pbytes + (sizeof(FocusTileHost) * 2 + 8) * (size_t)n + 65536));
+    TRY(ctx_arena_reserve(ctx, 2 * px + (out_tile ? 0 : bytes) + pbytes + (sizeof(TileView) * 2 + 8) * (size_t)n + 65536));
     ctx->pinned_off = 0;
     uint8_t *d_pre = (uint8_t *)ctx_arena_alloc(ctx, px), *d_index = (uint8_t *)ctx_arena_alloc(ctx, px);
     unsigned long long *d_scores = (unsigned long long *)ctx_arena_alloc(ctx, sizeof(unsigned long long) * n);
@@ -2858,25 +2787,20 @@ extern "C" int vfsms_focus_stack(vfsms_ctx *ctx, int n, const int64_t *planes, i
     if (rc == VFSMS_OK && index && hipMemcpy(index, d_index, px, hipMemcpyDeviceToHost) != hipSuccess) { vfsms_set_error("focus_stack: the download failed"); rc = VFSMS_ERR_HIP; }
     if (rc != VFSMS_OK) {
         hipStreamSynchronize(ctx->stream);                   // (nothing enqueued may still write the buffer that goes back to the pool)
-        if (out_tile) { PoolEnt pe; pe.bytes = bytes; pe.ptr = d_out; pe.idle = nullptr; ctx->tile_pool.push_back(pe); ctx->tile_pool_bytes += bytes; }
+        if (out_tile) (void)tile_pool_return(ctx, d_out, bytes, false);
         return rc;
     }
     if (scores) for (int i = 0; i < n; i++) scores[i] = (int64_t)S[i];
-    if (out_tile) {
-        TileRec t; t.ptr = d_out; t.h = h; t.w = w; t.stride = w * ch; t.owned = true; t.ready = nullptr; t.pending = false; t.ch = ch; t.bytes = bytes;
-        std::lock_guard<std::mutex> lk(ctx->tiles_mu);
-        *out_tile = ctx->next_handle++;
-        ctx->tiles[*out_tile] = t;
-    }
+    if (out_tile) tile_register(ctx, tile_rec(d_out, h, w, ch, w * ch, true), out_tile);
     return VFSMS_OK;
 }
 extern "C" int vfsms_focus_scores(vfsms_ctx *ctx, int n, const int64_t *tiles, int64_t *scores)
 {
     CTX_ENTER(ctx);
     if (!scores) { vfsms_set_error("focus_scores: bad arguments"); return VFSMS_ERR_BAD_ARG; }
-    std::vector<FocusTileHost> H;
-    TRY(focus_tiles(ctx, "focus_scores", n, 1, VFSMS_FOCUS_MAX_TILES, tiles, false, H));
-    TRY(ctx_arena_reserve(ctx, (sizeof(FocusTileHost) * 2 + 8) * (size_t)n + 65536));
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "focus_scores", FOCUS_SCORES, tiles, n, H));
+    TRY(ctx_arena_reserve(ctx, (sizeof(TileView) * 2 + 8) * (size_t)n + 65536));
     ctx->pinned_off = 0;
     unsigned long long *d_scores = (unsigned long long *)ctx_arena_alloc(ctx, sizeof(unsigned long long) * n);
     if (!d_scores) { vfsms_set_error("arena exhausted (focus_scores)"); return VFSMS_ERR_CAPACITY; }
@@ -2918,22 +2842,9 @@ extern "C" int vfsms_exposure_apply(vfsms_ctx *ctx, int n, const int64_t *tiles,
 {
     CTX_ENTER(ctx);
     if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles || !gain_q12) { vfsms_set_error("exposure_apply: 1..%d tiles and a gain for each", VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
-    std::vector<int64_t> seen(tiles, tiles + n);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("exposure_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
-    std::vector<ExpTileHost> H(n);
-    std::vector<TileRec *> T(n);
-    for (int i = 0; i < n; i++) {
-        auto it = ctx->tiles.find(tiles[i]);
-        if (it == ctx->tiles.end()) { vfsms_set_error("exposure_apply: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
-        T[i] = &it->second;
-        if (!T[i]->owned) { vfsms_set_error("exposure_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
-    }
-    for (int i = 0; i < n; i++) {
-        TRY(tile_ready(ctx, *T[i]));
-        H[i] = ExpTileHost{T[i]->ptr, T[i]->stride, T[i]->h, T[i]->w * T[i]->ch};
-    }
-    TRY(ctx_arena_reserve(ctx, sizeof(ExpTileHost) * 2 * (size_t)n + 65536));
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "exposure_apply", ANY_REWRITE, tiles, n, H));
+    TRY(ctx_arena_reserve(ctx, sizeof(TileView) * 2 * (size_t)n + 65536));
     ctx->pinned_off = 0;
     TRY(exposure_apply_device(ctx, H.data(), n, gain_q12));
     HIP_TRY(hipStreamSynchronize(ctx->stream));            // the tile table went through the pinned staging buffer: synchronous like every call that uses it
@@ -2993,23 +2904,10 @@ static int lens_check_map(const char *who, int h, int w, int32_t a1_q30, int32_t
 extern "C" int vfsms_lens_apply(vfsms_ctx *ctx, int n, const int64_t *tiles, int32_t a1_q30, int32_t a2_q30, int32_t cy2, int32_t cx2, int interp)
 {
     CTX_ENTER(ctx);
-    if (n < 1 || n > VFSMS_SHADE_MAX_TILES || !tiles) { vfsms_set_error("lens_apply: 1..%d tiles", VFSMS_SHADE_MAX_TILES); return VFSMS_ERR_BAD_ARG; }
-    std::vector<int64_t> seen(tiles, tiles + n);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("lens_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
-    std::vector<TileRec *> T(n);
-    for (int i = 0; i < n; i++) {
-        auto it = ctx->tiles.find(tiles[i]);
-        if (it == ctx->tiles.end()) { vfsms_set_error("lens_apply: unknown tile handle"); return VFSMS_ERR_BAD_ARG; }
-        T[i] = &it->second;
-        if (!T[i]->owned) { vfsms_set_error("lens_apply: tile %d comes from vfsms_tile_wrap: the library does not own its memory and does not rewrite it", i); return VFSMS_ERR_BAD_ARG; }
-        TRY(lens_check_map("lens_apply", T[i]->h, T[i]->w, a1_q30, a2_q30, cy2, cx2, interp));
-    }
-    std::vector<LensTileHost> H(n);
-    for (int i = 0; i < n; i++) {
-        TRY(tile_ready(ctx, *T[i]));
-        H[i] = LensTileHost{T[i]->ptr, T[i]->stride, T[i]->h, T[i]->w, T[i]->ch};
-    }
+    TileRule rule = ANY_REWRITE;
+    rule.pred = [=](int, const TileRec &t) { return lens_check_map("lens_apply", t.h, t.w, a1_q30, a2_q30, cy2, cx2, interp); };
+    std::vector<TileView> H;
+    TRY(tile_list(ctx, "lens_apply", rule, tiles, n, H));
     TRY(lens_apply_device(ctx, H.data(), n, a1_q30, a2_q30, cy2, cx2, interp));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;

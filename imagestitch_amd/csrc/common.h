@@ -160,9 +160,9 @@ struct MatchDev {
 // ---- context ------------------------------------------------------------------------------------------
 // pending: an async upload the compute stream has not yet waited for; bytes: size of an owned allocation;
 // fill: 0 filled (or being copied: `ready` is recorded), 1 reserved -- a decoder thread still owes the pixels (vfsms_tile_fill), 2 the decoder gave up
-struct TileRec { uint8_t *ptr; int h, w, stride; bool owned; hipEvent_t ready; bool pending; int ch = 1; size_t bytes = 0; int fill = 0; };
+struct TileRec { uint8_t *ptr = nullptr; int h = 0, w = 0, stride = 0; bool owned = false; hipEvent_t ready = nullptr; bool pending = false; int ch = 1; size_t bytes = 0; int fill = 0; };   // made by tile_rec, entered by tile_register (tile_table.h)
 struct StageBuf { uint8_t *ptr; size_t bytes; };                    // device staging of one decoded source image (vfsms_tile_fill_pair)
-struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer; idle: recorded on the compute stream when the tile was freed
+struct PoolEnt { size_t bytes; uint8_t *ptr; hipEvent_t idle; };   // a freed tile buffer (tile_pool_return, tile_table.h); idle: recorded on the compute stream when the tile was freed
 // device scratch of the JPEG encoder (jpeg_enc_kernels.hip), grown to the largest band seen: quantised coefficients, interval sizes + offsets,
 // the coded stream, and (vfsms_jpeg_encode_device only) the staged image
 struct JpegScratch { DevBuf coef, sizes, out, img; };
@@ -235,7 +235,7 @@ struct vfsms_ctx {
     DevBuf d_area_tab;                   // INTER_AREA tables of every descriptor-window size (ctx_prepare_area_tab)
     vfsms_orb_params cur_orb = {}; bool orb_valid = false; DevBuf d_orb_tables;   // OrbTables
     std::unordered_map<int64_t, TileRec> tiles;
-    std::mutex tiles_mu; std::condition_variable tiles_cv;   // reserved tiles are filled by other threads (vfsms_tile_fill*): they look tiles up and write TileRec::fill / pending under this mutex and enqueue on the copy stream; the map's structure, the buffer / event pools and the arena belong to the context's own thread
+    std::mutex tiles_mu; std::condition_variable tiles_cv;   // what belongs to which thread: tile_table.h
     std::mutex stage_mu; std::vector<StageBuf> stage_pool;   // device staging buffers of the decoder threads (vfsms_tile_fill_pair), the pools they share
     std::vector<StageBuf> pin_pool;                          // pinned host staging of the same threads (also under stage_mu)
     hipStream_t copy_stream = nullptr;                            // H2D uploads of tiles, overlapped with compute (vfsms_tile_upload_async)
@@ -304,6 +304,7 @@ static std::vector<ShapeRun> shape_runs(const Rec *recs, int n)
 }
 
 // ---- kernel launchers (each is stream-ordered, no host sync) --------------------------------------------
+struct TileView;                   // a handed-over resident tile: pointer, row stride in bytes, rows, columns, channels (tile_table.h)
 // surf_kernels.hip
 // every record's device arrays are described ONCE, by X_layout(ArenaWalk &, XDev *, shape): X_bytes counts with it, X_carve carves with it
 void surf_roi_layout(ArenaWalk &a, RoiDev *r, const uint8_t *img, int stride, int h, int w, int cap, const vfsms_surf_params *p);
@@ -422,31 +423,28 @@ int seam_fuse_canvas(vfsms_ctx *ctx, CanvasRec *cv, const uint8_t *d_tile, const
                      int blend, int levels);
 int seam_fuse_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int r, int c, int ch, int dx, int dy, const int *mode,
                   int blend, int levels, uint8_t *d_out, int32_t *d_seam);
-// shading_kernels.hip: Method.shadingCorrection.  Tiles as (pointer, row stride in bytes); h rows of w * ch bytes
+// shading_kernels.hip: Method.shadingCorrection.  Tiles as TileView (tile_table.h), all h rows of w * ch bytes
 #define VFSMS_SHADE_MAX_TILES 4096
 #define VFSMS_SHADE_MAX_RADIUS 127
-struct ShadeTileHost { uint8_t *ptr; int stride; };
-int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, int percentile, int radius,
+int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, int percentile, int radius,
                           uint16_t *gain, uint16_t *q8, uint8_t *prof);
-int shade_apply_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, const uint16_t *gain);
+int shade_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, const uint16_t *gain);
 // exposure_kernels.hip: Method.exposureCompensation.  A pair: two whole tiles (pointers, row strides in bytes, rows, row lengths in
 // BYTES = w * ch) of one channel count and the offset in pixels (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)).  ExpJob is
 // what the kernel reads: the rectangle of B that has a partner in A, cut on the host in 64 bits, everything in bytes
 struct ExpPairHost { const uint8_t *a, *b; int sa, sb, ha, wa, hb, wb, ch, dx, dy; };
 struct ExpJob { const uint8_t *a, *b; int sa, sb, wa, wb, r0, nrows, c0, c1, dx, dyb; };
-struct ExpTileHost { uint8_t *ptr; int stride, h, wb; };
 int overlap_stats_device(vfsms_ctx *ctx, const ExpPairHost *pairs, int n, int lo, int hi, unsigned long long *d_out3);   // d_out3: [n][3] = N, Sa, Sb
-int exposure_apply_device(vfsms_ctx *ctx, const ExpTileHost *tiles, int n, const uint16_t *gain_q12);
-// focus_kernels.hip: Method.focusStack.  Tiles as (pointer, row stride in bytes, rows, columns, channels); FocusPlane: the same as the kernels
+int exposure_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, const uint16_t *gain_q12);
+// focus_kernels.hip: Method.focusStack.  Tiles as TileView (tile_table.h); FocusPlane: the same as the kernels
 // read it, uploaded once per call (focus_table_device).  d_index: h x w bytes, D before the median; d_scores: n sums, set by the launchers
 #define VFSMS_FOCUS_MIN_PLANES 2
 #define VFSMS_FOCUS_MAX_PLANES 64
 #define VFSMS_FOCUS_MAX_RADIUS 31
 #define VFSMS_FOCUS_MAX_TILES 4096
-struct FocusTileHost { const uint8_t *ptr; int stride, h, w, ch; };
 struct FocusPlane;
-int focus_table_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, FocusPlane **d_tab);
-int focus_scores_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, unsigned long long *d_scores);
+int focus_table_device(vfsms_ctx *ctx, const TileView *tiles, int n, FocusPlane **d_tab);
+int focus_scores_device(vfsms_ctx *ctx, const TileView *tiles, int n, unsigned long long *d_scores);
 size_t focus_partials_bytes(int n, int h, int w);          // d_partials of focus_select_device: the blocks' shares of the scores
 int focus_select_device(vfsms_ctx *ctx, const FocusPlane *d_tab, int n, int h, int w, int ch, int radius, uint8_t *d_index, unsigned long long *d_scores,
                         uint32_t *d_partials);
@@ -454,19 +452,18 @@ int focus_compose_device(vfsms_ctx *ctx, const FocusPlane *d_tab, const uint8_t 
                          uint8_t *d_out, int out_stride, uint8_t *d_index_out);
 // lens_kernels.hip: Method.lensCorrection (tests/lens_ref.py).  A block job: two whole tiles of ONE shape and channel count (pointers, row
 // strides in bytes) and the offset (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)); lens_lattice: its block lattice.  A tile
-// to resample: pointer, row stride in bytes, rows, columns, channels.  A centre coordinate below 0 stands for the tile's own middle
+// to resample: a TileView (tile_table.h).  A centre coordinate below 0 stands for the tile's own middle
 #define VFSMS_LENS_MAX_RADIUS 16
 #define VFSMS_LENS_MAX_BLOCK 128
 #define VFSMS_LENS_MAX_SIDE 16384
 #define VFSMS_LENS_MAX_COEF (1 << 28)
 struct LensBlockHost { const uint8_t *a, *b; int sa, sb, h, w, ch, dx, dy; };
-struct LensTileHost { uint8_t *ptr; int stride, h, w, ch; };
 void lens_lattice(int h, int w, int dx, int dy, int block, int radius, int *r0, int *c0, int *nby, int *nbx);
 int lens_blocks_device(vfsms_ctx *ctx, const LensBlockHost *jobs, const long long *h_first, int njobs, int block, int radius,
                        int32_t *d_best4, int32_t *d_surface);
 int lens_remap_device(vfsms_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, int dstride, int h, int w, int ch, int a1_q30, int a2_q30,
                       int cy2, int cx2, int interp);
-int lens_apply_device(vfsms_ctx *ctx, const LensTileHost *tiles, int n, int a1_q30, int a2_q30, int cy2, int cx2, int interp);
+int lens_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, int a1_q30, int a2_q30, int cy2, int cx2, int interp);
 // jpeg_host.cpp / jpeg_enc_kernels.hip: the device JPEG encoder (tests/jpeg_enc_ref.py)
 const uint8_t *jpeg_std_huff_bits(int ac, int chroma);
 const uint8_t *jpeg_std_huff_vals(int ac, int chroma);

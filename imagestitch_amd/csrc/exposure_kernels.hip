@@ -26,6 +26,7 @@
 // mask bits 65536 * 128 = 8 388 608, both < 2^32.  overlap_stats_device sizes the grid for about EXP_LANE_ITEMS chunks per lane and refuses
 // a job that would exceed the cap.  64 bits from the wave reduction on; one 64-bit vector atomic add per workgroup and sum.
 #include "common.h"
+#include "tile_table.h"
 #include "overlap_sums.h"
 #include <algorithm>
 
@@ -175,15 +176,17 @@ int overlap_stats_device(vfsms_ctx *ctx, const ExpPairHost *pairs, int n, int lo
 }
 
 // the n tiles corrected in place, tile i by gain_q12[i]; a gain of 4096 changes no byte, so such a tile gets no workgroup
-int exposure_apply_device(vfsms_ctx *ctx, const ExpTileHost *tiles, int n, const uint16_t *gain_q12)
+static_assert(sizeof(ExpTile) <= 2 * sizeof(TileView), "api.hip reserves two TileView per tile for the table and its staging");
+int exposure_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, const uint16_t *gain_q12)
 {
     std::vector<ExpTile> T;
     size_t most = 0;
     for (int i = 0; i < n; i++) {
         if (gain_q12[i] == 4096) continue;
-        const ExpTileHost &t = tiles[i];
-        T.push_back(ExpTile{t.ptr, t.stride, t.h, t.wb, gain_q12[i], t.stride == t.wb && ((uintptr_t)t.ptr & 15u) == 0});
-        most = std::max(most, (size_t)t.h * t.wb);
+        const TileView &t = tiles[i];
+        const int wb = t.w * t.ch;                             // a row in bytes
+        T.push_back(ExpTile{t.ptr, t.stride, t.h, wb, gain_q12[i], t.stride == wb && ((uintptr_t)t.ptr & 15u) == 0});
+        most = std::max(most, (size_t)t.h * wb);
     }
     if (T.empty() || most == 0) return VFSMS_OK;
     const size_t gx = (most + 16 * EXP_THREADS - 1) / (16 * EXP_THREADS);

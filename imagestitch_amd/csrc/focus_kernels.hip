@@ -30,6 +30,7 @@
 //   k_focus_compose     the 3 x 3 median of D (a 19-exchange network over nine bytes), the chosen plane's pixel gathered (1 or 3 bytes), out and
 //                       the final D written; const_d >= 0 (mode "plane") takes that plane everywhere
 #include "common.h"
+#include "tile_table.h"
 #include <algorithm>
 
 #define FOCUS_TW 64                    // block width in pixels = one wave64 per block row
@@ -232,7 +233,8 @@ __global__ __launch_bounds__(FOCUS_THREADS) void k_focus_compose(const FocusPlan
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
 // the tiles' pointers, strides and shapes as the kernels read them
-int focus_table_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, FocusPlane **d_tab)
+static_assert(sizeof(FocusPlane) <= 2 * sizeof(TileView), "api.hip reserves two TileView per tile for the table and its staging");
+int focus_table_device(vfsms_ctx *ctx, const TileView *tiles, int n, FocusPlane **d_tab)
 {
     std::vector<FocusPlane> T(n);
     for (int i = 0; i < n; i++) { T[i].ptr = tiles[i].ptr; T[i].stride = tiles[i].stride; T[i].h = tiles[i].h; T[i].w = tiles[i].w; T[i].ch = tiles[i].ch; }
@@ -240,7 +242,7 @@ int focus_table_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, FocusP
 }
 
 // S of n tiles of any shapes into d_scores (n x uint64, zeroed here)
-int focus_scores_device(vfsms_ctx *ctx, const FocusTileHost *tiles, int n, unsigned long long *d_scores)
+int focus_scores_device(vfsms_ctx *ctx, const TileView *tiles, int n, unsigned long long *d_scores)
 {
     size_t most = 0;
     for (int i = 0; i < n; i++) {

@@ -23,6 +23,7 @@
 // int64 accumulators; the taps of an interior pixel are read a row at a time.  The kernel never reads the buffer it writes:
 // lens_apply_device copies a tile into the context's lens scratch first and resamples from there.
 #include "common.h"
+#include "tile_table.h"
 #include "verify_math.h"
 #include <algorithm>
 
@@ -300,14 +301,14 @@ int lens_remap_device(vfsms_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, int 
 
 // the n tiles resampled in place, one after the other through the context's lens scratch (grown to the largest tile under device_buf.h's
 // rule): the copy and the kernel that reads it are ordered by the stream, and so is the next tile's copy behind that kernel
-int lens_apply_device(vfsms_ctx *ctx, const LensTileHost *tiles, int n, int a1_q30, int a2_q30, int cy2, int cx2, int interp)
+int lens_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, int a1_q30, int a2_q30, int cy2, int cx2, int interp)
 {
     size_t most = 0;
     for (int i = 0; i < n; i++) most = std::max(most, (size_t)tiles[i].h * tiles[i].w * tiles[i].ch);
     TRY(ctx->lens_scratch.reserve(most, ctx->stream));
     ProfScope ps(ctx, "lens_apply");
     for (int i = 0; i < n; i++) {
-        const LensTileHost &t = tiles[i];
+        const TileView &t = tiles[i];
         const size_t rowb = (size_t)t.w * t.ch;
         if ((size_t)t.stride == rowb) HIP_TRY(hipMemcpyAsync(ctx->lens_scratch.as<void>(), t.ptr, rowb * t.h, hipMemcpyDeviceToDevice, ctx->stream));
         else HIP_TRY(hipMemcpy2DAsync(ctx->lens_scratch.as<void>(), rowb, t.ptr, (size_t)t.stride, rowb, (size_t)t.h, hipMemcpyDeviceToDevice, ctx->stream));

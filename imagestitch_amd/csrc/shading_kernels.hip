@@ -19,6 +19,7 @@
 //   k_shade_level   per-channel 64-bit sums (LDS atomics per workgroup, one vector atomic per workgroup and channel), k_shade_gain the division
 //   k_shade_apply   grid over 16-byte blocks of a tile, inner loop over the tiles: a gain vector is loaded once and used N times
 #include "common.h"
+#include "tile_table.h"
 #include <algorithm>
 
 #define SHADE_LDS_MAX_N 320            // tiles a wave stages in LDS: 320 x 256 B = 80 KiB, two waves per CU
@@ -172,7 +173,8 @@ __global__ __launch_bounds__(256) void k_shade_apply(const ShadeTile *tiles, int
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------------
-static int shade_table(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int wb, size_t align, ShadeTile **d_tiles, int *dense)
+static_assert(sizeof(ShadeTile) <= 2 * sizeof(TileView), "api.hip reserves two TileView per tile for the table and its staging");
+static int shade_table(vfsms_ctx *ctx, const TileView *tiles, int n, int wb, size_t align, ShadeTile **d_tiles, int *dense)
 {
     std::vector<ShadeTile> T(n);
     *dense = 1;
@@ -184,7 +186,7 @@ static int shade_table(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int wb
 }
 
 // profile, smoothed field and gain of n tiles (h rows of w * ch bytes each) into the three planes of a field
-int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, int percentile, int radius,
+int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, int percentile, int radius,
                           uint16_t *gain, uint16_t *q8, uint8_t *prof)
 {
     const int wb = w * ch;
@@ -221,7 +223,7 @@ int shade_estimate_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int
 }
 
 // the n tiles corrected in place by a field's gain
-int shade_apply_device(vfsms_ctx *ctx, const ShadeTileHost *tiles, int n, int h, int w, int ch, const uint16_t *gain)
+int shade_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, const uint16_t *gain)
 {
     const int wb = w * ch;
     const size_t total64 = (size_t)h * wb;

@@ -4,6 +4,7 @@ and the compensation through Stitcher.getStitchByOffset alone, behind the shadin
 import ctypes as C
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -151,10 +152,12 @@ def test_apply_in_place(engine):
             assert np.array_equal(got, want[k]), (tiles[k].shape, gains[k], int(np.count_nonzero(got != want[k])))
             if gains[k] == 4096:
                 assert np.array_equal(got, tiles[k])
-        for bad in (lambda: engine.exposure_apply([handles[0], handles[1], handles[0]], [5000, 5000, 5000]),      # a tile named twice
-                    lambda: engine.exposure_apply([handles[0], 987654321], [5000, 5000]),                         # an unknown handle
-                    lambda: engine.exposure_apply([], [])):                                                      # n = 0
-            with pytest.raises(isa.VfsmsError):
+        # (the call, what the library says): one fault each, then two at once -- an unknown handle is reported before a tile named twice
+        for bad, says in ((lambda: engine.exposure_apply([handles[0], handles[1], handles[0]], [5000, 5000, 5000]), "exposure_apply: a tile is named twice (it would be corrected twice)"),
+                          (lambda: engine.exposure_apply([handles[0], 987654321], [5000, 5000]), "exposure_apply: unknown tile handle"),
+                          (lambda: engine.exposure_apply([], []), "exposure_apply: 1..4096 tiles and a gain for each"),          # n = 0
+                          (lambda: engine.exposure_apply([handles[0], handles[0], 987654321], [5000, 5000, 5000]), "exposure_apply: unknown tile handle")):
+            with pytest.raises(isa.VfsmsError, match=re.escape(says)):
                 bad()
         with pytest.raises(ValueError):
             engine.exposure_apply(handles[:2], [5000])

@@ -3,6 +3,7 @@ are no multiple of four bytes, several blocks with ragged edges, radii beyond th
 tile, strided tiles behind an odd base address, the refusals of the C ABI, and the two-step call through Stitcher."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -207,22 +208,41 @@ def test_refusals_create_no_tile(engine):
         with pytest.raises(isa.VfsmsError) as e:
             engine.focus_stack(handles, radius=0)
         assert "error %d:" % BAD_ARG in str(e.value)           # the code the binding reports for a bad argument
-        for rc in (raw(handles[:1]), raw([handles[k % 3] for k in range(65)]), raw([]),        # n outside 2..64
-                   raw(handles + [987654321]),                                                  # an unknown handle
-                   raw(handles + [ho]), raw(handles + [hc]),                                    # another shape, another channel count
-                   raw(h2),                                                                     # two channels
-                   raw(handles, radius=0), raw(handles, radius=32),
-                   raw(handles, median=2), raw(handles, median=-1),
-                   raw(handles, mode=2), raw(handles, mode=-1),
-                   raw_scores([]), raw_scores([handles[0]] * 4097), raw_scores([handles[0], 987654321]), raw_scores([handles[0], h2[0]])):
-            assert rc == BAD_ARG
+        def said():
+            buf = C.create_string_buffer(512)
+            lib.vfsms_last_error(buf, 512)
+            return buf.value.decode()
+        # (the call, what the library says): one fault each, then two at once -- an unknown handle is reported before any tile is judged
+        for call, says in ((lambda: raw(handles[:1]), "focus_stack: 2..64 tiles, got 1"),                       # n outside 2..64
+                           (lambda: raw([handles[k % 3] for k in range(65)]), "focus_stack: 2..64 tiles, got 65"),
+                           (lambda: raw([]), "focus_stack: 2..64 tiles, got 0"),
+                           (lambda: raw(handles + [987654321]), "focus_stack: unknown tile handle"),
+                           (lambda: raw(handles + [ho]), "focus_stack: plane 3 is 16 x 25 x 1, plane 0 is 16 x 24 x 1"),   # another shape
+                           (lambda: raw(handles + [hc]), "focus_stack: plane 3 is 16 x 24 x 3, plane 0 is 16 x 24 x 1"),   # another channel count
+                           (lambda: raw(h2), "focus_stack: tile 0 has 2 channels (1 or 3)"),
+                           (lambda: raw(handles, radius=0), "focus_stack: mode 0 / radius 0 / median 1 (0 pixel or 1 plane; 1..31; 0 or 1)"),
+                           (lambda: raw(handles, radius=32), "focus_stack: mode 0 / radius 32 / median 1"),
+                           (lambda: raw(handles, median=2), "focus_stack: mode 0 / radius 4 / median 2"),
+                           (lambda: raw(handles, median=-1), "focus_stack: mode 0 / radius 4 / median -1"),
+                           (lambda: raw(handles, mode=2), "focus_stack: mode 2 / radius 4 / median 1"),
+                           (lambda: raw(handles, mode=-1), "focus_stack: mode -1 / radius 4 / median 1"),
+                           (lambda: raw_scores([]), "focus_scores: 1..4096 tiles, got 0"),
+                           (lambda: raw_scores([handles[0]] * 4097), "focus_scores: 1..4096 tiles, got 4097"),
+                           (lambda: raw_scores([handles[0], 987654321]), "focus_scores: unknown tile handle"),
+                           (lambda: raw_scores([handles[0], h2[0]]), "focus_scores: tile 1 has 2 channels (1 or 3)"),
+                           (lambda: raw([handles[0], handles[0], 987654321]), "focus_stack: unknown tile handle"),
+                           (lambda: raw([h2[0], 987654321]), "focus_stack: unknown tile handle"),
+                           (lambda: raw_scores([h2[0], handles[0], handles[0], 987654321]), "focus_scores: unknown tile handle")):
+            assert call() == BAD_ARG and says in said(), (says, said())
         assert tile.value == -9 and (out == 7).all() and (D == 7).all() and (S == -5).all()
         nxt = engine.tile_upload(tiles[0])                     # handles are consecutive: none was taken in between
         assert nxt == h2[1] + 1
         engine.tile_free(nxt)
-        for bad in (lambda: engine.focus_stack([]), lambda: engine.focus_stack([987654321, handles[0]]),
-                    lambda: engine.focus_stack(handles + [ho]), lambda: engine.focus_scores([])):
-            with pytest.raises(isa.VfsmsError):
+        for bad, says in ((lambda: engine.focus_stack([]), "focus_stack: 2..64 tiles, got 0"),
+                          (lambda: engine.focus_stack([987654321, handles[0]]), "focus_stack: unknown tile handle"),
+                          (lambda: engine.focus_stack(handles + [ho]), "focus_stack: plane 3 is 16 x 25 x 1, plane 0 is 16 x 24 x 1"),
+                          (lambda: engine.focus_scores([]), "focus_scores: 1..4096 tiles, got 0")):
+            with pytest.raises(isa.VfsmsError, match=re.escape(says)):
                 bad()
         with pytest.raises(ValueError):
             engine.focus_stack(handles, mode="voxel")

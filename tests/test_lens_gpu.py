@@ -4,6 +4,7 @@ and from host arrays at ragged shapes, extreme coefficients and centres; the ref
 Stitcher.getStitchByOffset alone, behind the shading correction, in front of the exposure compensation and with given coefficients."""
 import ctypes as C
 import functools
+import re
 
 import numpy as np
 import pytest
@@ -274,15 +275,21 @@ def test_resampling_refusals(engine):
     tiles = [remap_tiles()[5], remap_tiles()[3], remap_tiles()[1]]
     handles = _upload(engine, tiles)
     try:
-        for bad in (lambda: engine.lens_apply([handles[0], handles[1], handles[0]], 1 << 20, 0),            # a tile named twice
-                    lambda: engine.lens_apply([handles[0], 987654321], 1 << 20, 0),                         # an unknown handle
-                    lambda: engine.lens_apply([], 1 << 20, 0),
-                    lambda: engine.lens_apply(handles[:2], (1 << 28) + 1, 0), lambda: engine.lens_apply(handles[:2], 0, -(1 << 28) - 1),
-                    lambda: engine.lens_apply(handles[:1], 1 << 20, 0, (95 + 48, 127)),                     # the centre outside the middle half
-                    lambda: engine.lens_apply(handles[:1], 1 << 20, 0, (95, 127 - 64)),
-                    lambda: engine.lens_apply([handles[0], handles[2]], 1 << 20, 0, (95, 127)),             # ... of the second tile (1 x 9)
-                    lambda: engine.lens_apply(handles[:2], 1 << 20, 0, (-1, -1), 2), lambda: engine.lens_apply(handles[:2], 1 << 20, 0, (-1, -1), -1)):
-            with pytest.raises(isa.VfsmsError):
+        # (the call, what the library says): one fault each, then two at once -- an unknown handle is reported before a tile named twice
+        for bad, says in ((lambda: engine.lens_apply([handles[0], handles[1], handles[0]], 1 << 20, 0), "lens_apply: a tile is named twice (it would be corrected twice)"),
+                          (lambda: engine.lens_apply([handles[0], 987654321], 1 << 20, 0), "lens_apply: unknown tile handle"),
+                          (lambda: engine.lens_apply([], 1 << 20, 0), "lens_apply: 1..4096 tiles"),
+                          (lambda: engine.lens_apply(handles[:2], (1 << 28) + 1, 0), "lens_apply: coefficients 268435457, 0 outside +-2^28 (Q30)"),
+                          (lambda: engine.lens_apply(handles[:2], 0, -(1 << 28) - 1), "lens_apply: coefficients 0, -268435457 outside +-2^28 (Q30)"),
+                          (lambda: engine.lens_apply(handles[:1], 1 << 20, 0, (95 + 48, 127)),                    # the centre outside the middle half
+                           "lens_apply: the centre (143, 127) / 2 lies outside the middle half of a 96 x 128 image"),
+                          (lambda: engine.lens_apply(handles[:1], 1 << 20, 0, (95, 127 - 64)), "lens_apply: the centre (95, 63) / 2 lies outside the middle half of a 96 x 128 image"),
+                          (lambda: engine.lens_apply([handles[0], handles[2]], 1 << 20, 0, (95, 127)),            # ... of the second tile (1 x 9)
+                           "lens_apply: the centre (95, 127) / 2 lies outside the middle half of a 1 x 9 image"),
+                          (lambda: engine.lens_apply(handles[:2], 1 << 20, 0, (-1, -1), 2), "lens_apply: interp 2 (0 bilinear or 1 cubic)"),
+                          (lambda: engine.lens_apply(handles[:2], 1 << 20, 0, (-1, -1), -1), "lens_apply: interp -1 (0 bilinear or 1 cubic)"),
+                          (lambda: engine.lens_apply([handles[0], handles[0], 987654321], 1 << 20, 0), "lens_apply: unknown tile handle")):
+            with pytest.raises(isa.VfsmsError, match=re.escape(says)):
                 bad()
         with pytest.raises(ValueError):
             engine.lens_apply(handles[:1], 1 << 20, 0, (-1, -1), "lanczos")

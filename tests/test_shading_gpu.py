@@ -3,6 +3,7 @@ tile count where the selection kernel changes path, the smoothed field and the g
 refusals of the C ABI, and the correction through Stitcher.getStitchByOffset and behind an untouched registration."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -218,22 +219,24 @@ def test_refusals_leave_the_tiles_unchanged(engine):
     f = engine.shading_estimate(handles, 50, 2)
     f25 = engine.shading_estimate([ho], 50, 2)
     try:
-        for bad in (lambda: engine.shading_estimate(handles + [ho], 50, 2),            # mixed shapes
-                    lambda: engine.shading_estimate(handles + [hc], 50, 2),            # mixed channel counts
-                    lambda: engine.shading_estimate(handles, 101, 2),
-                    lambda: engine.shading_estimate(handles, -1, 2),
-                    lambda: engine.shading_estimate(handles, 50, 0),
-                    lambda: engine.shading_estimate(handles, 50, 128),
-                    lambda: engine.shading_estimate([], 50, 2),                        # n = 0
-                    lambda: engine.shading_estimate(handles + [987654321], 50, 2),     # unknown tile
-                    lambda: engine.shading_apply(f, handles + [ho]),                   # mixed shapes
-                    lambda: engine.shading_apply(f25, handles),                        # field and tile mismatch
-                    lambda: engine.shading_apply(f, [handles[0], hw]),                 # a wrapped tile
-                    lambda: engine.shading_apply(f, [handles[0], handles[1], handles[0]]),   # a handle named twice
-                    lambda: engine.shading_apply(f, []),                               # n = 0
-                    lambda: engine.shading_apply(987654321, handles),                  # unknown field
-                    lambda: engine.shading_free(987654321)):
-            with pytest.raises(isa.VfsmsError):
+        # (the call, what the library says): one fault each, then two at once -- an unknown handle is reported before a handle named twice
+        for bad, says in ((lambda: engine.shading_estimate(handles + [ho], 50, 2), "shading_estimate: tile 3 is 16 x 25 x 1, tile 0 is 16 x 24 x 1"),   # mixed shapes
+                          (lambda: engine.shading_estimate(handles + [hc], 50, 2), "shading_estimate: tile 3 is 16 x 24 x 3, tile 0 is 16 x 24 x 1"),   # mixed channel counts
+                          (lambda: engine.shading_estimate(handles, 101, 2), "shading_estimate: percentile 101 / radius 2 (0..100; 1..127)"),
+                          (lambda: engine.shading_estimate(handles, -1, 2), "shading_estimate: percentile -1 / radius 2 (0..100; 1..127)"),
+                          (lambda: engine.shading_estimate(handles, 50, 0), "shading_estimate: percentile 50 / radius 0 (0..100; 1..127)"),
+                          (lambda: engine.shading_estimate(handles, 50, 128), "shading_estimate: percentile 50 / radius 128 (0..100; 1..127)"),
+                          (lambda: engine.shading_estimate([], 50, 2), "shading_estimate: 1..4096 tiles"),                        # n = 0
+                          (lambda: engine.shading_estimate(handles + [987654321], 50, 2), "shading_estimate: unknown tile handle"),
+                          (lambda: engine.shading_apply(f, handles + [ho]), "shading_apply: tile 3 is 16 x 25 x 1, tile 0 is 16 x 24 x 1"),   # mixed shapes
+                          (lambda: engine.shading_apply(f25, handles), "shading_apply: the tiles are 16 x 24 x 1, the field is 16 x 25 x 1"),
+                          (lambda: engine.shading_apply(f, [handles[0], hw]), "shading_apply: tile 1 comes from vfsms_tile_wrap: the library does not own its memory"),
+                          (lambda: engine.shading_apply(f, [handles[0], handles[1], handles[0]]), "shading_apply: a tile is named twice (it would be corrected twice)"),
+                          (lambda: engine.shading_apply(f, []), "shading_apply: 1..4096 tiles"),                                  # n = 0
+                          (lambda: engine.shading_apply(987654321, handles), "shading_apply: unknown handle"),                    # unknown field
+                          (lambda: engine.shading_free(987654321), "shading_free: unknown handle"),
+                          (lambda: engine.shading_apply(f, [handles[0], handles[0], 987654321]), "shading_apply: unknown tile handle")):
+            with pytest.raises(isa.VfsmsError, match=re.escape(says)):
                 bad()
         fw = engine.shading_estimate([hw], 50, 2)                                      # a wrapped tile may be READ
         try:

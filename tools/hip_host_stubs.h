@@ -1,11 +1,11 @@
-// hip_host_stubs.h -- the HIP runtime calls behind csrc/device_buf.h, csrc/ingest_fill.h and csrc/canvas_band.h, defined over malloc / free /
-// memcpy for the sanitizer-built host checks (device_buf_host_check.cpp, arena_layout_host_check.cpp, ingest_fill_host_check.cpp,
-// canvas_band_host_check.cpp): no GPU, no HIP runtime
+// hip_host_stubs.h -- the HIP runtime calls behind csrc/device_buf.h, csrc/ingest_fill.h, csrc/canvas_band.h and csrc/tile_table.h, defined
+// over malloc / free / memcpy for the sanitizer-built host checks (device_buf_host_check.cpp, arena_layout_host_check.cpp,
+// ingest_fill_host_check.cpp, canvas_band_host_check.cpp, tile_table_host_check.cpp): no GPU, no HIP runtime
 // at work, and ASan / LeakSanitizer see every "device" allocation and every "copy".  Include it in exactly one translation unit of a program.
-// Every call is logged (`sync(stream)`, `free(ptr)`, `malloc(n)`, `copy(dst)`, `record(event)`, `wait(event)`, ...), live allocations and
+// Every call is logged (`sync(stream)`, `free(ptr)`, `malloc(n)`, `copy(dst)`, `record(event)`, `wait(event)`, `stream_wait(event)`, ...), live allocations and
 // events are counted, and two injections make calls fail (a failing call is logged all the same): fail_at = N, the N-th allocation of either
 // kind from now; fail_call(kind, N), the N-th call of that kind from now -- "hipMalloc", "hipHostMalloc", "copy", "sync", "record",
-// "wait", "event_create".  A failed call leaves the runtime's sticky error behind until hipGetLastError takes it.
+// "wait", "stream_wait", "event_create".  A failed call leaves the runtime's sticky error behind until hipGetLastError takes it.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -84,6 +84,7 @@ hipError_t hipEventCreateWithFlags(hipEvent_t *ev, unsigned)
 hipError_t hipEventDestroy(hipEvent_t ev) { g_hip.log.push_back(stub_name("event_destroy", (const void *)ev)); free((void *)ev); g_hip.events--; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t ev, hipStream_t) { return stub_call("record", (const void *)ev); }
 hipError_t hipEventSynchronize(hipEvent_t ev) { return stub_call("wait", (const void *)ev, true); }
+hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t ev, unsigned) { return stub_call("stream_wait", (const void *)ev); }
 hipError_t hipGetLastError(void) { g_hip.log.push_back("getlasterror"); const hipError_t e = g_hip.sticky; g_hip.sticky = hipSuccess; return e; }
 const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : e == hipErrorUnknown ? "unknown error" : "error"; }
 }
