@@ -210,6 +210,11 @@ _SIGNATURES = {
     "vfsms_shading_free": (C.c_int, [C.c_void_p, C.c_int64]),
     "vfsms_focus_stack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfsms_focus_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfsms_deep_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_deep_free": (C.c_int, [C.c_void_p, C.c_int64]),
+    "vfsms_deep_window": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_deep_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_deep_mosaic_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_overlap_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_exposure_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_block_ncc_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1183,6 +1188,61 @@ class Engine:
         S = np.zeros(len(th), np.int64)
         self._check(self.lib.vfsms_focus_scores(self.ctx, len(th), _ptr(th), _ptr(S)))
         return S
+
+    # -- 16-bit tiles (tests/deep_ref.py is the specification) ------------------------------------------------------------------
+    DEEP_MODES = {"paste": 0, "notFuse": 0, "feather": 1}
+
+    def deep_upload(self, img):
+        """A 16-bit gray tile resident on the device (vfsms_deep_upload): a 2-D uint16 array, any row stride -> deep handle (deep_free).
+        A handle kind of its own: only the deep_* methods take it."""
+        img = np.asarray(img)
+        if img.dtype != np.uint16 or img.ndim != 2:
+            raise ValueError("deep_upload takes a 2-D uint16 array, got %s %s" % (img.dtype, img.shape))
+        if (img.shape[1] > 1 and img.strides[1] != 2) or img.strides[0] < 2 * img.shape[1]:
+            img = np.ascontiguousarray(img)
+        h = C.c_int64()
+        self._check(self.lib.vfsms_deep_upload(self.ctx, _ptr(img), img.shape[0], img.shape[1], img.strides[0], C.byref(h)))
+        self.__dict__.setdefault("_shapes", {})[("deep", h.value)] = (int(img.shape[0]), int(img.shape[1]))
+        return h.value
+
+    def deep_free(self, handle):
+        self._check(self.lib.vfsms_deep_free(self.ctx, C.c_int64(handle)))
+        self.__dict__.get("_shapes", {}).pop(("deep", handle), None)
+
+    def deep_window(self, handles, lo_ppm=1000, hi_ppm=999000):
+        """vfsms_deep_window: the samples of rank (N - 1) * ppm // 10^6 among all samples of the deep tiles, exactly -> (lo, hi), lo < hi"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        win = np.zeros(2, np.int32)
+        self._check(self.lib.vfsms_deep_window(self.ctx, len(th), _ptr(th), int(lo_ppm), int(hi_ppm), _ptr(win)))
+        return int(win[0]), int(win[1])
+
+    def deep_reduce(self, handles, lo, hi):
+        """vfsms_deep_reduce: the 8-bit views of the deep tiles through the window (lo, hi) -> NEW ordinary gray tile handles (tile_free)"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        out = np.zeros(len(th), np.int64)
+        self._check(self.lib.vfsms_deep_reduce(self.ctx, len(th), _ptr(th), int(lo), int(hi), _ptr(out)))
+        shapes = self.__dict__.setdefault("_shapes", {})
+        return [self._note_tile(int(t), shapes.get(("deep", int(d)), (0, 0))) for t, d in zip(out, th)]
+
+    def deep_mosaic_rows(self, handles, yx, rows, cols, mode="feather", feather=0, row0=0, nrows=None, out=None):
+        """vfsms_deep_mosaic_rows: rows [row0, row0 + nrows) of the rows x cols uint16 mosaic gathered from the deep tiles at yx (int [n][2],
+        top-left corners) -> uint16 [nrows][cols].  mode "paste" / "notFuse" (the largest covering index) or "feather" (the mean weighted by
+        the distance to each tile's border, cut at `feather` when positive); 0 / 1 as in include/vfsms.h.  Stateless: any band on demand."""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        at = np.ascontiguousarray(yx, np.int32).reshape(-1, 2)
+        if len(at) != len(th):
+            raise ValueError("deep_mosaic_rows: %d tiles, %d positions" % (len(th), len(at)))
+        nrows = int(rows) - int(row0) if nrows is None else int(nrows)
+        m = self.DEEP_MODES[mode] if isinstance(mode, str) else int(mode)
+        if out is None:
+            out = np.empty((max(nrows, 0), max(int(cols), 0)), np.uint16)
+        self._check(self.lib.vfsms_deep_mosaic_rows(self.ctx, len(th), _ptr(th), _ptr(at), int(rows), int(cols), m, int(feather), int(row0), nrows, _ptr(out)))
+        return out
+
+    def deep_mosaic_bands(self, handles, yx, rows, cols, mode="feather", feather=0, band_rows=4096):
+        """the whole mosaic as (row0, band) pairs of at most band_rows rows, one gather launch each"""
+        for r0 in range(0, int(rows), int(band_rows)):
+            yield r0, self.deep_mosaic_rows(handles, yx, rows, cols, mode, feather, r0, min(int(band_rows), int(rows) - r0))
 
     # -- exposure compensation (tests/exposure_ref.py is the specification) -------------------------------------------------
     def overlap_stats_batch(self, jobs, lo, hi):

@@ -3,6 +3,7 @@
 #include "canvas_band.h"
 #include "ingest_fill.h"
 #include "tile_table.h"
+#include "deep_bins.h"
 #include "jpeg_huff_core.h"
 #include "phase_resolve_math.h"
 #include <math.h>
@@ -2809,6 +2810,128 @@ extern "C" int vfsms_focus_scores(vfsms_ctx *ctx, int n, const int64_t *tiles, i
     HIP_TRY(hipMemcpyAsync(S.data(), d_scores, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n; i++) scores[i] = (int64_t)S[i];
+    return VFSMS_OK;
+}
+
+// ---- 16-bit gray tiles (vfsms_deep_*; deep_kernels.hip, specified by tests/deep_ref.py) ----------------------------------------------------
+// The deep tiles a call names: the count, then every handle known, in index order (a handle of another kind is unknown here, as a deep
+// handle is unknown to every entry that takes tiles).  Reads arguments and records only
+static int deep_list(vfsms_ctx *ctx, const char *who, int n, const int64_t *deeps, std::vector<DeepSrc> &out)
+{
+    if (n < 1 || n > VFSMS_DEEP_MAX_TILES || !deeps) { vfsms_set_error("%s: 1..%d deep tiles, got %d", who, VFSMS_DEEP_MAX_TILES, n); return VFSMS_ERR_BAD_ARG; }
+    out.resize(n);
+    for (int i = 0; i < n; i++) {
+        auto it = ctx->deep_tiles.find(deeps[i]);
+        if (it == ctx->deep_tiles.end()) { vfsms_set_error("%s: handle %d is not a deep tile of this context", who, i); return VFSMS_ERR_BAD_ARG; }
+        out[i] = DeepSrc{it->second.pix.as<uint16_t>(), nullptr, it->second.h, it->second.w};
+    }
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_upload(vfsms_ctx *ctx, const uint16_t *img, int h, int w, int stride_bytes, int64_t *deep)
+{
+    CTX_ENTER(ctx);
+    if (!img || !deep || h < 1 || h > VFSMS_DEEP_MAX_SIDE || w < 1 || w > VFSMS_DEEP_MAX_SIDE || stride_bytes < 2 * w) {
+        vfsms_set_error("deep_upload: %d x %d samples, rows %d bytes apart (sides 1..%d, rows at least 2 w bytes apart)", h, w, stride_bytes, VFSMS_DEEP_MAX_SIDE);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    DeepRec R;
+    R.h = h; R.w = w;
+    TRY(R.pix.reserve((size_t)h * w * 2, ctx->stream));
+    if (hipMemcpy2D(R.pix.as<void>(), (size_t)w * 2, img, (size_t)stride_bytes, (size_t)w * 2, h, hipMemcpyHostToDevice) != hipSuccess) {
+        vfsms_set_error("deep_upload: the upload failed"); return VFSMS_ERR_HIP;
+    }
+    *deep = ctx->next_handle++;
+    ctx->deep_tiles.emplace(*deep, std::move(R));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_free(vfsms_ctx *ctx, int64_t deep)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->deep_tiles.find(deep);
+    if (it == ctx->deep_tiles.end()) { vfsms_set_error("deep_free: unknown handle"); return VFSMS_ERR_BAD_ARG; }
+    TRY(it->second.pix.release(ctx->stream));
+    ctx->deep_tiles.erase(it);
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_window(vfsms_ctx *ctx, int n, const int64_t *deeps, int lo_ppm, int hi_ppm, int32_t *window)
+{
+    CTX_ENTER(ctx);
+    std::vector<DeepSrc> T;
+    TRY(deep_list(ctx, "deep_window", n, deeps, T));
+    if (lo_ppm < 0 || lo_ppm > hi_ppm || hi_ppm > 1000000 || !window) {
+        vfsms_set_error("deep_window: ppm %d, %d (0 <= lo_ppm <= hi_ppm <= 1000000)", lo_ppm, hi_ppm);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    unsigned long long N = 0;
+    for (const DeepSrc &t : T) N += (unsigned long long)t.h * t.w;             // at most 2^42: (N - 1) * ppm stays below 2^62
+    TRY(ctx_arena_reserve(ctx, deep_table_bytes(n) + 65536));
+    ctx->pinned_off = 0;
+    int lo = 0, hi = 0;
+    TRY(deep_window_device(ctx, T.data(), n, (N - 1) * (unsigned long long)lo_ppm / 1000000ull, (N - 1) * (unsigned long long)hi_ppm / 1000000ull, &lo, &hi));
+    if (hi == lo) { if (lo < 65535) hi = lo + 1; else lo = hi - 1; }
+    window[0] = lo; window[1] = hi;
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_reduce(vfsms_ctx *ctx, int n, const int64_t *deeps, int lo, int hi, int64_t *tiles_out)
+{
+    CTX_ENTER(ctx);
+    std::vector<DeepSrc> T;
+    TRY(deep_list(ctx, "deep_reduce", n, deeps, T));
+    if (lo < 0 || lo >= hi || hi > 65535 || !tiles_out) { vfsms_set_error("deep_reduce: window %d, %d (0 <= lo < hi <= 65535)", lo, hi); return VFSMS_ERR_BAD_ARG; }
+    TRY(ctx_arena_reserve(ctx, deep_table_bytes(n) + 65536));
+    ctx->pinned_off = 0;
+    int rc = VFSMS_OK, got = 0;
+    for (; got < n && rc == VFSMS_OK; got++) {
+        rc = tile_buffer(ctx, (size_t)T[got].h * T[got].w, &T[got].dst, ctx->stream);
+        if (rc != VFSMS_OK) break;
+    }
+    if (rc == VFSMS_OK) rc = deep_reduce_device(ctx, T.data(), n, lo, hi);
+    if (rc == VFSMS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { vfsms_set_error("deep_reduce: the kernel failed"); rc = VFSMS_ERR_HIP; }
+    if (rc != VFSMS_OK) {                                    // no tile is created: the buffers go back behind a synchronisation
+        hipStreamSynchronize(ctx->stream);
+        for (int i = 0; i < got; i++) (void)tile_pool_return(ctx, T[i].dst, (size_t)T[i].h * T[i].w, false);
+        return rc;
+    }
+    for (int i = 0; i < n; i++) tile_register(ctx, tile_rec(T[i].dst, T[i].h, T[i].w, 1, T[i].w, true), &tiles_out[i]);
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_mosaic_rows(vfsms_ctx *ctx, int n, const int64_t *deeps, const int32_t *yx, int rows, int cols, int mode, int feather,
+                                      int row0, int nrows, uint16_t *out)
+{
+    CTX_ENTER(ctx);
+    std::vector<DeepSrc> T;
+    TRY(deep_list(ctx, "deep_mosaic_rows", n, deeps, T));
+    if (!yx || rows < 1 || cols < 1) { vfsms_set_error("deep_mosaic_rows: a canvas of %d x %d", rows, cols); return VFSMS_ERR_BAD_ARG; }
+    std::vector<DeepRect> at(n);
+    for (int i = 0; i < n; i++) {
+        const long long y = yx[2 * i], x = yx[2 * i + 1];
+        if (y < 0 || x < 0 || y + T[i].h > rows || x + T[i].w > cols) {
+            vfsms_set_error("deep_mosaic_rows: tile %d (%d x %d at %lld, %lld) lies outside the %d x %d canvas", i, T[i].h, T[i].w, y, x, rows, cols);
+            return VFSMS_ERR_BAD_ARG;
+        }
+        at[i] = DeepRect{(int)y, (int)x, T[i].h, T[i].w};
+    }
+    if ((mode != 0 && mode != 1) || feather < 0 || feather > 32767) {
+        vfsms_set_error("deep_mosaic_rows: mode %d / feather %d (0 paste or 1 feather; 0..32767)", mode, feather);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    if (row0 < 0 || nrows < 1 || (long long)row0 + nrows > rows || (long long)nrows * cols > (1ll << 30) || !out) {
+        vfsms_set_error("deep_mosaic_rows: rows %d..%d + %d of %d (inside the canvas, at most 2^30 samples)", row0, row0, nrows, rows);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    DeepBins B;
+    if (!deep_bins_build(at.data(), n, cols, row0, nrows, VFSMS_DEEP_MAX_BIN_ENTRIES, &B)) {
+        vfsms_set_error("deep_mosaic_rows: the band's bin table exceeds %zu entries (use shorter bands)", VFSMS_DEEP_MAX_BIN_ENTRIES);
+        return VFSMS_ERR_CAPACITY;
+    }
+    const size_t bytes = (size_t)nrows * cols * sizeof(uint16_t);
+    TRY(ctx_arena_reserve(ctx, bytes + deep_mosaic_table_bytes(n, B) + 65536));
+    ctx->pinned_off = 0;
+    uint16_t *d_out = (uint16_t *)ctx_arena_alloc(ctx, bytes);
+    if (!d_out) { vfsms_set_error("arena exhausted (deep_mosaic_rows)"); return VFSMS_ERR_CAPACITY; }
+    TRY(deep_mosaic_device(ctx, T.data(), at.data(), n, B, cols, row0, nrows, mode, feather, d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
 }
 

@@ -215,6 +215,7 @@ struct PhasePeak { double v; long long idx; };                      // a peak of
 struct PhasePeakSink { int K; PhasePeak *peaks; };
 struct ProfRec { int id; hipEvent_t a, b; };
 struct ShadeRec { int h, w, ch; DevBuf gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
+struct DeepRec { DevBuf pix; int h = 0, w = 0; };               // a 16-bit gray tile (deep_kernels.hip): h x w uint16 samples, dense, in an allocation of its own; a record and a handle kind of their own, so no entry that takes a TileRec can be handed one
 struct SiftChunk { DevBuf mem; size_t off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
 
 struct vfsms_ctx {
@@ -250,6 +251,7 @@ struct vfsms_ctx {
     DevBuf seam_scratch;                                           // energy, predecessor, seam and label planes of the optimal-seam fuse (seam_kernels.hip): grown to the largest seam, freed with the context
     DevBuf shade_scratch;                                          // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
     std::unordered_map<int64_t, ShadeRec> shade_fields;
+    std::unordered_map<int64_t, DeepRec> deep_tiles;               // the 16-bit gray tiles (vfsms_deep_*): handles from next_handle like every other kind
     DevBuf lens_scratch;                                           // the copy a tile is resampled from (lens_kernels.hip): grown to the largest tile, freed with the context
     DevBuf sift_scratch;                                           // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     DevBuf sift_kp;                                                // SIFT candidates, keypoints and descriptors, likewise
@@ -450,6 +452,21 @@ int focus_select_device(vfsms_ctx *ctx, const FocusPlane *d_tab, int n, int h, i
                         uint32_t *d_partials);
 int focus_compose_device(vfsms_ctx *ctx, const FocusPlane *d_tab, const uint8_t *d_index, int h, int w, int ch, int median, int const_d,
                          uint8_t *d_out, int out_stride, uint8_t *d_index_out);
+// deep_kernels.hip: 16-bit gray tiles (tests/deep_ref.py).  DeepSrc: a deep tile as the launchers take it (dense h x w samples at src;
+// dst: the dense h x w bytes of its reduced view, reduce only).  The tables of a call go through the arena: deep_table_bytes /
+// deep_mosaic_table_bytes say how much.  DeepRect, DeepBins: deep_bins.h
+#define VFSMS_DEEP_MAX_TILES 4096
+#define VFSMS_DEEP_MAX_SIDE 32768
+#define VFSMS_DEEP_MAX_BIN_ENTRIES ((size_t)1 << 26)
+struct DeepSrc { const uint16_t *src; uint8_t *dst; int h, w; };
+struct DeepRect;
+struct DeepBins;
+size_t deep_table_bytes(int n);
+int deep_window_device(vfsms_ctx *ctx, const DeepSrc *tiles, int n, unsigned long long k_lo, unsigned long long k_hi, int *lo, int *hi);
+int deep_reduce_device(vfsms_ctx *ctx, const DeepSrc *tiles, int n, int lo, int hi);
+size_t deep_mosaic_table_bytes(int n, const DeepBins &B);
+int deep_mosaic_device(vfsms_ctx *ctx, const DeepSrc *tiles, const DeepRect *at, int n, const DeepBins &B, int cols, int row0, int nrows, int mode,
+                       int feather, uint16_t *d_out);
 // lens_kernels.hip: Method.lensCorrection (tests/lens_ref.py).  A block job: two whole tiles of ONE shape and channel count (pointers, row
 // strides in bytes) and the offset (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)); lens_lattice: its block lattice.  A tile
 // to resample: a TileView (tile_table.h).  A centre coordinate below 0 stands for the tile's own middle

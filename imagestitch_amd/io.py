@@ -56,7 +56,9 @@ class NpyBandWriter:
             d = os.path.dirname(self.path)
             if d and not os.path.exists(d):
                 os.makedirs(d)
-            self._mm = np.lib.format.open_memmap(self.path, mode="w+", dtype=np.uint8, shape=tuple(full_shape))
+            # the sample width is the first band's: uint8, or uint16 (the bands of Engine.deep_mosaic_bands)
+            dtype = np.uint16 if np.asarray(band).dtype == np.uint16 else np.uint8
+            self._mm = np.lib.format.open_memmap(self.path, mode="w+", dtype=dtype, shape=tuple(full_shape))
         self._mm[row0:row0 + band.shape[0]] = band
         if row0 + band.shape[0] >= full_shape[0]:
             self._mm.flush()
@@ -317,19 +319,23 @@ class DevicePngFile:
 
 class TiffBandWriter:
     """A `Stitcher.mosaicSink` for uncompressed baseline TIFF (BigTIFF beyond 4 GB): one strip per band, the directory written behind the
-    last band.  R G B (or gray) 8-bit samples."""
+    last band.  R G B (or gray) 8-bit samples, or 16-bit little-endian ones: the sample width is the first band's dtype (uint16: a mosaic
+    of Engine.deep_mosaic_bands; anything else is written as 8-bit)."""
 
     transient_bands = True      # done with a band when the call returns
 
     def __init__(self, path, force_big=False):
-        self.path, self._f, self._strips = path, None, []
+        self.path, self._f, self._strips, self._bits = path, None, [], 8
         self.force_big = force_big                               # BigTIFF whatever the size (tests: the > 4 GB layout on a small image)
 
     def __call__(self, row0, band, full_shape):
         import struct
         rows, cols = full_shape[0], full_shape[1]
         ch = full_shape[2] if len(full_shape) == 3 else 1
-        big = self.force_big or rows * cols * ch + (1 << 20) >= (1 << 32)
+        if self._f is None:
+            self._bits = 16 if np.asarray(band).dtype == np.uint16 else 8
+        bits = self._bits
+        big = self.force_big or rows * cols * ch * (bits // 8) + (1 << 20) >= (1 << 32)
         if self._f is None:
             d = os.path.dirname(self.path)
             if d and not os.path.exists(d):
@@ -340,7 +346,9 @@ class TiffBandWriter:
         band = np.asarray(band)
         if band.ndim == 3:
             band = band[:, :, ::-1]
-        self._strips.append((self._f.tell(), band.size))
+        if bits == 16:
+            band = band.astype("<u2", copy=False)
+        self._strips.append((self._f.tell(), band.size * (bits // 8)))       # StripByteCounts are bytes
         self._f.write(np.ascontiguousarray(band).tobytes())
         if row0 + band.shape[0] < rows:
             return
@@ -352,12 +360,12 @@ class TiffBandWriter:
         cnt_pos = f.tell(); f.write(struct.pack(fmt_off, *[c for _o, c in self._strips]))
         # BitsPerSample 8, 8, 8: three SHORTs are 6 bytes -- more than classic TIFF's 4-byte value field (stored behind the strips, the field
         # holds the offset), but they FIT BigTIFF's 8-byte field and must then sit in it (a reader takes the field as the values)
-        bps = 8 | 8 << 16 | 8 << 32
+        bps = bits | bits << 16 | bits << 32
         if ch == 3 and not big:
-            bps = f.tell(); f.write(struct.pack("<3H", 8, 8, 8)); f.write(b"\0\0")
+            bps = f.tell(); f.write(struct.pack("<3H", bits, bits, bits)); f.write(b"\0\0")
         ifd = f.tell()
         ltype = 16 if big else 4                                 # LONG8 / LONG
-        tags = [(256, ltype, 1, cols), (257, ltype, 1, rows), (258, 3, ch, bps if ch == 3 else 8), (259, 3, 1, 1),
+        tags = [(256, ltype, 1, cols), (257, ltype, 1, rows), (258, 3, ch, bps if ch == 3 else bits), (259, 3, 1, 1),
                 (262, 3, 1, 2 if ch == 3 else 1), (273, ltype, n, off_pos if n > 1 else self._strips[0][0]), (277, 3, 1, ch),
                 (278, ltype, 1, self._band_rows), (279, ltype, n, cnt_pos if n > 1 else self._strips[0][1])]
         if big:

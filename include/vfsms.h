@@ -718,6 +718,37 @@ int vfsms_focus_stack(vfsms_ctx *ctx, int n, const int64_t *planes, int mode, in
 /* scores[i] = the sum of M over tile i (tests/focus_ref.py: scores): n (1..4096) resident tiles of any shapes, gray or B G R     */
 int vfsms_focus_scores(vfsms_ctx *ctx, int n, const int64_t *tiles, int64_t *scores);
 
+/* ---- 16-bit gray tiles.  No reference counterpart: the arithmetic, all integer, is this library's own
+ * specification, tests/deep_ref.py, and every stage equals it exactly.  A deep tile has a handle kind of its own: every vfsms_deep_*
+ * entry refuses any other handle, and every other entry refuses a deep handle, so no 8-bit call can be handed 16-bit memory. -------- */
+/* A deep tile from img: h x w uint16 samples (sides 1..32768), rows stride_bytes apart (at least 2 w; any alignment).  The samples are
+ * on the device when the call returns: the caller's memory is free.  VFSMS_ERR_BAD_ARG, nothing created: a side outside 1..32768, a
+ * stride below 2 w, a null pointer.                                                                                                 */
+int vfsms_deep_upload(vfsms_ctx *ctx, const uint16_t *img, int h, int w, int stride_bytes, int64_t *deep);
+/* releases a deep tile (tests/deep_ref.py has no state to free)                                                                    */
+int vfsms_deep_free(vfsms_ctx *ctx, int64_t deep);
+/* One intensity window for n (1..4096) deep tiles of any shapes: with s = all their samples sorted and N their number, window[0] =
+ * s[(N - 1) * lo_ppm / 1000000] and window[1] = s[(N - 1) * hi_ppm / 1000000], exactly (a two-pass radix select); when the two are
+ * equal, window[1] is one more (window[0] one less at 65535) (tests/deep_ref.py: window).  The tiles are only read.
+ * VFSMS_ERR_BAD_ARG, nothing written: n outside 1..4096, a handle that is no deep tile, not 0 <= lo_ppm <= hi_ppm <= 1000000.       */
+int vfsms_deep_window(vfsms_ctx *ctx, int n, const int64_t *deeps, int lo_ppm, int hi_ppm, int32_t *window);
+/* The 8-bit registration views of n (1..4096) deep tiles: out = ((min(max(v, lo), hi) - lo) * 255 + D / 2) / D, D = hi - lo
+ * (tests/deep_ref.py: reduce).  tiles_out[i]: a NEW ordinary resident gray tile of tile i's shape, freed with vfsms_tile_free, as
+ * vfsms_focus_stack returns its out_tile.  VFSMS_ERR_BAD_ARG, nothing written: n outside 1..4096, a handle that is no deep tile, not
+ * 0 <= lo < hi <= 65535.  On any error no tile is created.                                                                        */
+int vfsms_deep_reduce(vfsms_ctx *ctx, int n, const int64_t *deeps, int lo, int hi, int64_t *tiles_out);
+/* Rows [row0, row0 + nrows) of the rows x cols uint16 mosaic GATHERED from n (1..4096) deep tiles, tile i's top-left corner at
+ * (yx[2 i], yx[2 i + 1]), into out, dense [nrows][cols] on the host (tests/deep_ref.py: mosaic).  A pixel no tile covers is 0.  mode 0
+ * (paste): the sample of the covering tile of the largest index; mode 1 (feather): (sum w p + (sum w) / 2) / sum w over the covering
+ * tiles with w = min(r + 1, h - r, c + 1, w - c) at the tile's own (r, c), cut at `feather` when that is positive.  The result does not
+ * depend on the order of the tiles in mode 1.  Stateless: any band on demand, no canvas exists; the tiles are only read, may differ in
+ * shape, lie inside each other, share a position, and a handle may be named more than once.  VFSMS_ERR_BAD_ARG, nothing written, the
+ * first of these in this order: n outside 1..4096, a handle that is no deep tile, a tile outside the canvas, a mode other than 0 or 1,
+ * feather outside 0..32767, a band outside the canvas or of more than 2^30 samples.  VFSMS_ERR_CAPACITY: the band meets more than
+ * 2^26 (tile, 32 x 256 block) pairs; shorter bands do not.                                                                          */
+int vfsms_deep_mosaic_rows(vfsms_ctx *ctx, int n, const int64_t *deeps, const int32_t *yx, int rows, int cols, int mode, int feather,
+                           int row0, int nrows, uint16_t *out);
+
 /* ---- per-tile exposure compensation (Method.exposureCompensation).  No reference counterpart: the specification is
  * tests/exposure_ref.py; the sums and the corrected bytes are integers and equal it exactly. ------------------------------------ */
 /* The overlap statistic of n pairs of resident tiles (gray or interleaved colour, both tiles of a job of one channel count, any
