@@ -13,7 +13,8 @@ from .fusion import ImageFusion  # noqa: F401
 from .stitcher import Stitcher, ImageFeature, NpyBandWriter, PngBandWriter, TiffBandWriter, JpegBandWriter, PyramidTiffBandWriter, DeviceJpegFile, DevicePngFile, band_writer_for  # noqa: F401
 from .focus import fuse_stack, fuse_dataset  # noqa: F401
 from .lens import undistort  # noqa: F401
+from .deep import flatfield16  # noqa: F401
 
 __all__ = ["Stitcher", "ImageFusion", "Method", "ImageFeature", "Engine", "VfsmsError", "default_engine",
            "load_library", "roi_rect", "NpyBandWriter", "PngBandWriter", "TiffBandWriter", "JpegBandWriter", "PyramidTiffBandWriter", "DeviceJpegFile", "DevicePngFile", "band_writer_for",
-           "fuse_stack", "fuse_dataset", "undistort"]
+           "fuse_stack", "fuse_dataset", "undistort", "flatfield16"]

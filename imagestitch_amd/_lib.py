@@ -215,6 +215,12 @@ _SIGNATURES = {
     "vfsms_deep_window": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_deep_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_deep_mosaic_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfsms_deep_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]),
+    "vfsms_deep_shading_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_deep_shading_from_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "vfsms_deep_shading_download": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "vfsms_deep_shading_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "vfsms_deep_shading_free": (C.c_int, [C.c_void_p, C.c_int64]),
     "vfsms_overlap_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfsms_exposure_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vfsms_block_ncc_batch": (C.c_int, [C.c_void_p, C.POINTER(NccJob), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1243,6 +1249,63 @@ class Engine:
         """the whole mosaic as (row0, band) pairs of at most band_rows rows, one gather launch each"""
         for r0 in range(0, int(rows), int(band_rows)):
             yield r0, self.deep_mosaic_rows(handles, yx, rows, cols, mode, feather, r0, min(int(band_rows), int(rows) - r0))
+
+    def deep_download(self, handle, out=None):
+        """vfsms_deep_download: the samples of a deep tile -> uint16 (h, w); `out`: a uint16 array or view of that shape to fill (rows may
+        be strided, samples adjacent)"""
+        shape = self.__dict__.get("_shapes", {}).get(("deep", handle))
+        if shape is None:
+            raise ValueError("deep_download: not a deep tile of this engine's deep_upload")
+        if out is None:
+            out = np.empty(shape, np.uint16)
+        if out.dtype != np.uint16 or out.shape != shape or (shape[1] > 1 and out.strides[1] != 2) or out.strides[0] < 2 * shape[1]:
+            raise ValueError("deep_download: out must be a uint16 %s array with adjacent samples" % (shape,))
+        self._check(self.lib.vfsms_deep_download(self.ctx, C.c_int64(handle), _ptr(out), out.strides[0]))
+        return out
+
+    # -- shading correction of 16-bit tiles (tests/deep_shading_ref.py is the specification) ---------------------------------------
+    def deep_shading_estimate(self, handles, percentile=50, radius=32, pedestal=0):
+        """A shading field from deep tiles of one shape (vfsms_deep_shading_estimate): the `percentile` order statistic over the stack, less
+        the camera's dark level `pedestal`, smoothed by two box passes of `radius`, as a Q12 gain -> deep field handle
+        (deep_shading_apply, deep_shading_download, deep_shading_free).  A handle kind of its own: the shading_* methods refuse it."""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        f = C.c_int64()
+        self._check(self.lib.vfsms_deep_shading_estimate(self.ctx, len(th), _ptr(th), int(percentile), int(radius), int(pedestal), C.byref(f)))
+        shapes = self.__dict__.setdefault("_shapes", {})
+        shapes[("deep_field", f.value)] = shapes.get(("deep", int(th[0])))
+        return f.value
+
+    def deep_shading_from_gain(self, gain, pedestal=0):
+        """A deep field from a gain measured elsewhere (a blank slide): uint16 Q12 of shape (h, w), and the pedestal of the tiles it corrects."""
+        gain = np.asarray(gain)
+        if gain.dtype != np.uint16 or gain.ndim != 2:
+            raise ValueError("deep_shading_from_gain takes a uint16 (h, w) array, got %s %s" % (gain.dtype, gain.shape))
+        gain = np.ascontiguousarray(gain)
+        f = C.c_int64()
+        self._check(self.lib.vfsms_deep_shading_from_gain(self.ctx, _ptr(gain), gain.shape[0], gain.shape[1], int(pedestal), C.byref(f)))
+        self.__dict__.setdefault("_shapes", {})[("deep_field", f.value)] = gain.shape
+        return f.value
+
+    def deep_shading_download(self, field):
+        """-> (gain uint16 Q12, smoothed field uint16, profile uint16, pedestal), the planes of the tile shape; smooth and profile are zeros
+        for a field from deep_shading_from_gain."""
+        shape = self.__dict__.get("_shapes", {}).get(("deep_field", field))
+        if shape is None:
+            raise ValueError("deep_shading_download: not a field of this engine's deep_shading_estimate / deep_shading_from_gain")
+        gain, smooth, prof = (np.empty(shape, np.uint16) for _ in range(3))
+        ped = C.c_int32()
+        self._check(self.lib.vfsms_deep_shading_download(self.ctx, C.c_int64(field), _ptr(gain), _ptr(smooth), _ptr(prof), C.byref(ped)))
+        return gain, smooth, prof, int(ped.value)
+
+    def deep_shading_apply(self, field, handles):
+        """the deep tiles corrected in place by the field's gain above its pedestal (vfsms_deep_shading_apply); tiles of the field's shape,
+        each named once"""
+        th = np.ascontiguousarray(handles, np.int64).reshape(-1)
+        self._check(self.lib.vfsms_deep_shading_apply(self.ctx, C.c_int64(field), len(th), _ptr(th)))
+
+    def deep_shading_free(self, field):
+        self._check(self.lib.vfsms_deep_shading_free(self.ctx, C.c_int64(field)))
+        self.__dict__.get("_shapes", {}).pop(("deep_field", field), None)
 
     # -- exposure compensation (tests/exposure_ref.py is the specification) -------------------------------------------------
     def overlap_stats_batch(self, jobs, lo, hi):

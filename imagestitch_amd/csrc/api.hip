@@ -2934,6 +2934,117 @@ extern "C" int vfsms_deep_mosaic_rows(vfsms_ctx *ctx, int n, const int64_t *deep
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return VFSMS_OK;
 }
+extern "C" int vfsms_deep_download(vfsms_ctx *ctx, int64_t deep, uint16_t *out, int stride_bytes)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->deep_tiles.find(deep);
+    if (it == ctx->deep_tiles.end()) { vfsms_set_error("deep_download: the handle is not a deep tile of this context"); return VFSMS_ERR_BAD_ARG; }
+    const DeepRec &R = it->second;
+    if (!out || stride_bytes < 2 * R.w) { vfsms_set_error("deep_download: rows %d bytes apart for %d samples (at least 2 w), or a null pointer", stride_bytes, R.w); return VFSMS_ERR_BAD_ARG; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (hipMemcpy2D(out, (size_t)stride_bytes, R.pix.as<void>(), (size_t)R.w * 2, (size_t)R.w * 2, R.h, hipMemcpyDeviceToHost) != hipSuccess) {
+        vfsms_set_error("deep_download: the download failed"); return VFSMS_ERR_HIP;
+    }
+    return VFSMS_OK;
+}
+
+// ---- shading correction of deep tiles (deep_shading_kernels.hip, specified by tests/deep_shading_ref.py) ------------------------------------
+static int deep_field_new(vfsms_ctx *ctx, int h, int w, int pedestal, bool estimated, DeepShadeRec *F)
+{
+    const size_t P = (size_t)h * w, Pa = (P + 127) & ~(size_t)127;            // the three uint16 planes stay 256-byte aligned
+    F->h = h; F->w = w; F->pedestal = pedestal; F->estimated = estimated;
+    TRY(F->gain.reserve((estimated ? 3 : 1) * Pa * sizeof(uint16_t), ctx->stream));
+    if (estimated) { F->smooth = F->gain.as<uint16_t>() + Pa; F->prof = F->smooth + Pa; }
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *deeps, int percentile, int radius, int pedestal, int64_t *field)
+{
+    CTX_ENTER(ctx);
+    std::vector<DeepSrc> T;
+    TRY(deep_list(ctx, "deep_shading_estimate", n, deeps, T));
+    for (int i = 1; i < n; i++)
+        if (T[i].h != T[0].h || T[i].w != T[0].w) {
+            vfsms_set_error("deep_shading_estimate: tile %d is %d x %d, tile 0 is %d x %d (one shape)", i, T[i].h, T[i].w, T[0].h, T[0].w);
+            return VFSMS_ERR_BAD_ARG;
+        }
+    if (percentile < 0 || percentile > 100 || radius < 1 || radius > VFSMS_SHADE_MAX_RADIUS || pedestal < 0 || pedestal > 65535 || !field) {
+        vfsms_set_error("deep_shading_estimate: percentile %d / radius %d / pedestal %d (0..100; 1..%d; 0..65535), or a null pointer", percentile, radius, pedestal, VFSMS_SHADE_MAX_RADIUS);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    TRY(shade_plane_fits("deep_shading_estimate", T[0].h, (size_t)T[0].w));
+    TRY(ctx_arena_reserve(ctx, sizeof(void *) * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    DeepShadeRec F;
+    TRY(deep_field_new(ctx, T[0].h, T[0].w, pedestal, true, &F));
+    int rc = deep_shade_estimate_device(ctx, T.data(), n, F.h, F.w, percentile, radius, pedestal, F.gain.as<uint16_t>(), F.smooth, F.prof);
+    if (rc == VFSMS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { vfsms_set_error("deep_shading_estimate: the kernels failed"); rc = VFSMS_ERR_HIP; }
+    if (rc != VFSMS_OK) { hipStreamSynchronize(ctx->stream); return rc; }      // (the field goes with F; nothing enqueued may still write it)
+    *field = ctx->next_handle++;
+    ctx->deep_fields.emplace(*field, std::move(F));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int h, int w, int pedestal, int64_t *field)
+{
+    CTX_ENTER(ctx);
+    if (h < 1 || h > VFSMS_DEEP_MAX_SIDE || w < 1 || w > VFSMS_DEEP_MAX_SIDE || pedestal < 0 || pedestal > 65535 || !gain || !field) {
+        vfsms_set_error("deep_shading_from_gain: %d x %d samples / pedestal %d (sides 1..%d; 0..65535), or a null pointer", h, w, pedestal, VFSMS_DEEP_MAX_SIDE);
+        return VFSMS_ERR_BAD_ARG;
+    }
+    DeepShadeRec F;
+    TRY(deep_field_new(ctx, h, w, pedestal, false, &F));
+    if (hipMemcpy(F.gain.as<void>(), gain, sizeof(uint16_t) * (size_t)h * w, hipMemcpyHostToDevice) != hipSuccess) {
+        vfsms_set_error("deep_shading_from_gain: the upload failed"); return VFSMS_ERR_HIP;
+    }
+    *field = ctx->next_handle++;
+    ctx->deep_fields.emplace(*field, std::move(F));
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *gain, uint16_t *smooth, uint16_t *profile, int32_t *pedestal)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->deep_fields.find(field);
+    if (it == ctx->deep_fields.end()) { vfsms_set_error("deep_shading_download: the handle is not a deep shading field of this context"); return VFSMS_ERR_BAD_ARG; }
+    if (!gain) { vfsms_set_error("deep_shading_download: a null pointer"); return VFSMS_ERR_BAD_ARG; }
+    const DeepShadeRec &F = it->second;
+    const size_t bytes = sizeof(uint16_t) * (size_t)F.h * F.w;
+    HIP_TRY(hipMemcpyAsync(gain, F.gain.as<uint16_t>(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (smooth) { if (F.estimated) HIP_TRY(hipMemcpyAsync(smooth, F.smooth, bytes, hipMemcpyDeviceToHost, ctx->stream)); else memset(smooth, 0, bytes); }
+    if (profile) { if (F.estimated) HIP_TRY(hipMemcpyAsync(profile, F.prof, bytes, hipMemcpyDeviceToHost, ctx->stream)); else memset(profile, 0, bytes); }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (pedestal) *pedestal = F.pedestal;
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *deeps)
+{
+    CTX_ENTER(ctx);
+    std::vector<DeepSrc> T;
+    TRY(deep_list(ctx, "deep_shading_apply", n, deeps, T));
+    auto it = ctx->deep_fields.find(field);
+    if (it == ctx->deep_fields.end()) { vfsms_set_error("deep_shading_apply: the handle is not a deep shading field of this context"); return VFSMS_ERR_BAD_ARG; }
+    const DeepShadeRec &F = it->second;
+    for (int i = 0; i < n; i++)
+        if (T[i].h != F.h || T[i].w != F.w) {
+            vfsms_set_error("deep_shading_apply: tile %d is %d x %d, the field is %d x %d", i, T[i].h, T[i].w, F.h, F.w);
+            return VFSMS_ERR_BAD_ARG;
+        }
+    std::vector<int64_t> seen(deeps, deeps + n);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { vfsms_set_error("deep_shading_apply: a tile is named twice (it would be corrected twice)"); return VFSMS_ERR_BAD_ARG; }
+    TRY(ctx_arena_reserve(ctx, sizeof(void *) * (size_t)n + 65536));
+    ctx->pinned_off = 0;
+    TRY(deep_shade_apply_device(ctx, T.data(), n, F.h, F.w, F.pedestal, F.gain.as<uint16_t>()));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // the pointer table went through the pinned staging buffer: synchronous like every call that uses it
+    return VFSMS_OK;
+}
+extern "C" int vfsms_deep_shading_free(vfsms_ctx *ctx, int64_t field)
+{
+    CTX_ENTER(ctx);
+    auto it = ctx->deep_fields.find(field);
+    if (it == ctx->deep_fields.end()) { vfsms_set_error("deep_shading_free: the handle is not a deep shading field of this context"); return VFSMS_ERR_BAD_ARG; }
+    TRY(it->second.gain.release(ctx->stream));
+    ctx->deep_fields.erase(it);
+    return VFSMS_OK;
+}
 
 // ---- exposure compensation (Method.exposureCompensation; exposure_kernels.hip, specified by tests/exposure_ref.py) -----------------------
 // vfsms_overlap_stats_batch: every launch of the batch is enqueued before the one synchronisation that brings the sums back

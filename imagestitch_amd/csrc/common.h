@@ -216,6 +216,7 @@ struct PhasePeakSink { int K; PhasePeak *peaks; };
 struct ProfRec { int id; hipEvent_t a, b; };
 struct ShadeRec { int h, w, ch; DevBuf gain; uint16_t *q8; uint8_t *prof; bool estimated; };   // a shading field (shading_kernels.hip): one allocation behind `gain`; q8 / prof hold nothing for an uploaded gain
 struct DeepRec { DevBuf pix; int h = 0, w = 0; };               // a 16-bit gray tile (deep_kernels.hip): h x w uint16 samples, dense, in an allocation of its own; a record and a handle kind of their own, so no entry that takes a TileRec can be handed one
+struct DeepShadeRec { int h = 0, w = 0, pedestal = 0; DevBuf gain; uint16_t *smooth = nullptr, *prof = nullptr; bool estimated = false; };   // a shading field for deep tiles (deep_shading_kernels.hip): one allocation behind `gain`, uint16 planes; smooth / prof hold nothing for an uploaded gain; a record and a handle kind of their own, so no vfsms_shading_* entry can be handed one
 struct SiftChunk { DevBuf mem; size_t off; };                   // one allocation of the SIFT batch's pool (sift_pool_alloc)
 
 struct vfsms_ctx {
@@ -252,6 +253,7 @@ struct vfsms_ctx {
     DevBuf shade_scratch;                                          // uint32 row sums + channel sums of the shading estimate (shading_kernels.hip): grown to the largest tile, freed with the context
     std::unordered_map<int64_t, ShadeRec> shade_fields;
     std::unordered_map<int64_t, DeepRec> deep_tiles;               // the 16-bit gray tiles (vfsms_deep_*): handles from next_handle like every other kind
+    std::unordered_map<int64_t, DeepShadeRec> deep_fields;         // the shading fields of deep tiles (vfsms_deep_shading_*)
     DevBuf lens_scratch;                                           // the copy a tile is resampled from (lens_kernels.hip): grown to the largest tile, freed with the context
     DevBuf sift_scratch;                                           // SIFT pyramid + row counts (sift_kernels.hip): grown to the largest image, freed with the context
     DevBuf sift_kp;                                                // SIFT candidates, keypoints and descriptors, likewise
@@ -431,6 +433,9 @@ int seam_fuse_i64(vfsms_ctx *ctx, const long long *dA, const long long *dB, int 
 int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, int percentile, int radius,
                           uint16_t *gain, uint16_t *q8, uint8_t *prof);
 int shade_apply_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, const uint16_t *gain);
+// the ONE box / level / gain sequence, behind both profiles: q (h rows of w * ch uint16) smoothed in place, its gain; shade_plane_fits first
+int shade_plane_fits(const char *who, int h, size_t row_samples);
+int shade_field_device(vfsms_ctx *ctx, uint16_t *q, int h, int w, int ch, int radius, uint16_t *gain);
 // exposure_kernels.hip: Method.exposureCompensation.  A pair: two whole tiles (pointers, row strides in bytes, rows, row lengths in
 // BYTES = w * ch) of one channel count and the offset in pixels (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)).  ExpJob is
 // what the kernel reads: the rectangle of B that has a partner in A, cut on the host in 64 bits, everything in bytes
@@ -467,6 +472,11 @@ int deep_reduce_device(vfsms_ctx *ctx, const DeepSrc *tiles, int n, int lo, int 
 size_t deep_mosaic_table_bytes(int n, const DeepBins &B);
 int deep_mosaic_device(vfsms_ctx *ctx, const DeepSrc *tiles, const DeepRect *at, int n, const DeepBins &B, int cols, int row0, int nrows, int mode,
                        int feather, uint16_t *d_out);
+// deep_shading_kernels.hip: flat-field correction of deep tiles (tests/deep_shading_ref.py).  The tiles of a call are of ONE shape; their
+// pointer table goes through the arena (8 bytes a tile).  prof, field, gain: dense h x w uint16 planes, 256-byte aligned
+int deep_shade_estimate_device(vfsms_ctx *ctx, const DeepSrc *tiles, int n, int h, int w, int percentile, int radius, int pedestal,
+                               uint16_t *gain, uint16_t *field, uint16_t *prof);
+int deep_shade_apply_device(vfsms_ctx *ctx, const DeepSrc *tiles, int n, int h, int w, int pedestal, const uint16_t *gain);
 // lens_kernels.hip: Method.lensCorrection (tests/lens_ref.py).  A block job: two whole tiles of ONE shape and channel count (pointers, row
 // strides in bytes) and the offset (tile B's pixel (r, c) meets tile A's pixel (r + dx, c + dy)); lens_lattice: its block lattice.  A tile
 // to resample: a TileView (tile_table.h).  A centre coordinate below 0 stands for the tile's own middle

@@ -17,6 +17,7 @@
 //   k_shade_box_h   row sums of 2R + 1 clamped neighbours from an LDS copy of the row segment -> uint32
 //   k_shade_box_v   running column sums over bands of SHADE_BAND rows, rounding division -> uint16
 //   k_shade_level   per-channel 64-bit sums (LDS atomics per workgroup, one vector atomic per workgroup and channel), k_shade_gain the division
+//                   (box passes, level and gain are shade_field_device: the deep path's 16-bit field, deep_shading_kernels.hip, goes through it too)
 //   k_shade_apply   grid over 16-byte blocks of a tile, inner loop over the tiles: a gain vector is loaded once and used N times
 #include "common.h"
 #include "tile_table.h"
@@ -77,8 +78,9 @@ __global__ __launch_bounds__(256) void k_shade_q8(const uint8_t *prof, uint16_t 
 }
 
 // ---- box passes ------------------------------------------------------------------------------------------------------------------------------
-// uint32 is exact: a row sum is at most 255 * 65280, a window sum plus area / 2 at most 255^2 * 65280 + 32512 = 4 244 864 512 < 2^32
-// (R <= 127, Q <= 255 << 8; a rounded mean never exceeds its inputs' maximum, so the second pass has the same bound)
+// The plane is any uint16: the Q8 profile of the 8-bit path (at most 255 << 8) or the 16-bit field of the deep path (ch = 1, at most 65535).
+// uint32 is exact: a row sum is at most 255 * 65535, a window sum plus area / 2 at most 255^2 * 65535 + 32512 = 4 261 445 887 < 2^32
+// (R <= 127; a rounded mean never exceeds its inputs' maximum, so the second pass has the same bound)
 __global__ __launch_bounds__(256) void k_shade_box_h(const uint16_t *q, uint32_t *rows, int w, int ch, int R)
 {
     __shared__ uint16_t seg[SHADE_SEG + 2 * 127 * 4];
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(256) void k_shade_gain(const uint16_t *q, const uin
 {
     const unsigned e = blockIdx.x * 256u + threadIdx.x;
     if (e >= total) return;
-    const uint32_t v = q[e], m = mean[e % ch];               // m * 4096 + v / 2 <= 65280 * 4096 + 32640 < 2^32
+    const uint32_t v = q[e], m = mean[e % ch];               // m * 4096 + v / 2 <= 65535 * 4096 + 32767 < 2^32
     gain[e] = v ? (uint16_t)min(65535u, (m * 4096u + v / 2) / v) : (uint16_t)4096;
 }
 
@@ -185,19 +187,44 @@ static int shade_table(vfsms_ctx *ctx, const TileView *tiles, int n, int wb, siz
     return ctx_upload_small(ctx, T.data(), sizeof(ShadeTile) * n, (void **)d_tiles);
 }
 
-// profile, smoothed field and gain of n tiles (h rows of w * ch bytes each) into the three planes of a field
-int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, int percentile, int radius,
-                          uint16_t *gain, uint16_t *q8, uint8_t *prof)
+// What follows a profile, for the 8-bit and the deep path alike: the uint16 plane q (h rows of w * ch samples) smoothed in place by two
+// box passes, its channel levels, and the gain plane.  The caller has checked the plane's size (shade_plane_fits)
+int shade_field_device(vfsms_ctx *ctx, uint16_t *q, int h, int w, int ch, int radius, uint16_t *gain)
 {
     const int wb = w * ch;
     const size_t total64 = (size_t)h * wb;
-    if (total64 > 0x7fffffffu || h > 65535) { vfsms_set_error("shading_estimate: tiles of more than 2^31 - 1 bytes or 65535 rows are not supported"); return VFSMS_ERR_UNSUPPORTED; }
-    const unsigned total = (unsigned)total64;
+    const unsigned total = (unsigned)total64, eb = (total + 255) / 256;
     // scratch: the uint32 row sums, then 4 channel sums and 4 channel means
     TRY(ctx->shade_scratch.reserve(total64 * 4 + 256, ctx->stream));
     uint32_t *rows = ctx->shade_scratch.as<uint32_t>();
     unsigned long long *sums = (unsigned long long *)(ctx->shade_scratch.as<char>() + ((total64 * 4 + 63) & ~(size_t)63));
     uint32_t *mean = (uint32_t *)(sums + 4);
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(k_shade_box_h, dim3((wb + SHADE_SEG - 1) / SHADE_SEG, h), dim3(256), 0, ctx->stream, q, rows, w, ch, radius);
+        hipLaunchKernelGGL(k_shade_box_v, dim3((wb + 255) / 256, (h + SHADE_BAND - 1) / SHADE_BAND), dim3(256), 0, ctx->stream, rows, q, h, wb, radius);
+    }
+    HIP_TRY(hipMemsetAsync(sums, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_shade_level, dim3(SHADE_LEVEL_BLOCKS), dim3(256), 0, ctx->stream, q, total, ch, sums);
+    hipLaunchKernelGGL(k_shade_mean, dim3(1), dim3(64), 0, ctx->stream, sums, (unsigned long long)h * w, ch, mean);
+    hipLaunchKernelGGL(k_shade_gain, dim3(eb), dim3(256), 0, ctx->stream, q, mean, total, ch, gain);
+    HIP_TRY(hipGetLastError());
+    return VFSMS_OK;
+}
+// the planes those kernels index with 32 bits and a 16-bit grid row: `who` names the refused call
+int shade_plane_fits(const char *who, int h, size_t row_samples)
+{
+    if ((size_t)h * row_samples <= 0x7fffffffu && h <= 65535) return VFSMS_OK;
+    vfsms_set_error("%s: tiles of more than 2^31 - 1 samples or 65535 rows are not supported", who);
+    return VFSMS_ERR_UNSUPPORTED;
+}
+
+// profile, smoothed field and gain of n tiles (h rows of w * ch bytes each) into the three planes of a field
+int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, int w, int ch, int percentile, int radius,
+                          uint16_t *gain, uint16_t *q8, uint8_t *prof)
+{
+    const int wb = w * ch;
+    TRY(shade_plane_fits("shading_estimate", h, (size_t)wb));
+    const unsigned total = (unsigned)((size_t)h * wb);
     ShadeTile *d_tiles; int dense;
     TRY(shade_table(ctx, tiles, n, wb, 4, &d_tiles, &dense));
     const int k = (int)((long long)(n - 1) * percentile / 100);
@@ -208,18 +235,8 @@ int shade_estimate_device(vfsms_ctx *ctx, const TileView *tiles, int n, int h, i
         hipLaunchKernelGGL(k_shade_select<true>, dim3(sel_blocks), dim3(64), (size_t)n * 256, ctx->stream, d_tiles, n, k, total, wb, dense, prof);
     } else
         hipLaunchKernelGGL(k_shade_select<false>, dim3(sel_blocks), dim3(64), 0, ctx->stream, d_tiles, n, k, total, wb, dense, prof);
-    const unsigned eb = (total + 255) / 256;
-    hipLaunchKernelGGL(k_shade_q8, dim3(eb), dim3(256), 0, ctx->stream, prof, q8, total);
-    for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(k_shade_box_h, dim3((wb + SHADE_SEG - 1) / SHADE_SEG, h), dim3(256), 0, ctx->stream, q8, rows, w, ch, radius);
-        hipLaunchKernelGGL(k_shade_box_v, dim3((wb + 255) / 256, (h + SHADE_BAND - 1) / SHADE_BAND), dim3(256), 0, ctx->stream, rows, q8, h, wb, radius);
-    }
-    HIP_TRY(hipMemsetAsync(sums, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_shade_level, dim3(SHADE_LEVEL_BLOCKS), dim3(256), 0, ctx->stream, q8, total, ch, sums);
-    hipLaunchKernelGGL(k_shade_mean, dim3(1), dim3(64), 0, ctx->stream, sums, (unsigned long long)h * w, ch, mean);
-    hipLaunchKernelGGL(k_shade_gain, dim3(eb), dim3(256), 0, ctx->stream, q8, mean, total, ch, gain);
-    HIP_TRY(hipGetLastError());
-    return VFSMS_OK;
+    hipLaunchKernelGGL(k_shade_q8, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, prof, q8, total);
+    return shade_field_device(ctx, q8, h, w, ch, radius, gain);
 }
 
 // the n tiles corrected in place by a field's gain

@@ -748,6 +748,38 @@ int vfsms_deep_reduce(vfsms_ctx *ctx, int n, const int64_t *deeps, int lo, int h
  * 2^26 (tile, 32 x 256 block) pairs; shorter bands do not.                                                                          */
 int vfsms_deep_mosaic_rows(vfsms_ctx *ctx, int n, const int64_t *deeps, const int32_t *yx, int rows, int cols, int mode, int feather,
                            int row0, int nrows, uint16_t *out);
+/* The samples of a deep tile back on the host: out holds h rows of w uint16, rows stride_bytes apart (at least 2 w; any alignment).
+ * VFSMS_ERR_BAD_ARG, nothing written: a handle that is no deep tile, a null pointer, a stride below 2 w.                             */
+int vfsms_deep_download(vfsms_ctx *ctx, int64_t deep, uint16_t *out, int stride_bytes);
+
+/* ---- flat-field shading correction of deep tiles.  No reference counterpart: the arithmetic, all integer, is this library's own
+ * specification, tests/deep_shading_ref.py, and every stage equals it exactly.  A deep field has a handle kind of its own: every
+ * vfsms_shading_* entry refuses it, and the entries below refuse a field of vfsms_shading_estimate / vfsms_shading_from_gain and
+ * any handle that is no deep tile. ------------------------------------------------------------------------------------------------- */
+/* A deep shading field from n (1..4096) deep tiles of ONE shape: per position the k-th smallest sample over the tiles, k = (n - 1) *
+ * percentile / 100 (percentile 0..100), less the camera's dark level `pedestal` (0..65535) and clamped at 0: F = max(P - pedestal, 0),
+ * uint16 with no Q8 shift; F smoothed by two rounded (2 radius + 1)^2 box passes with replicated borders (radius 1..127); the Q12 gain
+ * min(65535, (mean * 4096 + F / 2) / F), 4096 where F == 0 (tests/deep_shading_ref.py: estimate).  The tiles are only read.
+ * VFSMS_ERR_BAD_ARG, nothing created and nothing written, the first of these in this order: n outside 1..4096, a handle that is no
+ * deep tile of this context, tiles of more than one shape, percentile / radius / pedestal outside their ranges, a null pointer.
+ * VFSMS_ERR_UNSUPPORTED: a plane of more than 2^31 - 1 samples or 65535 rows, as vfsms_shading_estimate.  On any error no field is
+ * created.                                                                                                                          */
+int vfsms_deep_shading_estimate(vfsms_ctx *ctx, int n, const int64_t *deeps, int percentile, int radius, int pedestal, int64_t *field);
+/* a field measured elsewhere (a blank slide): gain is uint16 Q12 [h][w] (sides 1..32768), used as it is, with the pedestal the
+ * corrected tiles carry (tests/deep_shading_ref.py: apply).  VFSMS_ERR_BAD_ARG, nothing created: a side or the pedestal outside its
+ * range, a null pointer.                                                                                                            */
+int vfsms_deep_shading_from_gain(vfsms_ctx *ctx, const uint16_t *gain, int h, int w, int pedestal, int64_t *field);
+/* gain: uint16 [h][w]; smooth (may be NULL): the smoothed field F; profile (may be NULL): the order statistic P, both uint16 [h][w] and
+ * zeros for a field from vfsms_deep_shading_from_gain; pedestal (may be NULL): the field's pedestal (tests/deep_shading_ref.py:
+ * estimate returns the three planes).  VFSMS_ERR_BAD_ARG, nothing written: a handle that is no deep field, a null gain.           */
+int vfsms_deep_shading_download(vfsms_ctx *ctx, int64_t field, uint16_t *gain, uint16_t *smooth, uint16_t *profile, int32_t *pedestal);
+/* In place on n (1..4096) deep tiles of the field's shape, with d the field's pedestal: a sample p <= d is left alone, any other
+ * becomes min(65535, d + (((p - d) * gain + 2048) >> 12)) (tests/deep_shading_ref.py: apply).  VFSMS_ERR_BAD_ARG, nothing written, the
+ * first of these in this order: n outside 1..4096, a handle that is no deep tile of this context, a handle that is no deep field, a
+ * shape other than the field's, a tile named twice in one call (it would be corrected twice).                                       */
+int vfsms_deep_shading_apply(vfsms_ctx *ctx, int64_t field, int n, const int64_t *deeps);
+/* releases a field of vfsms_deep_shading_estimate / vfsms_deep_shading_from_gain (tests/deep_shading_ref.py has no state to free)   */
+int vfsms_deep_shading_free(vfsms_ctx *ctx, int64_t field);
 
 /* ---- per-tile exposure compensation (Method.exposureCompensation).  No reference counterpart: the specification is
  * tests/exposure_ref.py; the sums and the corrected bytes are integers and equal it exactly. ------------------------------------ */
