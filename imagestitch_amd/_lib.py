@@ -18,7 +18,11 @@ ATTEMPT_INTS = 8
 
 
 class VfsmsError(RuntimeError):
-    pass
+    """An error the library reported.  `code` is its return code (VFSMS_ERR_*; None when the error did not come from a library call)."""
+
+    def __init__(self, message="", code=None):
+        super().__init__(message)
+        self.code = code
 
 
 class SurfParams(C.Structure):
@@ -291,7 +295,7 @@ class Engine:
         if rc != VFSMS_OK:
             buf = C.create_string_buffer(512)
             self.lib.vfsms_last_error(buf, 512)
-            raise VfsmsError("libvfsms error %d: %s" % (rc, buf.value.decode(errors="replace")))
+            raise VfsmsError("libvfsms error %d: %s" % (rc, buf.value.decode(errors="replace")), code=int(rc))
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -1672,7 +1676,7 @@ def tiff_jpeg_tables(ch, quality=95):
     n = C.c_size_t()
     rc = lib.vfsms_tiff_jpeg_tables(int(ch), int(quality), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
     if rc != VFSMS_OK:
-        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)), code=int(rc))
     return out[:n.value].tobytes()
 
 
@@ -1684,7 +1688,7 @@ def jpeg_header(rows, cols, ch, quality=95, restart_mcus=0):
     n = C.c_size_t()
     rc = lib.vfsms_jpeg_header(int(rows), int(cols), int(ch), int(quality), int(restart_mcus), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
     if rc != VFSMS_OK:
-        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)), code=int(rc))
     return out[:n.value].tobytes()
 
 
@@ -1813,7 +1817,7 @@ def jpeg_encode(img, bgr=True, quality=95):
         if rc == VFSMS_ERR_UNSUPPORTED:
             return None
         if rc != VFSMS_ERR_CAPACITY:
-            raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+            raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)), code=int(rc))
         cap = n.value
     raise VfsmsError("jpeg_encode: the stream did not fit the size the library asked for")
 
@@ -1831,7 +1835,7 @@ def jpeg_join(parts, stripe_rows, total_rows):
         out = np.empty(need.value, np.uint8)
         rc = lib.vfsms_jpeg_join(ptrs, sizes, n, int(stripe_rows), int(total_rows), out.ctypes.data_as(C.c_void_p), out.size, C.byref(need))
     if rc != VFSMS_OK:
-        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)), code=int(rc))
     return out
 
 
@@ -1867,7 +1871,7 @@ def _call_with_evaluator(attempts, call):
     if err:
         raise err[0]
     if rc != VFSMS_OK:
-        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)))
+        raise VfsmsError("libvfsms error %d: %s" % (rc, _last_error(lib)), code=int(rc))
 
 
 def pairs_offsets_blind_eval(attempts, shapes, params, first, last, per):

@@ -757,7 +757,7 @@ void k_nms(const RoiDev *rois, const LayerPat *pats, int layers_per_octave, int 
         if (!interpolate_keypoint(N9, ss, ss, ds, cd)) continue;
         const int slot = atomicAdd(&cn, 1);
         if (slot < NMS_LOCAL) local[slot] = cd;
-        else {                                           // local list full (never seen on real images): direct append
+        else {                                           // local list full (dense lattices reach this; see docs/history.md): direct append
             const int pos = atomicAdd(&R.counters[0], 1);
             if (pos < R.cap) R.cand[pos] = cd; else R.counters[2] = 1;
         }

@@ -17,7 +17,7 @@ while keeping the GPU full:
 """
 import numpy as np
 
-from ._lib import Engine, pairs_offsets_blind_eval, pairs_offsets_eval
+from ._lib import VFSMS_ERR_CAPACITY, Engine, pairs_offsets_blind_eval, pairs_offsets_eval
 from .utility import phase_resolver, roi_rect, vote_tail
 
 RESULT_INTS = 6   # status, dx, dy, direction, i, votes
@@ -139,7 +139,9 @@ class GridRegistrar:
     def _surf_batch(self, jobs):
         """Fused batch with an adaptive keypoint capacity: kernels are launched over capacity-sized grids (no host
         sync inside a batch), so the capacity follows the largest ROI seen so far (x1.5 + 1024); an overflow falls
-        back to the library default (h*w/24 + 4096) and repeats the batch."""
+        back to the library default (h*w/24 + 4096) and repeats the batch.  Only the library's VFSMS_ERR_CAPACITY is an overflow (as in
+        device_eval, csrc/grid.hip): any other error -- a HIP error from the device among them -- starts no further work and reaches
+        the caller, behind the reset of the override."""
         cap = getattr(self, "_kp_cap", 0)
         adaptive = hasattr(self.eng, "set_keypoint_capacity")
         try:
@@ -148,8 +150,8 @@ class GridRegistrar:
                 self.eng.set_keypoint_capacity(cap)
             try:
                 rows = self._surf_call(jobs)
-            except Exception:
-                if not cap:
+            except Exception as e:
+                if not (adaptive and cap) or getattr(e, "code", None) != VFSMS_ERR_CAPACITY:
                     raise
                 self.capacity_retries = getattr(self, "capacity_retries", 0) + 1      # reported by bench.py
                 self._kp_cap = 0
