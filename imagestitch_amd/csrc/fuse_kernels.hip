@@ -36,7 +36,7 @@ struct I64View {
         const long long *p = A + ((size_t)i * c + j) * ch;
         if (ch == 1) return p[0] != -1;
         long long s = 0; for (int k = 0; k < ch; k++) s += p[k];
-        return s != -3;
+        return s != -ch;                                               // empty = every channel -1 (the reference's BGR "!= -3" at ch = 3)
     }
     __device__ long long a_raw(int i, int j, int k) const { return A[((size_t)i * c + j) * ch + k]; }
     __device__ long long b_val(int i, int j, int k) const { return B[((size_t)i * c + j) * ch + k]; }

@@ -91,7 +91,7 @@ struct SeamI64 {                       // the reference's representation: int64 
     {
         if (ch == 1) return p[0] != -1;
         long long s = 0; for (int k = 0; k < ch; k++) s += p[k];
-        return s != -3;
+        return s != -ch;                   // empty = every channel -1, as I64View::a_valid
     }
     __device__ __forceinline__ bool av(int i, int j) const { return valid(A + ((size_t)i * c + j) * ch); }
     __device__ __forceinline__ bool bv(int i, int j) const { return valid(B + ((size_t)i * c + j) * ch); }

@@ -388,6 +388,8 @@ int vfsms_phase_resolve_u8(vfsms_ctx *ctx, const uint8_t *a, const uint8_t *b, i
 
 /* ImageFusion.fuseByFadeInAndFadeOut([A,B],dx,dy) (ImageFusion.py:192-244) on the reference's own
  * representation: int64 [r][c][ch] with -1 = empty (Stitcher.py:434-436).  out: uint8 [r][c][ch].
+ * ch 1..4.  A pixel is empty iff every channel is -1: the sum of its channels is -ch (the reference's BGR test "sum != -3" at ch = 3);
+ * every int64 operator below judges pixels by this rule, as the canvas path's validity plane does.
  * info (optional, 4 ints) = {mode 0 strip / 1 corner, corner index, rowIndex, colIndex}.           */
 int vfsms_fuse_fade_i64(vfsms_ctx *ctx, const int64_t *A, const int64_t *B, int r, int c, int ch,
                         int dx, int dy, uint8_t *out, int32_t *info);

@@ -893,12 +893,13 @@ void orc_phase_correlate_u8(const uint8_t *a, const uint8_t *b, int h, int w,
  * ---------------------------------------------------------------------------------------- */
 static inline int px_nonempty(const int64_t *A, int c, int ch, int i, int j)
 {
-    /* colour: imageA[i,j].sum() != -3 ; gray: imageA[i,j] != -1 */
+    /* colour: imageA[i,j].sum() != -3 ; gray: imageA[i,j] != -1.  The reference is BGR only; for any other channel count the rule
+     * keeps its meaning at 3, "not every channel is -1" (values are -1 or 0..255): sum != -ch */
     const int64_t *p = A + ((size_t)i * c + j) * ch;
     if (ch == 1) return p[0] != -1;
     int64_t s = 0;
     for (int k = 0; k < ch; k++) s += p[k];
-    return s != -3;
+    return s != -ch;
 }
 static inline int pywrap(int i, int n) { return i < 0 ? i + n : i; }
 

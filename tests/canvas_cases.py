@@ -96,9 +96,9 @@ def random_cases(colour):
 
 
 # ---- edge canvases -------------------------------------------------------------------------------------------------------------------------------
-def _pixels(rng, th, tw, colour):
-    """mid greys with 5 % black and 5 % saturated elements"""
-    shape = (th, tw, 3) if colour else (th, tw)
+def _pixels(rng, th, tw, colour, ch=None):
+    """mid greys with 5 % black and 5 % saturated elements; ch: that many channels instead of colour's 1 or 3"""
+    shape = (th, tw, ch) if ch is not None else (th, tw, 3) if colour else (th, tw)
     t = rng.integers(1, 255, shape, dtype=np.uint8)
     u = rng.random(shape)
     t[u < 0.05] = 0
@@ -107,15 +107,16 @@ def _pixels(rng, th, tw, colour):
     return t
 
 
-def _case(name, rects, rois, dxdy, colour, origin=(0, 0), pad=(0, 0)):
+def _case(name, rects, rois, dxdy, colour, origin=(0, 0), pad=(0, 0), ch=None):
     """rects: (y0, x0, h, w) per tile in any coordinates (shifted so that the smallest becomes `origin`); rois[k] for tile k >= 1: (ry0, rx0,
     ry1, rx1) in the same coordinates, or None for Stitcher.py:446-457's cut by the bounding box of the earlier tiles.  pad: empty canvas rows /
-    columns behind the last tile."""
-    rng = np.random.default_rng([len(rects), int(colour)] + [int(v) & 0xffff for r in rects for v in r])
+    columns behind the last tile.  ch (tests/channel_cases.py): tiles of that many channels from a stream of their own; None leaves every draw
+    of the gray and colour cases as it was."""
+    rng = np.random.default_rng([len(rects), int(colour) if ch is None else 16 + ch] + [int(v) & 0xffff for r in rects for v in r])
     sy = origin[0] - min(r[0] for r in rects); sx = origin[1] - min(r[1] for r in rects)
     tiles, geom, bbox = [], [], None
     for k, (y0, x0, h, w) in enumerate(rects):
-        tiles.append(_pixels(rng, h, w, colour))
+        tiles.append(_pixels(rng, h, w, colour, ch))
         if k == 0:
             geom.append((y0 + sy, x0 + sx, 0, 0, 0, 0, 0, 0, PASTE))
             bbox = [y0, x0, y0 + h, x0 + w]
@@ -135,17 +136,17 @@ def _case(name, rects, rois, dxdy, colour, origin=(0, 0), pad=(0, 0)):
 _SIGNS = ((7, -3), (-5, 9), (0, 0), (4, 4), (-6, -2))
 
 
-def _strip(name, r, c, colour, k, margins=None, origin=None):
+def _strip(name, r, c, colour, k, margins=None, origin=None, ch=None):
     """two tiles, the ROI (r x c, margins (top, left, bottom, right) inside the second tile) fully covered by the first"""
     mt, ml, mb, mr = margins if margins is not None else (k % 3, 1 + k % 4, (k + 1) % 3, (k + 2) % 4)
     oy, ox = origin if origin is not None else (k % 2, 1 + k % 3)            # second tile's x0 = 5 + ox: 6, 7 or 8 (x0 % 4 of 2, 3, 0)
     second = (3, 5, mt + r + mb, ml + c + mr)
     roi = (3 + mt, 5 + ml, 3 + mt + r, 5 + ml + c)
     first = (0, 0, roi[2], roi[3])
-    return _case(name, [first, second], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=(oy, ox), pad=(k % 2, k % 3))
+    return _case(name, [first, second], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=(oy, ox), pad=(k % 2, k % 3), ch=ch)
 
 
-def _corner(name, r, c, part, colour, k, bars=True, margins=(1, 2, 2, 1), origin=(1, 3)):
+def _corner(name, r, c, part, colour, k, bars=True, margins=(1, 2, 2, 1), origin=(1, 3), ch=None):
     """the last tile's ROI (r x c) with only its `part` (tl, tr, bl, br) valid.  bars: three tiles -- a horizontal bar over the top / bottom
     35 % of the rows and a vertical bar over the left / right 35 % of the columns, both running out of the ROI (the L a mosaic's turn leaves:
     58 % valid); else two tiles, the first covering 75 % x 75 % of the ROI from that corner (56 %)."""
@@ -157,10 +158,10 @@ def _corner(name, r, c, part, colour, k, bars=True, margins=(1, 2, 2, 1), origin
         a, b = max(1, (35 * r) // 100), max(1, (35 * c) // 100)
         hbar = (roi[0] - 9, roi[1] - 7, a + 9, c + 14) if top else (roi[2] - a, roi[1] - 7, a + 9, c + 14)
         vbar = (roi[0] - 9, roi[1] - 7, r + 18, b + 7) if left else (roi[0] - 9, roi[3] - b, r + 18, b + 7)
-        return _case(name, [hbar, vbar, tile], [None, None, roi], [_SIGNS[k % len(_SIGNS)], _SIGNS[(k + 1) % len(_SIGNS)]], colour, origin=origin)
+        return _case(name, [hbar, vbar, tile], [None, None, roi], [_SIGNS[k % len(_SIGNS)], _SIGNS[(k + 1) % len(_SIGNS)]], colour, origin=origin, ch=ch)
     a, b = max(1, (3 * r) // 4), max(1, (3 * c) // 4)
     first = (roi[0] - 5 if top else roi[2] - a, roi[1] - 6 if left else roi[3] - b, a + 5, b + 6)
-    return _case(name, [first, tile], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=origin)
+    return _case(name, [first, tile], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=origin, ch=ch)
 
 
 @functools.lru_cache(maxsize=None)
@@ -212,13 +213,13 @@ def edge_verdict_only(colour=False):
     return tuple(_thin(r, c, part, colour, k) for k, (r, c, part) in enumerate(_THIN) if (r, c, part) in _THIN_RAISES)
 
 
-def _thin(r, c, part, colour, k):
+def _thin(r, c, part, colour, k, ch=None):
     """a corner ROI, most of one or two rows or columns: the first tile covers its left / right / top / bottom half, or (none) lies beside it"""
     tile = (0, 0, r + 2, c + 3)
     roi = (1, 2, 1 + r, 2 + c)
     first = {"l": (-4, -5, r + 9, 7 + c // 2), "r": (-4, 2 + c - c // 2, r + 9, c // 2 + 6), "t": (-4, -5, 5 + r // 2, c + 11),
              "b": (1 + r - r // 2, -5, r // 2 + 6, c + 11), "none": (-4, -9, r + 9, 7)}[part]
-    return _case("thin %s %dx%d" % (part, r, c), [first, tile], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=(k % 2, 1 + k % 4))
+    return _case("thin %s %dx%d" % (part, r, c), [first, tile], [None, roi], [_SIGNS[k % len(_SIGNS)]], colour, origin=(k % 2, 1 + k % 4), ch=ch)
 
 
 _THIN = ((1, 5, "l"), (1, 5, "r"), (1, 257, "l"), (1, 257, "r"), (1, 1029, "r"), (1, 513, "none"), (33, 1, "t"), (33, 1, "b"), (65, 1, "none"),

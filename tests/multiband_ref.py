@@ -1,5 +1,6 @@
 """multiBandBlending as specified for this project: a Laplacian-pyramid blend of two int64 regions (-1 = empty) with a hard seam
-where the fadeInAndFadeOut weights are equal.  Plain numpy float32, every expression in the order the HIP kernels
+where the fadeInAndFadeOut weights are equal.  A pixel of ch channels is empty iff every channel is -1, i.e. the sum of its channels is
+-ch (what corner_ramps scans for; seam_ref.pixel_valid).  Plain numpy float32, every expression in the order the HIP kernels
 (imagestitch_amd/csrc/multiband_kernels.hip) evaluate it, so their bytes must equal these bit for bit.
 
 These formulas ARE the specification; they are not claimed to match cv2.pyrDown / cv2.pyrUp or the reference's

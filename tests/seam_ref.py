@@ -7,8 +7,9 @@ ImageFusion.fuseByOptimalSeamLine (ImageFusion.py:377-492), which cannot be run 
 
 Inputs: int64 regions A, B of shape r x c or r x c x ch, -1 = empty; the pair's offset (dx, dy).
 
-Validity (per pixel, as the fade's kernels count it): a gray pixel is valid where it is not -1, a colour pixel where the sum of its
-channels is not -3.  B's validity is judged by the same rule.
+Validity (per pixel, as the fade's kernels count it): a gray pixel is valid where it is not -1, a pixel of ch >= 2 channels where the sum
+of its channels is not -ch, i.e. where not every channel is -1 (the reference's BGR rule "sum != -3" at ch = 3).  B's validity is judged by
+the same rule.
 
 Fill (per element, multiband_ref.fill): A' = A where A >= 0 else B;  B' = B where B >= 0 else A';  empty in both -> 0.
 
@@ -61,7 +62,7 @@ def pixel_valid(X):
         return X != -1
     if X.shape[2] == 1:
         return X[:, :, 0] != -1
-    return X.sum(axis=2) != -3
+    return X.sum(axis=2) != -X.shape[2]
 
 
 def energy(A, B):
