@@ -984,34 +984,49 @@ __global__ __launch_bounds__(256) void k_bucket_rank(const RoiDev *rois, const L
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K4 orientation (SURFInvoker, upright == 0): 128 threads per keypoint
+// K4 orientation (SURFInvoker, upright == 0): one wave per keypoint
 // ---------------------------------------------------------------------------------------------------
+// The reference divides the smaller of |x|, |y| by the larger in either of its two branches: selecting the operands first leaves ONE
+// division and ONE polynomial on the same operands in the same order -- the same result, and no divergent pair of division sequences.
 __device__ __forceinline__ float fast_atan2_deg(float y, float x)   // core atan_f32 polynomial, degrees
 {
     const float s = (float)(180 / 3.1415926535897932384626433832795);
     const float p1 = 0.9997878412794807f * s, p3 = -0.3258083974640975f * s;
     const float p5 = 0.1555786518463281f * s, p7 = -0.04432655554792128f * s;
-    float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + (float)DBL_EPSILON);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + (float)DBL_EPSILON);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool xge = ax >= ay;
+    const float num = xge ? ay : ax, den = (xge ? ax : ay) + (float)DBL_EPSILON;
+    const float c = num / den;
+    const float c2 = c * c;
+    float a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    a = xge ? a : 90.f - a;
     if (x < 0) a = 180.f - a;
     if (y < 0) a = 360.f - a;
     return a;
 }
 
-// K4 dominant orientation, ORI_KP keypoints per workgroup of 128 lanes each (eight per 1024 threads until round 6, now two).  The three phases have different widths -- 113 gradient
-// samples, 72 sliding windows, one argmax per keypoint -- and a workgroup per keypoint left most lanes of its second wave idle in the
-// window phase (72 windows = one wave + 8 lanes) and one lane walking the 72 moduli.  Here phase 1 gives every keypoint 128 lanes
-// (sample = lane), phase 2 packs the 8 x 72 windows into nine full waves, phase 3 reduces each keypoint's 72 moduli in one wave
-// (first maximum in window order, as the reference's strict `>` scan keeps it).  The sums visit the samples in index order.
+__device__ __forceinline__ void wave_sync_lds()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// K4 dominant orientation: ONE WAVE PER KEYPOINT, ORI_K keypoints (= waves) per workgroup.  The three phases have different widths --
+// 113 gradient samples, 72 sliding windows, one argmax per keypoint.  Until this form a keypoint held 128 lanes (two wave slots) through
+// all three, so a CU at its 32 waves held 16 keypoints, and the kernel is bound by how many keypoints a CU holds against the latency of
+// one keypoint's chain (record -> 8 scattered integral taps -> divisions, atan2 -> oriMask row -> LDS -> 113 dependent packed fmas ->
+// argmax), not by issue.  Now:
+//   phase 1  the keypoint's wave takes its samples in two rounds (sample = 64 * round + lane: 64 + 49 working lanes) and writes the XY / Zb
+//            slots 0 .. 127 as before; the count of valid samples is two ballots, wave-uniform, in no LDS cell;
+//   phase 2  lane = window for windows 0 .. 63, in the keypoint's own wave, behind a wave-level fence (no workgroup barrier: one wave wrote
+//            and reads).  The leftover windows 64 .. 71 of ALL keypoints of the workgroup are packed into one pass of wave 0, eight lanes per
+//            keypoint -- the only part that reads another wave's samples, hence the only workgroup barriers (one before, one after);
+//   phase 3  the 64 moduli are still in the wave's registers: lanes 0 .. 7 fold in the leftover moduli from LDS, a butterfly finds the first
+//            maximum in window order (as the reference's strict `>` scan keeps it), and the winner's sums come by one shuffle (or, for a
+//            leftover window, from LDS).
+// The sums visit the samples in index order.  Wave-passes per keypoint: phase 1 two (as before), phase 2 1 + 1 / ORI_K (1.5 before).
+// The rows of XY and Zb are padded so that the packed pass, whose lanes read ORI_K different keypoints, and the nine byte rows of one
+// keypoint fall on different LDS banks.
 //
 // Round 6.  Phase 1: the two gradient wavelets of resizeHaarPattern (dx_s = {{0,0,2,4,-1},{2,0,4,4,1}}, dy_s = {{0,0,4,2,1},{0,2,4,4,-1}})
 // share a 3 x 3 corner lattice (x, y in {0, r2, r4}): eight distinct integral taps, and their four weights are +-1 / (r2 * r4) and
@@ -1021,121 +1036,169 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)   // core atan
 // with one shift and one mask, and each byte becomes the float 0 / 1 by v_cvt_f32_ubyteN; the masked accumulation of (x, y) is one packed
 // fma per sample -- fma(v, 1, s) = s + v and fma(v, 0, s) = s exactly (s is never -0: it starts at +0 and x + (-x) rounds to +0) -- 2.5
 // instructions per (sample, window) instead of 6.
-#ifndef ORI_KP
-#define ORI_KP 2                // keypoints per workgroup (128 lanes each): 8 -> 0.571, 4 -> 0.539, 2 -> 0.534, 1 -> 0.547 ms on the 16-pair batch
+#ifndef ORI_K
+#define ORI_K 4                 // keypoints = waves per workgroup: 2 -> 0.402, 4 -> 0.375 / 0.373, 8 -> 0.378 ms on the 16-pair batch (parent form 0.533 / 0.531;
+                                // the two rounds as branchy passes one after the other, at 4: 0.405; profiles/orientation_waves_microbench.txt)
 #endif
+#define ORI_XY_ROW 130          // float2 slots of a keypoint: 128 and one 16-byte step, so keypoint q's quad reads start 4 q banks on
+#define ORI_Z_ROW 136           // bytes of a membership row: 128 and two dwords, so rows g and g + 1 (and keypoints) start on other banks
 typedef float ori_f2 __attribute__((ext_vector_type(2)));
+
+// A keypoint's wave takes its samples in two rounds, and one round's chain -- table entry -> eight scattered integral taps -> oriMask row
+// -> LDS -- is two dependent trips to memory.  So a round is written in two halves WITHOUT a branch, and the wave issues the taps of both
+// rounds before it uses either: a sample outside the image (or past nOriSamples) reads the first cell of the integral eight times and
+// its results are replaced by zeros; a sample inside goes through exactly the operations it went through before.
+struct OriTaps { int a00, a02, a04, a20, a24, a40, a42, a44; };       // a<row><column> of the 3 x 3 corner lattice (x, y in {0, r2, r4})
+
+// The taps of sample t of a keypoint (wave-uniform x, y, scale s, wavelet size gws = r4, r2 = gws / 2); returns whether the sample is inside.
+__device__ __forceinline__ bool ori_taps(const RoiDev &R, const SurfTables *T, int nori, float kx, float ky, float s, int gws, int r2, int r4, int t, OriTaps &a)
+{
+    const int srows = R.h + 1, scols = R.w + 1, sw = R.w + 1;
+    const int tc = max(min(t, nori - 1), 0);
+    const int x = cv_round_f(kx + T->aptx[tc] * s - (float)(gws - 1) / 2);
+    const int y = cv_round_f(ky + T->apty[tc] * s - (float)(gws - 1) / 2);
+    const bool in = t < nori && !(y < 0 || y >= srows - gws || x < 0 || x >= scols - gws);
+    // resizeHaarPattern for the 4-unit gradient wavelets + calcHaarPattern (2 boxes each)
+    const int e2 = in ? r2 : 0, e4 = in ? r4 : 0;
+    g_ci32 p0 = (g_ci32)R.sum + (in ? (size_t)y * sw + x : (size_t)0);
+    g_ci32 p2 = p0 + (size_t)e2 * sw, p4 = p0 + (size_t)e4 * sw;
+    a.a00 = p0[0]; a.a02 = p0[e2]; a.a04 = p0[e4];
+    a.a20 = p2[0]; a.a24 = p2[e4];
+    a.a40 = p4[0]; a.a42 = p4[e2]; a.a44 = p4[e4];
+    return in;
+}
+
+struct OriSample { float xx, yy; uint32_t m0, m1, m2; };             // weighted gradient and the 72 window-membership bits of its direction
+
+// From the taps to the sample.  wA, wB: the reciprocal box areas of the two wavelet halves.
+__device__ __forceinline__ OriSample ori_gradient(const SurfTables *T, int nori, const OriTaps &a, float wA, float wB, int t)
+{
+    const int vx0 = a.a00 + a.a42 - a.a40 - a.a02, vx1 = a.a02 + a.a44 - a.a42 - a.a04;     // dx: {0,0,r2,r4} weight -wA, {r2,0,r4,r4} weight +wB
+    const int vy0 = a.a00 + a.a24 - a.a20 - a.a04, vy1 = a.a20 + a.a44 - a.a40 - a.a24;     // dy: {0,0,r4,r2} weight +wA, {0,r2,r4,r4} weight -wB
+    double dxd = 0; dxd += (double)(-((float)vx0 * wA)); dxd += (double)((float)vx1 * wB);
+    double dyd = 0; dyd += (double)((float)vy0 * wA); dyd += (double)(-((float)vy1 * wB));
+    const float vx = (float)dxd, vy = (float)dyd;
+    const float aw = T->aptw[max(min(t, nori - 1), 0)];
+    const float xx = vx * aw, yy = vy * aw;
+    const int ang = cv_round_f(fast_atan2_deg(yy, xx));     // cv::phase(X, Y, angle, true) then cvRound
+    const uint32_t *mrow = T->oriMask[min(max(ang, 0), 360)];
+    OriSample o;
+    o.xx = xx; o.yy = yy; o.m0 = mrow[0]; o.m1 = mrow[1]; o.m2 = mrow[2];
+    return o;
+}
+
+// Slot t of the keypoint's XY and Zb rows: the sample if it is inside, zeros if not.
+__device__ __forceinline__ void ori_store(bool in, const OriSample &o, int t, float2 *xyq, uint8_t *zq)
+{
+    const uint32_t m0 = in ? o.m0 : 0u, m1 = in ? o.m1 : 0u, m2 = in ? o.m2 : 0u;
+    xyq[t] = make_float2(in ? o.xx : 0.f, in ? o.yy : 0.f);
+    zq[0 * ORI_Z_ROW + t] = (uint8_t)m0; zq[1 * ORI_Z_ROW + t] = (uint8_t)(m0 >> 8); zq[2 * ORI_Z_ROW + t] = (uint8_t)(m0 >> 16); zq[3 * ORI_Z_ROW + t] = (uint8_t)(m0 >> 24);
+    zq[4 * ORI_Z_ROW + t] = (uint8_t)m1; zq[5 * ORI_Z_ROW + t] = (uint8_t)(m1 >> 8); zq[6 * ORI_Z_ROW + t] = (uint8_t)(m1 >> 16); zq[7 * ORI_Z_ROW + t] = (uint8_t)(m1 >> 24);
+    zq[8 * ORI_Z_ROW + t] = (uint8_t)m2;
+}
+
+// The sums of window w over a keypoint's samples, in index order.
+__device__ __forceinline__ ori_f2 ori_window_sum(const float2 *xyq, const uint8_t *zq, int w, int nori)
+{
+    const uint8_t *zrow = zq + (w >> 3) * ORI_Z_ROW;
+    const int bit = w & 7;
+    ori_f2 acc = {0.f, 0.f};
+    for (int j = 0; j < nori; j += 8) {                     // nori <= 113: the groups of eight cover 120 samples, the slots past nori are zero
+        const uint2 z8 = *reinterpret_cast<const uint2 *>(&zrow[j]);
+        const uint32_t za = (z8.x >> bit) & 0x01010101u, zb = (z8.y >> bit) & 0x01010101u;
+        const float4 p01 = *reinterpret_cast<const float4 *>(&xyq[j]), p23 = *reinterpret_cast<const float4 *>(&xyq[j + 2]);
+        const float4 p45 = *reinterpret_cast<const float4 *>(&xyq[j + 4]), p67 = *reinterpret_cast<const float4 *>(&xyq[j + 6]);
+#define ORI_ACC(Z, N, P, XC, YC) do { float mf; asm("v_cvt_f32_ubyte" #N " %0, %1" : "=v"(mf) : "v"(Z)); \
+                                   acc = __builtin_elementwise_fma((ori_f2){P.XC, P.YC}, (ori_f2){mf, mf}, acc); } while (0)
+        ORI_ACC(za, 0, p01, x, y); ORI_ACC(za, 1, p01, z, w); ORI_ACC(za, 2, p23, x, y); ORI_ACC(za, 3, p23, z, w);
+        ORI_ACC(zb, 0, p45, x, y); ORI_ACC(zb, 1, p45, z, w); ORI_ACC(zb, 2, p67, x, y); ORI_ACC(zb, 3, p67, z, w);
+#undef ORI_ACC
+    }
+    return acc;
+}
+
 __device__ __forceinline__ void orientation_block(const RoiDev &R, const SurfTables *T, const int k0, const int n, int upright)
 {
-    __shared__ __attribute__((aligned(16))) float2 XY[ORI_KP][128];      // weighted gradient (x, y) of every sample, interleaved: phase 2 reads pairs
-    __shared__ __attribute__((aligned(16))) uint8_t Zb[ORI_KP][9][128];   // byte g of the window membership of every sample (SurfTables::oriMask rows)
-    __shared__ float mod_s[ORI_KP][72], sx_s[ORI_KP][72], sy_s[ORI_KP][72];
-    __shared__ int nvalid[ORI_KP], state[ORI_KP];              // state: 0 compute, 1 done (deleted / upright / beyond n)
-    const int tid = threadIdx.x;
-    const int kq = __builtin_amdgcn_readfirstlane(tid >> 7), t = tid & 127;      // keypoint slot: wave-uniform, kept scalar
-    if (tid < ORI_KP) { nvalid[tid] = 0; state[tid] = 0; }
-    __syncthreads();
-    {
-        const int k = k0 + kq;
-        int valid = 0;
-        uint32_t m0 = 0, m1 = 0, m2 = 0;
-        float2 xy = make_float2(0.f, 0.f);
-        if (k < n) {
-            const vfsms_keypoint kp = R.kps[k];
-            const float s = kp.size * 1.2f / 9.0f;
-            const int gws = 2 * cv_round_f(2 * s);
-            const int srows = R.h + 1, scols = R.w + 1, sw = R.w + 1;
-            if (srows < gws || scols < gws) {                  // gradient wavelet larger than the image: delete
-                if (t == 0) { R.kps[k].size = -1.f; state[kq] = 1; }
-            } else if (upright) {
-                if (t == 0) { R.kps[k].angle = 270.f; state[kq] = 1; }
-            } else if (t < T->nOriSamples) {
-                int x = cv_round_f(kp.x + T->aptx[t] * s - (float)(gws - 1) / 2);
-                int y = cv_round_f(kp.y + T->apty[t] * s - (float)(gws - 1) / 2);
-                if (!(y < 0 || y >= srows - gws || x < 0 || x >= scols - gws)) {
-                    // resizeHaarPattern for the 4-unit gradient wavelets + calcHaarPattern (2 boxes each)
-                    const float ratio = (float)gws / 4;
-                    const int r2 = cv_round_f(ratio * 2), r4 = cv_round_f(ratio * 4);
-                    g_ci32 p0 = (g_ci32)R.sum + (size_t)y * sw + x;
-                    g_ci32 p2 = p0 + (size_t)r2 * sw, p4 = p0 + (size_t)r4 * sw;
-                    const int a00 = p0[0], a02 = p0[r2], a04 = p0[r4];          // a<row><column> of the corner lattice
-                    const int a20 = p2[0], a24 = p2[r4];
-                    const int a40 = p4[0], a42 = p4[r2], a44 = p4[r4];
-                    // gws is even, so r2 = gws / 2 and r4 = gws exactly and r4 - r2 = r2: the two boxes of a wavelet have ONE area -- one
-                    // division.  (A host-built table of the reciprocals measured 1.4 % SLOWER than the division: profiles/r06_ab_detect_stage.txt.)
-                    const float wA = 1.f / ((float)r2 * (float)r4);
-                    float wB = wA;
-                    if (r4 - r2 != r2) wB = 1.f / ((float)(r4 - r2) * (float)r4);
-                    const int vx0 = a00 + a42 - a40 - a02, vx1 = a02 + a44 - a42 - a04;     // dx: {0,0,r2,r4} weight -wA, {r2,0,r4,r4} weight +wB
-                    const int vy0 = a00 + a24 - a20 - a04, vy1 = a20 + a44 - a40 - a24;     // dy: {0,0,r4,r2} weight +wA, {0,r2,r4,r4} weight -wB
-                    double dxd = 0; dxd += (double)(-((float)vx0 * wA)); dxd += (double)((float)vx1 * wB);
-                    double dyd = 0; dyd += (double)((float)vy0 * wA); dyd += (double)(-((float)vy1 * wB));
-                    const float vx = (float)dxd, vy = (float)dyd;
-                    const float aw = T->aptw[t];
-                    const float xx = vx * aw, yy = vy * aw;
-                    xy = make_float2(xx, yy);
-                    const int ang = cv_round_f(fast_atan2_deg(yy, xx));     // cv::phase(X, Y, angle, true) then cvRound
-                    const uint32_t *mrow = T->oriMask[min(max(ang, 0), 360)];
-                    m0 = mrow[0]; m1 = mrow[1]; m2 = mrow[2];
-                    valid = 1;
-                }
+    __shared__ __attribute__((aligned(16))) float2 XY[ORI_K][ORI_XY_ROW];        // weighted gradient (x, y) of every sample, interleaved: phase 2 reads pairs
+    __shared__ __attribute__((aligned(16))) uint8_t Zb[ORI_K][9 * ORI_Z_ROW];    // row g: byte g of the window membership of every sample (SurfTables::oriMask rows)
+    __shared__ float mod_l[ORI_K][8], sx_l[ORI_K][8], sy_l[ORI_K][8];            // the leftover windows 64 .. 71
+    __shared__ int live[ORI_K];                                                  // the keypoint has window sums to form
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int q = __builtin_amdgcn_readfirstlane(tid >> 6);                      // keypoint slot = wave
+    const int k = k0 + q;
+    int compute = 0, nvalid = 0;                                                 // wave-uniform
+    const int nori = T->nOriSamples;
+    if (k < n) {
+        // the record is the same for the whole wave and was written by an earlier launch: through the scalar unit.  The scalar cache is
+        // not coherent with vector stores INSIDE a launch; this read is right only because the launch boundary invalidates that cache
+        // and a wave stores to its own record (angle, size) after it has read it.  Fused with the kernel that writes the records, or run
+        // twice inside one launch, a stale 64-byte line (shared with the neighbouring records) would be read: use vector loads then.
+        typedef const float __attribute__((address_space(4))) *ori_cf32;
+        const float kx = *(ori_cf32)(uintptr_t)&R.kps[k].x, ky = *(ori_cf32)(uintptr_t)&R.kps[k].y;
+        const float ksize = *(ori_cf32)(uintptr_t)&R.kps[k].size;
+        const float s = ksize * 1.2f / 9.0f;
+        const int gws = 2 * cv_round_f(2 * s);
+        if (R.h + 1 < gws || R.w + 1 < gws) {                  // gradient wavelet larger than the image: delete
+            if (lane == 0) R.kps[k].size = -1.f;
+        } else if (upright) {
+            if (lane == 0) R.kps[k].angle = 270.f;
+        } else {
+            compute = 1;
+            const float ratio = (float)gws / 4;
+            const int r2 = cv_round_f(ratio * 2), r4 = cv_round_f(ratio * 4);
+            // gws is even, so r2 = gws / 2 and r4 = gws exactly and r4 - r2 = r2: the two boxes of a wavelet have ONE area -- one
+            // division.  (A host-built table of the reciprocals measured 1.4 % SLOWER than the division: profiles/r06_ab_detect_stage.txt.)
+            const float wA = 1.f / ((float)r2 * (float)r4);
+            float wB = wA;
+            if (r4 - r2 != r2) wB = 1.f / ((float)(r4 - r2) * (float)r4);
+            OriTaps a0, a1;
+            const bool in0 = ori_taps(R, T, nori, kx, ky, s, gws, r2, r4, lane, a0);
+            const bool in1 = ori_taps(R, T, nori, kx, ky, s, gws, r2, r4, 64 + lane, a1);
+            nvalid = __popcll(__ballot(in0)) + __popcll(__ballot(in1));
+            if (nvalid > 0) {
+                const OriSample o0 = ori_gradient(T, nori, a0, wA, wB, lane), o1 = ori_gradient(T, nori, a1, wA, wB, 64 + lane);
+                ori_store(in0, o0, lane, XY[q], Zb[q]);
+                ori_store(in1, o1, 64 + lane, XY[q], Zb[q]);
             }
-        } else if (t == 0) state[kq] = 1;
-        // a sample outside the image (or past nOriSamples) belongs to no window and carries a zero gradient
-        XY[kq][t] = xy;
-        Zb[kq][0][t] = (uint8_t)m0; Zb[kq][1][t] = (uint8_t)(m0 >> 8); Zb[kq][2][t] = (uint8_t)(m0 >> 16); Zb[kq][3][t] = (uint8_t)(m0 >> 24);
-        Zb[kq][4][t] = (uint8_t)m1; Zb[kq][5][t] = (uint8_t)(m1 >> 8); Zb[kq][6][t] = (uint8_t)(m1 >> 16); Zb[kq][7][t] = (uint8_t)(m1 >> 24);
-        Zb[kq][8][t] = (uint8_t)m2;
-        const unsigned long long m = __ballot(valid);
-        if ((tid & 63) == 0 && m) atomicAdd(&nvalid[kq], __popcll(m));
+        }
     }
-    __syncthreads();
-    if (tid < ORI_KP * 72) {
-        const int q = tid / 72, w = tid - q * 72;
-        if (state[q] == 0 && nvalid[q] > 0) {
-            const int nori = T->nOriSamples;                  // <= 113: the groups of eight below cover 120 samples, the slots past nori are zero
-            const uint8_t *zrow = Zb[q][w >> 3];
-            const int bit = w & 7;
-            ori_f2 acc = {0.f, 0.f};
-            for (int j = 0; j < nori; j += 8) {
-                const uint2 z8 = *reinterpret_cast<const uint2 *>(&zrow[j]);
-                const uint32_t za = (z8.x >> bit) & 0x01010101u, zb = (z8.y >> bit) & 0x01010101u;
-                const float4 p01 = *reinterpret_cast<const float4 *>(&XY[q][j]), p23 = *reinterpret_cast<const float4 *>(&XY[q][j + 2]);
-                const float4 p45 = *reinterpret_cast<const float4 *>(&XY[q][j + 4]), p67 = *reinterpret_cast<const float4 *>(&XY[q][j + 6]);
-#define ORI_ACC(Z, N, P, XC, YC) do { float mf; asm("v_cvt_f32_ubyte" #N " %0, %1" : "=v"(mf) : "v"(Z)); \
-                                           acc = __builtin_elementwise_fma((ori_f2){P.XC, P.YC}, (ori_f2){mf, mf}, acc); } while (0)
-                ORI_ACC(za, 0, p01, x, y); ORI_ACC(za, 1, p01, z, w); ORI_ACC(za, 2, p23, x, y); ORI_ACC(za, 3, p23, z, w);
-                ORI_ACC(zb, 0, p45, x, y); ORI_ACC(zb, 1, p45, z, w); ORI_ACC(zb, 2, p67, x, y); ORI_ACC(zb, 3, p67, z, w);
-#undef ORI_ACC
-            }
-            const float sumx = acc.x, sumy = acc.y;
-            mod_s[q][w] = sumx * sumx + sumy * sumy;
-            sx_s[q][w] = sumx; sy_s[q][w] = sumy;
+    const int sums = compute && nvalid > 0;
+    if (lane == 0) live[q] = sums;
+    ori_f2 own = {0.f, 0.f};
+    if (sums) {
+        wave_sync_lds();                                       // this wave's samples, read by this wave
+        own = ori_window_sum(XY[q], Zb[q], lane, nori);
+    }
+    __syncthreads();                                           // every keypoint's samples are in LDS
+    if (q == 0 && lane < ORI_K * 8) {
+        const int lq = lane >> 3, lw = lane & 7;
+        if (live[lq]) {
+            const ori_f2 acc = ori_window_sum(XY[lq], Zb[lq], 64 + lw, nori);
+            mod_l[lq][lw] = acc.x * acc.x + acc.y * acc.y;
+            sx_l[lq][lw] = acc.x; sy_l[lq][lw] = acc.y;
         }
     }
     __syncthreads();
-    {
-        const int q = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-        if (q < ORI_KP && state[q] == 0) {
-            const int k = k0 + q;
-            if (nvalid[q] == 0) {
-                if (lane == 0) R.kps[k].size = -1.f;
-            } else {
-                // the reference keeps the FIRST window whose modulus exceeds every earlier one, starting from 0: a modulus that is
-                // not > 0 (zero or NaN) never wins; ties go to the lower window index
-                float bm = mod_s[q][lane]; int bi = lane;
-                if (!(bm > 0.f)) bm = 0.f;
-                if (lane < 8) { float m2 = mod_s[q][64 + lane]; if (m2 > bm) { bm = m2; bi = 64 + lane; } }
+    if (compute) {
+        if (nvalid == 0) {
+            if (lane == 0) R.kps[k].size = -1.f;
+        } else {
+            // the reference keeps the FIRST window whose modulus exceeds every earlier one, starting from 0: a modulus that is
+            // not > 0 (zero or NaN) never wins; ties go to the lower window index
+            float bm = own.x * own.x + own.y * own.y; int bi = lane;
+            if (!(bm > 0.f)) bm = 0.f;
+            if (lane < 8) { float m2 = mod_l[q][lane]; if (m2 > bm) { bm = m2; bi = 64 + lane; } }
 #pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) {
-                    const float om = __shfl_xor(bm, off, 64); const int oi = __shfl_xor(bi, off, 64);
-                    if (om > bm || (om == bm && oi < bi)) { bm = om; bi = oi; }
-                }
-                if (lane == 0) {
-                    float bestx = 0, besty = 0;
-                    if (bm > 0.f) { bestx = sx_s[q][bi]; besty = sy_s[q][bi]; }
-                    R.kps[k].angle = fast_atan2_deg(-besty, bestx);
-                }
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float om = __shfl_xor(bm, off, 64); const int oi = __shfl_xor(bi, off, 64);
+                const bool take = (om > bm) | ((om == bm) & (oi < bi));      // no short circuit: two selects, not two branches
+                bm = take ? om : bm; bi = take ? oi : bi;
+            }
+            const float ownx = __shfl(own.x, bi & 63, 64), owny = __shfl(own.y, bi & 63, 64);     // bi is the same in every lane by now
+            if (lane == 0) {
+                float bestx = 0, besty = 0;
+                if (bm > 0.f) { bestx = bi < 64 ? ownx : sx_l[q][bi - 64]; besty = bi < 64 ? owny : sy_l[q][bi - 64]; }
+                R.kps[k].angle = fast_atan2_deg(-besty, bestx);
             }
         }
     }
@@ -1802,11 +1865,15 @@ __global__ __launch_bounds__(256) void k_desc_recs(const RoiDev *rois, const Des
     (cls < 3 ? big : small)[plan->seg_base[roi][cls] + idx] = rec;
 }
 
-__global__ __launch_bounds__(ORI_KP * 128, 8) void k_orientation(const RoiDev *rois, const SurfTables *T, int upright)
+__global__ __launch_bounds__(ORI_K * 64, 8) void k_orientation(const RoiDev *rois, const SurfTables *T, int upright)
 {
     const RoiDev &R = rois[blockIdx.y];
-    const int n = min(R.counters[0], R.cap);
-    const int k0 = blockIdx.x * ORI_KP;
+    // The grid is sized by the capacity (no host read of the counts), so a third or more of the workgroups have nothing to do: the count
+    // comes through the scalar unit (the counters were written by earlier launches) and such a workgroup leaves on scalar loads and one
+    // scalar compare, before any vector instruction, LDS access or barrier.  (The same condition as for the record in
+    // orientation_block: valid while the counters are written by an EARLIER launch only; nothing enforces it.)
+    const int n = min(*(const int __attribute__((address_space(4))) *)(uintptr_t)R.counters, R.cap);
+    const int k0 = blockIdx.x * ORI_K;
     if (k0 >= n) return;
     orientation_block(R, T, k0, n, upright);
 }
@@ -1820,12 +1887,6 @@ __global__ __launch_bounds__(ORI_KP * 128, 8) void k_orientation(const RoiDev *r
 // ---------------------------------------------------------------------------------------------------
 #define DESC_SMALL_WIN 64
 struct SmallLds { uint8_t win[DESC_SMALL_WIN * DESC_SMALL_WIN + 64]; float sx[DESC_SMALL_WIN + 8], sy[DESC_SMALL_WIN + 8]; AreaRec rec[AREA_RECS]; int rec_win; uint8_t strip_in[DESC_SMALL_WIN / 8 + 8]; };
-
-__device__ __forceinline__ void wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ void describe_small(const RoiDev &R, const AreaRec *area_tab, const DescRec &rec, int upright, SmallLds &L)
 {
@@ -2294,7 +2355,7 @@ int launch_surf_describe(vfsms_ctx *ctx, const RoiDev *d_rois, const RoiDev *h_r
     for (int r = 0; r < nrois; r++) maxcap = h_rois[r].cap > maxcap ? h_rois[r].cap : maxcap;
     {
         ProfScope ps(ctx, "orientation");
-        hipLaunchKernelGGL(k_orientation, dim3((maxcap + ORI_KP - 1) / ORI_KP, nrois), dim3(ORI_KP * 128), 0, ctx->stream, d_rois, ctx->d_tables.as<SurfTables>(), p->upright);
+        hipLaunchKernelGGL(k_orientation, dim3((maxcap + ORI_K - 1) / ORI_K, nrois), dim3(ORI_K * 64), 0, ctx->stream, d_rois, ctx->d_tables.as<SurfTables>(), p->upright);
     }
     {
         ProfScope ps(ctx, "compact");
